@@ -16,7 +16,16 @@ Adam + bf16 shadow refresh); with N > 1 the gradient buckets are all-reduced ove
 backward and update, overlapped with the remaining backward GEMMs.
 
 Presets: --config c2 (3x128, batch 1024), c3 (default: 3x512, batch 8192 = BASELINE.json's metric), c5 (6x1024,
-batch 16384).  One JSON line on rank 0.  `f32_parity` (N = 1, c3 only): the same workload on the exact-fp32 engine
+batch 16384).  One JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps (no per-launch events inside them), writes the last timed step's
+outputs if --dump-outputs DIR is given, and prints the line; `f32_parity`, `roofline` (+ `roofline_fwd`) and
+`cpu_baseline` are then null.  --full adds them, measured as described below (the per-launch hipEvent pairs sit in
+the timed region, as they always have).  The extra ramp-up / burst steps beyond the W warm-up steps are rolled back
+before the timed region (parameters, Adam moments, step count and metric sums restored to the state after the W
+warm-up steps), so the timed steps and what --dump-outputs writes are the same from run to run for the same arguments.
+
+--full only:  `f32_parity` (N = 1, c3 only): the same workload on the exact-fp32 engine
 (the mode the rtol 1e-3 / atol 1e-5 reference replays run in), timed after the bf16 region.  `roofline`: the forward GEMM class (the 3-slot x 512 encoder GEMM), timed
 with hipEvent pairs recorded around every launch of the timed region on the launch stream
 (codae_profile_begin/_end); achieved = 2*M*N*K / mean launch time.  (dgrad and wgrad launches of a
@@ -46,6 +55,8 @@ PEAK_F32_TFLOPS = 157.3        # dense fp32 MFMA (v_mfma_f32_32x32x2_f32): the r
 # the fp32 engine's large GEMMs run on gemm_f32x3.hip: each fp32 product = six bf16 MFMA products (three bf16 planes per operand,
 # fp32 accumulation), so their roofline is a sixth of the bf16 MFMA peak; CODAE_F32_GEMM=native puts them back on the fp32 MFMA
 PEAK_F32_VIA_BF16_TFLOPS = PEAK_BF16_TFLOPS / 6.0
+DUMP_SEED = 0                  # --dump-outputs: the fixed sample of weight entries
+DUMP_WEIGHT_FLOATS = 8 << 20   # ... at most this many weight entries over all layers (32 MB)
 
 
 def f32_peak_tflops():
@@ -150,6 +161,61 @@ def torch_cpu_baseline(schedule, x_np, fmask_np, budget_s=8.0):
             "ms_per_step": 1e3 * t_sum / n, "sample": "%d timed steps (1 warm-up), torch %s CPU fp32" % (n, torch.__version__)}
 
 
+# The device buffers of the C ABI (codae.hip.Buffers; the library allocates none of its own), split into what a
+# training step carries over to the next one (field -> DaeEngine attribute: fp32 parameters, gradients, Adam moments,
+# the bf16 weight shadows plain and transposed, the scalars with the metric sums, loss and Adam step) and per-step
+# workspace that every step writes before it reads it.
+STATE_BUFFERS = {"params": "params", "grads": "grads", "adam_m": "adam_m", "adam_v": "adam_v", "shadow_w": "shadow",
+                 "shadow_wt": "shadow_t", "scalars": "scalars"}
+WORKSPACE_BUFFERS = ("acts", "dacts", "slabs", "bias_parts")
+
+
+def _state_tensors(eng):
+    return [t for t in (getattr(eng, a) for a in STATE_BUFFERS.values()) if t is not None]
+
+
+def snapshot_state(tr):
+    eng = tr.engine
+    return [t.clone() for t in _state_tensors(eng)], eng.step_count
+
+
+def restore_state(tr, snap):
+    eng = tr.engine
+    saved, step_count = snap
+    for dst, src in zip(_state_tensors(eng), saved):
+        dst.copy_(src)
+    eng.step_count = step_count
+
+
+def dump_outputs(tr, out_dir):
+    """What the last step gave its caller, as .npy: loss, grad_norm (before clipping) and the epoch metric sums
+    (float64, as the engine keeps them), every bias and a fixed sample of every layer's weights (float32; the same
+    DUMP_SEED positions in every run, all of them when a layer has few enough)."""
+    import numpy as np
+    import torch
+    eng = tr.engine
+    sq_full, sq_partial, _, _ = eng.read_scalars()
+    loss, gnorm = tr.last_loss_and_grad_norm()
+    out = {"loss": np.array([loss], np.float64), "grad_norm": np.array([gnorm], np.float64),
+           "metric_sums": np.array([sq_full, sq_partial], np.float64)}
+    rng = np.random.default_rng(DUMP_SEED)
+    per_layer = DUMP_WEIGHT_FLOATS // eng.L
+    ws, bs = [], []
+    for l in range(eng.L):
+        w = eng.weight(l).reshape(-1)
+        if w.numel() > per_layer:
+            pick = np.sort(rng.choice(w.numel(), per_layer, replace=False))
+            w = w[torch.from_numpy(pick).to(w.device)]
+        ws.append(w.cpu().numpy())
+        bs.append(eng.bias(l).cpu().numpy())
+    out["weights_sample"] = np.stack(ws).astype(np.float32)          # [layer, entry]: the square schedule's layers are alike
+    out["biases"] = np.stack(bs).astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -160,13 +226,20 @@ def main():
     ap.add_argument("--slots", type=int, default=None)
     ap.add_argument("--embedding", type=int, default=None)
     ap.add_argument("--batch", type=int, default=None)
-    ap.add_argument("--no-f32-parity", action="store_true", help="skip the exact-fp32 (parity mode) leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the exact-fp32 leg, the per-kernel / roofline figures "
+                         "(hipEvent pairs in the timed region) and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, grad norm, metric sums, biases, a "
+                         "fixed sample of the weights) as DIR/<name>.npy; one process: the same bits for the same arguments; "
+                         "N > 1: rank 0's replica (gathered first with --sharded-update), not rolled back to a fixed state")
+    ap.add_argument("--no-f32-parity", action="store_true", help="--full: skip the exact-fp32 (parity mode) leg")
     ap.add_argument("--kernel-events-every", type=int, default=16,
-                    help="record per-launch hipEvent pairs in every n-th timed step only (a sampled C3 step carries ~60 event "
-                         "records: every 4th step cost 4 %% of the reported rate, every 16th 0.7 %%, none 0)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: record per-launch hipEvent pairs in every n-th timed step only (a sampled C3 step carries ~60 "
+                         "event records: every 4th step cost 4 %% of the reported rate, every 16th 0.7 %%, none 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--no-kernel-events", action="store_true",
-                    help="do not record per-launch hipEvents in the timed region (roofline then null)")
+                    help="--full: do not record per-launch hipEvents in the timed region (roofline then null)")
     ap.add_argument("--buckets", type=int, default=0,
                     help="N > 1: gradient buckets of the all-reduce (0 = one per layer, SURVEY.md 8e: the first collective starts "
                          "one layer into the backward and the exposed tail is one layer's 9.4 MB; 4 with --sharded-update)")
@@ -175,9 +248,11 @@ def main():
     ap.add_argument("--native-rccl", action="store_true",
                     help="N > 1: the library's own RCCL communicator issues the bucket all-reduces inside one call per step "
                          "(codae_train_step_dp; opt-in: only ever run with one rank on this build's test boxes)")
-    ap.add_argument("--fwd-events-only", action="store_true", help="time only the forward GEMM class")
+    ap.add_argument("--fwd-events-only", action="store_true", help="--full: time only the forward GEMM class")
     ap.add_argument("--graph", action="store_true", help="replay the step from a hipGraph (single GPU; no live kernel events)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     cs, ce, cb = CONFIGS[args.config]
     args.slots = cs if args.slots is None else args.slots
     args.embedding = ce if args.embedding is None else args.embedding
@@ -259,6 +334,9 @@ def main():
     for st in range(args.warmup):
         tr.train_batch(idx_steps[st], run=0)
     barrier()
+    # the state after the W warm-up steps: the ramp-up and burst steps below are rolled back to it, and so is a re-timed
+    # pass, so that the timed steps always start from it (a data-parallel run keeps state outside the engine: not rolled back)
+    snap = snapshot_state(tr) if not distributed else None
     # Ramp-up guard (untimed, on top of the W warm-up steps the caller asked for): a process whose first kernels have
     # just run is not in steady state - code objects of kernels that only the 2nd step needs, the power state after an
     # idle lease (tools/cold_start.py).  Extra steps run one at a time until two consecutive ones
@@ -285,7 +363,10 @@ def main():
         for i in range(burst):
             tr.train_batch(idx_steps[i % max(1, args.warmup or 1)], run=0)
         barrier()
-    kernel_events = not args.no_kernel_events and not args.graph
+    if snap is not None:
+        restore_state(tr, snap)
+        barrier()
+    kernel_events = args.full and not args.no_kernel_events and not args.graph
     # at least three timed steps carry the per-launch event pairs (mean != min in by_kernel), spread over the region
     every = max(1, min(args.kernel_events_every, args.steps // 3 if args.steps >= 3 else 1))
     if kernel_events:
@@ -334,6 +415,9 @@ def main():
     if steady and world == 1 and step_times is None and 1e3 * elapsed / args.steps > 1.25 * steady:
         first = {"ms_per_step": 1e3 * elapsed / args.steps, "host_enqueue_ms_per_step": 1e3 * enqueue_s / args.steps,
                  "ramp_up_median_ms": steady}
+        if snap is not None:
+            restore_state(tr, snap)
+            barrier()
         evs = []
         start = torch.cuda.Event(enable_timing=True)
         start.record()
@@ -345,6 +429,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
     loss, gnorm = tr.last_loss_and_grad_norm()
+    if args.dump_outputs and tr.dp is not None:
+        tr.dp.gather_params()          # (collective, every rank) sharded update: each rank keeps only its own shards current
+    dumped = dump_outputs(tr, args.dump_outputs) if args.dump_outputs and rank == 0 else None
+    snap = None
     step_path = "layers (bucketed backward + collectives)" if distributed else tr.engine.step_path(B)
     dp_info = None
     if distributed:
@@ -354,7 +442,7 @@ def main():
 
     # exact-fp32 (parity) mode on the same workload: the mode every reference-pinned rtol 1e-3 / atol 1e-5 replay runs in
     f32_parity = None
-    if (world == 1 and not distributed and args.precision == "bf16" and args.config == "c3" and not args.no_f32_parity
+    if (args.full and world == 1 and not distributed and args.precision == "bf16" and args.config == "c3" and not args.no_f32_parity
             and (slots, emb, B) == CONFIGS["c3"] and not args.graph):
         del tr
         torch.cuda.empty_cache()
@@ -405,7 +493,8 @@ def main():
             "host_enqueue_done_ms_first_steps": enq_marks, "ramp_up_step_ms": ramp_ms,
             "host_cpu_share": host_share, "host_threads": torch.get_num_threads(),
             "step_path": step_path,
-            "f32_parity": f32_parity,
+            "f32_parity": f32_parity, "full": bool(args.full),
+            **({"dumped_outputs": {"dir": args.dump_outputs, "arrays": dumped}} if dumped is not None else {}),
             **({"step_done_ms": step_times} if step_times is not None else {}),
             **({"retimed": retimed} if retimed is not None else {}),
         }
@@ -473,7 +562,7 @@ def main():
         step_tf = fps * value / world / 1e12
         out["roofline_step"] = {"bound": "mfma", "achieved": step_tf, "peak": peak, "unit": "TFLOP/s", "frac": step_tf / peak,
                                 "note": "algorithmic flops of the whole step (29 GEMMs' worth at C3) / wall time per step"}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(schedule, data, blank, io, slots, B)
         else:
             out["cpu_baseline"] = None

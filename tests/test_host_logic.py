@@ -439,3 +439,73 @@ def test_three_bf16_planes_carry_an_fp32_value_and_six_products_carry_its_produc
     assert np.all(np.abs(total - a64 * b64) <= 1.5 * 2.0 ** -23 * np.abs(a64 * b64))
     ints = rng.integers(-(2 ** 24) + 1, 2 ** 24, 100000).astype(np.float32)
     assert np.array_equal(sum(p.astype(np.float64) for p in planes(ints)), ints.astype(np.float64))
+
+
+def test_bench_dump_outputs_and_rollback_on_host_tensors(tmp_path):
+    """bench.py's --dump-outputs writer and the roll-back of the extra warm-up steps, on a stand-in for the engine that keeps
+    the same state tensors on the host: the C3 shapes stay under 64 MB, the weight sample is the same every time, and a
+    restore puts every carried-over tensor and the step count back."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    io, L = 1536, 10
+
+    class Eng:
+        def __init__(self, seed):
+            g = torch.Generator().manual_seed(seed)
+            n = L * (io * io + io)
+            self.L, self.step_count = L, 0
+            self.params, self.grads = torch.rand(n, generator=g), torch.rand(n, generator=g)
+            self.adam_m, self.adam_v = torch.rand(n, generator=g), torch.rand(n, generator=g)
+            self.shadow = self.params[:L * io * io].to(torch.bfloat16)
+            self.shadow_t = self.shadow.clone()
+            self.scalars = torch.rand(80, generator=g, dtype=torch.float64)
+
+        def weight(self, l): return self.params[l * io * io:(l + 1) * io * io].view(io, io)
+        def bias(self, l): return self.params[L * io * io + l * io:L * io * io + (l + 1) * io]
+        def read_scalars(self): return float(self.scalars[0]), float(self.scalars[1]), float(self.scalars[2]), float(self.scalars[3])
+
+    class Tr:
+        def __init__(self, seed): self.engine = Eng(seed)
+        def last_loss_and_grad_norm(self): return float(self.engine.scalars[3]), float(self.engine.scalars[2]) ** 0.5
+
+    tr = Tr(0)
+    names = bench.dump_outputs(tr, str(tmp_path / "a"))
+    bench.dump_outputs(Tr(0), str(tmp_path / "b"))
+    assert names == sorted(["loss", "grad_norm", "metric_sums", "weights_sample", "biases"])
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / (n + ".npy")), np.load(tmp_path / "b" / (n + ".npy"))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 << 20
+    w = np.load(tmp_path / "a" / "weights_sample.npy")
+    assert w.shape == (L, bench.DUMP_WEIGHT_FLOATS // L)
+    assert np.isin(w[3], tr.engine.weight(3).numpy()).all()
+    assert np.array_equal(np.load(tmp_path / "a" / "biases.npy"), np.stack([tr.engine.bias(l).numpy() for l in range(L)]))
+    assert np.load(tmp_path / "a" / "loss.npy")[0] == tr.last_loss_and_grad_norm()[0]
+
+    # the roll-back list covers every device buffer the library is handed (codae.hip.Buffers: it allocates none of its own)
+    # except the per-step workspaces, and names the tensor the engine itself binds to that field
+    from codae.hip import Buffers
+    from codae.hip.engine import DaeEngine
+    import inspect
+    fields = [f for f, _ in Buffers._fields_]
+    assert set(bench.STATE_BUFFERS).isdisjoint(bench.WORKSPACE_BUFFERS)
+    assert set(bench.STATE_BUFFERS) | set(bench.WORKSPACE_BUFFERS) == set(fields)
+    bound = re.search(r"self\.bufs = Buffers\((.*?)\)\n", inspect.getsource(DaeEngine.__init__), re.S).group(1)
+    attrs = re.findall(r"ptr\(self\.(\w+)\)", bound)
+    assert len(attrs) == len(fields)
+    for field, attr in zip(fields, attrs):
+        if field in bench.STATE_BUFFERS:
+            assert attr in (bench.STATE_BUFFERS[field], "_" + bench.STATE_BUFFERS[field]), (field, attr)
+
+    snap = bench.snapshot_state(tr)
+    before = [t.clone() for t in bench._state_tensors(tr.engine)]
+    for t in bench._state_tensors(tr.engine):
+        t.add_(1)
+    tr.engine.step_count = 77
+    bench.restore_state(tr, snap)
+    assert tr.engine.step_count == 0
+    assert all(torch.equal(a, b) for a, b in zip(before, bench._state_tensors(tr.engine)))

@@ -4,8 +4,8 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_f32; mkdir -p $O
 python tools/abl/f32x3_check.py > $O/f32x3_check.txt 2>&1
 python tools/abl/f32_truth.py 2>&1 | grep -v "amdgpu\|UserWarning\|detach\|print(" > $O/f32_truth.txt
-python bench.py --precision f32 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_c3_f32.json.log 2>/dev/null
-CODAE_F32_GEMM=native python bench.py --precision f32 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_c3_f32_native.json.log 2>/dev/null
+python bench.py --full --precision f32 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_c3_f32.json.log 2>/dev/null
+CODAE_F32_GEMM=native python bench.py --full --precision f32 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_c3_f32_native.json.log 2>/dev/null
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --precision f32 --steps 6 --warmup 2 --no-cpu-baseline --no-kernel-events > $O/stats.log 2>&1
 timeout -k 10 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/pmc -- python3 $R/bench.py --precision f32 --steps 4 --warmup 2 --no-cpu-baseline --no-kernel-events > $O/pmc.log 2>&1

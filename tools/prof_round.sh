@@ -4,9 +4,9 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof_${PROF_TAG:-r03a}
 mkdir -p $O
 cd $R
-timeout -k 10 300 python bench.py > $O/bench_c3.json.log 2>$O/bench_c3.err
-timeout -k 10 300 python bench.py --config c2 > $O/bench_c2.json.log 2>$O/bench_c2.err
-timeout -k 10 400 python bench.py --config c5 --no-f32-parity > $O/bench_c5.json.log 2>$O/bench_c5.err
+timeout -k 10 300 python bench.py --full > $O/bench_c3.json.log 2>$O/bench_c3.err
+timeout -k 10 300 python bench.py --full --config c2 > $O/bench_c2.json.log 2>$O/bench_c2.err
+timeout -k 10 400 python bench.py --full --config c5 --no-f32-parity > $O/bench_c5.json.log 2>$O/bench_c5.err
 timeout -k 10 300 python bench.py --config c3 --batch 128 --no-f32-parity --no-cpu-baseline --no-kernel-events --steps 200 --warmup 20 > $O/bench_stock_b128.json.log 2>$O/bench_stock_b128.err
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-f32-parity > $O/stats.log 2>&1
