@@ -41,9 +41,10 @@ extern "C" {
  *   4: + codae_ranking_loss_batched, codae_gather_inventory_rows, codae_step_path (new entries only; no layout change)
  *   5: + codae_monitor_accumulate; codae_ranking_loss_batched takes val_group (rows of the validation inventory that are
  *      exact duplicates of each other) behind val_pos; + codae_dp_unique_id / _init / _destroy, codae_train_step_dp
+ *   6: codae_spec.act_kind / act_param (appended), CODAE_ACT_*, codae_linear_act_f32 / _bf16, codae_dgrad_act_f32 / _bf16
  * The binding must refuse a library whose codae_abi_version() differs and must check its own struct sizes against
  * codae_struct_sizes() at load (mui-deepautoencoder_amd/codae/hip/__init__.py does both). */
-#define CODAE_ABI_VERSION 5
+#define CODAE_ABI_VERSION 6
 
 enum {
     CODAE_OK = 0,
@@ -63,6 +64,27 @@ enum {
                           * codae_create returns CODAE_E_UNSUPPORTED otherwise (the caller falls back to CODAE_PREC_F32) */
 };
 
+/* activation after a Linear (the `activation` factory of the reference constructors, called as activation(True)).  Each is
+ * monotone, so the backward takes its derivative from the saved OUTPUT y - what torch's in-place backward of these modules
+ * does.  Parameters p[3] per layer:
+ *   NONE         identity                                               -
+ *   RELU         max(v, 0)                                               -
+ *   LEAKY        v > 0 ? v : s v                     dy/dv = y > 0 ? 1 : s             p = {s >= 0}
+ *   RELU6        min(max(v, 0), 6)                   dy/dv = 0 < y < 6                 -
+ *   ELU          v > 0 ? l v : l a (exp(v / b) - 1)  dy/dv = y > 0 ? l : (y + l a) / b  p = {l > 0, a > 0, 1 / b > 0}
+ *                (torch.nn.ELU: l = 1, b = 1; CELU: l = 1, b = a; SELU: torch's l and a, b = 1)
+ *   SOFTPLUS     b v > t ? v : log1p(exp(b v)) / b   dy/dv = b y > t ? 1 : -expm1(-b y) p = {b > 0, t}
+ *   HARDSIGMOID  clamp(v / 6 + 1/2, 0, 1)            dy/dv = 0 < y < 1 ? 1/6 : 0       - */
+enum {
+    CODAE_ACT_NONE = 0,
+    CODAE_ACT_RELU = 1,
+    CODAE_ACT_LEAKY = 2,
+    CODAE_ACT_RELU6 = 3,
+    CODAE_ACT_ELU = 4,
+    CODAE_ACT_SOFTPLUS = 5,
+    CODAE_ACT_HARDSIGMOID = 6
+};
+
 typedef struct codae_engine* codae_handle;
 
 /* Network description: the Linear stack built by
@@ -75,6 +97,13 @@ typedef struct {
     const uint8_t* relu;         /* [n_layers] 1 = ReLU follows this Linear */
     int32_t max_batch;           /* rows the workspaces are sized for */
     int32_t precision;           /* CODAE_PREC_* */
+    /* ABI 6.  NULL: `relu` alone says what follows each Linear (ReLU or nothing).  Else act_kind[l] (CODAE_ACT_*) does and
+     * `relu` is not read; act_param [n_layers][3] holds the parameters above (may be NULL when no layer needs any).  The
+     * last layer takes NONE or RELU only.  Layers with another kind than RELU get no 1-bit masks and keep the stack off the
+     * persistent chain kernel (codae_step_path).  codae_create returns CODAE_E_INVALID for an unknown kind or a parameter
+     * out of range. */
+    const uint8_t* act_kind;
+    const float* act_param;
 } codae_spec;
 
 /* Byte sizes / element offsets the caller needs to allocate the borrowed buffers. */
@@ -387,6 +416,17 @@ int codae_dgrad_bf16(const void* dy, const void* W, const void* relu_src, void* 
                      int32_t M, int32_t N, int32_t K, void* stream);
 int codae_wgrad_bf16(const void* dy, const void* x, float* dW, void* slabs, int64_t slab_bytes,
                      int32_t M, int32_t N, int32_t K, void* stream);
+/* The same forward / data-gradient GEMMs with any CODAE_ACT_* and its parameters (p0, p1, p2 as in codae_spec.act_param):
+ * y = act(x . W^T + b); dx = (dy . W) * act'(act_src), act_src = the saved output of the activation (NULL: no factor).
+ * act = NONE runs the plain kernels above; every other kind (RELU included) the generic-activation instantiations. */
+int codae_linear_act_f32(const float* x, const float* W, const float* b, float* y, int32_t M, int32_t N, int32_t K,
+                         int32_t act, float p0, float p1, float p2, void* stream);
+int codae_dgrad_act_f32(const float* dy, const float* W, const float* act_src, float* dx, int32_t M, int32_t N, int32_t K,
+                        int32_t act, float p0, float p1, float p2, void* stream);
+int codae_linear_act_bf16(const void* x, const void* W, const float* b, void* y, int32_t y_f32, int32_t M, int32_t N,
+                          int32_t K, int32_t act, float p0, float p1, float p2, void* stream);
+int codae_dgrad_act_bf16(const void* dy, const void* W, const void* act_src, void* dx, float* db_prev, float* db_ws,
+                         int32_t M, int32_t N, int32_t K, int32_t act, float p0, float p1, float p2, void* stream);
 /* Tuning aid: with CODAE_GEMM_DBG=8 the forward-form bf16 GEMM stamps a 100 MHz wall clock per workgroup (entry, first
  * MFMA phase, end of K loop, stores issued, stores retired, XCC id: 6 words each); this copies the first n_wg records to
  * host memory (synchronises the device). */

@@ -14,10 +14,12 @@ LIB_PATH = os.environ.get("CODAE_HIP_LIB") or os.path.join(_HERE, "libcodae_hip.
 PREC_F32 = 0
 PREC_BF16 = 1
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 # CODAE_S_* of include/codae_hip.h (tests/test_host_logic.py parses the header and compares)
 S_SQ_FULL, S_SQ_PARTIAL, S_GRAD_SQ, S_LAST_LOSS, S_STEP_SQ, S_CLIP_COEF = 0, 1, 2, 3, 4, 5
 S_GRAD_SQ_SLOTS, S_N_SLOTS, S_ADAM_STEP, S_COUNT = 8, 64, 72, 80
+# CODAE_ACT_* of include/codae_hip.h: the activation after a Linear (codae.model.activation maps torch modules to these)
+ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_RELU6, ACT_ELU, ACT_SOFTPLUS, ACT_HARDSIGMOID = 0, 1, 2, 3, 4, 5, 6
 KERNEL_CLASSES = ("gemm_fwd", "gemm_dgrad", "gemm_wgrad", "loss", "gather", "sumsq", "adam", "slab_reduce", "chain",
                   "bias_finish")
 
@@ -32,7 +34,9 @@ class Spec(C.Structure):
                 ("out_features", C.POINTER(C.c_int32)),
                 ("relu", C.POINTER(C.c_uint8)),
                 ("max_batch", C.c_int32),
-                ("precision", C.c_int32)]
+                ("precision", C.c_int32),
+                ("act_kind", C.POINTER(C.c_uint8)),
+                ("act_param", C.POINTER(C.c_float))]
 
 
 class Sizes(C.Structure):
@@ -113,6 +117,10 @@ PROTOTYPES = {
     "codae_linear_bf16": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
     "codae_dgrad_bf16": (C.c_int, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P]),
     "codae_wgrad_bf16": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I32, _I32, _P]),
+    "codae_linear_act_f32": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _F, _F, _F, _P]),
+    "codae_dgrad_act_f32": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _F, _F, _F, _P]),
+    "codae_linear_act_bf16": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _F, _F, _P]),
+    "codae_dgrad_act_bf16": (C.c_int, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _F, _F, _F, _P]),
     "codae_cast_f32_to_bf16": (C.c_int, [_P, _P, _I64, _P]),
     "codae_debug_gemm_timeline": (C.c_int, [_P, _I32]),
     "codae_transpose_bf16": (C.c_int, [_P, _P, _I32, _I32, _P]),

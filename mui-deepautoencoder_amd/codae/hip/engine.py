@@ -27,7 +27,10 @@ class DaeEngine:
     the model classes (embedding_denoising_autoencoder.py:49-129 of the reference).
     """
 
-    def __init__(self, schedule, max_batch, precision, device, with_optimizer_state=True):
+    def __init__(self, schedule, max_batch, precision, device, with_optimizer_state=True, activation=None):
+        """activation: None = ReLU after every layer whose schedule flag is set (as always); else what follows those
+        layers instead - an activation factory called as activation(True) (the model classes' convention), or a
+        (CODAE_ACT_* kind, p0, p1, p2) tuple, or one such tuple per layer (the flags are then ignored)."""
         device = torch.device(device)
         if device.type != "cuda":
             raise HipError("the codae HIP engine needs a HIP device (got %s); there is no CPU path" % device)
@@ -40,7 +43,11 @@ class DaeEngine:
         ins = (C.c_int32 * self.L)(*[s[0] for s in self.schedule])
         outs = (C.c_int32 * self.L)(*[s[1] for s in self.schedule])
         relu = (C.c_uint8 * self.L)(*[1 if s[2] else 0 for s in self.schedule])
+        self.activation = self._layer_acts(activation)
         spec = Spec(self.L, ins, outs, relu, self.max_batch, self.precision)
+        if self.activation is not None:
+            spec.act_kind = (C.c_uint8 * self.L)(*[a[0] for a in self.activation])
+            spec.act_param = (C.c_float * (3 * self.L))(*[float(p) for a in self.activation for p in a[1:]])
         h = C.c_void_p()
         check(self._lib.codae_create(C.byref(spec), C.byref(h)))
         self._h = h
@@ -78,6 +85,25 @@ class DaeEngine:
             self.b_off.append(b.value)
         self.step_count = 0
         self.generation = 0   # bumped by every forward: guards stale backward calls
+
+    def _layer_acts(self, activation):
+        """[(kind, p0, p1, p2)] per layer, or None (the relu flags alone)."""
+        if activation is None:
+            return None
+        if isinstance(activation, (list, tuple)) and len(activation) == self.L and all(
+                isinstance(a, (list, tuple)) for a in activation):
+            acts = [tuple(a) for a in activation]
+        else:
+            if isinstance(activation, (list, tuple)):
+                one = tuple(activation)
+            else:
+                from ..model.activation import from_factory
+                one = from_factory(activation)
+            acts = [one if s[2] else (0, 0.0, 0.0, 0.0) for s in self.schedule]
+        for a in acts:
+            if len(a) != 4:
+                raise HipError("activation per layer must be (kind, p0, p1, p2), got %r" % (a,))
+        return [(int(a[0]), float(a[1]), float(a[2]), float(a[3])) for a in acts]
 
     def __del__(self):
         h = getattr(self, "_h", None)

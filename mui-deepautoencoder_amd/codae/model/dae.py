@@ -18,6 +18,7 @@ import torch
 from ..hip import HipError
 from ..hip import lib as _hip_lib
 from ..hip import check as _check, ptr as _ptr, current_stream as _stream
+from .activation import as_engine_act
 from .schedule import linear_stack
 
 
@@ -67,6 +68,11 @@ class _HipDenoisingAutoencoder(torch.nn.Module):
         # decoder's) so that torch.manual_seed(s) yields bit-identical initial weights.
         self.input_layer = self._sequential(encoder, activation)
         self.output_layer = self._sequential(decoder, activation)
+        # what the engine runs after each Linear: read from the modules just built (HipError here, at construction, for an
+        # activation it cannot run - never a silent ReLU)
+        acts = self._engine_acts()
+        relu_only = all(a[0] == (1 if r else 0) for a, (_, _, r) in zip(acts, self._schedule))
+        self._acts = None if relu_only else acts        # (None: the engine's ReLU flags, exactly as before)
         self._engine = None
         self._act_stamp = [0] * len(self._schedule)
         self._synced_version = None
@@ -88,6 +94,17 @@ class _HipDenoisingAutoencoder(torch.nn.Module):
                 m.bias.data.fill_(0)                        # embedding_...py:200-211
         return seq
 
+    def _engine_acts(self):
+        """[(CODAE_ACT_* kind, p0, p1, p2)] per Linear, from the module that follows it (none: identity)."""
+        acts = []
+        for seq in (self.input_layer, self.output_layer):
+            mods = list(seq)
+            for i, m in enumerate(mods):
+                if isinstance(m, torch.nn.Linear):
+                    nxt = mods[i + 1] if i + 1 < len(mods) and not isinstance(mods[i + 1], torch.nn.Linear) else None
+                    acts.append((0, 0.0, 0.0, 0.0) if nxt is None else as_engine_act(nxt))
+        return acts
+
     # ---- engine plumbing --------------------------------------------------------------
     def _linears(self):
         return [m for seq in (self.input_layer, self.output_layer) for m in seq if isinstance(m, torch.nn.Linear)]
@@ -107,11 +124,11 @@ class _HipDenoisingAutoencoder(torch.nn.Module):
         if eng is None or eng.device != dev or eng.precision != want_prec or B > eng.max_batch:
             cap = max(B, eng.max_batch if eng is not None else 0, 256)
             try:
-                eng = DaeEngine(self._schedule, cap, want_prec, dev, with_optimizer_state=False)
+                eng = DaeEngine(self._schedule, cap, want_prec, dev, with_optimizer_state=False, activation=self._acts)
             except HipError:
                 if want_prec == precision_code("bf16"):
                     # widths the bf16 tiles cannot take (e.g. abalone's 11): fp32 kernels instead
-                    eng = DaeEngine(self._schedule, cap, "f32", dev, with_optimizer_state=False)
+                    eng = DaeEngine(self._schedule, cap, "f32", dev, with_optimizer_state=False, activation=self._acts)
                     self.precision = "f32"
                 else:
                     raise

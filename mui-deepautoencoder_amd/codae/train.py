@@ -383,13 +383,15 @@ class HipEmbeddingTrainer:
 
     def __init__(self, schedule, data, mask_table_u8, mask_to_use_i32, lr, weight_decay, clip=1.0,
                  max_batch=8192, precision="bf16", device="cuda:0", distributed=False, n_buckets=None, use_graph=False,
-                 sharded_update=False, native_dp=False):
+                 sharded_update=False, native_dp=False, activation=None):
         """use_graph: replay the fused step from a hipGraph (codae_train_step_graph): for launch-bound shapes
-        (small batches); single process only - the bucketed data-parallel step is not captured."""
+        (small batches); single process only - the bucketed data-parallel step is not captured.
+        activation: what follows every hidden Linear, as the model classes take it (a factory called as activation(True),
+        e.g. torch.nn.ELU); None = ReLU.  Every step form (fused, graph replay, data parallel) runs it."""
         from .hip.engine import DaeEngine
         fit_host_threads()      # the loop that feeds this trainer must not get its container CPU-throttled (codae/hostcpu.py)
         self.device = torch.device(device)
-        self.engine = DaeEngine(schedule, max_batch, precision, self.device)
+        self.engine = DaeEngine(schedule, max_batch, precision, self.device, activation=activation)
         self.data = data.to(device=self.device, dtype=torch.float32).contiguous()
         self.mask_table = None if mask_table_u8 is None else mask_table_u8.to(self.device).contiguous()
         self.mask_to_use = None if mask_to_use_i32 is None else mask_to_use_i32.to(self.device).contiguous()

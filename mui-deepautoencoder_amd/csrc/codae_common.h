@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <type_traits>
 
 #include "codae_hip.h"
 
@@ -77,6 +78,88 @@ __device__ __forceinline__ float4 load_bias4(const float* __restrict__ bias, con
     return make_float4(ok ? v.x : 0.f, ok ? v.y : 0.f, ok ? v.z : 0.f, ok ? v.w : 0.f);
 }
 
+// ---- activations other than ReLU (CODAE_ACT_*; include/codae_hip.h has the parameter table) -----------------------------
+// Only the generic-activation instantiations of the GEMM epilogues (template flag ACT) call these; the ReLU / identity
+// instantiations keep clamp_below and the sign / bit masks.  Every supported activation is monotone, so its derivative is a
+// function of the saved OUTPUT y: the data gradient multiplies by act_dy_from_y(saved activation) where ReLU masks by y > 0.
+// Formulas as torch's CPU kernels write them (elu / softplus / hardsigmoid and their is_result backwards).
+// The empty asm statements keep each element's arithmetic a scalar chain: left alone, the SLP vectorizer packs neighbouring
+// elements - and the double-float steps inside the device library's expm1f / log1pf - into v_pk_*_f32 with op_sel routing
+// (tools/check_isa.py rule 4 rejects that form).  So exp / log are the hardware v_exp_f32 / v_log_f32
+// and expm1 / log1p Kahan's identities on top of them (a few fp32 ulps; the fp32 engine's bar is rtol 1e-3).
+__device__ __forceinline__ float act_opaque(float x) { asm("" : "+v"(x)); return x; }
+__device__ __forceinline__ float act_exp(float x) { return __builtin_amdgcn_exp2f(act_opaque(x * 1.44269504f)); }
+__device__ __forceinline__ float act_log(float x) { return act_opaque(__builtin_amdgcn_logf(x)) * 0.693147181f; }
+__device__ __forceinline__ float act_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+__device__ __forceinline__ float act_expm1(float x) {     // (u - 1) x / log u: the rounding of u cancels
+    const float u = act_opaque(act_exp(x));
+    const float um1 = act_opaque(u - 1.f);
+    if (u == 1.f) return x;
+    if (um1 == -1.f) return -1.f;
+    return act_opaque(um1 * x) * act_rcp(act_log(u));
+}
+__device__ __forceinline__ float act_log1p(float t) {     // t log(1 + t) / ((1 + t) - 1)
+    const float u = act_opaque(1.f + t);
+    if (u == 1.f) return t;
+    return act_opaque(act_log(u) * t) * act_rcp(act_opaque(u - 1.f));
+}
+__device__ __forceinline__ float act_fwd_(int kind, const float* p, float v) {
+    switch (kind) {
+        case CODAE_ACT_RELU: return v > 0.f ? v : 0.f;
+        case CODAE_ACT_LEAKY: return v > 0.f ? v : v * p[0];
+        case CODAE_ACT_RELU6: return v <= 0.f ? 0.f : (v >= 6.f ? 6.f : v);
+        case CODAE_ACT_ELU: return v > 0.f ? v * p[0] : act_expm1(v * p[2]) * act_opaque(p[1] * p[0]);
+        case CODAE_ACT_SOFTPLUS: return v * p[0] > p[1] ? v : act_log1p(act_exp(v * p[0])) * act_rcp(p[0]);
+        case CODAE_ACT_HARDSIGMOID: return fminf(fmaxf(v + 3.f, 0.f), 6.f) * (1.f / 6.f);
+        default: return v;
+    }
+}
+__device__ __forceinline__ float act_fwd(int kind, const float* p, float v) {
+    asm("" : "+v"(v));
+    float r = act_fwd_(kind, p, v);
+    asm("" : "+v"(r));
+    return r;
+}
+__device__ __forceinline__ float act_dy_from_y_(int kind, const float* p, float y) {
+    switch (kind) {
+        case CODAE_ACT_RELU: return y > 0.f ? 1.f : 0.f;
+        case CODAE_ACT_LEAKY: return y > 0.f ? 1.f : p[0];
+        case CODAE_ACT_RELU6: return (y > 0.f && y < 6.f) ? 1.f : 0.f;
+        case CODAE_ACT_ELU: return y > 0.f ? p[0] : p[2] * act_opaque(y + act_opaque(p[1] * p[0]));
+        case CODAE_ACT_SOFTPLUS: return y * p[0] > p[1] ? 1.f : -act_expm1(-y * p[0]);
+        case CODAE_ACT_HARDSIGMOID: return (y > 0.f && y < 1.f) ? 1.f / 6.f : 0.f;
+        default: return 1.f;
+    }
+}
+__device__ __forceinline__ float act_dy_from_y(int kind, const float* p, float y) {
+    asm("" : "+v"(y));
+    float r = act_dy_from_y_(kind, p, y);
+    asm("" : "+v"(r));
+    return r;
+}
+
+// f(std::integral_constant<int, kind>): one switch per thread around a whole epilogue instead of one per element (a loop body
+// small enough to unroll fully - the accumulators stay in registers)
+template <typename F>
+__device__ __forceinline__ void act_dispatch(int kind, F&& f) {
+    switch (kind) {
+        case CODAE_ACT_RELU: f(std::integral_constant<int, CODAE_ACT_RELU>{}); break;
+        case CODAE_ACT_LEAKY: f(std::integral_constant<int, CODAE_ACT_LEAKY>{}); break;
+        case CODAE_ACT_RELU6: f(std::integral_constant<int, CODAE_ACT_RELU6>{}); break;
+        case CODAE_ACT_ELU: f(std::integral_constant<int, CODAE_ACT_ELU>{}); break;
+        case CODAE_ACT_SOFTPLUS: f(std::integral_constant<int, CODAE_ACT_SOFTPLUS>{}); break;
+        case CODAE_ACT_HARDSIGMOID: f(std::integral_constant<int, CODAE_ACT_HARDSIGMOID>{}); break;
+        default: f(std::integral_constant<int, CODAE_ACT_NONE>{}); break;
+    }
+}
+
+// data gradient of a bf16 pair: (g_lo, g_hi) * act'(saved pair (h_lo, h_hi)), rounded to bf16 again (the ReLU code masks instead)
+__device__ __forceinline__ uint32_t act_dgrad_bf16x2(int kind, const float* p, uint32_t g2, uint32_t h2) {
+    const float lo = bf16_to_f32((bf16_t)(g2 & 0xffffu)) * act_dy_from_y(kind, p, bf16_to_f32((bf16_t)(h2 & 0xffffu)));
+    const float hi = bf16_to_f32((bf16_t)(g2 >> 16)) * act_dy_from_y(kind, p, bf16_to_f32((bf16_t)(h2 >> 16)));
+    return pack_bf16x2(lo, hi);
+}
+
 static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 // CODAE_* tuning / ablation variables, read ONCE (library load, codae_create, codae_reload_env): nothing on the
@@ -119,6 +202,10 @@ struct GemmF32 {
     int split_k;             // > 1: K is cut into split_k ranges of whole 32-deep tiles (grid.z); range z writes its partial
                              // product to C + z * M * ldc (fp32 slabs, reduced in slab order by reduce_slabs_kernel); no
                              // bias / ReLU / column sums then
+    int act;                 // != CODAE_ACT_NONE: the generic-activation instantiation (gemm_f32_kernel / gemm_f32x3_kernel <.., ACT>):
+                             // stored value = act_fwd(act, act_p, v) when relu_src is null, else v * act_dy_from_y(act, act_p, relu_src);
+                             // `relu` is ignored then.  CODAE_ACT_NONE: the ReLU / identity code above
+    float act_p[3];
 };
 int gemm_f32(const GemmF32& g, hipStream_t s);
 int gemm_f32x3(const GemmF32& g, hipStream_t s);      // gemm_f32x3.hip: the same product from three bf16 planes per operand
@@ -182,6 +269,10 @@ struct GemmBf16 {
                              // has the chip to itself and lose 7.5 % of the step in that company (tools/abl/ab_dp.sh)
     double* sumsq_slots;     // fp32 output, 128 x 128 tile only: += sum of the stored values' squares, scattered over the
                              // CODAE_S_N_SLOTS clip_grad_norm_ slots (what sumsq_kernel would add in a pass of its own), or null
+    int act;                 // as GemmF32::act: != CODAE_ACT_NONE picks the generic-activation instantiation (forward form: act_fwd on
+                             // the stored values; data-gradient form: times act_dy_from_y of relu_src); no 1-bit masks, no fused loss,
+                             // no k-strided A operand there
+    float act_p[3];
 };
 bool gemm_bf16_supported(int M, int N, int K);
 bool gemm_bf16_takes_relu_bits(int M, int N);    // forward-form bf16 launch of this output shape runs on a pipelined kernel
@@ -260,8 +351,10 @@ int launch_transpose_bf16(const bf16_t* src, bf16_t* dst, int n, const int64_t* 
                           hipStream_t s);
 int gemm_bf16_timeline(unsigned long long* host_out, int n_wg);   // CODAE_GEMM_DBG=8 stamps
 // sumsq != null: += sum out^2 (slot-scattered)
+// act != CODAE_ACT_NONE: the generic-activation epilogue (see GemmF32::act; relu is ignored then)
 int launch_reduce_slabs_epi(const float* slabs, int n_slabs, int64_t stride, int M, int N, float* C, int64_t ldc, const float* bias,
-                            int relu, const float* relu_src, int64_t ld_relu, float* colsum_part, hipStream_t s);
+                            int relu, const float* relu_src, int64_t ld_relu, float* colsum_part, hipStream_t s,
+                            int act = CODAE_ACT_NONE, const float* act_p = nullptr);
 int launch_reduce_slabs(const float* slabs, int n_slabs, int64_t slab_stride, float* out, int64_t n, double* sumsq,
                         hipStream_t s);
 // parts != null: SQ_FULL += sum parts[i][0], SQ_PARTIAL += sum parts[i][1] (fixed order) and the step's loss from

@@ -440,10 +440,12 @@ __global__ __launch_bounds__(NT) void reduce_slabs_kernel(const float* __restric
 // fill the chip and this kernel finishes them): C[i][j] = epi(sum_z slabs[z][i][j]), epi = + bias, ReLU, * [relu_src > 0];
 // colsum_part[i / 64][j] = sum of the stored values over the block's 64 rows (the next bias gradient's partial rows, as
 // gemm_f32 writes them).  One workgroup = 64 rows x 64 columns: thread -> 4 columns x 4 rows (16 apart).
+// ACT: the generic-activation epilogue (GemmF32::act: act_fwd, or times act_dy_from_y(relu_src)); false: the ReLU / identity code
+template <bool ACT = false>
 __global__ __launch_bounds__(NT) void reduce_slabs_epi_kernel(const float* __restrict__ slabs, int n_slabs, int64_t stride, int M, int N,
                                                               float* __restrict__ C, int64_t ldc, const float* __restrict__ bias, int relu,
                                                               const float* __restrict__ relu_src, int64_t ld_relu,
-                                                              float* __restrict__ colsum_part) {
+                                                              float* __restrict__ colsum_part, int act, float p0, float p1, float p2) {
     __shared__ float red[16][64 + 4];
     const int cg = threadIdx.x & 15, rg = threadIdx.x >> 4;
     const int j = blockIdx.x * 64 + cg * 4;
@@ -462,10 +464,21 @@ __global__ __launch_bounds__(NT) void reduce_slabs_epi_kernel(const float* __res
                 a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
             }
             a.x += bj.x; a.y += bj.y; a.z += bj.z; a.w += bj.w;
-            if (relu) { a.x = fmaxf(a.x, 0.f); a.y = fmaxf(a.y, 0.f); a.z = fmaxf(a.z, 0.f); a.w = fmaxf(a.w, 0.f); }
-            if (relu_src != nullptr) {
-                const float4 h = *reinterpret_cast<const float4*>(relu_src + (int64_t)i * ld_relu + j);
-                a.x = h.x > 0.f ? a.x : 0.f; a.y = h.y > 0.f ? a.y : 0.f; a.z = h.z > 0.f ? a.z : 0.f; a.w = h.w > 0.f ? a.w : 0.f;
+            if constexpr (ACT) {
+                const float p[3] = {p0, p1, p2};
+                if (relu_src != nullptr) {
+                    const float4 h = *reinterpret_cast<const float4*>(relu_src + (int64_t)i * ld_relu + j);
+                    a.x *= act_dy_from_y(act, p, h.x); a.y *= act_dy_from_y(act, p, h.y);
+                    a.z *= act_dy_from_y(act, p, h.z); a.w *= act_dy_from_y(act, p, h.w);
+                } else {
+                    a.x = act_fwd(act, p, a.x); a.y = act_fwd(act, p, a.y); a.z = act_fwd(act, p, a.z); a.w = act_fwd(act, p, a.w);
+                }
+            } else {
+                if (relu) { a.x = fmaxf(a.x, 0.f); a.y = fmaxf(a.y, 0.f); a.z = fmaxf(a.z, 0.f); a.w = fmaxf(a.w, 0.f); }
+                if (relu_src != nullptr) {
+                    const float4 h = *reinterpret_cast<const float4*>(relu_src + (int64_t)i * ld_relu + j);
+                    a.x = h.x > 0.f ? a.x : 0.f; a.y = h.y > 0.f ? a.y : 0.f; a.z = h.z > 0.f ? a.z : 0.f; a.w = h.w > 0.f ? a.w : 0.f;
+                }
             }
             *reinterpret_cast<float4*>(C + (int64_t)i * ldc + j) = a;
             cs[0] += a.x; cs[1] += a.y; cs[2] += a.z; cs[3] += a.w;
@@ -944,12 +957,18 @@ int launch_reduce_slabs(const float* slabs, int n_slabs, int64_t stride, float* 
 }
 
 int launch_reduce_slabs_epi(const float* slabs, int n_slabs, int64_t stride, int M, int N, float* C, int64_t ldc, const float* bias,
-                            int relu, const float* relu_src, int64_t ld_relu, float* colsum_part, hipStream_t s) {
+                            int relu, const float* relu_src, int64_t ld_relu, float* colsum_part, hipStream_t s, int act,
+                            const float* act_p) {
     CODAE_REQUIRE(slabs && C && n_slabs >= 1 && M > 0 && N > 0 && N % 4 == 0 && ldc % 4 == 0 && (relu_src == nullptr || ld_relu % 4 == 0) &&
                       a16(slabs) && a16(C) && (bias == nullptr || a16(bias)) && (relu_src == nullptr || a16(relu_src)),
                   "reduce_slabs_epi: bad args");
-    hipLaunchKernelGGL(reduce_slabs_epi_kernel, dim3((N + 63) / 64, (M + 63) / 64), dim3(NT), 0, s, slabs, n_slabs, stride, M, N, C, ldc, bias,
-                       relu, relu_src, ld_relu, colsum_part);
+    CODAE_REQUIRE(act == CODAE_ACT_NONE || act_p != nullptr, "reduce_slabs_epi: activation without parameters");
+    if (act != CODAE_ACT_NONE)
+        hipLaunchKernelGGL(reduce_slabs_epi_kernel<true>, dim3((N + 63) / 64, (M + 63) / 64), dim3(NT), 0, s, slabs, n_slabs, stride, M, N, C, ldc,
+                           bias, relu, relu_src, ld_relu, colsum_part, act, act_p[0], act_p[1], act_p[2]);
+    else
+        hipLaunchKernelGGL(reduce_slabs_epi_kernel<false>, dim3((N + 63) / 64, (M + 63) / 64), dim3(NT), 0, s, slabs, n_slabs, stride, M, N, C, ldc,
+                           bias, relu, relu_src, ld_relu, colsum_part, 0, 0.f, 0.f, 0.f);
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;
 }

@@ -4,6 +4,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <cmath>
 #include <vector>
 
 #include "codae_common.h"
@@ -73,7 +74,9 @@ struct codae_engine {
     // the GEMM that reads the buffer walks whole 64-deep tiles) with ZERO pad columns - allocated zeroed, never written - so that
     // whatever the weight operand holds past a row's real width (the head of its next row) is multiplied by 0.  fp32: the width.
     std::vector<int> in_ld, out_ld;
-    std::vector<uint8_t> relu;
+    std::vector<uint8_t> relu;       // 1: ReLU after layer l (the ReLU code: 1-bit masks, clamp_below, the chain kernel)
+    std::vector<uint8_t> act;        // CODAE_ACT_* after layer l when it is neither NONE nor RELU (the generic-activation kernels), else 0
+    std::vector<float> act_p;        // [L][3] its parameters
     int max_batch = 0, max_rows = 0;  // max_rows = max_batch rounded up to 64
     int prec = CODAE_PREC_F32;
     std::vector<int64_t> w_off, b_off;
@@ -475,6 +478,13 @@ int run_wgrad_deferred(const codae_engine* e, const codae_buffers* b, int rows, 
     return gemm_bf16_pipe_grouped(grp, s);
 }
 
+// layer l's activation when it is not ReLU / none (those keep the `relu` flag and its kernels)
+template <typename G>
+void set_act(G& g, const codae_engine* e, int l) {
+    g.act = e->act[l];
+    for (int k = 0; k < 3; ++k) g.act_p[k] = e->act_p[3 * l + k];
+}
+
 // Exact-fp32 GEMM of a launch too small to fill the chip (forward / data gradient of a small batch): K split over
 // workgroups into fp32 slabs (slab slot 2: the caller's stream), then the reduce that applies the GEMM's epilogue.  Same
 // fp32 arithmetic in another summation order.  3 x 512 at batch 128, whole parity-mode step: 3.09 -> see DESIGN.md.
@@ -491,9 +501,11 @@ int gemm_f32_small(const codae_engine* e, const codae_buffers* b, const GemmF32&
     float* slab = reinterpret_cast<float*>(reinterpret_cast<char*>(b->slabs) + 2 * e->slab_bytes);
     GemmF32 p = g;
     p.C = slab; p.ldc = g.N; p.bias = nullptr; p.relu = 0; p.relu_src = nullptr; p.ld_relu = 0; p.colsum_part = nullptr; p.split_k = S;
+    p.act = CODAE_ACT_NONE;
     int rc = gemm_f32(p, s);
     if (rc) return rc;
-    return launch_reduce_slabs_epi(slab, S, (int64_t)g.M * g.N, g.M, g.N, g.C, g.ldc, g.bias, g.relu, g.relu_src, g.ld_relu, g.colsum_part, s);
+    return launch_reduce_slabs_epi(slab, S, (int64_t)g.M * g.N, g.M, g.N, g.C, g.ldc, g.bias, g.relu, g.relu_src, g.ld_relu, g.colsum_part, s,
+                                   g.act, g.act_p);
 }
 
 // y = act(x W^T + b) for layer l
@@ -509,6 +521,7 @@ int run_linear(const codae_engine* e, const codae_buffers* b, int l, const void*
         g.C = y; g.ldc = y_f32 ? N : e->out_ld[l]; g.c_f32 = y_f32 ? 1 : 0;
         g.M = rows; g.N = N; g.K = e->in_ld[l];
         g.bias = b->params + e->b_off[l]; g.relu = e->relu[l];
+        set_act(g, e, l);
         g.split_k = 1;
         if (!y_f32 && l + 1 < e->L && e->bits_off[l + 1] >= 0 && e->relu[l] && y == act_ptr(e, b, l + 1) && gemm_bf16_takes_relu_bits(rows, N)) {
             g.relu_bits_out = reinterpret_cast<uint8_t*>(b->acts) + e->bits_off[l + 1];
@@ -526,6 +539,7 @@ int run_linear(const codae_engine* e, const codae_buffers* b, int l, const void*
     g.C = reinterpret_cast<float*>(y); g.ldc = N;
     g.M = rows; g.N = N; g.K = K;
     g.bias = b->params + e->b_off[l]; g.relu = e->relu[l];
+    set_act(g, e, l);
     return gemm_f32_small(e, b, g, s);
 }
 
@@ -604,7 +618,11 @@ int run_dgrad(const codae_engine* e, const codae_buffers* b, int l, int rows, fl
             g.C = dx_f32; g.c_f32 = 1;
         } else {
             g.C = dact_ptr(e, b, l - 1); g.c_f32 = 0; g.ldc = e->out_ld[l - 1];
-            if (e->relu[l - 1]) {
+            if (e->act[l - 1] != CODAE_ACT_NONE) {
+                // another activation than ReLU: its derivative from the saved activation (no 1-bit masks for these layers)
+                g.relu_src = reinterpret_cast<const bf16_t*>(act_ptr(e, b, l)); g.ld_relu = e->in_ld[l];
+                set_act(g, e, l - 1);
+            } else if (e->relu[l - 1]) {
                 g.relu_src = reinterpret_cast<const bf16_t*>(act_ptr(e, b, l)); g.ld_relu = e->in_ld[l];
                 // (the forward launch that wrote act[l] had this output shape: rows x in[l]; same predicate on both sides)
                 if (e->bits_off[l] >= 0 && gemm_bf16_takes_relu_bits(rows, K)) {
@@ -630,7 +648,10 @@ int run_dgrad(const codae_engine* e, const codae_buffers* b, int l, int rows, fl
         g.C = dx_f32;
     } else {
         g.C = reinterpret_cast<float*>(dact_ptr(e, b, l - 1));
-        if (e->relu[l - 1]) { g.relu_src = reinterpret_cast<const float*>(act_ptr(e, b, l)); g.ld_relu = K; }
+        if (e->relu[l - 1] || e->act[l - 1] != CODAE_ACT_NONE) {
+            g.relu_src = reinterpret_cast<const float*>(act_ptr(e, b, l)); g.ld_relu = K;
+            set_act(g, e, l - 1);
+        }
         g.colsum_part = part_ptr(e, b, l - 1);
         e->parts_pending[l - 1] = gemm_f32_colsum_rows(rows);
     }
@@ -821,6 +842,25 @@ int codae_create(const codae_spec* spec, codae_handle* out) {
             }
         }
     }
+    if (spec->act_kind != nullptr) {
+        for (int l = 0; l < spec->n_layers; ++l) {
+            const int kind = spec->act_kind[l];
+            const float* p = spec->act_param ? spec->act_param + 3 * l : nullptr;
+            CODAE_REQUIRE(kind >= CODAE_ACT_NONE && kind <= CODAE_ACT_HARDSIGMOID, "codae_create: layer %d: unknown activation kind %d", l, kind);
+            CODAE_REQUIRE(l + 1 < spec->n_layers || kind == CODAE_ACT_NONE || kind == CODAE_ACT_RELU,
+                          "codae_create: the last layer takes no activation other than ReLU (kind %d)", kind);
+            const bool needs_p = kind == CODAE_ACT_LEAKY || kind == CODAE_ACT_ELU || kind == CODAE_ACT_SOFTPLUS;
+            CODAE_REQUIRE(!needs_p || p != nullptr, "codae_create: layer %d: activation kind %d needs act_param", l, kind);
+            if (kind == CODAE_ACT_LEAKY)
+                CODAE_REQUIRE(p[0] >= 0.f && std::isfinite(p[0]), "codae_create: layer %d: LeakyReLU slope %g (need >= 0)", l, p[0]);
+            if (kind == CODAE_ACT_ELU)
+                CODAE_REQUIRE(p[0] > 0.f && p[1] > 0.f && p[2] > 0.f && std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]),
+                              "codae_create: layer %d: ELU parameters scale %g alpha %g 1/beta %g (need all > 0)", l, p[0], p[1], p[2]);
+            if (kind == CODAE_ACT_SOFTPLUS)
+                CODAE_REQUIRE(p[0] > 0.f && std::isfinite(p[0]) && !std::isnan(p[1]),
+                              "codae_create: layer %d: Softplus beta %g threshold %g (need beta > 0)", l, p[0], p[1]);
+        }
+    }
     env_reload();                 // the one place (besides library load / codae_reload_env) the CODAE_* variables are read
     codae_engine* e = new codae_engine();
     e->cfg = env();
@@ -832,7 +872,10 @@ int codae_create(const codae_spec* spec, codae_handle* out) {
     for (int l = 0; l < e->L; ++l) {
         e->in.push_back(spec->in_features[l]);
         e->out.push_back(spec->out_features[l]);
-        e->relu.push_back(spec->relu[l] ? 1 : 0);
+        const int kind = spec->act_kind ? spec->act_kind[l] : (spec->relu[l] ? CODAE_ACT_RELU : CODAE_ACT_NONE);
+        e->relu.push_back(kind == CODAE_ACT_RELU ? 1 : 0);
+        e->act.push_back(kind == CODAE_ACT_RELU ? CODAE_ACT_NONE : (uint8_t)kind);
+        for (int k = 0; k < 3; ++k) e->act_p.push_back(spec->act_kind && spec->act_param ? spec->act_param[3 * l + k] : 0.f);
         e->in_ld.push_back(e->prec == CODAE_PREC_BF16 ? (int)round_up(e->in[l], 64) : e->in[l]);
         e->out_ld.push_back(e->prec == CODAE_PREC_BF16 ? (int)round_up(e->out[l], 64) : e->out[l]);
         e->w_off.push_back(off);
@@ -878,7 +921,10 @@ int codae_create(const codae_spec* spec, codae_handle* out) {
                 return CODAE_E_UNSUPPORTED;
             }
     }
-    e->chain_ok = e->prec == CODAE_PREC_BF16 && !e->cfg.no_chain && e->L + 1 <= CODAE_MAX_DACT &&
+    bool generic_act = false;
+    for (int l = 0; l < e->L; ++l) generic_act = generic_act || e->act[l] != CODAE_ACT_NONE;
+    // the persistent chain knows ReLU only: a stack with another activation runs the per-layer launches
+    e->chain_ok = e->prec == CODAE_PREC_BF16 && !e->cfg.no_chain && !generic_act && e->L + 1 <= CODAE_MAX_DACT &&
                   chain_supported(e->L, e->in.data(), e->out.data()) && e->in[0] == e->out[e->L - 1];
     // partial column-sum rows per layer: a producer writes at most one row per 64 batch rows (exact-fp32 GEMM, dense
     // colsum), the stand-alone loss kernel of the last layer one per 32, the persistent chain one per 16
@@ -1535,6 +1581,76 @@ int codae_dgrad_bf16(const void* dy, const void* W, const void* relu_src, void* 
     g.C = dx; g.ldc = K; g.c_f32 = 0; g.M = M; g.N = K; g.K = N;
     g.relu_src = reinterpret_cast<const bf16_t*>(relu_src); g.ld_relu = K;
     g.colsum_part = db_prev ? db_ws : nullptr; g.split_k = 1;
+    int rc = gemm_bf16(g, (hipStream_t)stream);
+    if (rc || db_prev == nullptr) return rc;
+    BiasFinishJobs jobs;
+    jobs.n = 1; jobs.parts[0] = db_ws; jobs.out[0] = db_prev; jobs.rows[0] = gemm_bf16_colsum_rows(g); jobs.cols[0] = K;
+    jobs.col_begin[0] = 0; jobs.col_begin[1] = K;
+    return launch_bias_finish(jobs, nullptr, (hipStream_t)stream);
+}
+
+static void act_args(GemmF32& g, int32_t act, float p0, float p1, float p2) {
+    g.act = act; g.act_p[0] = p0; g.act_p[1] = p1; g.act_p[2] = p2;
+}
+static void act_args(GemmBf16& g, int32_t act, float p0, float p1, float p2) {
+    g.act = act; g.act_p[0] = p0; g.act_p[1] = p1; g.act_p[2] = p2;
+}
+
+int codae_linear_act_f32(const float* x, const float* W, const float* bias, float* y, int32_t M, int32_t N, int32_t K, int32_t act,
+                         float p0, float p1, float p2, void* stream) {
+    CODAE_REQUIRE(act >= CODAE_ACT_NONE && act <= CODAE_ACT_HARDSIGMOID, "codae_linear_act_f32: activation kind %d", act);
+    if (act == CODAE_ACT_NONE) return codae_linear_f32(x, W, bias, y, M, N, K, 0, stream);
+    CODAE_REQUIRE(x && W && y, "codae_linear_act_f32: null operand");
+    GemmF32 g{};
+    g.A = x; g.a_rs = K; g.a_ks = 1;
+    g.B = W; g.b_rs = K; g.b_ks = 1;
+    g.C = y; g.ldc = N; g.M = M; g.N = N; g.K = K;
+    g.bias = bias;
+    act_args(g, act, p0, p1, p2);
+    return gemm_f32(g, (hipStream_t)stream);
+}
+
+int codae_dgrad_act_f32(const float* dy, const float* W, const float* act_src, float* dx, int32_t M, int32_t N, int32_t K, int32_t act,
+                        float p0, float p1, float p2, void* stream) {
+    CODAE_REQUIRE(act >= CODAE_ACT_NONE && act <= CODAE_ACT_HARDSIGMOID, "codae_dgrad_act_f32: activation kind %d", act);
+    if (act == CODAE_ACT_NONE || act_src == nullptr) return codae_dgrad_f32(dy, W, nullptr, dx, M, N, K, stream);
+    CODAE_REQUIRE(dy && W && dx, "codae_dgrad_act_f32: null operand");
+    GemmF32 g{};
+    g.A = dy; g.a_rs = N; g.a_ks = 1;
+    g.B = W; g.b_rs = 1; g.b_ks = K;
+    g.C = dx; g.ldc = K; g.M = M; g.N = K; g.K = N;
+    g.relu_src = act_src; g.ld_relu = K;
+    act_args(g, act, p0, p1, p2);
+    return gemm_f32(g, (hipStream_t)stream);
+}
+
+int codae_linear_act_bf16(const void* x, const void* W, const float* bias, void* y, int32_t y_f32, int32_t M, int32_t N, int32_t K,
+                          int32_t act, float p0, float p1, float p2, void* stream) {
+    CODAE_REQUIRE(act >= CODAE_ACT_NONE && act <= CODAE_ACT_HARDSIGMOID, "codae_linear_act_bf16: activation kind %d", act);
+    if (act == CODAE_ACT_NONE) return codae_linear_bf16(x, W, bias, y, y_f32, M, N, K, 0, stream);
+    CODAE_REQUIRE(x && W && y, "codae_linear_act_bf16: null operand");
+    GemmBf16 g{};
+    g.A = reinterpret_cast<const bf16_t*>(x); g.lda = K; g.a_mode = OP_KC;
+    g.B = reinterpret_cast<const bf16_t*>(W); g.ldb = K; g.b_mode = OP_KC;
+    g.C = y; g.ldc = N; g.c_f32 = y_f32; g.M = M; g.N = N; g.K = K;
+    g.bias = bias; g.split_k = 1;
+    act_args(g, act, p0, p1, p2);
+    return gemm_bf16(g, (hipStream_t)stream);
+}
+
+int codae_dgrad_act_bf16(const void* dy, const void* W, const void* act_src, void* dx, float* db_prev, float* db_ws, int32_t M,
+                         int32_t N, int32_t K, int32_t act, float p0, float p1, float p2, void* stream) {
+    CODAE_REQUIRE(act >= CODAE_ACT_NONE && act <= CODAE_ACT_HARDSIGMOID, "codae_dgrad_act_bf16: activation kind %d", act);
+    if (act == CODAE_ACT_NONE || act_src == nullptr) return codae_dgrad_bf16(dy, W, nullptr, dx, db_prev, db_ws, M, N, K, stream);
+    CODAE_REQUIRE(dy && W && dx, "codae_dgrad_act_bf16: null operand");
+    CODAE_REQUIRE(db_prev == nullptr || db_ws != nullptr, "codae_dgrad_act_bf16: db_prev needs the db_ws scratch");
+    GemmBf16 g{};
+    g.A = reinterpret_cast<const bf16_t*>(dy); g.lda = N; g.a_mode = OP_KC;
+    g.B = reinterpret_cast<const bf16_t*>(W); g.ldb = K; g.b_mode = OP_KS;
+    g.C = dx; g.ldc = K; g.c_f32 = 0; g.M = M; g.N = K; g.K = N;
+    g.relu_src = reinterpret_cast<const bf16_t*>(act_src); g.ld_relu = K;
+    g.colsum_part = db_prev ? db_ws : nullptr; g.split_k = 1;
+    act_args(g, act, p0, p1, p2);
     int rc = gemm_bf16(g, (hipStream_t)stream);
     if (rc || db_prev == nullptr) return rc;
     BiasFinishJobs jobs;

@@ -164,10 +164,12 @@ __device__ __forceinline__ bf16x8 read_frag(const lds_char* tile, int t, int s, 
 // t + 3 in flight (stock batch 128 at io 1536, whole step: 0.58 ms with 2 stages, 0.43 with 4, 0.44 with 8), for launches
 // too small to fill the chip - a 128-row batch of a wide layer is 12 workgroups, each
 // walking its 24 K-tiles of COLD weights one memory latency at a time (27 us for 0.6 GFLOP with NS = 2).
-template <int BM, int BN, int WM, int WN, int A_MODE, int B_MODE, bool C_F32, bool LOSS, int NS = 2>
+// ACT: the generic-activation epilogues (GemmBf16::act); false: the ReLU / identity code.
+template <int BM, int BN, int WM, int WN, int A_MODE, int B_MODE, bool C_F32, bool LOSS, int NS = 2, bool ACT = false>
 __device__ __forceinline__ void gemm_bf16_tile(const GemmBf16& g, int tiles_n, int tiles_mn, int kt_total, int wg, int nwg,
                                                char* smem_raw) {
     static_assert(NS == 2 || (NS == 4 && !LOSS), "2 or 4 stages (the fused-loss epilogue keeps its row table behind 2)");
+    static_assert(!(ACT && LOSS), "the fused-loss layer has no activation");
     constexpr int NW = WM * WN;
     constexpr int TM = BM / WM / 16, TN = BN / WN / 16;
     constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128, BUF_BYTES = A_BYTES + B_BYTES;
@@ -477,8 +479,19 @@ __device__ __forceinline__ void gemm_bf16_tile(const GemmBf16& g, int tiles_n, i
 #pragma unroll
             for (int mt = 0; mt < TM; ++mt) {
                 const int il = (BM / WM) * wr + 16 * mt + li;
-                const float v0 = clamp_below(acc[mt][nt][0] + bj.x, floor_v), v1 = clamp_below(acc[mt][nt][1] + bj.y, floor_v);
-                const float v2 = clamp_below(acc[mt][nt][2] + bj.z, floor_v), v3 = clamp_below(acc[mt][nt][3] + bj.w, floor_v);
+                float v0, v1, v2, v3;
+                if constexpr (ACT) {
+                    // (data-gradient form: relu_src set, no bias - the factor comes in the write-out pass)
+                    const bool fwd = g.relu_src == nullptr;
+                    v0 = acc[mt][nt][0] + bj.x; v1 = acc[mt][nt][1] + bj.y; v2 = acc[mt][nt][2] + bj.z; v3 = acc[mt][nt][3] + bj.w;
+                    if (fwd) {
+                        v0 = act_fwd(g.act, g.act_p, v0); v1 = act_fwd(g.act, g.act_p, v1);
+                        v2 = act_fwd(g.act, g.act_p, v2); v3 = act_fwd(g.act, g.act_p, v3);
+                    }
+                } else {
+                    v0 = clamp_below(acc[mt][nt][0] + bj.x, floor_v); v1 = clamp_below(acc[mt][nt][1] + bj.y, floor_v);
+                    v2 = clamp_below(acc[mt][nt][2] + bj.z, floor_v); v3 = clamp_below(acc[mt][nt][3] + bj.w, floor_v);
+                }
                 u32x2 o;
                 o[0] = pack_bf16x2(v0, v1);
                 o[1] = pack_bf16x2(v2, v3);
@@ -498,7 +511,11 @@ __device__ __forceinline__ void gemm_bf16_tile(const GemmBf16& g, int tiles_n, i
                 if (i >= g.M) break;
                 const u32x4 lv = *reinterpret_cast<const __attribute__((address_space(3))) u32x4*>(smem + r * PITCH + c * 16);
                 uint4 v = make_uint4(lv[0], lv[1], lv[2], lv[3]);
-                if (g.relu_src != nullptr) {
+                if (ACT && g.relu_src != nullptr) {
+                    const uint4 h = *reinterpret_cast<const uint4*>(g.relu_src + (int64_t)i * g.ld_relu + j);
+                    v.x = act_dgrad_bf16x2(g.act, g.act_p, v.x, h.x); v.y = act_dgrad_bf16x2(g.act, g.act_p, v.y, h.y);
+                    v.z = act_dgrad_bf16x2(g.act, g.act_p, v.z, h.z); v.w = act_dgrad_bf16x2(g.act, g.act_p, v.w, h.w);
+                } else if (g.relu_src != nullptr) {
                     const uint4 h = *reinterpret_cast<const uint4*>(g.relu_src + (int64_t)i * g.ld_relu + j);
                     // keep where the saved activation is > 0 (sign clear, magnitude non-zero), per bf16 half
                     auto keep = [](uint32_t val, uint32_t hh) -> uint32_t {
@@ -562,7 +579,7 @@ __device__ __forceinline__ void gemm_bf16_tile(const GemmBf16& g, int tiles_n, i
                         const int il = (BM / WM) * wr + 16 * mt + li - hh * HR;
                         f32x4 v = acc[mt][nt];
                         v[0] += bj.x; v[1] += bj.y; v[2] += bj.z; v[3] += bj.w;
-                        if (g.relu) {
+                        if (!ACT && g.relu) {          // (ACT: applied in the write-out pass below)
                             v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f);
                         }
                         *reinterpret_cast<__attribute__((address_space(3))) f32x4*>(smem + il * PITCH + jl * 4) = v;
@@ -574,7 +591,11 @@ __device__ __forceinline__ void gemm_bf16_tile(const GemmBf16& g, int tiles_n, i
                 for (int r = rl; r < HR; r += RL) {
                     const int i = i0 + hh * HR + r;
                     if (i >= g.M) break;
-                    const f32x4 v = *reinterpret_cast<const __attribute__((address_space(3))) f32x4*>(smem + r * PITCH + c * 16);
+                    f32x4 v = *reinterpret_cast<const __attribute__((address_space(3))) f32x4*>(smem + r * PITCH + c * 16);
+                    if constexpr (ACT) {
+                        v[0] = act_fwd(g.act, g.act_p, v[0]); v[1] = act_fwd(g.act, g.act_p, v[1]);
+                        v[2] = act_fwd(g.act, g.act_p, v[2]); v[3] = act_fwd(g.act, g.act_p, v[3]);
+                    }
                     *reinterpret_cast<float4*>(Cf + (int64_t)i * g.ldc + j) = make_float4(v[0], v[1], v[2], v[3]);
                     sq += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
                 }
@@ -596,13 +617,13 @@ __device__ __forceinline__ void gemm_bf16_tile(const GemmBf16& g, int tiles_n, i
     }
 }
 
-template <int BM, int BN, int WM, int WN, int A_MODE, int B_MODE, bool C_F32, bool LOSS = false, int NS = 2>
+template <int BM, int BN, int WM, int WN, int A_MODE, int B_MODE, bool C_F32, bool LOSS = false, int NS = 2, bool ACT = false>
 __global__ __launch_bounds__(64 * WM * WN, (64 * WM * WN) / 256 * ((NS * (BM + BN) * 128 <= 80 * 1024) ? 2 : 1))
 void gemm_bf16_kernel(GemmBf16 g, int tiles_n, int tiles_mn, int kt_total) {
     // LOSS: + {dataset row, mask id} of the tile's rows, fetched once at entry (two dependent loads that
     // would otherwise sit in front of every row of the epilogue)
     __shared__ __attribute__((aligned(16))) char smem_raw[NS * (BM + BN) * 128 + (LOSS ? BM * 8 : 0)];
-    gemm_bf16_tile<BM, BN, WM, WN, A_MODE, B_MODE, C_F32, LOSS, NS>(g, tiles_n, tiles_mn, kt_total, blockIdx.x, gridDim.x, smem_raw);
+    gemm_bf16_tile<BM, BN, WM, WN, A_MODE, B_MODE, C_F32, LOSS, NS, ACT>(g, tiles_n, tiles_mn, kt_total, blockIdx.x, gridDim.x, smem_raw);
 }
 
 // Several weight-gradient GEMMs (k-strided operands, fp32 output) in one launch: workgroup -> (GEMM, tile) by the prefix
@@ -625,6 +646,22 @@ int launch_cfg(const GemmBf16& g, hipStream_t s) {
     const int64_t nwg = (int64_t)tiles_m * tiles_n * g.split_k;
     CODAE_REQUIRE(nwg < (1 << 30), "gemm_bf16: grid too large");
     dim3 grid((unsigned)nwg), block(64 * WM * WN);
+    if (g.act != CODAE_ACT_NONE) {
+        // the generic-activation instantiations: forward / data-gradient forms only (gemm_bf16 refused the rest)
+#define LAUNCH_ACT(BMODE, CF, NS) \
+    hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, OP_KC, BMODE, CF, false, NS, true>), grid, block, 0, s, g, tiles_n, tiles_m * tiles_n, kt_total)
+        const bool deep = !g.c_f32 && nwg <= 256 && kt_total >= 6 && !env().no_deep_small && env().small_stages >= 4;
+        if (g.b_mode == OP_KC) {
+            if (g.c_f32) LAUNCH_ACT(OP_KC, true, 2);
+            else if (deep) LAUNCH_ACT(OP_KC, false, 4);
+            else LAUNCH_ACT(OP_KC, false, 2);
+        } else {
+            LAUNCH_ACT(OP_KS, false, 2);
+        }
+#undef LAUNCH_ACT
+        CODAE_LAUNCH_CHECK();
+        return CODAE_OK;
+    }
 #define LAUNCH(AM, BMODE, CF) \
     hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, AM, BMODE, CF>), grid, block, 0, s, g, tiles_n, tiles_m * tiles_n, kt_total)
     if (g.loss.enabled) {
@@ -746,7 +783,7 @@ bool gemm_bf16_takes_relu_bits(int M, int N) {
 // rows of g.colsum_part the launch gemm_bf16(g) makes will write: one per tile along M of the tile it picks
 int gemm_bf16_colsum_rows(const GemmBf16& g) {
     const int t = gemm_bf16_tile_big(g.M, g.N, g.loss.enabled ? 1 : g.split_k, g.b_mode == OP_KS || g.c_f32);
-    const int bm = t ? 256 : (small_tile_64(g) ? 64 : 128);
+    const int bm = (t && g.act == CODAE_ACT_NONE) ? 256 : (small_tile_64(g) ? 64 : 128);   // (activations: the one-barrier tiles)
     return (g.M + bm - 1) / bm;
 }
 
@@ -769,6 +806,12 @@ int gemm_bf16(const GemmBf16& g, hipStream_t s) {
                   "gemm_bf16: operands must be 16-byte aligned");
     CODAE_REQUIRE(g.split_k <= g.K / BK, "gemm_bf16: split_k %d > k tiles %d", g.split_k, g.K / BK);
     CODAE_REQUIRE(!g.c_f32 || (g.relu_src == nullptr && g.colsum_part == nullptr), "gemm_bf16: ReLU mask / column sums need bf16 output");
+    if (g.act != CODAE_ACT_NONE) {
+        CODAE_REQUIRE(!g.loss.enabled && g.a_mode == OP_KC && g.split_k == 1 && g.relu_bits == nullptr && g.relu_bits_out == nullptr &&
+                          !(g.c_f32 && g.b_mode == OP_KS) && g.dbg == 0,
+                      "gemm_bf16: an activation needs the forward / data-gradient form (k-contiguous A, unsplit, no 1-bit masks, "
+                      "no fused loss, k-strided B only with bf16 output)");
+    }
     if (g.loss.enabled) {
         CODAE_REQUIRE(g.a_mode == OP_KC && g.b_mode == OP_KC && !g.c_f32 && g.split_k == 1 && !g.relu && !g.relu_src,
                       "gemm_bf16: fused loss only on the plain forward form");
@@ -778,13 +821,16 @@ int gemm_bf16(const GemmBf16& g, hipStream_t s) {
                       "gemm_bf16: mask table must be 8-byte aligned");
         CODAE_REQUIRE((reinterpret_cast<uintptr_t>(g.loss.data) & 15) == 0, "gemm_bf16: dataset must be 16-byte aligned");
     }
-    if (env().gemm_dbg) { GemmBf16 g2 = g; g2.dbg = env().gemm_dbg; return gemm_bf16_pipe(g2, 0, s); }
+    if (env().gemm_dbg && g.act == CODAE_ACT_NONE) { GemmBf16 g2 = g; g2.dbg = env().gemm_dbg; return gemm_bf16_pipe(g2, 0, s); }
     if (g.loss.enabled) {
         const int t = gemm_bf16_tile_big(g.M, g.N, 1);
         if (t) return gemm_bf16_pipe(g, t >= 6 ? 6 : 1, s);       // 8-wave pipelined kernel, loss from the accumulators
         if (small_tile_64(g)) return launch_cfg<64, 64, 2, 2>(g, s);
         return launch_cfg<128, 128, 2, 2>(g, s);
     }
+    // generic activations: the one-barrier kernel on 64 x 64 / 128 x 128 tiles only (the pipelined kernels keep their ReLU / identity
+    // epilogues; DESIGN.md section 6, activations)
+    if (g.act != CODAE_ACT_NONE) return small_tile_64(g) ? launch_cfg<64, 64, 2, 2>(g, s) : launch_cfg<128, 128, 2, 2>(g, s);
     const int path = bf16_path(g);
     if (path > 0) return gemm_bf16_pipe(g, path, s);
     if (path == -64) return launch_cfg<64, 64, 2, 2>(g, s);

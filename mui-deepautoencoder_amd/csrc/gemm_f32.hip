@@ -78,7 +78,8 @@ __device__ __forceinline__ void store_tile(float* S, const float (&reg)[16], int
     }
 }
 
-template <bool A_KC, bool B_KC>
+// ACT: the generic-activation epilogue (GemmF32::act); false: the ReLU / identity code
+template <bool A_KC, bool B_KC, bool ACT = false>
 // (Three workgroups per CU - __launch_bounds__(NT, 3): 152 registers, no spills, 768 workgroups in one round - measured
 //  no faster than two: 349 vs 346 us for the 8192 x 1536 x 1536 forward form.)
 __global__ __launch_bounds__(NT) void gemm_f32_kernel(GemmF32 g, bool a_vec, bool b_vec) {
@@ -171,6 +172,37 @@ __global__ __launch_bounds__(NT) void gemm_f32_kernel(GemmF32 g, bool a_vec, boo
     }
 
     // epilogue: D layout of the 32x32 MFMA: col = lane & 31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
+    if constexpr (ACT) {
+        // the same loop once per activation kind (a switch per element made it too large to unroll: accumulators in scratch)
+        act_dispatch(g.act, [&](auto kc) {
+            constexpr int KIND = decltype(kc)::value;
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni) {
+                const int j = j0 + 64 * wc + 32 * ni + li;
+                const float bj = (g.bias != nullptr && j < g.N) ? g.bias[j] : 0.f;
+                float csum = 0.f;
+#pragma unroll
+                for (int mi = 0; mi < 2; ++mi) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int i = i0 + 64 * wr + 32 * mi + (r & 3) + 8 * (r >> 2) + 4 * kh;
+                        if (i < g.M && j < g.N) {
+                            float v = acc[mi][ni][r] + bj;
+                            if (g.relu_src != nullptr) v *= act_dy_from_y(KIND, g.act_p, g.relu_src[(int64_t)i * g.ld_relu + j]);
+                            else v = act_fwd(KIND, g.act_p, v);
+                            g.C[(int64_t)i * g.ldc + j] = v;
+                            csum += v;
+                        }
+                    }
+                }
+                if (g.colsum_part != nullptr) {
+                    csum += __shfl_xor(csum, 32);
+                    if (kh == 0 && j < g.N && i0 + 64 * wr < g.M) g.colsum_part[(int64_t)(2 * tile_m + wr) * g.N + j] = csum;
+                }
+            }
+        });
+        return;
+    }
 #pragma unroll
     for (int ni = 0; ni < 2; ++ni) {
         const int j = j0 + 64 * wc + 32 * ni + li;
@@ -217,11 +249,20 @@ int gemm_f32(const GemmF32& g, hipStream_t s) {
     // batch 8192: 6.0 against 10.4 (tools/abl/f32_gemm_threshold.sh); CODAE_F32_GEMM=native keeps everything here
     if (env().f32_gemm != 1 && gemm_f32x3_takes(g)) return gemm_f32x3(g, s);
     CODAE_REQUIRE(split == 1 || (g.bias == nullptr && !g.relu && g.relu_src == nullptr && g.colsum_part == nullptr && g.m_dev == nullptr &&
-                                 split <= (g.K + BK - 1) / BK),
+                                 g.act == CODAE_ACT_NONE && split <= (g.K + BK - 1) / BK),
                   "gemm_f32: split-K writes plain partial products (no epilogue terms), at most one range per K-tile");
     dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, split);
     CODAE_REQUIRE(grid.y <= 65535, "gemm_f32: M=%d too large", g.M);
-    if (a_kc && b_kc)
+    if (g.act != CODAE_ACT_NONE) {
+        if (a_kc && b_kc)
+            hipLaunchKernelGGL((gemm_f32_kernel<true, true, true>), grid, dim3(NT), 0, s, g, a_vec, b_vec);
+        else if (a_kc && !b_kc)
+            hipLaunchKernelGGL((gemm_f32_kernel<true, false, true>), grid, dim3(NT), 0, s, g, a_vec, b_vec);
+        else {
+            set_error("gemm_f32: an activation needs a k-contiguous A operand (forward / data-gradient form)");
+            return CODAE_E_UNSUPPORTED;
+        }
+    } else if (a_kc && b_kc)
         hipLaunchKernelGGL((gemm_f32_kernel<true, true>), grid, dim3(NT), 0, s, g, a_vec, b_vec);
     else if (a_kc && !b_kc)
         hipLaunchKernelGGL((gemm_f32_kernel<true, false>), grid, dim3(NT), 0, s, g, a_vec, b_vec);

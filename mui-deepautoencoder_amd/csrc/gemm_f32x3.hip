@@ -183,7 +183,8 @@ __device__ __forceinline__ int x3_xcd_remap(int id, int nwg) {
 }
 
 // one output tile (split-K range z of it) of one GEMM: the whole kernel body, shared by the plain kernel and the grouped one
-template <bool A_KC, bool B_KC>
+// ACT: the generic-activation epilogue (GemmF32::act); false: the ReLU / identity code
+template <bool A_KC, bool B_KC, bool ACT = false>
 __device__ __forceinline__ void x3_tile(GemmF32 g, int tile_m, int tile_n, int z, char* smem_raw) {
     lds_c* smem = (lds_c*)smem_raw;
 
@@ -350,9 +351,28 @@ __device__ __forceinline__ void x3_tile(GemmF32 g, int tile_m, int tile_n, int z
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     v[r] = acc[mt][nt][r] + bj[r];
-                    if (g.relu) v[r] = fmaxf(v[r], 0.f);
+                    if constexpr (!ACT) {
+                        if (g.relu) v[r] = fmaxf(v[r], 0.f);
+                    }
                 }
-                if (g.relu_src != nullptr) {
+                if constexpr (ACT) {
+                    if (g.relu_src != nullptr) {
+                        const float* m = g.relu_src + (int64_t)i * g.ld_relu + j;
+                        float h[4];
+                        if (vec_r && j + 3 < g.N) {
+                            const float4 mv = *reinterpret_cast<const float4*>(m);
+                            h[0] = mv.x; h[1] = mv.y; h[2] = mv.z; h[3] = mv.w;
+                        } else {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) h[r] = j + r < g.N ? m[r] : 0.f;
+                        }
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) v[r] *= act_dy_from_y(g.act, g.act_p, h[r]);
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) v[r] = act_fwd(g.act, g.act_p, v[r]);
+                    }
+                } else if (g.relu_src != nullptr) {
                     const float* m = g.relu_src + (int64_t)i * g.ld_relu + j;
                     if (vec_r && j + 3 < g.N) {
                         const float4 mv = *reinterpret_cast<const float4*>(m);
@@ -393,13 +413,13 @@ __device__ __forceinline__ void x3_tile(GemmF32 g, int tile_m, int tile_n, int z
     }
 }
 
-template <bool A_KC, bool B_KC>
+template <bool A_KC, bool B_KC, bool ACT = false>
 __global__ __launch_bounds__(XT) void gemm_f32x3_kernel(GemmF32 g) {
     __shared__ __attribute__((aligned(16))) char smem_raw[2 * XBUF];
     const int tiles_n = gridDim.x, tiles_m = gridDim.y;
     int tile_m, tile_n;
     x3_tile_of(x3_xcd_remap(blockIdx.y * tiles_n + blockIdx.x, tiles_n * tiles_m), tiles_m, tiles_n, tile_m, tile_n);
-    x3_tile<A_KC, B_KC>(g, tile_m, tile_n, blockIdx.z, smem_raw);
+    x3_tile<A_KC, B_KC, ACT>(g, tile_m, tile_n, blockIdx.z, smem_raw);
 }
 
 // several GEMMs of the row-contiguous x row-contiguous form (the weight gradients of every layer of the stack: dW_l = dA_l^T act_l) in
@@ -437,11 +457,20 @@ int gemm_f32x3(const GemmF32& g, hipStream_t s) {
     const bool b_kc = (g.b_ks == 1);
     const int split = g.split_k > 1 ? g.split_k : 1;
     CODAE_REQUIRE(split == 1 || (g.bias == nullptr && !g.relu && g.relu_src == nullptr && g.colsum_part == nullptr && g.m_dev == nullptr &&
-                                 split <= g.K / XK),
+                                 g.act == CODAE_ACT_NONE && split <= g.K / XK),
                   "gemm_f32x3: split-K writes plain partial products (no epilogue terms), at most one range per K-tile");
     dim3 grid((g.N + XN - 1) / XN, (g.M + XM - 1) / XM, split);
     CODAE_REQUIRE(grid.y <= 65535, "gemm_f32x3: M=%d too large", g.M);
-    if (a_kc && b_kc)
+    if (g.act != CODAE_ACT_NONE) {
+        if (a_kc && b_kc)
+            hipLaunchKernelGGL((gemm_f32x3_kernel<true, true, true>), grid, dim3(XT), 0, s, g);
+        else if (a_kc && !b_kc)
+            hipLaunchKernelGGL((gemm_f32x3_kernel<true, false, true>), grid, dim3(XT), 0, s, g);
+        else {
+            set_error("gemm_f32x3: an activation needs a k-contiguous A operand (forward / data-gradient form)");
+            return CODAE_E_UNSUPPORTED;
+        }
+    } else if (a_kc && b_kc)
         hipLaunchKernelGGL((gemm_f32x3_kernel<true, true>), grid, dim3(XT), 0, s, g);
     else if (a_kc && !b_kc)
         hipLaunchKernelGGL((gemm_f32x3_kernel<true, false>), grid, dim3(XT), 0, s, g);
@@ -459,7 +488,7 @@ int gemm_f32x3_grouped(GemmF32Group& grp, hipStream_t s) {
     for (int j = 0; j < grp.n; ++j) {
         const GemmF32& g = grp.g[j];
         CODAE_REQUIRE(gemm_f32x3_takes(g) && g.a_rs == 1 && g.b_rs == 1 && g.split_k <= 1 && g.m_dev == nullptr && g.bias == nullptr && !g.relu &&
-                          g.relu_src == nullptr && g.colsum_part == nullptr,
+                          g.relu_src == nullptr && g.colsum_part == nullptr && g.act == CODAE_ACT_NONE,
                       "gemm_f32x3_grouped: GEMM %d (M=%d N=%d K=%d) is not a plain row-contiguous x row-contiguous product", j, g.M, g.N, g.K);
         grp.wg_begin[j] = total;
         total += ((g.M + XM - 1) / XM) * ((g.N + XN - 1) / XN);

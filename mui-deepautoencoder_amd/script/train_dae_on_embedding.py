@@ -97,12 +97,19 @@ def main():
         raise Exception("Error: io_size must be a multiple of embedding_size")
     enc, dec = linear_stack(io_size, mc["Z_SIZE"], mc["NB_INPUT_LAYER"], mc["NB_OUTPUT_LAYER"], mc["STEEP_LAYER_SIZE"], False)
     precision = args.precision or config.get("HIP", {}).get("PRECISION", "bf16")
+    # HIP: ACTIVATION: <torch.nn module name> (build-only key, like PRECISION): what follows each hidden Linear, built as
+    # the model classes build it (activation(True)); absent = ReLU
+    act_name = config.get("HIP", {}).get("ACTIVATION")
+    activation = getattr(torch.nn, act_name) if act_name else None
+    if act_name and not (isinstance(activation, type) and issubclass(activation, torch.nn.Module)):
+        raise HipError("HIP: ACTIVATION: %r is not a torch.nn module" % act_name)
     dataset.to(device)
 
     def build(prec):
         return HipEmbeddingTrainer(enc + dec, dataset.data, corrupter.mask_table_u8, corrupter.mask_to_use_i32,
                                    mc["LEARNING_RATE"], mc["WEIGHT_DECAY"], clip=1.0 if mc["TRUNK_GRAD"] else 0.0,
-                                   max_batch=mc["BATCH_SIZE"], precision=prec, device=device, distributed=world > 1)
+                                   max_batch=mc["BATCH_SIZE"], precision=prec, device=device, distributed=world > 1,
+                                   activation=activation)
     try:
         trainer = build(precision)
     except HipError as e:
@@ -113,7 +120,8 @@ def main():
     trainer.init_params(seed=int(torch.empty((), dtype=torch.int64).random_().item()) % (2 ** 31))
 
     display_info(config, dataset.nb_observation, {})
-    log.info("Linear stack: " + " | ".join("%d->%d%s" % (k, n, "+ReLU" if r else "") for k, n, r in enc + dec))
+    act_label = "+" + (activation(True).__class__.__name__ if activation is not None else "ReLU")
+    log.info("Linear stack: " + " | ".join("%d->%d%s" % (k, n, act_label if r else "") for k, n, r in enc + dec))
     book = {k: [] for k in ("ftl", "ptl", "fvl", "pvl", "rl")}
     ranking_loss = RankingLoss(dataset, validation_indices, device=device)
     epochs = args.epochs if args.epochs is not None else mc["EPOCH"]
