@@ -42,9 +42,10 @@ extern "C" {
  *   5: + codae_monitor_accumulate; codae_ranking_loss_batched takes val_group (rows of the validation inventory that are
  *      exact duplicates of each other) behind val_pos; + codae_dp_unique_id / _init / _destroy, codae_train_step_dp
  *   6: codae_spec.act_kind / act_param (appended), CODAE_ACT_*, codae_linear_act_f32 / _bf16, codae_dgrad_act_f32 / _bf16
+ *   7: + codae_topk_init / _merge / _finish, codae_complete_topk (new entries only; no layout change)
  * The binding must refuse a library whose codae_abi_version() differs and must check its own struct sizes against
  * codae_struct_sizes() at load (mui-deepautoencoder_amd/codae/hip/__init__.py does both). */
-#define CODAE_ABI_VERSION 6
+#define CODAE_ABI_VERSION 7
 
 enum {
     CODAE_OK = 0,
@@ -396,6 +397,39 @@ int codae_ranking_loss_batched(const float* pred, int32_t B, int32_t io, int32_t
 /* dst[c][j][:] = inventory[c][val_idx[j]][:]  (inventory [n_slots][n_obs][E]) */
 int codae_gather_inventory_rows(const float* inventory, int64_t n_obs, int32_t E, int32_t n_slots, const int32_t* val_idx,
                                 int32_t n_val, float* dst, void* stream);
+
+/* ---- complementarity inference: the k best inventory items for a blanked slot (README step IV) ------------------------
+ * Order: score descending, equal scores by ascending candidate position (-0 == +0); NaN scores are never selected; a row
+ * with fewer than k candidates ends in (-1, -inf).  1 <= k <= 256.  Deterministic: no float atomics, no host
+ * synchronisation, the same bits every run.
+ * Selection primitive (running top-k over chunks of a score matrix).  state: B * k (score, index) pairs, one uint64 key each
+ * (8 * B * k bytes), owned by the caller and carried across merge calls.
+ *   codae_topk_init    state <- empty
+ *   codae_topk_merge   rows r < rows of scores[rows][ld] (n columns = candidates col0 .. col0 + n - 1) merged into state row
+ *                      row_map[r] (NULL: r); skip_col [B] (NULL: none): the candidate (a global column, -1 = none) that row
+ *                      b never selects
+ *   codae_topk_finish  out_idx [B][k] = cand_row_id[position] (NULL: the position itself), out_score [B][k] */
+int codae_topk_init(void* state, int32_t B, int32_t k, void* stream);
+int codae_topk_merge(const float* scores, int64_t ld, int32_t rows, int32_t n, int32_t col0, int32_t k, const int32_t* row_map,
+                     const int32_t* skip_col, void* state, void* stream);
+int codae_topk_finish(const void* state, int32_t B, int32_t k, const int32_t* cand_row_id, int32_t* out_idx, float* out_score,
+                      void* stream);
+/* End to end, modelled on codae_ranking_loss_batched: query b is pred[b][c E : (c+1) E] for its slot c, either slot[b] (a
+ * slot outside [0, n_slots) gives an all (-1, -inf) row) or, with slot NULL, the blanked slot of mask_table[id_b], id_b =
+ * mask_id[b] or mask_to_use[row_idx[b] * nb_run + run] (as rank_prep).  Candidates of slot c: rows [0, cand_count[c]) of
+ * cand [n_slots][n_cand][E] (cand_count: HOST array [n_slots], NULL = n_cand each), cand_norm [n_slots][n_cand] their norms,
+ * cand_row_id [n_slots][n_cand] their dataset row ids (ascending within a slot).  Score = <q, v> / (max(|q|, 1e-8)
+ * max(|v|, 1e-8)).  exclude [B] (NULL: none): query b never gets the candidate cand_pos[c][exclude[b]] (cand_pos
+ * [n_slots][n_obs]: dataset row -> candidate position of slot c, or -1).  Per slot: the slot's queries compacted on the
+ * device, one fp32 GEMM (the parity engine's, CODAE_F32_GEMM applies) per chunk of candidates, one selection pass over it;
+ * then one finish pass.  Workspaces: work B * chunk floats; row_state 12 * B bytes; perm_ws (n_slots * B + n_slots) int32;
+ * q_ws B * E floats; topk_state 8 * B * k bytes.  out_idx [B][k] int32 dataset rows, out_score [B][k]. */
+int codae_complete_topk(const float* pred, int32_t B, int32_t io, int32_t n_slots, int32_t E, const int32_t* slot,
+                        const int32_t* row_idx, const int32_t* mask_id, const int32_t* mask_to_use, int32_t nb_run, int32_t run,
+                        const uint8_t* mask_table, const float* cand, const float* cand_norm, const int32_t* cand_row_id,
+                        int32_t n_cand, const int32_t* cand_count, const int32_t* exclude, const int32_t* cand_pos, int64_t n_obs,
+                        int32_t k, float* work, int32_t chunk, void* row_state, int32_t* perm_ws, float* q_ws, void* topk_state,
+                        int32_t* out_idx, float* out_score, void* stream);
 
 /* ---- GEMM primitives (exported for kernel-level parity tests / benchmarks) - */
 /* y[M][N] = act(x[M][K] . W[N][K]^T + b[N]), fp32 in / fp32 out (the parity engine's GEMM: CODAE_PREC_F32 above) */

@@ -9,7 +9,7 @@ _PUBLIC = {
     batching: ("collate_embedding", "simple_collate", "load_dataset_of_embeddings", "Normalizer",
                "get_mask_transformation"),
     corruption: ("Corrupter",),
-    criteria: ("get_rmse", "RankingLoss", "CombinedCriterion"),
+    criteria: ("get_rmse", "RankingLoss", "ComplementRetriever", "CombinedCriterion"),
 }
 __all__ = []
 for _module, _names in _PUBLIC.items():

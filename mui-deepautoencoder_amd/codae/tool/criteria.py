@@ -1,7 +1,8 @@
 """Criteria and metrics of `codae.tool` (codae/tool/metering.py:24-204 of the reference).
 
 CombinedCriterion (the abalone loss) and RankingLoss (the validation-only rank metric) keep the
-reference's call signatures and numerics.  With tensors on a HIP device they run as kernels of
+reference's call signatures and numerics.  ComplementRetriever answers the question the rank metric scores: the k
+inventory items closest to a reconstructed slot (codae_complete_topk).  With tensors on a HIP device they run as kernels of
 libcodae_hip.so (criteria.hip: codae_combined_loss_fwd_bwd / _full, codae_ranking_loss); with host
 tensors (which upstream also accepts) they are whole-tensor torch expressions, no per-sample loops.
 """
@@ -10,7 +11,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ..hip import check as _check, current_stream as _stream, lib as _hip_lib, ptr as _ptr
+from ..hip import HipError, check as _check, current_stream as _stream, lib as _hip_lib, ptr as _ptr
 from .batching import get_mask_transformation
 
 
@@ -153,6 +154,182 @@ class RankingLoss:
             rank = (own > s[:, self._val]).sum(dim=1)                            # strict > over validation ids
             total += float((1 - rank.double() / (len(self.validation_indices) - 1)).sum())
         return total
+
+
+TOPK_MAX = 256
+
+
+class ComplementRetriever:
+    """Complementarity inference (README step IV of the reference): the k inventory items closest to the model's
+    reconstruction of a blanked slot.
+
+    For query b with slot c the score of candidate v is <q, v> / (max(|q|, 1e-8) max(|v|, 1e-8)), q = prediction[b][cE:(c+1)E];
+    candidates are the rows of data_per_category[c] (all dataset rows, or the `candidates` subset).  Results are ordered by
+    score descending, equal scores by ascending dataset row id (-0 == +0); NaN scores are never returned; missing results
+    are (-1, -inf).  With `distinct`, rows of a slot's inventory that hold the same bytes are one item, represented by its
+    lowest dataset row.  Device tensors run codae_complete_topk (fp32 GEMM per candidate chunk + the HIP top-k selection
+    kernel, no host synchronisation); host tensors a whole-tensor torch form of the same contract."""
+
+    def __init__(self, dataset, device, candidates=None, distinct=True):
+        self.dataset = dataset
+        self.device = device
+        self.distinct = bool(distinct)
+        self.S, self.E = int(dataset.nb_used_category), int(dataset.embedding_size)
+        self.n_obs = int(dataset.data_per_category[0].shape[0])
+        if candidates is None:
+            self.candidates = None
+        else:
+            rows = torch.as_tensor(list(candidates) if not torch.is_tensor(candidates) else candidates, dtype=torch.long).reshape(-1)
+            if rows.numel() == 0 or int(rows.min()) < 0 or int(rows.max()) >= self.n_obs:
+                raise ValueError("candidates must be a non-empty list of dataset rows in [0, %d)" % self.n_obs)
+            self.candidates = torch.unique(rows)                  # sorted: candidate positions follow dataset row order
+        self._tables = {}
+
+    # ---- tables: built once per device ------------------------------------------------------------------------------
+    def _host_tables(self):
+        """(cand [S, n_cand, E] f32, count [S], row_id [S, n_cand] i32 (pad -1), pos [S, n_obs] i32: row -> candidate
+        position or -1), built on the host."""
+        t = self._tables.get("host")
+        if t is not None:
+            return t
+        S, E, n_obs = self.S, self.E, self.n_obs
+        rows = self.candidates if self.candidates is not None else torch.arange(n_obs)
+        per = []
+        for c in range(S):
+            X = self.dataset.data_per_category[c].detach().to("cpu", torch.float32)[rows].contiguous()
+            if self.distinct:
+                # identical bytes = one item (compared as int32 words, so -0 and +0 or two NaN payloads stay apart);
+                # the item is its lowest dataset row, items in ascending order of that row
+                _, inv = torch.unique(X.view(torch.int32), dim=0, return_inverse=True)
+                local = torch.arange(rows.numel())
+                first = torch.full((int(inv.max()) + 1,), rows.numel(), dtype=torch.long).scatter_reduce(0, inv, local, "amin")
+                first = first.sort()[0]                               # (rows ascend: lowest local index = lowest row id)
+                item = torch.empty_like(first)
+                item[inv[first]] = torch.arange(first.numel())        # group id -> item position
+                ids, item_of_row, Xc = rows[first], item[inv], X[first]
+            else:
+                ids, item_of_row, Xc = rows, torch.arange(rows.numel()), X
+            pos = torch.full((n_obs,), -1, dtype=torch.int32)
+            pos[rows] = item_of_row.to(torch.int32)
+            per.append((Xc, ids, pos))
+        n_cand = max(p[0].shape[0] for p in per)
+        cand = torch.zeros((S, n_cand, E), dtype=torch.float32)
+        row_id = torch.full((S, n_cand), -1, dtype=torch.int32)
+        for c, (Xc, ids, _) in enumerate(per):
+            cand[c, :Xc.shape[0]] = Xc
+            row_id[c, :ids.numel()] = ids.to(torch.int32)
+        t = (cand, [p[0].shape[0] for p in per], row_id, torch.stack([p[2] for p in per]).contiguous())
+        self._tables["host"] = t
+        return t
+
+    def _device_tables(self, dev):
+        t = self._tables.get(dev)
+        if t is None:
+            cand, count, row_id, pos = self._host_tables()
+            S, n_cand = cand.shape[0], cand.shape[1]
+            cand_d = cand.to(dev).contiguous()
+            norm = torch.empty((S, n_cand), dtype=torch.float32, device=dev)
+            with torch.cuda.device(dev):
+                _check(_hip_lib().codae_row_norms(_ptr(cand_d), S * n_cand, self.E, _ptr(norm), _stream()))
+            t = (cand_d, norm, (C.c_int32 * S)(*count), row_id.to(dev).contiguous(), pos.to(dev).contiguous())
+            self._tables[dev] = t
+        return t
+
+    # ---- arguments ----------------------------------------------------------------------------------------------------
+    def _check_args(self, prediction, slot, k, exclude, chunk):
+        if not torch.is_tensor(prediction) or prediction.dim() != 2 or prediction.shape[1] != self.S * self.E or prediction.shape[0] < 1:
+            raise HipError("topk: prediction must be a [B, %d] tensor" % (self.S * self.E))
+        B = prediction.shape[0]
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= TOPK_MAX:
+            raise HipError("topk: k must be an int in [1, %d], got %r" % (TOPK_MAX, k))
+        if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or int(chunk) < 1:
+            raise HipError("topk: chunk must be a positive int, got %r" % (chunk,))
+        if torch.is_tensor(slot):
+            if slot.dim() != 1 or slot.shape[0] != B or slot.dtype.is_floating_point or slot.dtype == torch.bool:
+                raise HipError("topk: slot tensor must be an integer [B] tensor")
+            if slot.device.type == "cpu" and slot.numel() and (int(slot.min()) < 0 or int(slot.max()) >= self.S):
+                raise HipError("topk: slot outside [0, %d)" % self.S)
+        elif isinstance(slot, bool) or not isinstance(slot, (int, np.integer)) or not 0 <= int(slot) < self.S:
+            raise HipError("topk: slot must be an int in [0, %d) or a [B] tensor, got %r" % (self.S, slot))
+        if exclude is not None:
+            if not torch.is_tensor(exclude) or exclude.dim() != 1 or exclude.shape[0] != B or exclude.dtype.is_floating_point:
+                raise HipError("topk: exclude must be an integer [B] tensor of dataset rows")
+
+    def topk(self, prediction, slot, k, exclude=None, chunk=8192):
+        """(idx LongTensor [B, k] dataset rows, score FloatTensor [B, k]) of the k best candidates for every query row.
+        slot: int or integer [B] tensor (on the device it is not read back: a row whose slot lies outside [0, S) returns
+        only (-1, -inf)); exclude: optional integer [B] dataset rows, each skipped (with the item it belongs to) for its
+        query; chunk: candidates per GEMM + selection pass on the device."""
+        self._check_args(prediction, slot, k, exclude, chunk)
+        if prediction.device.type == "cuda":
+            return self._device_topk(prediction, int(k), exclude, int(chunk), slot=slot)
+        return self._host_topk(prediction, slot, int(k), exclude)
+
+    def _device_topk(self, prediction, k, exclude, chunk, slot=None, mask_id=None, mask_table=None):
+        dev = prediction.device
+        cand, norm, count, row_id, pos = self._device_tables(dev)
+        S, E, n_cand = self.S, self.E, cand.shape[1]
+        pred = prediction.detach()
+        if pred.dtype != torch.float32 or not pred.is_contiguous():
+            pred = pred.to(torch.float32).contiguous()
+        B = pred.shape[0]
+        i32 = dict(dtype=torch.int32, device=dev)
+        slot_t = None
+        if slot is not None:
+            slot_t = (torch.full((B,), int(slot), **i32) if not torch.is_tensor(slot) else slot.to(**i32).contiguous())
+        ex = None if exclude is None else exclude.to(**i32).contiguous()
+        chunk = min(chunk, n_cand)
+        work = torch.empty(B * chunk, dtype=torch.float32, device=dev)
+        rows = torch.empty(3 * B, **i32)
+        perm = torch.empty(S * B + S, **i32)
+        q = torch.empty(B * E, dtype=torch.float32, device=dev)
+        state = torch.empty(B * k, dtype=torch.int64, device=dev)
+        out_idx = torch.empty((B, k), **i32)
+        out_score = torch.empty((B, k), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _check(_hip_lib().codae_complete_topk(
+                _ptr(pred), B, S * E, S, E, _ptr(slot_t), None, _ptr(mask_id), None, 0, 0, _ptr(mask_table),
+                _ptr(cand), _ptr(norm), _ptr(row_id), n_cand, count, _ptr(ex), _ptr(pos) if ex is not None else None, self.n_obs,
+                k, _ptr(work), chunk, _ptr(rows), _ptr(perm), _ptr(q), _ptr(state), _ptr(out_idx), _ptr(out_score), _stream()))
+        self._keep = (pred, slot_t, ex, mask_id, work, rows, perm, q, state)     # (alive until the stream has consumed them)
+        return out_idx.long(), out_score
+
+    def _host_topk(self, prediction, slot, k, exclude):
+        cand, count, row_id, pos = self._host_tables()
+        E = self.E
+        pred = prediction.detach().to("cpu")
+        B = pred.shape[0]
+        slots = torch.full((B,), int(slot), dtype=torch.long) if not torch.is_tensor(slot) else slot.to("cpu", torch.long)
+        ex = None if exclude is None else exclude.to("cpu", torch.long)
+        out_idx = torch.full((B, k), -1, dtype=torch.long)
+        out_score = torch.full((B, k), float("-inf"), dtype=torch.float32)
+        for c in torch.unique(slots).tolist():
+            n = count[c]
+            rows = (slots == c).nonzero(as_tuple=True)[0]
+            if n == 0:
+                continue
+            V = cand[c, :n].double()
+            q = pred[rows, c * E:(c + 1) * E].double()
+            s = (q @ V.t()) / (q.norm(dim=1, keepdim=True).clamp_min(1e-8) * V.norm(dim=1).clamp_min(1e-8)[None, :])
+            s = s.float() + 0.0                                           # fp32 scores; -0 -> +0
+            bad = torch.isnan(s)
+            if ex is not None:
+                e = ex[rows]
+                ok = (e >= 0) & (e < self.n_obs)
+                p = torch.full_like(e, -1)
+                p[ok] = pos[c, e[ok]].long()
+                hit = (p >= 0).nonzero(as_tuple=True)[0]
+                bad[hit, p[hit]] = True
+            s = s.masked_fill(bad, float("-inf"))
+            # score descending with ties in candidate (= dataset row) order, then the invalid ones to the back
+            order = torch.sort(s, dim=1, descending=True, stable=True)[1]
+            order = order.gather(1, torch.sort(bad.gather(1, order).to(torch.int8), dim=1, stable=True)[1])
+            kk = min(k, n)
+            sel = order[:, :kk]
+            valid = ~bad.gather(1, sel)
+            out_idx[rows, :kk] = torch.where(valid, row_id[c].long()[sel], torch.full_like(sel, -1))
+            out_score[rows, :kk] = torch.where(valid, s.gather(1, sel), torch.full_like(s[:, :kk], float("-inf")))
+        return out_idx, out_score
 
 
 class CombinedCriterion:

@@ -26,6 +26,7 @@ valid for its own shards only until gather_params() is called (checkpoint, read-
 import torch
 
 from .hostcpu import fit_host_threads, host_cpu_share  # noqa: F401  (re-exported: scripts and bench.py import them here)
+from .hip import HipError
 
 
 class SubsetEpochSampler:
@@ -378,16 +379,26 @@ class DataParallel:
         return t
 
 
+class _ResidentInventory:
+    """The slots of a resident [N, S*E] data matrix in the shape tool.ComplementRetriever reads (data_per_category views).
+    The global scaling of dataset.data does not change cosines."""
+
+    def __init__(self, data, S, E):
+        self.nb_used_category, self.embedding_size = S, E
+        self.data_per_category = {c: data[:, c * E:(c + 1) * E] for c in range(S)}
+
+
 class HipEmbeddingTrainer:
     """Owns a DaeEngine, the resident dataset and the mask tables; runs train / eval steps."""
 
     def __init__(self, schedule, data, mask_table_u8, mask_to_use_i32, lr, weight_decay, clip=1.0,
                  max_batch=8192, precision="bf16", device="cuda:0", distributed=False, n_buckets=None, use_graph=False,
-                 sharded_update=False, native_dp=False, activation=None):
+                 sharded_update=False, native_dp=False, activation=None, n_slots=None):
         """use_graph: replay the fused step from a hipGraph (codae_train_step_graph): for launch-bound shapes
         (small batches); single process only - the bucketed data-parallel step is not captured.
         activation: what follows every hidden Linear, as the model classes take it (a factory called as activation(True),
-        e.g. torch.nn.ELU); None = ReLU.  Every step form (fused, graph replay, data parallel) runs it."""
+        e.g. torch.nn.ELU); None = ReLU.  Every step form (fused, graph replay, data parallel) runs it.
+        n_slots: categories per row (complete() only; default: read off the mask table)."""
         from .hip.engine import DaeEngine
         fit_host_threads()      # the loop that feeds this trainer must not get its container CPU-throttled (codae/hostcpu.py)
         self.device = torch.device(device)
@@ -396,6 +407,7 @@ class HipEmbeddingTrainer:
         self.mask_table = None if mask_table_u8 is None else mask_table_u8.to(self.device).contiguous()
         self.mask_to_use = None if mask_to_use_i32 is None else mask_to_use_i32.to(self.device).contiguous()
         self.lr, self.weight_decay, self.clip = lr, weight_decay, clip
+        self.n_slots = n_slots
         self.dp = DataParallel(self.engine, n_buckets=n_buckets, sharded=sharded_update, native=native_dp) if distributed else None
         self.world = self.dp.world if self.dp else 1
         self.use_graph = bool(use_graph) and self.dp is None
@@ -476,6 +488,56 @@ class HipEmbeddingTrainer:
         self.engine.eval_step(batch, y)
         self._keep = batch
         return y
+
+    def _slots(self):
+        """(S, E): from `n_slots`, else from the Corrupter table (row 0 = the 1-subset {slot 0}: its zeros are one slot)."""
+        io = int(self.data.shape[1])
+        if self.n_slots:
+            S = int(self.n_slots)
+        elif self.mask_table is not None:
+            S = io // int((self.mask_table[0] == 0).sum())
+        else:
+            raise HipError("complete(): the trainer has no mask table; construct it with n_slots")
+        if S < 1 or io % S:
+            raise HipError("complete(): %d slots do not divide io %d" % (S, io))
+        return S, io // S
+
+    def complete(self, row_idx, slot, k, exclude_self=False, distinct=True, candidates=None, chunk=8192):
+        """Complementarity inference: blank slot `slot` of dataset rows `row_idx`, run the eval forward, and return the k
+        resident-dataset rows whose slot is closest (cosine) to the reconstruction: (idx LongTensor [B, k], score FloatTensor
+        [B, k]), ordered as tool.ComplementRetriever.topk.  Mask id c is the 1-subset {c} of the Corrupter's table order
+        (the trainer's own S x io table when it has none), so the result does not depend on the mask run.  exclude_self:
+        never return a row's own item.  The metric sums of the engine are left as they were."""
+        from .tool.criteria import ComplementRetriever
+        S, E = self._slots()
+        if isinstance(slot, bool) or not isinstance(slot, int) or not 0 <= slot < S:
+            raise HipError("complete(): slot must be an int in [0, %d), got %r" % (S, slot))
+        idx = torch.as_tensor(row_idx, dtype=torch.int32).to(self.device).contiguous().reshape(-1)
+        table = self.mask_table
+        if table is None:
+            if getattr(self, "_own_table", None) is None:
+                t = torch.ones((S, S * E), dtype=torch.uint8)
+                for c in range(S):
+                    t[c, c * E:(c + 1) * E] = 0
+                self._own_table = t.to(self.device)
+            table = self._own_table
+        key = (bool(distinct), None if candidates is None else tuple(sorted(set(int(i) for i in candidates))))
+        cache = self.__dict__.setdefault("_retrievers", {})
+        if key not in cache:
+            inv = _ResidentInventory(self.data, S, E)
+            cache[key] = ComplementRetriever(inv, self.device, candidates=key[1], distinct=key[0])
+        ret = cache[key]
+        B = int(idx.numel())
+        mask_id = torch.full((B,), slot, dtype=torch.int32, device=self.device)
+        batch = self.engine.make_batch(self.data, idx, mask_id, table)
+        y = torch.empty((B, self.data.shape[1]), dtype=torch.float32, device=self.device)
+        sums = self.engine.scalars.clone()
+        self.engine.eval_step(batch, y)
+        self.engine.scalars.copy_(sums)                     # (the eval step adds into the epoch's metric sums)
+        self._keep = batch
+        ret._check_args(y, slot, k, idx if exclude_self else None, chunk)
+        # the blanked slot reaches the kernels through the same mask table as the forward (codae_complete_topk's mask route)
+        return ret._device_topk(y, int(k), idx if exclude_self else None, int(chunk), mask_id=mask_id, mask_table=table)
 
     def epoch_sums(self, reset=True, reduce=True):
         """(sum (x-y)^2, sum (1-fmask)(x-y)^2) accumulated since the last reset (summed over the

@@ -333,6 +333,221 @@ __global__ __launch_bounds__(NT) void gather_rows_kernel(const float* __restrict
     }
 }
 
+// ---- complementarity inference: top-k retrieval for a blanked slot -------------------------------------------------
+// Candidates are ranked by a 64-bit key with one total order and no comparator branches:
+//   key = orderable(score) << 32 | ~column,   orderable: the IEEE bits flipped so that unsigned order = float order
+// -0 is folded to +0 first, NaN never gets a key.  Higher key = better: score descending, then column ascending (the
+// tables keep candidates in ascending dataset-row order, so that is ascending row id).  Every finite or infinite score maps
+// to a key > 0, so 0 marks an empty slot of the state.
+__device__ __forceinline__ uint64_t topk_key(float s, int col) {
+    uint32_t u = (s == 0.f) ? 0u : __float_as_uint(s);
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((uint64_t)u << 32) | (uint32_t)~(uint32_t)col;
+}
+__device__ __forceinline__ float topk_key_score(uint64_t key) {
+    const uint32_t u = (uint32_t)(key >> 32);
+    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+}
+
+// LDS written by one lane and read by another lane of the SAME wave: LDS operations of a wave complete in order, so a
+// compiler fence at wavefront scope is all that is needed (what HIP's __syncwarp expands to)
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+constexpr int TK_WAVES = NT / 64;
+constexpr int TK_UNROLL = 4;             // columns in flight per lane (loads issued before the first compare)
+
+// top[0, KP) descending  U  buf[0, KP) (unsorted, empty entries 0)  ->  top = the KP best of both, descending; buf = 0.
+// Bitonic: sort buf ascending, keep the element-wise max (the upper half of a half-cleaner on top || buf: bitonic, and it
+// holds the KP largest), then one bitonic merge down to descending order.
+template <int KP>
+__device__ __forceinline__ void topk_merge_lds(uint64_t* top, uint64_t* buf, int lane) {
+    for (int size = 2; size <= KP; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+#pragma unroll
+            for (int t = lane; t < KP / 2; t += 64) {
+                const int i = 2 * t - (t & (stride - 1)), j = i + stride;
+                const bool up = (i & size) == 0;
+                const uint64_t a = buf[i], c = buf[j];
+                if ((a > c) == up) { buf[i] = c; buf[j] = a; }
+            }
+            wave_lds_sync();
+        }
+    }
+#pragma unroll
+    for (int t = lane; t < KP; t += 64) {
+        const uint64_t a = top[t], c = buf[t];
+        top[t] = a > c ? a : c;
+        buf[t] = 0;
+    }
+    wave_lds_sync();
+    for (int stride = KP / 2; stride > 0; stride >>= 1) {
+#pragma unroll
+        for (int t = lane; t < KP / 2; t += 64) {
+            const int i = 2 * t - (t & (stride - 1)), j = i + stride;
+            const uint64_t a = top[i], c = top[j];
+            if (a < c) { top[i] = c; top[j] = a; }
+        }
+        wave_lds_sync();
+    }
+}
+
+// Running top-k over one chunk of a score matrix, one wave per score row r < min(rows, *rows_dev).  The row's state
+// (k keys, descending, at state[b * k], b = row_map ? row_map[r] : r) is loaded into LDS; lanes read the row with stride 64
+// (coalesced), drop a score at once when its key does not beat the current k-th key (a register), and append survivors to a
+// per-wave LDS buffer at a ballot / mbcnt prefix.  A full buffer, and the end of the chunk, is merged into the state
+// (topk_merge_lds), which raises the threshold.  Scores are read once; only the k keys are written back.
+//   s = scores[r][j]                                         (raw; the selection primitive)
+//   s = scores[r][j] / (row_norm[b] * max(col_norm[j], 1e-8))  (col_norm != null: cosine from GEMM dot products, as rank_count_kernel)
+// Column j is candidate col0 + j; the candidate skip_col[b] (a global column, -1 = none) is skipped by position.
+template <int KP>
+__global__ __launch_bounds__(NT) void topk_merge_kernel(const float* __restrict__ scores, int64_t ld, int rows,
+                                                        const int32_t* __restrict__ rows_dev, int n, int col0, int k,
+                                                        const int32_t* __restrict__ row_map, const float* __restrict__ row_norm,
+                                                        const float* __restrict__ col_norm, const int32_t* __restrict__ skip_col,
+                                                        uint64_t* __restrict__ state) {
+    __shared__ uint64_t lds[TK_WAVES][2 * KP];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int r = blockIdx.x * TK_WAVES + w;
+    const int nrows = rows_dev ? min(rows, *rows_dev) : rows;
+    if (r >= nrows) return;
+    const int b = row_map ? row_map[r] : r;
+    uint64_t* top = lds[w];
+    uint64_t* buf = lds[w] + KP;
+    uint64_t* st = state + (int64_t)b * k;
+    for (int i = lane; i < KP; i += 64) { top[i] = i < k ? st[i] : 0; buf[i] = 0; }
+    wave_lds_sync();
+    uint64_t thr = top[k - 1];
+    const int skip = skip_col ? skip_col[b] : -1;
+    const float qs = row_norm ? row_norm[b] : 1.f;
+    const float* srow = scores + (int64_t)r * ld;
+    int cnt = 0;
+    for (int j0 = 0; j0 < n; j0 += 64 * TK_UNROLL) {
+        float v[TK_UNROLL];
+#pragma unroll
+        for (int u = 0; u < TK_UNROLL; ++u) {
+            const int j = j0 + u * 64 + lane;
+            v[u] = j < n ? srow[j] : __builtin_nanf("");
+        }
+#pragma unroll
+        for (int u = 0; u < TK_UNROLL; ++u) {
+            const int j = j0 + u * 64 + lane;
+            float s = v[u];
+            if (col_norm && j < n) s = s / (qs * fmaxf(col_norm[j], 1e-8f));
+            const uint64_t key = topk_key(s, col0 + j);
+            bool keep = (s == s) && (col0 + j != skip) && key > thr;
+            uint64_t m = __ballot(keep);
+            if (m == 0) continue;
+            if (cnt + __popcll(m) > KP) {            // buffer full: merge first (the threshold rises), then re-test
+                topk_merge_lds<KP>(top, buf, lane);
+                thr = top[k - 1];
+                cnt = 0;
+                keep = keep && key > thr;
+                m = __ballot(keep);
+            }
+            const int pos = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+            if (keep) buf[cnt + pos] = key;
+            cnt += __popcll(m);
+            wave_lds_sync();
+        }
+    }
+    if (cnt > 0) topk_merge_lds<KP>(top, buf, lane);
+    for (int i = lane; i < k; i += 64) st[i] = top[i];
+}
+
+// keys -> (dataset row id, score); an empty key -> (-1, -inf).  Row b's candidate table: cand_row_id + slot[b] * n_cand
+// (slot == null: one table; a slot outside [0, n_slots) has an empty state: its whole row is the -1 / -inf tail)
+__global__ __launch_bounds__(NT) void topk_finish_kernel(const uint64_t* __restrict__ state, int B, int k,
+                                                         const int32_t* __restrict__ cand_row_id, const int32_t* __restrict__ slot,
+                                                         int n_slots, int n_cand, int32_t* __restrict__ out_idx,
+                                                         float* __restrict__ out_score) {
+    const int64_t total = (int64_t)B * k;
+    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < total; e += (int64_t)gridDim.x * NT) {
+        const uint64_t key = state[e];
+        int32_t id = -1;
+        float sc = -__builtin_inff();
+        if (key != 0) {
+            const int pos = (int)~(uint32_t)key;
+            sc = topk_key_score(key);
+            id = pos;
+            if (cand_row_id) {
+                const int c = slot ? slot[e / k] : 0;
+                id = (c >= 0 && c < n_slots) ? cand_row_id[(int64_t)c * n_cand + pos] : -1;
+            }
+        }
+        out_idx[e] = id;
+        out_score[e] = sc;
+    }
+}
+
+// one wave per query: slot c (given, or the blanked slot of its mask as rank_prep_kernel finds it), |q| clamped, the
+// candidate to skip (exclude[b] mapped through cand_pos[c]), and the compaction of the slot's rows (perm / counts).
+// Row state: slot_out [B] (-1: slot outside [0, S), no candidates), qn_out [B], skip_out [B].
+__global__ __launch_bounds__(NT) void complete_prep_kernel(const float* __restrict__ pred, int B, int io, int S, int E,
+                                                           const int32_t* __restrict__ slot, const int32_t* __restrict__ row_idx,
+                                                           const int32_t* __restrict__ mask_id, const int32_t* __restrict__ mask_to_use,
+                                                           int nb_run, int run, const uint8_t* __restrict__ mask_table,
+                                                           const int32_t* __restrict__ exclude, const int32_t* __restrict__ cand_pos,
+                                                           int64_t n_obs, int32_t* __restrict__ slot_out, float* __restrict__ qn_out,
+                                                           int32_t* __restrict__ skip_out, int32_t* __restrict__ perm,
+                                                           int32_t* __restrict__ counts) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
+    if (b >= B) return;
+    int c;
+    if (slot) {
+        c = slot[b];
+    } else {
+        const int id = mask_id ? mask_id[b] : mask_to_use[(int64_t)row_idx[b] * nb_run + run];
+        c = 0;
+        for (int s = 1; s < S; ++s) c += (mask_table[(int64_t)id * io + (int64_t)s * E] == 0) ? s : 0;
+        c = c < S ? c : S - 1;
+    }
+    if (c < 0 || c >= S) {
+        if (lane == 0) { slot_out[b] = -1; qn_out[b] = 1.f; skip_out[b] = -1; }
+        return;
+    }
+    const float* q = pred + (int64_t)b * io + (int64_t)c * E;
+    float sq = 0.f;
+    for (int x = lane; x < E; x += 64) { const float v = q[x]; sq += v * v; }
+    sq = wave_sum_f(sq);
+    if (lane == 0) {
+        int skip = -1;
+        if (exclude && cand_pos) {
+            const int64_t ex = exclude[b];
+            skip = (ex >= 0 && ex < n_obs) ? cand_pos[(int64_t)c * n_obs + ex] : -1;
+        }
+        slot_out[b] = c;
+        qn_out[b] = fmaxf(sqrtf(sq), 1e-8f);
+        skip_out[b] = skip;
+        const int k = atomicAdd(&counts[c], 1);      // (integer: which GEMM row a query lands on changes none of its bits)
+        perm[(int64_t)c * B + k] = b;
+    }
+}
+
+template <int KP>
+int launch_topk_merge(const float* scores, int64_t ld, int rows, const int32_t* rows_dev, int n, int col0, int k,
+                      const int32_t* row_map, const float* row_norm, const float* col_norm, const int32_t* skip_col,
+                      uint64_t* state, hipStream_t s) {
+    hipLaunchKernelGGL(topk_merge_kernel<KP>, dim3((rows + TK_WAVES - 1) / TK_WAVES), dim3(NT), 0, s, scores, ld, rows, rows_dev,
+                       n, col0, k, row_map, row_norm, col_norm, skip_col, state);
+    CODAE_LAUNCH_CHECK();
+    return CODAE_OK;
+}
+
+// LDS capacity per wave: the k best plus a buffer of as many survivors, in powers of two from one wave's width
+int topk_merge(const float* scores, int64_t ld, int rows, const int32_t* rows_dev, int n, int col0, int k, const int32_t* row_map,
+               const float* row_norm, const float* col_norm, const int32_t* skip_col, uint64_t* state, hipStream_t s) {
+    if (k <= 64) return launch_topk_merge<64>(scores, ld, rows, rows_dev, n, col0, k, row_map, row_norm, col_norm, skip_col, state, s);
+    if (k <= 128) return launch_topk_merge<128>(scores, ld, rows, rows_dev, n, col0, k, row_map, row_norm, col_norm, skip_col, state, s);
+    return launch_topk_merge<256>(scores, ld, rows, rows_dev, n, col0, k, row_map, row_norm, col_norm, skip_col, state, s);
+}
+
+constexpr int TOPK_KMAX = 256;
+
 inline int grid_for(int64_t items) {
     int64_t b = (items + NT - 1) / NT;
     if (b < 1) b = 1;
@@ -457,6 +672,89 @@ int codae_ranking_loss_batched(const float* pred, int32_t B, int32_t io, int32_t
         }
     }
     hipLaunchKernelGGL(rank_finish_kernel, dim3(1), dim3(NT), 0, s, rs, B, n_val, out);
+    CODAE_LAUNCH_CHECK();
+    return CODAE_OK;
+}
+
+int codae_topk_init(void* state, int32_t B, int32_t k, void* stream) {
+    CODAE_REQUIRE(state && B > 0 && k >= 1 && k <= TOPK_KMAX, "topk_init: bad argument (B %d, k %d)", B, k);
+    CODAE_HIP_CHECK(hipMemsetAsync(state, 0, (size_t)B * k * sizeof(uint64_t), (hipStream_t)stream));
+    return CODAE_OK;
+}
+
+int codae_topk_merge(const float* scores, int64_t ld, int32_t rows, int32_t n, int32_t col0, int32_t k, const int32_t* row_map,
+                     const int32_t* skip_col, void* state, void* stream) {
+    CODAE_REQUIRE(scores && state, "topk_merge: null argument");
+    CODAE_REQUIRE(rows > 0 && n > 0 && ld >= n && col0 >= 0 && (int64_t)col0 + n <= INT32_MAX, "topk_merge: bad sizes");
+    CODAE_REQUIRE(k >= 1 && k <= TOPK_KMAX, "topk_merge: k %d outside [1, %d]", k, TOPK_KMAX);
+    return topk_merge(scores, ld, rows, nullptr, n, col0, k, row_map, nullptr, nullptr, skip_col, (uint64_t*)state,
+                      (hipStream_t)stream);
+}
+
+int codae_topk_finish(const void* state, int32_t B, int32_t k, const int32_t* cand_row_id, int32_t* out_idx, float* out_score,
+                      void* stream) {
+    CODAE_REQUIRE(state && out_idx && out_score, "topk_finish: null argument");
+    CODAE_REQUIRE(B > 0 && k >= 1 && k <= TOPK_KMAX, "topk_finish: bad sizes (B %d, k %d)", B, k);
+    hipLaunchKernelGGL(topk_finish_kernel, dim3(grid_for((int64_t)B * k)), dim3(NT), 0, (hipStream_t)stream, (const uint64_t*)state, B,
+                       k, cand_row_id, nullptr, 1, 0, out_idx, out_score);
+    CODAE_LAUNCH_CHECK();
+    return CODAE_OK;
+}
+
+int codae_complete_topk(const float* pred, int32_t B, int32_t io, int32_t n_slots, int32_t E, const int32_t* slot,
+                        const int32_t* row_idx, const int32_t* mask_id, const int32_t* mask_to_use, int32_t nb_run, int32_t run,
+                        const uint8_t* mask_table, const float* cand, const float* cand_norm, const int32_t* cand_row_id,
+                        int32_t n_cand, const int32_t* cand_count, const int32_t* exclude, const int32_t* cand_pos, int64_t n_obs,
+                        int32_t k, float* work, int32_t chunk, void* row_state, int32_t* perm_ws, float* q_ws, void* topk_state,
+                        int32_t* out_idx, float* out_score, void* stream) {
+    CODAE_REQUIRE(pred && cand && cand_norm && cand_row_id && work && row_state && perm_ws && q_ws && topk_state && out_idx && out_score,
+                  "complete_topk: null argument");
+    CODAE_REQUIRE(slot || (mask_table && (mask_id || (mask_to_use && row_idx))), "complete_topk: neither a slot array nor a mask route");
+    CODAE_REQUIRE(slot || mask_id || (nb_run > 0 && run >= 0 && run < nb_run), "complete_topk: run %d outside [0, %d)", run, nb_run);
+    CODAE_REQUIRE(B > 0 && n_slots > 0 && E > 0 && io == n_slots * E && n_cand > 0 && chunk > 0, "complete_topk: bad sizes");
+    CODAE_REQUIRE(k >= 1 && k <= TOPK_KMAX, "complete_topk: k %d outside [1, %d]", k, TOPK_KMAX);
+    CODAE_REQUIRE(!exclude || (cand_pos && n_obs > 0), "complete_topk: exclude needs cand_pos and n_obs");
+    if (cand_count)
+        for (int c = 0; c < n_slots; ++c)
+            CODAE_REQUIRE(cand_count[c] >= 0 && cand_count[c] <= n_cand, "complete_topk: cand_count[%d] = %d outside [0, %d]", c,
+                          cand_count[c], n_cand);
+    hipStream_t s = (hipStream_t)stream;
+    int32_t* slot_rs = reinterpret_cast<int32_t*>(row_state);          // [B] slot (-1: none)
+    float* qn_rs = reinterpret_cast<float*>(slot_rs + B);             // [B] |q| clamped
+    int32_t* skip_rs = slot_rs + 2 * (int64_t)B;                      // [B] candidate position to skip (-1: none)
+    int32_t* perm = perm_ws;                                          // [n_slots][B]
+    int32_t* counts = perm_ws + (int64_t)n_slots * B;                 // [n_slots]
+    uint64_t* st = reinterpret_cast<uint64_t*>(topk_state);
+    CODAE_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)n_slots * sizeof(int32_t), s));
+    CODAE_HIP_CHECK(hipMemsetAsync(st, 0, (size_t)B * k * sizeof(uint64_t), s));
+    const int rows_grid = (B + NT / 64 - 1) / (NT / 64);
+    hipLaunchKernelGGL(complete_prep_kernel, dim3(rows_grid), dim3(NT), 0, s, pred, B, io, n_slots, E, slot, row_idx, mask_id, mask_to_use,
+                       nb_run, run, mask_table, exclude, cand_pos, n_obs, slot_rs, qn_rs, skip_rs, perm, counts);
+    CODAE_LAUNCH_CHECK();
+    // per slot: its queries gathered (compacted: the row count stays on the device), one fp32 GEMM per chunk of candidates over
+    // those rows (gemm_f32: the x3 / native switch of the parity path), then the selection pass over the chunk it wrote
+    for (int c = 0; c < n_slots; ++c) {
+        const int nc = cand_count ? cand_count[c] : n_cand;
+        if (nc == 0) continue;
+        hipLaunchKernelGGL(rank_gather_q_kernel, dim3(grid_for((int64_t)B * E / 4)), dim3(NT), 0, s, pred, io, E, B, c, perm, counts, q_ws);
+        CODAE_LAUNCH_CHECK();
+        for (int v0 = 0; v0 < nc; v0 += chunk) {
+            const int n = nc - v0 < chunk ? nc - v0 : chunk;
+            GemmF32 g{};
+            g.A = q_ws; g.a_rs = E; g.a_ks = 1;
+            g.B = cand + ((int64_t)c * n_cand + v0) * E; g.b_rs = E; g.b_ks = 1;
+            g.C = work; g.ldc = chunk;
+            g.M = B; g.N = n; g.K = E;
+            g.m_dev = counts + c;
+            int rc = gemm_f32(g, s);
+            if (rc) return rc;
+            rc = topk_merge(work, chunk, B, counts + c, n, v0, k, perm + (int64_t)c * B, qn_rs, cand_norm + (int64_t)c * n_cand + v0,
+                            skip_rs, st, s);
+            if (rc) return rc;
+        }
+    }
+    hipLaunchKernelGGL(topk_finish_kernel, dim3(grid_for((int64_t)B * k)), dim3(NT), 0, s, st, B, k, cand_row_id, slot_rs, n_slots, n_cand,
+                       out_idx, out_score);
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;
 }
