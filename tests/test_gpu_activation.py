@@ -102,8 +102,11 @@ def test_model_forward_backward_fp32_matches_float64(kind, cls, E, steep):
 
 def bf16_restatement(model, x, g):
     """float64 forward / backward of the model rounded to bf16 where the bf16 engine rounds: input, weights, every stored
-    activation, the incoming and every stored activation gradient (the GEMM result, then - for a kind other than ReLU -
-    its product with the derivative taken from the stored activation).  Returns y, dx, [dW0, db0, dW1, ...]."""
+    layer output (the code layer's too: codae_forward keeps it in act[l+1] like any hidden output; only the last layer's y
+    goes out in fp32), the incoming and every stored activation gradient (the GEMM result, then - for a kind other than
+    ReLU - its product with the derivative taken from the stored activation).  Bias gradients: the top layer's sums the
+    caller's fp32 dy (colsum_parts_f32 in codae_backward), every other layer's the STORED bf16 activation gradient (the
+    data-gradient epilogues sum what they write).  Returns y, dx, [dW0, db0, dW1, ...]."""
     from codae.model.activation import as_engine_act
     bf = lambda a: torch.tensor(a).to(torch.bfloat16).double().numpy()     # noqa: E731
     layers = []
@@ -115,15 +118,16 @@ def bf16_restatement(model, x, g):
                 layers.append((bf(m.weight.detach().cpu().numpy()), m.bias.detach().cpu().double().numpy(),
                                None if nxt is None else as_engine_act(nxt)))
     hs = [bf(x)]
-    for W, b, act in layers:
+    for l, (W, b, act) in enumerate(layers):
         v = hs[-1] @ W.T + b
-        hs.append(v if act is None else bf(np_act(act[0], act[1:], v)))
+        v = v if act is None else np_act(act[0], act[1:], v)
+        hs.append(v if l == len(layers) - 1 else bf(v))
     y = hs[-1]
     da = bf(g)
     grads = []
     for l in range(len(layers) - 1, -1, -1):
         W, b, _ = layers[l]
-        grads[:0] = [da.T @ hs[l], da.sum(0)]
+        grads[:0] = [da.T @ hs[l], (g.astype(np.float64) if l == len(layers) - 1 else da).sum(0)]
         if l == 0:
             dx = da @ W
         else:
@@ -148,12 +152,86 @@ def test_model_forward_backward_bf16(kind, cls, E):
     assert model._engine.precision == 1
     ry, rdx, rgrads = bf16_restatement(model, x, g)
     assert rel_l2(y, ry) < 1e-2
-    # the gradients are 4-5.7 % off this restatement for ReLU as well - the unchanged ReLU code, so a rounding of the bf16
-    # backward the restatement does not reproduce, not an error of the activation epilogues; bounded at that level (the
-    # smooth kinds stay within 2 %)
-    assert rel_l2(dx, rdx) < 8e-2
-    for a, b in zip(grads, rgrads):
-        assert rel_l2(a, b) < 8e-2
+    errs = [rel_l2(dx, rdx)] + [rel_l2(a, b) for a, b in zip(grads, rgrads)]
+    print("MEASURE drop-in bf16 %s %s %d: y %.3g, max grad rel L2 %.3g (index %d)"
+          % (KIND_IDS[kind], cls, E, rel_l2(y, ry), max(errs), int(np.argmax(errs))))
+    assert max(errs) < DROPIN_BF16_REL_L2, errs
+
+
+# Measured on the MI355X over every kind, both classes and E = 48 / 64: at most 9.5e-4 (ReLU 1.3e-4).  The old restatement
+# left the code layer's output unrounded and summed the top bias gradient from the rounded dy, which put it 4-5.7 % off
+# for ReLU; the bound is about twice the measured deviation.
+DROPIN_BF16_REL_L2 = 2e-3
+
+
+def _encode_decode(model, x_np, g_np):
+    """decode(encode(x)) with a backward: two autograd nodes, the input gradient handed from one to the other."""
+    x = torch.tensor(x_np, device=dev(), requires_grad=True)
+    y = model.decode(model.encode(x))
+    (y * torch.tensor(g_np, device=dev())).sum().backward()
+    torch.cuda.synchronize()
+    grads = [p.grad.detach().cpu().numpy() for p in model.parameters()]
+    for p in model.parameters():
+        p.grad = None
+    return y.detach().cpu().numpy(), x.grad.cpu().numpy(), grads
+
+
+@pytest.mark.parametrize("precision", ["f32", "bf16"])
+@pytest.mark.parametrize("cls", ["embedding", "mixed"])
+def test_encode_then_decode_backward_equals_forward_backward(precision, cls):
+    """decode(encode(x)).backward - codae_backward on the two sub-ranges, decode's with an fp32 input gradient that becomes
+    encode's dy - against model(x).backward on a ragged batch (333 rows).  Both run the same GEMMs; the code layer's bias
+    gradient is summed from the fp32 dy on the split path and from the stored activation gradient on the whole chain
+    (in bf16: rounded), and the code layer's output leaves the encode GEMM in fp32 before decode stores it.  Every other
+    tensor within 1e-6 of the whole chain's; and against float64 (f32, 1e-4) or the bf16 restatement (bf16)."""
+    model = build(cls, 64, False, nn.ReLU).to(dev())
+    model.precision = precision
+    x = np.random.default_rng(3).random((333, 192)).astype(np.float32) * 2 - 0.5
+    y, dx, grads, g = run_model(model, x)
+    for p in model.parameters():
+        p.grad = None
+    y2, dx2, grads2 = _encode_decode(model, x, g)
+    assert model._engine.precision == (1 if precision == "bf16" else 0)
+    errs = [rel_l2(y2, y), rel_l2(dx2, dx)] + [rel_l2(a, b) for a, b in zip(grads2, grads)]
+    code_db = 2 + 2 * (model._n_enc - 1) + 1            # (errs index of the code layer's bias gradient)
+    print("MEASURE encode-decode %s %s vs whole chain: max %.3g (index %d), code-layer bias %.3g"
+          % (precision, cls, max(errs), int(np.argmax(errs)), errs[code_db]))
+    # everything else measured bit-identical in both precisions; the code layer's bias gradient in bf16 2.4e-3 (the
+    # rounding of the stored activation gradient it sums on the whole chain)
+    assert max(e for i, e in enumerate(errs) if i != code_db) <= 1e-6, errs
+    assert errs[code_db] <= (1e-6 if precision == "f32" else 5e-3), errs
+    if precision == "f32":
+        ry, rdx, rgrads = run_ref(cpu_copy(model), x, g)
+        assert rel_l2(y2, ry) < 1e-4 and rel_l2(dx2, rdx) < 1e-4
+    else:
+        ry, rdx, rgrads = bf16_restatement(model, x, g)
+        assert rel_l2(y2, ry) < 1e-2 and rel_l2(dx2, rdx) < DROPIN_BF16_REL_L2
+    for i, (a, b) in enumerate(zip(grads2, rgrads)):
+        # (the restatement sums the code layer's bias gradient as the whole chain does: the bf16 split path is 2.4e-3 off)
+        bound = 1e-4 if precision == "f32" else (5e-3 if i == code_db - 2 else DROPIN_BF16_REL_L2)
+        assert rel_l2(a, b) < bound, i
+
+
+@pytest.mark.parametrize("precision", ["f32", "bf16"])
+def test_backward_after_a_second_forward_is_refused(precision):
+    """The engine keeps one set of saved activations: a backward through a forward whose activations a later forward
+    overwrote raises HipError (_ChainFunction's stamps) instead of returning the later batch's gradients; the later
+    forward's own backward still runs, and a sub-range forward (encode) invalidates a whole-chain forward too."""
+    from codae.hip import HipError
+    model = build("embedding", 64, False, nn.ReLU).to(dev())
+    model.precision = precision
+    rng = np.random.default_rng(4)
+    x1, x2 = (torch.tensor(rng.random((100, 192), dtype=np.float32), device=dev()) for _ in range(2))
+    y1 = model(x1)
+    y2 = model(x2)
+    with pytest.raises(HipError, match="overwritten"):
+        y1.sum().backward()
+    y2.sum().backward()
+    assert all(p.grad is not None and float(p.grad.abs().sum()) > 0 for p in model.parameters())
+    y3 = model(x1)
+    model.encode(x2)
+    with pytest.raises(HipError, match="overwritten"):
+        y3.sum().backward()
 
 
 def test_explicit_relu_is_bitwise_the_default_and_keeps_masks_and_chain():
