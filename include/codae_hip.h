@@ -43,9 +43,11 @@ extern "C" {
  *      exact duplicates of each other) behind val_pos; + codae_dp_unique_id / _init / _destroy, codae_train_step_dp
  *   6: codae_spec.act_kind / act_param (appended), CODAE_ACT_*, codae_linear_act_f32 / _bf16, codae_dgrad_act_f32 / _bf16
  *   7: + codae_topk_init / _merge / _finish, codae_complete_topk (new entries only; no layout change)
+ *   8: + CODAE_NOISE_*, codae_noise, codae_set_input_noise, codae_corrupt_batch, codae_noise_box_muller (new entries only; no
+ *      layout change of an existing struct, codae_struct_sizes keeps its seven entries)
  * The binding must refuse a library whose codae_abi_version() differs and must check its own struct sizes against
  * codae_struct_sizes() at load (mui-deepautoencoder_amd/codae/hip/__init__.py does both). */
-#define CODAE_ABI_VERSION 7
+#define CODAE_ABI_VERSION 8
 
 enum {
     CODAE_OK = 0,
@@ -85,6 +87,33 @@ enum {
     CODAE_ACT_SOFTPLUS = 5,
     CODAE_ACT_HARDSIGMOID = 6
 };
+
+/* Input noise of the denoising autoencoder (Vincent et al. 2010), applied to the TRAINING input by the gather of the fused step,
+ * before the whole-slot mask (a blanked element is exactly 0 whatever the noise); the loss target stays the clean row.
+ * Random words: Philox4x32-10 (Salmon et al. 2011; multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9, 0xBB67AE85),
+ *   key = (seed & 0xffffffff, seed >> 32), counter = (g, row, step, 0), g = column / 4, row = the DATASET row (row_idx[b], or
+ *   b when row_idx is NULL - never the position in the batch), step = the 1-based Adam step index; the four output words
+ *   r[0..3] belong to columns 4g .. 4g + 3 (a last group that sticks out past io uses its leading words only).
+ * x = the gathered fp32 value, r = its word, T = floor(p 2^32) (formed in double, compared as a 64-bit integer):
+ *   MASKING      x <- 0 iff r < T (no rescaling)                                    p0 = p in [0, 1]
+ *   SALT_PEPPER  r < T: x <- r < T / 2 ? lo : hi                                    p0 = p in [0, 1], p1 = lo, p2 = hi
+ *   GAUSSIAN     x <- x + sigma n; the words of a group in pairs (r0, r1), (r2, r3): u1 = ((ra >> 8) + 1) 2^-24,
+ *                u2 = (rb >> 8) 2^-24, rho = sqrt(-2 ln u1), n_a = rho cos(2 pi u2), n_b = rho sin(2 pi u2)
+ *                                                                                   p0 = sigma >= 0
+ * The same dataset row gets the same noise wherever it sits in a batch and on whichever data-parallel rank (a row that
+ * appears twice in one batch gets the same noise twice; the epoch sampler draws without replacement). */
+enum {
+    CODAE_NOISE_NONE = 0,
+    CODAE_NOISE_GAUSSIAN = 1,
+    CODAE_NOISE_MASKING = 2,
+    CODAE_NOISE_SALT_PEPPER = 3
+};
+
+typedef struct {
+    int32_t kind;       /* CODAE_NOISE_* */
+    float p0, p1, p2;   /* sigma or p; lo, hi (SALT_PEPPER) */
+    uint64_t seed;
+} codae_noise;
 
 typedef struct codae_engine* codae_handle;
 
@@ -295,6 +324,14 @@ int codae_train_step_dp(codae_handle h, const codae_buffers* bufs, const codae_b
 /* 1 if codae_train_step / codae_eval_step with B rows run the persistent chain on this engine and these buffers, 0 if the
  * per-layer launches (tests and bench lines name the path they measured) */
 int codae_step_path(codae_handle h, const codae_buffers* bufs, int32_t B);
+/* Input noise of every training step that follows - codae_train_step, codae_train_step_graph (a change re-captures the
+ * graph; under replay the step index is read from scalars[CODAE_S_ADAM_STEP]), codae_step_forward_loss with a hyper (the
+ * torch.distributed data-parallel path) and codae_train_step_dp, each with hyper->step as the counter's step.  NULL or
+ * CODAE_NOISE_NONE switches it off.  CODAE_E_INVALID for an unknown kind, p outside [0, 1], a negative sigma or a non-finite
+ * parameter (nothing is launched, the previous setting stays).  Evaluation (codae_eval_step, hyper == NULL) is never
+ * noised.  While noise is on the stack stays off the persistent chain kernel, which fuses the gather (codae_step_path
+ * reports 0), exactly as a non-ReLU activation keeps it off. */
+int codae_set_input_noise(codae_handle h, const codae_noise* noise);
 /* validation body (:245-258): forward + metric sums only */
 int codae_eval_step(codae_handle h, const codae_buffers* bufs, const codae_batch* batch, float* out_y,
                     void* stream);
@@ -328,6 +365,17 @@ int codae_profile_end(codae_handle h, int32_t* kinds, float* ms, int32_t capacit
 /* ---- stand-alone ops (also used by the drop-in classes) ------------------- */
 /* model.corrupt(input, mask) = input.clone()*mask (embedding_...py:226-239) */
 int codae_corrupt(const float* x, const float* mask, float* out, int64_t n, void* stream);
+/* The fused step's gather + input noise + slot corruption on its own (the launcher the engine uses): out[b][:] =
+ * mask(noise(data[row_idx[b]][:])), fp32 or (out_bf16 != 0) bf16, rows out_ld elements apart (<= 0: io; columns past io are
+ * not written).  noise NULL or CODAE_NOISE_NONE: the plain gather; `step` is the counter's step word.  noise_rows (NULL: none):
+ * [B] dataset rows for the counter when batch->data is a batch that has ALREADY been gathered (row_idx NULL; the drop-in
+ * scripts hold them as batch_indices) - batch row b is then read at row b and noised as dataset row noise_rows[b]. */
+int codae_corrupt_batch(const codae_batch* batch, const codae_noise* noise, int32_t step, const int32_t* noise_rows, void* out,
+                        int32_t out_bf16, int64_t out_ld, void* stream);
+/* The Gaussian kind's device arithmetic on given words (tools/noise_accuracy.py sweeps all 2^24 values of u1 and of u2 through
+ * it): rho[i] = sqrt(-2 ln u1(ra[i])), c[i] = cos(2 pi u2(rb[i])), s[i] = sin(2 pi u2(rb[i])); the unit normals of a pair are
+ * rho c and rho s. */
+int codae_noise_box_muller(const uint32_t* ra, const uint32_t* rb, float* rho, float* c, float* s, int64_t n, void* stream);
 /* Corrupter.get_masks (data_tool.py:239-262): masks[k][b][:] = table[id_b] if k_of_mask[id_b]==k+1 else 0;
  * fmask = sum_k masks[k].  masks_out is [k_max][B][io] contiguous, fmask_out [B][io]. */
 int codae_expand_masks(const int32_t* mask_id, const uint8_t* mask_table, const int32_t* k_of_mask,

@@ -14,12 +14,14 @@ LIB_PATH = os.environ.get("CODAE_HIP_LIB") or os.path.join(_HERE, "libcodae_hip.
 PREC_F32 = 0
 PREC_BF16 = 1
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 # CODAE_S_* of include/codae_hip.h (tests/test_host_logic.py parses the header and compares)
 S_SQ_FULL, S_SQ_PARTIAL, S_GRAD_SQ, S_LAST_LOSS, S_STEP_SQ, S_CLIP_COEF = 0, 1, 2, 3, 4, 5
 S_GRAD_SQ_SLOTS, S_N_SLOTS, S_ADAM_STEP, S_COUNT = 8, 64, 72, 80
 # CODAE_ACT_* of include/codae_hip.h: the activation after a Linear (codae.model.activation maps torch modules to these)
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_RELU6, ACT_ELU, ACT_SOFTPLUS, ACT_HARDSIGMOID = 0, 1, 2, 3, 4, 5, 6
+# CODAE_NOISE_* of include/codae_hip.h: the input noise of the training steps (codae.tool.InputNoise builds the struct)
+NOISE_NONE, NOISE_GAUSSIAN, NOISE_MASKING, NOISE_SALT_PEPPER = 0, 1, 2, 3
 KERNEL_CLASSES = ("gemm_fwd", "gemm_dgrad", "gemm_wgrad", "loss", "gather", "sumsq", "adam", "slab_reduce", "chain",
                   "bias_finish")
 
@@ -64,6 +66,10 @@ class Hyper(C.Structure):
                 ("step", C.c_int32), ("loss_scale_rows", C.c_float)]
 
 
+class Noise(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("p0", C.c_float), ("p1", C.c_float), ("p2", C.c_float), ("seed", C.c_uint64)]
+
+
 _P, _I32, _I64, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
 # name -> (restype, argtypes); mirrors include/codae_hip.h one to one
@@ -91,6 +97,9 @@ PROTOTYPES = {
     "codae_sync_transposed": (C.c_int, [_P, C.POINTER(Buffers), _P]),
     "codae_train_step": (C.c_int, [_P, C.POINTER(Buffers), C.POINTER(Batch), C.POINTER(Hyper), _P]),
     "codae_train_step_graph": (C.c_int, [_P, C.POINTER(Buffers), C.POINTER(Batch), C.POINTER(Hyper), _P]),
+    "codae_set_input_noise": (C.c_int, [_P, C.POINTER(Noise)]),
+    "codae_corrupt_batch": (C.c_int, [C.POINTER(Batch), C.POINTER(Noise), _I32, _P, _P, _I32, _I64, _P]),
+    "codae_noise_box_muller": (C.c_int, [_P, _P, _P, _P, _P, _I64, _P]),
     "codae_eval_step": (C.c_int, [_P, C.POINTER(Buffers), C.POINTER(Batch), _P, _P]),
     "codae_profile_begin": (C.c_int, [_P, C.c_uint32, _I32]),
     "codae_profile_end": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_float), _I32, C.POINTER(C.c_int32)]),

@@ -83,6 +83,7 @@ class DaeEngine:
             check(self._lib.codae_param_offsets(self._h, l, C.byref(w), C.byref(b), C.byref(s)))
             self.w_off.append(w.value)
             self.b_off.append(b.value)
+        self.input_noise = None
         self.step_count = 0
         self.generation = 0   # bumped by every forward: guards stale backward calls
 
@@ -206,6 +207,16 @@ class DaeEngine:
     def hyper(self, lr, weight_decay, clip=1.0, global_rows=0, betas=(0.9, 0.999), eps=1e-8, step=None):
         return Hyper(lr, weight_decay, betas[0], betas[1], eps, clip if clip else 0.0,
                      self.step_count + 1 if step is None else step, float(global_rows))
+
+    def set_input_noise(self, noise):
+        """noise: a codae.tool.InputNoise, or None to switch it off.  Every training step form that follows applies it to
+        the gathered input before the slot mask (the loss target stays clean; eval steps are never noised); with
+        graph=True the next step re-captures.  While it is on, step_path() is 'layers'."""
+        if noise is not None and not hasattr(noise, "as_struct"):
+            raise HipError("set_input_noise: expected a codae.tool.InputNoise or None, got %r" % (noise,))
+        st = None if noise is None else noise.as_struct()
+        check(self._lib.codae_set_input_noise(self._h, None if st is None else C.byref(st)))
+        self.input_noise = noise
 
     def train_step(self, batch, hyper, graph=False):
         """graph=True: replay the step from a hipGraph (captured on first use; batch.row_idx / mask_id must be

@@ -393,16 +393,22 @@ class HipEmbeddingTrainer:
 
     def __init__(self, schedule, data, mask_table_u8, mask_to_use_i32, lr, weight_decay, clip=1.0,
                  max_batch=8192, precision="bf16", device="cuda:0", distributed=False, n_buckets=None, use_graph=False,
-                 sharded_update=False, native_dp=False, activation=None, n_slots=None):
+                 sharded_update=False, native_dp=False, activation=None, n_slots=None, input_noise=None):
         """use_graph: replay the fused step from a hipGraph (codae_train_step_graph): for launch-bound shapes
         (small batches); single process only - the bucketed data-parallel step is not captured.
         activation: what follows every hidden Linear, as the model classes take it (a factory called as activation(True),
         e.g. torch.nn.ELU); None = ReLU.  Every step form (fused, graph replay, data parallel) runs it.
-        n_slots: categories per row (complete() only; default: read off the mask table)."""
+        n_slots: categories per row (complete() only; default: read off the mask table).
+        input_noise: a codae.tool.InputNoise (Gaussian / masking / salt-and-pepper) applied to the gathered training input
+        before the slot mask, in every step form (fused, graph replay, torch.distributed, sharded, native data parallel);
+        keyed by the dataset row and the optimizer step, so N ranks noise their shards exactly as one process noises the
+        global batch.  eval_batch and complete never apply it.  None = off."""
         from .hip.engine import DaeEngine
         fit_host_threads()      # the loop that feeds this trainer must not get its container CPU-throttled (codae/hostcpu.py)
         self.device = torch.device(device)
         self.engine = DaeEngine(schedule, max_batch, precision, self.device, activation=activation)
+        if input_noise is not None:
+            self.engine.set_input_noise(input_noise)
         self.data = data.to(device=self.device, dtype=torch.float32).contiguous()
         self.mask_table = None if mask_table_u8 is None else mask_table_u8.to(self.device).contiguous()
         self.mask_to_use = None if mask_to_use_i32 is None else mask_to_use_i32.to(self.device).contiguous()

@@ -319,6 +319,13 @@ int launch_chain_step(const ChainArgs& a, hipStream_t s);
 // ---- elementwise / reductions (elementwise.hip) ----------------------------
 // out_ld: row stride of `out` in elements (0 = b->io: contiguous rows)
 int launch_gather_corrupt(const codae_batch* b, void* out, int out_bf16, hipStream_t s, int64_t out_ld = 0);
+// The same gather with the input noise of `noise` (codae_noise, include/codae_hip.h) in front of the slot mask: the noise-enabled
+// instantiations, beside the plain ones above.  step: the counter's step word; step_dev != null: read it from that device scalar
+// instead (graph replay: kernel arguments are frozen at capture); noise_rows: see codae_corrupt_batch.  check_noise: CODAE_E_INVALID with the offending argument named.
+int check_noise(const codae_noise* noise);
+int launch_gather_noise(const codae_batch* b, const codae_noise* noise, int32_t step, const double* step_dev, void* out,
+                        int out_bf16, hipStream_t s, int64_t out_ld = 0, const int32_t* noise_rows = nullptr);
+int launch_noise_box_muller(const uint32_t* ra, const uint32_t* rb, float* rho, float* c, float* sn, int64_t n, hipStream_t s);
 int launch_cast_bf16(const float* src, bf16_t* dst, int64_t n, hipStream_t s);
 int launch_corrupt(const float* x, const float* mask, float* out, int64_t n, hipStream_t s);
 int launch_expand_masks(const int32_t* mask_id, const uint8_t* table, const int32_t* k_of_mask, int B, int io,

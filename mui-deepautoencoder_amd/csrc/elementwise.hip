@@ -124,6 +124,164 @@ __global__ __launch_bounds__(NT) void gather_corrupt_kernel(const float* __restr
     }
 }
 
+// ---- input noise (codae_noise, include/codae_hip.h): the noise-enabled forms of the three gather kernels above -------------
+// Philox4x32-10 keyed by the seed, counter (column / 4, DATASET row, Adam step, 0): one call serves four columns, so a row's
+// noise does not depend on where the row sits in the batch or on which rank.  Noise first, then the slot mask.
+struct NoiseArgs {
+    uint32_t key0, key1;       // seed & 0xffffffff, seed >> 32
+    uint32_t step;             // counter word 2 ...
+    const double* step_dev;    // ... or, when not null, *step_dev (graph replay)
+    const int32_t* rows;       // not null: counter word 1 of batch row b is rows[b] (a batch gathered by the caller), else the row read
+    uint64_t thresh;           // MASKING / SALT_PEPPER: T = floor(p 2^32)
+    float p0, p1, p2;          // sigma; lo, hi
+};
+
+__device__ __forceinline__ uint4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return make_uint4(c0, c1, c2, c3);
+}
+
+// Box-Muller pieces from one pair of words.  u1 in (0, 1] and 2 u2 in [0, 2) are exact in fp32; logf keeps its relative accuracy
+// for u1 next to 1 (rho is a square root of it), sincospif reduces its argument exactly (tools/noise_accuracy.py: every one of
+// the 2^24 values of u1 and of u2 against float64)
+__device__ __forceinline__ void box_muller_parts(uint32_t ra, uint32_t rb, float& rho, float& c, float& sn) {
+    const float u1 = (float)((ra >> 8) + 1u) * 5.9604644775390625e-8f;       // 2^-24
+    const float two_u2 = (float)(rb >> 8) * 1.1920928955078125e-7f;          // 2^-23
+    rho = sqrtf(-2.f * logf(u1));
+    sincospif(two_u2, &sn, &c);
+}
+
+__device__ __forceinline__ float noise_elem(int kind_masking, uint32_t rk, float x, const NoiseArgs& a) {
+    const bool hit = (uint64_t)rk < a.thresh;
+    if (kind_masking) return hit ? 0.f : x;
+    return hit ? ((uint64_t)rk < (a.thresh >> 1) ? a.p1 : a.p2) : x;
+}
+
+// v[0..4) = columns 4g .. 4g + 3 of one row <- noised values; r: the group's four words
+template <int KIND>
+__device__ __forceinline__ void noise_apply4(float* v, const uint4 r, const NoiseArgs& a) {
+    if constexpr (KIND == CODAE_NOISE_GAUSSIAN) {
+        float rho, c, sn;
+        box_muller_parts(r.x, r.y, rho, c, sn);
+        v[0] = fmaf(a.p0, rho * c, v[0]); v[1] = fmaf(a.p0, rho * sn, v[1]);
+        box_muller_parts(r.z, r.w, rho, c, sn);
+        v[2] = fmaf(a.p0, rho * c, v[2]); v[3] = fmaf(a.p0, rho * sn, v[3]);
+    } else {
+        constexpr int M = KIND == CODAE_NOISE_MASKING;
+        v[0] = noise_elem(M, r.x, v[0], a); v[1] = noise_elem(M, r.y, v[1], a);
+        v[2] = noise_elem(M, r.z, v[2], a); v[3] = noise_elem(M, r.w, v[3], a);
+    }
+}
+
+// one column: word k = column % 4 of its group (selects, no indexed register array)
+template <int KIND>
+__device__ __forceinline__ float noise_apply1(float x, const uint4 r, int k, const NoiseArgs& a) {
+    if constexpr (KIND == CODAE_NOISE_GAUSSIAN) {
+        float rho, c, sn;
+        box_muller_parts((k & 2) ? r.z : r.x, (k & 2) ? r.w : r.y, rho, c, sn);
+        return fmaf(a.p0, rho * ((k & 1) ? sn : c), x);
+    } else {
+        const uint32_t rk = (k & 2) ? ((k & 1) ? r.w : r.z) : ((k & 1) ? r.y : r.x);
+        return noise_elem(KIND == CODAE_NOISE_MASKING, rk, x, a);
+    }
+}
+
+template <int KIND>
+__global__ __launch_bounds__(NT) void gather_noise_bf16x8_kernel(const float* __restrict__ data, const int32_t* __restrict__ row_idx,
+                                                                 const int32_t* __restrict__ mask_id, const uint8_t* __restrict__ table,
+                                                                 int B, int io, bf16_t* __restrict__ out,
+                                                                 const int32_t* __restrict__ mask_to_use, int nb_run, int run,
+                                                                 int64_t out_ld, NoiseArgs na) {
+    const bool masked = (mask_id != nullptr) || (mask_to_use != nullptr);
+    const uint32_t step = na.step_dev ? (uint32_t)*na.step_dev : na.step;
+    const int cols = io / 8;
+    const int64_t total = (int64_t)B * cols;
+    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < total; e += (int64_t)gridDim.x * NT) {
+        const int b = (int)(e / cols);
+        const int c = (int)(e - (int64_t)b * cols) * 8;
+        const int64_t src_row = row_idx ? row_idx[b] : b;
+        const float* src = data + src_row * io + c;
+        const float4 x0 = *reinterpret_cast<const float4*>(src);
+        const float4 x1 = *reinterpret_cast<const float4*>(src + 4);
+        float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+        const uint32_t nrow = na.rows ? (uint32_t)na.rows[b] : (uint32_t)src_row;
+        noise_apply4<KIND>(v, philox4x32_10((uint32_t)(c >> 2), nrow, step, 0u, na.key0, na.key1), na);
+        noise_apply4<KIND>(v + 4, philox4x32_10((uint32_t)(c >> 2) + 1u, nrow, step, 0u, na.key0, na.key1), na);
+        if (masked) {
+            const int id = mask_id ? mask_id[b] : mask_to_use[src_row * nb_run + run];
+            const uint2 m = *reinterpret_cast<const uint2*>(table + (int64_t)id * io + c);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = (((k < 4 ? m.x : m.y) >> (8 * (k & 3))) & 0xff) ? v[k] : 0.f;
+        }
+        uint4 o;
+        o.x = pack_bf16x2(v[0], v[1]); o.y = pack_bf16x2(v[2], v[3]);
+        o.z = pack_bf16x2(v[4], v[5]); o.w = pack_bf16x2(v[6], v[7]);
+        *reinterpret_cast<uint4*>(out + (int64_t)b * out_ld + c) = o;
+    }
+}
+
+template <bool VEC, bool OUT_BF16, int KIND>
+__global__ __launch_bounds__(NT) void gather_noise_kernel(const float* __restrict__ data, const int32_t* __restrict__ row_idx,
+                                                          const int32_t* __restrict__ mask_id, const uint8_t* __restrict__ table, int B,
+                                                          int io, void* __restrict__ out, const int32_t* __restrict__ mask_to_use,
+                                                          int nb_run, int run, int64_t out_ld, NoiseArgs na) {
+    constexpr int W = VEC ? 4 : 1;
+    const bool masked = (mask_id != nullptr) || (mask_to_use != nullptr);
+    const uint32_t step = na.step_dev ? (uint32_t)*na.step_dev : na.step;
+    const int cols = io / W;
+    const int64_t total = (int64_t)B * cols;
+    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < total; e += (int64_t)gridDim.x * NT) {
+        const int b = (int)(e / cols);
+        const int c = (int)(e - (int64_t)b * cols) * W;
+        const int64_t src_row = row_idx ? row_idx[b] : b;
+        const float* src = data + src_row * io + c;
+        const uint32_t nrow = na.rows ? (uint32_t)na.rows[b] : (uint32_t)src_row;
+        const uint4 r = philox4x32_10((uint32_t)(c >> 2), nrow, step, 0u, na.key0, na.key1);
+        float v[4];
+        if constexpr (VEC) {
+            const float4 x = *reinterpret_cast<const float4*>(src);
+            v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
+            noise_apply4<KIND>(v, r, na);
+            if (masked) {
+                const int id = mask_id ? mask_id[b] : mask_to_use[src_row * nb_run + run];
+                const uint32_t m = *reinterpret_cast<const uint32_t*>(table + (int64_t)id * io + c);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) v[k] = ((m >> (8 * k)) & 0xff) ? v[k] : 0.f;
+            }
+        } else {
+            v[0] = src[0];
+            v[0] = noise_apply1<KIND>(v[0], r, c & 3, na);
+            if (masked) {
+                const int id = mask_id ? mask_id[b] : mask_to_use[src_row * nb_run + run];
+                v[0] = table[(int64_t)id * io + c] ? v[0] : 0.f;
+            }
+        }
+        const int64_t o = (int64_t)b * out_ld + c;
+        if constexpr (OUT_BF16) {
+            bf16_t* op = reinterpret_cast<bf16_t*>(out) + o;
+            if constexpr (VEC) *reinterpret_cast<uint2*>(op) = pack_bf16x4(v[0], v[1], v[2], v[3]);
+            else op[0] = f32_to_bf16(v[0]);
+        } else {
+            float* op = reinterpret_cast<float*>(out) + o;
+            if constexpr (VEC) *reinterpret_cast<float4*>(op) = make_float4(v[0], v[1], v[2], v[3]);
+            else op[0] = v[0];
+        }
+    }
+}
+
+__global__ __launch_bounds__(NT) void noise_box_muller_kernel(const uint32_t* __restrict__ ra, const uint32_t* __restrict__ rb,
+                                                              float* __restrict__ rho, float* __restrict__ c, float* __restrict__ sn,
+                                                              int64_t n) {
+    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += (int64_t)gridDim.x * NT)
+        box_muller_parts(ra[e], rb[e], rho[e], c[e], sn[e]);
+}
+
 __global__ __launch_bounds__(NT) void cast_bf16_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst,
                                                        int64_t n) {
     const int64_t n4 = n / 4;
@@ -653,6 +811,73 @@ int launch_gather_corrupt(const codae_batch* b, void* out, int out_bf16, hipStre
     else if (out_bf16) GC(false, true);
     else GC(false, false);
 #undef GC
+    CODAE_LAUNCH_CHECK();
+    return CODAE_OK;
+}
+
+static bool finite_f(float x) { return x == x && fabsf(x) <= 3.402823466e38f; }
+
+int check_noise(const codae_noise* n) {
+    if (n == nullptr || n->kind == CODAE_NOISE_NONE) return CODAE_OK;
+    CODAE_REQUIRE(n->kind == CODAE_NOISE_GAUSSIAN || n->kind == CODAE_NOISE_MASKING || n->kind == CODAE_NOISE_SALT_PEPPER,
+                  "input noise: unknown kind %d", n->kind);
+    if (n->kind == CODAE_NOISE_GAUSSIAN) {
+        CODAE_REQUIRE(finite_f(n->p0) && n->p0 >= 0.f, "input noise: sigma %g must be finite and >= 0", (double)n->p0);
+        return CODAE_OK;
+    }
+    CODAE_REQUIRE(finite_f(n->p0) && n->p0 >= 0.f && n->p0 <= 1.f, "input noise: p %g outside [0, 1]", (double)n->p0);
+    if (n->kind == CODAE_NOISE_SALT_PEPPER) {
+        CODAE_REQUIRE(finite_f(n->p1), "input noise: lo %g is not finite", (double)n->p1);
+        CODAE_REQUIRE(finite_f(n->p2), "input noise: hi %g is not finite", (double)n->p2);
+    }
+    return CODAE_OK;
+}
+
+int launch_gather_noise(const codae_batch* b, const codae_noise* noise, int32_t step, const double* step_dev, void* out, int out_bf16,
+                        hipStream_t s, int64_t out_ld, const int32_t* noise_rows) {
+    if (noise == nullptr || noise->kind == CODAE_NOISE_NONE) return launch_gather_corrupt(b, out, out_bf16, s, out_ld);
+    int rc = check_noise(noise);
+    if (rc) return rc;
+    if (out_ld <= 0) out_ld = b ? b->io : 0;
+    CODAE_REQUIRE(b && b->data && out && b->B > 0 && b->io > 0, "gather_corrupt: bad batch");
+    const bool masked = b->mask_id || b->mask_to_use;
+    CODAE_REQUIRE(!masked || b->mask_table, "gather_corrupt: mask ids without mask_table");
+    CODAE_REQUIRE(!b->mask_to_use || b->mask_id || (b->nb_run > 0 && b->run >= 0 && b->run < b->nb_run),
+                  "gather_corrupt: run %d outside [0, %d)", b->run, b->nb_run);
+    NoiseArgs na{};
+    na.key0 = (uint32_t)(noise->seed & 0xffffffffu); na.key1 = (uint32_t)(noise->seed >> 32);
+    na.step = (uint32_t)step; na.step_dev = step_dev; na.rows = noise_rows;
+    na.thresh = (uint64_t)floor((double)noise->p0 * 4294967296.0);      // (p <= 1: at most 2^32, above every word)
+    na.p0 = noise->p0; na.p1 = noise->p1; na.p2 = noise->p2;
+    const bool vec = (b->io % 4 == 0) && (out_ld % 4 == 0) && a16(b->data) && a16(out) && (!masked || (reinterpret_cast<uintptr_t>(b->mask_table) & 3) == 0);
+    const int64_t items = (int64_t)b->B * (vec ? b->io / 4 : b->io);
+    const int grid = grid_for(items);
+    const bool x8 = vec && out_bf16 && b->io % 8 == 0 && (!masked || (reinterpret_cast<uintptr_t>(b->mask_table) & 7) == 0);
+#define GN8(K) hipLaunchKernelGGL((gather_noise_bf16x8_kernel<K>), dim3(grid_for(items / 2)), dim3(NT), 0, s, b->data, b->row_idx, b->mask_id, \
+                                  b->mask_table, b->B, b->io, reinterpret_cast<bf16_t*>(out), b->mask_to_use, b->nb_run, b->run, out_ld, na)
+#define GN(V, O, K) hipLaunchKernelGGL((gather_noise_kernel<V, O, K>), dim3(grid), dim3(NT), 0, s, b->data, b->row_idx, b->mask_id, \
+                                       b->mask_table, b->B, b->io, out, b->mask_to_use, b->nb_run, b->run, out_ld, na)
+#define GN_KIND(K)                           \
+    do {                                     \
+        if (x8) GN8(K);                      \
+        else if (vec && out_bf16) GN(true, true, K);  \
+        else if (vec) GN(true, false, K);    \
+        else if (out_bf16) GN(false, true, K);        \
+        else GN(false, false, K);            \
+    } while (0)
+    if (noise->kind == CODAE_NOISE_GAUSSIAN) GN_KIND(CODAE_NOISE_GAUSSIAN);
+    else if (noise->kind == CODAE_NOISE_MASKING) GN_KIND(CODAE_NOISE_MASKING);
+    else GN_KIND(CODAE_NOISE_SALT_PEPPER);
+#undef GN_KIND
+#undef GN
+#undef GN8
+    CODAE_LAUNCH_CHECK();
+    return CODAE_OK;
+}
+
+int launch_noise_box_muller(const uint32_t* ra, const uint32_t* rb, float* rho, float* c, float* sn, int64_t n, hipStream_t s) {
+    CODAE_REQUIRE(ra && rb && rho && c && sn && n > 0, "noise_box_muller: bad args");
+    hipLaunchKernelGGL(noise_box_muller_kernel, dim3(grid_for(n)), dim3(NT), 0, s, ra, rb, rho, c, sn, n);
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;
 }

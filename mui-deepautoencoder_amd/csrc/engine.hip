@@ -94,6 +94,7 @@ struct codae_engine {
     int64_t loss_part_off = 0;       // (floats, 8-byte aligned) per-workgroup metric sums of the loss kernels
     int loss_part_cap = 0;
     bool chain_ok = false;           // narrow bf16 stack: codae_train_step may take the persistent fused chain
+    codae_noise noise{};             // input noise of the training steps (codae_set_input_noise); kind NONE = off
     mutable std::vector<int> parts_pending;
     // optional per-launch hipEvent pairs (codae_profile_begin / _end)
     // backward on two streams: the weight-gradient GEMMs (+ slab reduce) run on `side`, concurrently with
@@ -116,7 +117,7 @@ struct codae_engine {
     // codae_train_step_graph: the captured step and what it was captured for
     mutable hipGraphExec_t graph_exec = nullptr;
     mutable bool capturing = false;          // inside stream capture: device-side Adam step, everything joined at the end
-    struct GraphKey { codae_batch batch; codae_hyper hyper; codae_buffers bufs; } mutable graph_key{};
+    struct GraphKey { codae_batch batch; codae_hyper hyper; codae_buffers bufs; codae_noise noise; } mutable graph_key{};
     mutable std::vector<hipEvent_t> prof_start, prof_stop;
     mutable std::vector<int> prof_kind;
     mutable std::vector<int> prof_count;    // launches covered by the record (a GroupScope spans several)
@@ -340,7 +341,8 @@ int finish_bias(const codae_engine* e, const codae_buffers* b, hipStream_t s, bo
 constexpr int CHAIN_MAX_ROWS = 2048;
 
 bool chain_eligible(const codae_engine* e, const codae_buffers* b, int B) {
-    return e->chain_ok && b->shadow_wt != nullptr && e->rows_for(B) <= CHAIN_MAX_ROWS;
+    // (the chain kernel fuses the plain gather: a noised input takes the per-layer launches)
+    return e->chain_ok && e->noise.kind == CODAE_NOISE_NONE && b->shadow_wt != nullptr && e->rows_for(B) <= CHAIN_MAX_ROWS;
 }
 
 // gather + forward chain + loss (+ data-gradient chain) of a narrow stack: one launch; then the loss finish
@@ -1122,7 +1124,11 @@ int codae_step_forward_loss(codae_handle h, const codae_buffers* b, const codae_
     const bool bf = h->prec == CODAE_PREC_BF16;
     {
         ProfScope prof(h, CODAE_K_GATHER, s);
-        rc = launch_gather_corrupt(batch, act_ptr(h, b, 0), bf, s, h->in_ld[0]);
+        if (hyper != nullptr && h->noise.kind != CODAE_NOISE_NONE)      // training input only; the loss below reads the clean row
+            rc = launch_gather_noise(batch, &h->noise, hyper->step, h->capturing ? b->scalars + CODAE_S_ADAM_STEP : nullptr,
+                                     act_ptr(h, b, 0), bf, s, h->in_ld[0]);
+        else
+            rc = launch_gather_corrupt(batch, act_ptr(h, b, 0), bf, s, h->in_ld[0]);
     }
     if (rc) return rc;
     rc = zero_pad_rows(h, act_ptr(h, b, 0), B, rows, h->in_ld[0], s);
@@ -1185,6 +1191,19 @@ int codae_step_forward_loss(codae_handle h, const codae_buffers* b, const codae_
     rc = launch_mse_loss(batch, y, nullptr, 0, 0.f, nullptr, loss_parts_ptr(h, b), 0, s);
     if (rc) return rc;
     return launch_finish_loss(b->scalars, 1.0 / ((double)B * batch->io), s, loss_parts_ptr(h, b), mse_loss_colsum_rows(B));
+}
+
+int codae_set_input_noise(codae_handle h, const codae_noise* noise) {
+    CODAE_REQUIRE(h != nullptr, "codae_set_input_noise: null handle");
+    int rc = check_noise(noise);
+    if (rc) return rc;
+    codae_noise n{};                     // (built field by field: the graph key compares bytes, padding included)
+    if (noise != nullptr && noise->kind != CODAE_NOISE_NONE) {
+        n.kind = noise->kind; n.p0 = noise->p0; n.seed = noise->seed;
+        if (noise->kind == CODAE_NOISE_SALT_PEPPER) { n.p1 = noise->p1; n.p2 = noise->p2; }
+    }
+    h->noise = n;
+    return CODAE_OK;
 }
 
 int codae_eval_step(codae_handle h, const codae_buffers* b, const codae_batch* batch, float* out_y, void* stream) {
@@ -1362,7 +1381,8 @@ int codae_train_step_graph(codae_handle h, const codae_buffers* b, const codae_b
     codae_hyper hk = *hyper;
     hk.step = 0;
     const bool fresh = h->graph_exec == nullptr || !same_bytes(&h->graph_key.batch, batch, sizeof(*batch)) ||
-                       !same_bytes(&h->graph_key.hyper, &hk, sizeof(hk)) || !same_bytes(&h->graph_key.bufs, b, sizeof(*b));
+                       !same_bytes(&h->graph_key.hyper, &hk, sizeof(hk)) || !same_bytes(&h->graph_key.bufs, b, sizeof(*b)) ||
+                       !same_bytes(&h->graph_key.noise, &h->noise, sizeof(h->noise));
     if (fresh) {
         if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
         int rc = check_common(h, b, batch->B);
@@ -1391,7 +1411,7 @@ int codae_train_step_graph(codae_handle h, const codae_buffers* b, const codae_b
             set_error("codae_train_step_graph: hipGraphInstantiate failed: %s", hipGetErrorString(ei));
             return CODAE_E_HIP;
         }
-        h->graph_key.batch = *batch; h->graph_key.hyper = hk; h->graph_key.bufs = *b;
+        h->graph_key.batch = *batch; h->graph_key.hyper = hk; h->graph_key.bufs = *b; h->graph_key.noise = h->noise;
     }
     int rc = launch_set_scalar(b->scalars + CODAE_S_ADAM_STEP, (double)hyper->step, s);
     if (rc) return rc;
@@ -1497,6 +1517,16 @@ int codae_train_step_dp(codae_handle h, const codae_buffers* b, const codae_batc
 
 int codae_corrupt(const float* x, const float* mask, float* out, int64_t n, void* stream) {
     return launch_corrupt(x, mask, out, n, (hipStream_t)stream);
+}
+
+int codae_corrupt_batch(const codae_batch* batch, const codae_noise* noise, int32_t step, const int32_t* noise_rows, void* out,
+                        int32_t out_bf16, int64_t out_ld, void* stream) {
+    CODAE_REQUIRE(noise_rows == nullptr || (batch != nullptr && batch->row_idx == nullptr), "codae_corrupt_batch: noise_rows go with an already gathered batch (row_idx NULL)");
+    return launch_gather_noise(batch, noise, step, nullptr, out, out_bf16, (hipStream_t)stream, out_ld, noise_rows);
+}
+
+int codae_noise_box_muller(const uint32_t* ra, const uint32_t* rb, float* rho, float* c, float* s, int64_t n, void* stream) {
+    return launch_noise_box_muller(ra, rb, rho, c, s, n, (hipStream_t)stream);
 }
 
 int codae_expand_masks(const int32_t* mask_id, const uint8_t* mask_table, const int32_t* k_of_mask, int32_t B, int32_t io,

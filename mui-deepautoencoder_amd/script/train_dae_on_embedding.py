@@ -104,12 +104,16 @@ def main():
     if act_name and not (isinstance(activation, type) and issubclass(activation, torch.nn.Module)):
         raise HipError("HIP: ACTIVATION: %r is not a torch.nn module" % act_name)
     dataset.to(device)
+    # HIP: INPUT_NOISE: {KIND: gaussian | masking | salt_pepper, SIGMA | P: ..., LO: ..., HI: ..., SEED: ...} (build-only key):
+    # noise on the training input in front of the slot blank; LO / HI default to the resident data's min / max
+    from codae.tool.noise import input_noise_from_config
+    input_noise = input_noise_from_config(config.get("HIP", {}).get("INPUT_NOISE"), dataset.data)
 
     def build(prec):
         return HipEmbeddingTrainer(enc + dec, dataset.data, corrupter.mask_table_u8, corrupter.mask_to_use_i32,
                                    mc["LEARNING_RATE"], mc["WEIGHT_DECAY"], clip=1.0 if mc["TRUNK_GRAD"] else 0.0,
                                    max_batch=mc["BATCH_SIZE"], precision=prec, device=device, distributed=world > 1,
-                                   activation=activation)
+                                   activation=activation, input_noise=input_noise)
     try:
         trainer = build(precision)
     except HipError as e:
