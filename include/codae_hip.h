@@ -78,6 +78,21 @@ enum {
  *                (torch.nn.ELU: l = 1, b = 1; CELU: l = 1, b = a; SELU: torch's l and a, b = 1)
  *   SOFTPLUS     b v > t ? v : log1p(exp(b v)) / b   dy/dv = b y > t ? 1 : -expm1(-b y) p = {b > 0, t}
  *   HARDSIGMOID  clamp(v / 6 + 1/2, 0, 1)            dy/dv = 0 < y < 1 ? 1/6 : 0       - */
+/* Non-finite values.  The kernels follow torch, so that a diverged run looks diverged (tests/test_gpu_nonfinite.py):
+ *   1. every forward epilogue computes act(v) as torch.nn's module does for a non-finite v: NaN stays NaN for every CODAE_ACT_*
+ *      and for the identity (ReLU is an IEEE 754-2019 maximum, not a max that drops the NaN operand); +-Inf maps as the module
+ *      maps it (ReLU: +Inf, 0; ReLU6: 6, 0; ELU: +Inf, -l a; Softplus: +Inf, 0; Hardsigmoid: 1, 0).  The backward of ReLU, ReLU6 and
+ *      Hardsigmoid SELECTS (0 under a dead unit whatever the incoming gradient), every other kind multiplies, as torch's do.
+ *   2. GEMM arithmetic propagates as IEEE does: an output is NaN, +Inf or -Inf exactly where the float64 product of the same
+ *      operands is, and a non-finite operand touches only the outputs that depend on it (ragged tiles, clamped loads, column-sum
+ *      partials and split-K slabs included).
+ *   3. a NaN total gradient norm gives a NaN clip coefficient - every parameter, both Adam moments and the bf16 shadows are NaN
+ *      after the update, as after clip_grad_norm_ + Adam.step; a total of +Inf gives coefficient 0 (torch.clamp(max=1), not fminf).
+ *   4. a training or evaluation step whose reference loss is non-finite reports a non-finite CODAE_S_LAST_LOSS and non-finite
+ *      epoch sums, never a finite one.
+ *   5. the one exception: the bf16-plane fp32 GEMM (CODAE_PREC_F32 above, gemm_f32x3.hip) turns an Inf ELEMENT of an operand
+ *      into NaN at the outputs that depend on it - the residual planes of an Inf are Inf - Inf.  Never a finite value, and not
+ *      for an Inf bias, which is added in fp32.  CODAE_F32_GEMM=native has no exception. */
 enum {
     CODAE_ACT_NONE = 0,
     CODAE_ACT_RELU = 1,
@@ -203,7 +218,8 @@ typedef struct {
 
 typedef struct {
     float lr, weight_decay, beta1, beta2, eps; /* torch.optim.Adam (train_dae_on_embedding.py:160-163) */
-    float max_grad_norm;   /* clip_grad_norm_(params, 1) (:213); <= 0 disables clipping */
+    float max_grad_norm;   /* clip_grad_norm_(params, 1) (:213); <= 0 disables clipping.  A NaN norm gives a NaN coefficient,
+                            * an infinite one 0 ("Non-finite values" above, point 3) */
     int32_t step;          /* 1-based Adam step index t */
     float loss_scale_rows; /* rows of the GLOBAL batch (data-parallel: sum over ranks); 0 = batch.B */
 } codae_hyper;

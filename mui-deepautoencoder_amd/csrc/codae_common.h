@@ -61,11 +61,15 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
     const f32x2_t v = {lo, hi};
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
 }
-// max(x, floor) as exactly one VALU op: fmaxf() puts a canonicalising v_max in front of the real one.
+// max(x, floor) that keeps a NaN x a NaN, as torch.relu does (include/codae_hip.h, "Non-finite values"), in ONE VALU op:
+// gfx950's v_maximum3_f32 is IEEE 754-2019 maximum (NaN-propagating).  v_max_f32 and fmaxf() return the OTHER operand for a
+// NaN - 0 under ReLU, -inf under the identity; a compare + select keeps it but costs a second op per element (measured: +0.4 %
+// of the C3 step, about +1 % of C2).
 // The GEMM epilogues clamp at `floor` = 0 (ReLU) or -inf (identity), so the ReLU switch costs no branch.
+// Every ReLU site of the library goes through this one form, so that they agree bit for bit.
 __device__ __forceinline__ float clamp_below(float x, float floor) {
     float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(floor), "v"(x));
+    asm("v_maximum3_f32 %0, %1, %2, %2" : "=v"(r) : "v"(x), "v"(floor));
     return r;
 }
 
@@ -105,12 +109,12 @@ __device__ __forceinline__ float act_log1p(float t) {     // t log(1 + t) / ((1 
 }
 __device__ __forceinline__ float act_fwd_(int kind, const float* p, float v) {
     switch (kind) {
-        case CODAE_ACT_RELU: return v > 0.f ? v : 0.f;
+        case CODAE_ACT_RELU: return clamp_below(v, 0.f);              // (NaN stays NaN: every kind, as torch.nn's modules)
         case CODAE_ACT_LEAKY: return v > 0.f ? v : v * p[0];
         case CODAE_ACT_RELU6: return v <= 0.f ? 0.f : (v >= 6.f ? 6.f : v);
         case CODAE_ACT_ELU: return v > 0.f ? v * p[0] : act_expm1(v * p[2]) * act_opaque(p[1] * p[0]);
         case CODAE_ACT_SOFTPLUS: return v * p[0] > p[1] ? v : act_log1p(act_exp(v * p[0])) * act_rcp(p[0]);
-        case CODAE_ACT_HARDSIGMOID: return fminf(fmaxf(v + 3.f, 0.f), 6.f) * (1.f / 6.f);
+        case CODAE_ACT_HARDSIGMOID: { const float t = clamp_below(v + 3.f, 0.f); return (t > 6.f ? 6.f : t) * (1.f / 6.f); }
         default: return v;
     }
 }
@@ -138,6 +142,14 @@ __device__ __forceinline__ float act_dy_from_y(int kind, const float* p, float y
     return r;
 }
 
+// g * act'(y) as torch's backward forms it: ReLU, ReLU6 and Hardsigmoid SELECT (0 where the derivative is 0, whatever g is - a
+// NaN or Inf gradient does not leak through a dead unit), every other kind multiplies (NaN * 0 = NaN there, in torch too)
+__device__ __forceinline__ float act_bwd(int kind, const float* p, float g, float y) {
+    const float d = act_dy_from_y(kind, p, y);
+    const bool selects = kind == CODAE_ACT_RELU || kind == CODAE_ACT_RELU6 || kind == CODAE_ACT_HARDSIGMOID;
+    return (selects && d == 0.f) ? 0.f : g * d;
+}
+
 // f(std::integral_constant<int, kind>): one switch per thread around a whole epilogue instead of one per element (a loop body
 // small enough to unroll fully - the accumulators stay in registers)
 template <typename F>
@@ -155,8 +167,8 @@ __device__ __forceinline__ void act_dispatch(int kind, F&& f) {
 
 // data gradient of a bf16 pair: (g_lo, g_hi) * act'(saved pair (h_lo, h_hi)), rounded to bf16 again (the ReLU code masks instead)
 __device__ __forceinline__ uint32_t act_dgrad_bf16x2(int kind, const float* p, uint32_t g2, uint32_t h2) {
-    const float lo = bf16_to_f32((bf16_t)(g2 & 0xffffu)) * act_dy_from_y(kind, p, bf16_to_f32((bf16_t)(h2 & 0xffffu)));
-    const float hi = bf16_to_f32((bf16_t)(g2 >> 16)) * act_dy_from_y(kind, p, bf16_to_f32((bf16_t)(h2 >> 16)));
+    const float lo = act_bwd(kind, p, bf16_to_f32((bf16_t)(g2 & 0xffffu)), bf16_to_f32((bf16_t)(h2 & 0xffffu)));
+    const float hi = act_bwd(kind, p, bf16_to_f32((bf16_t)(g2 >> 16)), bf16_to_f32((bf16_t)(h2 >> 16)));
     return pack_bf16x2(lo, hi);
 }
 

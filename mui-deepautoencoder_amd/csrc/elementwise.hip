@@ -493,9 +493,14 @@ __global__ __launch_bounds__(NT) void sumsq_to_kernel(const float* __restrict__ 
 }
 
 // clip_grad_norm_'s coefficient from a total sum g^2 (train_dae_on_embedding.py:213): min(1, max_norm / (norm + 1e-6))
+// as torch.clamp(max=1): a NaN norm gives a NaN coefficient (fminf would give 1), an infinite one gives 0
+__device__ __forceinline__ float clip_coef(float max_norm, float total) {
+    const float r = max_norm / (total + 1e-6f);
+    return r > 1.f ? 1.f : r;
+}
 __global__ void clip_coef_kernel(const double* total_sq, float max_norm, double* coef_out) {
     const float total = sqrtf((float)*total_sq);
-    *coef_out = (double)fminf(1.f, max_norm / (total + 1e-6f));
+    *coef_out = (double)clip_coef(max_norm, total);
 }
 
 // ---- a7 + a8: clip scale folded into Adam (torch.optim.Adam, amsgrad off, L2 decay) ----------
@@ -537,7 +542,7 @@ __global__ __launch_bounds__(NT) void clip_adam_kernel(float* __restrict__ p, co
         }
         __syncthreads();
         const float total = sqrtf((float)total_sq);
-        coef = fminf(1.f, c.max_norm / (total + 1e-6f));
+        coef = clip_coef(c.max_norm, total);
     }
     const int64_t n4 = n / 4;  // n is padded to a multiple of 64 by the engine; tail handled below anyway
     for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n4; e += (int64_t)gridDim.x * NT) {
@@ -626,13 +631,13 @@ __global__ __launch_bounds__(NT) void reduce_slabs_epi_kernel(const float* __res
                 const float p[3] = {p0, p1, p2};
                 if (relu_src != nullptr) {
                     const float4 h = *reinterpret_cast<const float4*>(relu_src + (int64_t)i * ld_relu + j);
-                    a.x *= act_dy_from_y(act, p, h.x); a.y *= act_dy_from_y(act, p, h.y);
-                    a.z *= act_dy_from_y(act, p, h.z); a.w *= act_dy_from_y(act, p, h.w);
+                    a.x = act_bwd(act, p, a.x, h.x); a.y = act_bwd(act, p, a.y, h.y);
+                    a.z = act_bwd(act, p, a.z, h.z); a.w = act_bwd(act, p, a.w, h.w);
                 } else {
                     a.x = act_fwd(act, p, a.x); a.y = act_fwd(act, p, a.y); a.z = act_fwd(act, p, a.z); a.w = act_fwd(act, p, a.w);
                 }
             } else {
-                if (relu) { a.x = fmaxf(a.x, 0.f); a.y = fmaxf(a.y, 0.f); a.z = fmaxf(a.z, 0.f); a.w = fmaxf(a.w, 0.f); }
+                if (relu) { a.x = clamp_below(a.x, 0.f); a.y = clamp_below(a.y, 0.f); a.z = clamp_below(a.z, 0.f); a.w = clamp_below(a.w, 0.f); }
                 if (relu_src != nullptr) {
                     const float4 h = *reinterpret_cast<const float4*>(relu_src + (int64_t)i * ld_relu + j);
                     a.x = h.x > 0.f ? a.x : 0.f; a.y = h.y > 0.f ? a.y : 0.f; a.z = h.z > 0.f ? a.z : 0.f; a.w = h.w > 0.f ? a.w : 0.f;
@@ -993,7 +998,7 @@ __global__ __launch_bounds__(NT) void clip_adam_tiled_kernel(float* __restrict__
             if (threadIdx.x == 0) total_sq = sv + grad_sq[0];
         }
         __syncthreads();
-        coef = fminf(1.f, c.max_norm / (sqrtf((float)total_sq) + 1e-6f));
+        coef = clip_coef(c.max_norm, sqrtf((float)total_sq));
     }
     const int n_tiles = jobs.tile_begin[jobs.n_layers];
     if ((int)blockIdx.x >= n_tiles) {

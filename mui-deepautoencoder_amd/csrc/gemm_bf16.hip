@@ -580,7 +580,7 @@ __device__ __forceinline__ void gemm_bf16_tile(const GemmBf16& g, int tiles_n, i
                         f32x4 v = acc[mt][nt];
                         v[0] += bj.x; v[1] += bj.y; v[2] += bj.z; v[3] += bj.w;
                         if (!ACT && g.relu) {          // (ACT: applied in the write-out pass below)
-                            v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f);
+                            v[0] = clamp_below(v[0], 0.f); v[1] = clamp_below(v[1], 0.f); v[2] = clamp_below(v[2], 0.f); v[3] = clamp_below(v[3], 0.f);
                         }
                         *reinterpret_cast<__attribute__((address_space(3))) f32x4*>(smem + il * PITCH + jl * 4) = v;
                     }

@@ -188,7 +188,7 @@ __global__ __launch_bounds__(NT) void gemm_f32_kernel(GemmF32 g, bool a_vec, boo
                         const int i = i0 + 64 * wr + 32 * mi + (r & 3) + 8 * (r >> 2) + 4 * kh;
                         if (i < g.M && j < g.N) {
                             float v = acc[mi][ni][r] + bj;
-                            if (g.relu_src != nullptr) v *= act_dy_from_y(KIND, g.act_p, g.relu_src[(int64_t)i * g.ld_relu + j]);
+                            if (g.relu_src != nullptr) v = act_bwd(KIND, g.act_p, v, g.relu_src[(int64_t)i * g.ld_relu + j]);
                             else v = act_fwd(KIND, g.act_p, v);
                             g.C[(int64_t)i * g.ldc + j] = v;
                             csum += v;
@@ -215,7 +215,7 @@ __global__ __launch_bounds__(NT) void gemm_f32_kernel(GemmF32 g, bool a_vec, boo
                 const int i = i0 + 64 * wr + 32 * mi + (r & 3) + 8 * (r >> 2) + 4 * kh;
                 if (i < g.M && j < g.N) {
                     float v = acc[mi][ni][r] + bj;
-                    if (g.relu) v = fmaxf(v, 0.f);
+                    if (g.relu) v = clamp_below(v, 0.f);
                     if (g.relu_src != nullptr) v = (g.relu_src[(int64_t)i * g.ld_relu + j] > 0.f) ? v : 0.f;
                     g.C[(int64_t)i * g.ldc + j] = v;
                     csum += v;

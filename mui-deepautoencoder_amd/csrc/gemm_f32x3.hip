@@ -352,7 +352,7 @@ __device__ __forceinline__ void x3_tile(GemmF32 g, int tile_m, int tile_n, int z
                 for (int r = 0; r < 4; ++r) {
                     v[r] = acc[mt][nt][r] + bj[r];
                     if constexpr (!ACT) {
-                        if (g.relu) v[r] = fmaxf(v[r], 0.f);
+                        if (g.relu) v[r] = clamp_below(v[r], 0.f);
                     }
                 }
                 if constexpr (ACT) {
@@ -367,7 +367,7 @@ __device__ __forceinline__ void x3_tile(GemmF32 g, int tile_m, int tile_n, int z
                             for (int r = 0; r < 4; ++r) h[r] = j + r < g.N ? m[r] : 0.f;
                         }
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] *= act_dy_from_y(g.act, g.act_p, h[r]);
+                        for (int r = 0; r < 4; ++r) v[r] = act_bwd(g.act, g.act_p, v[r], h[r]);
                     } else {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) v[r] = act_fwd(g.act, g.act_p, v[r]);

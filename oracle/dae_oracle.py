@@ -362,14 +362,17 @@ def backward(params, relu_flags, acts, dy, quant=None):
 
 def clip_grad_norm(grads, max_norm=1.0):
     """torch.nn.utils.clip_grad_norm_(params, 1) (train_dae_on_embedding.py:213):
-    total = ||(||g_i||)||_2 ; g *= min(1, max_norm / (total + 1e-6)).
+    total = ||(||g_i||)||_2 ; g *= clamp(max_norm / (total + 1e-6), max=1): NaN for a NaN norm.
     Returns (clipped grads, total_norm)."""
-    sq = F32(0)
-    for gw, gb in grads:
-        sq = sq + F32(np.sum(gw.astype(F32) ** 2, dtype=F32)) + F32(np.sum(gb ** 2, dtype=F32))
-    total = F32(np.sqrt(sq))
-    coef = F32(min(1.0, float(max_norm) / (float(total) + 1e-6)))
-    return [((gw * coef).astype(F32), (gb * coef).astype(F32)) for gw, gb in grads], total
+    with np.errstate(all="ignore"):
+        sq = F32(0)
+        for gw, gb in grads:
+            sq = sq + F32(np.sum(gw.astype(F32) ** 2, dtype=F32)) + F32(np.sum(gb ** 2, dtype=F32))
+        total = F32(np.sqrt(sq))
+        r = float(max_norm) / (float(total) + 1e-6)
+        # torch.clamp(max=1): a NaN norm gives a NaN coefficient (Python's min(1.0, nan) is 1.0), an infinite one gives 0
+        coef = F32(1.0 if r > 1.0 else r)
+        return [((gw * coef).astype(F32), (gb * coef).astype(F32)) for gw, gb in grads], total
 
 
 def adam_init(params):
