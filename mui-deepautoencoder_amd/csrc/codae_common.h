@@ -292,6 +292,7 @@ int gemm_bf16_colsum_rows(const GemmBf16& g);   // rows of colsum_part this laun
 int gemm_bf16_loss_parts(const GemmBf16& g);    // workgroups of the fused-loss launch = rows of LossFuse::parts
 int gemm_bf16(const GemmBf16& g, hipStream_t s);
 int gemm_bf16_pipe(const GemmBf16& g, int cfg, hipStream_t s);   // gemm_bf16_pipe.hip
+int choose_split_k(int N, int K, int rows);     // engine.hip: split-K factor of the weight gradient dW[N][K] over `rows` batch rows
 
 // several independent GEMMs (here: the weight gradients of every layer of a narrow stack) in ONE launch; tile
 // configuration 128 x 128 for all of them

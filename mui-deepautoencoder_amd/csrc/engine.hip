@@ -1,4 +1,4 @@
-// C-ABI entry points of libcodae_hip.so and the per-model engine that chains the kernels
+// The per-model engine of libcodae_hip.so and its C-ABI entry points: it chains the kernels
 // into the DAE training step (script/train_dae_on_embedding.py:198-215 of the reference).
 #include <stdarg.h>
 #include <stdlib.h>
@@ -7,8 +7,7 @@
 #include <cmath>
 #include <vector>
 
-#include "codae_common.h"
-#include <cstring>
+#include "layer_gemm.h"
 #include <dlfcn.h>
 #include <rccl/rccl.h>      // types and prototypes only: the library is dlopen()ed (codae_dp_init), libcodae_hip.so does not link it
 
@@ -95,33 +94,30 @@ struct codae_engine {
     int loss_part_cap = 0;
     bool chain_ok = false;           // narrow bf16 stack: codae_train_step may take the persistent fused chain
     codae_noise noise{};             // input noise of the training steps (codae_set_input_noise); kind NONE = off
-    mutable std::vector<int> parts_pending;
-    // optional per-launch hipEvent pairs (codae_profile_begin / _end)
+    std::vector<int> parts_pending;
     // backward on two streams: the weight-gradient GEMMs (+ slab reduce) run on `side`, concurrently with
     // the data-gradient chain on the caller's stream (they only share the read-only dA_l)
-    mutable hipStream_t side = nullptr;
-    mutable hipEvent_t ev_ready[CODAE_MAX_DACT] = {}, ev_join = nullptr, ev_w[CODAE_MAX_DACT] = {};
-    mutable unsigned ready_turn = 0;        // ev_ready is used round robin: an event is re-recorded 16 hand-offs later at the earliest
+    hipStream_t side = nullptr;
+    hipEvent_t ev_ready[CODAE_MAX_DACT] = {}, ev_join = nullptr, ev_w[CODAE_MAX_DACT] = {};
+    unsigned ready_turn = 0;        // ev_ready is used round robin: an event is re-recorded 16 hand-offs later at the earliest
     // dA buffer i is still being read by a side-stream wgrad (event ev_w[i]); kept across calls so that a backward
     // issued bucket by bucket without joins (codae_step_backward_async) stays ordered
-    mutable bool w_pending[CODAE_MAX_DACT] = {};
-    mutable bool side_dirty = false;      // side-stream work not yet joined into the caller's stream
-    mutable bool bwd_coscheduled = false; // inside a backward whose weight gradients run beside the data-gradient chain (GemmBf16::coscheduled)
-    // single-GPU fused step: the slab reduce of every layer also accumulates sum g^2 (clip_grad_norm_)
-    mutable bool norm_in_backward = false;
-    mutable bool norm_scalars_zero = false;   // finish_loss of this step zeroed GRAD_SQ + its slots and nothing added since
-    mutable bool prof_on = false;
-    mutable uint32_t prof_mask = 0;
-    mutable int prof_n = 0;
-    mutable int prof_every = 1, prof_step = 0;   // launches are timed in every prof_every-th training step only
+    bool w_pending[CODAE_MAX_DACT] = {};
+    bool side_dirty = false;      // side-stream work not yet joined into the caller's stream
+    bool norm_scalars_zero = false;   // finish_loss of this step zeroed GRAD_SQ + its slots and nothing added since
+    // optional per-launch hipEvent pairs (codae_profile_begin / _end)
+    bool prof_on = false;
+    uint32_t prof_mask = 0;
+    int prof_n = 0;
+    int prof_every = 1, prof_step = 0;   // launches are timed in every prof_every-th training step only
     // codae_train_step_graph: the captured step and what it was captured for
-    mutable hipGraphExec_t graph_exec = nullptr;
-    mutable bool capturing = false;          // inside stream capture: device-side Adam step, everything joined at the end
-    struct GraphKey { codae_batch batch; codae_hyper hyper; codae_buffers bufs; codae_noise noise; } mutable graph_key{};
-    mutable std::vector<hipEvent_t> prof_start, prof_stop;
-    mutable std::vector<int> prof_kind;
-    mutable std::vector<int> prof_count;    // launches covered by the record (a GroupScope spans several)
-    mutable bool prof_group = false;        // inside a GroupScope of the forward class: no per-launch pairs
+    hipGraphExec_t graph_exec = nullptr;
+    bool capturing = false;          // inside stream capture: device-side Adam step, everything joined at the end
+    struct GraphKey { codae_batch batch; codae_hyper hyper; codae_buffers bufs; codae_noise noise; } graph_key{};
+    std::vector<hipEvent_t> prof_start, prof_stop;
+    std::vector<int> prof_kind;
+    std::vector<int> prof_count;    // launches covered by the record (a GroupScope spans several)
+    bool prof_group = false;        // inside a GroupScope of the forward class: no per-launch pairs
     EnvToggles cfg;                         // the CODAE_* toggles as they stood at codae_create
     struct DpState* dp = nullptr;           // data parallel with a library-owned RCCL communicator (codae_dp_init), else null
     int esize() const { return prec == CODAE_PREC_BF16 ? 2 : 4; }
@@ -187,14 +183,45 @@ struct DpState {
     hipEvent_t ev_done = nullptr;                       // every collective of the step complete
 };
 
+namespace codae {
+
+// Split-K factor of the weight-gradient GEMM dW[N][K] = dA^T H over `rows` batch rows: enough
+// K-slices that the output tiles cover the chip once (256 x 192 tiles), or ~2 workgroups per CU
+// with the 128 x 128 tile when the big one cannot fill it.  Must agree with gemm_bf16_tile_big.
+int choose_split_k(int N, int K, int rows) {
+    const int kt = rows / 64;
+    int s;
+    // a batch of <= 256 rows is 1-4 K-tiles: the launch is all epilogue (the fp32 output), which a split multiplies and
+    // follows with a reduce (stock BATCH_SIZE 128 at io 1536: 18.8 + 13 us per layer split in two)
+    if (kt <= 4 && env().wgrad_splitk <= 0) return 1;
+    if (env().wgrad_splitk > 0) {
+        s = env().wgrad_splitk;
+    } else {
+        const int tiles_big = ((N + 255) / 256) * ((K + 191) / 192);
+        s = (256 + tiles_big / 2) / tiles_big;
+        if (s > 8) s = 8;
+        if (s > kt) s = kt;
+        if (s < 1) s = 1;
+        if (tiles_big * s >= 160) return s;
+        const int tiles = ((N + 127) / 128) * ((K + 127) / 128);
+        s = (512 + tiles / 2) / tiles;
+        if (s > 8) s = 8;
+    }
+    if (s > kt) s = kt;
+    if (s < 1) s = 1;
+    return s;
+}
+
+}  // namespace codae
+
 namespace {
 
 // records a start/stop event pair around the launches made while it is alive
 struct ProfScope {
-    const codae_engine* e;
+    codae_engine* e;
     hipStream_t s;
     int slot = -1;
-    ProfScope(const codae_engine* e_, int kind, hipStream_t s_) : e(e_), s(s_) {
+    ProfScope(codae_engine* e_, int kind, hipStream_t s_) : e(e_), s(s_) {
         if (e->prof_group && kind == CODAE_K_GEMM_FWD) return;
         if (e->prof_on && ((e->prof_mask >> kind) & 1u) && (e->prof_step % e->prof_every) == 0 &&
             e->prof_n < (int)e->prof_start.size()) {
@@ -215,10 +242,10 @@ struct ProfScope {
 // step: dependent kernels, zero gap between them): the pair's own cost (2-4 us of stream time) is paid once per run
 // instead of once per launch, and the per-launch figure (elapsed / launches) is within 0.3 us of rocprofv3's.
 struct GroupScope {
-    const codae_engine* e;
+    codae_engine* e;
     hipStream_t s;
     int slot = -1;
-    GroupScope(const codae_engine* e_, int kind, hipStream_t s_) : e(e_), s(s_) {
+    GroupScope(codae_engine* e_, int kind, hipStream_t s_) : e(e_), s(s_) {
         if (e->prof_on && ((e->prof_mask >> kind) & 1u) && (e->prof_step % e->prof_every) == 0 &&
             e->prof_n < (int)e->prof_start.size()) {
             slot = e->prof_n++;
@@ -235,9 +262,6 @@ struct GroupScope {
     ~GroupScope() { close(); }
 };
 
-// Split-K factor of the weight-gradient GEMM dW[N][K] = dA^T H over `rows` batch rows: enough
-// K-slices that the output tiles cover the chip once (256 x 192 tiles), or ~2 workgroups per CU
-// with the 128 x 128 tile when the big one cannot fill it.  Must agree with gemm_bf16_tile_big.
 // exact-fp32 weight gradient (128 x 128 tiles, two workgroups per CU): enough K ranges for ~1.5 workgroups per CU - a
 // 1536 x 1536 gradient is 144 tiles, whose 8192-row reductions were the critical path of the whole backward (0.97 ms per
 // layer on the side stream); never for batches of <= 1024 rows
@@ -263,39 +287,41 @@ int choose_split_k_f32(int N, int K, int rows) {
     return s < 1 ? 1 : s;
 }
 
-int choose_split_k(int N, int K, int rows) {
-    const int kt = rows / 64;
-    int s;
-    // a batch of <= 256 rows is 1-4 K-tiles: the launch is all epilogue (the fp32 output), which a split multiplies and
-    // follows with a reduce (stock BATCH_SIZE 128 at io 1536: 18.8 + 13 us per layer split in two)
-    if (kt <= 4 && env().wgrad_splitk <= 0) return 1;
-    if (env().wgrad_splitk > 0) {
-        s = env().wgrad_splitk;
-    } else {
-        const int tiles_big = ((N + 255) / 256) * ((K + 191) / 192);
-        s = (256 + tiles_big / 2) / tiles_big;
-        if (s > 8) s = 8;
-        if (s > kt) s = kt;
-        if (s < 1) s = 1;
-        if (tiles_big * s >= 160) return s;
-        const int tiles = ((N + 127) / 128) * ((K + 127) / 128);
-        s = (512 + tiles / 2) / tiles;
-        if (s > 8) s = 8;
-    }
-    if (s > kt) s = kt;
-    if (s < 1) s = 1;
-    return s;
-}
-
-inline void* act_ptr(const codae_engine* e, const codae_buffers* b, int l) {
+inline void* act_ptr(codae_engine* e, const codae_buffers* b, int l) {
     return reinterpret_cast<char*>(b->acts) + e->act_off[l];
 }
-inline float* part_ptr(const codae_engine* e, const codae_buffers* b, int l) { return b->bias_parts + e->part_off[l]; }
-inline double* loss_parts_ptr(const codae_engine* e, const codae_buffers* b) {
+inline float* part_ptr(codae_engine* e, const codae_buffers* b, int l) { return b->bias_parts + e->part_off[l]; }
+inline double* loss_parts_ptr(codae_engine* e, const codae_buffers* b) {
     return reinterpret_cast<double*>(b->bias_parts + e->loss_part_off);
 }
-inline void* dact_ptr(const codae_engine* e, const codae_buffers* b, int l) {
+inline void* dact_ptr(codae_engine* e, const codae_buffers* b, int l) {
     return reinterpret_cast<char*>(b->dacts) + (int64_t)(l % e->n_dact) * e->dact_one;   // see backward_range
+}
+
+// 1 / (rows x io) of the MSE mean: the global batch rows when a data-parallel caller gives them, else this batch's
+double loss_inv_n(const codae_hyper* hyper, const codae_batch* batch) {
+    const float rows = hyper != nullptr && hyper->loss_scale_rows > 0.f ? hyper->loss_scale_rows : (float)batch->B;
+    return 1.0 / ((double)rows * batch->io);
+}
+
+// the step's metric sums and loss (this batch's own mean) from the `parts` per-workgroup sums of its loss kernel
+int finish_loss(codae_engine* e, const codae_buffers* b, const codae_batch* batch, int parts, hipStream_t s) {
+    return launch_finish_loss(b->scalars, 1.0 / ((double)batch->B * batch->io), s, loss_parts_ptr(e, b), parts);
+}
+
+// layer l's GEMMs on the engine's buffers (layer_gemm.h)
+// forward: K = the PADDED input width: the extra k columns are zeros in x (see in_ld) times the head of W's next row
+GemmBf16 layer_fwd_bf16(codae_engine* e, const codae_buffers* b, int l, const void* x, void* y, int64_t ldy, bool y_f32, int rows) {
+    return fwd_gemm_bf16(x, e->in_ld[l], reinterpret_cast<const bf16_t*>(b->shadow_w) + e->w_off[l], e->in[l], y, ldy, y_f32 ? 1 : 0, rows,
+                         e->out[l], e->in_ld[l], b->params + e->b_off[l]);
+}
+// weight gradient dW_l = dA_l^T act[l] over `rows` batch rows, unsplit, into grads
+GemmBf16 layer_wgrad_bf16(codae_engine* e, const codae_buffers* b, int l, int rows) {
+    return wgrad_gemm_bf16(dact_ptr(e, b, l), e->out_ld[l], act_ptr(e, b, l), e->in_ld[l], b->grads + e->w_off[l], rows, e->out[l], e->in[l]);
+}
+GemmF32 layer_wgrad_f32(codae_engine* e, const codae_buffers* b, int l, int rows) {
+    return wgrad_gemm_f32(reinterpret_cast<const float*>(dact_ptr(e, b, l)), reinterpret_cast<const float*>(act_ptr(e, b, l)),
+                          b->grads + e->w_off[l], rows, e->out[l], e->in[l]);
 }
 
 int check_common(codae_handle h, const codae_buffers* b, int B) {
@@ -308,7 +334,7 @@ int check_common(codae_handle h, const codae_buffers* b, int B) {
 
 // db_l = sum of layer l's pending partial column-sum rows, in row order (every layer with pending rows, one launch);
 // with_norm: += sum db^2 into the clip_grad_norm_ slots
-int finish_bias(const codae_engine* e, const codae_buffers* b, hipStream_t s, bool with_norm, const LossFinish* loss = nullptr) {
+int finish_bias(codae_engine* e, const codae_buffers* b, hipStream_t s, bool with_norm, const LossFinish* loss = nullptr) {
     BiasFinishJobs jobs;
     jobs.n = 0;
     int cols = 0;
@@ -340,7 +366,7 @@ int finish_bias(const codae_engine* e, const codae_buffers* b, hipStream_t s, bo
 // 0.83 / 0.34, 8192: 1.71 / 0.40) the XCDs' L2s cannot feed them and the per-layer GEMMs (weights read once per 256 rows) win.
 constexpr int CHAIN_MAX_ROWS = 2048;
 
-bool chain_eligible(const codae_engine* e, const codae_buffers* b, int B) {
+bool chain_eligible(codae_engine* e, const codae_buffers* b, int B) {
     // (the chain kernel fuses the plain gather: a noised input takes the per-layer launches)
     return e->chain_ok && e->noise.kind == CODAE_NOISE_NONE && b->shadow_wt != nullptr && e->rows_for(B) <= CHAIN_MAX_ROWS;
 }
@@ -348,7 +374,7 @@ bool chain_eligible(const codae_engine* e, const codae_buffers* b, int B) {
 // gather + forward chain + loss (+ data-gradient chain) of a narrow stack: one launch; then the loss finish
 // (backward: the loss finish is left to the caller's bias-finish launch - *loss_out describes it - and the kernel zeroes
 //  the norm accumulators)
-int run_chain(const codae_engine* e, const codae_buffers* b, const codae_batch* batch, const codae_hyper* hyper, bool backward,
+int run_chain(codae_engine* e, const codae_buffers* b, const codae_batch* batch, const codae_hyper* hyper, bool backward,
               hipStream_t s, LossFinish* loss_out = nullptr) {
     const int B = batch->B, L = e->L, rows = e->rows_for(B);
     ChainArgs a{};
@@ -366,8 +392,7 @@ int run_chain(const codae_engine* e, const codae_buffers* b, const codae_batch* 
     a.width[L] = e->out[L - 1];
     a.data = batch->data; a.row_idx = batch->row_idx; a.mask_id = batch->mask_id; a.mask_table = batch->mask_table;
     a.mask_to_use = batch->mask_to_use; a.nb_run = batch->nb_run; a.run = batch->run;
-    const double n_glob = (double)(hyper != nullptr && hyper->loss_scale_rows > 0.f ? hyper->loss_scale_rows : (float)B) * batch->io;
-    a.inv_n = (float)(1.0 / n_glob);
+    a.inv_n = (float)loss_inv_n(hyper, batch);
     a.loss_parts = loss_parts_ptr(e, b);
     a.do_backward = backward ? 1 : 0;
     a.scalars = loss_out != nullptr ? b->scalars : nullptr;
@@ -387,21 +412,18 @@ int run_chain(const codae_engine* e, const codae_buffers* b, const codae_batch* 
         loss_out->parts = loss_parts_ptr(e, b); loss_out->n_parts = n_wg;
         return CODAE_OK;
     }
-    return launch_finish_loss(b->scalars, 1.0 / ((double)B * batch->io), s, loss_parts_ptr(e, b), n_wg);
+    return finish_loss(e, b, batch, n_wg, s);
 }
 
 // every layer's weight gradient dW_l = dA_l^T H_l in one grouped launch (fp32 straight into grads: no split-K slabs)
 // with_norm: each tile also adds its sum g^2 to the clip_grad_norm_ slots (no separate pass over the gradients)
-int run_wgrad_grouped(const codae_engine* e, const codae_buffers* b, int rows, bool with_norm, hipStream_t s) {
+int run_wgrad_grouped(codae_engine* e, const codae_buffers* b, int rows, bool with_norm, hipStream_t s) {
     for (int base = 0; base < e->L; base += CODAE_GROUP_MAX) {
         GemmBf16Group grp{};
         grp.n = 0;
         for (int l = base; l < e->L && grp.n < CODAE_GROUP_MAX; ++l) {
             GemmBf16& g = grp.g[grp.n++];
-            g.A = reinterpret_cast<const bf16_t*>(dact_ptr(e, b, l)); g.lda = e->out_ld[l]; g.a_mode = OP_KS;
-            g.B = reinterpret_cast<const bf16_t*>(act_ptr(e, b, l)); g.ldb = e->in_ld[l]; g.b_mode = OP_KS;
-            g.C = b->grads + e->w_off[l]; g.ldc = e->in[l]; g.c_f32 = 1;
-            g.M = e->out[l]; g.N = e->in[l]; g.K = rows; g.split_k = 1;
+            g = layer_wgrad_bf16(e, b, l, rows);
             g.sumsq_slots = with_norm ? b->scalars + CODAE_S_GRAD_SQ_SLOTS : nullptr;
         }
         ProfScope prof(e, CODAE_K_GEMM_WGRAD, s);
@@ -419,7 +441,7 @@ int run_wgrad_grouped(const codae_engine* e, const codae_buffers* b, int rows, b
 // reference's stock batch 128: 0.436 -> 0.402 ms/step; batch 512: 0.663 -> 0.433).
 // 0: per-layer weight gradients; 1: one grouped launch of the pipelined 256 x 192 tile; 2: one grouped launch of the one-barrier
 // kernel on 128 x 128 / 64 x 128 / 64 x 64 tiles (run_wgrad_grouped: stacks too narrow to fill the chip with the big tile)
-int defer_wgrad_mode(const codae_engine* e, int rows) {
+int defer_wgrad_mode(codae_engine* e, int rows) {
     if (e->prec == CODAE_PREC_F32) {
         // 3: the exact-fp32 engine on the bf16-plane GEMMs - every weight gradient in one launch of gemm_f32x3_grouped_kernel, K unsplit
         // (what mode 1 is to the bf16 engine: per layer it is 144 tiles, split 7 ways into fp32 slabs and reduced: 0.2 ms of reduce
@@ -448,49 +470,33 @@ int defer_wgrad_mode(const codae_engine* e, int rows) {
     return total_small >= 128 ? 2 : 0;
 }
 
-int run_wgrad_deferred_f32(const codae_engine* e, const codae_buffers* b, int rows, hipStream_t s) {
+int run_wgrad_deferred_f32(codae_engine* e, const codae_buffers* b, int rows, hipStream_t s) {
     GemmF32Group grp{};
     grp.n = 0;
-    for (int l = e->L - 1; l >= 0; --l) {            // (backward order: the layers whose operands were touched last come first)
-        GemmF32& g = grp.g[grp.n++];
-        const int N = e->out[l], K = e->in[l];
-        g.A = reinterpret_cast<const float*>(dact_ptr(e, b, l)); g.a_rs = 1; g.a_ks = N;
-        g.B = reinterpret_cast<const float*>(act_ptr(e, b, l)); g.b_rs = 1; g.b_ks = K;
-        g.C = b->grads + e->w_off[l]; g.ldc = K;
-        g.M = N; g.N = K; g.K = rows; g.split_k = 1;
-    }
+    for (int l = e->L - 1; l >= 0; --l)              // (backward order: the layers whose operands were touched last come first)
+        grp.g[grp.n++] = layer_wgrad_f32(e, b, l, rows);
     ProfScope prof(e, CODAE_K_GEMM_WGRAD, s);
     prof.counts_as(grp.n);
     return gemm_f32x3_grouped(grp, s);
 }
 
-int run_wgrad_deferred(const codae_engine* e, const codae_buffers* b, int rows, hipStream_t s) {
+int run_wgrad_deferred(codae_engine* e, const codae_buffers* b, int rows, bool with_norm, hipStream_t s) {
     GemmBf16Group grp{};
     grp.n = 0;
     for (int l = e->L - 1; l >= 0; --l) {            // (backward order: the layers whose operands were touched last come first)
         GemmBf16& g = grp.g[grp.n++];
-        g.A = reinterpret_cast<const bf16_t*>(dact_ptr(e, b, l)); g.lda = e->out_ld[l]; g.a_mode = OP_KS;
-        g.B = reinterpret_cast<const bf16_t*>(act_ptr(e, b, l)); g.ldb = e->in_ld[l]; g.b_mode = OP_KS;
-        g.C = b->grads + e->w_off[l]; g.ldc = e->in[l]; g.c_f32 = 1;
-        g.M = e->out[l]; g.N = e->in[l]; g.K = rows; g.split_k = 1;
-        g.sumsq_slots = e->norm_in_backward ? b->scalars + CODAE_S_GRAD_SQ_SLOTS : nullptr;
+        g = layer_wgrad_bf16(e, b, l, rows);
+        g.sumsq_slots = with_norm ? b->scalars + CODAE_S_GRAD_SQ_SLOTS : nullptr;
     }
     ProfScope prof(e, CODAE_K_GEMM_WGRAD, s);
     prof.counts_as(grp.n);
     return gemm_bf16_pipe_grouped(grp, s);
 }
 
-// layer l's activation when it is not ReLU / none (those keep the `relu` flag and its kernels)
-template <typename G>
-void set_act(G& g, const codae_engine* e, int l) {
-    g.act = e->act[l];
-    for (int k = 0; k < 3; ++k) g.act_p[k] = e->act_p[3 * l + k];
-}
-
 // Exact-fp32 GEMM of a launch too small to fill the chip (forward / data gradient of a small batch): K split over
 // workgroups into fp32 slabs (slab slot 2: the caller's stream), then the reduce that applies the GEMM's epilogue.  Same
 // fp32 arithmetic in another summation order.  3 x 512 at batch 128, whole parity-mode step: 3.09 -> see DESIGN.md.
-int gemm_f32_small(const codae_engine* e, const codae_buffers* b, const GemmF32& g, hipStream_t s) {
+int gemm_f32_small(codae_engine* e, const codae_buffers* b, const GemmF32& g, hipStream_t s) {
     const int tiles = ((g.M + 127) / 128) * ((g.N + 127) / 128);
     const int kt = (g.K + 31) / 32;
     int S = tiles >= 128 ? 1 : (256 + tiles / 2) / tiles;
@@ -511,20 +517,13 @@ int gemm_f32_small(const codae_engine* e, const codae_buffers* b, const GemmF32&
 }
 
 // y = act(x W^T + b) for layer l
-int run_linear(const codae_engine* e, const codae_buffers* b, int l, const void* x, void* y, bool y_f32, int rows,
+int run_linear(codae_engine* e, const codae_buffers* b, int l, const void* x, void* y, bool y_f32, int rows,
                hipStream_t s) {
     const int N = e->out[l], K = e->in[l];
     ProfScope prof(e, CODAE_K_GEMM_FWD, s);
     if (e->prec == CODAE_PREC_BF16) {
-        GemmBf16 g{};
-        // K = the PADDED input width: the extra k columns are zeros in x (see in_ld) times the head of W's next row
-        g.A = reinterpret_cast<const bf16_t*>(x); g.lda = e->in_ld[l]; g.a_mode = OP_KC;
-        g.B = reinterpret_cast<const bf16_t*>(b->shadow_w) + e->w_off[l]; g.ldb = K; g.b_mode = OP_KC;
-        g.C = y; g.ldc = y_f32 ? N : e->out_ld[l]; g.c_f32 = y_f32 ? 1 : 0;
-        g.M = rows; g.N = N; g.K = e->in_ld[l];
-        g.bias = b->params + e->b_off[l]; g.relu = e->relu[l];
-        set_act(g, e, l);
-        g.split_k = 1;
+        GemmBf16 g = layer_fwd_bf16(e, b, l, x, y, y_f32 ? N : e->out_ld[l], y_f32, rows);
+        set_activation(g, e->relu[l], e->act[l], &e->act_p[3 * l]);
         if (!y_f32 && l + 1 < e->L && e->bits_off[l + 1] >= 0 && e->relu[l] && y == act_ptr(e, b, l + 1) && gemm_bf16_takes_relu_bits(rows, N)) {
             g.relu_bits_out = reinterpret_cast<uint8_t*>(b->acts) + e->bits_off[l + 1];
             g.ld_bits = e->in_ld[l + 1] / 8;
@@ -535,27 +534,22 @@ int run_linear(const codae_engine* e, const codae_buffers* b, int l, const void*
         }
         return gemm_bf16(g, s);
     }
-    GemmF32 g{};
-    g.A = reinterpret_cast<const float*>(x); g.a_rs = K; g.a_ks = 1;
-    g.B = b->params + e->w_off[l]; g.b_rs = K; g.b_ks = 1;
-    g.C = reinterpret_cast<float*>(y); g.ldc = N;
-    g.M = rows; g.N = N; g.K = K;
-    g.bias = b->params + e->b_off[l]; g.relu = e->relu[l];
-    set_act(g, e, l);
+    GemmF32 g = fwd_gemm_f32(reinterpret_cast<const float*>(x), b->params + e->w_off[l], reinterpret_cast<float*>(y), rows, N, K,
+                             b->params + e->b_off[l]);
+    set_activation(g, e->relu[l], e->act[l], &e->act_p[3 * l]);
     return gemm_f32_small(e, b, g, s);
 }
 
 // dW_l = dA_l^T act[l] on stream s.  bf16: split-K partial slabs (slab buffer `slot`), then the reduce on the same stream.
-int run_wgrad(const codae_engine* e, const codae_buffers* b, int l, int rows, hipStream_t s, int slot = 0) {
+// with_norm (bf16): the launch that produces the final values - the slab reduce, or the unsplit GEMM's epilogue - also adds their
+// sum g^2 to the clip_grad_norm_ accumulators
+int run_wgrad(codae_engine* e, const codae_buffers* b, int l, int rows, bool with_norm, hipStream_t s, int slot = 0) {
     const int N = e->out[l], K = e->in[l];
     float* dW = b->grads + e->w_off[l];
     if (e->prec == CODAE_PREC_BF16) {
         const int S = e->split_k[l] <= rows / 64 ? e->split_k[l] : rows / 64;
-        GemmBf16 g{};
-        g.A = reinterpret_cast<const bf16_t*>(dact_ptr(e, b, l)); g.lda = e->out_ld[l]; g.a_mode = OP_KS;
-        g.B = reinterpret_cast<const bf16_t*>(act_ptr(e, b, l)); g.ldb = e->in_ld[l]; g.b_mode = OP_KS;
-        g.M = N; g.N = K; g.K = rows;
-        g.ldc = K; g.c_f32 = 1; g.split_k = S;
+        GemmBf16 g = layer_wgrad_bf16(e, b, l, rows);
+        g.split_k = S;
         if (S > 1) {
             CODAE_REQUIRE(b->slabs != nullptr, "bf16 wgrad needs the slab workspace");
             char* slab = reinterpret_cast<char*>(b->slabs) + (int64_t)slot * e->slab_bytes;
@@ -568,18 +562,13 @@ int run_wgrad(const codae_engine* e, const codae_buffers* b, int l, int rows, hi
             if (rc) return rc;
             ProfScope prof(e, CODAE_K_SLAB_REDUCE, s);
             return launch_reduce_slabs(reinterpret_cast<const float*>(slab), S, (int64_t)N * K, dW, (int64_t)N * K,
-                                       e->norm_in_backward ? b->scalars + CODAE_S_GRAD_SQ : nullptr, s);
+                                       with_norm ? b->scalars + CODAE_S_GRAD_SQ : nullptr, s);
         }
-        g.C = dW;
-        if (e->norm_in_backward) g.sumsq_slots = b->scalars + CODAE_S_GRAD_SQ_SLOTS;    // (unsplit: the epilogue sees the final values)
+        if (with_norm) g.sumsq_slots = b->scalars + CODAE_S_GRAD_SQ_SLOTS;    // (unsplit: the epilogue sees the final values)
         ProfScope prof(e, CODAE_K_GEMM_WGRAD, s);
         return gemm_bf16(g, s);
     }
-    GemmF32 g{};
-    g.A = reinterpret_cast<const float*>(dact_ptr(e, b, l)); g.a_rs = 1; g.a_ks = N;
-    g.B = reinterpret_cast<const float*>(act_ptr(e, b, l)); g.b_rs = 1; g.b_ks = K;
-    g.C = dW; g.ldc = K;
-    g.M = N; g.N = K; g.K = rows;
+    GemmF32 g = layer_wgrad_f32(e, b, l, rows);
     int S = e->split_k[l];
     if (S > rows / 32) S = rows / 32;
     if (S > 1 && b->slabs != nullptr) {
@@ -600,30 +589,23 @@ int run_wgrad(const codae_engine* e, const codae_buffers* b, int l, int rows, hi
 }
 
 // dA_{l-1} = (dA_l W_l) * [act[l] > 0]  (+ column sums -> db_{l-1});  l == 0 with dx: plain dX in fp32
-int run_dgrad(const codae_engine* e, const codae_buffers* b, int l, int rows, float* dx_f32, hipStream_t s) {
+// coscheduled: another stream's weight gradients run beside this launch (GemmBf16::coscheduled)
+int run_dgrad(codae_engine* e, const codae_buffers* b, int l, int rows, bool coscheduled, float* dx_f32, hipStream_t s) {
     const int N = e->out[l], K = e->in[l];
     const bool to_dx = (dx_f32 != nullptr);
     ProfScope prof(e, CODAE_K_GEMM_DGRAD, s);
     if (e->prec == CODAE_PREC_BF16) {
-        GemmBf16 g{};
-        g.coscheduled = e->bwd_coscheduled ? 1 : 0;
-        g.A = reinterpret_cast<const bf16_t*>(dact_ptr(e, b, l)); g.lda = e->out_ld[l]; g.a_mode = OP_KC;
-        if (b->shadow_wt != nullptr && l >= 1 && !e->cfg.no_wt) {
-            // dx[m][k] = sum_n dy[m][n] Wt[k][n]: both operands k-contiguous -> the forward-form kernel
-            g.B = reinterpret_cast<const bf16_t*>(b->shadow_wt) + e->w_off[l]; g.ldb = N; g.b_mode = OP_KC;
-        } else {
-            g.B = reinterpret_cast<const bf16_t*>(b->shadow_w) + e->w_off[l]; g.ldb = K; g.b_mode = OP_KS;
-        }
-        g.M = rows; g.N = K; g.K = e->out_ld[l];          // (k runs over the padded output width: zero pad columns of dA)
-        g.ldc = K; g.split_k = 1;
-        if (to_dx) {
-            g.C = dx_f32; g.c_f32 = 1;
-        } else {
-            g.C = dact_ptr(e, b, l - 1); g.c_f32 = 0; g.ldc = e->out_ld[l - 1];
+        const bool wt = b->shadow_wt != nullptr && l >= 1 && !e->cfg.no_wt;      // the transposed shadow: the forward-form kernel
+        const bf16_t* W = reinterpret_cast<const bf16_t*>(wt ? b->shadow_wt : b->shadow_w) + e->w_off[l];
+        // (k runs over the padded output width: zero pad columns of dA)
+        GemmBf16 g = dgrad_gemm_bf16(dact_ptr(e, b, l), e->out_ld[l], W, wt ? N : K, wt, to_dx ? (void*)dx_f32 : dact_ptr(e, b, l - 1),
+                                     to_dx ? K : e->out_ld[l - 1], to_dx ? 1 : 0, rows, K, e->out_ld[l]);
+        g.coscheduled = coscheduled ? 1 : 0;
+        if (!to_dx) {
             if (e->act[l - 1] != CODAE_ACT_NONE) {
                 // another activation than ReLU: its derivative from the saved activation (no 1-bit masks for these layers)
                 g.relu_src = reinterpret_cast<const bf16_t*>(act_ptr(e, b, l)); g.ld_relu = e->in_ld[l];
-                set_act(g, e, l - 1);
+                set_activation(g, 0, e->act[l - 1], &e->act_p[3 * (l - 1)]);
             } else if (e->relu[l - 1]) {
                 g.relu_src = reinterpret_cast<const bf16_t*>(act_ptr(e, b, l)); g.ld_relu = e->in_ld[l];
                 // (the forward launch that wrote act[l] had this output shape: rows x in[l]; same predicate on both sides)
@@ -641,18 +623,12 @@ int run_dgrad(const codae_engine* e, const codae_buffers* b, int l, int rows, fl
         }
         return gemm_bf16(g, s);
     }
-    GemmF32 g{};
-    g.A = reinterpret_cast<const float*>(dact_ptr(e, b, l)); g.a_rs = N; g.a_ks = 1;
-    g.B = b->params + e->w_off[l]; g.b_rs = 1; g.b_ks = K;
-    g.M = rows; g.N = K; g.K = N;
-    g.ldc = K;
-    if (to_dx) {
-        g.C = dx_f32;
-    } else {
-        g.C = reinterpret_cast<float*>(dact_ptr(e, b, l - 1));
+    GemmF32 g = dgrad_gemm_f32(reinterpret_cast<const float*>(dact_ptr(e, b, l)), b->params + e->w_off[l],
+                               to_dx ? dx_f32 : reinterpret_cast<float*>(dact_ptr(e, b, l - 1)), rows, N, K);
+    if (!to_dx) {
         if (e->relu[l - 1] || e->act[l - 1] != CODAE_ACT_NONE) {
             g.relu_src = reinterpret_cast<const float*>(act_ptr(e, b, l)); g.ld_relu = K;
-            set_act(g, e, l - 1);
+            set_activation(g, 0, e->act[l - 1], &e->act_p[3 * (l - 1)]);
         }
         g.colsum_part = part_ptr(e, b, l - 1);
         e->parts_pending[l - 1] = gemm_f32_colsum_rows(rows);
@@ -661,7 +637,7 @@ int run_dgrad(const codae_engine* e, const codae_buffers* b, int l, int rows, fl
 }
 
 // Wt_l [in][out] <- W_l [out][in] (bf16) for every layer that has a data gradient (l >= 1)
-int refresh_transposed(const codae_engine* e, const codae_buffers* b, hipStream_t s, int l_lo = 1, int l_hi = -1) {
+int refresh_transposed(codae_engine* e, const codae_buffers* b, hipStream_t s, int l_lo = 1, int l_hi = -1) {
     if (e->prec != CODAE_PREC_BF16 || b->shadow_wt == nullptr || e->L < 2) return CODAE_OK;
     if (l_hi < 0) l_hi = e->L;
     for (int base = l_lo; base < l_hi; base += 64) {             // the launch carries at most 64 matrices
@@ -675,7 +651,7 @@ int refresh_transposed(const codae_engine* e, const codae_buffers* b, hipStream_
 }
 
 // rows [B, rows) of a [rows][width] working-precision matrix -> 0 (bf16 mode pads the batch to 64)
-int zero_pad_rows(const codae_engine* e, void* base, int B, int rows, int width, hipStream_t s) {
+int zero_pad_rows(codae_engine* e, void* base, int B, int rows, int width, hipStream_t s) {
     if (rows > B) {
         char* p = reinterpret_cast<char*>(base) + (int64_t)B * width * e->esize();
         CODAE_HIP_CHECK(hipMemsetAsync(p, 0, (int64_t)(rows - B) * width * e->esize(), s));
@@ -683,7 +659,7 @@ int zero_pad_rows(const codae_engine* e, void* base, int B, int rows, int width,
     return CODAE_OK;
 }
 
-int ensure_side_stream(const codae_engine* h) {
+int ensure_side_stream(codae_engine* h) {
     if (h->side != nullptr) return CODAE_OK;
     // The side streams must land on a hardware queue of their own: two streams that share one execute serially
     // with ~11 us between dependent kernels (seen with RCCL initialised: every stream of the process on one queue,
@@ -701,7 +677,7 @@ int ensure_side_stream(const codae_engine* h) {
 }
 
 // s waits for everything the backward put on the side streams
-int join_side(const codae_engine* h, hipStream_t s) {
+int join_side(codae_engine* h, hipStream_t s) {
     if (!h->side_dirty || h->side == nullptr) return CODAE_OK;
     CODAE_HIP_CHECK(hipEventRecord(h->ev_join, h->side));
     CODAE_HIP_CHECK(hipStreamWaitEvent(s, h->ev_join, 0));
@@ -721,7 +697,9 @@ int join_side(const codae_engine* h, hipStream_t s) {
 // waits for the side stream; deeper stacks rotate (dgrad_l writes buffer (l-1) % n, which wgrad_{l-1+n} was
 // reading, and waits for that wgrad's event).  The last weight gradient (layer 0) runs on `s` itself, beside
 // wgrad_1 on the side stream.  With join the call returns with `s` waiting for every side-stream kernel.
-int backward_range(codae_handle h, const codae_buffers* b, int B, int lo, int hi, float* dx, bool step_mode,
+// with_norm (single-GPU fused bf16 step: nothing happens to the gradients between backward and update): every launch that
+// leaves final gradient values behind also adds their sum g^2 to the clip_grad_norm_ accumulators.
+int backward_range(codae_handle h, const codae_buffers* b, int B, int lo, int hi, float* dx, bool step_mode, bool with_norm,
                    hipStream_t s, bool join = true) {
     const int rows = h->rows_for(B);
     const bool dual = !h->cfg.single_stream;
@@ -739,33 +717,29 @@ int backward_range(codae_handle h, const codae_buffers* b, int B, int lo, int hi
         int rc = join_side(h, s);                  // (an earlier bucketed backward may have left work on the side stream)
         if (rc) return rc;
         for (int l = hi - 1; l >= 1; --l) {
-            rc = run_dgrad(h, b, l, rows, nullptr, s);
+            rc = run_dgrad(h, b, l, rows, false, nullptr, s);
             if (rc) return rc;
         }
         rc = defer == 3 ? run_wgrad_deferred_f32(h, b, rows, s)
-                        : (defer == 1 ? run_wgrad_deferred(h, b, rows, s) : run_wgrad_grouped(h, b, rows, h->norm_in_backward, s));
+                        : (defer == 1 ? run_wgrad_deferred(h, b, rows, with_norm, s) : run_wgrad_grouped(h, b, rows, with_norm, s));
         if (rc) return rc;
-        return finish_bias(h, b, s, h->norm_in_backward);
+        return finish_bias(h, b, s, with_norm);
     }
     bool* w_pending = h->w_pending;
-    struct Cosched {                       // (reset on every way out of the function)
-        codae_handle h;
-        ~Cosched() { h->bwd_coscheduled = false; }
-    } cosched_guard{h};
-    h->bwd_coscheduled = dual;
+    const bool coscheduled = dual;         // the weight gradients run beside the data-gradient chain
     for (int l = hi - 1; l >= lo; --l) {
         int rc;
         if (!dual) {
-            rc = run_wgrad(h, b, l, rows, s);
+            rc = run_wgrad(h, b, l, rows, with_norm, s);
         } else if (join && step_mode && l == 0 && hi - lo >= 3 && !h->cfg.tail_on_side) {
             // tail: the side stream still owes wgrad_1 when the dgrad chain ends, and the caller's stream has
             // nothing left to do: the last weight gradient runs here (third slab buffer), beside wgrad_1
-            rc = run_wgrad(h, b, l, rows, s, 2);
+            rc = run_wgrad(h, b, l, rows, with_norm, s, 2);
         } else {
             hipEvent_t ready = h->ev_ready[h->ready_turn++ % CODAE_MAX_DACT];
             CODAE_HIP_CHECK(hipEventRecord(ready, s));                      // dA_l (and act[l]) are complete on s
             CODAE_HIP_CHECK(hipStreamWaitEvent(h->side, ready, 0));
-            rc = run_wgrad(h, b, l, rows, h->side, l & 1);                  // two alternating slab buffers
+            rc = run_wgrad(h, b, l, rows, with_norm, h->side, l & 1);                 // two alternating slab buffers
             if (rc == CODAE_OK && h->n_dact <= h->L) {   // (with a buffer per layer nothing is overwritten within a step)
                 CODAE_HIP_CHECK(hipEventRecord(h->ev_w[l % h->n_dact], h->side));
                 w_pending[l % h->n_dact] = true;
@@ -781,7 +755,7 @@ int backward_range(codae_handle h, const codae_buffers* b, int B, int lo, int hi
                 CODAE_HIP_CHECK(hipStreamWaitEvent(s, h->ev_w[wb], 0));
                 w_pending[wb] = false;
             }
-            rc = chain ? run_dgrad(h, b, l, rows, nullptr, s) : run_dgrad(h, b, l, B, dx, s);
+            rc = chain ? run_dgrad(h, b, l, rows, coscheduled, nullptr, s) : run_dgrad(h, b, l, B, coscheduled, dx, s);
             if (rc) return rc;
         }
     }
@@ -791,7 +765,7 @@ int backward_range(codae_handle h, const codae_buffers* b, int B, int lo, int hi
     // range (lo == 0) - one finish launch per step instead of one per bucket (10 x 6 us at C3); codae_step_update finishes
     // whatever a caller that stopped short left behind.
     if (join || lo == 0) {
-        int rc = finish_bias(h, b, s, h->norm_in_backward);
+        int rc = finish_bias(h, b, s, with_norm);
         if (rc) return rc;
     }
     if (dual) {
@@ -1105,7 +1079,7 @@ int codae_backward(codae_handle h, const codae_buffers* b, const float* dy, floa
     rc = launch_colsum_parts_f32(dy, B, h->out[top], part_ptr(h, b, top), s);
     if (rc) return rc;
     h->parts_pending[top] = (B + 63) / 64;
-    return backward_range(h, b, B, layer_lo, layer_hi, dx, false, s);
+    return backward_range(h, b, B, layer_lo, layer_hi, dx, false, false, s);
 }
 
 int codae_step_forward_loss(codae_handle h, const codae_buffers* b, const codae_batch* batch, const codae_hyper* hyper,
@@ -1141,17 +1115,11 @@ int codae_step_forward_loss(codae_handle h, const codae_buffers* b, const codae_
         const bool last = (l == L - 1);
         if (last && fuse_loss) {
             fwd_group.close();
-            const double n_glob = (double)(hyper->loss_scale_rows > 0.f ? hyper->loss_scale_rows : (float)B) * batch->io;
-            GemmBf16 g{};
-            g.A = reinterpret_cast<const bf16_t*>(act_ptr(h, b, l)); g.lda = h->in_ld[l]; g.a_mode = OP_KC;
-            g.B = reinterpret_cast<const bf16_t*>(b->shadow_w) + h->w_off[l]; g.ldb = h->in[l]; g.b_mode = OP_KC;
-            g.C = dact_ptr(h, b, l); g.ldc = h->out_ld[l]; g.c_f32 = 0;
-            g.M = rows; g.N = h->out[l]; g.K = h->in_ld[l];
-            g.bias = b->params + h->b_off[l]; g.relu = 0; g.split_k = 1;
+            GemmBf16 g = layer_fwd_bf16(h, b, l, act_ptr(h, b, l), dact_ptr(h, b, l), h->out_ld[l], false, rows);
             g.colsum_part = part_ptr(h, b, l);
             g.loss.enabled = 1; g.loss.data = batch->data; g.loss.row_idx = batch->row_idx; g.loss.mask_id = batch->mask_id;
             g.loss.mask_to_use = batch->mask_to_use; g.loss.nb_run = batch->nb_run; g.loss.run = batch->run;
-            g.loss.table = batch->mask_table; g.loss.io = batch->io; g.loss.B = B; g.loss.inv_n = (float)(1.0 / n_glob);
+            g.loss.table = batch->mask_table; g.loss.io = batch->io; g.loss.B = B; g.loss.inv_n = (float)loss_inv_n(hyper, batch);
             g.loss.parts = loss_parts_ptr(h, b);
             if (b->shadow_wt != nullptr && l >= 1 && !h->cfg.no_wt && !h->cfg.no_prefetch) {     // the first data gradient's operand
                 g.prefetch = reinterpret_cast<const bf16_t*>(b->shadow_wt) + h->w_off[l];
@@ -1166,7 +1134,7 @@ int codae_step_forward_loss(codae_handle h, const codae_buffers* b, const codae_
             if (rc) return rc;
             h->parts_pending[l] = gemm_bf16_colsum_rows(g);
             h->norm_scalars_zero = true;
-            return launch_finish_loss(b->scalars, 1.0 / ((double)B * batch->io), s, loss_parts_ptr(h, b), n_loss_parts);
+            return finish_loss(h, b, batch, n_loss_parts, s);
         }
         rc = last ? run_linear(h, b, l, act_ptr(h, b, l), y, true, B, s)
                   : run_linear(h, b, l, act_ptr(h, b, l), act_ptr(h, b, l + 1), false, rows, s);
@@ -1175,22 +1143,21 @@ int codae_step_forward_loss(codae_handle h, const codae_buffers* b, const codae_
     }
     fwd_group.close();
     if (hyper != nullptr) {
-        const double n_glob = (double)(hyper->loss_scale_rows > 0.f ? hyper->loss_scale_rows : (float)B) * batch->io;
         rc = zero_pad_rows(h, dact_ptr(h, b, L - 1), B, rows, h->out_ld[L - 1], s);
         if (rc) return rc;
         {
             ProfScope prof(h, CODAE_K_LOSS, s);
-            rc = launch_mse_loss(batch, y, dact_ptr(h, b, L - 1), bf, (float)(1.0 / n_glob), part_ptr(h, b, L - 1),
+            rc = launch_mse_loss(batch, y, dact_ptr(h, b, L - 1), bf, (float)loss_inv_n(hyper, batch), part_ptr(h, b, L - 1),
                                  loss_parts_ptr(h, b), 1, s, h->out_ld[L - 1]);
         }
         if (rc) return rc;
         h->parts_pending[L - 1] = mse_loss_colsum_rows(B);
         h->norm_scalars_zero = true;
-        return launch_finish_loss(b->scalars, 1.0 / ((double)B * batch->io), s, loss_parts_ptr(h, b), mse_loss_colsum_rows(B));
+        return finish_loss(h, b, batch, mse_loss_colsum_rows(B), s);
     }
     rc = launch_mse_loss(batch, y, nullptr, 0, 0.f, nullptr, loss_parts_ptr(h, b), 0, s);
     if (rc) return rc;
-    return launch_finish_loss(b->scalars, 1.0 / ((double)B * batch->io), s, loss_parts_ptr(h, b), mse_loss_colsum_rows(B));
+    return finish_loss(h, b, batch, mse_loss_colsum_rows(B), s);
 }
 
 int codae_set_input_noise(codae_handle h, const codae_noise* noise) {
@@ -1215,7 +1182,7 @@ int codae_step_backward(codae_handle h, const codae_buffers* b, int32_t B, int32
     if (rc) return rc;
     CODAE_REQUIRE(b->grads && b->dacts, "codae_step_backward: grads / dacts missing");
     CODAE_REQUIRE(layer_lo >= 0 && layer_lo < layer_hi && layer_hi <= h->L, "codae_step_backward: layer range [%d, %d)", layer_lo, layer_hi);
-    return backward_range(h, b, B, layer_lo, layer_hi, nullptr, true, (hipStream_t)stream);
+    return backward_range(h, b, B, layer_lo, layer_hi, nullptr, true, false, (hipStream_t)stream);
 }
 
 int codae_step_backward_async(codae_handle h, const codae_buffers* b, int32_t B, int32_t layer_lo, int32_t layer_hi, void* stream) {
@@ -1223,7 +1190,7 @@ int codae_step_backward_async(codae_handle h, const codae_buffers* b, int32_t B,
     if (rc) return rc;
     CODAE_REQUIRE(b->grads && b->dacts, "codae_step_backward_async: grads / dacts missing");
     CODAE_REQUIRE(layer_lo >= 0 && layer_lo < layer_hi && layer_hi <= h->L, "codae_step_backward_async: layer range [%d, %d)", layer_lo, layer_hi);
-    return backward_range(h, b, B, layer_lo, layer_hi, nullptr, true, (hipStream_t)stream, false);
+    return backward_range(h, b, B, layer_lo, layer_hi, nullptr, true, false, (hipStream_t)stream, false);
 }
 
 int codae_side_stream(codae_handle h, void** out) {
@@ -1239,31 +1206,23 @@ int codae_side_stream(codae_handle h, void** out) {
 static int update_impl(codae_handle h, const codae_buffers* b, const codae_hyper* hyper, hipStream_t s, bool weights_norm_done) {
     CODAE_REQUIRE(h && b && hyper, "codae_step_update: null argument");
     CODAE_REQUIRE(b->params && b->grads && b->adam_m && b->adam_v && b->scalars, "codae_step_update: buffer missing");
-    {
-        int rcw = join_side(h, s);            // (a backward issued with codae_step_backward_async)
-        if (rcw) return rcw;
-    }
-    {
-        bool pending = false;
-        for (int l = 0; l < h->L; ++l) pending = pending || h->parts_pending[l] > 0;
-        if (pending && b->bias_parts != nullptr) {           // (a bucketed backward that did not reach layer 0)
-            int rcb = finish_bias(h, b, s, false);
-            if (rcb) return rcb;
-        }
+    int rc = join_side(h, s);                 // (a backward issued with codae_step_backward_async)
+    if (rc) return rc;
+    bool pending = false;
+    for (int l = 0; l < h->L; ++l) pending = pending || h->parts_pending[l] > 0;
+    if (pending && b->bias_parts != nullptr) {               // (a bucketed backward that did not reach layer 0)
+        rc = finish_bias(h, b, s, false);
+        if (rc) return rc;
     }
     const bool scalars_zero = h->norm_scalars_zero;
     h->norm_scalars_zero = false;
-    (void)scalars_zero;
     if (hyper->max_grad_norm > 0.f && !weights_norm_done) {    // (else: sum g^2 was accumulated by the slab reduces / the
         ProfScope prof(h, CODAE_K_SUMSQ, s);                    //  grouped weight-gradient epilogues and the bias finish)
-        int rc;
-        {
-            if (!scalars_zero) {                 // (a stand-alone update: no step_forward_loss of this step cleared them)
-                CODAE_HIP_CHECK(hipMemsetAsync(b->scalars + CODAE_S_GRAD_SQ, 0, sizeof(double), s));
-                CODAE_HIP_CHECK(hipMemsetAsync(b->scalars + CODAE_S_GRAD_SQ_SLOTS, 0, CODAE_S_N_SLOTS * sizeof(double), s));
-            }
-            rc = launch_sumsq(b->grads, h->n_param, b->scalars + CODAE_S_GRAD_SQ, s);
+        if (!scalars_zero) {                     // (a stand-alone update: no step_forward_loss of this step cleared them)
+            CODAE_HIP_CHECK(hipMemsetAsync(b->scalars + CODAE_S_GRAD_SQ, 0, sizeof(double), s));
+            CODAE_HIP_CHECK(hipMemsetAsync(b->scalars + CODAE_S_GRAD_SQ_SLOTS, 0, CODAE_S_N_SLOTS * sizeof(double), s));
         }
+        rc = launch_sumsq(b->grads, h->n_param, b->scalars + CODAE_S_GRAD_SQ, s);
         if (rc) return rc;
     }
     bf16_t* shadow = h->prec == CODAE_PREC_BF16 ? reinterpret_cast<bf16_t*>(b->shadow_w) : nullptr;
@@ -1278,9 +1237,9 @@ static int update_impl(codae_handle h, const codae_buffers* b, const codae_hyper
                                       reinterpret_cast<bf16_t*>(b->shadow_wt), h->L, h->w_off.data(), h->out.data(), h->in.data(),
                                       1, h->bias_begin, h->n_param - h->bias_begin, s, step_dev);
     }
-    int rca = launch_clip_adam(b->params, b->grads, b->adam_m, b->adam_v, h->n_param, hyper, b->scalars + CODAE_S_GRAD_SQ,
-                               shadow, nullptr, s, step_dev);
-    if (rca) return rca;
+    rc = launch_clip_adam(b->params, b->grads, b->adam_m, b->adam_v, h->n_param, hyper, b->scalars + CODAE_S_GRAD_SQ,
+                          shadow, nullptr, s, step_dev);
+    if (rc) return rc;
     return refresh_transposed(h, b, s);
 }
 
@@ -1362,9 +1321,8 @@ int codae_train_step(codae_handle h, const codae_buffers* b, const codae_batch* 
     // gathered while the split-K slabs are reduced (finish_loss zeroed GRAD_SQ before the backward)
     // bf16: every weight gradient leaves its sum g^2 behind - split ones in the slab reduce, unsplit ones in the GEMM epilogue
     const bool all_slabbed = h->prec == CODAE_PREC_BF16 && hyper->max_grad_norm > 0.f && !h->cfg.no_fused_norm;
-    h->norm_in_backward = all_slabbed;
-    rc = codae_step_backward(h, b, batch->B, 0, h->L, stream);
-    h->norm_in_backward = false;
+    // (codae_step_backward's argument checks - check_common, grads / dacts - were made by codae_step_forward_loss just above)
+    rc = backward_range(h, b, batch->B, 0, h->L, nullptr, true, all_slabbed, (hipStream_t)stream);
     if (rc) return rc;
     return update_impl(h, b, hyper, (hipStream_t)stream, all_slabbed);
 }
@@ -1490,7 +1448,7 @@ int codae_train_step_dp(codae_handle h, const codae_buffers* b, const codae_batc
     int rc = codae_step_forward_loss(h, b, batch, hyper, nullptr, stream);
     if (rc) return rc;
     for (int i = 0; i < n_buckets; ++i) {
-        rc = backward_range(h, b, batch->B, bucket_lo[i], bucket_hi[i], nullptr, true, s, false);
+        rc = backward_range(h, b, batch->B, bucket_lo[i], bucket_hi[i], nullptr, true, false, s, false);
         if (rc) return rc;
         // the bucket's weight gradients are complete, in order, on the side stream (or on s itself in single-stream mode)
         hipStream_t producer = h->side != nullptr && !h->cfg.single_stream ? h->side : s;
@@ -1511,214 +1469,6 @@ int codae_train_step_dp(codae_handle h, const codae_buffers* b, const codae_batc
     CODAE_HIP_CHECK(hipEventRecord(d->ev_done, d->stream));
     CODAE_HIP_CHECK(hipStreamWaitEvent(s, d->ev_done, 0));
     return update_impl(h, b, hyper, s, false);
-}
-
-// ---- stand-alone ops --------------------------------------------------------------------
-
-int codae_corrupt(const float* x, const float* mask, float* out, int64_t n, void* stream) {
-    return launch_corrupt(x, mask, out, n, (hipStream_t)stream);
-}
-
-int codae_corrupt_batch(const codae_batch* batch, const codae_noise* noise, int32_t step, const int32_t* noise_rows, void* out,
-                        int32_t out_bf16, int64_t out_ld, void* stream) {
-    CODAE_REQUIRE(noise_rows == nullptr || (batch != nullptr && batch->row_idx == nullptr), "codae_corrupt_batch: noise_rows go with an already gathered batch (row_idx NULL)");
-    return launch_gather_noise(batch, noise, step, nullptr, out, out_bf16, (hipStream_t)stream, out_ld, noise_rows);
-}
-
-int codae_noise_box_muller(const uint32_t* ra, const uint32_t* rb, float* rho, float* c, float* s, int64_t n, void* stream) {
-    return launch_noise_box_muller(ra, rb, rho, c, s, n, (hipStream_t)stream);
-}
-
-int codae_expand_masks(const int32_t* mask_id, const uint8_t* mask_table, const int32_t* k_of_mask, int32_t B, int32_t io,
-                       int32_t k_max, float* masks_out, float* fmask_out, void* stream) {
-    return launch_expand_masks(mask_id, mask_table, k_of_mask, B, io, k_max, masks_out, fmask_out, (hipStream_t)stream);
-}
-
-int codae_mse_loss_fwd_bwd(const float* x, const float* y, const float* fmask, float* dy, int64_t n, float inv_n,
-                           double* scalars, void* stream) {
-    int rc = launch_mse_dense(x, y, fmask, dy, n, inv_n, scalars, (hipStream_t)stream);
-    if (rc) return rc;
-    return launch_finish_loss(scalars, 1.0 / (double)n, (hipStream_t)stream);
-}
-
-int codae_clip_adam(float* params, float* grads, float* adam_m, float* adam_v, int64_t n, const codae_hyper* hyper,
-                    double* scalars, void* stream) {
-    CODAE_REQUIRE(hyper && scalars, "codae_clip_adam: null argument");
-    hipStream_t s = (hipStream_t)stream;
-    if (hyper->max_grad_norm > 0.f) {
-        CODAE_HIP_CHECK(hipMemsetAsync(scalars + CODAE_S_GRAD_SQ, 0, sizeof(double), s));
-        CODAE_HIP_CHECK(hipMemsetAsync(scalars + CODAE_S_GRAD_SQ_SLOTS, 0, CODAE_S_N_SLOTS * sizeof(double), s));
-        int rc = launch_sumsq(grads, n, scalars + CODAE_S_GRAD_SQ, s);
-        if (rc) return rc;
-    }
-    return launch_clip_adam(params, grads, adam_m, adam_v, n, hyper, scalars + CODAE_S_GRAD_SQ, nullptr, nullptr, s);
-}
-
-// ---- GEMM primitives ------------------------------------------------------------------------
-
-int codae_linear_f32(const float* x, const float* W, const float* bias, float* y, int32_t M, int32_t N, int32_t K,
-                     int32_t relu, void* stream) {
-    CODAE_REQUIRE(x && W && y, "codae_linear_f32: null operand");
-    GemmF32 g{};
-    g.A = x; g.a_rs = K; g.a_ks = 1;
-    g.B = W; g.b_rs = K; g.b_ks = 1;
-    g.C = y; g.ldc = N; g.M = M; g.N = N; g.K = K;
-    g.bias = bias; g.relu = relu;
-    return gemm_f32(g, (hipStream_t)stream);
-}
-
-int codae_dgrad_f32(const float* dy, const float* W, const float* relu_src, float* dx, int32_t M, int32_t N, int32_t K,
-                    void* stream) {
-    CODAE_REQUIRE(dy && W && dx, "codae_dgrad_f32: null operand");
-    GemmF32 g{};
-    g.A = dy; g.a_rs = N; g.a_ks = 1;
-    g.B = W; g.b_rs = 1; g.b_ks = K;
-    g.C = dx; g.ldc = K; g.M = M; g.N = K; g.K = N;
-    g.relu_src = relu_src; g.ld_relu = K;
-    return gemm_f32(g, (hipStream_t)stream);
-}
-
-int codae_wgrad_f32(const float* dy, const float* x, float* dW, float* db, int32_t M, int32_t N, int32_t K, void* stream) {
-    CODAE_REQUIRE(dy && x && dW, "codae_wgrad_f32: null operand");
-    GemmF32 g{};
-    g.A = dy; g.a_rs = 1; g.a_ks = N;
-    g.B = x; g.b_rs = 1; g.b_ks = K;
-    g.C = dW; g.ldc = K; g.M = N; g.N = K; g.K = M;
-    int rc = gemm_f32(g, (hipStream_t)stream);
-    if (rc) return rc;
-    if (db) return launch_colsum_f32(dy, M, N, db, (hipStream_t)stream);
-    return CODAE_OK;
-}
-
-int codae_linear_bf16(const void* x, const void* W, const float* bias, void* y, int32_t y_f32, int32_t M, int32_t N,
-                      int32_t K, int32_t relu, void* stream) {
-    CODAE_REQUIRE(x && W && y, "codae_linear_bf16: null operand");
-    GemmBf16 g{};
-    g.A = reinterpret_cast<const bf16_t*>(x); g.lda = K; g.a_mode = OP_KC;
-    g.B = reinterpret_cast<const bf16_t*>(W); g.ldb = K; g.b_mode = OP_KC;
-    g.C = y; g.ldc = N; g.c_f32 = y_f32; g.M = M; g.N = N; g.K = K;
-    g.bias = bias; g.relu = relu; g.split_k = 1;
-    return gemm_bf16(g, (hipStream_t)stream);
-}
-
-int codae_dgrad_bf16(const void* dy, const void* W, const void* relu_src, void* dx, float* db_prev, float* db_ws, int32_t M,
-                     int32_t N, int32_t K, void* stream) {
-    CODAE_REQUIRE(dy && W && dx, "codae_dgrad_bf16: null operand");
-    CODAE_REQUIRE(db_prev == nullptr || db_ws != nullptr, "codae_dgrad_bf16: db_prev needs the db_ws scratch");
-    GemmBf16 g{};
-    g.A = reinterpret_cast<const bf16_t*>(dy); g.lda = N; g.a_mode = OP_KC;
-    g.B = reinterpret_cast<const bf16_t*>(W); g.ldb = K; g.b_mode = OP_KS;
-    g.C = dx; g.ldc = K; g.c_f32 = 0; g.M = M; g.N = K; g.K = N;
-    g.relu_src = reinterpret_cast<const bf16_t*>(relu_src); g.ld_relu = K;
-    g.colsum_part = db_prev ? db_ws : nullptr; g.split_k = 1;
-    int rc = gemm_bf16(g, (hipStream_t)stream);
-    if (rc || db_prev == nullptr) return rc;
-    BiasFinishJobs jobs;
-    jobs.n = 1; jobs.parts[0] = db_ws; jobs.out[0] = db_prev; jobs.rows[0] = gemm_bf16_colsum_rows(g); jobs.cols[0] = K;
-    jobs.col_begin[0] = 0; jobs.col_begin[1] = K;
-    return launch_bias_finish(jobs, nullptr, (hipStream_t)stream);
-}
-
-static void act_args(GemmF32& g, int32_t act, float p0, float p1, float p2) {
-    g.act = act; g.act_p[0] = p0; g.act_p[1] = p1; g.act_p[2] = p2;
-}
-static void act_args(GemmBf16& g, int32_t act, float p0, float p1, float p2) {
-    g.act = act; g.act_p[0] = p0; g.act_p[1] = p1; g.act_p[2] = p2;
-}
-
-int codae_linear_act_f32(const float* x, const float* W, const float* bias, float* y, int32_t M, int32_t N, int32_t K, int32_t act,
-                         float p0, float p1, float p2, void* stream) {
-    CODAE_REQUIRE(act >= CODAE_ACT_NONE && act <= CODAE_ACT_HARDSIGMOID, "codae_linear_act_f32: activation kind %d", act);
-    if (act == CODAE_ACT_NONE) return codae_linear_f32(x, W, bias, y, M, N, K, 0, stream);
-    CODAE_REQUIRE(x && W && y, "codae_linear_act_f32: null operand");
-    GemmF32 g{};
-    g.A = x; g.a_rs = K; g.a_ks = 1;
-    g.B = W; g.b_rs = K; g.b_ks = 1;
-    g.C = y; g.ldc = N; g.M = M; g.N = N; g.K = K;
-    g.bias = bias;
-    act_args(g, act, p0, p1, p2);
-    return gemm_f32(g, (hipStream_t)stream);
-}
-
-int codae_dgrad_act_f32(const float* dy, const float* W, const float* act_src, float* dx, int32_t M, int32_t N, int32_t K, int32_t act,
-                        float p0, float p1, float p2, void* stream) {
-    CODAE_REQUIRE(act >= CODAE_ACT_NONE && act <= CODAE_ACT_HARDSIGMOID, "codae_dgrad_act_f32: activation kind %d", act);
-    if (act == CODAE_ACT_NONE || act_src == nullptr) return codae_dgrad_f32(dy, W, nullptr, dx, M, N, K, stream);
-    CODAE_REQUIRE(dy && W && dx, "codae_dgrad_act_f32: null operand");
-    GemmF32 g{};
-    g.A = dy; g.a_rs = N; g.a_ks = 1;
-    g.B = W; g.b_rs = 1; g.b_ks = K;
-    g.C = dx; g.ldc = K; g.M = M; g.N = K; g.K = N;
-    g.relu_src = act_src; g.ld_relu = K;
-    act_args(g, act, p0, p1, p2);
-    return gemm_f32(g, (hipStream_t)stream);
-}
-
-int codae_linear_act_bf16(const void* x, const void* W, const float* bias, void* y, int32_t y_f32, int32_t M, int32_t N, int32_t K,
-                          int32_t act, float p0, float p1, float p2, void* stream) {
-    CODAE_REQUIRE(act >= CODAE_ACT_NONE && act <= CODAE_ACT_HARDSIGMOID, "codae_linear_act_bf16: activation kind %d", act);
-    if (act == CODAE_ACT_NONE) return codae_linear_bf16(x, W, bias, y, y_f32, M, N, K, 0, stream);
-    CODAE_REQUIRE(x && W && y, "codae_linear_act_bf16: null operand");
-    GemmBf16 g{};
-    g.A = reinterpret_cast<const bf16_t*>(x); g.lda = K; g.a_mode = OP_KC;
-    g.B = reinterpret_cast<const bf16_t*>(W); g.ldb = K; g.b_mode = OP_KC;
-    g.C = y; g.ldc = N; g.c_f32 = y_f32; g.M = M; g.N = N; g.K = K;
-    g.bias = bias; g.split_k = 1;
-    act_args(g, act, p0, p1, p2);
-    return gemm_bf16(g, (hipStream_t)stream);
-}
-
-int codae_dgrad_act_bf16(const void* dy, const void* W, const void* act_src, void* dx, float* db_prev, float* db_ws, int32_t M,
-                         int32_t N, int32_t K, int32_t act, float p0, float p1, float p2, void* stream) {
-    CODAE_REQUIRE(act >= CODAE_ACT_NONE && act <= CODAE_ACT_HARDSIGMOID, "codae_dgrad_act_bf16: activation kind %d", act);
-    if (act == CODAE_ACT_NONE || act_src == nullptr) return codae_dgrad_bf16(dy, W, nullptr, dx, db_prev, db_ws, M, N, K, stream);
-    CODAE_REQUIRE(dy && W && dx, "codae_dgrad_act_bf16: null operand");
-    CODAE_REQUIRE(db_prev == nullptr || db_ws != nullptr, "codae_dgrad_act_bf16: db_prev needs the db_ws scratch");
-    GemmBf16 g{};
-    g.A = reinterpret_cast<const bf16_t*>(dy); g.lda = N; g.a_mode = OP_KC;
-    g.B = reinterpret_cast<const bf16_t*>(W); g.ldb = K; g.b_mode = OP_KS;
-    g.C = dx; g.ldc = K; g.c_f32 = 0; g.M = M; g.N = K; g.K = N;
-    g.relu_src = reinterpret_cast<const bf16_t*>(act_src); g.ld_relu = K;
-    g.colsum_part = db_prev ? db_ws : nullptr; g.split_k = 1;
-    act_args(g, act, p0, p1, p2);
-    int rc = gemm_bf16(g, (hipStream_t)stream);
-    if (rc || db_prev == nullptr) return rc;
-    BiasFinishJobs jobs;
-    jobs.n = 1; jobs.parts[0] = db_ws; jobs.out[0] = db_prev; jobs.rows[0] = gemm_bf16_colsum_rows(g); jobs.cols[0] = K;
-    jobs.col_begin[0] = 0; jobs.col_begin[1] = K;
-    return launch_bias_finish(jobs, nullptr, (hipStream_t)stream);
-}
-
-int codae_wgrad_bf16(const void* dy, const void* x, float* dW, void* slabs, int64_t slab_bytes, int32_t M, int32_t N,
-                     int32_t K, void* stream) {
-    CODAE_REQUIRE(dy && x && dW, "codae_wgrad_bf16: null operand");
-    CODAE_REQUIRE(M % 64 == 0, "codae_wgrad_bf16: batch rows %d must be a multiple of 64 (pad with zero rows)", M);
-    int S = choose_split_k(N, K, M);
-    while (S > 1 && (slabs == nullptr || (int64_t)S * N * K * 4 > slab_bytes)) --S;
-    GemmBf16 g{};
-    g.A = reinterpret_cast<const bf16_t*>(dy); g.lda = N; g.a_mode = OP_KS;
-    g.B = reinterpret_cast<const bf16_t*>(x); g.ldb = K; g.b_mode = OP_KS;
-    g.ldc = K; g.c_f32 = 1; g.M = N; g.N = K; g.K = M; g.split_k = S;
-    g.C = S > 1 ? slabs : (void*)dW;
-    int rc = gemm_bf16(g, (hipStream_t)stream);
-    if (rc) return rc;
-    if (S > 1) return launch_reduce_slabs(reinterpret_cast<const float*>(slabs), S, (int64_t)N * K, dW, (int64_t)N * K, nullptr, (hipStream_t)stream);
-    return CODAE_OK;
-}
-
-int codae_debug_gemm_timeline(uint64_t* host_out, int32_t n_wg) {
-    return gemm_bf16_timeline(reinterpret_cast<unsigned long long*>(host_out), n_wg);
-}
-
-int codae_transpose_bf16(const void* src, void* dst, int32_t rows, int32_t cols, void* stream) {
-    CODAE_REQUIRE(src && dst && rows > 0 && cols > 0, "transpose: bad args");
-    const int64_t off = 0;
-    return launch_transpose_bf16(reinterpret_cast<const bf16_t*>(src), reinterpret_cast<bf16_t*>(dst), 1, &off, &rows, &cols,
-                                 (hipStream_t)stream);
-}
-
-int codae_cast_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream) {
-    return launch_cast_bf16(src, reinterpret_cast<bf16_t*>(dst), n, (hipStream_t)stream);
 }
 
 }  // extern "C"

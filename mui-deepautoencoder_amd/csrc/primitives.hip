@@ -1,0 +1,187 @@
+// Stand-alone C-ABI primitives of libcodae_hip.so: single kernels and single GEMMs on the caller's tensors, no engine.
+#include "layer_gemm.h"
+
+using namespace codae;
+
+namespace {
+
+int linear_f32(const char* who, const float* x, const float* W, const float* bias, float* y, int M, int N, int K, int relu, int act,
+               const float* p, hipStream_t s) {
+    CODAE_REQUIRE(x && W && y, "%s: null operand", who);
+    GemmF32 g = fwd_gemm_f32(x, W, y, M, N, K, bias);
+    set_activation(g, relu, act, p);
+    return gemm_f32(g, s);
+}
+
+// src: the saved activation the mask / derivative is taken from, or null
+int dgrad_f32(const char* who, const float* dy, const float* W, const float* src, float* dx, int M, int N, int K, int act, const float* p,
+              hipStream_t s) {
+    CODAE_REQUIRE(dy && W && dx, "%s: null operand", who);
+    GemmF32 g = dgrad_gemm_f32(dy, W, dx, M, N, K);
+    g.relu_src = src; g.ld_relu = K;
+    set_activation(g, 0, act, p);
+    return gemm_f32(g, s);
+}
+
+int linear_bf16(const char* who, const void* x, const void* W, const float* bias, void* y, int y_f32, int M, int N, int K, int relu,
+                int act, const float* p, hipStream_t s) {
+    CODAE_REQUIRE(x && W && y, "%s: null operand", who);
+    GemmBf16 g = fwd_gemm_bf16(x, K, W, K, y, N, y_f32, M, N, K, bias);
+    set_activation(g, relu, act, p);
+    return gemm_bf16(g, s);
+}
+
+// data gradient, then (db_prev != null) the finish of its one bias job: db_prev[k] = column sums of dx
+int dgrad_bf16(const char* who, const void* dy, const void* W, const void* src, void* dx, float* db_prev, float* db_ws, int M, int N,
+               int K, int act, const float* p, hipStream_t s) {
+    CODAE_REQUIRE(dy && W && dx, "%s: null operand", who);
+    CODAE_REQUIRE(db_prev == nullptr || db_ws != nullptr, "%s: db_prev needs the db_ws scratch", who);
+    GemmBf16 g = dgrad_gemm_bf16(dy, N, W, K, false, dx, K, 0, M, K, N);
+    g.relu_src = reinterpret_cast<const bf16_t*>(src); g.ld_relu = K;
+    g.colsum_part = db_prev ? db_ws : nullptr;
+    set_activation(g, 0, act, p);
+    int rc = gemm_bf16(g, s);
+    if (rc || db_prev == nullptr) return rc;
+    BiasFinishJobs jobs;
+    jobs.n = 1; jobs.parts[0] = db_ws; jobs.out[0] = db_prev; jobs.rows[0] = gemm_bf16_colsum_rows(g); jobs.cols[0] = K;
+    jobs.col_begin[0] = 0; jobs.col_begin[1] = K;
+    return launch_bias_finish(jobs, nullptr, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int codae_corrupt(const float* x, const float* mask, float* out, int64_t n, void* stream) {
+    return launch_corrupt(x, mask, out, n, (hipStream_t)stream);
+}
+
+int codae_corrupt_batch(const codae_batch* batch, const codae_noise* noise, int32_t step, const int32_t* noise_rows, void* out,
+                        int32_t out_bf16, int64_t out_ld, void* stream) {
+    CODAE_REQUIRE(noise_rows == nullptr || (batch != nullptr && batch->row_idx == nullptr), "codae_corrupt_batch: noise_rows go with an already gathered batch (row_idx NULL)");
+    return launch_gather_noise(batch, noise, step, nullptr, out, out_bf16, (hipStream_t)stream, out_ld, noise_rows);
+}
+
+int codae_noise_box_muller(const uint32_t* ra, const uint32_t* rb, float* rho, float* c, float* s, int64_t n, void* stream) {
+    return launch_noise_box_muller(ra, rb, rho, c, s, n, (hipStream_t)stream);
+}
+
+int codae_expand_masks(const int32_t* mask_id, const uint8_t* mask_table, const int32_t* k_of_mask, int32_t B, int32_t io,
+                       int32_t k_max, float* masks_out, float* fmask_out, void* stream) {
+    return launch_expand_masks(mask_id, mask_table, k_of_mask, B, io, k_max, masks_out, fmask_out, (hipStream_t)stream);
+}
+
+int codae_mse_loss_fwd_bwd(const float* x, const float* y, const float* fmask, float* dy, int64_t n, float inv_n,
+                           double* scalars, void* stream) {
+    int rc = launch_mse_dense(x, y, fmask, dy, n, inv_n, scalars, (hipStream_t)stream);
+    if (rc) return rc;
+    return launch_finish_loss(scalars, 1.0 / (double)n, (hipStream_t)stream);
+}
+
+int codae_clip_adam(float* params, float* grads, float* adam_m, float* adam_v, int64_t n, const codae_hyper* hyper,
+                    double* scalars, void* stream) {
+    CODAE_REQUIRE(hyper && scalars, "codae_clip_adam: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    if (hyper->max_grad_norm > 0.f) {
+        CODAE_HIP_CHECK(hipMemsetAsync(scalars + CODAE_S_GRAD_SQ, 0, sizeof(double), s));
+        CODAE_HIP_CHECK(hipMemsetAsync(scalars + CODAE_S_GRAD_SQ_SLOTS, 0, CODAE_S_N_SLOTS * sizeof(double), s));
+        int rc = launch_sumsq(grads, n, scalars + CODAE_S_GRAD_SQ, s);
+        if (rc) return rc;
+    }
+    return launch_clip_adam(params, grads, adam_m, adam_v, n, hyper, scalars + CODAE_S_GRAD_SQ, nullptr, nullptr, s);
+}
+
+// ---- GEMM primitives ------------------------------------------------------------------------
+// The plain entry points run the ReLU / identity code (`relu`); the _act_ ones the generic-activation instantiation, CODAE_ACT_RELU
+// included, and hand CODAE_ACT_NONE (or a data gradient without a saved activation) to the plain one.
+
+int codae_linear_f32(const float* x, const float* W, const float* bias, float* y, int32_t M, int32_t N, int32_t K,
+                     int32_t relu, void* stream) {
+    return linear_f32("codae_linear_f32", x, W, bias, y, M, N, K, relu, CODAE_ACT_NONE, nullptr, (hipStream_t)stream);
+}
+
+int codae_dgrad_f32(const float* dy, const float* W, const float* relu_src, float* dx, int32_t M, int32_t N, int32_t K,
+                    void* stream) {
+    return dgrad_f32("codae_dgrad_f32", dy, W, relu_src, dx, M, N, K, CODAE_ACT_NONE, nullptr, (hipStream_t)stream);
+}
+
+int codae_wgrad_f32(const float* dy, const float* x, float* dW, float* db, int32_t M, int32_t N, int32_t K, void* stream) {
+    CODAE_REQUIRE(dy && x && dW, "codae_wgrad_f32: null operand");
+    int rc = gemm_f32(wgrad_gemm_f32(dy, x, dW, M, N, K), (hipStream_t)stream);
+    if (rc) return rc;
+    if (db) return launch_colsum_f32(dy, M, N, db, (hipStream_t)stream);
+    return CODAE_OK;
+}
+
+int codae_linear_bf16(const void* x, const void* W, const float* bias, void* y, int32_t y_f32, int32_t M, int32_t N,
+                      int32_t K, int32_t relu, void* stream) {
+    return linear_bf16("codae_linear_bf16", x, W, bias, y, y_f32, M, N, K, relu, CODAE_ACT_NONE, nullptr, (hipStream_t)stream);
+}
+
+int codae_dgrad_bf16(const void* dy, const void* W, const void* relu_src, void* dx, float* db_prev, float* db_ws, int32_t M,
+                     int32_t N, int32_t K, void* stream) {
+    return dgrad_bf16("codae_dgrad_bf16", dy, W, relu_src, dx, db_prev, db_ws, M, N, K, CODAE_ACT_NONE, nullptr, (hipStream_t)stream);
+}
+
+int codae_linear_act_f32(const float* x, const float* W, const float* bias, float* y, int32_t M, int32_t N, int32_t K, int32_t act,
+                         float p0, float p1, float p2, void* stream) {
+    CODAE_REQUIRE(act >= CODAE_ACT_NONE && act <= CODAE_ACT_HARDSIGMOID, "codae_linear_act_f32: activation kind %d", act);
+    if (act == CODAE_ACT_NONE) return codae_linear_f32(x, W, bias, y, M, N, K, 0, stream);
+    const float p[3] = {p0, p1, p2};
+    return linear_f32("codae_linear_act_f32", x, W, bias, y, M, N, K, 0, act, p, (hipStream_t)stream);
+}
+
+int codae_dgrad_act_f32(const float* dy, const float* W, const float* act_src, float* dx, int32_t M, int32_t N, int32_t K, int32_t act,
+                        float p0, float p1, float p2, void* stream) {
+    CODAE_REQUIRE(act >= CODAE_ACT_NONE && act <= CODAE_ACT_HARDSIGMOID, "codae_dgrad_act_f32: activation kind %d", act);
+    if (act == CODAE_ACT_NONE || act_src == nullptr) return codae_dgrad_f32(dy, W, nullptr, dx, M, N, K, stream);
+    const float p[3] = {p0, p1, p2};
+    return dgrad_f32("codae_dgrad_act_f32", dy, W, act_src, dx, M, N, K, act, p, (hipStream_t)stream);
+}
+
+int codae_linear_act_bf16(const void* x, const void* W, const float* bias, void* y, int32_t y_f32, int32_t M, int32_t N, int32_t K,
+                          int32_t act, float p0, float p1, float p2, void* stream) {
+    CODAE_REQUIRE(act >= CODAE_ACT_NONE && act <= CODAE_ACT_HARDSIGMOID, "codae_linear_act_bf16: activation kind %d", act);
+    if (act == CODAE_ACT_NONE) return codae_linear_bf16(x, W, bias, y, y_f32, M, N, K, 0, stream);
+    const float p[3] = {p0, p1, p2};
+    return linear_bf16("codae_linear_act_bf16", x, W, bias, y, y_f32, M, N, K, 0, act, p, (hipStream_t)stream);
+}
+
+int codae_dgrad_act_bf16(const void* dy, const void* W, const void* act_src, void* dx, float* db_prev, float* db_ws, int32_t M,
+                         int32_t N, int32_t K, int32_t act, float p0, float p1, float p2, void* stream) {
+    CODAE_REQUIRE(act >= CODAE_ACT_NONE && act <= CODAE_ACT_HARDSIGMOID, "codae_dgrad_act_bf16: activation kind %d", act);
+    if (act == CODAE_ACT_NONE || act_src == nullptr) return codae_dgrad_bf16(dy, W, nullptr, dx, db_prev, db_ws, M, N, K, stream);
+    const float p[3] = {p0, p1, p2};
+    return dgrad_bf16("codae_dgrad_act_bf16", dy, W, act_src, dx, db_prev, db_ws, M, N, K, act, p, (hipStream_t)stream);
+}
+
+int codae_wgrad_bf16(const void* dy, const void* x, float* dW, void* slabs, int64_t slab_bytes, int32_t M, int32_t N,
+                     int32_t K, void* stream) {
+    CODAE_REQUIRE(dy && x && dW, "codae_wgrad_bf16: null operand");
+    CODAE_REQUIRE(M % 64 == 0, "codae_wgrad_bf16: batch rows %d must be a multiple of 64 (pad with zero rows)", M);
+    int S = choose_split_k(N, K, M);
+    while (S > 1 && (slabs == nullptr || (int64_t)S * N * K * 4 > slab_bytes)) --S;
+    GemmBf16 g = wgrad_gemm_bf16(dy, N, x, K, S > 1 ? slabs : (void*)dW, M, N, K);
+    g.split_k = S;
+    int rc = gemm_bf16(g, (hipStream_t)stream);
+    if (rc) return rc;
+    if (S > 1) return launch_reduce_slabs(reinterpret_cast<const float*>(slabs), S, (int64_t)N * K, dW, (int64_t)N * K, nullptr, (hipStream_t)stream);
+    return CODAE_OK;
+}
+
+int codae_debug_gemm_timeline(uint64_t* host_out, int32_t n_wg) {
+    return gemm_bf16_timeline(reinterpret_cast<unsigned long long*>(host_out), n_wg);
+}
+
+int codae_transpose_bf16(const void* src, void* dst, int32_t rows, int32_t cols, void* stream) {
+    CODAE_REQUIRE(src && dst && rows > 0 && cols > 0, "transpose: bad args");
+    const int64_t off = 0;
+    return launch_transpose_bf16(reinterpret_cast<const bf16_t*>(src), reinterpret_cast<bf16_t*>(dst), 1, &off, &rows, &cols,
+                                 (hipStream_t)stream);
+}
+
+int codae_cast_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream) {
+    return launch_cast_bf16(src, reinterpret_cast<bf16_t*>(dst), n, (hipStream_t)stream);
+}
+
+}  // extern "C"
