@@ -174,6 +174,33 @@ __device__ __forceinline__ uint32_t act_dgrad_bf16x2(int kind, const float* p, u
 
 static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
+// ---- output store policy (GemmBf16::store_policy) ------------------------------------------------------
+// PLAIN: ordinary stores - the lines stay dirty in the writing XCD's L2 and are written back at the kernel's end, when no workgroup
+// computes any more.  WT: write-through stores (sc1) - every line leaves for memory as its store is issued, under the rest of the
+// epilogue and the K-loop tails of slower workgroups.  Same bytes, same addresses: a cache policy changes no value.
+// (sc0 sc1 measured the same as sc1 - 1.2043 against 1.2063 ms per C3 step over three alternating runs - and is not built.)
+enum { STORE_PLAIN = 0, STORE_WT = 1 };
+// policy of a launch that writes out_bytes: CODAE_STORE_POLICY when set, else by the output's size against the L2s (gemm_bf16.hip)
+int store_policy_for(int64_t out_bytes);
+
+// 16-byte-per-lane stores into one output tile under a policy fixed at COMPILE time (the cache-policy bits are instruction
+// immediates; a run-time choice per store - a scalar branch in front of each - ended the write-out loops' basic blocks at every
+// store and cost the plain path 1 us per C3 launch).  PLAIN: the ordinary pointer store this code always had.  WT: a raw buffer
+// descriptor over the tile's first row (wave-uniform base) + a 32-bit byte offset per lane (the launchers keep a tile's span under
+// 2 GiB or fall back to PLAIN).
+template <int POL>
+struct TileStore {
+    __amdgpu_buffer_rsrc_t rsrc;
+    __device__ __forceinline__ explicit TileStore(void* tile_base) {
+        if constexpr (POL != STORE_PLAIN) rsrc = __builtin_amdgcn_make_buffer_rsrc(tile_base, 0, 0x7fffffff, 0x00020000);
+    }
+    // p: the element's address; byte_off: the same place relative to tile_base
+    __device__ __forceinline__ void store16(void* p, uint32_t byte_off, u32x4 v) const {
+        if constexpr (POL == STORE_PLAIN) *reinterpret_cast<u32x4*>(p) = v;
+        else __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, (int)byte_off, 0, 16);      // aux 16: sc1
+    }
+};
+
 // CODAE_* tuning / ablation variables, read ONCE (library load, codae_create, codae_reload_env): nothing on the
 // launch path calls getenv (round 1 did, ~30 times per step)
 struct EnvToggles {
@@ -192,6 +219,8 @@ struct EnvToggles {
          no_relu_bits = false,        // CODAE_NO_RELU_BITS: the data gradient reads the saved activation for its ReLU mask
          no_prefetch = false,         // CODAE_NO_PREFETCH: no touch of the next launch's weights under the epilogue
          no_defer_wgrad = false;      // CODAE_NO_DEFER_WGRAD: per-layer split-K weight gradients beside the data-gradient chain (round 2's backward)
+    bool no_folded_loss_finish = false;      // CODAE_NO_FOLDED_LOSS_FINISH: the fused step's loss finish as a launch of its own
+    int store_policy = -1;       // CODAE_STORE_POLICY: plain (0), wt = sc1 write-through (1); -1 = by output size
 };
 const EnvToggles& env();
 void env_reload();
@@ -285,6 +314,8 @@ struct GemmBf16 {
                              // the stored values; data-gradient form: times act_dy_from_y of relu_src); no 1-bit masks, no fused loss,
                              // no k-strided A operand there
     float act_p[3];
+    int store_policy;        // STORE_*: how the pipelined kernels' epilogues store the output tile (bf16 rows, fused-loss dy, fp32 half
+                             // tiles; the mask dwords and column-sum rows stay plain).  Other kernels ignore it.
 };
 bool gemm_bf16_supported(int M, int N, int K);
 bool gemm_bf16_takes_relu_bits(int M, int N);    // forward-form bf16 launch of this output shape runs on a pipelined kernel
@@ -331,13 +362,15 @@ int launch_chain_step(const ChainArgs& a, hipStream_t s);
 
 // ---- elementwise / reductions (elementwise.hip) ----------------------------
 // out_ld: row stride of `out` in elements (0 = b->io: contiguous rows)
-int launch_gather_corrupt(const codae_batch* b, void* out, int out_bf16, hipStream_t s, int64_t out_ld = 0);
+// zero_norm != null: the scalars block - the launch also clears CODAE_S_GRAD_SQ and its slots (the fused step that folds its loss
+// finish into the bias finish: nothing else runs between the previous update and the first weight gradient)
+int launch_gather_corrupt(const codae_batch* b, void* out, int out_bf16, hipStream_t s, int64_t out_ld = 0, double* zero_norm = nullptr);
 // The same gather with the input noise of `noise` (codae_noise, include/codae_hip.h) in front of the slot mask: the noise-enabled
 // instantiations, beside the plain ones above.  step: the counter's step word; step_dev != null: read it from that device scalar
 // instead (graph replay: kernel arguments are frozen at capture); noise_rows: see codae_corrupt_batch.  check_noise: CODAE_E_INVALID with the offending argument named.
 int check_noise(const codae_noise* noise);
 int launch_gather_noise(const codae_batch* b, const codae_noise* noise, int32_t step, const double* step_dev, void* out,
-                        int out_bf16, hipStream_t s, int64_t out_ld = 0, const int32_t* noise_rows = nullptr);
+                        int out_bf16, hipStream_t s, int64_t out_ld = 0, const int32_t* noise_rows = nullptr, double* zero_norm = nullptr);
 int launch_noise_box_muller(const uint32_t* ra, const uint32_t* rb, float* rho, float* c, float* sn, int64_t n, hipStream_t s);
 int launch_cast_bf16(const float* src, bf16_t* dst, int64_t n, hipStream_t s);
 int launch_corrupt(const float* x, const float* mask, float* out, int64_t n, hipStream_t s);

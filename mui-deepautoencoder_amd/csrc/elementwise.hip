@@ -41,15 +41,27 @@ __device__ __forceinline__ uint2 pack_bf16x4(float a, float b, float c, float d)
     return o;
 }
 
+// zero_norm != null (the fused step whose loss finish rides in the bias-finish launch): the launch's first block clears the
+// clip_grad_norm_ accumulators - what finish_loss_kernel does in front of the backward when it runs as a launch of its own
+__device__ __forceinline__ void zero_norm_scalars(double* zero_norm) {
+    if (zero_norm != nullptr && blockIdx.x == 0) {
+        if (threadIdx.x == 0) zero_norm[CODAE_S_GRAD_SQ] = 0.0;
+        if (threadIdx.x < CODAE_S_N_SLOTS) zero_norm[CODAE_S_GRAD_SQ_SLOTS + threadIdx.x] = 0.0;
+    }
+}
+
 // The training step's form of the kernel below (bf16 out, io % 8 == 0): 8 elements per thread = two 16-B loads, one
 // 8-B mask load, one 16-B store (the 4-element form stores 8 B per lane, half-width store instructions).
+// (Measured and dropped: whole rows per wave - 2 rows x up to 4 column chunks of 16-B loads in flight per lane, row index and mask
+// id read once per row: 28.0 -> 27.1 us per launch on one box, 27.3 -> 27.8 on another: inside the noise)
 __global__ __launch_bounds__(NT) void gather_corrupt_bf16x8_kernel(const float* __restrict__ data,
                                                                    const int32_t* __restrict__ row_idx,
                                                                    const int32_t* __restrict__ mask_id,
                                                                    const uint8_t* __restrict__ table, int B, int io,
                                                                    bf16_t* __restrict__ out,
                                                                    const int32_t* __restrict__ mask_to_use, int nb_run,
-                                                                   int run, int64_t out_ld) {
+                                                                   int run, int64_t out_ld, double* zero_norm) {
+    zero_norm_scalars(zero_norm);
     const bool masked = (mask_id != nullptr) || (mask_to_use != nullptr);
     const int cols = io / 8;
     const int64_t total = (int64_t)B * cols;
@@ -84,7 +96,8 @@ __global__ __launch_bounds__(NT) void gather_corrupt_kernel(const float* __restr
                                                             const uint8_t* __restrict__ table, int B, int io,
                                                             void* __restrict__ out,
                                                             const int32_t* __restrict__ mask_to_use, int nb_run,
-                                                            int run, int64_t out_ld) {
+                                                            int run, int64_t out_ld, double* zero_norm) {
+    zero_norm_scalars(zero_norm);
     constexpr int W = VEC ? 4 : 1;
     const bool masked = (mask_id != nullptr) || (mask_to_use != nullptr);
     const int cols = io / W;
@@ -134,6 +147,7 @@ struct NoiseArgs {
     const int32_t* rows;       // not null: counter word 1 of batch row b is rows[b] (a batch gathered by the caller), else the row read
     uint64_t thresh;           // MASKING / SALT_PEPPER: T = floor(p 2^32)
     float p0, p1, p2;          // sigma; lo, hi
+    double* zero_norm;         // see zero_norm_scalars
 };
 
 __device__ __forceinline__ uint4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
@@ -198,6 +212,7 @@ __global__ __launch_bounds__(NT) void gather_noise_bf16x8_kernel(const float* __
                                                                  int B, int io, bf16_t* __restrict__ out,
                                                                  const int32_t* __restrict__ mask_to_use, int nb_run, int run,
                                                                  int64_t out_ld, NoiseArgs na) {
+    zero_norm_scalars(na.zero_norm);
     const bool masked = (mask_id != nullptr) || (mask_to_use != nullptr);
     const uint32_t step = na.step_dev ? (uint32_t)*na.step_dev : na.step;
     const int cols = io / 8;
@@ -231,6 +246,7 @@ __global__ __launch_bounds__(NT) void gather_noise_kernel(const float* __restric
                                                           const int32_t* __restrict__ mask_id, const uint8_t* __restrict__ table, int B,
                                                           int io, void* __restrict__ out, const int32_t* __restrict__ mask_to_use,
                                                           int nb_run, int run, int64_t out_ld, NoiseArgs na) {
+    zero_norm_scalars(na.zero_norm);
     constexpr int W = VEC ? 4 : 1;
     const bool masked = (mask_id != nullptr) || (mask_to_use != nullptr);
     const uint32_t step = na.step_dev ? (uint32_t)*na.step_dev : na.step;
@@ -793,7 +809,7 @@ inline bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) ==
 
 }  // namespace
 
-int launch_gather_corrupt(const codae_batch* b, void* out, int out_bf16, hipStream_t s, int64_t out_ld) {
+int launch_gather_corrupt(const codae_batch* b, void* out, int out_bf16, hipStream_t s, int64_t out_ld, double* zero_norm) {
     if (out_ld <= 0) out_ld = b ? b->io : 0;
     CODAE_REQUIRE(b && b->data && out && b->B > 0 && b->io > 0, "gather_corrupt: bad batch");
     const bool masked = b->mask_id || b->mask_to_use;
@@ -805,12 +821,12 @@ int launch_gather_corrupt(const codae_batch* b, void* out, int out_bf16, hipStre
     const int grid = grid_for(items);
     if (vec && out_bf16 && b->io % 8 == 0 && (!masked || (reinterpret_cast<uintptr_t>(b->mask_table) & 7) == 0)) {
         hipLaunchKernelGGL(gather_corrupt_bf16x8_kernel, dim3(grid_for(items / 2)), dim3(NT), 0, s, b->data, b->row_idx, b->mask_id,
-                           b->mask_table, b->B, b->io, reinterpret_cast<bf16_t*>(out), b->mask_to_use, b->nb_run, b->run, out_ld);
+                           b->mask_table, b->B, b->io, reinterpret_cast<bf16_t*>(out), b->mask_to_use, b->nb_run, b->run, out_ld, zero_norm);
         CODAE_LAUNCH_CHECK();
         return CODAE_OK;
     }
 #define GC(V, O) hipLaunchKernelGGL((gather_corrupt_kernel<V, O>), dim3(grid), dim3(NT), 0, s, b->data, b->row_idx, \
-                                    b->mask_id, b->mask_table, b->B, b->io, out, b->mask_to_use, b->nb_run, b->run, out_ld)
+                                    b->mask_id, b->mask_table, b->B, b->io, out, b->mask_to_use, b->nb_run, b->run, out_ld, zero_norm)
     if (vec && out_bf16) GC(true, true);
     else if (vec) GC(true, false);
     else if (out_bf16) GC(false, true);
@@ -839,8 +855,8 @@ int check_noise(const codae_noise* n) {
 }
 
 int launch_gather_noise(const codae_batch* b, const codae_noise* noise, int32_t step, const double* step_dev, void* out, int out_bf16,
-                        hipStream_t s, int64_t out_ld, const int32_t* noise_rows) {
-    if (noise == nullptr || noise->kind == CODAE_NOISE_NONE) return launch_gather_corrupt(b, out, out_bf16, s, out_ld);
+                        hipStream_t s, int64_t out_ld, const int32_t* noise_rows, double* zero_norm) {
+    if (noise == nullptr || noise->kind == CODAE_NOISE_NONE) return launch_gather_corrupt(b, out, out_bf16, s, out_ld, zero_norm);
     int rc = check_noise(noise);
     if (rc) return rc;
     if (out_ld <= 0) out_ld = b ? b->io : 0;
@@ -851,7 +867,7 @@ int launch_gather_noise(const codae_batch* b, const codae_noise* noise, int32_t 
                   "gather_corrupt: run %d outside [0, %d)", b->run, b->nb_run);
     NoiseArgs na{};
     na.key0 = (uint32_t)(noise->seed & 0xffffffffu); na.key1 = (uint32_t)(noise->seed >> 32);
-    na.step = (uint32_t)step; na.step_dev = step_dev; na.rows = noise_rows;
+    na.step = (uint32_t)step; na.step_dev = step_dev; na.rows = noise_rows; na.zero_norm = zero_norm;
     na.thresh = (uint64_t)floor((double)noise->p0 * 4294967296.0);      // (p <= 1: at most 2^32, above every word)
     na.p0 = noise->p0; na.p1 = noise->p1; na.p2 = noise->p2;
     const bool vec = (b->io % 4 == 0) && (out_ld % 4 == 0) && a16(b->data) && a16(out) && (!masked || (reinterpret_cast<uintptr_t>(b->mask_table) & 3) == 0);

@@ -45,6 +45,9 @@ void env_reload() {
     e.no_defer_wgrad = getenv("CODAE_NO_DEFER_WGRAD") != nullptr;
     e.no_prefetch = getenv("CODAE_NO_PREFETCH") != nullptr;
     e.no_relu_bits = getenv("CODAE_NO_RELU_BITS") != nullptr;
+    e.no_folded_loss_finish = getenv("CODAE_NO_FOLDED_LOSS_FINISH") != nullptr;
+    if (const char* k = getenv("CODAE_STORE_POLICY"))
+        e.store_policy = !strcmp(k, "plain") ? STORE_PLAIN : (!strcmp(k, "wt") ? STORE_WT : -1);
     if (const char* k = getenv("CODAE_F32_GEMM")) e.f32_gemm = k[0] == 'n' ? 1 : (k[0] == 'x' ? 2 : 0);
     if (const char* k = getenv("CODAE_SMALL_TILE_MAX")) e.small_tile_max = atoi(k);
     if (const char* k = getenv("CODAE_SMALL_STAGES")) e.small_stages = atoi(k) == 2 ? 2 : 4;
@@ -551,6 +554,7 @@ int run_wgrad(codae_engine* e, const codae_buffers* b, int l, int rows, bool wit
         GemmBf16 g = layer_wgrad_bf16(e, b, l, rows);
         g.split_k = S;
         if (S > 1) {
+            g.store_policy = store_policy_for((int64_t)S * N * K * 4);       // (the launch writes S slabs)
             CODAE_REQUIRE(b->slabs != nullptr, "bf16 wgrad needs the slab workspace");
             char* slab = reinterpret_cast<char*>(b->slabs) + (int64_t)slot * e->slab_bytes;
             g.C = slab;
@@ -699,8 +703,9 @@ int join_side(codae_engine* h, hipStream_t s) {
 // wgrad_1 on the side stream.  With join the call returns with `s` waiting for every side-stream kernel.
 // with_norm (single-GPU fused bf16 step: nothing happens to the gradients between backward and update): every launch that
 // leaves final gradient values behind also adds their sum g^2 to the clip_grad_norm_ accumulators.
+// loss: the step's loss finish, left to this call's bias-finish launch (codae_train_step)
 int backward_range(codae_handle h, const codae_buffers* b, int B, int lo, int hi, float* dx, bool step_mode, bool with_norm,
-                   hipStream_t s, bool join = true) {
+                   hipStream_t s, bool join = true, const LossFinish* loss = nullptr) {
     const int rows = h->rows_for(B);
     const bool dual = !h->cfg.single_stream;
     if (dual) {
@@ -723,7 +728,7 @@ int backward_range(codae_handle h, const codae_buffers* b, int B, int lo, int hi
         rc = defer == 3 ? run_wgrad_deferred_f32(h, b, rows, s)
                         : (defer == 1 ? run_wgrad_deferred(h, b, rows, with_norm, s) : run_wgrad_grouped(h, b, rows, with_norm, s));
         if (rc) return rc;
-        return finish_bias(h, b, s, with_norm);
+        return finish_bias(h, b, s, with_norm, loss);
     }
     bool* w_pending = h->w_pending;
     const bool coscheduled = dual;         // the weight gradients run beside the data-gradient chain
@@ -765,7 +770,7 @@ int backward_range(codae_handle h, const codae_buffers* b, int B, int lo, int hi
     // range (lo == 0) - one finish launch per step instead of one per bucket (10 x 6 us at C3); codae_step_update finishes
     // whatever a caller that stopped short left behind.
     if (join || lo == 0) {
-        int rc = finish_bias(h, b, s, with_norm);
+        int rc = finish_bias(h, b, s, with_norm, loss);
         if (rc) return rc;
     }
     if (dual) {
@@ -1082,8 +1087,12 @@ int codae_backward(codae_handle h, const codae_buffers* b, const float* dy, floa
     return backward_range(h, b, B, layer_lo, layer_hi, dx, false, false, s);
 }
 
-int codae_step_forward_loss(codae_handle h, const codae_buffers* b, const codae_batch* batch, const codae_hyper* hyper,
-                            float* out_y, void* stream) {
+// fold != null (codae_train_step): when the loss is fused into the last forward GEMM, its finish - 5 us of a one-block launch
+// plus a launch boundary between the loss GEMM and the first data gradient - is not launched: *fold describes it for the bias-finish
+// launch that ends the backward (as the chain path does), and the gather's first block clears the norm accumulators instead.
+// fold->scalars stays null when this call finished the loss itself.
+static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae_batch* batch, const codae_hyper* hyper,
+                             float* out_y, void* stream, LossFinish* fold) {
     CODAE_REQUIRE(batch != nullptr, "codae_step_forward_loss: null batch");
     int rc = check_common(h, b, batch->B);
     if (rc) return rc;
@@ -1096,20 +1105,22 @@ int codae_step_forward_loss(codae_handle h, const codae_buffers* b, const codae_
     const int B = batch->B, L = h->L;
     const int rows = h->rows_for(B);
     const bool bf = h->prec == CODAE_PREC_BF16;
+    // bf16 training step: the loss is folded into the last forward GEMM's epilogue (y never stored)
+    const bool fuse_loss = bf && hyper != nullptr && out_y == nullptr && !h->cfg.no_fused_loss;
+    const bool fold_finish = fuse_loss && fold != nullptr && !h->cfg.no_folded_loss_finish;
     {
         ProfScope prof(h, CODAE_K_GATHER, s);
+        double* zero_norm = fold_finish ? b->scalars : nullptr;
         if (hyper != nullptr && h->noise.kind != CODAE_NOISE_NONE)      // training input only; the loss below reads the clean row
             rc = launch_gather_noise(batch, &h->noise, hyper->step, h->capturing ? b->scalars + CODAE_S_ADAM_STEP : nullptr,
-                                     act_ptr(h, b, 0), bf, s, h->in_ld[0]);
+                                     act_ptr(h, b, 0), bf, s, h->in_ld[0], nullptr, zero_norm);
         else
-            rc = launch_gather_corrupt(batch, act_ptr(h, b, 0), bf, s, h->in_ld[0]);
+            rc = launch_gather_corrupt(batch, act_ptr(h, b, 0), bf, s, h->in_ld[0], zero_norm);
     }
     if (rc) return rc;
     rc = zero_pad_rows(h, act_ptr(h, b, 0), B, rows, h->in_ld[0], s);
     if (rc) return rc;
     float* y = out_y ? out_y : reinterpret_cast<float*>(act_ptr(h, b, L));
-    // bf16 training step: the loss is folded into the last forward GEMM's epilogue (y never stored)
-    const bool fuse_loss = bf && hyper != nullptr && out_y == nullptr && !h->cfg.no_fused_loss;
     GroupScope fwd_group(h, CODAE_K_GEMM_FWD, s);       // the plain forward launches of this step, back to back
     for (int l = 0; l < L; ++l) {
         const bool last = (l == L - 1);
@@ -1133,7 +1144,12 @@ int codae_step_forward_loss(codae_handle h, const codae_buffers* b, const codae_
             }
             if (rc) return rc;
             h->parts_pending[l] = gemm_bf16_colsum_rows(g);
-            h->norm_scalars_zero = true;
+            h->norm_scalars_zero = true;        // (by finish_loss below, or already by the gather's first block)
+            if (fold_finish) {
+                fold->scalars = b->scalars; fold->inv_n = 1.0 / ((double)B * batch->io);
+                fold->parts = loss_parts_ptr(h, b); fold->n_parts = n_loss_parts;
+                return CODAE_OK;
+            }
             return finish_loss(h, b, batch, n_loss_parts, s);
         }
         rc = last ? run_linear(h, b, l, act_ptr(h, b, l), y, true, B, s)
@@ -1158,6 +1174,11 @@ int codae_step_forward_loss(codae_handle h, const codae_buffers* b, const codae_
     rc = launch_mse_loss(batch, y, nullptr, 0, 0.f, nullptr, loss_parts_ptr(h, b), 0, s);
     if (rc) return rc;
     return finish_loss(h, b, batch, mse_loss_colsum_rows(B), s);
+}
+
+int codae_step_forward_loss(codae_handle h, const codae_buffers* b, const codae_batch* batch, const codae_hyper* hyper,
+                            float* out_y, void* stream) {
+    return forward_loss_impl(h, b, batch, hyper, out_y, stream, nullptr);
 }
 
 int codae_set_input_noise(codae_handle h, const codae_noise* noise) {
@@ -1315,14 +1336,15 @@ int codae_train_step(codae_handle h, const codae_buffers* b, const codae_batch* 
         if (rcc) return rcc;
         return update_impl(h, b, hyper, s, with_norm);
     }
-    int rc = codae_step_forward_loss(h, b, batch, hyper, nullptr, stream);
+    LossFinish lf{};                 // (filled when the loss finish is left to the backward's bias-finish launch)
+    int rc = forward_loss_impl(h, b, batch, hyper, nullptr, stream, &lf);
     if (rc) return rc;
     // single GPU: nothing happens to the gradients between backward and update, so the norm can be
     // gathered while the split-K slabs are reduced (finish_loss zeroed GRAD_SQ before the backward)
     // bf16: every weight gradient leaves its sum g^2 behind - split ones in the slab reduce, unsplit ones in the GEMM epilogue
     const bool all_slabbed = h->prec == CODAE_PREC_BF16 && hyper->max_grad_norm > 0.f && !h->cfg.no_fused_norm;
     // (codae_step_backward's argument checks - check_common, grads / dacts - were made by codae_step_forward_loss just above)
-    rc = backward_range(h, b, batch->B, 0, h->L, nullptr, true, all_slabbed, (hipStream_t)stream);
+    rc = backward_range(h, b, batch->B, 0, h->L, nullptr, true, all_slabbed, (hipStream_t)stream, true, lf.scalars != nullptr ? &lf : nullptr);
     if (rc) return rc;
     return update_impl(h, b, hyper, (hipStream_t)stream, all_slabbed);
 }

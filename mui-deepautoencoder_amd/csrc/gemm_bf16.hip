@@ -715,6 +715,13 @@ int gemm_bf16_grouped(GemmBf16Group& grp, hipStream_t s) {
     return CODAE_OK;
 }
 
+// Store policy of a launch from its output size: an output that fits the eight L2s together can still be
+// wholly dirty when the kernel ends, and the write-back then runs with every CU idle.
+int store_policy_for(int64_t out_bytes) {
+    if (env().store_policy >= 0) return env().store_policy;
+    return out_bytes <= ((int64_t)32 << 20) ? STORE_WT : STORE_PLAIN;
+}
+
 bool gemm_bf16_supported(int M, int N, int K) {
     // K: whole BK tiles; N: 16-byte rows for vector epilogue / staged chunks
     return M > 0 && N >= 8 && K >= BK && (K % BK) == 0 && (N % 8) == 0;

@@ -54,7 +54,8 @@ __device__ unsigned long long g_timeline[TIMELINE_WGS * TIMELINE_SLOTS];
 // One output tile (or split-K range of one) of one GEMM: the whole kernel body, shared by the plain kernel (one GEMM per
 // launch) and the grouped kernel (the weight gradients of every layer in one launch).  wg / nwg: this workgroup's index
 // among the nwg workgroups of ITS GEMM; smem_raw: 2 * BUF (+ BM * 8 for EPI 3) bytes of LDS.
-template <int BM, int BN, int WM, int WN, int NLB, int A_MODE, int B_MODE, bool C_F32, int DBG = 0, int EPI = 0>
+// POL: STORE_* policy of the output tile's 16-byte stores (GemmBf16::store_policy, chosen by the launcher)
+template <int BM, int BN, int WM, int WN, int NLB, int A_MODE, int B_MODE, bool C_F32, int DBG = 0, int EPI = 0, int POL = STORE_PLAIN>
 __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles_n, int tiles_mn, int kt_total, int wg, int nwg,
                                                     char* smem_raw) {
     constexpr int NW = WM * WN;
@@ -469,13 +470,14 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
             const int c = threadIdx.x % CH, rl = threadIdx.x / CH;
             const int j = j0 + c * 8;
             bf16_t* Cb = reinterpret_cast<bf16_t*>(g.C);
+            const TileStore<POL> out(Cb + (int64_t)i0 * g.ldc);
             constexpr int ITER = (BM + RL - 1) / RL;          // fully unrolled: every LDS read is issued before the first store
 #pragma unroll
             for (int it = 0; it < ITER; ++it) {
                 const int r = rl + it * RL;
                 const bool ok = rl < RL && j < g.N && r < BM && i0 + r < g.M;
                 const u32x4 lv = *reinterpret_cast<const __attribute__((address_space(3))) u32x4*>(smem + (ok ? r : 0) * PITCH + c * 16);
-                if (ok) *reinterpret_cast<uint4*>(Cb + (int64_t)(i0 + r) * g.ldc + j) = make_uint4(lv[0], lv[1], lv[2], lv[3]);
+                if (ok) out.store16(Cb + (int64_t)(i0 + r) * g.ldc + j, (uint32_t)(r * (int)g.ldc + j) * 2u, lv);
             }
         }
         if constexpr (dbg_time) { wait_vmcnt<0>(); stamp(4); }
@@ -583,6 +585,7 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
             // As a loop with one row per trip every trip waited for its own load: the data-gradient launch was 10 us
             // longer than the forward one.
             bf16_t* Cb = reinterpret_cast<bf16_t*>(g.C);
+            const TileStore<POL> out(Cb + (int64_t)i0 * g.ldc);
             const bool relu_mask = EPI != 1 && !bit_mask && g.relu_src != nullptr;
             const bf16_t* hsrc = relu_mask ? g.relu_src : g.A;                 // (no mask: any valid 16-B aligned bytes)
             const int64_t hld = relu_mask ? g.ld_relu : 0;
@@ -641,7 +644,7 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
                     }
                 }
                 if (ok) {
-                    *reinterpret_cast<uint4*>(Cb + (int64_t)(i0 + r) * g.ldc + j) = v;
+                    out.store16(Cb + (int64_t)(i0 + r) * g.ldc + j, (uint32_t)(r * (int)g.ldc + j) * 2u, (u32x4){v.x, v.y, v.z, v.w});
                     if (EPI != 1 && g.colsum_part != nullptr) {
                         cs[0] += bf16_to_f32((bf16_t)(v.x & 0xffff)); cs[1] += bf16_to_f32((bf16_t)(v.x >> 16));
                         cs[2] += bf16_to_f32((bf16_t)(v.y & 0xffff)); cs[3] += bf16_to_f32((bf16_t)(v.y >> 16));
@@ -707,13 +710,14 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
                 }
             __syncthreads();
             constexpr int ITER = (HR + RL - 1) / RL;
+            const TileStore<POL> out(Cf + (int64_t)(i0 + hh * HR) * g.ldc);
 #pragma unroll
             for (int it = 0; it < ITER; ++it) {
                 const int r = rl + it * RL;
                 const bool ok = rl < RL && j < g.N && r < HR && i0 + hh * HR + r < g.M;
                 const f32x4 v = *reinterpret_cast<const __attribute__((address_space(3))) f32x4*>(smem + (ok ? r : 0) * PITCH + c * 16);
                 if (ok) {
-                    *reinterpret_cast<float4*>(Cf + (int64_t)(i0 + hh * HR + r) * g.ldc + j) = make_float4(v[0], v[1], v[2], v[3]);
+                    out.store16(Cf + (int64_t)(i0 + hh * HR + r) * g.ldc + j, (uint32_t)(r * (int)g.ldc + j) * 4u, __builtin_bit_cast(u32x4, v));
                     sq += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
                 }
             }
@@ -734,13 +738,13 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
     }
 }
 
-template <int BM, int BN, int WM, int WN, int NLB, int A_MODE, int B_MODE, bool C_F32, int DBG = 0, int EPI = 0>
+template <int BM, int BN, int WM, int WN, int NLB, int A_MODE, int B_MODE, bool C_F32, int DBG = 0, int EPI = 0, int POL = STORE_PLAIN>
 __global__ __launch_bounds__(64 * WM * WN, (WM * WN + 3) / 4)
 void gemm_bf16_pipe_kernel(GemmBf16 g, int tiles_n, int tiles_mn, int kt_total) {
     // (EPI = 3: + {dataset row, mask id} of the tile's rows; ONE array: a second __shared__ object beside an LDS-DMA
     // staging array makes the compiler drain vmcnt in front of LDS reads)
     __shared__ __attribute__((aligned(16))) char smem_raw[2 * (BM + BN) * 128 + (EPI == 3 ? BM * 8 : 0)];
-    gemm_bf16_pipe_tile<BM, BN, WM, WN, NLB, A_MODE, B_MODE, C_F32, DBG, EPI>(g, tiles_n, tiles_mn, kt_total, blockIdx.x, gridDim.x, smem_raw);
+    gemm_bf16_pipe_tile<BM, BN, WM, WN, NLB, A_MODE, B_MODE, C_F32, DBG, EPI, POL>(g, tiles_n, tiles_mn, kt_total, blockIdx.x, gridDim.x, smem_raw);
 }
 
 // Every layer's weight gradient dW_l = dA_l^T H_l (both operands k-strided, fp32 straight into the gradient vector, K = the whole
@@ -748,6 +752,7 @@ void gemm_bf16_pipe_kernel(GemmBf16 g, int tiles_n, int tiles_mn, int kt_total) 
 // by the prefix sums of the descriptor block.  C3: 10 x 48 tiles of 128 K-tiles each on 256 CUs; the long K loop runs at the
 // rate DESIGN.md section 5 measured for K = 24576 (fixed costs amortised), where the per-layer launches (K = 1638 per workgroup
 // after a 5-way split) pay pipeline fill, epilogue and a 47 MB slab round trip per layer.
+template <int POL>
 __global__ __launch_bounds__(512, 2) void gemm_bf16_pipe_grouped_kernel(GemmBf16Group grp) {
     constexpr int BM = 256, BN = 192;
     __shared__ __attribute__((aligned(16))) char smem_raw[2 * (BM + BN) * 128];
@@ -766,7 +771,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pipe_grouped_kernel(GemmBf16
     while (j + 1 < grp.n && t >= grp.wg_begin[j + 1]) ++j;
     const GemmBf16& g = grp.g[j];
     const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN;
-    gemm_bf16_pipe_tile<BM, BN, 4, 2, 4, OP_KS, OP_KS, true, 0, 0>(g, tiles_n, tiles_m * tiles_n, g.K / BK, t - grp.wg_begin[j], 0, smem_raw);
+    gemm_bf16_pipe_tile<BM, BN, 4, 2, 4, OP_KS, OP_KS, true, 0, 0, POL>(g, tiles_n, tiles_m * tiles_n, g.K / BK, t - grp.wg_begin[j], 0, smem_raw);
 }
 
 template <int BM, int BN, int WM, int WN, int NLB>
@@ -780,8 +785,10 @@ int launch_pipe(const GemmBf16& g, hipStream_t s) {
                       (int64_t)(g.b_mode == OP_KC ? g.N : g.K) * g.ldb * 2 < (int64_t)1 << 32,
                   "gemm_bf16: operand larger than 4 GiB");
     dim3 grid((unsigned)nwg), block(64 * WM * WN);
+#define LAUNCH_POL(AM, BMODE, CF, EP, POL) \
+    hipLaunchKernelGGL((gemm_bf16_pipe_kernel<BM, BN, WM, WN, NLB, AM, BMODE, CF, 0, EP, POL>), grid, block, 0, s, g, tiles_n, tiles_m * tiles_n, kt_total)
 #define LAUNCH(AM, BMODE, CF, EP) \
-    hipLaunchKernelGGL((gemm_bf16_pipe_kernel<BM, BN, WM, WN, NLB, AM, BMODE, CF, 0, EP>), grid, block, 0, s, g, tiles_n, tiles_m * tiles_n, kt_total)
+    do { if (g.store_policy == STORE_WT) LAUNCH_POL(AM, BMODE, CF, EP, STORE_WT); else LAUNCH_POL(AM, BMODE, CF, EP, STORE_PLAIN); } while (0)
 #define LAUNCH_BF16(AM, BMODE) do { if (bwd_epi) LAUNCH(AM, BMODE, false, 2); else LAUNCH(AM, BMODE, false, 1); } while (0)
     const bool bwd_epi = g.relu_src != nullptr || g.colsum_part != nullptr;
     // (the data gradient beside another stream's weight gradients: the same kernel with the compiler's schedule, GemmBf16::coscheduled)
@@ -799,6 +806,7 @@ int launch_pipe(const GemmBf16& g, hipStream_t s) {
     else { set_error("gemm_bf16: operand mode combination not built"); return CODAE_E_UNSUPPORTED; }
 #undef LAUNCH_BF16
 #undef LAUNCH
+#undef LAUNCH_POL
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;
 }
@@ -810,6 +818,14 @@ template <int DBG>
 int launch_dbg(const GemmBf16& g, hipStream_t s) {
     constexpr int BM = 256, BN = 192;
     const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN;
+    if constexpr (DBG == 8) {          // (the stamped build follows the launch's store policy: tools/timeline_gemm.py)
+        if (g.store_policy == STORE_WT) {
+            hipLaunchKernelGGL((gemm_bf16_pipe_kernel<BM, BN, 4, 2, 4, OP_KC, OP_KC, false, 8, 0, STORE_WT>), dim3(tiles_m * tiles_n), dim3(512), 0, s, g,
+                               tiles_n, tiles_m * tiles_n, g.K / BK);
+            CODAE_LAUNCH_CHECK();
+            return CODAE_OK;
+        }
+    }
     hipLaunchKernelGGL((gemm_bf16_pipe_kernel<BM, BN, 4, 2, 4, OP_KC, OP_KC, false, DBG>), dim3(tiles_m * tiles_n), dim3(512), 0, s, g,
                        tiles_n, tiles_m * tiles_n, g.K / BK);
     CODAE_LAUNCH_CHECK();
@@ -824,10 +840,11 @@ int launch_pipe_mid(const GemmBf16& g, hipStream_t s) {
     CODAE_REQUIRE(g.a_mode == OP_KC && g.b_mode == OP_KC && !g.c_f32 && !g.loss.enabled && g.split_k == 1, "gemm_bf16: 128 x 192 tile is forward-form only");
     CODAE_REQUIRE((int64_t)g.M * g.lda * 2 < (int64_t)1 << 32 && (int64_t)g.N * g.ldb * 2 < (int64_t)1 << 32, "gemm_bf16: operand larger than 4 GiB");
     dim3 grid((unsigned)(tiles_m * tiles_n)), block(512);
-    if (g.relu_src != nullptr || g.colsum_part != nullptr)
-        hipLaunchKernelGGL((gemm_bf16_pipe_kernel<BM, BN, 4, 2, 4, OP_KC, OP_KC, false, 0, 2>), grid, block, 0, s, g, tiles_n, tiles_m * tiles_n, g.K / BK);
-    else
-        hipLaunchKernelGGL((gemm_bf16_pipe_kernel<BM, BN, 4, 2, 4, OP_KC, OP_KC, false, 0, 1>), grid, block, 0, s, g, tiles_n, tiles_m * tiles_n, g.K / BK);
+#define MID(EP, POL) hipLaunchKernelGGL((gemm_bf16_pipe_kernel<BM, BN, 4, 2, 4, OP_KC, OP_KC, false, 0, EP, POL>), grid, block, 0, s, g, tiles_n, tiles_m * tiles_n, g.K / BK)
+    const bool wt = g.store_policy == STORE_WT;
+    if (g.relu_src != nullptr || g.colsum_part != nullptr) { if (wt) MID(2, STORE_WT); else MID(2, STORE_PLAIN); }
+    else { if (wt) MID(1, STORE_WT); else MID(1, STORE_PLAIN); }
+#undef MID
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;
 }
@@ -836,6 +853,11 @@ int launch_pipe_mid(const GemmBf16& g, hipStream_t s) {
 int gemm_bf16_pipe_grouped(GemmBf16Group& grp, hipStream_t s) {
     CODAE_REQUIRE(grp.n >= 1 && grp.n <= CODAE_GROUP_MAX, "gemm_bf16_pipe_grouped: %d GEMMs", grp.n);
     int total = 0;
+    // one policy per launch, by everything the launch writes (C3: ten 9.4 MB gradients = 94 MB, more than the L2s hold: plain - the
+    // launch measured the same either way, 33.2-33.3 us per layer plain against 33.4 written through)
+    int64_t out_bytes = 0;
+    for (int j = 0; j < grp.n; ++j) out_bytes += (int64_t)grp.g[j].M * grp.g[j].N * 4;
+    bool all_wt = store_policy_for(out_bytes) == STORE_WT;
     for (int j = 0; j < grp.n; ++j) {
         const GemmBf16& g = grp.g[j];
         CODAE_REQUIRE(g.a_mode == OP_KS && g.b_mode == OP_KS && g.c_f32 && g.split_k == 1 && g.K % BK == 0 && g.K >= BK && g.M % 8 == 0 &&
@@ -846,17 +868,22 @@ int gemm_bf16_pipe_grouped(GemmBf16Group& grp, hipStream_t s) {
                       "gemm_bf16_pipe_grouped: operand larger than 4 GiB");
         CODAE_REQUIRE((reinterpret_cast<uintptr_t>(g.A) & 15) == 0 && (reinterpret_cast<uintptr_t>(g.B) & 15) == 0 &&
                           (reinterpret_cast<uintptr_t>(g.C) & 15) == 0, "gemm_bf16_pipe_grouped: operands must be 16-byte aligned");
+        if (g.store_policy != STORE_WT || g.ldc >= ((int64_t)1 << 20)) all_wt = false;      // (and only if every GEMM asks for it and keeps a tile's span addressable)
         grp.wg_begin[j] = total;
         total += ((g.M + 255) / 256) * ((g.N + 191) / 192);
     }
     grp.wg_begin[grp.n] = total;
-    hipLaunchKernelGGL(gemm_bf16_pipe_grouped_kernel, dim3(total), dim3(512), 0, s, grp);
+    if (all_wt) hipLaunchKernelGGL(gemm_bf16_pipe_grouped_kernel<STORE_WT>, dim3(total), dim3(512), 0, s, grp);
+    else hipLaunchKernelGGL(gemm_bf16_pipe_grouped_kernel<STORE_PLAIN>, dim3(total), dim3(512), 0, s, grp);
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;
 }
 
 // cfg 0: 256 x 192 with 4 waves; cfg 1: 256 x 192 with 8 waves
-int gemm_bf16_pipe(const GemmBf16& g, int cfg, hipStream_t s) {
+int gemm_bf16_pipe(const GemmBf16& g_in, int cfg, hipStream_t s) {
+    GemmBf16 g = g_in;
+    // write-through stores address a tile as {descriptor over its first row, 32-bit byte offset}: 256 rows must stay under 2 GiB
+    if (g.store_policy != STORE_WT || g.ldc >= ((int64_t)1 << 20)) g.store_policy = STORE_PLAIN;
     if (cfg == 7) return launch_pipe_mid(g, s);
     if (g.dbg == 8 && g.loss.enabled) {          // stamped build of the fused-loss kernel (tools/timeline_loss.py)
         const int tiles_m = (g.M + 255) / 256, tiles_n = (g.N + 191) / 192;

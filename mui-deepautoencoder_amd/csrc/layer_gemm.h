@@ -2,7 +2,8 @@
 // launch descriptors, once per role and precision.  Host code only (engine.hip, primitives.hip).  A builder takes what
 // varies between callers (operand pointers, leading dimensions, extents, bias, output kind) and sets what the role fixes:
 // operand modes / strides, which extent is the batch, split_k = 1.  Everything else stays zero for the caller to add
-// (activation, mask source, column sums, prefetch, fused loss, split-K slabs, norm slots).
+// (activation, mask source, column sums, prefetch, fused loss, split-K slabs, norm slots).  The output store policy comes from
+// the output's size (store_policy_for).
 // x [rows][n_in], W [n_out][n_in], y / dy [rows][n_out]; ld*: row strides in elements.
 #pragma once
 #include "codae_common.h"
@@ -18,6 +19,7 @@ inline GemmBf16 fwd_gemm_bf16(const void* x, int64_t ldx, const void* W, int64_t
     g.C = y; g.ldc = ldy; g.c_f32 = y_f32;
     g.M = rows; g.N = n_out; g.K = k;
     g.bias = bias; g.split_k = 1;
+    g.store_policy = store_policy_for((int64_t)rows * n_out * (y_f32 ? 4 : 2));
     return g;
 }
 
@@ -31,6 +33,7 @@ inline GemmBf16 dgrad_gemm_bf16(const void* dy, int64_t lddy, const void* W, int
     g.C = dx; g.ldc = lddx; g.c_f32 = dx_f32;
     g.M = rows; g.N = n_in; g.K = k;
     g.split_k = 1;
+    g.store_policy = store_policy_for((int64_t)rows * n_in * (dx_f32 ? 4 : 2));
     return g;
 }
 
@@ -42,6 +45,7 @@ inline GemmBf16 wgrad_gemm_bf16(const void* dy, int64_t lddy, const void* x, int
     g.C = dW; g.ldc = n_in; g.c_f32 = 1;
     g.M = n_out; g.N = n_in; g.K = rows;
     g.split_k = 1;
+    g.store_policy = store_policy_for((int64_t)n_out * n_in * 4);
     return g;
 }
 

@@ -1,7 +1,7 @@
 """Soak / race check at the full C3 size: N optimizer steps of the fused bf16 step, no host sync inside the loop, several times
 over from the same seeds.  The default step (round 3: one stream, grouped unsplit weight gradients, 1-bit ReLU masks, weights
 touched under the previous epilogue) must end on the SAME BITS every time - parameters, both Adam moments, the loss at every
-50th step - and with the 1-bit masks off (CODAE_NO_RELU_BITS=1); the per-layer two-stream backward (CODAE_NO_DEFER_WGRAD=1) and
+50th step - and with the 1-bit masks off (CODAE_NO_RELU_BITS=1) or any output store policy forced (CODAE_STORE_POLICY) or the loss finish as a launch of its own (CODAE_NO_FOLDED_LOSS_FINISH=1); the per-layer two-stream backward (CODAE_NO_DEFER_WGRAD=1) and
 the single-stream form of it sum the weight gradients in another order (split-K slabs): bit-identical to EACH OTHER, their loss
 curve drifts from the default one like any two bf16 runs whose gradients differ in the last bit (5e-3 bound; measured 2e-3 after 400
 steps, 1e-6 over the first 100).
@@ -22,7 +22,7 @@ table = np.ones((S, io), dtype=np.uint8)
 for s in range(S): table[s, s * E:(s + 1) * E] = 0
 rng = np.random.default_rng(3)
 order = [torch.tensor(rng.permutation(4 * B)[:B], dtype=torch.int32, device=dev) for _ in range(steps)]
-VARS = ("CODAE_SINGLE_STREAM", "CODAE_NO_DEFER_WGRAD", "CODAE_NO_RELU_BITS", "CODAE_NO_PREFETCH")
+VARS = ("CODAE_SINGLE_STREAM", "CODAE_NO_DEFER_WGRAD", "CODAE_NO_RELU_BITS", "CODAE_NO_PREFETCH", "CODAE_STORE_POLICY", "CODAE_NO_FOLDED_LOSS_FINISH")
 
 
 def run(env):
@@ -47,6 +47,8 @@ ok = True
 per_layer = None
 for name, env, exact in (("default again", {}, True), ("default #3", {}, True), ("no 1-bit masks", {"CODAE_NO_RELU_BITS": "1"}, True),
                          ("no prefetch", {"CODAE_NO_PREFETCH": "1"}, True),
+                         ("plain stores", {"CODAE_STORE_POLICY": "plain"}, True), ("sc1 stores", {"CODAE_STORE_POLICY": "wt"}, True),
+                         ("own loss finish", {"CODAE_NO_FOLDED_LOSS_FINISH": "1"}, True),
                          ("per-layer bwd ", {"CODAE_NO_DEFER_WGRAD": "1"}, False), ("single stream ", {"CODAE_NO_DEFER_WGRAD": "1", "CODAE_SINGLE_STREAM": "1"}, False)):
     got = run(env)
     same = got[0] == ref[0] and all(torch.equal(a, b) for a, b in zip(got[1:], ref[1:]))
