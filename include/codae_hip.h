@@ -45,9 +45,10 @@ extern "C" {
  *   7: + codae_topk_init / _merge / _finish, codae_complete_topk (new entries only; no layout change)
  *   8: + CODAE_NOISE_*, codae_noise, codae_set_input_noise, codae_corrupt_batch, codae_noise_box_muller (new entries only; no
  *      layout change of an existing struct, codae_struct_sizes keeps its seven entries)
+ *   9: + codae_debug_gemm_bf16_plan, CODAE_GEMM_PLAN_FIELDS (new entry only; no layout change)
  * The binding must refuse a library whose codae_abi_version() differs and must check its own struct sizes against
  * codae_struct_sizes() at load (mui-deepautoencoder_amd/codae/hip/__init__.py does both). */
-#define CODAE_ABI_VERSION 8
+#define CODAE_ABI_VERSION 9
 
 enum {
     CODAE_OK = 0,
@@ -529,6 +530,20 @@ int codae_dgrad_act_bf16(const void* dy, const void* W, const void* act_src, voi
  * MFMA phase, end of K loop, stores issued, stores retired, XCC id: 6 words each); this copies the first n_wg records to
  * host memory (synchronises the device). */
 int codae_debug_gemm_timeline(uint64_t* host_out, int32_t n_wg);
+/* Host-only query (no HIP call, no device needed): which kernel a bf16 GEMM launch with these descriptor facts takes under the
+ * CODAE_* variables as last read, and the counts the engine derives from that choice.  It pins the dispatch in tests.
+ *   desc[13]: a_mode, b_mode (0 = k contiguous, 1 = k strided), c_f32, M, N, K, split_k, act (CODAE_ACT_*), fused loss on / off,
+ *             backward epilogue (mask source or column sums) yes / no, coscheduled, store_policy (0 plain, 1 write-through,
+ *             -1 by the output's size as the engine sets it), ldc
+ *   out[CODAE_GEMM_PLAN_FIELDS]: family (0 one-barrier kernel, 1 phase-pipelined, 2 its timing-ablation builds), bm, bn, stages
+ *             (one-barrier: 2 / 4), loader layout (pipelined: 1 / 6 = 256 x 192 with every wave / one wave per SIMD loading,
+ *             7 = 128 x 192), epilogue (1 forward, 2 backward, 3 fused loss, 0 decided at run time), phase schedule (0 pinned, 64 the
+ *             compiler's, else the ablation build's number), generic-activation instantiation, effective store policy, tiles_m,
+ *             tiles_n, workgroups, colsum_rows, loss_parts (0 without the fused loss), takes_relu_bits (of an M x N forward-form
+ *             launch)
+ * capacity: room in out, >= CODAE_GEMM_PLAN_FIELDS. */
+#define CODAE_GEMM_PLAN_FIELDS 15
+int codae_debug_gemm_bf16_plan(const int32_t* desc, int32_t* out, int32_t capacity);
 int codae_cast_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream);
 /* dst[c][r] = src[r][c] on bf16 matrices (rows, cols multiples of 8): the kernel that refreshes codae_buffers.shadow_wt
  * after an EXTERNAL parameter update (codae_sync_shadows); codae_step_update writes it inside its Adam pass

@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("CODAE_HIP_LIB") or os.path.join(_HERE, "libcodae_hip.
 PREC_F32 = 0
 PREC_BF16 = 1
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 # CODAE_S_* of include/codae_hip.h (tests/test_host_logic.py parses the header and compares)
 S_SQ_FULL, S_SQ_PARTIAL, S_GRAD_SQ, S_LAST_LOSS, S_STEP_SQ, S_CLIP_COEF = 0, 1, 2, 3, 4, 5
 S_GRAD_SQ_SLOTS, S_N_SLOTS, S_ADAM_STEP, S_COUNT = 8, 64, 72, 80
@@ -137,6 +137,7 @@ PROTOTYPES = {
     "codae_dgrad_act_bf16": (C.c_int, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _F, _F, _F, _P]),
     "codae_cast_f32_to_bf16": (C.c_int, [_P, _P, _I64, _P]),
     "codae_debug_gemm_timeline": (C.c_int, [_P, _I32]),
+    "codae_debug_gemm_bf16_plan": (C.c_int, [_P, _P, _I32]),
     "codae_transpose_bf16": (C.c_int, [_P, _P, _I32, _I32, _P]),
 }
 

@@ -318,12 +318,43 @@ struct GemmBf16 {
                              // tiles; the mask dwords and column-sum rows stay plain).  Other kernels ignore it.
 };
 bool gemm_bf16_supported(int M, int N, int K);
+
+// The workgroup tiles of the GEMM kernels, and how many of one cover an M x N output: the one form of this arithmetic in the host
+// code (the plan below, the split-K choices, the engine's grouped weight-gradient modes, the grouped launchers)
+struct GemmTile { int bm, bn; };
+constexpr GemmTile TILE_256x192{256, 192}, TILE_128x192{128, 192}, TILE_128x128{128, 128}, TILE_64x128{64, 128}, TILE_64x64{64, 64};
+inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+inline int tile_count(int M, int N, GemmTile t) { return ceil_div(M, t.bm) * ceil_div(N, t.bn); }
+
+// What gemm_bf16(g) launches, decided ONCE by gemm_bf16_plan (gemm_bf16.hip): the launchers switch on these fields and
+// nothing else, and whoever must know a launch's tile in advance (the engine's partial-sum row counts, the 1-bit ReLU masks)
+// reads them from the same plan.
+enum { BF16_ONE_BARRIER = 0,      // gemm_bf16_kernel: one-barrier double buffer, or four stages (gemm_bf16.hip)
+       BF16_PIPELINED = 1,        // gemm_bf16_pipe_kernel: phase-pipelined (gemm_bf16_pipe.hip)
+       BF16_PIPELINED_ABL = 2     // its timing-only ablation / stamped builds (CODAE_GEMM_DBG; results wrong by design)
+};
+struct Bf16Plan {
+    int family;              // BF16_*
+    int bm, bn;              // workgroup tile: 64 x 64, 128 x 128 (one-barrier); 128 x 192, 256 x 192 (pipelined)
+    int stages;              // one-barrier: operand stages in LDS, 2 or 4; pipelined: 0
+    int loader;              // pipelined: 1 = 256 x 192, every wave loads (B halves by 6 of the 8); 6 = 256 x 192, LDS-DMA on one wave per
+                             // SIMD; 7 = 128 x 192 (forward form only); one-barrier: 0
+    int epi;                 // 3 = fused loss (either family); pipelined bf16 output: 1 = forward, 2 = data-gradient epilogue; else 0
+    int dbg;                 // pipelined DBG template argument: 0 = pinned phases, 64 = the compiler's schedule (GemmBf16::coscheduled),
+                             // anything else = that ablation build
+    int act;                 // the generic-activation instantiation (one-barrier only)
+    int store_policy;        // STORE_* the launch really stores with: the descriptor's, after the ldc fallback; PLAIN wherever the
+                             // kernel takes no policy
+    int tiles_m, tiles_n;
+    int64_t workgroups;      // tiles_m * tiles_n * split_k = the grid
+};
+Bf16Plan gemm_bf16_plan(const GemmBf16& g);
 bool gemm_bf16_takes_relu_bits(int M, int N);    // forward-form bf16 launch of this output shape runs on a pipelined kernel
-int gemm_bf16_colsum_rows(const GemmBf16& g);   // rows of colsum_part this launch writes (= its tiles along M)
+int gemm_bf16_colsum_rows(const GemmBf16& g);   // rows of colsum_part this launch writes (= its plan's tiles along M)
 int gemm_bf16_loss_parts(const GemmBf16& g);    // workgroups of the fused-loss launch = rows of LossFuse::parts
 int gemm_bf16(const GemmBf16& g, hipStream_t s);
-int gemm_bf16_pipe(const GemmBf16& g, int cfg, hipStream_t s);   // gemm_bf16_pipe.hip
-int choose_split_k(int N, int K, int rows);     // engine.hip: split-K factor of the weight gradient dW[N][K] over `rows` batch rows
+int gemm_bf16_pipe(const GemmBf16& g, const Bf16Plan& plan, hipStream_t s);   // gemm_bf16_pipe.hip: the pipelined families of a plan
+int choose_split_k(int N, int K, int rows);     // gemm_bf16.hip: split-K factor of the weight gradient dW[N][K] over `rows` batch rows
 
 // several independent GEMMs (here: the weight gradients of every layer of a narrow stack) in ONE launch; tile
 // configuration 128 x 128 for all of them

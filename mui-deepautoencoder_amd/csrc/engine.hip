@@ -186,37 +186,6 @@ struct DpState {
     hipEvent_t ev_done = nullptr;                       // every collective of the step complete
 };
 
-namespace codae {
-
-// Split-K factor of the weight-gradient GEMM dW[N][K] = dA^T H over `rows` batch rows: enough
-// K-slices that the output tiles cover the chip once (256 x 192 tiles), or ~2 workgroups per CU
-// with the 128 x 128 tile when the big one cannot fill it.  Must agree with gemm_bf16_tile_big.
-int choose_split_k(int N, int K, int rows) {
-    const int kt = rows / 64;
-    int s;
-    // a batch of <= 256 rows is 1-4 K-tiles: the launch is all epilogue (the fp32 output), which a split multiplies and
-    // follows with a reduce (stock BATCH_SIZE 128 at io 1536: 18.8 + 13 us per layer split in two)
-    if (kt <= 4 && env().wgrad_splitk <= 0) return 1;
-    if (env().wgrad_splitk > 0) {
-        s = env().wgrad_splitk;
-    } else {
-        const int tiles_big = ((N + 255) / 256) * ((K + 191) / 192);
-        s = (256 + tiles_big / 2) / tiles_big;
-        if (s > 8) s = 8;
-        if (s > kt) s = kt;
-        if (s < 1) s = 1;
-        if (tiles_big * s >= 160) return s;
-        const int tiles = ((N + 127) / 128) * ((K + 127) / 128);
-        s = (512 + tiles / 2) / tiles;
-        if (s > 8) s = 8;
-    }
-    if (s > kt) s = kt;
-    if (s < 1) s = 1;
-    return s;
-}
-
-}  // namespace codae
-
 namespace {
 
 // records a start/stop event pair around the launches made while it is alive
@@ -271,14 +240,14 @@ struct GroupScope {
 int choose_split_k_f32(int N, int K, int rows) {
     if (env().wgrad_splitk > 0) return env().wgrad_splitk <= rows / 32 ? env().wgrad_splitk : 1;
     if (rows <= 1024) return 1;
-    const int tiles = ((N + 127) / 128) * ((K + 127) / 128);
+    const int tiles = tile_count(N, K, TILE_128x128);
     if (env().f32_gemm != 1 && N % 4 == 0 && K % 4 == 0) {
         // the bf16-plane kernel (gemm_f32x3.hip) runs ONE workgroup per CU: the split that leaves the last round of 256 fullest
         // (1536 x 1536: 144 tiles x 7 = 1008 of 1024 slots), at least 8 K-tiles per range, the smallest such split on a tie
         int best = 1;
         double best_fill = 0.0;
         for (int s = 1; s <= 8 && s <= rows / 256; ++s) {
-            const int wgs = tiles * s, rounds = (wgs + 255) / 256;
+            const int wgs = tiles * s, rounds = ceil_div(wgs, 256);
             const double fill = (double)wgs / (256.0 * rounds);
             if (fill > best_fill + 0.02) { best_fill = fill; best = s; }
         }
@@ -455,7 +424,7 @@ int defer_wgrad_mode(codae_engine* e, int rows) {
         int total = 0;
         for (int l = 0; l < e->L; ++l) {
             if (e->in[l] % 4 != 0 || e->out[l] % 4 != 0) return 0;
-            total += ((e->out[l] + 127) / 128) * ((e->in[l] + 127) / 128);
+            total += tile_count(e->out[l], e->in[l], TILE_128x128);
         }
         return total >= 256 ? 3 : 0;
     }
@@ -463,8 +432,8 @@ int defer_wgrad_mode(codae_engine* e, int rows) {
         return 0;
     int total = 0, total_small = 0;
     for (int l = 0; l < e->L; ++l) {
-        total += ((e->out[l] + 255) / 256) * ((e->in[l] + 191) / 192);
-        total_small += ((e->out[l] + 63) / 64) * ((e->in[l] + 63) / 64);
+        total += tile_count(e->out[l], e->in[l], TILE_256x192);        // (gemm_bf16_pipe_grouped)
+        total_small += tile_count(e->out[l], e->in[l], TILE_64x64);     // (gemm_bf16_grouped, its smallest tile)
         if ((int64_t)rows * e->out_ld[l] * 2 >= (int64_t)1 << 32 || (int64_t)rows * e->in_ld[l] * 2 >= (int64_t)1 << 32) return 0;
     }
     // (round 3 first kept the per-layer backward when one layer alone fills the chip - C5: 31.2 ms/step against 32.9 grouped; with
@@ -500,7 +469,7 @@ int run_wgrad_deferred(codae_engine* e, const codae_buffers* b, int rows, bool w
 // workgroups into fp32 slabs (slab slot 2: the caller's stream), then the reduce that applies the GEMM's epilogue.  Same
 // fp32 arithmetic in another summation order.  3 x 512 at batch 128, whole parity-mode step: 3.09 -> see DESIGN.md.
 int gemm_f32_small(codae_engine* e, const codae_buffers* b, const GemmF32& g, hipStream_t s) {
-    const int tiles = ((g.M + 127) / 128) * ((g.N + 127) / 128);
+    const int tiles = tile_count(g.M, g.N, TILE_128x128);
     const int kt = (g.K + 31) / 32;
     int S = tiles >= 128 ? 1 : (256 + tiles / 2) / tiles;
     if (S > kt / 4) S = kt / 4;                       // at least 4 K-tiles per range
@@ -921,7 +890,7 @@ int codae_create(const codae_spec* spec, codae_handle* out) {
     {   // + the loss kernels' per-workgroup metric sums: [workgroups][2] doubles
         const int io = e->out[e->L - 1];
         const int by_rows = (e->max_rows + 31) / 32;                                             // stand-alone loss kernel
-        const int by_tiles = ((e->max_rows + 63) / 64) * ((io + 63) / 64);                       // fused into the last GEMM (smallest tile)
+        const int by_tiles = tile_count(e->max_rows, io, TILE_64x64);                          // fused into the last GEMM (smallest tile)
         e->loss_part_cap = by_rows > by_tiles ? by_rows : by_tiles;
         if (e->chain_ok && chain_rows / 16 > e->loss_part_cap) e->loss_part_cap = chain_rows / 16;
         e->loss_part_off = e->part_floats;

@@ -639,50 +639,37 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_grouped_kernel(GemmBf16Group
                                                             grp.wg_begin[j + 1] - grp.wg_begin[j], smem_raw);
 }
 
+// Launches the one-barrier instantiation a plan names: this tile, the descriptor's operand modes and output kind, the plan's
+// stages, activation and fused-loss flags.  With gemm_bf16_pipe (gemm_bf16_pipe.hip) the only code that names template arguments.
 template <int BM, int BN, int WM, int WN>
-int launch_cfg(const GemmBf16& g, hipStream_t s) {
-    const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN;
-    const int kt_total = g.K / BK;
-    const int64_t nwg = (int64_t)tiles_m * tiles_n * g.split_k;
-    CODAE_REQUIRE(nwg < (1 << 30), "gemm_bf16: grid too large");
-    dim3 grid((unsigned)nwg), block(64 * WM * WN);
-    if (g.act != CODAE_ACT_NONE) {
+int launch_cfg(const GemmBf16& g, const Bf16Plan& p, hipStream_t s) {
+    dim3 grid((unsigned)p.workgroups), block(64 * WM * WN);
+#define LAUNCH(AM, BMODE, CF, LOSS, NS, ACT) \
+    hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, AM, BMODE, CF, LOSS, NS, ACT>), grid, block, 0, s, g, p.tiles_n, p.tiles_m * p.tiles_n, g.K / BK)
+    const bool deep = p.stages == 4;
+    if (p.act) {
         // the generic-activation instantiations: forward / data-gradient forms only (gemm_bf16 refused the rest)
-#define LAUNCH_ACT(BMODE, CF, NS) \
-    hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, OP_KC, BMODE, CF, false, NS, true>), grid, block, 0, s, g, tiles_n, tiles_m * tiles_n, kt_total)
-        const bool deep = !g.c_f32 && nwg <= 256 && kt_total >= 6 && !env().no_deep_small && env().small_stages >= 4;
-        if (g.b_mode == OP_KC) {
-            if (g.c_f32) LAUNCH_ACT(OP_KC, true, 2);
-            else if (deep) LAUNCH_ACT(OP_KC, false, 4);
-            else LAUNCH_ACT(OP_KC, false, 2);
-        } else {
-            LAUNCH_ACT(OP_KS, false, 2);
-        }
-#undef LAUNCH_ACT
-        CODAE_LAUNCH_CHECK();
-        return CODAE_OK;
-    }
-#define LAUNCH(AM, BMODE, CF) \
-    hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, AM, BMODE, CF>), grid, block, 0, s, g, tiles_n, tiles_m * tiles_n, kt_total)
-    if (g.loss.enabled) {
-        hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, OP_KC, OP_KC, false, true>), grid, block, 0, s, g, tiles_n,
-                           tiles_m * tiles_n, kt_total);
+        if (g.b_mode == OP_KS) LAUNCH(OP_KC, OP_KS, false, false, 2, true);
+        else if (g.c_f32) LAUNCH(OP_KC, OP_KC, true, false, 2, true);
+        else if (deep) LAUNCH(OP_KC, OP_KC, false, false, 4, true);
+        else LAUNCH(OP_KC, OP_KC, false, false, 2, true);
+    } else if (p.epi == 3) {
+        LAUNCH(OP_KC, OP_KC, false, true, 2, false);
     } else if (g.a_mode == OP_KC && g.b_mode == OP_KC) {
-        // forward / data-gradient form of a launch that cannot fill the chip: four stages (see gemm_bf16_tile)
-        const bool deep = !g.c_f32 && nwg <= 256 && kt_total >= 6 && !env().no_deep_small && env().small_stages >= 4;
-        if (g.c_f32) LAUNCH(OP_KC, OP_KC, true);
-        else if (deep)
-            hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, OP_KC, OP_KC, false, false, 4>), grid, block, 0, s, g, tiles_n,
-                               tiles_m * tiles_n, kt_total);
-        else LAUNCH(OP_KC, OP_KC, false);
+        if (g.c_f32) LAUNCH(OP_KC, OP_KC, true, false, 2, false);
+        else if (deep) LAUNCH(OP_KC, OP_KC, false, false, 4, false);
+        else LAUNCH(OP_KC, OP_KC, false, false, 2, false);
     }
-    else if (g.a_mode == OP_KC && g.b_mode == OP_KS) { if (g.c_f32) LAUNCH(OP_KC, OP_KS, true); else LAUNCH(OP_KC, OP_KS, false); }
-    else if (g.a_mode == OP_KS && g.b_mode == OP_KS) { if (g.c_f32) LAUNCH(OP_KS, OP_KS, true); else LAUNCH(OP_KS, OP_KS, false); }
+    else if (g.a_mode == OP_KC && g.b_mode == OP_KS) { if (g.c_f32) LAUNCH(OP_KC, OP_KS, true, false, 2, false); else LAUNCH(OP_KC, OP_KS, false, false, 2, false); }
+    else if (g.a_mode == OP_KS && g.b_mode == OP_KS) { if (g.c_f32) LAUNCH(OP_KS, OP_KS, true, false, 2, false); else LAUNCH(OP_KS, OP_KS, false, false, 2, false); }
     else { set_error("gemm_bf16: operand mode combination not built"); return CODAE_E_UNSUPPORTED; }
 #undef LAUNCH
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;
 }
+
+// a launch on the 256 x 192 tile must yield this many workgroups to be worth it (see gemm_bf16_plan; choose_split_k aims for it)
+constexpr int BIG_TILE_MIN_WGS = 160;
 
 }  // namespace
 
@@ -690,12 +677,12 @@ int launch_cfg(const GemmBf16& g, hipStream_t s) {
 // 384 x 384 weight gradients: 90 / 180 / 360 workgroups).
 int gemm_bf16_grouped(GemmBf16Group& grp, hipStream_t s) {
     CODAE_REQUIRE(grp.n >= 1 && grp.n <= CODAE_GROUP_MAX, "gemm_bf16_grouped: %d GEMMs", grp.n);
-    auto count = [&](int bm, int bn) {
+    auto count = [&](GemmTile t) {
         int total = 0;
         for (int j = 0; j < grp.n; ++j) {
             const GemmBf16& g = grp.g[j];
             grp.wg_begin[j] = total;
-            total += ((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn) * g.split_k;
+            total += tile_count(g.M, g.N, t) * g.split_k;
         }
         grp.wg_begin[grp.n] = total;
         return total;
@@ -707,10 +694,10 @@ int gemm_bf16_grouped(GemmBf16Group& grp, hipStream_t s) {
                       "gemm_bf16_grouped: GEMM %d is not a plain weight-gradient form", j);
     }
     int tile = env().group_tile;
-    if (tile < 0) tile = count(128, 128) >= 256 ? 0 : (count(64, 128) >= 256 ? 1 : 2);
-    if (tile == 0) { const int total = count(128, 128); hipLaunchKernelGGL((gemm_bf16_grouped_kernel<128, 128>), dim3(total), dim3(256), 0, s, grp); }
-    else if (tile == 1) { const int total = count(64, 128); hipLaunchKernelGGL((gemm_bf16_grouped_kernel<64, 128>), dim3(total), dim3(256), 0, s, grp); }
-    else { const int total = count(64, 64); hipLaunchKernelGGL((gemm_bf16_grouped_kernel<64, 64>), dim3(total), dim3(256), 0, s, grp); }
+    if (tile < 0) tile = count(TILE_128x128) >= 256 ? 0 : (count(TILE_64x128) >= 256 ? 1 : 2);
+    if (tile == 0) { const int total = count(TILE_128x128); hipLaunchKernelGGL((gemm_bf16_grouped_kernel<128, 128>), dim3(total), dim3(256), 0, s, grp); }
+    else if (tile == 1) { const int total = count(TILE_64x128); hipLaunchKernelGGL((gemm_bf16_grouped_kernel<64, 128>), dim3(total), dim3(256), 0, s, grp); }
+    else { const int total = count(TILE_64x64); hipLaunchKernelGGL((gemm_bf16_grouped_kernel<64, 64>), dim3(total), dim3(256), 0, s, grp); }
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;
 }
@@ -727,12 +714,23 @@ bool gemm_bf16_supported(int M, int N, int K) {
     return M > 0 && N >= 8 && K >= BK && (K % BK) == 0 && (N % 8) == 0;
 }
 
-// Tile choice: the 256 x 192 / 8-wave tile when it yields enough workgroups to cover the chip
-// (its operand traffic per flop is 1.7x lower than the 128 x 128 tile's, which is what bounds
-// the small tile: ~39 TB/s of L2 reads at full MFMA rate); else 128 x 128 / 4 waves.
-int gemm_bf16_tile_big(int M, int N, int split_k, bool k_strided = false) {
-    if (env().gemm_tile >= 0) return env().gemm_tile;
-    const int64_t big = (int64_t)((M + 255) / 256) * ((N + 191) / 192) * split_k;
+// What gemm_bf16(g) launches: the ONE place that decides tile, kernel family, stages, loader layout, epilogue and store policy,
+// with the CODAE_GEMM_TILE / CODAE_GEMM_DBG overrides applied here and nowhere else.  gemm_bf16() launches what it says;
+// gemm_bf16_colsum_rows / _loss_parts / _takes_relu_bits read the same answer, so the row and part counts the engine adds up
+// follow the tile by construction, under every switch.
+Bf16Plan gemm_bf16_plan(const GemmBf16& g) {
+    const EnvToggles& e = env();
+    const bool loss = g.loss.enabled != 0;
+    const bool fwd_form = g.a_mode == OP_KC && g.b_mode == OP_KC && !g.c_f32 && g.split_k == 1;     // (the fused loss is one)
+    // generic activations: the one-barrier kernel on 64 x 64 / 128 x 128 tiles only (the pipelined kernels keep their ReLU / identity
+    // epilogues; DESIGN.md section 6, activations), whatever the switches force
+    const bool act = g.act != CODAE_ACT_NONE;
+    const int dbg = act ? 0 : e.gemm_dbg;
+
+    // ---- the big tile: 256 x 192 / 8 waves, phase-pipelined, when it yields enough workgroups to cover the chip (its operand
+    // traffic per flop is 1.7x lower than the 128 x 128 tile's, which is what bounds the small tile: ~39 TB/s of L2 reads at full
+    // MFMA rate).  big: 0 = not this launch, 3 = every wave loads (CODAE_GEMM_TILE=q), 6 = LDS-DMA issued by one wave per SIMD
+    // (default, =x), 7 = forced 128 x 192 (=m).
     // round 1 (tools/bench_gemm.py, 8192 x 1536 x 1536, us): 128 x 128 (s) 46.3 / 59.6 / 68.1 for forward / dgrad through W /
     // wgrad + reduce; one-barrier 256 x 192 (b) 38.4 / 46.4 / 55.1; two 128 x 192 workgroups per CU (c) 40.2 / 44.9 / 55.3;
     // 4-wave pipelined (p) slower than 8-wave (q) 37.0 / 43.3 / 53.9.  b, c and p were pruned in round 2.
@@ -742,66 +740,119 @@ int gemm_bf16_tile_big(int M, int N, int split_k, bool k_strided = false) {
     //   wgrad + slab reduce                                                 50.7  49.3      whole step 1.398 -> 1.362 ms
     // (x = q with every LDS-DMA piece issued by waves 0..3, one per SIMD: the SIMD partner multiplies while its
     // neighbour's issue slots are taken by the VMEM instructions)
-    (void)k_strided;
-    if (big < 160) return 0;
-    return 6;
-}
+    const int big_auto = (int64_t)tile_count(g.M, g.N, TILE_256x192) * g.split_k >= BIG_TILE_MIN_WGS ? 6 : 0;
+    int big = e.gemm_tile >= 0 ? e.gemm_tile : big_auto;
+    // the 128 x 192 instantiation is forward-form only (its k-strided half images would need 96 or 128 columns) and has no fused
+    // loss: forcing it sends the loss layer to the default 256 x 192 loader and leaves every other form to the automatic choice
+    if (big == 7 && loss) big = 6;
+    if (big == 7 && !fwd_form) big = big_auto;
 
-// Forward / data-gradient form (k-contiguous operands, bf16 out) of a launch with at most 200 tiles of 128 x 128 - a small
-// batch of a wide layer, or a narrow layer: 64 x 64 tiles.  One wave per SIMD issues every LDS-DMA piece, fragment read and
-// MFMA of its tile itself, so the time per K-tile is the wave's instruction stream (128 x 128: 8 pieces + 16 reads + 32
-// MFMAs = 0.75 us per K-tile even with hot weights: 17-22 us for 128 x 1536 x 1536); a quarter of the tile per wave and
-// four times the workgroups divide it.  tools/abl/small_tile_sweep.sh, us, 128 x 128 / 64 x 64 tiles: N = K = 1536, M = 256: 21.8 /
-// 9.1; 512: 22.0 / 9.8; 1024: 22.5 / 15.7; 2048 (192 tiles): 23.4 / 18.3; 4096 (384 tiles): 27.7 / 35.5.  N = K = 384, M = 1024:
-// 9.1 / 4.9; 4096: 9.4 / 5.4; 8192 (192 tiles): 9.9 / 7.5.
-static bool small_tile_64(const GemmBf16& g) {
-    if (env().no_deep_small || g.c_f32 || g.a_mode != OP_KC || g.b_mode != OP_KC || g.split_k != 1) return false;
-    return (int64_t)((g.M + 127) / 128) * ((g.N + 127) / 128) <= env().small_tile_max;
-}
+    // ---- the small tile.  Forward / data-gradient form (k-contiguous operands, bf16 out) of a launch with at most 200 tiles of
+    // 128 x 128 - a small batch of a wide layer, or a narrow layer: 64 x 64 tiles.  One wave per SIMD issues every LDS-DMA piece,
+    // fragment read and MFMA of its tile itself, so the time per K-tile is the wave's instruction stream (128 x 128: 8 pieces + 16
+    // reads + 32 MFMAs = 0.75 us per K-tile even with hot weights: 17-22 us for 128 x 1536 x 1536); a quarter of the tile per wave and
+    // four times the workgroups divide it.  tools/abl/small_tile_sweep.sh, us, 128 x 128 / 64 x 64 tiles: N = K = 1536, M = 256: 21.8 /
+    // 9.1; 512: 22.0 / 9.8; 1024: 22.5 / 15.7; 2048 (192 tiles): 23.4 / 18.3; 4096 (384 tiles): 27.7 / 35.5.  N = K = 384, M = 1024:
+    // 9.1 / 4.9; 4096: 9.4 / 5.4; 8192 (192 tiles): 9.9 / 7.5.
+    const bool small64 = !e.no_deep_small && fwd_form && tile_count(g.M, g.N, TILE_128x128) <= e.small_tile_max;
 
-// Which kernel a (non-loss) launch takes: the ONE place that decides, used by gemm_bf16() itself and by whoever has to know in
-// advance (gemm_bf16_takes_relu_bits).  > 0: the pipelined kernel with that cfg (1 / 6: 256 x 192, 7: 128 x 192);
-// -64 / -128: the one-barrier kernel on 64 x 64 / 128 x 128 tiles.
-static int bf16_path(const GemmBf16& g) {
-    const int t = gemm_bf16_tile_big(g.M, g.N, g.split_k, g.b_mode == OP_KS || g.c_f32);
-    switch (t) {
-        case 3: return 1;               // 256 x 192, 8 waves, phase-pipelined, every wave loads
-        case 6: return 6;               // 256 x 192, 8 waves, LDS-DMA issued by one wave per SIMD (default)
-        case 7: return 7;               // (forced: 128 x 192 pipelined, forward form only)
-        default:                        // small problems: one-barrier double buffer
-            if (small_tile_64(g)) return -64;
-            // between the 64 x 64 tiles and the 256 x 192 tile, forward / data-gradient form: the pipelined kernel on 128 x 192
-            // tiles (tools/bench_gemm_fwd.py, us, 128 x 128 one-barrier / 128 x 192 pipelined: 4096 x 1536 x 1536 28.3 / 21.9,
-            // 3000 x 1536 x 1536 26.4 / 19.8, 8192 x 768 x 768 17.9 / 14.6; same bits)
-            if (g.a_mode == OP_KC && g.b_mode == OP_KC && !g.c_f32 && g.split_k == 1 && !env().no_deep_small) return 7;
-            return -128;
+    Bf16Plan p{};
+    GemmTile tile;
+    if (dbg) {
+        // CODAE_GEMM_DBG: every launch without an activation on 256 x 192 tiles - the forward form on the ablation build of that
+        // number, the fused loss on its stamped build (8; tools/timeline_loss.py), anything else on the plain kernel, every wave loading
+        const bool abl_built = (dbg >= 1 && dbg <= 10) || dbg == 16 || dbg == 32;     // (9 / 10: stamps + no LDS-DMA / no MFMA; 16 / 32: no LDS-DMA of A / B)
+        tile = TILE_256x192;
+        if (loss && dbg == 8) { p.family = BF16_PIPELINED_ABL; p.loader = 1; p.dbg = 8; }
+        else if (!loss && fwd_form && abl_built) { p.family = BF16_PIPELINED_ABL; p.loader = 6; p.dbg = dbg; }
+        else { p.family = BF16_PIPELINED; p.loader = 1; }
+    } else if (!act && (big == 3 || big == 6)) {
+        tile = TILE_256x192; p.family = BF16_PIPELINED; p.loader = big == 3 ? 1 : 6;
+    } else if (!act && big == 7) {
+        tile = TILE_128x192; p.family = BF16_PIPELINED; p.loader = 7;
+    } else if (small64) {
+        tile = TILE_64x64; p.family = BF16_ONE_BARRIER;
+    } else if (!act && !loss && fwd_form && !e.no_deep_small) {
+        // between the 64 x 64 tiles and the 256 x 192 tile, forward / data-gradient form: the pipelined kernel on 128 x 192 tiles,
+        // 8 waves of 32 x 96 - 4096 x 1536 is 256 of these, one per CU (tools/bench_gemm_fwd.py, us, 128 x 128 one-barrier / 128 x 192
+        // pipelined: 4096 x 1536 x 1536 28.3 / 21.9, 3000 x 1536 x 1536 26.4 / 19.8, 8192 x 768 x 768 17.9 / 14.6; same bits)
+        tile = TILE_128x192; p.family = BF16_PIPELINED; p.loader = 7;
+    } else {
+        tile = TILE_128x128; p.family = BF16_ONE_BARRIER;        // small problems: one-barrier double buffer
     }
+    p.bm = tile.bm; p.bn = tile.bn;
+    p.tiles_m = ceil_div(g.M, tile.bm); p.tiles_n = ceil_div(g.N, tile.bn);
+    p.workgroups = (int64_t)p.tiles_m * p.tiles_n * g.split_k;
+
+    if (p.family == BF16_ONE_BARRIER) {
+        // forward / data-gradient form of a launch that cannot fill the chip: four stages (see gemm_bf16_tile)
+        const bool deep = g.a_mode == OP_KC && g.b_mode == OP_KC && !g.c_f32 && !loss && p.workgroups <= 256 && g.K / BK >= 6 &&
+                          !e.no_deep_small && e.small_stages >= 4;
+        p.stages = deep ? 4 : 2;
+        p.act = act;
+        p.epi = loss ? 3 : 0;
+        p.store_policy = STORE_PLAIN;           // (these kernels take no policy)
+        return p;
+    }
+    const bool bwd_epi = g.relu_src != nullptr || g.colsum_part != nullptr;
+    // write-through stores address a tile as {descriptor over its first row, 32-bit byte offset}: 256 rows must stay under 2 GiB
+    const int policy = (g.store_policy == STORE_WT && g.ldc < ((int64_t)1 << 20)) ? STORE_WT : STORE_PLAIN;
+    if (p.family == BF16_PIPELINED_ABL) {
+        p.epi = loss ? 3 : 0;
+        p.store_policy = (!loss && dbg == 8) ? policy : STORE_PLAIN;     // (the stamped build follows the launch's store policy: tools/timeline_gemm.py)
+        return p;
+    }
+    p.epi = loss ? 3 : (g.c_f32 ? 0 : (bwd_epi ? 2 : 1));
+    p.store_policy = policy;
+    // the data gradient beside another stream's weight gradients: the same kernel with the compiler's schedule
+    // (GemmBf16::coscheduled), built for the 256 x 192 tile with plain stores
+    if (g.coscheduled && p.epi == 2 && p.loader != 7 && g.a_mode == OP_KC && g.b_mode == OP_KC) { p.dbg = 64; p.store_policy = STORE_PLAIN; }
+    return p;
 }
 
 // a forward-form (k-contiguous operands, bf16 out, unsplit) launch with this output shape goes to a pipelined kernel (256 x 192 or
-// 128 x 192 tiles), whose epilogues write / read the 1-bit ReLU mask
+// 128 x 192 tiles), whose epilogues write / read the 1-bit ReLU mask: the forward and the data-gradient launch ask the same plan
 bool gemm_bf16_takes_relu_bits(int M, int N) {
-    if (env().gemm_dbg) return false;
     GemmBf16 probe{};
     probe.M = M; probe.N = N; probe.a_mode = OP_KC; probe.b_mode = OP_KC; probe.c_f32 = 0; probe.split_k = 1;
-    return bf16_path(probe) > 0;
+    return gemm_bf16_plan(probe).family == BF16_PIPELINED;
 }
 
-// rows of g.colsum_part the launch gemm_bf16(g) makes will write: one per tile along M of the tile it picks
-int gemm_bf16_colsum_rows(const GemmBf16& g) {
-    const int t = gemm_bf16_tile_big(g.M, g.N, g.loss.enabled ? 1 : g.split_k, g.b_mode == OP_KS || g.c_f32);
-    const int bm = (t && g.act == CODAE_ACT_NONE) ? 256 : (small_tile_64(g) ? 64 : 128);   // (activations: the one-barrier tiles)
-    return (g.M + bm - 1) / bm;
-}
+int gemm_bf16_colsum_rows(const GemmBf16& g) { return gemm_bf16_plan(g).tiles_m; }
 
 int gemm_bf16_loss_parts(const GemmBf16& g) {
-    const int t = gemm_bf16_tile_big(g.M, g.N, 1);
-    const int sm = small_tile_64(g) ? 64 : 128;
-    const int bm = t ? 256 : sm, bn = t ? 192 : sm;
-    return ((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn);
+    const Bf16Plan p = gemm_bf16_plan(g);
+    return p.tiles_m * p.tiles_n;
 }
 
-int gemm_bf16(const GemmBf16& g, hipStream_t s) {
+// Split-K factor of the weight-gradient GEMM dW[N][K] = dA^T H over `rows` batch rows: enough
+// K-slices that the output tiles cover the chip once (256 x 192 tiles), or ~2 workgroups per CU
+// with the 128 x 128 tile when the big one cannot fill it.
+int choose_split_k(int N, int K, int rows) {
+    const int kt = rows / 64;
+    int s;
+    // a batch of <= 256 rows is 1-4 K-tiles: the launch is all epilogue (the fp32 output), which a split multiplies and
+    // follows with a reduce (stock BATCH_SIZE 128 at io 1536: 18.8 + 13 us per layer split in two)
+    if (kt <= 4 && env().wgrad_splitk <= 0) return 1;
+    if (env().wgrad_splitk > 0) {
+        s = env().wgrad_splitk;
+    } else {
+        const int tiles_big = tile_count(N, K, TILE_256x192);
+        s = (256 + tiles_big / 2) / tiles_big;
+        if (s > 8) s = 8;
+        if (s > kt) s = kt;
+        if (s < 1) s = 1;
+        if (tiles_big * s >= BIG_TILE_MIN_WGS) return s;
+        const int tiles = tile_count(N, K, TILE_128x128);
+        s = (512 + tiles / 2) / tiles;
+        if (s > 8) s = 8;
+    }
+    if (s > kt) s = kt;
+    if (s < 1) s = 1;
+    return s;
+}
+
+static int validate(const GemmBf16& g) {
     CODAE_REQUIRE(gemm_bf16_supported(g.M, g.N, g.K), "gemm_bf16: unsupported shape M=%d N=%d K=%d (need K %% 64 == 0, N %% 8 == 0)",
                   g.M, g.N, g.K);
     CODAE_REQUIRE(g.a_mode == OP_KC || g.M % 8 == 0, "gemm_bf16: k-strided A needs M %% 8 == 0");
@@ -828,20 +879,15 @@ int gemm_bf16(const GemmBf16& g, hipStream_t s) {
                       "gemm_bf16: mask table must be 8-byte aligned");
         CODAE_REQUIRE((reinterpret_cast<uintptr_t>(g.loss.data) & 15) == 0, "gemm_bf16: dataset must be 16-byte aligned");
     }
-    if (env().gemm_dbg && g.act == CODAE_ACT_NONE) { GemmBf16 g2 = g; g2.dbg = env().gemm_dbg; return gemm_bf16_pipe(g2, 0, s); }
-    if (g.loss.enabled) {
-        const int t = gemm_bf16_tile_big(g.M, g.N, 1);
-        if (t) return gemm_bf16_pipe(g, t >= 6 ? 6 : 1, s);       // 8-wave pipelined kernel, loss from the accumulators
-        if (small_tile_64(g)) return launch_cfg<64, 64, 2, 2>(g, s);
-        return launch_cfg<128, 128, 2, 2>(g, s);
-    }
-    // generic activations: the one-barrier kernel on 64 x 64 / 128 x 128 tiles only (the pipelined kernels keep their ReLU / identity
-    // epilogues; DESIGN.md section 6, activations)
-    if (g.act != CODAE_ACT_NONE) return small_tile_64(g) ? launch_cfg<64, 64, 2, 2>(g, s) : launch_cfg<128, 128, 2, 2>(g, s);
-    const int path = bf16_path(g);
-    if (path > 0) return gemm_bf16_pipe(g, path, s);
-    if (path == -64) return launch_cfg<64, 64, 2, 2>(g, s);
-    return launch_cfg<128, 128, 2, 2>(g, s);
+    return CODAE_OK;
+}
+
+int gemm_bf16(const GemmBf16& g, hipStream_t s) {
+    if (int rc = validate(g)) return rc;
+    const Bf16Plan plan = gemm_bf16_plan(g);
+    CODAE_REQUIRE(plan.workgroups < (1 << 30), "gemm_bf16: grid too large");
+    if (plan.family != BF16_ONE_BARRIER) return gemm_bf16_pipe(g, plan, s);
+    return plan.bm == 64 ? launch_cfg<64, 64, 2, 2>(g, plan, s) : launch_cfg<128, 128, 2, 2>(g, plan, s);
 }
 
 #if defined(CODAE_DBG_5D) && (CODAE_DBG_5D & 2)

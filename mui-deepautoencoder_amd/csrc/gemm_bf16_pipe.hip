@@ -774,80 +774,51 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pipe_grouped_kernel(GemmBf16
     gemm_bf16_pipe_tile<BM, BN, 4, 2, 4, OP_KS, OP_KS, true, 0, 0, POL>(g, tiles_n, tiles_m * tiles_n, g.K / BK, t - grp.wg_begin[j], 0, smem_raw);
 }
 
-template <int BM, int BN, int WM, int WN, int NLB>
-int launch_pipe(const GemmBf16& g, hipStream_t s) {
-    const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN;
-    const int kt_total = g.K / BK;
-    const int64_t nwg = (int64_t)tiles_m * tiles_n * g.split_k;
-    CODAE_REQUIRE(nwg < (1 << 30), "gemm_bf16: grid too large");
-    // LDS-DMA sources are addressed as {scalar base, 32-bit lane offset}
-    CODAE_REQUIRE((int64_t)(g.a_mode == OP_KC ? g.M : g.K) * g.lda * 2 < (int64_t)1 << 32 &&
-                      (int64_t)(g.b_mode == OP_KC ? g.N : g.K) * g.ldb * 2 < (int64_t)1 << 32,
-                  "gemm_bf16: operand larger than 4 GiB");
-    dim3 grid((unsigned)nwg), block(64 * WM * WN);
-#define LAUNCH_POL(AM, BMODE, CF, EP, POL) \
-    hipLaunchKernelGGL((gemm_bf16_pipe_kernel<BM, BN, WM, WN, NLB, AM, BMODE, CF, 0, EP, POL>), grid, block, 0, s, g, tiles_n, tiles_m * tiles_n, kt_total)
+// The launchers below take a plan (gemm_bf16_plan) and decide nothing: they map its fields, and the descriptor's operand modes and
+// output kind, to the instantiation.  p.workgroups is the grid.
+#define PIPE_LAUNCH(BM, BN, NLB, AM, BMODE, CF, DBG, EP, POL)                                                                    \
+    hipLaunchKernelGGL((gemm_bf16_pipe_kernel<BM, BN, 4, 2, NLB, AM, BMODE, CF, DBG, EP, POL>), dim3((unsigned)p.workgroups), dim3(512), 0, s, g, \
+                       p.tiles_n, p.tiles_m * p.tiles_n, g.K / BK)
+
+// 256 x 192, 8 waves (64 x 96 per wave); NLB 6: B halves by 6 loader waves; NLB 4 (CODAE_GEMM_TILE=x, the default): all LDS-DMA
+// pieces on waves 0..3 (one per SIMD), their SIMD partners 4..7 only multiply
+template <int NLB>
+int launch_pipe(const GemmBf16& g, const Bf16Plan& p, hipStream_t s) {
+    constexpr int BM = 256, BN = 192;
 #define LAUNCH(AM, BMODE, CF, EP) \
-    do { if (g.store_policy == STORE_WT) LAUNCH_POL(AM, BMODE, CF, EP, STORE_WT); else LAUNCH_POL(AM, BMODE, CF, EP, STORE_PLAIN); } while (0)
-#define LAUNCH_BF16(AM, BMODE) do { if (bwd_epi) LAUNCH(AM, BMODE, false, 2); else LAUNCH(AM, BMODE, false, 1); } while (0)
-    const bool bwd_epi = g.relu_src != nullptr || g.colsum_part != nullptr;
-    // (the data gradient beside another stream's weight gradients: the same kernel with the compiler's schedule, GemmBf16::coscheduled)
-    if (g.coscheduled && bwd_epi && !g.loss.enabled && g.a_mode == OP_KC && g.b_mode == OP_KC && !g.c_f32) {
-        hipLaunchKernelGGL((gemm_bf16_pipe_kernel<BM, BN, WM, WN, NLB, OP_KC, OP_KC, false, 64, 2>), grid, block, 0, s, g, tiles_n, tiles_m * tiles_n, kt_total);
-        CODAE_LAUNCH_CHECK();
-        return CODAE_OK;
-    }
-    if (g.loss.enabled) {
-        if constexpr (WM * WN == 8) LAUNCH(OP_KC, OP_KC, false, 3);
-        else { set_error("gemm_bf16: fused loss is built for the 8-wave pipelined tile only"); return CODAE_E_UNSUPPORTED; }
-    } else if (g.a_mode == OP_KC && g.b_mode == OP_KC) { if (g.c_f32) LAUNCH(OP_KC, OP_KC, true, 0); else LAUNCH_BF16(OP_KC, OP_KC); }
+    do { if (p.store_policy == STORE_WT) PIPE_LAUNCH(BM, BN, NLB, AM, BMODE, CF, 0, EP, STORE_WT); else PIPE_LAUNCH(BM, BN, NLB, AM, BMODE, CF, 0, EP, STORE_PLAIN); } while (0)
+#define LAUNCH_BF16(AM, BMODE) do { if (p.epi == 2) LAUNCH(AM, BMODE, false, 2); else LAUNCH(AM, BMODE, false, 1); } while (0)
+    if (p.dbg == 64) PIPE_LAUNCH(BM, BN, NLB, OP_KC, OP_KC, false, 64, 2, STORE_PLAIN);      // the compiler's schedule (GemmBf16::coscheduled)
+    else if (p.epi == 3) LAUNCH(OP_KC, OP_KC, false, 3);
+    else if (g.a_mode == OP_KC && g.b_mode == OP_KC) { if (g.c_f32) LAUNCH(OP_KC, OP_KC, true, 0); else LAUNCH_BF16(OP_KC, OP_KC); }
     else if (g.a_mode == OP_KC && g.b_mode == OP_KS) { if (g.c_f32) LAUNCH(OP_KC, OP_KS, true, 0); else LAUNCH_BF16(OP_KC, OP_KS); }
     else if (g.a_mode == OP_KS && g.b_mode == OP_KS) { if (g.c_f32) LAUNCH(OP_KS, OP_KS, true, 0); else LAUNCH_BF16(OP_KS, OP_KS); }
     else { set_error("gemm_bf16: operand mode combination not built"); return CODAE_E_UNSUPPORTED; }
 #undef LAUNCH_BF16
 #undef LAUNCH
-#undef LAUNCH_POL
+    CODAE_LAUNCH_CHECK();
+    return CODAE_OK;
+}
+
+// timing-only ablation builds of the forward form (KC x KC, bf16 out), 256 x 192
+template <int DBG>
+int launch_dbg(const GemmBf16& g, const Bf16Plan& p, hipStream_t s) {
+    if (DBG == 8 && p.store_policy == STORE_WT) PIPE_LAUNCH(256, 192, 4, OP_KC, OP_KC, false, 8, 0, STORE_WT);
+    else PIPE_LAUNCH(256, 192, 4, OP_KC, OP_KC, false, DBG, 0, STORE_PLAIN);
+    CODAE_LAUNCH_CHECK();
+    return CODAE_OK;
+}
+
+// 128 x 192, 8 waves of 32 x 96 (forward / data-gradient form only: the k-strided half images need 96 or 128 columns)
+int launch_pipe_mid(const GemmBf16& g, const Bf16Plan& p, hipStream_t s) {
+    const bool wt = p.store_policy == STORE_WT;
+    if (p.epi == 2) { if (wt) PIPE_LAUNCH(128, 192, 4, OP_KC, OP_KC, false, 0, 2, STORE_WT); else PIPE_LAUNCH(128, 192, 4, OP_KC, OP_KC, false, 0, 2, STORE_PLAIN); }
+    else { if (wt) PIPE_LAUNCH(128, 192, 4, OP_KC, OP_KC, false, 0, 1, STORE_WT); else PIPE_LAUNCH(128, 192, 4, OP_KC, OP_KC, false, 0, 1, STORE_PLAIN); }
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;
 }
 
 }  // namespace
-
-// timing-only ablation builds of the forward form (KC x KC, bf16 out), 256 x 192
-template <int DBG>
-int launch_dbg(const GemmBf16& g, hipStream_t s) {
-    constexpr int BM = 256, BN = 192;
-    const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN;
-    if constexpr (DBG == 8) {          // (the stamped build follows the launch's store policy: tools/timeline_gemm.py)
-        if (g.store_policy == STORE_WT) {
-            hipLaunchKernelGGL((gemm_bf16_pipe_kernel<BM, BN, 4, 2, 4, OP_KC, OP_KC, false, 8, 0, STORE_WT>), dim3(tiles_m * tiles_n), dim3(512), 0, s, g,
-                               tiles_n, tiles_m * tiles_n, g.K / BK);
-            CODAE_LAUNCH_CHECK();
-            return CODAE_OK;
-        }
-    }
-    hipLaunchKernelGGL((gemm_bf16_pipe_kernel<BM, BN, 4, 2, 4, OP_KC, OP_KC, false, DBG>), dim3(tiles_m * tiles_n), dim3(512), 0, s, g,
-                       tiles_n, tiles_m * tiles_n, g.K / BK);
-    CODAE_LAUNCH_CHECK();
-    return CODAE_OK;
-}
-
-// 128 x 192, 8 waves of 32 x 96 (forward / data-gradient form only: the k-strided half images need 96 or 128 columns):
-// for launches between the 64 x 64 tiles and the 256 x 192 tile - 4096 x 1536 is 256 of these, one per CU
-int launch_pipe_mid(const GemmBf16& g, hipStream_t s) {
-    constexpr int BM = 128, BN = 192;
-    const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN;
-    CODAE_REQUIRE(g.a_mode == OP_KC && g.b_mode == OP_KC && !g.c_f32 && !g.loss.enabled && g.split_k == 1, "gemm_bf16: 128 x 192 tile is forward-form only");
-    CODAE_REQUIRE((int64_t)g.M * g.lda * 2 < (int64_t)1 << 32 && (int64_t)g.N * g.ldb * 2 < (int64_t)1 << 32, "gemm_bf16: operand larger than 4 GiB");
-    dim3 grid((unsigned)(tiles_m * tiles_n)), block(512);
-#define MID(EP, POL) hipLaunchKernelGGL((gemm_bf16_pipe_kernel<BM, BN, 4, 2, 4, OP_KC, OP_KC, false, 0, EP, POL>), grid, block, 0, s, g, tiles_n, tiles_m * tiles_n, g.K / BK)
-    const bool wt = g.store_policy == STORE_WT;
-    if (g.relu_src != nullptr || g.colsum_part != nullptr) { if (wt) MID(2, STORE_WT); else MID(2, STORE_PLAIN); }
-    else { if (wt) MID(1, STORE_WT); else MID(1, STORE_PLAIN); }
-#undef MID
-    CODAE_LAUNCH_CHECK();
-    return CODAE_OK;
-}
 
 // all weight gradients of a step in one launch (see gemm_bf16_pipe_grouped_kernel); fills grp.wg_begin
 int gemm_bf16_pipe_grouped(GemmBf16Group& grp, hipStream_t s) {
@@ -870,7 +841,7 @@ int gemm_bf16_pipe_grouped(GemmBf16Group& grp, hipStream_t s) {
                           (reinterpret_cast<uintptr_t>(g.C) & 15) == 0, "gemm_bf16_pipe_grouped: operands must be 16-byte aligned");
         if (g.store_policy != STORE_WT || g.ldc >= ((int64_t)1 << 20)) all_wt = false;      // (and only if every GEMM asks for it and keeps a tile's span addressable)
         grp.wg_begin[j] = total;
-        total += ((g.M + 255) / 256) * ((g.N + 191) / 192);
+        total += tile_count(g.M, g.N, TILE_256x192);
     }
     grp.wg_begin[grp.n] = total;
     if (all_wt) hipLaunchKernelGGL(gemm_bf16_pipe_grouped_kernel<STORE_WT>, dim3(total), dim3(512), 0, s, grp);
@@ -879,40 +850,41 @@ int gemm_bf16_pipe_grouped(GemmBf16Group& grp, hipStream_t s) {
     return CODAE_OK;
 }
 
-// cfg 0: 256 x 192 with 4 waves; cfg 1: 256 x 192 with 8 waves
-int gemm_bf16_pipe(const GemmBf16& g_in, int cfg, hipStream_t s) {
+// the pipelined families of a plan (BF16_PIPELINED, BF16_PIPELINED_ABL)
+int gemm_bf16_pipe(const GemmBf16& g_in, const Bf16Plan& p, hipStream_t s) {
+    // LDS-DMA sources are addressed as {scalar base, 32-bit lane offset}
+    CODAE_REQUIRE((int64_t)(g_in.a_mode == OP_KC ? g_in.M : g_in.K) * g_in.lda * 2 < (int64_t)1 << 32 &&
+                      (int64_t)(g_in.b_mode == OP_KC ? g_in.N : g_in.K) * g_in.ldb * 2 < (int64_t)1 << 32,
+                  "gemm_bf16: operand larger than 4 GiB");
     GemmBf16 g = g_in;
-    // write-through stores address a tile as {descriptor over its first row, 32-bit byte offset}: 256 rows must stay under 2 GiB
-    if (g.store_policy != STORE_WT || g.ldc >= ((int64_t)1 << 20)) g.store_policy = STORE_PLAIN;
-    if (cfg == 7) return launch_pipe_mid(g, s);
-    if (g.dbg == 8 && g.loss.enabled) {          // stamped build of the fused-loss kernel (tools/timeline_loss.py)
-        const int tiles_m = (g.M + 255) / 256, tiles_n = (g.N + 191) / 192;
-        hipLaunchKernelGGL((gemm_bf16_pipe_kernel<256, 192, 4, 2, 6, OP_KC, OP_KC, false, 8, 3>), dim3(tiles_m * tiles_n), dim3(512), 0, s, g,
-                           tiles_n, tiles_m * tiles_n, g.K / BK);
-        CODAE_LAUNCH_CHECK();
-        return CODAE_OK;
-    }
-    if (g.dbg && !g.loss.enabled && g.a_mode == OP_KC && g.b_mode == OP_KC && !g.c_f32 && g.split_k == 1) {
-        switch (g.dbg) {
-            case 1: return launch_dbg<1>(g, s);
-            case 2: return launch_dbg<2>(g, s);
-            case 3: return launch_dbg<3>(g, s);
-            case 4: return launch_dbg<4>(g, s);
-            case 5: return launch_dbg<5>(g, s);
-            case 6: return launch_dbg<6>(g, s);
-            case 7: return launch_dbg<7>(g, s);
-            case 8: return launch_dbg<8>(g, s);
-            case 9: return launch_dbg<9>(g, s);      // stamps + no LDS-DMA
-            case 10: return launch_dbg<10>(g, s);    // stamps + no MFMA
-            case 16: return launch_dbg<16>(g, s);    // no LDS-DMA of the A operand
-            case 32: return launch_dbg<32>(g, s);    // no LDS-DMA of the B operand
-            default: break;
+    g.store_policy = p.store_policy;
+    if (p.family == BF16_PIPELINED_ABL) {
+        g.dbg = p.dbg;
+        if (p.epi == 3) {          // stamped build of the fused-loss kernel (tools/timeline_loss.py)
+            PIPE_LAUNCH(256, 192, 6, OP_KC, OP_KC, false, 8, 3, STORE_PLAIN);
+            CODAE_LAUNCH_CHECK();
+            return CODAE_OK;
+        }
+        switch (p.dbg) {
+            case 1: return launch_dbg<1>(g, p, s);
+            case 2: return launch_dbg<2>(g, p, s);
+            case 3: return launch_dbg<3>(g, p, s);
+            case 4: return launch_dbg<4>(g, p, s);
+            case 5: return launch_dbg<5>(g, p, s);
+            case 6: return launch_dbg<6>(g, p, s);
+            case 7: return launch_dbg<7>(g, p, s);
+            case 8: return launch_dbg<8>(g, p, s);
+            case 9: return launch_dbg<9>(g, p, s);      // stamps + no LDS-DMA
+            case 10: return launch_dbg<10>(g, p, s);    // stamps + no MFMA
+            case 16: return launch_dbg<16>(g, p, s);    // no LDS-DMA of the A operand
+            case 32: return launch_dbg<32>(g, p, s);    // no LDS-DMA of the B operand
+            default: set_error("gemm_bf16: ablation build %d is not instantiated", p.dbg); return CODAE_E_UNSUPPORTED;
         }
     }
-    // CODAE_GEMM_TILE=x: all LDS-DMA pieces on waves 0..3 (one per SIMD), their SIMD partners 4..7 only multiply
-    if (cfg == 6) return launch_pipe<256, 192, 4, 2, 4>(g, s);
-    return launch_pipe<256, 192, 4, 2, 6>(g, s);                 // 8 waves (64 x 96 per wave), B halves by 6 loader waves
+    if (p.loader == 7) return launch_pipe_mid(g, p, s);
+    return p.loader == 6 ? launch_pipe<4>(g, p, s) : launch_pipe<6>(g, p, s);
 }
+#undef PIPE_LAUNCH
 
 // copies the DBG = 8 stamps of the first n_wg workgroups (TIMELINE_SLOTS words each) to the host
 int gemm_bf16_timeline(unsigned long long* host_out, int n_wg) {

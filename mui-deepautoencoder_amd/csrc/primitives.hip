@@ -169,6 +169,24 @@ int codae_wgrad_bf16(const void* dy, const void* x, float* dW, void* slabs, int6
     return CODAE_OK;
 }
 
+// what gemm_bf16() would launch for a descriptor with these facts: the plan, and the counts the engine derives from it
+int codae_debug_gemm_bf16_plan(const int32_t* desc, int32_t* out, int32_t capacity) {
+    CODAE_REQUIRE(desc && out && capacity >= CODAE_GEMM_PLAN_FIELDS, "codae_debug_gemm_bf16_plan: needs room for %d fields", CODAE_GEMM_PLAN_FIELDS);
+    GemmBf16 g{};
+    g.a_mode = desc[0]; g.b_mode = desc[1]; g.c_f32 = desc[2]; g.M = desc[3]; g.N = desc[4]; g.K = desc[5]; g.split_k = desc[6];
+    g.act = desc[7]; g.loss.enabled = desc[8]; g.coscheduled = desc[10]; g.store_policy = desc[11]; g.ldc = desc[12];
+    if (desc[11] < 0) g.store_policy = store_policy_for((int64_t)g.M * g.N * (g.c_f32 ? 4 : 2));      // (as the descriptor builders of layer_gemm.h)
+    static float some_rows;
+    if (desc[9]) g.colsum_part = &some_rows;          // (the plan only asks whether there is a backward epilogue; nothing is launched)
+    CODAE_REQUIRE(gemm_bf16_supported(g.M, g.N, g.K) && g.split_k >= 1, "codae_debug_gemm_bf16_plan: unsupported shape M=%d N=%d K=%d", g.M, g.N, g.K);
+    const Bf16Plan p = gemm_bf16_plan(g);
+    const int32_t fields[CODAE_GEMM_PLAN_FIELDS] = {p.family, p.bm, p.bn, p.stages, p.loader, p.epi, p.dbg, p.act, p.store_policy, p.tiles_m, p.tiles_n,
+                                                    (int32_t)p.workgroups, gemm_bf16_colsum_rows(g), g.loss.enabled ? gemm_bf16_loss_parts(g) : 0,
+                                                    gemm_bf16_takes_relu_bits(g.M, g.N) ? 1 : 0};
+    for (int i = 0; i < CODAE_GEMM_PLAN_FIELDS; ++i) out[i] = fields[i];
+    return CODAE_OK;
+}
+
 int codae_debug_gemm_timeline(uint64_t* host_out, int32_t n_wg) {
     return gemm_bf16_timeline(reinterpret_cast<unsigned long long*>(host_out), n_wg);
 }
