@@ -164,7 +164,24 @@ typedef struct {
     int32_t n_scalars;      /* doubles in the scalar block (CODAE_S_*) */
 } codae_sizes;
 
-/* Borrowed device buffers. */
+/* Borrowed device buffers.
+ * Buffer contents.  The library allocates nothing and zeroes nothing at first use, so the caller hands the buffers over in this
+ * state (tests/test_gpu_history.py poisons every byte that is NOT listed and compares the results bit for bit).
+ * Before the first call these borrowed bytes must be ZERO:
+ *   (1) params, grads, adam_m and adam_v outside the weight and bias tensors (the padding that rounds every tensor up to 64
+ *       floats): the norm and Adam kernels sweep the whole flat vectors, and the padding stays zero under them (g = 0, p = 0);
+ *   (2) all of scalars: the metric sums accumulate across calls until the caller zeroes them, the rest is scratch the step
+ *       clears itself on its way;
+ *   (3) only when a layer width is not a multiple of 64: all of acts and dacts (the pad columns between a row's width and its
+ *       64-element stride are never written and are multiplied with whatever follows a weight row) and the 64 * maxw elements of
+ *       shadow_w and shadow_wt behind n_param (the slack n_weight includes: a GEMM whose k extent is a padded width reads the
+ *       weight operand up to 63 elements past the last matrix).
+ * Everything else may hold anything: the weight and bias tensors inside params / adam_m / adam_v are the caller's to fill, the
+ * first n_param elements of shadow_w and shadow_wt are written by codae_sync_shadows, and every call writes what it reads of
+ * slabs, bias_parts, the weight and bias tensors inside grads, and - when every width is a multiple of 64 - acts, dacts and the
+ * slack behind n_param in both shadows.  That holds between calls too: a call never depends on what an earlier call with another
+ * batch size, another entry point or non-finite data left in a workspace (pad rows included); after a diverged step, reloading
+ * params / adam_m / adam_v (padding included) and codae_sync_shadows is the whole recovery. */
 typedef struct {
     float* params;      /* flat: per layer W[out*in] then b[out], each padded to 64 floats */
     float* grads;       /* same layout */

@@ -92,7 +92,8 @@ class RankingLoss:
             # copy of the sample's own row (equal similarities out of one cosine_similarity call), so neither may we (codae_hip.h)
             groups = [torch.unique(self._inv_val[c], dim=0, return_inverse=True)[1] for c in range(S)]
             grp = torch.stack(groups).to(torch.int32).contiguous()
-            self._val_group = grp if int(grp.max()) + 1 < V else None          # (no duplicates: nothing to skip)
+            # (kept as soon as ANY slot holds duplicates: a slot without any has V groups, and its maximum says nothing about the others)
+            self._val_group = grp if any(int(g.max()) + 1 < V for g in groups) else None     # (no duplicates: nothing to skip)
             self._acc = torch.zeros(1, dtype=torch.float64, device=dev)
             self._work = None
 

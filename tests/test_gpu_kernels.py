@@ -491,7 +491,9 @@ def test_ranking_loss_batched_never_counts_exact_copies_of_the_own_row():
     """the sample's own similarity (a wave sum) and the GEMM's columns are summed in different orders, so an
     inventory row that is an exact COPY of the sample's own row could be counted or not by an ulp; the reference never counts
     it (both values come out of one cosine_similarity call: s[idx] > s[j] is false for equal values).  The batched kernel
-    skips such rows by identity (val_group).  Inventory with every validation row duplicated 3x vs the oracle."""
+    skips such rows by identity (val_group).  Inventory with every validation row duplicated 3x vs the oracle.  Then an inventory
+    in which ONLY slot 1 holds the copies and slots 0 and 2 hold none: the group table must be kept for it (a single maximum over
+    the stacked table dropped it as soon as one slot had no duplicate rows)."""
     from codae.tool import RankingLoss
     from oracle import dae_oracle as O
     S, E, N = 3, 32, 240
@@ -520,6 +522,23 @@ def test_ranking_loss_batched_never_counts_exact_copies_of_the_own_row():
     got = rl.total()
     assert rl._val_group is not None
     assert abs(got - ref) <= 1e-9 + 1e-6 * abs(ref), (got, ref)            # no slack for flipped comparisons: there are none
+    # only slot 1 has its validation rows duplicated
+    inv1 = np.stack([rng.standard_normal((N, E)).astype(np.float32), inv[1], rng.standard_normal((N, E)).astype(np.float32)])
+    for c in (0, 2):
+        assert len(np.unique(inv1[c][val], axis=0)) == len(val)
+    assert len(np.unique(inv1[1][val], axis=0)) < len(val)
+
+    class DS1(DS):
+        data_per_category = {c: torch.tensor(inv1[c]) for c in range(S)}
+    rl = RankingLoss(DS1(), val, device=dev())
+    pred = np.concatenate([inv1[c][idx] for c in range(S)], axis=1) + 1e-3 * rng.standard_normal((len(idx), S * E)).astype(np.float32)
+    pred = pred.astype(np.float32)
+    assert int((mtu[idx, 0] == 1).sum()) > 8                                # (samples that blank the slot with the copies)
+    ref = O.ranking_loss(pred, fm, idx, [inv1[c] for c in range(S)], E, val)
+    rl.add(torch.tensor(pred, device=dev()), torch.tensor(idx, dtype=torch.int32, device=dev()), Corr, run=0, chunk=64)
+    got = rl.total()
+    assert rl._val_group is not None
+    assert abs(got - ref) <= 1e-9 + 1e-6 * abs(ref), (got, ref)
 
 
 def test_ranking_loss_kernel_matches_oracle():
