@@ -46,9 +46,11 @@ extern "C" {
  *   8: + CODAE_NOISE_*, codae_noise, codae_set_input_noise, codae_corrupt_batch, codae_noise_box_muller (new entries only; no
  *      layout change of an existing struct, codae_struct_sizes keeps its seven entries)
  *   9: + codae_debug_gemm_bf16_plan, CODAE_GEMM_PLAN_FIELDS (new entry only; no layout change)
+ *  10: + codae_emphasis, codae_set_loss_emphasis, codae_emph_loss, codae_emph_loss_blocks (new entries only; no layout change
+ *      of an existing struct; codae_sizes.bias_part_bytes grows by a third column of per-block loss sums)
  * The binding must refuse a library whose codae_abi_version() differs and must check its own struct sizes against
  * codae_struct_sizes() at load (mui-deepautoencoder_amd/codae/hip/__init__.py does both). */
-#define CODAE_ABI_VERSION 9
+#define CODAE_ABI_VERSION 10
 
 enum {
     CODAE_OK = 0,
@@ -130,6 +132,26 @@ typedef struct {
     float p0, p1, p2;   /* sigma or p; lo, hi (SALT_PEPPER) */
     uint64_t seed;
 } codae_noise;
+
+/* Emphasised denoising loss (Vincent et al. 2010, section 4.3): the TRAINING loss weights corrupted and untouched elements
+ * differently.  For batch row b (dataset row r = row_idx[b], or b when row_idx is NULL) and column c:
+ *   blank(b,c)     the row has a mask id (mask_id or mask_to_use) and mask_table[id_b][c] == 0
+ *   replaced(b,c)  the engine's input noise is MASKING or SALT_PEPPER and the element's Philox word satisfies r < T - word,
+ *                  counter and T exactly as under "Input noise" above, with this step's index; GAUSSIAN replaces nothing
+ *   corrupted      blank or replaced
+ *   w(b,c)         col_weight[c] * (corrupted ? alpha : beta), col_weight == 1 when absent; formed in fp32
+ *   L              sum w (x - y)^2 * inv_n, inv_n = 1 / (rows * io) with rows = hyper->loss_scale_rows (the GLOBAL batch), or
+ *                  batch->B when that is 0: no renormalisation by the weights
+ *   dL/dy          2 w (y - x) inv_n
+ * CODAE_S_LAST_LOSS is L.  The metric sums CODAE_S_SQ_FULL / CODAE_S_SQ_PARTIAL stay UNWEIGHTED, so monitors are comparable
+ * across runs with different emphasis.  The target is the clean row.  Evaluation (codae_eval_step, hyper == NULL) is never
+ * weighted.  Weights multiply: a NaN difference under weight 0 gives NaN in dy and in L, as (w * (x - y) ** 2).sum() does in
+ * torch.  w depends on (dataset row, column, step, seed) only, so data-parallel ranks weight their shards as one process
+ * weights the global batch. */
+typedef struct {
+    float alpha, beta;        /* weight of a corrupted / an untouched element; finite, >= 0 */
+    const float* col_weight;  /* device, [io] or NULL; borrowed until the setting is replaced */
+} codae_emphasis;
 
 typedef struct codae_engine* codae_handle;
 
@@ -366,6 +388,13 @@ int codae_step_path(codae_handle h, const codae_buffers* bufs, int32_t B);
  * noised.  While noise is on the stack stays off the persistent chain kernel, which fuses the gather (codae_step_path
  * reports 0), exactly as a non-ReLU activation keeps it off. */
 int codae_set_input_noise(codae_handle h, const codae_noise* noise);
+/* Loss emphasis of every training step that follows (the step forms codae_set_input_noise lists; a change re-captures the
+ * graph).  NULL switches it off; alpha = beta = 1 with a NULL col_weight also means off: the engine then runs exactly the
+ * launches it ran before.  CODAE_E_INVALID for a negative or non-finite alpha or beta (nothing is launched, the previous
+ * setting stays).  While it is on, the loss leaves the last forward GEMM's epilogue for a stand-alone kernel on the per-layer
+ * path (the route CODAE_NO_FUSED_LOSS and the fp32 engine take) and the stack stays off the persistent chain kernel
+ * (codae_step_path reports 0). */
+int codae_set_loss_emphasis(codae_handle h, const codae_emphasis* emphasis);
 /* validation body (:245-258): forward + metric sums only */
 int codae_eval_step(codae_handle h, const codae_buffers* bufs, const codae_batch* batch, float* out_y,
                     void* stream);
@@ -406,6 +435,15 @@ int codae_corrupt(const float* x, const float* mask, float* out, int64_t n, void
  * scripts hold them as batch_indices) - batch row b is then read at row b and noised as dataset row noise_rows[b]. */
 int codae_corrupt_batch(const codae_batch* batch, const codae_noise* noise, int32_t step, const int32_t* noise_rows, void* out,
                         int32_t out_bf16, int64_t out_ld, void* stream);
+/* The emphasised loss on its own (the launcher the engine uses): y [B][io] fp32 against the clean rows of `batch`; dy fp32 or
+ * (dy_bf16 != 0) bf16, rows dy_ld elements apart (<= 0: io; columns past io are not written); `noise` / `step` say which
+ * elements the gather of that step replaced (NULL, NONE or GAUSSIAN: none).  One block per 32 batch rows -
+ * codae_emph_loss_blocks(B) of them -, each leaving one row of colsum_part [blocks][io] (partial column sums of dy; may be NULL)
+ * and one row of parts [blocks][3] doubles: sum w (x-y)^2, sum (x-y)^2, sum (1-fmask)(x-y)^2 (0 without a mask).  No atomics: the
+ * same inputs give the same bits. */
+int codae_emph_loss(const codae_batch* batch, const codae_noise* noise, int32_t step, const codae_emphasis* emphasis, const float* y,
+                    void* dy, int32_t dy_bf16, int64_t dy_ld, float inv_n, float* colsum_part, double* parts, void* stream);
+int codae_emph_loss_blocks(int32_t B);
 /* The Gaussian kind's device arithmetic on given words (tools/noise_accuracy.py sweeps all 2^24 values of u1 and of u2 through
  * it): rho[i] = sqrt(-2 ln u1(ra[i])), c[i] = cos(2 pi u2(rb[i])), s[i] = sin(2 pi u2(rb[i])); the unit normals of a pair are
  * rho c and rho s. */

@@ -8,7 +8,7 @@ import ctypes as C
 import torch
 
 from . import (PREC_BF16, PREC_F32, S_COUNT, S_GRAD_SQ, S_GRAD_SQ_SLOTS, S_LAST_LOSS, S_N_SLOTS, S_SQ_FULL, S_SQ_PARTIAL,
-               Batch, Buffers,
+               Batch, Buffers, Emphasis,
                HipError, Hyper, Sizes, Spec, check, current_stream, lib, ptr)
 
 
@@ -84,6 +84,8 @@ class DaeEngine:
             self.w_off.append(w.value)
             self.b_off.append(b.value)
         self.input_noise = None
+        self.loss_emphasis = None
+        self._emph_weights = None     # the device tensor codae_emphasis.col_weight borrows
         self.step_count = 0
         self.generation = 0   # bumped by every forward: guards stale backward calls
 
@@ -217,6 +219,26 @@ class DaeEngine:
         st = None if noise is None else noise.as_struct()
         check(self._lib.codae_set_input_noise(self._h, None if st is None else C.byref(st)))
         self.input_noise = noise
+
+    def set_loss_emphasis(self, emphasis, n_slots=None):
+        """emphasis: a codae.tool.LossEmphasis, or None to switch it off.  Every training step form that follows minimises
+        sum w (x - y)^2 / (global rows * io) with w = column weight * (alpha on a corrupted element, beta elsewhere); the metric
+        sums stay unweighted and eval steps are never weighted; with graph=True the next step re-captures.  While it is on,
+        step_path() is 'layers'.  n_slots: the number of slots its slot_weight must match (when known).  All defaults
+        (LossEmphasis()) = off: the engine runs exactly what it ran before."""
+        if emphasis is not None and not hasattr(emphasis, "column_weights"):
+            raise HipError("set_loss_emphasis: expected a codae.tool.LossEmphasis or None, got %r" % (emphasis,))
+        weights = None
+        if emphasis is not None:
+            cw = emphasis.column_weights(self.schedule[-1][1], n_slots)
+            if cw is not None:
+                weights = torch.from_numpy(cw).to(self.device).contiguous()
+        self._set_emphasis_struct(None if emphasis is None else Emphasis(emphasis.alpha, emphasis.beta, ptr(weights)))
+        self._emph_weights = weights
+        self.loss_emphasis = emphasis
+
+    def _set_emphasis_struct(self, st):
+        check(self._lib.codae_set_loss_emphasis(self._h, None if st is None else C.byref(st)))
 
     def train_step(self, batch, hyper, graph=False):
         """graph=True: replay the step from a hipGraph (captured on first use; batch.row_idx / mask_id must be

@@ -393,7 +393,8 @@ class HipEmbeddingTrainer:
 
     def __init__(self, schedule, data, mask_table_u8, mask_to_use_i32, lr, weight_decay, clip=1.0,
                  max_batch=8192, precision="bf16", device="cuda:0", distributed=False, n_buckets=None, use_graph=False,
-                 sharded_update=False, native_dp=False, activation=None, n_slots=None, input_noise=None):
+                 sharded_update=False, native_dp=False, activation=None, n_slots=None, input_noise=None,
+                 loss_emphasis=None):
         """use_graph: replay the fused step from a hipGraph (codae_train_step_graph): for launch-bound shapes
         (small batches); single process only - the bucketed data-parallel step is not captured.
         activation: what follows every hidden Linear, as the model classes take it (a factory called as activation(True),
@@ -402,7 +403,10 @@ class HipEmbeddingTrainer:
         input_noise: a codae.tool.InputNoise (Gaussian / masking / salt-and-pepper) applied to the gathered training input
         before the slot mask, in every step form (fused, graph replay, torch.distributed, sharded, native data parallel);
         keyed by the dataset row and the optimizer step, so N ranks noise their shards exactly as one process noises the
-        global batch.  eval_batch and complete never apply it.  None = off."""
+        global batch.  eval_batch and complete never apply it.  None = off.
+        loss_emphasis: a codae.tool.LossEmphasis: the training loss weights corrupted elements (the blanked slot, elements the
+        input noise replaced) by alpha, untouched ones by beta, and every column by its slot / column weight, in every step
+        form; epoch_sums() stays unweighted, eval_batch and complete are never weighted.  None (or all defaults) = off."""
         from .hip.engine import DaeEngine
         fit_host_threads()      # the loop that feeds this trainer must not get its container CPU-throttled (codae/hostcpu.py)
         self.device = torch.device(device)
@@ -414,6 +418,8 @@ class HipEmbeddingTrainer:
         self.mask_to_use = None if mask_to_use_i32 is None else mask_to_use_i32.to(self.device).contiguous()
         self.lr, self.weight_decay, self.clip = lr, weight_decay, clip
         self.n_slots = n_slots
+        if loss_emphasis is not None:
+            self.set_loss_emphasis(loss_emphasis)
         self.dp = DataParallel(self.engine, n_buckets=n_buckets, sharded=sharded_update, native=native_dp) if distributed else None
         self.world = self.dp.world if self.dp else 1
         self.use_graph = bool(use_graph) and self.dp is None
@@ -423,6 +429,14 @@ class HipEmbeddingTrainer:
         # (the default stream cannot be captured: graph steps run on a stream of their own, ordered after / before
         # the caller's current stream)
         self._graph_stream = torch.cuda.Stream(device=self.device) if self.use_graph else None
+
+    def set_loss_emphasis(self, emphasis):
+        """DaeEngine.set_loss_emphasis with the trainer's number of slots (n_slots, else read off the mask table) for a
+        slot_weight."""
+        S = None
+        if emphasis is not None and getattr(emphasis, "slot_weight", None) is not None and (self.n_slots or self.mask_table is not None):
+            S = self._slots()[0]
+        self.engine.set_loss_emphasis(emphasis, n_slots=S)
 
     # ---- parameters ---------------------------------------------------------------------
     def load_params(self, params):

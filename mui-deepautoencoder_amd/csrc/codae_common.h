@@ -413,6 +413,16 @@ int launch_expand_masks(const int32_t* mask_id, const uint8_t* table, const int3
 int launch_mse_loss(const codae_batch* b, const float* y, void* dy, int dy_bf16, float inv_n, float* colsum_part,
                     double* loss_parts, int want_grad, hipStream_t s, int64_t dy_ld = 0);    // dy_ld: row stride of dy (0 = io)
 int mse_loss_colsum_rows(int B);
+// The emphasised denoising loss (codae_emphasis, include/codae_hip.h): launch_mse_loss's block shape - mse_loss_colsum_rows(B)
+// blocks, one colsum_part row each - with a weight per element; `noise` / step / step_dev as launch_gather_noise (which elements
+// the gather replaced is recomputed from the same words).  parts [mse_loss_colsum_rows(B)][3]: weighted sum, sum (x-y)^2,
+// sum (1-fmask)(x-y)^2; launch_finish_emph_loss adds them up in block order: LAST_LOSS = weighted sum * inv_n, the epoch
+// accumulators take the unweighted two.  check_emphasis: CODAE_E_INVALID for a negative or non-finite alpha / beta.
+int check_emphasis(const codae_emphasis* emph);
+int launch_emph_loss(const codae_batch* b, const codae_noise* noise, int32_t step, const double* step_dev, const codae_emphasis* emph,
+                     const float* y, void* dy, int dy_bf16, int64_t dy_ld, float inv_n, float* colsum_part, double* parts,
+                     hipStream_t s);
+int launch_finish_emph_loss(double* scalars, double inv_n, hipStream_t s, const double* parts, int n_parts);
 int launch_mse_dense(const float* x, const float* y, const float* fmask, float* dy, int64_t n, float inv_n,
                      double* scalars, hipStream_t s);
 int launch_sumsq(const float* g, int64_t n, double* out, hipStream_t s);

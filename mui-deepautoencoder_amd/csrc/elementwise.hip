@@ -426,6 +426,148 @@ __global__ __launch_bounds__(NT) void mse_loss_kernel(const float* __restrict__ 
     }
 }
 
+// ---- emphasised denoising loss (codae_emphasis, include/codae_hip.h; Vincent et al. 2010, section 4.3) ----------------------
+// mse_loss_kernel's block shape (LOSS_ROWS rows per block, one partial column-sum row per block) with a weight per element:
+//   w  = col_weight[c] * (corrupted ? alpha : beta),  corrupted = blanked by the slot mask OR replaced by the input noise
+//   dy = 2 w (y - x) inv_n, written as (-2 d) (w inv_n): with w == 1 the product mse_loss_kernel forms, bit for bit
+//   parts[block] = { sum w (x-y)^2, sum (x-y)^2, sum (1-fmask)(x-y)^2 }: the metric sums stay unweighted
+// "replaced" is recomputed from the element's Philox word (the gather's counter: column / 4, DATASET row, step), one call per
+// four columns; nothing is read back from the noised input, so the kernel works on the clean row alone.
+struct EmphArgs {
+    float alpha, beta;
+    const float* col_weight;   // [io] or null (all ones)
+    int replace;               // the input noise is MASKING or SALT_PEPPER: a word below thresh marks a replaced element
+    uint64_t thresh;           // T = floor(p 2^32)
+    uint32_t key0, key1;
+    uint32_t step;             // counter word 2 ...
+    const double* step_dev;    // ... or, when not null, *step_dev (graph replay)
+};
+
+template <bool VEC, bool DY_BF16>
+__global__ __launch_bounds__(NT) void emph_loss_kernel(const float* __restrict__ data, const int32_t* __restrict__ row_idx,
+                                                       const int32_t* __restrict__ mask_id, const uint8_t* __restrict__ table,
+                                                       int B, int io, const float* __restrict__ y, void* __restrict__ dy,
+                                                       float inv_n, float* __restrict__ colsum_part, double* __restrict__ parts,
+                                                       const int32_t* __restrict__ mask_to_use, int nb_run, int run, int64_t dy_ld,
+                                                       EmphArgs ea) {
+    __shared__ float red[4];
+    const bool masked = (mask_id != nullptr) || (mask_to_use != nullptr);
+    const uint32_t step = ea.step_dev ? (uint32_t)*ea.step_dev : ea.step;
+    constexpr int W = VEC ? 4 : 1;
+    const int cols = io / W;
+    const int r_begin = blockIdx.x * LOSS_ROWS;
+    float wsq = 0.f, sq = 0.f, sqp = 0.f;
+    for (int cv = threadIdx.x; cv < cols; cv += NT) {
+        const int c = cv * W;
+        float cw[4] = {1.f, 1.f, 1.f, 1.f};
+        if (ea.col_weight != nullptr) {
+            if constexpr (VEC) {
+                const float4 w4 = *reinterpret_cast<const float4*>(ea.col_weight + c);
+                cw[0] = w4.x; cw[1] = w4.y; cw[2] = w4.z; cw[3] = w4.w;
+            } else {
+                cw[0] = ea.col_weight[c];
+            }
+        }
+        float cs[4] = {0.f, 0.f, 0.f, 0.f};
+        // rows as in mse_loss_kernel: clamped (always valid) addresses, rows past the batch contribute nothing
+        for (int r0 = 0; r0 < LOSS_ROWS; r0 += LOSS_UNROLL)
+#pragma unroll
+        for (int ru = 0; ru < LOSS_UNROLL; ++ru) {
+            const int rr = r0 + ru;
+            const bool live = r_begin + rr < B;
+            const int b = live ? r_begin + rr : B - 1;
+            const int64_t src_row = row_idx ? row_idx[b] : b;
+            float xv[4], yv[4];
+            uint32_t m = 0x01010101u;
+            const int id = !masked ? 0 : (mask_id ? mask_id[b] : mask_to_use[src_row * nb_run + run]);
+            if constexpr (VEC) {
+                const float4 x4 = *reinterpret_cast<const float4*>(data + src_row * io + c);
+                const float4 y4 = *reinterpret_cast<const float4*>(y + (int64_t)b * io + c);
+                xv[0] = x4.x; xv[1] = x4.y; xv[2] = x4.z; xv[3] = x4.w;
+                yv[0] = y4.x; yv[1] = y4.y; yv[2] = y4.z; yv[3] = y4.w;
+                if (masked) m = *reinterpret_cast<const uint32_t*>(table + (int64_t)id * io + c);
+            } else {
+                xv[0] = data[src_row * io + c];
+                yv[0] = y[(int64_t)b * io + c];
+                if (masked) m = table[(int64_t)id * io + c];
+            }
+            bool hit[4] = {false, false, false, false};
+            if (ea.replace) {
+                const uint4 r = philox4x32_10((uint32_t)(c >> 2), (uint32_t)src_row, step, 0u, ea.key0, ea.key1);
+                if constexpr (VEC) {
+                    hit[0] = (uint64_t)r.x < ea.thresh; hit[1] = (uint64_t)r.y < ea.thresh;
+                    hit[2] = (uint64_t)r.z < ea.thresh; hit[3] = (uint64_t)r.w < ea.thresh;
+                } else {
+                    const int k = c & 3;            // word k of the group (selects, no indexed register array)
+                    const uint32_t rk = (k & 2) ? ((k & 1) ? r.w : r.z) : ((k & 1) ? r.y : r.x);
+                    hit[0] = (uint64_t)rk < ea.thresh;
+                }
+            }
+            float g[4];
+#pragma unroll
+            for (int k = 0; k < W; ++k) {
+                const bool blank = ((m >> (8 * k)) & 0xff) == 0;
+                const float w = live ? cw[k] * ((blank || hit[k]) ? ea.alpha : ea.beta) : 0.f;
+                const float d = live ? xv[k] - yv[k] : 0.f;
+                const float se = d * d;
+                wsq += w * se;
+                sq += se;
+                if (blank) sqp += se;
+                g[k] = -2.f * d * (w * inv_n);
+                cs[k] += g[k];
+            }
+            if (live) {
+                const int64_t o = (int64_t)b * dy_ld + c;
+                if constexpr (DY_BF16) {
+                    bf16_t* op = reinterpret_cast<bf16_t*>(dy) + o;
+                    if constexpr (VEC) *reinterpret_cast<uint2*>(op) = pack_bf16x4(g[0], g[1], g[2], g[3]);
+                    else op[0] = f32_to_bf16(g[0]);
+                } else {
+                    float* op = reinterpret_cast<float*>(dy) + o;
+                    if constexpr (VEC) *reinterpret_cast<float4*>(op) = make_float4(g[0], g[1], g[2], g[3]);
+                    else op[0] = g[0];
+                }
+            }
+        }
+        if (colsum_part) {
+#pragma unroll
+            for (int k = 0; k < W; ++k) colsum_part[(int64_t)blockIdx.x * io + c + k] = cs[k];
+        }
+    }
+    const float bwsq = block_sum(wsq, red);
+    const float bsq = block_sum(sq, red);
+    const float bsqp = block_sum(sqp, red);
+    if (threadIdx.x == 0) {
+        parts[3 * blockIdx.x] = (double)bwsq;
+        parts[3 * blockIdx.x + 1] = (double)bsq;
+        parts[3 * blockIdx.x + 2] = masked ? (double)bsqp : 0.0;
+    }
+}
+
+// finish_loss_kernel for the three sums of emph_loss_kernel (added in index order: deterministic): LAST_LOSS = the weighted
+// sum * inv_n, the epoch accumulators take the two unweighted sums; resets the per-step accumulators.  One block.
+__global__ __launch_bounds__(NT) void finish_emph_loss_kernel(double* scalars, double inv_n, const double* __restrict__ parts,
+                                                              int n_parts) {
+    __shared__ double red[3][NT];
+    double a[3] = {0.0, 0.0, 0.0};
+    for (int i = threadIdx.x; i < n_parts; i += NT) { a[0] += parts[3 * i]; a[1] += parts[3 * i + 1]; a[2] += parts[3 * i + 2]; }
+    red[0][threadIdx.x] = a[0]; red[1][threadIdx.x] = a[1]; red[2][threadIdx.x] = a[2];
+    __syncthreads();
+    for (int o = NT / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o)
+            for (int j = 0; j < 3; ++j) red[j][threadIdx.x] += red[j][threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        scalars[CODAE_S_SQ_FULL] += red[1][0];
+        scalars[CODAE_S_SQ_PARTIAL] += red[2][0];
+        scalars[CODAE_S_LAST_LOSS] = red[0][0] * inv_n;
+        scalars[CODAE_S_STEP_SQ] = 0.0;
+        scalars[CODAE_S_GRAD_SQ] = 0.0;
+    }
+    if (threadIdx.x < CODAE_S_N_SLOTS) scalars[CODAE_S_GRAD_SQ_SLOTS + threadIdx.x] = 0.0;
+}
+
 // dense variant for the drop-in path (x, y, fmask already materialised)
 __global__ __launch_bounds__(NT) void mse_dense_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                        const float* __restrict__ fmask, float* __restrict__ dy,
@@ -954,6 +1096,57 @@ int launch_mse_loss(const codae_batch* b, const float* y, void* dy, int dy_bf16,
     else if (dy_bf16) ML(false, true);
     else ML(false, false);
 #undef ML
+    CODAE_LAUNCH_CHECK();
+    return CODAE_OK;
+}
+
+int check_emphasis(const codae_emphasis* e) {
+    if (e == nullptr) return CODAE_OK;
+    CODAE_REQUIRE(finite_f(e->alpha) && e->alpha >= 0.f, "loss emphasis: alpha %g must be finite and >= 0", (double)e->alpha);
+    CODAE_REQUIRE(finite_f(e->beta) && e->beta >= 0.f, "loss emphasis: beta %g must be finite and >= 0", (double)e->beta);
+    return CODAE_OK;
+}
+
+int launch_emph_loss(const codae_batch* b, const codae_noise* noise, int32_t step, const double* step_dev, const codae_emphasis* emph,
+                     const float* y, void* dy, int dy_bf16, int64_t dy_ld, float inv_n, float* colsum_part, double* parts,
+                     hipStream_t s) {
+    if (dy_ld <= 0) dy_ld = b ? b->io : 0;
+    CODAE_REQUIRE(b && b->data && y && dy && parts && emph && b->B > 0 && b->io > 0, "emph_loss: bad args");
+    CODAE_REQUIRE(dy_ld >= b->io, "emph_loss: dy_ld %lld below io %d", (long long)dy_ld, b->io);
+    int rc = check_emphasis(emph);
+    if (rc) return rc;
+    rc = check_noise(noise);
+    if (rc) return rc;
+    const bool masked = b->mask_id || b->mask_to_use;
+    CODAE_REQUIRE(!masked || b->mask_table, "emph_loss: mask ids without mask_table");
+    CODAE_REQUIRE(!b->mask_to_use || b->mask_id || (b->nb_run > 0 && b->run >= 0 && b->run < b->nb_run),
+                  "emph_loss: run %d outside [0, %d)", b->run, b->nb_run);
+    EmphArgs ea{};
+    ea.alpha = emph->alpha; ea.beta = emph->beta; ea.col_weight = emph->col_weight;
+    ea.step = (uint32_t)step; ea.step_dev = step_dev;
+    if (noise != nullptr && (noise->kind == CODAE_NOISE_MASKING || noise->kind == CODAE_NOISE_SALT_PEPPER)) {
+        ea.replace = 1;
+        ea.key0 = (uint32_t)(noise->seed & 0xffffffffu); ea.key1 = (uint32_t)(noise->seed >> 32);
+        ea.thresh = (uint64_t)floor((double)noise->p0 * 4294967296.0);      // (the gather's T)
+    }
+    const bool vec = (b->io % 4 == 0) && (dy_ld % 4 == 0) && a16(b->data) && a16(y) && a16(dy) &&
+                     (!emph->col_weight || a16(emph->col_weight)) && (!masked || (reinterpret_cast<uintptr_t>(b->mask_table) & 3) == 0);
+    const int grid = mse_loss_colsum_rows(b->B);
+#define EL(V, O) hipLaunchKernelGGL((emph_loss_kernel<V, O>), dim3(grid), dim3(NT), 0, s, b->data, b->row_idx, b->mask_id, \
+                                    b->mask_table, b->B, b->io, y, dy, inv_n, colsum_part, parts, b->mask_to_use, b->nb_run, b->run, \
+                                    dy_ld, ea)
+    if (vec && dy_bf16) EL(true, true);
+    else if (vec) EL(true, false);
+    else if (dy_bf16) EL(false, true);
+    else EL(false, false);
+#undef EL
+    CODAE_LAUNCH_CHECK();
+    return CODAE_OK;
+}
+
+int launch_finish_emph_loss(double* scalars, double inv_n, hipStream_t s, const double* parts, int n_parts) {
+    CODAE_REQUIRE(scalars && parts && n_parts > 0, "finish_emph_loss: bad args");
+    hipLaunchKernelGGL(finish_emph_loss_kernel, dim3(1), dim3(NT), 0, s, scalars, inv_n, parts, n_parts);
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;
 }

@@ -97,6 +97,8 @@ struct codae_engine {
     int loss_part_cap = 0;
     bool chain_ok = false;           // narrow bf16 stack: codae_train_step may take the persistent fused chain
     codae_noise noise{};             // input noise of the training steps (codae_set_input_noise); kind NONE = off
+    codae_emphasis emph{};           // loss emphasis of the training steps (codae_set_loss_emphasis), meaningful while emph_on
+    bool emph_on = false;
     std::vector<int> parts_pending;
     // backward on two streams: the weight-gradient GEMMs (+ slab reduce) run on `side`, concurrently with
     // the data-gradient chain on the caller's stream (they only share the read-only dA_l)
@@ -116,7 +118,7 @@ struct codae_engine {
     // codae_train_step_graph: the captured step and what it was captured for
     hipGraphExec_t graph_exec = nullptr;
     bool capturing = false;          // inside stream capture: device-side Adam step, everything joined at the end
-    struct GraphKey { codae_batch batch; codae_hyper hyper; codae_buffers bufs; codae_noise noise; } graph_key{};
+    struct GraphKey { codae_batch batch; codae_hyper hyper; codae_buffers bufs; codae_noise noise; codae_emphasis emph; bool emph_on; } graph_key{};
     std::vector<hipEvent_t> prof_start, prof_stop;
     std::vector<int> prof_kind;
     std::vector<int> prof_count;    // launches covered by the record (a GroupScope spans several)
@@ -339,8 +341,9 @@ int finish_bias(codae_engine* e, const codae_buffers* b, hipStream_t s, bool wit
 constexpr int CHAIN_MAX_ROWS = 2048;
 
 bool chain_eligible(codae_engine* e, const codae_buffers* b, int B) {
-    // (the chain kernel fuses the plain gather: a noised input takes the per-layer launches)
-    return e->chain_ok && e->noise.kind == CODAE_NOISE_NONE && b->shadow_wt != nullptr && e->rows_for(B) <= CHAIN_MAX_ROWS;
+    // (the chain kernel fuses the plain gather and the unweighted loss: a noised input or an emphasised loss takes the per-layer
+    //  launches)
+    return e->chain_ok && e->noise.kind == CODAE_NOISE_NONE && !e->emph_on && b->shadow_wt != nullptr && e->rows_for(B) <= CHAIN_MAX_ROWS;
 }
 
 // gather + forward chain + loss (+ data-gradient chain) of a narrow stack: one launch; then the loss finish
@@ -887,14 +890,14 @@ int codae_create(const codae_spec* spec, codae_handle* out) {
         if (e->chain_ok && chain_rows / 16 > rows_cap) rows_cap = chain_rows / 16;
         e->part_floats += round_up(rows_cap * (int64_t)e->out[l], 64);
     }
-    {   // + the loss kernels' per-workgroup metric sums: [workgroups][2] doubles
+    {   // + the loss kernels' per-workgroup metric sums: [workgroups][2] doubles ([..][3] from the emphasised loss kernel)
         const int io = e->out[e->L - 1];
         const int by_rows = (e->max_rows + 31) / 32;                                             // stand-alone loss kernel
         const int by_tiles = tile_count(e->max_rows, io, TILE_64x64);                          // fused into the last GEMM (smallest tile)
         e->loss_part_cap = by_rows > by_tiles ? by_rows : by_tiles;
         if (e->chain_ok && chain_rows / 16 > e->loss_part_cap) e->loss_part_cap = chain_rows / 16;
         e->loss_part_off = e->part_floats;
-        e->part_floats += round_up((int64_t)e->loss_part_cap * 4, 64);
+        e->part_floats += round_up((int64_t)e->loss_part_cap * 6, 64);
     }
     e->slab_bytes = 0;
     for (int l = 0; l < e->L; ++l) {
@@ -1075,7 +1078,8 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
     const int rows = h->rows_for(B);
     const bool bf = h->prec == CODAE_PREC_BF16;
     // bf16 training step: the loss is folded into the last forward GEMM's epilogue (y never stored)
-    const bool fuse_loss = bf && hyper != nullptr && out_y == nullptr && !h->cfg.no_fused_loss;
+    // (not with loss emphasis: its weights live in a stand-alone kernel, below)
+    const bool fuse_loss = bf && hyper != nullptr && out_y == nullptr && !h->cfg.no_fused_loss && !h->emph_on;
     const bool fold_finish = fuse_loss && fold != nullptr && !h->cfg.no_folded_loss_finish;
     {
         ProfScope prof(h, CODAE_K_GATHER, s);
@@ -1130,6 +1134,18 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
     if (hyper != nullptr) {
         rc = zero_pad_rows(h, dact_ptr(h, b, L - 1), B, rows, h->out_ld[L - 1], s);
         if (rc) return rc;
+        if (h->emph_on) {
+            const double inv_n = loss_inv_n(hyper, batch);
+            {
+                ProfScope prof(h, CODAE_K_LOSS, s);
+                rc = launch_emph_loss(batch, &h->noise, hyper->step, h->capturing ? b->scalars + CODAE_S_ADAM_STEP : nullptr, &h->emph, y,
+                                      dact_ptr(h, b, L - 1), bf, h->out_ld[L - 1], (float)inv_n, part_ptr(h, b, L - 1), loss_parts_ptr(h, b), s);
+            }
+            if (rc) return rc;
+            h->parts_pending[L - 1] = mse_loss_colsum_rows(B);
+            h->norm_scalars_zero = true;
+            return launch_finish_emph_loss(b->scalars, inv_n, s, loss_parts_ptr(h, b), mse_loss_colsum_rows(B));
+        }
         {
             ProfScope prof(h, CODAE_K_LOSS, s);
             rc = launch_mse_loss(batch, y, dact_ptr(h, b, L - 1), bf, (float)loss_inv_n(hyper, batch), part_ptr(h, b, L - 1),
@@ -1160,6 +1176,18 @@ int codae_set_input_noise(codae_handle h, const codae_noise* noise) {
         if (noise->kind == CODAE_NOISE_SALT_PEPPER) { n.p1 = noise->p1; n.p2 = noise->p2; }
     }
     h->noise = n;
+    return CODAE_OK;
+}
+
+int codae_set_loss_emphasis(codae_handle h, const codae_emphasis* emphasis) {
+    CODAE_REQUIRE(h != nullptr, "codae_set_loss_emphasis: null handle");
+    int rc = check_emphasis(emphasis);
+    if (rc) return rc;
+    codae_emphasis e{};                  // (built field by field: the graph key compares bytes, padding included)
+    const bool on = emphasis != nullptr && !(emphasis->alpha == 1.f && emphasis->beta == 1.f && emphasis->col_weight == nullptr);
+    if (on) { e.alpha = emphasis->alpha; e.beta = emphasis->beta; e.col_weight = emphasis->col_weight; }
+    h->emph = e;
+    h->emph_on = on;
     return CODAE_OK;
 }
 
@@ -1331,7 +1359,8 @@ int codae_train_step_graph(codae_handle h, const codae_buffers* b, const codae_b
     hk.step = 0;
     const bool fresh = h->graph_exec == nullptr || !same_bytes(&h->graph_key.batch, batch, sizeof(*batch)) ||
                        !same_bytes(&h->graph_key.hyper, &hk, sizeof(hk)) || !same_bytes(&h->graph_key.bufs, b, sizeof(*b)) ||
-                       !same_bytes(&h->graph_key.noise, &h->noise, sizeof(h->noise));
+                       !same_bytes(&h->graph_key.noise, &h->noise, sizeof(h->noise)) ||
+                       !same_bytes(&h->graph_key.emph, &h->emph, sizeof(h->emph)) || h->graph_key.emph_on != h->emph_on;
     if (fresh) {
         if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
         int rc = check_common(h, b, batch->B);
@@ -1360,7 +1389,7 @@ int codae_train_step_graph(codae_handle h, const codae_buffers* b, const codae_b
             set_error("codae_train_step_graph: hipGraphInstantiate failed: %s", hipGetErrorString(ei));
             return CODAE_E_HIP;
         }
-        h->graph_key.batch = *batch; h->graph_key.hyper = hk; h->graph_key.bufs = *b; h->graph_key.noise = h->noise;
+        h->graph_key.batch = *batch; h->graph_key.hyper = hk; h->graph_key.bufs = *b; h->graph_key.noise = h->noise; h->graph_key.emph = h->emph; h->graph_key.emph_on = h->emph_on;
     }
     int rc = launch_set_scalar(b->scalars + CODAE_S_ADAM_STEP, (double)hyper->step, s);
     if (rc) return rc;

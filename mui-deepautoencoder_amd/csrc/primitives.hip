@@ -62,6 +62,13 @@ int codae_corrupt_batch(const codae_batch* batch, const codae_noise* noise, int3
     return launch_gather_noise(batch, noise, step, nullptr, out, out_bf16, (hipStream_t)stream, out_ld, noise_rows);
 }
 
+int codae_emph_loss(const codae_batch* batch, const codae_noise* noise, int32_t step, const codae_emphasis* emphasis, const float* y,
+                    void* dy, int32_t dy_bf16, int64_t dy_ld, float inv_n, float* colsum_part, double* parts, void* stream) {
+    return launch_emph_loss(batch, noise, step, nullptr, emphasis, y, dy, dy_bf16, dy_ld, inv_n, colsum_part, parts, (hipStream_t)stream);
+}
+
+int codae_emph_loss_blocks(int32_t B) { return B > 0 ? mse_loss_colsum_rows(B) : 0; }
+
 int codae_noise_box_muller(const uint32_t* ra, const uint32_t* rb, float* rho, float* c, float* s, int64_t n, void* stream) {
     return launch_noise_box_muller(ra, rb, rho, c, s, n, (hipStream_t)stream);
 }

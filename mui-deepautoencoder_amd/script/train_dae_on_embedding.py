@@ -108,12 +108,16 @@ def main():
     # noise on the training input in front of the slot blank; LO / HI default to the resident data's min / max
     from codae.tool.noise import input_noise_from_config
     input_noise = input_noise_from_config(config.get("HIP", {}).get("INPUT_NOISE"), dataset.data)
+    # HIP: LOSS_EMPHASIS: {ALPHA: ..., BETA: ..., SLOT_WEIGHT: [..] | COLUMN_WEIGHT: [..]} (build-only key): the training loss weights
+    # corrupted elements by ALPHA, untouched ones by BETA, every slot / column by its weight (the monitors stay unweighted)
+    from codae.tool.emphasis import loss_emphasis_from_config
+    loss_emphasis = loss_emphasis_from_config(config.get("HIP", {}).get("LOSS_EMPHASIS"))
 
     def build(prec):
         return HipEmbeddingTrainer(enc + dec, dataset.data, corrupter.mask_table_u8, corrupter.mask_to_use_i32,
                                    mc["LEARNING_RATE"], mc["WEIGHT_DECAY"], clip=1.0 if mc["TRUNK_GRAD"] else 0.0,
                                    max_batch=mc["BATCH_SIZE"], precision=prec, device=device, distributed=world > 1,
-                                   activation=activation, input_noise=input_noise)
+                                   activation=activation, input_noise=input_noise, loss_emphasis=loss_emphasis)
     try:
         trainer = build(precision)
     except HipError as e:
