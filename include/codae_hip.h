@@ -48,9 +48,11 @@ extern "C" {
  *   9: + codae_debug_gemm_bf16_plan, CODAE_GEMM_PLAN_FIELDS (new entry only; no layout change)
  *  10: + codae_emphasis, codae_set_loss_emphasis, codae_emph_loss, codae_emph_loss_blocks (new entries only; no layout change
  *      of an existing struct; codae_sizes.bias_part_bytes grows by a third column of per-block loss sums)
+ *  11: + codae_dropout, codae_set_hidden_dropout, codae_dropout_fwd, codae_dropout_bwd, codae_dropout_blocks, CODAE_K_DROPOUT /
+ *      CODAE_K_COUNT 11 (new entries only; no layout change of an existing struct)
  * The binding must refuse a library whose codae_abi_version() differs and must check its own struct sizes against
  * codae_struct_sizes() at load (mui-deepautoencoder_amd/codae/hip/__init__.py does both). */
-#define CODAE_ABI_VERSION 10
+#define CODAE_ABI_VERSION 11
 
 enum {
     CODAE_OK = 0,
@@ -152,6 +154,36 @@ typedef struct {
     float alpha, beta;        /* weight of a corrupted / an untouched element; finite, >= 0 */
     const float* col_weight;  /* device, [io] or NULL; borrowed until the setting is replaced */
 } codae_emphasis;
+
+/* Hidden dropout (Srivastava et al. 2014, inverted form as torch.nn.Dropout): the TRAINING step multiplies the output of layer l,
+ * 0 <= l <= n_layers - 2 - what layer l + 1 reads and the engine keeps as act[l + 1] - by a random factor.  The last layer's
+ * output is never dropped (the input has its own masking noise, above).  For batch row b and column c < out[l]:
+ *   row     the DATASET row: row_idx[b], or b when row_idx is NULL
+ *   r       Philox4x32-10 with the multipliers and Weyl constants of "Input noise", key = (seed & 0xffffffff, seed >> 32),
+ *           counter = (c / 4, row, step, 1 + l); word c % 4 of the output belongs to column c (a last group that sticks out past
+ *           the width uses its leading words only); step = the 1-based Adam step.  The fourth counter word keeps the stream apart
+ *           from the input noise (word 0) and from the other layers, even under the same seed
+ *   T       floor(p_l 2^32), formed in double and compared as a 64-bit integer; the element is DROPPED iff r < T
+ *   f       0 when dropped, else s_l = (float)(1.0 / (1.0 - (double)p_l))
+ *   forward   a <- a f: one fp32 multiplication (bf16 engine: the stored bf16 value widened, multiplied, rounded to nearest even)
+ *   backward  the stored activation gradient of layer l: d <- d f, the same factor and rounding, applied after the data-gradient
+ *             GEMM's epilogue has applied the activation derivative; the bias gradient of layer l is the column sum of the FINAL d
+ *             over rows < B
+ * The factor multiplies: a NaN under a dropped element stays NaN and an Inf becomes NaN, as torch.nn.functional.dropout does (in
+ * line with points 1 - 4 of "Non-finite values").  One case differs from torch in non-finite arithmetic only: a ReLU layer whose
+ * data gradient takes its mask from the saved (dropped) output instead of the 1-bit masks selects 0 under a dropped unit before
+ * the factor is applied, so a non-finite incoming gradient there gives 0 where torch gives NaN.
+ * Training steps only: codae_eval_step, codae_forward / codae_backward and a forward with hyper == NULL never drop.  The metric
+ * sums and CODAE_S_LAST_LOSS are those of the dropped network's output; no separate clean forward is run.
+ * The backward takes an activation's derivative from its saved output, which is y s after dropout, so p_l > 0 is accepted only
+ * where the derivative does not depend on the output's magnitude: CODAE_ACT_NONE, RELU (1-bit masks or the saved output) and
+ * LEAKY.  f depends on (seed, dataset row, column, step, layer) only, so data-parallel ranks drop their shards as one process
+ * drops the global batch. */
+typedef struct {
+    const float* p;     /* HOST array [n], n == n_layers - 1; copied by the setter */
+    int32_t n;
+    uint64_t seed;
+} codae_dropout;
 
 typedef struct codae_engine* codae_handle;
 
@@ -395,6 +427,16 @@ int codae_set_input_noise(codae_handle h, const codae_noise* noise);
  * path (the route CODAE_NO_FUSED_LOSS and the fp32 engine take) and the stack stays off the persistent chain kernel
  * (codae_step_path reports 0). */
 int codae_set_loss_emphasis(codae_handle h, const codae_emphasis* emphasis);
+/* Hidden dropout of every training step that follows (the step forms codae_set_input_noise lists; a change re-captures the
+ * graph; under replay the step index is read from scalars[CODAE_S_ADAM_STEP]).  NULL, or every p_l == 0, switches it off: the
+ * engine then runs exactly the launches it ran before.  CODAE_E_INVALID for a p_l outside [0, 1), a non-finite p_l or
+ * n != n_layers - 1; CODAE_E_UNSUPPORTED for p_l > 0 on a layer whose activation is RELU6, ELU, SOFTPLUS or HARDSIGMOID (the
+ * message names the layer).  On any error nothing is launched and the previous setting stays.  While it is on: one stand-alone
+ * kernel behind the forward GEMM of every dropped layer and one behind the data-gradient GEMM that produces its activation
+ * gradient (class CODAE_K_DROPOUT), and the stack stays off the persistent chain kernel (codae_step_path reports 0).
+ * The backward entry points take no batch: a training forward records batch->row_idx and hyper->step in the handle, so
+ * batch->row_idx must stay valid until the backward of that step has been issued. */
+int codae_set_hidden_dropout(codae_handle h, const codae_dropout* d);
 /* validation body (:245-258): forward + metric sums only */
 int codae_eval_step(codae_handle h, const codae_buffers* bufs, const codae_batch* batch, float* out_y,
                     void* stream);
@@ -413,7 +455,8 @@ enum {
     CODAE_K_SLAB_REDUCE = 7,
     CODAE_K_CHAIN = 8,       /* narrow stacks: gather + forward chain + loss + data-gradient chain in one launch */
     CODAE_K_BIAS_FINISH = 9, /* partial column sums -> bias gradients (+ their share of sum g^2) */
-    CODAE_K_COUNT = 10
+    CODAE_K_DROPOUT = 10,    /* hidden dropout: the factor on a layer's output / on its activation gradient (+ its column sums) */
+    CODAE_K_COUNT = 11
 };
 /* Start recording a hipEvent pair around every launch whose class bit is set in class_mask
  * (bit k = CODAE_K_k), on the stream the launch uses; at most max_records pairs are kept. */
@@ -444,6 +487,17 @@ int codae_corrupt_batch(const codae_batch* batch, const codae_noise* noise, int3
 int codae_emph_loss(const codae_batch* batch, const codae_noise* noise, int32_t step, const codae_emphasis* emphasis, const float* y,
                     void* dy, int32_t dy_bf16, int64_t dy_ld, float inv_n, float* colsum_part, double* parts, void* stream);
 int codae_emph_loss_blocks(int32_t B);
+/* The two hidden-dropout kernels on their own (the launchers the engine uses; "Hidden dropout" above has the definition): in
+ * place on rows < B and columns < width of a [B][ld] matrix, fp32 or (bf16 != 0) bf16; pad columns and pad rows are never
+ * written.  16-byte accesses where the base address, ld and width allow (bf16 x 8, fp32 x 4), element accesses otherwise.
+ * layer in [0, 254] (the counter's fourth word is 1 + layer), p in [0, 1), step >= 0.  The backward form takes one block per 64
+ * batch rows - codae_dropout_blocks(B) of them - and each leaves one row of colsum_part [blocks][width] (column sums of the
+ * final values, widened to fp32; may be NULL) with plain stores added in a fixed order: the same inputs give the same bits. */
+int codae_dropout_fwd(void* a, int32_t bf16, int64_t ld, int32_t B, int32_t width, const int32_t* row_idx, int32_t layer,
+                      int32_t step, float p, uint64_t seed, void* stream);
+int codae_dropout_bwd(void* d, int32_t bf16, int64_t ld, int32_t B, int32_t width, const int32_t* row_idx, int32_t layer,
+                      int32_t step, float p, uint64_t seed, float* colsum_part, void* stream);
+int codae_dropout_blocks(int32_t B);     /* part rows codae_dropout_bwd writes: one per 64 batch rows */
 /* The Gaussian kind's device arithmetic on given words (tools/noise_accuracy.py sweeps all 2^24 values of u1 and of u2 through
  * it): rho[i] = sqrt(-2 ln u1(ra[i])), c[i] = cos(2 pi u2(rb[i])), s[i] = sin(2 pi u2(rb[i])); the unit normals of a pair are
  * rho c and rho s. */

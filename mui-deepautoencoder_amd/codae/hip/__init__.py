@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("CODAE_HIP_LIB") or os.path.join(_HERE, "libcodae_hip.
 PREC_F32 = 0
 PREC_BF16 = 1
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 # CODAE_S_* of include/codae_hip.h (tests/test_host_logic.py parses the header and compares)
 S_SQ_FULL, S_SQ_PARTIAL, S_GRAD_SQ, S_LAST_LOSS, S_STEP_SQ, S_CLIP_COEF = 0, 1, 2, 3, 4, 5
 S_GRAD_SQ_SLOTS, S_N_SLOTS, S_ADAM_STEP, S_COUNT = 8, 64, 72, 80
@@ -23,7 +23,7 @@ ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_RELU6, ACT_ELU, ACT_SOFTPLUS, ACT_HARDSIGMOID
 # CODAE_NOISE_* of include/codae_hip.h: the input noise of the training steps (codae.tool.InputNoise builds the struct)
 NOISE_NONE, NOISE_GAUSSIAN, NOISE_MASKING, NOISE_SALT_PEPPER = 0, 1, 2, 3
 KERNEL_CLASSES = ("gemm_fwd", "gemm_dgrad", "gemm_wgrad", "loss", "gather", "sumsq", "adam", "slab_reduce", "chain",
-                  "bias_finish")
+                  "bias_finish", "dropout")
 
 
 class HipError(RuntimeError):
@@ -74,6 +74,10 @@ class Emphasis(C.Structure):
     _fields_ = [("alpha", C.c_float), ("beta", C.c_float), ("col_weight", C.c_void_p)]
 
 
+class Dropout(C.Structure):
+    _fields_ = [("p", C.POINTER(C.c_float)), ("n", C.c_int32), ("seed", C.c_uint64)]
+
+
 _P, _I32, _I64, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
 # name -> (restype, argtypes); mirrors include/codae_hip.h one to one
@@ -103,6 +107,10 @@ PROTOTYPES = {
     "codae_train_step_graph": (C.c_int, [_P, C.POINTER(Buffers), C.POINTER(Batch), C.POINTER(Hyper), _P]),
     "codae_set_input_noise": (C.c_int, [_P, C.POINTER(Noise)]),
     "codae_set_loss_emphasis": (C.c_int, [_P, C.POINTER(Emphasis)]),
+    "codae_set_hidden_dropout": (C.c_int, [_P, C.POINTER(Dropout)]),
+    "codae_dropout_fwd": (C.c_int, [_P, _I32, _I64, _I32, _I32, _P, _I32, _I32, _F, C.c_uint64, _P]),
+    "codae_dropout_bwd": (C.c_int, [_P, _I32, _I64, _I32, _I32, _P, _I32, _I32, _F, C.c_uint64, _P, _P]),
+    "codae_dropout_blocks": (C.c_int, [_I32]),
     "codae_emph_loss": (C.c_int, [C.POINTER(Batch), C.POINTER(Noise), _I32, C.POINTER(Emphasis), _P, _P, _I32, _I64, _F, _P, _P, _P]),
     "codae_emph_loss_blocks": (C.c_int, [_I32]),
     "codae_corrupt_batch": (C.c_int, [C.POINTER(Batch), C.POINTER(Noise), _I32, _P, _P, _I32, _I64, _P]),

@@ -8,7 +8,7 @@ import ctypes as C
 import torch
 
 from . import (PREC_BF16, PREC_F32, S_COUNT, S_GRAD_SQ, S_GRAD_SQ_SLOTS, S_LAST_LOSS, S_N_SLOTS, S_SQ_FULL, S_SQ_PARTIAL,
-               Batch, Buffers, Emphasis,
+               Batch, Buffers, Dropout, Emphasis,
                HipError, Hyper, Sizes, Spec, check, current_stream, lib, ptr)
 
 
@@ -86,6 +86,7 @@ class DaeEngine:
         self.input_noise = None
         self.loss_emphasis = None
         self._emph_weights = None     # the device tensor codae_emphasis.col_weight borrows
+        self.hidden_dropout = None
         self.step_count = 0
         self.generation = 0   # bumped by every forward: guards stale backward calls
 
@@ -239,6 +240,24 @@ class DaeEngine:
 
     def _set_emphasis_struct(self, st):
         check(self._lib.codae_set_loss_emphasis(self._h, None if st is None else C.byref(st)))
+
+    def set_hidden_dropout(self, dropout):
+        """dropout: a codae.tool.HiddenDropout, or None to switch it off.  Every training step form that follows multiplies the
+        output of hidden layer l by 0 (probability p_l) or 1 / (1 - p_l), forward and backward, keyed by (seed, dataset row,
+        column, step, layer); eval steps never drop; with graph=True the next step re-captures.  While it is on, step_path()
+        is 'layers'.  Accepted after no activation, ReLU and LeakyReLU only (HipError otherwise; the previous setting stays).
+        All zeros = off: the engine runs exactly what it ran before."""
+        if dropout is not None and not hasattr(dropout, "per_layer"):
+            raise HipError("set_hidden_dropout: expected a codae.tool.HiddenDropout or None, got %r" % (dropout,))
+        self._set_dropout_values(None if dropout is None else dropout.per_layer(self.L), 0 if dropout is None else dropout.seed)
+        self.hidden_dropout = dropout
+
+    def _set_dropout_values(self, p, seed=0):
+        st = None
+        if p is not None:
+            arr = (C.c_float * max(len(p), 1))(*[float(v) for v in p])
+            st = Dropout(arr, len(p), int(seed))
+        check(self._lib.codae_set_hidden_dropout(self._h, None if st is None else C.byref(st)))
 
     def train_step(self, batch, hyper, graph=False):
         """graph=True: replay the step from a hipGraph (captured on first use; batch.row_idx / mask_id must be

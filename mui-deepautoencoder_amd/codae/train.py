@@ -394,7 +394,7 @@ class HipEmbeddingTrainer:
     def __init__(self, schedule, data, mask_table_u8, mask_to_use_i32, lr, weight_decay, clip=1.0,
                  max_batch=8192, precision="bf16", device="cuda:0", distributed=False, n_buckets=None, use_graph=False,
                  sharded_update=False, native_dp=False, activation=None, n_slots=None, input_noise=None,
-                 loss_emphasis=None):
+                 loss_emphasis=None, hidden_dropout=None):
         """use_graph: replay the fused step from a hipGraph (codae_train_step_graph): for launch-bound shapes
         (small batches); single process only - the bucketed data-parallel step is not captured.
         activation: what follows every hidden Linear, as the model classes take it (a factory called as activation(True),
@@ -406,7 +406,11 @@ class HipEmbeddingTrainer:
         global batch.  eval_batch and complete never apply it.  None = off.
         loss_emphasis: a codae.tool.LossEmphasis: the training loss weights corrupted elements (the blanked slot, elements the
         input noise replaced) by alpha, untouched ones by beta, and every column by its slot / column weight, in every step
-        form; epoch_sums() stays unweighted, eval_batch and complete are never weighted.  None (or all defaults) = off."""
+        form; epoch_sums() stays unweighted, eval_batch and complete are never weighted.  None (or all defaults) = off.
+        hidden_dropout: a codae.tool.HiddenDropout: the output of every hidden Linear (after its activation: none, ReLU or
+        LeakyReLU) is multiplied by 0 with probability p or by 1 / (1 - p), in every step form, keyed by the dataset row, the
+        optimizer step and the layer; the loss and epoch_sums() of a training step are those of the dropped network;
+        eval_batch and complete never drop.  None (or p = 0) = off."""
         from .hip.engine import DaeEngine
         fit_host_threads()      # the loop that feeds this trainer must not get its container CPU-throttled (codae/hostcpu.py)
         self.device = torch.device(device)
@@ -420,6 +424,8 @@ class HipEmbeddingTrainer:
         self.n_slots = n_slots
         if loss_emphasis is not None:
             self.set_loss_emphasis(loss_emphasis)
+        if hidden_dropout is not None:
+            self.set_hidden_dropout(hidden_dropout)
         self.dp = DataParallel(self.engine, n_buckets=n_buckets, sharded=sharded_update, native=native_dp) if distributed else None
         self.world = self.dp.world if self.dp else 1
         self.use_graph = bool(use_graph) and self.dp is None
@@ -437,6 +443,10 @@ class HipEmbeddingTrainer:
         if emphasis is not None and getattr(emphasis, "slot_weight", None) is not None and (self.n_slots or self.mask_table is not None):
             S = self._slots()[0]
         self.engine.set_loss_emphasis(emphasis, n_slots=S)
+
+    def set_hidden_dropout(self, dropout):
+        """DaeEngine.set_hidden_dropout: a codae.tool.HiddenDropout, or None to switch it off."""
+        self.engine.set_hidden_dropout(dropout)
 
     # ---- parameters ---------------------------------------------------------------------
     def load_params(self, params):

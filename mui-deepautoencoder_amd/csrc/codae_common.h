@@ -172,6 +172,19 @@ __device__ __forceinline__ uint32_t act_dgrad_bf16x2(int kind, const float* p, u
     return pack_bf16x2(lo, hi);
 }
 
+// Philox4x32-10 (Salmon et al. 2011): the counter-based generator of the input noise (elementwise.hip) and of the hidden dropout
+// (dropout.hip); include/codae_hip.h says which counter words each uses
+__device__ __forceinline__ uint4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return make_uint4(c0, c1, c2, c3);
+}
+
 static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 // ---- output store policy (GemmBf16::store_policy) ------------------------------------------------------
@@ -423,6 +436,16 @@ int launch_emph_loss(const codae_batch* b, const codae_noise* noise, int32_t ste
                      const float* y, void* dy, int dy_bf16, int64_t dy_ld, float inv_n, float* colsum_part, double* parts,
                      hipStream_t s);
 int launch_finish_emph_loss(double* scalars, double inv_n, hipStream_t s, const double* parts, int n_parts);
+// Hidden dropout (codae_dropout, include/codae_hip.h; dropout.hip): a <- a * f in place on rows < B, columns < width of a [B][ld]
+// matrix (fp32 or bf16), f from the Philox words of counter (column / 4, dataset row, step, 1 + layer); step_dev as
+// launch_gather_noise.  The backward form takes dropout_blocks(B) blocks, each leaving one row of colsum_part [blocks][width]
+// (column sums of the stored values; may be null).  check_dropout_p: CODAE_E_INVALID for p outside [0, 1) or not finite.
+int check_dropout_p(float p, const char* who);
+inline int dropout_blocks(int B) { return (B + 63) / 64; }
+int launch_dropout_fwd(void* a, int bf16, int64_t ld, int B, int width, const int32_t* row_idx, int layer, int32_t step,
+                       const double* step_dev, float p, uint64_t seed, hipStream_t s);
+int launch_dropout_bwd(void* d, int bf16, int64_t ld, int B, int width, const int32_t* row_idx, int layer, int32_t step,
+                       const double* step_dev, float p, uint64_t seed, float* colsum_part, hipStream_t s);
 int launch_mse_dense(const float* x, const float* y, const float* fmask, float* dy, int64_t n, float inv_n,
                      double* scalars, hipStream_t s);
 int launch_sumsq(const float* g, int64_t n, double* out, hipStream_t s);

@@ -150,17 +150,6 @@ struct NoiseArgs {
     double* zero_norm;         // see zero_norm_scalars
 };
 
-__device__ __forceinline__ uint4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return make_uint4(c0, c1, c2, c3);
-}
-
 // Box-Muller pieces from one pair of words.  u1 in (0, 1] and 2 u2 in [0, 2) are exact in fp32; logf keeps its relative accuracy
 // for u1 next to 1 (rho is a square root of it), sincospif reduces its argument exactly (tools/noise_accuracy.py: every one of
 // the 2^24 values of u1 and of u2 against float64)

@@ -99,6 +99,14 @@ struct codae_engine {
     codae_noise noise{};             // input noise of the training steps (codae_set_input_noise); kind NONE = off
     codae_emphasis emph{};           // loss emphasis of the training steps (codae_set_loss_emphasis), meaningful while emph_on
     bool emph_on = false;
+    // hidden dropout of the training steps (codae_set_hidden_dropout): p[l] of layer l's output, all zero = off.  The backward entry
+    // points take no batch, so a training forward leaves what they need behind: drop_live = the activations in the workspace were
+    // dropped (an evaluation or drop-in forward clears it), with the batch rows, row indices and step of that forward
+    struct DropCfg { float p[64]; uint64_t seed; int32_t on; int32_t reserved; } drop{};
+    bool drop_live = false;
+    int drop_B = 0;
+    const int32_t* drop_rows = nullptr;
+    int32_t drop_step = 0;
     std::vector<int> parts_pending;
     // backward on two streams: the weight-gradient GEMMs (+ slab reduce) run on `side`, concurrently with
     // the data-gradient chain on the caller's stream (they only share the read-only dA_l)
@@ -118,7 +126,7 @@ struct codae_engine {
     // codae_train_step_graph: the captured step and what it was captured for
     hipGraphExec_t graph_exec = nullptr;
     bool capturing = false;          // inside stream capture: device-side Adam step, everything joined at the end
-    struct GraphKey { codae_batch batch; codae_hyper hyper; codae_buffers bufs; codae_noise noise; codae_emphasis emph; bool emph_on; } graph_key{};
+    struct GraphKey { codae_batch batch; codae_hyper hyper; codae_buffers bufs; codae_noise noise; codae_emphasis emph; bool emph_on; DropCfg drop; } graph_key{};
     std::vector<hipEvent_t> prof_start, prof_stop;
     std::vector<int> prof_kind;
     std::vector<int> prof_count;    // launches covered by the record (a GroupScope spans several)
@@ -341,9 +349,9 @@ int finish_bias(codae_engine* e, const codae_buffers* b, hipStream_t s, bool wit
 constexpr int CHAIN_MAX_ROWS = 2048;
 
 bool chain_eligible(codae_engine* e, const codae_buffers* b, int B) {
-    // (the chain kernel fuses the plain gather and the unweighted loss: a noised input or an emphasised loss takes the per-layer
-    //  launches)
-    return e->chain_ok && e->noise.kind == CODAE_NOISE_NONE && !e->emph_on && b->shadow_wt != nullptr && e->rows_for(B) <= CHAIN_MAX_ROWS;
+    // (the chain kernel fuses the plain gather and the unweighted loss and keeps the activations to itself: a noised input, an
+    //  emphasised loss or hidden dropout takes the per-layer launches)
+    return e->chain_ok && e->noise.kind == CODAE_NOISE_NONE && !e->emph_on && !e->drop.on && b->shadow_wt != nullptr && e->rows_for(B) <= CHAIN_MAX_ROWS;
 }
 
 // gather + forward chain + loss (+ data-gradient chain) of a narrow stack: one launch; then the loss finish
@@ -566,7 +574,7 @@ int run_wgrad(codae_engine* e, const codae_buffers* b, int l, int rows, bool wit
 
 // dA_{l-1} = (dA_l W_l) * [act[l] > 0]  (+ column sums -> db_{l-1});  l == 0 with dx: plain dX in fp32
 // coscheduled: another stream's weight gradients run beside this launch (GemmBf16::coscheduled)
-int run_dgrad(codae_engine* e, const codae_buffers* b, int l, int rows, bool coscheduled, float* dx_f32, hipStream_t s) {
+int run_dgrad_gemm(codae_engine* e, const codae_buffers* b, int l, int rows, bool coscheduled, float* dx_f32, hipStream_t s) {
     const int N = e->out[l], K = e->in[l];
     const bool to_dx = (dx_f32 != nullptr);
     ProfScope prof(e, CODAE_K_GEMM_DGRAD, s);
@@ -610,6 +618,35 @@ int run_dgrad(codae_engine* e, const codae_buffers* b, int l, int rows, bool cos
         e->parts_pending[l - 1] = gemm_f32_colsum_rows(rows);
     }
     return gemm_f32_small(e, b, g, s);
+}
+
+// step of the dropout counter: the forward's, or under graph capture the device scalar the replay refreshes
+inline const double* drop_step_dev(codae_engine* e, const codae_buffers* b) { return e->capturing ? b->scalars + CODAE_S_ADAM_STEP : nullptr; }
+inline bool drops_layer(codae_engine* e, int l) { return e->drop_live && e->drop.on && l >= 0 && l + 1 < e->L && e->drop.p[l] > 0.f; }
+
+// act[l + 1] <- act[l + 1] * f behind the forward GEMM of a dropped layer l (its 1-bit ReLU masks stay "pre-dropout y > 0": the
+// backward multiplies by f after the mask)
+int run_dropout_fwd(codae_engine* e, const codae_buffers* b, int l, hipStream_t s) {
+    ProfScope prof(e, CODAE_K_DROPOUT, s);
+    return launch_dropout_fwd(act_ptr(e, b, l + 1), e->prec == CODAE_PREC_BF16, e->in_ld[l + 1], e->drop_B, e->out[l], e->drop_rows, l,
+                              e->drop_step, drop_step_dev(e, b), e->drop.p[l], e->drop.seed, s);
+}
+
+// the data gradient of layer l and, when layer l - 1 was dropped in the forward, dA_{l-1} <- dA_{l-1} * f right behind it on the same
+// stream: the kernel writes layer l - 1's partial column sums again, from the final values, in place of the GEMM epilogue's (one row
+// per 64 batch rows: within the rows the layer owns), before the caller records the event the side-stream weight gradient waits for
+int run_dgrad(codae_engine* e, const codae_buffers* b, int l, int rows, bool coscheduled, float* dx_f32, hipStream_t s) {
+    int rc = run_dgrad_gemm(e, b, l, rows, coscheduled, dx_f32, s);
+    if (rc || dx_f32 != nullptr || !drops_layer(e, l - 1)) return rc;
+    {
+        ProfScope prof(e, CODAE_K_DROPOUT, s);
+        rc = launch_dropout_bwd(dact_ptr(e, b, l - 1), e->prec == CODAE_PREC_BF16, e->prec == CODAE_PREC_BF16 ? e->out_ld[l - 1] : e->out[l - 1],
+                                e->drop_B, e->out[l - 1], e->drop_rows, l - 1, e->drop_step, drop_step_dev(e, b), e->drop.p[l - 1], e->drop.seed,
+                                part_ptr(e, b, l - 1), s);
+    }
+    if (rc) return rc;
+    e->parts_pending[l - 1] = dropout_blocks(e->drop_B);
+    return CODAE_OK;
 }
 
 // Wt_l [in][out] <- W_l [out][in] (bf16) for every layer that has a data gradient (l >= 1)
@@ -680,6 +717,7 @@ int backward_range(codae_handle h, const codae_buffers* b, int B, int lo, int hi
                    hipStream_t s, bool join = true, const LossFinish* loss = nullptr) {
     const int rows = h->rows_for(B);
     const bool dual = !h->cfg.single_stream;
+    CODAE_REQUIRE(!(step_mode && h->drop_live && h->drop.on) || B == h->drop_B, "backward of %d rows after a dropped forward of %d", B, h->drop_B);
     if (dual) {
         int rc = ensure_side_stream(h);
         if (rc) return rc;
@@ -1014,6 +1052,7 @@ int codae_forward(codae_handle h, const codae_buffers* b, const float* x, float*
     CODAE_REQUIRE(x && y, "codae_forward: null x or y");
     CODAE_REQUIRE(layer_lo >= 0 && layer_lo < layer_hi && layer_hi <= h->L, "codae_forward: layer range [%d, %d)", layer_lo, layer_hi);
     (void)save_for_backward;  // activations always live in the workspace; a later forward overwrites them
+    h->drop_live = false;     // (a drop-in forward never drops)
     hipStream_t s = (hipStream_t)stream;
     const int rows = h->rows_for(B);
     // ingest x into act[layer_lo] in working precision (no gather, no mask)
@@ -1077,6 +1116,9 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
     const int B = batch->B, L = h->L;
     const int rows = h->rows_for(B);
     const bool bf = h->prec == CODAE_PREC_BF16;
+    // hidden dropout: training forwards only; the backward entry points find the rows and the step in the handle
+    h->drop_live = hyper != nullptr && h->drop.on;
+    if (h->drop_live) { h->drop_B = B; h->drop_rows = batch->row_idx; h->drop_step = hyper->step; }
     // bf16 training step: the loss is folded into the last forward GEMM's epilogue (y never stored)
     // (not with loss emphasis: its weights live in a stand-alone kernel, below)
     const bool fuse_loss = bf && hyper != nullptr && out_y == nullptr && !h->cfg.no_fused_loss && !h->emph_on;
@@ -1095,6 +1137,7 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
     if (rc) return rc;
     float* y = out_y ? out_y : reinterpret_cast<float*>(act_ptr(h, b, L));
     GroupScope fwd_group(h, CODAE_K_GEMM_FWD, s);       // the plain forward launches of this step, back to back
+    if (h->drop_live) fwd_group.close();                // (dropout kernels sit between them: every launch gets its own event pair)
     for (int l = 0; l < L; ++l) {
         const bool last = (l == L - 1);
         if (last && fuse_loss) {
@@ -1129,6 +1172,10 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
                   : run_linear(h, b, l, act_ptr(h, b, l), act_ptr(h, b, l + 1), false, rows, s);
         if (rc) return rc;
         fwd_group.launched();
+        if (drops_layer(h, l)) {
+            rc = run_dropout_fwd(h, b, l, s);
+            if (rc) return rc;
+        }
     }
     fwd_group.close();
     if (hyper != nullptr) {
@@ -1188,6 +1235,35 @@ int codae_set_loss_emphasis(codae_handle h, const codae_emphasis* emphasis) {
     if (on) { e.alpha = emphasis->alpha; e.beta = emphasis->beta; e.col_weight = emphasis->col_weight; }
     h->emph = e;
     h->emph_on = on;
+    return CODAE_OK;
+}
+
+int codae_set_hidden_dropout(codae_handle h, const codae_dropout* d) {
+    CODAE_REQUIRE(h != nullptr, "codae_set_hidden_dropout: null handle");
+    codae_engine::DropCfg c{};           // (built field by field: the graph key compares bytes, padding included)
+    if (d != nullptr) {
+        CODAE_REQUIRE(d->n == h->L - 1, "codae_set_hidden_dropout: %d values for %d hidden outputs (n_layers - 1)", d->n, h->L - 1);
+        CODAE_REQUIRE(d->n == 0 || d->p != nullptr, "codae_set_hidden_dropout: null p");
+        for (int l = 0; l < d->n; ++l) {
+            char who[64];
+            snprintf(who, sizeof(who), "codae_set_hidden_dropout: layer %d", l);
+            int rc = check_dropout_p(d->p[l], who);
+            if (rc) return rc;
+        }
+        for (int l = 0; l < d->n; ++l) {
+            if (!(d->p[l] > 0.f)) continue;
+            if (h->act[l] != CODAE_ACT_NONE && h->act[l] != CODAE_ACT_LEAKY) {
+                // (the backward takes the derivative from the saved output, which dropout rescales)
+                set_error("codae_set_hidden_dropout: layer %d: dropout after activation kind %d is not supported (NONE, RELU and LEAKY only)",
+                          l, (int)h->act[l]);
+                return CODAE_E_UNSUPPORTED;
+            }
+            c.p[l] = d->p[l];
+            c.on = 1;
+        }
+        if (c.on) c.seed = d->seed;
+    }
+    h->drop = c;
     return CODAE_OK;
 }
 
@@ -1323,6 +1399,7 @@ int codae_train_step(codae_handle h, const codae_buffers* b, const codae_batch* 
         hipStream_t s = (hipStream_t)stream;
         rcc = join_side(h, s);
         if (rcc) return rcc;
+        h->drop_live = false;
         LossFinish lf{};
         rcc = run_chain(h, b, batch, hyper, true, s, &lf);
         if (rcc) return rcc;
@@ -1360,7 +1437,8 @@ int codae_train_step_graph(codae_handle h, const codae_buffers* b, const codae_b
     const bool fresh = h->graph_exec == nullptr || !same_bytes(&h->graph_key.batch, batch, sizeof(*batch)) ||
                        !same_bytes(&h->graph_key.hyper, &hk, sizeof(hk)) || !same_bytes(&h->graph_key.bufs, b, sizeof(*b)) ||
                        !same_bytes(&h->graph_key.noise, &h->noise, sizeof(h->noise)) ||
-                       !same_bytes(&h->graph_key.emph, &h->emph, sizeof(h->emph)) || h->graph_key.emph_on != h->emph_on;
+                       !same_bytes(&h->graph_key.emph, &h->emph, sizeof(h->emph)) || h->graph_key.emph_on != h->emph_on ||
+                       !same_bytes(&h->graph_key.drop, &h->drop, sizeof(h->drop));
     if (fresh) {
         if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
         int rc = check_common(h, b, batch->B);
@@ -1390,6 +1468,7 @@ int codae_train_step_graph(codae_handle h, const codae_buffers* b, const codae_b
             return CODAE_E_HIP;
         }
         h->graph_key.batch = *batch; h->graph_key.hyper = hk; h->graph_key.bufs = *b; h->graph_key.noise = h->noise; h->graph_key.emph = h->emph; h->graph_key.emph_on = h->emph_on;
+        h->graph_key.drop = h->drop;
     }
     int rc = launch_set_scalar(b->scalars + CODAE_S_ADAM_STEP, (double)hyper->step, s);
     if (rc) return rc;

@@ -69,6 +69,18 @@ int codae_emph_loss(const codae_batch* batch, const codae_noise* noise, int32_t 
 
 int codae_emph_loss_blocks(int32_t B) { return B > 0 ? mse_loss_colsum_rows(B) : 0; }
 
+int codae_dropout_fwd(void* a, int32_t bf16, int64_t ld, int32_t B, int32_t width, const int32_t* row_idx, int32_t layer, int32_t step,
+                      float p, uint64_t seed, void* stream) {
+    return launch_dropout_fwd(a, bf16, ld, B, width, row_idx, layer, step, nullptr, p, seed, (hipStream_t)stream);
+}
+
+int codae_dropout_bwd(void* d, int32_t bf16, int64_t ld, int32_t B, int32_t width, const int32_t* row_idx, int32_t layer, int32_t step,
+                      float p, uint64_t seed, float* colsum_part, void* stream) {
+    return launch_dropout_bwd(d, bf16, ld, B, width, row_idx, layer, step, nullptr, p, seed, colsum_part, (hipStream_t)stream);
+}
+
+int codae_dropout_blocks(int32_t B) { return B > 0 ? dropout_blocks(B) : 0; }
+
 int codae_noise_box_muller(const uint32_t* ra, const uint32_t* rb, float* rho, float* c, float* s, int64_t n, void* stream) {
     return launch_noise_box_muller(ra, rb, rho, c, s, n, (hipStream_t)stream);
 }

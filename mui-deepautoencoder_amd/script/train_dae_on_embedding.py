@@ -112,12 +112,17 @@ def main():
     # corrupted elements by ALPHA, untouched ones by BETA, every slot / column by its weight (the monitors stay unweighted)
     from codae.tool.emphasis import loss_emphasis_from_config
     loss_emphasis = loss_emphasis_from_config(config.get("HIP", {}).get("LOSS_EMPHASIS"))
+    # HIP: HIDDEN_DROPOUT: {P: 0.5 | [.. one per hidden output ..], SEED: ...} (build-only key): dropout on the output of every
+    # hidden Linear of the training steps (validation never drops)
+    from codae.tool.dropout import hidden_dropout_from_config
+    hidden_dropout = hidden_dropout_from_config(config.get("HIP", {}).get("HIDDEN_DROPOUT"))
 
     def build(prec):
         return HipEmbeddingTrainer(enc + dec, dataset.data, corrupter.mask_table_u8, corrupter.mask_to_use_i32,
                                    mc["LEARNING_RATE"], mc["WEIGHT_DECAY"], clip=1.0 if mc["TRUNK_GRAD"] else 0.0,
                                    max_batch=mc["BATCH_SIZE"], precision=prec, device=device, distributed=world > 1,
-                                   activation=activation, input_noise=input_noise, loss_emphasis=loss_emphasis)
+                                   activation=activation, input_noise=input_noise, loss_emphasis=loss_emphasis,
+                                   hidden_dropout=hidden_dropout)
     try:
         trainer = build(precision)
     except HipError as e:
