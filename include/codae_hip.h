@@ -50,6 +50,8 @@ extern "C" {
  *      of an existing struct; codae_sizes.bias_part_bytes grows by a third column of per-block loss sums)
  *  11: + codae_dropout, codae_set_hidden_dropout, codae_dropout_fwd, codae_dropout_bwd, codae_dropout_blocks, CODAE_K_DROPOUT /
  *      CODAE_K_COUNT 11 (new entries only; no layout change of an existing struct)
+ *      (still 11) + CODAE_LOSS_*, CODAE_COS_EPS, codae_recon_loss, codae_set_recon_loss, codae_recon_loss_fwd_bwd,
+ *      codae_recon_loss_blocks: new entries only, no layout or enum change, the new kernels are booked under CODAE_K_LOSS
  * The binding must refuse a library whose codae_abi_version() differs and must check its own struct sizes against
  * codae_struct_sizes() at load (mui-deepautoencoder_amd/codae/hip/__init__.py does both). */
 #define CODAE_ABI_VERSION 11
@@ -154,6 +156,42 @@ typedef struct {
     float alpha, beta;        /* weight of a corrupted / an untouched element; finite, >= 0 */
     const float* col_weight;  /* device, [io] or NULL; borrowed until the setting is replaced */
 } codae_emphasis;
+
+/* Training criterion: what the TRAINING loss measures between the clean row x and the output y; the default is the mean squared
+ * error the reference script hard-wires.  d = x - y, rows = the global batch (hyper->loss_scale_rows, or batch->B when that is 0),
+ * io = S E, inv_n = 1 / (rows io), w(b,c) = the emphasis weight defined above (1 everywhere when emphasis is off).
+ * Element-wise kinds: L = sum w rho(d) inv_n, dL/dy = -w rho'(d) inv_n
+ *   MSE        rho = d^2 (no factor 1/2)                                   rho' = 2 d                      -
+ *   L1         rho = |d|                                                   rho' = sign(d), sign(0) = 0     -
+ *   SMOOTH_L1  rho = |d| < beta ? d^2 / (2 beta) : |d| - beta / 2          rho' = d / beta or sign(d)      param = beta > 0
+ *   HUBER      rho = |d| <= delta ? d^2 / 2 : delta (|d| - delta / 2)      rho' = d or delta sign(d)       param = delta > 0
+ * (torch's l1_loss, smooth_l1_loss(beta=) and huber_loss(delta=) with reduction="none", weighted and summed.)
+ * SLOT_COSINE, n_slots = S dividing io; for row b and slot s over its E columns:
+ *   dot = sum x y, nx = max(|x|, eps), ny = max(|y|, eps), eps = CODAE_COS_EPS, cos = dot / (nx ny)
+ *   W(b,s)  = (1 / E) sum_{c in s} w(b,c)
+ *   L       = sum_{b,s} W (1 - cos) / (rows S)  +  mse_weight sum w d^2 inv_n
+ *   dL/dy_c = -W / (rows S) (x_c / (nx ny) - [|y| > eps] cos y_c / |y|^2)  +  mse_weight 2 w (y_c - x_c) inv_n
+ *   (torch's cosine_similarity(dim=-1, eps=1e-8) and its autograd.)  A zero target slot: cos = 0, term W, gradient 0.
+ *   mse_weight >= 0 keeps the lengths anchored, which the cosine ignores.
+ * CODAE_S_LAST_LOSS is L; CODAE_S_SQ_FULL / CODAE_S_SQ_PARTIAL stay the unweighted squared-error sums whatever the criterion;
+ * evaluation never sees it.  Weights multiply and NaN propagates: a NaN in a slot of y makes that slot's dy and L NaN, under
+ * weight 0 too.  The order in which a pair's E products are added depends on E alone, so a data-parallel shard's dy rows are
+ * the bits of the same rows of the global batch. */
+enum {
+    CODAE_LOSS_MSE = 0,
+    CODAE_LOSS_L1 = 1,
+    CODAE_LOSS_SMOOTH_L1 = 2,
+    CODAE_LOSS_HUBER = 3,
+    CODAE_LOSS_SLOT_COSINE = 4
+};
+#define CODAE_COS_EPS 1e-8f
+
+typedef struct {
+    int32_t kind;       /* CODAE_LOSS_* */
+    float param;        /* beta (SMOOTH_L1) or delta (HUBER): finite, > 0; ignored by the other kinds */
+    float mse_weight;   /* SLOT_COSINE only: finite, >= 0; must be 0 for every other kind */
+    int32_t n_slots;    /* SLOT_COSINE only: 1 <= n_slots <= 128, dividing io */
+} codae_recon_loss;
 
 /* Hidden dropout (Srivastava et al. 2014, inverted form as torch.nn.Dropout): the TRAINING step multiplies the output of layer l,
  * 0 <= l <= n_layers - 2 - what layer l + 1 reads and the engine keeps as act[l + 1] - by a random factor.  The last layer's
@@ -427,6 +465,14 @@ int codae_set_input_noise(codae_handle h, const codae_noise* noise);
  * path (the route CODAE_NO_FUSED_LOSS and the fp32 engine take) and the stack stays off the persistent chain kernel
  * (codae_step_path reports 0). */
 int codae_set_loss_emphasis(codae_handle h, const codae_emphasis* emphasis);
+/* Training criterion of every training step that follows (the step forms codae_set_input_noise lists; a change re-captures the
+ * graph).  NULL or kind CODAE_LOSS_MSE switches it off: the engine then runs exactly the launches it ran before (the fused
+ * epilogue or the chain kernel, the emphasised kernel with emphasis).  CODAE_E_INVALID for an unknown kind, a beta / delta that
+ * is not finite and > 0, a negative or non-finite mse_weight, an mse_weight != 0 with a kind other than SLOT_COSINE, n_slots < 1
+ * or not dividing io; CODAE_E_UNSUPPORTED for n_slots > 128.  On any error nothing is launched and the previous setting stays.
+ * While it is on, the loss runs as a stand-alone kernel behind the last forward GEMM, with or without emphasis, and the stack
+ * stays off the persistent chain kernel (codae_step_path reports 0), exactly as with emphasis. */
+int codae_set_recon_loss(codae_handle h, const codae_recon_loss* loss);
 /* Hidden dropout of every training step that follows (the step forms codae_set_input_noise lists; a change re-captures the
  * graph; under replay the step index is read from scalars[CODAE_S_ADAM_STEP]).  NULL, or every p_l == 0, switches it off: the
  * engine then runs exactly the launches it ran before.  CODAE_E_INVALID for a p_l outside [0, 1), a non-finite p_l or
@@ -487,6 +533,16 @@ int codae_corrupt_batch(const codae_batch* batch, const codae_noise* noise, int3
 int codae_emph_loss(const codae_batch* batch, const codae_noise* noise, int32_t step, const codae_emphasis* emphasis, const float* y,
                     void* dy, int32_t dy_bf16, int64_t dy_ld, float inv_n, float* colsum_part, double* parts, void* stream);
 int codae_emph_loss_blocks(int32_t B);
+/* A criterion other than the MSE on its own (the launcher the engine uses; "Training criterion" above has the definition):
+ * arguments as codae_emph_loss, with `emphasis` NULL = all weights 1 and `loss` a validated non-MSE criterion (kind MSE:
+ * CODAE_E_INVALID - that one runs on codae_emph_loss).  One block per 32 batch rows - codae_recon_loss_blocks(B) of them -, each
+ * leaving one row of colsum_part [blocks][io] (may be NULL) and one row of parts [blocks][3] doubles: the criterion's sum (times
+ * inv_n = L; SLOT_COSINE: mse_weight sum w d^2 + E sum W (1 - cos)), sum (x-y)^2, sum (1-fmask)(x-y)^2.  No atomics: the same
+ * inputs give the same bits.  On an error nothing is launched and nothing is written. */
+int codae_recon_loss_fwd_bwd(const codae_batch* batch, const codae_noise* noise, int32_t step, const codae_emphasis* emphasis,
+                             const codae_recon_loss* loss, const float* y, void* dy, int32_t dy_bf16, int64_t dy_ld, float inv_n,
+                             float* colsum_part, double* parts, void* stream);
+int codae_recon_loss_blocks(int32_t B);
 /* The two hidden-dropout kernels on their own (the launchers the engine uses; "Hidden dropout" above has the definition): in
  * place on rows < B and columns < width of a [B][ld] matrix, fp32 or (bf16 != 0) bf16; pad columns and pad rows are never
  * written.  16-byte accesses where the base address, ld and width allow (bf16 x 8, fp32 x 4), element accesses otherwise.

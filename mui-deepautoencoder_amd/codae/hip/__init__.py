@@ -22,6 +22,8 @@ S_GRAD_SQ_SLOTS, S_N_SLOTS, S_ADAM_STEP, S_COUNT = 8, 64, 72, 80
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_RELU6, ACT_ELU, ACT_SOFTPLUS, ACT_HARDSIGMOID = 0, 1, 2, 3, 4, 5, 6
 # CODAE_NOISE_* of include/codae_hip.h: the input noise of the training steps (codae.tool.InputNoise builds the struct)
 NOISE_NONE, NOISE_GAUSSIAN, NOISE_MASKING, NOISE_SALT_PEPPER = 0, 1, 2, 3
+# CODAE_LOSS_* of include/codae_hip.h: the training criterion (codae.tool.ReconstructionLoss builds the struct)
+LOSS_MSE, LOSS_L1, LOSS_SMOOTH_L1, LOSS_HUBER, LOSS_SLOT_COSINE = 0, 1, 2, 3, 4
 KERNEL_CLASSES = ("gemm_fwd", "gemm_dgrad", "gemm_wgrad", "loss", "gather", "sumsq", "adam", "slab_reduce", "chain",
                   "bias_finish", "dropout")
 
@@ -74,6 +76,10 @@ class Emphasis(C.Structure):
     _fields_ = [("alpha", C.c_float), ("beta", C.c_float), ("col_weight", C.c_void_p)]
 
 
+class ReconLoss(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("param", C.c_float), ("mse_weight", C.c_float), ("n_slots", C.c_int32)]
+
+
 class Dropout(C.Structure):
     _fields_ = [("p", C.POINTER(C.c_float)), ("n", C.c_int32), ("seed", C.c_uint64)]
 
@@ -107,12 +113,16 @@ PROTOTYPES = {
     "codae_train_step_graph": (C.c_int, [_P, C.POINTER(Buffers), C.POINTER(Batch), C.POINTER(Hyper), _P]),
     "codae_set_input_noise": (C.c_int, [_P, C.POINTER(Noise)]),
     "codae_set_loss_emphasis": (C.c_int, [_P, C.POINTER(Emphasis)]),
+    "codae_set_recon_loss": (C.c_int, [_P, C.POINTER(ReconLoss)]),
     "codae_set_hidden_dropout": (C.c_int, [_P, C.POINTER(Dropout)]),
     "codae_dropout_fwd": (C.c_int, [_P, _I32, _I64, _I32, _I32, _P, _I32, _I32, _F, C.c_uint64, _P]),
     "codae_dropout_bwd": (C.c_int, [_P, _I32, _I64, _I32, _I32, _P, _I32, _I32, _F, C.c_uint64, _P, _P]),
     "codae_dropout_blocks": (C.c_int, [_I32]),
     "codae_emph_loss": (C.c_int, [C.POINTER(Batch), C.POINTER(Noise), _I32, C.POINTER(Emphasis), _P, _P, _I32, _I64, _F, _P, _P, _P]),
     "codae_emph_loss_blocks": (C.c_int, [_I32]),
+    "codae_recon_loss_fwd_bwd": (C.c_int, [C.POINTER(Batch), C.POINTER(Noise), _I32, C.POINTER(Emphasis), C.POINTER(ReconLoss), _P, _P, _I32, _I64,
+                                           _F, _P, _P, _P]),
+    "codae_recon_loss_blocks": (C.c_int, [_I32]),
     "codae_corrupt_batch": (C.c_int, [C.POINTER(Batch), C.POINTER(Noise), _I32, _P, _P, _I32, _I64, _P]),
     "codae_noise_box_muller": (C.c_int, [_P, _P, _P, _P, _P, _I64, _P]),
     "codae_eval_step": (C.c_int, [_P, C.POINTER(Buffers), C.POINTER(Batch), _P, _P]),

@@ -87,6 +87,7 @@ class DaeEngine:
         self.loss_emphasis = None
         self._emph_weights = None     # the device tensor codae_emphasis.col_weight borrows
         self.hidden_dropout = None
+        self.recon_loss = None
         self.step_count = 0
         self.generation = 0   # bumped by every forward: guards stale backward calls
 
@@ -240,6 +241,20 @@ class DaeEngine:
 
     def _set_emphasis_struct(self, st):
         check(self._lib.codae_set_loss_emphasis(self._h, None if st is None else C.byref(st)))
+
+    def set_recon_loss(self, criterion, n_slots=None):
+        """criterion: a codae.tool.ReconstructionLoss, or None for the mean squared error.  Every training step form that follows
+        minimises it (include/codae_hip.h, "Training criterion"), with the emphasis weights when emphasis is on; epoch_sums()
+        stays the unweighted squared-error sums and eval steps never see it; with graph=True the next step re-captures.  While
+        a criterion other than the MSE is set, step_path() is 'layers'.  n_slots: slots per row, for slot_cosine.  The default
+        (ReconstructionLoss()) = off: the engine runs exactly what it ran before."""
+        if criterion is not None and not hasattr(criterion, "as_struct"):
+            raise HipError("set_recon_loss: expected a codae.tool.ReconstructionLoss or None, got %r" % (criterion,))
+        self._set_recon_struct(None if criterion is None else criterion.as_struct(n_slots))
+        self.recon_loss = criterion
+
+    def _set_recon_struct(self, st):
+        check(self._lib.codae_set_recon_loss(self._h, None if st is None else C.byref(st)))
 
     def set_hidden_dropout(self, dropout):
         """dropout: a codae.tool.HiddenDropout, or None to switch it off.  Every training step form that follows multiplies the

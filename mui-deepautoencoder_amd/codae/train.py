@@ -394,7 +394,7 @@ class HipEmbeddingTrainer:
     def __init__(self, schedule, data, mask_table_u8, mask_to_use_i32, lr, weight_decay, clip=1.0,
                  max_batch=8192, precision="bf16", device="cuda:0", distributed=False, n_buckets=None, use_graph=False,
                  sharded_update=False, native_dp=False, activation=None, n_slots=None, input_noise=None,
-                 loss_emphasis=None, hidden_dropout=None):
+                 loss_emphasis=None, hidden_dropout=None, criterion=None):
         """use_graph: replay the fused step from a hipGraph (codae_train_step_graph): for launch-bound shapes
         (small batches); single process only - the bucketed data-parallel step is not captured.
         activation: what follows every hidden Linear, as the model classes take it (a factory called as activation(True),
@@ -410,7 +410,11 @@ class HipEmbeddingTrainer:
         hidden_dropout: a codae.tool.HiddenDropout: the output of every hidden Linear (after its activation: none, ReLU or
         LeakyReLU) is multiplied by 0 with probability p or by 1 / (1 - p), in every step form, keyed by the dataset row, the
         optimizer step and the layer; the loss and epoch_sums() of a training step are those of the dropped network;
-        eval_batch and complete never drop.  None (or p = 0) = off."""
+        eval_batch and complete never drop.  None (or p = 0) = off.
+        criterion: a codae.tool.ReconstructionLoss: the training loss is L1, SmoothL1, Huber or the per-slot cosine (optionally
+        with an MSE anchor) instead of the mean squared error, in every step form, weighted by loss_emphasis when that is on;
+        epoch_sums() stays the unweighted squared-error sums, eval_batch and complete never see it.  None (or the default
+        ReconstructionLoss()) = the mean squared error, exactly as before."""
         from .hip.engine import DaeEngine
         fit_host_threads()      # the loop that feeds this trainer must not get its container CPU-throttled (codae/hostcpu.py)
         self.device = torch.device(device)
@@ -426,6 +430,8 @@ class HipEmbeddingTrainer:
             self.set_loss_emphasis(loss_emphasis)
         if hidden_dropout is not None:
             self.set_hidden_dropout(hidden_dropout)
+        if criterion is not None:
+            self.set_criterion(criterion)
         self.dp = DataParallel(self.engine, n_buckets=n_buckets, sharded=sharded_update, native=native_dp) if distributed else None
         self.world = self.dp.world if self.dp else 1
         self.use_graph = bool(use_graph) and self.dp is None
@@ -443,6 +449,16 @@ class HipEmbeddingTrainer:
         if emphasis is not None and getattr(emphasis, "slot_weight", None) is not None and (self.n_slots or self.mask_table is not None):
             S = self._slots()[0]
         self.engine.set_loss_emphasis(emphasis, n_slots=S)
+
+    def set_criterion(self, criterion):
+        """DaeEngine.set_recon_loss with the trainer's number of slots (n_slots, else read off the mask table) for slot_cosine."""
+        S = None
+        if criterion is not None and getattr(criterion, "kind", None) == "slot_cosine":
+            if not self.n_slots and self.mask_table is None:
+                raise HipError("criterion slot_cosine: the trainer has neither n_slots nor a mask table to read the slots from; "
+                               "construct it with n_slots")
+            S = self._slots()[0]
+        self.engine.set_recon_loss(criterion, n_slots=S)
 
     def set_hidden_dropout(self, dropout):
         """DaeEngine.set_hidden_dropout: a codae.tool.HiddenDropout, or None to switch it off."""

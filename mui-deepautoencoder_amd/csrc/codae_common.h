@@ -436,6 +436,14 @@ int launch_emph_loss(const codae_batch* b, const codae_noise* noise, int32_t ste
                      const float* y, void* dy, int dy_bf16, int64_t dy_ld, float inv_n, float* colsum_part, double* parts,
                      hipStream_t s);
 int launch_finish_emph_loss(double* scalars, double inv_n, hipStream_t s, const double* parts, int n_parts);
+// A training criterion other than the MSE (codae_recon_loss, include/codae_hip.h; recon_loss.hip): launch_emph_loss's block shape,
+// arguments and outputs, `emph` may be null (all weights 1); parts[.][0] is the criterion's sum, so launch_finish_emph_loss
+// finishes it.  check_recon_loss: CODAE_E_INVALID / CODAE_E_UNSUPPORTED as codae_set_recon_loss documents (io <= 0: not checked
+// against n_slots).
+int check_recon_loss(const codae_recon_loss* loss, int io);
+int launch_recon_loss(const codae_batch* b, const codae_noise* noise, int32_t step, const double* step_dev, const codae_emphasis* emph,
+                      const codae_recon_loss* loss, const float* y, void* dy, int dy_bf16, int64_t dy_ld, float inv_n, float* colsum_part,
+                      double* parts, hipStream_t s);
 // Hidden dropout (codae_dropout, include/codae_hip.h; dropout.hip): a <- a * f in place on rows < B, columns < width of a [B][ld]
 // matrix (fp32 or bf16), f from the Philox words of counter (column / 4, dataset row, step, 1 + layer); step_dev as
 // launch_gather_noise.  The backward form takes dropout_blocks(B) blocks, each leaving one row of colsum_part [blocks][width]

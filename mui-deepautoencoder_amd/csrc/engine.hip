@@ -99,6 +99,8 @@ struct codae_engine {
     codae_noise noise{};             // input noise of the training steps (codae_set_input_noise); kind NONE = off
     codae_emphasis emph{};           // loss emphasis of the training steps (codae_set_loss_emphasis), meaningful while emph_on
     bool emph_on = false;
+    codae_recon_loss recon{};        // training criterion (codae_set_recon_loss), meaningful while recon_on: a kind other than MSE
+    bool recon_on = false;
     // hidden dropout of the training steps (codae_set_hidden_dropout): p[l] of layer l's output, all zero = off.  The backward entry
     // points take no batch, so a training forward leaves what they need behind: drop_live = the activations in the workspace were
     // dropped (an evaluation or drop-in forward clears it), with the batch rows, row indices and step of that forward
@@ -126,7 +128,7 @@ struct codae_engine {
     // codae_train_step_graph: the captured step and what it was captured for
     hipGraphExec_t graph_exec = nullptr;
     bool capturing = false;          // inside stream capture: device-side Adam step, everything joined at the end
-    struct GraphKey { codae_batch batch; codae_hyper hyper; codae_buffers bufs; codae_noise noise; codae_emphasis emph; bool emph_on; DropCfg drop; } graph_key{};
+    struct GraphKey { codae_batch batch; codae_hyper hyper; codae_buffers bufs; codae_noise noise; codae_emphasis emph; bool emph_on; DropCfg drop; codae_recon_loss recon; } graph_key{};
     std::vector<hipEvent_t> prof_start, prof_stop;
     std::vector<int> prof_kind;
     std::vector<int> prof_count;    // launches covered by the record (a GroupScope spans several)
@@ -350,8 +352,8 @@ constexpr int CHAIN_MAX_ROWS = 2048;
 
 bool chain_eligible(codae_engine* e, const codae_buffers* b, int B) {
     // (the chain kernel fuses the plain gather and the unweighted loss and keeps the activations to itself: a noised input, an
-    //  emphasised loss or hidden dropout takes the per-layer launches)
-    return e->chain_ok && e->noise.kind == CODAE_NOISE_NONE && !e->emph_on && !e->drop.on && b->shadow_wt != nullptr && e->rows_for(B) <= CHAIN_MAX_ROWS;
+    //  emphasised loss, another criterion or hidden dropout takes the per-layer launches)
+    return e->chain_ok && e->noise.kind == CODAE_NOISE_NONE && !e->emph_on && !e->recon_on && !e->drop.on && b->shadow_wt != nullptr && e->rows_for(B) <= CHAIN_MAX_ROWS;
 }
 
 // gather + forward chain + loss (+ data-gradient chain) of a narrow stack: one launch; then the loss finish
@@ -1120,8 +1122,8 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
     h->drop_live = hyper != nullptr && h->drop.on;
     if (h->drop_live) { h->drop_B = B; h->drop_rows = batch->row_idx; h->drop_step = hyper->step; }
     // bf16 training step: the loss is folded into the last forward GEMM's epilogue (y never stored)
-    // (not with loss emphasis: its weights live in a stand-alone kernel, below)
-    const bool fuse_loss = bf && hyper != nullptr && out_y == nullptr && !h->cfg.no_fused_loss && !h->emph_on;
+    // (not with loss emphasis or a criterion other than the MSE: those live in stand-alone kernels, below)
+    const bool fuse_loss = bf && hyper != nullptr && out_y == nullptr && !h->cfg.no_fused_loss && !h->emph_on && !h->recon_on;
     const bool fold_finish = fuse_loss && fold != nullptr && !h->cfg.no_folded_loss_finish;
     {
         ProfScope prof(h, CODAE_K_GATHER, s);
@@ -1181,6 +1183,19 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
     if (hyper != nullptr) {
         rc = zero_pad_rows(h, dact_ptr(h, b, L - 1), B, rows, h->out_ld[L - 1], s);
         if (rc) return rc;
+        if (h->recon_on) {     // (with or without emphasis: the criterion's kernels form the weight themselves)
+            const double inv_n = loss_inv_n(hyper, batch);
+            {
+                ProfScope prof(h, CODAE_K_LOSS, s);
+                rc = launch_recon_loss(batch, &h->noise, hyper->step, h->capturing ? b->scalars + CODAE_S_ADAM_STEP : nullptr,
+                                       h->emph_on ? &h->emph : nullptr, &h->recon, y, dact_ptr(h, b, L - 1), bf, h->out_ld[L - 1], (float)inv_n,
+                                       part_ptr(h, b, L - 1), loss_parts_ptr(h, b), s);
+            }
+            if (rc) return rc;
+            h->parts_pending[L - 1] = mse_loss_colsum_rows(B);
+            h->norm_scalars_zero = true;
+            return launch_finish_emph_loss(b->scalars, inv_n, s, loss_parts_ptr(h, b), mse_loss_colsum_rows(B));
+        }
         if (h->emph_on) {
             const double inv_n = loss_inv_n(hyper, batch);
             {
@@ -1235,6 +1250,22 @@ int codae_set_loss_emphasis(codae_handle h, const codae_emphasis* emphasis) {
     if (on) { e.alpha = emphasis->alpha; e.beta = emphasis->beta; e.col_weight = emphasis->col_weight; }
     h->emph = e;
     h->emph_on = on;
+    return CODAE_OK;
+}
+
+int codae_set_recon_loss(codae_handle h, const codae_recon_loss* loss) {
+    CODAE_REQUIRE(h != nullptr, "codae_set_recon_loss: null handle");
+    int rc = check_recon_loss(loss, h->out[h->L - 1]);
+    if (rc) return rc;
+    codae_recon_loss r{};                // (built field by field: the graph key compares bytes)
+    const bool on = loss != nullptr && loss->kind != CODAE_LOSS_MSE;
+    if (on) {
+        r.kind = loss->kind;
+        if (loss->kind == CODAE_LOSS_SMOOTH_L1 || loss->kind == CODAE_LOSS_HUBER) r.param = loss->param;
+        if (loss->kind == CODAE_LOSS_SLOT_COSINE) { r.mse_weight = loss->mse_weight; r.n_slots = loss->n_slots; }
+    }
+    h->recon = r;
+    h->recon_on = on;
     return CODAE_OK;
 }
 
@@ -1438,7 +1469,7 @@ int codae_train_step_graph(codae_handle h, const codae_buffers* b, const codae_b
                        !same_bytes(&h->graph_key.hyper, &hk, sizeof(hk)) || !same_bytes(&h->graph_key.bufs, b, sizeof(*b)) ||
                        !same_bytes(&h->graph_key.noise, &h->noise, sizeof(h->noise)) ||
                        !same_bytes(&h->graph_key.emph, &h->emph, sizeof(h->emph)) || h->graph_key.emph_on != h->emph_on ||
-                       !same_bytes(&h->graph_key.drop, &h->drop, sizeof(h->drop));
+                       !same_bytes(&h->graph_key.drop, &h->drop, sizeof(h->drop)) || !same_bytes(&h->graph_key.recon, &h->recon, sizeof(h->recon));
     if (fresh) {
         if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
         int rc = check_common(h, b, batch->B);
@@ -1468,7 +1499,7 @@ int codae_train_step_graph(codae_handle h, const codae_buffers* b, const codae_b
             return CODAE_E_HIP;
         }
         h->graph_key.batch = *batch; h->graph_key.hyper = hk; h->graph_key.bufs = *b; h->graph_key.noise = h->noise; h->graph_key.emph = h->emph; h->graph_key.emph_on = h->emph_on;
-        h->graph_key.drop = h->drop;
+        h->graph_key.drop = h->drop; h->graph_key.recon = h->recon;
     }
     int rc = launch_set_scalar(b->scalars + CODAE_S_ADAM_STEP, (double)hyper->step, s);
     if (rc) return rc;

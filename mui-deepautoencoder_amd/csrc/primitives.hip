@@ -69,6 +69,14 @@ int codae_emph_loss(const codae_batch* batch, const codae_noise* noise, int32_t 
 
 int codae_emph_loss_blocks(int32_t B) { return B > 0 ? mse_loss_colsum_rows(B) : 0; }
 
+int codae_recon_loss_fwd_bwd(const codae_batch* batch, const codae_noise* noise, int32_t step, const codae_emphasis* emphasis,
+                             const codae_recon_loss* loss, const float* y, void* dy, int32_t dy_bf16, int64_t dy_ld, float inv_n,
+                             float* colsum_part, double* parts, void* stream) {
+    return launch_recon_loss(batch, noise, step, nullptr, emphasis, loss, y, dy, dy_bf16, dy_ld, inv_n, colsum_part, parts, (hipStream_t)stream);
+}
+
+int codae_recon_loss_blocks(int32_t B) { return B > 0 ? mse_loss_colsum_rows(B) : 0; }
+
 int codae_dropout_fwd(void* a, int32_t bf16, int64_t ld, int32_t B, int32_t width, const int32_t* row_idx, int32_t layer, int32_t step,
                       float p, uint64_t seed, void* stream) {
     return launch_dropout_fwd(a, bf16, ld, B, width, row_idx, layer, step, nullptr, p, seed, (hipStream_t)stream);

@@ -116,13 +116,17 @@ def main():
     # hidden Linear of the training steps (validation never drops)
     from codae.tool.dropout import hidden_dropout_from_config
     hidden_dropout = hidden_dropout_from_config(config.get("HIP", {}).get("HIDDEN_DROPOUT"))
+    # HIP: CRITERION: {KIND: mse | l1 | smooth_l1 | huber | slot_cosine, BETA: .., DELTA: .., MSE_WEIGHT: ..} (build-only key): the
+    # training loss instead of the mean squared error (the monitors stay squared-error sums; validation never sees it)
+    from codae.tool.recon_loss import recon_loss_from_config
+    criterion = recon_loss_from_config(config.get("HIP", {}).get("CRITERION"))
 
     def build(prec):
         return HipEmbeddingTrainer(enc + dec, dataset.data, corrupter.mask_table_u8, corrupter.mask_to_use_i32,
                                    mc["LEARNING_RATE"], mc["WEIGHT_DECAY"], clip=1.0 if mc["TRUNK_GRAD"] else 0.0,
                                    max_batch=mc["BATCH_SIZE"], precision=prec, device=device, distributed=world > 1,
                                    activation=activation, input_noise=input_noise, loss_emphasis=loss_emphasis,
-                                   hidden_dropout=hidden_dropout)
+                                   hidden_dropout=hidden_dropout, criterion=criterion)
     try:
         trainer = build(precision)
     except HipError as e:
