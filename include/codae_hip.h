@@ -52,6 +52,8 @@ extern "C" {
  *      CODAE_K_COUNT 11 (new entries only; no layout change of an existing struct)
  *      (still 11) + CODAE_LOSS_*, CODAE_COS_EPS, codae_recon_loss, codae_set_recon_loss, codae_recon_loss_fwd_bwd,
  *      codae_recon_loss_blocks: new entries only, no layout or enum change, the new kernels are booked under CODAE_K_LOSS
+ *      (still 11) + codae_slot_contrast, codae_set_slot_contrast, codae_slot_contrast_ws_bytes, codae_slot_contrast_prepare,
+ *      codae_slot_contrast_fwd_bwd, codae_slot_contrast_blocks: new entries only, no layout or enum change, booked under CODAE_K_LOSS
  * The binding must refuse a library whose codae_abi_version() differs and must check its own struct sizes against
  * codae_struct_sizes() at load (mui-deepautoencoder_amd/codae/hip/__init__.py does both). */
 #define CODAE_ABI_VERSION 11
@@ -192,6 +194,49 @@ typedef struct {
     float mse_weight;   /* SLOT_COSINE only: finite, >= 0; must be 0 for every other kind */
     int32_t n_slots;    /* SLOT_COSINE only: 1 <= n_slots <= 128, dividing io */
 } codae_recon_loss;
+
+/* Slot contrast: a sampled softmax (InfoNCE) over the true item of a slot and K negatives sampled from the same inventory, an
+ * ADDITIONAL term of the TRAINING loss on top of whichever criterion is set (MSE included).  The stack is judged on a ranking by
+ * cosine; the criterion pulls a reconstruction towards its own item, this term pushes it away from the other items of the slot.
+ * Per batch row b and slot s (E columns, io = S E): x = the clean target slot, y = the output slot, eps = CODAE_COS_EPS, rows = the
+ * global batch exactly as the criterion defines it, W(b,s) = the mean emphasis weight over the slot's columns (slot_cosine's W; 1
+ * without emphasis).  Hats are unit vectors, v^ = v / max(|v|, eps).
+ * Candidates belong to step t and slot s and are shared by every row and every rank.  For k in 0 .. K - 1:
+ *   r       word k % 4 of Philox4x32-10 (constants of "Input noise"), key = (seed & 0xffffffff, seed >> 32), counter =
+ *           (k / 4, s, t, 256): the fourth word keeps the stream apart from input noise (0) and dropout (1 + layer <= 255)
+ *   j       ((uint64) r * P) >> 32, P = n_pool, or n_rows when pool is NULL;  row_k = pool ? pool[j] : j
+ *   c_k     slot s of data[row_k], the clean dataset row - never noised, never masked.  Drawing is with replacement: a candidate
+ *           drawn twice counts twice.  t = the 1-based Adam step (read from scalars[CODAE_S_ADAM_STEP] under graph replay)
+ * Accidental hits: candidate k is left out for pair (b, s) iff item_id[s][row_k] == item_id[s][row_b] (item_id NULL: iff
+ *   row_k == row_b), row_b = the dataset row of batch row b (row_idx[b], or b when row_idx is NULL).
+ * Loss of a pair:
+ *   z_0 = (x^ . y^) / tau,  z_k = (c_k^ . y^) / tau over the kept k
+ *   l   = logsumexp(z_0, z_kept) - z_0,  p_j = softmax(z_0, z_kept)
+ *   g   = sum_kept p_k c_k^ - (1 - p_0) x^
+ *   dl/dy = [|y| > eps] (g - (g . y^) y^) / (tau |y|)
+ *   a target slot with |x| <= eps has no positive: the pair contributes 0 to the loss and to the gradient; a pair whose candidates
+ *   are all left out has l = 0 and a zero gradient by the formulas themselves.
+ * Total: L = L_criterion + weight sum_{b,s} W l / (rows S); dL/dy is the sum of the two gradients; CODAE_S_LAST_LOSS is the total;
+ *   CODAE_S_SQ_FULL / CODAE_S_SQ_PARTIAL stay the unweighted squared-error sums; evaluation never sees the term.
+ * NaN: a NaN or Inf anywhere in a y slot makes that pair's dy and L NaN, under weight W = 0 and for a zero target too; no other pair
+ *   is affected.  (A finite slot whose squares overflow fp32, |y| > 1.8e19, counts as Inf.)
+ * Determinism: the order in which a pair's sums over E and over K are added depends on E and K alone - not on B, nor on the row's
+ *   position in the batch or in a tile: a data-parallel shard's dy rows are the bits of the same rows of the global batch.
+ * Operand precision follows the engine: bf16 unit vectors into v_mfma_f32_16x16x32_bf16 (the p_k rounded to bf16 for the weighted
+ *   sum), or fp32 into v_mfma_f32_16x16x4_f32; fp32 accumulation and fp32 softmax either way; z_0 always in fp32. */
+typedef struct {
+    int32_t n_slots;         /* S: 1 <= n_slots <= 128, dividing io; E = io / S <= 1024 */
+    int32_t n_neg;           /* K: 1 <= n_neg <= 4096 */
+    float tau;               /* finite, >= 0.01 */
+    float weight;            /* finite, >= 0; 0 = off */
+    uint64_t seed;
+    int32_t n_rows;          /* rows of batch->data */
+    int32_t n_pool;          /* entries of pool; 0 (or n_rows) when pool is NULL */
+    int64_t ws_bytes;        /* bytes behind ws: >= codae_slot_contrast_ws_bytes(S, K, E, bf16 engine) */
+    const int32_t* pool;     /* device, [n_pool] rows of data to draw from, or NULL = every row */
+    const int32_t* item_id;  /* device, [S][n_rows] item identity of every dataset row per slot, or NULL = the row itself */
+    void* ws;                /* device, 16-byte aligned work space; all three borrowed until the setting is replaced */
+} codae_slot_contrast;
 
 /* Hidden dropout (Srivastava et al. 2014, inverted form as torch.nn.Dropout): the TRAINING step multiplies the output of layer l,
  * 0 <= l <= n_layers - 2 - what layer l + 1 reads and the engine keeps as act[l + 1] - by a random factor.  The last layer's
@@ -483,6 +528,15 @@ int codae_set_recon_loss(codae_handle h, const codae_recon_loss* loss);
  * The backward entry points take no batch: a training forward records batch->row_idx and hyper->step in the handle, so
  * batch->row_idx must stay valid until the backward of that step has been issued. */
 int codae_set_hidden_dropout(codae_handle h, const codae_dropout* d);
+/* Slot contrast of every training step that follows (the step forms codae_set_input_noise lists; a change re-captures the graph;
+ * under replay the step index is read from scalars[CODAE_S_ADAM_STEP]).  NULL or weight == 0 switches it off: the engine then runs
+ * exactly what it ran before, bit for bit, codae_step_path included.  CODAE_E_INVALID for n_neg outside [1, 4096], a tau that is
+ * not finite or < 0.01, a negative or non-finite weight, n_slots < 1, > 128 or not dividing io, n_rows < 1, a pool without entries,
+ * a ws that is NULL, misaligned or smaller than codae_slot_contrast_ws_bytes says; CODAE_E_UNSUPPORTED for E > 1024 (the message
+ * names E).  On any error nothing is launched and the previous setting stays.  While it is on: the criterion runs as its
+ * stand-alone kernel (no fused-loss epilogue), followed by a prepare launch and the contrast launch (both booked under
+ * CODAE_K_LOSS, after the criterion's record) and a one-thread finish (not timed, like the criterion's), and the stack stays off the persistent chain kernel (codae_step_path reports 0). */
+int codae_set_slot_contrast(codae_handle h, const codae_slot_contrast* contrast);
 /* validation body (:245-258): forward + metric sums only */
 int codae_eval_step(codae_handle h, const codae_buffers* bufs, const codae_batch* batch, float* out_y,
                     void* stream);
@@ -543,6 +597,24 @@ int codae_recon_loss_fwd_bwd(const codae_batch* batch, const codae_noise* noise,
                              const codae_recon_loss* loss, const float* y, void* dy, int32_t dy_bf16, int64_t dy_ld, float inv_n,
                              float* colsum_part, double* parts, void* stream);
 int codae_recon_loss_blocks(int32_t B);
+/* Slot contrast on its own (the launchers the engine uses; "Slot contrast" above has the definition).
+ * codae_slot_contrast_ws_bytes: bytes of codae_slot_contrast.ws for S slots, K negatives, E columns per slot, bf16 != 0 for the bf16
+ * engine (-1 out of range): the normalised candidates in the operand type, once [K][E] and once [E][K], K and E padded to
+ * multiples of 32, and one int32 id per candidate.  Nothing grows with the batch.
+ * codae_slot_contrast_prepare: samples, gathers and normalises the S x K candidates of `step` from data [n_rows][io] into ws.
+ * codae_slot_contrast_fwd_bwd: dy is in and out - it holds what the criterion's kernel left and receives round(dy + scale W dl/dy),
+ * the sum formed in fp32 and rounded once to the stored type, scale = weight / (rows S); dy_bf16 also picks the operand type of
+ * the two products and must match what prepare was given.  Columns >= io and rows >= B are never written.  One block per 32
+ * batch rows - codae_slot_contrast_blocks(B) of them -, each leaving one row of colsum_part [blocks][io] (column sums of the FINAL
+ * stored values, widened to fp32, added in a fixed order; may be NULL) and one double of parts [blocks]: sum W l over its rows.
+ * `noise` / `step` / `emphasis` say which elements carry which emphasis weight, as for codae_recon_loss_fwd_bwd.  No atomics: the
+ * same inputs give the same bits.  On an error nothing is launched and nothing is written. */
+int64_t codae_slot_contrast_ws_bytes(int32_t n_slots, int32_t n_neg, int32_t E, int32_t bf16);
+int codae_slot_contrast_prepare(const float* data, int32_t io, const codae_slot_contrast* contrast, int32_t step, int32_t bf16, void* stream);
+int codae_slot_contrast_fwd_bwd(const codae_batch* batch, const codae_noise* noise, int32_t step, const codae_emphasis* emphasis,
+                                const codae_slot_contrast* contrast, const float* y, void* dy, int32_t dy_bf16, int64_t dy_ld, float scale,
+                                float* colsum_part, double* parts, void* stream);
+int codae_slot_contrast_blocks(int32_t B);
 /* The two hidden-dropout kernels on their own (the launchers the engine uses; "Hidden dropout" above has the definition): in
  * place on rows < B and columns < width of a [B][ld] matrix, fp32 or (bf16 != 0) bf16; pad columns and pad rows are never
  * written.  16-byte accesses where the base address, ld and width allow (bf16 x 8, fp32 x 4), element accesses otherwise.

@@ -80,6 +80,12 @@ class ReconLoss(C.Structure):
     _fields_ = [("kind", C.c_int32), ("param", C.c_float), ("mse_weight", C.c_float), ("n_slots", C.c_int32)]
 
 
+class SlotContrast(C.Structure):
+    _fields_ = [("n_slots", C.c_int32), ("n_neg", C.c_int32), ("tau", C.c_float), ("weight", C.c_float), ("seed", C.c_uint64),
+                ("n_rows", C.c_int32), ("n_pool", C.c_int32), ("ws_bytes", C.c_int64), ("pool", C.c_void_p),
+                ("item_id", C.c_void_p), ("ws", C.c_void_p)]
+
+
 class Dropout(C.Structure):
     _fields_ = [("p", C.POINTER(C.c_float)), ("n", C.c_int32), ("seed", C.c_uint64)]
 
@@ -115,6 +121,12 @@ PROTOTYPES = {
     "codae_set_loss_emphasis": (C.c_int, [_P, C.POINTER(Emphasis)]),
     "codae_set_recon_loss": (C.c_int, [_P, C.POINTER(ReconLoss)]),
     "codae_set_hidden_dropout": (C.c_int, [_P, C.POINTER(Dropout)]),
+    "codae_set_slot_contrast": (C.c_int, [_P, C.POINTER(SlotContrast)]),
+    "codae_slot_contrast_ws_bytes": (_I64, [_I32, _I32, _I32, _I32]),
+    "codae_slot_contrast_prepare": (C.c_int, [_P, _I32, C.POINTER(SlotContrast), _I32, _I32, _P]),
+    "codae_slot_contrast_fwd_bwd": (C.c_int, [C.POINTER(Batch), C.POINTER(Noise), _I32, C.POINTER(Emphasis), C.POINTER(SlotContrast), _P, _P,
+                                              _I32, _I64, _F, _P, _P, _P]),
+    "codae_slot_contrast_blocks": (C.c_int, [_I32]),
     "codae_dropout_fwd": (C.c_int, [_P, _I32, _I64, _I32, _I32, _P, _I32, _I32, _F, C.c_uint64, _P]),
     "codae_dropout_bwd": (C.c_int, [_P, _I32, _I64, _I32, _I32, _P, _I32, _I32, _F, C.c_uint64, _P, _P]),
     "codae_dropout_blocks": (C.c_int, [_I32]),

@@ -88,6 +88,8 @@ class DaeEngine:
         self._emph_weights = None     # the device tensor codae_emphasis.col_weight borrows
         self.hidden_dropout = None
         self.recon_loss = None
+        self.slot_contrast = None
+        self._contrast_pins = None    # the device tensors codae_slot_contrast borrows (pool, item ids, work space)
         self.step_count = 0
         self.generation = 0   # bumped by every forward: guards stale backward calls
 
@@ -255,6 +257,44 @@ class DaeEngine:
 
     def _set_recon_struct(self, st):
         check(self._lib.codae_set_recon_loss(self._h, None if st is None else C.byref(st)))
+
+    def set_slot_contrast(self, contrast, data=None, n_slots=None):
+        """contrast: a codae.tool.SlotContrast, or None to switch it off.  Every training step form that follows adds
+        weight * sum W l / (rows S) to the criterion's loss (include/codae_hip.h, "Slot contrast"): a softmax over the true item of
+        each slot and `negatives` rows sampled per step from `data` (the resident dataset the batches are gathered from, [N, io]
+        fp32 on this device); epoch_sums() stays the unweighted squared-error sums and eval steps never see it; with graph=True the
+        next step re-captures.  While it is on, step_path() is 'layers'.  weight = 0 = off: the engine runs exactly what it ran
+        before.  On a refusal (HipError) the previous setting stays."""
+        if contrast is not None and not hasattr(contrast, "candidate_rows"):
+            raise HipError("set_slot_contrast: expected a codae.tool.SlotContrast or None, got %r" % (contrast,))
+        if contrast is None or contrast.is_default:
+            self._set_contrast_struct(None)
+            self.slot_contrast, self._contrast_pins = contrast, None
+            return
+        if data is None or data.dtype != torch.float32 or not data.is_contiguous() or data.device != self.device or data.dim() != 2:
+            raise HipError("set_slot_contrast: data must be the contiguous fp32 [N, io] dataset on %s" % self.device)
+        io = self.schedule[-1][1]
+        if int(data.shape[1]) != io:
+            raise HipError("set_slot_contrast: data has %d columns, the model %d" % (int(data.shape[1]), io))
+        S = contrast._check_slots(n_slots, io)
+        N = int(data.shape[0])
+        contrast.check_rows(N)
+        with torch.cuda.device(self.device):
+            pool = None if contrast.candidates is None else torch.from_numpy(contrast.candidates).to(self.device)
+            ids = None
+            if contrast.distinct:
+                from ..tool.contrast import item_ids
+                ids = item_ids(data, S).to(torch.int32).contiguous()
+            need = int(self._lib.codae_slot_contrast_ws_bytes(S, contrast.negatives, io // S, int(self.precision == PREC_BF16)))
+            if need < 0:
+                raise HipError("set_slot_contrast: no work space for S = %d, K = %d, E = %d" % (S, contrast.negatives, io // S))
+            ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._set_contrast_struct(contrast.as_struct(S, N, pool, ids, ws))
+        self.slot_contrast, self._contrast_pins = contrast, (data, pool, ids, ws)
+
+    def _set_contrast_struct(self, st):
+        with torch.cuda.device(self.device):      # (the setter raises a per-device kernel attribute: this engine's device)
+            check(self._lib.codae_set_slot_contrast(self._h, None if st is None else C.byref(st)))
 
     def set_hidden_dropout(self, dropout):
         """dropout: a codae.tool.HiddenDropout, or None to switch it off.  Every training step form that follows multiplies the

@@ -394,7 +394,7 @@ class HipEmbeddingTrainer:
     def __init__(self, schedule, data, mask_table_u8, mask_to_use_i32, lr, weight_decay, clip=1.0,
                  max_batch=8192, precision="bf16", device="cuda:0", distributed=False, n_buckets=None, use_graph=False,
                  sharded_update=False, native_dp=False, activation=None, n_slots=None, input_noise=None,
-                 loss_emphasis=None, hidden_dropout=None, criterion=None):
+                 loss_emphasis=None, hidden_dropout=None, criterion=None, contrast=None):
         """use_graph: replay the fused step from a hipGraph (codae_train_step_graph): for launch-bound shapes
         (small batches); single process only - the bucketed data-parallel step is not captured.
         activation: what follows every hidden Linear, as the model classes take it (a factory called as activation(True),
@@ -414,7 +414,11 @@ class HipEmbeddingTrainer:
         criterion: a codae.tool.ReconstructionLoss: the training loss is L1, SmoothL1, Huber or the per-slot cosine (optionally
         with an MSE anchor) instead of the mean squared error, in every step form, weighted by loss_emphasis when that is on;
         epoch_sums() stays the unweighted squared-error sums, eval_batch and complete never see it.  None (or the default
-        ReconstructionLoss()) = the mean squared error, exactly as before."""
+        ReconstructionLoss()) = the mean squared error, exactly as before.
+        contrast: a codae.tool.SlotContrast: a sampled softmax over the true item of each slot and negatives drawn per step from
+        the resident dataset, added to the criterion's loss in every step form (candidates keyed by the optimizer step and the
+        slot, shared by all ranks); epoch_sums(), eval_batch and complete never see it.  None (or weight 0) = off, exactly as
+        before."""
         from .hip.engine import DaeEngine
         fit_host_threads()      # the loop that feeds this trainer must not get its container CPU-throttled (codae/hostcpu.py)
         self.device = torch.device(device)
@@ -432,6 +436,8 @@ class HipEmbeddingTrainer:
             self.set_hidden_dropout(hidden_dropout)
         if criterion is not None:
             self.set_criterion(criterion)
+        if contrast is not None:
+            self.set_contrast(contrast)
         self.dp = DataParallel(self.engine, n_buckets=n_buckets, sharded=sharded_update, native=native_dp) if distributed else None
         self.world = self.dp.world if self.dp else 1
         self.use_graph = bool(use_graph) and self.dp is None
@@ -459,6 +465,17 @@ class HipEmbeddingTrainer:
                                "construct it with n_slots")
             S = self._slots()[0]
         self.engine.set_recon_loss(criterion, n_slots=S)
+
+    def set_contrast(self, contrast):
+        """DaeEngine.set_slot_contrast on the resident dataset with the trainer's number of slots (n_slots, else read off the mask
+        table); None switches it off."""
+        S = None
+        if contrast is not None and not getattr(contrast, "is_default", True):
+            if not self.n_slots and self.mask_table is None:
+                raise HipError("slot contrast: the trainer has neither n_slots nor a mask table to read the slots from; "
+                               "construct it with n_slots")
+            S = self._slots()[0]
+        self.engine.set_slot_contrast(contrast, self.data, n_slots=S)
 
     def set_hidden_dropout(self, dropout):
         """DaeEngine.set_hidden_dropout: a codae.tool.HiddenDropout, or None to switch it off."""

@@ -444,6 +444,21 @@ int check_recon_loss(const codae_recon_loss* loss, int io);
 int launch_recon_loss(const codae_batch* b, const codae_noise* noise, int32_t step, const double* step_dev, const codae_emphasis* emph,
                       const codae_recon_loss* loss, const float* y, void* dy, int dy_bf16, int64_t dy_ld, float inv_n, float* colsum_part,
                       double* parts, hipStream_t s);
+// Sampled-softmax slot contrast (codae_slot_contrast, include/codae_hip.h; slot_contrast.hip): an additional term on top of the
+// criterion.  prepare fills the work space with the step's S x K normalised candidates; launch_slot_contrast adds the term's
+// gradient to the dy the criterion's kernel left (operand type of the products = dy's type), leaves slot_contrast_blocks(B) rows of
+// colsum_part (column sums of the final dy) and as many doubles of parts (sum W l); the finish adds scale * sum parts to LAST_LOSS.
+// check_slot_contrast: CODAE_E_INVALID / CODAE_E_UNSUPPORTED as codae_set_slot_contrast documents (io <= 0: the struct's own ranges only).
+int check_slot_contrast(const codae_slot_contrast* c, int io, int bf16);
+int64_t slot_contrast_ws_bytes(int S, int K, int E, int bf16);
+inline int slot_contrast_blocks(int B) { return (B + 31) / 32; }
+int slot_contrast_warm();     // one-time kernel attributes, outside any stream capture
+int launch_slot_contrast_prepare(const float* data, int io, const codae_slot_contrast* c, int32_t step, const double* step_dev, int bf16,
+                                 hipStream_t s);
+int launch_slot_contrast(const codae_batch* b, const codae_noise* noise, int32_t step, const double* step_dev, const codae_emphasis* emph,
+                         const codae_slot_contrast* c, const float* y, void* dy, int dy_bf16, int64_t dy_ld, float scale,
+                         float* colsum_part, double* parts, hipStream_t s);
+int launch_slot_contrast_finish(double* scalars, double scale, const double* parts, int n_parts, hipStream_t s);
 // Hidden dropout (codae_dropout, include/codae_hip.h; dropout.hip): a <- a * f in place on rows < B, columns < width of a [B][ld]
 // matrix (fp32 or bf16), f from the Philox words of counter (column / 4, dataset row, step, 1 + layer); step_dev as
 // launch_gather_noise.  The backward form takes dropout_blocks(B) blocks, each leaving one row of colsum_part [blocks][width]

@@ -101,6 +101,8 @@ struct codae_engine {
     bool emph_on = false;
     codae_recon_loss recon{};        // training criterion (codae_set_recon_loss), meaningful while recon_on: a kind other than MSE
     bool recon_on = false;
+    codae_slot_contrast contrast{};  // slot contrast on top of the criterion (codae_set_slot_contrast); all zero = off
+    bool contrast_on = false;
     // hidden dropout of the training steps (codae_set_hidden_dropout): p[l] of layer l's output, all zero = off.  The backward entry
     // points take no batch, so a training forward leaves what they need behind: drop_live = the activations in the workspace were
     // dropped (an evaluation or drop-in forward clears it), with the batch rows, row indices and step of that forward
@@ -128,7 +130,7 @@ struct codae_engine {
     // codae_train_step_graph: the captured step and what it was captured for
     hipGraphExec_t graph_exec = nullptr;
     bool capturing = false;          // inside stream capture: device-side Adam step, everything joined at the end
-    struct GraphKey { codae_batch batch; codae_hyper hyper; codae_buffers bufs; codae_noise noise; codae_emphasis emph; bool emph_on; DropCfg drop; codae_recon_loss recon; } graph_key{};
+    struct GraphKey { codae_batch batch; codae_hyper hyper; codae_buffers bufs; codae_noise noise; codae_emphasis emph; bool emph_on; DropCfg drop; codae_recon_loss recon; codae_slot_contrast contrast; } graph_key{};
     std::vector<hipEvent_t> prof_start, prof_stop;
     std::vector<int> prof_kind;
     std::vector<int> prof_count;    // launches covered by the record (a GroupScope spans several)
@@ -353,7 +355,7 @@ constexpr int CHAIN_MAX_ROWS = 2048;
 bool chain_eligible(codae_engine* e, const codae_buffers* b, int B) {
     // (the chain kernel fuses the plain gather and the unweighted loss and keeps the activations to itself: a noised input, an
     //  emphasised loss, another criterion or hidden dropout takes the per-layer launches)
-    return e->chain_ok && e->noise.kind == CODAE_NOISE_NONE && !e->emph_on && !e->recon_on && !e->drop.on && b->shadow_wt != nullptr && e->rows_for(B) <= CHAIN_MAX_ROWS;
+    return e->chain_ok && e->noise.kind == CODAE_NOISE_NONE && !e->emph_on && !e->recon_on && !e->contrast_on && !e->drop.on && b->shadow_wt != nullptr && e->rows_for(B) <= CHAIN_MAX_ROWS;
 }
 
 // gather + forward chain + loss (+ data-gradient chain) of a narrow stack: one launch; then the loss finish
@@ -1100,6 +1102,36 @@ int codae_backward(codae_handle h, const codae_buffers* b, const float* dy, floa
     return backward_range(h, b, B, layer_lo, layer_hi, dx, false, false, s);
 }
 
+// The slot contrast behind the criterion's kernel and its finish (a no-op while it is off): prepare this step's candidates, add the
+// term's gradient to the dY the criterion left - its partial column-sum rows replace the criterion kernel's -, then add the term
+// to CODAE_S_LAST_LOSS.  The per-block sums reuse the criterion's rows, which its finish has read by then (same stream).
+static int run_slot_contrast(codae_handle h, const codae_buffers* b, const codae_batch* batch, const codae_hyper* hyper, const float* y,
+                             hipStream_t s) {
+    if (!h->contrast_on) return CODAE_OK;
+    const int L = h->L, B = batch->B;
+    const bool bf = h->prec == CODAE_PREC_BF16;
+    const double* step_dev = h->capturing ? b->scalars + CODAE_S_ADAM_STEP : nullptr;
+    const int blocks = slot_contrast_blocks(B);
+    CODAE_REQUIRE(blocks <= h->loss_part_cap && blocks <= (h->max_rows + 31) / 32,
+                  "slot contrast: %d row blocks exceed the partial-sum rows (%d)", blocks, h->loss_part_cap);
+    const double rows = hyper->loss_scale_rows > 0.f ? (double)hyper->loss_scale_rows : (double)B;
+    const double scale = (double)h->contrast.weight / (rows * (double)h->contrast.n_slots);
+    int rc;
+    {
+        ProfScope prof(h, CODAE_K_LOSS, s);
+        rc = launch_slot_contrast_prepare(batch->data, batch->io, &h->contrast, hyper->step, step_dev, bf, s);
+    }
+    if (rc) return rc;
+    {
+        ProfScope prof(h, CODAE_K_LOSS, s);
+        rc = launch_slot_contrast(batch, &h->noise, hyper->step, step_dev, h->emph_on ? &h->emph : nullptr, &h->contrast, y,
+                                  dact_ptr(h, b, L - 1), bf, h->out_ld[L - 1], (float)scale, part_ptr(h, b, L - 1), loss_parts_ptr(h, b), s);
+    }
+    if (rc) return rc;
+    h->parts_pending[L - 1] = blocks;
+    return launch_slot_contrast_finish(b->scalars, scale, loss_parts_ptr(h, b), blocks, s);
+}
+
 // fold != null (codae_train_step): when the loss is fused into the last forward GEMM, its finish - 5 us of a one-block launch
 // plus a launch boundary between the loss GEMM and the first data gradient - is not launched: *fold describes it for the bias-finish
 // launch that ends the backward (as the chain path does), and the gather's first block clears the norm accumulators instead.
@@ -1123,7 +1155,7 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
     if (h->drop_live) { h->drop_B = B; h->drop_rows = batch->row_idx; h->drop_step = hyper->step; }
     // bf16 training step: the loss is folded into the last forward GEMM's epilogue (y never stored)
     // (not with loss emphasis or a criterion other than the MSE: those live in stand-alone kernels, below)
-    const bool fuse_loss = bf && hyper != nullptr && out_y == nullptr && !h->cfg.no_fused_loss && !h->emph_on && !h->recon_on;
+    const bool fuse_loss = bf && hyper != nullptr && out_y == nullptr && !h->cfg.no_fused_loss && !h->emph_on && !h->recon_on && !h->contrast_on;
     const bool fold_finish = fuse_loss && fold != nullptr && !h->cfg.no_folded_loss_finish;
     {
         ProfScope prof(h, CODAE_K_GATHER, s);
@@ -1194,7 +1226,8 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
             if (rc) return rc;
             h->parts_pending[L - 1] = mse_loss_colsum_rows(B);
             h->norm_scalars_zero = true;
-            return launch_finish_emph_loss(b->scalars, inv_n, s, loss_parts_ptr(h, b), mse_loss_colsum_rows(B));
+            rc = launch_finish_emph_loss(b->scalars, inv_n, s, loss_parts_ptr(h, b), mse_loss_colsum_rows(B));
+            return rc ? rc : run_slot_contrast(h, b, batch, hyper, y, s);
         }
         if (h->emph_on) {
             const double inv_n = loss_inv_n(hyper, batch);
@@ -1206,7 +1239,8 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
             if (rc) return rc;
             h->parts_pending[L - 1] = mse_loss_colsum_rows(B);
             h->norm_scalars_zero = true;
-            return launch_finish_emph_loss(b->scalars, inv_n, s, loss_parts_ptr(h, b), mse_loss_colsum_rows(B));
+            rc = launch_finish_emph_loss(b->scalars, inv_n, s, loss_parts_ptr(h, b), mse_loss_colsum_rows(B));
+            return rc ? rc : run_slot_contrast(h, b, batch, hyper, y, s);
         }
         {
             ProfScope prof(h, CODAE_K_LOSS, s);
@@ -1216,7 +1250,8 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
         if (rc) return rc;
         h->parts_pending[L - 1] = mse_loss_colsum_rows(B);
         h->norm_scalars_zero = true;
-        return finish_loss(h, b, batch, mse_loss_colsum_rows(B), s);
+        rc = finish_loss(h, b, batch, mse_loss_colsum_rows(B), s);
+        return rc ? rc : run_slot_contrast(h, b, batch, hyper, y, s);
     }
     rc = launch_mse_loss(batch, y, nullptr, 0, 0.f, nullptr, loss_parts_ptr(h, b), 0, s);
     if (rc) return rc;
@@ -1266,6 +1301,24 @@ int codae_set_recon_loss(codae_handle h, const codae_recon_loss* loss) {
     }
     h->recon = r;
     h->recon_on = on;
+    return CODAE_OK;
+}
+
+int codae_set_slot_contrast(codae_handle h, const codae_slot_contrast* contrast) {
+    CODAE_REQUIRE(h != nullptr, "codae_set_slot_contrast: null handle");
+    int rc = check_slot_contrast(contrast, h->out[h->L - 1], h->prec == CODAE_PREC_BF16);
+    if (rc) return rc;
+    codae_slot_contrast c{};             // (built field by field: the graph key compares bytes)
+    const bool on = contrast != nullptr && contrast->weight != 0.f;
+    if (on) {
+        rc = slot_contrast_warm();
+        if (rc) return rc;
+        c.n_slots = contrast->n_slots; c.n_neg = contrast->n_neg; c.tau = contrast->tau; c.weight = contrast->weight;
+        c.seed = contrast->seed; c.n_rows = contrast->n_rows; c.n_pool = contrast->pool ? contrast->n_pool : 0;
+        c.ws_bytes = contrast->ws_bytes; c.pool = contrast->pool; c.item_id = contrast->item_id; c.ws = contrast->ws;
+    }
+    h->contrast = c;
+    h->contrast_on = on;
     return CODAE_OK;
 }
 
@@ -1469,7 +1522,8 @@ int codae_train_step_graph(codae_handle h, const codae_buffers* b, const codae_b
                        !same_bytes(&h->graph_key.hyper, &hk, sizeof(hk)) || !same_bytes(&h->graph_key.bufs, b, sizeof(*b)) ||
                        !same_bytes(&h->graph_key.noise, &h->noise, sizeof(h->noise)) ||
                        !same_bytes(&h->graph_key.emph, &h->emph, sizeof(h->emph)) || h->graph_key.emph_on != h->emph_on ||
-                       !same_bytes(&h->graph_key.drop, &h->drop, sizeof(h->drop)) || !same_bytes(&h->graph_key.recon, &h->recon, sizeof(h->recon));
+                       !same_bytes(&h->graph_key.drop, &h->drop, sizeof(h->drop)) || !same_bytes(&h->graph_key.recon, &h->recon, sizeof(h->recon)) ||
+                       !same_bytes(&h->graph_key.contrast, &h->contrast, sizeof(h->contrast));
     if (fresh) {
         if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
         int rc = check_common(h, b, batch->B);
@@ -1499,7 +1553,7 @@ int codae_train_step_graph(codae_handle h, const codae_buffers* b, const codae_b
             return CODAE_E_HIP;
         }
         h->graph_key.batch = *batch; h->graph_key.hyper = hk; h->graph_key.bufs = *b; h->graph_key.noise = h->noise; h->graph_key.emph = h->emph; h->graph_key.emph_on = h->emph_on;
-        h->graph_key.drop = h->drop; h->graph_key.recon = h->recon;
+        h->graph_key.drop = h->drop; h->graph_key.recon = h->recon; h->graph_key.contrast = h->contrast;
     }
     int rc = launch_set_scalar(b->scalars + CODAE_S_ADAM_STEP, (double)hyper->step, s);
     if (rc) return rc;

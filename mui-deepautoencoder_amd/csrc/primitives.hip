@@ -77,6 +77,23 @@ int codae_recon_loss_fwd_bwd(const codae_batch* batch, const codae_noise* noise,
 
 int codae_recon_loss_blocks(int32_t B) { return B > 0 ? mse_loss_colsum_rows(B) : 0; }
 
+int64_t codae_slot_contrast_ws_bytes(int32_t n_slots, int32_t n_neg, int32_t E, int32_t bf16) {
+    return slot_contrast_ws_bytes(n_slots, n_neg, E, bf16);
+}
+
+int codae_slot_contrast_prepare(const float* data, int32_t io, const codae_slot_contrast* contrast, int32_t step, int32_t bf16, void* stream) {
+    return launch_slot_contrast_prepare(data, io, contrast, step, nullptr, bf16, (hipStream_t)stream);
+}
+
+int codae_slot_contrast_fwd_bwd(const codae_batch* batch, const codae_noise* noise, int32_t step, const codae_emphasis* emphasis,
+                                const codae_slot_contrast* contrast, const float* y, void* dy, int32_t dy_bf16, int64_t dy_ld, float scale,
+                                float* colsum_part, double* parts, void* stream) {
+    return launch_slot_contrast(batch, noise, step, nullptr, emphasis, contrast, y, dy, dy_bf16, dy_ld, scale, colsum_part, parts,
+                                (hipStream_t)stream);
+}
+
+int codae_slot_contrast_blocks(int32_t B) { return B > 0 ? slot_contrast_blocks(B) : 0; }
+
 int codae_dropout_fwd(void* a, int32_t bf16, int64_t ld, int32_t B, int32_t width, const int32_t* row_idx, int32_t layer, int32_t step,
                       float p, uint64_t seed, void* stream) {
     return launch_dropout_fwd(a, bf16, ld, B, width, row_idx, layer, step, nullptr, p, seed, (hipStream_t)stream);

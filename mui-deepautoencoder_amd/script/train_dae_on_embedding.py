@@ -120,13 +120,17 @@ def main():
     # training loss instead of the mean squared error (the monitors stay squared-error sums; validation never sees it)
     from codae.tool.recon_loss import recon_loss_from_config
     criterion = recon_loss_from_config(config.get("HIP", {}).get("CRITERION"))
+    # HIP: CONTRAST: {NEGATIVES: 256, TEMPERATURE: 0.1, WEIGHT: 1.0, SEED: 0, DISTINCT: true} (build-only key): a sampled softmax
+    # over the true item of each slot and NEGATIVES rows drawn per step from the dataset, added to the criterion's loss
+    from codae.tool.contrast import contrast_from_config
+    contrast = contrast_from_config(config.get("HIP", {}).get("CONTRAST"))
 
     def build(prec):
         return HipEmbeddingTrainer(enc + dec, dataset.data, corrupter.mask_table_u8, corrupter.mask_to_use_i32,
                                    mc["LEARNING_RATE"], mc["WEIGHT_DECAY"], clip=1.0 if mc["TRUNK_GRAD"] else 0.0,
                                    max_batch=mc["BATCH_SIZE"], precision=prec, device=device, distributed=world > 1,
                                    activation=activation, input_noise=input_noise, loss_emphasis=loss_emphasis,
-                                   hidden_dropout=hidden_dropout, criterion=criterion)
+                                   hidden_dropout=hidden_dropout, criterion=criterion, contrast=contrast)
     try:
         trainer = build(precision)
     except HipError as e:
