@@ -54,6 +54,8 @@ extern "C" {
  *      codae_recon_loss_blocks: new entries only, no layout or enum change, the new kernels are booked under CODAE_K_LOSS
  *      (still 11) + codae_slot_contrast, codae_set_slot_contrast, codae_slot_contrast_ws_bytes, codae_slot_contrast_prepare,
  *      codae_slot_contrast_fwd_bwd, codae_slot_contrast_blocks: new entries only, no layout or enum change, booked under CODAE_K_LOSS
+ *      (still 11) + CODAE_OPT_*, CODAE_SCHED_*, codae_optimizer, codae_set_optimizer, codae_optimizer_update, codae_graph_captures:
+ *      new entries only, no layout or enum change, every variant of the update is booked under CODAE_K_ADAM
  * The binding must refuse a library whose codae_abi_version() differs and must check its own struct sizes against
  * codae_struct_sizes() at load (mui-deepautoencoder_amd/codae/hip/__init__.py does both). */
 #define CODAE_ABI_VERSION 11
@@ -267,6 +269,46 @@ typedef struct {
     int32_t n;
     uint64_t seed;
 } codae_dropout;
+
+/* Optimizer and schedule: what the update at the end of every training step does with the clipped gradient; the default is the line
+ * the reference script hard-wires, clip_grad_norm_ + torch.optim.Adam with L2 decay, AMSGrad off and a constant lr.
+ * t = the 1-based step, coef = the clip coefficient ("Non-finite values", point 3), lr, wd, b1, b2, eps = the fields of codae_hyper.
+ * Schedule, evaluated in double (W = warmup, T = total):
+ *   w(t)  = W > 0 && t <= W ? t / W : 1
+ *   q(t)  = clamp((t - W) / (T - W), 0, 1)
+ *   f(t)  = w(t) * { CONSTANT: 1
+ *                    COSINE:   min_factor + (1 - min_factor) (1 + cos(pi q)) / 2
+ *                    LINEAR:   1 - (1 - min_factor) q
+ *                    STEP:     gamma ^ floor((t - 1) / period) }
+ *   lr_t  = (float)((double)lr * f(t))
+ *   Past T the factor stays at its end value: torch's LambdaLR with lambda(t - 1).  The factor is computed on the device, in the
+ *   update kernel's prologue, from t = hyper->step in a plain step and t = scalars[CODAE_S_ADAM_STEP] under graph replay - the same
+ *   code, so a replayed step has the bits of a plain one and a schedule never re-captures the graph.
+ * Updates, bc1 = 1 - b1^t, bc2 = 1 - b2^t:
+ *   ADAM   g' = g coef + wd p;  m' = b1 m + (1-b1) g';  v' = b2 v + (1-b2) g'^2;  d = v'
+ *   ADAMW  g' = g coef;         p1 = p (1 - lr_t wd);   m', v' as above from g';  d = v'     (torch.optim.AdamW)
+ *          (p1 is evaluated as p - (lr_t wd) p: one rounding at the size of p)
+ *     amsgrad: vmax' = max(vmax, v'), a NaN on either side staying NaN as in torch.maximum (not fmaxf);  d = vmax'
+ *          p' = (p | p1) - lr_t / bc1 * m' / (sqrt(d) / sqrt(bc2) + eps)
+ *   SGD    g' = g coef + wd p;  m' = mu m + g';  u = nesterov ? g' + mu m' : m';  p' = p - lr_t u;  v is neither read nor written
+ *          (torch.optim.SGD with dampening 0; with a zero-initialised m its first step is torch's)
+ * A NaN clip coefficient makes every parameter and every state tensor that is written NaN, as under the default.
+ * Every kind writes p, the moments it keeps, the bf16 shadow and the transposed shadow in the one pass the default makes. */
+enum { CODAE_OPT_ADAM = 0, CODAE_OPT_ADAMW = 1, CODAE_OPT_SGD = 2 };
+enum { CODAE_SCHED_CONSTANT = 0, CODAE_SCHED_COSINE = 1, CODAE_SCHED_LINEAR = 2, CODAE_SCHED_STEP = 3 };
+typedef struct {
+    int32_t kind;          /* CODAE_OPT_* */
+    int32_t amsgrad;       /* ADAM / ADAMW only */
+    float   momentum;      /* SGD: mu in [0, 1) */
+    int32_t nesterov;      /* SGD, needs mu > 0 */
+    int32_t sched;         /* CODAE_SCHED_* */
+    int32_t warmup;        /* W >= 0 steps */
+    int32_t total;         /* T > W for COSINE / LINEAR */
+    int32_t period;        /* STEP: >= 1 */
+    float   min_factor;    /* COSINE / LINEAR: in [0, 1] */
+    float   gamma;         /* STEP: in (0, 1] */
+    float*  vmax;          /* device [n_param] fp32, zero before first use (padding too); required iff amsgrad; borrowed */
+} codae_optimizer;
 
 typedef struct codae_engine* codae_handle;
 
@@ -537,6 +579,16 @@ int codae_set_hidden_dropout(codae_handle h, const codae_dropout* d);
  * stand-alone kernel (no fused-loss epilogue), followed by a prepare launch and the contrast launch (both booked under
  * CODAE_K_LOSS, after the criterion's record) and a one-thread finish (not timed, like the criterion's), and the stack stays off the persistent chain kernel (codae_step_path reports 0). */
 int codae_set_slot_contrast(codae_handle h, const codae_slot_contrast* contrast);
+/* Optimizer and schedule of every update that follows - codae_step_update, codae_step_update_span (with vmax + lo), codae_train_step,
+ * codae_train_step_graph and codae_train_step_dp.  NULL, or {ADAM, amsgrad 0, CONSTANT, warmup 0}, switches it off: the engine then
+ * launches exactly the kernel instantiation it launched before, with the same bits.  CODAE_E_INVALID for an unknown kind or
+ * schedule, a parameter outside the range the struct names, amsgrad with SGD, nesterov without momentum, and a NULL or misaligned
+ * (16 bytes) vmax with amsgrad; on an error nothing changes.  Fields the kind and the schedule do not read are ignored.  The
+ * setting is part of the graph key (a change re-captures; a schedule alone never does) and never changes which forward or backward
+ * path a stack takes: codae_step_path is unaffected.  vmax is borrowed until the setting is replaced; SGD leaves adam_v alone. */
+int codae_set_optimizer(codae_handle h, const codae_optimizer* opt);
+/* how many times codae_train_step_graph has captured (and instantiated) a graph on this handle since codae_create */
+int codae_graph_captures(codae_handle h);
 /* validation body (:245-258): forward + metric sums only */
 int codae_eval_step(codae_handle h, const codae_buffers* bufs, const codae_batch* batch, float* out_y,
                     void* stream);
@@ -642,6 +694,10 @@ int codae_mse_loss_fwd_bwd(const float* x, const float* y, const float* fmask, f
 /* clip_grad_norm_ + Adam on flat vectors (train_dae_on_embedding.py:212-215) */
 int codae_clip_adam(float* params, float* grads, float* adam_m, float* adam_v, int64_t n,
                     const codae_hyper* hyper, double* scalars, void* stream);
+/* The same with an optimizer setting ("Optimizer and schedule"; opt NULL = codae_clip_adam): v may be NULL under SGD, vmax is
+ * read and written under amsgrad only (opt->vmax is not used here).  t = hyper->step. */
+int codae_optimizer_update(float* p, float* g, float* m, float* v, float* vmax, int64_t n, const codae_hyper* hyper,
+                           const codae_optimizer* opt, double* scalars, void* stream);
 
 /* ---- "next" rows: abalone loss and validation rank metric ---- */
 /* CombinedCriterion(reduction="mean") forward + gradient (codae/tool/metering.py:155-180): per variable v with

@@ -24,6 +24,9 @@ ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_RELU6, ACT_ELU, ACT_SOFTPLUS, ACT_HARDSIGMOID
 NOISE_NONE, NOISE_GAUSSIAN, NOISE_MASKING, NOISE_SALT_PEPPER = 0, 1, 2, 3
 # CODAE_LOSS_* of include/codae_hip.h: the training criterion (codae.tool.ReconstructionLoss builds the struct)
 LOSS_MSE, LOSS_L1, LOSS_SMOOTH_L1, LOSS_HUBER, LOSS_SLOT_COSINE = 0, 1, 2, 3, 4
+# CODAE_OPT_* / CODAE_SCHED_* of include/codae_hip.h: the update's optimizer and schedule (codae.tool.Optimizer builds the struct)
+OPT_ADAM, OPT_ADAMW, OPT_SGD = 0, 1, 2
+SCHED_CONSTANT, SCHED_COSINE, SCHED_LINEAR, SCHED_STEP = 0, 1, 2, 3
 KERNEL_CLASSES = ("gemm_fwd", "gemm_dgrad", "gemm_wgrad", "loss", "gather", "sumsq", "adam", "slab_reduce", "chain",
                   "bias_finish", "dropout")
 
@@ -86,6 +89,12 @@ class SlotContrast(C.Structure):
                 ("item_id", C.c_void_p), ("ws", C.c_void_p)]
 
 
+class Optimizer(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("amsgrad", C.c_int32), ("momentum", C.c_float), ("nesterov", C.c_int32), ("sched", C.c_int32),
+                ("warmup", C.c_int32), ("total", C.c_int32), ("period", C.c_int32), ("min_factor", C.c_float), ("gamma", C.c_float),
+                ("vmax", C.c_void_p)]
+
+
 class Dropout(C.Structure):
     _fields_ = [("p", C.POINTER(C.c_float)), ("n", C.c_int32), ("seed", C.c_uint64)]
 
@@ -122,6 +131,9 @@ PROTOTYPES = {
     "codae_set_recon_loss": (C.c_int, [_P, C.POINTER(ReconLoss)]),
     "codae_set_hidden_dropout": (C.c_int, [_P, C.POINTER(Dropout)]),
     "codae_set_slot_contrast": (C.c_int, [_P, C.POINTER(SlotContrast)]),
+    "codae_set_optimizer": (C.c_int, [_P, C.POINTER(Optimizer)]),
+    "codae_optimizer_update": (C.c_int, [_P, _P, _P, _P, _P, _I64, C.POINTER(Hyper), C.POINTER(Optimizer), _P, _P]),
+    "codae_graph_captures": (C.c_int, [_P]),
     "codae_slot_contrast_ws_bytes": (_I64, [_I32, _I32, _I32, _I32]),
     "codae_slot_contrast_prepare": (C.c_int, [_P, _I32, C.POINTER(SlotContrast), _I32, _I32, _P]),
     "codae_slot_contrast_fwd_bwd": (C.c_int, [C.POINTER(Batch), C.POINTER(Noise), _I32, C.POINTER(Emphasis), C.POINTER(SlotContrast), _P, _P,

@@ -90,6 +90,8 @@ class DaeEngine:
         self.recon_loss = None
         self.slot_contrast = None
         self._contrast_pins = None    # the device tensors codae_slot_contrast borrows (pool, item ids, work space)
+        self.optimizer = None
+        self.adam_vmax = None         # AMSGrad's running maximum (codae_optimizer.vmax borrows it), allocated on first use
         self.step_count = 0
         self.generation = 0   # bumped by every forward: guards stale backward calls
 
@@ -295,6 +297,34 @@ class DaeEngine:
     def _set_contrast_struct(self, st):
         with torch.cuda.device(self.device):      # (the setter raises a per-device kernel attribute: this engine's device)
             check(self._lib.codae_set_slot_contrast(self._h, None if st is None else C.byref(st)))
+
+    def set_optimizer(self, optimizer):
+        """optimizer: a codae.tool.Optimizer, or None for the default.  Every update that follows - train_step (plain and graph=True),
+        step_update, step_update_span, train_step_dp - runs it (include/codae_hip.h, "Optimizer and schedule"): AdamW, SGD with
+        (Nesterov) momentum or AMSGrad instead of Adam with L2 decay, the learning rate scaled by the schedule's factor, which the
+        update kernel evaluates from the device's own step count - the lr handed to hyper() stays the base rate, and a schedule
+        never re-captures a graph (a change of the setting does).  step_path() is unaffected.  AMSGrad's running maximum
+        (adam_vmax, n_param floats, zero) is allocated on first use and kept.  The default (Optimizer()) = off: the engine runs
+        exactly what it ran before.  On a refusal (HipError) the previous setting stays."""
+        if optimizer is not None and not hasattr(optimizer, "lr_at"):
+            raise HipError("set_optimizer: expected a codae.tool.Optimizer or None, got %r" % (optimizer,))
+        if optimizer is None or optimizer.is_default:
+            self._set_optimizer_struct(None)
+            self.optimizer = optimizer
+            return
+        vmax = self.adam_vmax
+        if optimizer.amsgrad and vmax is None:
+            with torch.cuda.device(self.device):
+                vmax = torch.zeros(self.n_param, dtype=torch.float32, device=self.device)
+        self._set_optimizer_struct(optimizer.as_struct(ptr(vmax)))
+        self.optimizer, self.adam_vmax = optimizer, vmax
+
+    def _set_optimizer_struct(self, st):
+        check(self._lib.codae_set_optimizer(self._h, None if st is None else C.byref(st)))
+
+    def graph_captures(self):
+        """How many times train_step(graph=True) has captured a graph on this engine."""
+        return int(self._lib.codae_graph_captures(self._h))
 
     def set_hidden_dropout(self, dropout):
         """dropout: a codae.tool.HiddenDropout, or None to switch it off.  Every training step form that follows multiplies the

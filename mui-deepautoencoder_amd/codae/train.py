@@ -394,7 +394,7 @@ class HipEmbeddingTrainer:
     def __init__(self, schedule, data, mask_table_u8, mask_to_use_i32, lr, weight_decay, clip=1.0,
                  max_batch=8192, precision="bf16", device="cuda:0", distributed=False, n_buckets=None, use_graph=False,
                  sharded_update=False, native_dp=False, activation=None, n_slots=None, input_noise=None,
-                 loss_emphasis=None, hidden_dropout=None, criterion=None, contrast=None):
+                 loss_emphasis=None, hidden_dropout=None, criterion=None, contrast=None, optimizer=None):
         """use_graph: replay the fused step from a hipGraph (codae_train_step_graph): for launch-bound shapes
         (small batches); single process only - the bucketed data-parallel step is not captured.
         activation: what follows every hidden Linear, as the model classes take it (a factory called as activation(True),
@@ -418,7 +418,11 @@ class HipEmbeddingTrainer:
         contrast: a codae.tool.SlotContrast: a sampled softmax over the true item of each slot and negatives drawn per step from
         the resident dataset, added to the criterion's loss in every step form (candidates keyed by the optimizer step and the
         slot, shared by all ranks); epoch_sums(), eval_batch and complete never see it.  None (or weight 0) = off, exactly as
-        before."""
+        before.
+        optimizer: a codae.tool.Optimizer: AdamW, SGD with (Nesterov) momentum or AMSGrad instead of Adam with L2 decay, and a
+        warm-up + cosine / linear / step schedule on `lr`, in every step form (fused, graph replay - a schedule never re-captures
+        -, torch.distributed, sharded, native data parallel); `lr` stays the base rate, current_lr() tells the scheduled one.
+        None (or the default Optimizer()) = Adam at a constant rate, exactly as before."""
         from .hip.engine import DaeEngine
         fit_host_threads()      # the loop that feeds this trainer must not get its container CPU-throttled (codae/hostcpu.py)
         self.device = torch.device(device)
@@ -438,6 +442,8 @@ class HipEmbeddingTrainer:
             self.set_criterion(criterion)
         if contrast is not None:
             self.set_contrast(contrast)
+        if optimizer is not None:
+            self.set_optimizer(optimizer)
         self.dp = DataParallel(self.engine, n_buckets=n_buckets, sharded=sharded_update, native=native_dp) if distributed else None
         self.world = self.dp.world if self.dp else 1
         self.use_graph = bool(use_graph) and self.dp is None
@@ -476,6 +482,19 @@ class HipEmbeddingTrainer:
                                "construct it with n_slots")
             S = self._slots()[0]
         self.engine.set_slot_contrast(contrast, self.data, n_slots=S)
+
+    def set_optimizer(self, optimizer):
+        """DaeEngine.set_optimizer: a codae.tool.Optimizer, or None for Adam at a constant rate."""
+        self.engine.set_optimizer(optimizer)
+
+    def current_lr(self):
+        """The learning rate of the NEXT step as the update kernel forms it: the fp32 lr_t at step_count + 1 (the fp32 base lr
+        without a schedule)."""
+        opt = self.engine.optimizer
+        if opt is None:
+            from .tool.optimizer import Optimizer
+            opt = Optimizer()
+        return opt.lr_at(self.lr, self.engine.step_count + 1)
 
     def set_hidden_dropout(self, dropout):
         """DaeEngine.set_hidden_dropout: a codae.tool.HiddenDropout, or None to switch it off."""

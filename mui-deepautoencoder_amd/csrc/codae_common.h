@@ -476,16 +476,23 @@ int launch_sumsq_to(const float* g, int64_t n, double* acc, hipStream_t s);     
 int launch_clip_coef(const double* total_sq, float max_norm, double* coef_out, hipStream_t s);
 // coef_in != null: use that precomputed clip coefficient instead of folding grad_sq + slots
 // step_dev != null: take the step count (bias corrections) from that device scalar instead of hp->step
+// opt: the optimizer setting (codae_optimizer; null or the default = Adam with L2 decay and a constant lr, the instantiation this
+// launcher always ran); vmax: AMSGrad's running maximum, at the same offset as p / m / v (a span passes vmax + lo)
 int launch_clip_adam(float* p, float* g, float* m, float* v, int64_t n, const codae_hyper* hp,
                      const double* grad_sq, bf16_t* shadow, const double* coef_in, hipStream_t s,
-                     const double* step_dev = nullptr);
+                     const double* step_dev = nullptr, const codae_optimizer* opt = nullptr, float* vmax = nullptr);
+// CODAE_E_INVALID as codae_set_optimizer documents; is_default: null, or {ADAM, amsgrad 0, CONSTANT, warmup 0};
+// canonical: only the fields the kind and the schedule read, all else zero (the graph key compares bytes)
+int check_optimizer(const codae_optimizer* o);
+bool optimizer_is_default(const codae_optimizer* o);
+codae_optimizer optimizer_canonical(const codae_optimizer* o);
 int launch_set_scalar(double* dst, double value, hipStream_t s);
 // bf16 engine: Adam over the weight matrices in tiles, writing the bf16 shadow AND (layers >= transposed_from) the
 // transposed shadow in the same pass; the flat bias block [bias_off, bias_off + bias_n) rides along
 int launch_clip_adam_tiled(float* p, float* g, float* m, float* v, const codae_hyper* hp, const double* grad_sq,
                            bf16_t* shadow, bf16_t* shadow_t, int n_layers, const int64_t* w_off, const int* rows,
                            const int* cols, int transposed_from, int64_t bias_off, int64_t bias_n, hipStream_t s,
-                           const double* step_dev = nullptr);
+                           const double* step_dev = nullptr, const codae_optimizer* opt = nullptr, float* vmax = nullptr);
 // dst[c][r] = src[r][c] for n bf16 matrices (element offsets off[i], shapes rows[i] x cols[i]) in one launch
 int launch_transpose_bf16(const bf16_t* src, bf16_t* dst, int n, const int64_t* off, const int* rows, const int* cols,
                           hipStream_t s);

@@ -664,12 +664,80 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
     p = p - c.lr_over_bc1 * (m / denom);
 }
 
+// ---- optimizer kinds and the learning-rate schedule (codae_optimizer, include/codae_hip.h) ----
+// Both update kernels are templated on (KIND, AMS, SCHED); <CODAE_OPT_ADAM, false, false> is the code above, untouched.  Every other
+// instantiation rebuilds lr_t and the bias corrections in its prologue, in double, from the step count - the kernel argument in a
+// plain step, the device scalar under graph replay: the same code, so a replayed step has the bits of a plain one.
+struct OptConst {
+    float mu;                // SGD momentum
+    int nesterov;
+    int sched, warmup, total, period;
+    float min_factor, gamma;
+    int step;                // hyper->step (a plain step's t)
+    float decay;             // ADAMW: lr_t wd, filled by the prologue
+};
+
+// f(t) of include/codae_hip.h ("Optimizer and schedule"), in double
+__device__ __forceinline__ double lr_factor(const OptConst& o, double t) {
+    const double W = (double)o.warmup;
+    const double w = (o.warmup > 0 && t <= W) ? t / W : 1.0;
+    double f = 1.0;
+    if (o.sched == CODAE_SCHED_COSINE || o.sched == CODAE_SCHED_LINEAR) {
+        double q = (t - W) / ((double)o.total - W);
+        q = q < 0.0 ? 0.0 : (q > 1.0 ? 1.0 : q);
+        const double mf = (double)o.min_factor;
+        f = o.sched == CODAE_SCHED_COSINE ? mf + (1.0 - mf) * (1.0 + cos(M_PI * q)) / 2.0 : 1.0 - (1.0 - mf) * q;
+    } else if (o.sched == CODAE_SCHED_STEP) {
+        f = pow((double)o.gamma, floor((t - 1.0) / (double)o.period));
+    }
+    return w * f;
+}
+
+// c.lr <- lr_t, the bias-correction factors from it (ADAM / ADAMW), o.decay (ADAMW)
+template <int KIND, bool SCHED>
+__device__ __forceinline__ void opt_prologue(AdamConst& c, OptConst& o, const double* __restrict__ step_dev) {
+    const double t = step_dev != nullptr ? *step_dev : (double)o.step;
+    if constexpr (SCHED) c.lr = (float)((double)c.lr * lr_factor(o, t));
+    if constexpr (KIND != CODAE_OPT_SGD) {
+        c.lr_over_bc1 = (float)((double)c.lr / (1.0 - pow((double)c.beta1, t)));
+        c.inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)c.beta2, t)));
+    }
+    o.decay = c.lr * c.wd;
+}
+
+template <int KIND, bool AMS>
+__device__ __forceinline__ void opt_one(float& p, float g, float& m, float& v, float& vm, float coef, const AdamConst& c,
+                                        const OptConst& o) {
+    if constexpr (KIND == CODAE_OPT_SGD) {
+        g = g * coef + c.wd * p;
+        m = o.mu * m + g;
+        const float u = o.nesterov ? g + o.mu * m : m;
+        p = p - c.lr * u;
+    } else if constexpr (KIND == CODAE_OPT_ADAM && !AMS) {
+        adam_one(p, g, m, v, coef, c);
+    } else {
+        if constexpr (KIND == CODAE_OPT_ADAMW) { g = g * coef; p = p - o.decay * p; }     // p (1 - lr_t wd), rounded once at p's size
+        else g = g * coef + c.wd * p;
+        m = c.beta1 * m + (1.f - c.beta1) * g;
+        v = c.beta2 * v + (1.f - c.beta2) * g * g;
+        float d = v;
+        if constexpr (AMS) { vm = (v > vm || v != v) ? v : vm; d = vm; }       // torch.maximum: a NaN on either side stays
+        const float denom = sqrtf(d) * c.inv_sqrt_bc2 + c.eps;
+        p = p - c.lr_over_bc1 * (m / denom);
+    }
+}
+
+template <int KIND, bool AMS, bool SCHED>
 __global__ __launch_bounds__(NT) void clip_adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                        float* __restrict__ m, float* __restrict__ v, int64_t n,
                                                        AdamConst c, const double* __restrict__ grad_sq,
                                                        bf16_t* __restrict__ shadow, const double* __restrict__ coef_in,
-                                                       const double* __restrict__ step_dev) {
-    if (step_dev != nullptr) {
+                                                       const double* __restrict__ step_dev, float* __restrict__ vmax, OptConst o) {
+    constexpr bool PLAIN = KIND == CODAE_OPT_ADAM && !AMS && !SCHED;
+    constexpr bool HAS_V = KIND != CODAE_OPT_SGD;          // SGD neither reads nor writes v
+    if constexpr (!PLAIN) {
+        opt_prologue<KIND, SCHED>(c, o, step_dev);
+    } else if (step_dev != nullptr) {
         // replayed from a hipGraph: the step count lives in device memory (kernel arguments are frozen at capture)
         const double t = *step_dev;
         c.lr_over_bc1 = (float)((double)c.lr / (1.0 - pow((double)c.beta1, t)));
@@ -696,20 +764,27 @@ __global__ __launch_bounds__(NT) void clip_adam_kernel(float* __restrict__ p, co
         float4 pp = reinterpret_cast<float4*>(p)[e];
         const float4 gg = reinterpret_cast<const float4*>(g)[e];
         float4 mm = reinterpret_cast<float4*>(m)[e];
-        float4 vv = reinterpret_cast<float4*>(v)[e];
-        adam_one(pp.x, gg.x, mm.x, vv.x, coef, c);
-        adam_one(pp.y, gg.y, mm.y, vv.y, coef, c);
-        adam_one(pp.z, gg.z, mm.z, vv.z, coef, c);
-        adam_one(pp.w, gg.w, mm.w, vv.w, coef, c);
+        float4 vv = make_float4(0.f, 0.f, 0.f, 0.f), xx = vv;
+        if constexpr (HAS_V) vv = reinterpret_cast<float4*>(v)[e];
+        if constexpr (AMS) xx = reinterpret_cast<float4*>(vmax)[e];
+        opt_one<KIND, AMS>(pp.x, gg.x, mm.x, vv.x, xx.x, coef, c, o);
+        opt_one<KIND, AMS>(pp.y, gg.y, mm.y, vv.y, xx.y, coef, c, o);
+        opt_one<KIND, AMS>(pp.z, gg.z, mm.z, vv.z, xx.z, coef, c, o);
+        opt_one<KIND, AMS>(pp.w, gg.w, mm.w, vv.w, xx.w, coef, c, o);
         reinterpret_cast<float4*>(p)[e] = pp;
         reinterpret_cast<float4*>(m)[e] = mm;
-        reinterpret_cast<float4*>(v)[e] = vv;
+        if constexpr (HAS_V) reinterpret_cast<float4*>(v)[e] = vv;
+        if constexpr (AMS) reinterpret_cast<float4*>(vmax)[e] = xx;
         if (shadow) reinterpret_cast<uint2*>(shadow)[e] = pack_bf16x4(pp.x, pp.y, pp.z, pp.w);
     }
     for (int64_t e = n4 * 4 + (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += (int64_t)gridDim.x * NT) {
-        float pp = p[e], mm = m[e], vv = v[e];
-        adam_one(pp, g[e], mm, vv, coef, c);
-        p[e] = pp; m[e] = mm; v[e] = vv;
+        float pp = p[e], mm = m[e], vv = 0.f, xx = 0.f;
+        if constexpr (HAS_V) vv = v[e];
+        if constexpr (AMS) xx = vmax[e];
+        opt_one<KIND, AMS>(pp, g[e], mm, vv, xx, coef, c, o);
+        p[e] = pp; m[e] = mm;
+        if constexpr (HAS_V) v[e] = vv;
+        if constexpr (AMS) vmax[e] = xx;
         if (shadow) shadow[e] = f32_to_bf16(pp);
     }
 }
@@ -1175,14 +1250,19 @@ struct AdamTiles {
 };
 constexpr int AT_R = 64, AT_C = 128;
 
+template <int KIND, bool AMS, bool SCHED>
 __global__ __launch_bounds__(NT) void clip_adam_tiled_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                              float* __restrict__ m, float* __restrict__ v, AdamConst c,
                                                              const double* __restrict__ grad_sq, bf16_t* __restrict__ shadow,
                                                              bf16_t* __restrict__ shadow_t, AdamTiles jobs,
-                                                             const double* __restrict__ step_dev) {
+                                                             const double* __restrict__ step_dev, float* __restrict__ vmax, OptConst o) {
+    constexpr bool PLAIN = KIND == CODAE_OPT_ADAM && !AMS && !SCHED;
+    constexpr bool HAS_V = KIND != CODAE_OPT_SGD;
     __shared__ bf16_t tt[AT_C][AT_R + 8];          // transposed tile: [col][row], rows stay 16-byte aligned
     __shared__ double total_sq;
-    if (step_dev != nullptr) {
+    if constexpr (!PLAIN) {
+        opt_prologue<KIND, SCHED>(c, o, step_dev);
+    } else if (step_dev != nullptr) {
         const double t = *step_dev;
         c.lr_over_bc1 = (float)((double)c.lr / (1.0 - pow((double)c.beta1, t)));
         c.inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)c.beta2, t)));
@@ -1204,9 +1284,13 @@ __global__ __launch_bounds__(NT) void clip_adam_tiled_kernel(float* __restrict__
         const int64_t nb = (int64_t)gridDim.x - n_tiles;
         for (int64_t e = ((int64_t)blockIdx.x - n_tiles) * NT + threadIdx.x; e < jobs.bias_n; e += nb * NT) {
             const int64_t i = jobs.bias_off + e;
-            float pp = p[i], mm = m[i], vv = v[i];
-            adam_one(pp, g[i], mm, vv, coef, c);
-            p[i] = pp; m[i] = mm; v[i] = vv;
+            float pp = p[i], mm = m[i], vv = 0.f, xx = 0.f;
+            if constexpr (HAS_V) vv = v[i];
+            if constexpr (AMS) xx = vmax[i];
+            opt_one<KIND, AMS>(pp, g[i], mm, vv, xx, coef, c, o);
+            p[i] = pp; m[i] = mm;
+            if constexpr (HAS_V) v[i] = vv;
+            if constexpr (AMS) vmax[i] = xx;
             shadow[i] = f32_to_bf16(pp);
         }
         return;
@@ -1228,14 +1312,17 @@ __global__ __launch_bounds__(NT) void clip_adam_tiled_kernel(float* __restrict__
             float4 pp = *reinterpret_cast<float4*>(p + e);
             const float4 gg = *reinterpret_cast<const float4*>(g + e);
             float4 mm = *reinterpret_cast<float4*>(m + e);
-            float4 vv = *reinterpret_cast<float4*>(v + e);
-            adam_one(pp.x, gg.x, mm.x, vv.x, coef, c);
-            adam_one(pp.y, gg.y, mm.y, vv.y, coef, c);
-            adam_one(pp.z, gg.z, mm.z, vv.z, coef, c);
-            adam_one(pp.w, gg.w, mm.w, vv.w, coef, c);
+            float4 vv = make_float4(0.f, 0.f, 0.f, 0.f), xx = vv;
+            if constexpr (HAS_V) vv = *reinterpret_cast<float4*>(v + e);
+            if constexpr (AMS) xx = *reinterpret_cast<float4*>(vmax + e);
+            opt_one<KIND, AMS>(pp.x, gg.x, mm.x, vv.x, xx.x, coef, c, o);
+            opt_one<KIND, AMS>(pp.y, gg.y, mm.y, vv.y, xx.y, coef, c, o);
+            opt_one<KIND, AMS>(pp.z, gg.z, mm.z, vv.z, xx.z, coef, c, o);
+            opt_one<KIND, AMS>(pp.w, gg.w, mm.w, vv.w, xx.w, coef, c, o);
             *reinterpret_cast<float4*>(p + e) = pp;
             *reinterpret_cast<float4*>(m + e) = mm;
-            *reinterpret_cast<float4*>(v + e) = vv;
+            if constexpr (HAS_V) *reinterpret_cast<float4*>(v + e) = vv;
+            if constexpr (AMS) *reinterpret_cast<float4*>(vmax + e) = xx;
             const uint2 sh = pack_bf16x4(pp.x, pp.y, pp.z, pp.w);
             *reinterpret_cast<uint2*>(shadow + e) = sh;
             if (want_t) {
@@ -1266,13 +1353,47 @@ int launch_set_scalar(double* dst, double value, hipStream_t s) {
     return CODAE_OK;
 }
 
-int launch_clip_adam(float* p, float* g, float* m, float* v, int64_t n, const codae_hyper* hp,
-                     const double* grad_sq, bf16_t* shadow, const double* coef_in, hipStream_t s,
-                     const double* step_dev) {
-    CODAE_REQUIRE(p && g && m && v && hp && n > 0, "clip_adam: bad args");
-    CODAE_REQUIRE(a16(p) && a16(g) && a16(m) && a16(v), "clip_adam: buffers must be 16-byte aligned");
-    CODAE_REQUIRE(hp->step >= 1, "clip_adam: step must be >= 1");
-    CODAE_REQUIRE(hp->max_grad_norm <= 0.f || grad_sq || coef_in, "clip_adam: clipping needs the grad_sq scalar");
+// ---- the optimizer setting on the host: checks, kernel constants, instantiation --------------
+bool optimizer_is_default(const codae_optimizer* o) {
+    return o == nullptr || (o->kind == CODAE_OPT_ADAM && o->amsgrad == 0 && o->sched == CODAE_SCHED_CONSTANT && o->warmup == 0);
+}
+
+int check_optimizer(const codae_optimizer* o) {
+    if (o == nullptr) return CODAE_OK;
+    CODAE_REQUIRE(o->kind == CODAE_OPT_ADAM || o->kind == CODAE_OPT_ADAMW || o->kind == CODAE_OPT_SGD, "optimizer: unknown kind %d", o->kind);
+    CODAE_REQUIRE(o->amsgrad == 0 || o->amsgrad == 1, "optimizer: amsgrad %d is neither 0 nor 1", o->amsgrad);
+    CODAE_REQUIRE(o->nesterov == 0 || o->nesterov == 1, "optimizer: nesterov %d is neither 0 nor 1", o->nesterov);
+    CODAE_REQUIRE(!(o->kind == CODAE_OPT_SGD && o->amsgrad), "optimizer: amsgrad belongs to adam / adamw, not to sgd");
+    CODAE_REQUIRE(finite_f(o->momentum) && o->momentum >= 0.f && o->momentum < 1.f, "optimizer: momentum %g outside [0, 1)", (double)o->momentum);
+    CODAE_REQUIRE(!o->nesterov || o->momentum > 0.f, "optimizer: nesterov needs momentum > 0");
+    CODAE_REQUIRE(o->sched >= CODAE_SCHED_CONSTANT && o->sched <= CODAE_SCHED_STEP, "optimizer: unknown schedule %d", o->sched);
+    CODAE_REQUIRE(o->warmup >= 0, "optimizer: warmup %d < 0", o->warmup);
+    if (o->sched == CODAE_SCHED_COSINE || o->sched == CODAE_SCHED_LINEAR) {
+        CODAE_REQUIRE(o->total > o->warmup, "optimizer: total %d must exceed warmup %d", o->total, o->warmup);
+        CODAE_REQUIRE(finite_f(o->min_factor) && o->min_factor >= 0.f && o->min_factor <= 1.f, "optimizer: min_factor %g outside [0, 1]",
+                      (double)o->min_factor);
+    }
+    if (o->sched == CODAE_SCHED_STEP) {
+        CODAE_REQUIRE(o->period >= 1, "optimizer: period %d < 1", o->period);
+        CODAE_REQUIRE(finite_f(o->gamma) && o->gamma > 0.f && o->gamma <= 1.f, "optimizer: gamma %g outside (0, 1]", (double)o->gamma);
+    }
+    CODAE_REQUIRE(!o->amsgrad || (o->vmax != nullptr && a16(o->vmax)), "optimizer: amsgrad needs a 16-byte aligned vmax");
+    return CODAE_OK;
+}
+
+// Only the fields the kind and the schedule read, everything else zero: the setter stores this form, and the graph key compares its bytes
+codae_optimizer optimizer_canonical(const codae_optimizer* o) {
+    codae_optimizer c{};
+    if (optimizer_is_default(o)) return c;
+    c.kind = o->kind; c.sched = o->sched; c.warmup = o->warmup;
+    if (o->kind == CODAE_OPT_SGD) { c.momentum = o->momentum; c.nesterov = o->nesterov; }
+    else if (o->amsgrad) { c.amsgrad = 1; c.vmax = o->vmax; }
+    if (o->sched == CODAE_SCHED_COSINE || o->sched == CODAE_SCHED_LINEAR) { c.total = o->total; c.min_factor = o->min_factor; }
+    if (o->sched == CODAE_SCHED_STEP) { c.period = o->period; c.gamma = o->gamma; }
+    return c;
+}
+
+static AdamConst adam_const(const codae_hyper* hp) {
     AdamConst c;
     const double bc1 = 1.0 - pow((double)hp->beta1, (double)hp->step);
     const double bc2 = 1.0 - pow((double)hp->beta2, (double)hp->step);
@@ -1280,8 +1401,50 @@ int launch_clip_adam(float* p, float* g, float* m, float* v, int64_t n, const co
     c.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
     c.beta1 = hp->beta1; c.beta2 = hp->beta2; c.eps = hp->eps; c.wd = hp->weight_decay;
     c.max_norm = hp->max_grad_norm; c.lr = hp->lr;
-    hipLaunchKernelGGL(clip_adam_kernel, dim3(grid_for(n / 4 + 1)), dim3(NT), 0, s, p, g, m, v, n, c, grad_sq, shadow, coef_in,
-                       step_dev);
+    return c;
+}
+
+static OptConst opt_const(const codae_optimizer* opt, const codae_hyper* hp) {
+    OptConst o{};
+    o.step = hp->step;
+    if (!optimizer_is_default(opt)) {
+        o.mu = opt->momentum; o.nesterov = opt->nesterov; o.sched = opt->sched; o.warmup = opt->warmup; o.total = opt->total;
+        o.period = opt->period; o.min_factor = opt->min_factor; o.gamma = opt->gamma;
+    }
+    return o;
+}
+
+// f(std::integral_constant<int, KIND>, std::bool_constant<AMS>, std::bool_constant<SCHED>) for the setting's instantiation
+template <typename F>
+static void opt_dispatch(const codae_optimizer* opt, F&& f) {
+    const bool dflt = optimizer_is_default(opt);
+    const int kind = dflt ? CODAE_OPT_ADAM : opt->kind;
+    const bool ams = !dflt && opt->amsgrad != 0;
+    const bool sched = !dflt && (opt->sched != CODAE_SCHED_CONSTANT || opt->warmup > 0);
+    auto with_sched = [&](auto k, auto a) {
+        if (sched) f(k, a, std::true_type{}); else f(k, a, std::false_type{});
+    };
+    if (kind == CODAE_OPT_SGD) with_sched(std::integral_constant<int, CODAE_OPT_SGD>{}, std::false_type{});
+    else if (kind == CODAE_OPT_ADAMW) { if (ams) with_sched(std::integral_constant<int, CODAE_OPT_ADAMW>{}, std::true_type{}); else with_sched(std::integral_constant<int, CODAE_OPT_ADAMW>{}, std::false_type{}); }
+    else { if (ams) with_sched(std::integral_constant<int, CODAE_OPT_ADAM>{}, std::true_type{}); else with_sched(std::integral_constant<int, CODAE_OPT_ADAM>{}, std::false_type{}); }
+}
+
+int launch_clip_adam(float* p, float* g, float* m, float* v, int64_t n, const codae_hyper* hp,
+                     const double* grad_sq, bf16_t* shadow, const double* coef_in, hipStream_t s,
+                     const double* step_dev, const codae_optimizer* opt, float* vmax) {
+    const bool sgd = !optimizer_is_default(opt) && opt->kind == CODAE_OPT_SGD;
+    const bool ams = !optimizer_is_default(opt) && opt->amsgrad != 0;
+    CODAE_REQUIRE(p && g && m && (v || sgd) && hp && n > 0, "clip_adam: bad args");
+    CODAE_REQUIRE(a16(p) && a16(g) && a16(m) && (sgd || a16(v)), "clip_adam: buffers must be 16-byte aligned");
+    CODAE_REQUIRE(!ams || (vmax != nullptr && a16(vmax)), "clip_adam: amsgrad needs a 16-byte aligned vmax");
+    CODAE_REQUIRE(hp->step >= 1, "clip_adam: step must be >= 1");
+    CODAE_REQUIRE(hp->max_grad_norm <= 0.f || grad_sq || coef_in, "clip_adam: clipping needs the grad_sq scalar");
+    const AdamConst c = adam_const(hp);
+    const OptConst o = opt_const(opt, hp);
+    opt_dispatch(opt, [&](auto K, auto A, auto S) {
+        hipLaunchKernelGGL((clip_adam_kernel<decltype(K)::value, decltype(A)::value, decltype(S)::value>), dim3(grid_for(n / 4 + 1)), dim3(NT),
+                           0, s, p, g, m, v, n, c, grad_sq, shadow, coef_in, step_dev, vmax, o);
+    });
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;
 }
@@ -1289,18 +1452,16 @@ int launch_clip_adam(float* p, float* g, float* m, float* v, int64_t n, const co
 int launch_clip_adam_tiled(float* p, float* g, float* m, float* v, const codae_hyper* hp, const double* grad_sq,
                            bf16_t* shadow, bf16_t* shadow_t, int n_layers, const int64_t* w_off, const int* rows,
                            const int* cols, int transposed_from, int64_t bias_off, int64_t bias_n, hipStream_t s,
-                           const double* step_dev) {
-    CODAE_REQUIRE(p && g && m && v && hp && shadow && n_layers > 0 && n_layers <= 64, "clip_adam_tiled: bad args");
-    CODAE_REQUIRE(a16(p) && a16(g) && a16(m) && a16(v), "clip_adam_tiled: buffers must be 16-byte aligned");
+                           const double* step_dev, const codae_optimizer* opt, float* vmax) {
+    const bool sgd = !optimizer_is_default(opt) && opt->kind == CODAE_OPT_SGD;
+    const bool ams = !optimizer_is_default(opt) && opt->amsgrad != 0;
+    CODAE_REQUIRE(p && g && m && (v || sgd) && hp && shadow && n_layers > 0 && n_layers <= 64, "clip_adam_tiled: bad args");
+    CODAE_REQUIRE(a16(p) && a16(g) && a16(m) && (sgd || a16(v)), "clip_adam_tiled: buffers must be 16-byte aligned");
+    CODAE_REQUIRE(!ams || (vmax != nullptr && a16(vmax)), "clip_adam_tiled: amsgrad needs a 16-byte aligned vmax");
     CODAE_REQUIRE(hp->step >= 1, "clip_adam_tiled: step must be >= 1");
     CODAE_REQUIRE(hp->max_grad_norm <= 0.f || grad_sq, "clip_adam_tiled: clipping needs the grad_sq scalar");
-    AdamConst c;
-    const double bc1 = 1.0 - pow((double)hp->beta1, (double)hp->step);
-    const double bc2 = 1.0 - pow((double)hp->beta2, (double)hp->step);
-    c.lr_over_bc1 = (float)((double)hp->lr / bc1);
-    c.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-    c.beta1 = hp->beta1; c.beta2 = hp->beta2; c.eps = hp->eps; c.wd = hp->weight_decay;
-    c.max_norm = hp->max_grad_norm; c.lr = hp->lr;
+    const AdamConst c = adam_const(hp);
+    const OptConst o = opt_const(opt, hp);
     AdamTiles jobs;
     jobs.n_layers = n_layers; jobs.transposed_from = transposed_from; jobs.bias_off = bias_off; jobs.bias_n = bias_n;
     int total = 0;
@@ -1312,8 +1473,10 @@ int launch_clip_adam_tiled(float* p, float* g, float* m, float* v, const codae_h
     }
     jobs.tile_begin[n_layers] = total;
     const int bias_blocks = (int)((bias_n + NT * 8 - 1) / (NT * 8)) > 0 ? (int)((bias_n + NT * 8 - 1) / (NT * 8)) : 1;
-    hipLaunchKernelGGL(clip_adam_tiled_kernel, dim3(total + bias_blocks), dim3(NT), 0, s, p, g, m, v, c, grad_sq, shadow, shadow_t,
-                       jobs, step_dev);
+    opt_dispatch(opt, [&](auto K, auto A, auto S) {
+        hipLaunchKernelGGL((clip_adam_tiled_kernel<decltype(K)::value, decltype(A)::value, decltype(S)::value>), dim3(total + bias_blocks),
+                           dim3(NT), 0, s, p, g, m, v, c, grad_sq, shadow, shadow_t, jobs, step_dev, vmax, o);
+    });
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;
 }

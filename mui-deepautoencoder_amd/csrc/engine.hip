@@ -103,6 +103,8 @@ struct codae_engine {
     bool recon_on = false;
     codae_slot_contrast contrast{};  // slot contrast on top of the criterion (codae_set_slot_contrast); all zero = off
     bool contrast_on = false;
+    codae_optimizer opt{};           // optimizer and schedule of the update (codae_set_optimizer), canonical form; all zero = the default
+    int graph_captures = 0;          // captures of codae_train_step_graph since codae_create
     // hidden dropout of the training steps (codae_set_hidden_dropout): p[l] of layer l's output, all zero = off.  The backward entry
     // points take no batch, so a training forward leaves what they need behind: drop_live = the activations in the workspace were
     // dropped (an evaluation or drop-in forward clears it), with the batch rows, row indices and step of that forward
@@ -130,7 +132,7 @@ struct codae_engine {
     // codae_train_step_graph: the captured step and what it was captured for
     hipGraphExec_t graph_exec = nullptr;
     bool capturing = false;          // inside stream capture: device-side Adam step, everything joined at the end
-    struct GraphKey { codae_batch batch; codae_hyper hyper; codae_buffers bufs; codae_noise noise; codae_emphasis emph; bool emph_on; DropCfg drop; codae_recon_loss recon; codae_slot_contrast contrast; } graph_key{};
+    struct GraphKey { codae_batch batch; codae_hyper hyper; codae_buffers bufs; codae_noise noise; codae_emphasis emph; bool emph_on; DropCfg drop; codae_recon_loss recon; codae_slot_contrast contrast; codae_optimizer opt; } graph_key{};
     std::vector<hipEvent_t> prof_start, prof_stop;
     std::vector<int> prof_kind;
     std::vector<int> prof_count;    // launches covered by the record (a GroupScope spans several)
@@ -1322,6 +1324,16 @@ int codae_set_slot_contrast(codae_handle h, const codae_slot_contrast* contrast)
     return CODAE_OK;
 }
 
+int codae_set_optimizer(codae_handle h, const codae_optimizer* opt) {
+    CODAE_REQUIRE(h != nullptr, "codae_set_optimizer: null handle");
+    int rc = check_optimizer(opt);
+    if (rc) return rc;
+    h->opt = optimizer_canonical(opt);   // (built field by field from zero: the graph key compares bytes, padding included)
+    return CODAE_OK;
+}
+
+int codae_graph_captures(codae_handle h) { return h != nullptr ? h->graph_captures : 0; }
+
 int codae_set_hidden_dropout(codae_handle h, const codae_dropout* d) {
     CODAE_REQUIRE(h != nullptr, "codae_set_hidden_dropout: null handle");
     codae_engine::DropCfg c{};           // (built field by field: the graph key compares bytes, padding included)
@@ -1413,10 +1425,10 @@ static int update_impl(codae_handle h, const codae_buffers* b, const codae_hyper
         // one tiled pass: p, m, v, the bf16 shadow and the transposed shadow of every layer that has a data gradient
         return launch_clip_adam_tiled(b->params, b->grads, b->adam_m, b->adam_v, hyper, b->scalars + CODAE_S_GRAD_SQ, shadow,
                                       reinterpret_cast<bf16_t*>(b->shadow_wt), h->L, h->w_off.data(), h->out.data(), h->in.data(),
-                                      1, h->bias_begin, h->n_param - h->bias_begin, s, step_dev);
+                                      1, h->bias_begin, h->n_param - h->bias_begin, s, step_dev, &h->opt, h->opt.vmax);
     }
     rc = launch_clip_adam(b->params, b->grads, b->adam_m, b->adam_v, h->n_param, hyper, b->scalars + CODAE_S_GRAD_SQ,
-                          shadow, nullptr, s, step_dev);
+                          shadow, nullptr, s, step_dev, &h->opt, h->opt.vmax);
     if (rc) return rc;
     return refresh_transposed(h, b, s);
 }
@@ -1450,7 +1462,7 @@ int codae_step_update_span(codae_handle h, const codae_buffers* b, const codae_h
     CODAE_REQUIRE(h->prec != CODAE_PREC_BF16 || shadow, "codae_step_update_span: shadow_w missing");
     ProfScope prof(h, CODAE_K_ADAM, s);
     return launch_clip_adam(b->params + lo, b->grads + lo, b->adam_m + lo, b->adam_v + lo, hi - lo, hyper, nullptr,
-                            shadow ? shadow + lo : nullptr, coef, s);
+                            shadow ? shadow + lo : nullptr, coef, s, nullptr, &h->opt, h->opt.vmax ? h->opt.vmax + lo : nullptr);
 }
 
 int codae_sync_transposed(codae_handle h, const codae_buffers* b, void* stream) {
@@ -1523,7 +1535,8 @@ int codae_train_step_graph(codae_handle h, const codae_buffers* b, const codae_b
                        !same_bytes(&h->graph_key.noise, &h->noise, sizeof(h->noise)) ||
                        !same_bytes(&h->graph_key.emph, &h->emph, sizeof(h->emph)) || h->graph_key.emph_on != h->emph_on ||
                        !same_bytes(&h->graph_key.drop, &h->drop, sizeof(h->drop)) || !same_bytes(&h->graph_key.recon, &h->recon, sizeof(h->recon)) ||
-                       !same_bytes(&h->graph_key.contrast, &h->contrast, sizeof(h->contrast));
+                       !same_bytes(&h->graph_key.contrast, &h->contrast, sizeof(h->contrast)) ||
+                       !same_bytes(&h->graph_key.opt, &h->opt, sizeof(h->opt));
     if (fresh) {
         if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
         int rc = check_common(h, b, batch->B);
@@ -1553,7 +1566,8 @@ int codae_train_step_graph(codae_handle h, const codae_buffers* b, const codae_b
             return CODAE_E_HIP;
         }
         h->graph_key.batch = *batch; h->graph_key.hyper = hk; h->graph_key.bufs = *b; h->graph_key.noise = h->noise; h->graph_key.emph = h->emph; h->graph_key.emph_on = h->emph_on;
-        h->graph_key.drop = h->drop; h->graph_key.recon = h->recon; h->graph_key.contrast = h->contrast;
+        h->graph_key.drop = h->drop; h->graph_key.recon = h->recon; h->graph_key.contrast = h->contrast; h->graph_key.opt = h->opt;
+        ++h->graph_captures;
     }
     int rc = launch_set_scalar(b->scalars + CODAE_S_ADAM_STEP, (double)hyper->step, s);
     if (rc) return rc;

@@ -135,6 +135,24 @@ int codae_clip_adam(float* params, float* grads, float* adam_m, float* adam_v, i
     return launch_clip_adam(params, grads, adam_m, adam_v, n, hyper, scalars + CODAE_S_GRAD_SQ, nullptr, nullptr, s);
 }
 
+int codae_optimizer_update(float* p, float* g, float* m, float* v, float* vmax, int64_t n, const codae_hyper* hyper,
+                           const codae_optimizer* opt, double* scalars, void* stream) {
+    CODAE_REQUIRE(hyper && scalars, "codae_optimizer_update: null argument");
+    codae_optimizer o{};
+    if (opt != nullptr) { o = *opt; o.vmax = vmax; }       // (the range checks are the setter's; the maximum is this call's own)
+    int rc = check_optimizer(opt != nullptr ? &o : nullptr);
+    if (rc) return rc;
+    o = optimizer_canonical(opt != nullptr ? &o : nullptr);
+    hipStream_t s = (hipStream_t)stream;
+    if (hyper->max_grad_norm > 0.f) {
+        CODAE_HIP_CHECK(hipMemsetAsync(scalars + CODAE_S_GRAD_SQ, 0, sizeof(double), s));
+        CODAE_HIP_CHECK(hipMemsetAsync(scalars + CODAE_S_GRAD_SQ_SLOTS, 0, CODAE_S_N_SLOTS * sizeof(double), s));
+        rc = launch_sumsq(g, n, scalars + CODAE_S_GRAD_SQ, s);
+        if (rc) return rc;
+    }
+    return launch_clip_adam(p, g, m, v, n, hyper, scalars + CODAE_S_GRAD_SQ, nullptr, nullptr, s, nullptr, &o, o.vmax);
+}
+
 // ---- GEMM primitives ------------------------------------------------------------------------
 // The plain entry points run the ReLU / identity code (`relu`); the _act_ ones the generic-activation instantiation, CODAE_ACT_RELU
 // included, and hand CODAE_ACT_NONE (or a data gradient without a saved activation) to the plain one.

@@ -124,13 +124,19 @@ def main():
     # over the true item of each slot and NEGATIVES rows drawn per step from the dataset, added to the criterion's loss
     from codae.tool.contrast import contrast_from_config
     contrast = contrast_from_config(config.get("HIP", {}).get("CONTRAST"))
+    # HIP: OPTIMIZER: {KIND: adam | adamw | sgd, AMSGRAD: false, MOMENTUM: 0.9, NESTEROV: true, SCHEDULE: {KIND: cosine, WARMUP: 100,
+    # TOTAL: 10000, MIN_FACTOR: 0.01}} (build-only key): the update instead of Adam with L2 decay at a constant rate; a SCHEDULE
+    # without TOTAL runs over this script's own loop: epochs x runs (one mask run) x batches per epoch
+    from codae.tool.optimizer import optimizer_from_config
+    epochs = args.epochs if args.epochs is not None else mc["EPOCH"]
+    optimizer = optimizer_from_config(config.get("HIP", {}).get("OPTIMIZER"), total_steps=max(1, epochs * 1 * len(train_sampler)))
 
     def build(prec):
         return HipEmbeddingTrainer(enc + dec, dataset.data, corrupter.mask_table_u8, corrupter.mask_to_use_i32,
                                    mc["LEARNING_RATE"], mc["WEIGHT_DECAY"], clip=1.0 if mc["TRUNK_GRAD"] else 0.0,
                                    max_batch=mc["BATCH_SIZE"], precision=prec, device=device, distributed=world > 1,
                                    activation=activation, input_noise=input_noise, loss_emphasis=loss_emphasis,
-                                   hidden_dropout=hidden_dropout, criterion=criterion, contrast=contrast)
+                                   hidden_dropout=hidden_dropout, criterion=criterion, contrast=contrast, optimizer=optimizer)
     try:
         trainer = build(precision)
     except HipError as e:
@@ -145,11 +151,12 @@ def main():
     log.info("Linear stack: " + " | ".join("%d->%d%s" % (k, n, act_label if r else "") for k, n, r in enc + dec))
     book = {k: [] for k in ("ftl", "ptl", "fvl", "pvl", "rl")}
     ranking_loss = RankingLoss(dataset, validation_indices, device=device)
-    epochs = args.epochs if args.epochs is not None else mc["EPOCH"]
     S = dataset.nb_used_category
 
     for epoch in range(epochs):
         log.info("===================================================== EPOCH = %d" % epoch)
+        if optimizer is not None:
+            log.info("LEARNING RATE            = %.6g" % trainer.current_lr())
         for batch_indices in train_sampler.device_batches(device):      # one index copy per epoch, int32, on the device
             shard = shard_batch(batch_indices, rank, world)
             if shard is None:                   # fewer rows than ranks (ragged last batch): skipped by every rank
