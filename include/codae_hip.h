@@ -56,6 +56,9 @@ extern "C" {
  *      codae_slot_contrast_fwd_bwd, codae_slot_contrast_blocks: new entries only, no layout or enum change, booked under CODAE_K_LOSS
  *      (still 11) + CODAE_OPT_*, CODAE_SCHED_*, codae_optimizer, codae_set_optimizer, codae_optimizer_update, codae_graph_captures:
  *      new entries only, no layout or enum change, every variant of the update is booked under CODAE_K_ADAM
+ *      (still 11) + codae_set_slot_presence, codae_corrupt_batch_present, codae_mse_loss_present, codae_emph_loss_present,
+ *      codae_recon_loss_fwd_bwd_present, codae_slot_contrast_prepare_present, codae_slot_contrast_fwd_bwd_present: new entries only, no
+ *      layout or enum change, no new kernel class
  * The binding must refuse a library whose codae_abi_version() differs and must check its own struct sizes against
  * codae_struct_sizes() at load (mui-deepautoencoder_amd/codae/hip/__init__.py does both). */
 #define CODAE_ABI_VERSION 11
@@ -160,6 +163,32 @@ typedef struct {
     float alpha, beta;        /* weight of a corrupted / an untouched element; finite, >= 0 */
     const float* col_weight;  /* device, [io] or NULL; borrowed until the setting is replaced */
 } codae_emphasis;
+
+/* Slot presence: rows that lack an item in some slot take part in training, evaluation and completion.
+ * A presence table is present[n_rows][S] of uint8, device resident; present[r][s] == 0 says that DATASET row r has no item in slot
+ * s.  S = the slot count, io = S E, 1 <= S <= 128.  The table is keyed by the dataset row - row_idx[b], or b when row_idx is NULL -,
+ * never by the position in the batch.  The rule is SELECTION, not multiplication: what `data` holds in an absent slot is never used
+ * and may be NaN (compare "Loss emphasis", where weights multiply and a NaN under weight 0 stays a NaN).
+ *   1. input      the gather writes exactly 0 into every column of an absent slot, in training and in evaluation, behind the input
+ *                 noise and the slot blank: an absent element is never noised, and it never counts as corrupted or replaced.
+ *   2. element-wise loss (MSE, emphasised MSE, L1, SMOOTH_L1, HUBER, the MSE anchor of SLOT_COSINE): an absent element's term is 0
+ *                 and its dL/dy is exactly +0, whatever x and y hold; present elements keep their formulas, rounding order and
+ *                 weights.  inv_n = 1 / (rows io) does not change: nothing renormalises by the number of present elements.
+ *   3. SLOT_COSINE an absent pair (b, s) contributes 0 to L and 0 to dy - not the term W of a zero PRESENT target; W(b,s) of a
+ *                 present pair is unchanged.
+ *   4. slot contrast  an absent pair is a pair without a positive: 0 to loss and gradient (a NaN or Inf in its y slot still makes
+ *                 the pair's dy and L NaN, as for any pair without a positive).  A candidate row_k whose slot s is absent is left out
+ *                 of every pair, next to the accidental hits, and its vector reaches the products as zeros.  Drawing is unchanged
+ *                 (same Philox stream, same j): the candidates of a step do not depend on the table.  Item ids are >= 0.
+ *   5. monitors   CODAE_S_SQ_FULL sums (x-y)^2 over present elements, CODAE_S_SQ_PARTIAL over present and blanked ones, in training
+ *                 and in codae_eval_step; CODAE_S_LAST_LOSS is L as defined here.
+ *   6. everything else - dropout, clip, optimizer, schedule, shadows - is untouched.  Absence depends on the dataset row only, so a
+ *                 data-parallel shard's dy rows are the bits of the same rows of the global batch, and a replayed graph has the bits
+ *                 of a plain step.
+ * While a table is set the training loss runs in the stand-alone kernels (the emphasised kernel with unit weights for the plain
+ * MSE, the criterion's kernels otherwise), never in the last GEMM's epilogue, and the stack stays off the persistent chain kernel.
+ * Not covered: renormalising by present counts, the ranking monitor on incomplete rows, the mixed-variable path, and
+ * codae_forward / codae_backward on dense x (the binding has torch helpers for those loops). */
 
 /* Training criterion: what the TRAINING loss measures between the clean row x and the output y; the default is the mean squared
  * error the reference script hard-wires.  d = x - y, rows = the global batch (hyper->loss_scale_rows, or batch->B when that is 0),
@@ -587,6 +616,13 @@ int codae_set_slot_contrast(codae_handle h, const codae_slot_contrast* contrast)
  * setting is part of the graph key (a change re-captures; a schedule alone never does) and never changes which forward or backward
  * path a stack takes: codae_step_path is unaffected.  vmax is borrowed until the setting is replaced; SGD leaves adam_v alone. */
 int codae_set_optimizer(codae_handle h, const codae_optimizer* opt);
+/* Slot presence of every step that follows - training (every step form codae_set_input_noise lists; the pointer is part of the
+ * graph key) AND codae_eval_step.  present [n_rows][n_slots] uint8 on the device, borrowed until replaced; NULL switches it off: the
+ * engine then runs exactly what it ran before, bit for bit, codae_step_path included.  CODAE_E_INVALID for n_slots outside [1, 128]
+ * or not dividing io, n_rows < 1, and an n_slots that differs from the one a SLOT_COSINE criterion or a slot contrast is set with
+ * (those two setters refuse a disagreement with the table the same way: whichever comes second); nothing is launched, the previous
+ * setting stays.  Every row index of a batch must be < n_rows.  While a table is set codae_step_path reports 0. */
+int codae_set_slot_presence(codae_handle h, const uint8_t* present, int64_t n_rows, int32_t n_slots);
 /* how many times codae_train_step_graph has captured (and instantiated) a graph on this handle since codae_create */
 int codae_graph_captures(codae_handle h);
 /* validation body (:245-258): forward + metric sums only */
@@ -667,6 +703,26 @@ int codae_slot_contrast_fwd_bwd(const codae_batch* batch, const codae_noise* noi
                                 const codae_slot_contrast* contrast, const float* y, void* dy, int32_t dy_bf16, int64_t dy_ld, float scale,
                                 float* colsum_part, double* parts, void* stream);
 int codae_slot_contrast_blocks(int32_t B);
+/* The same primitives under a presence table ("Slot presence"; the launchers the engine uses, the PRES instantiations of the same
+ * kernels): arguments as their namesakes, with present [n_rows][n_slots] (NULL: exactly the namesake) in front of the stream.
+ * codae_corrupt_batch_present keys the table by the row the noise counter uses (noise_rows[b] when given, which needs a noise kind).
+ * codae_mse_loss_present is the un-weighted kernel of the evaluation sums: parts [blocks][2] = sum (x-y)^2, sum (1-fmask)(x-y)^2 over
+ * present elements; dy NULL = sums only.  A SLOT_COSINE criterion or a contrast whose n_slots differs from the table's is refused. */
+int codae_corrupt_batch_present(const codae_batch* batch, const codae_noise* noise, int32_t step, const int32_t* noise_rows, void* out,
+                                int32_t out_bf16, int64_t out_ld, const uint8_t* present, int32_t n_slots, void* stream);
+int codae_mse_loss_present(const codae_batch* batch, const float* y, void* dy, int32_t dy_bf16, int64_t dy_ld, float inv_n,
+                           float* colsum_part, double* parts, const uint8_t* present, int32_t n_slots, void* stream);
+int codae_emph_loss_present(const codae_batch* batch, const codae_noise* noise, int32_t step, const codae_emphasis* emphasis, const float* y,
+                            void* dy, int32_t dy_bf16, int64_t dy_ld, float inv_n, float* colsum_part, double* parts,
+                            const uint8_t* present, int32_t n_slots, void* stream);
+int codae_recon_loss_fwd_bwd_present(const codae_batch* batch, const codae_noise* noise, int32_t step, const codae_emphasis* emphasis,
+                                     const codae_recon_loss* loss, const float* y, void* dy, int32_t dy_bf16, int64_t dy_ld, float inv_n,
+                                     float* colsum_part, double* parts, const uint8_t* present, int32_t n_slots, void* stream);
+int codae_slot_contrast_prepare_present(const float* data, int32_t io, const codae_slot_contrast* contrast, int32_t step, int32_t bf16,
+                                        const uint8_t* present, int32_t n_slots, void* stream);
+int codae_slot_contrast_fwd_bwd_present(const codae_batch* batch, const codae_noise* noise, int32_t step, const codae_emphasis* emphasis,
+                                        const codae_slot_contrast* contrast, const float* y, void* dy, int32_t dy_bf16, int64_t dy_ld,
+                                        float scale, float* colsum_part, double* parts, const uint8_t* present, int32_t n_slots, void* stream);
 /* The two hidden-dropout kernels on their own (the launchers the engine uses; "Hidden dropout" above has the definition): in
  * place on rows < B and columns < width of a [B][ld] matrix, fp32 or (bf16 != 0) bf16; pad columns and pad rows are never
  * written.  16-byte accesses where the base address, ld and width allow (bf16 x 8, fp32 x 4), element accesses otherwise.

@@ -134,6 +134,16 @@ PROTOTYPES = {
     "codae_set_optimizer": (C.c_int, [_P, C.POINTER(Optimizer)]),
     "codae_optimizer_update": (C.c_int, [_P, _P, _P, _P, _P, _I64, C.POINTER(Hyper), C.POINTER(Optimizer), _P, _P]),
     "codae_graph_captures": (C.c_int, [_P]),
+    "codae_set_slot_presence": (C.c_int, [_P, _P, _I64, _I32]),
+    "codae_corrupt_batch_present": (C.c_int, [C.POINTER(Batch), C.POINTER(Noise), _I32, _P, _P, _I32, _I64, _P, _I32, _P]),
+    "codae_mse_loss_present": (C.c_int, [C.POINTER(Batch), _P, _P, _I32, _I64, _F, _P, _P, _P, _I32, _P]),
+    "codae_emph_loss_present": (C.c_int, [C.POINTER(Batch), C.POINTER(Noise), _I32, C.POINTER(Emphasis), _P, _P, _I32, _I64, _F, _P, _P,
+                                          _P, _I32, _P]),
+    "codae_recon_loss_fwd_bwd_present": (C.c_int, [C.POINTER(Batch), C.POINTER(Noise), _I32, C.POINTER(Emphasis), C.POINTER(ReconLoss), _P,
+                                                   _P, _I32, _I64, _F, _P, _P, _P, _I32, _P]),
+    "codae_slot_contrast_prepare_present": (C.c_int, [_P, _I32, C.POINTER(SlotContrast), _I32, _I32, _P, _I32, _P]),
+    "codae_slot_contrast_fwd_bwd_present": (C.c_int, [C.POINTER(Batch), C.POINTER(Noise), _I32, C.POINTER(Emphasis),
+                                                      C.POINTER(SlotContrast), _P, _P, _I32, _I64, _F, _P, _P, _P, _I32, _P]),
     "codae_slot_contrast_ws_bytes": (_I64, [_I32, _I32, _I32, _I32]),
     "codae_slot_contrast_prepare": (C.c_int, [_P, _I32, C.POINTER(SlotContrast), _I32, _I32, _P]),
     "codae_slot_contrast_fwd_bwd": (C.c_int, [C.POINTER(Batch), C.POINTER(Noise), _I32, C.POINTER(Emphasis), C.POINTER(SlotContrast), _P, _P,

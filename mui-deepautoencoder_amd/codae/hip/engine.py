@@ -90,6 +90,8 @@ class DaeEngine:
         self.recon_loss = None
         self.slot_contrast = None
         self._contrast_pins = None    # the device tensors codae_slot_contrast borrows (pool, item ids, work space)
+        self.slot_presence = None
+        self._presence_table = None   # the device tensor codae_set_slot_presence borrows
         self.optimizer = None
         self.adam_vmax = None         # AMSGrad's running maximum (codae_optimizer.vmax borrows it), allocated on first use
         self.step_count = 0
@@ -297,6 +299,31 @@ class DaeEngine:
     def _set_contrast_struct(self, st):
         with torch.cuda.device(self.device):      # (the setter raises a per-device kernel attribute: this engine's device)
             check(self._lib.codae_set_slot_contrast(self._h, None if st is None else C.byref(st)))
+
+    def set_slot_presence(self, presence):
+        """presence: a codae.tool.SlotPresence, or None to switch it off.  Every step that follows - training in every step form
+        AND eval_step - treats the absent slots of a dataset row as missing (include/codae_hip.h, "Slot presence"): 0 in the
+        gathered input, no term in the loss, +0 in dL/dy, not in epoch_sums(), not a contrast pair nor a contrast candidate;
+        whatever the data holds there is never used.  With graph=True the next step re-captures.  While a table is set,
+        step_path() is 'layers' and the loss runs in its stand-alone kernels.  None, or a table without an absent slot
+        (SlotPresence.is_default), = off: the engine runs exactly what it ran before.  On a refusal (HipError: slots that do not
+        divide io or disagree with slot_cosine / the slot contrast) the previous setting stays."""
+        if presence is not None and not hasattr(presence, "assign_masks"):
+            raise HipError("set_slot_presence: expected a codae.tool.SlotPresence or None, got %r" % (presence,))
+        if presence is None or presence.is_default:
+            self._set_presence_table(None)
+            self.slot_presence, self._presence_table = presence, None
+            return
+        table = presence.to(self.device)
+        self._set_presence_table(table)
+        self.slot_presence, self._presence_table = presence, table
+
+    def _set_presence_table(self, table, n_rows=None, n_slots=None):
+        if table is None:
+            check(self._lib.codae_set_slot_presence(self._h, None, 0, 0))
+            return
+        check(self._lib.codae_set_slot_presence(self._h, ptr(table), int(table.shape[0]) if n_rows is None else int(n_rows),
+                                                int(table.shape[1]) if n_slots is None else int(n_slots)))
 
     def set_optimizer(self, optimizer):
         """optimizer: a codae.tool.Optimizer, or None for the default.  Every update that follows - train_step (plain and graph=True),

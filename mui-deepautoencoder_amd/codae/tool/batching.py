@@ -53,11 +53,19 @@ def simple_collate(batch):
     return torch.stack(batch)
 
 
-def load_dataset_of_embeddings(embedding_path, config, cache_dir="tmp/"):
+def load_dataset_of_embeddings(embedding_path, config, cache_dir="tmp/", keep_incomplete=False, min_present=2):
     """JSON `{obs_id: {category: [float]}}` -> ConcatenatedEmbeddingDataset
     (data_tool.py:114-162).  The reference caches a pickle of the dataset object keyed by
-    the file's ctime; this build keeps the key but stores plain arrays (.npz), never a pickle."""
+    the file's ctime; this build keeps the key but stores plain arrays (.npz), never a pickle.
+    keep_incomplete / min_present: as ConcatenatedEmbeddingDataset takes them (built from the JSON, not cached)."""
     used = config["DATASET"]["USED_CATEGORY"]
+    if keep_incomplete:
+        try:
+            with open(embedding_path, 'r') as f:
+                embeddings = json.load(f)
+        except Exception:
+            raise Exception("Error while reading embedding json file.")
+        return ConcatenatedEmbeddingDataset(embeddings=embeddings, used_category=used, keep_incomplete=True, min_present=min_present)
     key = hashlib.sha1(str(os.stat(embedding_path)[9]).encode('utf-8')).hexdigest()
     cache = os.path.join(cache_dir, key + "_" + hashlib.sha1("|".join(used).encode()).hexdigest()[:8] + "_dataset.npz")
     if os.path.exists(cache):

@@ -394,7 +394,7 @@ class HipEmbeddingTrainer:
     def __init__(self, schedule, data, mask_table_u8, mask_to_use_i32, lr, weight_decay, clip=1.0,
                  max_batch=8192, precision="bf16", device="cuda:0", distributed=False, n_buckets=None, use_graph=False,
                  sharded_update=False, native_dp=False, activation=None, n_slots=None, input_noise=None,
-                 loss_emphasis=None, hidden_dropout=None, criterion=None, contrast=None, optimizer=None):
+                 loss_emphasis=None, hidden_dropout=None, criterion=None, contrast=None, optimizer=None, presence=None):
         """use_graph: replay the fused step from a hipGraph (codae_train_step_graph): for launch-bound shapes
         (small batches); single process only - the bucketed data-parallel step is not captured.
         activation: what follows every hidden Linear, as the model classes take it (a factory called as activation(True),
@@ -422,7 +422,11 @@ class HipEmbeddingTrainer:
         optimizer: a codae.tool.Optimizer: AdamW, SGD with (Nesterov) momentum or AMSGrad instead of Adam with L2 decay, and a
         warm-up + cosine / linear / step schedule on `lr`, in every step form (fused, graph replay - a schedule never re-captures
         -, torch.distributed, sharded, native data parallel); `lr` stays the base rate, current_lr() tells the scheduled one.
-        None (or the default Optimizer()) = Adam at a constant rate, exactly as before."""
+        None (or the default Optimizer()) = Adam at a constant rate, exactly as before.
+        presence: a codae.tool.SlotPresence over the rows of `data`: rows that lack an item in some slots train, evaluate and
+        complete - an absent slot is 0 in the input, has no term in the loss, the monitors or the contrast, and is never a
+        candidate of complete(); what `data` holds there is never used.  Every step form and eval_batch.  None (or a table
+        without an absent slot) = off, exactly as before."""
         from .hip.engine import DaeEngine
         fit_host_threads()      # the loop that feeds this trainer must not get its container CPU-throttled (codae/hostcpu.py)
         self.device = torch.device(device)
@@ -444,6 +448,9 @@ class HipEmbeddingTrainer:
             self.set_contrast(contrast)
         if optimizer is not None:
             self.set_optimizer(optimizer)
+        self.presence = None
+        if presence is not None:
+            self.set_presence(presence)
         self.dp = DataParallel(self.engine, n_buckets=n_buckets, sharded=sharded_update, native=native_dp) if distributed else None
         self.world = self.dp.world if self.dp else 1
         self.use_graph = bool(use_graph) and self.dp is None
@@ -482,6 +489,15 @@ class HipEmbeddingTrainer:
                                "construct it with n_slots")
             S = self._slots()[0]
         self.engine.set_slot_contrast(contrast, self.data, n_slots=S)
+
+    def set_presence(self, presence):
+        """DaeEngine.set_slot_presence for the resident dataset: a codae.tool.SlotPresence with one row per dataset row, or None to
+        switch it off.  complete() then ranks only rows that have the slot."""
+        if presence is not None and not getattr(presence, "is_default", True) and presence.n_rows != int(self.data.shape[0]):
+            raise HipError("slot presence: the table has %d rows, the dataset %d" % (presence.n_rows, int(self.data.shape[0])))
+        self.engine.set_slot_presence(presence)
+        self.presence = None if presence is None or presence.is_default else presence
+        self.__dict__.pop("_retrievers", None)
 
     def set_optimizer(self, optimizer):
         """DaeEngine.set_optimizer: a codae.tool.Optimizer, or None for Adam at a constant rate."""
@@ -589,7 +605,9 @@ class HipEmbeddingTrainer:
         resident-dataset rows whose slot is closest (cosine) to the reconstruction: (idx LongTensor [B, k], score FloatTensor
         [B, k]), ordered as tool.ComplementRetriever.topk.  Mask id c is the 1-subset {c} of the Corrupter's table order
         (the trainer's own S x io table when it has none), so the result does not depend on the mask run.  exclude_self:
-        never return a row's own item.  The metric sums of the engine are left as they were."""
+        never return a row's own item.  The metric sums of the engine are left as they were.
+        With a presence table only rows that HAVE the slot are candidates (intersected with `candidates`); a query row that
+        lacks the slot is the normal case; a slot no candidate row has gives (-1, -inf) everywhere."""
         from .tool.criteria import ComplementRetriever
         S, E = self._slots()
         if isinstance(slot, bool) or not isinstance(slot, int) or not 0 <= slot < S:
@@ -603,13 +621,23 @@ class HipEmbeddingTrainer:
                     t[c, c * E:(c + 1) * E] = 0
                 self._own_table = t.to(self.device)
             table = self._own_table
-        key = (bool(distinct), None if candidates is None else tuple(sorted(set(int(i) for i in candidates))))
+        cand = None if candidates is None else tuple(sorted(set(int(i) for i in candidates)))
+        B = int(idx.numel())
+        pslot = None
+        if self.presence is not None:
+            # the slot's inventory is the rows that have it: one retriever per (slot, subset)
+            pslot = slot
+            has = self.presence.table[:, slot] != 0
+            cand = tuple(int(i) for i in (has.nonzero()[0] if cand is None else [i for i in cand if 0 <= i < has.shape[0] and has[i]]))
+            if not cand:
+                return (torch.full((B, int(k)), -1, dtype=torch.long, device=self.device),
+                        torch.full((B, int(k)), float("-inf"), dtype=torch.float32, device=self.device))
+        key = (bool(distinct), cand, pslot)
         cache = self.__dict__.setdefault("_retrievers", {})
         if key not in cache:
             inv = _ResidentInventory(self.data, S, E)
             cache[key] = ComplementRetriever(inv, self.device, candidates=key[1], distinct=key[0])
         ret = cache[key]
-        B = int(idx.numel())
         mask_id = torch.full((B,), slot, dtype=torch.int32, device=self.device)
         batch = self.engine.make_batch(self.data, idx, mask_id, table)
         y = torch.empty((B, self.data.shape[1]), dtype=torch.float32, device=self.device)

@@ -185,6 +185,27 @@ __device__ __forceinline__ uint4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_
     return make_uint4(c0, c1, c2, c3);
 }
 
+// Per-row slot presence ("Slot presence", include/codae_hip.h): tab[row * S + slot] == 0 says that DATASET row `row` has no item in
+// that slot.  Kernels take it behind a template flag, so the instantiations of a step without a table stay the ones they were.
+struct PresArgs {
+    const uint8_t* tab;   // device [n_rows][S]; null = every slot present
+    int S, E;             // slots per row, columns per slot
+};
+// Which of the W columns c .. c + W - 1 of dataset row `row` are present, as bit k of the result.  sl[k] = (c + k) / E, formed
+// once by the caller (a loss kernel's thread keeps its columns while it walks the rows: no division in the row loop).  One byte per
+// (row, slot): a group inside one slot reads one byte, a group that straddles slots (E = 6, E = 12) decides per column.
+template <int W>
+__device__ __forceinline__ uint32_t present_bits(const PresArgs& p, int64_t row, const int* sl) {
+    const uint8_t* __restrict__ t = p.tab + row * p.S;
+    const uint32_t p0 = t[sl[0]] != 0 ? 1u : 0u;
+    if (sl[W - 1] == sl[0]) return p0 ? ((1u << W) - 1u) : 0u;
+    uint32_t bits = p0;
+#pragma unroll
+    for (int k = 1; k < W; ++k) bits |= (t[sl[k]] != 0 ? 1u : 0u) << k;
+    return bits;
+}
+int check_presence(const uint8_t* present, int n_slots, int io, const char* who);
+
 static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 // ---- output store policy (GemmBf16::store_policy) ------------------------------------------------------
@@ -408,13 +429,17 @@ int launch_chain_step(const ChainArgs& a, hipStream_t s);
 // out_ld: row stride of `out` in elements (0 = b->io: contiguous rows)
 // zero_norm != null: the scalars block - the launch also clears CODAE_S_GRAD_SQ and its slots (the fused step that folds its loss
 // finish into the bias finish: nothing else runs between the previous update and the first weight gradient)
-int launch_gather_corrupt(const codae_batch* b, void* out, int out_bf16, hipStream_t s, int64_t out_ld = 0, double* zero_norm = nullptr);
+// present != null (every launcher below that takes it): the presence table [n_rows][n_slots] of "Slot presence" - the PRES
+// instantiations; null launches exactly what it launched before.
+int launch_gather_corrupt(const codae_batch* b, void* out, int out_bf16, hipStream_t s, int64_t out_ld = 0, double* zero_norm = nullptr,
+                          const uint8_t* present = nullptr, int n_slots = 0);
 // The same gather with the input noise of `noise` (codae_noise, include/codae_hip.h) in front of the slot mask: the noise-enabled
 // instantiations, beside the plain ones above.  step: the counter's step word; step_dev != null: read it from that device scalar
 // instead (graph replay: kernel arguments are frozen at capture); noise_rows: see codae_corrupt_batch.  check_noise: CODAE_E_INVALID with the offending argument named.
 int check_noise(const codae_noise* noise);
 int launch_gather_noise(const codae_batch* b, const codae_noise* noise, int32_t step, const double* step_dev, void* out,
-                        int out_bf16, hipStream_t s, int64_t out_ld = 0, const int32_t* noise_rows = nullptr, double* zero_norm = nullptr);
+                        int out_bf16, hipStream_t s, int64_t out_ld = 0, const int32_t* noise_rows = nullptr, double* zero_norm = nullptr,
+                        const uint8_t* present = nullptr, int n_slots = 0);
 int launch_noise_box_muller(const uint32_t* ra, const uint32_t* rb, float* rho, float* c, float* sn, int64_t n, hipStream_t s);
 int launch_cast_bf16(const float* src, bf16_t* dst, int64_t n, hipStream_t s);
 int launch_corrupt(const float* x, const float* mask, float* out, int64_t n, hipStream_t s);
@@ -424,7 +449,8 @@ int launch_expand_masks(const int32_t* mask_id, const uint8_t* table, const int3
 // [mse_loss_colsum_rows(B)][io] (partial sums of the last bias gradient, one row per block)
 // loss_parts [mse_loss_colsum_rows(B)][2]: per-block metric sums (see LossFuse::parts)
 int launch_mse_loss(const codae_batch* b, const float* y, void* dy, int dy_bf16, float inv_n, float* colsum_part,
-                    double* loss_parts, int want_grad, hipStream_t s, int64_t dy_ld = 0);    // dy_ld: row stride of dy (0 = io)
+                    double* loss_parts, int want_grad, hipStream_t s, int64_t dy_ld = 0,     // dy_ld: row stride of dy (0 = io)
+                    const uint8_t* present = nullptr, int n_slots = 0);
 int mse_loss_colsum_rows(int B);
 // The emphasised denoising loss (codae_emphasis, include/codae_hip.h): launch_mse_loss's block shape - mse_loss_colsum_rows(B)
 // blocks, one colsum_part row each - with a weight per element; `noise` / step / step_dev as launch_gather_noise (which elements
@@ -434,7 +460,7 @@ int mse_loss_colsum_rows(int B);
 int check_emphasis(const codae_emphasis* emph);
 int launch_emph_loss(const codae_batch* b, const codae_noise* noise, int32_t step, const double* step_dev, const codae_emphasis* emph,
                      const float* y, void* dy, int dy_bf16, int64_t dy_ld, float inv_n, float* colsum_part, double* parts,
-                     hipStream_t s);
+                     hipStream_t s, const uint8_t* present = nullptr, int n_slots = 0);
 int launch_finish_emph_loss(double* scalars, double inv_n, hipStream_t s, const double* parts, int n_parts);
 // A training criterion other than the MSE (codae_recon_loss, include/codae_hip.h; recon_loss.hip): launch_emph_loss's block shape,
 // arguments and outputs, `emph` may be null (all weights 1); parts[.][0] is the criterion's sum, so launch_finish_emph_loss
@@ -443,7 +469,7 @@ int launch_finish_emph_loss(double* scalars, double inv_n, hipStream_t s, const 
 int check_recon_loss(const codae_recon_loss* loss, int io);
 int launch_recon_loss(const codae_batch* b, const codae_noise* noise, int32_t step, const double* step_dev, const codae_emphasis* emph,
                       const codae_recon_loss* loss, const float* y, void* dy, int dy_bf16, int64_t dy_ld, float inv_n, float* colsum_part,
-                      double* parts, hipStream_t s);
+                      double* parts, hipStream_t s, const uint8_t* present = nullptr, int n_slots = 0);
 // Sampled-softmax slot contrast (codae_slot_contrast, include/codae_hip.h; slot_contrast.hip): an additional term on top of the
 // criterion.  prepare fills the work space with the step's S x K normalised candidates; launch_slot_contrast adds the term's
 // gradient to the dy the criterion's kernel left (operand type of the products = dy's type), leaves slot_contrast_blocks(B) rows of
@@ -454,10 +480,10 @@ int64_t slot_contrast_ws_bytes(int S, int K, int E, int bf16);
 inline int slot_contrast_blocks(int B) { return (B + 31) / 32; }
 int slot_contrast_warm();     // one-time kernel attributes, outside any stream capture
 int launch_slot_contrast_prepare(const float* data, int io, const codae_slot_contrast* c, int32_t step, const double* step_dev, int bf16,
-                                 hipStream_t s);
+                                 hipStream_t s, const uint8_t* present = nullptr, int n_slots = 0);
 int launch_slot_contrast(const codae_batch* b, const codae_noise* noise, int32_t step, const double* step_dev, const codae_emphasis* emph,
                          const codae_slot_contrast* c, const float* y, void* dy, int dy_bf16, int64_t dy_ld, float scale,
-                         float* colsum_part, double* parts, hipStream_t s);
+                         float* colsum_part, double* parts, hipStream_t s, const uint8_t* present = nullptr, int n_slots = 0);
 int launch_slot_contrast_finish(double* scalars, double scale, const double* parts, int n_parts, hipStream_t s);
 // Hidden dropout (codae_dropout, include/codae_hip.h; dropout.hip): a <- a * f in place on rows < B, columns < width of a [B][ld]
 // matrix (fp32 or bf16), f from the Philox words of counter (column / 4, dataset row, step, 1 + layer); step_dev as

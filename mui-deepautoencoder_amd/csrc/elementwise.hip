@@ -41,6 +41,28 @@ __device__ __forceinline__ uint2 pack_bf16x4(float a, float b, float c, float d)
     return o;
 }
 
+// sl[k] = slot of column c + k (E columns per slot): one division where the group sits inside one slot
+template <int W>
+__device__ __forceinline__ void slots_of(int c, int E, int* sl) {
+    const int s0 = c / E, rem = c - s0 * E;
+    if (rem + W <= E) {
+#pragma unroll
+        for (int k = 0; k < W; ++k) sl[k] = s0;
+    } else {
+#pragma unroll
+        for (int k = 0; k < W; ++k) sl[k] = s0 + (rem + k) / E;
+    }
+}
+// the gather's presence rule: exactly 0 in every column of an absent slot, behind the noise and the slot mask
+template <int W>
+__device__ __forceinline__ void zero_absent(float* v, const PresArgs& pa, int64_t row, int c) {
+    int sl[W];
+    slots_of<W>(c, pa.E, sl);
+    const uint32_t pb = present_bits<W>(pa, row, sl);
+#pragma unroll
+    for (int k = 0; k < W; ++k) v[k] = ((pb >> k) & 1u) ? v[k] : 0.f;
+}
+
 // zero_norm != null (the fused step whose loss finish rides in the bias-finish launch): the launch's first block clears the
 // clip_grad_norm_ accumulators - what finish_loss_kernel does in front of the backward when it runs as a launch of its own
 __device__ __forceinline__ void zero_norm_scalars(double* zero_norm) {
@@ -54,13 +76,14 @@ __device__ __forceinline__ void zero_norm_scalars(double* zero_norm) {
 // 8-B mask load, one 16-B store (the 4-element form stores 8 B per lane, half-width store instructions).
 // (Measured and dropped: whole rows per wave - 2 rows x up to 4 column chunks of 16-B loads in flight per lane, row index and mask
 // id read once per row: 28.0 -> 27.1 us per launch on one box, 27.3 -> 27.8 on another: inside the noise)
+template <bool PRES>
 __global__ __launch_bounds__(NT) void gather_corrupt_bf16x8_kernel(const float* __restrict__ data,
                                                                    const int32_t* __restrict__ row_idx,
                                                                    const int32_t* __restrict__ mask_id,
                                                                    const uint8_t* __restrict__ table, int B, int io,
                                                                    bf16_t* __restrict__ out,
                                                                    const int32_t* __restrict__ mask_to_use, int nb_run,
-                                                                   int run, int64_t out_ld, double* zero_norm) {
+                                                                   int run, int64_t out_ld, double* zero_norm, PresArgs pa) {
     zero_norm_scalars(zero_norm);
     const bool masked = (mask_id != nullptr) || (mask_to_use != nullptr);
     const int cols = io / 8;
@@ -79,6 +102,7 @@ __global__ __launch_bounds__(NT) void gather_corrupt_bf16x8_kernel(const float* 
 #pragma unroll
             for (int k = 0; k < 8; ++k) v[k] = (((k < 4 ? m.x : m.y) >> (8 * (k & 3))) & 0xff) ? v[k] : 0.f;
         }
+        if constexpr (PRES) zero_absent<8>(v, pa, src_row, c);
         uint4 o;
         o.x = pack_bf16x2(v[0], v[1]); o.y = pack_bf16x2(v[2], v[3]);
         o.z = pack_bf16x2(v[4], v[5]); o.w = pack_bf16x2(v[6], v[7]);
@@ -89,14 +113,14 @@ __global__ __launch_bounds__(NT) void gather_corrupt_bf16x8_kernel(const float* 
 // ---- a2 + a10: out[b][:] = data[row_idx[b]][:] * mask_table[mask_id[b]][:] -----------------
 // (collate_embedding data_tool.py:96-103 + corrupt embedding_...py:226-239 fused; the [B,io]
 // fp32 mask of Corrupter.get_masks is never materialised.)
-template <bool VEC, bool OUT_BF16>
+template <bool VEC, bool OUT_BF16, bool PRES>
 __global__ __launch_bounds__(NT) void gather_corrupt_kernel(const float* __restrict__ data,
                                                             const int32_t* __restrict__ row_idx,
                                                             const int32_t* __restrict__ mask_id,
                                                             const uint8_t* __restrict__ table, int B, int io,
                                                             void* __restrict__ out,
                                                             const int32_t* __restrict__ mask_to_use, int nb_run,
-                                                            int run, int64_t out_ld, double* zero_norm) {
+                                                            int run, int64_t out_ld, double* zero_norm, PresArgs pa) {
     zero_norm_scalars(zero_norm);
     constexpr int W = VEC ? 4 : 1;
     const bool masked = (mask_id != nullptr) || (mask_to_use != nullptr);
@@ -124,6 +148,7 @@ __global__ __launch_bounds__(NT) void gather_corrupt_kernel(const float* __restr
                 v[0] = table[(int64_t)id * io + c] ? v[0] : 0.f;
             }
         }
+        if constexpr (PRES) zero_absent<W>(v, pa, src_row, c);
         const int64_t o = (int64_t)b * out_ld + c;
         if constexpr (OUT_BF16) {
             bf16_t* op = reinterpret_cast<bf16_t*>(out) + o;
@@ -195,12 +220,12 @@ __device__ __forceinline__ float noise_apply1(float x, const uint4 r, int k, con
     }
 }
 
-template <int KIND>
+template <int KIND, bool PRES>
 __global__ __launch_bounds__(NT) void gather_noise_bf16x8_kernel(const float* __restrict__ data, const int32_t* __restrict__ row_idx,
                                                                  const int32_t* __restrict__ mask_id, const uint8_t* __restrict__ table,
                                                                  int B, int io, bf16_t* __restrict__ out,
                                                                  const int32_t* __restrict__ mask_to_use, int nb_run, int run,
-                                                                 int64_t out_ld, NoiseArgs na) {
+                                                                 int64_t out_ld, NoiseArgs na, PresArgs pa) {
     zero_norm_scalars(na.zero_norm);
     const bool masked = (mask_id != nullptr) || (mask_to_use != nullptr);
     const uint32_t step = na.step_dev ? (uint32_t)*na.step_dev : na.step;
@@ -223,6 +248,7 @@ __global__ __launch_bounds__(NT) void gather_noise_bf16x8_kernel(const float* __
 #pragma unroll
             for (int k = 0; k < 8; ++k) v[k] = (((k < 4 ? m.x : m.y) >> (8 * (k & 3))) & 0xff) ? v[k] : 0.f;
         }
+        if constexpr (PRES) zero_absent<8>(v, pa, (int64_t)nrow, c);
         uint4 o;
         o.x = pack_bf16x2(v[0], v[1]); o.y = pack_bf16x2(v[2], v[3]);
         o.z = pack_bf16x2(v[4], v[5]); o.w = pack_bf16x2(v[6], v[7]);
@@ -230,11 +256,11 @@ __global__ __launch_bounds__(NT) void gather_noise_bf16x8_kernel(const float* __
     }
 }
 
-template <bool VEC, bool OUT_BF16, int KIND>
+template <bool VEC, bool OUT_BF16, int KIND, bool PRES>
 __global__ __launch_bounds__(NT) void gather_noise_kernel(const float* __restrict__ data, const int32_t* __restrict__ row_idx,
                                                           const int32_t* __restrict__ mask_id, const uint8_t* __restrict__ table, int B,
                                                           int io, void* __restrict__ out, const int32_t* __restrict__ mask_to_use,
-                                                          int nb_run, int run, int64_t out_ld, NoiseArgs na) {
+                                                          int nb_run, int run, int64_t out_ld, NoiseArgs na, PresArgs pa) {
     zero_norm_scalars(na.zero_norm);
     constexpr int W = VEC ? 4 : 1;
     const bool masked = (mask_id != nullptr) || (mask_to_use != nullptr);
@@ -267,6 +293,7 @@ __global__ __launch_bounds__(NT) void gather_noise_kernel(const float* __restric
                 v[0] = table[(int64_t)id * io + c] ? v[0] : 0.f;
             }
         }
+        if constexpr (PRES) zero_absent<W>(v, pa, (int64_t)nrow, c);
         const int64_t o = (int64_t)b * out_ld + c;
         if constexpr (OUT_BF16) {
             bf16_t* op = reinterpret_cast<bf16_t*>(out) + o;
@@ -338,7 +365,10 @@ __global__ __launch_bounds__(NT) void expand_masks_kernel(const int32_t* __restr
 //   SQ_PARTIAL += sum (1-fmask)(x-y)^2               (:223)
 constexpr int LOSS_ROWS = 32;   // rows per block = rows per partial column-sum row
 constexpr int LOSS_UNROLL = 8;  // rows in flight per thread
-template <bool VEC, bool DY_BF16>
+// PRES (a presence table is set): an absent element's x and y are SELECTED to 0 as they are loaded - x may be NaN there -, so it
+// adds exact zeros to every sum, and its stored dy is +0.  The arithmetic between the loads and the stores is the text of the
+// instantiation without a table: an all-ones table gives its bits.
+template <bool VEC, bool DY_BF16, bool PRES>
 __global__ __launch_bounds__(NT) void mse_loss_kernel(const float* __restrict__ data,
                                                       const int32_t* __restrict__ row_idx,
                                                       const int32_t* __restrict__ mask_id,
@@ -346,7 +376,8 @@ __global__ __launch_bounds__(NT) void mse_loss_kernel(const float* __restrict__ 
                                                       const float* __restrict__ y, void* __restrict__ dy,
                                                       float inv_n, float* __restrict__ colsum_part,
                                                       double* __restrict__ loss_parts, int want_grad,
-                                                      const int32_t* __restrict__ mask_to_use, int nb_run, int run, int64_t dy_ld) {
+                                                      const int32_t* __restrict__ mask_to_use, int nb_run, int run, int64_t dy_ld,
+                                                      PresArgs pa) {
     __shared__ float red[4];
     const bool masked = (mask_id != nullptr) || (mask_to_use != nullptr);
     constexpr int W = VEC ? 4 : 1;
@@ -355,6 +386,8 @@ __global__ __launch_bounds__(NT) void mse_loss_kernel(const float* __restrict__ 
     float sq = 0.f, sqp = 0.f;
     for (int cv = threadIdx.x; cv < cols; cv += NT) {
         const int c = cv * W;
+        int sl[W];
+        if constexpr (PRES) slots_of<W>(c, pa.E, sl);
         float cs[4] = {0.f, 0.f, 0.f, 0.f};
         // rows are independent: unrolled with clamped (always valid) addresses so that the loads of
         // all LOSS_ROWS rows are in flight together; rows past the batch contribute nothing
@@ -379,6 +412,13 @@ __global__ __launch_bounds__(NT) void mse_loss_kernel(const float* __restrict__ 
                 yv[0] = y[(int64_t)b * io + c];
                 if (masked) m = table[(int64_t)id * io + c];
             }
+            uint32_t pb = 0xfu;
+            if constexpr (PRES) {
+                pb = present_bits<W>(pa, src_row, sl);
+#pragma unroll
+                for (int k = 0; k < W; ++k)
+                    if (!((pb >> k) & 1u)) { xv[k] = 0.f; yv[k] = 0.f; }
+            }
             float g[4];
 #pragma unroll
             for (int k = 0; k < W; ++k) {
@@ -388,6 +428,10 @@ __global__ __launch_bounds__(NT) void mse_loss_kernel(const float* __restrict__ 
                 if (((m >> (8 * k)) & 0xff) == 0) sqp += se;
                 g[k] = -2.f * d * inv_n;
                 cs[k] += g[k];
+            }
+            if constexpr (PRES) {      // (-2 * 0 is -0: the column sum does not see the sign, the stored gradient is +0)
+#pragma unroll
+                for (int k = 0; k < W; ++k) g[k] = ((pb >> k) & 1u) ? g[k] : 0.f;
             }
             if (want_grad && live) {
                 const int64_t o = (int64_t)b * dy_ld + c;
@@ -432,13 +476,15 @@ struct EmphArgs {
     const double* step_dev;    // ... or, when not null, *step_dev (graph replay)
 };
 
-template <bool VEC, bool DY_BF16>
+// PRES: as in mse_loss_kernel - x and y selected to 0 at the loads, +0 at the store: selection, not a weight of 0, so a NaN in an
+// absent element of x reaches nothing.
+template <bool VEC, bool DY_BF16, bool PRES>
 __global__ __launch_bounds__(NT) void emph_loss_kernel(const float* __restrict__ data, const int32_t* __restrict__ row_idx,
                                                        const int32_t* __restrict__ mask_id, const uint8_t* __restrict__ table,
                                                        int B, int io, const float* __restrict__ y, void* __restrict__ dy,
                                                        float inv_n, float* __restrict__ colsum_part, double* __restrict__ parts,
                                                        const int32_t* __restrict__ mask_to_use, int nb_run, int run, int64_t dy_ld,
-                                                       EmphArgs ea) {
+                                                       EmphArgs ea, PresArgs pa) {
     __shared__ float red[4];
     const bool masked = (mask_id != nullptr) || (mask_to_use != nullptr);
     const uint32_t step = ea.step_dev ? (uint32_t)*ea.step_dev : ea.step;
@@ -448,6 +494,8 @@ __global__ __launch_bounds__(NT) void emph_loss_kernel(const float* __restrict__
     float wsq = 0.f, sq = 0.f, sqp = 0.f;
     for (int cv = threadIdx.x; cv < cols; cv += NT) {
         const int c = cv * W;
+        int sl[W];
+        if constexpr (PRES) slots_of<W>(c, pa.E, sl);
         float cw[4] = {1.f, 1.f, 1.f, 1.f};
         if (ea.col_weight != nullptr) {
             if constexpr (VEC) {
@@ -492,6 +540,13 @@ __global__ __launch_bounds__(NT) void emph_loss_kernel(const float* __restrict__
                     hit[0] = (uint64_t)rk < ea.thresh;
                 }
             }
+            uint32_t pb = 0xfu;
+            if constexpr (PRES) {
+                pb = present_bits<W>(pa, src_row, sl);
+#pragma unroll
+                for (int k = 0; k < W; ++k)
+                    if (!((pb >> k) & 1u)) { xv[k] = 0.f; yv[k] = 0.f; }
+            }
             float g[4];
 #pragma unroll
             for (int k = 0; k < W; ++k) {
@@ -504,6 +559,10 @@ __global__ __launch_bounds__(NT) void emph_loss_kernel(const float* __restrict__
                 if (blank) sqp += se;
                 g[k] = -2.f * d * (w * inv_n);
                 cs[k] += g[k];
+            }
+            if constexpr (PRES) {      // (the stored gradient of an absent element is +0, not the product's -0)
+#pragma unroll
+                for (int k = 0; k < W; ++k) g[k] = ((pb >> k) & 1u) ? g[k] : 0.f;
             }
             if (live) {
                 const int64_t o = (int64_t)b * dy_ld + c;
@@ -1015,9 +1074,20 @@ inline bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) ==
 
 }  // namespace
 
-int launch_gather_corrupt(const codae_batch* b, void* out, int out_bf16, hipStream_t s, int64_t out_ld, double* zero_norm) {
+int check_presence(const uint8_t* present, int n_slots, int io, const char* who) {
+    if (present == nullptr) return CODAE_OK;
+    CODAE_REQUIRE(n_slots >= 1 && n_slots <= 128, "%s: slot presence takes 1 .. 128 slots, got %d", who, n_slots);
+    CODAE_REQUIRE(io > 0 && io % n_slots == 0, "%s: slot presence: n_slots %d does not divide io %d", who, n_slots, io);
+    return CODAE_OK;
+}
+
+int launch_gather_corrupt(const codae_batch* b, void* out, int out_bf16, hipStream_t s, int64_t out_ld, double* zero_norm,
+                          const uint8_t* present, int n_slots) {
     if (out_ld <= 0) out_ld = b ? b->io : 0;
     CODAE_REQUIRE(b && b->data && out && b->B > 0 && b->io > 0, "gather_corrupt: bad batch");
+    int prc = check_presence(present, n_slots, b->io, "gather_corrupt");
+    if (prc) return prc;
+    const PresArgs pa{present, n_slots, present ? b->io / n_slots : 0};
     const bool masked = b->mask_id || b->mask_to_use;
     CODAE_REQUIRE(!masked || b->mask_table, "gather_corrupt: mask ids without mask_table");
     CODAE_REQUIRE(!b->mask_to_use || b->mask_id || (b->nb_run > 0 && b->run >= 0 && b->run < b->nb_run),
@@ -1026,18 +1096,23 @@ int launch_gather_corrupt(const codae_batch* b, void* out, int out_bf16, hipStre
     const int64_t items = (int64_t)b->B * (vec ? b->io / 4 : b->io);
     const int grid = grid_for(items);
     if (vec && out_bf16 && b->io % 8 == 0 && (!masked || (reinterpret_cast<uintptr_t>(b->mask_table) & 7) == 0)) {
-        hipLaunchKernelGGL(gather_corrupt_bf16x8_kernel, dim3(grid_for(items / 2)), dim3(NT), 0, s, b->data, b->row_idx, b->mask_id,
-                           b->mask_table, b->B, b->io, reinterpret_cast<bf16_t*>(out), b->mask_to_use, b->nb_run, b->run, out_ld, zero_norm);
+#define GC8(P) hipLaunchKernelGGL((gather_corrupt_bf16x8_kernel<P>), dim3(grid_for(items / 2)), dim3(NT), 0, s, b->data, b->row_idx, b->mask_id, \
+                                  b->mask_table, b->B, b->io, reinterpret_cast<bf16_t*>(out), b->mask_to_use, b->nb_run, b->run, out_ld, zero_norm, pa)
+        if (present) GC8(true);
+        else GC8(false);
+#undef GC8
         CODAE_LAUNCH_CHECK();
         return CODAE_OK;
     }
-#define GC(V, O) hipLaunchKernelGGL((gather_corrupt_kernel<V, O>), dim3(grid), dim3(NT), 0, s, b->data, b->row_idx, \
-                                    b->mask_id, b->mask_table, b->B, b->io, out, b->mask_to_use, b->nb_run, b->run, out_ld, zero_norm)
+#define GCP(V, O, P) hipLaunchKernelGGL((gather_corrupt_kernel<V, O, P>), dim3(grid), dim3(NT), 0, s, b->data, b->row_idx, \
+                                    b->mask_id, b->mask_table, b->B, b->io, out, b->mask_to_use, b->nb_run, b->run, out_ld, zero_norm, pa)
+#define GC(V, O) do { if (present) GCP(V, O, true); else GCP(V, O, false); } while (0)
     if (vec && out_bf16) GC(true, true);
     else if (vec) GC(true, false);
     else if (out_bf16) GC(false, true);
     else GC(false, false);
 #undef GC
+#undef GCP
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;
 }
@@ -1061,10 +1136,17 @@ int check_noise(const codae_noise* n) {
 }
 
 int launch_gather_noise(const codae_batch* b, const codae_noise* noise, int32_t step, const double* step_dev, void* out, int out_bf16,
-                        hipStream_t s, int64_t out_ld, const int32_t* noise_rows, double* zero_norm) {
-    if (noise == nullptr || noise->kind == CODAE_NOISE_NONE) return launch_gather_corrupt(b, out, out_bf16, s, out_ld, zero_norm);
+                        hipStream_t s, int64_t out_ld, const int32_t* noise_rows, double* zero_norm, const uint8_t* present, int n_slots) {
+    if (noise == nullptr || noise->kind == CODAE_NOISE_NONE) {
+        // (the plain gather keys the table by the row it reads: a batch gathered by the caller has lost its dataset rows)
+        CODAE_REQUIRE(present == nullptr || noise_rows == nullptr, "gather_corrupt: a presence table with noise_rows needs an input noise kind");
+        return launch_gather_corrupt(b, out, out_bf16, s, out_ld, zero_norm, present, n_slots);
+    }
     int rc = check_noise(noise);
     if (rc) return rc;
+    rc = check_presence(present, n_slots, b ? b->io : 0, "gather_corrupt");
+    if (rc) return rc;
+    const PresArgs pa{present, n_slots, present ? b->io / n_slots : 0};
     if (out_ld <= 0) out_ld = b ? b->io : 0;
     CODAE_REQUIRE(b && b->data && out && b->B > 0 && b->io > 0, "gather_corrupt: bad batch");
     const bool masked = b->mask_id || b->mask_to_use;
@@ -1080,10 +1162,12 @@ int launch_gather_noise(const codae_batch* b, const codae_noise* noise, int32_t 
     const int64_t items = (int64_t)b->B * (vec ? b->io / 4 : b->io);
     const int grid = grid_for(items);
     const bool x8 = vec && out_bf16 && b->io % 8 == 0 && (!masked || (reinterpret_cast<uintptr_t>(b->mask_table) & 7) == 0);
-#define GN8(K) hipLaunchKernelGGL((gather_noise_bf16x8_kernel<K>), dim3(grid_for(items / 2)), dim3(NT), 0, s, b->data, b->row_idx, b->mask_id, \
-                                  b->mask_table, b->B, b->io, reinterpret_cast<bf16_t*>(out), b->mask_to_use, b->nb_run, b->run, out_ld, na)
-#define GN(V, O, K) hipLaunchKernelGGL((gather_noise_kernel<V, O, K>), dim3(grid), dim3(NT), 0, s, b->data, b->row_idx, b->mask_id, \
-                                       b->mask_table, b->B, b->io, out, b->mask_to_use, b->nb_run, b->run, out_ld, na)
+#define GN8P(K, P) hipLaunchKernelGGL((gather_noise_bf16x8_kernel<K, P>), dim3(grid_for(items / 2)), dim3(NT), 0, s, b->data, b->row_idx, b->mask_id, \
+                                  b->mask_table, b->B, b->io, reinterpret_cast<bf16_t*>(out), b->mask_to_use, b->nb_run, b->run, out_ld, na, pa)
+#define GNP(V, O, K, P) hipLaunchKernelGGL((gather_noise_kernel<V, O, K, P>), dim3(grid), dim3(NT), 0, s, b->data, b->row_idx, b->mask_id, \
+                                       b->mask_table, b->B, b->io, out, b->mask_to_use, b->nb_run, b->run, out_ld, na, pa)
+#define GN8(K) do { if (present) GN8P(K, true); else GN8P(K, false); } while (0)
+#define GN(V, O, K) do { if (present) GNP(V, O, K, true); else GNP(V, O, K, false); } while (0)
 #define GN_KIND(K)                           \
     do {                                     \
         if (x8) GN8(K);                      \
@@ -1098,6 +1182,8 @@ int launch_gather_noise(const codae_batch* b, const codae_noise* noise, int32_t 
 #undef GN_KIND
 #undef GN
 #undef GN8
+#undef GNP
+#undef GN8P
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;
 }
@@ -1143,23 +1229,28 @@ int launch_expand_masks(const int32_t* mask_id, const uint8_t* table, const int3
 int mse_loss_colsum_rows(int B) { return (B + LOSS_ROWS - 1) / LOSS_ROWS; }
 
 int launch_mse_loss(const codae_batch* b, const float* y, void* dy, int dy_bf16, float inv_n, float* colsum_part,
-                    double* loss_parts, int want_grad, hipStream_t s, int64_t dy_ld) {
+                    double* loss_parts, int want_grad, hipStream_t s, int64_t dy_ld, const uint8_t* present, int n_slots) {
     if (dy_ld <= 0) dy_ld = b ? b->io : 0;
     CODAE_REQUIRE(b && b->data && y && loss_parts && b->B > 0 && b->io > 0, "mse_loss: bad args");
+    int prc = check_presence(present, n_slots, b->io, "mse_loss");
+    if (prc) return prc;
+    const PresArgs pa{present, n_slots, present ? b->io / n_slots : 0};
     CODAE_REQUIRE(!want_grad || dy, "mse_loss: gradient requested without dy");
     const bool masked = b->mask_id || b->mask_to_use;
     CODAE_REQUIRE(!masked || b->mask_table, "mse_loss: mask ids without mask_table");
     const bool vec = (b->io % 4 == 0) && (dy_ld % 4 == 0) && a16(b->data) && a16(y) && (!dy || a16(dy)) &&
                      (!masked || (reinterpret_cast<uintptr_t>(b->mask_table) & 3) == 0);
     const int grid = (b->B + LOSS_ROWS - 1) / LOSS_ROWS;
-#define ML(V, O) hipLaunchKernelGGL((mse_loss_kernel<V, O>), dim3(grid), dim3(NT), 0, s, b->data, b->row_idx, \
+#define MLP(V, O, P) hipLaunchKernelGGL((mse_loss_kernel<V, O, P>), dim3(grid), dim3(NT), 0, s, b->data, b->row_idx, \
                                     b->mask_id, b->mask_table, b->B, b->io, y, dy, inv_n, colsum_part, loss_parts, want_grad, \
-                                    b->mask_to_use, b->nb_run, b->run, dy_ld)
+                                    b->mask_to_use, b->nb_run, b->run, dy_ld, pa)
+#define ML(V, O) do { if (present) MLP(V, O, true); else MLP(V, O, false); } while (0)
     if (vec && dy_bf16) ML(true, true);
     else if (vec) ML(true, false);
     else if (dy_bf16) ML(false, true);
     else ML(false, false);
 #undef ML
+#undef MLP
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;
 }
@@ -1173,9 +1264,12 @@ int check_emphasis(const codae_emphasis* e) {
 
 int launch_emph_loss(const codae_batch* b, const codae_noise* noise, int32_t step, const double* step_dev, const codae_emphasis* emph,
                      const float* y, void* dy, int dy_bf16, int64_t dy_ld, float inv_n, float* colsum_part, double* parts,
-                     hipStream_t s) {
+                     hipStream_t s, const uint8_t* present, int n_slots) {
     if (dy_ld <= 0) dy_ld = b ? b->io : 0;
     CODAE_REQUIRE(b && b->data && y && dy && parts && emph && b->B > 0 && b->io > 0, "emph_loss: bad args");
+    int prc = check_presence(present, n_slots, b->io, "emph_loss");
+    if (prc) return prc;
+    const PresArgs pa{present, n_slots, present ? b->io / n_slots : 0};
     CODAE_REQUIRE(dy_ld >= b->io, "emph_loss: dy_ld %lld below io %d", (long long)dy_ld, b->io);
     int rc = check_emphasis(emph);
     if (rc) return rc;
@@ -1196,14 +1290,16 @@ int launch_emph_loss(const codae_batch* b, const codae_noise* noise, int32_t ste
     const bool vec = (b->io % 4 == 0) && (dy_ld % 4 == 0) && a16(b->data) && a16(y) && a16(dy) &&
                      (!emph->col_weight || a16(emph->col_weight)) && (!masked || (reinterpret_cast<uintptr_t>(b->mask_table) & 3) == 0);
     const int grid = mse_loss_colsum_rows(b->B);
-#define EL(V, O) hipLaunchKernelGGL((emph_loss_kernel<V, O>), dim3(grid), dim3(NT), 0, s, b->data, b->row_idx, b->mask_id, \
+#define ELP(V, O, P) hipLaunchKernelGGL((emph_loss_kernel<V, O, P>), dim3(grid), dim3(NT), 0, s, b->data, b->row_idx, b->mask_id, \
                                     b->mask_table, b->B, b->io, y, dy, inv_n, colsum_part, parts, b->mask_to_use, b->nb_run, b->run, \
-                                    dy_ld, ea)
+                                    dy_ld, ea, pa)
+#define EL(V, O) do { if (present) ELP(V, O, true); else ELP(V, O, false); } while (0)
     if (vec && dy_bf16) EL(true, true);
     else if (vec) EL(true, false);
     else if (dy_bf16) EL(false, true);
     else EL(false, false);
 #undef EL
+#undef ELP
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;
 }

@@ -103,6 +103,8 @@ struct codae_engine {
     bool recon_on = false;
     codae_slot_contrast contrast{};  // slot contrast on top of the criterion (codae_set_slot_contrast); all zero = off
     bool contrast_on = false;
+    // per-row slot presence (codae_set_slot_presence): table null = off.  Built field by field: the graph key compares bytes.
+    struct PresCfg { const uint8_t* table; int64_t n_rows; int32_t n_slots; int32_t reserved; } pres{};
     codae_optimizer opt{};           // optimizer and schedule of the update (codae_set_optimizer), canonical form; all zero = the default
     int graph_captures = 0;          // captures of codae_train_step_graph since codae_create
     // hidden dropout of the training steps (codae_set_hidden_dropout): p[l] of layer l's output, all zero = off.  The backward entry
@@ -132,7 +134,7 @@ struct codae_engine {
     // codae_train_step_graph: the captured step and what it was captured for
     hipGraphExec_t graph_exec = nullptr;
     bool capturing = false;          // inside stream capture: device-side Adam step, everything joined at the end
-    struct GraphKey { codae_batch batch; codae_hyper hyper; codae_buffers bufs; codae_noise noise; codae_emphasis emph; bool emph_on; DropCfg drop; codae_recon_loss recon; codae_slot_contrast contrast; codae_optimizer opt; } graph_key{};
+    struct GraphKey { codae_batch batch; codae_hyper hyper; codae_buffers bufs; codae_noise noise; codae_emphasis emph; bool emph_on; DropCfg drop; codae_recon_loss recon; codae_slot_contrast contrast; codae_optimizer opt; PresCfg pres; } graph_key{};
     std::vector<hipEvent_t> prof_start, prof_stop;
     std::vector<int> prof_kind;
     std::vector<int> prof_count;    // launches covered by the record (a GroupScope spans several)
@@ -356,8 +358,8 @@ constexpr int CHAIN_MAX_ROWS = 2048;
 
 bool chain_eligible(codae_engine* e, const codae_buffers* b, int B) {
     // (the chain kernel fuses the plain gather and the unweighted loss and keeps the activations to itself: a noised input, an
-    //  emphasised loss, another criterion or hidden dropout takes the per-layer launches)
-    return e->chain_ok && e->noise.kind == CODAE_NOISE_NONE && !e->emph_on && !e->recon_on && !e->contrast_on && !e->drop.on && b->shadow_wt != nullptr && e->rows_for(B) <= CHAIN_MAX_ROWS;
+    //  emphasised loss, another criterion, hidden dropout or a slot-presence table takes the per-layer launches)
+    return e->chain_ok && e->noise.kind == CODAE_NOISE_NONE && !e->emph_on && !e->recon_on && !e->contrast_on && !e->drop.on && e->pres.table == nullptr && b->shadow_wt != nullptr && e->rows_for(B) <= CHAIN_MAX_ROWS;
 }
 
 // gather + forward chain + loss (+ data-gradient chain) of a narrow stack: one launch; then the loss finish
@@ -1121,13 +1123,14 @@ static int run_slot_contrast(codae_handle h, const codae_buffers* b, const codae
     int rc;
     {
         ProfScope prof(h, CODAE_K_LOSS, s);
-        rc = launch_slot_contrast_prepare(batch->data, batch->io, &h->contrast, hyper->step, step_dev, bf, s);
+        rc = launch_slot_contrast_prepare(batch->data, batch->io, &h->contrast, hyper->step, step_dev, bf, s, h->pres.table, h->pres.n_slots);
     }
     if (rc) return rc;
     {
         ProfScope prof(h, CODAE_K_LOSS, s);
         rc = launch_slot_contrast(batch, &h->noise, hyper->step, step_dev, h->emph_on ? &h->emph : nullptr, &h->contrast, y,
-                                  dact_ptr(h, b, L - 1), bf, h->out_ld[L - 1], (float)scale, part_ptr(h, b, L - 1), loss_parts_ptr(h, b), s);
+                                  dact_ptr(h, b, L - 1), bf, h->out_ld[L - 1], (float)scale, part_ptr(h, b, L - 1), loss_parts_ptr(h, b), s,
+                                  h->pres.table, h->pres.n_slots);
     }
     if (rc) return rc;
     h->parts_pending[L - 1] = blocks;
@@ -1157,16 +1160,20 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
     if (h->drop_live) { h->drop_B = B; h->drop_rows = batch->row_idx; h->drop_step = hyper->step; }
     // bf16 training step: the loss is folded into the last forward GEMM's epilogue (y never stored)
     // (not with loss emphasis or a criterion other than the MSE: those live in stand-alone kernels, below)
-    const bool fuse_loss = bf && hyper != nullptr && out_y == nullptr && !h->cfg.no_fused_loss && !h->emph_on && !h->recon_on && !h->contrast_on;
+    // (nor with a slot-presence table: the stand-alone kernels carry the predicate, the GEMM epilogue does not)
+    const uint8_t* const pres = h->pres.table;
+    const int pres_slots = h->pres.n_slots;
+    const bool fuse_loss = bf && hyper != nullptr && out_y == nullptr && !h->cfg.no_fused_loss && !h->emph_on && !h->recon_on && !h->contrast_on &&
+                           pres == nullptr;
     const bool fold_finish = fuse_loss && fold != nullptr && !h->cfg.no_folded_loss_finish;
     {
         ProfScope prof(h, CODAE_K_GATHER, s);
         double* zero_norm = fold_finish ? b->scalars : nullptr;
         if (hyper != nullptr && h->noise.kind != CODAE_NOISE_NONE)      // training input only; the loss below reads the clean row
             rc = launch_gather_noise(batch, &h->noise, hyper->step, h->capturing ? b->scalars + CODAE_S_ADAM_STEP : nullptr,
-                                     act_ptr(h, b, 0), bf, s, h->in_ld[0], nullptr, zero_norm);
+                                     act_ptr(h, b, 0), bf, s, h->in_ld[0], nullptr, zero_norm, pres, pres_slots);
         else
-            rc = launch_gather_corrupt(batch, act_ptr(h, b, 0), bf, s, h->in_ld[0], zero_norm);
+            rc = launch_gather_corrupt(batch, act_ptr(h, b, 0), bf, s, h->in_ld[0], zero_norm, pres, pres_slots);
     }
     if (rc) return rc;
     rc = zero_pad_rows(h, act_ptr(h, b, 0), B, rows, h->in_ld[0], s);
@@ -1223,7 +1230,7 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
                 ProfScope prof(h, CODAE_K_LOSS, s);
                 rc = launch_recon_loss(batch, &h->noise, hyper->step, h->capturing ? b->scalars + CODAE_S_ADAM_STEP : nullptr,
                                        h->emph_on ? &h->emph : nullptr, &h->recon, y, dact_ptr(h, b, L - 1), bf, h->out_ld[L - 1], (float)inv_n,
-                                       part_ptr(h, b, L - 1), loss_parts_ptr(h, b), s);
+                                       part_ptr(h, b, L - 1), loss_parts_ptr(h, b), s, pres, pres_slots);
             }
             if (rc) return rc;
             h->parts_pending[L - 1] = mse_loss_colsum_rows(B);
@@ -1231,12 +1238,15 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
             rc = launch_finish_emph_loss(b->scalars, inv_n, s, loss_parts_ptr(h, b), mse_loss_colsum_rows(B));
             return rc ? rc : run_slot_contrast(h, b, batch, hyper, y, s);
         }
-        if (h->emph_on) {
+        if (h->emph_on || pres != nullptr) {       // (a table without emphasis: the same kernel with unit weights)
             const double inv_n = loss_inv_n(hyper, batch);
+            codae_emphasis unit{};
+            unit.alpha = 1.f; unit.beta = 1.f;
             {
                 ProfScope prof(h, CODAE_K_LOSS, s);
-                rc = launch_emph_loss(batch, &h->noise, hyper->step, h->capturing ? b->scalars + CODAE_S_ADAM_STEP : nullptr, &h->emph, y,
-                                      dact_ptr(h, b, L - 1), bf, h->out_ld[L - 1], (float)inv_n, part_ptr(h, b, L - 1), loss_parts_ptr(h, b), s);
+                rc = launch_emph_loss(batch, &h->noise, hyper->step, h->capturing ? b->scalars + CODAE_S_ADAM_STEP : nullptr,
+                                      h->emph_on ? &h->emph : &unit, y, dact_ptr(h, b, L - 1), bf, h->out_ld[L - 1], (float)inv_n,
+                                      part_ptr(h, b, L - 1), loss_parts_ptr(h, b), s, pres, pres_slots);
             }
             if (rc) return rc;
             h->parts_pending[L - 1] = mse_loss_colsum_rows(B);
@@ -1255,7 +1265,7 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
         rc = finish_loss(h, b, batch, mse_loss_colsum_rows(B), s);
         return rc ? rc : run_slot_contrast(h, b, batch, hyper, y, s);
     }
-    rc = launch_mse_loss(batch, y, nullptr, 0, 0.f, nullptr, loss_parts_ptr(h, b), 0, s);
+    rc = launch_mse_loss(batch, y, nullptr, 0, 0.f, nullptr, loss_parts_ptr(h, b), 0, s, 0, pres, pres_slots);
     if (rc) return rc;
     return finish_loss(h, b, batch, mse_loss_colsum_rows(B), s);
 }
@@ -1294,6 +1304,8 @@ int codae_set_recon_loss(codae_handle h, const codae_recon_loss* loss) {
     CODAE_REQUIRE(h != nullptr, "codae_set_recon_loss: null handle");
     int rc = check_recon_loss(loss, h->out[h->L - 1]);
     if (rc) return rc;
+    CODAE_REQUIRE(loss == nullptr || loss->kind != CODAE_LOSS_SLOT_COSINE || h->pres.table == nullptr || loss->n_slots == h->pres.n_slots,
+                  "codae_set_recon_loss: slot_cosine n_slots %d differs from the presence table's %d", loss->n_slots, h->pres.n_slots);
     codae_recon_loss r{};                // (built field by field: the graph key compares bytes)
     const bool on = loss != nullptr && loss->kind != CODAE_LOSS_MSE;
     if (on) {
@@ -1310,6 +1322,10 @@ int codae_set_slot_contrast(codae_handle h, const codae_slot_contrast* contrast)
     CODAE_REQUIRE(h != nullptr, "codae_set_slot_contrast: null handle");
     int rc = check_slot_contrast(contrast, h->out[h->L - 1], h->prec == CODAE_PREC_BF16);
     if (rc) return rc;
+    CODAE_REQUIRE(contrast == nullptr || contrast->weight == 0.f || h->pres.table == nullptr ||
+                      (contrast->n_slots == h->pres.n_slots && (int64_t)contrast->n_rows <= h->pres.n_rows),
+                  "codae_set_slot_contrast: n_slots %d / n_rows %d do not fit the presence table (%d slots, %lld rows)", contrast->n_slots,
+                  contrast->n_rows, h->pres.n_slots, (long long)h->pres.n_rows);
     codae_slot_contrast c{};             // (built field by field: the graph key compares bytes)
     const bool on = contrast != nullptr && contrast->weight != 0.f;
     if (on) {
@@ -1321,6 +1337,24 @@ int codae_set_slot_contrast(codae_handle h, const codae_slot_contrast* contrast)
     }
     h->contrast = c;
     h->contrast_on = on;
+    return CODAE_OK;
+}
+
+int codae_set_slot_presence(codae_handle h, const uint8_t* present, int64_t n_rows, int32_t n_slots) {
+    CODAE_REQUIRE(h != nullptr, "codae_set_slot_presence: null handle");
+    codae_engine::PresCfg p{};           // (built field by field: the graph key compares bytes, padding included)
+    if (present != nullptr) {
+        int rc = check_presence(present, n_slots, h->out[h->L - 1], "codae_set_slot_presence");
+        if (rc) return rc;
+        CODAE_REQUIRE(n_rows >= 1, "codae_set_slot_presence: n_rows %lld must be >= 1", (long long)n_rows);
+        CODAE_REQUIRE(!(h->recon_on && h->recon.kind == CODAE_LOSS_SLOT_COSINE) || h->recon.n_slots == n_slots,
+                      "codae_set_slot_presence: n_slots %d differs from slot_cosine's %d", n_slots, h->recon.n_slots);
+        CODAE_REQUIRE(!h->contrast_on || (h->contrast.n_slots == n_slots && (int64_t)h->contrast.n_rows <= n_rows),
+                      "codae_set_slot_presence: %d slots / %lld rows do not fit the slot contrast (%d slots, %d rows)", n_slots,
+                      (long long)n_rows, h->contrast.n_slots, h->contrast.n_rows);
+        p.table = present; p.n_rows = n_rows; p.n_slots = n_slots;
+    }
+    h->pres = p;
     return CODAE_OK;
 }
 
@@ -1536,7 +1570,7 @@ int codae_train_step_graph(codae_handle h, const codae_buffers* b, const codae_b
                        !same_bytes(&h->graph_key.emph, &h->emph, sizeof(h->emph)) || h->graph_key.emph_on != h->emph_on ||
                        !same_bytes(&h->graph_key.drop, &h->drop, sizeof(h->drop)) || !same_bytes(&h->graph_key.recon, &h->recon, sizeof(h->recon)) ||
                        !same_bytes(&h->graph_key.contrast, &h->contrast, sizeof(h->contrast)) ||
-                       !same_bytes(&h->graph_key.opt, &h->opt, sizeof(h->opt));
+                       !same_bytes(&h->graph_key.opt, &h->opt, sizeof(h->opt)) || !same_bytes(&h->graph_key.pres, &h->pres, sizeof(h->pres));
     if (fresh) {
         if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
         int rc = check_common(h, b, batch->B);
@@ -1566,7 +1600,7 @@ int codae_train_step_graph(codae_handle h, const codae_buffers* b, const codae_b
             return CODAE_E_HIP;
         }
         h->graph_key.batch = *batch; h->graph_key.hyper = hk; h->graph_key.bufs = *b; h->graph_key.noise = h->noise; h->graph_key.emph = h->emph; h->graph_key.emph_on = h->emph_on;
-        h->graph_key.drop = h->drop; h->graph_key.recon = h->recon; h->graph_key.contrast = h->contrast; h->graph_key.opt = h->opt;
+        h->graph_key.drop = h->drop; h->graph_key.recon = h->recon; h->graph_key.contrast = h->contrast; h->graph_key.opt = h->opt; h->graph_key.pres = h->pres;
         ++h->graph_captures;
     }
     int rc = launch_set_scalar(b->scalars + CODAE_S_ADAM_STEP, (double)hyper->step, s);

@@ -67,6 +67,43 @@ int codae_emph_loss(const codae_batch* batch, const codae_noise* noise, int32_t 
     return launch_emph_loss(batch, noise, step, nullptr, emphasis, y, dy, dy_bf16, dy_ld, inv_n, colsum_part, parts, (hipStream_t)stream);
 }
 
+int codae_corrupt_batch_present(const codae_batch* batch, const codae_noise* noise, int32_t step, const int32_t* noise_rows, void* out,
+                                int32_t out_bf16, int64_t out_ld, const uint8_t* present, int32_t n_slots, void* stream) {
+    CODAE_REQUIRE(noise_rows == nullptr || (batch != nullptr && batch->row_idx == nullptr), "codae_corrupt_batch_present: noise_rows go with an already gathered batch (row_idx NULL)");
+    return launch_gather_noise(batch, noise, step, nullptr, out, out_bf16, (hipStream_t)stream, out_ld, noise_rows, nullptr, present, n_slots);
+}
+
+int codae_mse_loss_present(const codae_batch* batch, const float* y, void* dy, int32_t dy_bf16, int64_t dy_ld, float inv_n,
+                           float* colsum_part, double* parts, const uint8_t* present, int32_t n_slots, void* stream) {
+    return launch_mse_loss(batch, y, dy, dy_bf16, inv_n, colsum_part, parts, dy != nullptr, (hipStream_t)stream, dy_ld, present, n_slots);
+}
+
+int codae_emph_loss_present(const codae_batch* batch, const codae_noise* noise, int32_t step, const codae_emphasis* emphasis, const float* y,
+                            void* dy, int32_t dy_bf16, int64_t dy_ld, float inv_n, float* colsum_part, double* parts,
+                            const uint8_t* present, int32_t n_slots, void* stream) {
+    return launch_emph_loss(batch, noise, step, nullptr, emphasis, y, dy, dy_bf16, dy_ld, inv_n, colsum_part, parts, (hipStream_t)stream,
+                            present, n_slots);
+}
+
+int codae_recon_loss_fwd_bwd_present(const codae_batch* batch, const codae_noise* noise, int32_t step, const codae_emphasis* emphasis,
+                                     const codae_recon_loss* loss, const float* y, void* dy, int32_t dy_bf16, int64_t dy_ld, float inv_n,
+                                     float* colsum_part, double* parts, const uint8_t* present, int32_t n_slots, void* stream) {
+    return launch_recon_loss(batch, noise, step, nullptr, emphasis, loss, y, dy, dy_bf16, dy_ld, inv_n, colsum_part, parts, (hipStream_t)stream,
+                             present, n_slots);
+}
+
+int codae_slot_contrast_prepare_present(const float* data, int32_t io, const codae_slot_contrast* contrast, int32_t step, int32_t bf16,
+                                        const uint8_t* present, int32_t n_slots, void* stream) {
+    return launch_slot_contrast_prepare(data, io, contrast, step, nullptr, bf16, (hipStream_t)stream, present, n_slots);
+}
+
+int codae_slot_contrast_fwd_bwd_present(const codae_batch* batch, const codae_noise* noise, int32_t step, const codae_emphasis* emphasis,
+                                        const codae_slot_contrast* contrast, const float* y, void* dy, int32_t dy_bf16, int64_t dy_ld,
+                                        float scale, float* colsum_part, double* parts, const uint8_t* present, int32_t n_slots, void* stream) {
+    return launch_slot_contrast(batch, noise, step, nullptr, emphasis, contrast, y, dy, dy_bf16, dy_ld, scale, colsum_part, parts,
+                                (hipStream_t)stream, present, n_slots);
+}
+
 int codae_emph_loss_blocks(int32_t B) { return B > 0 ? mse_loss_colsum_rows(B) : 0; }
 
 int codae_recon_loss_fwd_bwd(const codae_batch* batch, const codae_noise* noise, int32_t step, const codae_emphasis* emphasis,

@@ -100,12 +100,27 @@ __device__ __forceinline__ bool hit1(int c, uint32_t row, uint32_t step, const R
     return (uint64_t)rk < a.thresh;
 }
 
+// sl[k] = slot of column c + k (E columns per slot): one division where the group sits inside one slot
+template <int W>
+__device__ __forceinline__ void slots_of(int c, int E, int* sl) {
+    const int s0 = c / E, rem = c - s0 * E;
+    if (rem + W <= E) {
+#pragma unroll
+        for (int k = 0; k < W; ++k) sl[k] = s0;
+    } else {
+#pragma unroll
+        for (int k = 0; k < W; ++k) sl[k] = s0 + (rem + k) / E;
+    }
+}
+
 // ---- L1 / SmoothL1 / Huber -----------------------------------------------------------------------------------------------------
 //   dy = w rho'(d) (-1) inv_n, d = x - y;   parts[block] = { sum w rho(d), sum d^2, sum (1-fmask) d^2 }
-template <int KIND, bool VEC, bool DY_BF16>
+// PRES (a presence table is set): an absent element's x and y are SELECTED to 0 as they are loaded (x may be NaN there): d = 0,
+// rho = rho' = 0, exact zeros into every sum; its stored dy is +0.  Between the loads and the stores the text is the one without a table.
+template <int KIND, bool VEC, bool DY_BF16, bool PRES>
 __global__ __launch_bounds__(NT) void recon_elem_kernel(BatchArgs ba, const float* __restrict__ y, void* __restrict__ dy, float inv_n,
                                                         float* __restrict__ colsum_part, double* __restrict__ parts, int64_t dy_ld,
-                                                        ReconArgs ea) {
+                                                        ReconArgs ea, PresArgs pa) {
     __shared__ float red[WAVES];
     const float* __restrict__ data = ba.data;
     const uint8_t* __restrict__ table = ba.table;
@@ -118,6 +133,8 @@ __global__ __launch_bounds__(NT) void recon_elem_kernel(BatchArgs ba, const floa
     float wr = 0.f, sq = 0.f, sqp = 0.f;
     for (int cv = threadIdx.x; cv < cols; cv += NT) {
         const int c = cv * W;
+        int psl[W];
+        if constexpr (PRES) slots_of<W>(c, pa.E, psl);
         float cw[4] = {1.f, 1.f, 1.f, 1.f};
         if (ea.col_weight != nullptr) {
             if constexpr (VEC) {
@@ -155,6 +172,13 @@ __global__ __launch_bounds__(NT) void recon_elem_kernel(BatchArgs ba, const floa
                 if constexpr (VEC) hits4(hit, c, (uint32_t)src_row, step, ea);
                 else hit[0] = hit1(c, (uint32_t)src_row, step, ea);
             }
+            uint32_t pb = 0xfu;
+            if constexpr (PRES) {
+                pb = present_bits<W>(pa, src_row, psl);
+#pragma unroll
+                for (int k = 0; k < W; ++k)
+                    if (!((pb >> k) & 1u)) { xv[k] = 0.f; yv[k] = 0.f; }
+            }
             float g[4];
 #pragma unroll
             for (int k = 0; k < W; ++k) {
@@ -169,6 +193,10 @@ __global__ __launch_bounds__(NT) void recon_elem_kernel(BatchArgs ba, const floa
                 if (blank) sqp = opaque(sqp + se);
                 g[k] = -drho * opaque(w * inv_n);
                 cs[k] = opaque(cs[k] + g[k]);
+            }
+            if constexpr (PRES) {      // (the stored gradient of an absent element is +0, not the product's -0)
+#pragma unroll
+                for (int k = 0; k < W; ++k) g[k] = ((pb >> k) & 1u) ? g[k] : 0.f;
             }
             if (live) {
                 const int64_t o = (int64_t)b * dy_ld + c;
@@ -271,10 +299,12 @@ __device__ __forceinline__ void slot_pair_sums(const BatchArgs& ba, const float*
     dot = wave_sum(dot); nx2 = wave_sum(nx2); ny2 = wave_sum(ny2); sw = wave_sum(sw);
 }
 
-template <bool VEC1, bool VEC, bool DY_BF16>
+// PRES: an absent pair is skipped in phase 1 - coefficients 0, no term, its x never read -, and phase 2 selects x = y = 0 for its
+// columns as they are loaded and stores +0 (the table's slots are the criterion's: pa.S == ea.S).
+template <bool VEC1, bool VEC, bool DY_BF16, bool PRES>
 __global__ __launch_bounds__(NT) void slot_cosine_kernel(BatchArgs ba, const float* __restrict__ y, void* __restrict__ dy, float inv_n,
                                                          float* __restrict__ colsum_part, double* __restrict__ parts, int64_t dy_ld,
-                                                         ReconArgs ea) {
+                                                         ReconArgs ea, PresArgs pa) {
     extern __shared__ float coef[];      // [LOSS_ROWS][S][2]
     __shared__ float red[WAVES];
     const float* __restrict__ data = ba.data;
@@ -291,7 +321,14 @@ __global__ __launch_bounds__(NT) void slot_cosine_kernel(BatchArgs ba, const flo
     for (int p = wave; p < LOSS_ROWS * S; p += WAVES) {
         const int rr = p / S, s = p - rr * S;
         float a = 0.f, bq = 0.f;
-        if (r_begin + rr < B) {                  // (wave-uniform)
+        bool pair_on = r_begin + rr < B;         // (wave-uniform)
+        if constexpr (PRES) {
+            if (pair_on) {
+                const int64_t prow = ba.row_idx ? ba.row_idx[r_begin + rr] : r_begin + rr;
+                pair_on = pa.tab[prow * pa.S + s] != 0;
+            }
+        }
+        if (pair_on) {
             float dot, nx2, ny2, sw;
             slot_pair_sums<VEC1>(ba, y, ea, r_begin + rr, s, step, dot, nx2, ny2, sw);
             const float nxr = sqrtf(nx2), nyr = sqrtf(ny2);
@@ -356,6 +393,13 @@ __global__ __launch_bounds__(NT) void slot_cosine_kernel(BatchArgs ba, const flo
                 if constexpr (VEC) hits4(hit, c, (uint32_t)src_row, step, ea);
                 else hit[0] = hit1(c, (uint32_t)src_row, step, ea);
             }
+            uint32_t pb = 0xfu;
+            if constexpr (PRES) {
+                pb = present_bits<W>(pa, src_row, sl);
+#pragma unroll
+                for (int k = 0; k < W; ++k)
+                    if (!((pb >> k) & 1u)) { xv[k] = 0.f; yv[k] = 0.f; }
+            }
             float g[4];
 #pragma unroll
             for (int k = 0; k < W; ++k) {
@@ -373,6 +417,10 @@ __global__ __launch_bounds__(NT) void slot_cosine_kernel(BatchArgs ba, const flo
                 }
                 g[k] = live ? gk : 0.f;
                 cs[k] = opaque(cs[k] + g[k]);
+            }
+            if constexpr (PRES) {      // (the stored gradient of an absent element is +0 whatever sign its zero came out with)
+#pragma unroll
+                for (int k = 0; k < W; ++k) g[k] = ((pb >> k) & 1u) ? g[k] : 0.f;
             }
             if (live) {
                 const int64_t o = (int64_t)b * dy_ld + c;
@@ -437,9 +485,14 @@ int check_recon_loss(const codae_recon_loss* l, int io) {
 
 int launch_recon_loss(const codae_batch* b, const codae_noise* noise, int32_t step, const double* step_dev, const codae_emphasis* emph,
                       const codae_recon_loss* loss, const float* y, void* dy, int dy_bf16, int64_t dy_ld, float inv_n, float* colsum_part,
-                      double* parts, hipStream_t s) {
+                      double* parts, hipStream_t s, const uint8_t* present, int n_slots) {
     if (dy_ld <= 0) dy_ld = b ? b->io : 0;
     CODAE_REQUIRE(b && b->data && y && dy && parts && loss && b->B > 0 && b->io > 0, "recon_loss: bad args");
+    int prc = check_presence(present, n_slots, b->io, "recon_loss");
+    if (prc) return prc;
+    CODAE_REQUIRE(present == nullptr || loss->kind != CODAE_LOSS_SLOT_COSINE || loss->n_slots == n_slots,
+                  "recon_loss: slot_cosine n_slots %d differs from the presence table's %d", loss->n_slots, n_slots);
+    const PresArgs pa{present, n_slots, present ? b->io / n_slots : 0};
     CODAE_REQUIRE(dy_ld >= b->io, "recon_loss: dy_ld %lld below io %d", (long long)dy_ld, b->io);
     int rc = check_recon_loss(loss, b->io);
     if (rc) return rc;
@@ -472,7 +525,8 @@ int launch_recon_loss(const codae_batch* b, const codae_noise* noise, int32_t st
         ea.mse_weight = loss->mse_weight; ea.S = loss->n_slots; ea.E = b->io / loss->n_slots;
         const bool vec1 = (ea.E % 4 == 0) && in16;
         const size_t lds = (size_t)LOSS_ROWS * ea.S * 2 * sizeof(float);
-#define SC(V1, V, O) hipLaunchKernelGGL((slot_cosine_kernel<V1, V, O>), dim3(grid), dim3(NT), lds, s, ba, y, dy, inv_n, colsum_part, parts, dy_ld, ea)
+#define SCP(V1, V, O, P) hipLaunchKernelGGL((slot_cosine_kernel<V1, V, O, P>), dim3(grid), dim3(NT), lds, s, ba, y, dy, inv_n, colsum_part, parts, dy_ld, ea, pa)
+#define SC(V1, V, O) do { if (present) SCP(V1, V, O, true); else SCP(V1, V, O, false); } while (0)
         if (vec1) {
             if (vec && dy_bf16) SC(true, true, true);
             else if (vec) SC(true, true, false);
@@ -485,8 +539,10 @@ int launch_recon_loss(const codae_batch* b, const codae_noise* noise, int32_t st
             else SC(false, false, false);
         }
 #undef SC
+#undef SCP
     } else {
-#define RL(K, V, O) hipLaunchKernelGGL((recon_elem_kernel<K, V, O>), dim3(grid), dim3(NT), 0, s, ba, y, dy, inv_n, colsum_part, parts, dy_ld, ea)
+#define RLP(K, V, O, P) hipLaunchKernelGGL((recon_elem_kernel<K, V, O, P>), dim3(grid), dim3(NT), 0, s, ba, y, dy, inv_n, colsum_part, parts, dy_ld, ea, pa)
+#define RL(K, V, O) do { if (present) RLP(K, V, O, true); else RLP(K, V, O, false); } while (0)
 #define RK(K) do { if (vec && dy_bf16) RL(K, true, true); else if (vec) RL(K, true, false); else if (dy_bf16) RL(K, false, true); \
                    else RL(K, false, false); } while (0)
         if (loss->kind == CODAE_LOSS_L1) RK(CODAE_LOSS_L1);
@@ -494,6 +550,7 @@ int launch_recon_loss(const codae_batch* b, const codae_noise* noise, int32_t st
         else RK(CODAE_LOSS_HUBER);
 #undef RK
 #undef RL
+#undef RLP
     }
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;

@@ -26,6 +26,9 @@ constexpr int MAX_NEG = 4096;
 constexpr int MAX_SLOTS = 128;
 constexpr int PAD = 32;          // K and E are padded to multiples of this in the work space (zeros; pad logits are masked)
 constexpr int NSC = 8;           // per-row scalars in LDS
+// id of a candidate whose slot is absent in its dataset row ("Slot presence"): never kept by any pair, its vector stored as zeros.
+// (item ids and dataset rows are >= 0; the pad candidates' -1 is never read under the k < K test.)
+constexpr int32_t ABSENT_ID = INT32_MIN;
 
 __device__ __forceinline__ float opaque(float x) { asm("" : "+v"(x)); return x; }
 
@@ -68,6 +71,7 @@ struct ContrastArgs {
     const void* cn;               // [S][Kpad][Epad] T
     const void* ct;               // [S][Epad][Kpad] T
     const int32_t* ids;           // [S][Kpad]
+    const uint8_t* present;       // [n_rows][S] or null: slot presence of the batch rows (a uniform null test, no instantiation of its own)
 };
 
 struct PrepArgs {
@@ -78,6 +82,7 @@ struct PrepArgs {
     uint32_t key0, key1, step;
     const double* step_dev;
     void* cn; void* ct; int32_t* ids;
+    const uint8_t* present;       // [n_rows][S] or null
 };
 
 template <typename T> __device__ __forceinline__ T to_op(float v);
@@ -113,6 +118,13 @@ __global__ __launch_bounds__(64) void slot_contrast_prepare_kernel(PrepArgs a) {
     const int j = (int)(((uint64_t)r * (uint64_t)a.P) >> 32);
     int row = a.pool ? a.pool[j] : j;
     row = row < 0 ? 0 : (row >= a.n_rows ? a.n_rows - 1 : row);      // (the host checks the pool; never read out of bounds)
+    if (a.present != nullptr && a.present[(int64_t)row * a.S + s] == 0) {
+        // an absent candidate: zeros in both orders - whatever data holds there (a NaN included) reaches no product - and the id
+        // that no pair keeps.  The draw itself is the one a step without a table makes.
+        for (int e = lane; e < a.Epad; e += 64) { cn[e] = to_op<T>(0.f); ct[(int64_t)e * a.Kpad] = to_op<T>(0.f); }
+        if (lane == 0) a.ids[s * a.Kpad + k] = ABSENT_ID;
+        return;
+    }
     const float* __restrict__ src = a.data + (int64_t)row * a.io + s * a.E;
     float n2 = 0.f;
     for (int e = lane; e < a.E; e += 64) { const float v = src[e]; n2 = opaque(__fmaf_rn(v, v, n2)); }
@@ -211,7 +223,8 @@ __device__ __forceinline__ float ex(float v) { return __expf(v); }
 
 // ---- the contrast ----------------------------------------------------------------------------------------------------------------
 // per-row scalars (LDS, one set per wave): 0 cos(x, y), 1 1 / max(|x|, eps), 2 1 / max(|y|, eps), 3 [|y| > eps] / (tau |y|), 4 W, 5 flags
-// (1 = bad: a NaN or Inf in the y slot, 2 = no positive: |x| <= eps, 4 = a row of the batch), 6 1 - p0, 7 g . y^
+// (1 = bad: a NaN or Inf in the y slot, 2 = no positive: |x| <= eps, 4 = a row of the batch, 8 = the slot is absent in this row:
+// its x is never used - selected to 0, which makes it a pair without a positive), 6 1 - p0, 7 g . y^
 template <typename T, int MAXT, int NH>
 __global__ __launch_bounds__(NT) void slot_contrast_kernel(BatchArgs ba, const float* __restrict__ y, T* __restrict__ dy, int64_t dy_ld,
                                                            float scale, float* __restrict__ colsum_part, double* __restrict__ parts,
@@ -250,9 +263,10 @@ __global__ __launch_bounds__(NT) void slot_contrast_kernel(BatchArgs ba, const f
                 const int id = !masked ? 0 : (ba.mask_id ? ba.mask_id[b] : ba.mask_to_use[src_row * ba.nb_run + ba.run]);
                 const float* __restrict__ xr = ba.data + src_row * io + s * E;
                 const float* __restrict__ yr = y + (int64_t)b * io + s * E;
+                const bool absent = ca.present != nullptr && ca.present[src_row * S + s] == 0;     // (wave-uniform)
                 float dot = 0.f, nx2 = 0.f, ny2 = 0.f, sw = 0.f;
                 for (int e = lane; e < E; e += 64) {
-                    const float xv = xr[e], yv = yr[e];
+                    const float xv = absent ? 0.f : xr[e], yv = yr[e];
                     float w = ew.beta;
                     if (weighted) {
                         const int c = s * E + e;
@@ -280,7 +294,7 @@ __global__ __launch_bounds__(NT) void slot_contrast_kernel(BatchArgs ba, const f
                     sc[rr * NSC + 2] = iny;
                     sc[rr * NSC + 3] = nyr > CODAE_COS_EPS ? inv_tau / nyr : 0.f;
                     sc[rr * NSC + 4] = live ? sw / (float)E : 0.f;
-                    sc[rr * NSC + 5] = __int_as_float((bad ? 1 : 0) | (nopos ? 2 : 0) | (live ? 4 : 0));
+                    sc[rr * NSC + 5] = __int_as_float((bad ? 1 : 0) | (nopos ? 2 : 0) | (live ? 4 : 0) | (absent ? 8 : 0));
                 }
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -301,7 +315,7 @@ __global__ __launch_bounds__(NT) void slot_contrast_kernel(BatchArgs ba, const f
                 const int idv[4] = {id4.x, id4.y, id4.z, id4.w};
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const bool keep = (c0 + 4 * g + j < K) && idv[j] != my_id;
+                    const bool keep = (c0 + 4 * g + j < K) && idv[j] != my_id && idv[j] != ABSENT_ID;
                     const float zz = z[j] * inv_tau;
                     if (keep) {
                         if (zz > m) { sum = opaque(sum * ex(m - zz)) + 1.f; m = zz; }     // (m = -inf, sum = 0: 0 * 0 + 1)
@@ -352,8 +366,8 @@ __global__ __launch_bounds__(NT) void slot_contrast_kernel(BatchArgs ba, const f
                     float pa[4], pb[4];
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        const bool ka = (c0 + 4 * g + j < K) && iav[j] != my_id;
-                        const bool kb = (c0 + 16 + 4 * g + j < K) && ibv[j] != my_id;
+                        const bool ka = (c0 + 4 * g + j < K) && iav[j] != my_id && iav[j] != ABSENT_ID;
+                        const bool kb = (c0 + 16 + 4 * g + j < K) && ibv[j] != my_id && ibv[j] != ABSENT_ID;
                         pa[j] = as_operand<T>(ka ? ex(za[j] * inv_tau - lse) : 0.f);
                         pb[j] = as_operand<T>(kb ? ex(zb[j] * inv_tau - lse) : 0.f);
                     }
@@ -395,7 +409,7 @@ __global__ __launch_bounds__(NT) void slot_contrast_kernel(BatchArgs ba, const f
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
                             const bool live = (fl[j] & 4) && e < E;
-                            const float xh = ba.data[xoff[j] + ec] * inx[j];
+                            const float xh = (fl[j] & 8) ? 0.f : ba.data[xoff[j] + ec] * inx[j];
                             const float yh = y[yoff[j] + ec] * iny[j];
                             const float ge = opaque(__fmaf_rn(-omp0r[j], xh, acc[t][j]));
                             const float dl = opaque(__fmaf_rn(-gy[j], yh, ge)) * dls[j];
@@ -523,10 +537,14 @@ int check_slot_contrast(const codae_slot_contrast* c, int io, int bf16) {
 int slot_contrast_warm() { return raise_lds(); }
 
 int launch_slot_contrast_prepare(const float* data, int io, const codae_slot_contrast* c, int32_t step, const double* step_dev, int bf16,
-                                 hipStream_t s) {
+                                 hipStream_t s, const uint8_t* present, int n_slots) {
     CODAE_REQUIRE(data != nullptr && c != nullptr && io > 0 && c->weight != 0.f, "slot contrast prepare: bad args");
     int rc = check_slot_contrast(c, io, bf16);
     if (rc) return rc;
+    rc = check_presence(present, n_slots, io, "slot contrast prepare");
+    if (rc) return rc;
+    CODAE_REQUIRE(present == nullptr || n_slots == c->n_slots, "slot contrast prepare: n_slots %d differs from the presence table's %d",
+                  c->n_slots, n_slots);
     const int E = io / c->n_slots;
     const WsLayout w = ws_layout(c->n_slots, c->n_neg, E, bf16);
     PrepArgs a{};
@@ -535,6 +553,7 @@ int launch_slot_contrast_prepare(const float* data, int io, const codae_slot_con
     a.key0 = (uint32_t)(c->seed & 0xffffffffu); a.key1 = (uint32_t)(c->seed >> 32); a.step = (uint32_t)step; a.step_dev = step_dev;
     unsigned char* base = reinterpret_cast<unsigned char*>(c->ws);
     a.cn = base + w.cn_off; a.ct = base + w.ct_off; a.ids = reinterpret_cast<int32_t*>(base + w.ids_off);
+    a.present = present;
     if (bf16) hipLaunchKernelGGL(slot_contrast_prepare_kernel<bf16_t>, dim3(w.Kpad, a.S), dim3(64), 0, s, a);
     else hipLaunchKernelGGL(slot_contrast_prepare_kernel<float>, dim3(w.Kpad, a.S), dim3(64), 0, s, a);
     CODAE_LAUNCH_CHECK();
@@ -543,9 +562,13 @@ int launch_slot_contrast_prepare(const float* data, int io, const codae_slot_con
 
 int launch_slot_contrast(const codae_batch* b, const codae_noise* noise, int32_t step, const double* step_dev, const codae_emphasis* emph,
                          const codae_slot_contrast* c, const float* y, void* dy, int dy_bf16, int64_t dy_ld, float scale,
-                         float* colsum_part, double* parts, hipStream_t s) {
+                         float* colsum_part, double* parts, hipStream_t s, const uint8_t* present, int n_slots) {
     if (dy_ld <= 0) dy_ld = b ? b->io : 0;
     CODAE_REQUIRE(b && b->data && y && dy && parts && c && b->B > 0 && b->io > 0 && c->weight != 0.f, "slot contrast: bad args");
+    int prc = check_presence(present, n_slots, b->io, "slot contrast");
+    if (prc) return prc;
+    CODAE_REQUIRE(present == nullptr || n_slots == c->n_slots, "slot contrast: n_slots %d differs from the presence table's %d",
+                  c->n_slots, n_slots);
     CODAE_REQUIRE(dy_ld >= b->io, "slot contrast: dy_ld %lld below io %d", (long long)dy_ld, b->io);
     CODAE_REQUIRE(finite_f(scale), "slot contrast: scale %g is not finite", (double)scale);
     int rc = check_slot_contrast(c, b->io, dy_bf16);
@@ -574,6 +597,7 @@ int launch_slot_contrast(const codae_batch* b, const codae_noise* noise, int32_t
     ca.inv_tau = (float)(1.0 / (double)c->tau); ca.n_rows = c->n_rows; ca.item_id = c->item_id;
     const unsigned char* base = reinterpret_cast<const unsigned char*>(c->ws);
     ca.cn = base + w.cn_off; ca.ct = base + w.ct_off; ca.ids = reinterpret_cast<const int32_t*>(base + w.ids_off);
+    ca.present = present;
     BatchArgs ba{b->data, b->row_idx, b->mask_id, b->mask_table, b->mask_to_use, b->nb_run, b->run, b->B, b->io};
     const int es = dy_bf16 ? 2 : 4;
     const size_t lds = (size_t)WAVES * WROWS * (w.Epad + 16 / es) * es + (size_t)(WAVES * WROWS * NSC + WAVES * w.Epad + WAVES) * 4;

@@ -70,7 +70,15 @@ def main():
         seed_all_ranks(int(config["SEED"]))
 
     log.info("Loading dataset.")
-    dataset = load_dataset_of_embeddings(embedding_path=args.embedding_path, config=config, cache_dir="tmp/")
+    # HIP: KEEP_INCOMPLETE: true (+ MIN_PRESENT: 2) (build-only keys): keep the observations that have at least MIN_PRESENT of
+    # the used categories; their absent slots stay out of the input, the loss, the monitors and complete()'s inventory
+    keep_incomplete = bool(config.get("HIP", {}).get("KEEP_INCOMPLETE", False))
+    if keep_incomplete:
+        dataset = load_dataset_of_embeddings(embedding_path=args.embedding_path, config=config, cache_dir="tmp/", keep_incomplete=True,
+                                             min_present=int(config.get("HIP", {}).get("MIN_PRESENT", 2)))
+        log.info("Keeping incomplete observations: %d of %d slots are absent" % (int((dataset.presence == 0).sum()), dataset.presence.size))
+    else:
+        dataset = load_dataset_of_embeddings(embedding_path=args.embedding_path, config=config, cache_dir="tmp/")
     dataset_std = torch.std(dataset.data)
     log.info("Dataset STD = " + str(dataset_std))
     log.info("CUDA available, loading GPU device")
@@ -90,6 +98,13 @@ def main():
     c = list(range(len(dc["USED_CATEGORY"])))
     [random.sample(c, len(c)) for _ in range(dataset.nb_observation)]
     corrupter = Corrupter(nb_observation=dataset.nb_observation, arch=dataset.arch, k_max=args.nb_missing, device=device)
+
+    presence, mask_to_use = None, corrupter.mask_to_use_i32
+    if keep_incomplete:
+        from codae.tool import SlotPresence
+        presence = SlotPresence(dataset.presence)
+        # every row's runs reordered so that run 0 blanks a slot the row has and leaves one of its slots visible
+        mask_to_use = presence.assign_masks(corrupter).to(device)
 
     log.info("Initializing the model.")
     io_size = dc["EMBEDDING_SIZE"] * len(dc["USED_CATEGORY"])
@@ -132,11 +147,12 @@ def main():
     optimizer = optimizer_from_config(config.get("HIP", {}).get("OPTIMIZER"), total_steps=max(1, epochs * 1 * len(train_sampler)))
 
     def build(prec):
-        return HipEmbeddingTrainer(enc + dec, dataset.data, corrupter.mask_table_u8, corrupter.mask_to_use_i32,
+        return HipEmbeddingTrainer(enc + dec, dataset.data, corrupter.mask_table_u8, mask_to_use,
                                    mc["LEARNING_RATE"], mc["WEIGHT_DECAY"], clip=1.0 if mc["TRUNK_GRAD"] else 0.0,
                                    max_batch=mc["BATCH_SIZE"], precision=prec, device=device, distributed=world > 1,
                                    activation=activation, input_noise=input_noise, loss_emphasis=loss_emphasis,
-                                   hidden_dropout=hidden_dropout, criterion=criterion, contrast=contrast, optimizer=optimizer)
+                                   hidden_dropout=hidden_dropout, criterion=criterion, contrast=contrast, optimizer=optimizer,
+                                   presence=presence)
     try:
         trainer = build(precision)
     except HipError as e:
@@ -150,8 +166,29 @@ def main():
     act_label = "+" + (activation(True).__class__.__name__ if activation is not None else "ReLU")
     log.info("Linear stack: " + " | ".join("%d->%d%s" % (k, n, act_label if r else "") for k, n, r in enc + dec))
     book = {k: [] for k in ("ftl", "ptl", "fvl", "pvl", "rl")}
-    ranking_loss = RankingLoss(dataset, validation_indices, device=device)
     S = dataset.nb_used_category
+    rank_indices, nb_ranked = validation_indices, nb_validation
+    if keep_incomplete:
+        # the four RMSE monitors divide by what the sums ran over (SlotPresence.counts, in slots: times E = elements); the
+        # ranking monitor sees the complete validation rows only (its inventory has no notion of an absent item)
+        E = dataset.embedding_size
+        m2u_host = mask_to_use.cpu()
+        den = {}
+        for name, rows in (("train", train_indices), ("validation", validation_indices)):
+            full, part = presence.counts(rows, mask_ids=m2u_host[torch.as_tensor(rows, dtype=torch.long), 0], mask_table=corrupter.binary_masks)
+            den[name] = (max(full, 1) * E, max(part, 1) * E)
+        complete_row = dataset.presence.all(axis=1)
+        rank_indices = [i for i in validation_indices if complete_row[i]]
+        nb_ranked = max(len(rank_indices), 1)
+    else:
+        den = {"train": (dataset.nb_predictor * nb_train, nb_train * dataset.nb_predictor / S),
+               "validation": (dataset.nb_predictor * nb_validation, nb_validation * dataset.nb_predictor / S)}
+    ranking_loss = RankingLoss(dataset, rank_indices if rank_indices else validation_indices, device=device)
+    is_ranked = None
+    if keep_incomplete:
+        is_ranked = torch.zeros(dataset.nb_observation, dtype=torch.bool, device=device)
+        if rank_indices:
+            is_ranked[torch.as_tensor(rank_indices, dtype=torch.long, device=device)] = True
 
     for epoch in range(epochs):
         log.info("===================================================== EPOCH = %d" % epoch)
@@ -165,8 +202,8 @@ def main():
                 continue
             trainer.train_batch(shard.contiguous(), run=0, global_rows=len(batch_indices))
         sq, sqp = trainer.epoch_sums()
-        book["ftl"].append(np.sqrt(sq / (dataset.nb_predictor * nb_train)))
-        book["ptl"].append(np.sqrt(sqp / (nb_train * dataset.nb_predictor / S)))
+        book["ftl"].append(np.sqrt(sq / den["train"][0]))
+        book["ptl"].append(np.sqrt(sqp / den["train"][1]))
         log.info("TRAINING FULL ERROR      = %7f" % book["ftl"][-1])
         log.info("TRAINING PARTIAL ERROR   = %7f" % book["ptl"][-1])
 
@@ -175,12 +212,17 @@ def main():
         # read-back per epoch instead of a mask expansion, two .tolist() and a host sync per batch
         for idx in validation_sampler.device_batches(device):
             y = trainer.eval_batch(idx, run=0, want_y=True)
-            ranking_loss.add(y, idx, corrupter, run=0)
-        rl = ranking_loss.total()
+            if is_ranked is None:
+                ranking_loss.add(y, idx, corrupter, run=0)
+            elif rank_indices:
+                keep = is_ranked[idx.long()]
+                if bool(keep.any()):
+                    ranking_loss.add(y[keep].contiguous(), idx[keep].contiguous(), corrupter, run=0)
+        rl = ranking_loss.total() if (is_ranked is None or rank_indices) else 0.0     # (no complete validation row: nothing was ranked)
         sq, sqp = trainer.epoch_sums(reduce=False)      # every rank evaluates the whole validation set
-        book["fvl"].append(np.sqrt(sq / (dataset.nb_predictor * nb_validation)))
-        book["pvl"].append(np.sqrt(sqp / (nb_validation * dataset.nb_predictor / S)))
-        book["rl"].append(rl / nb_validation)
+        book["fvl"].append(np.sqrt(sq / den["validation"][0]))
+        book["pvl"].append(np.sqrt(sqp / den["validation"][1]))
+        book["rl"].append(rl / nb_ranked)
         log.info("VALIDATION FULL ERROR    = %7f" % book["fvl"][-1])
         log.info("VALIDATION PARTIAL ERROR = %7f" % book["pvl"][-1])
         log.info("VALIDATION RANKING ERROR = %7f" % book["rl"][-1])
