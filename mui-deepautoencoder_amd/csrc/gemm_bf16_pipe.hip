@@ -48,13 +48,30 @@ constexpr int TIMELINE_WGS = 4096, TIMELINE_SLOTS = 6;
 __device__ unsigned long long g_timeline[TIMELINE_WGS * TIMELINE_SLOTS];
 
 // EPI (bf16 output only): 1 = forward epilogue (bias + ReLU), 2 = data-gradient epilogue (ReLU mask from the saved
-// activation + column sums = bias gradient), 3 = last forward layer of a training step with the MSE loss, its gradient
+// activation + column sums = bias gradient), 4 = the same with the 1-bit ReLU mask and nothing else (a kernel of its own: beside the
+// activation-mask copy of the write-out in ONE kernel, the compiler made the bit copy's LDS reads wait for the other copy's loads), 3 = last forward layer of a training step with the MSE loss, its gradient
 // and the metric sums computed straight from the accumulators (g.loss), 0 = everything decided at run time.  Apart from trimming the forward's
 // epilogue this gives the forward and the data-gradient launches distinct kernel symbols in rocprofv3 traces.
 // One output tile (or split-K range of one) of one GEMM: the whole kernel body, shared by the plain kernel (one GEMM per
 // launch) and the grouped kernel (the weight gradients of every layer in one launch).  wg / nwg: this workgroup's index
-// among the nwg workgroups of ITS GEMM; smem_raw: 2 * BUF (+ BM * 8 for EPI 3) bytes of LDS.
+// among the nwg workgroups of ITS GEMM; smem_raw: pipe_smem_bytes<BM, BN, C_F32, EPI>() bytes of LDS: the two K-tile buffers and,
+// behind them, what the epilogue needs beside the accumulators (EPI 3's rowinfo, the tile's bias slice, the tile's ReLU bits).
 // POL: STORE_* policy of the output tile's 16-byte stores (GemmBf16::store_policy, chosen by the launcher)
+// The epilogue's operands are PARKED in LDS by LDS-DMA issued at kernel entry, in front of the prologue's operand loads, so
+// their round trip lies under the pipeline fill instead of between the last MFMA and the first output store:
+//   bias  [BN floats (+ pad to one 16-B piece per lane of a wave)]   one 16-B piece per lane of ONE wave; only if there is a bias
+//   bits  [BM][BN / 8 bytes]  the tile of the 1-bit ReLU mask the data gradient applies; 4-B pieces, BM * BN / 32 / 64 instructions
+//                             spread over the waves; only if the launch has bits
+// Being OLDER than every operand load, they have retired whenever one of the K loop's counted waits is satisfied (loads retire in
+// order), so no count changes; the drain + barrier in front of the epilogue publishes them to every wave.  The 256-row tiles only:
+// the 128 x 192 tile's two buffers are exactly half a CU's LDS, a tail would halve its occupancy - it keeps plain loads.
+constexpr int PARK_BIAS_BYTES = 1024;
+template <int BM, int BN, bool C_F32, int EPI>
+constexpr int pipe_smem_bytes() {
+    const bool park = BM == 256;
+    return 2 * (BM + BN) * 128 + (EPI == 3 ? BM * 8 : 0) + (park ? PARK_BIAS_BYTES : 0) + (park && !C_F32 && (EPI == 0 || EPI == 2 || EPI == 4) ? BM * BN / 8 : 0);
+}
+
 template <int BM, int BN, int WM, int WN, int NLB, int A_MODE, int B_MODE, bool C_F32, int DBG = 0, int EPI = 0, int POL = STORE_PLAIN>
 __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles_n, int tiles_mn, int kt_total, int wg, int nwg,
                                                     char* smem_raw) {
@@ -75,6 +92,10 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
     static_assert(NLB <= NW && NLA <= NW && (AHR / 8) % NLA == 0 && (BHR / 8) % NLB == 0, "loader waves");
     static_assert(SM % 32 == 0 && SN % 32 == 0, "wave sub-tile must split into 16-wide half tiles");
     lds_char* smem = (lds_char*)smem_raw;
+    constexpr bool PARK = BM == 256;
+    constexpr bool PARK_BITS = PARK && !C_F32 && (EPI == 0 || EPI == 2 || EPI == 4);
+    constexpr int BIAS_OFF = 2 * BUF + (EPI == 3 ? BM * 8 : 0), BITS_OFF = BIAS_OFF + PARK_BIAS_BYTES;
+    static_assert(BN * 4 <= PARK_BIAS_BYTES && BN % 32 == 0, "bias slice: one 16-B piece per lane of one wave");
 
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -139,6 +160,47 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
             rowinfo[2 * r] = src; rowinfo[2 * r + 1] = id;
         }
     }
+
+    const bool has_bias = g.bias != nullptr;
+    if constexpr (PARK) {
+        // bias[j0 .. j0 + BN): lane l of the last wave fetches columns j0 + 4 l .. + 3, clamped into the N columns (N % 4 == 0 as for
+        // load_bias4; a clamped piece lands in a column group past N or in the pad, which nobody reads)
+        if (has_bias && w == NW - 1) {
+            int j = j0 + 4 * lane;
+            j = j + 4 <= g.N ? j : g.N - 4;
+            __builtin_amdgcn_global_load_lds((gvoid*)(g.bias + j), (__attribute__((address_space(3))) void*)(smem + BIAS_OFF), 16, 0, 0);
+        }
+    }
+    if constexpr (PARK_BITS) {
+        // bits of rows i0 .. i0 + BM, bytes j0 / 8 .. + BN / 8 (rows are ld_bits apart, a multiple of 8 bytes; j0 / 8 is a multiple of 4):
+        // 4-B piece q = row * (BN / 32) + dword, rows clamped to M - 1 and dwords to the row's last one, as half_src clamps
+        if (g.relu_bits != nullptr) {
+            constexpr int DPR = BN / 32, NI = BM * DPR / 64;
+            static_assert((BM * DPR) % 64 == 0, "bit tile: whole 64-lane instructions");
+#pragma unroll
+            for (int q0 = 0; q0 < NI; q0 += NW) {
+                const int ins = q0 + w;            // wave-uniform
+                if (ins < NI) {
+                    const int q = ins * 64 + lane, r = q / DPR, cd = q - r * DPR;
+                    const int row = i0 + r < g.M ? i0 + r : g.M - 1;
+                    int off = (j0 >> 3) + 4 * cd;
+                    off = off + 4 <= (int)g.ld_bits ? off : (int)g.ld_bits - 4;
+                    __builtin_amdgcn_global_load_lds((gvoid*)(g.relu_bits + (int64_t)row * g.ld_bits + off),
+                                                     (__attribute__((address_space(3))) void*)(smem + BITS_OFF + ins * 256), 4, 0, 0);
+                }
+            }
+        }
+    }
+    // bias[j0 + jl .. + 3] of the tile's column group jl (zeros without a bias or past N)
+    auto bias4 = [&](int jl) -> float4 {
+        if constexpr (PARK) {
+            const f32x4 v = *reinterpret_cast<const __attribute__((address_space(3))) f32x4*>(smem + BIAS_OFF + jl * 4);
+            const bool ok = has_bias && j0 + jl < g.N;
+            return make_float4(ok ? v[0] : 0.f, ok ? v[1] : 0.f, ok ? v[2] : 0.f, ok ? v[3] : 0.f);
+        } else {
+            return load_bias4(g.bias, g.A, j0 + jl, g.N);
+        }
+    };
 
     f32x4 acc[2][TMH][2][TNH];
 #pragma unroll
@@ -345,25 +407,38 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
             else k_loop(std::false_type{}, std::false_type{});
         }
     }
-    wait_vmcnt<0>();        // the trailing dummy loads must not outlive the kernel's use of LDS
+    // The trailing dummy loads must not outlive the kernel's use of LDS.  As the BUILTIN (vmcnt(0), the other counters left at their
+    // maxima), not the asm form the K loop uses: the compiler then knows that no LDS-DMA is in flight any more.  Behind the opaque
+    // asm wait it assumed some were and put a vmcnt(0) of its own - which also waits for the next-weights touch - in front of the
+    // write-out's LDS reads on the paths where it could not count the loads issued since.
+    __builtin_amdgcn_s_waitcnt(0x0f70);
+    asm volatile("" ::: "memory");
     stamp(2);
 
     // ---- epilogue: lane holds C[i][j .. j+3] of each 16 x 16 tile (swapped MFMA operands)
     const int li = lane & 15, g4 = (lane >> 4) * 4;
     // the next launch's weights: this workgroup's share of the matrix, one 4-B load per 128-B line, issued now and consumed
-    // (by a store that never happens) after the epilogue's own stores - its whole latency lies under the epilogue
-    uint32_t pf_val = 0;
-    if (g.prefetch != nullptr) {
-        const int64_t lines = (g.prefetch_bytes + 127) >> 7;
-        const int64_t per_wg = (lines + nwg - 1) / nwg;
-        for (int64_t i = threadIdx.x; i < per_wg; i += 64 * NW) {
-            const int64_t mine = (int64_t)wg * per_wg + i;
-            if (mine < lines) pf_val ^= *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(g.prefetch) + (mine << 7));
-        }
+    // (by a store that never happens) after the epilogue's own stores - its whole latency lies under the epilogue.  ONE load per
+    // thread here (every shipped shape: at most 64 * NW lines per workgroup), no loop: inside a loop the compiler waits for each
+    // load where it accumulates it, i.e. right here, in front of the epilogue.  A larger share is touched at the exits.
+    // (line counts in 32 bits - an operand is under 4 GiB -: the 64-bit division was 150 scalar instructions on every wave, here)
+    uint32_t pf_val = 0, pf_lines = 0, pf_per_wg = 0;
+    if (g.prefetch != nullptr && nwg > 0) {
+        pf_lines = (uint32_t)((g.prefetch_bytes + 127) >> 7);
+        pf_per_wg = (pf_lines + (uint32_t)nwg - 1) / (uint32_t)nwg;
+        const uint32_t mine = (uint32_t)wg * pf_per_wg + threadIdx.x;
+        if (threadIdx.x < pf_per_wg && mine < pf_lines)
+            pf_val = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(g.prefetch) + ((int64_t)mine << 7));
     }
-    // (consumed at the kernel's exits by an empty asm that names the register: the compiler keeps the loads and waits for
-    // them only there, after the epilogue's own stores have been issued)
-    auto consume_prefetch = [&]() { asm volatile("" ::"v"(pf_val)); };
+    // (consumed at the kernel's exits by an empty asm that names the register: the compiler keeps the load and waits for
+    // it only there, after the epilogue's own stores have been issued)
+    auto consume_prefetch = [&]() {
+        for (uint32_t i = threadIdx.x + 64 * NW; i < pf_per_wg; i += 64 * NW) {
+            const uint32_t mine = (uint32_t)wg * pf_per_wg + i;
+            if (mine < pf_lines) pf_val ^= *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(g.prefetch) + ((int64_t)mine << 7));
+        }
+        asm volatile("" ::"v"(pf_val));
+    };
     phase_barrier();          // every wave is past its last fragment read and every DMA has landed: LDS is free
     if constexpr (EPI == 3) {
         // Last forward layer of a training step (train_dae_on_embedding.py:206-223): y = acc + bias stays in registers.
@@ -390,7 +465,7 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
                 const int j = j0 + nh * BHR + wc * (SN / 2) + 16 * nt + g4;
                 jok[nh][nt] = j < g.N;
                 jcl[nh][nt] = jok[nh][nt] ? j : 0;
-                const float4 bj = load_bias4(g.bias, g.A, j, g.N);          // y = acc + bias, in place (frees 24 registers)
+                const float4 bj = bias4(nh * BHR + wc * (SN / 2) + 16 * nt + g4);          // y = acc + bias, in place (frees 24 registers)
 #pragma unroll
                 for (int mh = 0; mh < 2; ++mh)
 #pragma unroll
@@ -541,28 +616,34 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
         const int jc = j < g.N ? j : 0;
         // ReLU mask of the data gradient: one BIT per element when the forward launch left them (g.relu_bits: 1 byte per lane
         // and row instead of 16 - the saved activation is 25 MB per launch at C3 and comes from HBM), else the activation.
-        // The byte loads depend on nothing but indices: issued HERE, in front of the staging pass, their latency lies under it
-        // (behind the barrier that ends the staging they were the first thing the write-out waited for).
-        const bool bit_mask = EPI != 1 && g.relu_bits != nullptr;
+        // The kind is decided ONCE, around the write-out (MASK_* below): merged into one loop, the bit path issued - and waited
+        // for - the activation path's 16-byte loads from a dummy address.
+        const bool bit_mask = EPI == 4 || (EPI != 1 && g.relu_bits != nullptr);
+        // the 128-row tile (bits not parked): byte loads that depend on nothing but indices, issued HERE, in front of the staging pass
         uint8_t hb[ITER];
-        if constexpr (EPI != 1) {
-            const uint8_t* bsrc = bit_mask ? g.relu_bits : reinterpret_cast<const uint8_t*>(g.A);
-            const int64_t bld = bit_mask ? g.ld_bits : 0;
+        if constexpr (EPI != 1 && !PARK_BITS) {
             if (bit_mask) {
 #pragma unroll
                 for (int it = 0; it < ITER; ++it) {
                     const int r = rl + it * RL;
                     const bool ok = rl < RL && j < g.N && r < BM && i0 + r < g.M;
-                    hb[it] = bsrc[(int64_t)(ok ? i0 + r : 0) * bld + (ok ? (jc >> 3) : 0)];
+                    hb[it] = g.relu_bits[(int64_t)(ok ? i0 + r : 0) * g.ld_bits + (ok ? (jc >> 3) : 0)];
                 }
             }
         }
+        // (the lane's 6 bias groups are read BEFORE the first staging write: behind one, the compiler must assume the write
+        //  may alias the bias region and waits for each read where it issues it)
+        float4 bjs[2][TNH];
+#pragma unroll
+        for (int nh = 0; nh < 2; ++nh)
+#pragma unroll
+            for (int nt = 0; nt < TNH; ++nt) bjs[nh][nt] = bias4(nh * BHR + wc * (SN / 2) + 16 * nt + g4);
 #pragma unroll
         for (int nh = 0; nh < 2; ++nh)
 #pragma unroll
             for (int nt = 0; nt < TNH; ++nt) {
                 const int jl = nh * BHR + wc * (SN / 2) + 16 * nt + g4;
-                const float4 bj = load_bias4(g.bias, g.A, j0 + jl, g.N);
+                const float4 bj = bjs[nh][nt];
 #pragma unroll
                 for (int mh = 0; mh < 2; ++mh)
 #pragma unroll
@@ -577,7 +658,9 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
                         *reinterpret_cast<__attribute__((address_space(3))) u32x2*>(smem + il * PITCH + jl * 2) = o;
                     }
             }
-        __syncthreads();
+        // (phase_barrier, not __syncthreads, here and below: LDS is all these barriers order, and __syncthreads also drains vmcnt -
+        //  the next-weights touch in front of the first store, the first row half's stores in front of the second half's staging)
+        phase_barrier();
         float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         {
             // Fully unrolled with predicated stores and UNCONDITIONAL loads from clamped addresses: the ReLU-mask loads
@@ -587,33 +670,42 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
             bf16_t* Cb = reinterpret_cast<bf16_t*>(g.C);
             const TileStore<POL> out(Cb + (int64_t)i0 * g.ldc);
             const bool relu_mask = EPI != 1 && !bit_mask && g.relu_src != nullptr;
-            const bf16_t* hsrc = relu_mask ? g.relu_src : g.A;                 // (no mask: any valid 16-B aligned bytes)
-            const int64_t hld = relu_mask ? g.ld_relu : 0;
-            uint4 hv[ITER];
-            if constexpr (EPI != 1) {
-                if (!bit_mask) {
+            constexpr int MASK_NONE = 0, MASK_BITS = 1, MASK_ACT = 2;
+            // one copy of the write-out per mask kind: the bit and the plain copies load nothing from global memory, their stores
+            // wait for their own LDS reads only
+            auto write_out = [&](auto kind_tag) {
+                constexpr int KIND = decltype(kind_tag)::value;
+                uint4 hv[ITER];
+                if constexpr (KIND == MASK_ACT) {
 #pragma unroll
                     for (int it = 0; it < ITER; ++it) {
                         const int r = rl + it * RL;
                         const bool ok = rl < RL && j < g.N && r < BM && i0 + r < g.M;
-                        hv[it] = *reinterpret_cast<const uint4*>(hsrc + (int64_t)(ok ? i0 + r : 0) * hld + (relu_mask ? jc : 0));
+                        hv[it] = *reinterpret_cast<const uint4*>(g.relu_src + (int64_t)(ok ? i0 + r : 0) * g.ld_relu + jc);
                     }
                 }
-            }
+                if constexpr (KIND == MASK_BITS && PARK_BITS) {
+                    // the tile's bits were parked at kernel entry: row r, byte c (clamped rows hold row M - 1's bits, never used)
 #pragma unroll
-            for (int it = 0; it < ITER; ++it) {
-                const int r = rl + it * RL;
-                const bool ok = rl < RL && j < g.N && r < BM && i0 + r < g.M;
-                const u32x4 lv = *reinterpret_cast<const __attribute__((address_space(3))) u32x4*>(smem + (ok ? r : 0) * PITCH + c * 16);
-                uint4 v = make_uint4(lv[0], lv[1], lv[2], lv[3]);
-                if constexpr (EPI != 1) {
-                    if (bit_mask) {
+                    for (int it = 0; it < ITER; ++it) {
+                        const int r = rl + it * RL;
+                        const bool ok = rl < RL && r < BM;
+                        hb[it] = *reinterpret_cast<const __attribute__((address_space(3))) uint8_t*>(smem + BITS_OFF + (ok ? r * (BN / 8) + c : 0));
+                    }
+                }
+#pragma unroll
+                for (int it = 0; it < ITER; ++it) {
+                    const int r = rl + it * RL;
+                    const bool ok = rl < RL && j < g.N && r < BM && i0 + r < g.M;
+                    const u32x4 lv = *reinterpret_cast<const __attribute__((address_space(3))) u32x4*>(smem + (ok ? r : 0) * PITCH + c * 16);
+                    uint4 v = make_uint4(lv[0], lv[1], lv[2], lv[3]);
+                    if constexpr (KIND == MASK_BITS) {
                         const uint32_t hbv = hb[it];
                         auto keepb = [](uint32_t val, uint32_t b2) -> uint32_t {        // b2: the element pair's two mask bits
                             return val & (((b2 & 1u) ? 0x0000ffffu : 0u) | ((b2 & 2u) ? 0xffff0000u : 0u));
                         };
                         v.x = keepb(v.x, hbv); v.y = keepb(v.y, hbv >> 2); v.z = keepb(v.z, hbv >> 4); v.w = keepb(v.w, hbv >> 6);
-                    } else if (relu_mask) {
+                    } else if constexpr (KIND == MASK_ACT) {
                         const uint4 h = hv[it];
                         auto keep = [](uint32_t val, uint32_t hh) -> uint32_t {
                             const uint32_t lo = ((hh & 0x8000u) == 0 && (hh & 0x7fffu) != 0) ? 0x0000ffffu : 0u;
@@ -622,49 +714,54 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
                         };
                         v.x = keep(v.x, h.x); v.y = keep(v.y, h.y); v.z = keep(v.z, h.z); v.w = keep(v.w, h.w);
                     }
-                }
-                if constexpr (EPI == 1) {
-                    if (g.relu_bits_out != nullptr) {
-                        // 1 bit per stored element: > 0 for a bf16 = sign clear and not zero - what the data gradient's `keep` tests on
-                        // the activation.  A lane's 8 elements are one byte; the 4 lanes of a quad hold 4 consecutive bytes of one
-                        // row (CH and the wave size are multiples of 4), gathered by DPP quad rotations into ONE dword store by the
-                        // quad's first lane (byte stores, 24 per row: + 1.6 us per launch; dwords: see DESIGN.md 5e).
-                        // (a ReLU output is never negative, so "> 0" = "magnitude not zero": adding 0x7fff to a 15-bit magnitude carries
-                        //  into bit 15 exactly when it is not zero - both halves of the pair at once, no compares)
-                        auto pos = [](uint32_t w2) -> uint32_t {
-                            const uint32_t t = (w2 & 0x7fff7fffu) + 0x7fff7fffu;
-                            return ((t >> 15) & 1u) | ((t >> 30) & 2u);
-                        };
-                        const uint32_t b0 = ok ? (pos(v.x) | (pos(v.y) << 2) | (pos(v.z) << 4) | (pos(v.w) << 6)) : 0u;
-                        const uint32_t b1 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)b0, 0x39, 0xf, 0xf, true);      // quad_perm [1,2,3,0]
-                        const uint32_t b2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)b0, 0x4e, 0xf, 0xf, true);      // [2,3,0,1]
-                        const uint32_t b3 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)b0, 0x93, 0xf, 0xf, true);      // [3,0,1,2]
-                        if (ok && (c & 3) == 0)
-                            *reinterpret_cast<uint32_t*>(g.relu_bits_out + (int64_t)(i0 + r) * g.ld_bits + (j >> 3)) = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+                    if constexpr (EPI == 1) {
+                        if (g.relu_bits_out != nullptr) {
+                            // 1 bit per stored element: > 0 for a bf16 = sign clear and not zero - what the data gradient's `keep` tests on
+                            // the activation.  A lane's 8 elements are one byte; the 4 lanes of a quad hold 4 consecutive bytes of one
+                            // row (CH and the wave size are multiples of 4), gathered by DPP quad rotations into ONE dword store by the
+                            // quad's first lane (byte stores, 24 per row: + 1.6 us per launch; dwords: see DESIGN.md 5e).
+                            // (a ReLU output is never negative, so "> 0" = "magnitude not zero": adding 0x7fff to a 15-bit magnitude carries
+                            //  into bit 15 exactly when it is not zero - both halves of the pair at once, no compares)
+                            auto pos = [](uint32_t w2) -> uint32_t {
+                                const uint32_t t = (w2 & 0x7fff7fffu) + 0x7fff7fffu;
+                                return ((t >> 15) & 1u) | ((t >> 30) & 2u);
+                            };
+                            const uint32_t b0 = ok ? (pos(v.x) | (pos(v.y) << 2) | (pos(v.z) << 4) | (pos(v.w) << 6)) : 0u;
+                            const uint32_t b1 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)b0, 0x39, 0xf, 0xf, true);      // quad_perm [1,2,3,0]
+                            const uint32_t b2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)b0, 0x4e, 0xf, 0xf, true);      // [2,3,0,1]
+                            const uint32_t b3 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)b0, 0x93, 0xf, 0xf, true);      // [3,0,1,2]
+                            if (ok && (c & 3) == 0)
+                                *reinterpret_cast<uint32_t*>(g.relu_bits_out + (int64_t)(i0 + r) * g.ld_bits + (j >> 3)) = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+                        }
+                    }
+                    if (ok) {
+                        out.store16(Cb + (int64_t)(i0 + r) * g.ldc + j, (uint32_t)(r * (int)g.ldc + j) * 2u, (u32x4){v.x, v.y, v.z, v.w});
+                        if (EPI != 1 && g.colsum_part != nullptr) {
+                            cs[0] += bf16_to_f32((bf16_t)(v.x & 0xffff)); cs[1] += bf16_to_f32((bf16_t)(v.x >> 16));
+                            cs[2] += bf16_to_f32((bf16_t)(v.y & 0xffff)); cs[3] += bf16_to_f32((bf16_t)(v.y >> 16));
+                            cs[4] += bf16_to_f32((bf16_t)(v.z & 0xffff)); cs[5] += bf16_to_f32((bf16_t)(v.z >> 16));
+                            cs[6] += bf16_to_f32((bf16_t)(v.w & 0xffff)); cs[7] += bf16_to_f32((bf16_t)(v.w >> 16));
+                        }
                     }
                 }
-                if (ok) {
-                    out.store16(Cb + (int64_t)(i0 + r) * g.ldc + j, (uint32_t)(r * (int)g.ldc + j) * 2u, (u32x4){v.x, v.y, v.z, v.w});
-                    if (EPI != 1 && g.colsum_part != nullptr) {
-                        cs[0] += bf16_to_f32((bf16_t)(v.x & 0xffff)); cs[1] += bf16_to_f32((bf16_t)(v.x >> 16));
-                        cs[2] += bf16_to_f32((bf16_t)(v.y & 0xffff)); cs[3] += bf16_to_f32((bf16_t)(v.y >> 16));
-                        cs[4] += bf16_to_f32((bf16_t)(v.z & 0xffff)); cs[5] += bf16_to_f32((bf16_t)(v.z >> 16));
-                        cs[6] += bf16_to_f32((bf16_t)(v.w & 0xffff)); cs[7] += bf16_to_f32((bf16_t)(v.w >> 16));
-                    }
-                }
-            }
+            };
+            if constexpr (EPI == 1) write_out(std::integral_constant<int, MASK_NONE>{});
+            else if constexpr (EPI == 4) write_out(std::integral_constant<int, MASK_BITS>{});
+            else if (bit_mask) write_out(std::integral_constant<int, MASK_BITS>{});
+            else if (relu_mask) write_out(std::integral_constant<int, MASK_ACT>{});
+            else write_out(std::integral_constant<int, MASK_NONE>{});
         }
         stamp(3);
         if constexpr (dbg_time) { wait_vmcnt<0>(); stamp(4); }
         if (EPI != 1 && g.colsum_part != nullptr) {
-            __syncthreads();
+            phase_barrier();
             float* red = reinterpret_cast<float*>(smem_raw);
             static_assert(RL * BN * 4 <= 2 * BUF, "reduction scratch must fit");
             if (rl < RL) {
 #pragma unroll
                 for (int k = 0; k < 8; ++k) red[rl * BN + c * 8 + k] = cs[k];
             }
-            __syncthreads();
+            phase_barrier();
             for (int col = threadIdx.x; col < BN; col += NT) {
                 float sum = 0.f;
                 for (int r = 0; r < RL; ++r) sum += red[r * BN + col];
@@ -690,6 +787,11 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
         const int c = threadIdx.x % CH, rl = threadIdx.x / CH;
         const int j = j0 + c * 4;
         float sq = 0.f;                                  // sum of the stored values' squares (g.sumsq_slots)
+        float4 bjs[2][TNH];                              // (read once, in front of the first staging write: see the bf16 path)
+#pragma unroll
+        for (int nh = 0; nh < 2; ++nh)
+#pragma unroll
+            for (int nt = 0; nt < TNH; ++nt) bjs[nh][nt] = bias4(nh * BHR + wc * (SN / 2) + 16 * nt + g4);
 #pragma unroll
         for (int hh = 0; hh < 2; ++hh) {
 #pragma unroll
@@ -697,7 +799,7 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
 #pragma unroll
                 for (int nt = 0; nt < TNH; ++nt) {
                     const int jl = nh * BHR + wc * (SN / 2) + 16 * nt + g4;
-                    const float4 bj = load_bias4(g.bias, g.A, j0 + jl, g.N);
+                    const float4 bj = bjs[nh][nt];
 #pragma unroll
                     for (int mt = 0; mt < TMH; ++mt) {
                         const int il = wr * (SM / 2) + 16 * mt + li;          // row inside this half
@@ -708,7 +810,7 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
                         *reinterpret_cast<__attribute__((address_space(3))) f32x4*>(smem + il * PITCH + jl * 4) = v;
                     }
                 }
-            __syncthreads();
+            phase_barrier();
             constexpr int ITER = (HR + RL - 1) / RL;
             const TileStore<POL> out(Cf + (int64_t)(i0 + hh * HR) * g.ldc);
 #pragma unroll
@@ -721,14 +823,14 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
                     sq += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
                 }
             }
-            __syncthreads();
+            phase_barrier();
         }
         if (g.sumsq_slots != nullptr) {      // an unsplit weight gradient: clip_grad_norm_'s sum g^2 without a pass of its own
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
             float* red = reinterpret_cast<float*>(smem_raw);
             if (lane == 0) red[w] = sq;
-            __syncthreads();
+            phase_barrier();
             if (threadIdx.x == 0) {
                 float t = 0.f;
                 for (int ww = 0; ww < NW; ++ww) t += red[ww];
@@ -741,9 +843,9 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
 template <int BM, int BN, int WM, int WN, int NLB, int A_MODE, int B_MODE, bool C_F32, int DBG = 0, int EPI = 0, int POL = STORE_PLAIN>
 __global__ __launch_bounds__(64 * WM * WN, (WM * WN + 3) / 4)
 void gemm_bf16_pipe_kernel(GemmBf16 g, int tiles_n, int tiles_mn, int kt_total) {
-    // (EPI = 3: + {dataset row, mask id} of the tile's rows; ONE array: a second __shared__ object beside an LDS-DMA
+    // (behind the K-tile buffers: EPI 3's {dataset row, mask id} of the tile's rows, the parked bias slice and ReLU bits; ONE array: a second __shared__ object beside an LDS-DMA
     // staging array makes the compiler drain vmcnt in front of LDS reads)
-    __shared__ __attribute__((aligned(16))) char smem_raw[2 * (BM + BN) * 128 + (EPI == 3 ? BM * 8 : 0)];
+    __shared__ __attribute__((aligned(16))) char smem_raw[pipe_smem_bytes<BM, BN, C_F32, EPI>()];
     gemm_bf16_pipe_tile<BM, BN, WM, WN, NLB, A_MODE, B_MODE, C_F32, DBG, EPI, POL>(g, tiles_n, tiles_mn, kt_total, blockIdx.x, gridDim.x, smem_raw);
 }
 
@@ -755,7 +857,7 @@ void gemm_bf16_pipe_kernel(GemmBf16 g, int tiles_n, int tiles_mn, int kt_total) 
 template <int POL>
 __global__ __launch_bounds__(512, 2) void gemm_bf16_pipe_grouped_kernel(GemmBf16Group grp) {
     constexpr int BM = 256, BN = 192;
-    __shared__ __attribute__((aligned(16))) char smem_raw[2 * (BM + BN) * 128];
+    __shared__ __attribute__((aligned(16))) char smem_raw[pipe_smem_bytes<BM, BN, true, 0>()];
     // Workgroup b runs on XCD b % 8, the s-th of that XCD's workgroups (s = b / 8).  Each XCD takes a CONTIGUOUS eighth of the
     // launch's tile list (GEMM after GEMM, row panel after row panel), so that the 32 workgroups an XCD runs at a time are 4
     // consecutive row panels x all column tiles of ONE weight gradient: they share 4 dA strips and the layer's 8 H strips in that
@@ -788,9 +890,10 @@ int launch_pipe(const GemmBf16& g, const Bf16Plan& p, hipStream_t s) {
 #define LAUNCH(AM, BMODE, CF, EP) \
     do { if (p.store_policy == STORE_WT) PIPE_LAUNCH(BM, BN, NLB, AM, BMODE, CF, 0, EP, STORE_WT); else PIPE_LAUNCH(BM, BN, NLB, AM, BMODE, CF, 0, EP, STORE_PLAIN); } while (0)
 #define LAUNCH_BF16(AM, BMODE) do { if (p.epi == 2) LAUNCH(AM, BMODE, false, 2); else LAUNCH(AM, BMODE, false, 1); } while (0)
+    const bool bits = p.epi == 2 && g.relu_bits != nullptr;          // (the forward-form data gradient behind a forward that left bits)
     if (p.dbg == 64) PIPE_LAUNCH(BM, BN, NLB, OP_KC, OP_KC, false, 64, 2, STORE_PLAIN);      // the compiler's schedule (GemmBf16::coscheduled)
     else if (p.epi == 3) LAUNCH(OP_KC, OP_KC, false, 3);
-    else if (g.a_mode == OP_KC && g.b_mode == OP_KC) { if (g.c_f32) LAUNCH(OP_KC, OP_KC, true, 0); else LAUNCH_BF16(OP_KC, OP_KC); }
+    else if (g.a_mode == OP_KC && g.b_mode == OP_KC) { if (g.c_f32) LAUNCH(OP_KC, OP_KC, true, 0); else if (bits) LAUNCH(OP_KC, OP_KC, false, 4); else LAUNCH_BF16(OP_KC, OP_KC); }
     else if (g.a_mode == OP_KC && g.b_mode == OP_KS) { if (g.c_f32) LAUNCH(OP_KC, OP_KS, true, 0); else LAUNCH_BF16(OP_KC, OP_KS); }
     else if (g.a_mode == OP_KS && g.b_mode == OP_KS) { if (g.c_f32) LAUNCH(OP_KS, OP_KS, true, 0); else LAUNCH_BF16(OP_KS, OP_KS); }
     else { set_error("gemm_bf16: operand mode combination not built"); return CODAE_E_UNSUPPORTED; }
