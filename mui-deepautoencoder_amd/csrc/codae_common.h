@@ -91,28 +91,28 @@ __device__ __forceinline__ float4 load_bias4(const float* __restrict__ bias, con
 // elements - and the double-float steps inside the device library's expm1f / log1pf - into v_pk_*_f32 with op_sel routing
 // (tools/check_isa.py rule 4 rejects that form).  So exp / log are the hardware v_exp_f32 / v_log_f32
 // and expm1 / log1p Kahan's identities on top of them (a few fp32 ulps; the fp32 engine's bar is rtol 1e-3).
-__device__ __forceinline__ float act_opaque(float x) { asm("" : "+v"(x)); return x; }
-__device__ __forceinline__ float act_exp(float x) { return __builtin_amdgcn_exp2f(act_opaque(x * 1.44269504f)); }
-__device__ __forceinline__ float act_log(float x) { return act_opaque(__builtin_amdgcn_logf(x)) * 0.693147181f; }
+__device__ __forceinline__ float opaque(float x) { asm("" : "+v"(x)); return x; }
+__device__ __forceinline__ float act_exp(float x) { return __builtin_amdgcn_exp2f(opaque(x * 1.44269504f)); }
+__device__ __forceinline__ float act_log(float x) { return opaque(__builtin_amdgcn_logf(x)) * 0.693147181f; }
 __device__ __forceinline__ float act_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 __device__ __forceinline__ float act_expm1(float x) {     // (u - 1) x / log u: the rounding of u cancels
-    const float u = act_opaque(act_exp(x));
-    const float um1 = act_opaque(u - 1.f);
+    const float u = opaque(act_exp(x));
+    const float um1 = opaque(u - 1.f);
     if (u == 1.f) return x;
     if (um1 == -1.f) return -1.f;
-    return act_opaque(um1 * x) * act_rcp(act_log(u));
+    return opaque(um1 * x) * act_rcp(act_log(u));
 }
 __device__ __forceinline__ float act_log1p(float t) {     // t log(1 + t) / ((1 + t) - 1)
-    const float u = act_opaque(1.f + t);
+    const float u = opaque(1.f + t);
     if (u == 1.f) return t;
-    return act_opaque(act_log(u) * t) * act_rcp(act_opaque(u - 1.f));
+    return opaque(act_log(u) * t) * act_rcp(opaque(u - 1.f));
 }
 __device__ __forceinline__ float act_fwd_(int kind, const float* p, float v) {
     switch (kind) {
         case CODAE_ACT_RELU: return clamp_below(v, 0.f);              // (NaN stays NaN: every kind, as torch.nn's modules)
         case CODAE_ACT_LEAKY: return v > 0.f ? v : v * p[0];
         case CODAE_ACT_RELU6: return v <= 0.f ? 0.f : (v >= 6.f ? 6.f : v);
-        case CODAE_ACT_ELU: return v > 0.f ? v * p[0] : act_expm1(v * p[2]) * act_opaque(p[1] * p[0]);
+        case CODAE_ACT_ELU: return v > 0.f ? v * p[0] : act_expm1(v * p[2]) * opaque(p[1] * p[0]);
         case CODAE_ACT_SOFTPLUS: return v * p[0] > p[1] ? v : act_log1p(act_exp(v * p[0])) * act_rcp(p[0]);
         case CODAE_ACT_HARDSIGMOID: { const float t = clamp_below(v + 3.f, 0.f); return (t > 6.f ? 6.f : t) * (1.f / 6.f); }
         default: return v;
@@ -129,7 +129,7 @@ __device__ __forceinline__ float act_dy_from_y_(int kind, const float* p, float 
         case CODAE_ACT_RELU: return y > 0.f ? 1.f : 0.f;
         case CODAE_ACT_LEAKY: return y > 0.f ? 1.f : p[0];
         case CODAE_ACT_RELU6: return (y > 0.f && y < 6.f) ? 1.f : 0.f;
-        case CODAE_ACT_ELU: return y > 0.f ? p[0] : p[2] * act_opaque(y + act_opaque(p[1] * p[0]));
+        case CODAE_ACT_ELU: return y > 0.f ? p[0] : p[2] * opaque(y + opaque(p[1] * p[0]));
         case CODAE_ACT_SOFTPLUS: return y * p[0] > p[1] ? 1.f : -act_expm1(-y * p[0]);
         case CODAE_ACT_HARDSIGMOID: return (y > 0.f && y < 1.f) ? 1.f / 6.f : 0.f;
         default: return 1.f;
@@ -445,12 +445,21 @@ int launch_cast_bf16(const float* src, bf16_t* dst, int64_t n, hipStream_t s);
 int launch_corrupt(const float* x, const float* mask, float* out, int64_t n, hipStream_t s);
 int launch_expand_masks(const int32_t* mask_id, const uint8_t* table, const int32_t* k_of_mask, int B, int io,
                         int k_max, float* masks_out, float* fmask_out, hipStream_t s);
-// y fp32 [B][io]; x gathered from batch; writes dy (fp32 or bf16), metric sums, optional colsum_part
-// [mse_loss_colsum_rows(B)][io] (partial sums of the last bias gradient, one row per block)
-// loss_parts [mse_loss_colsum_rows(B)][2]: per-block metric sums (see LossFuse::parts)
-int launch_mse_loss(const codae_batch* b, const float* y, void* dy, int dy_bf16, float inv_n, float* colsum_part,
-                    double* loss_parts, int want_grad, hipStream_t s, int64_t dy_ld = 0,     // dy_ld: row stride of dy (0 = io)
-                    const uint8_t* present = nullptr, int n_slots = 0);
+// One stand-alone loss launch: y fp32 [B][io], x gathered from `batch`; writes dy (fp32 or bf16, row stride dy_ld; 0 = io), one
+// colsum_part row per block (partial sums of the last bias gradient; may be null) and the per-block sums `parts`.
+// noise / step / step_dev as launch_gather_noise (which elements the gather replaced is recomputed from the same words); emph may
+// be null (all weights 1); present != null: the presence table [n_rows][n_slots] - the PRES instantiations.
+struct LossLaunch {
+    const codae_batch* batch; const codae_noise* noise; int32_t step; const double* step_dev;
+    const codae_emphasis* emph; const uint8_t* present; int n_slots;
+    const float* y; void* dy; int dy_bf16; int64_t dy_ld; float scale /* inv_n, or the contrast's scale */;
+    float* colsum_part; double* parts;
+};
+inline int64_t loss_dy_ld(const LossLaunch& ll) { return ll.dy_ld > 0 ? ll.dy_ld : (ll.batch ? ll.batch->io : 0); }
+// the argument checks every loss launcher makes, the error texts prefixed with `who`; needs_dy: dy must be there
+int check_loss_launch(const char* who, const LossLaunch& ll, bool needs_dy);
+// parts [mse_loss_colsum_rows(B)][2]: per-block metric sums (see LossFuse::parts); want_grad 0: the sums alone (dy may be null)
+int launch_mse_loss(const LossLaunch& ll, int want_grad, hipStream_t s);
 int mse_loss_colsum_rows(int B);
 // The emphasised denoising loss (codae_emphasis, include/codae_hip.h): launch_mse_loss's block shape - mse_loss_colsum_rows(B)
 // blocks, one colsum_part row each - with a weight per element; `noise` / step / step_dev as launch_gather_noise (which elements
@@ -458,18 +467,14 @@ int mse_loss_colsum_rows(int B);
 // sum (1-fmask)(x-y)^2; launch_finish_emph_loss adds them up in block order: LAST_LOSS = weighted sum * inv_n, the epoch
 // accumulators take the unweighted two.  check_emphasis: CODAE_E_INVALID for a negative or non-finite alpha / beta.
 int check_emphasis(const codae_emphasis* emph);
-int launch_emph_loss(const codae_batch* b, const codae_noise* noise, int32_t step, const double* step_dev, const codae_emphasis* emph,
-                     const float* y, void* dy, int dy_bf16, int64_t dy_ld, float inv_n, float* colsum_part, double* parts,
-                     hipStream_t s, const uint8_t* present = nullptr, int n_slots = 0);
+int launch_emph_loss(const LossLaunch& ll, hipStream_t s);
 int launch_finish_emph_loss(double* scalars, double inv_n, hipStream_t s, const double* parts, int n_parts);
 // A training criterion other than the MSE (codae_recon_loss, include/codae_hip.h; recon_loss.hip): launch_emph_loss's block shape,
 // arguments and outputs, `emph` may be null (all weights 1); parts[.][0] is the criterion's sum, so launch_finish_emph_loss
 // finishes it.  check_recon_loss: CODAE_E_INVALID / CODAE_E_UNSUPPORTED as codae_set_recon_loss documents (io <= 0: not checked
 // against n_slots).
 int check_recon_loss(const codae_recon_loss* loss, int io);
-int launch_recon_loss(const codae_batch* b, const codae_noise* noise, int32_t step, const double* step_dev, const codae_emphasis* emph,
-                      const codae_recon_loss* loss, const float* y, void* dy, int dy_bf16, int64_t dy_ld, float inv_n, float* colsum_part,
-                      double* parts, hipStream_t s, const uint8_t* present = nullptr, int n_slots = 0);
+int launch_recon_loss(const LossLaunch& ll, const codae_recon_loss* loss, hipStream_t s);
 // Sampled-softmax slot contrast (codae_slot_contrast, include/codae_hip.h; slot_contrast.hip): an additional term on top of the
 // criterion.  prepare fills the work space with the step's S x K normalised candidates; launch_slot_contrast adds the term's
 // gradient to the dy the criterion's kernel left (operand type of the products = dy's type), leaves slot_contrast_blocks(B) rows of
@@ -481,9 +486,7 @@ inline int slot_contrast_blocks(int B) { return (B + 31) / 32; }
 int slot_contrast_warm();     // one-time kernel attributes, outside any stream capture
 int launch_slot_contrast_prepare(const float* data, int io, const codae_slot_contrast* c, int32_t step, const double* step_dev, int bf16,
                                  hipStream_t s, const uint8_t* present = nullptr, int n_slots = 0);
-int launch_slot_contrast(const codae_batch* b, const codae_noise* noise, int32_t step, const double* step_dev, const codae_emphasis* emph,
-                         const codae_slot_contrast* c, const float* y, void* dy, int dy_bf16, int64_t dy_ld, float scale,
-                         float* colsum_part, double* parts, hipStream_t s, const uint8_t* present = nullptr, int n_slots = 0);
+int launch_slot_contrast(const LossLaunch& ll, const codae_slot_contrast* c, hipStream_t s);
 int launch_slot_contrast_finish(double* scalars, double scale, const double* parts, int n_parts, hipStream_t s);
 // Hidden dropout (codae_dropout, include/codae_hip.h; dropout.hip): a <- a * f in place on rows < B, columns < width of a [B][ld]
 // matrix (fp32 or bf16), f from the Philox words of counter (column / 4, dataset row, step, 1 + layer); step_dev as

@@ -19,10 +19,6 @@ struct DropArgs {
     float scale;               // (float)(1 / (1 - p))
 };
 
-// keeps a product a scalar VALU op of its own: the SLP vectorizer otherwise packs neighbouring columns' multiply / add chains into
-// v_pk_*_f32 with op_sel routing (tools/check_isa.py rule 4)
-__device__ __forceinline__ float opaque(float x) { asm("" : "+v"(x)); return x; }
-
 // the factors of columns 4 g .. 4 g + 3 of dataset row `row`
 __device__ __forceinline__ void drop_factors4(float* f, uint32_t g, uint32_t row, uint32_t step, const DropArgs& a) {
     const uint4 r = philox4x32_10(g, row, step, a.word3, a.key0, a.key1);

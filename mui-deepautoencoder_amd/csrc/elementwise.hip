@@ -2,12 +2,13 @@
 // fused MSE loss forward/backward with the reference's per-step metrics, gradient norm,
 // clip + Adam with bf16 shadow refresh.  All are single-pass, 16 B per lane where the
 // row width allows, grid capped at 2048 blocks with a grid-stride loop.
-#include "codae_common.h"
+#include "loss_sweep.h"
 
 namespace codae {
 namespace {
 
 constexpr int NT = 256;
+static_assert(NT == LOSS_NT, "loss_sweep strides the columns by LOSS_NT threads");
 
 inline int grid_for(int64_t work_items) {
     int64_t b = (work_items + NT - 1) / NT;
@@ -16,43 +17,6 @@ inline int grid_for(int64_t work_items) {
     return (int)b;
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// sum over the 256-thread block; result valid in thread 0
-__device__ __forceinline__ float block_sum(float v, float* red /*[4]*/) {
-    v = wave_sum(v);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) red[w] = v;
-    __syncthreads();
-    float r = 0.f;
-    if (threadIdx.x == 0) r = red[0] + red[1] + red[2] + red[3];
-    __syncthreads();
-    return r;
-}
-
-__device__ __forceinline__ uint2 pack_bf16x4(float a, float b, float c, float d) {
-    uint2 o;
-    o.x = (uint32_t)f32_to_bf16(a) | ((uint32_t)f32_to_bf16(b) << 16);
-    o.y = (uint32_t)f32_to_bf16(c) | ((uint32_t)f32_to_bf16(d) << 16);
-    return o;
-}
-
-// sl[k] = slot of column c + k (E columns per slot): one division where the group sits inside one slot
-template <int W>
-__device__ __forceinline__ void slots_of(int c, int E, int* sl) {
-    const int s0 = c / E, rem = c - s0 * E;
-    if (rem + W <= E) {
-#pragma unroll
-        for (int k = 0; k < W; ++k) sl[k] = s0;
-    } else {
-#pragma unroll
-        for (int k = 0; k < W; ++k) sl[k] = s0 + (rem + k) / E;
-    }
-}
 // the gather's presence rule: exactly 0 in every column of an absent slot, behind the noise and the slot mask
 template <int W>
 __device__ __forceinline__ void zero_absent(float* v, const PresArgs& pa, int64_t row, int c) {
@@ -363,11 +327,7 @@ __global__ __launch_bounds__(NT) void expand_masks_kernel(const int32_t* __restr
 //   dy = 2 (y - x) * inv_n                          (autograd of train_dae_on_embedding.py:206)
 //   SQ_FULL    += sum (x-y)^2                        (:218-220)
 //   SQ_PARTIAL += sum (1-fmask)(x-y)^2               (:223)
-constexpr int LOSS_ROWS = 32;   // rows per block = rows per partial column-sum row
-constexpr int LOSS_UNROLL = 8;  // rows in flight per thread
-// PRES (a presence table is set): an absent element's x and y are SELECTED to 0 as they are loaded - x may be NaN there -, so it
-// adds exact zeros to every sum, and its stored dy is +0.  The arithmetic between the loads and the stores is the text of the
-// instantiation without a table: an all-ones table gives its bits.
+// The row sweep and the arithmetic (MseTerm) are loss_sweep.h's; parts[block] = { sq, sqp }
 template <bool VEC, bool DY_BF16, bool PRES>
 __global__ __launch_bounds__(NT) void mse_loss_kernel(const float* __restrict__ data,
                                                       const int32_t* __restrict__ row_idx,
@@ -380,79 +340,11 @@ __global__ __launch_bounds__(NT) void mse_loss_kernel(const float* __restrict__ 
                                                       PresArgs pa) {
     __shared__ float red[4];
     const bool masked = (mask_id != nullptr) || (mask_to_use != nullptr);
-    constexpr int W = VEC ? 4 : 1;
-    const int cols = io / W;
-    const int r_begin = blockIdx.x * LOSS_ROWS;
-    float sq = 0.f, sqp = 0.f;
-    for (int cv = threadIdx.x; cv < cols; cv += NT) {
-        const int c = cv * W;
-        int sl[W];
-        if constexpr (PRES) slots_of<W>(c, pa.E, sl);
-        float cs[4] = {0.f, 0.f, 0.f, 0.f};
-        // rows are independent: unrolled with clamped (always valid) addresses so that the loads of
-        // all LOSS_ROWS rows are in flight together; rows past the batch contribute nothing
-        for (int r0 = 0; r0 < LOSS_ROWS; r0 += LOSS_UNROLL)
-#pragma unroll
-        for (int ru = 0; ru < LOSS_UNROLL; ++ru) {
-            const int rr = r0 + ru;
-            const bool live = r_begin + rr < B;
-            const int b = live ? r_begin + rr : B - 1;
-            const int64_t src_row = row_idx ? row_idx[b] : b;
-            float xv[4], yv[4];
-            uint32_t m = 0x01010101u;
-            const int id = !masked ? 0 : (mask_id ? mask_id[b] : mask_to_use[src_row * nb_run + run]);
-            if constexpr (VEC) {
-                const float4 x4 = *reinterpret_cast<const float4*>(data + src_row * io + c);
-                const float4 y4 = *reinterpret_cast<const float4*>(y + (int64_t)b * io + c);
-                xv[0] = x4.x; xv[1] = x4.y; xv[2] = x4.z; xv[3] = x4.w;
-                yv[0] = y4.x; yv[1] = y4.y; yv[2] = y4.z; yv[3] = y4.w;
-                if (masked) m = *reinterpret_cast<const uint32_t*>(table + (int64_t)id * io + c);
-            } else {
-                xv[0] = data[src_row * io + c];
-                yv[0] = y[(int64_t)b * io + c];
-                if (masked) m = table[(int64_t)id * io + c];
-            }
-            uint32_t pb = 0xfu;
-            if constexpr (PRES) {
-                pb = present_bits<W>(pa, src_row, sl);
-#pragma unroll
-                for (int k = 0; k < W; ++k)
-                    if (!((pb >> k) & 1u)) { xv[k] = 0.f; yv[k] = 0.f; }
-            }
-            float g[4];
-#pragma unroll
-            for (int k = 0; k < W; ++k) {
-                const float d = live ? xv[k] - yv[k] : 0.f;
-                const float se = d * d;
-                sq += se;
-                if (((m >> (8 * k)) & 0xff) == 0) sqp += se;
-                g[k] = -2.f * d * inv_n;
-                cs[k] += g[k];
-            }
-            if constexpr (PRES) {      // (-2 * 0 is -0: the column sum does not see the sign, the stored gradient is +0)
-#pragma unroll
-                for (int k = 0; k < W; ++k) g[k] = ((pb >> k) & 1u) ? g[k] : 0.f;
-            }
-            if (want_grad && live) {
-                const int64_t o = (int64_t)b * dy_ld + c;
-                if constexpr (DY_BF16) {
-                    bf16_t* op = reinterpret_cast<bf16_t*>(dy) + o;
-                    if constexpr (VEC) *reinterpret_cast<uint2*>(op) = pack_bf16x4(g[0], g[1], g[2], g[3]);
-                    else op[0] = f32_to_bf16(g[0]);
-                } else {
-                    float* op = reinterpret_cast<float*>(dy) + o;
-                    if constexpr (VEC) *reinterpret_cast<float4*>(op) = make_float4(g[0], g[1], g[2], g[3]);
-                    else op[0] = g[0];
-                }
-            }
-        }
-        if (want_grad && colsum_part) {
-#pragma unroll
-            for (int k = 0; k < W; ++k) colsum_part[(int64_t)blockIdx.x * io + c + k] = cs[k];
-        }
-    }
-    const float bsq = block_sum(sq, red);
-    const float bsqp = block_sum(sqp, red);
+    const BatchArgs ba{data, row_idx, mask_id, table, mask_to_use, nb_run, run, B, io};
+    MseTerm term(inv_n, want_grad);
+    loss_sweep<VEC, DY_BF16, PRES>(ba, y, dy, dy_ld, colsum_part, pa, WeightArgs{}, term);
+    const float bsq = block_sum(term.sq, red);
+    const float bsqp = block_sum(term.sqp, red);
     if (threadIdx.x == 0) {
         loss_parts[2 * blockIdx.x] = (double)bsq;
         loss_parts[2 * blockIdx.x + 1] = masked ? (double)bsqp : 0.0;
@@ -460,131 +352,23 @@ __global__ __launch_bounds__(NT) void mse_loss_kernel(const float* __restrict__ 
 }
 
 // ---- emphasised denoising loss (codae_emphasis, include/codae_hip.h; Vincent et al. 2010, section 4.3) ----------------------
-// mse_loss_kernel's block shape (LOSS_ROWS rows per block, one partial column-sum row per block) with a weight per element:
-//   w  = col_weight[c] * (corrupted ? alpha : beta),  corrupted = blanked by the slot mask OR replaced by the input noise
-//   dy = 2 w (y - x) inv_n, written as (-2 d) (w inv_n): with w == 1 the product mse_loss_kernel forms, bit for bit
+// mse_loss_kernel's block shape with a weight per element (WeightArgs and EmphTerm, loss_sweep.h):
 //   parts[block] = { sum w (x-y)^2, sum (x-y)^2, sum (1-fmask)(x-y)^2 }: the metric sums stay unweighted
-// "replaced" is recomputed from the element's Philox word (the gather's counter: column / 4, DATASET row, step), one call per
-// four columns; nothing is read back from the noised input, so the kernel works on the clean row alone.
-struct EmphArgs {
-    float alpha, beta;
-    const float* col_weight;   // [io] or null (all ones)
-    int replace;               // the input noise is MASKING or SALT_PEPPER: a word below thresh marks a replaced element
-    uint64_t thresh;           // T = floor(p 2^32)
-    uint32_t key0, key1;
-    uint32_t step;             // counter word 2 ...
-    const double* step_dev;    // ... or, when not null, *step_dev (graph replay)
-};
-
-// PRES: as in mse_loss_kernel - x and y selected to 0 at the loads, +0 at the store: selection, not a weight of 0, so a NaN in an
-// absent element of x reaches nothing.
 template <bool VEC, bool DY_BF16, bool PRES>
 __global__ __launch_bounds__(NT) void emph_loss_kernel(const float* __restrict__ data, const int32_t* __restrict__ row_idx,
                                                        const int32_t* __restrict__ mask_id, const uint8_t* __restrict__ table,
                                                        int B, int io, const float* __restrict__ y, void* __restrict__ dy,
                                                        float inv_n, float* __restrict__ colsum_part, double* __restrict__ parts,
                                                        const int32_t* __restrict__ mask_to_use, int nb_run, int run, int64_t dy_ld,
-                                                       EmphArgs ea, PresArgs pa) {
+                                                       WeightArgs wa, PresArgs pa) {
     __shared__ float red[4];
     const bool masked = (mask_id != nullptr) || (mask_to_use != nullptr);
-    const uint32_t step = ea.step_dev ? (uint32_t)*ea.step_dev : ea.step;
-    constexpr int W = VEC ? 4 : 1;
-    const int cols = io / W;
-    const int r_begin = blockIdx.x * LOSS_ROWS;
-    float wsq = 0.f, sq = 0.f, sqp = 0.f;
-    for (int cv = threadIdx.x; cv < cols; cv += NT) {
-        const int c = cv * W;
-        int sl[W];
-        if constexpr (PRES) slots_of<W>(c, pa.E, sl);
-        float cw[4] = {1.f, 1.f, 1.f, 1.f};
-        if (ea.col_weight != nullptr) {
-            if constexpr (VEC) {
-                const float4 w4 = *reinterpret_cast<const float4*>(ea.col_weight + c);
-                cw[0] = w4.x; cw[1] = w4.y; cw[2] = w4.z; cw[3] = w4.w;
-            } else {
-                cw[0] = ea.col_weight[c];
-            }
-        }
-        float cs[4] = {0.f, 0.f, 0.f, 0.f};
-        // rows as in mse_loss_kernel: clamped (always valid) addresses, rows past the batch contribute nothing
-        for (int r0 = 0; r0 < LOSS_ROWS; r0 += LOSS_UNROLL)
-#pragma unroll
-        for (int ru = 0; ru < LOSS_UNROLL; ++ru) {
-            const int rr = r0 + ru;
-            const bool live = r_begin + rr < B;
-            const int b = live ? r_begin + rr : B - 1;
-            const int64_t src_row = row_idx ? row_idx[b] : b;
-            float xv[4], yv[4];
-            uint32_t m = 0x01010101u;
-            const int id = !masked ? 0 : (mask_id ? mask_id[b] : mask_to_use[src_row * nb_run + run]);
-            if constexpr (VEC) {
-                const float4 x4 = *reinterpret_cast<const float4*>(data + src_row * io + c);
-                const float4 y4 = *reinterpret_cast<const float4*>(y + (int64_t)b * io + c);
-                xv[0] = x4.x; xv[1] = x4.y; xv[2] = x4.z; xv[3] = x4.w;
-                yv[0] = y4.x; yv[1] = y4.y; yv[2] = y4.z; yv[3] = y4.w;
-                if (masked) m = *reinterpret_cast<const uint32_t*>(table + (int64_t)id * io + c);
-            } else {
-                xv[0] = data[src_row * io + c];
-                yv[0] = y[(int64_t)b * io + c];
-                if (masked) m = table[(int64_t)id * io + c];
-            }
-            bool hit[4] = {false, false, false, false};
-            if (ea.replace) {
-                const uint4 r = philox4x32_10((uint32_t)(c >> 2), (uint32_t)src_row, step, 0u, ea.key0, ea.key1);
-                if constexpr (VEC) {
-                    hit[0] = (uint64_t)r.x < ea.thresh; hit[1] = (uint64_t)r.y < ea.thresh;
-                    hit[2] = (uint64_t)r.z < ea.thresh; hit[3] = (uint64_t)r.w < ea.thresh;
-                } else {
-                    const int k = c & 3;            // word k of the group (selects, no indexed register array)
-                    const uint32_t rk = (k & 2) ? ((k & 1) ? r.w : r.z) : ((k & 1) ? r.y : r.x);
-                    hit[0] = (uint64_t)rk < ea.thresh;
-                }
-            }
-            uint32_t pb = 0xfu;
-            if constexpr (PRES) {
-                pb = present_bits<W>(pa, src_row, sl);
-#pragma unroll
-                for (int k = 0; k < W; ++k)
-                    if (!((pb >> k) & 1u)) { xv[k] = 0.f; yv[k] = 0.f; }
-            }
-            float g[4];
-#pragma unroll
-            for (int k = 0; k < W; ++k) {
-                const bool blank = ((m >> (8 * k)) & 0xff) == 0;
-                const float w = live ? cw[k] * ((blank || hit[k]) ? ea.alpha : ea.beta) : 0.f;
-                const float d = live ? xv[k] - yv[k] : 0.f;
-                const float se = d * d;
-                wsq += w * se;
-                sq += se;
-                if (blank) sqp += se;
-                g[k] = -2.f * d * (w * inv_n);
-                cs[k] += g[k];
-            }
-            if constexpr (PRES) {      // (the stored gradient of an absent element is +0, not the product's -0)
-#pragma unroll
-                for (int k = 0; k < W; ++k) g[k] = ((pb >> k) & 1u) ? g[k] : 0.f;
-            }
-            if (live) {
-                const int64_t o = (int64_t)b * dy_ld + c;
-                if constexpr (DY_BF16) {
-                    bf16_t* op = reinterpret_cast<bf16_t*>(dy) + o;
-                    if constexpr (VEC) *reinterpret_cast<uint2*>(op) = pack_bf16x4(g[0], g[1], g[2], g[3]);
-                    else op[0] = f32_to_bf16(g[0]);
-                } else {
-                    float* op = reinterpret_cast<float*>(dy) + o;
-                    if constexpr (VEC) *reinterpret_cast<float4*>(op) = make_float4(g[0], g[1], g[2], g[3]);
-                    else op[0] = g[0];
-                }
-            }
-        }
-        if (colsum_part) {
-#pragma unroll
-            for (int k = 0; k < W; ++k) colsum_part[(int64_t)blockIdx.x * io + c + k] = cs[k];
-        }
-    }
-    const float bwsq = block_sum(wsq, red);
-    const float bsq = block_sum(sq, red);
-    const float bsqp = block_sum(sqp, red);
+    const BatchArgs ba{data, row_idx, mask_id, table, mask_to_use, nb_run, run, B, io};
+    EmphTerm term(wa, inv_n);
+    loss_sweep<VEC, DY_BF16, PRES>(ba, y, dy, dy_ld, colsum_part, pa, wa, term);
+    const float bwsq = block_sum(term.wsq, red);
+    const float bsq = block_sum(term.sq, red);
+    const float bsqp = block_sum(term.sqp, red);
     if (threadIdx.x == 0) {
         parts[3 * blockIdx.x] = (double)bwsq;
         parts[3 * blockIdx.x + 1] = (double)bsq;
@@ -1070,8 +854,6 @@ __global__ __launch_bounds__(NT) void transpose_bf16_kernel(const bf16_t* __rest
     }
 }
 
-inline bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 int check_presence(const uint8_t* present, int n_slots, int io, const char* who) {
@@ -1116,8 +898,6 @@ int launch_gather_corrupt(const codae_batch* b, void* out, int out_bf16, hipStre
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;
 }
-
-static bool finite_f(float x) { return x == x && fabsf(x) <= 3.402823466e38f; }
 
 int check_noise(const codae_noise* n) {
     if (n == nullptr || n->kind == CODAE_NOISE_NONE) return CODAE_OK;
@@ -1228,29 +1008,37 @@ int launch_expand_masks(const int32_t* mask_id, const uint8_t* table, const int3
 
 int mse_loss_colsum_rows(int B) { return (B + LOSS_ROWS - 1) / LOSS_ROWS; }
 
-int launch_mse_loss(const codae_batch* b, const float* y, void* dy, int dy_bf16, float inv_n, float* colsum_part,
-                    double* loss_parts, int want_grad, hipStream_t s, int64_t dy_ld, const uint8_t* present, int n_slots) {
-    if (dy_ld <= 0) dy_ld = b ? b->io : 0;
-    CODAE_REQUIRE(b && b->data && y && loss_parts && b->B > 0 && b->io > 0, "mse_loss: bad args");
-    int prc = check_presence(present, n_slots, b->io, "mse_loss");
-    if (prc) return prc;
-    const PresArgs pa{present, n_slots, present ? b->io / n_slots : 0};
-    CODAE_REQUIRE(!want_grad || dy, "mse_loss: gradient requested without dy");
+int check_loss_launch(const char* who, const LossLaunch& ll, bool needs_dy) {
+    const codae_batch* b = ll.batch;
+    CODAE_REQUIRE(b && b->data && ll.y && ll.parts && (ll.dy || !needs_dy) && b->B > 0 && b->io > 0, "%s: bad args", who);
+    int rc = check_presence(ll.present, ll.n_slots, b->io, who);
+    if (rc) return rc;
+    rc = check_emphasis(ll.emph);
+    if (rc) return rc;
+    rc = check_noise(ll.noise);
+    if (rc) return rc;
     const bool masked = b->mask_id || b->mask_to_use;
-    CODAE_REQUIRE(!masked || b->mask_table, "mse_loss: mask ids without mask_table");
-    const bool vec = (b->io % 4 == 0) && (dy_ld % 4 == 0) && a16(b->data) && a16(y) && (!dy || a16(dy)) &&
-                     (!masked || (reinterpret_cast<uintptr_t>(b->mask_table) & 3) == 0);
-    const int grid = (b->B + LOSS_ROWS - 1) / LOSS_ROWS;
-#define MLP(V, O, P) hipLaunchKernelGGL((mse_loss_kernel<V, O, P>), dim3(grid), dim3(NT), 0, s, b->data, b->row_idx, \
-                                    b->mask_id, b->mask_table, b->B, b->io, y, dy, inv_n, colsum_part, loss_parts, want_grad, \
-                                    b->mask_to_use, b->nb_run, b->run, dy_ld, pa)
-#define ML(V, O) do { if (present) MLP(V, O, true); else MLP(V, O, false); } while (0)
-    if (vec && dy_bf16) ML(true, true);
-    else if (vec) ML(true, false);
-    else if (dy_bf16) ML(false, true);
-    else ML(false, false);
-#undef ML
-#undef MLP
+    CODAE_REQUIRE(!masked || b->mask_table, "%s: mask ids without mask_table", who);
+    if (!needs_dy) return CODAE_OK;      // (a launch that may run for its sums alone takes dy's stride and the run as they come)
+    CODAE_REQUIRE(loss_dy_ld(ll) >= b->io, "%s: dy_ld %lld below io %d", who, (long long)loss_dy_ld(ll), b->io);
+    CODAE_REQUIRE(!b->mask_to_use || b->mask_id || (b->nb_run > 0 && b->run >= 0 && b->run < b->nb_run),
+                  "%s: run %d outside [0, %d)", who, b->run, b->nb_run);
+    return CODAE_OK;
+}
+
+int launch_mse_loss(const LossLaunch& ll, int want_grad, hipStream_t s) {
+    int rc = check_loss_launch("mse_loss", ll, false);
+    if (rc) return rc;
+    CODAE_REQUIRE(!want_grad || ll.dy, "mse_loss: gradient requested without dy");
+    const codae_batch* b = ll.batch;
+    const int64_t dy_ld = loss_dy_ld(ll);
+    const bool vec = (b->io % 4 == 0) && (dy_ld % 4 == 0) && loss_inputs_a16(ll) && (!ll.dy || a16(ll.dy));
+    const dim3 grid(mse_loss_colsum_rows(b->B));
+    loss_dispatch(vec, ll.dy_bf16, ll.present != nullptr, [&](auto V, auto O, auto P) {
+        hipLaunchKernelGGL((mse_loss_kernel<decltype(V)::value, decltype(O)::value, decltype(P)::value>), grid, dim3(NT), 0, s, b->data,
+                           b->row_idx, b->mask_id, b->mask_table, b->B, b->io, ll.y, ll.dy, ll.scale, ll.colsum_part, ll.parts, want_grad,
+                           b->mask_to_use, b->nb_run, b->run, dy_ld, pres_args(ll));
+    });
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;
 }
@@ -1262,44 +1050,20 @@ int check_emphasis(const codae_emphasis* e) {
     return CODAE_OK;
 }
 
-int launch_emph_loss(const codae_batch* b, const codae_noise* noise, int32_t step, const double* step_dev, const codae_emphasis* emph,
-                     const float* y, void* dy, int dy_bf16, int64_t dy_ld, float inv_n, float* colsum_part, double* parts,
-                     hipStream_t s, const uint8_t* present, int n_slots) {
-    if (dy_ld <= 0) dy_ld = b ? b->io : 0;
-    CODAE_REQUIRE(b && b->data && y && dy && parts && emph && b->B > 0 && b->io > 0, "emph_loss: bad args");
-    int prc = check_presence(present, n_slots, b->io, "emph_loss");
-    if (prc) return prc;
-    const PresArgs pa{present, n_slots, present ? b->io / n_slots : 0};
-    CODAE_REQUIRE(dy_ld >= b->io, "emph_loss: dy_ld %lld below io %d", (long long)dy_ld, b->io);
-    int rc = check_emphasis(emph);
+int launch_emph_loss(const LossLaunch& ll, hipStream_t s) {
+    CODAE_REQUIRE(ll.emph, "emph_loss: bad args");
+    int rc = check_loss_launch("emph_loss", ll, true);
     if (rc) return rc;
-    rc = check_noise(noise);
-    if (rc) return rc;
-    const bool masked = b->mask_id || b->mask_to_use;
-    CODAE_REQUIRE(!masked || b->mask_table, "emph_loss: mask ids without mask_table");
-    CODAE_REQUIRE(!b->mask_to_use || b->mask_id || (b->nb_run > 0 && b->run >= 0 && b->run < b->nb_run),
-                  "emph_loss: run %d outside [0, %d)", b->run, b->nb_run);
-    EmphArgs ea{};
-    ea.alpha = emph->alpha; ea.beta = emph->beta; ea.col_weight = emph->col_weight;
-    ea.step = (uint32_t)step; ea.step_dev = step_dev;
-    if (noise != nullptr && (noise->kind == CODAE_NOISE_MASKING || noise->kind == CODAE_NOISE_SALT_PEPPER)) {
-        ea.replace = 1;
-        ea.key0 = (uint32_t)(noise->seed & 0xffffffffu); ea.key1 = (uint32_t)(noise->seed >> 32);
-        ea.thresh = (uint64_t)floor((double)noise->p0 * 4294967296.0);      // (the gather's T)
-    }
-    const bool vec = (b->io % 4 == 0) && (dy_ld % 4 == 0) && a16(b->data) && a16(y) && a16(dy) &&
-                     (!emph->col_weight || a16(emph->col_weight)) && (!masked || (reinterpret_cast<uintptr_t>(b->mask_table) & 3) == 0);
-    const int grid = mse_loss_colsum_rows(b->B);
-#define ELP(V, O, P) hipLaunchKernelGGL((emph_loss_kernel<V, O, P>), dim3(grid), dim3(NT), 0, s, b->data, b->row_idx, b->mask_id, \
-                                    b->mask_table, b->B, b->io, y, dy, inv_n, colsum_part, parts, b->mask_to_use, b->nb_run, b->run, \
-                                    dy_ld, ea, pa)
-#define EL(V, O) do { if (present) ELP(V, O, true); else ELP(V, O, false); } while (0)
-    if (vec && dy_bf16) EL(true, true);
-    else if (vec) EL(true, false);
-    else if (dy_bf16) EL(false, true);
-    else EL(false, false);
-#undef EL
-#undef ELP
+    const codae_batch* b = ll.batch;
+    const int64_t dy_ld = loss_dy_ld(ll);
+    const WeightArgs wa = weight_args(ll, true);
+    const bool vec = (b->io % 4 == 0) && (dy_ld % 4 == 0) && loss_inputs_a16(ll) && a16(ll.dy) && (!wa.col_weight || a16(wa.col_weight));
+    const dim3 grid(mse_loss_colsum_rows(b->B));
+    loss_dispatch(vec, ll.dy_bf16, ll.present != nullptr, [&](auto V, auto O, auto P) {
+        hipLaunchKernelGGL((emph_loss_kernel<decltype(V)::value, decltype(O)::value, decltype(P)::value>), grid, dim3(NT), 0, s, b->data,
+                           b->row_idx, b->mask_id, b->mask_table, b->B, b->io, ll.y, ll.dy, ll.scale, ll.colsum_part, ll.parts, b->mask_to_use, b->nb_run,
+                           b->run, dy_ld, wa, pres_args(ll));
+    });
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;
 }

@@ -96,21 +96,28 @@ struct codae_engine {
     int64_t loss_part_off = 0;       // (floats, 8-byte aligned) per-workgroup metric sums of the loss kernels
     int loss_part_cap = 0;
     bool chain_ok = false;           // narrow bf16 stack: codae_train_step may take the persistent fused chain
-    codae_noise noise{};             // input noise of the training steps (codae_set_input_noise); kind NONE = off
-    codae_emphasis emph{};           // loss emphasis of the training steps (codae_set_loss_emphasis), meaningful while emph_on
-    bool emph_on = false;
-    codae_recon_loss recon{};        // training criterion (codae_set_recon_loss), meaningful while recon_on: a kind other than MSE
-    bool recon_on = false;
-    codae_slot_contrast contrast{};  // slot contrast on top of the criterion (codae_set_slot_contrast); all zero = off
-    bool contrast_on = false;
-    // per-row slot presence (codae_set_slot_presence): table null = off.  Built field by field: the graph key compares bytes.
-    struct PresCfg { const uint8_t* table; int64_t n_rows; int32_t n_slots; int32_t reserved; } pres{};
-    codae_optimizer opt{};           // optimizer and schedule of the update (codae_set_optimizer), canonical form; all zero = the default
+    // Every setting of the training steps, in the canonical form its setter builds field by field from zero: the graph key
+    // compares the whole block byte by byte (padding included: zeroed at codae_create), so a setting added here reaches the key.
+    struct PresCfg { const uint8_t* table; int64_t n_rows; int32_t n_slots; int32_t reserved; };
+    struct DropCfg { float p[64]; uint64_t seed; int32_t on; int32_t reserved; };
+    struct TrainCfg {
+        codae_noise noise;               // input noise (codae_set_input_noise); kind NONE = off
+        codae_emphasis emph;             // loss emphasis (codae_set_loss_emphasis), meaningful while emph_on
+        int32_t emph_on, reserved;       // (stored: {alpha 0, beta 0} is a legal "on")
+        codae_recon_loss recon;          // training criterion (codae_set_recon_loss); kind MSE (all zero) = off
+        codae_slot_contrast contrast;    // slot contrast on top of the criterion (codae_set_slot_contrast); weight 0 (all zero) = off
+        PresCfg pres;                    // per-row slot presence (codae_set_slot_presence): table null = off
+        DropCfg drop;                    // hidden dropout (codae_set_hidden_dropout): p[l] of layer l's output, all zero = off
+        codae_optimizer opt;             // optimizer and schedule of the update (codae_set_optimizer); all zero = the default
+    } tc;
+    bool recon_on() const { return tc.recon.kind != CODAE_LOSS_MSE; }
+    bool contrast_on() const { return tc.contrast.weight != 0.f; }
+    // the loss is the plain MSE of every slot: what the chain kernel and the last forward GEMM's epilogue compute
+    bool plain_mse() const { return !tc.emph_on && !recon_on() && !contrast_on() && tc.pres.table == nullptr; }
     int graph_captures = 0;          // captures of codae_train_step_graph since codae_create
-    // hidden dropout of the training steps (codae_set_hidden_dropout): p[l] of layer l's output, all zero = off.  The backward entry
-    // points take no batch, so a training forward leaves what they need behind: drop_live = the activations in the workspace were
-    // dropped (an evaluation or drop-in forward clears it), with the batch rows, row indices and step of that forward
-    struct DropCfg { float p[64]; uint64_t seed; int32_t on; int32_t reserved; } drop{};
+    // hidden dropout: the backward entry points take no batch, so a training forward leaves what they need behind: drop_live = the
+    // activations in the workspace were dropped (an evaluation or drop-in forward clears it), with the batch rows, row indices and
+    // step of that forward
     bool drop_live = false;
     int drop_B = 0;
     const int32_t* drop_rows = nullptr;
@@ -134,7 +141,7 @@ struct codae_engine {
     // codae_train_step_graph: the captured step and what it was captured for
     hipGraphExec_t graph_exec = nullptr;
     bool capturing = false;          // inside stream capture: device-side Adam step, everything joined at the end
-    struct GraphKey { codae_batch batch; codae_hyper hyper; codae_buffers bufs; codae_noise noise; codae_emphasis emph; bool emph_on; DropCfg drop; codae_recon_loss recon; codae_slot_contrast contrast; codae_optimizer opt; PresCfg pres; } graph_key{};
+    struct GraphKey { codae_batch batch; codae_hyper hyper; codae_buffers bufs; TrainCfg tc; } graph_key{};
     std::vector<hipEvent_t> prof_start, prof_stop;
     std::vector<int> prof_kind;
     std::vector<int> prof_count;    // launches covered by the record (a GroupScope spans several)
@@ -359,7 +366,8 @@ constexpr int CHAIN_MAX_ROWS = 2048;
 bool chain_eligible(codae_engine* e, const codae_buffers* b, int B) {
     // (the chain kernel fuses the plain gather and the unweighted loss and keeps the activations to itself: a noised input, an
     //  emphasised loss, another criterion, hidden dropout or a slot-presence table takes the per-layer launches)
-    return e->chain_ok && e->noise.kind == CODAE_NOISE_NONE && !e->emph_on && !e->recon_on && !e->contrast_on && !e->drop.on && e->pres.table == nullptr && b->shadow_wt != nullptr && e->rows_for(B) <= CHAIN_MAX_ROWS;
+    return e->chain_ok && e->plain_mse() && e->tc.noise.kind == CODAE_NOISE_NONE && !e->tc.drop.on && b->shadow_wt != nullptr &&
+           e->rows_for(B) <= CHAIN_MAX_ROWS;
 }
 
 // gather + forward chain + loss (+ data-gradient chain) of a narrow stack: one launch; then the loss finish
@@ -629,15 +637,16 @@ int run_dgrad_gemm(codae_engine* e, const codae_buffers* b, int l, int rows, boo
 }
 
 // step of the dropout counter: the forward's, or under graph capture the device scalar the replay refreshes
-inline const double* drop_step_dev(codae_engine* e, const codae_buffers* b) { return e->capturing ? b->scalars + CODAE_S_ADAM_STEP : nullptr; }
-inline bool drops_layer(codae_engine* e, int l) { return e->drop_live && e->drop.on && l >= 0 && l + 1 < e->L && e->drop.p[l] > 0.f; }
+// the step count as the kernels of a captured step read it: from the device scalar (kernel arguments are frozen at capture)
+inline const double* step_dev(codae_engine* e, const codae_buffers* b) { return e->capturing ? b->scalars + CODAE_S_ADAM_STEP : nullptr; }
+inline bool drops_layer(codae_engine* e, int l) { return e->drop_live && e->tc.drop.on && l >= 0 && l + 1 < e->L && e->tc.drop.p[l] > 0.f; }
 
 // act[l + 1] <- act[l + 1] * f behind the forward GEMM of a dropped layer l (its 1-bit ReLU masks stay "pre-dropout y > 0": the
 // backward multiplies by f after the mask)
 int run_dropout_fwd(codae_engine* e, const codae_buffers* b, int l, hipStream_t s) {
     ProfScope prof(e, CODAE_K_DROPOUT, s);
     return launch_dropout_fwd(act_ptr(e, b, l + 1), e->prec == CODAE_PREC_BF16, e->in_ld[l + 1], e->drop_B, e->out[l], e->drop_rows, l,
-                              e->drop_step, drop_step_dev(e, b), e->drop.p[l], e->drop.seed, s);
+                              e->drop_step, step_dev(e, b), e->tc.drop.p[l], e->tc.drop.seed, s);
 }
 
 // the data gradient of layer l and, when layer l - 1 was dropped in the forward, dA_{l-1} <- dA_{l-1} * f right behind it on the same
@@ -649,7 +658,7 @@ int run_dgrad(codae_engine* e, const codae_buffers* b, int l, int rows, bool cos
     {
         ProfScope prof(e, CODAE_K_DROPOUT, s);
         rc = launch_dropout_bwd(dact_ptr(e, b, l - 1), e->prec == CODAE_PREC_BF16, e->prec == CODAE_PREC_BF16 ? e->out_ld[l - 1] : e->out[l - 1],
-                                e->drop_B, e->out[l - 1], e->drop_rows, l - 1, e->drop_step, drop_step_dev(e, b), e->drop.p[l - 1], e->drop.seed,
+                                e->drop_B, e->out[l - 1], e->drop_rows, l - 1, e->drop_step, step_dev(e, b), e->tc.drop.p[l - 1], e->tc.drop.seed,
                                 part_ptr(e, b, l - 1), s);
     }
     if (rc) return rc;
@@ -725,7 +734,7 @@ int backward_range(codae_handle h, const codae_buffers* b, int B, int lo, int hi
                    hipStream_t s, bool join = true, const LossFinish* loss = nullptr) {
     const int rows = h->rows_for(B);
     const bool dual = !h->cfg.single_stream;
-    CODAE_REQUIRE(!(step_mode && h->drop_live && h->drop.on) || B == h->drop_B, "backward of %d rows after a dropped forward of %d", B, h->drop_B);
+    CODAE_REQUIRE(!(step_mode && h->drop_live && h->tc.drop.on) || B == h->drop_B, "backward of %d rows after a dropped forward of %d", B, h->drop_B);
     if (dual) {
         int rc = ensure_side_stream(h);
         if (rc) return rc;
@@ -863,6 +872,7 @@ int codae_create(const codae_spec* spec, codae_handle* out) {
     env_reload();                 // the one place (besides library load / codae_reload_env) the CODAE_* variables are read
     codae_engine* e = new codae_engine();
     e->cfg = env();
+    memset(&e->tc, 0, sizeof(e->tc));       // (padding included: the graph key compares bytes)
     e->L = spec->n_layers;
     e->prec = spec->precision;
     e->max_batch = spec->max_batch;
@@ -1109,32 +1119,61 @@ int codae_backward(codae_handle h, const codae_buffers* b, const float* dy, floa
 // The slot contrast behind the criterion's kernel and its finish (a no-op while it is off): prepare this step's candidates, add the
 // term's gradient to the dY the criterion left - its partial column-sum rows replace the criterion kernel's -, then add the term
 // to CODAE_S_LAST_LOSS.  The per-block sums reuse the criterion's rows, which its finish has read by then (same stream).
-static int run_slot_contrast(codae_handle h, const codae_buffers* b, const codae_batch* batch, const codae_hyper* hyper, const float* y,
-                             hipStream_t s) {
-    if (!h->contrast_on) return CODAE_OK;
-    const int L = h->L, B = batch->B;
-    const bool bf = h->prec == CODAE_PREC_BF16;
-    const double* step_dev = h->capturing ? b->scalars + CODAE_S_ADAM_STEP : nullptr;
+static int run_slot_contrast(codae_handle h, const codae_buffers* b, const codae_hyper* hyper, LossLaunch ll, hipStream_t s) {
+    if (!h->contrast_on()) return CODAE_OK;
+    const int B = ll.batch->B;
     const int blocks = slot_contrast_blocks(B);
     CODAE_REQUIRE(blocks <= h->loss_part_cap && blocks <= (h->max_rows + 31) / 32,
                   "slot contrast: %d row blocks exceed the partial-sum rows (%d)", blocks, h->loss_part_cap);
     const double rows = hyper->loss_scale_rows > 0.f ? (double)hyper->loss_scale_rows : (double)B;
-    const double scale = (double)h->contrast.weight / (rows * (double)h->contrast.n_slots);
+    const double scale = (double)h->tc.contrast.weight / (rows * (double)h->tc.contrast.n_slots);
+    ll.emph = h->tc.emph_on ? &h->tc.emph : nullptr;
+    ll.scale = (float)scale;
     int rc;
     {
         ProfScope prof(h, CODAE_K_LOSS, s);
-        rc = launch_slot_contrast_prepare(batch->data, batch->io, &h->contrast, hyper->step, step_dev, bf, s, h->pres.table, h->pres.n_slots);
+        rc = launch_slot_contrast_prepare(ll.batch->data, ll.batch->io, &h->tc.contrast, ll.step, ll.step_dev, ll.dy_bf16, s, ll.present, ll.n_slots);
     }
     if (rc) return rc;
     {
         ProfScope prof(h, CODAE_K_LOSS, s);
-        rc = launch_slot_contrast(batch, &h->noise, hyper->step, step_dev, h->emph_on ? &h->emph : nullptr, &h->contrast, y,
-                                  dact_ptr(h, b, L - 1), bf, h->out_ld[L - 1], (float)scale, part_ptr(h, b, L - 1), loss_parts_ptr(h, b), s,
-                                  h->pres.table, h->pres.n_slots);
+        rc = launch_slot_contrast(ll, &h->tc.contrast, s);
+    }
+    if (rc) return rc;
+    h->parts_pending[h->L - 1] = blocks;
+    return launch_slot_contrast_finish(b->scalars, scale, ll.parts, blocks, s);
+}
+
+// The training step's stand-alone loss behind the last forward GEMM: dY, the last bias gradient's partial rows and the per-block
+// sums from y, the finish that goes with the kernel, then the slot contrast.  A criterion other than the MSE first (with or without
+// emphasis: its kernels form the weight themselves), then the emphasised MSE (a presence table without emphasis: the same kernel
+// with unit weights), then the plain MSE.
+static int run_standalone_loss(codae_handle h, const codae_buffers* b, const codae_batch* batch, const codae_hyper* hyper, const float* y,
+                               hipStream_t s) {
+    const int L = h->L, blocks = mse_loss_colsum_rows(batch->B);
+    const double inv_n = loss_inv_n(hyper, batch);
+    codae_emphasis unit{};
+    unit.alpha = 1.f; unit.beta = 1.f;
+    LossLaunch ll{batch, &h->tc.noise, hyper->step, step_dev(h, b), h->tc.emph_on ? &h->tc.emph : nullptr, h->tc.pres.table, h->tc.pres.n_slots,
+                  y, dact_ptr(h, b, L - 1), h->prec == CODAE_PREC_BF16, h->out_ld[L - 1], (float)inv_n, part_ptr(h, b, L - 1), loss_parts_ptr(h, b)};
+    const bool weighted = h->recon_on() || h->tc.emph_on || ll.present != nullptr;      // (the kernels that leave three sums per block)
+    int rc;
+    {
+        ProfScope prof(h, CODAE_K_LOSS, s);
+        if (h->recon_on()) {
+            rc = launch_recon_loss(ll, &h->tc.recon, s);
+        } else if (weighted) {
+            if (!h->tc.emph_on) ll.emph = &unit;
+            rc = launch_emph_loss(ll, s);
+        } else {
+            rc = launch_mse_loss(ll, 1, s);
+        }
     }
     if (rc) return rc;
     h->parts_pending[L - 1] = blocks;
-    return launch_slot_contrast_finish(b->scalars, scale, loss_parts_ptr(h, b), blocks, s);
+    h->norm_scalars_zero = true;
+    rc = weighted ? launch_finish_emph_loss(b->scalars, inv_n, s, ll.parts, blocks) : finish_loss(h, b, batch, blocks, s);
+    return rc ? rc : run_slot_contrast(h, b, hyper, ll, s);
 }
 
 // fold != null (codae_train_step): when the loss is fused into the last forward GEMM, its finish - 5 us of a one-block launch
@@ -1156,21 +1195,20 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
     const int rows = h->rows_for(B);
     const bool bf = h->prec == CODAE_PREC_BF16;
     // hidden dropout: training forwards only; the backward entry points find the rows and the step in the handle
-    h->drop_live = hyper != nullptr && h->drop.on;
+    h->drop_live = hyper != nullptr && h->tc.drop.on;
     if (h->drop_live) { h->drop_B = B; h->drop_rows = batch->row_idx; h->drop_step = hyper->step; }
     // bf16 training step: the loss is folded into the last forward GEMM's epilogue (y never stored)
     // (not with loss emphasis or a criterion other than the MSE: those live in stand-alone kernels, below)
     // (nor with a slot-presence table: the stand-alone kernels carry the predicate, the GEMM epilogue does not)
-    const uint8_t* const pres = h->pres.table;
-    const int pres_slots = h->pres.n_slots;
-    const bool fuse_loss = bf && hyper != nullptr && out_y == nullptr && !h->cfg.no_fused_loss && !h->emph_on && !h->recon_on && !h->contrast_on &&
-                           pres == nullptr;
+    const uint8_t* const pres = h->tc.pres.table;
+    const int pres_slots = h->tc.pres.n_slots;
+    const bool fuse_loss = bf && hyper != nullptr && out_y == nullptr && !h->cfg.no_fused_loss && h->plain_mse();
     const bool fold_finish = fuse_loss && fold != nullptr && !h->cfg.no_folded_loss_finish;
     {
         ProfScope prof(h, CODAE_K_GATHER, s);
         double* zero_norm = fold_finish ? b->scalars : nullptr;
-        if (hyper != nullptr && h->noise.kind != CODAE_NOISE_NONE)      // training input only; the loss below reads the clean row
-            rc = launch_gather_noise(batch, &h->noise, hyper->step, h->capturing ? b->scalars + CODAE_S_ADAM_STEP : nullptr,
+        if (hyper != nullptr && h->tc.noise.kind != CODAE_NOISE_NONE)      // training input only; the loss below reads the clean row
+            rc = launch_gather_noise(batch, &h->tc.noise, hyper->step, step_dev(h, b),
                                      act_ptr(h, b, 0), bf, s, h->in_ld[0], nullptr, zero_norm, pres, pres_slots);
         else
             rc = launch_gather_corrupt(batch, act_ptr(h, b, 0), bf, s, h->in_ld[0], zero_norm, pres, pres_slots);
@@ -1224,48 +1262,11 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
     if (hyper != nullptr) {
         rc = zero_pad_rows(h, dact_ptr(h, b, L - 1), B, rows, h->out_ld[L - 1], s);
         if (rc) return rc;
-        if (h->recon_on) {     // (with or without emphasis: the criterion's kernels form the weight themselves)
-            const double inv_n = loss_inv_n(hyper, batch);
-            {
-                ProfScope prof(h, CODAE_K_LOSS, s);
-                rc = launch_recon_loss(batch, &h->noise, hyper->step, h->capturing ? b->scalars + CODAE_S_ADAM_STEP : nullptr,
-                                       h->emph_on ? &h->emph : nullptr, &h->recon, y, dact_ptr(h, b, L - 1), bf, h->out_ld[L - 1], (float)inv_n,
-                                       part_ptr(h, b, L - 1), loss_parts_ptr(h, b), s, pres, pres_slots);
-            }
-            if (rc) return rc;
-            h->parts_pending[L - 1] = mse_loss_colsum_rows(B);
-            h->norm_scalars_zero = true;
-            rc = launch_finish_emph_loss(b->scalars, inv_n, s, loss_parts_ptr(h, b), mse_loss_colsum_rows(B));
-            return rc ? rc : run_slot_contrast(h, b, batch, hyper, y, s);
-        }
-        if (h->emph_on || pres != nullptr) {       // (a table without emphasis: the same kernel with unit weights)
-            const double inv_n = loss_inv_n(hyper, batch);
-            codae_emphasis unit{};
-            unit.alpha = 1.f; unit.beta = 1.f;
-            {
-                ProfScope prof(h, CODAE_K_LOSS, s);
-                rc = launch_emph_loss(batch, &h->noise, hyper->step, h->capturing ? b->scalars + CODAE_S_ADAM_STEP : nullptr,
-                                      h->emph_on ? &h->emph : &unit, y, dact_ptr(h, b, L - 1), bf, h->out_ld[L - 1], (float)inv_n,
-                                      part_ptr(h, b, L - 1), loss_parts_ptr(h, b), s, pres, pres_slots);
-            }
-            if (rc) return rc;
-            h->parts_pending[L - 1] = mse_loss_colsum_rows(B);
-            h->norm_scalars_zero = true;
-            rc = launch_finish_emph_loss(b->scalars, inv_n, s, loss_parts_ptr(h, b), mse_loss_colsum_rows(B));
-            return rc ? rc : run_slot_contrast(h, b, batch, hyper, y, s);
-        }
-        {
-            ProfScope prof(h, CODAE_K_LOSS, s);
-            rc = launch_mse_loss(batch, y, dact_ptr(h, b, L - 1), bf, (float)loss_inv_n(hyper, batch), part_ptr(h, b, L - 1),
-                                 loss_parts_ptr(h, b), 1, s, h->out_ld[L - 1]);
-        }
-        if (rc) return rc;
-        h->parts_pending[L - 1] = mse_loss_colsum_rows(B);
-        h->norm_scalars_zero = true;
-        rc = finish_loss(h, b, batch, mse_loss_colsum_rows(B), s);
-        return rc ? rc : run_slot_contrast(h, b, batch, hyper, y, s);
+        return run_standalone_loss(h, b, batch, hyper, y, s);
     }
-    rc = launch_mse_loss(batch, y, nullptr, 0, 0.f, nullptr, loss_parts_ptr(h, b), 0, s, 0, pres, pres_slots);
+    // evaluation: the sums alone
+    const LossLaunch sums{batch, nullptr, 0, nullptr, nullptr, pres, pres_slots, y, nullptr, 0, 0, 0.f, nullptr, loss_parts_ptr(h, b)};
+    rc = launch_mse_loss(sums, 0, s);
     if (rc) return rc;
     return finish_loss(h, b, batch, mse_loss_colsum_rows(B), s);
 }
@@ -1284,7 +1285,7 @@ int codae_set_input_noise(codae_handle h, const codae_noise* noise) {
         n.kind = noise->kind; n.p0 = noise->p0; n.seed = noise->seed;
         if (noise->kind == CODAE_NOISE_SALT_PEPPER) { n.p1 = noise->p1; n.p2 = noise->p2; }
     }
-    h->noise = n;
+    h->tc.noise = n;
     return CODAE_OK;
 }
 
@@ -1295,8 +1296,8 @@ int codae_set_loss_emphasis(codae_handle h, const codae_emphasis* emphasis) {
     codae_emphasis e{};                  // (built field by field: the graph key compares bytes, padding included)
     const bool on = emphasis != nullptr && !(emphasis->alpha == 1.f && emphasis->beta == 1.f && emphasis->col_weight == nullptr);
     if (on) { e.alpha = emphasis->alpha; e.beta = emphasis->beta; e.col_weight = emphasis->col_weight; }
-    h->emph = e;
-    h->emph_on = on;
+    h->tc.emph = e;
+    h->tc.emph_on = on;
     return CODAE_OK;
 }
 
@@ -1304,8 +1305,8 @@ int codae_set_recon_loss(codae_handle h, const codae_recon_loss* loss) {
     CODAE_REQUIRE(h != nullptr, "codae_set_recon_loss: null handle");
     int rc = check_recon_loss(loss, h->out[h->L - 1]);
     if (rc) return rc;
-    CODAE_REQUIRE(loss == nullptr || loss->kind != CODAE_LOSS_SLOT_COSINE || h->pres.table == nullptr || loss->n_slots == h->pres.n_slots,
-                  "codae_set_recon_loss: slot_cosine n_slots %d differs from the presence table's %d", loss->n_slots, h->pres.n_slots);
+    CODAE_REQUIRE(loss == nullptr || loss->kind != CODAE_LOSS_SLOT_COSINE || h->tc.pres.table == nullptr || loss->n_slots == h->tc.pres.n_slots,
+                  "codae_set_recon_loss: slot_cosine n_slots %d differs from the presence table's %d", loss->n_slots, h->tc.pres.n_slots);
     codae_recon_loss r{};                // (built field by field: the graph key compares bytes)
     const bool on = loss != nullptr && loss->kind != CODAE_LOSS_MSE;
     if (on) {
@@ -1313,8 +1314,7 @@ int codae_set_recon_loss(codae_handle h, const codae_recon_loss* loss) {
         if (loss->kind == CODAE_LOSS_SMOOTH_L1 || loss->kind == CODAE_LOSS_HUBER) r.param = loss->param;
         if (loss->kind == CODAE_LOSS_SLOT_COSINE) { r.mse_weight = loss->mse_weight; r.n_slots = loss->n_slots; }
     }
-    h->recon = r;
-    h->recon_on = on;
+    h->tc.recon = r;
     return CODAE_OK;
 }
 
@@ -1322,10 +1322,10 @@ int codae_set_slot_contrast(codae_handle h, const codae_slot_contrast* contrast)
     CODAE_REQUIRE(h != nullptr, "codae_set_slot_contrast: null handle");
     int rc = check_slot_contrast(contrast, h->out[h->L - 1], h->prec == CODAE_PREC_BF16);
     if (rc) return rc;
-    CODAE_REQUIRE(contrast == nullptr || contrast->weight == 0.f || h->pres.table == nullptr ||
-                      (contrast->n_slots == h->pres.n_slots && (int64_t)contrast->n_rows <= h->pres.n_rows),
+    CODAE_REQUIRE(contrast == nullptr || contrast->weight == 0.f || h->tc.pres.table == nullptr ||
+                      (contrast->n_slots == h->tc.pres.n_slots && (int64_t)contrast->n_rows <= h->tc.pres.n_rows),
                   "codae_set_slot_contrast: n_slots %d / n_rows %d do not fit the presence table (%d slots, %lld rows)", contrast->n_slots,
-                  contrast->n_rows, h->pres.n_slots, (long long)h->pres.n_rows);
+                  contrast->n_rows, h->tc.pres.n_slots, (long long)h->tc.pres.n_rows);
     codae_slot_contrast c{};             // (built field by field: the graph key compares bytes)
     const bool on = contrast != nullptr && contrast->weight != 0.f;
     if (on) {
@@ -1335,8 +1335,7 @@ int codae_set_slot_contrast(codae_handle h, const codae_slot_contrast* contrast)
         c.seed = contrast->seed; c.n_rows = contrast->n_rows; c.n_pool = contrast->pool ? contrast->n_pool : 0;
         c.ws_bytes = contrast->ws_bytes; c.pool = contrast->pool; c.item_id = contrast->item_id; c.ws = contrast->ws;
     }
-    h->contrast = c;
-    h->contrast_on = on;
+    h->tc.contrast = c;
     return CODAE_OK;
 }
 
@@ -1347,14 +1346,14 @@ int codae_set_slot_presence(codae_handle h, const uint8_t* present, int64_t n_ro
         int rc = check_presence(present, n_slots, h->out[h->L - 1], "codae_set_slot_presence");
         if (rc) return rc;
         CODAE_REQUIRE(n_rows >= 1, "codae_set_slot_presence: n_rows %lld must be >= 1", (long long)n_rows);
-        CODAE_REQUIRE(!(h->recon_on && h->recon.kind == CODAE_LOSS_SLOT_COSINE) || h->recon.n_slots == n_slots,
-                      "codae_set_slot_presence: n_slots %d differs from slot_cosine's %d", n_slots, h->recon.n_slots);
-        CODAE_REQUIRE(!h->contrast_on || (h->contrast.n_slots == n_slots && (int64_t)h->contrast.n_rows <= n_rows),
+        CODAE_REQUIRE(!(h->recon_on() && h->tc.recon.kind == CODAE_LOSS_SLOT_COSINE) || h->tc.recon.n_slots == n_slots,
+                      "codae_set_slot_presence: n_slots %d differs from slot_cosine's %d", n_slots, h->tc.recon.n_slots);
+        CODAE_REQUIRE(!h->contrast_on() || (h->tc.contrast.n_slots == n_slots && (int64_t)h->tc.contrast.n_rows <= n_rows),
                       "codae_set_slot_presence: %d slots / %lld rows do not fit the slot contrast (%d slots, %d rows)", n_slots,
-                      (long long)n_rows, h->contrast.n_slots, h->contrast.n_rows);
+                      (long long)n_rows, h->tc.contrast.n_slots, h->tc.contrast.n_rows);
         p.table = present; p.n_rows = n_rows; p.n_slots = n_slots;
     }
-    h->pres = p;
+    h->tc.pres = p;
     return CODAE_OK;
 }
 
@@ -1362,7 +1361,7 @@ int codae_set_optimizer(codae_handle h, const codae_optimizer* opt) {
     CODAE_REQUIRE(h != nullptr, "codae_set_optimizer: null handle");
     int rc = check_optimizer(opt);
     if (rc) return rc;
-    h->opt = optimizer_canonical(opt);   // (built field by field from zero: the graph key compares bytes, padding included)
+    h->tc.opt = optimizer_canonical(opt);   // (built field by field from zero: the graph key compares bytes, padding included)
     return CODAE_OK;
 }
 
@@ -1393,7 +1392,7 @@ int codae_set_hidden_dropout(codae_handle h, const codae_dropout* d) {
         }
         if (c.on) c.seed = d->seed;
     }
-    h->drop = c;
+    h->tc.drop = c;
     return CODAE_OK;
 }
 
@@ -1453,16 +1452,15 @@ static int update_impl(codae_handle h, const codae_buffers* b, const codae_hyper
     CODAE_REQUIRE(h->prec != CODAE_PREC_BF16 || shadow, "codae_step_update: shadow_w missing");
     // (Measured and dropped: per-layer Adam kernels on the side stream beside the NEXT forward - HBM / L2 contention
     // slowed those GEMMs from 46.8 to 56.9 us each and the step from 1.76 to 1.84 ms.)
-    const double* step_dev = h->capturing ? b->scalars + CODAE_S_ADAM_STEP : nullptr;
     ProfScope prof(h, CODAE_K_ADAM, s);
     if (h->prec == CODAE_PREC_BF16 && b->shadow_wt != nullptr && h->L <= 64 && !h->cfg.flat_adam) {
         // one tiled pass: p, m, v, the bf16 shadow and the transposed shadow of every layer that has a data gradient
         return launch_clip_adam_tiled(b->params, b->grads, b->adam_m, b->adam_v, hyper, b->scalars + CODAE_S_GRAD_SQ, shadow,
                                       reinterpret_cast<bf16_t*>(b->shadow_wt), h->L, h->w_off.data(), h->out.data(), h->in.data(),
-                                      1, h->bias_begin, h->n_param - h->bias_begin, s, step_dev, &h->opt, h->opt.vmax);
+                                      1, h->bias_begin, h->n_param - h->bias_begin, s, step_dev(h, b), &h->tc.opt, h->tc.opt.vmax);
     }
     rc = launch_clip_adam(b->params, b->grads, b->adam_m, b->adam_v, h->n_param, hyper, b->scalars + CODAE_S_GRAD_SQ,
-                          shadow, nullptr, s, step_dev, &h->opt, h->opt.vmax);
+                          shadow, nullptr, s, step_dev(h, b), &h->tc.opt, h->tc.opt.vmax);
     if (rc) return rc;
     return refresh_transposed(h, b, s);
 }
@@ -1496,7 +1494,7 @@ int codae_step_update_span(codae_handle h, const codae_buffers* b, const codae_h
     CODAE_REQUIRE(h->prec != CODAE_PREC_BF16 || shadow, "codae_step_update_span: shadow_w missing");
     ProfScope prof(h, CODAE_K_ADAM, s);
     return launch_clip_adam(b->params + lo, b->grads + lo, b->adam_m + lo, b->adam_v + lo, hi - lo, hyper, nullptr,
-                            shadow ? shadow + lo : nullptr, coef, s, nullptr, &h->opt, h->opt.vmax ? h->opt.vmax + lo : nullptr);
+                            shadow ? shadow + lo : nullptr, coef, s, nullptr, &h->tc.opt, h->tc.opt.vmax ? h->tc.opt.vmax + lo : nullptr);
 }
 
 int codae_sync_transposed(codae_handle h, const codae_buffers* b, void* stream) {
@@ -1566,11 +1564,7 @@ int codae_train_step_graph(codae_handle h, const codae_buffers* b, const codae_b
     hk.step = 0;
     const bool fresh = h->graph_exec == nullptr || !same_bytes(&h->graph_key.batch, batch, sizeof(*batch)) ||
                        !same_bytes(&h->graph_key.hyper, &hk, sizeof(hk)) || !same_bytes(&h->graph_key.bufs, b, sizeof(*b)) ||
-                       !same_bytes(&h->graph_key.noise, &h->noise, sizeof(h->noise)) ||
-                       !same_bytes(&h->graph_key.emph, &h->emph, sizeof(h->emph)) || h->graph_key.emph_on != h->emph_on ||
-                       !same_bytes(&h->graph_key.drop, &h->drop, sizeof(h->drop)) || !same_bytes(&h->graph_key.recon, &h->recon, sizeof(h->recon)) ||
-                       !same_bytes(&h->graph_key.contrast, &h->contrast, sizeof(h->contrast)) ||
-                       !same_bytes(&h->graph_key.opt, &h->opt, sizeof(h->opt)) || !same_bytes(&h->graph_key.pres, &h->pres, sizeof(h->pres));
+                       !same_bytes(&h->graph_key.tc, &h->tc, sizeof(h->tc));
     if (fresh) {
         if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
         int rc = check_common(h, b, batch->B);
@@ -1599,8 +1593,7 @@ int codae_train_step_graph(codae_handle h, const codae_buffers* b, const codae_b
             set_error("codae_train_step_graph: hipGraphInstantiate failed: %s", hipGetErrorString(ei));
             return CODAE_E_HIP;
         }
-        h->graph_key.batch = *batch; h->graph_key.hyper = hk; h->graph_key.bufs = *b; h->graph_key.noise = h->noise; h->graph_key.emph = h->emph; h->graph_key.emph_on = h->emph_on;
-        h->graph_key.drop = h->drop; h->graph_key.recon = h->recon; h->graph_key.contrast = h->contrast; h->graph_key.opt = h->opt; h->graph_key.pres = h->pres;
+        h->graph_key.batch = *batch; h->graph_key.hyper = hk; h->graph_key.bufs = *b; h->graph_key.tc = h->tc;
         ++h->graph_captures;
     }
     int rc = launch_set_scalar(b->scalars + CODAE_S_ADAM_STEP, (double)hyper->step, s);

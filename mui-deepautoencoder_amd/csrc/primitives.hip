@@ -48,6 +48,13 @@ int dgrad_bf16(const char* who, const void* dy, const void* W, const void* src, 
     return launch_bias_finish(jobs, nullptr, s);
 }
 
+// the C entry points' arguments as one stand-alone loss launch (no device step scalar: these run outside any graph)
+LossLaunch loss_launch(const codae_batch* batch, const codae_noise* noise, int32_t step, const codae_emphasis* emphasis, const float* y,
+                       void* dy, int32_t dy_bf16, int64_t dy_ld, float scale, float* colsum_part, double* parts,
+                       const uint8_t* present = nullptr, int32_t n_slots = 0) {
+    return LossLaunch{batch, noise, step, nullptr, emphasis, present, n_slots, y, dy, dy_bf16, dy_ld, scale, colsum_part, parts};
+}
+
 }  // namespace
 
 extern "C" {
@@ -64,7 +71,7 @@ int codae_corrupt_batch(const codae_batch* batch, const codae_noise* noise, int3
 
 int codae_emph_loss(const codae_batch* batch, const codae_noise* noise, int32_t step, const codae_emphasis* emphasis, const float* y,
                     void* dy, int32_t dy_bf16, int64_t dy_ld, float inv_n, float* colsum_part, double* parts, void* stream) {
-    return launch_emph_loss(batch, noise, step, nullptr, emphasis, y, dy, dy_bf16, dy_ld, inv_n, colsum_part, parts, (hipStream_t)stream);
+    return launch_emph_loss(loss_launch(batch, noise, step, emphasis, y, dy, dy_bf16, dy_ld, inv_n, colsum_part, parts), (hipStream_t)stream);
 }
 
 int codae_corrupt_batch_present(const codae_batch* batch, const codae_noise* noise, int32_t step, const int32_t* noise_rows, void* out,
@@ -75,21 +82,22 @@ int codae_corrupt_batch_present(const codae_batch* batch, const codae_noise* noi
 
 int codae_mse_loss_present(const codae_batch* batch, const float* y, void* dy, int32_t dy_bf16, int64_t dy_ld, float inv_n,
                            float* colsum_part, double* parts, const uint8_t* present, int32_t n_slots, void* stream) {
-    return launch_mse_loss(batch, y, dy, dy_bf16, inv_n, colsum_part, parts, dy != nullptr, (hipStream_t)stream, dy_ld, present, n_slots);
+    return launch_mse_loss(loss_launch(batch, nullptr, 0, nullptr, y, dy, dy_bf16, dy_ld, inv_n, colsum_part, parts, present, n_slots), dy != nullptr,
+                           (hipStream_t)stream);
 }
 
 int codae_emph_loss_present(const codae_batch* batch, const codae_noise* noise, int32_t step, const codae_emphasis* emphasis, const float* y,
                             void* dy, int32_t dy_bf16, int64_t dy_ld, float inv_n, float* colsum_part, double* parts,
                             const uint8_t* present, int32_t n_slots, void* stream) {
-    return launch_emph_loss(batch, noise, step, nullptr, emphasis, y, dy, dy_bf16, dy_ld, inv_n, colsum_part, parts, (hipStream_t)stream,
-                            present, n_slots);
+    return launch_emph_loss(loss_launch(batch, noise, step, emphasis, y, dy, dy_bf16, dy_ld, inv_n, colsum_part, parts, present, n_slots),
+                            (hipStream_t)stream);
 }
 
 int codae_recon_loss_fwd_bwd_present(const codae_batch* batch, const codae_noise* noise, int32_t step, const codae_emphasis* emphasis,
                                      const codae_recon_loss* loss, const float* y, void* dy, int32_t dy_bf16, int64_t dy_ld, float inv_n,
                                      float* colsum_part, double* parts, const uint8_t* present, int32_t n_slots, void* stream) {
-    return launch_recon_loss(batch, noise, step, nullptr, emphasis, loss, y, dy, dy_bf16, dy_ld, inv_n, colsum_part, parts, (hipStream_t)stream,
-                             present, n_slots);
+    return launch_recon_loss(loss_launch(batch, noise, step, emphasis, y, dy, dy_bf16, dy_ld, inv_n, colsum_part, parts, present, n_slots), loss,
+                             (hipStream_t)stream);
 }
 
 int codae_slot_contrast_prepare_present(const float* data, int32_t io, const codae_slot_contrast* contrast, int32_t step, int32_t bf16,
@@ -100,8 +108,8 @@ int codae_slot_contrast_prepare_present(const float* data, int32_t io, const cod
 int codae_slot_contrast_fwd_bwd_present(const codae_batch* batch, const codae_noise* noise, int32_t step, const codae_emphasis* emphasis,
                                         const codae_slot_contrast* contrast, const float* y, void* dy, int32_t dy_bf16, int64_t dy_ld,
                                         float scale, float* colsum_part, double* parts, const uint8_t* present, int32_t n_slots, void* stream) {
-    return launch_slot_contrast(batch, noise, step, nullptr, emphasis, contrast, y, dy, dy_bf16, dy_ld, scale, colsum_part, parts,
-                                (hipStream_t)stream, present, n_slots);
+    return launch_slot_contrast(loss_launch(batch, noise, step, emphasis, y, dy, dy_bf16, dy_ld, scale, colsum_part, parts, present, n_slots),
+                                contrast, (hipStream_t)stream);
 }
 
 int codae_emph_loss_blocks(int32_t B) { return B > 0 ? mse_loss_colsum_rows(B) : 0; }
@@ -109,7 +117,7 @@ int codae_emph_loss_blocks(int32_t B) { return B > 0 ? mse_loss_colsum_rows(B) :
 int codae_recon_loss_fwd_bwd(const codae_batch* batch, const codae_noise* noise, int32_t step, const codae_emphasis* emphasis,
                              const codae_recon_loss* loss, const float* y, void* dy, int32_t dy_bf16, int64_t dy_ld, float inv_n,
                              float* colsum_part, double* parts, void* stream) {
-    return launch_recon_loss(batch, noise, step, nullptr, emphasis, loss, y, dy, dy_bf16, dy_ld, inv_n, colsum_part, parts, (hipStream_t)stream);
+    return launch_recon_loss(loss_launch(batch, noise, step, emphasis, y, dy, dy_bf16, dy_ld, inv_n, colsum_part, parts), loss, (hipStream_t)stream);
 }
 
 int codae_recon_loss_blocks(int32_t B) { return B > 0 ? mse_loss_colsum_rows(B) : 0; }
@@ -125,7 +133,7 @@ int codae_slot_contrast_prepare(const float* data, int32_t io, const codae_slot_
 int codae_slot_contrast_fwd_bwd(const codae_batch* batch, const codae_noise* noise, int32_t step, const codae_emphasis* emphasis,
                                 const codae_slot_contrast* contrast, const float* y, void* dy, int32_t dy_bf16, int64_t dy_ld, float scale,
                                 float* colsum_part, double* parts, void* stream) {
-    return launch_slot_contrast(batch, noise, step, nullptr, emphasis, contrast, y, dy, dy_bf16, dy_ld, scale, colsum_part, parts,
+    return launch_slot_contrast(loss_launch(batch, noise, step, emphasis, y, dy, dy_bf16, dy_ld, scale, colsum_part, parts), contrast,
                                 (hipStream_t)stream);
 }
 

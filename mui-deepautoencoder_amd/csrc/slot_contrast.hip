@@ -12,7 +12,7 @@
 
 #include <mutex>
 
-#include "codae_common.h"
+#include "loss_sweep.h"
 
 namespace codae {
 namespace {
@@ -30,38 +30,16 @@ constexpr int NSC = 8;           // per-row scalars in LDS
 // (item ids and dataset rows are >= 0; the pad candidates' -1 is never read under the k < K test.)
 constexpr int32_t ABSENT_ID = INT32_MIN;
 
-__device__ __forceinline__ float opaque(float x) { asm("" : "+v"(x)); return x; }
-
 // keeps the loads of an unrolled loop where they are written: hoisted as a whole, the operand loads of 64 column tiles need more
 // registers than the 256 accumulators leave
 __device__ __forceinline__ void load_fence() { asm volatile("" ::: "memory"); }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 // sum over the 16 lanes that share lane >> 4 (the 16 columns of an accumulator row)
 __device__ __forceinline__ float sum16(float v) {
 #pragma unroll
     for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
-
-struct EmphW {                    // the emphasis weight of an element, formed as recon_loss.hip forms it
-    float alpha, beta;
-    const float* col_weight;
-    int replace;
-    uint64_t thresh;
-    uint32_t key0, key1;
-    uint32_t step;
-    const double* step_dev;
-};
-
-struct BatchArgs {
-    const float* data; const int32_t* row_idx; const int32_t* mask_id; const uint8_t* table; const int32_t* mask_to_use;
-    int nb_run, run, B, io;
-};
 
 struct ContrastArgs {
     int S, K, E, Kpad, Epad;
@@ -91,13 +69,6 @@ template <> __device__ __forceinline__ bf16_t to_op<bf16_t>(float v) { return f3
 // v as the product will see it: rounded to the operand type
 template <typename T> __device__ __forceinline__ float as_operand(float v) {
     if constexpr (sizeof(T) == 2) return bf16_to_f32(f32_to_bf16(v)); else return v;
-}
-
-__device__ __forceinline__ bool hit1(int c, uint32_t row, uint32_t step, const EmphW& a) {
-    const uint4 r = philox4x32_10((uint32_t)(c >> 2), row, step, 0u, a.key0, a.key1);
-    const int k = c & 3;
-    const uint32_t rk = (k & 2) ? ((k & 1) ? r.w : r.z) : ((k & 1) ? r.y : r.x);
-    return (uint64_t)rk < a.thresh;
 }
 
 // ---- prepare ---------------------------------------------------------------------------------------------------------------------
@@ -228,7 +199,7 @@ __device__ __forceinline__ float ex(float v) { return __expf(v); }
 template <typename T, int MAXT, int NH>
 __global__ __launch_bounds__(NT) void slot_contrast_kernel(BatchArgs ba, const float* __restrict__ y, T* __restrict__ dy, int64_t dy_ld,
                                                            float scale, float* __restrict__ colsum_part, double* __restrict__ parts,
-                                                           ContrastArgs ca, EmphW ew) {
+                                                           ContrastArgs ca, WeightArgs ew) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r16 = lane & 15, g = lane >> 4;
@@ -462,9 +433,6 @@ __global__ void slot_contrast_finish_kernel(double* __restrict__ scalars, double
     scalars[CODAE_S_LAST_LOSS] += scale * t;
 }
 
-bool finite_f(float x) { return x == x && fabsf(x) <= 3.402823466e38f; }
-inline bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 struct WsLayout { int Kpad, Epad; int64_t cn_off, ct_off, ids_off, bytes; };
 WsLayout ws_layout(int S, int K, int E, int bf16) {
     WsLayout w;
@@ -496,7 +464,7 @@ int raise_lds() {
 
 template <typename T, int MAXT, int NH>
 int launch_one(int grid, size_t lds, hipStream_t s, const BatchArgs& ba, const float* y, void* dy, int64_t dy_ld, float scale,
-               float* colsum_part, double* parts, const ContrastArgs& ca, const EmphW& ew) {
+               float* colsum_part, double* parts, const ContrastArgs& ca, const WeightArgs& ew) {
     hipLaunchKernelGGL((slot_contrast_kernel<T, MAXT, NH>), dim3(grid), dim3(NT), lds, s, ba, y, reinterpret_cast<T*>(dy), dy_ld, scale,
                        colsum_part, parts, ca, ew);
     CODAE_LAUNCH_CHECK();
@@ -560,36 +528,21 @@ int launch_slot_contrast_prepare(const float* data, int io, const codae_slot_con
     return CODAE_OK;
 }
 
-int launch_slot_contrast(const codae_batch* b, const codae_noise* noise, int32_t step, const double* step_dev, const codae_emphasis* emph,
-                         const codae_slot_contrast* c, const float* y, void* dy, int dy_bf16, int64_t dy_ld, float scale,
-                         float* colsum_part, double* parts, hipStream_t s, const uint8_t* present, int n_slots) {
-    if (dy_ld <= 0) dy_ld = b ? b->io : 0;
-    CODAE_REQUIRE(b && b->data && y && dy && parts && c && b->B > 0 && b->io > 0 && c->weight != 0.f, "slot contrast: bad args");
-    int prc = check_presence(present, n_slots, b->io, "slot contrast");
-    if (prc) return prc;
-    CODAE_REQUIRE(present == nullptr || n_slots == c->n_slots, "slot contrast: n_slots %d differs from the presence table's %d",
-                  c->n_slots, n_slots);
-    CODAE_REQUIRE(dy_ld >= b->io, "slot contrast: dy_ld %lld below io %d", (long long)dy_ld, b->io);
-    CODAE_REQUIRE(finite_f(scale), "slot contrast: scale %g is not finite", (double)scale);
-    int rc = check_slot_contrast(c, b->io, dy_bf16);
+int launch_slot_contrast(const LossLaunch& ll, const codae_slot_contrast* c, hipStream_t s) {
+    CODAE_REQUIRE(c && c->weight != 0.f, "slot contrast: bad args");
+    int rc = check_loss_launch("slot contrast", ll, true);
     if (rc) return rc;
-    rc = check_emphasis(emph);
+    const codae_batch* b = ll.batch;
+    const float* y = ll.y;
+    void* dy = ll.dy;
+    const int dy_bf16 = ll.dy_bf16;
+    const int64_t dy_ld = loss_dy_ld(ll);
+    CODAE_REQUIRE(ll.present == nullptr || ll.n_slots == c->n_slots, "slot contrast: n_slots %d differs from the presence table's %d",
+                  c->n_slots, ll.n_slots);
+    CODAE_REQUIRE(finite_f(ll.scale), "slot contrast: scale %g is not finite", (double)ll.scale);
+    rc = check_slot_contrast(c, b->io, dy_bf16);
     if (rc) return rc;
-    rc = check_noise(noise);
-    if (rc) return rc;
-    const bool masked = b->mask_id || b->mask_to_use;
-    CODAE_REQUIRE(!masked || b->mask_table, "slot contrast: mask ids without mask_table");
-    CODAE_REQUIRE(!b->mask_to_use || b->mask_id || (b->nb_run > 0 && b->run >= 0 && b->run < b->nb_run),
-                  "slot contrast: run %d outside [0, %d)", b->run, b->nb_run);
-    EmphW ew{};
-    ew.alpha = 1.f; ew.beta = 1.f;
-    if (emph != nullptr) { ew.alpha = emph->alpha; ew.beta = emph->beta; ew.col_weight = emph->col_weight; }
-    ew.step = (uint32_t)step; ew.step_dev = step_dev;
-    if (emph != nullptr && noise != nullptr && (noise->kind == CODAE_NOISE_MASKING || noise->kind == CODAE_NOISE_SALT_PEPPER)) {
-        ew.replace = 1;
-        ew.key0 = (uint32_t)(noise->seed & 0xffffffffu); ew.key1 = (uint32_t)(noise->seed >> 32);
-        ew.thresh = (uint64_t)floor((double)noise->p0 * 4294967296.0);
-    }
+    const WeightArgs ew = weight_args(ll, ll.emph != nullptr);
     const int E = b->io / c->n_slots;
     const WsLayout w = ws_layout(c->n_slots, c->n_neg, E, dy_bf16);
     ContrastArgs ca{};
@@ -597,15 +550,15 @@ int launch_slot_contrast(const codae_batch* b, const codae_noise* noise, int32_t
     ca.inv_tau = (float)(1.0 / (double)c->tau); ca.n_rows = c->n_rows; ca.item_id = c->item_id;
     const unsigned char* base = reinterpret_cast<const unsigned char*>(c->ws);
     ca.cn = base + w.cn_off; ca.ct = base + w.ct_off; ca.ids = reinterpret_cast<const int32_t*>(base + w.ids_off);
-    ca.present = present;
-    BatchArgs ba{b->data, b->row_idx, b->mask_id, b->mask_table, b->mask_to_use, b->nb_run, b->run, b->B, b->io};
+    ca.present = ll.present;
+    const BatchArgs ba = batch_args(b);
     const int es = dy_bf16 ? 2 : 4;
     const size_t lds = (size_t)WAVES * WROWS * (w.Epad + 16 / es) * es + (size_t)(WAVES * WROWS * NSC + WAVES * w.Epad + WAVES) * 4;
     rc = raise_lds();
     if (rc) return rc;
     const int grid = slot_contrast_blocks(b->B);
     const int nt = (E + 15) / 16;
-#define SCK(T, M, H) return launch_one<T, M, H>(grid, lds, s, ba, y, dy, dy_ld, scale, colsum_part, parts, ca, ew)
+#define SCK(T, M, H) return launch_one<T, M, H>(grid, lds, s, ba, y, dy, dy_ld, ll.scale, ll.colsum_part, ll.parts, ca, ew)
     if (dy_bf16) { if (nt <= 8) SCK(bf16_t, 8, 1); if (nt <= 32) SCK(bf16_t, 32, 1); SCK(bf16_t, 32, 2); }
     if (nt <= 8) SCK(float, 8, 1);
     if (nt <= 32) SCK(float, 32, 1);
