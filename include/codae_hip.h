@@ -59,6 +59,8 @@ extern "C" {
  *      (still 11) + codae_set_slot_presence, codae_corrupt_batch_present, codae_mse_loss_present, codae_emph_loss_present,
  *      codae_recon_loss_fwd_bwd_present, codae_slot_contrast_prepare_present, codae_slot_contrast_fwd_bwd_present: new entries only, no
  *      layout or enum change, no new kernel class
+ *      (still 11) + codae_tie_pair, codae_set_tied_weights, codae_tie_fold, codae_tie_mirror: new entries only, no layout or enum
+ *      change; the fold is booked under CODAE_K_SUMSQ (it forms the vector the norm is taken of), the mirror under CODAE_K_ADAM
  * The binding must refuse a library whose codae_abi_version() differs and must check its own struct sizes against
  * codae_struct_sizes() at load (mui-deepautoencoder_amd/codae/hip/__init__.py does both). */
 #define CODAE_ABI_VERSION 11
@@ -338,6 +340,29 @@ typedef struct {
     float   gamma;         /* STEP: in (0, 1] */
     float*  vmax;          /* device [n_param] fp32, zero before first use (padding too); required iff amsgrad; borrowed */
 } codae_optimizer;
+
+/* Tied weights (Vincent et al. 2010): the decoder's Linear l' = L-1-l uses the transpose of the encoder's Linear l.  With tying on
+ * (codae_set_tied_weights) the FREE parameters are the weights of the layers l < L/2, the middle layer's weight when L is odd, and
+ * every bias (biases stay untied).  The tie is MATERIALISED: for every pair (l, l') with l < l' the decoder matrix is kept in memory
+ * as W_l' = W_l^T - in the fp32 parameter vector, in the bf16 shadow of l' (bf16 of the transpose), and in the transposed shadow of
+ * l' (the bits of l's plain shadow) - so the forward, the data-gradient chain and the weight-gradient launches run unchanged (the
+ * persistent chain kernel, the grouped weight-gradient launch and graph replay included) and every reader of the parameters sees
+ * a whole decoder.  The backward still leaves a gradient for W_l and one for W_l'.  The tie lives between backward and update:
+ *   1. fold    g[W_l][i][j] <- g[W_l][i][j] + g[W_l'][j][i] (one fp32 add, in that operand order), then g[W_l'] <- +0.  The flat
+ *              gradient vector IS then the gradient of the tied parameter set.  Under data parallel it runs after the reduce.
+ *   2. norm    the flat sum g^2 over that vector (every tied weight once, as clip_grad_norm_ counts a shared nn.Parameter; the bias
+ *              block once); the per-matrix sums of the weight-gradient epilogues and slab reduces are not gathered.
+ *   3. update  the optimizer of "Optimizer and schedule", every kind, on the free parameters only: weight decay acts once per
+ *              tied weight; adam_m, adam_v and vmax of the decoder matrices are never read or written.
+ *   4. mirror  W_l' <- W_l^T in fp32, the bf16 shadow of l' (the rounding of the cast: bf16 of the fp32 value) and the transposed
+ *              shadow of l'.  codae_sync_shadows runs it too: the encoder is the truth, a decoder matrix found in params is overwritten.
+ * Refused with CODAE_E_UNSUPPORTED, the message naming the pair: a stack where in_l != out_l' or out_l != in_l' for some pair; and
+ * codae_step_update_span while tying is on (a tied pair straddles two shards of the sharded update). */
+typedef struct {
+    int64_t enc_off;       /* element offset of the encoder matrix W [rows][cols] in the flat vectors */
+    int64_t dec_off;       /* element offset of the decoder matrix W' [cols][rows] = W^T */
+    int32_t rows, cols;
+} codae_tie_pair;
 
 typedef struct codae_engine* codae_handle;
 
@@ -623,6 +648,13 @@ int codae_set_optimizer(codae_handle h, const codae_optimizer* opt);
  * (those two setters refuse a disagreement with the table the same way: whichever comes second); nothing is launched, the previous
  * setting stays.  Every row index of a batch must be < n_rows.  While a table is set codae_step_path reports 0. */
 int codae_set_slot_presence(codae_handle h, const uint8_t* present, int64_t n_rows, int32_t n_slots);
+/* Tied weights ("Tied weights" above) of every update that follows - codae_step_update, codae_train_step, codae_train_step_graph
+ * and codae_train_step_dp; codae_sync_shadows mirrors the decoder while it is on.  on = 0 switches it off: the engine then runs
+ * exactly what it ran before, bit for bit.  CODAE_E_UNSUPPORTED for a stack that is not mirror-symmetric, naming the first
+ * offending layer pair; nothing changes then.  The setter moves no data: call codae_sync_shadows afterwards, which makes the state
+ * tied (decoder matrices and their shadows overwritten from the encoder's).  The setting is part of the graph key and never
+ * changes which forward or backward path a stack takes: codae_step_path is unaffected. */
+int codae_set_tied_weights(codae_handle h, int32_t on);
 /* how many times codae_train_step_graph has captured (and instantiated) a graph on this handle since codae_create */
 int codae_graph_captures(codae_handle h);
 /* validation body (:245-258): forward + metric sums only */
@@ -754,6 +786,16 @@ int codae_clip_adam(float* params, float* grads, float* adam_m, float* adam_v, i
  * read and written under amsgrad only (opt->vmax is not used here).  t = hyper->step. */
 int codae_optimizer_update(float* p, float* g, float* m, float* v, float* vmax, int64_t n, const codae_hyper* hyper,
                            const codae_optimizer* opt, double* scalars, void* stream);
+
+/* The fold of "Tied weights" on caller-supplied buffers: for every pair, grads[enc_off + i cols + j] += grads[dec_off + j rows + i]
+ * (fp32, that operand order), then the decoder range <- +0.  Nothing outside the paired ranges is touched.  Ranges must not
+ * overlap; any n_pairs >= 1 (64 per launch).  16-byte accesses when every offset, rows and cols are multiples of 4. */
+int codae_tie_fold(float* grads, const codae_tie_pair* pairs, int32_t n_pairs, void* stream);
+/* The mirror of "Tied weights" on caller-supplied buffers: for every pair, params[dec_off + j rows + i] = params[enc_off + i cols + j];
+ * with shadow_w (bf16 [>= the parameter layout], may be NULL) shadow_w[dec_off ..] = bf16 of those values; with shadow_wt (may be
+ * NULL) shadow_wt[dec_off + i cols + j] = bf16(params[enc_off + i cols + j]) - the decoder matrix transposed.  Nothing else is
+ * written.  With a shadow, every offset, rows and cols must be multiples of 8 (what the bf16 engine's layout guarantees). */
+int codae_tie_mirror(float* params, void* shadow_w, void* shadow_wt, const codae_tie_pair* pairs, int32_t n_pairs, void* stream);
 
 /* ---- "next" rows: abalone loss and validation rank metric ---- */
 /* CombinedCriterion(reduction="mean") forward + gradient (codae/tool/metering.py:155-180): per variable v with

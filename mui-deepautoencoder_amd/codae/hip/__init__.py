@@ -95,6 +95,13 @@ class Optimizer(C.Structure):
                 ("vmax", C.c_void_p)]
 
 
+# codae_tie_pair.  Like every struct added since ABI 8 (Noise, Emphasis, ReconLoss, SlotContrast, Optimizer, Dropout) it is not in
+# codae_struct_sizes(), whose seven entries are fixed (tests pin them): four fixed-width fields without padding, 24 bytes, pinned
+# by tests/test_tied_host.py.
+class TiePair(C.Structure):
+    _fields_ = [("enc_off", C.c_int64), ("dec_off", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32)]
+
+
 class Dropout(C.Structure):
     _fields_ = [("p", C.POINTER(C.c_float)), ("n", C.c_int32), ("seed", C.c_uint64)]
 
@@ -134,6 +141,9 @@ PROTOTYPES = {
     "codae_set_optimizer": (C.c_int, [_P, C.POINTER(Optimizer)]),
     "codae_optimizer_update": (C.c_int, [_P, _P, _P, _P, _P, _I64, C.POINTER(Hyper), C.POINTER(Optimizer), _P, _P]),
     "codae_graph_captures": (C.c_int, [_P]),
+    "codae_set_tied_weights": (C.c_int, [_P, _I32]),
+    "codae_tie_fold": (C.c_int, [_P, C.POINTER(TiePair), _I32, _P]),
+    "codae_tie_mirror": (C.c_int, [_P, _P, _P, C.POINTER(TiePair), _I32, _P]),
     "codae_set_slot_presence": (C.c_int, [_P, _P, _I64, _I32]),
     "codae_corrupt_batch_present": (C.c_int, [C.POINTER(Batch), C.POINTER(Noise), _I32, _P, _P, _I32, _I64, _P, _I32, _P]),
     "codae_mse_loss_present": (C.c_int, [C.POINTER(Batch), _P, _P, _I32, _I64, _F, _P, _P, _P, _I32, _P]),

@@ -9,7 +9,7 @@ import torch
 
 from . import (PREC_BF16, PREC_F32, S_COUNT, S_GRAD_SQ, S_GRAD_SQ_SLOTS, S_LAST_LOSS, S_N_SLOTS, S_SQ_FULL, S_SQ_PARTIAL,
                Batch, Buffers, Dropout, Emphasis,
-               HipError, Hyper, Sizes, Spec, check, current_stream, lib, ptr)
+               HipError, Hyper, Sizes, Spec, TiePair, check, current_stream, lib, ptr)
 
 
 def precision_code(precision):
@@ -18,6 +18,37 @@ def precision_code(precision):
     if precision in (PREC_BF16, "bf16", "throughput"):
         return PREC_BF16
     raise ValueError("unknown precision %r (use 'f32' or 'bf16')" % (precision,))
+
+
+def _tie_pair_array(pairs):
+    """pairs: [(enc_off, dec_off, rows, cols)] -> a ctypes array of codae_tie_pair."""
+    arr = (TiePair * max(len(pairs), 1))()
+    for i, (e, d, r, c) in enumerate(pairs):
+        arr[i] = TiePair(int(e), int(d), int(r), int(c))
+    return arr
+
+
+def tie_fold(grads, pairs):
+    """codae_tie_fold on a flat fp32 device tensor, in place: for every (enc_off, dec_off, rows, cols) the decoder range, read as
+    [cols][rows], is added transposed onto the encoder range [rows][cols] and left +0."""
+    if grads.dtype != torch.float32 or not grads.is_cuda or not grads.is_contiguous():
+        raise HipError("tie_fold: grads must be a contiguous fp32 tensor on a HIP device")
+    with torch.cuda.device(grads.device):
+        check(lib().codae_tie_fold(ptr(grads), _tie_pair_array(pairs), len(pairs), current_stream()))
+    return grads
+
+
+def tie_mirror(params, pairs, shadow=None, shadow_t=None):
+    """codae_tie_mirror on a flat fp32 device tensor, in place: every decoder range becomes the transpose of its encoder range;
+    shadow / shadow_t (flat bf16 tensors in the parameter layout, optional) get the decoder's bf16 shadow and transposed shadow."""
+    if params.dtype != torch.float32 or not params.is_cuda or not params.is_contiguous():
+        raise HipError("tie_mirror: params must be a contiguous fp32 tensor on a HIP device")
+    for t in (shadow, shadow_t):
+        if t is not None and (t.dtype != torch.bfloat16 or t.device != params.device or not t.is_contiguous()):
+            raise HipError("tie_mirror: the shadows must be contiguous bf16 tensors on %s" % params.device)
+    with torch.cuda.device(params.device):
+        check(lib().codae_tie_mirror(ptr(params), ptr(shadow), ptr(shadow_t), _tie_pair_array(pairs), len(pairs), current_stream()))
+    return params
 
 
 class DaeEngine:
@@ -92,6 +123,7 @@ class DaeEngine:
         self._contrast_pins = None    # the device tensors codae_slot_contrast borrows (pool, item ids, work space)
         self.slot_presence = None
         self._presence_table = None   # the device tensor codae_set_slot_presence borrows
+        self.tied_weights = False
         self.optimizer = None
         self.adam_vmax = None         # AMSGrad's running maximum (codae_optimizer.vmax borrows it), allocated on first use
         self.step_count = 0
@@ -348,6 +380,26 @@ class DaeEngine:
 
     def _set_optimizer_struct(self, st):
         check(self._lib.codae_set_optimizer(self._h, None if st is None else C.byref(st)))
+
+    def set_tied_weights(self, on):
+        """on: True ties the decoder to the encoder (include/codae_hip.h, "Tied weights"): Linear L-1-l uses the transpose of Linear
+        l < L/2, kept in memory as a mirror.  The free parameters are the encoder matrices, the middle matrix of an odd stack and
+        every bias; every update that follows - train_step (plain and graph=True), step_update, train_step_dp - folds the decoder
+        gradients into the encoder's, takes the norm of the folded vector, updates the free parameters alone and mirrors them
+        back.  Switching it on overwrites the decoder matrices and their shadows from the encoder's, as load_params and
+        sync_shadows do while it is on.  step_path() is unaffected; with graph=True the next step re-captures.  None / False = off:
+        the engine runs exactly what it ran before.  A stack that is not mirror-symmetric is refused (HipError naming the layer
+        pair; the previous setting stays), as is step_update_span while tying is on."""
+        on = bool(on)
+        check(self._lib.codae_set_tied_weights(self._h, 1 if on else 0))
+        self.tied_weights = on
+        if on:
+            self.sync_shadows()
+
+    def tie_pairs(self):
+        """[(enc_off, dec_off, rows, cols)] of the tied layer pairs in this engine's flat layout (whether or not tying is on)."""
+        from ..tool.tied import TiedWeights
+        return TiedWeights.flat_pairs(self.schedule, self.w_off)
 
     def graph_captures(self):
         """How many times train_step(graph=True) has captured a graph on this engine."""

@@ -180,6 +180,9 @@ class DataParallel:
         # True): it has only ever run with one rank on this build's single-GPU test boxes.
         import os as _os
         self.native = bool(native) or _os.environ.get("CODAE_DP_NATIVE") == "1"
+        # tied weights: the fold runs inside the engine's update, behind every reduce of the non-sharded paths (torch.distributed,
+        # bucketed, native); a shard of the sharded update would hold one half of a tied pair
+        self._refuse_sharded_tie()
         if self.native:
             if self.sharded:
                 raise ValueError("native RCCL data parallel: the sharded update goes through torch.distributed only")
@@ -200,6 +203,12 @@ class DataParallel:
         import os
         self.always_reduce = dist.is_initialized() and os.environ.get("CODAE_DP_FORCE_ALLREDUCE") == "1"
         self._tw_every, self._tw_step, self._tw = 0, 0, []
+
+    def _refuse_sharded_tie(self):
+        eng = self.engine
+        if self.sharded and getattr(eng, "tied_weights", False) and eng.L >= 2:
+            from .tool.tied import TiedWeights
+            raise TiedWeights.sharded_refusal(eng.L)
 
     # ---- exposed-wait timing (bench.py --gpus N) ------------------------------------------
     def time_waits(self, every=4):
@@ -287,6 +296,7 @@ class DataParallel:
         if self.native:
             self.engine.train_step_dp(batch, hyper, self.buckets)
             return
+        self._refuse_sharded_tie()             # (tying switched on after this object was built)
         self.engine.step_forward_loss(batch, hyper)
         if self.sharded and (self.world > 1 or self.always_reduce):
             self._backward_reduce_scatter(B)
@@ -394,7 +404,8 @@ class HipEmbeddingTrainer:
     def __init__(self, schedule, data, mask_table_u8, mask_to_use_i32, lr, weight_decay, clip=1.0,
                  max_batch=8192, precision="bf16", device="cuda:0", distributed=False, n_buckets=None, use_graph=False,
                  sharded_update=False, native_dp=False, activation=None, n_slots=None, input_noise=None,
-                 loss_emphasis=None, hidden_dropout=None, criterion=None, contrast=None, optimizer=None, presence=None):
+                 loss_emphasis=None, hidden_dropout=None, criterion=None, contrast=None, optimizer=None, presence=None,
+                 tied_weights=None):
         """use_graph: replay the fused step from a hipGraph (codae_train_step_graph): for launch-bound shapes
         (small batches); single process only - the bucketed data-parallel step is not captured.
         activation: what follows every hidden Linear, as the model classes take it (a factory called as activation(True),
@@ -426,7 +437,11 @@ class HipEmbeddingTrainer:
         presence: a codae.tool.SlotPresence over the rows of `data`: rows that lack an item in some slots train, evaluate and
         complete - an absent slot is 0 in the input, has no term in the loss, the monitors or the contrast, and is never a
         candidate of complete(); what `data` holds there is never used.  Every step form and eval_batch.  None (or a table
-        without an absent slot) = off, exactly as before."""
+        without an absent slot) = off, exactly as before.
+        tied_weights: True ties the decoder to the encoder (include/codae_hip.h, "Tied weights"): Linear L-1-l uses the transpose of
+        Linear l, the free parameters are the encoder matrices, the middle one of an odd stack and every bias, in every step form
+        but the sharded update (refused, as is a stack that is not mirror-symmetric: HipError naming the layer pair).  params(),
+        eval_batch and complete see whole decoder matrices, kept as mirrors.  None / False = off, exactly as before."""
         from .hip.engine import DaeEngine
         fit_host_threads()      # the loop that feeds this trainer must not get its container CPU-throttled (codae/hostcpu.py)
         self.device = torch.device(device)
@@ -451,6 +466,8 @@ class HipEmbeddingTrainer:
         self.presence = None
         if presence is not None:
             self.set_presence(presence)
+        if tied_weights:
+            self.set_tied_weights(True)
         self.dp = DataParallel(self.engine, n_buckets=n_buckets, sharded=sharded_update, native=native_dp) if distributed else None
         self.world = self.dp.world if self.dp else 1
         self.use_graph = bool(use_graph) and self.dp is None
@@ -499,6 +516,15 @@ class HipEmbeddingTrainer:
         self.presence = None if presence is None or presence.is_default else presence
         self.__dict__.pop("_retrievers", None)
 
+    def set_tied_weights(self, on):
+        """DaeEngine.set_tied_weights: True ties the decoder to the encoder (the decoder matrices become mirrors at once), None /
+        False unties it (the matrices stay as they are and train freely from there)."""
+        dp = self.__dict__.get("dp")
+        if on and dp is not None and dp.sharded and self.engine.L >= 2:
+            from .tool.tied import TiedWeights
+            raise TiedWeights.sharded_refusal(self.engine.L)
+        self.engine.set_tied_weights(bool(on))
+
     def set_optimizer(self, optimizer):
         """DaeEngine.set_optimizer: a codae.tool.Optimizer, or None for Adam at a constant rate."""
         self.engine.set_optimizer(optimizer)
@@ -524,7 +550,8 @@ class HipEmbeddingTrainer:
             self.engine.sync_shadows()
 
     def init_params(self, seed=0):
-        """Xavier-uniform weights / zero bias (embedding_...py:188-211), same on every rank."""
+        """Xavier-uniform weights / zero bias (embedding_...py:188-211), same on every rank.  Tied weights: the free tensors and
+        the biases have the bits of the untied init for that seed; the decoder matrices are mirrors (load_params)."""
         g = torch.Generator(device="cpu")
         g.manual_seed(seed)
         ps = []

@@ -523,6 +523,10 @@ int launch_clip_adam_tiled(float* p, float* g, float* m, float* v, const codae_h
                            const int* cols, int transposed_from, int64_t bias_off, int64_t bias_n, hipStream_t s,
                            const double* step_dev = nullptr, const codae_optimizer* opt = nullptr, float* vmax = nullptr);
 // dst[c][r] = src[r][c] for n bf16 matrices (element offsets off[i], shapes rows[i] x cols[i]) in one launch
+// tied weights (tied.hip; include/codae_hip.h, "Tied weights"): the fold of the decoder gradients into the encoder's, and the mirror of
+// the encoder matrices into the decoder's fp32 image and (when given) its two bf16 shadows
+int launch_tie_fold(float* g, const codae_tie_pair* pairs, int n, hipStream_t s);
+int launch_tie_mirror(float* p, bf16_t* shadow, bf16_t* shadow_t, const codae_tie_pair* pairs, int n, hipStream_t s);
 int launch_transpose_bf16(const bf16_t* src, bf16_t* dst, int n, const int64_t* off, const int* rows, const int* cols,
                           hipStream_t s);
 int gemm_bf16_timeline(unsigned long long* host_out, int n_wg);   // CODAE_GEMM_DBG=8 stamps

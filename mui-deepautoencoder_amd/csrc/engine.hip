@@ -109,9 +109,13 @@ struct codae_engine {
         PresCfg pres;                    // per-row slot presence (codae_set_slot_presence): table null = off
         DropCfg drop;                    // hidden dropout (codae_set_hidden_dropout): p[l] of layer l's output, all zero = off
         codae_optimizer opt;             // optimizer and schedule of the update (codae_set_optimizer); all zero = the default
+        int32_t tied, tied_reserved;     // tied encoder / decoder weights (codae_set_tied_weights); 0 = off
     } tc;
     bool recon_on() const { return tc.recon.kind != CODAE_LOSS_MSE; }
     bool contrast_on() const { return tc.contrast.weight != 0.f; }
+    // tied weights: the layers [0, n_free()) own their matrices, layer L-1-l mirrors layer l < L / 2 (tie_pairs: those pairs)
+    int n_free() const { return (L + 1) / 2; }
+    std::vector<codae_tie_pair> tie_pairs;
     // the loss is the plain MSE of every slot: what the chain kernel and the last forward GEMM's epilogue compute
     bool plain_mse() const { return !tc.emph_on && !recon_on() && !contrast_on() && tc.pres.table == nullptr; }
     int graph_captures = 0;          // captures of codae_train_step_graph since codae_create
@@ -1056,6 +1060,11 @@ int codae_param_offsets(codae_handle h, int32_t layer, int64_t* w_off, int64_t* 
 
 int codae_sync_shadows(codae_handle h, const codae_buffers* b, void* stream) {
     CODAE_REQUIRE(h && b && b->params, "codae_sync_shadows: null argument");
+    if (h->tc.tied && !h->tie_pairs.empty()) {
+        // the encoder is the truth: the decoder's fp32 image first, the cast and the transposes below then see a tied vector
+        int rc = launch_tie_mirror(b->params, nullptr, nullptr, h->tie_pairs.data(), (int)h->tie_pairs.size(), (hipStream_t)stream);
+        if (rc) return rc;
+    }
     if (h->prec != CODAE_PREC_BF16) return CODAE_OK;
     CODAE_REQUIRE(b->shadow_w, "codae_sync_shadows: shadow_w missing");
     int rc = launch_cast_bf16(b->params, reinterpret_cast<bf16_t*>(b->shadow_w), h->n_param, (hipStream_t)stream);
@@ -1365,6 +1374,28 @@ int codae_set_optimizer(codae_handle h, const codae_optimizer* opt) {
     return CODAE_OK;
 }
 
+int codae_set_tied_weights(codae_handle h, int32_t on) {
+    CODAE_REQUIRE(h != nullptr, "codae_set_tied_weights: null handle");
+    if (on) {
+        for (int l = 0; l < h->L / 2; ++l) {
+            const int m = h->L - 1 - l;
+            if (h->in[l] != h->out[m] || h->out[l] != h->in[m]) {
+                set_error("tied weights: layers %d and %d are not mirror images (%d -> %d against %d -> %d)", l, m, h->in[l], h->out[l],
+                          h->in[m], h->out[m]);
+                return CODAE_E_UNSUPPORTED;
+            }
+        }
+        h->tie_pairs.clear();
+        for (int l = 0; l < h->L / 2; ++l) {
+            codae_tie_pair p{};
+            p.enc_off = h->w_off[l]; p.dec_off = h->w_off[h->L - 1 - l]; p.rows = h->out[l]; p.cols = h->in[l];
+            h->tie_pairs.push_back(p);
+        }
+    }
+    h->tc.tied = on ? 1 : 0;             // (tied_reserved stays zero: the graph key compares bytes)
+    return CODAE_OK;
+}
+
 int codae_graph_captures(codae_handle h) { return h != nullptr ? h->graph_captures : 0; }
 
 int codae_set_hidden_dropout(codae_handle h, const codae_dropout* d) {
@@ -1437,6 +1468,15 @@ static int update_impl(codae_handle h, const codae_buffers* b, const codae_hyper
         rc = finish_bias(h, b, s, false);
         if (rc) return rc;
     }
+    // tied weights: the decoder matrices' gradients are folded into the encoder's (behind every reduce of a data-parallel step, which
+    // ends here) and left +0: the flat vector is the gradient of the tied parameter set, and the flat norm below counts it once
+    const bool tied = h->tc.tied != 0 && !h->tie_pairs.empty();
+    CODAE_REQUIRE(!(h->tc.tied && weights_norm_done), "codae_step_update: tied weights take the flat norm pass");
+    if (tied) {
+        ProfScope prof(h, CODAE_K_SUMSQ, s);
+        rc = launch_tie_fold(b->grads, h->tie_pairs.data(), (int)h->tie_pairs.size(), s);
+        if (rc) return rc;
+    }
     const bool scalars_zero = h->norm_scalars_zero;
     h->norm_scalars_zero = false;
     if (hyper->max_grad_norm > 0.f && !weights_norm_done) {    // (else: sum g^2 was accumulated by the slab reduces / the
@@ -1453,6 +1493,30 @@ static int update_impl(codae_handle h, const codae_buffers* b, const codae_hyper
     // (Measured and dropped: per-layer Adam kernels on the side stream beside the NEXT forward - HBM / L2 contention
     // slowed those GEMMs from 46.8 to 56.9 us each and the step from 1.76 to 1.84 ms.)
     ProfScope prof(h, CODAE_K_ADAM, s);
+    if (tied) {
+        // the free parameters only - the encoder matrices (and the middle one of an odd stack) and every bias; the moments of the
+        // decoder matrices are neither read nor written - then the decoder's three images from the updated encoder
+        const int nf = h->n_free();
+        bf16_t* shadow_t = h->prec == CODAE_PREC_BF16 ? reinterpret_cast<bf16_t*>(b->shadow_wt) : nullptr;
+        if (h->prec == CODAE_PREC_BF16 && shadow_t != nullptr && h->L <= 64 && !h->cfg.flat_adam) {
+            rc = launch_clip_adam_tiled(b->params, b->grads, b->adam_m, b->adam_v, hyper, b->scalars + CODAE_S_GRAD_SQ, shadow, shadow_t, nf,
+                                        h->w_off.data(), h->out.data(), h->in.data(), 1, h->bias_begin, h->n_param - h->bias_begin, s,
+                                        step_dev(h, b), &h->tc.opt, h->tc.opt.vmax);
+            if (rc) return rc;
+        } else {
+            const int64_t spans[2][2] = {{0, h->w_off[nf]}, {h->bias_begin, h->n_param}};
+            for (const auto& sp : spans) {
+                const int64_t lo = sp[0], n = sp[1] - sp[0];
+                rc = launch_clip_adam(b->params + lo, b->grads + lo, b->adam_m + lo, b->adam_v + lo, n, hyper, b->scalars + CODAE_S_GRAD_SQ,
+                                      shadow ? shadow + lo : nullptr, nullptr, s, step_dev(h, b), &h->tc.opt,
+                                      h->tc.opt.vmax ? h->tc.opt.vmax + lo : nullptr);
+                if (rc) return rc;
+            }
+            rc = refresh_transposed(h, b, s, 1, nf);
+            if (rc) return rc;
+        }
+        return launch_tie_mirror(b->params, shadow, shadow_t, h->tie_pairs.data(), (int)h->tie_pairs.size(), s);
+    }
     if (h->prec == CODAE_PREC_BF16 && b->shadow_wt != nullptr && h->L <= 64 && !h->cfg.flat_adam) {
         // one tiled pass: p, m, v, the bf16 shadow and the transposed shadow of every layer that has a data gradient
         return launch_clip_adam_tiled(b->params, b->grads, b->adam_m, b->adam_v, hyper, b->scalars + CODAE_S_GRAD_SQ, shadow,
@@ -1480,6 +1544,10 @@ int codae_step_update_span(codae_handle h, const codae_buffers* b, const codae_h
     CODAE_REQUIRE(lo >= 0 && lo < hi && hi <= h->n_param && lo % 4 == 0 && hi % 4 == 0, "codae_step_update_span: range [%lld, %lld)",
                   (long long)lo, (long long)hi);
     CODAE_REQUIRE(hyper->max_grad_norm <= 0.f || total_sq != nullptr, "codae_step_update_span: clipping needs the global sum g^2");
+    if (h->tc.tied && !h->tie_pairs.empty()) {
+        set_error("tied weights: the sharded update is not supported: the tied layers %d and %d lie in different shards", 0, h->L - 1);
+        return CODAE_E_UNSUPPORTED;
+    }
     hipStream_t s = (hipStream_t)stream;
     int rc = join_side(h, s);
     if (rc) return rc;
@@ -1531,7 +1599,8 @@ int codae_train_step(codae_handle h, const codae_buffers* b, const codae_batch* 
         LossFinish lf{};
         rcc = run_chain(h, b, batch, hyper, true, s, &lf);
         if (rcc) return rcc;
-        const bool with_norm = hyper->max_grad_norm > 0.f && !h->cfg.no_fused_norm;     // (finish_loss zeroed the norm slots)
+        // (finish_loss zeroed the norm slots; tied weights: the norm is that of the FOLDED gradients - the flat pass of update_impl)
+        const bool with_norm = hyper->max_grad_norm > 0.f && !h->cfg.no_fused_norm && !h->tc.tied;
         rcc = run_wgrad_grouped(h, b, h->rows_for(batch->B), with_norm, s);
         if (rcc) return rcc;
         rcc = finish_bias(h, b, s, with_norm, &lf);
@@ -1544,7 +1613,8 @@ int codae_train_step(codae_handle h, const codae_buffers* b, const codae_batch* 
     // single GPU: nothing happens to the gradients between backward and update, so the norm can be
     // gathered while the split-K slabs are reduced (finish_loss zeroed GRAD_SQ before the backward)
     // bf16: every weight gradient leaves its sum g^2 behind - split ones in the slab reduce, unsplit ones in the GEMM epilogue
-    const bool all_slabbed = h->prec == CODAE_PREC_BF16 && hyper->max_grad_norm > 0.f && !h->cfg.no_fused_norm;
+    // (not with tied weights: the norm is that of the folded gradients - the flat pass of update_impl)
+    const bool all_slabbed = h->prec == CODAE_PREC_BF16 && hyper->max_grad_norm > 0.f && !h->cfg.no_fused_norm && !h->tc.tied;
     // (codae_step_backward's argument checks - check_common, grads / dacts - were made by codae_step_forward_loss just above)
     rc = backward_range(h, b, batch->B, 0, h->L, nullptr, true, all_slabbed, (hipStream_t)stream, true, lf.scalars != nullptr ? &lf : nullptr);
     if (rc) return rc;

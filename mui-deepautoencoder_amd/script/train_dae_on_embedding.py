@@ -146,13 +146,18 @@ def main():
     epochs = args.epochs if args.epochs is not None else mc["EPOCH"]
     optimizer = optimizer_from_config(config.get("HIP", {}).get("OPTIMIZER"), total_steps=max(1, epochs * 1 * len(train_sampler)))
 
+    # HIP: TIED_WEIGHTS: true (build-only key): the decoder's Linears use the transposed matrices of the encoder's (Vincent et al.
+    # 2010); needs a mirror-symmetric stack (NB_INPUT_LAYER == NB_OUTPUT_LAYER)
+    from codae.tool import TiedWeights
+    tied_weights = TiedWeights.from_config(config.get("HIP", {}).get("TIED_WEIGHTS"))
+
     def build(prec):
         return HipEmbeddingTrainer(enc + dec, dataset.data, corrupter.mask_table_u8, mask_to_use,
                                    mc["LEARNING_RATE"], mc["WEIGHT_DECAY"], clip=1.0 if mc["TRUNK_GRAD"] else 0.0,
                                    max_batch=mc["BATCH_SIZE"], precision=prec, device=device, distributed=world > 1,
                                    activation=activation, input_noise=input_noise, loss_emphasis=loss_emphasis,
                                    hidden_dropout=hidden_dropout, criterion=criterion, contrast=contrast, optimizer=optimizer,
-                                   presence=presence)
+                                   presence=presence, tied_weights=tied_weights)
     try:
         trainer = build(precision)
     except HipError as e:
@@ -165,6 +170,9 @@ def main():
     display_info(config, dataset.nb_observation, {})
     act_label = "+" + (activation(True).__class__.__name__ if activation is not None else "ReLU")
     log.info("Linear stack: " + " | ".join("%d->%d%s" % (k, n, act_label if r else "") for k, n, r in enc + dec))
+    if tied_weights:
+        log.info("TIED WEIGHTS: %d free parameters of %d" % (TiedWeights.free_parameter_count(enc + dec),
+                                                            sum(k * n + n for k, n, _ in enc + dec)))
     book = {k: [] for k in ("ftl", "ptl", "fvl", "pvl", "rl")}
     S = dataset.nb_used_category
     rank_indices, nb_ranked = validation_indices, nb_validation
