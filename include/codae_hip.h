@@ -61,6 +61,8 @@ extern "C" {
  *      layout or enum change, no new kernel class
  *      (still 11) + codae_tie_pair, codae_set_tied_weights, codae_tie_fold, codae_tie_mirror: new entries only, no layout or enum
  *      change; the fold is booked under CODAE_K_SUMSQ (it forms the vector the norm is taken of), the mirror under CODAE_K_ADAM
+ *      (still 11) + codae_set_dataset_image, codae_corrupt_batch_image: new entries only, no layout or enum change; the image gather is
+ *      booked under CODAE_K_GATHER
  * The binding must refuse a library whose codae_abi_version() differs and must check its own struct sizes against
  * codae_struct_sizes() at load (mui-deepautoencoder_amd/codae/hip/__init__.py does both). */
 #define CODAE_ABI_VERSION 11
@@ -648,6 +650,17 @@ int codae_set_optimizer(codae_handle h, const codae_optimizer* opt);
  * (those two setters refuse a disagreement with the table the same way: whichever comes second); nothing is launched, the previous
  * setting stays.  Every row index of a batch must be < n_rows.  While a table is set codae_step_path reports 0. */
 int codae_set_slot_presence(codae_handle h, const uint8_t* present, int64_t n_rows, int32_t n_slots);
+/* A resident bf16 image of the dataset: image_bf16 [n_rows][io] bf16 on the device, image[r][c] = bf16(data[r][c]) as
+ * codae_cast_f32_to_bf16 rounds it, borrowed until replaced; NULL clears the registration.  The bf16 engine's steps - training in
+ * every step form, and codae_eval_step - then gather their input from the image instead of converting the fp32 rows again, whenever
+ * batch->data == data, batch->io == io, io % 8 == 0 and the call applies no input noise (noise is added in fp32 before the
+ * rounding); every other call, and the fp32 engine, runs exactly what it ran before.  The gathered input has the same bits either
+ * way, so no result changes; the loss keeps reading the fp32 target rows.  Every row index of such a batch must be < n_rows.  A
+ * caller that rewrites the dataset in place registers the image again (after casting it again): the engine cannot see the
+ * change.  The registration is part of the graph key.  CODAE_NO_DATASET_IMAGE (read at codae_create) keeps the fp32 gather.
+ * CODAE_E_INVALID for an image without data, n_rows < 1, an io that is not the model's, or an image that is not 16-byte aligned;
+ * the previous registration stays. */
+int codae_set_dataset_image(codae_handle h, const float* data, const void* image_bf16, int64_t n_rows, int32_t io);
 /* Tied weights ("Tied weights" above) of every update that follows - codae_step_update, codae_train_step, codae_train_step_graph
  * and codae_train_step_dp; codae_sync_shadows mirrors the decoder while it is on.  on = 0 switches it off: the engine then runs
  * exactly what it ran before, bit for bit.  CODAE_E_UNSUPPORTED for a stack that is not mirror-symmetric, naming the first
@@ -682,7 +695,9 @@ enum {
  * (bit k = CODAE_K_k), on the stream the launch uses; at most max_records pairs are kept. */
 int codae_profile_begin(codae_handle h, uint32_t class_mask, int32_t max_records);
 /* Stop recording, wait for the recorded events and return per record the class and the elapsed
- * milliseconds.  n_out receives the number of records written (<= capacity). */
+ * milliseconds.  n_out receives the number of records written (<= capacity).  A class of work that rides in the launch recorded
+ * just before it instead of being launched - the bias finish as trailing workgroups of the pipelined grouped weight-gradient launch -
+ * is listed where the host would have issued it, as one record of exactly 0 ms: the carrying launch keeps its whole time. */
 /* Time launches only in every n-th training step (default 1 = every step): an event pair costs 2-4 us of stream time,
  * which matters when the region being timed is also the throughput measurement. */
 int codae_profile_stride(codae_handle h, int32_t every_n_steps);
@@ -936,6 +951,12 @@ int codae_debug_gemm_timeline(uint64_t* host_out, int32_t n_wg);
 #define CODAE_GEMM_PLAN_FIELDS 15
 int codae_debug_gemm_bf16_plan(const int32_t* desc, int32_t* out, int32_t capacity);
 int codae_cast_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream);
+/* The image form of the plain gather on its own (the launcher the engine uses): out[b][:] = mask(image[row_idx[b]][:]) in bf16, rows
+ * out_ld elements apart (<= 0: io), bit for bit what codae_corrupt_batch_present(batch, NULL, ..., out_bf16 = 1) writes when image =
+ * codae_cast_f32_to_bf16(batch->data).  batch->data is not read.  present NULL: no presence table.  CODAE_E_INVALID unless io and
+ * out_ld are multiples of 8, image and out 16-byte and the mask table 8-byte aligned. */
+int codae_corrupt_batch_image(const codae_batch* batch, const void* image_bf16, const uint8_t* present, int32_t n_slots, void* out,
+                              int64_t out_ld, void* stream);
 /* dst[c][r] = src[r][c] on bf16 matrices (rows, cols multiples of 8): the kernel that refreshes codae_buffers.shadow_wt
  * after an EXTERNAL parameter update (codae_sync_shadows); codae_step_update writes it inside its Adam pass
  * (W.t() in torch.nn.Linear's data gradient, embedding_denoising_autoencoder.py:137-151). */

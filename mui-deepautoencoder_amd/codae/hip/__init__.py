@@ -145,6 +145,7 @@ PROTOTYPES = {
     "codae_tie_fold": (C.c_int, [_P, C.POINTER(TiePair), _I32, _P]),
     "codae_tie_mirror": (C.c_int, [_P, _P, _P, C.POINTER(TiePair), _I32, _P]),
     "codae_set_slot_presence": (C.c_int, [_P, _P, _I64, _I32]),
+    "codae_set_dataset_image": (C.c_int, [_P, _P, _P, _I64, _I32]),
     "codae_corrupt_batch_present": (C.c_int, [C.POINTER(Batch), C.POINTER(Noise), _I32, _P, _P, _I32, _I64, _P, _I32, _P]),
     "codae_mse_loss_present": (C.c_int, [C.POINTER(Batch), _P, _P, _I32, _I64, _F, _P, _P, _P, _I32, _P]),
     "codae_emph_loss_present": (C.c_int, [C.POINTER(Batch), C.POINTER(Noise), _I32, C.POINTER(Emphasis), _P, _P, _I32, _I64, _F, _P, _P,
@@ -205,6 +206,7 @@ PROTOTYPES = {
     "codae_linear_act_bf16": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _F, _F, _P]),
     "codae_dgrad_act_bf16": (C.c_int, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _F, _F, _F, _P]),
     "codae_cast_f32_to_bf16": (C.c_int, [_P, _P, _I64, _P]),
+    "codae_corrupt_batch_image": (C.c_int, [C.POINTER(Batch), _P, _P, _I32, _P, _I64, _P]),
     "codae_debug_gemm_timeline": (C.c_int, [_P, _I32]),
     "codae_debug_gemm_bf16_plan": (C.c_int, [_P, _P, _I32]),
     "codae_transpose_bf16": (C.c_int, [_P, _P, _I32, _I32, _P]),

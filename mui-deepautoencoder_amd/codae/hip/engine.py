@@ -124,6 +124,7 @@ class DaeEngine:
         self.slot_presence = None
         self._presence_table = None   # the device tensor codae_set_slot_presence borrows
         self.tied_weights = False
+        self._dataset_image = None    # (data, image): the device tensors codae_set_dataset_image borrows
         self.optimizer = None
         self.adam_vmax = None         # AMSGrad's running maximum (codae_optimizer.vmax borrows it), allocated on first use
         self.step_count = 0
@@ -356,6 +357,25 @@ class DaeEngine:
             return
         check(self._lib.codae_set_slot_presence(self._h, ptr(table), int(table.shape[0]) if n_rows is None else int(n_rows),
                                                 int(table.shape[1]) if n_slots is None else int(n_slots)))
+
+    def set_dataset_image(self, data):
+        """data: the resident fp32 [N, io] dataset the batches are gathered from, or None to clear the registration.  bf16 engine only
+        (the fp32 engine: a no-op that registers nothing): casts `data` to a bf16 image once (codae_cast_f32_to_bf16, half the
+        dataset's bytes) and registers it (include/codae_hip.h, codae_set_dataset_image); every un-noised gather of a batch made
+        from this very tensor then reads the image.  No result changes.  A caller that rewrites `data` in place calls this again.
+        -> the image tensor, or None."""
+        if data is None or self.precision != PREC_BF16:
+            check(self._lib.codae_set_dataset_image(self._h, None, None, 0, 0))
+            self._dataset_image = None
+            return None
+        if data.dtype != torch.float32 or not data.is_contiguous() or data.device != self.device or data.dim() != 2:
+            raise HipError("set_dataset_image: data must be the contiguous fp32 [N, io] dataset on %s" % self.device)
+        with torch.cuda.device(self.device):
+            image = torch.empty(data.shape, dtype=torch.bfloat16, device=self.device)
+            check(self._lib.codae_cast_f32_to_bf16(ptr(data), ptr(image), data.numel(), current_stream()))
+        check(self._lib.codae_set_dataset_image(self._h, ptr(data), ptr(image), int(data.shape[0]), int(data.shape[1])))
+        self._dataset_image = (data, image)
+        return image
 
     def set_optimizer(self, optimizer):
         """optimizer: a codae.tool.Optimizer, or None for the default.  Every update that follows - train_step (plain and graph=True),

@@ -23,6 +23,8 @@ next forward / backward actually read - are all-gathered: 25 % fewer bytes on xG
 4 + 4 bytes per parameter), Adam's 750 MB pass shrinks N-fold, and the fp32 master parameters / moments of a rank stay
 valid for its own shards only until gather_params() is called (checkpoint, read-out).
 """
+import os
+
 import torch
 
 from .hostcpu import fit_host_threads, host_cpu_share  # noqa: F401  (re-exported: scripts and bench.py import them here)
@@ -405,7 +407,7 @@ class HipEmbeddingTrainer:
                  max_batch=8192, precision="bf16", device="cuda:0", distributed=False, n_buckets=None, use_graph=False,
                  sharded_update=False, native_dp=False, activation=None, n_slots=None, input_noise=None,
                  loss_emphasis=None, hidden_dropout=None, criterion=None, contrast=None, optimizer=None, presence=None,
-                 tied_weights=None):
+                 tied_weights=None, dataset_image=True):
         """use_graph: replay the fused step from a hipGraph (codae_train_step_graph): for launch-bound shapes
         (small batches); single process only - the bucketed data-parallel step is not captured.
         activation: what follows every hidden Linear, as the model classes take it (a factory called as activation(True),
@@ -441,7 +443,12 @@ class HipEmbeddingTrainer:
         tied_weights: True ties the decoder to the encoder (include/codae_hip.h, "Tied weights"): Linear L-1-l uses the transpose of
         Linear l, the free parameters are the encoder matrices, the middle one of an odd stack and every bias, in every step form
         but the sharded update (refused, as is a stack that is not mirror-symmetric: HipError naming the layer pair).  params(),
-        eval_batch and complete see whole decoder matrices, kept as mirrors.  None / False = off, exactly as before."""
+        eval_batch and complete see whole decoder matrices, kept as mirrors.  None / False = off, exactly as before.
+        dataset_image: bf16 precision only: keep a bf16 image of `data` beside it (half its bytes again), cast once here, and let
+        every un-noised gather - training in every step form, eval_batch - read it instead of converting the fp32 rows every step
+        (DaeEngine.set_dataset_image); the results are bit for bit the same.  The trainer never writes to `data`; a caller that
+        rewrites self.data in place calls refresh_dataset_image().  False, or CODAE_NO_DATASET_IMAGE in the environment = no
+        image, exactly as before."""
         from .hip.engine import DaeEngine
         fit_host_threads()      # the loop that feeds this trainer must not get its container CPU-throttled (codae/hostcpu.py)
         self.device = torch.device(device)
@@ -449,6 +456,8 @@ class HipEmbeddingTrainer:
         if input_noise is not None:
             self.engine.set_input_noise(input_noise)
         self.data = data.to(device=self.device, dtype=torch.float32).contiguous()
+        self.dataset_image = bool(dataset_image) and not os.environ.get("CODAE_NO_DATASET_IMAGE")
+        self.refresh_dataset_image()
         self.mask_table = None if mask_table_u8 is None else mask_table_u8.to(self.device).contiguous()
         self.mask_to_use = None if mask_to_use_i32 is None else mask_to_use_i32.to(self.device).contiguous()
         self.lr, self.weight_decay, self.clip = lr, weight_decay, clip
@@ -477,6 +486,13 @@ class HipEmbeddingTrainer:
         # (the default stream cannot be captured: graph steps run on a stream of their own, ordered after / before
         # the caller's current stream)
         self._graph_stream = torch.cuda.Stream(device=self.device) if self.use_graph else None
+
+    def refresh_dataset_image(self):
+        """(Re)build and register the bf16 image of self.data - after the dataset was rewritten in place.  Nothing happens when the
+        trainer keeps no image (dataset_image=False, fp32 precision, CODAE_NO_DATASET_IMAGE)."""
+        from .hip import PREC_BF16
+        if self.dataset_image and self.engine.precision == PREC_BF16:
+            self.engine.set_dataset_image(self.data)
 
     def set_loss_emphasis(self, emphasis):
         """DaeEngine.set_loss_emphasis with the trainer's number of slots (n_slots, else read off the mask table) for a

@@ -254,6 +254,8 @@ struct EnvToggles {
          no_prefetch = false,         // CODAE_NO_PREFETCH: no touch of the next launch's weights under the epilogue
          no_defer_wgrad = false;      // CODAE_NO_DEFER_WGRAD: per-layer split-K weight gradients beside the data-gradient chain (round 2's backward)
     bool no_folded_loss_finish = false;      // CODAE_NO_FOLDED_LOSS_FINISH: the fused step's loss finish as a launch of its own
+    bool no_folded_bias_finish = false;      // CODAE_NO_FOLDED_BIAS_FINISH: the bias finish behind the pipelined grouped weight gradients as a launch of its own
+    bool no_dataset_image = false;           // CODAE_NO_DATASET_IMAGE: the gather reads the fp32 rows although a bf16 image is registered
     int store_policy = -1;       // CODAE_STORE_POLICY: plain (0), wt = sc1 write-through (1); -1 = by output size
 };
 const EnvToggles& env();
@@ -398,7 +400,9 @@ struct GemmBf16Group {
     int wg_begin[CODAE_GROUP_MAX + 1];     // prefix sum of workgroups per GEMM (filled by the launcher)
 };
 int gemm_bf16_grouped(GemmBf16Group& grp, hipStream_t s);
-int gemm_bf16_pipe_grouped(GemmBf16Group& grp, hipStream_t s);   // 256 x 192 pipelined tiles, unsplit K (gemm_bf16_pipe.hip)
+// 256 x 192 pipelined tiles, unsplit K (gemm_bf16_pipe.hip); fold != null: the step's bias finish rides in the same launch (BiasFold, below)
+struct BiasFold;
+int gemm_bf16_pipe_grouped(GemmBf16Group& grp, hipStream_t s, const BiasFold* fold = nullptr);
 
 // ---- persistent fused chain for narrow stacks (chain_bf16.hip) ----------------
 constexpr int CODAE_CHAIN_MAX_WIDTH = 512;
@@ -433,6 +437,12 @@ int launch_chain_step(const ChainArgs& a, hipStream_t s);
 // instantiations; null launches exactly what it launched before.
 int launch_gather_corrupt(const codae_batch* b, void* out, int out_bf16, hipStream_t s, int64_t out_ld = 0, double* zero_norm = nullptr,
                           const uint8_t* present = nullptr, int n_slots = 0);
+// The plain gather (bf16 out, no noise) from the dataset's bf16 image instead of its fp32 rows (codae_set_dataset_image): the same
+// bits as launch_gather_corrupt(b, out, 1, ...) on the data the image was cast from.  gather_image_takes: the shape / alignment
+// conditions of its 16-byte accesses (io and out_ld multiples of 8, image and out 16-byte, the mask table 8-byte aligned).
+bool gather_image_takes(const codae_batch* b, const void* image, const void* out, int64_t out_ld);
+int launch_gather_image(const codae_batch* b, const bf16_t* image, bf16_t* out, hipStream_t s, int64_t out_ld = 0, double* zero_norm = nullptr,
+                        const uint8_t* present = nullptr, int n_slots = 0);
 // The same gather with the input noise of `noise` (codae_noise, include/codae_hip.h) in front of the slot mask: the noise-enabled
 // instantiations, beside the plain ones above.  step: the counter's step word; step_dev != null: read it from that device scalar
 // instead (graph replay: kernel arguments are frozen at capture); noise_rows: see codae_corrupt_batch.  check_noise: CODAE_E_INVALID with the offending argument named.
@@ -558,5 +568,20 @@ struct BiasFinishJobs {
 // norm accumulators (the chain kernel zeroed them before the weight gradients started adding to them)
 struct LossFinish { double* scalars; double inv_n; const double* parts; int n_parts; };
 int launch_bias_finish(const BiasFinishJobs& jobs, double* sumsq, hipStream_t s, const LossFinish* loss = nullptr);
+// The same finish as TRAILING workgroups of gemm_bf16_pipe_grouped's launch (the fused bf16 step's deferred weight gradients: 480
+// tiles on 256 CUs at C3, 32 CUs idle through the second round) instead of a launch of its own behind it: what it reads - the
+// partial rows, the loss kernel's sums - was complete before the weight gradients started.  The same bits as launch_bias_finish:
+// every column's rows in row order, one float sum of squares per 256 columns added as a double to slot (that block's index & 63),
+// the loss sums added by 256 threads in the same order.  At most CODAE_GROUP_MAX jobs: the table travels in the kernel-argument
+// block beside the GEMM descriptors (BiasFinishJobs' 64 slots would not fit there).
+struct BiasFold {
+    int n;
+    int rows[CODAE_GROUP_MAX], cols[CODAE_GROUP_MAX];
+    int col_begin[CODAE_GROUP_MAX + 1];      // prefix sum of cols
+    const float* parts[CODAE_GROUP_MAX];
+    float* out[CODAE_GROUP_MAX];
+    double* sumsq;                           // as launch_bias_finish's; null = no norm
+    LossFinish loss;                         // scalars null = no loss finish
+};
 
 }  // namespace codae

@@ -74,6 +74,56 @@ __global__ __launch_bounds__(NT) void gather_corrupt_bf16x8_kernel(const float* 
     }
 }
 
+// 0xffff in the half of a packed bf16 pair whose mask byte (bits 0-7 / 8-15 of m2) is not zero
+__device__ __forceinline__ uint32_t keep_pair(uint32_t m2) {
+    return ((m2 & 0xffu) ? 0x0000ffffu : 0u) | ((m2 & 0xff00u) ? 0xffff0000u : 0u);
+}
+
+// The same rows from the dataset's resident bf16 image (codae_set_dataset_image: image[r][c] = bf16(data[r][c]), rounded as
+// pack_bf16x2 rounds): rounding and then clearing gives the bits of clearing and then rounding, since a cleared element is +0
+// either way.  Per thread 8 columns: the 8 mask bytes first - a group they blank altogether (the corrupted slot: a third of a
+// C3 row) is stored as zeros and never loaded -, else ONE 16-B load, the masked and absent halves cleared by an AND on the
+// packed pairs (a masked NaN or -0 comes out +0, as the select on the fp32 value leaves it), one 16-B store.
+template <bool PRES>
+__global__ __launch_bounds__(NT) void gather_corrupt_image_kernel(const bf16_t* __restrict__ image,
+                                                                  const int32_t* __restrict__ row_idx,
+                                                                  const int32_t* __restrict__ mask_id,
+                                                                  const uint8_t* __restrict__ table, int B, int io,
+                                                                  bf16_t* __restrict__ out,
+                                                                  const int32_t* __restrict__ mask_to_use, int nb_run,
+                                                                  int run, int64_t out_ld, double* zero_norm, PresArgs pa) {
+    zero_norm_scalars(zero_norm);
+    const bool masked = (mask_id != nullptr) || (mask_to_use != nullptr);
+    const int cols = io / 8;
+    const int64_t total = (int64_t)B * cols;
+    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < total; e += (int64_t)gridDim.x * NT) {
+        const int b = (int)(e / cols);
+        const int c = (int)(e - (int64_t)b * cols) * 8;
+        const int64_t src_row = row_idx ? row_idx[b] : b;
+        uint4 keep = make_uint4(~0u, ~0u, ~0u, ~0u);
+        if (masked) {
+            const int id = mask_id ? mask_id[b] : mask_to_use[src_row * nb_run + run];
+            const uint2 m = *reinterpret_cast<const uint2*>(table + (int64_t)id * io + c);
+            keep = make_uint4(keep_pair(m.x), keep_pair(m.x >> 16), keep_pair(m.y), keep_pair(m.y >> 16));
+        }
+        if constexpr (PRES) {
+            int sl[8];
+            slots_of<8>(c, pa.E, sl);
+            const uint32_t pb = present_bits<8>(pa, src_row, sl);
+            keep.x &= ((pb & 1u) ? 0x0000ffffu : 0u) | ((pb & 2u) ? 0xffff0000u : 0u);
+            keep.y &= ((pb & 4u) ? 0x0000ffffu : 0u) | ((pb & 8u) ? 0xffff0000u : 0u);
+            keep.z &= ((pb & 16u) ? 0x0000ffffu : 0u) | ((pb & 32u) ? 0xffff0000u : 0u);
+            keep.w &= ((pb & 64u) ? 0x0000ffffu : 0u) | ((pb & 128u) ? 0xffff0000u : 0u);
+        }
+        uint4 o = make_uint4(0u, 0u, 0u, 0u);
+        if ((keep.x | keep.y | keep.z | keep.w) != 0u) {
+            const uint4 x = *reinterpret_cast<const uint4*>(image + src_row * io + c);
+            o = make_uint4(x.x & keep.x, x.y & keep.y, x.z & keep.z, x.w & keep.w);
+        }
+        *reinterpret_cast<uint4*>(out + (int64_t)b * out_ld + c) = o;
+    }
+}
+
 // ---- a2 + a10: out[b][:] = data[row_idx[b]][:] * mask_table[mask_id[b]][:] -----------------
 // (collate_embedding data_tool.py:96-103 + corrupt embedding_...py:226-239 fused; the [B,io]
 // fp32 mask of Corrupter.get_masks is never materialised.)
@@ -895,6 +945,37 @@ int launch_gather_corrupt(const codae_batch* b, void* out, int out_bf16, hipStre
     else GC(false, false);
 #undef GC
 #undef GCP
+    CODAE_LAUNCH_CHECK();
+    return CODAE_OK;
+}
+
+bool gather_image_takes(const codae_batch* b, const void* image, const void* out, int64_t out_ld) {
+    if (b == nullptr || image == nullptr || out == nullptr || b->io <= 0 || b->io % 8 != 0) return false;
+    if (out_ld <= 0) out_ld = b->io;
+    const bool masked = b->mask_id || b->mask_to_use;
+    return out_ld % 8 == 0 && a16(image) && a16(out) && (!masked || (reinterpret_cast<uintptr_t>(b->mask_table) & 7) == 0);
+}
+
+int launch_gather_image(const codae_batch* b, const bf16_t* image, bf16_t* out, hipStream_t s, int64_t out_ld, double* zero_norm,
+                        const uint8_t* present, int n_slots) {
+    if (out_ld <= 0) out_ld = b ? b->io : 0;
+    CODAE_REQUIRE(b && image && out && b->B > 0 && b->io > 0, "gather_image: bad batch");
+    int prc = check_presence(present, n_slots, b->io, "gather_image");
+    if (prc) return prc;
+    const PresArgs pa{present, n_slots, present ? b->io / n_slots : 0};
+    const bool masked = b->mask_id || b->mask_to_use;
+    CODAE_REQUIRE(!masked || b->mask_table, "gather_image: mask ids without mask_table");
+    CODAE_REQUIRE(!b->mask_to_use || b->mask_id || (b->nb_run > 0 && b->run >= 0 && b->run < b->nb_run),
+                  "gather_image: run %d outside [0, %d)", b->run, b->nb_run);
+    CODAE_REQUIRE(gather_image_takes(b, image, out, out_ld),
+                  "gather_image: io %d and out_ld %lld must be multiples of 8, image and out 16-byte and mask_table 8-byte aligned", b->io,
+                  (long long)out_ld);
+    const int grid = grid_for((int64_t)b->B * (b->io / 8));
+#define GCI(P) hipLaunchKernelGGL((gather_corrupt_image_kernel<P>), dim3(grid), dim3(NT), 0, s, image, b->row_idx, b->mask_id, b->mask_table, \
+                                  b->B, b->io, out, b->mask_to_use, b->nb_run, b->run, out_ld, zero_norm, pa)
+    if (present) GCI(true);
+    else GCI(false);
+#undef GCI
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;
 }

@@ -46,6 +46,8 @@ void env_reload() {
     e.no_prefetch = getenv("CODAE_NO_PREFETCH") != nullptr;
     e.no_relu_bits = getenv("CODAE_NO_RELU_BITS") != nullptr;
     e.no_folded_loss_finish = getenv("CODAE_NO_FOLDED_LOSS_FINISH") != nullptr;
+    e.no_dataset_image = getenv("CODAE_NO_DATASET_IMAGE") != nullptr;
+    e.no_folded_bias_finish = getenv("CODAE_NO_FOLDED_BIAS_FINISH") != nullptr;
     if (const char* k = getenv("CODAE_STORE_POLICY"))
         e.store_policy = !strcmp(k, "plain") ? STORE_PLAIN : (!strcmp(k, "wt") ? STORE_WT : -1);
     if (const char* k = getenv("CODAE_F32_GEMM")) e.f32_gemm = k[0] == 'n' ? 1 : (k[0] == 'x' ? 2 : 0);
@@ -100,6 +102,7 @@ struct codae_engine {
     // compares the whole block byte by byte (padding included: zeroed at codae_create), so a setting added here reaches the key.
     struct PresCfg { const uint8_t* table; int64_t n_rows; int32_t n_slots; int32_t reserved; };
     struct DropCfg { float p[64]; uint64_t seed; int32_t on; int32_t reserved; };
+    struct ImageCfg { const float* data; const void* image; int64_t n_rows; int32_t io; int32_t reserved; };
     struct TrainCfg {
         codae_noise noise;               // input noise (codae_set_input_noise); kind NONE = off
         codae_emphasis emph;             // loss emphasis (codae_set_loss_emphasis), meaningful while emph_on
@@ -110,6 +113,7 @@ struct codae_engine {
         DropCfg drop;                    // hidden dropout (codae_set_hidden_dropout): p[l] of layer l's output, all zero = off
         codae_optimizer opt;             // optimizer and schedule of the update (codae_set_optimizer); all zero = the default
         int32_t tied, tied_reserved;     // tied encoder / decoder weights (codae_set_tied_weights); 0 = off
+        ImageCfg img;                    // bf16 image of the dataset (codae_set_dataset_image): image null = none
     } tc;
     bool recon_on() const { return tc.recon.kind != CODAE_LOSS_MSE; }
     bool contrast_on() const { return tc.contrast.weight != 0.f; }
@@ -148,7 +152,7 @@ struct codae_engine {
     struct GraphKey { codae_batch batch; codae_hyper hyper; codae_buffers bufs; TrainCfg tc; } graph_key{};
     std::vector<hipEvent_t> prof_start, prof_stop;
     std::vector<int> prof_kind;
-    std::vector<int> prof_count;    // launches covered by the record (a GroupScope spans several)
+    std::vector<int> prof_count;    // launches covered by the record (a GroupScope spans several); -1: prof_rides_along, no events
     bool prof_group = false;        // inside a GroupScope of the forward class: no per-launch pairs
     EnvToggles cfg;                         // the CODAE_* toggles as they stood at codae_create
     struct DpState* dp = nullptr;           // data parallel with a library-owned RCCL communicator (codae_dp_init), else null
@@ -262,6 +266,17 @@ struct GroupScope {
     }
     ~GroupScope() { close(); }
 };
+
+// A class of work that has no launch of its own in this step because it rides in the launch recorded just before it (the bias finish
+// inside the grouped weight-gradient launch): one record of that class with 0 ms and no event pair, where the host would have issued
+// the launch - the profile keeps listing every class of the step in issue order, and the carrying launch keeps its whole time.
+void prof_rides_along(codae_engine* e, int kind) {
+    if (e->prof_on && ((e->prof_mask >> kind) & 1u) && (e->prof_step % e->prof_every) == 0 && e->prof_n < (int)e->prof_start.size()) {
+        const int slot = e->prof_n++;
+        e->prof_kind[slot] = kind;
+        e->prof_count[slot] = -1;
+    }
+}
 
 // exact-fp32 weight gradient (128 x 128 tiles, two workgroups per CU): enough K ranges for ~1.5 workgroups per CU - a
 // 1536 x 1536 gradient is 144 tiles, whose 8192-row reductions were the critical path of the whole backward (0.97 ms per
@@ -483,7 +498,32 @@ int run_wgrad_deferred_f32(codae_engine* e, const codae_buffers* b, int rows, hi
     return gemm_f32x3_grouped(grp, s);
 }
 
-int run_wgrad_deferred(codae_engine* e, const codae_buffers* b, int rows, bool with_norm, hipStream_t s) {
+// the pending bias finish (every layer with partial rows; with_norm / loss as finish_bias takes them) as the job table of the grouped
+// weight-gradient launch; false - nothing taken, finish_bias runs as always - when there is nothing pending or more than fits
+bool take_bias_fold(codae_engine* e, const codae_buffers* b, bool with_norm, const LossFinish* loss, BiasFold* f) {
+    int n = 0;
+    for (int l = 0; l < e->L; ++l) n += e->parts_pending[l] > 0 ? 1 : 0;
+    if (n == 0 || n > CODAE_GROUP_MAX) return false;
+    *f = BiasFold{};
+    int cols = 0;
+    for (int l = 0; l < e->L; ++l) {
+        if (e->parts_pending[l] <= 0) continue;
+        f->parts[f->n] = part_ptr(e, b, l);
+        f->out[f->n] = b->grads + e->b_off[l];
+        f->rows[f->n] = e->parts_pending[l];
+        f->cols[f->n] = e->out[l];
+        f->col_begin[f->n] = cols;
+        cols += e->out[l];
+        ++f->n;
+        e->parts_pending[l] = 0;
+    }
+    f->col_begin[f->n] = cols;
+    f->sumsq = with_norm ? b->scalars + CODAE_S_GRAD_SQ : nullptr;
+    if (loss != nullptr) f->loss = *loss;
+    return true;
+}
+
+int run_wgrad_deferred(codae_engine* e, const codae_buffers* b, int rows, bool with_norm, hipStream_t s, const BiasFold* fold = nullptr) {
     GemmBf16Group grp{};
     grp.n = 0;
     for (int l = e->L - 1; l >= 0; --l) {            // (backward order: the layers whose operands were touched last come first)
@@ -493,7 +533,7 @@ int run_wgrad_deferred(codae_engine* e, const codae_buffers* b, int rows, bool w
     }
     ProfScope prof(e, CODAE_K_GEMM_WGRAD, s);
     prof.counts_as(grp.n);
-    return gemm_bf16_pipe_grouped(grp, s);
+    return gemm_bf16_pipe_grouped(grp, s, fold);
 }
 
 // Exact-fp32 GEMM of a launch too small to fill the chip (forward / data gradient of a small batch): K split over
@@ -756,9 +796,14 @@ int backward_range(codae_handle h, const codae_buffers* b, int B, int lo, int hi
             rc = run_dgrad(h, b, l, rows, false, nullptr, s);
             if (rc) return rc;
         }
+        // (the pipelined grouped launch carries the bias finish - and the loss finish left to it - as trailing workgroups)
+        BiasFold fold;
+        const bool folded = defer == 1 && !h->cfg.no_folded_bias_finish && take_bias_fold(h, b, with_norm, loss, &fold);
         rc = defer == 3 ? run_wgrad_deferred_f32(h, b, rows, s)
-                        : (defer == 1 ? run_wgrad_deferred(h, b, rows, with_norm, s) : run_wgrad_grouped(h, b, rows, with_norm, s));
+                        : (defer == 1 ? run_wgrad_deferred(h, b, rows, with_norm, s, folded ? &fold : nullptr)
+                                      : run_wgrad_grouped(h, b, rows, with_norm, s));
         if (rc) return rc;
+        if (folded) { prof_rides_along(h, CODAE_K_BIAS_FINISH); return CODAE_OK; }
         return finish_bias(h, b, s, with_norm, loss);
     }
     bool* w_pending = h->w_pending;
@@ -1024,6 +1069,7 @@ int codae_profile_end(codae_handle h, int32_t* kinds, float* ms, int32_t capacit
     h->prof_on = false;
     int n = 0;
     for (int i = 0; i < h->prof_n && n < capacity; ++i) {
+        if (h->prof_count[i] < 0) { kinds[n] = h->prof_kind[i]; ms[n] = 0.f; ++n; continue; }      // (prof_rides_along)
         CODAE_HIP_CHECK(hipEventSynchronize(h->prof_stop[i]));
         float t = 0.f;
         CODAE_HIP_CHECK(hipEventElapsedTime(&t, h->prof_start[i], h->prof_stop[i]));
@@ -1185,6 +1231,14 @@ static int run_standalone_loss(codae_handle h, const codae_buffers* b, const cod
     return rc ? rc : run_slot_contrast(h, b, hyper, ll, s);
 }
 
+// The un-noised gather of a bf16 step reads the registered bf16 image instead of the fp32 rows: only for the very dataset the image
+// was registered with, and only where the image kernel's 16-byte accesses are legal; everything else runs what it always ran.
+static bool gathers_from_image(codae_handle h, const codae_batch* batch, const void* out) {
+    const codae_engine::ImageCfg& im = h->tc.img;
+    return h->prec == CODAE_PREC_BF16 && !h->cfg.no_dataset_image && im.image != nullptr && batch->data == im.data && batch->io == im.io &&
+           gather_image_takes(batch, im.image, out, h->in_ld[0]);
+}
+
 // fold != null (codae_train_step): when the loss is fused into the last forward GEMM, its finish - 5 us of a one-block launch
 // plus a launch boundary between the loss GEMM and the first data gradient - is not launched: *fold describes it for the bias-finish
 // launch that ends the backward (as the chain path does), and the gather's first block clears the norm accumulators instead.
@@ -1219,6 +1273,9 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
         if (hyper != nullptr && h->tc.noise.kind != CODAE_NOISE_NONE)      // training input only; the loss below reads the clean row
             rc = launch_gather_noise(batch, &h->tc.noise, hyper->step, step_dev(h, b),
                                      act_ptr(h, b, 0), bf, s, h->in_ld[0], nullptr, zero_norm, pres, pres_slots);
+        else if (gathers_from_image(h, batch, act_ptr(h, b, 0)))
+            rc = launch_gather_image(batch, reinterpret_cast<const bf16_t*>(h->tc.img.image), reinterpret_cast<bf16_t*>(act_ptr(h, b, 0)), s,
+                                     h->in_ld[0], zero_norm, pres, pres_slots);
         else
             rc = launch_gather_corrupt(batch, act_ptr(h, b, 0), bf, s, h->in_ld[0], zero_norm, pres, pres_slots);
     }
@@ -1363,6 +1420,20 @@ int codae_set_slot_presence(codae_handle h, const uint8_t* present, int64_t n_ro
         p.table = present; p.n_rows = n_rows; p.n_slots = n_slots;
     }
     h->tc.pres = p;
+    return CODAE_OK;
+}
+
+int codae_set_dataset_image(codae_handle h, const float* data, const void* image_bf16, int64_t n_rows, int32_t io) {
+    CODAE_REQUIRE(h != nullptr, "codae_set_dataset_image: null handle");
+    codae_engine::ImageCfg im{};         // (built field by field: the graph key compares bytes, padding included)
+    if (image_bf16 != nullptr) {
+        CODAE_REQUIRE(data != nullptr, "codae_set_dataset_image: an image without the dataset it was cast from");
+        CODAE_REQUIRE(n_rows >= 1, "codae_set_dataset_image: n_rows %lld must be >= 1", (long long)n_rows);
+        CODAE_REQUIRE(io == h->in[0], "codae_set_dataset_image: io %d does not match the model (%d)", io, h->in[0]);
+        CODAE_REQUIRE((reinterpret_cast<uintptr_t>(image_bf16) & 15) == 0, "codae_set_dataset_image: the image must be 16-byte aligned");
+        im.data = data; im.image = image_bf16; im.n_rows = n_rows; im.io = io;
+    }
+    h->tc.img = im;
     return CODAE_OK;
 }
 

@@ -49,7 +49,9 @@ __device__ unsigned long long g_timeline[TIMELINE_WGS * TIMELINE_SLOTS];
 
 // EPI (bf16 output only): 1 = forward epilogue (bias + ReLU), 2 = data-gradient epilogue (ReLU mask from the saved
 // activation + column sums = bias gradient), 4 = the same with the 1-bit ReLU mask and nothing else (a kernel of its own: beside the
-// activation-mask copy of the write-out in ONE kernel, the compiler made the bit copy's LDS reads wait for the other copy's loads), 3 = last forward layer of a training step with the MSE loss, its gradient
+// activation-mask copy of the write-out in ONE kernel, the compiler made the bit copy's LDS reads wait for the other copy's loads),
+// 5 = the data-gradient epilogue with NO mask at all (the layer behind the code layer: column sums, nothing parked but the bias; a kernel of its
+// own for the same reason: one kind of write-out per instantiation), 3 = last forward layer of a training step with the MSE loss, its gradient
 // and the metric sums computed straight from the accumulators (g.loss), 0 = everything decided at run time.  Apart from trimming the forward's
 // epilogue this gives the forward and the data-gradient launches distinct kernel symbols in rocprofv3 traces.
 // One output tile (or split-K range of one) of one GEMM: the whole kernel body, shared by the plain kernel (one GEMM per
@@ -618,10 +620,10 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
         // and row instead of 16 - the saved activation is 25 MB per launch at C3 and comes from HBM), else the activation.
         // The kind is decided ONCE, around the write-out (MASK_* below): merged into one loop, the bit path issued - and waited
         // for - the activation path's 16-byte loads from a dummy address.
-        const bool bit_mask = EPI == 4 || (EPI != 1 && g.relu_bits != nullptr);
+        const bool bit_mask = EPI == 4 || (EPI != 1 && EPI != 5 && g.relu_bits != nullptr);
         // the 128-row tile (bits not parked): byte loads that depend on nothing but indices, issued HERE, in front of the staging pass
         uint8_t hb[ITER];
-        if constexpr (EPI != 1 && !PARK_BITS) {
+        if constexpr (EPI != 1 && EPI != 5 && !PARK_BITS) {
             if (bit_mask) {
 #pragma unroll
                 for (int it = 0; it < ITER; ++it) {
@@ -669,7 +671,7 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
             // longer than the forward one.
             bf16_t* Cb = reinterpret_cast<bf16_t*>(g.C);
             const TileStore<POL> out(Cb + (int64_t)i0 * g.ldc);
-            const bool relu_mask = EPI != 1 && !bit_mask && g.relu_src != nullptr;
+            const bool relu_mask = EPI != 1 && EPI != 5 && !bit_mask && g.relu_src != nullptr;
             constexpr int MASK_NONE = 0, MASK_BITS = 1, MASK_ACT = 2;
             // one copy of the write-out per mask kind: the bit and the plain copies load nothing from global memory, their stores
             // wait for their own LDS reads only
@@ -745,7 +747,7 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
                     }
                 }
             };
-            if constexpr (EPI == 1) write_out(std::integral_constant<int, MASK_NONE>{});
+            if constexpr (EPI == 1 || EPI == 5) write_out(std::integral_constant<int, MASK_NONE>{});
             else if constexpr (EPI == 4) write_out(std::integral_constant<int, MASK_BITS>{});
             else if (bit_mask) write_out(std::integral_constant<int, MASK_BITS>{});
             else if (relu_mask) write_out(std::integral_constant<int, MASK_ACT>{});
@@ -849,15 +851,102 @@ void gemm_bf16_pipe_kernel(GemmBf16 g, int tiles_n, int tiles_mn, int kt_total) 
     gemm_bf16_pipe_tile<BM, BN, WM, WN, NLB, A_MODE, B_MODE, C_F32, DBG, EPI, POL>(g, tiles_n, tiles_mn, kt_total, blockIdx.x, gridDim.x, smem_raw);
 }
 
+// The bias finish as workgroup `fb` of the n_fb trailing ones of the grouped launch below (BiasFold, codae_common.h): 512 threads =
+// two of bias_finish_kernel's 256-thread blocks, 2 fb and 2 fb + 1, each with that block's columns, row order, float block sum (the
+// waves' sums added in wave order) and norm slot; with a loss finish the LAST workgroup is that kernel's extra block, on its first
+// 256 threads.  Not inlined, and its table read through the kernarg segment pointer (a by-value struct indexed per lane is copied
+// to scratch first): the tile path's code and registers stay what they are without it.
+typedef const __attribute__((address_space(4))) BiasFold* FoldArgs;
+__device__ __attribute__((noinline)) void grouped_bias_finish(FoldArgs f, int fb, int n_fb, char* smem_raw) {
+    constexpr int NT = 256;
+    const int tl = threadIdx.x & (NT - 1), half = threadIdx.x >> 8;
+    if (f->loss.scalars != nullptr && fb == n_fb - 1) {
+        double* lred = reinterpret_cast<double*>(smem_raw);        // [2][NT]
+        double a = 0.0, b = 0.0;
+        if (half == 0) {
+            const double* parts = f->loss.parts;
+            for (int i = tl; i < f->loss.n_parts; i += NT) { a += parts[2 * i]; b += parts[2 * i + 1]; }
+            lred[tl] = a; lred[NT + tl] = b;
+        }
+        __syncthreads();
+        for (int o = NT / 2; o > 0; o >>= 1) {
+            if (half == 0 && tl < o) { lred[tl] += lred[tl + o]; lred[NT + tl] += lred[NT + tl + o]; }
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) {
+            double* sc = f->loss.scalars;
+            sc[CODAE_S_SQ_FULL] += lred[0];
+            sc[CODAE_S_SQ_PARTIAL] += lred[NT];
+            sc[CODAE_S_LAST_LOSS] = lred[0] * f->loss.inv_n;
+            sc[CODAE_S_STEP_SQ] = 0.0;
+        }
+        return;
+    }
+    const int n = f->n, total = f->col_begin[n];
+    const int vb = 2 * fb + half;                       // bias_finish_kernel's block index
+    const int gc = vb * NT + tl;                        // column in the concatenation of all jobs
+    float sq = 0.f;
+    if (gc < total) {
+        int j = 0;
+        while (j + 1 < n && gc >= f->col_begin[j + 1]) ++j;
+        const int c = gc - f->col_begin[j];
+        const int N = f->cols[j], R = f->rows[j];
+        const float* p = f->parts[j] + c;
+        float s = 0.f;
+        int r = 0;
+        for (; r + 32 <= R; r += 32) {              // 32 independent loads in flight, added in row order (bias_finish_kernel)
+            float v[32];
+#pragma unroll
+            for (int u = 0; u < 32; ++u) v[u] = p[(int64_t)(r + u) * N];
+#pragma unroll
+            for (int u = 0; u < 32; ++u) s += v[u];
+        }
+        for (; r + 8 <= R; r += 8) {
+            float v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = p[(int64_t)(r + u) * N];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) s += v[u];
+        }
+        for (; r < R; ++r) s += p[(int64_t)r * N];
+        f->out[j][c] = s;
+        sq = s * s;
+    }
+    if (f->sumsq != nullptr) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
+        float* red = reinterpret_cast<float*>(smem_raw);           // [8]: the waves' sums
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
+        __syncthreads();
+        if (tl == 0 && vb * NT < total) {
+            const float bsq = red[4 * half] + red[4 * half + 1] + red[4 * half + 2] + red[4 * half + 3];
+            atomicAdd(f->sumsq + (CODAE_S_GRAD_SQ_SLOTS - CODAE_S_GRAD_SQ) + (vb & (CODAE_S_N_SLOTS - 1)), (double)bsq);
+        }
+    }
+}
+// workgroups of the launch that run it
+inline int bias_fold_workgroups(const BiasFold& f) {
+    return f.n > 0 ? ceil_div(ceil_div(f.col_begin[f.n], 256), 2) + (f.loss.scalars != nullptr ? 1 : 0) : 0;
+}
+// The kernel-argument block of the grouped launch: the GEMM descriptors, the job table behind them.  The descriptors alone are 4.7 KiB
+// and have always launched; the budget keeps a wider CODAE_GROUP_MAX or a grown GemmBf16 from pushing the block past 6 KiB unnoticed.
+constexpr size_t GROUPED_FOLD_OFFSET = (sizeof(GemmBf16Group) + alignof(BiasFold) - 1) / alignof(BiasFold) * alignof(BiasFold);
+static_assert(GROUPED_FOLD_OFFSET + sizeof(BiasFold) <= 6144, "grouped launch: kernel-argument block over its budget");
+
 // Every layer's weight gradient dW_l = dA_l^T H_l (both operands k-strided, fp32 straight into the gradient vector, K = the whole
 // batch: NO split-K slabs, no reduce pass, sum g^2 from the epilogue) in ONE launch of 256 x 192 tiles: workgroup -> (GEMM, tile)
 // by the prefix sums of the descriptor block.  C3: 10 x 48 tiles of 128 K-tiles each on 256 CUs; the long K loop runs at the
 // rate DESIGN.md section 5 measured for K = 24576 (fixed costs amortised), where the per-layer launches (K = 1638 per workgroup
 // after a 5-way split) pay pipeline fill, epilogue and a 47 MB slab round trip per layer.
 template <int POL>
-__global__ __launch_bounds__(512, 2) void gemm_bf16_pipe_grouped_kernel(GemmBf16Group grp) {
+__global__ __launch_bounds__(512, 2) void gemm_bf16_pipe_grouped_kernel(GemmBf16Group grp, BiasFold fold_by_value) {
     constexpr int BM = 256, BN = 192;
     __shared__ __attribute__((aligned(16))) char smem_raw[pipe_smem_bytes<BM, BN, true, 0>()];
+    if ((int)blockIdx.x >= grp.wg_begin[grp.n]) {          // the trailing workgroups: the bias finish (dispatched last, onto CUs the tiles leave idle)
+        const FoldArgs f = (FoldArgs)((const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() + GROUPED_FOLD_OFFSET);
+        grouped_bias_finish(f, (int)blockIdx.x - grp.wg_begin[grp.n], (int)gridDim.x - grp.wg_begin[grp.n], smem_raw);
+        return;
+    }
     // Workgroup b runs on XCD b % 8, the s-th of that XCD's workgroups (s = b / 8).  Each XCD takes a CONTIGUOUS eighth of the
     // launch's tile list (GEMM after GEMM, row panel after row panel), so that the 32 workgroups an XCD runs at a time are 4
     // consecutive row panels x all column tiles of ONE weight gradient: they share 4 dA strips and the layer's 8 H strips in that
@@ -891,10 +980,12 @@ int launch_pipe(const GemmBf16& g, const Bf16Plan& p, hipStream_t s) {
     do { if (p.store_policy == STORE_WT) PIPE_LAUNCH(BM, BN, NLB, AM, BMODE, CF, 0, EP, STORE_WT); else PIPE_LAUNCH(BM, BN, NLB, AM, BMODE, CF, 0, EP, STORE_PLAIN); } while (0)
 #define LAUNCH_BF16(AM, BMODE) do { if (p.epi == 2) LAUNCH(AM, BMODE, false, 2); else LAUNCH(AM, BMODE, false, 1); } while (0)
     const bool bits = p.epi == 2 && g.relu_bits != nullptr;          // (the forward-form data gradient behind a forward that left bits)
+    // (the data gradient behind the code layer - with the transposed weight shadow or, codae_dgrad_bf16, without it; the plan still says 2)
+    const bool unmasked = p.epi == 2 && g.relu_bits == nullptr && g.relu_src == nullptr;
     if (p.dbg == 64) PIPE_LAUNCH(BM, BN, NLB, OP_KC, OP_KC, false, 64, 2, STORE_PLAIN);      // the compiler's schedule (GemmBf16::coscheduled)
     else if (p.epi == 3) LAUNCH(OP_KC, OP_KC, false, 3);
-    else if (g.a_mode == OP_KC && g.b_mode == OP_KC) { if (g.c_f32) LAUNCH(OP_KC, OP_KC, true, 0); else if (bits) LAUNCH(OP_KC, OP_KC, false, 4); else LAUNCH_BF16(OP_KC, OP_KC); }
-    else if (g.a_mode == OP_KC && g.b_mode == OP_KS) { if (g.c_f32) LAUNCH(OP_KC, OP_KS, true, 0); else LAUNCH_BF16(OP_KC, OP_KS); }
+    else if (g.a_mode == OP_KC && g.b_mode == OP_KC) { if (g.c_f32) LAUNCH(OP_KC, OP_KC, true, 0); else if (bits) LAUNCH(OP_KC, OP_KC, false, 4); else if (unmasked) LAUNCH(OP_KC, OP_KC, false, 5); else LAUNCH_BF16(OP_KC, OP_KC); }
+    else if (g.a_mode == OP_KC && g.b_mode == OP_KS) { if (g.c_f32) LAUNCH(OP_KC, OP_KS, true, 0); else if (unmasked) LAUNCH(OP_KC, OP_KS, false, 5); else LAUNCH_BF16(OP_KC, OP_KS); }
     else if (g.a_mode == OP_KS && g.b_mode == OP_KS) { if (g.c_f32) LAUNCH(OP_KS, OP_KS, true, 0); else LAUNCH_BF16(OP_KS, OP_KS); }
     else { set_error("gemm_bf16: operand mode combination not built"); return CODAE_E_UNSUPPORTED; }
 #undef LAUNCH_BF16
@@ -924,7 +1015,7 @@ int launch_pipe_mid(const GemmBf16& g, const Bf16Plan& p, hipStream_t s) {
 }  // namespace
 
 // all weight gradients of a step in one launch (see gemm_bf16_pipe_grouped_kernel); fills grp.wg_begin
-int gemm_bf16_pipe_grouped(GemmBf16Group& grp, hipStream_t s) {
+int gemm_bf16_pipe_grouped(GemmBf16Group& grp, hipStream_t s, const BiasFold* fold) {
     CODAE_REQUIRE(grp.n >= 1 && grp.n <= CODAE_GROUP_MAX, "gemm_bf16_pipe_grouped: %d GEMMs", grp.n);
     int total = 0;
     // one policy per launch, by everything the launch writes (C3: ten 9.4 MB gradients = 94 MB, more than the L2s hold: plain - the
@@ -947,8 +1038,15 @@ int gemm_bf16_pipe_grouped(GemmBf16Group& grp, hipStream_t s) {
         total += tile_count(g.M, g.N, TILE_256x192);
     }
     grp.wg_begin[grp.n] = total;
-    if (all_wt) hipLaunchKernelGGL(gemm_bf16_pipe_grouped_kernel<STORE_WT>, dim3(total), dim3(512), 0, s, grp);
-    else hipLaunchKernelGGL(gemm_bf16_pipe_grouped_kernel<STORE_PLAIN>, dim3(total), dim3(512), 0, s, grp);
+    BiasFold f{};
+    if (fold != nullptr) {
+        f = *fold;
+        CODAE_REQUIRE(f.n >= 1 && f.n <= CODAE_GROUP_MAX && f.col_begin[f.n] > 0, "gemm_bf16_pipe_grouped: %d bias-finish jobs", f.n);
+        CODAE_REQUIRE(f.loss.scalars == nullptr || (f.loss.parts != nullptr && f.loss.n_parts > 0), "gemm_bf16_pipe_grouped: bad loss block");
+    }
+    const int grid = total + bias_fold_workgroups(f);
+    if (all_wt) hipLaunchKernelGGL(gemm_bf16_pipe_grouped_kernel<STORE_WT>, dim3(grid), dim3(512), 0, s, grp, f);
+    else hipLaunchKernelGGL(gemm_bf16_pipe_grouped_kernel<STORE_PLAIN>, dim3(grid), dim3(512), 0, s, grp, f);
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;
 }

@@ -305,6 +305,12 @@ int codae_transpose_bf16(const void* src, void* dst, int32_t rows, int32_t cols,
                                  (hipStream_t)stream);
 }
 
+int codae_corrupt_batch_image(const codae_batch* batch, const void* image_bf16, const uint8_t* present, int32_t n_slots, void* out,
+                              int64_t out_ld, void* stream) {
+    return launch_gather_image(batch, reinterpret_cast<const bf16_t*>(image_bf16), reinterpret_cast<bf16_t*>(out), (hipStream_t)stream, out_ld,
+                               nullptr, present, n_slots);
+}
+
 int codae_cast_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream) {
     return launch_cast_bf16(src, reinterpret_cast<bf16_t*>(dst), n, (hipStream_t)stream);
 }
