@@ -172,7 +172,7 @@ __device__ __forceinline__ uint32_t act_dgrad_bf16x2(int kind, const float* p, u
     return pack_bf16x2(lo, hi);
 }
 
-// Philox4x32-10 (Salmon et al. 2011): the counter-based generator of the input noise (elementwise.hip) and of the hidden dropout
+// Philox4x32-10 (Salmon et al. 2011): the counter-based generator of the input noise (gather.hip) and of the hidden dropout
 // (dropout.hip); include/codae_hip.h says which counter words each uses
 __device__ __forceinline__ uint4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
 #pragma unroll
@@ -207,6 +207,15 @@ __device__ __forceinline__ uint32_t present_bits(const PresArgs& p, int64_t row,
 int check_presence(const uint8_t* present, int n_slots, int io, const char* who);
 
 static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
+
+// the launch shape of the single-pass kernels: GRID_NT threads per block, a grid-stride loop over at most 2048 blocks
+constexpr int GRID_NT = 256;
+inline int grid_for(int64_t work_items) {
+    int64_t b = (work_items + GRID_NT - 1) / GRID_NT;
+    if (b < 1) b = 1;
+    if (b > 2048) b = 2048;
+    return (int)b;
+}
 
 // ---- output store policy (GemmBf16::store_policy) ------------------------------------------------------
 // PLAIN: ordinary stores - the lines stay dirty in the writing XCD's L2 and are written back at the kernel's end, when no workgroup
@@ -429,32 +438,32 @@ bool chain_supported(int L, const int* in, const int* out);
 int chain_rows_per_workgroup();
 int launch_chain_step(const ChainArgs& a, hipStream_t s);
 
-// ---- elementwise / reductions (elementwise.hip) ----------------------------
+// ---- the batch gather (gather.hip) -----------------------------------------
+// out[b] = the batch's row b: gathered, then the input noise of `noise` (codae_noise, include/codae_hip.h; null or
+// CODAE_NOISE_NONE = the plain gather), then the slot mask, then the presence rule.  One launcher for every instantiation.
 // out_ld: row stride of `out` in elements (0 = b->io: contiguous rows)
+// step: the noise counter's step word; step_dev != null: read it from that device scalar instead (graph replay: kernel arguments
+// are frozen at capture); noise_rows: see codae_corrupt_batch.  check_noise: CODAE_E_INVALID with the offending argument named.
 // zero_norm != null: the scalars block - the launch also clears CODAE_S_GRAD_SQ and its slots (the fused step that folds its loss
 // finish into the bias finish: nothing else runs between the previous update and the first weight gradient)
 // present != null (every launcher below that takes it): the presence table [n_rows][n_slots] of "Slot presence" - the PRES
 // instantiations; null launches exactly what it launched before.
-int launch_gather_corrupt(const codae_batch* b, void* out, int out_bf16, hipStream_t s, int64_t out_ld = 0, double* zero_norm = nullptr,
-                          const uint8_t* present = nullptr, int n_slots = 0);
-// The plain gather (bf16 out, no noise) from the dataset's bf16 image instead of its fp32 rows (codae_set_dataset_image): the same
-// bits as launch_gather_corrupt(b, out, 1, ...) on the data the image was cast from.  gather_image_takes: the shape / alignment
-// conditions of its 16-byte accesses (io and out_ld multiples of 8, image and out 16-byte, the mask table 8-byte aligned).
-bool gather_image_takes(const codae_batch* b, const void* image, const void* out, int64_t out_ld);
-int launch_gather_image(const codae_batch* b, const bf16_t* image, bf16_t* out, hipStream_t s, int64_t out_ld = 0, double* zero_norm = nullptr,
-                        const uint8_t* present = nullptr, int n_slots = 0);
-// The same gather with the input noise of `noise` (codae_noise, include/codae_hip.h) in front of the slot mask: the noise-enabled
-// instantiations, beside the plain ones above.  step: the counter's step word; step_dev != null: read it from that device scalar
-// instead (graph replay: kernel arguments are frozen at capture); noise_rows: see codae_corrupt_batch.  check_noise: CODAE_E_INVALID with the offending argument named.
 int check_noise(const codae_noise* noise);
 int launch_gather_noise(const codae_batch* b, const codae_noise* noise, int32_t step, const double* step_dev, void* out,
                         int out_bf16, hipStream_t s, int64_t out_ld = 0, const int32_t* noise_rows = nullptr, double* zero_norm = nullptr,
+                        const uint8_t* present = nullptr, int n_slots = 0);
+// The plain gather (bf16 out, no noise) from the dataset's bf16 image instead of its fp32 rows (codae_set_dataset_image): the same
+// bits as launch_gather_noise(b, nullptr, .., out, 1, ...) on the data the image was cast from.  gather_image_takes: the shape / alignment
+// conditions of its 16-byte accesses (io and out_ld multiples of 8, image and out 16-byte, the mask table 8-byte aligned).
+bool gather_image_takes(const codae_batch* b, const void* image, const void* out, int64_t out_ld);
+int launch_gather_image(const codae_batch* b, const bf16_t* image, bf16_t* out, hipStream_t s, int64_t out_ld = 0, double* zero_norm = nullptr,
                         const uint8_t* present = nullptr, int n_slots = 0);
 int launch_noise_box_muller(const uint32_t* ra, const uint32_t* rb, float* rho, float* c, float* sn, int64_t n, hipStream_t s);
 int launch_cast_bf16(const float* src, bf16_t* dst, int64_t n, hipStream_t s);
 int launch_corrupt(const float* x, const float* mask, float* out, int64_t n, hipStream_t s);
 int launch_expand_masks(const int32_t* mask_id, const uint8_t* table, const int32_t* k_of_mask, int B, int io,
                         int k_max, float* masks_out, float* fmask_out, hipStream_t s);
+// ---- stand-alone losses and reductions (elementwise.hip and the files named below); the update (optimizer.hip) ----
 // One stand-alone loss launch: y fp32 [B][io], x gathered from `batch`; writes dy (fp32 or bf16, row stride dy_ld; 0 = io), one
 // colsum_part row per block (partial sums of the last bias gradient; may be null) and the per-block sums `parts`.
 // noise / step / step_dev as launch_gather_noise (which elements the gather replaced is recomputed from the same words); emph may
@@ -510,6 +519,7 @@ int launch_dropout_bwd(void* d, int bf16, int64_t ld, int B, int width, const in
                        const double* step_dev, float p, uint64_t seed, float* colsum_part, hipStream_t s);
 int launch_mse_dense(const float* x, const float* y, const float* fmask, float* dy, int64_t n, float inv_n,
                      double* scalars, hipStream_t s);
+// optimizer.hip: the gradient norm, the clip coefficient, the update
 int launch_sumsq(const float* g, int64_t n, double* out, hipStream_t s);
 int launch_sumsq_to(const float* g, int64_t n, double* acc, hipStream_t s);      // *acc += sum g^2 (one address, <= 64 blocks)
 int launch_clip_coef(const double* total_sq, float max_norm, double* coef_out, hipStream_t s);

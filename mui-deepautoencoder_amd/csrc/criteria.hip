@@ -7,7 +7,7 @@
 namespace codae {
 namespace {
 
-constexpr int NT = 256;
+constexpr int NT = GRID_NT;
 
 __device__ __forceinline__ float wave_sum_f(float v) {
 #pragma unroll
@@ -547,13 +547,6 @@ int topk_merge(const float* scores, int64_t ld, int rows, const int32_t* rows_de
 }
 
 constexpr int TOPK_KMAX = 256;
-
-inline int grid_for(int64_t items) {
-    int64_t b = (items + NT - 1) / NT;
-    if (b < 1) b = 1;
-    if (b > 2048) b = 2048;
-    return (int)b;
-}
 
 }  // namespace
 }  // namespace codae

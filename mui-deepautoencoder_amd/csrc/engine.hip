@@ -1131,7 +1131,7 @@ int codae_forward(codae_handle h, const codae_buffers* b, const float* x, float*
     // ingest x into act[layer_lo] in working precision (no gather, no mask)
     codae_batch in{};
     in.data = x; in.B = B; in.io = h->in[layer_lo];
-    rc = launch_gather_corrupt(&in, act_ptr(h, b, layer_lo), h->prec == CODAE_PREC_BF16, s, h->in_ld[layer_lo]);
+    rc = launch_gather_noise(&in, nullptr, 0, nullptr, act_ptr(h, b, layer_lo), h->prec == CODAE_PREC_BF16, s, h->in_ld[layer_lo]);
     if (rc) return rc;
     rc = zero_pad_rows(h, act_ptr(h, b, layer_lo), B, rows, h->in_ld[layer_lo], s);
     if (rc) return rc;
@@ -1161,7 +1161,7 @@ int codae_backward(codae_handle h, const codae_buffers* b, const float* dy, floa
     // dA_top = dy in working precision; db_top = column sums of dy (per 64-row block here, added up after the chain)
     codae_batch in{};
     in.data = dy; in.B = B; in.io = h->out[top];
-    rc = launch_gather_corrupt(&in, dact_ptr(h, b, top), h->prec == CODAE_PREC_BF16, s, h->out_ld[top]);
+    rc = launch_gather_noise(&in, nullptr, 0, nullptr, dact_ptr(h, b, top), h->prec == CODAE_PREC_BF16, s, h->out_ld[top]);
     if (rc) return rc;
     rc = zero_pad_rows(h, dact_ptr(h, b, top), B, rows, h->out_ld[top], s);
     if (rc) return rc;
@@ -1270,14 +1270,13 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
     {
         ProfScope prof(h, CODAE_K_GATHER, s);
         double* zero_norm = fold_finish ? b->scalars : nullptr;
-        if (hyper != nullptr && h->tc.noise.kind != CODAE_NOISE_NONE)      // training input only; the loss below reads the clean row
-            rc = launch_gather_noise(batch, &h->tc.noise, hyper->step, step_dev(h, b),
-                                     act_ptr(h, b, 0), bf, s, h->in_ld[0], nullptr, zero_norm, pres, pres_slots);
-        else if (gathers_from_image(h, batch, act_ptr(h, b, 0)))
+        const bool noised = hyper != nullptr && h->tc.noise.kind != CODAE_NOISE_NONE;      // training input only; the loss below reads the clean row
+        if (!noised && gathers_from_image(h, batch, act_ptr(h, b, 0)))
             rc = launch_gather_image(batch, reinterpret_cast<const bf16_t*>(h->tc.img.image), reinterpret_cast<bf16_t*>(act_ptr(h, b, 0)), s,
                                      h->in_ld[0], zero_norm, pres, pres_slots);
         else
-            rc = launch_gather_corrupt(batch, act_ptr(h, b, 0), bf, s, h->in_ld[0], zero_norm, pres, pres_slots);
+            rc = launch_gather_noise(batch, noised ? &h->tc.noise : nullptr, noised ? hyper->step : 0, step_dev(h, b),
+                                     act_ptr(h, b, 0), bf, s, h->in_ld[0], nullptr, zero_norm, pres, pres_slots);
     }
     if (rc) return rc;
     rc = zero_pad_rows(h, act_ptr(h, b, 0), B, rows, h->in_ld[0], s);

@@ -1,0 +1,440 @@
+// The parameter update of the DAE step: sum g^2 and the clip_grad_norm_ coefficient, clip folded into Adam / AdamW / SGD with the
+// learning-rate schedule, the bf16 shadow refresh (flat, or tiled with the transposed shadow in the same pass).
+#include "loss_sweep.h"
+
+namespace codae {
+namespace {
+
+constexpr int NT = GRID_NT;
+
+// ---- a7: sum g^2 (clip_grad_norm_, train_dae_on_embedding.py:213) ---------------------------
+__global__ __launch_bounds__(NT) void sumsq_kernel(const float* __restrict__ g, int64_t n, double* out) {
+    __shared__ float red[4];
+    float s = 0.f;
+    const int64_t n4 = n / 4;
+    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n4; e += (int64_t)gridDim.x * NT) {
+        const float4 v = reinterpret_cast<const float4*>(g)[e];
+        s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+    }
+    for (int64_t e = n4 * 4 + (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += (int64_t)gridDim.x * NT)
+        s += g[e] * g[e];
+    const float b = block_sum(s, red);
+    // `out` points at scalars[GRAD_SQ]; scatter over the slot array that follows the named scalars
+    if (threadIdx.x == 0)
+        atomicAdd(out + (CODAE_S_GRAD_SQ_SLOTS - CODAE_S_GRAD_SQ) + (blockIdx.x & (CODAE_S_N_SLOTS - 1)), (double)b);
+}
+
+// *acc += sum g^2 with at most 64 blocks (a rank's parameter shard in the sharded update): one address, few adders
+__global__ __launch_bounds__(NT) void sumsq_to_kernel(const float* __restrict__ g, int64_t n, double* acc) {
+    __shared__ float red[4];
+    float s = 0.f;
+    const int64_t n4 = n / 4;
+    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n4; e += (int64_t)gridDim.x * NT) {
+        const float4 v = reinterpret_cast<const float4*>(g)[e];
+        s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+    }
+    for (int64_t e = n4 * 4 + (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += (int64_t)gridDim.x * NT) s += g[e] * g[e];
+    const float b = block_sum(s, red);
+    if (threadIdx.x == 0) atomicAdd(acc, (double)b);
+}
+
+// clip_grad_norm_'s coefficient from a total sum g^2 (train_dae_on_embedding.py:213): min(1, max_norm / (norm + 1e-6))
+// as torch.clamp(max=1): a NaN norm gives a NaN coefficient (fminf would give 1), an infinite one gives 0
+__device__ __forceinline__ float clip_coef(float max_norm, float total) {
+    const float r = max_norm / (total + 1e-6f);
+    return r > 1.f ? 1.f : r;
+}
+__global__ void clip_coef_kernel(const double* total_sq, float max_norm, double* coef_out) {
+    const float total = sqrtf((float)*total_sq);
+    *coef_out = (double)clip_coef(max_norm, total);
+}
+
+// ---- a7 + a8: clip scale folded into Adam (torch.optim.Adam, amsgrad off, L2 decay) ----------
+struct AdamConst {
+    float lr_over_bc1, inv_sqrt_bc2, beta1, beta2, eps, wd, max_norm;
+    float lr;                // graph replay: the bias corrections are rebuilt on the device from *step_dev
+};
+
+__device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, float coef, const AdamConst& c) {
+    g = g * coef + c.wd * p;
+    m = c.beta1 * m + (1.f - c.beta1) * g;
+    v = c.beta2 * v + (1.f - c.beta2) * g * g;
+    const float denom = sqrtf(v) * c.inv_sqrt_bc2 + c.eps;
+    p = p - c.lr_over_bc1 * (m / denom);
+}
+
+// ---- optimizer kinds and the learning-rate schedule (codae_optimizer, include/codae_hip.h) ----
+// Both update kernels are templated on (KIND, AMS, SCHED); <CODAE_OPT_ADAM, false, false> is the code above, untouched.  Every other
+// instantiation rebuilds lr_t and the bias corrections in its prologue, in double, from the step count - the kernel argument in a
+// plain step, the device scalar under graph replay: the same code, so a replayed step has the bits of a plain one.
+struct OptConst {
+    float mu;                // SGD momentum
+    int nesterov;
+    int sched, warmup, total, period;
+    float min_factor, gamma;
+    int step;                // hyper->step (a plain step's t)
+    float decay;             // ADAMW: lr_t wd, filled by the prologue
+};
+
+// f(t) of include/codae_hip.h ("Optimizer and schedule"), in double
+__device__ __forceinline__ double lr_factor(const OptConst& o, double t) {
+    const double W = (double)o.warmup;
+    const double w = (o.warmup > 0 && t <= W) ? t / W : 1.0;
+    double f = 1.0;
+    if (o.sched == CODAE_SCHED_COSINE || o.sched == CODAE_SCHED_LINEAR) {
+        double q = (t - W) / ((double)o.total - W);
+        q = q < 0.0 ? 0.0 : (q > 1.0 ? 1.0 : q);
+        const double mf = (double)o.min_factor;
+        f = o.sched == CODAE_SCHED_COSINE ? mf + (1.0 - mf) * (1.0 + cos(M_PI * q)) / 2.0 : 1.0 - (1.0 - mf) * q;
+    } else if (o.sched == CODAE_SCHED_STEP) {
+        f = pow((double)o.gamma, floor((t - 1.0) / (double)o.period));
+    }
+    return w * f;
+}
+
+// c.lr <- lr_t, the bias-correction factors from it (ADAM / ADAMW), o.decay (ADAMW)
+template <int KIND, bool SCHED>
+__device__ __forceinline__ void opt_prologue(AdamConst& c, OptConst& o, const double* __restrict__ step_dev) {
+    const double t = step_dev != nullptr ? *step_dev : (double)o.step;
+    if constexpr (SCHED) c.lr = (float)((double)c.lr * lr_factor(o, t));
+    if constexpr (KIND != CODAE_OPT_SGD) {
+        c.lr_over_bc1 = (float)((double)c.lr / (1.0 - pow((double)c.beta1, t)));
+        c.inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)c.beta2, t)));
+    }
+    o.decay = c.lr * c.wd;
+}
+
+template <int KIND, bool AMS>
+__device__ __forceinline__ void opt_one(float& p, float g, float& m, float& v, float& vm, float coef, const AdamConst& c,
+                                        const OptConst& o) {
+    if constexpr (KIND == CODAE_OPT_SGD) {
+        g = g * coef + c.wd * p;
+        m = o.mu * m + g;
+        const float u = o.nesterov ? g + o.mu * m : m;
+        p = p - c.lr * u;
+    } else if constexpr (KIND == CODAE_OPT_ADAM && !AMS) {
+        adam_one(p, g, m, v, coef, c);
+    } else {
+        if constexpr (KIND == CODAE_OPT_ADAMW) { g = g * coef; p = p - o.decay * p; }     // p (1 - lr_t wd), rounded once at p's size
+        else g = g * coef + c.wd * p;
+        m = c.beta1 * m + (1.f - c.beta1) * g;
+        v = c.beta2 * v + (1.f - c.beta2) * g * g;
+        float d = v;
+        if constexpr (AMS) { vm = (v > vm || v != v) ? v : vm; d = vm; }       // torch.maximum: a NaN on either side stays
+        const float denom = sqrtf(d) * c.inv_sqrt_bc2 + c.eps;
+        p = p - c.lr_over_bc1 * (m / denom);
+    }
+}
+
+// What both update kernels do first: the step's constants (c, o) and the clip coefficient, which is returned - *coef_in when
+// given, else from sum g^2 = scalars[GRAD_SQ] + its 64 partial slots (one wave adds them up, LDS broadcasts), 1 without clipping
+template <int KIND, bool AMS, bool SCHED>
+__device__ __forceinline__ float opt_begin(AdamConst& c, OptConst& o, const double* __restrict__ step_dev,
+                                           const double* __restrict__ grad_sq, const double* __restrict__ coef_in) {
+    if constexpr (KIND != CODAE_OPT_ADAM || AMS || SCHED) {
+        opt_prologue<KIND, SCHED>(c, o, step_dev);
+    } else if (step_dev != nullptr) {
+        // replayed from a hipGraph: the step count lives in device memory (kernel arguments are frozen at capture)
+        const double t = *step_dev;
+        c.lr_over_bc1 = (float)((double)c.lr / (1.0 - pow((double)c.beta1, t)));
+        c.inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)c.beta2, t)));
+    }
+    if (coef_in != nullptr) return (float)(*coef_in);
+    if (!(c.max_norm > 0.f)) return 1.f;
+    __shared__ double total_sq;
+    if (threadIdx.x < 64) {
+        double v = grad_sq[(CODAE_S_GRAD_SQ_SLOTS - CODAE_S_GRAD_SQ) + threadIdx.x];
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
+        if (threadIdx.x == 0) total_sq = v + grad_sq[0];
+    }
+    __syncthreads();
+    return clip_coef(c.max_norm, sqrtf((float)total_sq));
+}
+
+// the update of the four elements at offset e of the flat vectors (16-B accesses; SGD neither reads nor writes v, only AMSGrad
+// touches vmax); returns the new parameters, for the caller's shadows
+template <int KIND, bool AMS>
+__device__ __forceinline__ float4 opt_four(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                           float* __restrict__ vmax, int64_t e, float coef, const AdamConst& c, const OptConst& o) {
+    constexpr bool HAS_V = KIND != CODAE_OPT_SGD;
+    float4 pp = *reinterpret_cast<float4*>(p + e);
+    const float4 gg = *reinterpret_cast<const float4*>(g + e);
+    float4 mm = *reinterpret_cast<float4*>(m + e);
+    float4 vv = make_float4(0.f, 0.f, 0.f, 0.f), xx = vv;
+    if constexpr (HAS_V) vv = *reinterpret_cast<float4*>(v + e);
+    if constexpr (AMS) xx = *reinterpret_cast<float4*>(vmax + e);
+    opt_one<KIND, AMS>(pp.x, gg.x, mm.x, vv.x, xx.x, coef, c, o);
+    opt_one<KIND, AMS>(pp.y, gg.y, mm.y, vv.y, xx.y, coef, c, o);
+    opt_one<KIND, AMS>(pp.z, gg.z, mm.z, vv.z, xx.z, coef, c, o);
+    opt_one<KIND, AMS>(pp.w, gg.w, mm.w, vv.w, xx.w, coef, c, o);
+    *reinterpret_cast<float4*>(p + e) = pp;
+    *reinterpret_cast<float4*>(m + e) = mm;
+    if constexpr (HAS_V) *reinterpret_cast<float4*>(v + e) = vv;
+    if constexpr (AMS) *reinterpret_cast<float4*>(vmax + e) = xx;
+    return pp;
+}
+
+template <int KIND, bool AMS, bool SCHED>
+__global__ __launch_bounds__(NT) void clip_adam_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                       float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                       AdamConst c, const double* __restrict__ grad_sq,
+                                                       bf16_t* __restrict__ shadow, const double* __restrict__ coef_in,
+                                                       const double* __restrict__ step_dev, float* __restrict__ vmax, OptConst o) {
+    constexpr bool HAS_V = KIND != CODAE_OPT_SGD;          // SGD neither reads nor writes v
+    const float coef = opt_begin<KIND, AMS, SCHED>(c, o, step_dev, grad_sq, coef_in);
+    const int64_t n4 = n / 4;  // n is padded to a multiple of 64 by the engine; tail handled below anyway
+    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n4; e += (int64_t)gridDim.x * NT) {
+        const float4 pp = opt_four<KIND, AMS>(p, g, m, v, vmax, 4 * e, coef, c, o);
+        if (shadow) reinterpret_cast<uint2*>(shadow)[e] = pack_bf16x4(pp.x, pp.y, pp.z, pp.w);
+    }
+    for (int64_t e = n4 * 4 + (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += (int64_t)gridDim.x * NT) {
+        float pp = p[e], mm = m[e], vv = 0.f, xx = 0.f;
+        if constexpr (HAS_V) vv = v[e];
+        if constexpr (AMS) xx = vmax[e];
+        opt_one<KIND, AMS>(pp, g[e], mm, vv, xx, coef, c, o);
+        p[e] = pp; m[e] = mm;
+        if constexpr (HAS_V) v[e] = vv;
+        if constexpr (AMS) vmax[e] = xx;
+        if (shadow) shadow[e] = f32_to_bf16(pp);
+    }
+}
+
+// Tiled form of clip_adam for the bf16 engine: the weight matrices are walked in 64 x 128 tiles so that the same
+// pass can also write the TRANSPOSED bf16 shadow (Wt_l [in][out], what the data-gradient GEMM reads) through LDS;
+// the blocks past the last tile do the flat bias block.  Replaces clip_adam_kernel + transpose_bf16_kernel: 85 MB
+// less traffic per step at C3 and no cross-stream hand-off for the transposes.
+struct AdamTiles {
+    int n_layers;
+    int64_t off[64];          // element offset of W_l in the flat vectors (same in the shadows)
+    int rows[64], cols[64];   // W_l is [rows = out][cols = in]
+    int tile_begin[65];       // prefix sum of 64 x 128 tiles per layer
+    int transposed_from;      // layers >= this also get the transposed shadow
+    int64_t bias_off, bias_n; // flat tail
+};
+constexpr int AT_R = 64, AT_C = 128;
+
+template <int KIND, bool AMS, bool SCHED>
+__global__ __launch_bounds__(NT) void clip_adam_tiled_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                             float* __restrict__ m, float* __restrict__ v, AdamConst c,
+                                                             const double* __restrict__ grad_sq, bf16_t* __restrict__ shadow,
+                                                             bf16_t* __restrict__ shadow_t, AdamTiles jobs,
+                                                             const double* __restrict__ step_dev, float* __restrict__ vmax, OptConst o) {
+    constexpr bool HAS_V = KIND != CODAE_OPT_SGD;
+    __shared__ bf16_t tt[AT_C][AT_R + 8];          // transposed tile: [col][row], rows stay 16-byte aligned
+    const float coef = opt_begin<KIND, AMS, SCHED>(c, o, step_dev, grad_sq, nullptr);
+    const int n_tiles = jobs.tile_begin[jobs.n_layers];
+    if ((int)blockIdx.x >= n_tiles) {
+        // flat bias block, grid-strided over the remaining blocks
+        const int64_t nb = (int64_t)gridDim.x - n_tiles;
+        for (int64_t e = ((int64_t)blockIdx.x - n_tiles) * NT + threadIdx.x; e < jobs.bias_n; e += nb * NT) {
+            const int64_t i = jobs.bias_off + e;
+            float pp = p[i], mm = m[i], vv = 0.f, xx = 0.f;
+            if constexpr (HAS_V) vv = v[i];
+            if constexpr (AMS) xx = vmax[i];
+            opt_one<KIND, AMS>(pp, g[i], mm, vv, xx, coef, c, o);
+            p[i] = pp; m[i] = mm;
+            if constexpr (HAS_V) v[i] = vv;
+            if constexpr (AMS) vmax[i] = xx;
+            shadow[i] = f32_to_bf16(pp);
+        }
+        return;
+    }
+    int l = 0;
+    while (l + 1 < jobs.n_layers && (int)blockIdx.x >= jobs.tile_begin[l + 1]) ++l;
+    const int t = blockIdx.x - jobs.tile_begin[l];
+    const int R = jobs.rows[l], C = jobs.cols[l];
+    const int tiles_c = (C + AT_C - 1) / AT_C;
+    const int r0 = (t / tiles_c) * AT_R, c0 = (t % tiles_c) * AT_C;
+    const int64_t base = jobs.off[l];
+    const bool want_t = shadow_t != nullptr && l >= jobs.transposed_from;
+#pragma unroll
+    for (int it = 0; it < AT_R * AT_C / 4 / NT; ++it) {
+        const int q = threadIdx.x + it * NT;          // float4 index inside the tile
+        const int r = q / (AT_C / 4), cc = (q % (AT_C / 4)) * 4;
+        if (r0 + r < R && c0 + cc < C) {
+            const int64_t e = base + (int64_t)(r0 + r) * C + c0 + cc;
+            const float4 pp = opt_four<KIND, AMS>(p, g, m, v, vmax, e, coef, c, o);
+            const uint2 sh = pack_bf16x4(pp.x, pp.y, pp.z, pp.w);
+            *reinterpret_cast<uint2*>(shadow + e) = sh;
+            if (want_t) {
+                tt[cc + 0][r] = (bf16_t)(sh.x & 0xffff); tt[cc + 1][r] = (bf16_t)(sh.x >> 16);
+                tt[cc + 2][r] = (bf16_t)(sh.y & 0xffff); tt[cc + 3][r] = (bf16_t)(sh.y >> 16);
+            }
+        }
+    }
+    if (!want_t) return;
+    __syncthreads();
+    // Wt[c0 + c][r0 .. r0 + 63]: 128-B row segments, 16 B per lane
+#pragma unroll
+    for (int it = 0; it < AT_C * (AT_R / 8) / NT; ++it) {
+        const int q = threadIdx.x + it * NT;
+        const int cidx = q / (AT_R / 8), r8 = (q % (AT_R / 8)) * 8;
+        if (c0 + cidx < C && r0 + r8 < R)
+            *reinterpret_cast<uint4*>(shadow_t + base + (int64_t)(c0 + cidx) * R + r0 + r8) =
+                *reinterpret_cast<const uint4*>(&tt[cidx][r8]);
+    }
+}
+
+__global__ void set_scalar_kernel(double* dst, double value) { *dst = value; }
+
+// ---- the optimizer setting on the host: kernel constants, instantiation ----------------------
+AdamConst adam_const(const codae_hyper* hp) {
+    AdamConst c;
+    const double bc1 = 1.0 - pow((double)hp->beta1, (double)hp->step);
+    const double bc2 = 1.0 - pow((double)hp->beta2, (double)hp->step);
+    c.lr_over_bc1 = (float)((double)hp->lr / bc1);
+    c.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    c.beta1 = hp->beta1; c.beta2 = hp->beta2; c.eps = hp->eps; c.wd = hp->weight_decay;
+    c.max_norm = hp->max_grad_norm; c.lr = hp->lr;
+    return c;
+}
+
+OptConst opt_const(const codae_optimizer* opt, const codae_hyper* hp) {
+    OptConst o{};
+    o.step = hp->step;
+    if (!optimizer_is_default(opt)) {
+        o.mu = opt->momentum; o.nesterov = opt->nesterov; o.sched = opt->sched; o.warmup = opt->warmup; o.total = opt->total;
+        o.period = opt->period; o.min_factor = opt->min_factor; o.gamma = opt->gamma;
+    }
+    return o;
+}
+
+// f(std::integral_constant<int, KIND>, std::bool_constant<AMS>, std::bool_constant<SCHED>) for the setting's instantiation
+template <typename F>
+void opt_dispatch(const codae_optimizer* opt, F&& f) {
+    const bool dflt = optimizer_is_default(opt);
+    const int kind = dflt ? CODAE_OPT_ADAM : opt->kind;
+    const bool ams = !dflt && opt->amsgrad != 0;
+    const bool sched = !dflt && (opt->sched != CODAE_SCHED_CONSTANT || opt->warmup > 0);
+    auto with_sched = [&](auto k, auto a) {
+        if (sched) f(k, a, std::true_type{}); else f(k, a, std::false_type{});
+    };
+    if (kind == CODAE_OPT_SGD) with_sched(std::integral_constant<int, CODAE_OPT_SGD>{}, std::false_type{});
+    else if (kind == CODAE_OPT_ADAMW) { if (ams) with_sched(std::integral_constant<int, CODAE_OPT_ADAMW>{}, std::true_type{}); else with_sched(std::integral_constant<int, CODAE_OPT_ADAMW>{}, std::false_type{}); }
+    else { if (ams) with_sched(std::integral_constant<int, CODAE_OPT_ADAM>{}, std::true_type{}); else with_sched(std::integral_constant<int, CODAE_OPT_ADAM>{}, std::false_type{}); }
+}
+
+}  // namespace
+
+int launch_sumsq(const float* g, int64_t n, double* out, hipStream_t s) {
+    CODAE_REQUIRE(g && out && n > 0 && a16(g), "sumsq: bad args");
+    hipLaunchKernelGGL(sumsq_kernel, dim3(grid_for(n / 4 + 1)), dim3(NT), 0, s, g, n, out);
+    CODAE_LAUNCH_CHECK();
+    return CODAE_OK;
+}
+
+int launch_sumsq_to(const float* g, int64_t n, double* acc, hipStream_t s) {
+    CODAE_REQUIRE(g && acc && n > 0, "sumsq_to: bad args");
+    int grid = grid_for(n / 4 + 1);
+    if (grid > 64) grid = 64;
+    hipLaunchKernelGGL(sumsq_to_kernel, dim3(grid), dim3(NT), 0, s, g, n, acc);
+    CODAE_LAUNCH_CHECK();
+    return CODAE_OK;
+}
+
+int launch_clip_coef(const double* total_sq, float max_norm, double* coef_out, hipStream_t s) {
+    hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(1), 0, s, total_sq, max_norm, coef_out);
+    CODAE_LAUNCH_CHECK();
+    return CODAE_OK;
+}
+
+int launch_set_scalar(double* dst, double value, hipStream_t s) {
+    CODAE_REQUIRE(dst != nullptr, "set_scalar: null destination");
+    hipLaunchKernelGGL(set_scalar_kernel, dim3(1), dim3(1), 0, s, dst, value);
+    CODAE_LAUNCH_CHECK();
+    return CODAE_OK;
+}
+
+bool optimizer_is_default(const codae_optimizer* o) {
+    return o == nullptr || (o->kind == CODAE_OPT_ADAM && o->amsgrad == 0 && o->sched == CODAE_SCHED_CONSTANT && o->warmup == 0);
+}
+
+int check_optimizer(const codae_optimizer* o) {
+    if (o == nullptr) return CODAE_OK;
+    CODAE_REQUIRE(o->kind == CODAE_OPT_ADAM || o->kind == CODAE_OPT_ADAMW || o->kind == CODAE_OPT_SGD, "optimizer: unknown kind %d", o->kind);
+    CODAE_REQUIRE(o->amsgrad == 0 || o->amsgrad == 1, "optimizer: amsgrad %d is neither 0 nor 1", o->amsgrad);
+    CODAE_REQUIRE(o->nesterov == 0 || o->nesterov == 1, "optimizer: nesterov %d is neither 0 nor 1", o->nesterov);
+    CODAE_REQUIRE(!(o->kind == CODAE_OPT_SGD && o->amsgrad), "optimizer: amsgrad belongs to adam / adamw, not to sgd");
+    CODAE_REQUIRE(finite_f(o->momentum) && o->momentum >= 0.f && o->momentum < 1.f, "optimizer: momentum %g outside [0, 1)", (double)o->momentum);
+    CODAE_REQUIRE(!o->nesterov || o->momentum > 0.f, "optimizer: nesterov needs momentum > 0");
+    CODAE_REQUIRE(o->sched >= CODAE_SCHED_CONSTANT && o->sched <= CODAE_SCHED_STEP, "optimizer: unknown schedule %d", o->sched);
+    CODAE_REQUIRE(o->warmup >= 0, "optimizer: warmup %d < 0", o->warmup);
+    if (o->sched == CODAE_SCHED_COSINE || o->sched == CODAE_SCHED_LINEAR) {
+        CODAE_REQUIRE(o->total > o->warmup, "optimizer: total %d must exceed warmup %d", o->total, o->warmup);
+        CODAE_REQUIRE(finite_f(o->min_factor) && o->min_factor >= 0.f && o->min_factor <= 1.f, "optimizer: min_factor %g outside [0, 1]",
+                      (double)o->min_factor);
+    }
+    if (o->sched == CODAE_SCHED_STEP) {
+        CODAE_REQUIRE(o->period >= 1, "optimizer: period %d < 1", o->period);
+        CODAE_REQUIRE(finite_f(o->gamma) && o->gamma > 0.f && o->gamma <= 1.f, "optimizer: gamma %g outside (0, 1]", (double)o->gamma);
+    }
+    CODAE_REQUIRE(!o->amsgrad || (o->vmax != nullptr && a16(o->vmax)), "optimizer: amsgrad needs a 16-byte aligned vmax");
+    return CODAE_OK;
+}
+
+// Only the fields the kind and the schedule read, everything else zero: the setter stores this form, and the graph key compares its bytes
+codae_optimizer optimizer_canonical(const codae_optimizer* o) {
+    codae_optimizer c{};
+    if (optimizer_is_default(o)) return c;
+    c.kind = o->kind; c.sched = o->sched; c.warmup = o->warmup;
+    if (o->kind == CODAE_OPT_SGD) { c.momentum = o->momentum; c.nesterov = o->nesterov; }
+    else if (o->amsgrad) { c.amsgrad = 1; c.vmax = o->vmax; }
+    if (o->sched == CODAE_SCHED_COSINE || o->sched == CODAE_SCHED_LINEAR) { c.total = o->total; c.min_factor = o->min_factor; }
+    if (o->sched == CODAE_SCHED_STEP) { c.period = o->period; c.gamma = o->gamma; }
+    return c;
+}
+
+int launch_clip_adam(float* p, float* g, float* m, float* v, int64_t n, const codae_hyper* hp,
+                     const double* grad_sq, bf16_t* shadow, const double* coef_in, hipStream_t s,
+                     const double* step_dev, const codae_optimizer* opt, float* vmax) {
+    const bool sgd = !optimizer_is_default(opt) && opt->kind == CODAE_OPT_SGD;
+    const bool ams = !optimizer_is_default(opt) && opt->amsgrad != 0;
+    CODAE_REQUIRE(p && g && m && (v || sgd) && hp && n > 0, "clip_adam: bad args");
+    CODAE_REQUIRE(a16(p) && a16(g) && a16(m) && (sgd || a16(v)), "clip_adam: buffers must be 16-byte aligned");
+    CODAE_REQUIRE(!ams || (vmax != nullptr && a16(vmax)), "clip_adam: amsgrad needs a 16-byte aligned vmax");
+    CODAE_REQUIRE(hp->step >= 1, "clip_adam: step must be >= 1");
+    CODAE_REQUIRE(hp->max_grad_norm <= 0.f || grad_sq || coef_in, "clip_adam: clipping needs the grad_sq scalar");
+    const AdamConst c = adam_const(hp);
+    const OptConst o = opt_const(opt, hp);
+    opt_dispatch(opt, [&](auto K, auto A, auto S) {
+        hipLaunchKernelGGL((clip_adam_kernel<decltype(K)::value, decltype(A)::value, decltype(S)::value>), dim3(grid_for(n / 4 + 1)), dim3(NT),
+                           0, s, p, g, m, v, n, c, grad_sq, shadow, coef_in, step_dev, vmax, o);
+    });
+    CODAE_LAUNCH_CHECK();
+    return CODAE_OK;
+}
+
+int launch_clip_adam_tiled(float* p, float* g, float* m, float* v, const codae_hyper* hp, const double* grad_sq,
+                           bf16_t* shadow, bf16_t* shadow_t, int n_layers, const int64_t* w_off, const int* rows,
+                           const int* cols, int transposed_from, int64_t bias_off, int64_t bias_n, hipStream_t s,
+                           const double* step_dev, const codae_optimizer* opt, float* vmax) {
+    const bool sgd = !optimizer_is_default(opt) && opt->kind == CODAE_OPT_SGD;
+    const bool ams = !optimizer_is_default(opt) && opt->amsgrad != 0;
+    CODAE_REQUIRE(p && g && m && (v || sgd) && hp && shadow && n_layers > 0 && n_layers <= 64, "clip_adam_tiled: bad args");
+    CODAE_REQUIRE(a16(p) && a16(g) && a16(m) && (sgd || a16(v)), "clip_adam_tiled: buffers must be 16-byte aligned");
+    CODAE_REQUIRE(!ams || (vmax != nullptr && a16(vmax)), "clip_adam_tiled: amsgrad needs a 16-byte aligned vmax");
+    CODAE_REQUIRE(hp->step >= 1, "clip_adam_tiled: step must be >= 1");
+    CODAE_REQUIRE(hp->max_grad_norm <= 0.f || grad_sq, "clip_adam_tiled: clipping needs the grad_sq scalar");
+    const AdamConst c = adam_const(hp);
+    const OptConst o = opt_const(opt, hp);
+    AdamTiles jobs;
+    jobs.n_layers = n_layers; jobs.transposed_from = transposed_from; jobs.bias_off = bias_off; jobs.bias_n = bias_n;
+    int total = 0;
+    for (int l = 0; l < n_layers; ++l) {
+        CODAE_REQUIRE(rows[l] % 8 == 0 && cols[l] % 4 == 0 && w_off[l] % 8 == 0, "clip_adam_tiled: layer %d shape %d x %d", l, rows[l], cols[l]);
+        jobs.off[l] = w_off[l]; jobs.rows[l] = rows[l]; jobs.cols[l] = cols[l];
+        jobs.tile_begin[l] = total;
+        total += ((rows[l] + AT_R - 1) / AT_R) * ((cols[l] + AT_C - 1) / AT_C);
+    }
+    jobs.tile_begin[n_layers] = total;
+    const int bias_blocks = (int)((bias_n + NT * 8 - 1) / (NT * 8)) > 0 ? (int)((bias_n + NT * 8 - 1) / (NT * 8)) : 1;
+    opt_dispatch(opt, [&](auto K, auto A, auto S) {
+        hipLaunchKernelGGL((clip_adam_tiled_kernel<decltype(K)::value, decltype(A)::value, decltype(S)::value>), dim3(total + bias_blocks),
+                           dim3(NT), 0, s, p, g, m, v, c, grad_sq, shadow, shadow_t, jobs, step_dev, vmax, o);
+    });
+    CODAE_LAUNCH_CHECK();
+    return CODAE_OK;
+}
+
+}  // namespace codae

@@ -9,7 +9,7 @@
 namespace codae {
 namespace {
 
-constexpr int NT = 256;
+constexpr int NT = GRID_NT;
 static_assert(NT == LOSS_NT, "loss_sweep strides the columns by LOSS_NT threads");
 constexpr int WAVES = NT / 64;
 constexpr int MAX_SLOTS = 128;   // slot_cosine: the coefficient table is LOSS_ROWS * n_slots * 2 floats of LDS (32 KiB at most)

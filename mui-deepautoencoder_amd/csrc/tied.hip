@@ -7,7 +7,7 @@
 namespace codae {
 namespace {
 
-constexpr int NT = 256;
+constexpr int NT = GRID_NT;
 constexpr int TT = 64;                 // tile edge
 constexpr int TIE_MAX = 64;            // pairs per launch
 

@@ -342,7 +342,7 @@ def test_bf16_gemms_c5_size_random(hip):
 
 
 # ---------------------------------------------------------------------------------------------
-# elementwise kernels vs the oracle
+# gather, loss, reduction and update kernels (gather.hip, elementwise.hip, optimizer.hip) vs the oracle
 # ---------------------------------------------------------------------------------------------
 
 def test_corrupt_and_expand_masks(hip):

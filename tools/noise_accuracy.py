@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Exhaustive accuracy of the Gaussian input noise's device arithmetic (csrc/elementwise.hip, box_muller_parts) against a
+"""Exhaustive accuracy of the Gaussian input noise's device arithmetic (csrc/gather.hip, box_muller_parts) against a
 float64 evaluation of the same formulas (include/codae_hip.h, "Input noise").
 
 Every one of the 2^24 values of u1 = (k + 1) 2^-24 goes through rho = sqrt(-2 ln u1), every one of the 2^24 values of
