@@ -63,6 +63,8 @@ extern "C" {
  *      change; the fold is booked under CODAE_K_SUMSQ (it forms the vector the norm is taken of), the mirror under CODAE_K_ADAM
  *      (still 11) + codae_set_dataset_image, codae_corrupt_batch_image: new entries only, no layout or enum change; the image gather is
  *      booked under CODAE_K_GATHER
+ *      (still 11) + CODAE_AVG_*, codae_weight_average, codae_set_weight_average, codae_weight_average_update: new entries only, no
+ *      layout or enum change; the average rides in the update's launch (CODAE_K_ADAM)
  * The binding must refuse a library whose codae_abi_version() differs and must check its own struct sizes against
  * codae_struct_sizes() at load (mui-deepautoencoder_amd/codae/hip/__init__.py does both). */
 #define CODAE_ABI_VERSION 11
@@ -366,6 +368,33 @@ typedef struct {
     int32_t rows, cols;
 } codae_tie_pair;
 
+/* Weight average: an average of the iterates, kept beside the parameters by the update itself, for evaluation (Polyak & Juditsky
+ * 1992; Izmailov et al. 2018, SWA; torch.optim.swa_utils.AveragedModel).  t = the 1-based step of this update (hyper->step in a plain
+ * step, scalars[CODAE_S_ADAM_STEP] under graph replay), p' = the parameter the update has just produced, a = avg at that element.
+ *   t < start or (t - start) % every != 0:  the step does not SAMPLE: avg is neither read nor written.
+ *   otherwise n = (t - start) / every, the number of earlier samples, and, in double:
+ *     SWA  w = 1 / (n + 1)                                        (the equal-weight mean of the samples)
+ *     EMA  w = 1 when n == 0, else 1 - d_n,  d_n = debias ? min(decay, (1 + n) / (10 + n)) : decay
+ *   w32 = (float)w;  a' = p' bit for bit when w32 == 1 (avg is not read), else a' = a + w32 (p' - a) in fp32 (the compiler may
+ *   contract the product and the sum into one fma).  A NaN in p' becomes a NaN in a'.
+ * The weight is computed in the update kernel's prologue from the same step count as the schedule, so a replayed step has the
+ * bits of a plain one and a graph is never re-captured for a new w; a step that does not sample issues no access to avg.
+ * avg has the layout of params; its padding stays zero (p' = 0 there).  Tied weights: only the free parameters are averaged - the
+ * decoder ranges of avg are never written by the update; averaging is linear, so the decoder of the average is the mirror of the
+ * averaged encoder, which codae_sync_shadows on a codae_buffers whose params point at avg materialises.
+ * p, the moments and the shadows of a step are bit for bit those of the same step without averaging.
+ * Not covered: the sharded update (codae_step_update_span refuses while averaging is on: a shard's average would have to be
+ * all-gathered too), the mixed-variable path, averaging of optimizer moments, checkpoint files. */
+enum { CODAE_AVG_OFF = 0, CODAE_AVG_EMA = 1, CODAE_AVG_SWA = 2 };
+typedef struct {
+    int32_t kind;          /* CODAE_AVG_* */
+    float   decay;         /* EMA: in [0, 1) */
+    int32_t debias;        /* EMA: 0 or 1 */
+    int32_t start;         /* >= 1: the first averaged step */
+    int32_t every;         /* >= 1 */
+    float*  avg;           /* device [n_param] fp32 in the layout of params, padding zero, 16-byte aligned; borrowed */
+} codae_weight_average;
+
 typedef struct codae_engine* codae_handle;
 
 /* Network description: the Linear stack built by
@@ -668,6 +697,14 @@ int codae_set_dataset_image(codae_handle h, const float* data, const void* image
  * tied (decoder matrices and their shadows overwritten from the encoder's).  The setting is part of the graph key and never
  * changes which forward or backward path a stack takes: codae_step_path is unaffected. */
 int codae_set_tied_weights(codae_handle h, int32_t on);
+/* Weight average ("Weight average" above) of every update that follows - codae_step_update, codae_train_step, codae_train_step_graph
+ * and codae_train_step_dp: the average is one more stream of the update's own launch.  NULL or kind CODAE_AVG_OFF switches it off:
+ * the engine then launches exactly the kernel instantiations it launched before.  CODAE_E_INVALID for an unknown kind, a decay
+ * outside [0, 1) or not finite, a debias that is neither 0 nor 1, start < 1, every < 1, a NULL or misaligned (16 bytes) avg; on an
+ * error nothing changes.  Fields the kind does not read are ignored.  The setting is part of the graph key (a change re-captures;
+ * a new weight never does) and never changes which path a stack takes.  While it is on codae_step_update_span returns
+ * CODAE_E_UNSUPPORTED.  avg is borrowed until the setting is replaced; the setter moves no data. */
+int codae_set_weight_average(codae_handle h, const codae_weight_average* wa);
 /* how many times codae_train_step_graph has captured (and instantiated) a graph on this handle since codae_create */
 int codae_graph_captures(codae_handle h);
 /* validation body (:245-258): forward + metric sums only */
@@ -801,6 +838,11 @@ int codae_clip_adam(float* params, float* grads, float* adam_m, float* adam_v, i
  * read and written under amsgrad only (opt->vmax is not used here).  t = hyper->step. */
 int codae_optimizer_update(float* p, float* g, float* m, float* v, float* vmax, int64_t n, const codae_hyper* hyper,
                            const codae_optimizer* opt, double* scalars, void* stream);
+
+/* The weight average on its own, for loops that keep another optimizer: avg[i] <- the definition of "Weight average" with p' = p[i],
+ * i in [0, n), t = step; wa->avg is not used here.  A step that does not sample launches nothing.  float4 accesses for the body,
+ * scalar ones for the tail; avg and p 16-byte aligned, nothing else demanded.  Validated as the setter validates. */
+int codae_weight_average_update(float* avg, const float* p, int64_t n, const codae_weight_average* wa, int32_t step, void* stream);
 
 /* The fold of "Tied weights" on caller-supplied buffers: for every pair, grads[enc_off + i cols + j] += grads[dec_off + j rows + i]
  * (fp32, that operand order), then the decoder range <- +0.  Nothing outside the paired ranges is touched.  Ranges must not

@@ -27,6 +27,8 @@ LOSS_MSE, LOSS_L1, LOSS_SMOOTH_L1, LOSS_HUBER, LOSS_SLOT_COSINE = 0, 1, 2, 3, 4
 # CODAE_OPT_* / CODAE_SCHED_* of include/codae_hip.h: the update's optimizer and schedule (codae.tool.Optimizer builds the struct)
 OPT_ADAM, OPT_ADAMW, OPT_SGD = 0, 1, 2
 SCHED_CONSTANT, SCHED_COSINE, SCHED_LINEAR, SCHED_STEP = 0, 1, 2, 3
+# CODAE_AVG_* of include/codae_hip.h: the average of the iterates the update keeps (codae.tool.WeightAverage builds the struct)
+AVG_OFF, AVG_EMA, AVG_SWA = 0, 1, 2
 KERNEL_CLASSES = ("gemm_fwd", "gemm_dgrad", "gemm_wgrad", "loss", "gather", "sumsq", "adam", "slab_reduce", "chain",
                   "bias_finish", "dropout")
 
@@ -95,6 +97,12 @@ class Optimizer(C.Structure):
                 ("vmax", C.c_void_p)]
 
 
+# codae_weight_average: five 4-byte fields, four bytes of padding, the pointer: 32 bytes (tests/test_weight_average_host.py)
+class WeightAverage(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("decay", C.c_float), ("debias", C.c_int32), ("start", C.c_int32), ("every", C.c_int32),
+                ("avg", C.c_void_p)]
+
+
 # codae_tie_pair.  Like every struct added since ABI 8 (Noise, Emphasis, ReconLoss, SlotContrast, Optimizer, Dropout) it is not in
 # codae_struct_sizes(), whose seven entries are fixed (tests pin them): four fixed-width fields without padding, 24 bytes, pinned
 # by tests/test_tied_host.py.
@@ -141,6 +149,8 @@ PROTOTYPES = {
     "codae_set_optimizer": (C.c_int, [_P, C.POINTER(Optimizer)]),
     "codae_optimizer_update": (C.c_int, [_P, _P, _P, _P, _P, _I64, C.POINTER(Hyper), C.POINTER(Optimizer), _P, _P]),
     "codae_graph_captures": (C.c_int, [_P]),
+    "codae_set_weight_average": (C.c_int, [_P, C.POINTER(WeightAverage)]),
+    "codae_weight_average_update": (C.c_int, [_P, _P, _I64, C.POINTER(WeightAverage), _I32, _P]),
     "codae_set_tied_weights": (C.c_int, [_P, _I32]),
     "codae_tie_fold": (C.c_int, [_P, C.POINTER(TiePair), _I32, _P]),
     "codae_tie_mirror": (C.c_int, [_P, _P, _P, C.POINTER(TiePair), _I32, _P]),

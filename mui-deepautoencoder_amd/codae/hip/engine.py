@@ -9,7 +9,7 @@ import torch
 
 from . import (PREC_BF16, PREC_F32, S_COUNT, S_GRAD_SQ, S_GRAD_SQ_SLOTS, S_LAST_LOSS, S_N_SLOTS, S_SQ_FULL, S_SQ_PARTIAL,
                Batch, Buffers, Dropout, Emphasis,
-               HipError, Hyper, Sizes, Spec, TiePair, check, current_stream, lib, ptr)
+               HipError, Hyper, Sizes, Spec, TiePair, WeightAverage, check, current_stream, lib, ptr)
 
 
 def precision_code(precision):
@@ -127,6 +127,11 @@ class DaeEngine:
         self._dataset_image = None    # (data, image): the device tensors codae_set_dataset_image borrows
         self.optimizer = None
         self.adam_vmax = None         # AMSGrad's running maximum (codae_optimizer.vmax borrows it), allocated on first use
+        self.weight_average = None    # the codae.tool.WeightAverage in force (None = off)
+        self.weight_avg = None        # the average itself: n_param floats in the layout of params, allocated on first use and kept
+        self.avg_shadow = None        # its bf16 image (bf16 precision), written by sync_average()
+        self.avg_bufs = None          # self.bufs with params / shadow_w pointing at the average: what an averaged evaluation reads
+        self._avg_stale = True        # the average moved since the last sync_average()
         self.step_count = 0
         self.generation = 0   # bumped by every forward: guards stale backward calls
 
@@ -189,6 +194,7 @@ class DaeEngine:
                 self.weight(l).copy_(torch.as_tensor(w, dtype=torch.float32))
                 self.bias(l).copy_(torch.as_tensor(b, dtype=torch.float32))
         self.sync_shadows()
+        self.reset_average()
 
     def sync_shadows(self):
         with torch.cuda.device(self.device):
@@ -401,6 +407,87 @@ class DaeEngine:
     def _set_optimizer_struct(self, st):
         check(self._lib.codae_set_optimizer(self._h, None if st is None else C.byref(st)))
 
+    # ---- weight average ----------------------------------------------------------------------
+    def set_weight_average(self, average):
+        """average: a codae.tool.WeightAverage, or None to switch it off.  Every update that follows - train_step (plain and
+        graph=True), step_update, train_step_dp - also keeps an EMA or the equal-weight mean of the parameters it produces
+        (include/codae_hip.h, "Weight average"), in the same launch; eval_step(weights="average") evaluates on it.  The average
+        (weight_avg, n_param floats; avg_shadow, its bf16 image in bf16 precision) is allocated on first use and starts as a copy of
+        the current parameters, so it is always a valid model; switching the setting off and on again keeps it (reset_average()
+        starts over).  step_path() is unaffected, a new weight never re-captures a graph, a changed setting does.  Parameters,
+        moments and shadows keep the bits they have without it.  Refused (HipError, the previous setting stays): a setting out of
+        range, and step_update_span while it is on."""
+        if average is not None and not hasattr(average, "weight"):
+            raise HipError("set_weight_average: expected a codae.tool.WeightAverage or None, got %r" % (average,))
+        if average is None or average.is_default:
+            self._set_average_struct(None)
+            self.weight_average = average
+            return
+        avg, shadow, fresh = self.weight_avg, self.avg_shadow, self.weight_avg is None
+        if fresh:
+            with torch.cuda.device(self.device):
+                avg = self.params.clone()
+                if self.shadow is not None:
+                    shadow = torch.zeros_like(self.shadow)
+        self._set_average_struct(average.as_struct(ptr(avg)))
+        self.weight_average, self.weight_avg, self.avg_shadow = average, avg, shadow
+        if fresh:
+            self.avg_bufs = Buffers(ptr(avg), ptr(self.grads), ptr(self.adam_m), ptr(self.adam_v), ptr(shadow), ptr(self.acts),
+                                    ptr(self.dacts), ptr(self.slabs), ptr(self.scalars), None, ptr(self.bias_parts))
+            self._avg_stale = True
+
+    def _set_average_struct(self, st):
+        check(self._lib.codae_set_weight_average(self._h, None if st is None else C.byref(st)))
+
+    def averaging(self):
+        return self.weight_average is not None and not self.weight_average.is_default
+
+    def reset_average(self):
+        """average <- the current parameters (nothing happens before the first set_weight_average)."""
+        if self.weight_avg is not None:
+            with torch.no_grad():
+                self.weight_avg.copy_(self.params)
+            self._avg_stale = True
+
+    def load_average(self, params):
+        """params: list of (W[out,in], b[out]) tensors/arrays, as load_params takes them, into the average."""
+        if self.weight_avg is None:
+            raise HipError("load_average: no weight average is kept (set_weight_average first)")
+        with torch.no_grad():
+            for l, (w, b) in enumerate(params):
+                self._view(self.weight_avg, l, False).copy_(torch.as_tensor(w, dtype=torch.float32))
+                self._view(self.weight_avg, l, True).copy_(torch.as_tensor(b, dtype=torch.float32))
+        self._avg_stale = True
+
+    def sync_average(self):
+        """What an averaged evaluation reads, from the fp32 average: with tied weights the decoder matrices of the average as
+        mirrors of its encoder's, then (bf16 precision) the bf16 image.  Lazy: only when the average has moved since the last call -
+        a training step, load_params, load_average and reset_average mark it."""
+        if self.weight_avg is None:
+            raise HipError("sync_average: no weight average is kept (set_weight_average first)")
+        if self._avg_stale:
+            with torch.cuda.device(self.device):
+                check(self._lib.codae_sync_shadows(self._h, C.byref(self.avg_bufs), current_stream()))
+            self._avg_stale = False
+
+    def average_weight(self, l):
+        self.sync_average()
+        return self._view(self.weight_avg, l, False)
+
+    def average_bias(self, l):
+        self.sync_average()
+        return self._view(self.weight_avg, l, True)
+
+    def _eval_bufs(self, weights):
+        if weights == "live":
+            return self.bufs
+        if weights != "average":
+            raise HipError("weights must be 'live' or 'average', got %r" % (weights,))
+        if not self.averaging() or self.weight_avg is None:
+            raise HipError("weights='average': no weight average is kept (set_weight_average first)")
+        self.sync_average()
+        return self.avg_bufs
+
     def set_tied_weights(self, on):
         """on: True ties the decoder to the encoder (include/codae_hip.h, "Tied weights"): Linear L-1-l uses the transpose of Linear
         l < L/2, kept in memory as a mirror.  The free parameters are the encoder matrices, the middle matrix of an odd stack and
@@ -450,6 +537,7 @@ class DaeEngine:
         with torch.cuda.device(self.device):
             check(fn(self._h, C.byref(self.bufs), C.byref(batch), C.byref(hyper), current_stream()))
         self.step_count += 1
+        self._avg_stale = True
 
     # ---- data parallel with the library's own RCCL communicator (codae_dp_*) ----------------------------------------
     def dp_unique_id(self):
@@ -473,6 +561,7 @@ class DaeEngine:
         with torch.cuda.device(self.device):
             check(self._lib.codae_train_step_dp(self._h, C.byref(self.bufs), C.byref(batch), C.byref(hyper), n, lo, hi, current_stream()))
         self.step_count += 1
+        self._avg_stale = True
 
     def step_forward_loss(self, batch, hyper, out_y=None):
         with torch.cuda.device(self.device):
@@ -499,6 +588,7 @@ class DaeEngine:
         with torch.cuda.device(self.device):
             check(self._lib.codae_step_update(self._h, C.byref(self.bufs), C.byref(hyper), current_stream()))
         self.step_count += 1
+        self._avg_stale = True
 
     # ---- sharded data-parallel update (codae.train.DataParallel(sharded=True)) -------------------
     def span_sumsq(self, lo, hi, acc):
@@ -529,9 +619,12 @@ class DaeEngine:
         """'chain' if a fused step of B rows runs the persistent chain kernel, 'layers' for per-layer launches."""
         return "chain" if self._lib.codae_step_path(self._h, C.byref(self.bufs), int(B)) == 1 else "layers"
 
-    def eval_step(self, batch, out_y=None):
+    def eval_step(self, batch, out_y=None, weights="live"):
+        """weights: "live" = the parameters the last step left; "average" = the weight average (synchronised first when it has
+        moved): the same kernels and workspaces, reading the average's images."""
+        bufs = self._eval_bufs(weights)
         with torch.cuda.device(self.device):
-            check(self._lib.codae_eval_step(self._h, C.byref(self.bufs), C.byref(batch), ptr(out_y), current_stream()))
+            check(self._lib.codae_eval_step(self._h, C.byref(bufs), C.byref(batch), ptr(out_y), current_stream()))
 
     def profile_begin(self, classes=("gemm_fwd", "gemm_dgrad", "gemm_wgrad"), max_records=4096, every=1):
         from . import KERNEL_CLASSES

@@ -2,7 +2,7 @@
 `from codae.tool import Corrupter, CombinedCriterion, ...` resolves here), gathered from this build's modules.
 The reference's legacy argparse table (codae/tool/parser.py) and attr-dict (dictionnary.py) are out of scope
 (SURVEY.md section 2): nothing on the path uses them, so they have no counterpart here."""
-from . import batching, contrast, corruption, criteria, dropout, emphasis, noise, optimizer, presence, recon_loss, runlog, tied
+from . import average, batching, contrast, corruption, criteria, dropout, emphasis, noise, optimizer, presence, recon_loss, runlog, tied
 
 _PUBLIC = {
     runlog: ("set_logging", "display_info", "get_date", "PlotDrawer", "export_parameters_to_json"),
@@ -16,6 +16,7 @@ _PUBLIC = {
     presence: ("SlotPresence",),   # rows that lack an item in some slots: absent slots stay out of input, loss and inventory
     dropout: ("HiddenDropout",),   # torch users expect Dropout between the Linears: the fused step's form of it
     optimizer: ("Optimizer", "LRSchedule", "optimizer_from_config"),   # what the update does: AdamW / SGD / AMSGrad, lr schedule
+    average: ("WeightAverage", "weight_average_from_config"),   # an EMA / SWA of the iterates kept by the update, for evaluation
     tied: ("TiedWeights",),        # the decoder uses the encoder's transposed matrices: pairs, and the fold / mirror in torch ops
     criteria: ("get_rmse", "RankingLoss", "ComplementRetriever", "CombinedCriterion"),
 }

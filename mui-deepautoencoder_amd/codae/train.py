@@ -185,6 +185,7 @@ class DataParallel:
         # tied weights: the fold runs inside the engine's update, behind every reduce of the non-sharded paths (torch.distributed,
         # bucketed, native); a shard of the sharded update would hold one half of a tied pair
         self._refuse_sharded_tie()
+        self._refuse_sharded_average()
         if self.native:
             if self.sharded:
                 raise ValueError("native RCCL data parallel: the sharded update goes through torch.distributed only")
@@ -211,6 +212,12 @@ class DataParallel:
         if self.sharded and getattr(eng, "tied_weights", False) and eng.L >= 2:
             from .tool.tied import TiedWeights
             raise TiedWeights.sharded_refusal(eng.L)
+
+    def _refuse_sharded_average(self):
+        eng = self.engine
+        if self.sharded and getattr(eng, "averaging", None) is not None and eng.averaging():
+            raise HipError("weight average: the sharded update is not supported: the average of a shard would have to be "
+                           "all-gathered too")
 
     # ---- exposed-wait timing (bench.py --gpus N) ------------------------------------------
     def time_waits(self, every=4):
@@ -299,6 +306,7 @@ class DataParallel:
             self.engine.train_step_dp(batch, hyper, self.buckets)
             return
         self._refuse_sharded_tie()             # (tying switched on after this object was built)
+        self._refuse_sharded_average()
         self.engine.step_forward_loss(batch, hyper)
         if self.sharded and (self.world > 1 or self.always_reduce):
             self._backward_reduce_scatter(B)
@@ -407,7 +415,7 @@ class HipEmbeddingTrainer:
                  max_batch=8192, precision="bf16", device="cuda:0", distributed=False, n_buckets=None, use_graph=False,
                  sharded_update=False, native_dp=False, activation=None, n_slots=None, input_noise=None,
                  loss_emphasis=None, hidden_dropout=None, criterion=None, contrast=None, optimizer=None, presence=None,
-                 tied_weights=None, dataset_image=True):
+                 tied_weights=None, dataset_image=True, weight_average=None):
         """use_graph: replay the fused step from a hipGraph (codae_train_step_graph): for launch-bound shapes
         (small batches); single process only - the bucketed data-parallel step is not captured.
         activation: what follows every hidden Linear, as the model classes take it (a factory called as activation(True),
@@ -448,7 +456,12 @@ class HipEmbeddingTrainer:
         every un-noised gather - training in every step form, eval_batch - read it instead of converting the fp32 rows every step
         (DaeEngine.set_dataset_image); the results are bit for bit the same.  The trainer never writes to `data`; a caller that
         rewrites self.data in place calls refresh_dataset_image().  False, or CODAE_NO_DATASET_IMAGE in the environment = no
-        image, exactly as before."""
+        image, exactly as before.
+        weight_average: a codae.tool.WeightAverage: every update also keeps an EMA or the equal-weight mean (SWA) of the parameters
+        it produces, in the update's own launch and in every step form but the sharded update (refused); eval_batch and complete
+        take weights="average" to run on it, params(average=True) / average_params() read it.  It starts as a copy of the
+        parameters; load_params and init_params reset it.  Training itself is untouched: parameters, moments and shadows keep
+        their bits.  None (or kind "off") = off, exactly as before."""
         from .hip.engine import DaeEngine
         fit_host_threads()      # the loop that feeds this trainer must not get its container CPU-throttled (codae/hostcpu.py)
         self.device = torch.device(device)
@@ -477,6 +490,8 @@ class HipEmbeddingTrainer:
             self.set_presence(presence)
         if tied_weights:
             self.set_tied_weights(True)
+        if weight_average is not None:
+            self.set_weight_average(weight_average)
         self.dp = DataParallel(self.engine, n_buckets=n_buckets, sharded=sharded_update, native=native_dp) if distributed else None
         self.world = self.dp.world if self.dp else 1
         self.use_graph = bool(use_graph) and self.dp is None
@@ -541,6 +556,15 @@ class HipEmbeddingTrainer:
             raise TiedWeights.sharded_refusal(self.engine.L)
         self.engine.set_tied_weights(bool(on))
 
+    def set_weight_average(self, average):
+        """DaeEngine.set_weight_average: a codae.tool.WeightAverage, or None to switch it off (the average kept so far stays
+        readable).  Refused with the sharded update."""
+        dp = self.__dict__.get("dp")
+        if average is not None and not getattr(average, "is_default", True) and dp is not None and dp.sharded:
+            raise HipError("weight average: the sharded update is not supported: the average of a shard would have to be "
+                           "all-gathered too")
+        self.engine.set_weight_average(average)
+
     def set_optimizer(self, optimizer):
         """DaeEngine.set_optimizer: a codae.tool.Optimizer, or None for Adam at a constant rate."""
         self.engine.set_optimizer(optimizer)
@@ -564,6 +588,7 @@ class HipEmbeddingTrainer:
         if self.dp:
             self.dp.broadcast_params(self.engine.params)
             self.engine.sync_shadows()
+            self.engine.reset_average()        # (behind the broadcast: every rank's average starts from rank 0's parameters)
 
     def init_params(self, seed=0):
         """Xavier-uniform weights / zero bias (embedding_...py:188-211), same on every rank.  Tied weights: the free tensors and
@@ -576,8 +601,23 @@ class HipEmbeddingTrainer:
             ps.append(((torch.rand((n, k), generator=g) * 2 - 1) * a, torch.zeros(n)))
         self.load_params(ps)
 
-    def params(self):
+    def params(self, average=False):
+        """[(W, b)] views of the parameters; average=True: of the weight average, synchronised first (with tied weights its
+        decoder matrices are then mirrors of its encoder's)."""
+        if average:
+            return self.average_params()
         return [(self.engine.weight(l), self.engine.bias(l)) for l in range(self.engine.L)]
+
+    def average_params(self):
+        return [(self.engine.average_weight(l), self.engine.average_bias(l)) for l in range(self.engine.L)]
+
+    def load_average(self, params):
+        """params: [(W, b)] as load_params takes them, into the weight average (a restored run)."""
+        self.engine.load_average(params)
+
+    def reset_average(self):
+        """weight average <- the current parameters."""
+        self.engine.reset_average()
 
     # ---- steps ---------------------------------------------------------------------------
     def _batch(self, row_idx, run):
@@ -622,11 +662,12 @@ class HipEmbeddingTrainer:
         self._keep = batch  # keep the ctypes struct (and its tensors) alive until the next call
         return B
 
-    def eval_batch(self, row_idx, run=0, want_y=False):
+    def eval_batch(self, row_idx, run=0, want_y=False, weights="live"):
+        """weights: "live" = the parameters the last step left, "average" = the weight average (HipError when none is kept)."""
         batch = self._batch(row_idx, run)
         y = (torch.empty((batch.B, self.data.shape[1]), dtype=torch.float32, device=self.device)
              if want_y else None)
-        self.engine.eval_step(batch, y)
+        self.engine.eval_step(batch, y, weights=weights)
         self._keep = batch
         return y
 
@@ -643,14 +684,15 @@ class HipEmbeddingTrainer:
             raise HipError("complete(): %d slots do not divide io %d" % (S, io))
         return S, io // S
 
-    def complete(self, row_idx, slot, k, exclude_self=False, distinct=True, candidates=None, chunk=8192):
+    def complete(self, row_idx, slot, k, exclude_self=False, distinct=True, candidates=None, chunk=8192, weights="live"):
         """Complementarity inference: blank slot `slot` of dataset rows `row_idx`, run the eval forward, and return the k
         resident-dataset rows whose slot is closest (cosine) to the reconstruction: (idx LongTensor [B, k], score FloatTensor
         [B, k]), ordered as tool.ComplementRetriever.topk.  Mask id c is the 1-subset {c} of the Corrupter's table order
         (the trainer's own S x io table when it has none), so the result does not depend on the mask run.  exclude_self:
         never return a row's own item.  The metric sums of the engine are left as they were.
         With a presence table only rows that HAVE the slot are candidates (intersected with `candidates`); a query row that
-        lacks the slot is the normal case; a slot no candidate row has gives (-1, -inf) everywhere."""
+        lacks the slot is the normal case; a slot no candidate row has gives (-1, -inf) everywhere.
+        weights: "live", or "average" to reconstruct with the weight average."""
         from .tool.criteria import ComplementRetriever
         S, E = self._slots()
         if isinstance(slot, bool) or not isinstance(slot, int) or not 0 <= slot < S:
@@ -685,7 +727,7 @@ class HipEmbeddingTrainer:
         batch = self.engine.make_batch(self.data, idx, mask_id, table)
         y = torch.empty((B, self.data.shape[1]), dtype=torch.float32, device=self.device)
         sums = self.engine.scalars.clone()
-        self.engine.eval_step(batch, y)
+        self.engine.eval_step(batch, y, weights=weights)
         self.engine.scalars.copy_(sums)                     # (the eval step adds into the epoch's metric sums)
         self._keep = batch
         ret._check_args(y, slot, k, idx if exclude_self else None, chunk)

@@ -529,7 +529,16 @@ int launch_clip_coef(const double* total_sq, float max_norm, double* coef_out, h
 // launcher always ran); vmax: AMSGrad's running maximum, at the same offset as p / m / v (a span passes vmax + lo)
 int launch_clip_adam(float* p, float* g, float* m, float* v, int64_t n, const codae_hyper* hp,
                      const double* grad_sq, bf16_t* shadow, const double* coef_in, hipStream_t s,
-                     const double* step_dev = nullptr, const codae_optimizer* opt = nullptr, float* vmax = nullptr);
+                     const double* step_dev = nullptr, const codae_optimizer* opt = nullptr, float* vmax = nullptr,
+                     const codae_weight_average* wa = nullptr, float* avg = nullptr);
+// wa / avg (both launchers): the weight-average setting (null or kind OFF = the instantiations without it) and the average at the
+// same offset as p (a span passes avg + lo; wa->avg itself is not read here)
+// CODAE_E_INVALID as codae_set_weight_average documents (need_avg: the avg pointer is checked too); canonical: only the fields the
+// kind reads; launch_weight_average: the stand-alone kernel, nothing launched on a step that does not sample
+bool weight_average_is_off(const codae_weight_average* w);
+int check_weight_average(const codae_weight_average* w, bool need_avg);
+codae_weight_average weight_average_canonical(const codae_weight_average* w);
+int launch_weight_average(float* avg, const float* p, int64_t n, const codae_weight_average* wa, int32_t step, hipStream_t s);
 // CODAE_E_INVALID as codae_set_optimizer documents; is_default: null, or {ADAM, amsgrad 0, CONSTANT, warmup 0};
 // canonical: only the fields the kind and the schedule read, all else zero (the graph key compares bytes)
 int check_optimizer(const codae_optimizer* o);
@@ -541,7 +550,8 @@ int launch_set_scalar(double* dst, double value, hipStream_t s);
 int launch_clip_adam_tiled(float* p, float* g, float* m, float* v, const codae_hyper* hp, const double* grad_sq,
                            bf16_t* shadow, bf16_t* shadow_t, int n_layers, const int64_t* w_off, const int* rows,
                            const int* cols, int transposed_from, int64_t bias_off, int64_t bias_n, hipStream_t s,
-                           const double* step_dev = nullptr, const codae_optimizer* opt = nullptr, float* vmax = nullptr);
+                           const double* step_dev = nullptr, const codae_optimizer* opt = nullptr, float* vmax = nullptr,
+                           const codae_weight_average* wa = nullptr, float* avg = nullptr);
 // dst[c][r] = src[r][c] for n bf16 matrices (element offsets off[i], shapes rows[i] x cols[i]) in one launch
 // tied weights (tied.hip; include/codae_hip.h, "Tied weights"): the fold of the decoder gradients into the encoder's, and the mirror of
 // the encoder matrices into the decoder's fp32 image and (when given) its two bf16 shadows

@@ -114,6 +114,7 @@ struct codae_engine {
         codae_optimizer opt;             // optimizer and schedule of the update (codae_set_optimizer); all zero = the default
         int32_t tied, tied_reserved;     // tied encoder / decoder weights (codae_set_tied_weights); 0 = off
         ImageCfg img;                    // bf16 image of the dataset (codae_set_dataset_image): image null = none
+        codae_weight_average avg;        // average of the iterates kept by the update (codae_set_weight_average); all zero = off
     } tc;
     bool recon_on() const { return tc.recon.kind != CODAE_LOSS_MSE; }
     bool contrast_on() const { return tc.contrast.weight != 0.f; }
@@ -1444,6 +1445,18 @@ int codae_set_optimizer(codae_handle h, const codae_optimizer* opt) {
     return CODAE_OK;
 }
 
+int codae_set_weight_average(codae_handle h, const codae_weight_average* wa) {
+    CODAE_REQUIRE(h != nullptr, "codae_set_weight_average: null handle");
+    int rc = check_weight_average(wa, true);
+    if (rc) return rc;
+    // (the graph key compares bytes and the struct has four bytes of padding in front of its pointer: zeroed here, then field by field)
+    const codae_weight_average c = weight_average_canonical(wa);
+    codae_weight_average& d = h->tc.avg;
+    memset(&d, 0, sizeof(d));
+    d.kind = c.kind; d.decay = c.decay; d.debias = c.debias; d.start = c.start; d.every = c.every; d.avg = c.avg;
+    return CODAE_OK;
+}
+
 int codae_set_tied_weights(codae_handle h, int32_t on) {
     CODAE_REQUIRE(h != nullptr, "codae_set_tied_weights: null handle");
     if (on) {
@@ -1563,6 +1576,9 @@ static int update_impl(codae_handle h, const codae_buffers* b, const codae_hyper
     // (Measured and dropped: per-layer Adam kernels on the side stream beside the NEXT forward - HBM / L2 contention
     // slowed those GEMMs from 46.8 to 56.9 us each and the step from 1.76 to 1.84 ms.)
     ProfScope prof(h, CODAE_K_ADAM, s);
+    // the weight average rides in every launch below, at the offsets of p (tied: the free parameters only)
+    const codae_weight_average* wa = &h->tc.avg;
+    float* avg = h->tc.avg.avg;
     if (tied) {
         // the free parameters only - the encoder matrices (and the middle one of an odd stack) and every bias; the moments of the
         // decoder matrices are neither read nor written - then the decoder's three images from the updated encoder
@@ -1571,7 +1587,7 @@ static int update_impl(codae_handle h, const codae_buffers* b, const codae_hyper
         if (h->prec == CODAE_PREC_BF16 && shadow_t != nullptr && h->L <= 64 && !h->cfg.flat_adam) {
             rc = launch_clip_adam_tiled(b->params, b->grads, b->adam_m, b->adam_v, hyper, b->scalars + CODAE_S_GRAD_SQ, shadow, shadow_t, nf,
                                         h->w_off.data(), h->out.data(), h->in.data(), 1, h->bias_begin, h->n_param - h->bias_begin, s,
-                                        step_dev(h, b), &h->tc.opt, h->tc.opt.vmax);
+                                        step_dev(h, b), &h->tc.opt, h->tc.opt.vmax, wa, avg);
             if (rc) return rc;
         } else {
             const int64_t spans[2][2] = {{0, h->w_off[nf]}, {h->bias_begin, h->n_param}};
@@ -1579,7 +1595,7 @@ static int update_impl(codae_handle h, const codae_buffers* b, const codae_hyper
                 const int64_t lo = sp[0], n = sp[1] - sp[0];
                 rc = launch_clip_adam(b->params + lo, b->grads + lo, b->adam_m + lo, b->adam_v + lo, n, hyper, b->scalars + CODAE_S_GRAD_SQ,
                                       shadow ? shadow + lo : nullptr, nullptr, s, step_dev(h, b), &h->tc.opt,
-                                      h->tc.opt.vmax ? h->tc.opt.vmax + lo : nullptr);
+                                      h->tc.opt.vmax ? h->tc.opt.vmax + lo : nullptr, wa, avg ? avg + lo : nullptr);
                 if (rc) return rc;
             }
             rc = refresh_transposed(h, b, s, 1, nf);
@@ -1591,10 +1607,10 @@ static int update_impl(codae_handle h, const codae_buffers* b, const codae_hyper
         // one tiled pass: p, m, v, the bf16 shadow and the transposed shadow of every layer that has a data gradient
         return launch_clip_adam_tiled(b->params, b->grads, b->adam_m, b->adam_v, hyper, b->scalars + CODAE_S_GRAD_SQ, shadow,
                                       reinterpret_cast<bf16_t*>(b->shadow_wt), h->L, h->w_off.data(), h->out.data(), h->in.data(),
-                                      1, h->bias_begin, h->n_param - h->bias_begin, s, step_dev(h, b), &h->tc.opt, h->tc.opt.vmax);
+                                      1, h->bias_begin, h->n_param - h->bias_begin, s, step_dev(h, b), &h->tc.opt, h->tc.opt.vmax, wa, avg);
     }
     rc = launch_clip_adam(b->params, b->grads, b->adam_m, b->adam_v, h->n_param, hyper, b->scalars + CODAE_S_GRAD_SQ,
-                          shadow, nullptr, s, step_dev(h, b), &h->tc.opt, h->tc.opt.vmax);
+                          shadow, nullptr, s, step_dev(h, b), &h->tc.opt, h->tc.opt.vmax, wa, avg);
     if (rc) return rc;
     return refresh_transposed(h, b, s);
 }
@@ -1616,6 +1632,10 @@ int codae_step_update_span(codae_handle h, const codae_buffers* b, const codae_h
     CODAE_REQUIRE(hyper->max_grad_norm <= 0.f || total_sq != nullptr, "codae_step_update_span: clipping needs the global sum g^2");
     if (h->tc.tied && !h->tie_pairs.empty()) {
         set_error("tied weights: the sharded update is not supported: the tied layers %d and %d lie in different shards", 0, h->L - 1);
+        return CODAE_E_UNSUPPORTED;
+    }
+    if (h->tc.avg.kind != CODAE_AVG_OFF) {
+        set_error("weight average: the sharded update is not supported: the average of a shard would have to be all-gathered too");
         return CODAE_E_UNSUPPORTED;
     }
     hipStream_t s = (hipStream_t)stream;

@@ -152,11 +152,65 @@ __device__ __forceinline__ float opt_begin(AdamConst& c, OptConst& o, const doub
     return clip_coef(c.max_norm, sqrtf((float)total_sq));
 }
 
+// ---- weight average (codae_weight_average, include/codae_hip.h "Weight average") --------------
+// Both update kernels carry a fourth template flag AVG; the AVG = false instantiations are the code above and below without a line
+// of this.  AVG = true: the prologue decides from the step count - the same source the schedule reads - whether this step samples
+// and with which weight, and every element's new parameter goes into the average on its way to memory.
+struct AvgConst {
+    float* avg;              // at the same offset as p (a span passes avg + lo)
+    int kind, debias, start, every;
+    float decay;
+};
+struct AvgStep { float* avg; float w; bool sample; };      // this launch: wave-uniform, all of it
+
+// w32 of step t, in double; false: the step does not sample
+__host__ __device__ inline bool avg_weight(int kind, float decay, int debias, int start, int every, int64_t t, float* w32) {
+    if (t < (int64_t)start || (t - start) % every != 0) return false;
+    const int64_t n = (t - start) / every;
+    double w = 1.0;
+    if (kind == CODAE_AVG_SWA) w = 1.0 / (double)(n + 1);
+    else if (n > 0) {
+        double d = (double)decay;
+        if (debias) { const double r = (1.0 + (double)n) / (10.0 + (double)n); d = d < r ? d : r; }
+        w = 1.0 - d;
+    }
+    *w32 = (float)w;
+    return true;
+}
+
+template <bool AVG>
+__device__ __forceinline__ AvgStep avg_begin(const AvgConst& a, const OptConst& o, const double* __restrict__ step_dev) {
+    AvgStep st{nullptr, 1.f, false};
+    if constexpr (AVG) {
+        const double t = step_dev != nullptr ? *step_dev : (double)o.step;
+        st.avg = a.avg;
+        st.sample = avg_weight(a.kind, a.decay, a.debias, a.start, a.every, (int64_t)t, &st.w);
+    }
+    return st;
+}
+
+__device__ __forceinline__ float avg_one(float a, float p, float w) { return a + w * (p - a); }
+// one element / four elements (16-B accesses) of the average at offset e; w == 1: a bit copy, the old average is not read
+__device__ __forceinline__ void avg_put(const AvgStep& st, int64_t e, float p) {
+    st.avg[e] = st.w == 1.f ? p : avg_one(st.avg[e], p, st.w);
+}
+__device__ __forceinline__ void avg_put4(const AvgStep& st, int64_t e, const float4& pp) {
+    float4 aa = pp;
+    if (st.w != 1.f) {
+        aa = *reinterpret_cast<const float4*>(st.avg + e);
+        aa.x = avg_one(aa.x, pp.x, st.w); aa.y = avg_one(aa.y, pp.y, st.w);
+        aa.z = avg_one(aa.z, pp.z, st.w); aa.w = avg_one(aa.w, pp.w, st.w);
+    }
+    *reinterpret_cast<float4*>(st.avg + e) = aa;
+}
+
 // the update of the four elements at offset e of the flat vectors (16-B accesses; SGD neither reads nor writes v, only AMSGrad
-// touches vmax); returns the new parameters, for the caller's shadows
-template <int KIND, bool AMS>
+// touches vmax; AVG: one more float4 load and store on a sampling step, none otherwise); returns the new parameters, for the
+// caller's shadows
+template <int KIND, bool AMS, bool AVG>
 __device__ __forceinline__ float4 opt_four(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                           float* __restrict__ vmax, int64_t e, float coef, const AdamConst& c, const OptConst& o) {
+                                           float* __restrict__ vmax, int64_t e, float coef, const AdamConst& c, const OptConst& o,
+                                           const AvgStep& av) {
     constexpr bool HAS_V = KIND != CODAE_OPT_SGD;
     float4 pp = *reinterpret_cast<float4*>(p + e);
     const float4 gg = *reinterpret_cast<const float4*>(g + e);
@@ -172,20 +226,31 @@ __device__ __forceinline__ float4 opt_four(float* __restrict__ p, const float* _
     *reinterpret_cast<float4*>(m + e) = mm;
     if constexpr (HAS_V) *reinterpret_cast<float4*>(v + e) = vv;
     if constexpr (AMS) *reinterpret_cast<float4*>(vmax + e) = xx;
+    if constexpr (AVG) {
+        if (av.sample) {
+            // the average takes p' through an opaque copy: the update's own arithmetic must be selected, packed and contracted exactly
+            // as without the average (its bits are pinned), so nothing of the average's may be visible to the passes that shape it
+            float4 q = pp;
+            asm volatile("" : "+v"(q.x), "+v"(q.y), "+v"(q.z), "+v"(q.w));
+            avg_put4(av, e, q);
+        }
+    }
     return pp;
 }
 
-template <int KIND, bool AMS, bool SCHED>
+template <int KIND, bool AMS, bool SCHED, bool AVG>
 __global__ __launch_bounds__(NT) void clip_adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                        float* __restrict__ m, float* __restrict__ v, int64_t n,
                                                        AdamConst c, const double* __restrict__ grad_sq,
                                                        bf16_t* __restrict__ shadow, const double* __restrict__ coef_in,
-                                                       const double* __restrict__ step_dev, float* __restrict__ vmax, OptConst o) {
+                                                       const double* __restrict__ step_dev, float* __restrict__ vmax, OptConst o,
+                                                       AvgConst a) {
     constexpr bool HAS_V = KIND != CODAE_OPT_SGD;          // SGD neither reads nor writes v
     const float coef = opt_begin<KIND, AMS, SCHED>(c, o, step_dev, grad_sq, coef_in);
+    const AvgStep av = avg_begin<AVG>(a, o, step_dev);
     const int64_t n4 = n / 4;  // n is padded to a multiple of 64 by the engine; tail handled below anyway
     for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n4; e += (int64_t)gridDim.x * NT) {
-        const float4 pp = opt_four<KIND, AMS>(p, g, m, v, vmax, 4 * e, coef, c, o);
+        const float4 pp = opt_four<KIND, AMS, AVG>(p, g, m, v, vmax, 4 * e, coef, c, o, av);
         if (shadow) reinterpret_cast<uint2*>(shadow)[e] = pack_bf16x4(pp.x, pp.y, pp.z, pp.w);
     }
     for (int64_t e = n4 * 4 + (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += (int64_t)gridDim.x * NT) {
@@ -197,6 +262,12 @@ __global__ __launch_bounds__(NT) void clip_adam_kernel(float* __restrict__ p, co
         if constexpr (HAS_V) v[e] = vv;
         if constexpr (AMS) vmax[e] = xx;
         if (shadow) shadow[e] = f32_to_bf16(pp);
+    }
+    // (the tail's average in a sweep of its own, every thread over the elements it has just written: inside the loop above it
+    //  changed which of that loop's products the compiler packs and contracts, and with that the pinned bits of p)
+    if constexpr (AVG) {
+        if (av.sample)
+            for (int64_t e = n4 * 4 + (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += (int64_t)gridDim.x * NT) avg_put(av, e, p[e]);
     }
 }
 
@@ -214,15 +285,17 @@ struct AdamTiles {
 };
 constexpr int AT_R = 64, AT_C = 128;
 
-template <int KIND, bool AMS, bool SCHED>
+template <int KIND, bool AMS, bool SCHED, bool AVG>
 __global__ __launch_bounds__(NT) void clip_adam_tiled_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                              float* __restrict__ m, float* __restrict__ v, AdamConst c,
                                                              const double* __restrict__ grad_sq, bf16_t* __restrict__ shadow,
                                                              bf16_t* __restrict__ shadow_t, AdamTiles jobs,
-                                                             const double* __restrict__ step_dev, float* __restrict__ vmax, OptConst o) {
+                                                             const double* __restrict__ step_dev, float* __restrict__ vmax, OptConst o,
+                                                             AvgConst a) {
     constexpr bool HAS_V = KIND != CODAE_OPT_SGD;
     __shared__ bf16_t tt[AT_C][AT_R + 8];          // transposed tile: [col][row], rows stay 16-byte aligned
     const float coef = opt_begin<KIND, AMS, SCHED>(c, o, step_dev, grad_sq, nullptr);
+    const AvgStep av = avg_begin<AVG>(a, o, step_dev);
     const int n_tiles = jobs.tile_begin[jobs.n_layers];
     if ((int)blockIdx.x >= n_tiles) {
         // flat bias block, grid-strided over the remaining blocks
@@ -237,6 +310,12 @@ __global__ __launch_bounds__(NT) void clip_adam_tiled_kernel(float* __restrict__
             if constexpr (HAS_V) v[i] = vv;
             if constexpr (AMS) vmax[i] = xx;
             shadow[i] = f32_to_bf16(pp);
+        }
+        // (the bias block's average in a sweep of its own, as in clip_adam_kernel's tail)
+        if constexpr (AVG) {
+            if (av.sample)
+                for (int64_t e = ((int64_t)blockIdx.x - n_tiles) * NT + threadIdx.x; e < jobs.bias_n; e += nb * NT)
+                    avg_put(av, jobs.bias_off + e, p[jobs.bias_off + e]);
         }
         return;
     }
@@ -254,7 +333,7 @@ __global__ __launch_bounds__(NT) void clip_adam_tiled_kernel(float* __restrict__
         const int r = q / (AT_C / 4), cc = (q % (AT_C / 4)) * 4;
         if (r0 + r < R && c0 + cc < C) {
             const int64_t e = base + (int64_t)(r0 + r) * C + c0 + cc;
-            const float4 pp = opt_four<KIND, AMS>(p, g, m, v, vmax, e, coef, c, o);
+            const float4 pp = opt_four<KIND, AMS, AVG>(p, g, m, v, vmax, e, coef, c, o, av);
             const uint2 sh = pack_bf16x4(pp.x, pp.y, pp.z, pp.w);
             *reinterpret_cast<uint2*>(shadow + e) = sh;
             if (want_t) {
@@ -274,6 +353,15 @@ __global__ __launch_bounds__(NT) void clip_adam_tiled_kernel(float* __restrict__
             *reinterpret_cast<uint4*>(shadow_t + base + (int64_t)(c0 + cidx) * R + r0 + r8) =
                 *reinterpret_cast<const uint4*>(&tt[cidx][r8]);
     }
+}
+
+// The average alone, behind somebody else's update (codae_weight_average_update): the host has decided that the step samples
+__global__ __launch_bounds__(NT) void weight_average_kernel(float* __restrict__ avg, const float* __restrict__ p, int64_t n, float w) {
+    const AvgStep av{avg, w, true};
+    const int64_t n4 = n / 4;
+    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n4; e += (int64_t)gridDim.x * NT)
+        avg_put4(av, 4 * e, *reinterpret_cast<const float4*>(p + 4 * e));
+    for (int64_t e = n4 * 4 + (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += (int64_t)gridDim.x * NT) avg_put(av, e, p[e]);
 }
 
 __global__ void set_scalar_kernel(double* dst, double value) { *dst = value; }
@@ -300,15 +388,25 @@ OptConst opt_const(const codae_optimizer* opt, const codae_hyper* hp) {
     return o;
 }
 
-// f(std::integral_constant<int, KIND>, std::bool_constant<AMS>, std::bool_constant<SCHED>) for the setting's instantiation
+AvgConst avg_const(const codae_weight_average* wa, float* avg) {
+    AvgConst a{};
+    if (!weight_average_is_off(wa)) {
+        a.avg = avg; a.kind = wa->kind; a.debias = wa->debias; a.start = wa->start; a.every = wa->every; a.decay = wa->decay;
+    }
+    return a;
+}
+
+// f(std::integral_constant<int, KIND>, std::bool_constant<AMS>, std::bool_constant<SCHED>, std::bool_constant<AVG>) for the
+// settings' instantiation
 template <typename F>
-void opt_dispatch(const codae_optimizer* opt, F&& f) {
+void opt_dispatch(const codae_optimizer* opt, bool avg, F&& f) {
     const bool dflt = optimizer_is_default(opt);
     const int kind = dflt ? CODAE_OPT_ADAM : opt->kind;
     const bool ams = !dflt && opt->amsgrad != 0;
     const bool sched = !dflt && (opt->sched != CODAE_SCHED_CONSTANT || opt->warmup > 0);
     auto with_sched = [&](auto k, auto a) {
-        if (sched) f(k, a, std::true_type{}); else f(k, a, std::false_type{});
+        if (sched) { if (avg) f(k, a, std::true_type{}, std::true_type{}); else f(k, a, std::true_type{}, std::false_type{}); }
+        else { if (avg) f(k, a, std::false_type{}, std::true_type{}); else f(k, a, std::false_type{}, std::false_type{}); }
     };
     if (kind == CODAE_OPT_SGD) with_sched(std::integral_constant<int, CODAE_OPT_SGD>{}, std::false_type{});
     else if (kind == CODAE_OPT_ADAMW) { if (ams) with_sched(std::integral_constant<int, CODAE_OPT_ADAMW>{}, std::true_type{}); else with_sched(std::integral_constant<int, CODAE_OPT_ADAMW>{}, std::false_type{}); }
@@ -385,21 +483,61 @@ codae_optimizer optimizer_canonical(const codae_optimizer* o) {
     return c;
 }
 
+bool weight_average_is_off(const codae_weight_average* w) { return w == nullptr || w->kind == CODAE_AVG_OFF; }
+
+int check_weight_average(const codae_weight_average* w, bool need_avg) {
+    if (weight_average_is_off(w)) return CODAE_OK;
+    CODAE_REQUIRE(w->kind == CODAE_AVG_EMA || w->kind == CODAE_AVG_SWA, "weight average: unknown kind %d", w->kind);
+    if (w->kind == CODAE_AVG_EMA) {
+        CODAE_REQUIRE(finite_f(w->decay) && w->decay >= 0.f && w->decay < 1.f, "weight average: decay %g outside [0, 1)", (double)w->decay);
+        CODAE_REQUIRE(w->debias == 0 || w->debias == 1, "weight average: debias %d is neither 0 nor 1", w->debias);
+    }
+    CODAE_REQUIRE(w->start >= 1, "weight average: start %d < 1", w->start);
+    CODAE_REQUIRE(w->every >= 1, "weight average: every %d < 1", w->every);
+    CODAE_REQUIRE(!need_avg || (w->avg != nullptr && a16(w->avg)), "weight average: avg must be a 16-byte aligned device vector");
+    return CODAE_OK;
+}
+
+// Only the fields the kind reads, everything else zero: the setter stores this form, and the graph key compares its bytes
+codae_weight_average weight_average_canonical(const codae_weight_average* w) {
+    codae_weight_average c{};
+    if (weight_average_is_off(w)) return c;
+    c.kind = w->kind; c.start = w->start; c.every = w->every; c.avg = w->avg;
+    if (w->kind == CODAE_AVG_EMA) { c.decay = w->decay; c.debias = w->debias; }
+    return c;
+}
+
+int launch_weight_average(float* avg, const float* p, int64_t n, const codae_weight_average* wa, int32_t step, hipStream_t s) {
+    CODAE_REQUIRE(wa != nullptr, "weight_average_update: null setting");
+    int rc = check_weight_average(wa, false);
+    if (rc) return rc;
+    CODAE_REQUIRE(avg && p && n > 0 && a16(avg) && a16(p), "weight_average_update: avg and p must be 16-byte aligned, n > 0");
+    CODAE_REQUIRE(step >= 1, "weight_average_update: step must be >= 1");
+    float w = 1.f;
+    if (weight_average_is_off(wa) || !avg_weight(wa->kind, wa->decay, wa->debias, wa->start, wa->every, step, &w)) return CODAE_OK;
+    hipLaunchKernelGGL(weight_average_kernel, dim3(grid_for(n / 4 + 1)), dim3(NT), 0, s, avg, p, n, w);
+    CODAE_LAUNCH_CHECK();
+    return CODAE_OK;
+}
+
 int launch_clip_adam(float* p, float* g, float* m, float* v, int64_t n, const codae_hyper* hp,
                      const double* grad_sq, bf16_t* shadow, const double* coef_in, hipStream_t s,
-                     const double* step_dev, const codae_optimizer* opt, float* vmax) {
+                     const double* step_dev, const codae_optimizer* opt, float* vmax, const codae_weight_average* wa, float* avg) {
     const bool sgd = !optimizer_is_default(opt) && opt->kind == CODAE_OPT_SGD;
     const bool ams = !optimizer_is_default(opt) && opt->amsgrad != 0;
+    const bool avg_on = !weight_average_is_off(wa);
     CODAE_REQUIRE(p && g && m && (v || sgd) && hp && n > 0, "clip_adam: bad args");
+    CODAE_REQUIRE(!avg_on || (avg != nullptr && a16(avg)), "clip_adam: the weight average needs a 16-byte aligned avg");
     CODAE_REQUIRE(a16(p) && a16(g) && a16(m) && (sgd || a16(v)), "clip_adam: buffers must be 16-byte aligned");
     CODAE_REQUIRE(!ams || (vmax != nullptr && a16(vmax)), "clip_adam: amsgrad needs a 16-byte aligned vmax");
     CODAE_REQUIRE(hp->step >= 1, "clip_adam: step must be >= 1");
     CODAE_REQUIRE(hp->max_grad_norm <= 0.f || grad_sq || coef_in, "clip_adam: clipping needs the grad_sq scalar");
     const AdamConst c = adam_const(hp);
     const OptConst o = opt_const(opt, hp);
-    opt_dispatch(opt, [&](auto K, auto A, auto S) {
-        hipLaunchKernelGGL((clip_adam_kernel<decltype(K)::value, decltype(A)::value, decltype(S)::value>), dim3(grid_for(n / 4 + 1)), dim3(NT),
-                           0, s, p, g, m, v, n, c, grad_sq, shadow, coef_in, step_dev, vmax, o);
+    const AvgConst ac = avg_const(wa, avg);
+    opt_dispatch(opt, avg_on, [&](auto K, auto A, auto S, auto V) {
+        hipLaunchKernelGGL((clip_adam_kernel<decltype(K)::value, decltype(A)::value, decltype(S)::value, decltype(V)::value>),
+                           dim3(grid_for(n / 4 + 1)), dim3(NT), 0, s, p, g, m, v, n, c, grad_sq, shadow, coef_in, step_dev, vmax, o, ac);
     });
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;
@@ -408,10 +546,12 @@ int launch_clip_adam(float* p, float* g, float* m, float* v, int64_t n, const co
 int launch_clip_adam_tiled(float* p, float* g, float* m, float* v, const codae_hyper* hp, const double* grad_sq,
                            bf16_t* shadow, bf16_t* shadow_t, int n_layers, const int64_t* w_off, const int* rows,
                            const int* cols, int transposed_from, int64_t bias_off, int64_t bias_n, hipStream_t s,
-                           const double* step_dev, const codae_optimizer* opt, float* vmax) {
+                           const double* step_dev, const codae_optimizer* opt, float* vmax, const codae_weight_average* wa, float* avg) {
     const bool sgd = !optimizer_is_default(opt) && opt->kind == CODAE_OPT_SGD;
     const bool ams = !optimizer_is_default(opt) && opt->amsgrad != 0;
+    const bool avg_on = !weight_average_is_off(wa);
     CODAE_REQUIRE(p && g && m && (v || sgd) && hp && shadow && n_layers > 0 && n_layers <= 64, "clip_adam_tiled: bad args");
+    CODAE_REQUIRE(!avg_on || (avg != nullptr && a16(avg)), "clip_adam_tiled: the weight average needs a 16-byte aligned avg");
     CODAE_REQUIRE(a16(p) && a16(g) && a16(m) && (sgd || a16(v)), "clip_adam_tiled: buffers must be 16-byte aligned");
     CODAE_REQUIRE(!ams || (vmax != nullptr && a16(vmax)), "clip_adam_tiled: amsgrad needs a 16-byte aligned vmax");
     CODAE_REQUIRE(hp->step >= 1, "clip_adam_tiled: step must be >= 1");
@@ -429,9 +569,10 @@ int launch_clip_adam_tiled(float* p, float* g, float* m, float* v, const codae_h
     }
     jobs.tile_begin[n_layers] = total;
     const int bias_blocks = (int)((bias_n + NT * 8 - 1) / (NT * 8)) > 0 ? (int)((bias_n + NT * 8 - 1) / (NT * 8)) : 1;
-    opt_dispatch(opt, [&](auto K, auto A, auto S) {
-        hipLaunchKernelGGL((clip_adam_tiled_kernel<decltype(K)::value, decltype(A)::value, decltype(S)::value>), dim3(total + bias_blocks),
-                           dim3(NT), 0, s, p, g, m, v, c, grad_sq, shadow, shadow_t, jobs, step_dev, vmax, o);
+    const AvgConst ac = avg_const(wa, avg);
+    opt_dispatch(opt, avg_on, [&](auto K, auto A, auto S, auto V) {
+        hipLaunchKernelGGL((clip_adam_tiled_kernel<decltype(K)::value, decltype(A)::value, decltype(S)::value, decltype(V)::value>),
+                           dim3(total + bias_blocks), dim3(NT), 0, s, p, g, m, v, c, grad_sq, shadow, shadow_t, jobs, step_dev, vmax, o, ac);
     });
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;

@@ -198,6 +198,10 @@ int codae_optimizer_update(float* p, float* g, float* m, float* v, float* vmax, 
     return launch_clip_adam(p, g, m, v, n, hyper, scalars + CODAE_S_GRAD_SQ, nullptr, nullptr, s, nullptr, &o, o.vmax);
 }
 
+int codae_weight_average_update(float* avg, const float* p, int64_t n, const codae_weight_average* wa, int32_t step, void* stream) {
+    return launch_weight_average(avg, p, n, wa, step, (hipStream_t)stream);
+}
+
 // ---- GEMM primitives ------------------------------------------------------------------------
 // The plain entry points run the ReLU / identity code (`relu`); the _act_ ones the generic-activation instantiation, CODAE_ACT_RELU
 // included, and hand CODAE_ACT_NONE (or a data gradient without a saved activation) to the plain one.

@@ -151,13 +151,20 @@ def main():
     from codae.tool import TiedWeights
     tied_weights = TiedWeights.from_config(config.get("HIP", {}).get("TIED_WEIGHTS"))
 
+    # HIP: WEIGHT_AVERAGE: {KIND: ema | swa, DECAY: 0.999, DEBIAS: true, START: 1 | START_EPOCH: k, EVERY: 1} (build-only key): the update
+    # also keeps an average of the parameters it produces, and the validation sweep below runs on that average; START_EPOCH counts
+    # this script's own batches per epoch
+    from codae.tool.average import weight_average_from_config
+    weight_average = weight_average_from_config(config.get("HIP", {}).get("WEIGHT_AVERAGE"), batches_per_epoch=max(1, len(train_sampler)))
+    eval_weights = "average" if weight_average is not None and not weight_average.is_default else "live"
+
     def build(prec):
         return HipEmbeddingTrainer(enc + dec, dataset.data, corrupter.mask_table_u8, mask_to_use,
                                    mc["LEARNING_RATE"], mc["WEIGHT_DECAY"], clip=1.0 if mc["TRUNK_GRAD"] else 0.0,
                                    max_batch=mc["BATCH_SIZE"], precision=prec, device=device, distributed=world > 1,
                                    activation=activation, input_noise=input_noise, loss_emphasis=loss_emphasis,
                                    hidden_dropout=hidden_dropout, criterion=criterion, contrast=contrast, optimizer=optimizer,
-                                   presence=presence, tied_weights=tied_weights)
+                                   presence=presence, tied_weights=tied_weights, weight_average=weight_average)
     try:
         trainer = build(precision)
     except HipError as e:
@@ -173,6 +180,8 @@ def main():
     if tied_weights:
         log.info("TIED WEIGHTS: %d free parameters of %d" % (TiedWeights.free_parameter_count(enc + dec),
                                                             sum(k * n + n for k, n, _ in enc + dec)))
+    if eval_weights == "average":
+        log.info("WEIGHT AVERAGE: %r - the validation errors and the ranking error are those of the averaged weights" % (weight_average,))
     book = {k: [] for k in ("ftl", "ptl", "fvl", "pvl", "rl")}
     S = dataset.nb_used_category
     rank_indices, nb_ranked = validation_indices, nb_validation
@@ -219,7 +228,7 @@ def main():
         # batched GEMMs against the validation inventory with the masks taken from the Corrupter's device tables; one
         # read-back per epoch instead of a mask expansion, two .tolist() and a host sync per batch
         for idx in validation_sampler.device_batches(device):
-            y = trainer.eval_batch(idx, run=0, want_y=True)
+            y = trainer.eval_batch(idx, run=0, want_y=True, weights=eval_weights)
             if is_ranked is None:
                 ranking_loss.add(y, idx, corrupter, run=0)
             elif rank_indices:
