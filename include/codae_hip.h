@@ -65,6 +65,8 @@ extern "C" {
  *      booked under CODAE_K_GATHER
  *      (still 11) + CODAE_AVG_*, codae_weight_average, codae_set_weight_average, codae_weight_average_update: new entries only, no
  *      layout or enum change; the average rides in the update's launch (CODAE_K_ADAM)
+ *      (still 11) + CODAE_RM_*, codae_retrieval_metrics_batched: a new entry with plain arguments only, no struct, no layout or enum
+ *      change
  * The binding must refuse a library whose codae_abi_version() differs and must check its own struct sizes against
  * codae_struct_sizes() at load (mui-deepautoencoder_amd/codae/hip/__init__.py does both). */
 #define CODAE_ABI_VERSION 11
@@ -943,6 +945,44 @@ int codae_complete_topk(const float* pred, int32_t B, int32_t io, int32_t n_slot
                         int32_t n_cand, const int32_t* cand_count, const int32_t* exclude, const int32_t* cand_pos, int64_t n_obs,
                         int32_t k, float* work, int32_t chunk, void* row_state, int32_t* perm_ws, float* q_ws, void* topk_state,
                         int32_t* out_idx, float* out_score, void* stream);
+
+/* ---- Retrieval metrics: hit@k, MRR, rank error and a position histogram of a validation batch, per slot ---------------
+ * What codae_complete_topk serves, scored: modelled on it, and fed the same candidate tables.
+ * Items.  Slot c's items are rows [0, cand_count[c]) of cand [n_slots][n_cand][E] (cand_count: HOST array), cand_norm
+ * [n_slots][n_cand] their norms, cand_pos [n_slots][n_obs] the item a dataset row belongs to in slot c, or -1.  Rows holding
+ * the same bytes have already been folded into one item by whoever built the tables (or not: then an item is a row).
+ * Query pairs.  (b, c) is a pair iff mask_table[id_b][c E] == 0 (id_b = mask_id[b] or mask_to_use[row_idx[b] * nb_run + run], as
+ * codae_batch), presence[row_idx[b]][c] != 0 (presence uint8 [n_obs][n_slots], NULL = every slot of every row) and the slot has a
+ * competitor.  EVERY blanked slot the row has is a pair: a mask that blanks two slots gives two.
+ * Scores.  own = cos(pred[b][cE:(c+1)E], inventory[c][row_idx[b]]), s_j the same cosine against item j (the GEMM's dot product
+ * over |q| max(|v_j|, 1e-8)), both norms clamped at 1e-8; fp32.
+ * Position.  Competitors: every item of slot c but the one row_idx[b] belongs to (cand_pos >= 0), n of them;
+ * beaten = #{competitors: own > s_j}; p = 1 + n - beaten in [1, n + 1].  Ties and NaN on either side count against the model.
+ * acc: double [n_slots][CODAE_RM_STRIDE], ADDED to (the caller zeroes it; it accumulates over the batches of an epoch):
+ *   [CODAE_RM_PAIRS] pairs   [CODAE_RM_RRE] sum (p - 1) / n   [CODAE_RM_RR] sum 1 / p
+ *   [CODAE_RM_HIT + i] #{p <= ks[i]}, i < n_ks <= CODAE_RM_MAX_KS (ks: HOST array, ascending positive ints)
+ *   [CODAE_RM_HIST + i] #{floor(log2 p) == i}, i < 32
+ * Counts are exact integers; the two sums are added per slot by one workgroup in a fixed order: the same bits every run, no
+ * float atomics, no host synchronisation.
+ * Three kernels: prepare (one wave per batch row; the pairs of a slot compacted with one atomic per slot and workgroup), per
+ * slot and chunk of items gemm_f32 over the slot's pairs only (row count on the device) followed by the compare-and-count pass
+ * (every score read once with 16-byte loads: chunk % 4 == 0, n_cand % 4 == 0, work and cand_norm 16-byte aligned), then one
+ * finish workgroup per slot.
+ * Workspaces: work B * chunk floats; pair_state 16 * n_slots * B bytes; perm_ws (n_slots * B + n_slots) int32; q_ws B * E floats. */
+#define CODAE_RM_PAIRS 0
+#define CODAE_RM_RRE 1
+#define CODAE_RM_RR 2
+#define CODAE_RM_HIT 3
+#define CODAE_RM_MAX_KS 8
+#define CODAE_RM_HIST 16
+#define CODAE_RM_STRIDE 48
+int codae_retrieval_metrics_batched(const float* pred, int32_t B, int32_t io, int32_t n_slots, int32_t E, const int32_t* row_idx,
+                                    const int32_t* mask_id, const int32_t* mask_to_use, int32_t nb_run, int32_t run,
+                                    const uint8_t* mask_table, const uint8_t* presence, const float* inventory,
+                                    const float* inventory_norm, int64_t n_obs, const float* cand, const float* cand_norm,
+                                    int32_t n_cand, const int32_t* cand_count, const int32_t* cand_pos, const int32_t* ks, int32_t n_ks,
+                                    float* work, int32_t chunk, void* pair_state, int32_t* perm_ws, float* q_ws, double* acc,
+                                    void* stream);
 
 /* ---- GEMM primitives (exported for kernel-level parity tests / benchmarks) - */
 /* y[M][N] = act(x[M][K] . W[N][K]^T + b[N]), fp32 in / fp32 out (the parity engine's GEMM: CODAE_PREC_F32 above) */

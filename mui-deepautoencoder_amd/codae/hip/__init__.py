@@ -29,6 +29,8 @@ OPT_ADAM, OPT_ADAMW, OPT_SGD = 0, 1, 2
 SCHED_CONSTANT, SCHED_COSINE, SCHED_LINEAR, SCHED_STEP = 0, 1, 2, 3
 # CODAE_AVG_* of include/codae_hip.h: the average of the iterates the update keeps (codae.tool.WeightAverage builds the struct)
 AVG_OFF, AVG_EMA, AVG_SWA = 0, 1, 2
+# CODAE_RM_* of include/codae_hip.h: the fields of one slot's block of retrieval-metric sums (codae.tool.RetrievalMetrics reads them)
+RM_PAIRS, RM_RRE, RM_RR, RM_HIT, RM_MAX_KS, RM_HIST, RM_STRIDE = 0, 1, 2, 3, 8, 16, 48
 KERNEL_CLASSES = ("gemm_fwd", "gemm_dgrad", "gemm_wgrad", "loss", "gather", "sumsq", "adam", "slab_reduce", "chain",
                   "bias_finish", "dropout")
 
@@ -204,6 +206,8 @@ PROTOTYPES = {
     "codae_topk_finish": (C.c_int, [_P, _I32, _I32, _P, _P, _P, _P]),
     "codae_complete_topk": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _I32, _P, _P, _P, _I64,
                                       _I32, _P, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "codae_retrieval_metrics_batched": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _I64, _P, _P, _I32, _P,
+                                                  _P, _P, _I32, _P, _I32, _P, _P, _P, _P, _P]),
     "codae_step_path": (C.c_int, [_P, _P, _I32]),
     "codae_linear_f32": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _P]),
     "codae_dgrad_f32": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P]),

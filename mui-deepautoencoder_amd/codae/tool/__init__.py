@@ -18,7 +18,8 @@ _PUBLIC = {
     optimizer: ("Optimizer", "LRSchedule", "optimizer_from_config"),   # what the update does: AdamW / SGD / AMSGrad, lr schedule
     average: ("WeightAverage", "weight_average_from_config"),   # an EMA / SWA of the iterates kept by the update, for evaluation
     tied: ("TiedWeights",),        # the decoder uses the encoder's transposed matrices: pairs, and the fold / mirror in torch ops
-    criteria: ("get_rmse", "RankingLoss", "ComplementRetriever", "CombinedCriterion"),
+    criteria: ("get_rmse", "RankingLoss", "ComplementRetriever", "RetrievalMetrics", "retrieval_metrics_from_config",
+               "CombinedCriterion"),
 }
 __all__ = []
 for _module, _names in _PUBLIC.items():

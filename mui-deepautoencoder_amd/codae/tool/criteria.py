@@ -2,7 +2,8 @@
 
 CombinedCriterion (the abalone loss) and RankingLoss (the validation-only rank metric) keep the
 reference's call signatures and numerics.  ComplementRetriever answers the question the rank metric scores: the k
-inventory items closest to a reconstructed slot (codae_complete_topk).  With tensors on a HIP device they run as kernels of
+inventory items closest to a reconstructed slot (codae_complete_topk); RetrievalMetrics scores that answer over a validation
+set: hit@k, MRR and a position histogram per slot, incomplete rows included (codae_retrieval_metrics_batched).  With tensors on a HIP device they run as kernels of
 libcodae_hip.so (criteria.hip: codae_combined_loss_fwd_bwd / _full, codae_ranking_loss); with host
 tensors (which upstream also accepts) they are whole-tensor torch expressions, no per-sample loops.
 """
@@ -12,6 +13,7 @@ import numpy as np
 import torch
 
 from ..hip import HipError, check as _check, current_stream as _stream, lib as _hip_lib, ptr as _ptr
+from ..hip import RM_HIST, RM_HIT, RM_MAX_KS, RM_PAIRS, RM_RR, RM_RRE, RM_STRIDE
 from .batching import get_mask_transformation
 
 
@@ -331,6 +333,255 @@ class ComplementRetriever:
             out_idx[rows, :kk] = torch.where(valid, row_id[c].long()[sel], torch.full_like(sel, -1))
             out_score[rows, :kk] = torch.where(valid, s.gather(1, sel), torch.full_like(s[:, :kk], float("-inf")))
         return out_idx, out_score
+
+
+class _OneSlot:
+    """Slot c of a dataset as a one-slot dataset: what ComplementRetriever builds one slot's candidate table from."""
+
+    def __init__(self, dataset, c):
+        self.nb_used_category, self.embedding_size = 1, int(dataset.embedding_size)
+        self.data_per_category = {0: dataset.data_per_category[c]}
+
+
+def _check_ks(ks):
+    try:
+        ks = tuple(ks)
+    except TypeError:
+        raise HipError("retrieval metrics: ks must be a sequence of ints, got %r" % (ks,))
+    if len(ks) > RM_MAX_KS:
+        raise HipError("retrieval metrics: at most %d thresholds, got %d" % (RM_MAX_KS, len(ks)))
+    for i, k in enumerate(ks):
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or int(k) < 1 or int(k) >= 2 ** 31 or (i and int(k) <= int(ks[i - 1])):
+            raise HipError("retrieval metrics: thresholds must be ascending positive ints, got %r" % (ks,))
+    return tuple(int(k) for k in ks)
+
+
+class RetrievalMetrics:
+    """hit@k, MRR, rank error and a position histogram of the reconstructed slots of a validation batch, per slot
+    (include/codae_hip.h, "Retrieval metrics": the one definition the kernels, get() and the tests' reference share).
+
+    Candidates of slot c are the validation rows that have the slot (`presence`: a SlotPresence or a uint8 [n_obs, S] table; None =
+    all of them); with `distinct` candidates holding the same bytes are one item, as ComplementRetriever folds them.  Every slot a
+    row's mask blanks and the row has is a query pair; its competitors are the slot's items without the row's own; position
+    p = 1 + competitors - #{own > s_j}, so ties and NaN count against the model.  add() runs on device tensors without a host
+    synchronisation (codae_retrieval_metrics_batched) and accumulates; total() reads the sums; get() is the whole-tensor torch form
+    for host tensors."""
+
+    def __init__(self, dataset, validation_indices, device, ks=(1, 5, 10, 50), presence=None, distinct=True):
+        self.dataset = dataset
+        self.device = device
+        self.ks = _check_ks(ks)
+        self.distinct = bool(distinct)
+        self.S, self.E = int(dataset.nb_used_category), int(dataset.embedding_size)
+        self.n_obs = int(dataset.data_per_category[0].shape[0])
+        table = getattr(presence, "table", presence)
+        if table is not None:
+            table = np.asarray(table.detach().cpu().numpy() if hasattr(table, "detach") else table)
+            if table.shape != (self.n_obs, self.S):
+                raise HipError("retrieval metrics: the presence table must be [%d, %d], got shape %r" % (self.n_obs, self.S, tuple(table.shape)))
+            table = np.ascontiguousarray(table != 0).astype(np.uint8)
+        self.presence = table
+        rows = torch.as_tensor(list(validation_indices) if not torch.is_tensor(validation_indices) else validation_indices, dtype=torch.long).reshape(-1)
+        if rows.numel() == 0 or int(rows.min()) < 0 or int(rows.max()) >= self.n_obs:
+            raise HipError("retrieval metrics: validation_indices must be a non-empty list of dataset rows in [0, %d)" % self.n_obs)
+        self.validation_indices = torch.unique(rows)
+        self.mask_table = None                 # bound by HipEmbeddingTrainer.retrieval_metrics: add() then needs no corrupter
+        self.mask_to_use = None
+        self._tables = {}
+
+    # ---- tables ---------------------------------------------------------------------------------------------------------
+    def _host_tables(self):
+        """(cand [S, n_cand, E] f32 (n_cand a multiple of 4), count [S], pos [S, n_obs] i32): per slot the table
+        ComplementRetriever._host_tables builds over the validation rows that have the slot."""
+        t = self._tables.get("host")
+        if t is not None:
+            return t
+        S, E = self.S, self.E
+        per = []
+        for c in range(S):
+            rows = self.validation_indices
+            if self.presence is not None:
+                rows = rows[torch.from_numpy(self.presence[rows.numpy(), c] != 0)]
+            if rows.numel() == 0:
+                per.append((torch.zeros((0, E), dtype=torch.float32), 0, torch.full((self.n_obs,), -1, dtype=torch.int32)))
+                continue
+            cand, count, _, pos = ComplementRetriever(_OneSlot(self.dataset, c), "cpu", candidates=rows, distinct=self.distinct)._host_tables()
+            per.append((cand[0, :count[0]], count[0], pos[0]))
+        n_cand = max(4, -(-max(p[1] for p in per) // 4) * 4)
+        cand = torch.zeros((S, n_cand, E), dtype=torch.float32)
+        for c, (Xc, n, _) in enumerate(per):
+            cand[c, :n] = Xc
+        t = (cand, [p[1] for p in per], torch.stack([p[2] for p in per]).contiguous())
+        self._tables["host"] = t
+        return t
+
+    def _device_tables(self, dev):
+        t = self._tables.get(dev)
+        if t is None:
+            cand, count, pos = self._host_tables()
+            S, E, n_cand = self.S, self.E, cand.shape[1]
+            cand_d = cand.to(dev).contiguous()
+            inv = torch.stack([self.dataset.data_per_category[c].to(dev, torch.float32) for c in range(S)]).contiguous()
+            norm = torch.empty((S, n_cand), dtype=torch.float32, device=dev)
+            inv_norm = torch.empty((S, self.n_obs), dtype=torch.float32, device=dev)
+            with torch.cuda.device(dev):
+                _check(_hip_lib().codae_row_norms(_ptr(cand_d), S * n_cand, E, _ptr(norm), _stream()))
+                _check(_hip_lib().codae_row_norms(_ptr(inv), S * self.n_obs, E, _ptr(inv_norm), _stream()))
+            t = dict(cand=cand_d, norm=norm, count=(C.c_int32 * S)(*count), pos=pos.to(dev).contiguous(), inv=inv, inv_norm=inv_norm,
+                     presence=None if self.presence is None else torch.from_numpy(self.presence).to(dev).contiguous(),
+                     ks=(C.c_int32 * max(1, len(self.ks)))(*self.ks), acc=torch.zeros((S, RM_STRIDE), dtype=torch.float64, device=dev),
+                     work=None)
+            self._tables[dev] = t
+            self._dev = dev
+        return t
+
+    # ---- device ---------------------------------------------------------------------------------------------------------
+    def add(self, prediction, row_idx, corrupter=None, run=0, chunk=4096, mask_to_use=None):
+        """Accumulate one validation batch ON THE DEVICE: `prediction` [B, S*E], `row_idx` int32 dataset rows (device), masks from
+        `corrupter`'s device tables for `run` (`mask_to_use`: an int32 [n_obs, nb_run] device table instead of
+        corrupter.mask_to_use_i32, e.g. what SlotPresence.assign_masks returns).  chunk: items per GEMM + count pass.  No host
+        synchronisation; read the sums with total()."""
+        dev = prediction.device
+        t = self._device_tables(dev)
+        S, E, n_cand = self.S, self.E, t["cand"].shape[1]
+        table = corrupter.mask_table_u8 if corrupter is not None else self.mask_table
+        m2u = mask_to_use if mask_to_use is not None else (corrupter.mask_to_use_i32 if corrupter is not None else self.mask_to_use)
+        if table is None or m2u is None:
+            raise HipError("retrieval metrics: add() needs a corrupter (or a metric bound to a trainer's mask tables)")
+        if prediction.dim() != 2 or prediction.shape[1] != S * E or prediction.shape[0] < 1 or row_idx.numel() != prediction.shape[0]:
+            raise HipError("retrieval metrics: prediction must be [B, %d] with one dataset row per batch row" % (S * E))
+        if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or int(chunk) < 1:
+            raise HipError("retrieval metrics: chunk must be a positive int, got %r" % (chunk,))
+        pred = prediction.detach()
+        if pred.dtype != torch.float32 or not pred.is_contiguous():
+            pred = pred.to(torch.float32).contiguous()
+        B = pred.shape[0]
+        chunk = min(-(-int(chunk) // 4) * 4, n_cand)             # (whole groups of four columns: the count pass loads 16 bytes)
+        if t["work"] is None or t["work"].numel() < B * chunk or t["perm"].numel() < S * B + S:
+            t["work"] = torch.empty(B * chunk, dtype=torch.float32, device=dev)
+            t["state"] = torch.empty(4 * S * B, dtype=torch.int32, device=dev)
+            t["perm"] = torch.empty(S * B + S, dtype=torch.int32, device=dev)
+            t["q"] = torch.empty(B * E, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _check(_hip_lib().codae_retrieval_metrics_batched(
+                _ptr(pred), B, S * E, S, E, _ptr(row_idx), None, _ptr(m2u), m2u.shape[1], int(run), _ptr(table), _ptr(t["presence"]),
+                _ptr(t["inv"]), _ptr(t["inv_norm"]), self.n_obs, _ptr(t["cand"]), _ptr(t["norm"]), n_cand, t["count"], _ptr(t["pos"]),
+                t["ks"], len(self.ks), _ptr(t["work"]), chunk, _ptr(t["state"]), _ptr(t["perm"]), _ptr(t["q"]), _ptr(t["acc"]), _stream()))
+        self._keep = (pred, row_idx, m2u, table)             # (alive until the stream has consumed them)
+
+    def total(self, reset=True):
+        """The metrics of the batches add()ed since the last reset (one device-to-host read): see summary()."""
+        dev = getattr(self, "_dev", None)
+        if dev is None:
+            return self.summary(np.zeros((self.S, RM_STRIDE)))
+        acc = self._tables[dev]["acc"]
+        sums = acc.cpu().numpy().copy()
+        if reset:
+            acc.zero_()
+        return self.summary(sums)
+
+    def last_positions(self):
+        """int64 [S, B] on the host: the position p of every query pair of the LAST add() (0 where (b, c) is no pair), read from
+        the kernels' pair state.  Synchronises: for analysis ("which rows missed") and tests, not for the sweep."""
+        dev = getattr(self, "_dev", None)
+        if dev is None or getattr(self, "_keep", None) is None:
+            raise HipError("retrieval metrics: last_positions() needs an add() first")
+        t, S, B = self._tables[dev], self.S, self._keep[0].shape[0]
+        st = t["state"][:4 * S * B].cpu().view(S, B, 4).long()
+        self_col, beaten = st[..., 2], st[..., 3]
+        n = torch.tensor(list(t["count"]), dtype=torch.long)[:, None] - (self_col >= 0).long()
+        p = 1 + n - beaten
+        p[(self_col == -2) | (n < 1)] = 0
+        return p
+
+    # ---- the sums as metrics --------------------------------------------------------------------------------------------
+    def _one(self, s):
+        pairs = float(s[RM_PAIRS])
+        mean = (lambda v: float(v) / pairs) if pairs > 0 else (lambda v: float("nan"))
+        out = {"pairs": int(round(pairs)), "rre": mean(s[RM_RRE]), "mrr": mean(s[RM_RR])}
+        for i, k in enumerate(self.ks):
+            out["hit@%d" % k] = mean(s[RM_HIT + i])
+        # the bucket [2^i, 2^(i+1)) of positions that holds the median pair (None without pairs)
+        cum = np.cumsum(s[RM_HIST:RM_HIST + 32])
+        out["median_position_bucket"] = int(np.searchsorted(cum, pairs / 2.0)) if pairs > 0 else None
+        return out
+
+    def summary(self, sums):
+        """{pairs, rre, mrr, hit@<k>.. (means over the pairs), median_position_bucket, per_slot: [the same per slot], sums: the raw
+        float64 [S, RM_STRIDE] block} of a block of sums."""
+        sums = np.asarray(sums, dtype=np.float64).reshape(self.S, RM_STRIDE)
+        out = self._one(sums.sum(axis=0))
+        out["per_slot"] = [self._one(sums[c]) for c in range(self.S)]
+        out["sums"] = sums
+        return out
+
+    # ---- host -----------------------------------------------------------------------------------------------------------
+    def get(self, prediction, fmask_or_mask_ids, indices, mask_table=None):
+        """The same definition for HOST tensors, in whole-tensor torch ops (float64 cosines rounded to fp32, then compared):
+        `fmask_or_mask_ids` is the float mask [B, S*E] of the batch (0 = blanked) or integer mask ids [B] into `mask_table`
+        ([n_masks, S*E], 0 = blanked; default: the table the metric is bound to); `indices` the dataset rows.  Returns summary()
+        of this batch alone; nothing is accumulated."""
+        S, E = self.S, self.E
+        cand, count, pos = self._host_tables()
+        pred = prediction.detach().to("cpu")
+        idx = torch.as_tensor(list(indices) if not torch.is_tensor(indices) else indices).to("cpu", torch.long).reshape(-1)
+        m = fmask_or_mask_ids if torch.is_tensor(fmask_or_mask_ids) else torch.as_tensor(np.asarray(fmask_or_mask_ids))
+        m = m.detach().to("cpu")
+        if m.dim() == 1:
+            table = mask_table if mask_table is not None else self.mask_table
+            if table is None:
+                raise HipError("retrieval metrics: mask ids need a mask table")
+            m = torch.as_tensor(table).detach().to("cpu")[m.long()]
+        if pred.dim() != 2 or pred.shape[1] != S * E or m.shape != pred.shape or idx.numel() != pred.shape[0]:
+            raise HipError("retrieval metrics: prediction and mask must be [B, %d] with one dataset row per batch row" % (S * E))
+        blank = m[:, ::E] == 0                                            # [B, S]
+        if self.presence is not None:
+            blank = blank & torch.from_numpy(self.presence[idx.numpy()] != 0)
+        sums = np.zeros((S, RM_STRIDE), dtype=np.float64)
+        for c in range(S):
+            nc = count[c]
+            rows = blank[:, c].nonzero(as_tuple=True)[0]
+            if nc == 0 or rows.numel() == 0:
+                continue
+            V = cand[c, :nc].double()
+            q = pred[rows, c * E:(c + 1) * E].double()
+            own_v = self.dataset.data_per_category[c].detach().to("cpu")[idx[rows]].double()
+            qn = q.norm(dim=1).clamp_min(1e-8)
+            s = ((q @ V.t()) / (qn[:, None] * V.norm(dim=1).clamp_min(1e-8)[None, :])).float()
+            own = ((q * own_v).sum(dim=1) / (qn * own_v.norm(dim=1).clamp_min(1e-8))).float()
+            beats = own[:, None] > s                                      # (a NaN on either side: False)
+            self_col = pos[c, idx[rows]].long()
+            mine = (self_col >= 0).nonzero(as_tuple=True)[0]
+            beats[mine, self_col[mine]] = False                           # the own item is skipped by position
+            n = nc - (self_col >= 0).long()
+            keep = n >= 1
+            n, p = n[keep].double(), (1 + n - beats.sum(dim=1))[keep]
+            sums[c, RM_PAIRS] = p.numel()
+            sums[c, RM_RRE] = float(((p.double() - 1) / n).sum())
+            sums[c, RM_RR] = float((1.0 / p.double()).sum())
+            for i, k in enumerate(self.ks):
+                sums[c, RM_HIT + i] = int((p <= k).sum())
+            if p.numel():
+                sums[c, RM_HIST:RM_HIST + 32] = np.bincount(np.floor(np.log2(p.numpy().astype(np.float64))).astype(np.int64), minlength=32)[:32]
+        return self.summary(sums)
+
+
+def retrieval_metrics_from_config(block):
+    """The `HIP: RETRIEVAL_METRICS:` block of the embedding script's config: {K: [1, 10, 50], DISTINCT: true}.  None -> None (the
+    script then runs, logs and writes exactly what it does without the key); else the keyword arguments of RetrievalMetrics /
+    HipEmbeddingTrainer.retrieval_metrics: {"ks": (..), "distinct": bool}."""
+    if block is None:
+        return None
+    if not isinstance(block, dict):
+        raise HipError("RETRIEVAL_METRICS must be a mapping, got %r" % (block,))
+    known = {"K", "DISTINCT"}
+    extra = sorted(set(map(str, block)) - known)
+    if extra:
+        raise HipError("RETRIEVAL_METRICS: unknown key(s) %s (known: %s)" % (", ".join(extra), ", ".join(sorted(known))))
+    distinct = block.get("DISTINCT", True)
+    if not isinstance(distinct, bool):
+        raise HipError("RETRIEVAL_METRICS: DISTINCT must be true or false, got %r" % (distinct,))
+    return {"ks": _check_ks(block.get("K", (1, 10, 50))), "distinct": distinct}
 
 
 class CombinedCriterion:

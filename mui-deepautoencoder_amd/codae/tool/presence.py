@@ -13,7 +13,8 @@ factor for ReconstructionLoss.loss(weight=...).  (A weight multiplies: with the 
 finite - ConcatenatedEmbeddingDataset(keep_incomplete=True) stores zeros there.)  `assign_masks` reorders a Corrupter's mask
 assignment so that every run blanks a slot the row actually has.
 
-Not covered: renormalising by present counts, RankingLoss on incomplete rows, the mixed-variable (abalone) path.
+Not covered: renormalising by present counts, the mixed-variable (abalone) path.  RankingLoss itself ranks complete rows only;
+codae.tool.RetrievalMetrics(presence=...) ranks every validation row among the rows that have the slot.
 """
 import numpy as np
 

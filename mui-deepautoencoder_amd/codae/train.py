@@ -734,6 +734,19 @@ class HipEmbeddingTrainer:
         # the blanked slot reaches the kernels through the same mask table as the forward (codae_complete_topk's mask route)
         return ret._device_topk(y, int(k), idx if exclude_self else None, int(chunk), mask_id=mask_id, mask_table=table)
 
+    def retrieval_metrics(self, validation_indices, ks=(1, 5, 10, 50), distinct=True):
+        """A tool.RetrievalMetrics over the resident data, bound to this trainer's presence table, mask table and mask_to_use:
+        its add(y, row_idx, run=0) takes the output of eval_batch(row_idx, run, want_y=True) and needs nothing else.  hit@k, MRR
+        and the position histogram of every blanked slot a validation row has, incomplete rows included."""
+        from .tool.criteria import RetrievalMetrics
+        if self.mask_table is None or self.mask_to_use is None:
+            raise HipError("retrieval_metrics(): the trainer has no mask tables")
+        S, E = self._slots()
+        rm = RetrievalMetrics(_ResidentInventory(self.data, S, E), validation_indices, self.device, ks=ks,
+                              presence=self.presence, distinct=distinct)
+        rm.mask_table, rm.mask_to_use = self.mask_table, self.mask_to_use
+        return rm
+
     def epoch_sums(self, reset=True, reduce=True):
         """(sum (x-y)^2, sum (1-fmask)(x-y)^2) accumulated since the last reset (summed over the
         ranks when `reduce`)."""

@@ -548,6 +548,168 @@ int topk_merge(const float* scores, int64_t ld, int rows, const int32_t* rows_de
 
 constexpr int TOPK_KMAX = 256;
 
+// ---- validation retrieval metrics: hit@k, MRR, rank error and a position histogram per slot ------------------------------
+// (include/codae_hip.h, "Retrieval metrics".)  A query pair (b, c) is a batch row b and a slot c that its mask blanks and its
+// dataset row has.  Its competitors are the items of slot c's candidate table (duplicates already folded into one item) except
+// the item the row itself belongs to; position = 1 + competitors - beaten.  State [S][B], indexed by the BATCH row so that the
+// finish pass adds the pairs of a slot in a fixed order whatever order the compaction handed the rows to the GEMM in.
+struct MetricPair { float qn; float own; int self_col; int beaten; };      // self_col: candidate position of the own item, -1 none, -2 no pair
+constexpr int RM_NO_PAIR = -2;
+constexpr int RM_PREP_ROWS = 16;         // batch rows per workgroup of the prepare pass (four per wave): one counter update per slot
+constexpr int RM_MAX_SLOTS = 128;
+constexpr int RM_VEC = 4;                // 16-byte loads in flight per lane of the count pass
+constexpr int RM_SEG = 64 * 4 * RM_VEC * 2;      // score columns per wave: two sweeps of 64 lanes x RM_VEC x 4 columns
+struct MetricKs { int n; int k[CODAE_RM_MAX_KS]; };
+
+// one wave per batch row: which slots are query pairs (mask table and presence byte, lanes over slots), then |q| and the own
+// similarity of each of them (lanes over E).  The workgroup's rows take their places in every slot's compacted list with ONE
+// atomic per slot and workgroup (flags in LDS, counted by one thread per slot).
+__global__ __launch_bounds__(NT) void metrics_prep_kernel(const float* __restrict__ pred, const int32_t* __restrict__ row_idx,
+                                                          const int32_t* __restrict__ mask_id, const int32_t* __restrict__ mask_to_use,
+                                                          int nb_run, int run, const uint8_t* __restrict__ mask_table,
+                                                          const uint8_t* __restrict__ presence, int B, int io, int S, int E,
+                                                          const float* __restrict__ inv, const float* __restrict__ inv_norm, int64_t n_obs,
+                                                          const int32_t* __restrict__ cand_pos, MetricPair* __restrict__ state,
+                                                          int32_t* __restrict__ perm, int32_t* __restrict__ counts) {
+    __shared__ uint8_t flag[RM_PREP_ROWS][RM_MAX_SLOTS];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int row0 = blockIdx.x * RM_PREP_ROWS;
+    for (int i = w; i < RM_PREP_ROWS; i += NT / 64) {
+        const int b = row0 + i;
+        const int64_t me = b < B ? row_idx[b] : -1;
+        const bool row_ok = me >= 0 && me < n_obs;                       // (wave-uniform)
+        const int id = !row_ok ? 0 : (mask_id ? mask_id[b] : mask_to_use[me * nb_run + run]);
+        for (int c0 = 0; c0 < S; c0 += 64) {
+            const int c = c0 + lane;
+            bool q = false;
+            if (row_ok && c < S)
+                q = mask_table[(int64_t)id * io + (int64_t)c * E] == 0 && (presence == nullptr || presence[me * S + c] != 0);
+            if (c < S) {
+                flag[i][c] = q ? 1 : 0;
+                if (b < B && !q) { MetricPair o; o.qn = 1.f; o.own = 0.f; o.self_col = RM_NO_PAIR; o.beaten = 0; state[(int64_t)c * B + b] = o; }
+            }
+            uint64_t m = __ballot(q);
+            while (m != 0) {                                             // (wave-uniform: at most nb_missing turns)
+                const int cc = c0 + __builtin_ctzll(m);
+                m &= m - 1;
+                const float* qv = pred + (int64_t)b * io + (int64_t)cc * E;
+                const float* r = inv + ((int64_t)cc * n_obs + me) * E;
+                float sq = 0.f, d = 0.f;
+                for (int x = lane; x < E; x += 64) { const float v = qv[x]; sq += v * v; d += v * r[x]; }
+                sq = wave_sum_f(sq); d = wave_sum_f(d);
+                if (lane == 0) {
+                    MetricPair o;
+                    o.qn = fmaxf(sqrtf(sq), 1e-8f);
+                    o.own = d / (o.qn * fmaxf(inv_norm[(int64_t)cc * n_obs + me], 1e-8f));
+                    o.self_col = cand_pos[(int64_t)cc * n_obs + me];     // (-1: the row is no candidate of this slot)
+                    o.beaten = 0;
+                    state[(int64_t)cc * B + b] = o;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < S; c += NT) {
+        int cnt = 0;
+        for (int i = 0; i < RM_PREP_ROWS; ++i) cnt += flag[i][c];
+        if (cnt == 0) continue;
+        int k = atomicAdd(&counts[c], cnt);          // (integer: which GEMM row a pair lands on changes none of its bits)
+        for (int i = 0; i < RM_PREP_ROWS; ++i)
+            if (flag[i][c]) perm[(int64_t)c * B + k++] = row0 + i;
+    }
+}
+
+// The compare-and-count pass over one chunk of slot c's score block: wave (k, segment) takes RM_SEG columns of compact row
+// k < counts[c].  Every score is read once, as 16-byte loads, RM_VEC of them issued before the first compare; one comparison
+// and one skip-by-position test per element (s = dot / (|q| max(|v|, 1e-8)), as rank_count_kernel; a NaN on either side
+// counts nothing); the n % 4 ragged columns go through scalar code; a wave reduction, then one integer add per wave.
+__device__ __forceinline__ int metrics_beats(float own, float qn, float dot, float nrm, int j, int skip) {
+    return (int)(j != skip) & (int)(own > dot / (qn * fmaxf(nrm, 1e-8f)));       // (no short circuit: no branch per element)
+}
+__global__ __launch_bounds__(NT) void metrics_count_kernel(const float* __restrict__ dots, int64_t ld, int B, int n, int c, int v0,
+                                                           const float* __restrict__ col_norm, MetricPair* __restrict__ state,
+                                                           const int32_t* __restrict__ perm, const int32_t* __restrict__ counts) {
+    const int lane = threadIdx.x & 63;
+    const int k = blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
+    if (k >= counts[c]) return;
+    MetricPair* st = state + (int64_t)c * B + perm[(int64_t)c * B + k];
+    const float own = st->own, qn = st->qn;
+    const int skip = st->self_col - v0;
+    const float* d = dots + (int64_t)k * ld;
+    const int j0 = blockIdx.y * RM_SEG;
+    const int j1 = min(j0 + RM_SEG, n);
+    const int jv = min(j1, n & ~3);                  // (a multiple of 4: whole 16-byte groups below it)
+    int cnt = 0;
+    int jw = j0;                                     // (wave-uniform)
+    for (; jw + 64 * 4 * RM_VEC <= jv; jw += 64 * 4 * RM_VEC) {      // whole sweeps: every load in range, all issued before the first compare
+        float4 v[RM_VEC], nr[RM_VEC];
+#pragma unroll
+        for (int u = 0; u < RM_VEC; ++u) {
+            const int jj = jw + u * 256 + 4 * lane;
+            v[u] = *reinterpret_cast<const float4*>(d + jj);
+            nr[u] = *reinterpret_cast<const float4*>(col_norm + jj);
+        }
+#pragma unroll
+        for (int u = 0; u < RM_VEC; ++u) {
+            const int jj = jw + u * 256 + 4 * lane;
+            cnt += metrics_beats(own, qn, v[u].x, nr[u].x, jj, skip) + metrics_beats(own, qn, v[u].y, nr[u].y, jj + 1, skip) +
+                   metrics_beats(own, qn, v[u].z, nr[u].z, jj + 2, skip) + metrics_beats(own, qn, v[u].w, nr[u].w, jj + 3, skip);
+        }
+    }
+    for (int jj = jw + 4 * lane; jj < jv; jj += 256) {               // the rest of the segment, one 16-byte group per lane and turn
+        const float4 v = *reinterpret_cast<const float4*>(d + jj);
+        const float4 nr = *reinterpret_cast<const float4*>(col_norm + jj);
+        cnt += metrics_beats(own, qn, v.x, nr.x, jj, skip) + metrics_beats(own, qn, v.y, nr.y, jj + 1, skip) +
+               metrics_beats(own, qn, v.z, nr.z, jj + 2, skip) + metrics_beats(own, qn, v.w, nr.w, jj + 3, skip);
+    }
+    if (j1 == n) {                                   // the last segment also takes the n % 4 ragged columns, one per lane
+        const int j = (n & ~3) + lane;
+        if (j < n) cnt += metrics_beats(own, qn, d[j], col_norm[j], j, skip);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+    if (lane == 0 && cnt != 0) atomicAdd(&st->beaten, cnt);
+}
+
+// One workgroup for one slot: position, rank error and reciprocal rank of every pair of the slot, added into the slot's block.
+// Counts are integers (LDS atomics: exact in any order); the two fp64 sums are per-thread partials over rows t, t + NT, ...
+// folded by a tree - a fixed order, the same bits every run.  nc: the slot's item count.
+__global__ __launch_bounds__(NT) void metrics_finish_kernel(const MetricPair* __restrict__ st, int B, int nc, MetricKs ks,
+                                                            double* __restrict__ acc) {
+    __shared__ double red[2][NT];
+    __shared__ unsigned int cnt[CODAE_RM_STRIDE];
+    const int t = threadIdx.x;
+    if (t < CODAE_RM_STRIDE) cnt[t] = 0;
+    __syncthreads();
+    double rre = 0.0, rr = 0.0;
+    for (int b = t; b < B; b += NT) {
+        const MetricPair p = st[b];
+        if (p.self_col == RM_NO_PAIR) continue;
+        const int n = nc - (p.self_col >= 0 ? 1 : 0);
+        if (n < 1) continue;                         // (no competitor: not a query pair)
+        const int beaten = p.beaten < 0 ? 0 : (p.beaten > n ? n : p.beaten);
+        const int pos = 1 + n - beaten;
+        rre += (double)(pos - 1) / (double)n;
+        rr += 1.0 / (double)pos;
+        atomicAdd(&cnt[CODAE_RM_PAIRS], 1u);
+        for (int i = 0; i < ks.n; ++i)
+            if (pos <= ks.k[i]) atomicAdd(&cnt[CODAE_RM_HIT + i], 1u);
+        atomicAdd(&cnt[CODAE_RM_HIST + 31 - __builtin_clz((unsigned)pos)], 1u);
+    }
+    red[0][t] = rre; red[1][t] = rr;
+    __syncthreads();
+    for (int o = NT / 2; o > 0; o >>= 1) {
+        if (t < o) { red[0][t] += red[0][t + o]; red[1][t] += red[1][t + o]; }
+        __syncthreads();
+    }
+    if (t < CODAE_RM_STRIDE) {
+        double add = (double)cnt[t];
+        if (t == CODAE_RM_RRE) add = red[0][0];
+        if (t == CODAE_RM_RR) add = red[1][0];
+        acc[t] += add;
+    }
+}
+
 }  // namespace
 }  // namespace codae
 
@@ -749,6 +911,67 @@ int codae_complete_topk(const float* pred, int32_t B, int32_t io, int32_t n_slot
     hipLaunchKernelGGL(topk_finish_kernel, dim3(grid_for((int64_t)B * k)), dim3(NT), 0, s, st, B, k, cand_row_id, slot_rs, n_slots, n_cand,
                        out_idx, out_score);
     CODAE_LAUNCH_CHECK();
+    return CODAE_OK;
+}
+
+int codae_retrieval_metrics_batched(const float* pred, int32_t B, int32_t io, int32_t n_slots, int32_t E, const int32_t* row_idx,
+                                    const int32_t* mask_id, const int32_t* mask_to_use, int32_t nb_run, int32_t run,
+                                    const uint8_t* mask_table, const uint8_t* presence, const float* inventory,
+                                    const float* inventory_norm, int64_t n_obs, const float* cand, const float* cand_norm,
+                                    int32_t n_cand, const int32_t* cand_count, const int32_t* cand_pos, const int32_t* ks, int32_t n_ks,
+                                    float* work, int32_t chunk, void* pair_state, int32_t* perm_ws, float* q_ws, double* acc,
+                                    void* stream) {
+    CODAE_REQUIRE(pred && row_idx && (mask_id || mask_to_use) && mask_table && inventory && inventory_norm && cand && cand_norm &&
+                      cand_count && cand_pos && work && pair_state && perm_ws && q_ws && acc, "retrieval_metrics: null argument");
+    CODAE_REQUIRE(B > 0 && n_slots > 0 && n_slots <= RM_MAX_SLOTS && E > 0 && io == n_slots * E && n_obs > 0 && n_cand > 0,
+                  "retrieval_metrics: bad sizes (B %d, slots %d, E %d, io %d)", B, n_slots, E, io);
+    CODAE_REQUIRE(mask_id || (nb_run > 0 && run >= 0 && run < nb_run), "retrieval_metrics: run %d outside [0, %d)", run, nb_run);
+    // 16-byte loads of the score rows and of the norms: whole groups of four columns from aligned bases
+    CODAE_REQUIRE(chunk > 0 && chunk % 4 == 0 && n_cand % 4 == 0, "retrieval_metrics: chunk %d and n_cand %d must be multiples of 4", chunk, n_cand);
+    CODAE_REQUIRE((reinterpret_cast<uintptr_t>(work) & 15) == 0 && (reinterpret_cast<uintptr_t>(cand_norm) & 15) == 0,
+                  "retrieval_metrics: work and cand_norm must be 16-byte aligned");
+    CODAE_REQUIRE(n_ks >= 0 && n_ks <= CODAE_RM_MAX_KS && (n_ks == 0 || ks), "retrieval_metrics: %d thresholds (at most %d)", n_ks, CODAE_RM_MAX_KS);
+    MetricKs mk{};
+    mk.n = n_ks;
+    for (int i = 0; i < n_ks; ++i) {
+        CODAE_REQUIRE(ks[i] >= 1 && (i == 0 || ks[i] > ks[i - 1]), "retrieval_metrics: thresholds must be ascending positive ints (ks[%d] = %d)", i, ks[i]);
+        mk.k[i] = ks[i];
+    }
+    for (int c = 0; c < n_slots; ++c)
+        CODAE_REQUIRE(cand_count[c] >= 0 && cand_count[c] <= n_cand, "retrieval_metrics: cand_count[%d] = %d outside [0, %d]", c, cand_count[c], n_cand);
+    hipStream_t s = (hipStream_t)stream;
+    MetricPair* st = reinterpret_cast<MetricPair*>(pair_state);        // [n_slots][B]
+    int32_t* perm = perm_ws;                                           // [n_slots][B]
+    int32_t* counts = perm_ws + (int64_t)n_slots * B;                  // [n_slots]
+    CODAE_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)n_slots * sizeof(int32_t), s));
+    hipLaunchKernelGGL(metrics_prep_kernel, dim3((B + RM_PREP_ROWS - 1) / RM_PREP_ROWS), dim3(NT), 0, s, pred, row_idx, mask_id, mask_to_use,
+                       nb_run, run, mask_table, presence, B, io, n_slots, E, inventory, inventory_norm, n_obs, cand_pos, st, perm, counts);
+    CODAE_LAUNCH_CHECK();
+    // per slot: its pairs' queries gathered, one fp32 GEMM per chunk of items over those rows only (gemm_f32 with the row count on
+    // the device, exactly as codae_complete_topk), the count pass over the chunk it wrote, then the slot's finish
+    const int rows_grid = (B + NT / 64 - 1) / (NT / 64);
+    for (int c = 0; c < n_slots; ++c) {
+        const int nc = cand_count[c];
+        if (nc == 0) continue;                        // (no item: no competitor, no pair)
+        hipLaunchKernelGGL(rank_gather_q_kernel, dim3(grid_for((int64_t)B * E / 4)), dim3(NT), 0, s, pred, io, E, B, c, perm, counts, q_ws);
+        CODAE_LAUNCH_CHECK();
+        for (int v0 = 0; v0 < nc; v0 += chunk) {
+            const int n = nc - v0 < chunk ? nc - v0 : chunk;
+            GemmF32 g{};
+            g.A = q_ws; g.a_rs = E; g.a_ks = 1;
+            g.B = cand + ((int64_t)c * n_cand + v0) * E; g.b_rs = E; g.b_ks = 1;
+            g.C = work; g.ldc = chunk;
+            g.M = B; g.N = n; g.K = E;
+            g.m_dev = counts + c;
+            int rc = gemm_f32(g, s);
+            if (rc) return rc;
+            hipLaunchKernelGGL(metrics_count_kernel, dim3(rows_grid, (n + RM_SEG - 1) / RM_SEG), dim3(NT), 0, s, work, (int64_t)chunk, B, n, c,
+                               v0, cand_norm + (int64_t)c * n_cand + v0, st, perm, counts);
+            CODAE_LAUNCH_CHECK();
+        }
+        hipLaunchKernelGGL(metrics_finish_kernel, dim3(1), dim3(NT), 0, s, st + (int64_t)c * B, B, nc, mk, acc + (int64_t)c * CODAE_RM_STRIDE);
+        CODAE_LAUNCH_CHECK();
+    }
     return CODAE_OK;
 }
 

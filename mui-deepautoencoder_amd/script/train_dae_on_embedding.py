@@ -206,6 +206,14 @@ def main():
         is_ranked = torch.zeros(dataset.nb_observation, dtype=torch.bool, device=device)
         if rank_indices:
             is_ranked[torch.as_tensor(rank_indices, dtype=torch.long, device=device)] = True
+    # HIP: RETRIEVAL_METRICS: {K: [1, 10, 50], DISTINCT: true} (build-only key): hit@k and MRR of every blanked slot of EVERY
+    # validation row - the incomplete ones included, each ranked among the validation rows that have the slot - beside the ranking
+    # error; absent = nothing is added to the sweep, the log or book.json
+    from codae.tool import retrieval_metrics_from_config
+    rm_args = retrieval_metrics_from_config(config.get("HIP", {}).get("RETRIEVAL_METRICS"))
+    retrieval = trainer.retrieval_metrics(validation_indices, **rm_args) if rm_args is not None else None
+    if retrieval is not None:
+        book.update({k: [] for k in ["mrr"] + ["hit@%d" % k for k in retrieval.ks] + ["ranked_pairs"]})
 
     for epoch in range(epochs):
         log.info("===================================================== EPOCH = %d" % epoch)
@@ -235,6 +243,8 @@ def main():
                 keep = is_ranked[idx.long()]
                 if bool(keep.any()):
                     ranking_loss.add(y[keep].contiguous(), idx[keep].contiguous(), corrupter, run=0)
+            if retrieval is not None:
+                retrieval.add(y, idx, run=0)
         rl = ranking_loss.total() if (is_ranked is None or rank_indices) else 0.0     # (no complete validation row: nothing was ranked)
         sq, sqp = trainer.epoch_sums(reduce=False)      # every rank evaluates the whole validation set
         book["fvl"].append(np.sqrt(sq / den["validation"][0]))
@@ -243,6 +253,15 @@ def main():
         log.info("VALIDATION FULL ERROR    = %7f" % book["fvl"][-1])
         log.info("VALIDATION PARTIAL ERROR = %7f" % book["pvl"][-1])
         log.info("VALIDATION RANKING ERROR = %7f" % book["rl"][-1])
+        if retrieval is not None:
+            rm = retrieval.total()
+            for k in retrieval.ks:
+                book["hit@%d" % k].append(rm["hit@%d" % k])
+                log.info("VALIDATION HIT@%-4d       = %7f" % (k, rm["hit@%d" % k]))
+            book["mrr"].append(rm["mrr"])
+            book["ranked_pairs"].append(rm["pairs"])
+            log.info("VALIDATION MRR           = %7f" % rm["mrr"])
+            log.info("VALIDATION RANKED PAIRS  = %d" % rm["pairs"])
     log.info("TRAINING HAS ENDED.")
 
     if rank == 0:
