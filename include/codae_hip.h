@@ -67,6 +67,8 @@ extern "C" {
  *      layout or enum change; the average rides in the update's launch (CODAE_K_ADAM)
  *      (still 11) + CODAE_RM_*, codae_retrieval_metrics_batched: a new entry with plain arguments only, no struct, no layout or enum
  *      change
+ *      (still 11) - the copy-out of the stamped GEMM build's timeline: an entry with no caller outside tools/ was removed; no
+ *      layout or enum change
  * The binding must refuse a library whose codae_abi_version() differs and must check its own struct sizes against
  * codae_struct_sizes() at load (mui-deepautoencoder_amd/codae/hip/__init__.py does both). */
 #define CODAE_ABI_VERSION 11
@@ -516,7 +518,7 @@ int codae_abi_version(void);
  * engine read shadow_wt past the caller's struct). */
 #define CODAE_N_STRUCTS 7
 int codae_struct_sizes(int32_t* out, int32_t capacity);
-/* The CODAE_* tuning / ablation environment variables (CODAE_GEMM_TILE, CODAE_SINGLE_STREAM, CODAE_NO_FUSED_LOSS ...)
+/* The CODAE_* tuning environment variables (CODAE_GEMM_TILE, CODAE_SINGLE_STREAM, CODAE_NO_FUSED_LOSS ...)
  * are read when the library is first used and at every codae_create, never on the launch path; a caller that
  * changes one and wants the stand-alone GEMM entry points to see it calls this. */
 int codae_reload_env(void);
@@ -1014,19 +1016,15 @@ int codae_linear_act_bf16(const void* x, const void* W, const float* b, void* y,
                           int32_t K, int32_t act, float p0, float p1, float p2, void* stream);
 int codae_dgrad_act_bf16(const void* dy, const void* W, const void* act_src, void* dx, float* db_prev, float* db_ws,
                          int32_t M, int32_t N, int32_t K, int32_t act, float p0, float p1, float p2, void* stream);
-/* Tuning aid: with CODAE_GEMM_DBG=8 the forward-form bf16 GEMM stamps a 100 MHz wall clock per workgroup (entry, first
- * MFMA phase, end of K loop, stores issued, stores retired, XCC id: 6 words each); this copies the first n_wg records to
- * host memory (synchronises the device). */
-int codae_debug_gemm_timeline(uint64_t* host_out, int32_t n_wg);
 /* Host-only query (no HIP call, no device needed): which kernel a bf16 GEMM launch with these descriptor facts takes under the
  * CODAE_* variables as last read, and the counts the engine derives from that choice.  It pins the dispatch in tests.
  *   desc[13]: a_mode, b_mode (0 = k contiguous, 1 = k strided), c_f32, M, N, K, split_k, act (CODAE_ACT_*), fused loss on / off,
  *             backward epilogue (mask source or column sums) yes / no, coscheduled, store_policy (0 plain, 1 write-through,
  *             -1 by the output's size as the engine sets it), ldc
- *   out[CODAE_GEMM_PLAN_FIELDS]: family (0 one-barrier kernel, 1 phase-pipelined, 2 its timing-ablation builds), bm, bn, stages
+ *   out[CODAE_GEMM_PLAN_FIELDS]: family (0 one-barrier kernel, 1 phase-pipelined), bm, bn, stages
  *             (one-barrier: 2 / 4), loader layout (pipelined: 1 / 6 = 256 x 192 with every wave / one wave per SIMD loading,
- *             7 = 128 x 192), epilogue (1 forward, 2 backward, 3 fused loss, 0 decided at run time), phase schedule (0 pinned, 64 the
- *             compiler's, else the ablation build's number), generic-activation instantiation, effective store policy, tiles_m,
+ *             7 = 128 x 192), epilogue (1 forward, 2 backward, 3 fused loss, 0 fp32 output or one-barrier kernel), phase schedule (0 pinned, 64 the
+ *             compiler's), generic-activation instantiation, effective store policy, tiles_m,
  *             tiles_n, workgroups, colsum_rows, loss_parts (0 without the fused loss), takes_relu_bits (of an M x N forward-form
  *             launch)
  * capacity: room in out, >= CODAE_GEMM_PLAN_FIELDS. */

@@ -18,7 +18,7 @@
 // written as one partial row per workgroup.  Biases are staged in LDS once: inside the layer loops the only vector
 // memory operations are the ring's requests and plain stores, so nothing ever has to wait for the ring to drain.
 //
-// What bounds it (C2, tools/chain_timeline.py on the CHAIN_ABL=9 build): 3.6 us per 384 x 384 matrix and workgroup,
+// What bounds it (C2, a stamped timing build, removed): 3.6 us per 384 x 384 matrix and workgroup,
 // whatever the ring depth (10, 12, 13 units measured the same) - a CU takes its weights at ~81 GB/s: every byte is
 // written to LDS by the DMA and read back once as a fragment (without the reads: 3.1 us, 96 GB/s; without requests at
 // all: 1.5 us).  Epilogues 1.3 us per layer, prologue 8 us, 108 us in all; 64 of the 256 CUs are busy.  Not MFMA (72
@@ -28,44 +28,22 @@
 // the same lines at the same time (slower: 3.6 -> 3.9 us per matrix; L2 serves the lockstep requests better).
 #include "codae_common.h"
 
-#ifndef CHAIN_ABL
-#define CHAIN_ABL 0          // timing ablations (tools/abl): 1 no weight requests, 2 no MFMA, 3 no row stores, 9 timeline stamps
-#endif
-
 namespace codae {
 namespace {
 
 constexpr int CH_ROWS = 16;          // batch rows per workgroup = one MFMA tile
 constexpr int CH_NW = 4;             // waves: each owns width / 4 output columns
 constexpr int CH_NT = 64 * CH_NW;
-#ifdef CH_ABL_MAXW            // (ablation builds: a deeper ring needs the other LDS regions cut to one configuration)
-constexpr int CH_MAXW = CH_ABL_MAXW;
-#else
 constexpr int CH_MAXW = CODAE_CHAIN_MAX_WIDTH;
-#endif
 constexpr int CH_MAXL = CODAE_CHAIN_MAX_LAYERS;
-#ifdef CH_ABL_MROWS
-constexpr int CH_MROWS = CH_ABL_MROWS;
-#else
 constexpr int CH_MROWS = CH_MAXL;
-#endif
 constexpr int CH_MAXT = CH_MAXW / (16 * CH_NW);     // 16-column MFMA tiles per wave at the widest layer
 constexpr int CH_PITCH = CH_MAXW * 2 + 16;          // bytes per panel row: + 16 so that the 16 rows of an A fragment
                                                     // read (ds_read_b128) fall on different banks
 constexpr int CH_JJ = (CH_MAXW + CH_NT - 1) / CH_NT;   // bias staging: columns per thread
 constexpr int CH_UNIT = 2048;                       // weight unit: one 16-column tile x 64 k = 16 rows x 128 B
-#ifdef CH_ABL_RU
-constexpr int CH_RU = CH_ABL_RU;
-#else
-constexpr int CH_RU = 10;
-#endif
-//                          // units in a wave's ring (CH_RU - 1 requested ahead of the multiply)
-#ifdef CH_ABL_BIAS
-constexpr int CH_BIAS = CH_ABL_BIAS;
-#else
-constexpr int CH_BIAS = CODAE_CHAIN_MAX_BIAS;
-#endif
-//       // floats of bias staged in LDS (sum of the layers' output widths)
+constexpr int CH_RU = 10;                           // units in a wave's ring (CH_RU - 1 requested ahead of the multiply)
+constexpr int CH_BIAS = CODAE_CHAIN_MAX_BIAS;        // floats of bias staged in LDS (sum of the layers' output widths)
 
 typedef __attribute__((address_space(3))) char lds_char;
 typedef __attribute__((address_space(1))) const void gvoid;
@@ -136,10 +114,8 @@ __device__ __forceinline__ void cursor_matrix(WCursor& c, KArgs a, int w, int la
 __device__ __forceinline__ void cursor_issue(WCursor& c, KArgs a, lds_char* ring, int w, int lane) {
     const char* src = c.base + ((int64_t)(16 * c.t) * c.K + c.trip * 64) * 2;          // wave-uniform
     lds_char* dst = ring + c.slot * CH_UNIT;
-#if CHAIN_ABL != 1
     glds16(src + c.off0, dst);
     glds16(src + c.off1, dst + 1024);
-#endif
     c.slot = c.slot + 1 == CH_RU ? 0 : c.slot + 1;
     if (++c.t == c.T) {
         c.t = 0;
@@ -172,16 +148,10 @@ __device__ __forceinline__ void chain_matmul_t(f32x4 (&acc)[CH_MAXT], const lds_
             wait_vmcnt<2 * (CH_RU - 2)>();
             const int nslot = cslot + 1 == CH_RU ? 0 : cslot + 1;
             const lds_char* nu = ring + nslot * CH_UNIT;
-#ifdef CH_ABL_NOREAD
-            const s16x8 bn0 = bc[1], bn1 = bc[0]; (void)nu; (void)roff0; (void)roff1;
-#else
             const s16x8 bn0 = *reinterpret_cast<const __attribute__((address_space(3))) s16x8*>(nu + roff0);
             const s16x8 bn1 = *reinterpret_cast<const __attribute__((address_space(3))) s16x8*>(nu + roff1);
-#endif
-#if CHAIN_ABL != 2
             acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bc[0]), a0, acc[t], 0, 0, 0);
             acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bc[1]), a1, acc[t], 0, 0, 0);
-#endif
             __builtin_amdgcn_sched_barrier(0);       // the request below overwrites the slot bc came from
             cursor_issue(cur, a, ring, w, lane);
             bc[0] = bn0; bc[1] = bn1;
@@ -206,9 +176,6 @@ __device__ __forceinline__ void chain_matmul(f32x4 (&acc)[CH_MAXT], const lds_ch
 
 // panel rows -> HBM, whole rows, 16 B per lane
 __device__ __forceinline__ void panel_to_global(const lds_char* panel, bf16_t* __restrict__ dst, int row0, int rows_total, int width) {
-#if CHAIN_ABL == 3
-    return;
-#endif
     const int r = threadIdx.x >> 4;                      // 16 lanes x 16 B = 256 contiguous bytes of one row per step
     if (row0 + r >= rows_total) return;
     const lds_char* src = panel + r * CH_PITCH;
@@ -218,12 +185,6 @@ __device__ __forceinline__ void panel_to_global(const lds_char* panel, bf16_t* _
         *reinterpret_cast<uint4*>(out + c * 8) = make_uint4(v[0], v[1], v[2], v[3]);
     }
 }
-
-#if CHAIN_ABL == 9          // timeline build: workgroup 0 / thread 0 stamps the 100 MHz clock into LDS, copied out at the end
-#define CH_STAMP() do { if (blockIdx.x == 0 && threadIdx.x == 0) { stamp_s[n_stamp & 63] = wall_clock64(); ++n_stamp; } } while (0)
-#else
-#define CH_STAMP() do { } while (0)
-#endif
 
 __global__ __launch_bounds__(CH_NT, 1) void chain_step_kernel(ChainArgs a_by_value) {
     KArgs a = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
@@ -238,11 +199,6 @@ __global__ __launch_bounds__(CH_NT, 1) void chain_step_kernel(ChainArgs a_by_val
 
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#if CHAIN_ABL == 9
-    unsigned long long* stamp_s = reinterpret_cast<unsigned long long*>(mbits);       // activation 0 has no mask row
-    int n_stamp = 0;
-#endif
-    CH_STAMP();
     const int li = lane & 15, g4 = (lane >> 4) * 4;
     const int row0 = blockIdx.x * CH_ROWS;
     const int io = a->width[0];
@@ -274,7 +230,6 @@ __global__ __launch_bounds__(CH_NT, 1) void chain_step_kernel(ChainArgs a_by_val
             bv[jj][l] = 0.f;
             if (l < a->L && jj * CH_NT + (int)threadIdx.x < a->width[l + 1]) bv[jj][l] = a->bias[l][jj * CH_NT + threadIdx.x];
         }
-    CH_STAMP();
     // ---- start the weight stream: the first CH_RU units of the chain --------------------------------------------------
     lds_char* ring = smem + w * (CH_RU * CH_UNIT);
     WCursor cur;
@@ -282,7 +237,6 @@ __global__ __launch_bounds__(CH_NT, 1) void chain_step_kernel(ChainArgs a_by_val
     cursor_matrix(cur, a, w, lane);
 #pragma unroll
     for (int u = 0; u < CH_RU; ++u) cursor_issue(cur, a, ring, w, lane);
-    CH_STAMP();
     // ---- biases -> LDS (the epilogues then issue no global loads: a load's wait would also wait for the ring's requests)
 #pragma unroll
     for (int jj = 0; jj < CH_JJ; ++jj) {
@@ -295,7 +249,6 @@ __global__ __launch_bounds__(CH_NT, 1) void chain_step_kernel(ChainArgs a_by_val
             }
     }
     if (threadIdx.x < CH_ROWS) { rowinfo[2 * threadIdx.x] = src; rowinfo[2 * threadIdx.x + 1] = id; }
-    CH_STAMP();
     // ---- batch gather + slot corruption (data_tool.py:96-103, embedding_...py:226-239): x * mask (bf16) -> panel 0 and
     //      act[0]; rows past the batch are zero
     lds_barrier();
@@ -319,7 +272,6 @@ __global__ __launch_bounds__(CH_NT, 1) void chain_step_kernel(ChainArgs a_by_val
     lds_barrier();
     panel_to_global(panel[0], a->act[0], row0, a->rows, io);
 
-    CH_STAMP();
     // unit 0's fragments
     const int fr = lane & 15, fk = lane >> 4;
     s16x8 bc[2];
@@ -339,9 +291,7 @@ __global__ __launch_bounds__(CH_NT, 1) void chain_step_kernel(ChainArgs a_by_val
     for (int l = 0; l < a->L; ++l) {
         const int K = a->width[l], N = a->width[l + 1];
         const int n_tiles = N / (16 * CH_NW), n_lo = w * (N / CH_NW);
-        CH_STAMP();
         chain_matmul(acc, panel[cur_p], K, n_tiles, ring, cslot, bc, cur, a, w, lane);
-        CH_STAMP();
         const bool last = l == a->L - 1;
         lds_char* out = panel[cur_p ^ 1];
         const float* bl = bias_s + boff;
@@ -421,9 +371,7 @@ __global__ __launch_bounds__(CH_NT, 1) void chain_step_kernel(ChainArgs a_by_val
         for (int l = a->L - 1; l >= 1; --l) {
             const int K = a->width[l + 1], N = a->width[l];            // contraction over layer l's outputs, result per input
             const int n_tiles = N / (16 * CH_NW), n_lo = w * (N / CH_NW);
-            CH_STAMP();
             chain_matmul(acc, panel[cur_p], K, n_tiles, ring, cslot, bc, cur, a, w, lane);
-            CH_STAMP();
             lds_char* out = panel[cur_p ^ 1];
             const uint32_t bits = ((relu_flags >> (l - 1)) & 1u) ? mbits[l * CH_NT + threadIdx.x] : 0xffffffffu;     // [h_l > 0], from the forward
 #pragma unroll
@@ -446,14 +394,6 @@ __global__ __launch_bounds__(CH_NT, 1) void chain_step_kernel(ChainArgs a_by_val
             panel_to_global(out, a->dact[l - 1], row0, a->rows, N);
             cur_p ^= 1;
         }
-    CH_STAMP();
-#if CHAIN_ABL == 9
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        unsigned long long* o = reinterpret_cast<unsigned long long*>(a->colsum_part[0]);
-        o[0] = n_stamp;
-        for (int i = 0; i < n_stamp && i < 64; ++i) o[1 + i] = stamp_s[i];
-    }
-#endif
     wait_vmcnt<0>();            // the trailing re-requests of the ring land before the workgroup's LDS is released
 }
 

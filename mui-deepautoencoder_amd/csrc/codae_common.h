@@ -244,12 +244,11 @@ struct TileStore {
     }
 };
 
-// CODAE_* tuning / ablation variables, read ONCE (library load, codae_create, codae_reload_env): nothing on the
+// CODAE_* tuning variables, read ONCE (library load, codae_create, codae_reload_env): nothing on the
 // launch path calls getenv (round 1 did, ~30 times per step)
 struct EnvToggles {
     int gemm_tile = -1;          // CODAE_GEMM_TILE: s = 128 x 128 (0), q = 256 x 192 pipelined, every wave loads (3),
                                  // x = 256 x 192 pipelined, LDS-DMA on one wave per SIMD (6); -1 = automatic
-    int gemm_dbg = 0;            // CODAE_GEMM_DBG timing-only ablation builds of the forward form
     int wgrad_splitk = 0;        // CODAE_WGRAD_SPLITK > 0 forces the split
     int small_tile_max = 200;    // CODAE_SMALL_TILE_MAX: forward-form launches of up to this many 128 x 128 tiles run on 64 x 64 tiles
     int small_stages = 4;        // CODAE_SMALL_STAGES=2: launches that cannot fill the chip keep the 2-stage double buffer
@@ -340,7 +339,7 @@ struct GemmBf16 {
     float* colsum_part;      // [tiles_m][N] per-tile column sums of the stored values (plain stores; see GemmF32), or null
     int split_k;             // >1: fp32 partial slabs C + z*M*ldc, K range split evenly in BK units
     LossFuse loss;           // enabled: C receives dy (bf16), colsum_part the last bias gradient's partial sums
-    int dbg;                 // timing-only ablations (CODAE_GEMM_DBG): 1 no LDS-DMA, 2 no MFMA, 4 no epilogue stores
+    int : 32;                // pad: keeps the kernel-argument offsets behind it, and with them eight EPI 5 kernels' code, as they were
     // ReLU mask as one bit per element, [rows][ld_bits] bytes, bit k of byte (i, j / 8) = (stored value (i, j + k) > 0): written by a
     // forward launch (relu_bits_out), read by the data-gradient launch INSTEAD of the saved activation (relu_bits; relu_src stays
     // set for the kernels that do not take bits).  Pipelined kernels only: gemm_bf16_takes_relu_bits() says whether a launch
@@ -375,8 +374,11 @@ inline int tile_count(int M, int N, GemmTile t) { return ceil_div(M, t.bm) * cei
 // nothing else, and whoever must know a launch's tile in advance (the engine's partial-sum row counts, the 1-bit ReLU masks)
 // reads them from the same plan.
 enum { BF16_ONE_BARRIER = 0,      // gemm_bf16_kernel: one-barrier double buffer, or four stages (gemm_bf16.hip)
-       BF16_PIPELINED = 1,        // gemm_bf16_pipe_kernel: phase-pipelined (gemm_bf16_pipe.hip)
-       BF16_PIPELINED_ABL = 2     // its timing-only ablation / stamped builds (CODAE_GEMM_DBG; results wrong by design)
+       BF16_PIPELINED = 1         // gemm_bf16_pipe_kernel: phase-pipelined (gemm_bf16_pipe.hip)
+};
+// instruction schedule of the pipelined kernel's K loop (its SCHED template argument; the values are part of the kernels' symbol names)
+enum { SCHED_PINNED = 0,          // the phases pinned and ordered by hand (gemm_bf16_halftile.h)
+       SCHED_COMPILER = 64        // the compiler's own schedule (GemmBf16::coscheduled)
 };
 struct Bf16Plan {
     int family;              // BF16_*
@@ -385,8 +387,7 @@ struct Bf16Plan {
     int loader;              // pipelined: 1 = 256 x 192, every wave loads (B halves by 6 of the 8); 6 = 256 x 192, LDS-DMA on one wave per
                              // SIMD; 7 = 128 x 192 (forward form only); one-barrier: 0
     int epi;                 // 3 = fused loss (either family); pipelined bf16 output: 1 = forward, 2 = data-gradient epilogue; else 0
-    int dbg;                 // pipelined DBG template argument: 0 = pinned phases, 64 = the compiler's schedule (GemmBf16::coscheduled),
-                             // anything else = that ablation build
+    int sched;               // pipelined: SCHED_PINNED, or SCHED_COMPILER for a GemmBf16::coscheduled launch; one-barrier: 0
     int act;                 // the generic-activation instantiation (one-barrier only)
     int store_policy;        // STORE_* the launch really stores with: the descriptor's, after the ldc fallback; PLAIN wherever the
                              // kernel takes no policy
@@ -398,7 +399,7 @@ bool gemm_bf16_takes_relu_bits(int M, int N);    // forward-form bf16 launch of 
 int gemm_bf16_colsum_rows(const GemmBf16& g);   // rows of colsum_part this launch writes (= its plan's tiles along M)
 int gemm_bf16_loss_parts(const GemmBf16& g);    // workgroups of the fused-loss launch = rows of LossFuse::parts
 int gemm_bf16(const GemmBf16& g, hipStream_t s);
-int gemm_bf16_pipe(const GemmBf16& g, const Bf16Plan& plan, hipStream_t s);   // gemm_bf16_pipe.hip: the pipelined families of a plan
+int gemm_bf16_pipe(const GemmBf16& g, const Bf16Plan& plan, hipStream_t s);   // gemm_bf16_pipe.hip: the pipelined family of a plan
 int choose_split_k(int N, int K, int rows);     // gemm_bf16.hip: split-K factor of the weight gradient dW[N][K] over `rows` batch rows
 
 // several independent GEMMs (here: the weight gradients of every layer of a narrow stack) in ONE launch; tile
@@ -559,7 +560,6 @@ int launch_tie_fold(float* g, const codae_tie_pair* pairs, int n, hipStream_t s)
 int launch_tie_mirror(float* p, bf16_t* shadow, bf16_t* shadow_t, const codae_tie_pair* pairs, int n, hipStream_t s);
 int launch_transpose_bf16(const bf16_t* src, bf16_t* dst, int n, const int64_t* off, const int* rows, const int* cols,
                           hipStream_t s);
-int gemm_bf16_timeline(unsigned long long* host_out, int n_wg);   // CODAE_GEMM_DBG=8 stamps
 // sumsq != null: += sum out^2 (slot-scattered)
 // act != CODAE_ACT_NONE: the generic-activation epilogue (see GemmF32::act; relu is ignored then)
 int launch_reduce_slabs_epi(const float* slabs, int n_slabs, int64_t stride, int M, int N, float* C, int64_t ldc, const float* bias,

@@ -30,7 +30,6 @@ void env_reload() {
     if (const char* t = getenv("CODAE_GEMM_TILE")) {
         switch (t[0]) { case 's': e.gemm_tile = 0; break; case 'q': e.gemm_tile = 3; break; case 'x': e.gemm_tile = 6; break; case 'm': e.gemm_tile = 7; break; default: break; }
     }
-    if (const char* d = getenv("CODAE_GEMM_DBG")) e.gemm_dbg = atoi(d);
     if (const char* k = getenv("CODAE_WGRAD_SPLITK")) e.wgrad_splitk = atoi(k) > 0 ? atoi(k) : 0;
     if (const char* k = getenv("CODAE_GROUP_TILE")) e.group_tile = (k[0] >= '0' && k[0] <= '2') ? k[0] - '0' : -1;
     if (const char* pr = getenv("CODAE_SIDE_PRIORITY")) { e.side_priority_set = true; e.side_priority = atoi(pr); }

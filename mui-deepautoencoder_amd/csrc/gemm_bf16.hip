@@ -35,13 +35,6 @@ namespace {
 
 constexpr int BK = 64;
 
-#if defined(CODAE_DBG_5D)
-// section 5d probe builds only (tools/abl/probe_5d.py): bit 0 = no scalar-chain guard in the fused-loss epilogue, bit 1 = every
-// thread's {sq, sqp} of the 64 x 64 fused-loss tile dumped here before the cross-lane reduction
-constexpr int DBG5D_WGS = 1024;
-__device__ float g_dbg5d[DBG5D_WGS * 256 * 2];
-#endif
-
 typedef __attribute__((address_space(3))) char lds_char;
 typedef __attribute__((address_space(1))) const void gvoid;
 
@@ -297,10 +290,6 @@ __device__ __forceinline__ void gemm_bf16_tile(const GemmBf16& g, int tiles_n, i
         const int j = j0 + c * 8;
         float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         float sq = 0.f, sqp = 0.f;
-#if defined(CODAE_DBG_5D) && (CODAE_DBG_5D & 4)
-        typedef float f32x2_t __attribute__((ext_vector_type(2)));
-        f32x2_t sq2 = {0.f, 0.f};
-#endif
         bf16_t* Cb = reinterpret_cast<bf16_t*>(g.C);
         constexpr int ITER = (HR + RL - 1) / RL;                // rows per thread per pass
         const int* rowinfo = reinterpret_cast<const int*>(smem_raw + 2 * BUF_BYTES);
@@ -325,15 +314,10 @@ __device__ __forceinline__ void gemm_bf16_tile(const GemmBf16& g, int tiles_n, i
                 const int id = rowinfo[2 * (hh * HR + rr) + 1];
                 live[it] = rl < RL && j < g.N && r < HR && src_row >= 0;
                 const float* xp = L.data + (int64_t)(src_row >= 0 ? src_row : 0) * L.io + jc;
-#if defined(CODAE_LOSS_ABL) && (CODAE_LOSS_ABL & 1)     // timing-only ablation: no gather of the target rows
-                xa[it] = make_float4(0.5f, 0.25f, 0.125f, 0.75f); xb[it] = xa[it]; (void)xp; (void)tb; (void)id;
-                mk[it] = make_uint2(0x01010101u, 0x00010101u);
-#else
                 xa[it] = *reinterpret_cast<const float4*>(xp);
                 xb[it] = *reinterpret_cast<const float4*>(xp + 4);
                 const uint2 mv = *reinterpret_cast<const uint2*>(tb + (int64_t)id * L.io + jc);
                 mk[it] = masked ? mv : make_uint2(0x01010101u, 0x01010101u);
-#endif
             }
             if (((BM / WM) * wr) / HR == hh) {
 #pragma unroll
@@ -364,40 +348,11 @@ __device__ __forceinline__ void gemm_bf16_tile(const GemmBf16& g, int tiles_n, i
                         const float xv[8] = {xa[it].x, xa[it].y, xa[it].z, xa[it].w, xb[it].x, xb[it].y, xb[it].z, xb[it].w};
                         const float yv[8] = {ya[0], ya[1], ya[2], ya[3], yb[0], yb[1], yb[2], yb[3]};
                         float gq[8];
-#if defined(CODAE_DBG_5D) && (CODAE_DBG_5D & 4)
-                        // probe variant: the sum of squares as an explicit packed chain WITHOUT half swaps (even / odd lanes
-                        // accumulate apart, v_pk_fma_f32 with default op_sel); folded after the loop
-                        {
-                            typedef float f32x2_t __attribute__((ext_vector_type(2)));
-#pragma unroll
-                            for (int k = 0; k < 8; k += 2) {
-                                f32x2_t d2 = {xv[k] - yv[k], xv[k + 1] - yv[k + 1]};
-#if (CODAE_DBG_5D & 8)
-                                // in-place form the compiler chose in the failing build: dst = src0 = src1, accumulator as src2
-                                asm volatile("v_pk_fma_f32 %0, %0, %0, %1" : "+v"(d2) : "v"(sq2));
-                                sq2 = d2;
-#elif (CODAE_DBG_5D & 16)
-                                // the failing build's FIRST op: squares of d added to the HALF-SWAPPED src2 (op_sel on src2)
-                                if (k == 0) {
-                                    f32x2_t se2 = d2 * d2, r2;
-                                    asm volatile("v_pk_fma_f32 %0, %1, %1, %2 op_sel:[0,0,1] op_sel_hi:[1,1,0]" : "=v"(r2) : "v"(d2), "v"(se2));
-                                    sq2 += r2 * 0.5f;
-                                } else {
-                                    asm volatile("v_pk_fma_f32 %0, %1, %1, %0" : "+v"(sq2) : "v"(d2));
-                                }
-#else
-                                asm volatile("v_pk_fma_f32 %0, %1, %1, %0" : "+v"(sq2) : "v"(d2));
-#endif
-                            }
-                        }
-#endif
 #pragma unroll
                         for (int k = 0; k < 8; ++k) {
                             const float d = xv[k] - yv[k];
                             const float se = d * d;
-#if !(defined(CODAE_DBG_5D) && (CODAE_DBG_5D & 4))
                             sq += se;
-#endif
                             // Keeps sq a scalar chain.  Left alone, the SLP vectorizer packs this
                             // accumulation into v_pk_fma_f32 / v_pk_add_f32 pairs and folds the lane shuffle into op_sel; one of
                             // them is `v_pk_fma_f32 D, A, A, C op_sel:[0,0,1] op_sel_hi:[1,1,0]` (lo result = A.lo^2 + C.HI).
@@ -407,9 +362,7 @@ __device__ __forceinline__ void gemm_bf16_tile(const GemmBf16& g, int tiles_n, i
                             // Stand-alone proof: tools/abl/pk_fma_opsel_repro.hip; in this kernel: tools/abl/probe_5d.py.  The
                             // empty asm makes sq opaque between additions, so no vector chain can be formed from it, and
                             // tools/check_isa.py (rule 4) rejects any such instruction anywhere in the shipped code object.
-#if !(defined(CODAE_DBG_5D) && (CODAE_DBG_5D & 1))
                             asm volatile("" : "+v"(sq));
-#endif
                             const uint32_t mb = ((k < 4 ? m.x : m.y) >> (8 * (k & 3))) & 0xff;
                             if (mb == 0) sqp += se;
                             gq[k] = -2.f * d * L.inv_n;
@@ -419,21 +372,11 @@ __device__ __forceinline__ void gemm_bf16_tile(const GemmBf16& g, int tiles_n, i
 #pragma unroll
                         for (int k = 0; k < 8; ++k) cs[k] += gq[k];
                     }
-#if defined(CODAE_LOSS_ABL) && (CODAE_LOSS_ABL & 2)     // timing-only ablation: no dY stores (kept live)
-                    asm volatile("" ::"v"(o.x), "v"(o.y), "v"(o.z), "v"(o.w));
-#else
                     *reinterpret_cast<uint4*>(Cb + (int64_t)i * g.ldc + j) = o;
-#endif
                 }
             }
             __syncthreads();
         }
-#if defined(CODAE_DBG_5D) && (CODAE_DBG_5D & 4)
-        sq = sq2[0] + sq2[1];
-#endif
-#if defined(CODAE_DBG_5D) && (CODAE_DBG_5D & 2)
-        if (bid < DBG5D_WGS && NT == 256) { g_dbg5d[(bid * 256 + threadIdx.x) * 2] = sq; g_dbg5d[(bid * 256 + threadIdx.x) * 2 + 1] = sqp; }
-#endif
         // block sums -> scalars; column sums -> bias gradient
         float* red = reinterpret_cast<float*>(smem_raw);
         static_assert(RL * BN * 4 + 64 <= 2 * BUF_BYTES, "reduction scratch must fit");
@@ -715,7 +658,7 @@ bool gemm_bf16_supported(int M, int N, int K) {
 }
 
 // What gemm_bf16(g) launches: the ONE place that decides tile, kernel family, stages, loader layout, epilogue and store policy,
-// with the CODAE_GEMM_TILE / CODAE_GEMM_DBG overrides applied here and nowhere else.  gemm_bf16() launches what it says;
+// with the CODAE_GEMM_TILE override applied here and nowhere else.  gemm_bf16() launches what it says;
 // gemm_bf16_colsum_rows / _loss_parts / _takes_relu_bits read the same answer, so the row and part counts the engine adds up
 // follow the tile by construction, under every switch.
 Bf16Plan gemm_bf16_plan(const GemmBf16& g) {
@@ -725,7 +668,6 @@ Bf16Plan gemm_bf16_plan(const GemmBf16& g) {
     // generic activations: the one-barrier kernel on 64 x 64 / 128 x 128 tiles only (the pipelined kernels keep their ReLU / identity
     // epilogues; DESIGN.md section 6, activations), whatever the switches force
     const bool act = g.act != CODAE_ACT_NONE;
-    const int dbg = act ? 0 : e.gemm_dbg;
 
     // ---- the big tile: 256 x 192 / 8 waves, phase-pipelined, when it yields enough workgroups to cover the chip (its operand
     // traffic per flop is 1.7x lower than the 128 x 128 tile's, which is what bounds the small tile: ~39 TB/s of L2 reads at full
@@ -758,15 +700,7 @@ Bf16Plan gemm_bf16_plan(const GemmBf16& g) {
 
     Bf16Plan p{};
     GemmTile tile;
-    if (dbg) {
-        // CODAE_GEMM_DBG: every launch without an activation on 256 x 192 tiles - the forward form on the ablation build of that
-        // number, the fused loss on its stamped build (8; tools/timeline_loss.py), anything else on the plain kernel, every wave loading
-        const bool abl_built = (dbg >= 1 && dbg <= 10) || dbg == 16 || dbg == 32;     // (9 / 10: stamps + no LDS-DMA / no MFMA; 16 / 32: no LDS-DMA of A / B)
-        tile = TILE_256x192;
-        if (loss && dbg == 8) { p.family = BF16_PIPELINED_ABL; p.loader = 1; p.dbg = 8; }
-        else if (!loss && fwd_form && abl_built) { p.family = BF16_PIPELINED_ABL; p.loader = 6; p.dbg = dbg; }
-        else { p.family = BF16_PIPELINED; p.loader = 1; }
-    } else if (!act && (big == 3 || big == 6)) {
+    if (!act && (big == 3 || big == 6)) {
         tile = TILE_256x192; p.family = BF16_PIPELINED; p.loader = big == 3 ? 1 : 6;
     } else if (!act && big == 7) {
         tile = TILE_128x192; p.family = BF16_PIPELINED; p.loader = 7;
@@ -797,16 +731,11 @@ Bf16Plan gemm_bf16_plan(const GemmBf16& g) {
     const bool bwd_epi = g.relu_src != nullptr || g.colsum_part != nullptr;
     // write-through stores address a tile as {descriptor over its first row, 32-bit byte offset}: 256 rows must stay under 2 GiB
     const int policy = (g.store_policy == STORE_WT && g.ldc < ((int64_t)1 << 20)) ? STORE_WT : STORE_PLAIN;
-    if (p.family == BF16_PIPELINED_ABL) {
-        p.epi = loss ? 3 : 0;
-        p.store_policy = (!loss && dbg == 8) ? policy : STORE_PLAIN;     // (the stamped build follows the launch's store policy: tools/timeline_gemm.py)
-        return p;
-    }
     p.epi = loss ? 3 : (g.c_f32 ? 0 : (bwd_epi ? 2 : 1));
     p.store_policy = policy;
     // the data gradient beside another stream's weight gradients: the same kernel with the compiler's schedule
     // (GemmBf16::coscheduled), built for the 256 x 192 tile with plain stores
-    if (g.coscheduled && p.epi == 2 && p.loader != 7 && g.a_mode == OP_KC && g.b_mode == OP_KC) { p.dbg = 64; p.store_policy = STORE_PLAIN; }
+    if (g.coscheduled && p.epi == 2 && p.loader != 7 && g.a_mode == OP_KC && g.b_mode == OP_KC) { p.sched = SCHED_COMPILER; p.store_policy = STORE_PLAIN; }
     return p;
 }
 
@@ -866,7 +795,7 @@ static int validate(const GemmBf16& g) {
     CODAE_REQUIRE(!g.c_f32 || (g.relu_src == nullptr && g.colsum_part == nullptr), "gemm_bf16: ReLU mask / column sums need bf16 output");
     if (g.act != CODAE_ACT_NONE) {
         CODAE_REQUIRE(!g.loss.enabled && g.a_mode == OP_KC && g.split_k == 1 && g.relu_bits == nullptr && g.relu_bits_out == nullptr &&
-                          !(g.c_f32 && g.b_mode == OP_KS) && g.dbg == 0,
+                          !(g.c_f32 && g.b_mode == OP_KS),
                       "gemm_bf16: an activation needs the forward / data-gradient form (k-contiguous A, unsplit, no 1-bit masks, "
                       "no fused loss, k-strided B only with bf16 output)");
     }
@@ -890,12 +819,4 @@ int gemm_bf16(const GemmBf16& g, hipStream_t s) {
     return plan.bm == 64 ? launch_cfg<64, 64, 2, 2>(g, plan, s) : launch_cfg<128, 128, 2, 2>(g, plan, s);
 }
 
-#if defined(CODAE_DBG_5D) && (CODAE_DBG_5D & 2)
-}  // namespace codae
-extern "C" int codae_debug_5d(float* host_out, int n_floats) {
-    if (hipMemcpyFromSymbol(host_out, HIP_SYMBOL(codae::g_dbg5d), (size_t)n_floats * sizeof(float)) != hipSuccess) return -1;
-    return 0;
-}
-namespace codae {
-#endif
 }  // namespace codae

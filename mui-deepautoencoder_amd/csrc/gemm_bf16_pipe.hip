@@ -42,17 +42,14 @@ namespace {
 
 #include "gemm_bf16_halftile.h"
 
-// DBG = 8 build only: per-workgroup wall-clock stamps (100 MHz s_memrealtime) at entry, first MFMA phase,
-// end of the K loop, epilogue stores issued, stores retired; + the XCC the workgroup ran on
-constexpr int TIMELINE_WGS = 4096, TIMELINE_SLOTS = 6;
-__device__ unsigned long long g_timeline[TIMELINE_WGS * TIMELINE_SLOTS];
-
+// SCHED (Bf16Plan::sched): SCHED_PINNED = the phases pinned by sched_group_barriers (k-contiguous operands; phase_order, phase_barrier),
+// SCHED_COMPILER = the compiler's own schedule, launched for GemmBf16::coscheduled.
 // EPI (bf16 output only): 1 = forward epilogue (bias + ReLU), 2 = data-gradient epilogue (ReLU mask from the saved
 // activation + column sums = bias gradient), 4 = the same with the 1-bit ReLU mask and nothing else (a kernel of its own: beside the
 // activation-mask copy of the write-out in ONE kernel, the compiler made the bit copy's LDS reads wait for the other copy's loads),
 // 5 = the data-gradient epilogue with NO mask at all (the layer behind the code layer: column sums, nothing parked but the bias; a kernel of its
 // own for the same reason: one kind of write-out per instantiation), 3 = last forward layer of a training step with the MSE loss, its gradient
-// and the metric sums computed straight from the accumulators (g.loss), 0 = everything decided at run time.  Apart from trimming the forward's
+// and the metric sums computed straight from the accumulators (g.loss); 0 goes with the fp32 output and nothing else (static_assert in the tile body).  Apart from trimming the forward's
 // epilogue this gives the forward and the data-gradient launches distinct kernel symbols in rocprofv3 traces.
 // One output tile (or split-K range of one) of one GEMM: the whole kernel body, shared by the plain kernel (one GEMM per
 // launch) and the grouped kernel (the weight gradients of every layer in one launch).  wg / nwg: this workgroup's index
@@ -71,12 +68,14 @@ constexpr int PARK_BIAS_BYTES = 1024;
 template <int BM, int BN, bool C_F32, int EPI>
 constexpr int pipe_smem_bytes() {
     const bool park = BM == 256;
-    return 2 * (BM + BN) * 128 + (EPI == 3 ? BM * 8 : 0) + (park ? PARK_BIAS_BYTES : 0) + (park && !C_F32 && (EPI == 0 || EPI == 2 || EPI == 4) ? BM * BN / 8 : 0);
+    return 2 * (BM + BN) * 128 + (EPI == 3 ? BM * 8 : 0) + (park ? PARK_BIAS_BYTES : 0) + (park && !C_F32 && (EPI == 2 || EPI == 4) ? BM * BN / 8 : 0);
 }
 
-template <int BM, int BN, int WM, int WN, int NLB, int A_MODE, int B_MODE, bool C_F32, int DBG = 0, int EPI = 0, int POL = STORE_PLAIN>
+template <int BM, int BN, int WM, int WN, int NLB, int A_MODE, int B_MODE, bool C_F32, int SCHED = SCHED_PINNED, int EPI = 0, int POL = STORE_PLAIN>
 __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles_n, int tiles_mn, int kt_total, int wg, int nwg,
                                                     char* smem_raw) {
+    static_assert(C_F32 || EPI != 0, "a bf16 output names its epilogue");
+    static_assert(SCHED == SCHED_PINNED || SCHED == SCHED_COMPILER, "SCHED");
     constexpr int NW = WM * WN;
     constexpr int SM = BM / WM, SN = BN / WN;        // wave sub-tile
     constexpr int AHR = BM / 2, BHR = BN / 2;        // rows / cols per half-tile
@@ -95,7 +94,7 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
     static_assert(SM % 32 == 0 && SN % 32 == 0, "wave sub-tile must split into 16-wide half tiles");
     lds_char* smem = (lds_char*)smem_raw;
     constexpr bool PARK = BM == 256;
-    constexpr bool PARK_BITS = PARK && !C_F32 && (EPI == 0 || EPI == 2 || EPI == 4);
+    constexpr bool PARK_BITS = PARK && !C_F32 && (EPI == 2 || EPI == 4);
     constexpr int BIAS_OFF = 2 * BUF + (EPI == 3 ? BM * 8 : 0), BITS_OFF = BIAS_OFF + PARK_BIAS_BYTES;
     static_assert(BN * 4 <= PARK_BIAS_BYTES && BN % 32 == 0, "bias slice: one 16-B piece per lane of one wave");
 
@@ -130,22 +129,6 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
 
     auto a_img = [&](int tile, int h) { return smem + (tile & 1) * BUF + h * AH; };
     auto b_img = [&](int tile, int h) { return smem + (tile & 1) * BUF + 2 * AH + h * BH; };
-    // timing-only ablations (compile-time; DBG = 0 in the shipped instantiations)
-    constexpr bool dbg_noload = DBG & 1, dbg_nomma = DBG & 2, dbg_nostore = DBG & 4, dbg_time = DBG & 8;
-    constexpr bool dbg_no_a = DBG & 16, dbg_no_b = DBG & 32;        // only one operand's LDS-DMA
-    auto stamp = [&](int slot) {
-        if constexpr (dbg_time) {
-            if (threadIdx.x == 0 && blockIdx.x < TIMELINE_WGS) g_timeline[blockIdx.x * TIMELINE_SLOTS + slot] = wall_clock64();
-        }
-    };
-    stamp(0);
-    if constexpr (dbg_time) {
-        if (threadIdx.x == 0 && blockIdx.x < TIMELINE_WGS) {
-            unsigned xcc;
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-            g_timeline[blockIdx.x * TIMELINE_SLOTS + 5] = xcc & 0xf;
-        }
-    }
     if constexpr (EPI == 3) {
         // {dataset row or -1, mask id} per tile row, fetched once here (two dependent loads that would otherwise sit in
         // front of the epilogue); published to the other waves by the K loop's barriers
@@ -237,7 +220,7 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
     // the schedule assigns: every phase stays one straight-line block the scheduler can interleave,
     // and the vmcnt arithmetic is exact to the end (cost: ~2 extra K-tiles of L2-hit DMA per workgroup).
     auto issue_a = [&](int tile, int h) {
-        if constexpr (!dbg_noload && !dbg_no_a && a_loader) {
+        if constexpr (a_loader) {
             const char* base = a_base + (int64_t)(tile < nkt ? tile : nkt - 1) * a_step;      // wave-uniform
             lds_char* img = a_img(tile, h);
 #pragma unroll
@@ -245,7 +228,7 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
         }
     };
     auto issue_b = [&](int tile, int h) {
-        if constexpr (!dbg_noload && !dbg_no_b && b_loader) {
+        if constexpr (b_loader) {
             const char* base = b_base + (int64_t)(tile < nkt ? tile : nkt - 1) * b_step;
             lds_char* img = b_img(tile, h);
 #pragma unroll
@@ -268,17 +251,6 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
         for (int nt = 0; nt < TNH; ++nt) dst[nt][1] = read_frag<B_MODE, BHR, 1>(b_img(tile, h), wc * TNH + nt, lane);
     };
     auto mma = [&](const bf16x8 (&a)[TMH][2], const bf16x8 (&b)[TNH][2], int mh, int nh) {
-        if constexpr (dbg_nomma) {
-            // keep the fragments alive so the ds_reads stay
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-#pragma unroll
-                for (int mt = 0; mt < TMH; ++mt) asm volatile("" ::"v"(a[mt][s]));
-#pragma unroll
-                for (int nt = 0; nt < TNH; ++nt) asm volatile("" ::"v"(b[nt][s]));
-            }
-            return;
-        }
 #pragma unroll
         for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -308,7 +280,6 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
     phase_barrier();
     read_b(b0, 0, 0);
 
-    stamp(1);
     // reads that may stay in flight across the barrier after a phase that read an A / a B half: the compiler-visible
     // ds_read_b128 of a k-contiguous operand (it waits for them itself before their first use); the asm-issued
     // transposed reads of a k-strided operand are waited for in full (settle() follows the barrier)
@@ -325,7 +296,7 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
     // MFMAs, reads, three MFMAs, DMA, rest; two MFMAs, DMA + reads, rest -: grouped weight gradients 33.1-33.6 us against 32.8-33.1
     // for the compiler's own interleaving: left alone.)
     auto phase_order = [&](auto nread_tag, auto ndma_tag) {
-        if constexpr (A_MODE == OP_KC && B_MODE == OP_KC && (DBG & 64) == 0) {
+        if constexpr (A_MODE == OP_KC && B_MODE == OP_KC && SCHED == SCHED_PINNED) {
             constexpr int NREAD = decltype(nread_tag)::value, NDMA = decltype(ndma_tag)::value;
 #pragma unroll
             for (int i = 0; i < 6; ++i) {
@@ -340,7 +311,7 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
             __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
         }
     };
-    constexpr bool PINP = (A_MODE == OP_KC && B_MODE == OP_KC) && (DBG & 64) == 0;      // see phase_barrier; DBG 64: GemmBf16::coscheduled
+    constexpr bool PINP = (A_MODE == OP_KC && B_MODE == OP_KC) && SCHED == SCHED_PINNED;      // see phase_barrier
     using RA = std::integral_constant<int, 2 * TMH>;
     using RB = std::integral_constant<int, 2 * TNH>;
     using DA = std::integral_constant<int, a_loader ? NA : 0>;
@@ -415,7 +386,6 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
     // write-out's LDS reads on the paths where it could not count the loads issued since.
     __builtin_amdgcn_s_waitcnt(0x0f70);
     asm volatile("" ::: "memory");
-    stamp(2);
 
     // ---- epilogue: lane holds C[i][j .. j+3] of each 16 x 16 tile (swapped MFMA operands)
     const int li = lane & 15, g4 = (lane >> 4) * 4;
@@ -540,7 +510,6 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
             }
         };
         if (j0 + BN <= g.N) loss_rows(std::true_type{}); else loss_rows(std::false_type{});
-        stamp(3);                 // (DBG 8: loss arithmetic done, dy tile staged)
         phase_barrier();
         {
             constexpr int CH = BN / 8, RL = NT / CH;
@@ -557,7 +526,6 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
                 if (ok) out.store16(Cb + (int64_t)(i0 + r) * g.ldc + j, (uint32_t)(r * (int)g.ldc + j) * 2u, lv);
             }
         }
-        if constexpr (dbg_time) { wait_vmcnt<0>(); stamp(4); }
         // metric sums: lanes -> wave -> workgroup -> this workgroup's row of L.parts
 #pragma unroll
         for (int o2 = 32; o2 > 0; o2 >>= 1) { sq += __shfl_xor(sq, o2); sqp += __shfl_xor(sqp, o2); }
@@ -605,7 +573,7 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
         consume_prefetch();
         return;
     }
-    if constexpr (!C_F32 && !dbg_nostore) {
+    if constexpr (!C_F32) {
         // bf16 output through LDS, whole rows, 16 B per lane (see gemm_bf16.hip); mask + bias-grad sums ride along
         constexpr int NT = 64 * NW;
         constexpr int PITCH = BN * 2 + 16;
@@ -753,8 +721,6 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
             else if (relu_mask) write_out(std::integral_constant<int, MASK_ACT>{});
             else write_out(std::integral_constant<int, MASK_NONE>{});
         }
-        stamp(3);
-        if constexpr (dbg_time) { wait_vmcnt<0>(); stamp(4); }
         if (EPI != 1 && g.colsum_part != nullptr) {
             phase_barrier();
             float* red = reinterpret_cast<float*>(smem_raw);
@@ -842,13 +808,13 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
     }
 }
 
-template <int BM, int BN, int WM, int WN, int NLB, int A_MODE, int B_MODE, bool C_F32, int DBG = 0, int EPI = 0, int POL = STORE_PLAIN>
+template <int BM, int BN, int WM, int WN, int NLB, int A_MODE, int B_MODE, bool C_F32, int SCHED = SCHED_PINNED, int EPI = 0, int POL = STORE_PLAIN>
 __global__ __launch_bounds__(64 * WM * WN, (WM * WN + 3) / 4)
 void gemm_bf16_pipe_kernel(GemmBf16 g, int tiles_n, int tiles_mn, int kt_total) {
     // (behind the K-tile buffers: EPI 3's {dataset row, mask id} of the tile's rows, the parked bias slice and ReLU bits; ONE array: a second __shared__ object beside an LDS-DMA
     // staging array makes the compiler drain vmcnt in front of LDS reads)
     __shared__ __attribute__((aligned(16))) char smem_raw[pipe_smem_bytes<BM, BN, C_F32, EPI>()];
-    gemm_bf16_pipe_tile<BM, BN, WM, WN, NLB, A_MODE, B_MODE, C_F32, DBG, EPI, POL>(g, tiles_n, tiles_mn, kt_total, blockIdx.x, gridDim.x, smem_raw);
+    gemm_bf16_pipe_tile<BM, BN, WM, WN, NLB, A_MODE, B_MODE, C_F32, SCHED, EPI, POL>(g, tiles_n, tiles_mn, kt_total, blockIdx.x, gridDim.x, smem_raw);
 }
 
 // The bias finish as workgroup `fb` of the n_fb trailing ones of the grouped launch below (BiasFold, codae_common.h): 512 threads =
@@ -962,13 +928,13 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pipe_grouped_kernel(GemmBf16
     while (j + 1 < grp.n && t >= grp.wg_begin[j + 1]) ++j;
     const GemmBf16& g = grp.g[j];
     const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN;
-    gemm_bf16_pipe_tile<BM, BN, 4, 2, 4, OP_KS, OP_KS, true, 0, 0, POL>(g, tiles_n, tiles_m * tiles_n, g.K / BK, t - grp.wg_begin[j], 0, smem_raw);
+    gemm_bf16_pipe_tile<BM, BN, 4, 2, 4, OP_KS, OP_KS, true, SCHED_PINNED, 0, POL>(g, tiles_n, tiles_m * tiles_n, g.K / BK, t - grp.wg_begin[j], 0, smem_raw);
 }
 
 // The launchers below take a plan (gemm_bf16_plan) and decide nothing: they map its fields, and the descriptor's operand modes and
 // output kind, to the instantiation.  p.workgroups is the grid.
-#define PIPE_LAUNCH(BM, BN, NLB, AM, BMODE, CF, DBG, EP, POL)                                                                    \
-    hipLaunchKernelGGL((gemm_bf16_pipe_kernel<BM, BN, 4, 2, NLB, AM, BMODE, CF, DBG, EP, POL>), dim3((unsigned)p.workgroups), dim3(512), 0, s, g, \
+#define PIPE_LAUNCH(BM, BN, NLB, AM, BMODE, CF, SCHED, EP, POL)                                                                  \
+    hipLaunchKernelGGL((gemm_bf16_pipe_kernel<BM, BN, 4, 2, NLB, AM, BMODE, CF, SCHED, EP, POL>), dim3((unsigned)p.workgroups), dim3(512), 0, s, g, \
                        p.tiles_n, p.tiles_m * p.tiles_n, g.K / BK)
 
 // 256 x 192, 8 waves (64 x 96 per wave); NLB 6: B halves by 6 loader waves; NLB 4 (CODAE_GEMM_TILE=x, the default): all LDS-DMA
@@ -977,12 +943,12 @@ template <int NLB>
 int launch_pipe(const GemmBf16& g, const Bf16Plan& p, hipStream_t s) {
     constexpr int BM = 256, BN = 192;
 #define LAUNCH(AM, BMODE, CF, EP) \
-    do { if (p.store_policy == STORE_WT) PIPE_LAUNCH(BM, BN, NLB, AM, BMODE, CF, 0, EP, STORE_WT); else PIPE_LAUNCH(BM, BN, NLB, AM, BMODE, CF, 0, EP, STORE_PLAIN); } while (0)
+    do { if (p.store_policy == STORE_WT) PIPE_LAUNCH(BM, BN, NLB, AM, BMODE, CF, SCHED_PINNED, EP, STORE_WT); else PIPE_LAUNCH(BM, BN, NLB, AM, BMODE, CF, SCHED_PINNED, EP, STORE_PLAIN); } while (0)
 #define LAUNCH_BF16(AM, BMODE) do { if (p.epi == 2) LAUNCH(AM, BMODE, false, 2); else LAUNCH(AM, BMODE, false, 1); } while (0)
     const bool bits = p.epi == 2 && g.relu_bits != nullptr;          // (the forward-form data gradient behind a forward that left bits)
     // (the data gradient behind the code layer - with the transposed weight shadow or, codae_dgrad_bf16, without it; the plan still says 2)
     const bool unmasked = p.epi == 2 && g.relu_bits == nullptr && g.relu_src == nullptr;
-    if (p.dbg == 64) PIPE_LAUNCH(BM, BN, NLB, OP_KC, OP_KC, false, 64, 2, STORE_PLAIN);      // the compiler's schedule (GemmBf16::coscheduled)
+    if (p.sched == SCHED_COMPILER) PIPE_LAUNCH(BM, BN, NLB, OP_KC, OP_KC, false, SCHED_COMPILER, 2, STORE_PLAIN);      // (GemmBf16::coscheduled)
     else if (p.epi == 3) LAUNCH(OP_KC, OP_KC, false, 3);
     else if (g.a_mode == OP_KC && g.b_mode == OP_KC) { if (g.c_f32) LAUNCH(OP_KC, OP_KC, true, 0); else if (bits) LAUNCH(OP_KC, OP_KC, false, 4); else if (unmasked) LAUNCH(OP_KC, OP_KC, false, 5); else LAUNCH_BF16(OP_KC, OP_KC); }
     else if (g.a_mode == OP_KC && g.b_mode == OP_KS) { if (g.c_f32) LAUNCH(OP_KC, OP_KS, true, 0); else if (unmasked) LAUNCH(OP_KC, OP_KS, false, 5); else LAUNCH_BF16(OP_KC, OP_KS); }
@@ -994,20 +960,11 @@ int launch_pipe(const GemmBf16& g, const Bf16Plan& p, hipStream_t s) {
     return CODAE_OK;
 }
 
-// timing-only ablation builds of the forward form (KC x KC, bf16 out), 256 x 192
-template <int DBG>
-int launch_dbg(const GemmBf16& g, const Bf16Plan& p, hipStream_t s) {
-    if (DBG == 8 && p.store_policy == STORE_WT) PIPE_LAUNCH(256, 192, 4, OP_KC, OP_KC, false, 8, 0, STORE_WT);
-    else PIPE_LAUNCH(256, 192, 4, OP_KC, OP_KC, false, DBG, 0, STORE_PLAIN);
-    CODAE_LAUNCH_CHECK();
-    return CODAE_OK;
-}
-
 // 128 x 192, 8 waves of 32 x 96 (forward / data-gradient form only: the k-strided half images need 96 or 128 columns)
 int launch_pipe_mid(const GemmBf16& g, const Bf16Plan& p, hipStream_t s) {
     const bool wt = p.store_policy == STORE_WT;
-    if (p.epi == 2) { if (wt) PIPE_LAUNCH(128, 192, 4, OP_KC, OP_KC, false, 0, 2, STORE_WT); else PIPE_LAUNCH(128, 192, 4, OP_KC, OP_KC, false, 0, 2, STORE_PLAIN); }
-    else { if (wt) PIPE_LAUNCH(128, 192, 4, OP_KC, OP_KC, false, 0, 1, STORE_WT); else PIPE_LAUNCH(128, 192, 4, OP_KC, OP_KC, false, 0, 1, STORE_PLAIN); }
+    if (p.epi == 2) { if (wt) PIPE_LAUNCH(128, 192, 4, OP_KC, OP_KC, false, SCHED_PINNED, 2, STORE_WT); else PIPE_LAUNCH(128, 192, 4, OP_KC, OP_KC, false, SCHED_PINNED, 2, STORE_PLAIN); }
+    else { if (wt) PIPE_LAUNCH(128, 192, 4, OP_KC, OP_KC, false, SCHED_PINNED, 1, STORE_WT); else PIPE_LAUNCH(128, 192, 4, OP_KC, OP_KC, false, SCHED_PINNED, 1, STORE_PLAIN); }
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;
 }
@@ -1051,7 +1008,7 @@ int gemm_bf16_pipe_grouped(GemmBf16Group& grp, hipStream_t s, const BiasFold* fo
     return CODAE_OK;
 }
 
-// the pipelined families of a plan (BF16_PIPELINED, BF16_PIPELINED_ABL)
+// the pipelined family of a plan (BF16_PIPELINED)
 int gemm_bf16_pipe(const GemmBf16& g_in, const Bf16Plan& p, hipStream_t s) {
     // LDS-DMA sources are addressed as {scalar base, 32-bit lane offset}
     CODAE_REQUIRE((int64_t)(g_in.a_mode == OP_KC ? g_in.M : g_in.K) * g_in.lda * 2 < (int64_t)1 << 32 &&
@@ -1059,39 +1016,9 @@ int gemm_bf16_pipe(const GemmBf16& g_in, const Bf16Plan& p, hipStream_t s) {
                   "gemm_bf16: operand larger than 4 GiB");
     GemmBf16 g = g_in;
     g.store_policy = p.store_policy;
-    if (p.family == BF16_PIPELINED_ABL) {
-        g.dbg = p.dbg;
-        if (p.epi == 3) {          // stamped build of the fused-loss kernel (tools/timeline_loss.py)
-            PIPE_LAUNCH(256, 192, 6, OP_KC, OP_KC, false, 8, 3, STORE_PLAIN);
-            CODAE_LAUNCH_CHECK();
-            return CODAE_OK;
-        }
-        switch (p.dbg) {
-            case 1: return launch_dbg<1>(g, p, s);
-            case 2: return launch_dbg<2>(g, p, s);
-            case 3: return launch_dbg<3>(g, p, s);
-            case 4: return launch_dbg<4>(g, p, s);
-            case 5: return launch_dbg<5>(g, p, s);
-            case 6: return launch_dbg<6>(g, p, s);
-            case 7: return launch_dbg<7>(g, p, s);
-            case 8: return launch_dbg<8>(g, p, s);
-            case 9: return launch_dbg<9>(g, p, s);      // stamps + no LDS-DMA
-            case 10: return launch_dbg<10>(g, p, s);    // stamps + no MFMA
-            case 16: return launch_dbg<16>(g, p, s);    // no LDS-DMA of the A operand
-            case 32: return launch_dbg<32>(g, p, s);    // no LDS-DMA of the B operand
-            default: set_error("gemm_bf16: ablation build %d is not instantiated", p.dbg); return CODAE_E_UNSUPPORTED;
-        }
-    }
     if (p.loader == 7) return launch_pipe_mid(g, p, s);
     return p.loader == 6 ? launch_pipe<4>(g, p, s) : launch_pipe<6>(g, p, s);
 }
 #undef PIPE_LAUNCH
-
-// copies the DBG = 8 stamps of the first n_wg workgroups (TIMELINE_SLOTS words each) to the host
-int gemm_bf16_timeline(unsigned long long* host_out, int n_wg) {
-    CODAE_REQUIRE(host_out && n_wg > 0 && n_wg <= TIMELINE_WGS, "timeline: bad args");
-    CODAE_HIP_CHECK(hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_timeline), (size_t)n_wg * TIMELINE_SLOTS * sizeof(unsigned long long)));
-    return CODAE_OK;
-}
 
 }  // namespace codae

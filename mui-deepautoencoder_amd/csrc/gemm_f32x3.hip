@@ -33,13 +33,6 @@ namespace codae {
 namespace {
 
 constexpr int XM = 128, XN = 128, XK = 32, XT = 512;
-// timing-only ablation builds (make EXTRA=-DX3_DBG=n, bits): 1 no MFMAs, 2 no split arithmetic (planes = raw halves), 4 no LDS stores
-// in the loop, 8 no global loads in the loop, 64 the compiler's own issue order in the first half, 128 no workgroup barrier, 256 no
-// fragment reads in the loop.  Wrong results, right instruction mix: what DESIGN.md 5f's breakdown was measured with.  0 in the
-// library that ships.
-#ifndef X3_DBG
-#define X3_DBG 0
-#endif
 constexpr int PLANE = 128 * 64;        // bytes of one plane image: [128 rows][32 k] bf16
 constexpr int OPND = 3 * PLANE;        // an operand's three planes
 constexpr int XBUF = 2 * OPND;         // A + B
@@ -66,10 +59,6 @@ __device__ __forceinline__ int ks_block(int block, int kr) { return block ^ ((kr
 // two fp32 values -> their three bf16 planes, each as one packed pair (low half = x), round-to-nearest-even at every cut
 // (v_cvt_pk_bf16_f32); the two subtractions are exact in fp32
 __device__ __forceinline__ void split_pair(float x, float y, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
-    if constexpr ((X3_DBG & 2) != 0) {
-        p0 = __float_as_uint(x); p1 = __float_as_uint(y); p2 = p0 ^ p1;
-        return;
-    }
     p0 = pack_bf16x2(x, y);
     const float rx = x - __uint_as_float(p0 << 16), ry = y - __uint_as_float(p0 & 0xffff0000u);
     p1 = pack_bf16x2(rx, ry);
@@ -255,7 +244,6 @@ __device__ __forceinline__ void x3_tile(GemmF32 g, int tile_m, int tile_n, int z
             for (int p = 0; p < 3; ++p) bf[SET][nt][p] = x3_frag<B_KC>(cb + OPND + p * PLANE, 2 * wc + nt, lane);
     };
     read_frags(S0{});
-    if constexpr ((X3_DBG & 256) != 0) read_frags(S1{});
 
     // K-tile `tile` (fragments already in register set CUR): the first half of its MFMAs with the split + LDS stores of tile + 1
     // (register set CUR ^ 1 -> the other LDS buffer) and the global loads of tile + 3 issued between them; the barrier; the
@@ -267,7 +255,7 @@ __device__ __forceinline__ void x3_tile(GemmF32 g, int tile_m, int tile_n, int z
         // half h of the K-tile's MFMAs: three of the six plane products (smallest first: 2^-16, 2^-16, 2^-16 | 2^-8, 2^-8, 1
         // relative to a0 b0) for ALL eight accumulator tiles, product by product - eight independent accumulators between two
         // MFMAs of one chain.  (Split by column block instead - four accumulators x six products each - the launch took the same
-        // time; with every load, store, split, fragment read and the barrier compiled out (X3_DBG 398) the MFMAs + prologue +
+        // time; with every load, store, split, fragment read and the barrier compiled out (timing build, removed) the MFMAs + prologue +
         // epilogue of the 8192 x 1536 x 1536 forward form take 137-143 us either way: 92 us of pure pipe time at the nominal rate.)
         auto mma_block = [&](auto h_tag) {
             constexpr int h = decltype(h_tag)::value;
@@ -278,10 +266,6 @@ __device__ __forceinline__ void x3_tile(GemmF32 g, int tile_m, int tile_n, int z
                 for (int nt = 0; nt < 2; ++nt) {
 #pragma unroll
                     for (int mt = 0; mt < 4; ++mt) {
-                        if constexpr ((X3_DBG & 1) != 0) {
-                            asm volatile("" ::"v"(bf[CUR][nt][PB[q]]), "v"(af[CUR][mt][PA[q]]));
-                            continue;
-                        }
                         acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[CUR][nt][PB[q]], af[CUR][mt][PA[q]], acc[mt][nt], 0, 0, 0);
                     }
                 }
@@ -289,14 +273,12 @@ __device__ __forceinline__ void x3_tile(GemmF32 g, int tile_m, int tile_n, int z
         };
         mma_block(std::integral_constant<int, 0>{});
         // (after the last tile this stages a dummy nobody reads)
-        if constexpr ((X3_DBG & 4) == 0) {
-            x3_store<A_KC>(nb, ra[NXT], t);
-            x3_store<B_KC>(nb + OPND, rb[NXT], t);
-        }
+        x3_store<A_KC>(nb, ra[NXT], t);
+        x3_store<B_KC>(nb + OPND, rb[NXT], t);
         // the register set just staged is free: re-load it with tile + 3 at once (a K-tile and a half ahead of its use; issued behind
         // the second column block instead, one K-tile ahead, the wait for these loads was 17 % of the launch)
-        if constexpr ((X3_DBG & 8) == 0) load(std::integral_constant<int, NXT>{}, tile + 3);
-        if constexpr ((X3_DBG & 64) == 0) {
+        load(std::integral_constant<int, NXT>{}, tile + 3);
+        {
             // issue order of this half: the split and the LDS stores spread over the first 12 MFMAs (so that the stores have landed
             // when the barrier asks), the global loads over the next four.  (Left to itself the scheduler bunches them: 22 MFMAs in
             // a row, then the stores right in front of the barrier's lgkmcnt(0).)
@@ -315,12 +297,11 @@ __device__ __forceinline__ void x3_tile(GemmF32 g, int tile_m, int tile_n, int z
             }
         }
         __builtin_amdgcn_sched_barrier(0);      // (MFMAs of this half must not sink behind the barrier, in front of the fragment reads)
-        if constexpr ((X3_DBG & 128) == 0) __syncthreads();
-        else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __syncthreads();
         // nothing moves across (in particular not the next K-tile's split, plain VALU work on the register set whose loads were
         // issued last: the wait for those loads would come up here with it)
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr ((X3_DBG & 256) == 0) read_frags(std::integral_constant<int, NXT>{});
+        read_frags(std::integral_constant<int, NXT>{});
         __builtin_amdgcn_sched_barrier(0);      // (the scheduler sinks the reads below the MFMAs otherwise: fewer live registers)
         mma_block(std::integral_constant<int, 1>{});
         __builtin_amdgcn_sched_barrier(0);

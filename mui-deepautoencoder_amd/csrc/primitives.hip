@@ -291,15 +291,11 @@ int codae_debug_gemm_bf16_plan(const int32_t* desc, int32_t* out, int32_t capaci
     if (desc[9]) g.colsum_part = &some_rows;          // (the plan only asks whether there is a backward epilogue; nothing is launched)
     CODAE_REQUIRE(gemm_bf16_supported(g.M, g.N, g.K) && g.split_k >= 1, "codae_debug_gemm_bf16_plan: unsupported shape M=%d N=%d K=%d", g.M, g.N, g.K);
     const Bf16Plan p = gemm_bf16_plan(g);
-    const int32_t fields[CODAE_GEMM_PLAN_FIELDS] = {p.family, p.bm, p.bn, p.stages, p.loader, p.epi, p.dbg, p.act, p.store_policy, p.tiles_m, p.tiles_n,
+    const int32_t fields[CODAE_GEMM_PLAN_FIELDS] = {p.family, p.bm, p.bn, p.stages, p.loader, p.epi, p.sched, p.act, p.store_policy, p.tiles_m, p.tiles_n,
                                                     (int32_t)p.workgroups, gemm_bf16_colsum_rows(g), g.loss.enabled ? gemm_bf16_loss_parts(g) : 0,
                                                     gemm_bf16_takes_relu_bits(g.M, g.N) ? 1 : 0};
     for (int i = 0; i < CODAE_GEMM_PLAN_FIELDS; ++i) out[i] = fields[i];
     return CODAE_OK;
-}
-
-int codae_debug_gemm_timeline(uint64_t* host_out, int32_t n_wg) {
-    return gemm_bf16_timeline(reinterpret_cast<unsigned long long*>(host_out), n_wg);
 }
 
 int codae_transpose_bf16(const void* src, void* dst, int32_t rows, int32_t cols, void* stream) {

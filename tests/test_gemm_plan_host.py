@@ -26,7 +26,7 @@ FIELDS = ["family", "bm", "bn", "stages", "loader", "epi", "dbg", "act", "store_
           "colsum_rows", "loss_parts", "takes_relu_bits"]
 COUNT_FIELDS = ("colsum_rows", "loss_parts", "takes_relu_bits")
 KC, KS = 0, 1
-ONE_BARRIER, PIPELINED, ABLATION = 0, 1, 2
+ONE_BARRIER, PIPELINED = 0, 1
 PLAIN, WT, BY_SIZE = 0, 1, -1
 LEAKY = 2
 SWITCHES = ("CODAE_GEMM_TILE", "CODAE_NO_DEEP_SMALL", "CODAE_SMALL_TILE_MAX", "CODAE_SMALL_STAGES", "CODAE_GEMM_DBG", "CODAE_STORE_POLICY")
@@ -121,15 +121,6 @@ case("small-max0-loss-96x192", loss(96, 192), (ONE_BARRIER, 128, 128, 2), SMALL0
 case("small-max0-act-96x192", fwd(96, 192, act=LEAKY), (ONE_BARRIER, 128, 128, 4), SMALL0)
 case("small-stages2-fwd-96x192", fwd(96, 192), (ONE_BARRIER, 64, 64, 2), {"CODAE_SMALL_STAGES": "2"})
 case("small-stages2-act-96x192", fwd(96, 192, act=LEAKY), (ONE_BARRIER, 64, 64, 2), {"CODAE_SMALL_STAGES": "2"})
-for n in ("1", "8"):
-    env = {"CODAE_GEMM_DBG": n}
-    case("dbg%s-fwd-96x192" % n, fwd(96, 192), (ABLATION, 256, 192), env)
-    case("dbg%s-fwd-3328x1024-bwd-plain" % n, fwd(3328, 1024, bwd=1, policy=PLAIN), (ABLATION, 256, 192), env)
-    case("dbg%s-loss-96x192" % n, loss(96, 192), (ABLATION if n == "8" else PIPELINED, 256, 192), env)
-    case("dbg%s-fwd-f32-96x192" % n, fwd(96, 192, f32=1), (PIPELINED, 256, 192), env)
-    case("dbg%s-dgradw-96x192-bwd-cosched" % n, dgrad_w(96, 192, bwd=1, cosched=1), (PIPELINED, 256, 192), env)
-    case("dbg%s-wgrad-1536x1536-split5" % n, wgrad(1536, 1536, 512, 5), (PIPELINED, 256, 192), env)
-    case("dbg%s-act-96x192" % n, fwd(96, 192, act=LEAKY), (ONE_BARRIER, 64, 64, 4), env)
 for pol in ("plain", "wt"):
     env = {"CODAE_STORE_POLICY": pol}
     case("store-%s-by-size-16MB" % pol, fwd(5120, 1536, policy=BY_SIZE), (PIPELINED, 256, 192), env)
@@ -174,9 +165,9 @@ def test_fixture_covers_exactly_the_cases(golden):
     assert sorted(golden["cases"]) == sorted(CASES)
     for name, g in golden["cases"].items():
         assert g["desc"] == CASES[name]["desc"] and g["env"] == CASES[name]["env"], name
-        # the recording commit's own counts differ from the fixture's only under the two switches that misled them
+        # the recording commit's own counts differ from the fixture's only under the switch that misled them
         if "parent_counts" in g:
-            assert set(CASES[name]["env"]) & {"CODAE_GEMM_TILE", "CODAE_GEMM_DBG"}, name
+            assert set(CASES[name]["env"]) & {"CODAE_GEMM_TILE"}, name
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
@@ -214,6 +205,22 @@ def test_forced_mid_tile_leaves_other_forms_to_the_automatic_choice(lib):
             del CASES["_forced"]
         # (the 1-bit mask answer is about the forward form of that output shape, which the switch does move)
         assert {k: v for k, v in forced.items() if k != "takes_relu_bits"} == {k: v for k, v in plain.items() if k != "takes_relu_bits"}, name
+
+
+def test_the_removed_ablation_switch_is_not_read(lib):
+    """CODAE_GEMM_DBG once selected timing builds of the pipelined kernel whose results were wrong by design (family 2).  The
+    builds are gone and the variable is not read: the plan under it is the plan without it, field for field."""
+    for d in (fwd(96, 192), loss(96, 192), fwd(3328, 1024, bwd=1, policy=PLAIN)):
+        CASES["_unset"] = dict(desc=d, want=None, env={})
+        CASES["_dbg8"] = dict(desc=d, want=None, env={"CODAE_GEMM_DBG": "8"})
+        try:
+            unset, dbg8 = query(lib, "_unset"), query(lib, "_dbg8")
+        finally:
+            del CASES["_unset"], CASES["_dbg8"]
+        assert sorted(dbg8) == sorted(FIELDS)
+        for f in FIELDS:
+            assert dbg8[f] == unset[f], (d, f, dbg8, unset)
+        assert dbg8["family"] != 2 and unset["family"] != 2, (d, dbg8)
 
 
 def test_query_refuses_a_short_output_and_a_bad_shape(lib):

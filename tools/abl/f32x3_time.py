@@ -1,5 +1,5 @@
-"""Time one GEMM form of the fp32-from-bf16-planes kernel (CODAE_F32_GEMM=x3 forced) at a given shape; used with the
-timing-only ablation builds of gemm_f32x3.hip (make EXTRA=-DX3_DBG=n OUT=...; CODAE_HIP_LIB=that library).
+"""Time one GEMM form of the fp32-from-bf16-planes kernel (CODAE_F32_GEMM=x3 forced) at a given shape, on the shipped library
+or the one CODAE_HIP_LIB names.
 Usage: python tools/abl/f32x3_time.py [M N K]"""
 import os, sys
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..")

@@ -8,7 +8,6 @@ L = hip.lib()
 M, N = 8192, 1536
 dev = torch.device("cuda:0")
 cfgs = sys.argv[1].split(",") if len(sys.argv) > 1 else ["b", "p"]
-dbgs = sys.argv[2].split(",") if len(sys.argv) > 2 else ["0"]
 g = torch.Generator(device="cpu").manual_seed(0)
 st = hip.current_stream()
 for K in (64, 1536, 3072):
@@ -16,9 +15,8 @@ for K in (64, 1536, 3072):
     W = ((torch.rand(N, K, generator=g) * 2 - 1) * 0.05).to(dev).bfloat16()
     b = torch.randn(N, generator=g).to(dev)
     y = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
-    for c, d in [(c, d) for c in cfgs for d in dbgs]:
+    for c in cfgs:
         os.environ["CODAE_GEMM_TILE"] = c
-        os.environ["CODAE_GEMM_DBG"] = d
         hip.lib().codae_reload_env()
         ts = []
         for rnd in range(5):
@@ -30,4 +28,4 @@ for K in (64, 1536, 3072):
             e1.record(); torch.cuda.synchronize()
             ts.append(e0.elapsed_time(e1) / 20 * 1e3)
         ts.sort()
-        print("K %5d tile %s dbg %s  median %7.2f us   per K-tile %6.3f us" % (K, c, d, ts[2], ts[2] / (K / 64)))
+        print("K %5d tile %s  median %7.2f us   per K-tile %6.3f us" % (K, c, ts[2], ts[2] / (K / 64)))

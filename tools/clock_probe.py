@@ -1,6 +1,6 @@
-"""Long forward GEMM (8192 x 1536 x K, K = 24576 -> ~1 ms) in the ablation variants of the 8-wave
-phase-pipelined kernel; run under `rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace` the counter / 8 /
-duration is the shader clock the chip holds in each regime (MI355X guide, DVFS give-back)."""
+"""Long forward GEMM (8192 x 1536 x K, K = 24576 -> ~1 ms) of the 8-wave phase-pipelined kernel; run under
+`rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace` the counter / 8 / duration is the shader clock the chip holds
+under the kernel's MFMA load (MI355X guide, DVFS give-back)."""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "mui-deepautoencoder_amd"))
 import torch
@@ -15,10 +15,8 @@ b = torch.zeros(N, device=dev)
 y = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
 st = hip.current_stream()
 os.environ["CODAE_GEMM_TILE"] = "q"
-for d in ("0", "1", "2", "0", "1", "2"):
-    os.environ["CODAE_GEMM_DBG"] = d
-    hip.lib().codae_reload_env()
-    for _ in range(3):
-        hip.check(L.codae_linear_bf16(hip.ptr(x), hip.ptr(W), hip.ptr(b), hip.ptr(y), 0, M, N, K, 0, st))
-    torch.cuda.synchronize()
+hip.lib().codae_reload_env()
+for _ in range(6):
+    hip.check(L.codae_linear_bf16(hip.ptr(x), hip.ptr(W), hip.ptr(b), hip.ptr(y), 0, M, N, K, 0, st))
+torch.cuda.synchronize()
 print("done")
