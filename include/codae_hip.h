@@ -69,6 +69,7 @@ extern "C" {
  *      change
  *      (still 11) - the copy-out of the stamped GEMM build's timeline: an entry with no caller outside tools/ was removed; no
  *      layout or enum change
+ *      (still 11) + codae_debug_gemm_bf16: a new entry with plain arguments only, no layout or enum change
  * The binding must refuse a library whose codae_abi_version() differs and must check its own struct sizes against
  * codae_struct_sizes() at load (mui-deepautoencoder_amd/codae/hip/__init__.py does both). */
 #define CODAE_ABI_VERSION 11
@@ -1030,6 +1031,13 @@ int codae_dgrad_act_bf16(const void* dy, const void* W, const void* act_src, voi
  * capacity: room in out, >= CODAE_GEMM_PLAN_FIELDS. */
 #define CODAE_GEMM_PLAN_FIELDS 15
 int codae_debug_gemm_bf16_plan(const int32_t* desc, int32_t* out, int32_t capacity);
+/* One bf16 GEMM launch with the operand modes and leading dimensions spelled out (kernel-level tests of the operand staging; the
+ * entries above fix them per role): C[M][N] = A . B^T (+ bias, ReLU).  a_mode / b_mode 0 = k contiguous (A [M][lda], B [N][ldb]),
+ * 1 = k strided (A [K][lda], B [K][ldb]); ld* in elements.  c_f32 != 0: fp32 C, no bias, no ReLU; split_k > 1 then writes split_k
+ * partial products, M * ldc floats apart, for the caller to add up.  The kernel is the one gemm_bf16's plan picks under the CODAE_*
+ * variables as last read; the descriptor passes the same validation as every other launch. */
+int codae_debug_gemm_bf16(const void* A, int64_t lda, int32_t a_mode, const void* B, int64_t ldb, int32_t b_mode, void* C, int64_t ldc,
+                          int32_t c_f32, int32_t M, int32_t N, int32_t K, int32_t split_k, const float* bias, int32_t relu, void* stream);
 int codae_cast_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream);
 /* The image form of the plain gather on its own (the launcher the engine uses): out[b][:] = mask(image[row_idx[b]][:]) in bf16, rows
  * out_ld elements apart (<= 0: io), bit for bit what codae_corrupt_batch_present(batch, NULL, ..., out_bf16 = 1) writes when image =

@@ -222,6 +222,7 @@ PROTOTYPES = {
     "codae_cast_f32_to_bf16": (C.c_int, [_P, _P, _I64, _P]),
     "codae_corrupt_batch_image": (C.c_int, [C.POINTER(Batch), _P, _P, _I32, _P, _I64, _P]),
     "codae_debug_gemm_bf16_plan": (C.c_int, [_P, _P, _I32]),
+    "codae_debug_gemm_bf16": (C.c_int, [_P, _I64, _I32, _P, _I64, _I32, _P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _I32, _P]),
     "codae_transpose_bf16": (C.c_int, [_P, _P, _I32, _I32, _P]),
 }
 

@@ -48,8 +48,11 @@ constexpr int CH_BIAS = CODAE_CHAIN_MAX_BIAS;        // floats of bias staged in
 typedef __attribute__((address_space(3))) char lds_char;
 typedef __attribute__((address_space(1))) const void gvoid;
 
-__device__ __forceinline__ void glds16(const void* gsrc, lds_char* dst_wave_base) {
-    __builtin_amdgcn_global_load_lds((gvoid*)gsrc, (__attribute__((address_space(3))) void*)dst_wave_base, 16, 0, 0);
+// {wave-uniform base, 32-bit lane offset}: the empty asm keeps the offset's zero-extension in the block of the load, where instruction
+// selection matches `global_load_lds_dwordx4 v, s[..]` (gemm_bf16_halftile.h)
+__device__ __forceinline__ void glds16(const char* base, uint32_t& off, lds_char* dst_wave_base) {
+    asm volatile("" : "+v"(off));
+    __builtin_amdgcn_global_load_lds((gvoid*)(base + off), (__attribute__((address_space(3))) void*)dst_wave_base, 16, 0, 0);
 }
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
@@ -114,8 +117,8 @@ __device__ __forceinline__ void cursor_matrix(WCursor& c, KArgs a, int w, int la
 __device__ __forceinline__ void cursor_issue(WCursor& c, KArgs a, lds_char* ring, int w, int lane) {
     const char* src = c.base + ((int64_t)(16 * c.t) * c.K + c.trip * 64) * 2;          // wave-uniform
     lds_char* dst = ring + c.slot * CH_UNIT;
-    glds16(src + c.off0, dst);
-    glds16(src + c.off1, dst + 1024);
+    glds16(src, c.off0, dst);
+    glds16(src, c.off1, dst + 1024);
     c.slot = c.slot + 1 == CH_RU ? 0 : c.slot + 1;
     if (++c.t == c.T) {
         c.t = 0;

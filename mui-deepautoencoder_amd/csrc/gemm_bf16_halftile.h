@@ -9,8 +9,15 @@ constexpr int BK = 64;
 typedef __attribute__((address_space(3))) char lds_char;
 typedef __attribute__((address_space(1))) const void gvoid;
 
-__device__ __forceinline__ void glds16(const void* gsrc, lds_char* dst_wave_base) {
-    __builtin_amdgcn_global_load_lds((gvoid*)gsrc, (__attribute__((address_space(3))) void*)dst_wave_base, 16, 0, 0);
+// One 16-byte-per-lane LDS-DMA piece from {wave-uniform base, 32-bit lane offset}.  `off` is loop invariant; the empty asm makes it
+// opaque in the block of the load, so its zero-extension stays there and instruction selection (which works block by block) matches
+// the scalar-base form `global_load_lds_dwordx4 v, s[..]`.  Without it LICM hoists the extension out of the K loop, the loop body holds
+// `sgpr64 + vgpr64` with an upper half nobody can prove zero, and every piece becomes `v_lshl_add_u64 v[..], s[..], 0, v[..]` +
+// `global_load_lds_dwordx4 v[..], off` on a register PAIR per lane offset (tests/test_kloop_dma_isa_host.py keeps it).
+// The builtin stays, so sched_group_barrier still counts the piece as a VMEM load.
+__device__ __forceinline__ void glds16(const char* base, uint32_t& off, lds_char* dst_wave_base) {
+    asm volatile("" : "+v"(off));
+    __builtin_amdgcn_global_load_lds((gvoid*)(base + off), (__attribute__((address_space(3))) void*)dst_wave_base, 16, 0, 0);
 }
 
 template <int N>
@@ -74,7 +81,8 @@ __device__ __forceinline__ int ks_from_lds_block(int lds_block, int kr) {
 // places with its `it`-th LDS-DMA instruction of half-tile h (instruction j = it * NW + w writes img + j * 1024 +
 // lane * 16).  Everything here is loop invariant; the K advance is wave-uniform and goes into the scalar base, so the
 // DMA instruction takes {SGPR base, 32-bit VGPR offset}: half the address registers of per-lane 64-bit pointers and no
-// 64-bit VALU add per issue (operands are < 4 GiB: checked at launch).
+// 64-bit VALU add per issue (operands are < 4 GiB: checked at launch) - in the K loop too since glds16 keeps the offset's
+// zero-extension inside the loop body; up to then only the prologue's pieces had that form.
 template <int MODE, int RH, int S, int NW>
 __device__ __forceinline__ uint32_t half_src(int64_t ld, int r0, int rmax, int h, int it, int w, int lane) {
     const int j = it * NW + w;

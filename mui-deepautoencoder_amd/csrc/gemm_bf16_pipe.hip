@@ -224,7 +224,7 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
             const char* base = a_base + (int64_t)(tile < nkt ? tile : nkt - 1) * a_step;      // wave-uniform
             lds_char* img = a_img(tile, h);
 #pragma unroll
-            for (int it = 0; it < NA; ++it) glds16(base + a_src[h][it], img + (it * NLA + w) * 1024);
+            for (int it = 0; it < NA; ++it) glds16(base, a_src[h][it], img + (it * NLA + w) * 1024);
         }
     };
     auto issue_b = [&](int tile, int h) {
@@ -232,7 +232,7 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
             const char* base = b_base + (int64_t)(tile < nkt ? tile : nkt - 1) * b_step;
             lds_char* img = b_img(tile, h);
 #pragma unroll
-            for (int it = 0; it < NB; ++it) glds16(base + b_src[h][it], img + (it * NLB + w) * 1024);
+            for (int it = 0; it < NB; ++it) glds16(base, b_src[h][it], img + (it * NLB + w) * 1024);
         }
     };
 
@@ -286,8 +286,14 @@ __device__ __forceinline__ void gemm_bf16_pipe_tile(const GemmBf16& g, int tiles
     constexpr int KEEP_A = A_MODE == OP_KC ? 2 * TMH : 0, KEEP_B = B_MODE == OP_KC ? 2 * TNH : 0;
     // one K-tile; `a0` holds A0(t), `a0n` receives A0(t+1).  Reads of a tile past the end fetch the
     // dummy re-load and are never multiplied (see the settle block behind the loop).
-    // Issue order inside a phase (k-contiguous operands): an MFMA right behind the barrier, then the fragment reads of the NEXT phase
-    // one per MFMA, then this wave's LDS-DMA pieces one per MFMA, then the rest of the 12 MFMAs.  Measured against the
+    // Issue order inside a phase (k-contiguous operands): the group barriers below ASK for an MFMA right behind the barrier, then the
+    // fragment reads of the NEXT phase one per MFMA, then this wave's LDS-DMA pieces one per MFMA, then the rest of the 12 MFMAs.  What
+    // the compiler EMITS is: one MFMA, ALL of the phase's LDS-DMA pieces back to back (each behind its m0 write), then the reads one
+    // per MFMA, then the remaining MFMAs - the pieces are issued in front of the reads in program order (issue_a / read_a) and write
+    // LDS the reads might alias, so no group barrier can move them behind the reads.  That emitted order is the one all the numbers here
+    // were taken on, and it is the faster one: with the reads in front of the pieces in program order the code object has exactly the
+    // requested order (reads one per MFMA, then pieces one per MFMA, no s_nop left) and the whole C3 step is 5.0 us SLOWER (1.1225 ->
+    // 1.1275 ms, slower in all ten alternating pairs).  Measured against the
     // compiler's own order with the phases pinned (phase_barrier), whole C3 step on one box, three alternating runs each:
     // 1.190 -> 1.182 ms (forward 35.4 -> 34.9 us, data gradient 38.3 -> 37.7, fused loss 54.7 -> 52.4); DMA pieces first: 1.197;
     // reads and DMA pieces paired behind the first six MFMAs: 1.191; all reads at once behind the first MFMA: 1.206; three more

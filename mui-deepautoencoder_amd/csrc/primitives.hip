@@ -298,6 +298,24 @@ int codae_debug_gemm_bf16_plan(const int32_t* desc, int32_t* out, int32_t capaci
     return CODAE_OK;
 }
 
+int codae_debug_gemm_bf16(const void* A, int64_t lda, int32_t a_mode, const void* B, int64_t ldb, int32_t b_mode, void* C, int64_t ldc,
+                          int32_t c_f32, int32_t M, int32_t N, int32_t K, int32_t split_k, const float* bias, int32_t relu, void* stream) {
+    CODAE_REQUIRE(A && B && C, "codae_debug_gemm_bf16: null operand");
+    CODAE_REQUIRE((a_mode == OP_KC || a_mode == OP_KS) && (b_mode == OP_KC || b_mode == OP_KS), "codae_debug_gemm_bf16: operand modes %d, %d", a_mode, b_mode);
+    CODAE_REQUIRE(split_k >= 1 && (c_f32 ? (bias == nullptr && !relu) : split_k == 1), "codae_debug_gemm_bf16: epilogue and output kind do not go together");
+    CODAE_REQUIRE(lda >= (a_mode == OP_KC ? K : M) && ldb >= (b_mode == OP_KC ? K : N) && ldc >= N,
+                  "codae_debug_gemm_bf16: a leading dimension is shorter than its row");
+    GemmBf16 g{};
+    g.A = reinterpret_cast<const bf16_t*>(A); g.lda = lda; g.a_mode = a_mode;
+    g.B = reinterpret_cast<const bf16_t*>(B); g.ldb = ldb; g.b_mode = b_mode;
+    g.C = C; g.ldc = ldc; g.c_f32 = c_f32 != 0 ? 1 : 0;
+    g.M = M; g.N = N; g.K = K;
+    g.bias = bias; g.split_k = split_k;
+    g.store_policy = store_policy_for((int64_t)M * N * (c_f32 ? 4 : 2));
+    set_activation(g, relu != 0, CODAE_ACT_NONE, nullptr);
+    return gemm_bf16(g, (hipStream_t)stream);
+}
+
 int codae_transpose_bf16(const void* src, void* dst, int32_t rows, int32_t cols, void* stream) {
     CODAE_REQUIRE(src && dst && rows > 0 && cols > 0, "transpose: bad args");
     const int64_t off = 0;
