@@ -70,6 +70,7 @@ extern "C" {
  *      (still 11) - the copy-out of the stamped GEMM build's timeline: an entry with no caller outside tools/ was removed; no
  *      layout or enum change
  *      (still 11) + codae_debug_gemm_bf16: a new entry with plain arguments only, no layout or enum change
+ *      (still 11) + codae_debug_step_plan, CODAE_STEP_PLAN_FIELDS: a new host-only entry with plain arguments, no layout or enum change
  * The binding must refuse a library whose codae_abi_version() differs and must check its own struct sizes against
  * codae_struct_sizes() at load (mui-deepautoencoder_amd/codae/hip/__init__.py does both). */
 #define CODAE_ABI_VERSION 11
@@ -624,9 +625,36 @@ int codae_dp_destroy(codae_handle h);
  * GLOBAL batch rows.  (What DistributedDataParallel's bucket hooks + optimizer.step do around script/train_dae_on_embedding.py:210-215.) */
 int codae_train_step_dp(codae_handle h, const codae_buffers* bufs, const codae_batch* batch, const codae_hyper* hyper,
                         int32_t n_buckets, const int32_t* bucket_lo, const int32_t* bucket_hi, void* stream);
-/* 1 if codae_train_step / codae_eval_step with B rows run the persistent chain on this engine and these buffers, 0 if the
- * per-layer launches (tests and bench lines name the path they measured) */
+/* 1 if codae_train_step with B rows runs the persistent chain on this engine and these buffers, 0 if the per-layer launches
+ * (tests and bench lines name the path they measured).  Only the fused training step takes the chain: codae_eval_step, the
+ * step-by-step entries and codae_train_step_dp always run the per-layer launches.  It is field `path` of codae_debug_step_plan. */
 int codae_step_path(codae_handle h, const codae_buffers* bufs, int32_t B);
+/* Host-only query (no HIP call is made, no device needed; the members of bufs are only tested for null, never read through):
+ * which launches a call makes on this engine with its settings as they stand and the CODAE_* variables as codae_create read them.
+ * Every entry point that issues a step, or a part of one, asks the same function once and hands the answer down; this entry pins
+ * it in tests.
+ *   call[8]: kind (0 codae_train_step, 1 codae_step_forward_loss with a hyper, 2 codae_eval_step, 3 a range of the step's backward
+ *            - codae_step_backward, _async, the buckets of codae_train_step_dp -, 4 codae_backward, 5 codae_step_update), B,
+ *            layer_lo, layer_hi (kinds 3 and 4), join (kind 3: 0 for _async and the buckets), dx wanted (kind 4), out_y given
+ *            (kinds 1 and 2), clipping on (max_grad_norm > 0; kinds 0 and 5)
+ *   out[CODAE_STEP_PLAN_FIELDS], 0 wherever the call has no such part:
+ *            rows           B as the kernels see it (bf16: padded to 64)
+ *            path           0 per-layer launches, 1 persistent chain
+ *            loss           0 none, 1 stand-alone kernels, 2 fused into the last forward GEMM, 3 inside the chain kernel
+ *            loss_finish    0 none, 1 a launch of its own, 2 carried by the bias finish that ends the backward
+ *            wgrad          0 per layer, beside the data gradients; after them in one grouped launch of 1 the pipelined 256 x 192
+ *                           tile, 2 the one-barrier kernel, 3 the exact-fp32 engine's bf16-plane kernel
+ *            streams        1 or 2: the per-layer weight gradients go to the side stream (a grouped launch stays on the caller's)
+ *            tail_on_caller layer 0's weight gradient runs on the caller's stream, third slab buffer
+ *            bias_finish    0 none in this call (left pending), 1 a launch of its own, 2 trailing workgroups of the grouped launch
+ *            norm           0 no clipping, 1 sum g^2 gathered by the backward's launches, 2 a flat pass in the update
+ *            update         0 none, 1 the flat kernel + transposes, 2 one tiled pass
+ * Not in the plan: whether the gather reads the registered bf16 image (that depends on the batch's pointers and alignment), and
+ * what one call leaves for the next (pending bias rows, cleared norm scalars, a dropped forward, side-stream work not yet joined).
+ * CODAE_E_INVALID for a null argument, capacity < CODAE_STEP_PLAN_FIELDS, an unknown kind, B outside (0, max_batch] (kind 5
+ * takes none) or a layer range outside the stack. */
+#define CODAE_STEP_PLAN_FIELDS 10
+int codae_debug_step_plan(codae_handle h, const codae_buffers* bufs, const int32_t* call, int32_t* out, int32_t capacity);
 /* Input noise of every training step that follows - codae_train_step, codae_train_step_graph (a change re-captures the
  * graph; under replay the step index is read from scalars[CODAE_S_ADAM_STEP]), codae_step_forward_loss with a hyper (the
  * torch.distributed data-parallel path) and codae_train_step_dp, each with hyper->step as the counter's step.  NULL or

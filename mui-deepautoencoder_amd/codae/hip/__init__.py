@@ -209,6 +209,7 @@ PROTOTYPES = {
     "codae_retrieval_metrics_batched": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _I64, _P, _P, _I32, _P,
                                                   _P, _P, _I32, _P, _I32, _P, _P, _P, _P, _P]),
     "codae_step_path": (C.c_int, [_P, _P, _I32]),
+    "codae_debug_step_plan": (C.c_int, [_P, C.POINTER(Buffers), _P, _P, _I32]),
     "codae_linear_f32": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _P]),
     "codae_dgrad_f32": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P]),
     "codae_wgrad_f32": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P]),

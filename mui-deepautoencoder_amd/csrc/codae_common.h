@@ -524,16 +524,32 @@ int launch_mse_dense(const float* x, const float* y, const float* fmask, float* 
 int launch_sumsq(const float* g, int64_t n, double* out, hipStream_t s);
 int launch_sumsq_to(const float* g, int64_t n, double* acc, hipStream_t s);      // *acc += sum g^2 (one address, <= 64 blocks)
 int launch_clip_coef(const double* total_sq, float max_norm, double* coef_out, hipStream_t s);
-// coef_in != null: use that precomputed clip coefficient instead of folding grad_sq + slots
-// step_dev != null: take the step count (bias corrections) from that device scalar instead of hp->step
-// opt: the optimizer setting (codae_optimizer; null or the default = Adam with L2 decay and a constant lr, the instantiation this
-// launcher always ran); vmax: AMSGrad's running maximum, at the same offset as p / m / v (a span passes vmax + lo)
-int launch_clip_adam(float* p, float* g, float* m, float* v, int64_t n, const codae_hyper* hp,
-                     const double* grad_sq, bf16_t* shadow, const double* coef_in, hipStream_t s,
-                     const double* step_dev = nullptr, const codae_optimizer* opt = nullptr, float* vmax = nullptr,
-                     const codae_weight_average* wa = nullptr, float* avg = nullptr);
-// wa / avg (both launchers): the weight-average setting (null or kind OFF = the instantiations without it) and the average at the
-// same offset as p (a span passes avg + lo; wa->avg itself is not read here)
+// clip_grad_norm_'s sum g^2 of a flat gradient vector into scalars[CODAE_S_GRAD_SQ] (+ its slots); clear: zero them first (a caller
+// whose step's loss finish has not already done so)
+int launch_grad_sumsq(const float* g, int64_t n, double* scalars, bool clear, hipStream_t s);
+// The vectors one update launch walks, element for element: parameters, gradients, the moments, AMSGrad's running maximum, the
+// weight average, the bf16 shadow (each of the last three null when its feature is off).  at(lo): the same vectors from element lo on.
+struct ParamVectors {
+    float *p, *g, *m, *v, *vmax, *avg;
+    bf16_t* shadow;
+    ParamVectors at(int64_t lo) const {
+        return {p ? p + lo : p, g ? g + lo : g, m ? m + lo : m, v ? v + lo : v, vmax ? vmax + lo : vmax, avg ? avg + lo : avg,
+                shadow ? shadow + lo : shadow};
+    }
+};
+// One update launch over x[0, n).  grad_sq: the sum g^2 scalar the clip coefficient is folded from (with its slots); coef_in != null:
+// use that precomputed coefficient instead; step_dev != null: take the step count (bias corrections) from that device scalar instead
+// of hp->step; opt: the optimizer setting (codae_optimizer; null or the default = Adam with L2 decay and a constant lr, the
+// instantiation the launchers always ran); wa: the weight-average setting (null or kind OFF = the instantiations without it; the
+// average itself is x.avg - wa->avg is not read here)
+struct UpdateLaunch {
+    ParamVectors x; int64_t n;
+    const codae_hyper* hp; const double* grad_sq; const double* coef_in; const double* step_dev;
+    const codae_optimizer* opt; const codae_weight_average* wa;
+};
+// the argument checks both update launchers make, the error texts prefixed with `who`
+int check_update_launch(const char* who, const UpdateLaunch& u);
+int launch_update(const UpdateLaunch& u, hipStream_t s);      // the flat kernel over x[0, u.n)
 // CODAE_E_INVALID as codae_set_weight_average documents (need_avg: the avg pointer is checked too); canonical: only the fields the
 // kind reads; launch_weight_average: the stand-alone kernel, nothing launched on a step that does not sample
 bool weight_average_is_off(const codae_weight_average* w);
@@ -547,12 +563,14 @@ bool optimizer_is_default(const codae_optimizer* o);
 codae_optimizer optimizer_canonical(const codae_optimizer* o);
 int launch_set_scalar(double* dst, double value, hipStream_t s);
 // bf16 engine: Adam over the weight matrices in tiles, writing the bf16 shadow AND (layers >= transposed_from) the
-// transposed shadow in the same pass; the flat bias block [bias_off, bias_off + bias_n) rides along
-int launch_clip_adam_tiled(float* p, float* g, float* m, float* v, const codae_hyper* hp, const double* grad_sq,
-                           bf16_t* shadow, bf16_t* shadow_t, int n_layers, const int64_t* w_off, const int* rows,
-                           const int* cols, int transposed_from, int64_t bias_off, int64_t bias_n, hipStream_t s,
-                           const double* step_dev = nullptr, const codae_optimizer* opt = nullptr, float* vmax = nullptr,
-                           const codae_weight_average* wa = nullptr, float* avg = nullptr);
+// transposed shadow in the same pass; the flat bias block [bias_off, bias_off + bias_n) rides along (u.n: the whole vector's length; u.coef_in stays null: the kernel takes none)
+struct UpdateTiles {
+    bf16_t* shadow_t;
+    int n_layers; const int64_t* w_off; const int* rows; const int* cols;     // the layer table: element offset and shape of each matrix
+    int transposed_from;
+    int64_t bias_off, bias_n;
+};
+int launch_update_tiled(const UpdateLaunch& u, const UpdateTiles& t, hipStream_t s);
 // dst[c][r] = src[r][c] for n bf16 matrices (element offsets off[i], shapes rows[i] x cols[i]) in one launch
 // tied weights (tied.hip; include/codae_hip.h, "Tied weights"): the fold of the decoder gradients into the encoder's, and the mirror of
 // the encoder matrices into the decoder's fp32 image and (when given) its two bf16 shadows

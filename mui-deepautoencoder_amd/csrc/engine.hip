@@ -221,6 +221,15 @@ struct DpState {
 
 namespace {
 
+// the next record of the launch profile for a launch of class `kind`, counted as `count` launches; -1: not profiled
+int prof_take_slot(codae_engine* e, int kind, int count) {
+    if (!(e->prof_on && ((e->prof_mask >> kind) & 1u) && (e->prof_step % e->prof_every) == 0 && e->prof_n < (int)e->prof_start.size())) return -1;
+    const int slot = e->prof_n++;
+    e->prof_kind[slot] = kind;
+    e->prof_count[slot] = count;
+    return slot;
+}
+
 // records a start/stop event pair around the launches made while it is alive
 struct ProfScope {
     codae_engine* e;
@@ -228,13 +237,8 @@ struct ProfScope {
     int slot = -1;
     ProfScope(codae_engine* e_, int kind, hipStream_t s_) : e(e_), s(s_) {
         if (e->prof_group && kind == CODAE_K_GEMM_FWD) return;
-        if (e->prof_on && ((e->prof_mask >> kind) & 1u) && (e->prof_step % e->prof_every) == 0 &&
-            e->prof_n < (int)e->prof_start.size()) {
-            slot = e->prof_n++;
-            e->prof_kind[slot] = kind;
-            e->prof_count[slot] = 1;
-            (void)hipEventRecord(e->prof_start[slot], s);
-        }
+        slot = prof_take_slot(e, kind, 1);
+        if (slot >= 0) (void)hipEventRecord(e->prof_start[slot], s);
     }
     // the launches made inside count as `n` of this class (a grouped launch: one record, reported as n launches of elapsed / n)
     void counts_as(int n) { if (slot >= 0) e->prof_count[slot] = n; }
@@ -251,14 +255,8 @@ struct GroupScope {
     hipStream_t s;
     int slot = -1;
     GroupScope(codae_engine* e_, int kind, hipStream_t s_) : e(e_), s(s_) {
-        if (e->prof_on && ((e->prof_mask >> kind) & 1u) && (e->prof_step % e->prof_every) == 0 &&
-            e->prof_n < (int)e->prof_start.size()) {
-            slot = e->prof_n++;
-            e->prof_kind[slot] = kind;
-            e->prof_count[slot] = 0;
-            e->prof_group = true;
-            (void)hipEventRecord(e->prof_start[slot], s);
-        }
+        slot = prof_take_slot(e, kind, 0);
+        if (slot >= 0) { e->prof_group = true; (void)hipEventRecord(e->prof_start[slot], s); }
     }
     void launched() { if (slot >= 0) ++e->prof_count[slot]; }
     void close() {
@@ -270,13 +268,7 @@ struct GroupScope {
 // A class of work that has no launch of its own in this step because it rides in the launch recorded just before it (the bias finish
 // inside the grouped weight-gradient launch): one record of that class with 0 ms and no event pair, where the host would have issued
 // the launch - the profile keeps listing every class of the step in issue order, and the carrying launch keeps its whole time.
-void prof_rides_along(codae_engine* e, int kind) {
-    if (e->prof_on && ((e->prof_mask >> kind) & 1u) && (e->prof_step % e->prof_every) == 0 && e->prof_n < (int)e->prof_start.size()) {
-        const int slot = e->prof_n++;
-        e->prof_kind[slot] = kind;
-        e->prof_count[slot] = -1;
-    }
-}
+void prof_rides_along(codae_engine* e, int kind) { (void)prof_take_slot(e, kind, -1); }
 
 // exact-fp32 weight gradient (128 x 128 tiles, two workgroups per CU): enough K ranges for ~1.5 workgroups per CU - a
 // 1536 x 1536 gradient is 144 tiles, whose 8192-row reductions were the critical path of the whole backward (0.97 ms per
@@ -348,52 +340,197 @@ int check_common(codae_handle h, const codae_buffers* b, int B) {
     return CODAE_OK;
 }
 
+// The pending bias-finish jobs of the layers from `from` on, at most `cap` of them, into t - BiasFinishJobs or BiasFold: the same
+// members, two structs because the second travels in a kernel-argument block.  The rows taken are no longer pending; returns the
+// layer the walk stopped at.
+template <typename Table>
+int take_bias_jobs(codae_engine* e, const codae_buffers* b, int from, int cap, Table& t) {
+    t.n = 0;
+    int cols = 0, l = from;
+    for (; l < e->L && t.n < cap; ++l) {
+        if (e->parts_pending[l] <= 0) continue;
+        t.parts[t.n] = part_ptr(e, b, l);
+        t.out[t.n] = b->grads + e->b_off[l];
+        t.rows[t.n] = e->parts_pending[l];
+        t.cols[t.n] = e->out[l];
+        t.col_begin[t.n] = cols;
+        cols += e->out[l];
+        ++t.n;
+        e->parts_pending[l] = 0;
+    }
+    t.col_begin[t.n] = cols;
+    return l;
+}
+
+bool bias_pending_from(const codae_engine* e, int from) {
+    for (int l = from; l < e->L; ++l)
+        if (e->parts_pending[l] > 0) return true;
+    return false;
+}
+
 // db_l = sum of layer l's pending partial column-sum rows, in row order (every layer with pending rows, one launch);
 // with_norm: += sum db^2 into the clip_grad_norm_ slots
 int finish_bias(codae_engine* e, const codae_buffers* b, hipStream_t s, bool with_norm, const LossFinish* loss = nullptr) {
+    double* sumsq = with_norm ? b->scalars + CODAE_S_GRAD_SQ : nullptr;
     BiasFinishJobs jobs;
-    jobs.n = 0;
-    int cols = 0;
-    for (int l = 0; l < e->L; ++l) {
-        if (e->parts_pending[l] <= 0) continue;
-        if (jobs.n == 64) {                                   // (more than 64 layers pending: several launches)
-            jobs.col_begin[jobs.n] = cols;
-            int rc = launch_bias_finish(jobs, with_norm ? b->scalars + CODAE_S_GRAD_SQ : nullptr, s);
-            if (rc) return rc;
-            jobs.n = 0; cols = 0;
-        }
-        jobs.parts[jobs.n] = part_ptr(e, b, l);
-        jobs.out[jobs.n] = b->grads + e->b_off[l];
-        jobs.rows[jobs.n] = e->parts_pending[l];
-        jobs.cols[jobs.n] = e->out[l];
-        jobs.col_begin[jobs.n] = cols;
-        cols += e->out[l];
-        ++jobs.n;
-        e->parts_pending[l] = 0;
+    for (int l = take_bias_jobs(e, b, 0, 64, jobs); bias_pending_from(e, l); l = take_bias_jobs(e, b, l, 64, jobs)) {
+        int rc = launch_bias_finish(jobs, sumsq, s);              // (more than 64 layers pending: several launches)
+        if (rc) return rc;
     }
     if (jobs.n == 0) return CODAE_OK;
-    jobs.col_begin[jobs.n] = cols;
     ProfScope prof(e, CODAE_K_BIAS_FINISH, s);
-    return launch_bias_finish(jobs, with_norm ? b->scalars + CODAE_S_GRAD_SQ : nullptr, s, loss);
+    return launch_bias_finish(jobs, sumsq, s, loss);
 }
+
+// The same finish (with_norm / loss as finish_bias takes them) as the job table of the pipelined grouped weight-gradient launch;
+// false - nothing taken, finish_bias runs as always - when there is nothing pending or more than fits
+bool fold_bias_finish(codae_engine* e, const codae_buffers* b, bool with_norm, const LossFinish* loss, BiasFold* f) {
+    int n = 0;
+    for (int l = 0; l < e->L; ++l) n += e->parts_pending[l] > 0 ? 1 : 0;
+    if (n == 0 || n > CODAE_GROUP_MAX) return false;
+    *f = BiasFold{};
+    take_bias_jobs(e, b, 0, CODAE_GROUP_MAX, *f);
+    f->sumsq = with_norm ? b->scalars + CODAE_S_GRAD_SQ : nullptr;
+    if (loss != nullptr) f->loss = *loss;
+    return true;
+}
+
+// ---- the step plan: which launches a call makes, decided once ----------------------------------------------------------------
+// Every entry point that issues a step, or a part of one, describes its call (StepCall) and asks step_plan; the code below it reads the
+// answer and decides nothing again.  Not in the plan: whether the gather reads the bf16 image - that depends on the batch's pointers
+// and alignment (gathers_from_image) - and what one call leaves behind for the next, which stays state in the handle:
+// parts_pending, norm_scalars_zero, drop_live, w_pending.  The plan is derived per call, never stored (the graph key does not see it).
+// (include/codae_hip.h, codae_debug_step_plan, says what every value means; the weight-gradient values are the ones they always had)
+enum StepKind { STEP_TRAIN = 0, STEP_FORWARD_LOSS = 1, STEP_EVAL = 2, STEP_BACKWARD = 3, STEP_DROPIN_BACKWARD = 4, STEP_UPDATE = 5 };
+struct StepCall {
+    int kind, B;
+    int layer_lo, layer_hi;          // the backward's range [lo, hi)
+    bool join;                       // the call returns with the caller's stream waiting for the side stream
+    bool want_dx, has_out_y;         // drop-in backward: an input gradient is asked for; forward: the caller takes y
+    bool clip;                       // max_grad_norm > 0
+};
+enum { PATH_LAYERS = 0, PATH_CHAIN = 1 };
+enum { LOSS_NONE = 0, LOSS_STANDALONE = 1, LOSS_FUSED = 2, LOSS_IN_CHAIN = 3 };
+enum { LOSS_FINISH_NONE = 0, LOSS_FINISH_OWN = 1, LOSS_FINISH_CARRIED = 2 };
+enum { WGRAD_PER_LAYER = 0, WGRAD_GROUPED_PIPE = 1, WGRAD_GROUPED_ONE_BARRIER = 2, WGRAD_GROUPED_F32 = 3 };
+enum { BIAS_FINISH_NONE = 0, BIAS_FINISH_OWN = 1, BIAS_FINISH_FOLDED = 2 };
+enum { NORM_NONE = 0, NORM_FROM_BACKWARD = 1, NORM_FLAT = 2 };
+enum { UPDATE_NONE = 0, UPDATE_FLAT = 1, UPDATE_TILED = 2 };
+struct StepPlan {
+    int rows;                // rows_for(B)
+    int path, loss, loss_finish, wgrad;
+    int streams;             // 2: the call's per-layer weight gradients go to the side stream (a grouped schedule keeps to the caller's)
+    int tail_on_caller;      // layer 0's weight gradient runs on the caller's stream (third slab buffer)
+    int bias_finish, norm, update;
+};
 
 // Every 16 rows stream all the weights from L2.  Up to 128 workgroups (16 per XCD) that costs nothing extra per row: 3 x 128
 // stack, ms / step chain vs per-layer: 1024 rows 0.158 / 0.31, 2048 rows 0.161 / 0.31.  With every CU streaming (4096 rows:
 // 0.83 / 0.34, 8192: 1.71 / 0.40) the XCDs' L2s cannot feed them and the per-layer GEMMs (weights read once per 256 rows) win.
 constexpr int CHAIN_MAX_ROWS = 2048;
 
-bool chain_eligible(codae_engine* e, const codae_buffers* b, int B) {
-    // (the chain kernel fuses the plain gather and the unweighted loss and keeps the activations to itself: a noised input, an
-    //  emphasised loss, another criterion, hidden dropout or a slot-presence table takes the per-layer launches)
-    return e->chain_ok && e->plain_mse() && e->tc.noise.kind == CODAE_NOISE_NONE && !e->tc.drop.on && b->shadow_wt != nullptr &&
-           e->rows_for(B) <= CHAIN_MAX_ROWS;
+bool two_streams(const codae_engine* e) { return !e->cfg.single_stream; }
+
+// Wide bf16 stack, single-GPU fused step: every layer's weight gradient in ONE launch of 256 x 192 tiles with K = the whole batch
+// (no split-K slabs, no reduce pass; sum g^2 from the epilogue), issued AFTER the data-gradient chain, which then has the chip to
+// itself.  Needs dA_l of every layer alive at once (n_dact > L) and enough tiles in total to fill the chip (C3: 48 tiles per
+// layer -> round 2 split K five ways: 47 MB of fp32 slabs written and read back per layer, 0.28 ms of reduce launches per step;
+// all ten together: 480 tiles on 256 CUs).  Small batches gain even more: their per-layer launches are all fixed cost (3 x 512 at the
+// reference's stock batch 128: 0.436 -> 0.402 ms/step; batch 512: 0.663 -> 0.433).
+// Stacks too narrow to fill the chip with the big tile take the one-barrier kernel's grouped launch instead.
+int grouped_wgrad_strategy(const codae_engine* e, int rows) {
+    if (e->prec == CODAE_PREC_F32) {
+        // the exact-fp32 engine on the bf16-plane GEMMs - every weight gradient in one launch of gemm_f32x3_grouped_kernel, K unsplit
+        // (what the pipelined grouped launch is to the bf16 engine: per layer it is 144 tiles, split 7 ways into fp32 slabs and reduced:
+        // 0.2 ms of reduce launches per C3 step and a prologue / epilogue per 37 K-tiles)
+        if (env().f32_gemm == 1 || e->cfg.no_defer_wgrad || e->cfg.single_stream || e->L > CODAE_GROUP_MAX || e->n_dact <= e->L || rows < 256 ||
+            rows % 32 != 0)
+            return WGRAD_PER_LAYER;
+        int total = 0;
+        for (int l = 0; l < e->L; ++l) {
+            if (e->in[l] % 4 != 0 || e->out[l] % 4 != 0) return WGRAD_PER_LAYER;
+            total += tile_count(e->out[l], e->in[l], TILE_128x128);
+        }
+        return total >= 256 ? WGRAD_GROUPED_F32 : WGRAD_PER_LAYER;
+    }
+    if (e->prec != CODAE_PREC_BF16 || e->cfg.no_defer_wgrad || e->cfg.single_stream || e->L > CODAE_GROUP_MAX || e->n_dact <= e->L || rows < 64)
+        return WGRAD_PER_LAYER;
+    int total = 0, total_small = 0;
+    for (int l = 0; l < e->L; ++l) {
+        total += tile_count(e->out[l], e->in[l], TILE_256x192);        // (gemm_bf16_pipe_grouped)
+        total_small += tile_count(e->out[l], e->in[l], TILE_64x64);     // (gemm_bf16_grouped, its smallest tile)
+        if ((int64_t)rows * e->out_ld[l] * 2 >= (int64_t)1 << 32 || (int64_t)rows * e->in_ld[l] * 2 >= (int64_t)1 << 32) return WGRAD_PER_LAYER;
+    }
+    // (round 3 first kept the per-layer backward when one layer alone fills the chip - C5: 31.2 ms/step against 32.9 grouped; with
+    //  the 4 x 8 tile order of the pipelined kernel the grouped launch wins there too: 29.5 against 30.2)
+    if (total >= 200) return WGRAD_GROUPED_PIPE;
+    return total_small >= 128 ? WGRAD_GROUPED_ONE_BARRIER : WGRAD_PER_LAYER;
 }
 
-// gather + forward chain + loss (+ data-gradient chain) of a narrow stack: one launch; then the loss finish
-// (backward: the loss finish is left to the caller's bias-finish launch - *loss_out describes it - and the kernel zeroes
-//  the norm accumulators)
-int run_chain(codae_engine* e, const codae_buffers* b, const codae_batch* batch, const codae_hyper* hyper, bool backward,
-              hipStream_t s, LossFinish* loss_out = nullptr) {
+// The one place that reads the engine's cfg toggles and tc settings to choose launches.  Pure: no HIP call, nothing written; the
+// buffers are only tested for null (shadow_wt here; slabs and bias_parts by the launches that need them).
+StepPlan step_plan(const codae_engine* e, const codae_buffers* b, const StepCall& c) {
+    StepPlan p{};
+    p.rows = e->rows_for(c.B);
+    p.streams = 1;
+    const bool bf = e->prec == CODAE_PREC_BF16;
+    const bool forward = c.kind == STEP_TRAIN || c.kind == STEP_FORWARD_LOSS || c.kind == STEP_EVAL;
+    const bool backward = c.kind == STEP_TRAIN || c.kind == STEP_BACKWARD || c.kind == STEP_DROPIN_BACKWARD;
+    const bool training = c.kind == STEP_TRAIN || c.kind == STEP_FORWARD_LOSS;       // (the forward has a hyper)
+    // (the chain kernel fuses the plain gather and the unweighted loss and keeps the activations to itself: a noised input, an
+    //  emphasised loss, another criterion, hidden dropout or a slot-presence table takes the per-layer launches)
+    if (c.kind == STEP_TRAIN && e->chain_ok && e->plain_mse() && e->tc.noise.kind == CODAE_NOISE_NONE && !e->tc.drop.on &&
+        b->shadow_wt != nullptr && p.rows <= CHAIN_MAX_ROWS) {
+        // narrow stack: persistent fused chain + grouped weight gradients (4 launches for the whole step)
+        p.path = PATH_CHAIN;
+        p.loss = LOSS_IN_CHAIN; p.loss_finish = LOSS_FINISH_CARRIED;
+        p.wgrad = WGRAD_GROUPED_ONE_BARRIER; p.bias_finish = BIAS_FINISH_OWN;
+    } else {
+        if (forward) {
+            // bf16 training step: the loss is folded into the last forward GEMM's epilogue (y never stored)
+            // (not with loss emphasis or a criterion other than the MSE: those live in stand-alone kernels)
+            // (nor with a slot-presence table: the stand-alone kernels carry the predicate, the GEMM epilogue does not)
+            const bool fused = bf && training && !c.has_out_y && !e->cfg.no_fused_loss && e->plain_mse();
+            p.loss = fused ? LOSS_FUSED : LOSS_STANDALONE;
+            // the fused step leaves the fused loss's finish - 5 us of a one-block launch plus a launch boundary between the loss GEMM
+            // and the first data gradient - to the bias-finish launch that ends its backward, as the chain path does
+            p.loss_finish = fused && c.kind == STEP_TRAIN && !e->cfg.no_folded_loss_finish ? LOSS_FINISH_CARRIED : LOSS_FINISH_OWN;
+        }
+        if (backward) {
+            const bool step_mode = c.kind != STEP_DROPIN_BACKWARD;
+            const bool whole = c.layer_lo == 0 && c.layer_hi == e->L;
+            p.streams = two_streams(e) ? 2 : 1;
+            // (the drop-in backward over the whole stack without an input gradient takes the step's schedule)
+            if ((step_mode || !c.want_dx) && c.join && whole && e->L >= 2) p.wgrad = grouped_wgrad_strategy(e, p.rows);
+            if (p.wgrad != WGRAD_PER_LAYER) {
+                // (the pipelined grouped launch carries the bias finish - and the loss finish left to it - as trailing workgroups)
+                p.bias_finish = p.wgrad == WGRAD_GROUPED_PIPE && !e->cfg.no_folded_bias_finish ? BIAS_FINISH_FOLDED : BIAS_FINISH_OWN;
+            } else {
+                // tail: the side stream still owes wgrad_1 when the dgrad chain ends, and the caller's stream has nothing left to do:
+                // the last weight gradient runs there, beside wgrad_1
+                p.tail_on_caller = p.streams == 2 && c.join && step_mode && c.layer_lo == 0 && c.layer_hi - c.layer_lo >= 3 && !e->cfg.tail_on_side;
+                // A backward issued bucket by bucket without joins (data parallel: one bucket per layer) leaves the partial rows
+                // pending until its LAST range (lo == 0) - one finish launch per step instead of one per bucket (10 x 6 us at C3)
+                p.bias_finish = c.join || c.layer_lo == 0 ? BIAS_FINISH_OWN : BIAS_FINISH_NONE;
+            }
+        }
+    }
+    if (c.kind == STEP_TRAIN || c.kind == STEP_UPDATE) {
+        // single GPU fused bf16 step: nothing happens to the gradients between backward and update, so every weight gradient leaves its
+        // sum g^2 behind - split ones in the slab reduce, unsplit and grouped ones in the GEMM epilogue - and the bias finish adds db^2.
+        // Tied weights: the norm is that of the FOLDED gradients - the flat pass
+        const bool from_backward = c.kind == STEP_TRAIN && bf && !e->cfg.no_fused_norm && !e->tc.tied;
+        p.norm = !c.clip ? NORM_NONE : (from_backward ? NORM_FROM_BACKWARD : NORM_FLAT);
+        p.update = bf && b->shadow_wt != nullptr && e->L <= 64 && !e->cfg.flat_adam ? UPDATE_TILED : UPDATE_FLAT;
+    }
+    return p;
+}
+
+StepCall update_call(const codae_hyper* hyper) { return StepCall{STEP_UPDATE, 0, 0, 0, true, false, false, hyper->max_grad_norm > 0.f}; }
+
+// gather + forward chain + loss + data-gradient chain of a narrow stack: one launch.  The loss finish is left to the caller's
+// bias-finish launch - *loss_out describes it - and the kernel zeroes the norm accumulators.
+int run_chain(codae_engine* e, const codae_buffers* b, const codae_batch* batch, const codae_hyper* hyper, hipStream_t s, LossFinish* loss_out) {
     const int B = batch->B, L = e->L, rows = e->rows_for(B);
     ChainArgs a{};
     a.L = L; a.rows = rows; a.B = B;
@@ -412,8 +549,8 @@ int run_chain(codae_engine* e, const codae_buffers* b, const codae_batch* batch,
     a.mask_to_use = batch->mask_to_use; a.nb_run = batch->nb_run; a.run = batch->run;
     a.inv_n = (float)loss_inv_n(hyper, batch);
     a.loss_parts = loss_parts_ptr(e, b);
-    a.do_backward = backward ? 1 : 0;
-    a.scalars = loss_out != nullptr ? b->scalars : nullptr;
+    a.do_backward = 1;
+    a.scalars = b->scalars;
     const int n_wg = rows / chain_rows_per_workgroup();
     CODAE_REQUIRE(n_wg <= e->loss_part_cap, "chain: %d workgroups exceed the partial-sum rows (%d)", n_wg, e->loss_part_cap);
     int rc;
@@ -422,120 +559,56 @@ int run_chain(codae_engine* e, const codae_buffers* b, const codae_batch* batch,
         rc = launch_chain_step(a, s);
     }
     if (rc) return rc;
-    if (backward)
-        for (int l = 0; l < L; ++l) e->parts_pending[l] = n_wg;
+    for (int l = 0; l < L; ++l) e->parts_pending[l] = n_wg;
     e->norm_scalars_zero = true;
-    if (loss_out != nullptr) {
-        loss_out->scalars = b->scalars; loss_out->inv_n = 1.0 / ((double)B * batch->io);
-        loss_out->parts = loss_parts_ptr(e, b); loss_out->n_parts = n_wg;
-        return CODAE_OK;
-    }
-    return finish_loss(e, b, batch, n_wg, s);
+    loss_out->scalars = b->scalars; loss_out->inv_n = 1.0 / ((double)B * batch->io);
+    loss_out->parts = loss_parts_ptr(e, b); loss_out->n_parts = n_wg;
+    return CODAE_OK;
 }
 
-// every layer's weight gradient dW_l = dA_l^T H_l in one grouped launch (fp32 straight into grads: no split-K slabs)
-// with_norm: each tile also adds its sum g^2 to the clip_grad_norm_ slots (no separate pass over the gradients)
-int run_wgrad_grouped(codae_engine* e, const codae_buffers* b, int rows, bool with_norm, hipStream_t s) {
+// Every layer's weight gradient dW_l = dA_l^T H_l, K unsplit, fp32 straight into grads, in one grouped launch per CODAE_GROUP_MAX layers
+// of the kernel p.wgrad names.  NORM_FROM_BACKWARD: each bf16 tile also adds its sum g^2 to the clip_grad_norm_ slots.  The one-barrier
+// kernel takes the layers in ascending order, one profile record per launch; the other two in backward order (the layers whose operands
+// were touched last come first), a launch reported as one record per layer.  fold: the bias finish riding in the pipelined launch.
+int run_wgrad_grouped(codae_engine* e, const codae_buffers* b, const StepPlan& p, hipStream_t s, const BiasFold* fold = nullptr) {
+    const bool ascending = p.wgrad == WGRAD_GROUPED_ONE_BARRIER;
+    double* sumsq_slots = p.norm == NORM_FROM_BACKWARD ? b->scalars + CODAE_S_GRAD_SQ_SLOTS : nullptr;
     for (int base = 0; base < e->L; base += CODAE_GROUP_MAX) {
-        GemmBf16Group grp{};
-        grp.n = 0;
-        for (int l = base; l < e->L && grp.n < CODAE_GROUP_MAX; ++l) {
-            GemmBf16& g = grp.g[grp.n++];
-            g = layer_wgrad_bf16(e, b, l, rows);
-            g.sumsq_slots = with_norm ? b->scalars + CODAE_S_GRAD_SQ_SLOTS : nullptr;
+        const int n = e->L - base < CODAE_GROUP_MAX ? e->L - base : CODAE_GROUP_MAX;
+        auto layer = [&](int i) { return ascending ? base + i : e->L - 1 - base - i; };
+        int rc;
+        if (p.wgrad == WGRAD_GROUPED_F32) {
+            GemmF32Group grp{};
+            for (grp.n = 0; grp.n < n; ++grp.n) grp.g[grp.n] = layer_wgrad_f32(e, b, layer(grp.n), p.rows);
+            ProfScope prof(e, CODAE_K_GEMM_WGRAD, s);
+            prof.counts_as(n);
+            rc = gemm_f32x3_grouped(grp, s);
+        } else {
+            GemmBf16Group grp{};
+            for (grp.n = 0; grp.n < n; ++grp.n) {
+                grp.g[grp.n] = layer_wgrad_bf16(e, b, layer(grp.n), p.rows);
+                grp.g[grp.n].sumsq_slots = sumsq_slots;
+            }
+            ProfScope prof(e, CODAE_K_GEMM_WGRAD, s);
+            if (!ascending) prof.counts_as(n);
+            rc = ascending ? gemm_bf16_grouped(grp, s) : gemm_bf16_pipe_grouped(grp, s, fold);
         }
-        ProfScope prof(e, CODAE_K_GEMM_WGRAD, s);
-        int rc = gemm_bf16_grouped(grp, s);
         if (rc) return rc;
     }
     return CODAE_OK;
 }
 
-// Wide bf16 stack, single-GPU fused step: every layer's weight gradient in ONE launch of 256 x 192 tiles with K = the whole batch
-// (no split-K slabs, no reduce pass; sum g^2 from the epilogue), issued AFTER the data-gradient chain, which then has the chip to
-// itself (defer_wgrad_mode).  Needs dA_l of every layer alive at once (n_dact > L) and enough tiles in total to fill the chip (C3: 48 tiles per
-// layer -> round 2 split K five ways: 47 MB of fp32 slabs written and read back per layer, 0.28 ms of reduce launches per step;
-// all ten together: 480 tiles on 256 CUs).  Small batches gain even more: their per-layer launches are all fixed cost (3 x 512 at the
-// reference's stock batch 128: 0.436 -> 0.402 ms/step; batch 512: 0.663 -> 0.433).
-// 0: per-layer weight gradients; 1: one grouped launch of the pipelined 256 x 192 tile; 2: one grouped launch of the one-barrier
-// kernel on 128 x 128 / 64 x 128 / 64 x 64 tiles (run_wgrad_grouped: stacks too narrow to fill the chip with the big tile)
-int defer_wgrad_mode(codae_engine* e, int rows) {
-    if (e->prec == CODAE_PREC_F32) {
-        // 3: the exact-fp32 engine on the bf16-plane GEMMs - every weight gradient in one launch of gemm_f32x3_grouped_kernel, K unsplit
-        // (what mode 1 is to the bf16 engine: per layer it is 144 tiles, split 7 ways into fp32 slabs and reduced: 0.2 ms of reduce
-        // launches per C3 step and a prologue / epilogue per 37 K-tiles)
-        if (env().f32_gemm == 1 || e->cfg.no_defer_wgrad || e->cfg.single_stream || e->L > CODAE_GROUP_MAX || e->n_dact <= e->L || rows < 256 ||
-            rows % 32 != 0)
-            return 0;
-        int total = 0;
-        for (int l = 0; l < e->L; ++l) {
-            if (e->in[l] % 4 != 0 || e->out[l] % 4 != 0) return 0;
-            total += tile_count(e->out[l], e->in[l], TILE_128x128);
-        }
-        return total >= 256 ? 3 : 0;
-    }
-    if (e->prec != CODAE_PREC_BF16 || e->cfg.no_defer_wgrad || e->cfg.single_stream || e->L > CODAE_GROUP_MAX || e->n_dact <= e->L || rows < 64)
-        return 0;
-    int total = 0, total_small = 0;
-    for (int l = 0; l < e->L; ++l) {
-        total += tile_count(e->out[l], e->in[l], TILE_256x192);        // (gemm_bf16_pipe_grouped)
-        total_small += tile_count(e->out[l], e->in[l], TILE_64x64);     // (gemm_bf16_grouped, its smallest tile)
-        if ((int64_t)rows * e->out_ld[l] * 2 >= (int64_t)1 << 32 || (int64_t)rows * e->in_ld[l] * 2 >= (int64_t)1 << 32) return 0;
-    }
-    // (round 3 first kept the per-layer backward when one layer alone fills the chip - C5: 31.2 ms/step against 32.9 grouped; with
-    //  the 4 x 8 tile order of the pipelined kernel the grouped launch wins there too: 29.5 against 30.2)
-    if (total >= 200) return 1;
-    return total_small >= 128 ? 2 : 0;
+// What ends a backward whose data gradients are complete on s (the chain kernel's, or the per-layer chain of a grouped schedule): the
+// grouped weight gradients, then the bias finish - with the loss finish left to it - in that launch or behind it
+int run_grouped_tail(codae_engine* e, const codae_buffers* b, const StepPlan& p, hipStream_t s, const LossFinish* loss) {
+    const bool with_norm = p.norm == NORM_FROM_BACKWARD;
+    BiasFold fold;
+    const bool folded = p.bias_finish == BIAS_FINISH_FOLDED && fold_bias_finish(e, b, with_norm, loss, &fold);
+    int rc = run_wgrad_grouped(e, b, p, s, folded ? &fold : nullptr);
+    if (rc) return rc;
+    if (folded) { prof_rides_along(e, CODAE_K_BIAS_FINISH); return CODAE_OK; }
+    return finish_bias(e, b, s, with_norm, loss);
 }
-
-int run_wgrad_deferred_f32(codae_engine* e, const codae_buffers* b, int rows, hipStream_t s) {
-    GemmF32Group grp{};
-    grp.n = 0;
-    for (int l = e->L - 1; l >= 0; --l)              // (backward order: the layers whose operands were touched last come first)
-        grp.g[grp.n++] = layer_wgrad_f32(e, b, l, rows);
-    ProfScope prof(e, CODAE_K_GEMM_WGRAD, s);
-    prof.counts_as(grp.n);
-    return gemm_f32x3_grouped(grp, s);
-}
-
-// the pending bias finish (every layer with partial rows; with_norm / loss as finish_bias takes them) as the job table of the grouped
-// weight-gradient launch; false - nothing taken, finish_bias runs as always - when there is nothing pending or more than fits
-bool take_bias_fold(codae_engine* e, const codae_buffers* b, bool with_norm, const LossFinish* loss, BiasFold* f) {
-    int n = 0;
-    for (int l = 0; l < e->L; ++l) n += e->parts_pending[l] > 0 ? 1 : 0;
-    if (n == 0 || n > CODAE_GROUP_MAX) return false;
-    *f = BiasFold{};
-    int cols = 0;
-    for (int l = 0; l < e->L; ++l) {
-        if (e->parts_pending[l] <= 0) continue;
-        f->parts[f->n] = part_ptr(e, b, l);
-        f->out[f->n] = b->grads + e->b_off[l];
-        f->rows[f->n] = e->parts_pending[l];
-        f->cols[f->n] = e->out[l];
-        f->col_begin[f->n] = cols;
-        cols += e->out[l];
-        ++f->n;
-        e->parts_pending[l] = 0;
-    }
-    f->col_begin[f->n] = cols;
-    f->sumsq = with_norm ? b->scalars + CODAE_S_GRAD_SQ : nullptr;
-    if (loss != nullptr) f->loss = *loss;
-    return true;
-}
-
-int run_wgrad_deferred(codae_engine* e, const codae_buffers* b, int rows, bool with_norm, hipStream_t s, const BiasFold* fold = nullptr) {
-    GemmBf16Group grp{};
-    grp.n = 0;
-    for (int l = e->L - 1; l >= 0; --l) {            // (backward order: the layers whose operands were touched last come first)
-        GemmBf16& g = grp.g[grp.n++];
-        g = layer_wgrad_bf16(e, b, l, rows);
-        g.sumsq_slots = with_norm ? b->scalars + CODAE_S_GRAD_SQ_SLOTS : nullptr;
-    }
-    ProfScope prof(e, CODAE_K_GEMM_WGRAD, s);
-    prof.counts_as(grp.n);
-    return gemm_bf16_pipe_grouped(grp, s, fold);
-}
-
 // Exact-fp32 GEMM of a launch too small to fill the chip (forward / data gradient of a small batch): K split over
 // workgroups into fp32 slabs (slab slot 2: the caller's stream), then the reduce that applies the GEMM's epilogue.  Same
 // fp32 arithmetic in another summation order.  3 x 512 at batch 128, whole parity-mode step: 3.09 -> see DESIGN.md.
@@ -771,13 +844,13 @@ int join_side(codae_engine* h, hipStream_t s) {
 // waits for the side stream; deeper stacks rotate (dgrad_l writes buffer (l-1) % n, which wgrad_{l-1+n} was
 // reading, and waits for that wgrad's event).  The last weight gradient (layer 0) runs on `s` itself, beside
 // wgrad_1 on the side stream.  With join the call returns with `s` waiting for every side-stream kernel.
-// with_norm (single-GPU fused bf16 step: nothing happens to the gradients between backward and update): every launch that
-// leaves final gradient values behind also adds their sum g^2 to the clip_grad_norm_ accumulators.
-// loss: the step's loss finish, left to this call's bias-finish launch (codae_train_step)
-int backward_range(codae_handle h, const codae_buffers* b, int B, int lo, int hi, float* dx, bool step_mode, bool with_norm,
-                   hipStream_t s, bool join = true, const LossFinish* loss = nullptr) {
-    const int rows = h->rows_for(B);
-    const bool dual = !h->cfg.single_stream;
+// p.norm == NORM_FROM_BACKWARD: every launch that leaves final gradient values behind also adds their sum g^2 to the clip_grad_norm_
+// accumulators.  loss: the step's loss finish, left to this call's bias-finish launch (codae_train_step)
+int backward_range(codae_handle h, const codae_buffers* b, const StepCall& c, const StepPlan& p, float* dx, hipStream_t s,
+                   const LossFinish* loss = nullptr) {
+    const int B = c.B, lo = c.layer_lo, hi = c.layer_hi, rows = p.rows;
+    const bool step_mode = c.kind != STEP_DROPIN_BACKWARD, join = c.join;
+    const bool dual = p.streams == 2, with_norm = p.norm == NORM_FROM_BACKWARD;
     CODAE_REQUIRE(!(step_mode && h->drop_live && h->tc.drop.on) || B == h->drop_B, "backward of %d rows after a dropped forward of %d", B, h->drop_B);
     if (dual) {
         int rc = ensure_side_stream(h);
@@ -786,25 +859,15 @@ int backward_range(codae_handle h, const codae_buffers* b, int B, int lo, int hi
     // (Measured and dropped: the slab reduces on the caller's stream one layer late, or on a third stream - no
     // gain, 1.83 / 1.84 vs 1.82 ms at the time; every GEMM on the caller's stream with only the reduces beside
     // them - 0.27 ms slower: each cross-queue event costs ~10 us.)
-    // (the drop-in backward - codae_backward over the whole stack without an input gradient - takes the same schedule)
-    const int defer = ((step_mode || dx == nullptr) && join && lo == 0 && hi == h->L && h->L >= 2) ? defer_wgrad_mode(h, rows) : 0;
-    if (defer != 0) {
-        // data-gradient chain alone on the chip, then all weight gradients in one launch (see defer_wgrad_mode); one stream
+    if (p.wgrad != WGRAD_PER_LAYER) {
+        // data-gradient chain alone on the chip, then all weight gradients in one launch (see grouped_wgrad_strategy); one stream
         int rc = join_side(h, s);                  // (an earlier bucketed backward may have left work on the side stream)
         if (rc) return rc;
         for (int l = hi - 1; l >= 1; --l) {
             rc = run_dgrad(h, b, l, rows, false, nullptr, s);
             if (rc) return rc;
         }
-        // (the pipelined grouped launch carries the bias finish - and the loss finish left to it - as trailing workgroups)
-        BiasFold fold;
-        const bool folded = defer == 1 && !h->cfg.no_folded_bias_finish && take_bias_fold(h, b, with_norm, loss, &fold);
-        rc = defer == 3 ? run_wgrad_deferred_f32(h, b, rows, s)
-                        : (defer == 1 ? run_wgrad_deferred(h, b, rows, with_norm, s, folded ? &fold : nullptr)
-                                      : run_wgrad_grouped(h, b, rows, with_norm, s));
-        if (rc) return rc;
-        if (folded) { prof_rides_along(h, CODAE_K_BIAS_FINISH); return CODAE_OK; }
-        return finish_bias(h, b, s, with_norm, loss);
+        return run_grouped_tail(h, b, p, s, loss);
     }
     bool* w_pending = h->w_pending;
     const bool coscheduled = dual;         // the weight gradients run beside the data-gradient chain
@@ -812,10 +875,8 @@ int backward_range(codae_handle h, const codae_buffers* b, int B, int lo, int hi
         int rc;
         if (!dual) {
             rc = run_wgrad(h, b, l, rows, with_norm, s);
-        } else if (join && step_mode && l == 0 && hi - lo >= 3 && !h->cfg.tail_on_side) {
-            // tail: the side stream still owes wgrad_1 when the dgrad chain ends, and the caller's stream has
-            // nothing left to do: the last weight gradient runs here (third slab buffer), beside wgrad_1
-            rc = run_wgrad(h, b, l, rows, with_norm, s, 2);
+        } else if (p.tail_on_caller && l == 0) {
+            rc = run_wgrad(h, b, l, rows, with_norm, s, 2);           // (third slab buffer)
         } else {
             hipEvent_t ready = h->ev_ready[h->ready_turn++ % CODAE_MAX_DACT];
             CODAE_HIP_CHECK(hipEventRecord(ready, s));                      // dA_l (and act[l]) are complete on s
@@ -841,11 +902,9 @@ int backward_range(codae_handle h, const codae_buffers* b, int B, int lo, int hi
         }
     }
     // bias gradients of every layer whose activation gradient was produced since the last finish (this range's dgrads; the
-    // loss, when the range starts at the top): partial rows -> grads' bias block, on the caller's stream.  A backward issued
-    // bucket by bucket without joins (data parallel: one bucket per layer) leaves the partial rows pending until its LAST
-    // range (lo == 0) - one finish launch per step instead of one per bucket (10 x 6 us at C3); codae_step_update finishes
-    // whatever a caller that stopped short left behind.
-    if (join || lo == 0) {
+    // loss, when the range starts at the top): partial rows -> grads' bias block, on the caller's stream.  codae_step_update
+    // finishes whatever a caller that stopped short left behind.
+    if (p.bias_finish != BIAS_FINISH_NONE) {
         int rc = finish_bias(h, b, s, with_norm, loss);
         if (rc) return rc;
     }
@@ -1168,7 +1227,8 @@ int codae_backward(codae_handle h, const codae_buffers* b, const float* dy, floa
     rc = launch_colsum_parts_f32(dy, B, h->out[top], part_ptr(h, b, top), s);
     if (rc) return rc;
     h->parts_pending[top] = (B + 63) / 64;
-    return backward_range(h, b, B, layer_lo, layer_hi, dx, false, false, s);
+    const StepCall call{STEP_DROPIN_BACKWARD, B, layer_lo, layer_hi, true, dx != nullptr, false, false};
+    return backward_range(h, b, call, step_plan(h, b, call), dx, s);
 }
 
 // The slot contrast behind the criterion's kernel and its finish (a no-op while it is off): prepare this step's candidates, add the
@@ -1239,13 +1299,11 @@ static bool gathers_from_image(codae_handle h, const codae_batch* batch, const v
            gather_image_takes(batch, im.image, out, h->in_ld[0]);
 }
 
-// fold != null (codae_train_step): when the loss is fused into the last forward GEMM, its finish - 5 us of a one-block launch
-// plus a launch boundary between the loss GEMM and the first data gradient - is not launched: *fold describes it for the bias-finish
-// launch that ends the backward (as the chain path does), and the gather's first block clears the norm accumulators instead.
+// plan.loss_finish == LOSS_FINISH_CARRIED (codae_train_step): the fused loss's finish is not launched: *fold describes it for the
+// bias-finish launch that ends the backward, and the gather's first block clears the norm accumulators instead.
 // fold->scalars stays null when this call finished the loss itself.
 static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae_batch* batch, const codae_hyper* hyper,
-                             float* out_y, void* stream, LossFinish* fold) {
-    CODAE_REQUIRE(batch != nullptr, "codae_step_forward_loss: null batch");
+                             float* out_y, void* stream, const StepPlan& plan, LossFinish* fold) {
     int rc = check_common(h, b, batch->B);
     if (rc) return rc;
     CODAE_REQUIRE(batch->io == h->in[0] && batch->io == h->out[h->L - 1], "batch.io %d does not match the model (%d -> %d)",
@@ -1255,18 +1313,14 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
     if (h->prof_on) ++h->prof_step;
     hipStream_t s = (hipStream_t)stream;
     const int B = batch->B, L = h->L;
-    const int rows = h->rows_for(B);
+    const int rows = plan.rows;
     const bool bf = h->prec == CODAE_PREC_BF16;
     // hidden dropout: training forwards only; the backward entry points find the rows and the step in the handle
     h->drop_live = hyper != nullptr && h->tc.drop.on;
     if (h->drop_live) { h->drop_B = B; h->drop_rows = batch->row_idx; h->drop_step = hyper->step; }
-    // bf16 training step: the loss is folded into the last forward GEMM's epilogue (y never stored)
-    // (not with loss emphasis or a criterion other than the MSE: those live in stand-alone kernels, below)
-    // (nor with a slot-presence table: the stand-alone kernels carry the predicate, the GEMM epilogue does not)
     const uint8_t* const pres = h->tc.pres.table;
     const int pres_slots = h->tc.pres.n_slots;
-    const bool fuse_loss = bf && hyper != nullptr && out_y == nullptr && !h->cfg.no_fused_loss && h->plain_mse();
-    const bool fold_finish = fuse_loss && fold != nullptr && !h->cfg.no_folded_loss_finish;
+    const bool fuse_loss = plan.loss == LOSS_FUSED, fold_finish = plan.loss_finish == LOSS_FINISH_CARRIED;
     {
         ProfScope prof(h, CODAE_K_GATHER, s);
         double* zero_norm = fold_finish ? b->scalars : nullptr;
@@ -1338,7 +1392,10 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
 
 int codae_step_forward_loss(codae_handle h, const codae_buffers* b, const codae_batch* batch, const codae_hyper* hyper,
                             float* out_y, void* stream) {
-    return forward_loss_impl(h, b, batch, hyper, out_y, stream, nullptr);
+    CODAE_REQUIRE(batch != nullptr, "codae_step_forward_loss: null batch");
+    CODAE_REQUIRE(h != nullptr && b != nullptr, "null handle or buffers");
+    const StepCall call{hyper != nullptr ? STEP_FORWARD_LOSS : STEP_EVAL, batch->B, 0, h->L, true, false, out_y != nullptr, false};
+    return forward_loss_impl(h, b, batch, hyper, out_y, stream, step_plan(h, b, call), nullptr);
 }
 
 int codae_set_input_noise(codae_handle h, const codae_noise* noise) {
@@ -1513,47 +1570,47 @@ int codae_eval_step(codae_handle h, const codae_buffers* b, const codae_batch* b
     return codae_step_forward_loss(h, b, batch, nullptr, out_y, stream);
 }
 
-int codae_step_backward(codae_handle h, const codae_buffers* b, int32_t B, int32_t layer_lo, int32_t layer_hi, void* stream) {
+// a layer range of the step's backward; join: the call returns with `stream` waiting for the side stream
+static int step_backward(const char* who, codae_handle h, const codae_buffers* b, int B, int layer_lo, int layer_hi, bool join, void* stream) {
     int rc = check_common(h, b, B);
     if (rc) return rc;
-    CODAE_REQUIRE(b->grads && b->dacts, "codae_step_backward: grads / dacts missing");
-    CODAE_REQUIRE(layer_lo >= 0 && layer_lo < layer_hi && layer_hi <= h->L, "codae_step_backward: layer range [%d, %d)", layer_lo, layer_hi);
-    return backward_range(h, b, B, layer_lo, layer_hi, nullptr, true, false, (hipStream_t)stream);
+    CODAE_REQUIRE(b->grads && b->dacts, "%s: grads / dacts missing", who);
+    CODAE_REQUIRE(layer_lo >= 0 && layer_lo < layer_hi && layer_hi <= h->L, "%s: layer range [%d, %d)", who, layer_lo, layer_hi);
+    const StepCall call{STEP_BACKWARD, B, layer_lo, layer_hi, join, false, false, false};
+    return backward_range(h, b, call, step_plan(h, b, call), nullptr, (hipStream_t)stream);
+}
+
+int codae_step_backward(codae_handle h, const codae_buffers* b, int32_t B, int32_t layer_lo, int32_t layer_hi, void* stream) {
+    return step_backward("codae_step_backward", h, b, B, layer_lo, layer_hi, true, stream);
 }
 
 int codae_step_backward_async(codae_handle h, const codae_buffers* b, int32_t B, int32_t layer_lo, int32_t layer_hi, void* stream) {
-    int rc = check_common(h, b, B);
-    if (rc) return rc;
-    CODAE_REQUIRE(b->grads && b->dacts, "codae_step_backward_async: grads / dacts missing");
-    CODAE_REQUIRE(layer_lo >= 0 && layer_lo < layer_hi && layer_hi <= h->L, "codae_step_backward_async: layer range [%d, %d)", layer_lo, layer_hi);
-    return backward_range(h, b, B, layer_lo, layer_hi, nullptr, true, false, (hipStream_t)stream, false);
+    return step_backward("codae_step_backward_async", h, b, B, layer_lo, layer_hi, false, stream);
 }
 
 int codae_side_stream(codae_handle h, void** out) {
     CODAE_REQUIRE(h && out, "codae_side_stream: null argument");
     *out = nullptr;
-    if (h->cfg.single_stream) return CODAE_OK;      // everything runs on the caller's stream
+    if (!two_streams(h)) return CODAE_OK;           // everything runs on the caller's stream
     int rc = ensure_side_stream(h);
     if (rc) return rc;
     *out = h->side;
     return CODAE_OK;
 }
 
-static int update_impl(codae_handle h, const codae_buffers* b, const codae_hyper* hyper, hipStream_t s, bool weights_norm_done) {
-    CODAE_REQUIRE(h && b && hyper, "codae_step_update: null argument");
+// The update behind a backward: what earlier calls left open (side stream, pending bias rows), the tied fold, the norm where plan.norm
+// leaves it to a flat pass, then the kernels plan.update names over the free parameters.
+static int update_impl(codae_handle h, const codae_buffers* b, const codae_hyper* hyper, hipStream_t s, const StepPlan& plan) {
     CODAE_REQUIRE(b->params && b->grads && b->adam_m && b->adam_v && b->scalars, "codae_step_update: buffer missing");
     int rc = join_side(h, s);                 // (a backward issued with codae_step_backward_async)
     if (rc) return rc;
-    bool pending = false;
-    for (int l = 0; l < h->L; ++l) pending = pending || h->parts_pending[l] > 0;
-    if (pending && b->bias_parts != nullptr) {               // (a bucketed backward that did not reach layer 0)
+    if (bias_pending_from(h, 0) && b->bias_parts != nullptr) {               // (a bucketed backward that did not reach layer 0)
         rc = finish_bias(h, b, s, false);
         if (rc) return rc;
     }
     // tied weights: the decoder matrices' gradients are folded into the encoder's (behind every reduce of a data-parallel step, which
     // ends here) and left +0: the flat vector is the gradient of the tied parameter set, and the flat norm below counts it once
     const bool tied = h->tc.tied != 0 && !h->tie_pairs.empty();
-    CODAE_REQUIRE(!(h->tc.tied && weights_norm_done), "codae_step_update: tied weights take the flat norm pass");
     if (tied) {
         ProfScope prof(h, CODAE_K_SUMSQ, s);
         rc = launch_tie_fold(b->grads, h->tie_pairs.data(), (int)h->tie_pairs.size(), s);
@@ -1561,61 +1618,50 @@ static int update_impl(codae_handle h, const codae_buffers* b, const codae_hyper
     }
     const bool scalars_zero = h->norm_scalars_zero;
     h->norm_scalars_zero = false;
-    if (hyper->max_grad_norm > 0.f && !weights_norm_done) {    // (else: sum g^2 was accumulated by the slab reduces / the
-        ProfScope prof(h, CODAE_K_SUMSQ, s);                    //  grouped weight-gradient epilogues and the bias finish)
-        if (!scalars_zero) {                     // (a stand-alone update: no step_forward_loss of this step cleared them)
-            CODAE_HIP_CHECK(hipMemsetAsync(b->scalars + CODAE_S_GRAD_SQ, 0, sizeof(double), s));
-            CODAE_HIP_CHECK(hipMemsetAsync(b->scalars + CODAE_S_GRAD_SQ_SLOTS, 0, CODAE_S_N_SLOTS * sizeof(double), s));
-        }
-        rc = launch_sumsq(b->grads, h->n_param, b->scalars + CODAE_S_GRAD_SQ, s);
+    if (plan.norm == NORM_FLAT) {
+        ProfScope prof(h, CODAE_K_SUMSQ, s);
+        // (cleared here for a stand-alone update: no step_forward_loss of this step did it)
+        rc = launch_grad_sumsq(b->grads, h->n_param, b->scalars, !scalars_zero, s);
         if (rc) return rc;
     }
-    bf16_t* shadow = h->prec == CODAE_PREC_BF16 ? reinterpret_cast<bf16_t*>(b->shadow_w) : nullptr;
-    CODAE_REQUIRE(h->prec != CODAE_PREC_BF16 || shadow, "codae_step_update: shadow_w missing");
+    const bool bf = h->prec == CODAE_PREC_BF16;
+    bf16_t* shadow = bf ? reinterpret_cast<bf16_t*>(b->shadow_w) : nullptr;
+    bf16_t* shadow_t = bf ? reinterpret_cast<bf16_t*>(b->shadow_wt) : nullptr;
+    CODAE_REQUIRE(!bf || shadow, "codae_step_update: shadow_w missing");
     // (Measured and dropped: per-layer Adam kernels on the side stream beside the NEXT forward - HBM / L2 contention
     // slowed those GEMMs from 46.8 to 56.9 us each and the step from 1.76 to 1.84 ms.)
     ProfScope prof(h, CODAE_K_ADAM, s);
-    // the weight average rides in every launch below, at the offsets of p (tied: the free parameters only)
-    const codae_weight_average* wa = &h->tc.avg;
-    float* avg = h->tc.avg.avg;
-    if (tied) {
-        // the free parameters only - the encoder matrices (and the middle one of an odd stack) and every bias; the moments of the
-        // decoder matrices are neither read nor written - then the decoder's three images from the updated encoder
-        const int nf = h->n_free();
-        bf16_t* shadow_t = h->prec == CODAE_PREC_BF16 ? reinterpret_cast<bf16_t*>(b->shadow_wt) : nullptr;
-        if (h->prec == CODAE_PREC_BF16 && shadow_t != nullptr && h->L <= 64 && !h->cfg.flat_adam) {
-            rc = launch_clip_adam_tiled(b->params, b->grads, b->adam_m, b->adam_v, hyper, b->scalars + CODAE_S_GRAD_SQ, shadow, shadow_t, nf,
-                                        h->w_off.data(), h->out.data(), h->in.data(), 1, h->bias_begin, h->n_param - h->bias_begin, s,
-                                        step_dev(h, b), &h->tc.opt, h->tc.opt.vmax, wa, avg);
-            if (rc) return rc;
-        } else {
-            const int64_t spans[2][2] = {{0, h->w_off[nf]}, {h->bias_begin, h->n_param}};
-            for (const auto& sp : spans) {
-                const int64_t lo = sp[0], n = sp[1] - sp[0];
-                rc = launch_clip_adam(b->params + lo, b->grads + lo, b->adam_m + lo, b->adam_v + lo, n, hyper, b->scalars + CODAE_S_GRAD_SQ,
-                                      shadow ? shadow + lo : nullptr, nullptr, s, step_dev(h, b), &h->tc.opt,
-                                      h->tc.opt.vmax ? h->tc.opt.vmax + lo : nullptr, wa, avg ? avg + lo : nullptr);
-                if (rc) return rc;
-            }
-            rc = refresh_transposed(h, b, s, 1, nf);
+    // the weight average rides in every launch below, at the offsets of p
+    UpdateLaunch u{};
+    u.x = ParamVectors{b->params, b->grads, b->adam_m, b->adam_v, h->tc.opt.vmax, h->tc.avg.avg, shadow};
+    u.n = h->n_param; u.hp = hyper; u.grad_sq = b->scalars + CODAE_S_GRAD_SQ; u.step_dev = step_dev(h, b);
+    u.opt = &h->tc.opt; u.wa = &h->tc.avg;
+    // tied: the free parameters only - the encoder matrices (and the middle one of an odd stack) and every bias; the moments of the
+    // decoder matrices are neither read nor written - then the decoder's three images from the updated encoder
+    const int n_mats = tied ? h->n_free() : h->L;
+    if (plan.update == UPDATE_TILED) {
+        // one tiled pass: p, m, v, the bf16 shadow and the transposed shadow of every layer that has a data gradient
+        const UpdateTiles tiles{shadow_t, n_mats, h->w_off.data(), h->out.data(), h->in.data(), 1, h->bias_begin, h->n_param - h->bias_begin};
+        rc = launch_update_tiled(u, tiles, s);
+        if (rc) return rc;
+    } else {
+        const int64_t mats_end = tied ? h->w_off[n_mats] : h->n_param;         // (untied: one span, matrices and biases)
+        const int64_t spans[2][2] = {{0, mats_end}, {h->bias_begin, h->n_param}};
+        for (int i = 0; i < (tied ? 2 : 1); ++i) {
+            UpdateLaunch span = u;
+            span.x = u.x.at(spans[i][0]); span.n = spans[i][1] - spans[i][0];
+            rc = launch_update(span, s);
             if (rc) return rc;
         }
-        return launch_tie_mirror(b->params, shadow, shadow_t, h->tie_pairs.data(), (int)h->tie_pairs.size(), s);
+        rc = refresh_transposed(h, b, s, 1, n_mats);
+        if (rc) return rc;
     }
-    if (h->prec == CODAE_PREC_BF16 && b->shadow_wt != nullptr && h->L <= 64 && !h->cfg.flat_adam) {
-        // one tiled pass: p, m, v, the bf16 shadow and the transposed shadow of every layer that has a data gradient
-        return launch_clip_adam_tiled(b->params, b->grads, b->adam_m, b->adam_v, hyper, b->scalars + CODAE_S_GRAD_SQ, shadow,
-                                      reinterpret_cast<bf16_t*>(b->shadow_wt), h->L, h->w_off.data(), h->out.data(), h->in.data(),
-                                      1, h->bias_begin, h->n_param - h->bias_begin, s, step_dev(h, b), &h->tc.opt, h->tc.opt.vmax, wa, avg);
-    }
-    rc = launch_clip_adam(b->params, b->grads, b->adam_m, b->adam_v, h->n_param, hyper, b->scalars + CODAE_S_GRAD_SQ,
-                          shadow, nullptr, s, step_dev(h, b), &h->tc.opt, h->tc.opt.vmax, wa, avg);
-    if (rc) return rc;
-    return refresh_transposed(h, b, s);
+    return tied ? launch_tie_mirror(b->params, shadow, shadow_t, h->tie_pairs.data(), (int)h->tie_pairs.size(), s) : CODAE_OK;
 }
 
 int codae_step_update(codae_handle h, const codae_buffers* b, const codae_hyper* hyper, void* stream) {
-    return update_impl(h, b, hyper, (hipStream_t)stream, false);
+    CODAE_REQUIRE(h && b && hyper, "codae_step_update: null argument");
+    return update_impl(h, b, hyper, (hipStream_t)stream, step_plan(h, b, update_call(hyper)));
 }
 
 int codae_span_sumsq(const float* g, int64_t n, double* acc, void* stream) {
@@ -1650,8 +1696,10 @@ int codae_step_update_span(codae_handle h, const codae_buffers* b, const codae_h
     bf16_t* shadow = h->prec == CODAE_PREC_BF16 ? reinterpret_cast<bf16_t*>(b->shadow_w) : nullptr;
     CODAE_REQUIRE(h->prec != CODAE_PREC_BF16 || shadow, "codae_step_update_span: shadow_w missing");
     ProfScope prof(h, CODAE_K_ADAM, s);
-    return launch_clip_adam(b->params + lo, b->grads + lo, b->adam_m + lo, b->adam_v + lo, hi - lo, hyper, nullptr,
-                            shadow ? shadow + lo : nullptr, coef, s, nullptr, &h->tc.opt, h->tc.opt.vmax ? h->tc.opt.vmax + lo : nullptr);
+    UpdateLaunch u{};
+    u.x = ParamVectors{b->params, b->grads, b->adam_m, b->adam_v, h->tc.opt.vmax, nullptr, shadow}.at(lo);
+    u.n = hi - lo; u.hp = hyper; u.coef_in = coef; u.opt = &h->tc.opt;
+    return launch_update(u, s);
 }
 
 int codae_sync_transposed(codae_handle h, const codae_buffers* b, void* stream) {
@@ -1665,49 +1713,42 @@ int codae_join(codae_handle h, void* stream) {
 }
 
 int codae_step_path(codae_handle h, const codae_buffers* b, int32_t B) {
-    return (h != nullptr && b != nullptr && B > 0 && B <= h->max_batch && chain_eligible(h, b, B)) ? 1 : 0;
+    if (h == nullptr || b == nullptr || B <= 0 || B > h->max_batch) return 0;
+    return step_plan(h, b, StepCall{STEP_TRAIN, B, 0, h->L, true, false, false, false}).path;
 }
 
 int codae_train_step(codae_handle h, const codae_buffers* b, const codae_batch* batch, const codae_hyper* hyper, void* stream) {
     CODAE_REQUIRE(hyper != nullptr, "codae_train_step: null hyper");
     CODAE_REQUIRE(batch != nullptr, "codae_train_step: null batch");
-    if (h != nullptr && b != nullptr && chain_eligible(h, b, batch->B)) {
-        // narrow stack: persistent fused chain + grouped weight gradients (6 launches for the whole step)
-        int rcc = check_common(h, b, batch->B);
-        if (rcc) return rcc;
+    CODAE_REQUIRE(h != nullptr && b != nullptr, "null handle or buffers");
+    const StepCall call{STEP_TRAIN, batch->B, 0, h->L, true, false, false, hyper->max_grad_norm > 0.f};
+    const StepPlan plan = step_plan(h, b, call);
+    hipStream_t s = (hipStream_t)stream;
+    LossFinish lf{};                 // (filled when the loss finish is left to the backward's bias-finish launch)
+    int rc;
+    if (plan.path == PATH_CHAIN) {
+        rc = check_common(h, b, batch->B);
+        if (rc) return rc;
         CODAE_REQUIRE(batch->io == h->in[0], "batch.io %d does not match the model (%d)", batch->io, h->in[0]);
         CODAE_REQUIRE(b->grads && b->dacts && b->scalars && b->bias_parts, "codae_train_step: grads / dacts / scalars / bias_parts missing");
         CODAE_REQUIRE(batch->data && batch->B > 0 && (!(batch->mask_id || batch->mask_to_use) || batch->mask_table), "codae_train_step: bad batch");
         CODAE_REQUIRE(!batch->mask_to_use || batch->mask_id || (batch->nb_run > 0 && batch->run >= 0 && batch->run < batch->nb_run),
                       "codae_train_step: run %d outside [0, %d)", batch->run, batch->nb_run);
         if (h->prof_on) ++h->prof_step;
-        hipStream_t s = (hipStream_t)stream;
-        rcc = join_side(h, s);
-        if (rcc) return rcc;
+        rc = join_side(h, s);
+        if (rc) return rc;
         h->drop_live = false;
-        LossFinish lf{};
-        rcc = run_chain(h, b, batch, hyper, true, s, &lf);
-        if (rcc) return rcc;
-        // (finish_loss zeroed the norm slots; tied weights: the norm is that of the FOLDED gradients - the flat pass of update_impl)
-        const bool with_norm = hyper->max_grad_norm > 0.f && !h->cfg.no_fused_norm && !h->tc.tied;
-        rcc = run_wgrad_grouped(h, b, h->rows_for(batch->B), with_norm, s);
-        if (rcc) return rcc;
-        rcc = finish_bias(h, b, s, with_norm, &lf);
-        if (rcc) return rcc;
-        return update_impl(h, b, hyper, s, with_norm);
+        rc = run_chain(h, b, batch, hyper, s, &lf);                // (forward, loss and every data gradient)
+        if (rc) return rc;
+        rc = run_grouped_tail(h, b, plan, s, &lf);
+    } else {
+        rc = forward_loss_impl(h, b, batch, hyper, nullptr, stream, plan, &lf);
+        if (rc) return rc;
+        // (codae_step_backward's argument checks - check_common, grads / dacts - were made by the forward just above)
+        rc = backward_range(h, b, call, plan, nullptr, s, lf.scalars != nullptr ? &lf : nullptr);
     }
-    LossFinish lf{};                 // (filled when the loss finish is left to the backward's bias-finish launch)
-    int rc = forward_loss_impl(h, b, batch, hyper, nullptr, stream, &lf);
     if (rc) return rc;
-    // single GPU: nothing happens to the gradients between backward and update, so the norm can be
-    // gathered while the split-K slabs are reduced (finish_loss zeroed GRAD_SQ before the backward)
-    // bf16: every weight gradient leaves its sum g^2 behind - split ones in the slab reduce, unsplit ones in the GEMM epilogue
-    // (not with tied weights: the norm is that of the folded gradients - the flat pass of update_impl)
-    const bool all_slabbed = h->prec == CODAE_PREC_BF16 && hyper->max_grad_norm > 0.f && !h->cfg.no_fused_norm && !h->tc.tied;
-    // (codae_step_backward's argument checks - check_common, grads / dacts - were made by codae_step_forward_loss just above)
-    rc = backward_range(h, b, batch->B, 0, h->L, nullptr, true, all_slabbed, (hipStream_t)stream, true, lf.scalars != nullptr ? &lf : nullptr);
-    if (rc) return rc;
-    return update_impl(h, b, hyper, (hipStream_t)stream, all_slabbed);
+    return update_impl(h, b, hyper, s, plan);
 }
 
 static bool same_bytes(const void* a, const void* b, size_t n) { return memcmp(a, b, n) == 0; }
@@ -1728,7 +1769,7 @@ int codae_train_step_graph(codae_handle h, const codae_buffers* b, const codae_b
         if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
         int rc = check_common(h, b, batch->B);
         if (rc) return rc;
-        if (!h->cfg.single_stream) {
+        if (two_streams(h)) {
             rc = ensure_side_stream(h);                      // (no stream / event creation inside the capture)
             if (rc) return rc;
         }
@@ -1832,10 +1873,11 @@ int codae_train_step_dp(codae_handle h, const codae_buffers* b, const codae_batc
     int rc = codae_step_forward_loss(h, b, batch, hyper, nullptr, stream);
     if (rc) return rc;
     for (int i = 0; i < n_buckets; ++i) {
-        rc = backward_range(h, b, batch->B, bucket_lo[i], bucket_hi[i], nullptr, true, false, s, false);
+        const StepCall range{STEP_BACKWARD, batch->B, bucket_lo[i], bucket_hi[i], false, false, false, false};
+        rc = backward_range(h, b, range, step_plan(h, b, range), nullptr, s);
         if (rc) return rc;
         // the bucket's weight gradients are complete, in order, on the side stream (or on s itself in single-stream mode)
-        hipStream_t producer = h->side != nullptr && !h->cfg.single_stream ? h->side : s;
+        hipStream_t producer = h->side != nullptr && two_streams(h) ? h->side : s;
         CODAE_HIP_CHECK(hipEventRecord(d->ev_bucket[i], producer));
         CODAE_HIP_CHECK(hipStreamWaitEvent(d->stream, d->ev_bucket[i], 0));
         const int64_t lo_off = h->w_off[bucket_lo[i]];
@@ -1852,7 +1894,24 @@ int codae_train_step_dp(codae_handle h, const codae_buffers* b, const codae_batc
     CODAE_RCCL_CHECK(g_rccl.AllReduce(bias, bias, (size_t)(h->n_param - h->bias_begin), ncclFloat, ncclSum, d->comm, d->stream));
     CODAE_HIP_CHECK(hipEventRecord(d->ev_done, d->stream));
     CODAE_HIP_CHECK(hipStreamWaitEvent(s, d->ev_done, 0));
-    return update_impl(h, b, hyper, s, false);
+    return update_impl(h, b, hyper, s, step_plan(h, b, update_call(hyper)));
+}
+
+// what step_plan answers for a call described in integers (include/codae_hip.h); nothing is launched
+int codae_debug_step_plan(codae_handle h, const codae_buffers* b, const int32_t* call, int32_t* out, int32_t capacity) {
+    CODAE_REQUIRE(h != nullptr && b != nullptr && call != nullptr, "codae_debug_step_plan: null argument");
+    CODAE_REQUIRE(out != nullptr && capacity >= CODAE_STEP_PLAN_FIELDS, "codae_debug_step_plan: needs room for %d fields", CODAE_STEP_PLAN_FIELDS);
+    StepCall c{call[0], call[1], call[2], call[3], call[4] != 0, call[5] != 0, call[6] != 0, call[7] != 0};
+    CODAE_REQUIRE(c.kind >= STEP_TRAIN && c.kind <= STEP_UPDATE, "codae_debug_step_plan: unknown kind %d", c.kind);
+    CODAE_REQUIRE(c.kind == STEP_UPDATE || (c.B > 0 && c.B <= h->max_batch), "codae_debug_step_plan: batch %d outside (0, %d]", c.B, h->max_batch);
+    if (c.kind == STEP_BACKWARD || c.kind == STEP_DROPIN_BACKWARD)
+        CODAE_REQUIRE(c.layer_lo >= 0 && c.layer_lo < c.layer_hi && c.layer_hi <= h->L, "codae_debug_step_plan: layer range [%d, %d)", c.layer_lo, c.layer_hi);
+    if (c.kind == STEP_TRAIN) { c.layer_lo = 0; c.layer_hi = h->L; c.join = true; c.want_dx = false; c.has_out_y = false; }      // (as codae_train_step)
+    const StepPlan p = step_plan(h, b, c);
+    const int32_t fields[CODAE_STEP_PLAN_FIELDS] = {p.rows, p.path, p.loss, p.loss_finish, p.wgrad, p.streams, p.tail_on_caller, p.bias_finish,
+                                                    p.norm, p.update};
+    for (int i = 0; i < CODAE_STEP_PLAN_FIELDS; ++i) out[i] = fields[i];
+    return CODAE_OK;
 }
 
 }  // extern "C"

@@ -520,59 +520,64 @@ int launch_weight_average(float* avg, const float* p, int64_t n, const codae_wei
     return CODAE_OK;
 }
 
-int launch_clip_adam(float* p, float* g, float* m, float* v, int64_t n, const codae_hyper* hp,
-                     const double* grad_sq, bf16_t* shadow, const double* coef_in, hipStream_t s,
-                     const double* step_dev, const codae_optimizer* opt, float* vmax, const codae_weight_average* wa, float* avg) {
-    const bool sgd = !optimizer_is_default(opt) && opt->kind == CODAE_OPT_SGD;
-    const bool ams = !optimizer_is_default(opt) && opt->amsgrad != 0;
-    const bool avg_on = !weight_average_is_off(wa);
-    CODAE_REQUIRE(p && g && m && (v || sgd) && hp && n > 0, "clip_adam: bad args");
-    CODAE_REQUIRE(!avg_on || (avg != nullptr && a16(avg)), "clip_adam: the weight average needs a 16-byte aligned avg");
-    CODAE_REQUIRE(a16(p) && a16(g) && a16(m) && (sgd || a16(v)), "clip_adam: buffers must be 16-byte aligned");
-    CODAE_REQUIRE(!ams || (vmax != nullptr && a16(vmax)), "clip_adam: amsgrad needs a 16-byte aligned vmax");
-    CODAE_REQUIRE(hp->step >= 1, "clip_adam: step must be >= 1");
-    CODAE_REQUIRE(hp->max_grad_norm <= 0.f || grad_sq || coef_in, "clip_adam: clipping needs the grad_sq scalar");
-    const AdamConst c = adam_const(hp);
-    const OptConst o = opt_const(opt, hp);
-    const AvgConst ac = avg_const(wa, avg);
-    opt_dispatch(opt, avg_on, [&](auto K, auto A, auto S, auto V) {
+int launch_grad_sumsq(const float* g, int64_t n, double* scalars, bool clear, hipStream_t s) {
+    if (clear) {
+        CODAE_HIP_CHECK(hipMemsetAsync(scalars + CODAE_S_GRAD_SQ, 0, sizeof(double), s));
+        CODAE_HIP_CHECK(hipMemsetAsync(scalars + CODAE_S_GRAD_SQ_SLOTS, 0, CODAE_S_N_SLOTS * sizeof(double), s));
+    }
+    return launch_sumsq(g, n, scalars + CODAE_S_GRAD_SQ, s);
+}
+
+int check_update_launch(const char* who, const UpdateLaunch& u) {
+    const ParamVectors& x = u.x;
+    const bool sgd = !optimizer_is_default(u.opt) && u.opt->kind == CODAE_OPT_SGD;
+    const bool ams = !optimizer_is_default(u.opt) && u.opt->amsgrad != 0;
+    CODAE_REQUIRE(x.p && x.g && x.m && (x.v || sgd) && u.hp && u.n > 0, "%s: bad args", who);
+    CODAE_REQUIRE(weight_average_is_off(u.wa) || (x.avg != nullptr && a16(x.avg)), "%s: the weight average needs a 16-byte aligned avg", who);
+    CODAE_REQUIRE(a16(x.p) && a16(x.g) && a16(x.m) && (sgd || a16(x.v)), "%s: buffers must be 16-byte aligned", who);
+    CODAE_REQUIRE(!ams || (x.vmax != nullptr && a16(x.vmax)), "%s: amsgrad needs a 16-byte aligned vmax", who);
+    CODAE_REQUIRE(u.hp->step >= 1, "%s: step must be >= 1", who);
+    CODAE_REQUIRE(u.hp->max_grad_norm <= 0.f || u.grad_sq || u.coef_in, "%s: clipping needs the grad_sq scalar", who);
+    return CODAE_OK;
+}
+
+int launch_update(const UpdateLaunch& u, hipStream_t s) {
+    int rc = check_update_launch("clip_adam", u);
+    if (rc) return rc;
+    const ParamVectors& x = u.x;
+    const AdamConst c = adam_const(u.hp);
+    const OptConst o = opt_const(u.opt, u.hp);
+    const AvgConst ac = avg_const(u.wa, x.avg);
+    opt_dispatch(u.opt, !weight_average_is_off(u.wa), [&](auto K, auto A, auto S, auto V) {
         hipLaunchKernelGGL((clip_adam_kernel<decltype(K)::value, decltype(A)::value, decltype(S)::value, decltype(V)::value>),
-                           dim3(grid_for(n / 4 + 1)), dim3(NT), 0, s, p, g, m, v, n, c, grad_sq, shadow, coef_in, step_dev, vmax, o, ac);
+                           dim3(grid_for(u.n / 4 + 1)), dim3(NT), 0, s, x.p, x.g, x.m, x.v, u.n, c, u.grad_sq, x.shadow, u.coef_in, u.step_dev, x.vmax, o, ac);
     });
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;
 }
 
-int launch_clip_adam_tiled(float* p, float* g, float* m, float* v, const codae_hyper* hp, const double* grad_sq,
-                           bf16_t* shadow, bf16_t* shadow_t, int n_layers, const int64_t* w_off, const int* rows,
-                           const int* cols, int transposed_from, int64_t bias_off, int64_t bias_n, hipStream_t s,
-                           const double* step_dev, const codae_optimizer* opt, float* vmax, const codae_weight_average* wa, float* avg) {
-    const bool sgd = !optimizer_is_default(opt) && opt->kind == CODAE_OPT_SGD;
-    const bool ams = !optimizer_is_default(opt) && opt->amsgrad != 0;
-    const bool avg_on = !weight_average_is_off(wa);
-    CODAE_REQUIRE(p && g && m && (v || sgd) && hp && shadow && n_layers > 0 && n_layers <= 64, "clip_adam_tiled: bad args");
-    CODAE_REQUIRE(!avg_on || (avg != nullptr && a16(avg)), "clip_adam_tiled: the weight average needs a 16-byte aligned avg");
-    CODAE_REQUIRE(a16(p) && a16(g) && a16(m) && (sgd || a16(v)), "clip_adam_tiled: buffers must be 16-byte aligned");
-    CODAE_REQUIRE(!ams || (vmax != nullptr && a16(vmax)), "clip_adam_tiled: amsgrad needs a 16-byte aligned vmax");
-    CODAE_REQUIRE(hp->step >= 1, "clip_adam_tiled: step must be >= 1");
-    CODAE_REQUIRE(hp->max_grad_norm <= 0.f || grad_sq, "clip_adam_tiled: clipping needs the grad_sq scalar");
-    const AdamConst c = adam_const(hp);
-    const OptConst o = opt_const(opt, hp);
+int launch_update_tiled(const UpdateLaunch& u, const UpdateTiles& t, hipStream_t s) {
+    int rc = check_update_launch("clip_adam_tiled", u);
+    if (rc) return rc;
+    const ParamVectors& x = u.x;
+    CODAE_REQUIRE(x.shadow && t.n_layers > 0 && t.n_layers <= 64 && u.coef_in == nullptr, "clip_adam_tiled: bad args");
+    const AdamConst c = adam_const(u.hp);
+    const OptConst o = opt_const(u.opt, u.hp);
     AdamTiles jobs;
-    jobs.n_layers = n_layers; jobs.transposed_from = transposed_from; jobs.bias_off = bias_off; jobs.bias_n = bias_n;
+    jobs.n_layers = t.n_layers; jobs.transposed_from = t.transposed_from; jobs.bias_off = t.bias_off; jobs.bias_n = t.bias_n;
     int total = 0;
-    for (int l = 0; l < n_layers; ++l) {
-        CODAE_REQUIRE(rows[l] % 8 == 0 && cols[l] % 4 == 0 && w_off[l] % 8 == 0, "clip_adam_tiled: layer %d shape %d x %d", l, rows[l], cols[l]);
-        jobs.off[l] = w_off[l]; jobs.rows[l] = rows[l]; jobs.cols[l] = cols[l];
+    for (int l = 0; l < t.n_layers; ++l) {
+        CODAE_REQUIRE(t.rows[l] % 8 == 0 && t.cols[l] % 4 == 0 && t.w_off[l] % 8 == 0, "clip_adam_tiled: layer %d shape %d x %d", l, t.rows[l], t.cols[l]);
+        jobs.off[l] = t.w_off[l]; jobs.rows[l] = t.rows[l]; jobs.cols[l] = t.cols[l];
         jobs.tile_begin[l] = total;
-        total += ((rows[l] + AT_R - 1) / AT_R) * ((cols[l] + AT_C - 1) / AT_C);
+        total += ((t.rows[l] + AT_R - 1) / AT_R) * ((t.cols[l] + AT_C - 1) / AT_C);
     }
-    jobs.tile_begin[n_layers] = total;
-    const int bias_blocks = (int)((bias_n + NT * 8 - 1) / (NT * 8)) > 0 ? (int)((bias_n + NT * 8 - 1) / (NT * 8)) : 1;
-    const AvgConst ac = avg_const(wa, avg);
-    opt_dispatch(opt, avg_on, [&](auto K, auto A, auto S, auto V) {
+    jobs.tile_begin[t.n_layers] = total;
+    const int bias_blocks = (int)((t.bias_n + NT * 8 - 1) / (NT * 8)) > 0 ? (int)((t.bias_n + NT * 8 - 1) / (NT * 8)) : 1;
+    const AvgConst ac = avg_const(u.wa, x.avg);
+    opt_dispatch(u.opt, !weight_average_is_off(u.wa), [&](auto K, auto A, auto S, auto V) {
         hipLaunchKernelGGL((clip_adam_tiled_kernel<decltype(K)::value, decltype(A)::value, decltype(S)::value, decltype(V)::value>),
-                           dim3(total + bias_blocks), dim3(NT), 0, s, p, g, m, v, c, grad_sq, shadow, shadow_t, jobs, step_dev, vmax, o, ac);
+                           dim3(total + bias_blocks), dim3(NT), 0, s, x.p, x.g, x.m, x.v, c, u.grad_sq, x.shadow, t.shadow_t, jobs, u.step_dev, x.vmax, o, ac);
     });
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;

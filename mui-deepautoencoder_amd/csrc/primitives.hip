@@ -167,17 +167,11 @@ int codae_mse_loss_fwd_bwd(const float* x, const float* y, const float* fmask, f
     return launch_finish_loss(scalars, 1.0 / (double)n, (hipStream_t)stream);
 }
 
+// (codae_optimizer_update with opt NULL: the default Adam, the instantiation this entry always ran)
 int codae_clip_adam(float* params, float* grads, float* adam_m, float* adam_v, int64_t n, const codae_hyper* hyper,
                     double* scalars, void* stream) {
     CODAE_REQUIRE(hyper && scalars, "codae_clip_adam: null argument");
-    hipStream_t s = (hipStream_t)stream;
-    if (hyper->max_grad_norm > 0.f) {
-        CODAE_HIP_CHECK(hipMemsetAsync(scalars + CODAE_S_GRAD_SQ, 0, sizeof(double), s));
-        CODAE_HIP_CHECK(hipMemsetAsync(scalars + CODAE_S_GRAD_SQ_SLOTS, 0, CODAE_S_N_SLOTS * sizeof(double), s));
-        int rc = launch_sumsq(grads, n, scalars + CODAE_S_GRAD_SQ, s);
-        if (rc) return rc;
-    }
-    return launch_clip_adam(params, grads, adam_m, adam_v, n, hyper, scalars + CODAE_S_GRAD_SQ, nullptr, nullptr, s);
+    return codae_optimizer_update(params, grads, adam_m, adam_v, nullptr, n, hyper, nullptr, scalars, stream);
 }
 
 int codae_optimizer_update(float* p, float* g, float* m, float* v, float* vmax, int64_t n, const codae_hyper* hyper,
@@ -190,12 +184,12 @@ int codae_optimizer_update(float* p, float* g, float* m, float* v, float* vmax, 
     o = optimizer_canonical(opt != nullptr ? &o : nullptr);
     hipStream_t s = (hipStream_t)stream;
     if (hyper->max_grad_norm > 0.f) {
-        CODAE_HIP_CHECK(hipMemsetAsync(scalars + CODAE_S_GRAD_SQ, 0, sizeof(double), s));
-        CODAE_HIP_CHECK(hipMemsetAsync(scalars + CODAE_S_GRAD_SQ_SLOTS, 0, CODAE_S_N_SLOTS * sizeof(double), s));
-        rc = launch_sumsq(g, n, scalars + CODAE_S_GRAD_SQ, s);
+        rc = launch_grad_sumsq(g, n, scalars, true, s);
         if (rc) return rc;
     }
-    return launch_clip_adam(p, g, m, v, n, hyper, scalars + CODAE_S_GRAD_SQ, nullptr, nullptr, s, nullptr, &o, o.vmax);
+    UpdateLaunch u{};
+    u.x.p = p; u.x.g = g; u.x.m = m; u.x.v = v; u.x.vmax = o.vmax; u.n = n; u.hp = hyper; u.grad_sq = scalars + CODAE_S_GRAD_SQ; u.opt = &o;
+    return launch_update(u, s);
 }
 
 int codae_weight_average_update(float* avg, const float* p, int64_t n, const codae_weight_average* wa, int32_t step, void* stream) {

@@ -6,10 +6,13 @@ launch profiler records the class of every profiled launch in the order the host
 one shape per scheduling branch, to tests/golden/launch_plan.json.  The fixture was recorded once with record_case() below
 on the commit it names and is compared verbatim: a change that leaves the schedule alone passes against it unchanged.
 
-Each shape is the smallest that takes its branch by the conditions in defer_wgrad_mode, choose_split_k*, chain_supported
-and gemm_f32_small (csrc/engine.hip); `counts` restates what the branch means in launches, independently of the fixture,
-so that a shape that missed its branch on the recording commit could not have been recorded as if it had taken it.
+Each shape is the smallest that takes its branch by the conditions in step_plan / grouped_wgrad_strategy, choose_split_k*,
+chain_supported and gemm_f32_small (csrc/engine.hip); `counts` restates what the branch means in launches, independently of the
+fixture, so that a shape that missed its branch on the recording commit could not have been recorded as if it had taken it.
 No numerics are checked here.
+
+The same run also closes the loop with tests/test_step_plan_host.py: the plan the live engine answers for the calls the case made
+(codae_debug_step_plan, with the engine's real buffers) must say what the record shows was launched.
 """
 import ctypes as C
 import json
@@ -88,8 +91,24 @@ def env_toggle():
     hip.lib().codae_reload_env()
 
 
+PLAN_FIELDS = ["rows", "path", "loss", "loss_finish", "wgrad", "streams", "tail_on_caller", "bias_finish", "norm", "update"]
+TRAIN, FORWARD_LOSS, EVAL, BACKWARD, DROPIN_BACKWARD, UPDATE = range(6)           # call kinds of codae_debug_step_plan
+LOSS_FUSED, LOSS_IN_CHAIN = 2, 3
+
+
+def calls_of(case):
+    """The calls CASES[case] makes, as codae_debug_step_plan takes them: kind, B, lo, hi, join, dx wanted, out_y given, clipping."""
+    c = CASES[case]
+    B, L, run = c["B"], c["L"], c.get("run", "train")
+    if run == "train":
+        return [(TRAIN, B, 0, L, 1, 0, 0, 1)]
+    if run == "bucketed":
+        return [(FORWARD_LOSS, B, 0, L, 1, 0, 0, 0)] + [(BACKWARD, B, l, l + 1, 0, 0, 0, 0) for l in range(L - 1, -1, -1)] + [(UPDATE, 0, 0, 0, 1, 0, 0, 1)]
+    return [(EVAL, B, 0, L, 1, 0, 0, 0), (DROPIN_BACKWARD, B, 0, L, 1, 0, 0, 0), (DROPIN_BACKWARD, B, 0, L, 1, 1, 0, 0)]
+
+
 def record_case(case, setenv):
-    """(step_path, class names of the second step's launches in issue order) of CASES[case]."""
+    """(step_path, class names of the second step's launches in issue order, the plans of the calls made) of CASES[case]."""
     import bench
     from codae import hip
     from codae.hip import ACT_LEAKY, KERNEL_CLASSES
@@ -143,18 +162,34 @@ def record_case(case, setenv):
     hip.check(lib.codae_profile_end(eng._h, kinds, ms, cap, C.byref(n)))
     assert 0 < n.value < cap
     path = eng.step_path(B)
+    plans = []
+    for call in calls_of(case) + [(TRAIN, B, 0, L, 1, 0, 0, 1)]:          # (last: the fused step's, which codae_step_path is about)
+        out = (C.c_int32 * len(PLAN_FIELDS))()
+        hip.check(lib.codae_debug_step_plan(eng._h, C.byref(eng.bufs), (C.c_int32 * 8)(*call), out, len(PLAN_FIELDS)))
+        plans.append(dict(zip(PLAN_FIELDS, list(out)), kind=call[0]))
     torch.cuda.synchronize()
-    return path, [KERNEL_CLASSES[kinds[i]] for i in range(n.value)]
+    return path, [KERNEL_CLASSES[kinds[i]] for i in range(n.value)], plans
 
 
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_launch_plan(case, env_toggle):
     with open(FIXTURE) as f:
         want = json.load(f)["cases"][case]
-    path, kinds = record_case(case, env_toggle)
+    path, kinds, plans = record_case(case, env_toggle)
     print("MEASURE launch plan %s: %s %s" % (case, path, " ".join(kinds)))
     assert path == CASES[case]["path"], (case, path)
     for cls, n in CASES[case]["counts"].items():
         assert kinds.count(cls) == n, (case, cls, kinds.count(cls), n, kinds)
     assert path == want["step_path"], (case, path, want["step_path"])
     assert kinds == want["kinds"], (case, kinds, want["kinds"])
+    # the plan says what was launched, where the record can show it
+    L, fused_step, plans = CASES[case]["L"], plans[-1], plans[:-1]
+    assert ("chain", "layers")[fused_step["path"] == 0] == path, (case, fused_step, path)
+    grouped = {p["wgrad"] != 0 for p in plans if p["kind"] in (TRAIN, BACKWARD, DROPIN_BACKWARD)}
+    assert len(grouped) == 1, (case, plans)
+    last_dgrad = max(i for i, k in enumerate(["gemm_dgrad"] + kinds) if k == "gemm_dgrad")         # (0: the chain kernel made them all)
+    assert grouped.pop() == ("gemm_wgrad" not in kinds[:last_dgrad]), (case, plans, kinds)
+    fwd_then_loss = kinds.count("loss") == 1 and kinds[:kinds.index("loss")].count("gemm_fwd") == L - 1
+    assert any(p["loss"] == LOSS_FUSED for p in plans) == fwd_then_loss, (case, plans, kinds)
+    assert any(p["loss"] == LOSS_IN_CHAIN for p in plans) == (kinds.count("chain") == 1 and "gemm_fwd" not in kinds), (case, plans, kinds)
+    assert any(p["update"] != 0 for p in plans) == (kinds.count("adam") == 1), (case, plans, kinds)
