@@ -71,6 +71,8 @@ extern "C" {
  *      layout or enum change
  *      (still 11) + codae_debug_gemm_bf16: a new entry with plain arguments only, no layout or enum change
  *      (still 11) + codae_debug_step_plan, CODAE_STEP_PLAN_FIELDS: a new host-only entry with plain arguments, no layout or enum change
+ *      (still 11) + CODAE_AUC_*, codae_assemble_outfits, codae_outfit_scores, codae_auc_blocks, codae_auc_counts, codae_score_outfits:
+ *      new entries with plain arguments only, no struct, no layout or enum change; the assemble is booked under CODAE_K_GATHER
  * The binding must refuse a library whose codae_abi_version() differs and must check its own struct sizes against
  * codae_struct_sizes() at load (mui-deepautoencoder_amd/codae/hip/__init__.py does both). */
 #define CODAE_ABI_VERSION 11
@@ -1014,6 +1016,60 @@ int codae_retrieval_metrics_batched(const float* pred, int32_t B, int32_t io, in
                                     int32_t n_cand, const int32_t* cand_count, const int32_t* cand_pos, const int32_t* ks, int32_t n_ks,
                                     float* work, int32_t chunk, void* pair_state, int32_t* perm_ws, float* q_ws, double* acc,
                                     void* stream);
+
+/* ---- Assembled outfits and compatibility --------------------------------------------------------------------------------
+ * S slots, E columns per slot, io = S E.  data [n_rows][io] fp32, optionally with its bf16 image (codae_cast_f32_to_bf16).
+ * Assembled outfit.  items int32 [Q][S]: items[q][s] = r >= 0 says slot s of outfit q holds the slot-s item of dataset row r; a
+ * negative value (and, in the kernels, a value >= n_rows: no index reaches memory unchecked) says the outfit has no item there.  With
+ * a presence table (uint8 [n_rows][S], "Slot presence"), present[r][s] == 0 makes the pair absent exactly as a negative entry does:
+ * selection, what data holds there is never read into a result and may be NaN.  n_q = present slots of outfit q.
+ * Assemble.  X[row][s E + e] = +0 if the pair (q, s) is absent or slot s is blanked for this row, else src[items[q][s]][s E + e];
+ * src = the fp32 rows or (src_bf16) the bf16 image, which assembles into bf16 rows only.  Two forms: blank int32 [Q] or NULL - one
+ * output row per outfit, slot blank[q] blanked (negative: none); leave_one_out != 0 - S rows per outfit, row q S + v has slot v
+ * blanked (blank must be NULL).  A copy: bit-exact (fp32 -> bf16 rounds to nearest even as every gather here), a NaN in a present
+ * unblanked element is copied.  out rows out_ld elements apart (<= 0: io).  16 bytes per lane where E, the strides and the pointers
+ * allow (8 columns into bf16, 4 into fp32), narrower forms elsewhere; a blanked or absent group is stored as zeros and never loaded.
+ * Slot scores.  Y [Q S][y_ld] fp32 = the evaluation forward of the leave-one-out rows (live or averaged weights, no noise, no
+ * dropout, no criterion, no metric sums touched, no presence lookup by batch position).  For a present pair, y = Y[q S + s][slot s],
+ * x = data[items[q][s]][slot s]:
+ *   cos[q][s] = dot / (max(|x|, eps) max(|y|, eps)), eps = CODAE_COS_EPS, as CODAE_LOSS_SLOT_COSINE defines it
+ *   sq[q][s]  = sum (x - y)^2
+ * fp32 products and sums in an order that depends on E (and on whether the 16-byte form applies) alone: the bits do not depend on Q,
+ * on the position in the batch or on the chunking.  Absent pairs: cos = sq = 0, not counted.
+ * Outfit score.  score[q] = (sum over present s, ascending, of cos[q][s]) / n_q in fp32; NaN when n_q < 2 (an outfit of one item has
+ * no context to be reconstructed from); a NaN in Y propagates.  n_present[q] = n_q.
+ * AUC.  Positive scores pos [P], negative scores neg [M], neg_slot [M] the slot that was swapped, neg_parent [M] (or NULL) the
+ * positive each negative was made from.  pos_on uint8 [P] (or NULL = all): a positive that is off takes part in nothing, nor does a
+ * negative whose slot lies outside [0, n_slots) or whose parent is off.  A pair (i, j) is a win iff pos_i > neg_j, a tie iff pos_i ==
+ * neg_j, everything else - every comparison with a NaN on either side included - a loss: a collapsed model scores last, as in the
+ * retrieval metrics.  counts int64 [n_slots + 1][CODAE_AUC_STRIDE], overwritten:
+ *   counts[s] = {wins, ties, pairs = live positives x live negatives of slot s, paired wins = #{j of slot s: pos[parent_j] > neg_j}}
+ *   counts[n_slots] = {live positives, live negatives, 0, 0}
+ * auc = (wins + ties / 2) / pairs per slot and in total (the caller divides: pairs 0 has no AUC); paired accuracy = paired wins /
+ * live negatives.  Exact 64-bit integers: per-workgroup partial counts with plain stores (parts_ws: codae_auc_blocks(M) * n_slots * 3
+ * 64-bit words), one finish workgroup adding them in a fixed order; the same bits every run.
+ * codae_score_outfits: assemble (leave-one-out) -> the engine's forward launches of an evaluation step -> slot scores for Q outfits,
+ * Q n_slots <= max_batch, in the engine's own workspaces, without a host synchronisation; data = the dataset the items index (bf16
+ * engine: its registered image is read when there is one), the presence table = the engine's (codae_set_slot_presence), b = the live
+ * buffers or those of the weight average.  cos, sq [Q][n_slots], score [Q], n_present int32 [Q].
+ * CODAE_E_INVALID with the offending value in codae_last_error(): n_slots outside 1 .. 128 or not dividing io, Q < 1, Q n_slots >
+ * max_batch (codae_score_outfits), a presence table of another shape, P or M < 1. */
+#define CODAE_AUC_WINS 0
+#define CODAE_AUC_TIES 1
+#define CODAE_AUC_PAIRS 2
+#define CODAE_AUC_PAIRED 3
+#define CODAE_AUC_STRIDE 4
+int codae_assemble_outfits(const void* src, int32_t src_bf16, int64_t n_rows, int32_t io, int32_t n_slots, const int32_t* items, int32_t Q,
+                           const int32_t* blank, int32_t leave_one_out, const uint8_t* present, void* out, int32_t out_bf16, int64_t out_ld,
+                           void* stream);
+int codae_outfit_scores(const float* data, int64_t n_rows, int32_t io, int32_t n_slots, const int32_t* items, int32_t Q,
+                        const uint8_t* present, const float* Y, int64_t y_ld, float* cos, float* sq, float* score, int32_t* n_present,
+                        void* stream);
+int codae_auc_blocks(int32_t M);
+int codae_auc_counts(const float* pos, const uint8_t* pos_on, int32_t P, const float* neg, const int32_t* neg_slot,
+                     const int32_t* neg_parent, int32_t M, int32_t n_slots, void* parts_ws, int64_t* counts, void* stream);
+int codae_score_outfits(codae_handle h, const codae_buffers* b, const float* data, int64_t n_rows, const int32_t* items, int32_t Q,
+                        int32_t n_slots, float* cos, float* sq, float* score, int32_t* n_present, void* stream);
 
 /* ---- GEMM primitives (exported for kernel-level parity tests / benchmarks) - */
 /* y[M][N] = act(x[M][K] . W[N][K]^T + b[N]), fp32 in / fp32 out (the parity engine's GEMM: CODAE_PREC_F32 above) */

@@ -31,6 +31,8 @@ SCHED_CONSTANT, SCHED_COSINE, SCHED_LINEAR, SCHED_STEP = 0, 1, 2, 3
 AVG_OFF, AVG_EMA, AVG_SWA = 0, 1, 2
 # CODAE_RM_* of include/codae_hip.h: the fields of one slot's block of retrieval-metric sums (codae.tool.RetrievalMetrics reads them)
 RM_PAIRS, RM_RRE, RM_RR, RM_HIT, RM_MAX_KS, RM_HIST, RM_STRIDE = 0, 1, 2, 3, 8, 16, 48
+# CODAE_AUC_* of include/codae_hip.h: the fields of one slot's row of AUC counts (codae.tool.Compatibility reads them)
+AUC_WINS, AUC_TIES, AUC_PAIRS, AUC_PAIRED, AUC_STRIDE = 0, 1, 2, 3, 4
 KERNEL_CLASSES = ("gemm_fwd", "gemm_dgrad", "gemm_wgrad", "loss", "gather", "sumsq", "adam", "slab_reduce", "chain",
                   "bias_finish", "dropout")
 
@@ -208,6 +210,11 @@ PROTOTYPES = {
                                       _I32, _P, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "codae_retrieval_metrics_batched": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _I64, _P, _P, _I32, _P,
                                                   _P, _P, _I32, _P, _I32, _P, _P, _P, _P, _P]),
+    "codae_assemble_outfits": (C.c_int, [_P, _I32, _I64, _I32, _I32, _P, _I32, _P, _I32, _P, _P, _I32, _I64, _P]),
+    "codae_outfit_scores": (C.c_int, [_P, _I64, _I32, _I32, _P, _I32, _P, _P, _I64, _P, _P, _P, _P, _P]),
+    "codae_auc_blocks": (C.c_int, [_I32]),
+    "codae_auc_counts": (C.c_int, [_P, _P, _I32, _P, _P, _P, _I32, _I32, _P, _P, _P]),
+    "codae_score_outfits": (C.c_int, [_P, C.POINTER(Buffers), _P, _I64, _P, _I32, _I32, _P, _P, _P, _P, _P]),
     "codae_step_path": (C.c_int, [_P, _P, _I32]),
     "codae_debug_step_plan": (C.c_int, [_P, C.POINTER(Buffers), _P, _P, _I32]),
     "codae_linear_f32": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _P]),

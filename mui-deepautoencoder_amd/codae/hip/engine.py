@@ -201,8 +201,10 @@ class DaeEngine:
             check(self._lib.codae_sync_shadows(self._h, C.byref(self.bufs), current_stream()))
 
     # ---- drop-in path -----------------------------------------------------------------
-    def forward(self, x, layer_lo=0, layer_hi=None):
+    def forward(self, x, layer_lo=0, layer_hi=None, weights="live"):
+        """weights: "live", or "average" to run on the weight average (as eval_step)."""
         layer_hi = self.L if layer_hi is None else layer_hi
+        bufs = self._eval_bufs(weights)
         if x.dim() != 2 or x.shape[1] != self.schedule[layer_lo][0]:
             raise HipError("forward: input shape %s does not match layer %d (%d features)"
                            % (tuple(x.shape), layer_lo, self.schedule[layer_lo][0]))
@@ -211,7 +213,7 @@ class DaeEngine:
         x = x.detach().to(dtype=torch.float32).contiguous()
         y = torch.empty((x.shape[0], self.schedule[layer_hi - 1][1]), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            check(self._lib.codae_forward(self._h, C.byref(self.bufs), ptr(x), ptr(y), x.shape[0], layer_lo, layer_hi,
+            check(self._lib.codae_forward(self._h, C.byref(bufs), ptr(x), ptr(y), x.shape[0], layer_lo, layer_hi,
                                           1, current_stream()))
         self.generation += 1
         return y
@@ -625,6 +627,30 @@ class DaeEngine:
         bufs = self._eval_bufs(weights)
         with torch.cuda.device(self.device):
             check(self._lib.codae_eval_step(self._h, C.byref(bufs), C.byref(batch), ptr(out_y), current_stream()))
+
+    def score_outfits(self, data, items, weights="live", n_slots=None):
+        """codae_score_outfits (include/codae_hip.h, "Assembled outfits and compatibility"): items int32 [Q, S] on this device, rows of
+        `data` (the contiguous fp32 [N, io] dataset on this device) per (outfit, slot), negative = no item; Q * S <= max_batch.  The S
+        leave-one-out rows of every outfit go through the evaluation forward (weights: "live" or "average") and each left-out item is
+        compared with its reconstruction -> {"score": [Q], "cos": [Q, S], "sq": [Q, S], "n_present": [Q] int32}.  The presence table in
+        force (set_slot_presence) makes the pairs it marks absent.  The metric sums, the parameters and the optimizer state are not
+        touched; no host synchronisation.  n_slots: S when items is not given as [Q, S]."""
+        if data.dtype != torch.float32 or not data.is_contiguous() or data.device != self.device or data.dim() != 2:
+            raise HipError("score_outfits: data must be the contiguous fp32 [N, io] dataset on %s" % self.device)
+        if not torch.is_tensor(items) or items.dtype != torch.int32 or items.device != self.device or not items.is_contiguous() \
+                or items.dim() != 2:
+            raise HipError("score_outfits: items must be a contiguous int32 [Q, S] tensor on %s" % self.device)
+        Q, S = int(items.shape[0]), int(items.shape[1] if n_slots is None else n_slots)
+        bufs = self._eval_bufs(weights)
+        with torch.cuda.device(self.device):
+            f32 = dict(dtype=torch.float32, device=self.device)
+            out = {"score": torch.empty(max(Q, 1), **f32), "cos": torch.empty((max(Q, 1), S), **f32), "sq": torch.empty((max(Q, 1), S), **f32),
+                   "n_present": torch.empty(max(Q, 1), dtype=torch.int32, device=self.device)}
+            check(self._lib.codae_score_outfits(self._h, C.byref(bufs), ptr(data), int(data.shape[0]), ptr(items), Q, S, ptr(out["cos"]),
+                                                ptr(out["sq"]), ptr(out["score"]), ptr(out["n_present"]), current_stream()))
+        self.generation += 1
+        self._keep_outfits = (data, items)        # (raw pointers: alive until the next call's kernels are queued behind these)
+        return out
 
     def profile_begin(self, classes=("gemm_fwd", "gemm_dgrad", "gemm_wgrad"), max_records=4096, every=1):
         from . import KERNEL_CLASSES

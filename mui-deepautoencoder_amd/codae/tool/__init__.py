@@ -2,7 +2,7 @@
 `from codae.tool import Corrupter, CombinedCriterion, ...` resolves here), gathered from this build's modules.
 The reference's legacy argparse table (codae/tool/parser.py) and attr-dict (dictionnary.py) are out of scope
 (SURVEY.md section 2): nothing on the path uses them, so they have no counterpart here."""
-from . import average, batching, contrast, corruption, criteria, dropout, emphasis, noise, optimizer, presence, recon_loss, runlog, tied
+from . import average, batching, compat, contrast, corruption, criteria, dropout, emphasis, noise, optimizer, presence, recon_loss, runlog, tied
 
 _PUBLIC = {
     runlog: ("set_logging", "display_info", "get_date", "PlotDrawer", "export_parameters_to_json"),
@@ -20,6 +20,8 @@ _PUBLIC = {
     tied: ("TiedWeights",),        # the decoder uses the encoder's transposed matrices: pairs, and the fold / mirror in torch ops
     criteria: ("get_rmse", "RankingLoss", "ComplementRetriever", "RetrievalMetrics", "retrieval_metrics_from_config",
                "CombinedCriterion"),
+    # outfits assembled per (query, slot) from the items of different rows: their score, and the AUC of real against swapped ones
+    compat: ("Compatibility", "CompatibilityMetrics", "compatibility_from_config"),
 }
 __all__ = []
 for _module, _names in _PUBLIC.items():

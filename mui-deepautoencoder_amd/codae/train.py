@@ -747,6 +747,82 @@ class HipEmbeddingTrainer:
         rm.mask_table, rm.mask_to_use = self.mask_table, self.mask_to_use
         return rm
 
+    # ---- assembled outfits (include/codae_hip.h, "Assembled outfits and compatibility") ------------------------------------
+    def _outfit_items(self, items, who):
+        """items -> a contiguous int32 [Q, S] device tensor; a host tensor / list is checked against the dataset's rows first (on the
+        device an entry past the last row counts as absent: the kernels never read through an unchecked index)."""
+        S, _ = self._slots()
+        t = items if torch.is_tensor(items) else torch.as_tensor(items)
+        if t.dim() != 2 or t.shape[1] != S or t.shape[0] < 1 or t.dtype.is_floating_point or t.dtype == torch.bool:
+            raise HipError("%s: items must be an integer [Q, %d] tensor with Q >= 1, got %s %s" % (who, S, t.dtype, tuple(t.shape)))
+        if t.device.type == "cpu" and int(t.max()) >= int(self.data.shape[0]):
+            raise HipError("%s: items name row %d, the dataset has %d" % (who, int(t.max()), int(self.data.shape[0])))
+        return t.to(device=self.device, dtype=torch.int32).contiguous()
+
+    def score_outfits(self, items, weights="live"):
+        """Score assembled outfits: items integer [Q, S], items[q][s] = the dataset row whose slot-s item outfit q holds, negative =
+        none (with a presence table a slot the row lacks is absent too).  Every present item is left out in turn, reconstructed by
+        the evaluation forward from the others (weights: "live" or "average") and compared with itself -> {"score": [Q] the mean
+        cosine (NaN with fewer than two items), "cos": [Q, S], "sq": [Q, S] the squared error, "n_present": [Q] int32}, device
+        tensors.  Runs in chunks of max_batch // S outfits without a host synchronisation; epoch_sums(), the parameters and the
+        optimizer state stay exactly as they were."""
+        S, _ = self._slots()
+        it = self._outfit_items(items, "score_outfits()")
+        per = self.engine.max_batch // S
+        if per < 1:
+            raise HipError("score_outfits(): max_batch %d holds no outfit of %d slots" % (self.engine.max_batch, S))
+        parts = [self.engine.score_outfits(self.data, it[o:o + per], weights=weights) for o in range(0, int(it.shape[0]), per)]
+        if len(parts) == 1:
+            return parts[0]
+        return {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+
+    def complete_items(self, items, slot, k, exclude_items=True, distinct=True, candidates=None, chunk=8192, weights="live"):
+        """complete() for assembled outfits: slot `slot` of every outfit is blanked - whatever items[:, slot] holds -, the rest runs
+        through the evaluation forward and the reconstruction is ranked against the resident rows' items of that slot, with
+        complete()'s contract: (idx LongTensor [Q, k], score FloatTensor [Q, k]), ordering, (-1, -inf) padding, presence-restricted
+        candidates.  exclude_items: never return the item the query itself names in items[:, slot] (with `distinct`, the item that
+        row belongs to)."""
+        from .tool.compat import Compatibility
+        from .tool.criteria import ComplementRetriever
+        S, E = self._slots()
+        if isinstance(slot, bool) or not isinstance(slot, int) or not 0 <= slot < S:
+            raise HipError("complete_items(): slot must be an int in [0, %d), got %r" % (S, slot))
+        it = self._outfit_items(items, "complete_items()")
+        Q = int(it.shape[0])
+        if Q > self.engine.max_batch:
+            raise HipError("complete_items(): %d outfits exceed max_batch %d" % (Q, self.engine.max_batch))
+        cand = None if candidates is None else tuple(sorted(set(int(i) for i in candidates)))
+        pslot = None
+        if self.presence is not None:
+            pslot = slot
+            has = self.presence.table[:, slot] != 0
+            cand = tuple(int(i) for i in (has.nonzero()[0] if cand is None else [i for i in cand if 0 <= i < has.shape[0] and has[i]]))
+            if not cand:
+                return (torch.full((Q, int(k)), -1, dtype=torch.long, device=self.device),
+                        torch.full((Q, int(k)), float("-inf"), dtype=torch.float32, device=self.device))
+        key = (bool(distinct), cand, pslot)
+        cache = self.__dict__.setdefault("_retrievers", {})
+        if key not in cache:
+            cache[key] = ComplementRetriever(_ResidentInventory(self.data, S, E), self.device, candidates=key[1], distinct=key[0])
+        ret = cache[key]
+        blank = torch.full((Q,), slot, dtype=torch.int32, device=self.device)
+        x = Compatibility.assemble(self.data, it, blank=blank, presence=self.presence)
+        y = self.engine.forward(x, weights=weights)          # the evaluation's forward launches; no loss kernel, no metric sums
+        exclude = it[:, slot].contiguous() if exclude_items else None
+        ret._check_args(y, slot, k, exclude, chunk)
+        return ret._device_topk(y, int(k), exclude, int(chunk), slot=slot)
+
+    def compatibility_metrics(self, validation_indices, negatives=1, seed=0, distinct=True):
+        """A tool.CompatibilityMetrics over the resident data, bound to this trainer and its presence table: add_batch(row_idx,
+        weights=...) scores the outfits of those validation rows and their swapped negatives; total() gives the AUC and the paired
+        accuracy."""
+        from .tool.compat import CompatibilityMetrics
+        S, E = self._slots()
+        cm = CompatibilityMetrics(_ResidentInventory(self.data, S, E), validation_indices, self.device, negatives=negatives, seed=seed,
+                                  presence=self.presence, distinct=distinct)
+        cm.trainer = self
+        return cm
+
     def epoch_sums(self, reset=True, reduce=True):
         """(sum (x-y)^2, sum (1-fmask)(x-y)^2) accumulated since the last reset (summed over the
         ranks when `reduce`)."""

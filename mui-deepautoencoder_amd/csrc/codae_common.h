@@ -464,6 +464,18 @@ int launch_cast_bf16(const float* src, bf16_t* dst, int64_t n, hipStream_t s);
 int launch_corrupt(const float* x, const float* mask, float* out, int64_t n, hipStream_t s);
 int launch_expand_masks(const int32_t* mask_id, const uint8_t* table, const int32_t* k_of_mask, int B, int io,
                         int k_max, float* masks_out, float* fmask_out, hipStream_t s);
+// ---- assembled outfits and compatibility (compat.hip; include/codae_hip.h, "Assembled outfits and compatibility") ----
+// assemble: out rows [Q] (blank [Q] or null) or [Q S] (leave_one_out) from src = the fp32 rows or, src_bf16, their bf16 image (bf16 out
+// only); out_ld 0 = io.  outfit_scores: Y [Q S][y_ld] fp32, the leave-one-out reconstruction.  auc_counts: parts_ws auc_blocks(M) * S * 3
+// 64-bit words, counts int64 [S + 1][4].  Every argument error is CODAE_E_INVALID with the offending value named.
+int launch_assemble_outfits(const void* src, int src_bf16, int64_t n_rows, int io, int n_slots, const int32_t* items, int Q,
+                            const int32_t* blank, int leave_one_out, const uint8_t* present, void* out, int out_bf16, int64_t out_ld,
+                            hipStream_t s);
+int launch_outfit_scores(const float* data, int64_t n_rows, int io, int n_slots, const int32_t* items, int Q, const uint8_t* present,
+                         const float* Y, int64_t y_ld, float* cos_out, float* sq_out, float* score, int32_t* n_present, hipStream_t s);
+int auc_blocks(int M);
+int launch_auc_counts(const float* pos, const uint8_t* pos_on, int P, const float* neg, const int32_t* neg_slot, const int32_t* neg_parent,
+                      int M, int n_slots, void* parts_ws, int64_t* counts, hipStream_t s);
 // ---- stand-alone losses and reductions (elementwise.hip and the files named below); the update (optimizer.hip) ----
 // One stand-alone loss launch: y fp32 [B][io], x gathered from `batch`; writes dy (fp32 or bf16, row stride dy_ld; 0 = io), one
 // colsum_part row per block (partial sums of the last bias gradient; may be null) and the per-block sums `parts`.

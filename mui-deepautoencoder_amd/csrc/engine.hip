@@ -1570,6 +1570,51 @@ int codae_eval_step(codae_handle h, const codae_buffers* b, const codae_batch* b
     return codae_step_forward_loss(h, b, batch, nullptr, out_y, stream);
 }
 
+// Assemble the leave-one-out rows of Q outfits into act[0], run the evaluation's forward launches over them (run_linear per layer, the
+// last one into the fp32 output buffer) and score them: no noise, no dropout, no criterion, no loss kernel - the metric sums are not
+// touched -, the presence table consulted by ITEM row, never by batch position.  bf16 engine: the rows come from the registered bf16
+// image when `data` is the dataset it was made from (the same bits as rounding the fp32 rows).
+int codae_score_outfits(codae_handle h, const codae_buffers* b, const float* data, int64_t n_rows, const int32_t* items, int32_t Q,
+                        int32_t n_slots, float* cos, float* sq, float* score, int32_t* n_present, void* stream) {
+    CODAE_REQUIRE(h != nullptr && b != nullptr, "null handle or buffers");
+    const int L = h->L, io = h->in[0];
+    CODAE_REQUIRE(io == h->out[L - 1], "codae_score_outfits: the model maps %d columns to %d", io, h->out[L - 1]);
+    CODAE_REQUIRE(n_slots >= 1 && n_slots <= 128, "codae_score_outfits: 1 .. 128 slots, got %d", n_slots);
+    CODAE_REQUIRE(io % n_slots == 0, "codae_score_outfits: n_slots %d does not divide io %d", n_slots, io);
+    CODAE_REQUIRE(Q >= 1, "codae_score_outfits: Q %d must be at least 1", Q);
+    CODAE_REQUIRE((int64_t)Q * n_slots <= h->max_batch, "codae_score_outfits: %d outfits of %d slots exceed max_batch %d", Q, n_slots,
+                  h->max_batch);
+    CODAE_REQUIRE(data && items && cos && sq && score && n_present && n_rows > 0, "codae_score_outfits: null argument, or no rows");
+    const uint8_t* const pres = h->tc.pres.table;
+    CODAE_REQUIRE(pres == nullptr || (h->tc.pres.n_slots == n_slots && h->tc.pres.n_rows == n_rows),
+                  "codae_score_outfits: the presence table is [%lld][%d], the outfits index [%lld][%d]", (long long)h->tc.pres.n_rows,
+                  h->tc.pres.n_slots, (long long)n_rows, n_slots);
+    const int B = Q * n_slots;
+    int rc = check_common(h, b, B);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const bool bf = h->prec == CODAE_PREC_BF16;
+    const int rows = h->rows_for(B);
+    h->drop_live = false;     // (an evaluation forward never drops)
+    const codae_engine::ImageCfg& im = h->tc.img;
+    const bool from_image = bf && !h->cfg.no_dataset_image && im.image != nullptr && data == im.data && io == im.io && n_rows == im.n_rows;
+    {
+        ProfScope prof(h, CODAE_K_GATHER, s);
+        rc = launch_assemble_outfits(from_image ? im.image : (const void*)data, from_image, n_rows, io, n_slots, items, Q, nullptr, 1, pres,
+                                     act_ptr(h, b, 0), bf, h->in_ld[0], s);
+    }
+    if (rc) return rc;
+    rc = zero_pad_rows(h, act_ptr(h, b, 0), B, rows, h->in_ld[0], s);
+    if (rc) return rc;
+    float* y = reinterpret_cast<float*>(act_ptr(h, b, L));
+    for (int l = 0; l < L; ++l) {
+        rc = (l == L - 1) ? run_linear(h, b, l, act_ptr(h, b, l), y, true, B, s)
+                          : run_linear(h, b, l, act_ptr(h, b, l), act_ptr(h, b, l + 1), false, rows, s);
+        if (rc) return rc;
+    }
+    return launch_outfit_scores(data, n_rows, io, n_slots, items, Q, pres, y, io, cos, sq, score, n_present, s);
+}
+
 // a layer range of the step's backward; join: the call returns with `stream` waiting for the side stream
 static int step_backward(const char* who, codae_handle h, const codae_buffers* b, int B, int layer_lo, int layer_hi, bool join, void* stream) {
     int rc = check_common(h, b, B);

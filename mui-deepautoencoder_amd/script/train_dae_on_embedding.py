@@ -214,6 +214,15 @@ def main():
     retrieval = trainer.retrieval_metrics(validation_indices, **rm_args) if rm_args is not None else None
     if retrieval is not None:
         book.update({k: [] for k in ["mrr"] + ["hit@%d" % k for k in retrieval.ks] + ["ranked_pairs"]})
+    # HIP: COMPATIBILITY: {NEGATIVES: 1, SEED: 0, DISTINCT: true} (build-only key): compatibility prediction on the validation rows -
+    # every row scored as an outfit (each item left out in turn and reconstructed from the others) against NEGATIVES copies of it with
+    # one item swapped for another validation row's: the AUC and the share of swapped outfits that score below their original;
+    # absent = nothing is added to the sweep, the log or book.json
+    from codae.tool import compatibility_from_config
+    cm_args = compatibility_from_config(config.get("HIP", {}).get("COMPATIBILITY"))
+    compat = trainer.compatibility_metrics(validation_indices, **cm_args) if cm_args is not None else None
+    if compat is not None:
+        book.update({k: [] for k in ("auc", "paired_acc", "scored_outfits")})
 
     for epoch in range(epochs):
         log.info("===================================================== EPOCH = %d" % epoch)
@@ -245,6 +254,8 @@ def main():
                     ranking_loss.add(y[keep].contiguous(), idx[keep].contiguous(), corrupter, run=0)
             if retrieval is not None:
                 retrieval.add(y, idx, run=0)
+            if compat is not None:
+                compat.add_batch(idx, weights=eval_weights)
         rl = ranking_loss.total() if (is_ranked is None or rank_indices) else 0.0     # (no complete validation row: nothing was ranked)
         sq, sqp = trainer.epoch_sums(reduce=False)      # every rank evaluates the whole validation set
         book["fvl"].append(np.sqrt(sq / den["validation"][0]))
@@ -262,6 +273,14 @@ def main():
             book["ranked_pairs"].append(rm["pairs"])
             log.info("VALIDATION MRR           = %7f" % rm["mrr"])
             log.info("VALIDATION RANKED PAIRS  = %d" % rm["pairs"])
+        if compat is not None:
+            cm = compat.total()
+            book["auc"].append(cm["auc"])
+            book["paired_acc"].append(cm["paired_acc"])
+            book["scored_outfits"].append(cm["outfits"])
+            log.info("VALIDATION COMPATIBILITY AUC = %7f" % cm["auc"])
+            log.info("VALIDATION PAIRED ACCURACY   = %7f" % cm["paired_acc"])
+            log.info("VALIDATION SCORED OUTFITS    = %d" % cm["outfits"])
     log.info("TRAINING HAS ENDED.")
 
     if rank == 0:
