@@ -73,6 +73,9 @@ extern "C" {
  *      (still 11) + codae_debug_step_plan, CODAE_STEP_PLAN_FIELDS: a new host-only entry with plain arguments, no layout or enum change
  *      (still 11) + CODAE_AUC_*, codae_assemble_outfits, codae_outfit_scores, codae_auc_blocks, codae_auc_counts, codae_score_outfits:
  *      new entries with plain arguments only, no struct, no layout or enum change; the assemble is booked under CODAE_K_GATHER
+ *      (still 11) + CODAE_NOISE_SWAP, codae_swap, codae_set_swap_pool, codae_corrupt_batch_swap, codae_emph_loss_swap,
+ *      codae_recon_loss_fwd_bwd_swap: a new noise kind and new entries only, codae_noise keeps its layout, no existing enum value
+ *      changes; the swap gathers are booked under CODAE_K_GATHER
  * The binding must refuse a library whose codae_abi_version() differs and must check its own struct sizes against
  * codae_struct_sizes() at load (mui-deepautoencoder_amd/codae/hip/__init__.py does both). */
 #define CODAE_ABI_VERSION 11
@@ -144,12 +147,37 @@ enum {
  *                u2 = (rb >> 8) 2^-24, rho = sqrt(-2 ln u1), n_a = rho cos(2 pi u2), n_b = rho sin(2 pi u2)
  *                                                                                   p0 = sigma >= 0
  * The same dataset row gets the same noise wherever it sits in a batch and on whichever data-parallel rank (a row that
- * appears twice in one batch gets the same noise twice; the epoch sampler draws without replacement). */
+ * appears twice in one batch gets the same noise twice; the epoch sampler draws without replacement).
+ *
+ * Swap noise (CODAE_NOISE_SWAP): with probability p a whole SLOT of the training input is replaced by the same slot of another
+ * dataset row - the corruption of denoising autoencoders on categorical and entity data, and the training-side counterpart of the
+ * swapped negatives of "Assembled outfits and compatibility".  p0 = p in [0, 1]; a codae_swap carries the slot count S (io = S E)
+ * and an optional pool: a device int32 [P] of dataset rows that items may be taken from, 1 <= P < 2^31, every entry a valid row,
+ * borrowed until replaced; pool NULL = every row of the dataset: P = n_pool = n_rows, pool[j] = j.  (A training script passes its
+ * training rows, so that no validation item ever reaches a training input.)  For dataset row r (row_idx[b], or noise_rows[b] for a
+ * batch gathered by the caller - never the position in the batch), slot s and the 1-based step t:
+ *   words     (w0, w1, w2, w3) = Philox4x32-10(key = (seed & 0xffffffff, seed >> 32), counter = (s, r, t, 512)); counter word
+ *             3 = 512 keeps the stream apart from the element noises (0), dropout (1 + layer) and the slot contrast (256);
+ *             w2 and w3 are unused
+ *   hit       w0 < T, T = floor(p 2^32) formed in double and compared as 64-bit - the rule of the kinds above
+ *   source    j = ((uint64) w1 * P) >> 32, q = pool[j]
+ *   accepted  hit && q != r, and with a presence table additionally present[r][s] && present[q][s].  No redraw and no loop: a
+ *             rejected draw leaves the slot as it is; an absent slot is never noised
+ *   input     every column of slot s of the batch row is data[q][sE .. (s+1)E) instead of data[r][..]; behind that the slot
+ *             blank (a blanked element stays exactly 0), behind that the presence rule.  No arithmetic is done on the values,
+ *             so a bf16 step may gather a swapped row from the dataset's bf16 image (codae_set_dataset_image): same bits
+ *   target    the loss target and the monitors stay the clean row r; evaluation, completion and scoring never swap
+ *   replaced  for "Loss emphasis": replaced(b, c) = accepted(r, c / E, t), recomputed from the words, the pool and the presence
+ *             table - nothing is read back from the input; an accepted swap counts even when q holds the same bytes
+ * The definition depends on (seed, pool, step, presence) alone: one process and N data-parallel ranks build the same inputs.
+ * Not covered: swap combined with an element noise (one kind at a time), the mixed-variable path, redrawing after a rejection, the
+ * persistent chain kernel (as for every noise kind). */
 enum {
     CODAE_NOISE_NONE = 0,
     CODAE_NOISE_GAUSSIAN = 1,
     CODAE_NOISE_MASKING = 2,
-    CODAE_NOISE_SALT_PEPPER = 3
+    CODAE_NOISE_SALT_PEPPER = 3,
+    CODAE_NOISE_SWAP = 4
 };
 
 typedef struct {
@@ -158,11 +186,19 @@ typedef struct {
     uint64_t seed;
 } codae_noise;
 
+/* what CODAE_NOISE_SWAP needs beside codae_noise, whose layout stays: the graph key compares its bytes */
+typedef struct {
+    const int32_t* pool;   /* device [n_pool] dataset rows, or NULL = rows 0 .. n_pool - 1; borrowed */
+    int32_t n_pool;        /* P >= 1; with pool NULL: the dataset's row count */
+    int32_t n_slots;       /* S >= 1, dividing io */
+} codae_swap;
+
 /* Emphasised denoising loss (Vincent et al. 2010, section 4.3): the TRAINING loss weights corrupted and untouched elements
  * differently.  For batch row b (dataset row r = row_idx[b], or b when row_idx is NULL) and column c:
  *   blank(b,c)     the row has a mask id (mask_id or mask_to_use) and mask_table[id_b][c] == 0
  *   replaced(b,c)  the engine's input noise is MASKING or SALT_PEPPER and the element's Philox word satisfies r < T - word,
- *                  counter and T exactly as under "Input noise" above, with this step's index; GAUSSIAN replaces nothing
+ *                  counter and T exactly as under "Input noise" above, with this step's index; GAUSSIAN replaces nothing;
+ *                  SWAP: the element's slot took an accepted swap ("Swap noise")
  *   corrupted      blank or replaced
  *   w(b,c)         col_weight[c] * (corrupted ? alpha : beta), col_weight == 1 when absent; formed in fp32
  *   L              sum w (x - y)^2 * inv_n, inv_n = 1 / (rows * io) with rows = hyper->loss_scale_rows (the GLOBAL batch), or
@@ -665,6 +701,14 @@ int codae_debug_step_plan(codae_handle h, const codae_buffers* bufs, const int32
  * noised.  While noise is on the stack stays off the persistent chain kernel, which fuses the gather (codae_step_path
  * reports 0), exactly as a non-ReLU activation keeps it off. */
 int codae_set_input_noise(codae_handle h, const codae_noise* noise);
+/* The slot count and the pool of CODAE_NOISE_SWAP ("Swap noise" above) for the training steps that follow: pool [n_pool] int32 on the
+ * device, borrowed until replaced, or NULL = every row (n_pool is then the dataset's row count).  Required before
+ * codae_set_input_noise accepts CODAE_NOISE_SWAP; the setting is part of the graph key (a change re-captures).  pool NULL with
+ * n_pool == 0 and n_slots == 0 clears it (refused while SWAP is the noise kind).  CODAE_E_INVALID for n_slots < 1 or not dividing
+ * io, n_pool < 1, and an n_slots that differs from a presence table's; codae_set_input_noise returns CODAE_E_INVALID for SWAP
+ * without slots and for p outside [0, 1].  On an error nothing is launched and the previous setting stays.  A bf16 step with swap
+ * noise keeps gathering from the registered bf16 image (codae_set_dataset_image). */
+int codae_set_swap_pool(codae_handle h, const int32_t* pool, int32_t n_pool, int32_t n_slots);
 /* Loss emphasis of every training step that follows (the step forms codae_set_input_noise lists; a change re-captures the
  * graph).  NULL switches it off; alpha = beta = 1 with a NULL col_weight also means off: the engine then runs exactly the
  * launches it ran before.  CODAE_E_INVALID for a negative or non-finite alpha or beta (nothing is launched, the previous
@@ -711,14 +755,15 @@ int codae_set_optimizer(codae_handle h, const codae_optimizer* opt);
  * graph key) AND codae_eval_step.  present [n_rows][n_slots] uint8 on the device, borrowed until replaced; NULL switches it off: the
  * engine then runs exactly what it ran before, bit for bit, codae_step_path included.  CODAE_E_INVALID for n_slots outside [1, 128]
  * or not dividing io, n_rows < 1, and an n_slots that differs from the one a SLOT_COSINE criterion or a slot contrast is set with
- * (those two setters refuse a disagreement with the table the same way: whichever comes second); nothing is launched, the previous
+ * (those two setters refuse a disagreement with the table the same way: whichever comes second), or from the swap noise's slot
+ * count (codae_set_swap_pool, likewise); nothing is launched, the previous
  * setting stays.  Every row index of a batch must be < n_rows.  While a table is set codae_step_path reports 0. */
 int codae_set_slot_presence(codae_handle h, const uint8_t* present, int64_t n_rows, int32_t n_slots);
 /* A resident bf16 image of the dataset: image_bf16 [n_rows][io] bf16 on the device, image[r][c] = bf16(data[r][c]) as
  * codae_cast_f32_to_bf16 rounds it, borrowed until replaced; NULL clears the registration.  The bf16 engine's steps - training in
  * every step form, and codae_eval_step - then gather their input from the image instead of converting the fp32 rows again, whenever
- * batch->data == data, batch->io == io, io % 8 == 0 and the call applies no input noise (noise is added in fp32 before the
- * rounding); every other call, and the fp32 engine, runs exactly what it ran before.  The gathered input has the same bits either
+ * batch->data == data, batch->io == io, io % 8 == 0 and the call applies no input noise other than CODAE_NOISE_SWAP (the element
+ * noises are added in fp32 before the rounding; a swapped slot is a bf16 row of another row); every other call, and the fp32 engine, runs exactly what it ran before.  The gathered input has the same bits either
  * way, so no result changes; the loss keeps reading the fp32 target rows.  Every row index of such a batch must be < n_rows.  A
  * caller that rewrites the dataset in place registers the image again (after casting it again): the engine cannot see the
  * change.  The registration is part of the graph key.  CODAE_NO_DATASET_IMAGE (read at codae_create) keeps the fp32 gather.
@@ -842,6 +887,23 @@ int codae_slot_contrast_prepare_present(const float* data, int32_t io, const cod
 int codae_slot_contrast_fwd_bwd_present(const codae_batch* batch, const codae_noise* noise, int32_t step, const codae_emphasis* emphasis,
                                         const codae_slot_contrast* contrast, const float* y, void* dy, int32_t dy_bf16, int64_t dy_ld,
                                         float scale, float* colsum_part, double* parts, const uint8_t* present, int32_t n_slots, void* stream);
+/* The same primitives under swap noise ("Swap noise"; the launchers the engine uses).  codae_corrupt_batch_swap: arguments as
+ * codae_corrupt_batch_present, noise->kind == CODAE_NOISE_SWAP, plus `dataset` - the matrix [n_rows][io] the swapped slots are read
+ * from (NULL: batch->data; required with noise_rows, where batch->data is a batch that has already been gathered) - and `swap`;
+ * present (may be NULL) has swap->n_slots slots.  image != 0: `batch->data` and `dataset` are bf16 images of the rows and out is
+ * bf16 (the image gather; io % 8 == 0, no noise_rows).  codae_emph_loss_swap / codae_recon_loss_fwd_bwd_swap: arguments as their
+ * _present namesakes with `swap` in front of the presence table; swap NULL is exactly the namesake.  The namesakes themselves stay
+ * callable with unchanged behaviour (they refuse CODAE_NOISE_SWAP: it needs the descriptor). */
+int codae_corrupt_batch_swap(const codae_batch* batch, const codae_noise* noise, int32_t step, const int32_t* noise_rows, const void* dataset,
+                             const codae_swap* swap, void* out, int32_t out_bf16, int64_t out_ld, const uint8_t* present, int32_t image,
+                             void* stream);
+int codae_emph_loss_swap(const codae_batch* batch, const codae_noise* noise, int32_t step, const codae_emphasis* emphasis, const float* y,
+                         void* dy, int32_t dy_bf16, int64_t dy_ld, float inv_n, float* colsum_part, double* parts, const codae_swap* swap,
+                         const uint8_t* present, int32_t n_slots, void* stream);
+int codae_recon_loss_fwd_bwd_swap(const codae_batch* batch, const codae_noise* noise, int32_t step, const codae_emphasis* emphasis,
+                                  const codae_recon_loss* loss, const float* y, void* dy, int32_t dy_bf16, int64_t dy_ld, float inv_n,
+                                  float* colsum_part, double* parts, const codae_swap* swap, const uint8_t* present, int32_t n_slots,
+                                  void* stream);
 /* The two hidden-dropout kernels on their own (the launchers the engine uses; "Hidden dropout" above has the definition): in
  * place on rows < B and columns < width of a [B][ld] matrix, fp32 or (bf16 != 0) bf16; pad columns and pad rows are never
  * written.  16-byte accesses where the base address, ld and width allow (bf16 x 8, fp32 x 4), element accesses otherwise.

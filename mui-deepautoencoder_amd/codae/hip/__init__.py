@@ -21,7 +21,7 @@ S_GRAD_SQ_SLOTS, S_N_SLOTS, S_ADAM_STEP, S_COUNT = 8, 64, 72, 80
 # CODAE_ACT_* of include/codae_hip.h: the activation after a Linear (codae.model.activation maps torch modules to these)
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_RELU6, ACT_ELU, ACT_SOFTPLUS, ACT_HARDSIGMOID = 0, 1, 2, 3, 4, 5, 6
 # CODAE_NOISE_* of include/codae_hip.h: the input noise of the training steps (codae.tool.InputNoise builds the struct)
-NOISE_NONE, NOISE_GAUSSIAN, NOISE_MASKING, NOISE_SALT_PEPPER = 0, 1, 2, 3
+NOISE_NONE, NOISE_GAUSSIAN, NOISE_MASKING, NOISE_SALT_PEPPER, NOISE_SWAP = 0, 1, 2, 3, 4
 # CODAE_LOSS_* of include/codae_hip.h: the training criterion (codae.tool.ReconstructionLoss builds the struct)
 LOSS_MSE, LOSS_L1, LOSS_SMOOTH_L1, LOSS_HUBER, LOSS_SLOT_COSINE = 0, 1, 2, 3, 4
 # CODAE_OPT_* / CODAE_SCHED_* of include/codae_hip.h: the update's optimizer and schedule (codae.tool.Optimizer builds the struct)
@@ -79,6 +79,11 @@ class Hyper(C.Structure):
 
 class Noise(C.Structure):
     _fields_ = [("kind", C.c_int32), ("p0", C.c_float), ("p1", C.c_float), ("p2", C.c_float), ("seed", C.c_uint64)]
+
+
+# codae_swap: the pool and the slot count of swap noise: a pointer and two 4-byte fields, 16 bytes
+class Swap(C.Structure):
+    _fields_ = [("pool", C.c_void_p), ("n_pool", C.c_int32), ("n_slots", C.c_int32)]
 
 
 class Emphasis(C.Structure):
@@ -146,6 +151,12 @@ PROTOTYPES = {
     "codae_train_step": (C.c_int, [_P, C.POINTER(Buffers), C.POINTER(Batch), C.POINTER(Hyper), _P]),
     "codae_train_step_graph": (C.c_int, [_P, C.POINTER(Buffers), C.POINTER(Batch), C.POINTER(Hyper), _P]),
     "codae_set_input_noise": (C.c_int, [_P, C.POINTER(Noise)]),
+    "codae_set_swap_pool": (C.c_int, [_P, _P, _I32, _I32]),
+    "codae_corrupt_batch_swap": (C.c_int, [C.POINTER(Batch), C.POINTER(Noise), _I32, _P, _P, C.POINTER(Swap), _P, _I32, _I64, _P, _I32, _P]),
+    "codae_emph_loss_swap": (C.c_int, [C.POINTER(Batch), C.POINTER(Noise), _I32, C.POINTER(Emphasis), _P, _P, _I32, _I64, _F, _P, _P,
+                                       C.POINTER(Swap), _P, _I32, _P]),
+    "codae_recon_loss_fwd_bwd_swap": (C.c_int, [C.POINTER(Batch), C.POINTER(Noise), _I32, C.POINTER(Emphasis), C.POINTER(ReconLoss), _P, _P,
+                                                _I32, _I64, _F, _P, _P, C.POINTER(Swap), _P, _I32, _P]),
     "codae_set_loss_emphasis": (C.c_int, [_P, C.POINTER(Emphasis)]),
     "codae_set_recon_loss": (C.c_int, [_P, C.POINTER(ReconLoss)]),
     "codae_set_hidden_dropout": (C.c_int, [_P, C.POINTER(Dropout)]),

@@ -259,14 +259,29 @@ class DaeEngine:
         return Hyper(lr, weight_decay, betas[0], betas[1], eps, clip if clip else 0.0,
                      self.step_count + 1 if step is None else step, float(global_rows))
 
-    def set_input_noise(self, noise):
+    def set_input_noise(self, noise, n_slots=None, n_rows=None):
         """noise: a codae.tool.InputNoise, or None to switch it off.  Every training step form that follows applies it to
         the gathered input before the slot mask (the loss target stays clean; eval steps are never noised); with
-        graph=True the next step re-captures.  While it is on, step_path() is 'layers'."""
+        graph=True the next step re-captures.  While it is on, step_path() is 'layers'.
+        Swap noise takes the dataset's slot count and row count (n_slots, n_rows); its pool is checked against n_rows and
+        moved to the device once, here; a bf16 engine keeps gathering from the registered dataset image."""
         if noise is not None and not hasattr(noise, "as_struct"):
             raise HipError("set_input_noise: expected a codae.tool.InputNoise or None, got %r" % (noise,))
         st = None if noise is None else noise.as_struct()
+        pool = None
+        if noise is not None and getattr(noise, "kind", None) == "swap":
+            # the slots and the pool first: the library refuses the kind without them (a refusal below leaves them set, unused)
+            if not n_slots or not n_rows:
+                raise HipError("set_input_noise: swap noise needs n_slots and n_rows (the dataset's slot count and rows)")
+            rows = noise.pool_rows(int(n_rows))
+            with torch.cuda.device(self.device):
+                pool = None if rows is None else torch.from_numpy(rows.astype("int32")).to(self.device).contiguous()
+            check(self._lib.codae_set_swap_pool(self._h, ptr(pool), int(n_rows) if pool is None else int(pool.numel()), int(n_slots)))
         check(self._lib.codae_set_input_noise(self._h, None if st is None else C.byref(st)))
+        swap = noise is not None and getattr(noise, "kind", None) == "swap"
+        if not swap and getattr(self, "_swap_set", False):
+            check(self._lib.codae_set_swap_pool(self._h, None, 0, 0))      # (the borrowed pool goes with the kind)
+        self._swap_pool, self._swap_set = pool, swap
         self.input_noise = noise
 
     def set_loss_emphasis(self, emphasis, n_slots=None):

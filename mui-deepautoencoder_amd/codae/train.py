@@ -421,8 +421,8 @@ class HipEmbeddingTrainer:
         activation: what follows every hidden Linear, as the model classes take it (a factory called as activation(True),
         e.g. torch.nn.ELU); None = ReLU.  Every step form (fused, graph replay, data parallel) runs it.
         n_slots: categories per row (complete() only; default: read off the mask table).
-        input_noise: a codae.tool.InputNoise (Gaussian / masking / salt-and-pepper) applied to the gathered training input
-        before the slot mask, in every step form (fused, graph replay, torch.distributed, sharded, native data parallel);
+        input_noise: a codae.tool.InputNoise (Gaussian / masking / salt-and-pepper, or swap: a slot replaced by another row's item
+        of that slot, drawn from the noise's pool) applied to the gathered training input before the slot mask, in every step form (fused, graph replay, torch.distributed, sharded, native data parallel);
         keyed by the dataset row and the optimizer step, so N ranks noise their shards exactly as one process noises the
         global batch.  eval_batch and complete never apply it.  None = off.
         loss_emphasis: a codae.tool.LossEmphasis: the training loss weights corrupted elements (the blanked slot, elements the
@@ -466,7 +466,7 @@ class HipEmbeddingTrainer:
         fit_host_threads()      # the loop that feeds this trainer must not get its container CPU-throttled (codae/hostcpu.py)
         self.device = torch.device(device)
         self.engine = DaeEngine(schedule, max_batch, precision, self.device, activation=activation)
-        if input_noise is not None:
+        if input_noise is not None and getattr(input_noise, "kind", None) != "swap":
             self.engine.set_input_noise(input_noise)
         self.data = data.to(device=self.device, dtype=torch.float32).contiguous()
         self.dataset_image = bool(dataset_image) and not os.environ.get("CODAE_NO_DATASET_IMAGE")
@@ -475,6 +475,8 @@ class HipEmbeddingTrainer:
         self.mask_to_use = None if mask_to_use_i32 is None else mask_to_use_i32.to(self.device).contiguous()
         self.lr, self.weight_decay, self.clip = lr, weight_decay, clip
         self.n_slots = n_slots
+        if input_noise is not None and getattr(input_noise, "kind", None) == "swap":
+            self.set_input_noise(input_noise)      # (needs the slots and the dataset's rows)
         if loss_emphasis is not None:
             self.set_loss_emphasis(loss_emphasis)
         if hidden_dropout is not None:
@@ -508,6 +510,17 @@ class HipEmbeddingTrainer:
         from .hip import PREC_BF16
         if self.dataset_image and self.engine.precision == PREC_BF16:
             self.engine.set_dataset_image(self.data)
+
+    def set_input_noise(self, noise):
+        """DaeEngine.set_input_noise; swap noise gets the trainer's number of slots (n_slots, else read off the mask table) and the
+        resident dataset's row count, against which its pool is checked.  The presence table it honours is the trainer's own."""
+        if noise is not None and getattr(noise, "kind", None) == "swap":
+            if not self.n_slots and self.mask_table is None:
+                raise HipError("swap noise: the trainer has neither n_slots nor a mask table to read the slots from; "
+                               "construct it with n_slots")
+            self.engine.set_input_noise(noise, n_slots=self._slots()[0], n_rows=int(self.data.shape[0]))
+        else:
+            self.engine.set_input_noise(noise)
 
     def set_loss_emphasis(self, emphasis):
         """DaeEngine.set_loss_emphasis with the trainer's number of slots (n_slots, else read off the mask table) for a

@@ -1,6 +1,7 @@
 // Shared declarations for libcodae_hip.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <type_traits>
@@ -205,6 +206,38 @@ __device__ __forceinline__ uint32_t present_bits(const PresArgs& p, int64_t row,
     return bits;
 }
 int check_presence(const uint8_t* present, int n_slots, int io, const char* who);
+
+// Swap noise ("Swap noise", include/codae_hip.h): whether slot `slot` of DATASET row `row` takes another row's item at `step`, and
+// which row's.  One Philox call per (row, slot), counter (slot, row, step, 512); pres (null: none) is the presence table [.][S].
+struct SwapArgs {
+    const int32_t* pool;   // device [P], or null = the row itself
+    uint32_t P;
+    int S, E;              // slots per row, columns per slot
+    uint64_t thresh;       // T = floor(p 2^32)
+    uint32_t key0, key1;
+    const uint8_t* pres;
+};
+constexpr uint32_t SWAP_STREAM = 512u;
+// the source row q of an accepted swap, or -1: not hit, q == row, or a side absent
+__device__ __forceinline__ int64_t swap_source(const SwapArgs& a, uint32_t row, int slot, uint32_t step) {
+    const uint4 r = philox4x32_10((uint32_t)slot, row, step, SWAP_STREAM, a.key0, a.key1);
+    if (!((uint64_t)r.x < a.thresh)) return -1;
+    const uint32_t j = (uint32_t)(((uint64_t)r.y * a.P) >> 32);
+    const uint32_t q = a.pool ? (uint32_t)a.pool[j] : j;
+    if (q == row) return -1;
+    if (a.pres != nullptr && (a.pres[(int64_t)row * a.S + slot] == 0 || a.pres[(int64_t)q * a.S + slot] == 0)) return -1;
+    return (int64_t)q;
+}
+// host side: the kernel argument of a validated (noise, swap) pair; check_swap: CODAE_E_INVALID with the offending argument named
+int check_swap(const codae_swap* swap, int io, const uint8_t* present, int pres_slots, const char* who);
+inline SwapArgs swap_args(const codae_noise* n, const codae_swap* sw, int io, const uint8_t* present) {
+    SwapArgs a{};
+    a.pool = sw->pool; a.P = (uint32_t)sw->n_pool; a.S = sw->n_slots; a.E = io / sw->n_slots;
+    a.thresh = (uint64_t)floor((double)n->p0 * 4294967296.0);
+    a.key0 = (uint32_t)(n->seed & 0xffffffffu); a.key1 = (uint32_t)(n->seed >> 32);
+    a.pres = present;
+    return a;
+}
 
 static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
@@ -452,13 +485,16 @@ int launch_chain_step(const ChainArgs& a, hipStream_t s);
 int check_noise(const codae_noise* noise);
 int launch_gather_noise(const codae_batch* b, const codae_noise* noise, int32_t step, const double* step_dev, void* out,
                         int out_bf16, hipStream_t s, int64_t out_ld = 0, const int32_t* noise_rows = nullptr, double* zero_norm = nullptr,
-                        const uint8_t* present = nullptr, int n_slots = 0);
+                        const uint8_t* present = nullptr, int n_slots = 0, const codae_swap* swap = nullptr, const float* swap_data = nullptr);
+// (swap: required by CODAE_NOISE_SWAP; swap_data: the matrix the swapped slots are read from, null = b->data)
 // The plain gather (bf16 out, no noise) from the dataset's bf16 image instead of its fp32 rows (codae_set_dataset_image): the same
 // bits as launch_gather_noise(b, nullptr, .., out, 1, ...) on the data the image was cast from.  gather_image_takes: the shape / alignment
 // conditions of its 16-byte accesses (io and out_ld multiples of 8, image and out 16-byte, the mask table 8-byte aligned).
 bool gather_image_takes(const codae_batch* b, const void* image, const void* out, int64_t out_ld);
+// noise (null, NONE or SWAP) with step / step_dev / swap as launch_gather_noise: the swapped slots come from the image too.
 int launch_gather_image(const codae_batch* b, const bf16_t* image, bf16_t* out, hipStream_t s, int64_t out_ld = 0, double* zero_norm = nullptr,
-                        const uint8_t* present = nullptr, int n_slots = 0);
+                        const uint8_t* present = nullptr, int n_slots = 0, const codae_noise* noise = nullptr, int32_t step = 0,
+                        const double* step_dev = nullptr, const codae_swap* swap = nullptr);
 int launch_noise_box_muller(const uint32_t* ra, const uint32_t* rb, float* rho, float* c, float* sn, int64_t n, hipStream_t s);
 int launch_cast_bf16(const float* src, bf16_t* dst, int64_t n, hipStream_t s);
 int launch_corrupt(const float* x, const float* mask, float* out, int64_t n, hipStream_t s);
@@ -486,6 +522,7 @@ struct LossLaunch {
     const codae_emphasis* emph; const uint8_t* present; int n_slots;
     const float* y; void* dy; int dy_bf16; int64_t dy_ld; float scale /* inv_n, or the contrast's scale */;
     float* colsum_part; double* parts;
+    const codae_swap* swap;      // with noise->kind == CODAE_NOISE_SWAP: its slots and pool
 };
 inline int64_t loss_dy_ld(const LossLaunch& ll) { return ll.dy_ld > 0 ? ll.dy_ld : (ll.batch ? ll.batch->io : 0); }
 // the argument checks every loss launcher makes, the error texts prefixed with `who`; needs_dy: dy must be there

@@ -43,18 +43,18 @@ __global__ __launch_bounds__(NT) void mse_loss_kernel(const float* __restrict__ 
 // ---- emphasised denoising loss (codae_emphasis, include/codae_hip.h; Vincent et al. 2010, section 4.3) ----------------------
 // mse_loss_kernel's block shape with a weight per element (WeightArgs and EmphTerm, loss_sweep.h):
 //   parts[block] = { sum w (x-y)^2, sum (x-y)^2, sum (1-fmask)(x-y)^2 }: the metric sums stay unweighted
-template <bool VEC, bool DY_BF16, bool PRES>
+template <bool VEC, bool DY_BF16, bool PRES, bool SWAP = false>
 __global__ __launch_bounds__(NT) void emph_loss_kernel(const float* __restrict__ data, const int32_t* __restrict__ row_idx,
                                                        const int32_t* __restrict__ mask_id, const uint8_t* __restrict__ table,
                                                        int B, int io, const float* __restrict__ y, void* __restrict__ dy,
                                                        float inv_n, float* __restrict__ colsum_part, double* __restrict__ parts,
                                                        const int32_t* __restrict__ mask_to_use, int nb_run, int run, int64_t dy_ld,
-                                                       WeightArgs wa, PresArgs pa) {
+                                                       WeightArgsOf<SWAP> wa, PresArgs pa) {
     __shared__ float red[4];
     const bool masked = (mask_id != nullptr) || (mask_to_use != nullptr);
     const BatchArgs ba{data, row_idx, mask_id, table, mask_to_use, nb_run, run, B, io};
     EmphTerm term(wa, inv_n);
-    loss_sweep<VEC, DY_BF16, PRES>(ba, y, dy, dy_ld, colsum_part, pa, wa, term);
+    loss_sweep<VEC, DY_BF16, PRES, SWAP>(ba, y, dy, dy_ld, colsum_part, pa, wa, term);
     const float bwsq = block_sum(term.wsq, red);
     const float bsq = block_sum(term.sq, red);
     const float bsqp = block_sum(term.sqp, red);
@@ -375,6 +375,10 @@ int check_loss_launch(const char* who, const LossLaunch& ll, bool needs_dy) {
     if (rc) return rc;
     rc = check_noise(ll.noise);
     if (rc) return rc;
+    if (ll.noise != nullptr && ll.noise->kind == CODAE_NOISE_SWAP) {
+        rc = check_swap(ll.swap, b->io, ll.present, ll.n_slots, who);
+        if (rc) return rc;
+    }
     const bool masked = b->mask_id || b->mask_to_use;
     CODAE_REQUIRE(!masked || b->mask_table, "%s: mask ids without mask_table", who);
     if (!needs_dy) return CODAE_OK;      // (a launch that may run for its sums alone takes dy's stride and the run as they come)
@@ -414,13 +418,15 @@ int launch_emph_loss(const LossLaunch& ll, hipStream_t s) {
     if (rc) return rc;
     const codae_batch* b = ll.batch;
     const int64_t dy_ld = loss_dy_ld(ll);
-    const WeightArgs wa = weight_args(ll, true);
+    const SwapWeightArgs wa = weight_args(ll, true);
     const bool vec = (b->io % 4 == 0) && (dy_ld % 4 == 0) && loss_inputs_a16(ll) && a16(ll.dy) && (!wa.col_weight || a16(wa.col_weight));
     const dim3 grid(mse_loss_colsum_rows(b->B));
     loss_dispatch(vec, ll.dy_bf16, ll.present != nullptr, [&](auto V, auto O, auto P) {
-        hipLaunchKernelGGL((emph_loss_kernel<decltype(V)::value, decltype(O)::value, decltype(P)::value>), grid, dim3(NT), 0, s, b->data,
-                           b->row_idx, b->mask_id, b->mask_table, b->B, b->io, ll.y, ll.dy, ll.scale, ll.colsum_part, ll.parts, b->mask_to_use, b->nb_run,
-                           b->run, dy_ld, wa, pres_args(ll));
+        swap_dispatch(wa, [&](auto W) {
+            hipLaunchKernelGGL((emph_loss_kernel<decltype(V)::value, decltype(O)::value, decltype(P)::value, decltype(W)::value>), grid, dim3(NT), 0,
+                               s, b->data, b->row_idx, b->mask_id, b->mask_table, b->B, b->io, ll.y, ll.dy, ll.scale, ll.colsum_part, ll.parts,
+                               b->mask_to_use, b->nb_run, b->run, dy_ld, weight_args_of<decltype(W)::value>(wa), pres_args(ll));
+        });
     });
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;

@@ -104,6 +104,7 @@ struct codae_engine {
     struct ImageCfg { const float* data; const void* image; int64_t n_rows; int32_t io; int32_t reserved; };
     struct TrainCfg {
         codae_noise noise;               // input noise (codae_set_input_noise); kind NONE = off
+        codae_swap swap;                 // slots and pool of CODAE_NOISE_SWAP (codae_set_swap_pool); n_slots 0 = not set
         codae_emphasis emph;             // loss emphasis (codae_set_loss_emphasis), meaningful while emph_on
         int32_t emph_on, reserved;       // (stored: {alpha 0, beta 0} is a legal "on")
         codae_recon_loss recon;          // training criterion (codae_set_recon_loss); kind MSE (all zero) = off
@@ -1270,7 +1271,8 @@ static int run_standalone_loss(codae_handle h, const codae_buffers* b, const cod
     codae_emphasis unit{};
     unit.alpha = 1.f; unit.beta = 1.f;
     LossLaunch ll{batch, &h->tc.noise, hyper->step, step_dev(h, b), h->tc.emph_on ? &h->tc.emph : nullptr, h->tc.pres.table, h->tc.pres.n_slots,
-                  y, dact_ptr(h, b, L - 1), h->prec == CODAE_PREC_BF16, h->out_ld[L - 1], (float)inv_n, part_ptr(h, b, L - 1), loss_parts_ptr(h, b)};
+                  y, dact_ptr(h, b, L - 1), h->prec == CODAE_PREC_BF16, h->out_ld[L - 1], (float)inv_n, part_ptr(h, b, L - 1), loss_parts_ptr(h, b),
+                  &h->tc.swap};
     const bool weighted = h->recon_on() || h->tc.emph_on || ll.present != nullptr;      // (the kernels that leave three sums per block)
     int rc;
     {
@@ -1291,10 +1293,13 @@ static int run_standalone_loss(codae_handle h, const codae_buffers* b, const cod
     return rc ? rc : run_slot_contrast(h, b, hyper, ll, s);
 }
 
-// The un-noised gather of a bf16 step reads the registered bf16 image instead of the fp32 rows: only for the very dataset the image
-// was registered with, and only where the image kernel's 16-byte accesses are legal; everything else runs what it always ran.
-static bool gathers_from_image(codae_handle h, const codae_batch* batch, const void* out) {
+// The gather of a bf16 step reads the registered bf16 image instead of the fp32 rows: only for the very dataset the image
+// was registered with, only where the image kernel's 16-byte accesses are legal, and only when no arithmetic is done on the values -
+// no noise (noise_kind: the kind this call applies), or swap noise, whose swapped slot is a bf16 row of another row; everything
+// else runs what it always ran.
+static bool gathers_from_image(codae_handle h, const codae_batch* batch, const void* out, int noise_kind) {
     const codae_engine::ImageCfg& im = h->tc.img;
+    if (noise_kind != CODAE_NOISE_NONE && noise_kind != CODAE_NOISE_SWAP) return false;
     return h->prec == CODAE_PREC_BF16 && !h->cfg.no_dataset_image && im.image != nullptr && batch->data == im.data && batch->io == im.io &&
            gather_image_takes(batch, im.image, out, h->in_ld[0]);
 }
@@ -1325,12 +1330,14 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
         ProfScope prof(h, CODAE_K_GATHER, s);
         double* zero_norm = fold_finish ? b->scalars : nullptr;
         const bool noised = hyper != nullptr && h->tc.noise.kind != CODAE_NOISE_NONE;      // training input only; the loss below reads the clean row
-        if (!noised && gathers_from_image(h, batch, act_ptr(h, b, 0)))
+        const codae_noise* noise = noised ? &h->tc.noise : nullptr;
+        const int32_t nstep = noised ? hyper->step : 0;
+        if (gathers_from_image(h, batch, act_ptr(h, b, 0), noised ? h->tc.noise.kind : CODAE_NOISE_NONE))
             rc = launch_gather_image(batch, reinterpret_cast<const bf16_t*>(h->tc.img.image), reinterpret_cast<bf16_t*>(act_ptr(h, b, 0)), s,
-                                     h->in_ld[0], zero_norm, pres, pres_slots);
+                                     h->in_ld[0], zero_norm, pres, pres_slots, noise, nstep, step_dev(h, b), &h->tc.swap);
         else
-            rc = launch_gather_noise(batch, noised ? &h->tc.noise : nullptr, noised ? hyper->step : 0, step_dev(h, b),
-                                     act_ptr(h, b, 0), bf, s, h->in_ld[0], nullptr, zero_norm, pres, pres_slots);
+            rc = launch_gather_noise(batch, noise, nstep, step_dev(h, b), act_ptr(h, b, 0), bf, s, h->in_ld[0], nullptr, zero_norm, pres,
+                                     pres_slots, &h->tc.swap);
     }
     if (rc) return rc;
     rc = zero_pad_rows(h, act_ptr(h, b, 0), B, rows, h->in_ld[0], s);
@@ -1402,12 +1409,30 @@ int codae_set_input_noise(codae_handle h, const codae_noise* noise) {
     CODAE_REQUIRE(h != nullptr, "codae_set_input_noise: null handle");
     int rc = check_noise(noise);
     if (rc) return rc;
+    if (noise != nullptr && noise->kind == CODAE_NOISE_SWAP) {
+        rc = check_swap(&h->tc.swap, h->in[0], h->tc.pres.table, h->tc.pres.n_slots, "codae_set_input_noise");
+        if (rc) return rc;
+    }
     codae_noise n{};                     // (built field by field: the graph key compares bytes, padding included)
     if (noise != nullptr && noise->kind != CODAE_NOISE_NONE) {
         n.kind = noise->kind; n.p0 = noise->p0; n.seed = noise->seed;
         if (noise->kind == CODAE_NOISE_SALT_PEPPER) { n.p1 = noise->p1; n.p2 = noise->p2; }
     }
     h->tc.noise = n;
+    return CODAE_OK;
+}
+
+int codae_set_swap_pool(codae_handle h, const int32_t* pool, int32_t n_pool, int32_t n_slots) {
+    CODAE_REQUIRE(h != nullptr, "codae_set_swap_pool: null handle");
+    codae_swap sw{};                     // (built field by field: the graph key compares bytes)
+    if (pool == nullptr && n_pool == 0 && n_slots == 0) {
+        CODAE_REQUIRE(h->tc.noise.kind != CODAE_NOISE_SWAP, "codae_set_swap_pool: swap noise is on: switch it off before clearing its slots");
+    } else {
+        sw.pool = pool; sw.n_pool = n_pool; sw.n_slots = n_slots;
+        const int rc = check_swap(&sw, h->in[0], h->tc.pres.table, h->tc.pres.n_slots, "codae_set_swap_pool");
+        if (rc) return rc;
+    }
+    h->tc.swap = sw;
     return CODAE_OK;
 }
 
@@ -1473,6 +1498,8 @@ int codae_set_slot_presence(codae_handle h, const uint8_t* present, int64_t n_ro
         CODAE_REQUIRE(!h->contrast_on() || (h->tc.contrast.n_slots == n_slots && (int64_t)h->tc.contrast.n_rows <= n_rows),
                       "codae_set_slot_presence: %d slots / %lld rows do not fit the slot contrast (%d slots, %d rows)", n_slots,
                       (long long)n_rows, h->tc.contrast.n_slots, h->tc.contrast.n_rows);
+        CODAE_REQUIRE(h->tc.swap.n_slots == 0 || h->tc.swap.n_slots == n_slots, "codae_set_slot_presence: n_slots %d differs from the swap noise's %d",
+                      n_slots, h->tc.swap.n_slots);
         p.table = present; p.n_rows = n_rows; p.n_slots = n_slots;
     }
     h->tc.pres = p;

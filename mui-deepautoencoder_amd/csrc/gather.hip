@@ -29,15 +29,26 @@ struct NoiseArgs {
     float p0, p1, p2;          // sigma; lo, hi
     double* zero_norm;         // see zero_norm_scalars
 };
+// swap noise moves whole slots and does no arithmetic: the words' key and threshold travel in sw; sdata = the matrix the swapped
+// slots are read from (the batch's own data unless the caller gathered the batch)
+struct SwapGather {
+    SwapArgs sw; const float* sdata;
+};
 // the kernel argument of one noise kind; the plain gather (CODAE_NOISE_NONE) keeps the argument block it always had
 template <int KIND>
 struct NoiseArgsOf : NoiseArgs {
-    explicit NoiseArgsOf(const NoiseArgs& a) : NoiseArgs(a) {}
+    NoiseArgsOf(const NoiseArgs& a, const SwapGather&) : NoiseArgs(a) {}
 };
 template <>
 struct NoiseArgsOf<CODAE_NOISE_NONE> {
     double* zero_norm;
-    explicit NoiseArgsOf(const NoiseArgs& a) : zero_norm(a.zero_norm) {}
+    NoiseArgsOf(const NoiseArgs& a, const SwapGather&) : zero_norm(a.zero_norm) {}
+};
+template <>
+struct NoiseArgsOf<CODAE_NOISE_SWAP> {
+    uint32_t step; const double* step_dev; const int32_t* rows; double* zero_norm;
+    SwapArgs sw; const float* sdata;
+    NoiseArgsOf(const NoiseArgs& a, const SwapGather& g) : step(a.step), step_dev(a.step_dev), rows(a.rows), zero_norm(a.zero_norm), sw(g.sw), sdata(g.sdata) {}
 };
 
 // Box-Muller pieces from one pair of words.  u1 in (0, 1] and 2 u2 in [0, 2) are exact in fp32; logf keeps its relative accuracy
@@ -125,6 +136,35 @@ __device__ __forceinline__ uint32_t load_noised(float* v, const float* __restric
     }
 }
 
+// the same columns of batch row b under swap noise: each column comes from the row its slot's draw accepted (sdata[q]), else from
+// `src`.  A group inside one slot - every group when E % W == 0 - is one Philox call and the vector load of one row; a group that
+// straddles slots (E = 6, E = 12) forms a draw per slot it touches and loads by column.  Returns the noise row.
+template <int W>
+__device__ __forceinline__ uint32_t load_swapped(float* v, const float* __restrict__ src, int c, int b, int64_t src_row, int io,
+                                                 uint32_t step, const NoiseArgsOf<CODAE_NOISE_SWAP>& na) {
+    const uint32_t nrow = na.rows ? (uint32_t)na.rows[b] : (uint32_t)src_row;
+    const int E = na.sw.E;
+    const int s0 = c / E, rem = c - s0 * E;
+    if (W == 1 || rem + W <= E) {
+        const int64_t q = swap_source(na.sw, nrow, s0, step);
+        load_cols<W>(v, q >= 0 ? na.sdata + q * io + c : src);
+    } else {
+        const float* __restrict__ from = src;
+        int s_at = -1;
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+            const int sk = s0 + (rem + k) / E;
+            if (sk != s_at) {
+                const int64_t q = swap_source(na.sw, nrow, sk, step);
+                from = q >= 0 ? na.sdata + q * io + c : src;
+                s_at = sk;
+            }
+            v[k] = from[k];
+        }
+    }
+    return nrow;
+}
+
 // the slot mask: v[k] survives where byte k of the mask row is not zero (the W bytes in one load)
 template <int W>
 __device__ __forceinline__ void mask_cols(float* v, const uint8_t* __restrict__ mrow) {
@@ -188,7 +228,8 @@ __global__ __launch_bounds__(NT) void gather_corrupt_kernel(const float* __restr
         const float* src = data + src_row * io + c;
         int64_t pres_row = src_row;
         float v[W];
-        if constexpr (NOISE) pres_row = (int64_t)load_noised<W, KIND>(v, src, c, b, src_row, step, na);
+        if constexpr (KIND == CODAE_NOISE_SWAP) pres_row = (int64_t)load_swapped<W>(v, src, c, b, src_row, io, step, na);
+        else if constexpr (NOISE) pres_row = (int64_t)load_noised<W, KIND>(v, src, c, b, src_row, step, na);
         else load_cols<W>(v, src);
         if (masked) {
             const int id = mask_id ? mask_id[b] : mask_to_use[src_row * nb_run + run];
@@ -209,16 +250,31 @@ __device__ __forceinline__ uint32_t keep_pair(uint32_t m2) {
 // either way.  Per thread 8 columns: the 8 mask bytes first - a group they blank altogether (the corrupted slot: a third of a
 // C3 row) is stored as zeros and never loaded -, else ONE 16-B load, the masked and absent halves cleared by an AND on the
 // packed pairs (a masked NaN or -0 comes out +0, as the select on the fp32 value leaves it), one 16-B store.
-template <bool PRES>
+// SWAP (swap noise): a kept group reads the image row its slot's draw accepted - the bits of the fp32 route, which rounds the same
+// fp32 row -; the draw is formed behind the blank test, so a wholly blanked group still costs neither a word nor a load.  A group
+// that straddles slots (E % 8 != 0) loads by column.  The un-swapped instantiations keep their argument block and their code.
+template <bool SWAP>
+struct ImageHead {
+    double* zero_norm;
+};
+template <>
+struct ImageHead<true> {
+    double* zero_norm;
+    uint32_t step; const double* step_dev;
+    SwapArgs sw;
+};
+template <bool PRES, bool SWAP>
 __global__ __launch_bounds__(NT) void gather_corrupt_image_kernel(const bf16_t* __restrict__ image,
                                                                   const int32_t* __restrict__ row_idx,
                                                                   const int32_t* __restrict__ mask_id,
                                                                   const uint8_t* __restrict__ table, int B, int io,
                                                                   bf16_t* __restrict__ out,
                                                                   const int32_t* __restrict__ mask_to_use, int nb_run,
-                                                                  int run, int64_t out_ld, double* zero_norm, PresArgs pa) {
-    zero_norm_scalars(zero_norm);
+                                                                  int run, int64_t out_ld, ImageHead<SWAP> hd, PresArgs pa) {
+    zero_norm_scalars(hd.zero_norm);
     const bool masked = (mask_id != nullptr) || (mask_to_use != nullptr);
+    uint32_t step = 0u;
+    if constexpr (SWAP) step = hd.step_dev ? (uint32_t)*hd.step_dev : hd.step;
     const int cols = io / 8;
     const int64_t total = (int64_t)B * cols;
     for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < total; e += (int64_t)gridDim.x * NT) {
@@ -242,8 +298,34 @@ __global__ __launch_bounds__(NT) void gather_corrupt_image_kernel(const bf16_t* 
         }
         uint4 o = make_uint4(0u, 0u, 0u, 0u);
         if ((keep.x | keep.y | keep.z | keep.w) != 0u) {
-            const uint4 x = *reinterpret_cast<const uint4*>(image + src_row * io + c);
-            o = make_uint4(x.x & keep.x, x.y & keep.y, x.z & keep.z, x.w & keep.w);
+            if constexpr (SWAP) {
+                const int E = hd.sw.E;
+                const int s0 = c / E, rem = c - s0 * E;
+                uint4 x;
+                if (rem + 8 <= E) {
+                    const int64_t q = swap_source(hd.sw, (uint32_t)src_row, s0, step);
+                    x = *reinterpret_cast<const uint4*>(image + (q >= 0 ? q : src_row) * io + c);
+                } else {
+                    const bf16_t* __restrict__ from = image + src_row * io + c;
+                    int s_at = -1;
+                    uint32_t h[8];
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) {
+                        const int sk = s0 + (rem + k) / E;
+                        if (sk != s_at) {
+                            const int64_t q = swap_source(hd.sw, (uint32_t)src_row, sk, step);
+                            from = image + (q >= 0 ? q : src_row) * io + c;
+                            s_at = sk;
+                        }
+                        h[k] = from[k];
+                    }
+                    x = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
+                }
+                o = make_uint4(x.x & keep.x, x.y & keep.y, x.z & keep.z, x.w & keep.w);
+            } else {
+                const uint4 x = *reinterpret_cast<const uint4*>(image + src_row * io + c);
+                o = make_uint4(x.x & keep.x, x.y & keep.y, x.z & keep.z, x.w & keep.w);
+            }
         }
         *reinterpret_cast<uint4*>(out + (int64_t)b * out_ld + c) = o;
     }
@@ -318,6 +400,7 @@ void gather_dispatch(int width, bool out_bf16, int kind, bool pres, F&& f) {
         if (kind == CODAE_NOISE_GAUSSIAN) with_pres(W, O, std::integral_constant<int, CODAE_NOISE_GAUSSIAN>{});
         else if (kind == CODAE_NOISE_MASKING) with_pres(W, O, std::integral_constant<int, CODAE_NOISE_MASKING>{});
         else if (kind == CODAE_NOISE_SALT_PEPPER) with_pres(W, O, std::integral_constant<int, CODAE_NOISE_SALT_PEPPER>{});
+        else if (kind == CODAE_NOISE_SWAP) with_pres(W, O, std::integral_constant<int, CODAE_NOISE_SWAP>{});
         else with_pres(W, O, std::integral_constant<int, CODAE_NOISE_NONE>{});
     };
     auto with_out = [&](auto W) { if (out_bf16) with_kind(W, std::true_type{}); else with_kind(W, std::false_type{}); };
@@ -335,9 +418,19 @@ int check_presence(const uint8_t* present, int n_slots, int io, const char* who)
     return CODAE_OK;
 }
 
+int check_swap(const codae_swap* sw, int io, const uint8_t* present, int pres_slots, const char* who) {
+    CODAE_REQUIRE(sw != nullptr && sw->n_slots >= 1, "%s: swap noise needs its slot count (codae_set_swap_pool / codae_swap)", who);
+    CODAE_REQUIRE(io > 0 && io % sw->n_slots == 0, "%s: swap noise: n_slots %d does not divide io %d", who, sw->n_slots, io);
+    CODAE_REQUIRE(sw->n_pool >= 1, "%s: swap noise: a pool of %d rows", who, sw->n_pool);
+    CODAE_REQUIRE(present == nullptr || pres_slots == sw->n_slots, "%s: swap noise: n_slots %d differs from the presence table's %d", who,
+                  sw->n_slots, pres_slots);
+    return CODAE_OK;
+}
+
 int check_noise(const codae_noise* n) {
     if (n == nullptr || n->kind == CODAE_NOISE_NONE) return CODAE_OK;
-    CODAE_REQUIRE(n->kind == CODAE_NOISE_GAUSSIAN || n->kind == CODAE_NOISE_MASKING || n->kind == CODAE_NOISE_SALT_PEPPER,
+    CODAE_REQUIRE(n->kind == CODAE_NOISE_GAUSSIAN || n->kind == CODAE_NOISE_MASKING || n->kind == CODAE_NOISE_SALT_PEPPER ||
+                      n->kind == CODAE_NOISE_SWAP,
                   "input noise: unknown kind %d", n->kind);
     if (n->kind == CODAE_NOISE_GAUSSIAN) {
         CODAE_REQUIRE(finite_f(n->p0) && n->p0 >= 0.f, "input noise: sigma %g must be finite and >= 0", (double)n->p0);
@@ -352,7 +445,8 @@ int check_noise(const codae_noise* n) {
 }
 
 int launch_gather_noise(const codae_batch* b, const codae_noise* noise, int32_t step, const double* step_dev, void* out, int out_bf16,
-                        hipStream_t s, int64_t out_ld, const int32_t* noise_rows, double* zero_norm, const uint8_t* present, int n_slots) {
+                        hipStream_t s, int64_t out_ld, const int32_t* noise_rows, double* zero_norm, const uint8_t* present, int n_slots,
+                        const codae_swap* swap, const float* swap_data) {
     const int kind = noise ? noise->kind : CODAE_NOISE_NONE;
     // (the plain gather keys the table by the row it reads: a batch gathered by the caller has lost its dataset rows)
     CODAE_REQUIRE(kind != CODAE_NOISE_NONE || present == nullptr || noise_rows == nullptr,
@@ -361,6 +455,14 @@ int launch_gather_noise(const codae_batch* b, const codae_noise* noise, int32_t 
     if (rc) return rc;
     rc = check_gather("gather_corrupt", b, b ? b->data : nullptr, out, present, n_slots);
     if (rc) return rc;
+    SwapGather sg{};
+    if (kind == CODAE_NOISE_SWAP) {
+        rc = check_swap(swap, b->io, present, n_slots, "gather_corrupt");
+        if (rc) return rc;
+        CODAE_REQUIRE(noise_rows == nullptr || swap_data != nullptr, "gather_corrupt: swap noise on a gathered batch (noise_rows) needs the dataset");
+        sg.sw = swap_args(noise, swap, b->io, present);
+        sg.sdata = swap_data ? swap_data : b->data;
+    }
     if (out_ld <= 0) out_ld = b->io;
     const PresArgs pa{present, n_slots, present ? b->io / n_slots : 0};
     NoiseArgs na{};
@@ -372,14 +474,14 @@ int launch_gather_noise(const codae_batch* b, const codae_noise* noise, int32_t 
         na.p0 = noise->p0; na.p1 = noise->p1; na.p2 = noise->p2;
     }
     const bool masked = b->mask_id || b->mask_to_use;
-    const bool vec = (b->io % 4 == 0) && (out_ld % 4 == 0) && a16(b->data) && a16(out) && (!masked || (reinterpret_cast<uintptr_t>(b->mask_table) & 3) == 0);
+    const bool vec = (b->io % 4 == 0) && (out_ld % 4 == 0) && a16(b->data) && (sg.sdata == nullptr || a16(sg.sdata)) && a16(out) && (!masked || (reinterpret_cast<uintptr_t>(b->mask_table) & 3) == 0);
     const int64_t items = (int64_t)b->B * (vec ? b->io / 4 : b->io);
     const bool x8 = vec && out_bf16 && b->io % 8 == 0 && (!masked || (reinterpret_cast<uintptr_t>(b->mask_table) & 7) == 0);
     const int grid = grid_for(x8 ? items / 2 : items);
     gather_dispatch(x8 ? 8 : (vec ? 4 : 1), out_bf16 != 0, kind, present != nullptr, [&](auto W, auto O, auto K, auto P) {
         hipLaunchKernelGGL((gather_corrupt_kernel<decltype(W)::value, decltype(O)::value, decltype(K)::value, decltype(P)::value>), dim3(grid),
                            dim3(NT), 0, s, b->data, b->row_idx, b->mask_id, b->mask_table, b->B, b->io, out, b->mask_to_use, b->nb_run, b->run,
-                           out_ld, NoiseArgsOf<decltype(K)::value>(na), pa);
+                           out_ld, NoiseArgsOf<decltype(K)::value>(na, sg), pa);
     });
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;
@@ -393,19 +495,37 @@ bool gather_image_takes(const codae_batch* b, const void* image, const void* out
 }
 
 int launch_gather_image(const codae_batch* b, const bf16_t* image, bf16_t* out, hipStream_t s, int64_t out_ld, double* zero_norm,
-                        const uint8_t* present, int n_slots) {
-    const int rc = check_gather("gather_image", b, image, out, present, n_slots);
+                        const uint8_t* present, int n_slots, const codae_noise* noise, int32_t step, const double* step_dev,
+                        const codae_swap* swap) {
+    int rc = check_gather("gather_image", b, image, out, present, n_slots);
     if (rc) return rc;
+    const int kind = noise ? noise->kind : CODAE_NOISE_NONE;
+    CODAE_REQUIRE(kind == CODAE_NOISE_NONE || kind == CODAE_NOISE_SWAP, "gather_image: noise kind %d needs the fp32 rows", kind);
+    ImageHead<true> hs{};
+    if (kind == CODAE_NOISE_SWAP) {
+        rc = check_noise(noise);
+        if (rc) return rc;
+        rc = check_swap(swap, b->io, present, n_slots, "gather_image");
+        if (rc) return rc;
+        hs.zero_norm = zero_norm; hs.step = (uint32_t)step; hs.step_dev = step_dev;
+        hs.sw = swap_args(noise, swap, b->io, present);
+    }
     if (out_ld <= 0) out_ld = b->io;
     const PresArgs pa{present, n_slots, present ? b->io / n_slots : 0};
     CODAE_REQUIRE(gather_image_takes(b, image, out, out_ld),
                   "gather_image: io %d and out_ld %lld must be multiples of 8, image and out 16-byte and mask_table 8-byte aligned", b->io,
                   (long long)out_ld);
     const int grid = grid_for((int64_t)b->B * (b->io / 8));
-#define GCI(P) hipLaunchKernelGGL((gather_corrupt_image_kernel<P>), dim3(grid), dim3(NT), 0, s, image, b->row_idx, b->mask_id, b->mask_table, \
-                                  b->B, b->io, out, b->mask_to_use, b->nb_run, b->run, out_ld, zero_norm, pa)
-    if (present) GCI(true);
-    else GCI(false);
+#define GCI(P, W, HD) hipLaunchKernelGGL((gather_corrupt_image_kernel<P, W>), dim3(grid), dim3(NT), 0, s, image, b->row_idx, b->mask_id, b->mask_table, \
+                                         b->B, b->io, out, b->mask_to_use, b->nb_run, b->run, out_ld, HD, pa)
+    const ImageHead<false> hp{zero_norm};
+    if (kind == CODAE_NOISE_SWAP) {
+        if (present) GCI(true, true, hs);
+        else GCI(false, true, hs);
+    } else {
+        if (present) GCI(true, false, hp);
+        else GCI(false, false, hp);
+    }
 #undef GCI
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;

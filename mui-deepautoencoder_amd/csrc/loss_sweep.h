@@ -67,12 +67,22 @@ struct BatchArgs {
 struct WeightArgs {
     float alpha, beta;
     const float* col_weight;   // [io] or null (all ones)
-    int replace;               // the input noise is MASKING or SALT_PEPPER: a word below thresh marks a replaced element
+    int replace;               // 1: the input noise is MASKING or SALT_PEPPER: a word below thresh marks a replaced element
+                               // 2: SWAP: every element of a slot whose swap was accepted (SwapWeightArgs::sw; one word per (row, slot))
     uint64_t thresh;           // T = floor(p 2^32)
     uint32_t key0, key1;
     uint32_t step;             // counter word 2 ...
     const double* step_dev;    // ... or, when not null, *step_dev (graph replay)
 };
+constexpr int REPLACE_ELEMS = 1, REPLACE_SWAP = 2;
+// the SWAP instantiations take the draw's arguments behind the weights; every other instantiation keeps the argument block it had
+struct SwapWeightArgs : WeightArgs {
+    SwapArgs sw;               // replace == REPLACE_SWAP
+};
+template <bool SWAP>
+using WeightArgsOf = std::conditional_t<SWAP, SwapWeightArgs, WeightArgs>;
+template <bool SWAP>
+inline WeightArgsOf<SWAP> weight_args_of(const SwapWeightArgs& a) { return a; }
 
 // which of the four columns c .. c + 3 of dataset row `row` the gather's noise replaced (c a multiple of 4: one Philox group)
 __device__ __forceinline__ void hits4(bool* hit, int c, uint32_t row, uint32_t step, const WeightArgs& a) {
@@ -88,6 +98,19 @@ __device__ __forceinline__ bool hit1(int c, uint32_t row, uint32_t step, const W
     return (uint64_t)rk < a.thresh;
 }
 
+// Swap noise: which of the W columns whose swap slots are ssl[0 .. W) (slots_of with the swap's E, formed once per thread) sit in a
+// slot of dataset row `row` that took an accepted swap: one Philox call per slot the group touches
+template <int W>
+__device__ __forceinline__ void swap_hits(bool* hit, const int* ssl, uint32_t row, uint32_t step, const SwapArgs& sw) {
+    hit[0] = swap_source(sw, row, ssl[0], step) >= 0;
+#pragma unroll
+    for (int k = 1; k < W; ++k) hit[k] = ssl[k] == ssl[k - 1] ? hit[k - 1] : swap_source(sw, row, ssl[k], step) >= 0;
+}
+// the same for the single column c of a kernel that walks a slot's columns (slot_cosine's phase 1, the slot contrast)
+__device__ __forceinline__ bool swap_hit1(int c, uint32_t row, uint32_t step, const SwapArgs& sw) {
+    return swap_source(sw, row, c / sw.E, step) >= 0;
+}
+
 // ---- host side: what the launchers make of a LossLaunch ----------------------------------------------------------------------------
 inline BatchArgs batch_args(const codae_batch* b) {
     return BatchArgs{b->data, b->row_idx, b->mask_id, b->mask_table, b->mask_to_use, b->nb_run, b->run, b->B, b->io};
@@ -96,14 +119,18 @@ inline PresArgs pres_args(const LossLaunch& ll) {
     return PresArgs{ll.present, ll.n_slots, ll.present ? ll.batch->io / ll.n_slots : 0};
 }
 // weighted: an element's weight may depend on what the input noise replaced (without emphasis no weight does)
-inline WeightArgs weight_args(const LossLaunch& ll, bool weighted) {
-    WeightArgs wa{};
+inline SwapWeightArgs weight_args(const LossLaunch& ll, bool weighted) {
+    SwapWeightArgs wa{};
     wa.alpha = 1.f; wa.beta = 1.f;
     if (ll.emph != nullptr) { wa.alpha = ll.emph->alpha; wa.beta = ll.emph->beta; wa.col_weight = ll.emph->col_weight; }
     wa.step = (uint32_t)ll.step; wa.step_dev = ll.step_dev;
     const codae_noise* n = ll.noise;
+    if (weighted && n != nullptr && n->kind == CODAE_NOISE_SWAP) {      // (check_loss_launch has seen ll.swap)
+        wa.replace = REPLACE_SWAP;
+        wa.sw = swap_args(n, ll.swap, ll.batch->io, ll.present);
+    }
     if (weighted && n != nullptr && (n->kind == CODAE_NOISE_MASKING || n->kind == CODAE_NOISE_SALT_PEPPER)) {
-        wa.replace = 1;
+        wa.replace = REPLACE_ELEMS;
         wa.key0 = (uint32_t)(n->seed & 0xffffffffu); wa.key1 = (uint32_t)(n->seed >> 32);
         wa.thresh = (uint64_t)floor((double)n->p0 * 4294967296.0);      // (the gather's T)
     }
@@ -114,6 +141,11 @@ inline bool loss_inputs_a16(const LossLaunch& ll) {
     const codae_batch* b = ll.batch;
     const bool masked = b->mask_id || b->mask_to_use;
     return a16(b->data) && a16(ll.y) && (!masked || (reinterpret_cast<uintptr_t>(b->mask_table) & 3) == 0);
+}
+// g(std::bool_constant<SWAP>) for the launch's instantiation of the "replaced" test
+template <typename G>
+inline void swap_dispatch(const SwapWeightArgs& wa, G&& g) {
+    if (wa.replace == REPLACE_SWAP) g(std::true_type{}); else g(std::false_type{});
 }
 // f(std::bool_constant<VEC>, std::bool_constant<DY_BF16>, std::bool_constant<PRES>) for the launch's instantiation
 template <typename F>
@@ -142,9 +174,12 @@ inline void loss_dispatch(bool vec, bool dy_bf16, bool pres, F&& f) {
 //   Term::PER_SLOT    the term reads a value per (row, slot): every column's slot is formed, with the term's E
 // Whether a sum is wrapped in opaque() is the term's: it decides whether neighbouring columns' chains are packed (DESIGN.md
 // section 5d), and it is part of the bits tests/test_gpu_loss_kernel_bits.py pins.
-template <bool VEC, bool DY_BF16, bool PRES, typename Term>
+// SWAP (the input noise is CODAE_NOISE_SWAP, wa.replace == REPLACE_SWAP): "replaced" is the swap form - one Philox call per (row,
+// slot) the thread's columns touch.  A template flag, so that the instantiations of every other setting stay the code they were
+// (tests/test_gpu_loss_kernel_bits.py pins their bits; whether a sum is contracted into an fma is decided per instantiation).
+template <bool VEC, bool DY_BF16, bool PRES, bool SWAP = false, typename Term>
 __device__ __forceinline__ void loss_sweep(const BatchArgs& ba, const float* __restrict__ y, void* __restrict__ dy, int64_t dy_ld,
-                                           float* __restrict__ colsum_part, const PresArgs& pa, const WeightArgs& wa, Term& term) {
+                                           float* __restrict__ colsum_part, const PresArgs& pa, const WeightArgsOf<SWAP>& wa, Term& term) {
     const float* __restrict__ data = ba.data;
     const uint8_t* __restrict__ table = ba.table;
     const int B = ba.B, io = ba.io;
@@ -161,6 +196,10 @@ __device__ __forceinline__ void loss_sweep(const BatchArgs& ba, const float* __r
             for (int k = 0; k < W; ++k) sl[k] = (c + k) / term.E;
         } else if constexpr (PRES) {
             slots_of<W>(c, pa.E, sl);
+        }
+        int ssl[4] = {0, 0, 0, 0};
+        if constexpr (SWAP) {
+            if (term.weighted()) slots_of<W>(c, wa.sw.E, ssl);
         }
         float cw[4] = {1.f, 1.f, 1.f, 1.f};
         if (term.weighted() && wa.col_weight != nullptr) {
@@ -196,7 +235,9 @@ __device__ __forceinline__ void loss_sweep(const BatchArgs& ba, const float* __r
                 if (masked) m = table[(int64_t)id * io + c];
             }
             bool hit[4] = {false, false, false, false};
-            if (term.weighted() && wa.replace) {
+            if constexpr (SWAP) {
+                if (term.weighted()) swap_hits<W>(hit, ssl, (uint32_t)src_row, step, wa.sw);
+            } else if (term.weighted() && wa.replace) {
                 if constexpr (VEC) hits4(hit, c, (uint32_t)src_row, step, wa);
                 else hit[0] = hit1(c, (uint32_t)src_row, step, wa);
             }

@@ -51,8 +51,8 @@ int dgrad_bf16(const char* who, const void* dy, const void* W, const void* src, 
 // the C entry points' arguments as one stand-alone loss launch (no device step scalar: these run outside any graph)
 LossLaunch loss_launch(const codae_batch* batch, const codae_noise* noise, int32_t step, const codae_emphasis* emphasis, const float* y,
                        void* dy, int32_t dy_bf16, int64_t dy_ld, float scale, float* colsum_part, double* parts,
-                       const uint8_t* present = nullptr, int32_t n_slots = 0) {
-    return LossLaunch{batch, noise, step, nullptr, emphasis, present, n_slots, y, dy, dy_bf16, dy_ld, scale, colsum_part, parts};
+                       const uint8_t* present = nullptr, int32_t n_slots = 0, const codae_swap* swap = nullptr) {
+    return LossLaunch{batch, noise, step, nullptr, emphasis, present, n_slots, y, dy, dy_bf16, dy_ld, scale, colsum_part, parts, swap};
 }
 
 }  // namespace
@@ -110,6 +110,37 @@ int codae_slot_contrast_fwd_bwd_present(const codae_batch* batch, const codae_no
                                         float scale, float* colsum_part, double* parts, const uint8_t* present, int32_t n_slots, void* stream) {
     return launch_slot_contrast(loss_launch(batch, noise, step, emphasis, y, dy, dy_bf16, dy_ld, scale, colsum_part, parts, present, n_slots),
                                 contrast, (hipStream_t)stream);
+}
+
+int codae_corrupt_batch_swap(const codae_batch* batch, const codae_noise* noise, int32_t step, const int32_t* noise_rows, const void* dataset,
+                             const codae_swap* swap, void* out, int32_t out_bf16, int64_t out_ld, const uint8_t* present, int32_t image,
+                             void* stream) {
+    CODAE_REQUIRE(batch != nullptr && noise != nullptr && noise->kind == CODAE_NOISE_SWAP && swap != nullptr,
+                  "codae_corrupt_batch_swap: needs a batch, a CODAE_NOISE_SWAP noise and its codae_swap");
+    CODAE_REQUIRE(noise_rows == nullptr || batch->row_idx == nullptr, "codae_corrupt_batch_swap: noise_rows go with an already gathered batch (row_idx NULL)");
+    if (image) {
+        CODAE_REQUIRE(out_bf16 && noise_rows == nullptr && (dataset == nullptr || dataset == (const void*)batch->data),
+                      "codae_corrupt_batch_swap: the image gather writes bf16 and reads the one image (no noise_rows, no other dataset)");
+        return launch_gather_image(batch, reinterpret_cast<const bf16_t*>(batch->data), reinterpret_cast<bf16_t*>(out), (hipStream_t)stream, out_ld,
+                                   nullptr, present, present ? swap->n_slots : 0, noise, step, nullptr, swap);
+    }
+    return launch_gather_noise(batch, noise, step, nullptr, out, out_bf16, (hipStream_t)stream, out_ld, noise_rows, nullptr, present,
+                               present ? swap->n_slots : 0, swap, reinterpret_cast<const float*>(dataset));
+}
+
+int codae_emph_loss_swap(const codae_batch* batch, const codae_noise* noise, int32_t step, const codae_emphasis* emphasis, const float* y,
+                         void* dy, int32_t dy_bf16, int64_t dy_ld, float inv_n, float* colsum_part, double* parts, const codae_swap* swap,
+                         const uint8_t* present, int32_t n_slots, void* stream) {
+    return launch_emph_loss(loss_launch(batch, noise, step, emphasis, y, dy, dy_bf16, dy_ld, inv_n, colsum_part, parts, present, n_slots, swap),
+                            (hipStream_t)stream);
+}
+
+int codae_recon_loss_fwd_bwd_swap(const codae_batch* batch, const codae_noise* noise, int32_t step, const codae_emphasis* emphasis,
+                                  const codae_recon_loss* loss, const float* y, void* dy, int32_t dy_bf16, int64_t dy_ld, float inv_n,
+                                  float* colsum_part, double* parts, const codae_swap* swap, const uint8_t* present, int32_t n_slots,
+                                  void* stream) {
+    return launch_recon_loss(loss_launch(batch, noise, step, emphasis, y, dy, dy_bf16, dy_ld, inv_n, colsum_part, parts, present, n_slots, swap),
+                             loss, (hipStream_t)stream);
 }
 
 int codae_emph_loss_blocks(int32_t B) { return B > 0 ? mse_loss_colsum_rows(B) : 0; }

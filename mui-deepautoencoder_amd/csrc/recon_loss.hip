@@ -16,14 +16,14 @@ constexpr int MAX_SLOTS = 128;   // slot_cosine: the coefficient table is LOSS_R
 
 // ---- L1 / SmoothL1 / Huber -----------------------------------------------------------------------------------------------------
 //   dy = w rho'(d) (-1) inv_n, d = x - y;   parts[block] = { sum w rho(d), sum d^2, sum (1-fmask) d^2 }
-template <int KIND, bool VEC, bool DY_BF16, bool PRES>
+template <int KIND, bool VEC, bool DY_BF16, bool PRES, bool SWAP = false>
 __global__ __launch_bounds__(NT) void recon_elem_kernel(BatchArgs ba, const float* __restrict__ y, void* __restrict__ dy, float inv_n,
                                                         float* __restrict__ colsum_part, double* __restrict__ parts, int64_t dy_ld,
-                                                        WeightArgs wa, ReconArgs ra, PresArgs pa) {
+                                                        WeightArgsOf<SWAP> wa, ReconArgs ra, PresArgs pa) {
     __shared__ float red[WAVES];
     const bool masked = (ba.mask_id != nullptr) || (ba.mask_to_use != nullptr);
     RhoTerm<KIND> term(wa, ra, inv_n);
-    loss_sweep<VEC, DY_BF16, PRES>(ba, y, dy, dy_ld, colsum_part, pa, wa, term);
+    loss_sweep<VEC, DY_BF16, PRES, SWAP>(ba, y, dy, dy_ld, colsum_part, pa, wa, term);
     const float bwr = block_sum(term.wr, red);
     const float bsq = block_sum(term.sq, red);
     const float bsqp = block_sum(term.sqp, red);
@@ -44,8 +44,8 @@ __global__ __launch_bounds__(NT) void recon_elem_kernel(BatchArgs ba, const floa
 // Phase 2 (after one barrier): the row sweep with CosineTerm: g = -(a x - b y) + mse_weight 2 w (y - x) inv_n, dY, the column
 // sums in registers, the squared-error sums.  x and y are read again (from L2: a block's rows are 2 x 32 x io x 4 B).
 //   parts[block] = { mse_weight sum w d^2 + E sum W (1 - cos), sum d^2, sum (1-fmask) d^2 }
-template <bool VEC1>
-__device__ __forceinline__ void slot_pair_sums(const BatchArgs& ba, const float* __restrict__ y, const WeightArgs& ea, int E, int b, int s,
+template <bool VEC1, bool SWAP>
+__device__ __forceinline__ void slot_pair_sums(const BatchArgs& ba, const float* __restrict__ y, const WeightArgsOf<SWAP>& ea, int E, int b, int s,
                                                uint32_t step, float& dot, float& nx2, float& ny2, float& sw) {
     const int io = ba.io;
     const int lane = threadIdx.x & 63;
@@ -57,6 +57,12 @@ __device__ __forceinline__ void slot_pair_sums(const BatchArgs& ba, const float*
     const uint8_t* __restrict__ tr = ba.table + (int64_t)id * io;
     const bool weighted = ea.col_weight != nullptr || ea.replace || ea.alpha != ea.beta;
     dot = 0.f; nx2 = 0.f; ny2 = 0.f; sw = 0.f;
+    // swap noise: the pair's own draw when the swap's slots are the criterion's (one word per pair), else a draw per column
+    bool swap_pair = false, pair_hit = false;
+    if constexpr (SWAP) {
+        swap_pair = ea.sw.E == E;
+        pair_hit = weighted && swap_pair && swap_source(ea.sw, (uint32_t)src_row, s, step) >= 0;
+    }
     const int pieces = (E + 3) >> 2;
     for (int j = lane; j < pieces; j += 64) {
         const int e0 = j * 4;
@@ -75,7 +81,12 @@ __device__ __forceinline__ void slot_pair_sums(const BatchArgs& ba, const float*
                 }
                 const uint32_t m = masked ? *reinterpret_cast<const uint32_t*>(tr + c) : 0x01010101u;
                 bool hit[4] = {false, false, false, false};
-                if (ea.replace) hits4(hit, c, (uint32_t)src_row, step, ea);
+                if constexpr (SWAP) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) hit[k] = swap_pair ? pair_hit : swap_hit1(c + k, (uint32_t)src_row, step, ea.sw);
+                } else {
+                    if (ea.replace) hits4(hit, c, (uint32_t)src_row, step, ea);
+                }
 #pragma unroll
                 for (int k = 0; k < 4; ++k) wv[k] = cw[k] * ((((m >> (8 * k)) & 0xff) == 0 || hit[k]) ? ea.alpha : ea.beta);
             } else {
@@ -90,7 +101,9 @@ __device__ __forceinline__ void slot_pair_sums(const BatchArgs& ba, const float*
                     yv[k] = yr[c + k];
                     const float cw = ea.col_weight != nullptr ? ea.col_weight[c + k] : 1.f;
                     const bool blank = masked && tr[c + k] == 0;
-                    const bool hit = ea.replace ? hit1(c + k, (uint32_t)src_row, step, ea) : false;
+                    bool hit;
+                    if constexpr (SWAP) hit = swap_pair ? pair_hit : swap_hit1(c + k, (uint32_t)src_row, step, ea.sw);
+                    else hit = ea.replace ? hit1(c + k, (uint32_t)src_row, step, ea) : false;
                     wv[k] = cw * ((blank || hit) ? ea.alpha : ea.beta);
                 }
             }
@@ -109,10 +122,10 @@ __device__ __forceinline__ void slot_pair_sums(const BatchArgs& ba, const float*
 
 // PRES: an absent pair is skipped in phase 1 - coefficients 0, no term, its x never read -, and phase 2 selects x = y = 0 for its
 // columns as they are loaded and stores +0 (the table's slots are the criterion's: pa.S == ea.S).
-template <bool VEC1, bool VEC, bool DY_BF16, bool PRES>
+template <bool VEC1, bool VEC, bool DY_BF16, bool PRES, bool SWAP = false>
 __global__ __launch_bounds__(NT) void slot_cosine_kernel(BatchArgs ba, const float* __restrict__ y, void* __restrict__ dy, float inv_n,
                                                          float* __restrict__ colsum_part, double* __restrict__ parts, int64_t dy_ld,
-                                                         WeightArgs ea, ReconArgs ra, PresArgs pa) {
+                                                         WeightArgsOf<SWAP> ea, ReconArgs ra, PresArgs pa) {
     extern __shared__ float coef[];      // [LOSS_ROWS][S][2]
     __shared__ float red[WAVES];
     const int B = ba.B, S = ra.S, E = ra.E;
@@ -136,7 +149,7 @@ __global__ __launch_bounds__(NT) void slot_cosine_kernel(BatchArgs ba, const flo
         }
         if (pair_on) {
             float dot, nx2, ny2, sw;
-            slot_pair_sums<VEC1>(ba, y, ea, E, r_begin + rr, s, step, dot, nx2, ny2, sw);
+            slot_pair_sums<VEC1, SWAP>(ba, y, ea, E, r_begin + rr, s, step, dot, nx2, ny2, sw);
             const float nxr = sqrtf(nx2), nyr = sqrtf(ny2);
             const float nx = nxr < CODAE_COS_EPS ? CODAE_COS_EPS : nxr;     // max(., eps) that keeps a NaN norm a NaN
             const float ny = nyr < CODAE_COS_EPS ? CODAE_COS_EPS : nyr;
@@ -155,7 +168,7 @@ __global__ __launch_bounds__(NT) void slot_cosine_kernel(BatchArgs ba, const flo
     // ---- phase 2
     const float mw = ra.mse_weight;
     CosineTerm term(coef, ea, ra, inv_n);
-    loss_sweep<VEC, DY_BF16, PRES>(ba, y, dy, dy_ld, colsum_part, pa, ea, term);
+    loss_sweep<VEC, DY_BF16, PRES, SWAP>(ba, y, dy, dy_ld, colsum_part, pa, ea, term);
     // every lane of a wave holds the same cos_terms: count it once per wave
     const float bcos = block_sum((threadIdx.x & 63) == 0 ? cos_terms : 0.f, red);
     const float bwsq = block_sum(term.wsq, red);
@@ -206,7 +219,7 @@ int launch_recon_loss(const LossLaunch& ll, const codae_recon_loss* loss, hipStr
     rc = check_recon_loss(loss, b->io);
     if (rc) return rc;
     CODAE_REQUIRE(loss->kind != CODAE_LOSS_MSE, "recon_loss: kind MSE runs on the mean-squared-error kernels (codae_emph_loss)");
-    const WeightArgs wa = weight_args(ll, ll.emph != nullptr);
+    const SwapWeightArgs wa = weight_args(ll, ll.emph != nullptr);
     ReconArgs ra{};
     ra.param = loss->param; ra.rparam = (loss->kind == CODAE_LOSS_SMOOTH_L1) ? (float)(1.0 / (double)loss->param) : 0.f;
     const BatchArgs ba = batch_args(b);
@@ -221,17 +234,22 @@ int launch_recon_loss(const LossLaunch& ll, const codae_recon_loss* loss, hipStr
         const size_t lds = (size_t)LOSS_ROWS * ra.S * 2 * sizeof(float);
         loss_dispatch(vec, ll.dy_bf16, ll.present != nullptr, [&](auto V, auto O, auto P) {
             constexpr bool v = decltype(V)::value, o = decltype(O)::value, p = decltype(P)::value;
-            if (vec1) hipLaunchKernelGGL((slot_cosine_kernel<true, v, o, p>), grid, block, lds, s, ba, ll.y, ll.dy, ll.scale, ll.colsum_part,
-                                         ll.parts, dy_ld, wa, ra, pa);
-            else hipLaunchKernelGGL((slot_cosine_kernel<false, v, o, p>), grid, block, lds, s, ba, ll.y, ll.dy, ll.scale, ll.colsum_part,
-                                    ll.parts, dy_ld, wa, ra, pa);
+            swap_dispatch(wa, [&](auto W) {
+                constexpr bool w = decltype(W)::value;
+                if (vec1) hipLaunchKernelGGL((slot_cosine_kernel<true, v, o, p, w>), grid, block, lds, s, ba, ll.y, ll.dy, ll.scale, ll.colsum_part,
+                                             ll.parts, dy_ld, weight_args_of<w>(wa), ra, pa);
+                else hipLaunchKernelGGL((slot_cosine_kernel<false, v, o, p, w>), grid, block, lds, s, ba, ll.y, ll.dy, ll.scale, ll.colsum_part,
+                                        ll.parts, dy_ld, weight_args_of<w>(wa), ra, pa);
+            });
         });
     } else {
         loss_dispatch(vec, ll.dy_bf16, ll.present != nullptr, [&](auto V, auto O, auto P) {
             constexpr bool v = decltype(V)::value, o = decltype(O)::value, p = decltype(P)::value;
             auto go = [&](auto K) {
-                hipLaunchKernelGGL((recon_elem_kernel<decltype(K)::value, v, o, p>), grid, block, 0, s, ba, ll.y, ll.dy, ll.scale, ll.colsum_part,
-                                   ll.parts, dy_ld, wa, ra, pa);
+                swap_dispatch(wa, [&](auto W) {
+                    hipLaunchKernelGGL((recon_elem_kernel<decltype(K)::value, v, o, p, decltype(W)::value>), grid, block, 0, s, ba, ll.y, ll.dy,
+                                       ll.scale, ll.colsum_part, ll.parts, dy_ld, weight_args_of<decltype(W)::value>(wa), ra, pa);
+                });
             };
             if (loss->kind == CODAE_LOSS_L1) go(std::integral_constant<int, CODAE_LOSS_L1>{});
             else if (loss->kind == CODAE_LOSS_SMOOTH_L1) go(std::integral_constant<int, CODAE_LOSS_SMOOTH_L1>{});

@@ -196,10 +196,10 @@ __device__ __forceinline__ float ex(float v) { return __expf(v); }
 // per-row scalars (LDS, one set per wave): 0 cos(x, y), 1 1 / max(|x|, eps), 2 1 / max(|y|, eps), 3 [|y| > eps] / (tau |y|), 4 W, 5 flags
 // (1 = bad: a NaN or Inf in the y slot, 2 = no positive: |x| <= eps, 4 = a row of the batch, 8 = the slot is absent in this row:
 // its x is never used - selected to 0, which makes it a pair without a positive), 6 1 - p0, 7 g . y^
-template <typename T, int MAXT, int NH>
+template <typename T, int MAXT, int NH, bool SWAP = false>
 __global__ __launch_bounds__(NT) void slot_contrast_kernel(BatchArgs ba, const float* __restrict__ y, T* __restrict__ dy, int64_t dy_ld,
                                                            float scale, float* __restrict__ colsum_part, double* __restrict__ parts,
-                                                           ContrastArgs ca, WeightArgs ew) {
+                                                           ContrastArgs ca, WeightArgsOf<SWAP> ew) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r16 = lane & 15, g = lane >> 4;
@@ -236,6 +236,12 @@ __global__ __launch_bounds__(NT) void slot_contrast_kernel(BatchArgs ba, const f
                 const float* __restrict__ yr = y + (int64_t)b * io + s * E;
                 const bool absent = ca.present != nullptr && ca.present[src_row * S + s] == 0;     // (wave-uniform)
                 float dot = 0.f, nx2 = 0.f, ny2 = 0.f, sw = 0.f;
+                // swap noise: the pair's own draw when the swap's slots are the contrast's, else a draw per column
+                bool swap_pair = false, pair_hit = false;
+                if constexpr (SWAP) {
+                    swap_pair = ew.sw.E == E;
+                    pair_hit = weighted && swap_pair && swap_source(ew.sw, (uint32_t)src_row, s, step) >= 0;
+                }
                 for (int e = lane; e < E; e += 64) {
                     const float xv = absent ? 0.f : xr[e], yv = yr[e];
                     float w = ew.beta;
@@ -243,7 +249,9 @@ __global__ __launch_bounds__(NT) void slot_contrast_kernel(BatchArgs ba, const f
                         const int c = s * E + e;
                         const float cw = ew.col_weight != nullptr ? ew.col_weight[c] : 1.f;
                         const bool blank = masked && ba.table[(int64_t)id * io + c] == 0;
-                        const bool hit = ew.replace ? hit1(c, (uint32_t)src_row, step, ew) : false;
+                        bool hit;
+                        if constexpr (SWAP) hit = swap_pair ? pair_hit : swap_hit1(c, (uint32_t)src_row, step, ew.sw);
+                        else hit = ew.replace ? hit1(c, (uint32_t)src_row, step, ew) : false;
                         w = cw * ((blank || hit) ? ew.alpha : ew.beta);
                     }
                     dot = opaque(__fmaf_rn(xv, yv, dot));
@@ -454,19 +462,23 @@ int raise_lds() {
     CODAE_HIP_CHECK(hipGetDevice(&dev));
     std::lock_guard<std::mutex> hold(lock);
     if (dev >= 0 && dev < MAX_DEV && raised[dev]) return CODAE_OK;
-#define RAISE(T, M, H) CODAE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&slot_contrast_kernel<T, M, H>), \
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
+#define RAISE1(T, M, H, W) CODAE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&slot_contrast_kernel<T, M, H, W>), \
+                                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
+#define RAISE(T, M, H) RAISE1(T, M, H, false); RAISE1(T, M, H, true)
     RAISE(bf16_t, 8, 1); RAISE(bf16_t, 32, 1); RAISE(bf16_t, 32, 2); RAISE(float, 8, 1); RAISE(float, 32, 1); RAISE(float, 32, 2);
 #undef RAISE
+#undef RAISE1
     if (dev >= 0 && dev < MAX_DEV) raised[dev] = true;
     return CODAE_OK;
 }
 
 template <typename T, int MAXT, int NH>
 int launch_one(int grid, size_t lds, hipStream_t s, const BatchArgs& ba, const float* y, void* dy, int64_t dy_ld, float scale,
-               float* colsum_part, double* parts, const ContrastArgs& ca, const WeightArgs& ew) {
-    hipLaunchKernelGGL((slot_contrast_kernel<T, MAXT, NH>), dim3(grid), dim3(NT), lds, s, ba, y, reinterpret_cast<T*>(dy), dy_ld, scale,
-                       colsum_part, parts, ca, ew);
+               float* colsum_part, double* parts, const ContrastArgs& ca, const SwapWeightArgs& ew) {
+    swap_dispatch(ew, [&](auto W) {
+        hipLaunchKernelGGL((slot_contrast_kernel<T, MAXT, NH, decltype(W)::value>), dim3(grid), dim3(NT), lds, s, ba, y, reinterpret_cast<T*>(dy),
+                           dy_ld, scale, colsum_part, parts, ca, weight_args_of<decltype(W)::value>(ew));
+    });
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;
 }
@@ -542,7 +554,7 @@ int launch_slot_contrast(const LossLaunch& ll, const codae_slot_contrast* c, hip
     CODAE_REQUIRE(finite_f(ll.scale), "slot contrast: scale %g is not finite", (double)ll.scale);
     rc = check_slot_contrast(c, b->io, dy_bf16);
     if (rc) return rc;
-    const WeightArgs ew = weight_args(ll, ll.emph != nullptr);
+    const SwapWeightArgs ew = weight_args(ll, ll.emph != nullptr);
     const int E = b->io / c->n_slots;
     const WsLayout w = ws_layout(c->n_slots, c->n_neg, E, dy_bf16);
     ContrastArgs ca{};

@@ -120,9 +120,14 @@ def main():
         raise HipError("HIP: ACTIVATION: %r is not a torch.nn module" % act_name)
     dataset.to(device)
     # HIP: INPUT_NOISE: {KIND: gaussian | masking | salt_pepper, SIGMA | P: ..., LO: ..., HI: ..., SEED: ...} (build-only key):
-    # noise on the training input in front of the slot blank; LO / HI default to the resident data's min / max
+    # noise on the training input in front of the slot blank; LO / HI default to the resident data's min / max.
+    # {KIND: swap, P: 0.15, SEED: 7, POOL: train | all}: a slot replaced by another row's item of that slot; POOL: train (the default)
+    # takes the items from the training rows only, so that no validation item ever reaches a training input
     from codae.tool.noise import input_noise_from_config
-    input_noise = input_noise_from_config(config.get("HIP", {}).get("INPUT_NOISE"), dataset.data)
+    input_noise = input_noise_from_config(config.get("HIP", {}).get("INPUT_NOISE"), dataset.data, train_rows=train_indices)
+    if input_noise is not None and input_noise.kind == "swap":
+        log.info("INPUT NOISE: swap, p = %g, pool of %d rows" % (input_noise.p, dataset.nb_observation if input_noise.pool is None
+                                                                 else input_noise.pool.size))
     # HIP: LOSS_EMPHASIS: {ALPHA: ..., BETA: ..., SLOT_WEIGHT: [..] | COLUMN_WEIGHT: [..]} (build-only key): the training loss weights
     # corrupted elements by ALPHA, untouched ones by BETA, every slot / column by its weight (the monitors stay unweighted)
     from codae.tool.emphasis import loss_emphasis_from_config
