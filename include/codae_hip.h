@@ -1133,6 +1133,29 @@ int codae_auc_counts(const float* pos, const uint8_t* pos_on, int32_t P, const f
 int codae_score_outfits(codae_handle h, const codae_buffers* b, const float* data, int64_t n_rows, const int32_t* items, int32_t Q,
                         int32_t n_slots, float* cos, float* sq, float* score, int32_t* n_present, void* stream);
 
+/* ---- State digest -------------------------------------------------------------------------------------------------------
+ * A 128-bit fingerprint of a device buffer, computed on the device in one pass, and - with dst - a copy of the buffer made in that
+ * same pass (the snapshot of a checkpoint: codae.train.HipEmbeddingTrainer.snapshot).  It verifies a loaded state where it lies and
+ * lets data-parallel replicas be compared 16 bytes at a time.  It is NOT cryptographic: it detects accidents, not adversaries.
+ * Definition.  The n_bytes of src (a multiple of 4) are read as little-endian uint32 words w_0 .. w_{n-1}, zero-padded to a multiple
+ * of four words; all arithmetic is mod 2^64:
+ *   G      = 0x9E3779B97F4A7C15
+ *   mix(x) : z = x + G;  z = (z ^ z>>30) * 0xBF58476D1CE4E5B9;  z = (z ^ z>>27) * 0x94D049BB133111EB;  return z ^ z>>31
+ *   group g = words 4g .. 4g+3:   a = w0 | w1<<32,   b = w2 | w3<<32,   h_g = mix(a ^ mix(b + g*G))
+ *   out[0] = (sum_g h_g) ^ mix(n_bytes)          out[1] = xor_g mix(h_g ^ g)
+ * Bitwise, not by value: -0.0 differs from +0.0 and NaN payloads count; positional: swapping two words changes it.  The empty buffer
+ * has out = {mix(0), 0}.  codae.tool.checkpoint.StateDigest is the numpy restatement.
+ * Order.  Sum and xor are associative and commutative, so the lanes, waves and workgroups combine in whatever order they finish and
+ * the bits are the same every run: per-lane 64-bit accumulators, a wave64 butterfly, one 64-bit integer atomic add and xor per
+ * workgroup into the zeroed out (a buffer one workgroup covers is finished by that workgroup, in one launch).  The training step's
+ * "no float atomics" rule is untouched: these are integers.
+ * Paths.  src (and dst) 16-byte aligned: one 16-byte load (and store) per group; 4-byte aligned only: four dword accesses per group,
+ * same result.  The 1 .. 3 words behind the last whole group are padded in registers; nothing is read or written past n_bytes.  dst
+ * (or NULL) must not overlap src.  out: two 64-bit words on the device, written on the stream; no host synchronisation.
+ * CODAE_E_INVALID before any launch, with the offending value in codae_last_error(): n_bytes negative or not a multiple of 4, out
+ * NULL, src NULL with n_bytes > 0, a pointer that is not 4-byte (out: 8-byte) aligned.  n_bytes == 0 is valid (src may be NULL). */
+int codae_state_digest(const void* src, void* dst, int64_t n_bytes, uint64_t* out, void* stream);
+
 /* ---- GEMM primitives (exported for kernel-level parity tests / benchmarks) - */
 /* y[M][N] = act(x[M][K] . W[N][K]^T + b[N]), fp32 in / fp32 out (the parity engine's GEMM: CODAE_PREC_F32 above) */
 int codae_linear_f32(const float* x, const float* W, const float* b, float* y, int32_t M, int32_t N,

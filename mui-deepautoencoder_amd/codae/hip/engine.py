@@ -712,3 +712,58 @@ class DaeEngine:
 
     def zero_metric_sums(self):
         self.scalars[:2].zero_()
+
+    # ---- state: what defines the run (checkpoint, replica comparison; include/codae_hip.h, "State digest") ---------------------
+    def state_tensors(self):
+        """Ordered {name: flat tensor} of what defines the run: params, adam_m, adam_v, adam_vmax and weight_avg when allocated, and the
+        whole float64 scalars vector (it carries the running epoch sums).  The bf16 shadows (shadow, shadow_t, avg_shadow) are derived:
+        sync_shadows() / sync_average() rebuild them from these with the bits the update kernels leave.  Joins the side stream."""
+        self.join()
+        out = {"params": self._params}
+        for name in ("adam_m", "adam_v", "adam_vmax", "weight_avg"):
+            if getattr(self, name) is not None:
+                out[name] = getattr(self, name)
+        out["scalars"] = self.scalars
+        return out
+
+    def digest_into(self, src, out, dst=None):
+        """Enqueue codae_state_digest on the current stream: out (2 int64 on this device) <- the digest of the contiguous device tensor
+        src; dst (same bytes, or None) <- a copy made in the same pass.  No host synchronisation."""
+        if not src.is_contiguous() or src.device != self.device:
+            raise HipError("digest: the tensor must be contiguous and on %s" % self.device)
+        n_bytes = src.numel() * src.element_size()
+        if dst is not None and (not dst.is_contiguous() or dst.device != self.device or dst.numel() * dst.element_size() != n_bytes):
+            raise HipError("digest: dst must be a contiguous tensor of the same %d bytes on %s" % (n_bytes, self.device))
+        if out.dtype != torch.int64 or out.numel() != 2 or out.device != self.device or not out.is_contiguous():
+            raise HipError("digest: out must be 2 contiguous int64 on %s" % self.device)
+        with torch.cuda.device(self.device):
+            check(self._lib.codae_state_digest(ptr(src) if n_bytes else None, ptr(dst) if n_bytes else None, n_bytes, ptr(out),
+                                               current_stream()))
+
+    @staticmethod
+    def _digest_pairs(host_i64):
+        """int64 [n, 2] host tensor -> [(out0, out1)] as unsigned Python ints."""
+        return [(int(a) & 0xFFFFFFFFFFFFFFFF, int(b) & 0xFFFFFFFFFFFFFFFF) for a, b in host_i64.tolist()]
+
+    def digest(self, tensor_or_name):
+        """(out[0], out[1]) of a state tensor's name or of any contiguous device tensor whose byte count is a multiple of 4;
+        synchronises."""
+        t = self.state_tensors()[tensor_or_name] if isinstance(tensor_or_name, str) else tensor_or_name
+        out = torch.empty(2, dtype=torch.int64, device=self.device)
+        self.digest_into(t, out)
+        return self._digest_pairs(out.cpu().reshape(1, 2))[0]
+
+    def digests(self):
+        """{name: (out[0], out[1])} of every state tensor, in state_tensors() order, in one read; synchronises."""
+        st = self.state_tensors()
+        out = torch.empty((len(st), 2), dtype=torch.int64, device=self.device)
+        for i, t in enumerate(st.values()):
+            self.digest_into(t, out[i])
+        return dict(zip(st, self._digest_pairs(out.cpu())))
+
+    def set_step_count(self, n):
+        """The number of optimizer steps taken (a restored run): the next step is n + 1 for the schedule, the noise, the dropout,
+        the contrast's candidates and the weight average."""
+        if isinstance(n, bool) or int(n) != n or n < 0:
+            raise HipError("set_step_count: expected a count >= 0, got %r" % (n,))
+        self.step_count = int(n)

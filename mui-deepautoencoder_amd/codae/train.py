@@ -389,6 +389,27 @@ class DataParallel:
             sa, sb = self._shard_bounds(lo, hi)
             self.dist.all_gather_into_tensor(p[a:b], p[sa:sb].clone(), group=self.group)
 
+    def replicas_agree(self):
+        """Collective: whether every rank holds rank 0's state, bit for bit - the per-tensor state digests (16 bytes each, computed
+        on the device: include/codae_hip.h, "State digest") are all-gathered and compared; the same answer on every rank.  A check
+        against silent divergence that moves no tensor to the host.  The scalars vector is left out: it holds each rank's own partial
+        epoch sums and the loss of its own shard.  Refused with the sharded update, whose moments live in shards."""
+        if self.sharded:
+            raise HipError("replicas_agree(): the sharded update is not supported: the moments of a rank live in its shards")
+        eng = self.engine
+        with torch.cuda.device(eng.device):
+            st = {n: t for n, t in eng.state_tensors().items() if n != "scalars"}
+            mine = torch.empty((len(st), 2), dtype=torch.int64, device=eng.device)
+            for i, t in enumerate(st.values()):
+                eng.digest_into(t, mine[i])
+        if self.world == 1:
+            return True
+        if self.dist.get_backend(self.group) != "nccl":
+            mine = mine.cpu()                  # (gloo, the CPU test backend)
+        every = [torch.empty_like(mine) for _ in range(self.world)]
+        self.dist.all_gather(every, mine, group=self.group)
+        return all(bool(torch.equal(every[0], e)) for e in every[1:])
+
     def broadcast_params(self, params_flat):
         if self.world > 1:
             self.dist.broadcast(params_flat, src=0, group=self.group)
@@ -850,3 +871,256 @@ class HipEmbeddingTrainer:
     def last_loss_and_grad_norm(self):
         _, _, gsq, loss = self.engine.read_scalars()
         return loss, gsq ** 0.5
+
+    # ---- checkpoint and resume (include/codae_hip.h, "State digest"; codae/tool/checkpoint.py) --------------------------------------
+    def _refuse_sharded(self, who):
+        if self.dp is not None and self.dp.sharded:
+            raise HipError("%s: the sharded update is not supported: the moments of a rank live in its shards" % who)
+
+    def _state_meta(self):
+        """What the file records beside the tensors: the structure load() checks, and the training options for information."""
+        eng = self.engine
+        opt, avg = eng.optimizer, eng.weight_average
+        return {
+            "step_count": int(eng.step_count),
+            "schedule": [[k, n, bool(r)] for k, n, r in eng.schedule],
+            "n_param": int(eng.n_param),
+            "precision": "bf16" if eng.precision == 1 else "f32",
+            "activation": None if eng.activation is None else [list(a) for a in eng.activation],
+            "tied_weights": bool(eng.tied_weights),
+            "optimizer": "adam" if opt is None else opt.kind,
+            "amsgrad": bool(opt is not None and opt.amsgrad),
+            "weight_average": None if avg is None or avg.is_default else
+            {"kind": avg.kind, "decay": avg.decay, "debias": avg.debias, "start": avg.start, "every": avg.every},
+            "optional": [n for n in ("adam_vmax", "weight_avg") if getattr(eng, n) is not None],
+            "lr": float(self.lr), "weight_decay": float(self.weight_decay), "clip": float(self.clip or 0.0),
+            # construction options of the trainer that wrote the file: load() does not read them
+            "options": {n: (None if getattr(eng, n) is None else repr(getattr(eng, n)))
+                        for n in ("input_noise", "loss_emphasis", "hidden_dropout", "recon_loss", "slot_contrast", "optimizer",
+                                  "slot_presence")},
+        }
+
+    def snapshot(self):
+        """Freeze the state as it is behind the steps enqueued so far, without blocking the host: on the current stream, behind
+        engine.join(), one codae_state_digest(src, staging) per state tensor - one pass that fingerprints it and copies it to a device
+        staging buffer -, then on a side stream the copies into pinned host buffers and an event.  Steps enqueued afterwards overlap
+        the device-to-host copy.  -> a Snapshot: write(path) waits for the event and writes the file, release() drops it.  The staging
+        set is allocated on first use and kept; there is one, so a second snapshot() while one is neither written nor released is
+        refused (HipError).  Data parallel: every rank may take one; save() writes on rank 0 only."""
+        self._refuse_sharded("snapshot()")
+        if getattr(self, "_snap_live", None) is not None:
+            raise HipError("snapshot(): the previous snapshot is neither written nor released (there is one staging set)")
+        eng = self.engine
+        with torch.cuda.device(self.device):
+            st = eng.state_tensors()                     # (joins the engine's side stream into the current one)
+            sig = tuple((n, t.dtype, t.numel()) for n, t in st.items())
+            if getattr(self, "_snap_sig", None) != sig:
+                self._snap_dev = {n: torch.empty_like(t) for n, t in st.items()}
+                self._snap_host = {n: torch.empty(t.numel(), dtype=t.dtype).pin_memory() for n, t in st.items()}
+                self._snap_dig = torch.zeros((len(st), 2), dtype=torch.int64, device=self.device)
+                self._snap_dig_host = torch.zeros((len(st), 2), dtype=torch.int64).pin_memory()
+                self._snap_stream = torch.cuda.Stream(device=self.device)
+                self._snap_event = torch.cuda.Event()
+                self._snap_sig = sig
+            else:
+                # a released snapshot's copies may still be reading the staging buffers
+                torch.cuda.current_stream(self.device).wait_event(self._snap_event)
+            for i, (n, t) in enumerate(st.items()):
+                eng.digest_into(t, self._snap_dig[i], dst=self._snap_dev[n])
+            self._snap_stream.wait_stream(torch.cuda.current_stream(self.device))
+            with torch.cuda.stream(self._snap_stream):
+                for n in st:
+                    self._snap_host[n].copy_(self._snap_dev[n], non_blocking=True)
+                self._snap_dig_host.copy_(self._snap_dig, non_blocking=True)
+                self._snap_event.record(self._snap_stream)
+        self._snap_live = Snapshot(self, list(st), self._state_meta())
+        return self._snap_live
+
+    def save(self, path, extra=None):
+        """snapshot().write(path): the file of codae/tool/checkpoint.py.  Data parallel: a collective every rank calls; rank 0 writes,
+        every other rank returns None (the replicas hold the same state: DataParallel.replicas_agree()).  The two running epoch sums
+        of the scalars are each rank's own partial sums: the file gets their sum over the ranks, and load() gives it to rank 0 alone,
+        so epoch_sums() goes on as in the run that was not interrupted.  -> bytes written."""
+        self._refuse_sharded("save()")
+        sums = None
+        if self.dp is not None and self.dp.world > 1:
+            sums = self.dp.reduce_scalars(self.engine.scalars[:2].clone()).cpu()
+            if self.dp.rank != 0:
+                return None
+        return self.snapshot().write(path, extra=extra, metric_sums=sums)
+
+    def state_digest(self):
+        """{name: (out0, out1)} of every state tensor, computed on the device, and "all": the digest of the concatenated little-endian
+        per-tensor digests in that order.  Synchronises."""
+        from .tool.checkpoint import StateDigest
+        with torch.cuda.device(self.device):
+            d = self.engine.digests()
+        d["all"] = StateDigest.combine(d.values())
+        return d
+
+    def _check_structure(self, path, tensors, meta, strict, need=("params", "adam_m", "adam_v", "scalars")):
+        eng = self.engine
+
+        def refuse(piece, what):
+            raise HipError("load(%s): %s: %s" % (path, piece, what))
+        if [list(x) for x in meta.get("schedule", [])] != [[k, n, bool(r)] for k, n, r in eng.schedule]:
+            refuse("schedule", "the file was written for %r, this trainer runs %r" % (meta.get("schedule"), eng.schedule))
+        if bool(meta.get("tied_weights")) != bool(eng.tied_weights):
+            refuse("tied_weights", "the file was written with tied weights %s, this trainer has them %s"
+                   % ("on" if meta.get("tied_weights") else "off", "on" if eng.tied_weights else "off"))
+        live = eng.state_tensors()
+        for n in need:
+            if n not in tensors:
+                refuse(n, "the file does not hold it")
+        for n, t in tensors.items():
+            if n in live and (t.size != live[n].numel() or "torch." + t.dtype.name != str(live[n].dtype)):
+                refuse(n, "the file holds %d x %s, this trainer %d x %s" % (t.size, t.dtype, live[n].numel(), live[n].dtype))
+            if n not in meta.get("digests", {}):
+                refuse(n, "'meta' records no digest for it")
+        if "adam_vmax" in need or (eng.optimizer is not None and eng.optimizer.amsgrad and "adam_m" in need):
+            if "adam_vmax" not in tensors:
+                refuse("adam_vmax", "AMSGrad is on and the file does not hold its running maximum")
+        if strict and eng.averaging() and "adam_m" in need and "weight_avg" not in tensors:
+            refuse("weight_avg", "weight averaging is on and the file holds no average (strict=False starts it from the parameters)")
+        if strict and "adam_m" in need:
+            prec = "bf16" if eng.precision == 1 else "f32"
+            if meta.get("precision") != prec:
+                refuse("precision", "the file was written by a %s engine, this one is %s" % (meta.get("precision"), prec))
+            act = None if eng.activation is None else [list(a) for a in eng.activation]
+            if meta.get("activation") != act:
+                refuse("activation", "the file was written with %r, this trainer runs %r" % (meta.get("activation"), act))
+
+    def _upload_verified(self, path, tensors, meta, names):
+        """Upload the named tensors into temporaries, digest each ON THE DEVICE and compare with `meta`: -> {name: device tensor}, or
+        HipError naming the first tensor that differs (nothing is kept)."""
+        from .tool.checkpoint import StateDigest
+        eng = self.engine
+        with torch.cuda.device(self.device):
+            tmp = {n: torch.from_numpy(tensors[n].reshape(-1)).to(self.device) for n in names}
+            out = torch.empty((len(names), 2), dtype=torch.int64, device=self.device)
+            for i, n in enumerate(names):
+                eng.digest_into(tmp[n], out[i])
+            got = eng._digest_pairs(out.cpu())
+        for n, d in zip(names, got):
+            if StateDigest.hex(d) != meta["digests"][n]:
+                raise HipError("load(%s): tensor '%s' has digest %s on the device, the file recorded %s"
+                               % (path, n, StateDigest.hex(d), meta["digests"][n]))
+        return tmp
+
+    def load(self, path, strict=True):
+        """Restore the state save() wrote, so that the next step is bit for bit the step the writing run took next.  Structure first
+        (HipError naming the piece; the trainer stays as it was): the schedule and parameter count, tied weights on in one and off in
+        the other, adam_vmax missing while AMSGrad is on; under `strict` also an average missing while averaging is on, another
+        precision or activation, and optional tensors this trainer does not keep.  Then every tensor is uploaded into a temporary,
+        digested on the device and compared with the file's record (HipError naming the tensor; nothing is kept), and only then
+        copied over the live state.  On success: step_count is set, the scalars are the file's, the bf16 shadows are rebuilt
+        (sync_shadows) and the average's images marked stale; the average is NOT reset.  Training options (noise, emphasis, criterion,
+        contrast, dropout, presence, optimizer) belong to this trainer's construction, not to the file.  Data parallel: every rank
+        reads the file.  -> the file's `meta`."""
+        from .tool.checkpoint import CheckpointError, read_checkpoint
+        self._refuse_sharded("load()")
+        try:
+            tensors, meta = read_checkpoint(path, verify=False)
+        except CheckpointError as e:
+            raise HipError(str(e))
+        eng = self.engine
+        self._check_structure(path, tensors, meta, strict)
+        live = eng.state_tensors()
+        if strict:
+            for n in tensors:
+                if n not in live:
+                    raise HipError("load(%s): %s: the file holds it and this trainer does not keep it (strict=False ignores it)" % (path, n))
+        names = [n for n in live if n in tensors]
+        tmp = self._upload_verified(path, tensors, meta, names)
+        with torch.no_grad():
+            for n in names:
+                live[n].copy_(tmp[n])
+            if "weight_avg" in live and "weight_avg" not in tensors:
+                live["weight_avg"].copy_(live["params"])
+            if self.dp is not None and self.dp.world > 1 and self.dp.rank != 0:
+                eng.scalars[:2].zero_()                    # (the file's epoch sums are the sum over the ranks: rank 0 carries them)
+        eng.set_step_count(int(meta["step_count"]))
+        eng.sync_shadows()
+        eng._avg_stale = True
+        return meta
+
+    @classmethod
+    def load_for_inference(cls, path, data, mask_table_u8=None, mask_to_use_i32=None, n_slots=None, max_batch=8192, device="cuda:0",
+                           presence=None):
+        """A trainer built from the file's own record (schedule, precision, activation, tied weights, the kind of average) over
+        `data`, holding the file's parameters and - when it has one - weight average, each verified on the device as load() does:
+        eval_batch, complete*, score_outfits and the metrics give what the writing process gave.  The moments are neither read nor
+        required (a file stripped of them loads)."""
+        from .tool.average import WeightAverage
+        from .tool.checkpoint import CheckpointError, read_checkpoint
+        try:
+            tensors, meta = read_checkpoint(path, verify=False)
+        except CheckpointError as e:
+            raise HipError(str(e))
+        act = meta.get("activation")
+        tr = cls([tuple(x) for x in meta["schedule"]], data, mask_table_u8, mask_to_use_i32, meta.get("lr", 0.0), meta.get("weight_decay", 0.0),
+                 clip=meta.get("clip", 0.0), max_batch=max_batch, precision=meta.get("precision", "bf16"), device=device,
+                 activation=None if act is None else [tuple(a) for a in act], n_slots=n_slots, presence=presence,
+                 tied_weights=bool(meta.get("tied_weights")))
+        eng = tr.engine
+        names = ["params"]
+        wa = meta.get("weight_average")
+        if "weight_avg" in tensors:
+            eng.set_weight_average(WeightAverage(**wa) if wa else WeightAverage())
+            names.append("weight_avg")
+        tr._check_structure(path, tensors, meta, False, need=("params",))
+        tmp = tr._upload_verified(path, tensors, meta, names)
+        live = eng.state_tensors()
+        with torch.no_grad():
+            for n in names:
+                live[n].copy_(tmp[n])
+        eng.set_step_count(int(meta["step_count"]))
+        eng.sync_shadows()
+        eng._avg_stale = True
+        return tr
+
+
+class Snapshot:
+    """The state of a HipEmbeddingTrainer at one point of its stream, on its way to pinned host memory (HipEmbeddingTrainer.snapshot).
+    write(path) waits for the copies and writes the checkpoint file; release() drops it.  Either frees the trainer's staging set."""
+
+    def __init__(self, trainer, names, meta):
+        self._trainer, self._names, self.meta = trainer, names, meta
+
+    def _live(self):
+        if self._trainer is None or self._trainer._snap_live is not self:
+            raise HipError("Snapshot: already written or released")
+
+    def wait(self):
+        """Block until the copies have landed (write() does)."""
+        self._live()
+        self._trainer._snap_event.synchronize()
+
+    def digests(self):
+        """{name: (out0, out1)} as the device computed them while copying; waits for the copies."""
+        self.wait()
+        from .hip.engine import DaeEngine
+        return dict(zip(self._names, DaeEngine._digest_pairs(self._trainer._snap_dig_host)))
+
+    def write(self, path, extra=None, metric_sums=None):
+        """-> bytes written.  extra: a JSON-serialisable dict of the caller's, kept in meta["extra"].  metric_sums: two float64 that
+        replace the running epoch sums in the file's scalars (save() on data-parallel replicas: the sum over the ranks)."""
+        from .tool.checkpoint import StateDigest, write_checkpoint
+        dig = self.digests()
+        tr = self._trainer
+        if metric_sums is not None:
+            tr._snap_host["scalars"][:2] = torch.as_tensor(metric_sums, dtype=torch.float64)
+            dig["scalars"] = StateDigest.get(tr._snap_host["scalars"].numpy())
+        meta = dict(self.meta)
+        meta["digests"] = {n: StateDigest.hex(d) for n, d in dig.items()}
+        meta["all"] = StateDigest.hex(StateDigest.combine(dig.values()))
+        meta["extra"] = {} if extra is None else extra
+        try:
+            return write_checkpoint(path, {n: tr._snap_host[n].numpy() for n in self._names}, meta)
+        finally:
+            self.release()
+
+    def release(self):
+        tr, self._trainer = self._trainer, None
+        if tr is not None and tr._snap_live is self:
+            tr._snap_live = None

@@ -7,6 +7,10 @@ script/train_dae_on_embedding.py (--embedding_path --output_path --config [--deb
 minibatch over the HBM-resident dataset (codae.train.HipEmbeddingTrainer) instead of
 DataLoader + per-sample mask loop + autograd + per-step host copies.
 
+Checkpoints: `HIP: CHECKPOINT: {EVERY: 1, KEEP: 2, DIR: <the run's output directory>}` writes checkpoint_epoch<k>.npz after every
+EVERY-th epoch's validation sweep and keeps the newest KEEP; --resume PATH continues such a file's run at its next epoch, bit for bit
+the run that was never interrupted (codae.train.HipEmbeddingTrainer.save / load).
+
 Extra flags: --precision {bf16,f32} (default: HIP.PRECISION of the config, else bf16; widths the
 bf16 tiles cannot take fall back to the exact-fp32 kernels), --epochs N (override MODEL.EPOCH).
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N`; each rank takes
@@ -44,6 +48,7 @@ def parse():
     p.add_argument('--nb_missing', type=int, default=1)
     p.add_argument('--precision', type=str, default=None, choices=[None, "bf16", "f32"])
     p.add_argument('--epochs', type=int, default=None)
+    p.add_argument('--resume', type=str, default=None)
     return p.parse_args()
 
 
@@ -91,6 +96,17 @@ def main():
         np.random.seed(config["SEED"])
         np.random.shuffle(indices)
     train_indices, validation_indices = indices[:nb_train], indices[nb_train:]
+    # --resume: the split and (below) the mask table are the interrupted run's: this script seeds neither in a single process
+    resumed = None
+    if args.resume is not None:
+        from codae.tool.checkpoint import read_checkpoint
+        resumed = read_checkpoint(args.resume)[1]["extra"]
+        if "epoch" not in resumed or "rng" not in resumed:
+            raise HipError("--resume %s: not an epoch-boundary checkpoint of this script" % args.resume)
+        train_indices, validation_indices = list(resumed["train_indices"]), list(resumed["validation_indices"])
+        if len(train_indices) != nb_train or len(validation_indices) != nb_validation:
+            raise HipError("--resume %s: the file's split is %d + %d rows, this dataset and config give %d + %d"
+                           % (args.resume, len(train_indices), len(validation_indices), nb_train, nb_validation))
     train_sampler = SubsetEpochSampler(train_indices, mc["BATCH_SIZE"])
     validation_sampler = SubsetEpochSampler(validation_indices, mc["BATCH_SIZE"])
 
@@ -98,6 +114,13 @@ def main():
     c = list(range(len(dc["USED_CATEGORY"])))
     [random.sample(c, len(c)) for _ in range(dataset.nb_observation)]
     corrupter = Corrupter(nb_observation=dataset.nb_observation, arch=dataset.arch, k_max=args.nb_missing, device=device)
+    if resumed is not None:
+        table = torch.tensor(resumed["mask_to_use"], dtype=torch.long)
+        if table.shape != corrupter.mask_to_use.shape:
+            raise HipError("--resume %s: the file's mask table is %s, this run's %s" % (args.resume, tuple(table.shape),
+                                                                                      tuple(corrupter.mask_to_use.shape)))
+        corrupter.mask_to_use = table
+        corrupter.mask_to_use_i32 = table.to(torch.int32).contiguous().to(device)
 
     presence, mask_to_use = None, corrupter.mask_to_use_i32
     if keep_incomplete:
@@ -229,7 +252,57 @@ def main():
     if compat is not None:
         book.update({k: [] for k in ("auc", "paired_acc", "scored_outfits")})
 
-    for epoch in range(epochs):
+    # HIP: CHECKPOINT: {EVERY: 1, KEEP: 2, DIR: ...} (build-only key): a checkpoint file after every EVERY-th epoch's validation sweep,
+    # the newest KEEP kept; absent (and no --resume) = nothing is logged, written or drawn differently
+    ck = config.get("HIP", {}).get("CHECKPOINT")
+    ck_every = ck_keep = 0
+    if ck is not None:
+        unknown = set(ck) - {"EVERY", "KEEP", "DIR"}
+        if unknown:
+            raise HipError("HIP: CHECKPOINT: unknown keys %s" % sorted(unknown))
+        ck_every, ck_keep = int(ck.get("EVERY", 1)), int(ck.get("KEEP", 2))
+        if ck_every < 1 or ck_keep < 1:
+            raise HipError("HIP: CHECKPOINT: EVERY and KEEP must be at least 1, got %d and %d" % (ck_every, ck_keep))
+    run_dir = []
+
+    def out_dir():
+        if not run_dir:
+            run_dir.append(os.path.join(args.output_path, get_date() + "_train_" + dc["NAME"]))
+            os.makedirs(run_dir[0], exist_ok=True)
+        return run_dir[0]
+
+    from codae.tool.checkpoint import StateDigest
+    data_digest = StateDigest.hex(trainer.engine.digest(trainer.data)) if (ck is not None or resumed is not None) else None
+    first_epoch = 0
+    if resumed is not None:
+        if resumed["dataset_digest"] != data_digest:
+            raise HipError("--resume %s: the file was written over a dataset with digest %s, this run's dataset has %s"
+                           % (args.resume, resumed["dataset_digest"], data_digest))
+        trainer.load(args.resume)
+        for k, v in resumed["book"].items():
+            book[k] = list(v)
+        first_epoch = int(resumed["epoch"])
+        rng = resumed["rng"]
+        torch.set_rng_state(torch.tensor(rng["torch"], dtype=torch.uint8))
+        np.random.set_state((rng["numpy"][0], np.asarray(rng["numpy"][1], dtype=np.uint32), rng["numpy"][2], rng["numpy"][3], rng["numpy"][4]))
+        random.setstate((rng["python"][0], tuple(rng["python"][1]), rng["python"][2]))
+        log.info("RESUMED %s: %d epochs done, state digest %s" % (args.resume, first_epoch, StateDigest.hex(trainer.state_digest()["all"])))
+    pending, written = [], []
+
+    def write_pending():
+        # the file write hides behind the device work enqueued since the snapshot
+        while pending:
+            snap, path, extra = pending.pop()
+            all_digest = StateDigest.hex(StateDigest.combine(snap.digests().values()))
+            nbytes = snap.write(path, extra=extra)
+            log.info("CHECKPOINT %s: %d bytes, state digest %s" % (path, nbytes, all_digest))
+            written.append(path)
+            while len(written) > ck_keep:
+                old = written.pop(0)
+                if os.path.exists(old):
+                    os.remove(old)
+
+    for epoch in range(first_epoch, epochs):
         log.info("===================================================== EPOCH = %d" % epoch)
         if optimizer is not None:
             log.info("LEARNING RATE            = %.6g" % trainer.current_lr())
@@ -240,6 +313,8 @@ def main():
                 log.info("skipping a global batch of %d rows on %d ranks" % (nb_skipped, world))
                 continue
             trainer.train_batch(shard.contiguous(), run=0, global_rows=len(batch_indices))
+            if pending:
+                write_pending()
         sq, sqp = trainer.epoch_sums()
         book["ftl"].append(np.sqrt(sq / den["train"][0]))
         book["ptl"].append(np.sqrt(sqp / den["train"][1]))
@@ -286,14 +361,27 @@ def main():
             log.info("VALIDATION COMPATIBILITY AUC = %7f" % cm["auc"])
             log.info("VALIDATION PAIRED ACCURACY   = %7f" % cm["paired_acc"])
             log.info("VALIDATION SCORED OUTFITS    = %d" % cm["outfits"])
+        write_pending()                  # (an epoch that trained no batch)
+        if ck is not None and rank == 0 and (epoch + 1) % ck_every == 0:
+            # two phases: the snapshot here, at the epoch boundary; the file once the next epoch's first batch is enqueued (or at exit)
+            np_state, py_state = np.random.get_state(), random.getstate()
+            extra = {"epoch": epoch + 1, "book": {k: [float(v) for v in vs] for k, vs in book.items()},
+                     "train_indices": [int(i) for i in train_indices], "validation_indices": [int(i) for i in validation_indices],
+                     "mask_to_use": corrupter.mask_to_use.tolist(), "dataset_digest": data_digest,
+                     "rng": {"torch": torch.get_rng_state().tolist(),
+                             "numpy": [np_state[0], np_state[1].tolist(), int(np_state[2]), int(np_state[3]), float(np_state[4])],
+                             "python": [py_state[0], list(py_state[1]), py_state[2]]}}
+            ck_dir = ck.get("DIR") or out_dir()
+            os.makedirs(ck_dir, exist_ok=True)
+            pending.append((trainer.snapshot(), os.path.join(ck_dir, "checkpoint_epoch%d.npz" % (epoch + 1)), extra))
+    write_pending()
     log.info("TRAINING HAS ENDED.")
 
     if rank == 0:
         import matplotlib
         matplotlib.use('agg')
         import matplotlib.pyplot as plt
-        d = os.path.join(args.output_path, get_date() + "_train_" + dc["NAME"])
-        os.makedirs(d, exist_ok=True)
+        d = out_dir()
         axis = np.arange(0, epochs)
         for name, a, b, extra in (("full_RMSE", "ftl", "fvl", None), ("partial_RMSE", "ptl", "pvl", float(dataset_std))):
             plt.plot(axis, book[a], label="Training")
