@@ -76,6 +76,9 @@ extern "C" {
  *      (still 11) + CODAE_NOISE_SWAP, codae_swap, codae_set_swap_pool, codae_corrupt_batch_swap, codae_emph_loss_swap,
  *      codae_recon_loss_fwd_bwd_swap: a new noise kind and new entries only, codae_noise keeps its layout, no existing enum value
  *      changes; the swap gathers are booked under CODAE_K_GATHER
+ *      (still 11) + codae_residual, codae_residual_ws_bytes, codae_set_residual, codae_residual_fwd, codae_residual_bwd,
+ *      codae_residual_blocks: new entries only, no layout or enum change; the two kernels are booked under CODAE_K_DROPOUT, the
+ *      class of the streaming kernels between a step's GEMMs
  * The binding must refuse a library whose codae_abi_version() differs and must check its own struct sizes against
  * codae_struct_sizes() at load (mui-deepautoencoder_amd/codae/hip/__init__.py does both). */
 #define CODAE_ABI_VERSION 11
@@ -348,6 +351,36 @@ typedef struct {
     int32_t n;
     uint64_t seed;
 } codae_dropout;
+
+/* Residual connections: an identity skip around a hidden layer of equal widths (He et al. 2016); no parameters, no projection.
+ * Layers are l = 0 .. L-1, h_0 is the corrupted input, skip_l in {0, 1}:
+ *   z_l = W_l h_l + b_l          a_l = act_l(z_l)   (times the dropout factor f_l when layer l is dropped)
+ *   h_{l+1} = a_l + skip_l h_l                       loss on h_L
+ * Backward, with G_l = dL/dh_l and D_l = dL/dz_l (what dA_l holds, read by the weight and the data gradient of layer l):
+ *   U_l = W_l^T D_l                                  (the data-gradient GEMM of layer l, UNMASKED)
+ *   G_l = U_l + skip_l G_{l+1}
+ *   D_{l-1} = G_l * act'_{l-1} (* f_{l-1})           db_{l-1} = column sums of D_{l-1} over rows < B
+ * skip_l = 1 is accepted only where in[l] == out[l], l <= L-2 and act_l is CODAE_ACT_NONE, RELU or LEAKY.  The last layer never
+ * has a skip: its output is the reconstruction.  Other activations are excluded because the derivative is taken from the saved
+ * output, and once h_l is added that output no longer determines it.
+ * It is part of the MODEL: every forward adds the skips - the training steps, codae_eval_step, codae_forward over the whole stack,
+ * codae_score_outfits, and whatever buffer set (the weight average's) the call is given.
+ * Forward, behind the GEMM of a skipped layer l and behind its dropout kernel: act[l + 1] <- rne(float(act[l + 1]) + float(act[l]))
+ * in place, one fp32 add, rounded to the working type.  A TRAINING forward first writes the 1-bit mask of a_l the backward needs
+ * (act[l + 1] afterwards holds h_{l+1}, from which the sign of a_l cannot be recovered): one bit per element, 8 columns per byte,
+ * column 8 j + k in bit k of byte j, set iff the stored a_l has its sign clear and is not zero - the predicate and the layout of the
+ * forward GEMM's 1-bit ReLU masks, so a NaN with a clear sign counts as positive.  Layers with CODAE_ACT_NONE need no mask.
+ * Backward, behind the data-gradient GEMM of layer l iff skip_l or skip_{l-1}: that GEMM runs unmasked and leaves U_l in dA_{l-1}
+ * in working precision; the kernel reads G_{l+1} (iff skip_l), adds in fp32, stores G_l (iff skip_{l-1}), forms D_{l-1} = G_l where
+ * the bit is set, else 0 (RELU) or G_l slope (LEAKY), stores it over U_l in working precision and leaves the column sums of the
+ * STORED values as layer l-1's partial bias-gradient rows (fixed order, no atomics).  When skip_{l-1} = 0 the derivative of layer
+ * l-1 comes from the saved activation act[l], as the GEMM epilogue takes it.  Dropout's backward kernel then scales D_{l-1} and
+ * rewrites the rows.  G is kept in fp32 in one [rows][width] buffer of the work space, updated in place: it is a sum of up to
+ * L-2 terms, and in the bf16 engine every U_l already arrives rounded once.  Every other data gradient runs masked as always. */
+typedef struct {
+    int32_t n;            /* == n_layers */
+    const uint8_t* on;    /* HOST array [n]: on[l] != 0 = a skip around layer l; copied by the setter */
+} codae_residual;
 
 /* Optimizer and schedule: what the update at the end of every training step does with the clipped gradient; the default is the line
  * the reference script hard-wires, clip_grad_norm_ + torch.optim.Adam with L2 decay, AMSGrad off and a constant lr.
@@ -734,6 +767,21 @@ int codae_set_recon_loss(codae_handle h, const codae_recon_loss* loss);
  * The backward entry points take no batch: a training forward records batch->row_idx and hyper->step in the handle, so
  * batch->row_idx must stay valid until the backward of that step has been issued. */
 int codae_set_hidden_dropout(codae_handle h, const codae_dropout* d);
+/* Residual connections ("Residual connections" above) of every call that follows - training steps in every step form AND every
+ * evaluation forward; a change re-captures the graph.  NULL, or an all-zero `on`, switches them off: the engine then runs exactly
+ * the launches it ran before, bit for bit, codae_step_path included, and ws may be NULL.  CODAE_E_INVALID for n != n_layers, a
+ * null `on`, a ws that is NULL, not 16-byte aligned or smaller than codae_residual_ws_bytes says; CODAE_E_UNSUPPORTED for a skip
+ * around the last layer, around a layer of unequal widths or around one whose activation is RELU6, ELU, SOFTPLUS or HARDSIGMOID (the
+ * message names the layer and the reason).  On any error nothing is launched and the previous setting stays.  ws is borrowed until
+ * the setting is replaced; it holds G and the mask bits, its contents need not be zero, and codae_sizes / codae_buffers do not
+ * change.  codae_residual_ws_bytes: the bytes needed (0 when off), or -1 with the same errors.
+ * While skips are on: one stand-alone kernel behind the forward GEMM of every skipped layer and one behind the data-gradient GEMM of
+ * every layer l with skip_l or skip_{l-1} (class CODAE_K_DROPOUT), the stack stays off the persistent chain kernel (codae_step_path
+ * reports 0), and nothing else of the step plan changes (fused loss, grouped weight gradients, two streams, the backward by ranges -
+ * G lives in ws between the range calls).  codae_backward, and codae_forward over a partial layer range, return
+ * CODAE_E_UNSUPPORTED.  A step backward needs a training forward before it: only that writes the masks. */
+int64_t codae_residual_ws_bytes(codae_handle h, const codae_residual* r);
+int codae_set_residual(codae_handle h, const codae_residual* r, void* ws, int64_t ws_bytes);
 /* Slot contrast of every training step that follows (the step forms codae_set_input_noise lists; a change re-captures the graph;
  * under replay the step index is read from scalars[CODAE_S_ADAM_STEP]).  NULL or weight == 0 switches it off: the engine then runs
  * exactly what it ran before, bit for bit, codae_step_path included.  CODAE_E_INVALID for n_neg outside [1, 4096], a tau that is
@@ -805,7 +853,8 @@ enum {
     CODAE_K_SLAB_REDUCE = 7,
     CODAE_K_CHAIN = 8,       /* narrow stacks: gather + forward chain + loss + data-gradient chain in one launch */
     CODAE_K_BIAS_FINISH = 9, /* partial column sums -> bias gradients (+ their share of sum g^2) */
-    CODAE_K_DROPOUT = 10,    /* hidden dropout: the factor on a layer's output / on its activation gradient (+ its column sums) */
+    CODAE_K_DROPOUT = 10,    /* streaming kernels between a step's GEMMs - hidden dropout: the factor on a layer's output / on its
+                              * activation gradient (+ its column sums); residual connections: the skip add, and G + the derivative */
     CODAE_K_COUNT = 11
 };
 /* Start recording a hipEvent pair around every launch whose class bit is set in class_mask
@@ -915,6 +964,23 @@ int codae_dropout_fwd(void* a, int32_t bf16, int64_t ld, int32_t B, int32_t widt
 int codae_dropout_bwd(void* d, int32_t bf16, int64_t ld, int32_t B, int32_t width, const int32_t* row_idx, int32_t layer,
                       int32_t step, float p, uint64_t seed, float* colsum_part, void* stream);
 int codae_dropout_blocks(int32_t B);     /* part rows codae_dropout_bwd writes: one per 64 batch rows */
+/* The two residual kernels on their own (the launchers the engine uses; "Residual connections" above has the definition), on rows
+ * < B and columns < width of [B][ld] matrices, fp32 or (bf16 != 0) bf16; pad columns and pad rows are never written.  16-byte
+ * accesses where every base address, every ld and the width allow (bf16 x 8, fp32 x 4), element accesses otherwise.
+ * forward: y <- rne(y + x) in place; bits != NULL: first bits[b][j] <- the mask byte of columns 8 j .. 8 j + 7 of the y it read
+ * (bits past the width clear), rows ld_bits >= ceil(width / 8) bytes apart.
+ * backward: U = d; G = U + g_in (one fp32 add; g_in may be NULL); g_out <- G (may be NULL, may be g_in; rows ld_g floats apart);
+ * d <- D rounded to the working type, D = G times the derivative, which comes from `bits` (act_kind CODAE_ACT_RELU: G or 0,
+ * CODAE_ACT_LEAKY: G or G act_param[0]), from the saved activation `src` ([B][ld_src] in working precision, any CODAE_ACT_* kind
+ * with its three act_param; RELU selects by the mask predicate) or is 1 (both NULL); not both.  One block per 64 batch rows -
+ * codae_residual_blocks(B) of them - and each leaves one row of colsum_part [blocks][width] (column sums of the STORED D widened
+ * to fp32; may be NULL) with plain stores added in a fixed order: the same inputs give the same bits. */
+int codae_residual_fwd(void* y, const void* x, int32_t bf16, int64_t ldy, int64_t ldx, int32_t B, int32_t width, uint8_t* bits,
+                       int64_t ld_bits, void* stream);
+int codae_residual_bwd(void* d, int32_t bf16, int64_t ld, int32_t B, int32_t width, const float* g_in, float* g_out, int64_t ld_g,
+                       const uint8_t* bits, int64_t ld_bits, const void* src, int64_t ld_src, int32_t act_kind, const float* act_param,
+                       float* colsum_part, void* stream);
+int codae_residual_blocks(int32_t B);    /* part rows codae_residual_bwd writes: one per 64 batch rows */
 /* The Gaussian kind's device arithmetic on given words (tools/noise_accuracy.py sweeps all 2^24 values of u1 and of u2 through
  * it): rho[i] = sqrt(-2 ln u1(ra[i])), c[i] = cos(2 pi u2(rb[i])), s[i] = sin(2 pi u2(rb[i])); the unit normals of a pair are
  * rho c and rho s. */

@@ -123,6 +123,11 @@ class Dropout(C.Structure):
     _fields_ = [("p", C.POINTER(C.c_float)), ("n", C.c_int32), ("seed", C.c_uint64)]
 
 
+class ResidualFlags(C.Structure):
+    """codae_residual: n == n_layers, on[l] != 0 = a skip around layer l (a host array the setter copies)"""
+    _fields_ = [("n", C.c_int32), ("on", C.POINTER(C.c_uint8))]
+
+
 _P, _I32, _I64, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
 # name -> (restype, argtypes); mirrors include/codae_hip.h one to one
@@ -188,6 +193,11 @@ PROTOTYPES = {
     "codae_dropout_fwd": (C.c_int, [_P, _I32, _I64, _I32, _I32, _P, _I32, _I32, _F, C.c_uint64, _P]),
     "codae_dropout_bwd": (C.c_int, [_P, _I32, _I64, _I32, _I32, _P, _I32, _I32, _F, C.c_uint64, _P, _P]),
     "codae_dropout_blocks": (C.c_int, [_I32]),
+    "codae_residual_ws_bytes": (_I64, [_P, C.POINTER(ResidualFlags)]),
+    "codae_set_residual": (C.c_int, [_P, C.POINTER(ResidualFlags), _P, _I64]),
+    "codae_residual_fwd": (C.c_int, [_P, _P, _I32, _I64, _I64, _I32, _I32, _P, _I64, _P]),
+    "codae_residual_bwd": (C.c_int, [_P, _I32, _I64, _I32, _I32, _P, _P, _I64, _P, _I64, _P, _I64, _I32, _P, _P, _P]),
+    "codae_residual_blocks": (C.c_int, [_I32]),
     "codae_emph_loss": (C.c_int, [C.POINTER(Batch), C.POINTER(Noise), _I32, C.POINTER(Emphasis), _P, _P, _I32, _I64, _F, _P, _P, _P]),
     "codae_emph_loss_blocks": (C.c_int, [_I32]),
     "codae_recon_loss_fwd_bwd": (C.c_int, [C.POINTER(Batch), C.POINTER(Noise), _I32, C.POINTER(Emphasis), C.POINTER(ReconLoss), _P, _P, _I32, _I64,

@@ -118,6 +118,9 @@ class DaeEngine:
         self.loss_emphasis = None
         self._emph_weights = None     # the device tensor codae_emphasis.col_weight borrows
         self.hidden_dropout = None
+        self.residual = None          # the codae.tool.Residual in force (None = off)
+        self.residual_layers = []     # the skipped layers it resolved to on this stack
+        self._residual_ws = None      # the device tensor codae_set_residual borrows (G and the 1-bit masks)
         self.recon_loss = None
         self.slot_contrast = None
         self._contrast_pins = None    # the device tensors codae_slot_contrast borrows (pool, item ids, work space)
@@ -546,6 +549,39 @@ class DaeEngine:
             arr = (C.c_float * max(len(p), 1))(*[float(v) for v in p])
             st = Dropout(arr, len(p), int(seed))
         check(self._lib.codae_set_hidden_dropout(self._h, None if st is None else C.byref(st)))
+
+    def layer_activations(self):
+        """[(kind, p0, p1, p2)] per layer: what follows each Linear, as codae.tool.Residual.resolve takes it."""
+        if self.activation is not None:
+            return list(self.activation)
+        return [(1 if s[2] else 0, 0.0, 0.0, 0.0) for s in self.schedule]
+
+    def set_residual(self, residual):
+        """residual: a codae.tool.Residual, or None to switch the skips off.  Every call that follows - training steps in every
+        step form, eval steps, forward, score_outfits, with the engine's own or the averaged weights - adds h_l to the output of
+        every skipped layer l (include/codae_hip.h, "Residual connections"); with graph=True the next step re-captures.  While a
+        skip is on, step_path() is 'layers'; backward() and a forward over a partial layer range raise.  Accepted around layers
+        of equal widths other than the last, after no activation, ReLU and LeakyReLU only (HipError naming the layer otherwise;
+        the previous setting stays).  None, or no layer = off: the engine runs exactly what it ran before.  The work space (G and
+        the 1-bit masks) is allocated here and borrowed by the library until the setting is replaced."""
+        if residual is not None and not hasattr(residual, "resolve"):
+            raise HipError("set_residual: expected a codae.tool.Residual or None, got %r" % (residual,))
+        flags = None
+        if residual is not None:
+            flags = residual.resolve([s[0] for s in self.schedule], [s[1] for s in self.schedule], self.layer_activations())
+        if flags is None or not any(flags):
+            check(self._lib.codae_set_residual(self._h, None, None, 0))
+            self.residual, self.residual_layers, self._residual_ws = residual, [], None
+            return
+        from . import ResidualFlags
+        arr = (C.c_uint8 * self.L)(*flags)
+        st = ResidualFlags(self.L, arr)
+        # (flags the library refuses give -1 here: no work space then, and the setter itself reports the error with its own code)
+        need = max(int(self._lib.codae_residual_ws_bytes(self._h, C.byref(st))), 0)
+        with torch.cuda.device(self.device):
+            ws = torch.empty(need, dtype=torch.uint8, device=self.device) if need else None
+            check(self._lib.codae_set_residual(self._h, C.byref(st), ptr(ws), need))
+        self.residual, self.residual_layers, self._residual_ws = residual, [l for l, f in enumerate(flags) if f], ws
 
     def train_step(self, batch, hyper, graph=False):
         """graph=True: replay the step from a hipGraph (captured on first use; batch.row_idx / mask_id must be

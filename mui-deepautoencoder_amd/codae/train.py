@@ -436,7 +436,7 @@ class HipEmbeddingTrainer:
                  max_batch=8192, precision="bf16", device="cuda:0", distributed=False, n_buckets=None, use_graph=False,
                  sharded_update=False, native_dp=False, activation=None, n_slots=None, input_noise=None,
                  loss_emphasis=None, hidden_dropout=None, criterion=None, contrast=None, optimizer=None, presence=None,
-                 tied_weights=None, dataset_image=True, weight_average=None):
+                 tied_weights=None, dataset_image=True, weight_average=None, residual=None):
         """use_graph: replay the fused step from a hipGraph (codae_train_step_graph): for launch-bound shapes
         (small batches); single process only - the bucketed data-parallel step is not captured.
         activation: what follows every hidden Linear, as the model classes take it (a factory called as activation(True),
@@ -482,7 +482,12 @@ class HipEmbeddingTrainer:
         it produces, in the update's own launch and in every step form but the sharded update (refused); eval_batch and complete
         take weights="average" to run on it, params(average=True) / average_params() read it.  It starts as a copy of the
         parameters; load_params and init_params reset it.  Training itself is untouched: parameters, moments and shadows keep
-        their bits.  None (or kind "off") = off, exactly as before."""
+        their bits.  None (or kind "off") = off, exactly as before.
+        residual: a codae.tool.Residual: an identity skip around every chosen hidden layer of equal widths (after no activation,
+        ReLU or LeakyReLU; never the last layer), h_{l+1} = act(W_l h_l + b_l) + h_l.  It is part of the model: every step form,
+        eval_batch, complete, score_outfits and weights="average" run through the skips, and checkpoints record them.  A layer
+        that cannot take a skip is refused (HipError naming the layer and the reason).  None (or no layer) = off, exactly as
+        before."""
         from .hip.engine import DaeEngine
         fit_host_threads()      # the loop that feeds this trainer must not get its container CPU-throttled (codae/hostcpu.py)
         self.device = torch.device(device)
@@ -502,6 +507,8 @@ class HipEmbeddingTrainer:
             self.set_loss_emphasis(loss_emphasis)
         if hidden_dropout is not None:
             self.set_hidden_dropout(hidden_dropout)
+        if residual is not None:
+            self.set_residual(residual)
         if criterion is not None:
             self.set_criterion(criterion)
         if contrast is not None:
@@ -615,6 +622,10 @@ class HipEmbeddingTrainer:
     def set_hidden_dropout(self, dropout):
         """DaeEngine.set_hidden_dropout: a codae.tool.HiddenDropout, or None to switch it off."""
         self.engine.set_hidden_dropout(dropout)
+
+    def set_residual(self, residual):
+        """DaeEngine.set_residual: a codae.tool.Residual, or None to switch the skips off."""
+        self.engine.set_residual(residual)
 
     # ---- parameters ---------------------------------------------------------------------
     def load_params(self, params):
@@ -888,6 +899,7 @@ class HipEmbeddingTrainer:
             "precision": "bf16" if eng.precision == 1 else "f32",
             "activation": None if eng.activation is None else [list(a) for a in eng.activation],
             "tied_weights": bool(eng.tied_weights),
+            "residual": list(eng.residual_layers) or None,       # the skipped layers: part of the model, load() checks them
             "optimizer": "adam" if opt is None else opt.kind,
             "amsgrad": bool(opt is not None and opt.amsgrad),
             "weight_average": None if avg is None or avg.is_default else
@@ -968,6 +980,10 @@ class HipEmbeddingTrainer:
         if bool(meta.get("tied_weights")) != bool(eng.tied_weights):
             refuse("tied_weights", "the file was written with tied weights %s, this trainer has them %s"
                    % ("on" if meta.get("tied_weights") else "off", "on" if eng.tied_weights else "off"))
+        from .tool.residual import meta_mismatch
+        why = meta_mismatch(meta, eng.residual_layers)
+        if why is not None:
+            refuse("residual", why)
         live = eng.state_tensors()
         for n in need:
             if n not in tensors:
@@ -1010,7 +1026,7 @@ class HipEmbeddingTrainer:
     def load(self, path, strict=True):
         """Restore the state save() wrote, so that the next step is bit for bit the step the writing run took next.  Structure first
         (HipError naming the piece; the trainer stays as it was): the schedule and parameter count, tied weights on in one and off in
-        the other, adam_vmax missing while AMSGrad is on; under `strict` also an average missing while averaging is on, another
+        the other, residual connections around other layers (a file without the record has none), adam_vmax missing while AMSGrad is on; under `strict` also an average missing while averaging is on, another
         precision or activation, and optional tensors this trainer does not keep.  Then every tensor is uploaded into a temporary,
         digested on the device and compared with the file's record (HipError naming the tensor; nothing is kept), and only then
         copied over the live state.  On success: step_count is set, the scalars are the file's, the bf16 shadows are rebuilt
@@ -1047,12 +1063,13 @@ class HipEmbeddingTrainer:
     @classmethod
     def load_for_inference(cls, path, data, mask_table_u8=None, mask_to_use_i32=None, n_slots=None, max_batch=8192, device="cuda:0",
                            presence=None):
-        """A trainer built from the file's own record (schedule, precision, activation, tied weights, the kind of average) over
+        """A trainer built from the file's own record (schedule, precision, activation, tied weights, skips, the kind of average) over
         `data`, holding the file's parameters and - when it has one - weight average, each verified on the device as load() does:
         eval_batch, complete*, score_outfits and the metrics give what the writing process gave.  The moments are neither read nor
         required (a file stripped of them loads)."""
         from .tool.average import WeightAverage
         from .tool.checkpoint import CheckpointError, read_checkpoint
+        from .tool.residual import Residual
         try:
             tensors, meta = read_checkpoint(path, verify=False)
         except CheckpointError as e:
@@ -1061,7 +1078,7 @@ class HipEmbeddingTrainer:
         tr = cls([tuple(x) for x in meta["schedule"]], data, mask_table_u8, mask_to_use_i32, meta.get("lr", 0.0), meta.get("weight_decay", 0.0),
                  clip=meta.get("clip", 0.0), max_batch=max_batch, precision=meta.get("precision", "bf16"), device=device,
                  activation=None if act is None else [tuple(a) for a in act], n_slots=n_slots, presence=presence,
-                 tied_weights=bool(meta.get("tied_weights")))
+                 tied_weights=bool(meta.get("tied_weights")), residual=Residual(meta["residual"]) if meta.get("residual") else None)
         eng = tr.engine
         names = ["params"]
         wa = meta.get("weight_average")

@@ -567,6 +567,28 @@ int launch_dropout_fwd(void* a, int bf16, int64_t ld, int B, int width, const in
                        const double* step_dev, float p, uint64_t seed, hipStream_t s);
 int launch_dropout_bwd(void* d, int bf16, int64_t ld, int B, int width, const int32_t* row_idx, int layer, int32_t step,
                        const double* step_dev, float p, uint64_t seed, float* colsum_part, hipStream_t s);
+// Residual connections (codae_residual, include/codae_hip.h; residual.hip): the two streaming kernels of a skipped layer.
+// forward: y <- rne(y + x) in place on rows < B, columns < width (fp32 or bf16); bits != null: first the 1-bit mask "stored y > 0" of
+// the value BEFORE the add, 8 columns per byte, column 8 j + k in bit k of byte j (the layout of the forward GEMM's masks).
+// backward: U = d (working precision), G = U + g_in (one fp32 add; g_in may be null), g_out <- G (may be null, may be g_in),
+// d <- D = G * act' rounded to the working type, act' from `bits` (act_kind RELU selects, LEAKY multiplies by act_p[0]), from the
+// saved activation `src` (any CODAE_ACT_* kind) or 1 (both null); residual_blocks(B) blocks, each leaving one row of colsum_part
+// [blocks][width] (column sums of the stored D; may be null).
+struct ResidualBwd {
+    const float* g_in;
+    float* g_out;
+    int64_t ld_g;
+    const uint8_t* bits;
+    int64_t ld_bits;
+    const void* src;
+    int64_t ld_src;
+    int act_kind;
+    float act_p[3];
+};
+inline int residual_blocks(int B) { return (B + 63) / 64; }
+int launch_residual_fwd(void* y, const void* x, int bf16, int64_t ldy, int64_t ldx, int B, int width, uint8_t* bits, int64_t ld_bits,
+                        hipStream_t s);
+int launch_residual_bwd(void* d, int bf16, int64_t ld, int B, int width, const ResidualBwd& r, float* colsum_part, hipStream_t s);
 int launch_mse_dense(const float* x, const float* y, const float* fmask, float* dy, int64_t n, float inv_n,
                      double* scalars, hipStream_t s);
 // optimizer.hip: the gradient norm, the clip coefficient, the update

@@ -102,6 +102,7 @@ struct codae_engine {
     struct PresCfg { const uint8_t* table; int64_t n_rows; int32_t n_slots; int32_t reserved; };
     struct DropCfg { float p[64]; uint64_t seed; int32_t on; int32_t reserved; };
     struct ImageCfg { const float* data; const void* image; int64_t n_rows; int32_t io; int32_t reserved; };
+    struct ResCfg { uint8_t on[64]; void* ws; int64_t ws_bytes; int32_t any; int32_t reserved; };
     struct TrainCfg {
         codae_noise noise;               // input noise (codae_set_input_noise); kind NONE = off
         codae_swap swap;                 // slots and pool of CODAE_NOISE_SWAP (codae_set_swap_pool); n_slots 0 = not set
@@ -115,6 +116,7 @@ struct codae_engine {
         int32_t tied, tied_reserved;     // tied encoder / decoder weights (codae_set_tied_weights); 0 = off
         ImageCfg img;                    // bf16 image of the dataset (codae_set_dataset_image): image null = none
         codae_weight_average avg;        // average of the iterates kept by the update (codae_set_weight_average); all zero = off
+        ResCfg res;                      // residual connections (codae_set_residual): on[l] = a skip around layer l, all zero = off
     } tc;
     bool recon_on() const { return tc.recon.kind != CODAE_LOSS_MSE; }
     bool contrast_on() const { return tc.contrast.weight != 0.f; }
@@ -131,6 +133,12 @@ struct codae_engine {
     int drop_B = 0;
     const int32_t* drop_rows = nullptr;
     int32_t drop_step = 0;
+    // residual connections: where the setting's work space keeps G (offset 0, [rows][width of the skipped layer] fp32) and the
+    // 1-bit mask of every skipped layer that has a ReLU or a LeakyReLU (byte offset, rows ld_bits apart; -1: none); res_bits_live =
+    // the last forward was a training forward and wrote them; res_B = the rows of the backward in flight
+    std::vector<int64_t> res_bits_off;
+    bool res_bits_live = false;
+    int res_B = 0;
     std::vector<int> parts_pending;
     // backward on two streams: the weight-gradient GEMMs (+ slab reduce) run on `side`, concurrently with
     // the data-gradient chain on the caller's stream (they only share the read-only dA_l)
@@ -479,9 +487,9 @@ StepPlan step_plan(const codae_engine* e, const codae_buffers* b, const StepCall
     const bool backward = c.kind == STEP_TRAIN || c.kind == STEP_BACKWARD || c.kind == STEP_DROPIN_BACKWARD;
     const bool training = c.kind == STEP_TRAIN || c.kind == STEP_FORWARD_LOSS;       // (the forward has a hyper)
     // (the chain kernel fuses the plain gather and the unweighted loss and keeps the activations to itself: a noised input, an
-    //  emphasised loss, another criterion, hidden dropout or a slot-presence table takes the per-layer launches)
+    //  emphasised loss, another criterion, hidden dropout, a skip or a slot-presence table takes the per-layer launches)
     if (c.kind == STEP_TRAIN && e->chain_ok && e->plain_mse() && e->tc.noise.kind == CODAE_NOISE_NONE && !e->tc.drop.on &&
-        b->shadow_wt != nullptr && p.rows <= CHAIN_MAX_ROWS) {
+        !e->tc.res.any && b->shadow_wt != nullptr && p.rows <= CHAIN_MAX_ROWS) {
         // narrow stack: persistent fused chain + grouped weight gradients (4 launches for the whole step)
         p.path = PATH_CHAIN;
         p.loss = LOSS_IN_CHAIN; p.loss_finish = LOSS_FINISH_CARRIED;
@@ -708,7 +716,9 @@ int run_wgrad(codae_engine* e, const codae_buffers* b, int l, int rows, bool wit
 
 // dA_{l-1} = (dA_l W_l) * [act[l] > 0]  (+ column sums -> db_{l-1});  l == 0 with dx: plain dX in fp32
 // coscheduled: another stream's weight gradients run beside this launch (GemmBf16::coscheduled)
-int run_dgrad_gemm(codae_engine* e, const codae_buffers* b, int l, int rows, bool coscheduled, float* dx_f32, hipStream_t s) {
+// unmasked: dA_{l-1} = dA_l W_l alone (relu_src == relu_bits == nullptr) - the residual kernel behind it applies the derivative
+int run_dgrad_gemm(codae_engine* e, const codae_buffers* b, int l, int rows, bool coscheduled, float* dx_f32, hipStream_t s,
+                   bool unmasked = false) {
     const int N = e->out[l], K = e->in[l];
     const bool to_dx = (dx_f32 != nullptr);
     ProfScope prof(e, CODAE_K_GEMM_DGRAD, s);
@@ -720,7 +730,10 @@ int run_dgrad_gemm(codae_engine* e, const codae_buffers* b, int l, int rows, boo
                                      to_dx ? K : e->out_ld[l - 1], to_dx ? 1 : 0, rows, K, e->out_ld[l]);
         g.coscheduled = coscheduled ? 1 : 0;
         if (!to_dx) {
-            if (e->act[l - 1] != CODAE_ACT_NONE) {
+            if (unmasked) {
+                // (no mask, no derivative: the write-out the layer behind a code layer takes; the column sums it leaves are
+                //  rewritten by the residual kernel)
+            } else if (e->act[l - 1] != CODAE_ACT_NONE) {
                 // another activation than ReLU: its derivative from the saved activation (no 1-bit masks for these layers)
                 g.relu_src = reinterpret_cast<const bf16_t*>(act_ptr(e, b, l)); g.ld_relu = e->in_ld[l];
                 set_activation(g, 0, e->act[l - 1], &e->act_p[3 * (l - 1)]);
@@ -744,7 +757,7 @@ int run_dgrad_gemm(codae_engine* e, const codae_buffers* b, int l, int rows, boo
     GemmF32 g = dgrad_gemm_f32(reinterpret_cast<const float*>(dact_ptr(e, b, l)), b->params + e->w_off[l],
                                to_dx ? dx_f32 : reinterpret_cast<float*>(dact_ptr(e, b, l - 1)), rows, N, K);
     if (!to_dx) {
-        if (e->relu[l - 1] || e->act[l - 1] != CODAE_ACT_NONE) {
+        if (!unmasked && (e->relu[l - 1] || e->act[l - 1] != CODAE_ACT_NONE)) {
             g.relu_src = reinterpret_cast<const float*>(act_ptr(e, b, l)); g.ld_relu = K;
             set_activation(g, 0, e->act[l - 1], &e->act_p[3 * (l - 1)]);
         }
@@ -767,12 +780,56 @@ int run_dropout_fwd(codae_engine* e, const codae_buffers* b, int l, hipStream_t 
                               e->drop_step, step_dev(e, b), e->tc.drop.p[l], e->tc.drop.seed, s);
 }
 
+inline bool skips_layer(const codae_engine* e, int l) { return e->tc.res.any && l >= 0 && l + 1 < e->L && e->tc.res.on[l] != 0; }
+
+// act[l + 1] <- act[l + 1] + act[l] behind the forward GEMM of a skipped layer l (and behind its dropout kernel); training: the
+// 1-bit mask of the value before the add goes to the setting's work space first.  Part of the MODEL: every forward loop calls it.
+int run_residual_fwd(codae_engine* e, const codae_buffers* b, int l, int B, bool training, hipStream_t s) {
+    uint8_t* bits = training && e->res_bits_off[l] >= 0 ? reinterpret_cast<uint8_t*>(e->tc.res.ws) + e->res_bits_off[l] : nullptr;
+    ProfScope prof(e, CODAE_K_DROPOUT, s);
+    return launch_residual_fwd(act_ptr(e, b, l + 1), act_ptr(e, b, l), e->prec == CODAE_PREC_BF16, e->in_ld[l + 1], e->in_ld[l], B, e->out[l], bits,
+                               (e->out[l] + 7) / 8, s);
+}
+
 // the data gradient of layer l and, when layer l - 1 was dropped in the forward, dA_{l-1} <- dA_{l-1} * f right behind it on the same
 // stream: the kernel writes layer l - 1's partial column sums again, from the final values, in place of the GEMM epilogue's (one row
 // per 64 batch rows: within the rows the layer owns), before the caller records the event the side-stream weight gradient waits for
+// With a skip around layer l or around layer l - 1 (codae_residual) the GEMM runs unmasked and the residual kernel sits between it and
+// dropout's: G_l = U_l + skip_l G_{l+1}, kept for the next level when layer l - 1 is skipped too, dA_{l-1} <- G_l * act'_{l-1} and its
+// partial column sums.  act'_{l-1} comes from the 1-bit mask the forward skip kernel wrote when layer l - 1 is skipped (act[l] then
+// holds a_{l-1} + h_{l-1}), else from the saved activation act[l], as the GEMM epilogue takes it.
 int run_dgrad(codae_engine* e, const codae_buffers* b, int l, int rows, bool coscheduled, float* dx_f32, hipStream_t s) {
-    int rc = run_dgrad_gemm(e, b, l, rows, coscheduled, dx_f32, s);
-    if (rc || dx_f32 != nullptr || !drops_layer(e, l - 1)) return rc;
+    const bool res = dx_f32 == nullptr && l >= 1 && (skips_layer(e, l) || skips_layer(e, l - 1));
+    int rc = run_dgrad_gemm(e, b, l, rows, coscheduled, dx_f32, s, res);
+    if (rc || dx_f32 != nullptr) return rc;
+    if (res) {
+        const bool bf = e->prec == CODAE_PREC_BF16;
+        const int m = l - 1;                                     // the layer whose derivative is applied
+        const int kind = e->relu[m] ? CODAE_ACT_RELU : (int)e->act[m];
+        float* G = reinterpret_cast<float*>(e->tc.res.ws);
+        ResidualBwd r{};
+        r.g_in = skips_layer(e, l) ? G : nullptr;
+        r.g_out = skips_layer(e, m) && m >= 1 ? G : nullptr;     // (layer 0's input gradient is never formed)
+        r.ld_g = e->in[l];
+        r.act_kind = kind;
+        for (int k = 0; k < 3; ++k) r.act_p[k] = e->act_p[3 * m + k];
+        if (skips_layer(e, m)) {
+            if (e->res_bits_off[m] >= 0) {
+                CODAE_REQUIRE(e->res_bits_live, "backward through the skip of layer %d without a training forward before it", m);
+                r.bits = reinterpret_cast<const uint8_t*>(e->tc.res.ws) + e->res_bits_off[m];
+                r.ld_bits = (e->out[m] + 7) / 8;
+            }
+        } else if (kind != CODAE_ACT_NONE) {
+            r.src = act_ptr(e, b, l); r.ld_src = e->in_ld[l];
+        }
+        {
+            ProfScope prof(e, CODAE_K_DROPOUT, s);
+            rc = launch_residual_bwd(dact_ptr(e, b, m), bf, bf ? e->out_ld[m] : e->out[m], e->res_B, e->out[m], r, part_ptr(e, b, m), s);
+        }
+        if (rc) return rc;
+        e->parts_pending[m] = residual_blocks(e->res_B);
+    }
+    if (!drops_layer(e, l - 1)) return CODAE_OK;
     {
         ProfScope prof(e, CODAE_K_DROPOUT, s);
         rc = launch_dropout_bwd(dact_ptr(e, b, l - 1), e->prec == CODAE_PREC_BF16, e->prec == CODAE_PREC_BF16 ? e->out_ld[l - 1] : e->out[l - 1],
@@ -853,6 +910,7 @@ int backward_range(codae_handle h, const codae_buffers* b, const StepCall& c, co
     const bool step_mode = c.kind != STEP_DROPIN_BACKWARD, join = c.join;
     const bool dual = p.streams == 2, with_norm = p.norm == NORM_FROM_BACKWARD;
     CODAE_REQUIRE(!(step_mode && h->drop_live && h->tc.drop.on) || B == h->drop_B, "backward of %d rows after a dropped forward of %d", B, h->drop_B);
+    h->res_B = B;             // (the residual kernels behind the data gradients cover the batch's own rows)
     if (dual) {
         int rc = ensure_side_stream(h);
         if (rc) return rc;
@@ -1047,6 +1105,7 @@ int codae_create(const codae_spec* spec, codae_handle* out) {
     // partial column-sum rows per layer: a producer writes at most one row per 64 batch rows (exact-fp32 GEMM, dense
     // colsum), the stand-alone loss kernel of the last layer one per 32, the persistent chain one per 16
     e->parts_pending.assign(e->L, 0);
+    e->res_bits_off.assign(e->L, -1);
     e->part_floats = 0;
     const int chain_rows = e->max_rows < CHAIN_MAX_ROWS ? e->max_rows : CHAIN_MAX_ROWS;
     for (int l = 0; l < e->L; ++l) {
@@ -1185,7 +1244,13 @@ int codae_forward(codae_handle h, const codae_buffers* b, const float* x, float*
     CODAE_REQUIRE(x && y, "codae_forward: null x or y");
     CODAE_REQUIRE(layer_lo >= 0 && layer_lo < layer_hi && layer_hi <= h->L, "codae_forward: layer range [%d, %d)", layer_lo, layer_hi);
     (void)save_for_backward;  // activations always live in the workspace; a later forward overwrites them
+    if (h->tc.res.any && !(layer_lo == 0 && layer_hi == h->L)) {
+        set_error("codae_forward: residual connections are on: a forward over the layer range [%d, %d) of %d layers is not supported", layer_lo,
+                  layer_hi, h->L);
+        return CODAE_E_UNSUPPORTED;
+    }
     h->drop_live = false;     // (a drop-in forward never drops)
+    h->res_bits_live = false; // (nor writes the skips' masks)
     hipStream_t s = (hipStream_t)stream;
     const int rows = h->rows_for(B);
     // ingest x into act[layer_lo] in working precision (no gather, no mask)
@@ -1204,6 +1269,10 @@ int codae_forward(codae_handle h, const codae_buffers* b, const float* x, float*
             rc = run_linear(h, b, l, act_ptr(h, b, l), act_ptr(h, b, l + 1), false, rows, s);
         }
         if (rc) return rc;
+        if (skips_layer(h, l)) {
+            rc = run_residual_fwd(h, b, l, B, false, s);
+            if (rc) return rc;
+        }
     }
     return CODAE_OK;
 }
@@ -1214,6 +1283,11 @@ int codae_backward(codae_handle h, const codae_buffers* b, const float* dy, floa
     if (rc) return rc;
     CODAE_REQUIRE(dy && b->grads && b->dacts, "codae_backward: null dy / grads / dacts");
     CODAE_REQUIRE(layer_lo >= 0 && layer_lo < layer_hi && layer_hi <= h->L, "codae_backward: layer range [%d, %d)", layer_lo, layer_hi);
+    if (h->tc.res.any) {
+        // (the drop-in forward writes no masks, and its sub-chains cut the sum G across the cut)
+        set_error("codae_backward: residual connections are on: the drop-in backward is not supported (use the step entry points)");
+        return CODAE_E_UNSUPPORTED;
+    }
     hipStream_t s = (hipStream_t)stream;
     const int rows = h->rows_for(B);
     const int top = layer_hi - 1;
@@ -1323,6 +1397,8 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
     // hidden dropout: training forwards only; the backward entry points find the rows and the step in the handle
     h->drop_live = hyper != nullptr && h->tc.drop.on;
     if (h->drop_live) { h->drop_B = B; h->drop_rows = batch->row_idx; h->drop_step = hyper->step; }
+    // residual connections: every forward adds the skips; a training forward also leaves their 1-bit masks for the backward
+    h->res_bits_live = hyper != nullptr && h->tc.res.any;
     const uint8_t* const pres = h->tc.pres.table;
     const int pres_slots = h->tc.pres.n_slots;
     const bool fuse_loss = plan.loss == LOSS_FUSED, fold_finish = plan.loss_finish == LOSS_FINISH_CARRIED;
@@ -1344,7 +1420,7 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
     if (rc) return rc;
     float* y = out_y ? out_y : reinterpret_cast<float*>(act_ptr(h, b, L));
     GroupScope fwd_group(h, CODAE_K_GEMM_FWD, s);       // the plain forward launches of this step, back to back
-    if (h->drop_live) fwd_group.close();                // (dropout kernels sit between them: every launch gets its own event pair)
+    if (h->drop_live || h->tc.res.any) fwd_group.close();   // (streaming kernels sit between them: every launch gets its own event pair)
     for (int l = 0; l < L; ++l) {
         const bool last = (l == L - 1);
         if (last && fuse_loss) {
@@ -1381,6 +1457,10 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
         fwd_group.launched();
         if (drops_layer(h, l)) {
             rc = run_dropout_fwd(h, b, l, s);
+            if (rc) return rc;
+        }
+        if (skips_layer(h, l)) {
+            rc = run_residual_fwd(h, b, l, B, hyper != nullptr, s);
             if (rc) return rc;
         }
     }
@@ -1593,6 +1673,67 @@ int codae_set_hidden_dropout(codae_handle h, const codae_dropout* d) {
     return CODAE_OK;
 }
 
+// The canonical flags of a codae_residual on this stack (all zero = off) and the layout of its work space: G first, then the 1-bit
+// mask of every skipped layer with a ReLU or a LeakyReLU.  CODAE_E_INVALID / CODAE_E_UNSUPPORTED as codae_set_residual documents.
+static int residual_layout(codae_handle h, const codae_residual* r, const char* who, uint8_t* on, std::vector<int64_t>* bits_off, int64_t* bytes) {
+    memset(on, 0, 64);
+    if (bits_off) bits_off->assign(h->L, -1);
+    *bytes = 0;
+    if (r == nullptr) return CODAE_OK;
+    CODAE_REQUIRE(r->n == h->L, "%s: %d flags for %d layers", who, r->n, h->L);
+    CODAE_REQUIRE(r->on != nullptr, "%s: null on", who);
+    int maxw = 0;
+    for (int l = 0; l < h->L; ++l) {
+        if (!r->on[l]) continue;
+        // (codae_create keeps a ReLU layer as relu[l] = 1 with act[l] = NONE: act[l] names the generic activations only, so NONE
+        //  below is "no activation or ReLU" and kind 1 never appears)
+        const char* why = nullptr;
+        if (l == h->L - 1) why = "the last layer's output is the reconstruction and takes no skip";
+        else if (h->in[l] != h->out[l]) why = "an identity skip needs equal widths";
+        else if (h->act[l] != CODAE_ACT_NONE && h->act[l] != CODAE_ACT_LEAKY) why = "a skipped layer's activation must be none, ReLU or LeakyReLU";
+        if (why != nullptr) {
+            set_error("%s: layer %d (%d -> %d, activation kind %d): %s", who, l, h->in[l], h->out[l], h->relu[l] ? CODAE_ACT_RELU : (int)h->act[l], why);
+            return CODAE_E_UNSUPPORTED;
+        }
+        on[l] = 1;
+        if (h->out[l] > maxw) maxw = h->out[l];
+    }
+    if (maxw == 0) return CODAE_OK;
+    int64_t off = round_up((int64_t)h->max_batch * maxw * 4, 256);
+    for (int l = 0; l < h->L; ++l) {
+        if (!on[l] || !(h->relu[l] || h->act[l] == CODAE_ACT_LEAKY)) continue;
+        if (bits_off) (*bits_off)[l] = off;
+        off += round_up((int64_t)h->max_batch * ((h->out[l] + 7) / 8), 256);
+    }
+    *bytes = off;
+    return CODAE_OK;
+}
+
+int64_t codae_residual_ws_bytes(codae_handle h, const codae_residual* r) {
+    if (h == nullptr) { set_error("codae_residual_ws_bytes: null handle"); return -1; }
+    uint8_t on[64];
+    int64_t bytes = 0;
+    return residual_layout(h, r, "codae_residual_ws_bytes", on, nullptr, &bytes) == CODAE_OK ? bytes : -1;
+}
+
+int codae_set_residual(codae_handle h, const codae_residual* r, void* ws, int64_t ws_bytes) {
+    CODAE_REQUIRE(h != nullptr, "codae_set_residual: null handle");
+    codae_engine::ResCfg c{};            // (built field by field: the graph key compares bytes)
+    std::vector<int64_t> bits_off;
+    int64_t need = 0;
+    int rc = residual_layout(h, r, "codae_set_residual", c.on, &bits_off, &need);
+    if (rc) return rc;
+    if (need > 0) {
+        CODAE_REQUIRE(ws != nullptr && (reinterpret_cast<uintptr_t>(ws) & 15) == 0 && ws_bytes >= need,
+                      "codae_set_residual: the work space must be 16-byte aligned and hold %lld bytes (got %lld)", (long long)need, (long long)ws_bytes);
+        c.ws = ws; c.ws_bytes = ws_bytes; c.any = 1;
+    }
+    h->tc.res = c;
+    h->res_bits_off = bits_off;
+    h->res_bits_live = false;
+    return CODAE_OK;
+}
+
 int codae_eval_step(codae_handle h, const codae_buffers* b, const codae_batch* batch, float* out_y, void* stream) {
     return codae_step_forward_loss(h, b, batch, nullptr, out_y, stream);
 }
@@ -1623,6 +1764,7 @@ int codae_score_outfits(codae_handle h, const codae_buffers* b, const float* dat
     const bool bf = h->prec == CODAE_PREC_BF16;
     const int rows = h->rows_for(B);
     h->drop_live = false;     // (an evaluation forward never drops)
+    h->res_bits_live = false;
     const codae_engine::ImageCfg& im = h->tc.img;
     const bool from_image = bf && !h->cfg.no_dataset_image && im.image != nullptr && data == im.data && io == im.io && n_rows == im.n_rows;
     {
@@ -1638,6 +1780,10 @@ int codae_score_outfits(codae_handle h, const codae_buffers* b, const float* dat
         rc = (l == L - 1) ? run_linear(h, b, l, act_ptr(h, b, l), y, true, B, s)
                           : run_linear(h, b, l, act_ptr(h, b, l), act_ptr(h, b, l + 1), false, rows, s);
         if (rc) return rc;
+        if (skips_layer(h, l)) {
+            rc = run_residual_fwd(h, b, l, B, false, s);
+            if (rc) return rc;
+        }
     }
     return launch_outfit_scores(data, n_rows, io, n_slots, items, Q, pres, y, io, cos, sq, score, n_present, s);
 }

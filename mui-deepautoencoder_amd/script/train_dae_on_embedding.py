@@ -159,6 +159,10 @@ def main():
     # hidden Linear of the training steps (validation never drops)
     from codae.tool.dropout import hidden_dropout_from_config
     hidden_dropout = hidden_dropout_from_config(config.get("HIP", {}).get("HIDDEN_DROPOUT"))
+    # HIP: RESIDUAL: {LAYERS: hidden | [1, 2, ..]} (build-only key): an identity skip around the chosen hidden layers of equal widths,
+    # in training and in validation alike (it is part of the model)
+    from codae.tool.residual import residual_from_config
+    residual = residual_from_config(config.get("HIP", {}).get("RESIDUAL"))
     # HIP: CRITERION: {KIND: mse | l1 | smooth_l1 | huber | slot_cosine, BETA: .., DELTA: .., MSE_WEIGHT: ..} (build-only key): the
     # training loss instead of the mean squared error (the monitors stay squared-error sums; validation never sees it)
     from codae.tool.recon_loss import recon_loss_from_config
@@ -192,7 +196,7 @@ def main():
                                    max_batch=mc["BATCH_SIZE"], precision=prec, device=device, distributed=world > 1,
                                    activation=activation, input_noise=input_noise, loss_emphasis=loss_emphasis,
                                    hidden_dropout=hidden_dropout, criterion=criterion, contrast=contrast, optimizer=optimizer,
-                                   presence=presence, tied_weights=tied_weights, weight_average=weight_average)
+                                   presence=presence, tied_weights=tied_weights, weight_average=weight_average, residual=residual)
     try:
         trainer = build(precision)
     except HipError as e:
@@ -208,6 +212,8 @@ def main():
     if tied_weights:
         log.info("TIED WEIGHTS: %d free parameters of %d" % (TiedWeights.free_parameter_count(enc + dec),
                                                             sum(k * n + n for k, n, _ in enc + dec)))
+    if trainer.engine.residual_layers:
+        log.info("RESIDUAL: %r - identity skips around layers %s" % (residual, trainer.engine.residual_layers))
     if eval_weights == "average":
         log.info("WEIGHT AVERAGE: %r - the validation errors and the ranking error are those of the averaged weights" % (weight_average,))
     book = {k: [] for k in ("ftl", "ptl", "fvl", "pvl", "rl")}
