@@ -79,6 +79,8 @@ extern "C" {
  *      (still 11) + codae_residual, codae_residual_ws_bytes, codae_set_residual, codae_residual_fwd, codae_residual_bwd,
  *      codae_residual_blocks: new entries only, no layout or enum change; the two kernels are booked under CODAE_K_DROPOUT, the
  *      class of the streaming kernels between a step's GEMMs
+ *      (still 11) + codae_norm, CODAE_NORM_*, codae_norm_ws_bytes, codae_set_norm, codae_norm_fwd, codae_norm_bwd, codae_norm_blocks:
+ *      new entries only, no layout or existing enum change; the two kernels are booked under CODAE_K_DROPOUT as well
  * The binding must refuse a library whose codae_abi_version() differs and must check its own struct sizes against
  * codae_struct_sizes() at load (mui-deepautoencoder_amd/codae/hip/__init__.py does both). */
 #define CODAE_ABI_VERSION 11
@@ -381,6 +383,41 @@ typedef struct {
     int32_t n;            /* == n_layers */
     const uint8_t* on;    /* HOST array [n]: on[l] != 0 = a skip around layer l; copied by the setter */
 } codae_residual;
+
+/* Normalisation: parameter-free layer / RMS normalisation (Ba et al. 2016; Zhang & Sennrich 2019) of a hidden layer's output, per
+ * batch row, as the last thing the layer does (post-norm).  With f_l the dropout factor and skip_l the residual flag, norm_l in {0, 1}:
+ *   a_l = f_l act_l(W_l h_l + b_l)      s_l = a_l + skip_l h_l      h_{l+1} = norm_l ? N(s_l) : s_l
+ * N acts on one batch row x of width w = out[l], eps > 0:
+ *   CODAE_NORM_LAYER  mu = sum x / w, v = sum (x - mu)^2 / w (biased, two passes), r = 1 / sqrt(v + eps), xhat = (x - mu) r
+ *   CODAE_NORM_RMS    r = 1 / sqrt(sum x^2 / w + eps), xhat = x r
+ * There is no gain and no bias: every normalised layer is followed by a Linear, which absorbs them (W diag(gamma), b + W beta), so
+ * the parameter vector, the optimizer spans, tied weights, the average and the checkpoint tensors keep their shape.  The statistics
+ * are per row: no value crosses rows or ranks, evaluation needs no running average, and a shard of a batch gives the bits of the
+ * same rows of the whole batch.
+ * Precision: the statistics are fp32, formed from the STORED working-precision s_l; a lane adds its columns in ascending order, the
+ * 64 lanes' sums meet in a butterfly whose result is the same in every lane; no atomics.  xhat is rounded to nearest even into the
+ * working type and stored IN PLACE in act[l + 1]; r stays fp32, one value per (normalised layer, batch row), in the work space.
+ * Backward, Gh_{l+1} = dL/dh_{l+1} as the UNMASKED data-gradient GEMM of layer l + 1 leaves it (working precision) plus the skip
+ * term skip_{l+1} G, all arithmetic fp32, xhat = the stored (rounded) activation:
+ *   c1 = sum Gh / w (LAYER only)          c2 = sum (Gh xhat) / w
+ *   Gs_l = r (Gh - c1 - xhat c2) (LAYER)  Gs_l = r (Gh - xhat c2) (RMS)       Gs_l = Gh (norm_l = 0)
+ *   D_l = Gs_l act'_l (rounded once into the working type; then dropout's factor, in dropout's own kernel)
+ *   Gh_l = D_l W_l + skip_l Gs_l          (the matrix G of "Residual connections" holds Gs)
+ * act'_l comes from a 1-bit mask of the pre-norm value (layout and predicate of the residual masks): after normalising, the saved
+ * output no longer determines it.  A skipped layer's mask is the residual kernel's; otherwise a TRAINING forward's norm kernel
+ * writes it into the norm's work space before it normalises.
+ * norm_l = 1 is accepted only for l <= L-2 (the last layer's output is the reconstruction) and only behind CODAE_ACT_NONE, RELU or
+ * LEAKY; eps must be finite and > 0.  Unlike a skip it needs no equal widths: layer 0 and tapered stacks are allowed.
+ * It is part of the MODEL: every forward normalises - the training steps, codae_eval_step, codae_forward over the whole stack,
+ * codae_score_outfits, with whatever buffer set (the weight average's) the call is given.  Pad columns (ld > width) and pad rows are
+ * never written: xhat of a zero pad column would be -mu r, and the next GEMM runs k over the padded width. */
+enum { CODAE_NORM_LAYER = 1, CODAE_NORM_RMS = 2 };
+typedef struct {
+    int32_t n;            /* == n_layers */
+    const uint8_t* on;    /* HOST array [n]: on[l] != 0 = layer l's output is normalised; copied by the setter */
+    int32_t kind;         /* CODAE_NORM_LAYER or CODAE_NORM_RMS, one kind for the stack */
+    float eps;
+} codae_norm;
 
 /* Optimizer and schedule: what the update at the end of every training step does with the clipped gradient; the default is the line
  * the reference script hard-wires, clip_grad_norm_ + torch.optim.Adam with L2 decay, AMSGrad off and a constant lr.
@@ -782,6 +819,21 @@ int codae_set_hidden_dropout(codae_handle h, const codae_dropout* d);
  * CODAE_E_UNSUPPORTED.  A step backward needs a training forward before it: only that writes the masks. */
 int64_t codae_residual_ws_bytes(codae_handle h, const codae_residual* r);
 int codae_set_residual(codae_handle h, const codae_residual* r, void* ws, int64_t ws_bytes);
+/* Normalisation ("Normalisation" above) of every call that follows - training steps in every step form AND every evaluation
+ * forward; a change re-captures the graph.  NULL, or an all-zero `on`, switches it off: the engine then runs exactly the launches it
+ * ran before, bit for bit, codae_step_path included, and ws may be NULL.  The error contract of codae_set_residual: CODAE_E_INVALID
+ * for n != n_layers, a null `on`, an unknown kind, an eps that is not finite or not > 0, a ws that is NULL, not 16-byte aligned or
+ * smaller than codae_norm_ws_bytes says; CODAE_E_UNSUPPORTED for a norm on the last layer or behind RELU6, ELU, SOFTPLUS or
+ * HARDSIGMOID (the message names the layer and the reason).  On any error nothing is launched and the previous setting stays.  ws is
+ * borrowed until the setting is replaced; it holds r and the 1-bit masks, its contents need not be zero, and codae_sizes /
+ * codae_buffers do not change.  codae_norm_ws_bytes: the bytes needed (0 when off), or -1 with the same errors.
+ * While a norm is on: one stand-alone kernel behind the forward GEMM of every normalised layer l (behind its dropout and skip
+ * kernels), and behind the data-gradient GEMM of layer l + 1, which runs unmasked, one kernel that does the whole job of the
+ * residual backward kernel at that site and TAKES ITS PLACE (both class CODAE_K_DROPOUT); the stack stays off the persistent chain
+ * kernel (codae_step_path reports 0), and nothing else of the step plan changes.  codae_backward, and codae_forward over a partial
+ * layer range, return CODAE_E_UNSUPPORTED.  A step backward needs a training forward before it: only that writes the masks. */
+int64_t codae_norm_ws_bytes(codae_handle h, const codae_norm* n);
+int codae_set_norm(codae_handle h, const codae_norm* n, void* ws, int64_t ws_bytes);
 /* Slot contrast of every training step that follows (the step forms codae_set_input_noise lists; a change re-captures the graph;
  * under replay the step index is read from scalars[CODAE_S_ADAM_STEP]).  NULL or weight == 0 switches it off: the engine then runs
  * exactly what it ran before, bit for bit, codae_step_path included.  CODAE_E_INVALID for n_neg outside [1, 4096], a tau that is
@@ -854,7 +906,8 @@ enum {
     CODAE_K_CHAIN = 8,       /* narrow stacks: gather + forward chain + loss + data-gradient chain in one launch */
     CODAE_K_BIAS_FINISH = 9, /* partial column sums -> bias gradients (+ their share of sum g^2) */
     CODAE_K_DROPOUT = 10,    /* streaming kernels between a step's GEMMs - hidden dropout: the factor on a layer's output / on its
-                              * activation gradient (+ its column sums); residual connections: the skip add, and G + the derivative */
+                              * activation gradient (+ its column sums); residual connections: the skip add, and G + the derivative;
+                              * normalisation: the row statistics + xhat, and Gs + the derivative */
     CODAE_K_COUNT = 11
 };
 /* Start recording a hipEvent pair around every launch whose class bit is set in class_mask
@@ -981,6 +1034,24 @@ int codae_residual_bwd(void* d, int32_t bf16, int64_t ld, int32_t B, int32_t wid
                        const uint8_t* bits, int64_t ld_bits, const void* src, int64_t ld_src, int32_t act_kind, const float* act_param,
                        float* colsum_part, void* stream);
 int codae_residual_blocks(int32_t B);    /* part rows codae_residual_bwd writes: one per 64 batch rows */
+/* The two normalisation kernels on their own (the launchers the engine uses; "Normalisation" above has the definition), on rows
+ * < B and columns < width of [B][ld] matrices, fp32 or (bf16 != 0) bf16; pad columns and pad rows are never written.  A wave owns
+ * a row and reads it once per pass (sum, centred squares, write-out) - the passes after the first find it in the caches; 16-byte
+ * accesses where every base address, every ld and the width allow (bf16 x 8, fp32 x 4), element accesses otherwise.
+ * forward: bits != NULL: first bits[b][j] <- the mask byte of columns 8 j .. 8 j + 7 of the y it read (bits past the width clear),
+ * rows ld_bits >= ceil(width / 8) bytes apart; then y <- xhat in place and rstd[b] <- r.
+ * backward: U = d; Gh = U + g_in (one fp32 add; g_in may be NULL); Gs from Gh, xhat ([B][ld_x], working precision) and rstd;
+ * g_out <- Gs (may be NULL, may be g_in; rows ld_g floats apart); d <- D = Gs times the derivative rounded to the working type,
+ * the derivative from `bits` (act_kind CODAE_ACT_RELU: Gs or 0, CODAE_ACT_LEAKY: Gs or Gs act_param[0]) or 1 (bits NULL).  One block
+ * per 64 batch rows - codae_norm_blocks(B) of them - and each leaves one row of colsum_part [blocks][width] (column sums of the
+ * STORED D widened to fp32; may be NULL) with plain stores added in a fixed order: the same inputs give the same bits, and a row's
+ * results do not depend on the other rows of the call. */
+int codae_norm_fwd(void* y, int32_t bf16, int64_t ld, int32_t B, int32_t width, int32_t kind, float eps, float* rstd, uint8_t* bits,
+                   int64_t ld_bits, void* stream);
+int codae_norm_bwd(void* d, int32_t bf16, int64_t ld, int32_t B, int32_t width, int32_t kind, const void* xhat, int64_t ld_x,
+                   const float* rstd, const float* g_in, float* g_out, int64_t ld_g, const uint8_t* bits, int64_t ld_bits,
+                   int32_t act_kind, const float* act_param, float* colsum_part, void* stream);
+int codae_norm_blocks(int32_t B);        /* part rows codae_norm_bwd writes: one per 64 batch rows */
 /* The Gaussian kind's device arithmetic on given words (tools/noise_accuracy.py sweeps all 2^24 values of u1 and of u2 through
  * it): rho[i] = sqrt(-2 ln u1(ra[i])), c[i] = cos(2 pi u2(rb[i])), s[i] = sin(2 pi u2(rb[i])); the unit normals of a pair are
  * rho c and rho s. */

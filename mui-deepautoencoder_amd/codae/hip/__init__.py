@@ -128,6 +128,12 @@ class ResidualFlags(C.Structure):
     _fields_ = [("n", C.c_int32), ("on", C.POINTER(C.c_uint8))]
 
 
+class NormFlags(C.Structure):
+    """codae_norm: n == n_layers, on[l] != 0 = layer l's output is normalised (a host array the setter copies), kind = CODAE_NORM_LAYER
+    (1) or CODAE_NORM_RMS (2), eps > 0"""
+    _fields_ = [("n", C.c_int32), ("on", C.POINTER(C.c_uint8)), ("kind", C.c_int32), ("eps", C.c_float)]
+
+
 _P, _I32, _I64, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
 # name -> (restype, argtypes); mirrors include/codae_hip.h one to one
@@ -198,6 +204,11 @@ PROTOTYPES = {
     "codae_residual_fwd": (C.c_int, [_P, _P, _I32, _I64, _I64, _I32, _I32, _P, _I64, _P]),
     "codae_residual_bwd": (C.c_int, [_P, _I32, _I64, _I32, _I32, _P, _P, _I64, _P, _I64, _P, _I64, _I32, _P, _P, _P]),
     "codae_residual_blocks": (C.c_int, [_I32]),
+    "codae_norm_ws_bytes": (_I64, [_P, C.POINTER(NormFlags)]),
+    "codae_set_norm": (C.c_int, [_P, C.POINTER(NormFlags), _P, _I64]),
+    "codae_norm_fwd": (C.c_int, [_P, _I32, _I64, _I32, _I32, _I32, _F, _P, _P, _I64, _P]),
+    "codae_norm_bwd": (C.c_int, [_P, _I32, _I64, _I32, _I32, _I32, _P, _I64, _P, _P, _P, _I64, _P, _I64, _I32, _P, _P, _P]),
+    "codae_norm_blocks": (C.c_int, [_I32]),
     "codae_emph_loss": (C.c_int, [C.POINTER(Batch), C.POINTER(Noise), _I32, C.POINTER(Emphasis), _P, _P, _I32, _I64, _F, _P, _P, _P]),
     "codae_emph_loss_blocks": (C.c_int, [_I32]),
     "codae_recon_loss_fwd_bwd": (C.c_int, [C.POINTER(Batch), C.POINTER(Noise), _I32, C.POINTER(Emphasis), C.POINTER(ReconLoss), _P, _P, _I32, _I64,

@@ -121,6 +121,9 @@ class DaeEngine:
         self.residual = None          # the codae.tool.Residual in force (None = off)
         self.residual_layers = []     # the skipped layers it resolved to on this stack
         self._residual_ws = None      # the device tensor codae_set_residual borrows (G and the 1-bit masks)
+        self.norm = None              # the codae.tool.Norm in force (None = off)
+        self.norm_layers = []         # the normalised layers it resolved to on this stack
+        self._norm_ws = None          # the device tensor codae_set_norm borrows (r per row and the 1-bit masks)
         self.recon_loss = None
         self.slot_contrast = None
         self._contrast_pins = None    # the device tensors codae_slot_contrast borrows (pool, item ids, work space)
@@ -582,6 +585,33 @@ class DaeEngine:
             ws = torch.empty(need, dtype=torch.uint8, device=self.device) if need else None
             check(self._lib.codae_set_residual(self._h, C.byref(st), ptr(ws), need))
         self.residual, self.residual_layers, self._residual_ws = residual, [l for l, f in enumerate(flags) if f], ws
+
+    def set_norm(self, norm):
+        """norm: a codae.tool.Norm, or None to switch it off.  Every call that follows - training steps in every step form, eval
+        steps, forward, score_outfits, with the engine's own or the averaged weights - normalises the output of every chosen layer
+        per batch row (include/codae_hip.h, "Normalisation"); with graph=True the next step re-captures.  While a norm is on,
+        step_path() is 'layers'; backward() and a forward over a partial layer range raise.  Accepted on every layer but the last,
+        after no activation, ReLU and LeakyReLU only (HipError naming the layer otherwise; the previous setting stays).  None, or
+        no layer = off: the engine runs exactly what it ran before.  The work space (r and the 1-bit masks) is allocated here and
+        borrowed by the library until the setting is replaced."""
+        if norm is not None and not (hasattr(norm, "resolve") and hasattr(norm, "kind_id")):
+            raise HipError("set_norm: expected a codae.tool.Norm or None, got %r" % (norm,))
+        flags = None
+        if norm is not None:
+            flags = norm.resolve([s[0] for s in self.schedule], [s[1] for s in self.schedule], self.layer_activations())
+        if flags is None or not any(flags):
+            check(self._lib.codae_set_norm(self._h, None, None, 0))
+            self.norm, self.norm_layers, self._norm_ws = norm, [], None
+            return
+        from . import NormFlags
+        arr = (C.c_uint8 * self.L)(*flags)
+        st = NormFlags(self.L, arr, norm.kind_id, float(norm.eps))
+        # (flags the library refuses give -1 here: no work space then, and the setter itself reports the error with its own code)
+        need = max(int(self._lib.codae_norm_ws_bytes(self._h, C.byref(st))), 0)
+        with torch.cuda.device(self.device):
+            ws = torch.empty(need, dtype=torch.uint8, device=self.device) if need else None
+            check(self._lib.codae_set_norm(self._h, C.byref(st), ptr(ws), need))
+        self.norm, self.norm_layers, self._norm_ws = norm, [l for l, f in enumerate(flags) if f], ws
 
     def train_step(self, batch, hyper, graph=False):
         """graph=True: replay the step from a hipGraph (captured on first use; batch.row_idx / mask_id must be

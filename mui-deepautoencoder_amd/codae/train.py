@@ -436,7 +436,7 @@ class HipEmbeddingTrainer:
                  max_batch=8192, precision="bf16", device="cuda:0", distributed=False, n_buckets=None, use_graph=False,
                  sharded_update=False, native_dp=False, activation=None, n_slots=None, input_noise=None,
                  loss_emphasis=None, hidden_dropout=None, criterion=None, contrast=None, optimizer=None, presence=None,
-                 tied_weights=None, dataset_image=True, weight_average=None, residual=None):
+                 tied_weights=None, dataset_image=True, weight_average=None, residual=None, norm=None):
         """use_graph: replay the fused step from a hipGraph (codae_train_step_graph): for launch-bound shapes
         (small batches); single process only - the bucketed data-parallel step is not captured.
         activation: what follows every hidden Linear, as the model classes take it (a factory called as activation(True),
@@ -487,7 +487,12 @@ class HipEmbeddingTrainer:
         ReLU or LeakyReLU; never the last layer), h_{l+1} = act(W_l h_l + b_l) + h_l.  It is part of the model: every step form,
         eval_batch, complete, score_outfits and weights="average" run through the skips, and checkpoints record them.  A layer
         that cannot take a skip is refused (HipError naming the layer and the reason).  None (or no layer) = off, exactly as
-        before."""
+        before.
+        norm: a codae.tool.Norm: parameter-free layer or RMS normalisation of every chosen layer's output, per batch row, after the
+        activation, dropout and the skip (never the last layer; after no activation, ReLU or LeakyReLU; any widths).  It is part
+        of the model like the skips: every step form, eval_batch, complete, score_outfits and weights="average" run through it,
+        and checkpoints record it.  A layer that cannot take it is refused (HipError naming the layer and the reason).  None (or
+        no layer) = off, exactly as before."""
         from .hip.engine import DaeEngine
         fit_host_threads()      # the loop that feeds this trainer must not get its container CPU-throttled (codae/hostcpu.py)
         self.device = torch.device(device)
@@ -509,6 +514,8 @@ class HipEmbeddingTrainer:
             self.set_hidden_dropout(hidden_dropout)
         if residual is not None:
             self.set_residual(residual)
+        if norm is not None:
+            self.set_norm(norm)
         if criterion is not None:
             self.set_criterion(criterion)
         if contrast is not None:
@@ -626,6 +633,10 @@ class HipEmbeddingTrainer:
     def set_residual(self, residual):
         """DaeEngine.set_residual: a codae.tool.Residual, or None to switch the skips off."""
         self.engine.set_residual(residual)
+
+    def set_norm(self, norm):
+        """DaeEngine.set_norm: a codae.tool.Norm, or None to switch the normalisation off."""
+        self.engine.set_norm(norm)
 
     # ---- parameters ---------------------------------------------------------------------
     def load_params(self, params):
@@ -892,7 +903,9 @@ class HipEmbeddingTrainer:
         """What the file records beside the tensors: the structure load() checks, and the training options for information."""
         eng = self.engine
         opt, avg = eng.optimizer, eng.weight_average
-        return {
+        from .tool.norm import meta_record
+        norm = meta_record(getattr(eng, "norm", None), getattr(eng, "norm_layers", None))
+        meta = {
             "step_count": int(eng.step_count),
             "schedule": [[k, n, bool(r)] for k, n, r in eng.schedule],
             "n_param": int(eng.n_param),
@@ -911,6 +924,9 @@ class HipEmbeddingTrainer:
                         for n in ("input_noise", "loss_emphasis", "hidden_dropout", "recon_loss", "slot_contrast", "optimizer",
                                   "slot_presence")},
         }
+        if norm is not None:          # (written only when a norm is on: the files of runs without one keep their bytes)
+            meta["norm"] = norm       # {kind, eps, layers}: part of the model, load() checks it
+        return meta
 
     def snapshot(self):
         """Freeze the state as it is behind the steps enqueued so far, without blocking the host: on the current stream, behind
@@ -984,6 +1000,10 @@ class HipEmbeddingTrainer:
         why = meta_mismatch(meta, eng.residual_layers)
         if why is not None:
             refuse("residual", why)
+        from .tool.norm import meta_mismatch as norm_mismatch
+        why = norm_mismatch(meta, getattr(eng, "norm", None), getattr(eng, "norm_layers", None))
+        if why is not None:
+            refuse("norm", why)
         live = eng.state_tensors()
         for n in need:
             if n not in tensors:
@@ -1026,7 +1046,7 @@ class HipEmbeddingTrainer:
     def load(self, path, strict=True):
         """Restore the state save() wrote, so that the next step is bit for bit the step the writing run took next.  Structure first
         (HipError naming the piece; the trainer stays as it was): the schedule and parameter count, tied weights on in one and off in
-        the other, residual connections around other layers (a file without the record has none), adam_vmax missing while AMSGrad is on; under `strict` also an average missing while averaging is on, another
+        the other, residual connections around other layers or another norm (a file without the record has none), adam_vmax missing while AMSGrad is on; under `strict` also an average missing while averaging is on, another
         precision or activation, and optional tensors this trainer does not keep.  Then every tensor is uploaded into a temporary,
         digested on the device and compared with the file's record (HipError naming the tensor; nothing is kept), and only then
         copied over the live state.  On success: step_count is set, the scalars are the file's, the bf16 shadows are rebuilt
@@ -1063,13 +1083,14 @@ class HipEmbeddingTrainer:
     @classmethod
     def load_for_inference(cls, path, data, mask_table_u8=None, mask_to_use_i32=None, n_slots=None, max_batch=8192, device="cuda:0",
                            presence=None):
-        """A trainer built from the file's own record (schedule, precision, activation, tied weights, skips, the kind of average) over
+        """A trainer built from the file's own record (schedule, precision, activation, tied weights, skips, norm, the kind of average) over
         `data`, holding the file's parameters and - when it has one - weight average, each verified on the device as load() does:
         eval_batch, complete*, score_outfits and the metrics give what the writing process gave.  The moments are neither read nor
         required (a file stripped of them loads)."""
         from .tool.average import WeightAverage
         from .tool.checkpoint import CheckpointError, read_checkpoint
         from .tool.residual import Residual
+        from .tool.norm import norm_from_meta
         try:
             tensors, meta = read_checkpoint(path, verify=False)
         except CheckpointError as e:
@@ -1078,7 +1099,8 @@ class HipEmbeddingTrainer:
         tr = cls([tuple(x) for x in meta["schedule"]], data, mask_table_u8, mask_to_use_i32, meta.get("lr", 0.0), meta.get("weight_decay", 0.0),
                  clip=meta.get("clip", 0.0), max_batch=max_batch, precision=meta.get("precision", "bf16"), device=device,
                  activation=None if act is None else [tuple(a) for a in act], n_slots=n_slots, presence=presence,
-                 tied_weights=bool(meta.get("tied_weights")), residual=Residual(meta["residual"]) if meta.get("residual") else None)
+                 tied_weights=bool(meta.get("tied_weights")), residual=Residual(meta["residual"]) if meta.get("residual") else None,
+                 norm=norm_from_meta(meta))
         eng = tr.engine
         names = ["params"]
         wa = meta.get("weight_average")

@@ -589,6 +589,27 @@ inline int residual_blocks(int B) { return (B + 63) / 64; }
 int launch_residual_fwd(void* y, const void* x, int bf16, int64_t ldy, int64_t ldx, int B, int width, uint8_t* bits, int64_t ld_bits,
                         hipStream_t s);
 int launch_residual_bwd(void* d, int bf16, int64_t ld, int B, int width, const ResidualBwd& r, float* colsum_part, hipStream_t s);
+// Normalisation (codae_norm, include/codae_hip.h; norm.hip): the two streaming kernels of a normalised layer, a wave per row.
+// forward: bits != null: first the 1-bit mask "stored y > 0" (layout of the residual masks); then y <- xhat in place on rows < B,
+// columns < width, rstd[b] <- r.  backward: Gh = d + g_in (g_in may be null), Gs = r (Gh - c1 - xhat c2) (LAYER) / r (Gh - xhat c2)
+// (RMS), g_out <- Gs (may be null, may be g_in), d <- D = Gs * act' rounded to the working type, act' from `bits` (act_kind RELU
+// selects, LEAKY multiplies by slope) or 1 (null); norm_blocks(B) blocks, each leaving one row of colsum_part [blocks][width].
+struct NormBwd {
+    const void* xhat;
+    int64_t ld_x;
+    const float* rstd;
+    const float* g_in;
+    float* g_out;
+    int64_t ld_g;
+    const uint8_t* bits;
+    int64_t ld_bits;
+    int act_kind;
+    float slope;
+};
+inline int norm_blocks(int B) { return (B + 63) / 64; }
+int launch_norm_fwd(void* y, int bf16, int64_t ld, int B, int width, int kind, float eps, float* rstd, uint8_t* bits, int64_t ld_bits,
+                    hipStream_t s);
+int launch_norm_bwd(void* d, int bf16, int64_t ld, int B, int width, int kind, const NormBwd& n, float* colsum_part, hipStream_t s);
 int launch_mse_dense(const float* x, const float* y, const float* fmask, float* dy, int64_t n, float inv_n,
                      double* scalars, hipStream_t s);
 // optimizer.hip: the gradient norm, the clip coefficient, the update

@@ -103,6 +103,7 @@ struct codae_engine {
     struct DropCfg { float p[64]; uint64_t seed; int32_t on; int32_t reserved; };
     struct ImageCfg { const float* data; const void* image; int64_t n_rows; int32_t io; int32_t reserved; };
     struct ResCfg { uint8_t on[64]; void* ws; int64_t ws_bytes; int32_t any; int32_t reserved; };
+    struct NormCfg { uint8_t on[64]; void* ws; int64_t ws_bytes; int32_t any; int32_t kind; float eps; int32_t reserved; };
     struct TrainCfg {
         codae_noise noise;               // input noise (codae_set_input_noise); kind NONE = off
         codae_swap swap;                 // slots and pool of CODAE_NOISE_SWAP (codae_set_swap_pool); n_slots 0 = not set
@@ -117,6 +118,7 @@ struct codae_engine {
         ImageCfg img;                    // bf16 image of the dataset (codae_set_dataset_image): image null = none
         codae_weight_average avg;        // average of the iterates kept by the update (codae_set_weight_average); all zero = off
         ResCfg res;                      // residual connections (codae_set_residual): on[l] = a skip around layer l, all zero = off
+        NormCfg norm;                    // normalisation (codae_set_norm): on[l] = layer l's output is normalised, all zero = off
     } tc;
     bool recon_on() const { return tc.recon.kind != CODAE_LOSS_MSE; }
     bool contrast_on() const { return tc.contrast.weight != 0.f; }
@@ -139,6 +141,11 @@ struct codae_engine {
     std::vector<int64_t> res_bits_off;
     bool res_bits_live = false;
     int res_B = 0;
+    // normalisation: where the setting's work space keeps r of every normalised layer ([max_batch] fp32; byte offset, -1: none) and
+    // the 1-bit mask of every normalised layer that has a ReLU or a LeakyReLU (written only when the layer has no skip: a skipped
+    // layer's mask is the residual kernel's); norm_bits_live = the last forward was a training forward and wrote them
+    std::vector<int64_t> norm_r_off, norm_bits_off;
+    bool norm_bits_live = false;
     std::vector<int> parts_pending;
     // backward on two streams: the weight-gradient GEMMs (+ slab reduce) run on `side`, concurrently with
     // the data-gradient chain on the caller's stream (they only share the read-only dA_l)
@@ -487,9 +494,9 @@ StepPlan step_plan(const codae_engine* e, const codae_buffers* b, const StepCall
     const bool backward = c.kind == STEP_TRAIN || c.kind == STEP_BACKWARD || c.kind == STEP_DROPIN_BACKWARD;
     const bool training = c.kind == STEP_TRAIN || c.kind == STEP_FORWARD_LOSS;       // (the forward has a hyper)
     // (the chain kernel fuses the plain gather and the unweighted loss and keeps the activations to itself: a noised input, an
-    //  emphasised loss, another criterion, hidden dropout, a skip or a slot-presence table takes the per-layer launches)
+    //  emphasised loss, another criterion, hidden dropout, a skip, a norm or a slot-presence table takes the per-layer launches)
     if (c.kind == STEP_TRAIN && e->chain_ok && e->plain_mse() && e->tc.noise.kind == CODAE_NOISE_NONE && !e->tc.drop.on &&
-        !e->tc.res.any && b->shadow_wt != nullptr && p.rows <= CHAIN_MAX_ROWS) {
+        !e->tc.res.any && !e->tc.norm.any && b->shadow_wt != nullptr && p.rows <= CHAIN_MAX_ROWS) {
         // narrow stack: persistent fused chain + grouped weight gradients (4 launches for the whole step)
         p.path = PATH_CHAIN;
         p.loss = LOSS_IN_CHAIN; p.loss_finish = LOSS_FINISH_CARRIED;
@@ -791,6 +798,19 @@ int run_residual_fwd(codae_engine* e, const codae_buffers* b, int l, int B, bool
                                (e->out[l] + 7) / 8, s);
 }
 
+inline bool norms_layer(const codae_engine* e, int l) { return e->tc.norm.any && l >= 0 && l + 1 < e->L && e->tc.norm.on[l] != 0; }
+
+// act[l + 1] <- N(act[l + 1]) in place behind the forward GEMM of a normalised layer l, behind its dropout and skip kernels; r goes
+// to the setting's work space; training, ReLU / LeakyReLU and no skip: the 1-bit mask of the value before the norm goes there first
+// (a skipped layer's residual kernel has written that mask already).  Part of the MODEL: every forward loop calls it.
+int run_norm_fwd(codae_engine* e, const codae_buffers* b, int l, int B, bool training, hipStream_t s) {
+    char* ws = reinterpret_cast<char*>(e->tc.norm.ws);
+    uint8_t* bits = training && !skips_layer(e, l) && e->norm_bits_off[l] >= 0 ? reinterpret_cast<uint8_t*>(ws + e->norm_bits_off[l]) : nullptr;
+    ProfScope prof(e, CODAE_K_DROPOUT, s);
+    return launch_norm_fwd(act_ptr(e, b, l + 1), e->prec == CODAE_PREC_BF16, e->in_ld[l + 1], B, e->out[l], e->tc.norm.kind, e->tc.norm.eps,
+                           reinterpret_cast<float*>(ws + e->norm_r_off[l]), bits, (e->out[l] + 7) / 8, s);
+}
+
 // the data gradient of layer l and, when layer l - 1 was dropped in the forward, dA_{l-1} <- dA_{l-1} * f right behind it on the same
 // stream: the kernel writes layer l - 1's partial column sums again, from the final values, in place of the GEMM epilogue's (one row
 // per 64 batch rows: within the rows the layer owns), before the caller records the event the side-stream weight gradient waits for
@@ -798,11 +818,43 @@ int run_residual_fwd(codae_engine* e, const codae_buffers* b, int l, int B, bool
 // dropout's: G_l = U_l + skip_l G_{l+1}, kept for the next level when layer l - 1 is skipped too, dA_{l-1} <- G_l * act'_{l-1} and its
 // partial column sums.  act'_{l-1} comes from the 1-bit mask the forward skip kernel wrote when layer l - 1 is skipped (act[l] then
 // holds a_{l-1} + h_{l-1}), else from the saved activation act[l], as the GEMM epilogue takes it.
+// With a norm on layer l - 1 (codae_norm) the GEMM runs unmasked as well and the norm backward kernel takes the residual kernel's place
+// and does its whole job: Gh = U_l + skip_l G, Gs_{l-1} from Gh, xhat = act[l] and r, G <- Gs_{l-1} when layer l - 1 is skipped too,
+// dA_{l-1} <- Gs_{l-1} * act'_{l-1} from the 1-bit mask (the residual's when layer l - 1 is skipped, else the norm's), the column sums.
 int run_dgrad(codae_engine* e, const codae_buffers* b, int l, int rows, bool coscheduled, float* dx_f32, hipStream_t s) {
-    const bool res = dx_f32 == nullptr && l >= 1 && (skips_layer(e, l) || skips_layer(e, l - 1));
+    const bool nrm = dx_f32 == nullptr && l >= 1 && norms_layer(e, l - 1);
+    const bool res = dx_f32 == nullptr && l >= 1 && (nrm || skips_layer(e, l) || skips_layer(e, l - 1));
     int rc = run_dgrad_gemm(e, b, l, rows, coscheduled, dx_f32, s, res);
     if (rc || dx_f32 != nullptr) return rc;
-    if (res) {
+    if (nrm) {
+        const bool bf = e->prec == CODAE_PREC_BF16;
+        const int m = l - 1;                                     // the normalised layer, whose derivative is applied
+        const int kind = e->relu[m] ? CODAE_ACT_RELU : (int)e->act[m];
+        float* G = reinterpret_cast<float*>(e->tc.res.ws);
+        const char* ws = reinterpret_cast<const char*>(e->tc.norm.ws);
+        NormBwd n{};
+        n.xhat = act_ptr(e, b, l); n.ld_x = e->in_ld[l];
+        n.rstd = reinterpret_cast<const float*>(ws + e->norm_r_off[m]);
+        n.g_in = skips_layer(e, l) ? G : nullptr;
+        n.g_out = skips_layer(e, m) && m >= 1 ? G : nullptr;     // (layer 0's input gradient is never formed)
+        n.ld_g = e->in[l];
+        n.act_kind = kind;
+        n.slope = e->act_p[3 * m];
+        if (kind != CODAE_ACT_NONE) {
+            const bool from_skip = skips_layer(e, m);
+            CODAE_REQUIRE(from_skip ? e->res_bits_live : e->norm_bits_live, "backward through the norm of layer %d without a training forward before it", m);
+            const int64_t off = from_skip ? e->res_bits_off[m] : e->norm_bits_off[m];
+            CODAE_REQUIRE(off >= 0, "backward through the norm of layer %d: no 1-bit mask for activation kind %d", m, kind);
+            n.bits = reinterpret_cast<const uint8_t*>(from_skip ? reinterpret_cast<const char*>(e->tc.res.ws) : ws) + off;
+            n.ld_bits = (e->out[m] + 7) / 8;
+        }
+        {
+            ProfScope prof(e, CODAE_K_DROPOUT, s);
+            rc = launch_norm_bwd(dact_ptr(e, b, m), bf, bf ? e->out_ld[m] : e->out[m], e->res_B, e->out[m], e->tc.norm.kind, n, part_ptr(e, b, m), s);
+        }
+        if (rc) return rc;
+        e->parts_pending[m] = norm_blocks(e->res_B);
+    } else if (res) {
         const bool bf = e->prec == CODAE_PREC_BF16;
         const int m = l - 1;                                     // the layer whose derivative is applied
         const int kind = e->relu[m] ? CODAE_ACT_RELU : (int)e->act[m];
@@ -1106,6 +1158,8 @@ int codae_create(const codae_spec* spec, codae_handle* out) {
     // colsum), the stand-alone loss kernel of the last layer one per 32, the persistent chain one per 16
     e->parts_pending.assign(e->L, 0);
     e->res_bits_off.assign(e->L, -1);
+    e->norm_r_off.assign(e->L, -1);
+    e->norm_bits_off.assign(e->L, -1);
     e->part_floats = 0;
     const int chain_rows = e->max_rows < CHAIN_MAX_ROWS ? e->max_rows : CHAIN_MAX_ROWS;
     for (int l = 0; l < e->L; ++l) {
@@ -1249,8 +1303,13 @@ int codae_forward(codae_handle h, const codae_buffers* b, const float* x, float*
                   layer_hi, h->L);
         return CODAE_E_UNSUPPORTED;
     }
+    if (h->tc.norm.any && !(layer_lo == 0 && layer_hi == h->L)) {
+        set_error("codae_forward: a norm is on: a forward over the layer range [%d, %d) of %d layers is not supported", layer_lo, layer_hi, h->L);
+        return CODAE_E_UNSUPPORTED;
+    }
     h->drop_live = false;     // (a drop-in forward never drops)
     h->res_bits_live = false; // (nor writes the skips' masks)
+    h->norm_bits_live = false;
     hipStream_t s = (hipStream_t)stream;
     const int rows = h->rows_for(B);
     // ingest x into act[layer_lo] in working precision (no gather, no mask)
@@ -1273,6 +1332,10 @@ int codae_forward(codae_handle h, const codae_buffers* b, const float* x, float*
             rc = run_residual_fwd(h, b, l, B, false, s);
             if (rc) return rc;
         }
+        if (norms_layer(h, l)) {
+            rc = run_norm_fwd(h, b, l, B, false, s);
+            if (rc) return rc;
+        }
     }
     return CODAE_OK;
 }
@@ -1286,6 +1349,11 @@ int codae_backward(codae_handle h, const codae_buffers* b, const float* dy, floa
     if (h->tc.res.any) {
         // (the drop-in forward writes no masks, and its sub-chains cut the sum G across the cut)
         set_error("codae_backward: residual connections are on: the drop-in backward is not supported (use the step entry points)");
+        return CODAE_E_UNSUPPORTED;
+    }
+    if (h->tc.norm.any) {
+        // (the drop-in forward writes no masks, and a sub-chain's forward does not normalise)
+        set_error("codae_backward: a norm is on: the drop-in backward is not supported (use the step entry points)");
         return CODAE_E_UNSUPPORTED;
     }
     hipStream_t s = (hipStream_t)stream;
@@ -1399,6 +1467,7 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
     if (h->drop_live) { h->drop_B = B; h->drop_rows = batch->row_idx; h->drop_step = hyper->step; }
     // residual connections: every forward adds the skips; a training forward also leaves their 1-bit masks for the backward
     h->res_bits_live = hyper != nullptr && h->tc.res.any;
+    h->norm_bits_live = hyper != nullptr && h->tc.norm.any;
     const uint8_t* const pres = h->tc.pres.table;
     const int pres_slots = h->tc.pres.n_slots;
     const bool fuse_loss = plan.loss == LOSS_FUSED, fold_finish = plan.loss_finish == LOSS_FINISH_CARRIED;
@@ -1420,7 +1489,7 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
     if (rc) return rc;
     float* y = out_y ? out_y : reinterpret_cast<float*>(act_ptr(h, b, L));
     GroupScope fwd_group(h, CODAE_K_GEMM_FWD, s);       // the plain forward launches of this step, back to back
-    if (h->drop_live || h->tc.res.any) fwd_group.close();   // (streaming kernels sit between them: every launch gets its own event pair)
+    if (h->drop_live || h->tc.res.any || h->tc.norm.any) fwd_group.close();   // (streaming kernels sit between them: every launch gets its own event pair)
     for (int l = 0; l < L; ++l) {
         const bool last = (l == L - 1);
         if (last && fuse_loss) {
@@ -1461,6 +1530,10 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
         }
         if (skips_layer(h, l)) {
             rc = run_residual_fwd(h, b, l, B, hyper != nullptr, s);
+            if (rc) return rc;
+        }
+        if (norms_layer(h, l)) {
+            rc = run_norm_fwd(h, b, l, B, hyper != nullptr, s);
             if (rc) return rc;
         }
     }
@@ -1734,6 +1807,70 @@ int codae_set_residual(codae_handle h, const codae_residual* r, void* ws, int64_
     return CODAE_OK;
 }
 
+// The canonical flags of a codae_norm on this stack (all zero = off) and the layout of its work space: r of every normalised layer
+// first, then the 1-bit mask of every normalised layer with a ReLU or a LeakyReLU.  CODAE_E_INVALID / CODAE_E_UNSUPPORTED as
+// codae_set_norm documents.
+static int norm_layout(codae_handle h, const codae_norm* n, const char* who, uint8_t* on, std::vector<int64_t>* r_off, std::vector<int64_t>* bits_off,
+                       int64_t* bytes) {
+    memset(on, 0, 64);
+    if (r_off) r_off->assign(h->L, -1);
+    if (bits_off) bits_off->assign(h->L, -1);
+    *bytes = 0;
+    if (n == nullptr) return CODAE_OK;
+    CODAE_REQUIRE(n->n == h->L, "%s: %d flags for %d layers", who, n->n, h->L);
+    CODAE_REQUIRE(n->on != nullptr, "%s: null on", who);
+    CODAE_REQUIRE(n->kind == CODAE_NORM_LAYER || n->kind == CODAE_NORM_RMS, "%s: kind %d is neither CODAE_NORM_LAYER nor CODAE_NORM_RMS", who, n->kind);
+    CODAE_REQUIRE(n->eps > 0.f && n->eps <= 3.402823466e38f, "%s: eps %g must be finite and > 0", who, (double)n->eps);
+    int64_t off = 0;
+    for (int l = 0; l < h->L; ++l) {
+        if (!n->on[l]) continue;
+        // (act[l] names the generic activations only: NONE below is "no activation or ReLU", see residual_layout)
+        const char* why = nullptr;
+        if (l == h->L - 1) why = "the last layer's output is the reconstruction and takes no norm";
+        else if (h->act[l] != CODAE_ACT_NONE && h->act[l] != CODAE_ACT_LEAKY) why = "a normalised layer's activation must be none, ReLU or LeakyReLU";
+        if (why != nullptr) {
+            set_error("%s: layer %d (%d -> %d, activation kind %d): %s", who, l, h->in[l], h->out[l], h->relu[l] ? CODAE_ACT_RELU : (int)h->act[l], why);
+            return CODAE_E_UNSUPPORTED;
+        }
+        on[l] = 1;
+        if (r_off) (*r_off)[l] = off;
+        off += round_up((int64_t)h->max_batch * 4, 256);
+    }
+    for (int l = 0; l < h->L; ++l) {
+        if (!on[l] || !(h->relu[l] || h->act[l] == CODAE_ACT_LEAKY)) continue;
+        if (bits_off) (*bits_off)[l] = off;
+        off += round_up((int64_t)h->max_batch * ((h->out[l] + 7) / 8), 256);
+    }
+    *bytes = off;
+    return CODAE_OK;
+}
+
+int64_t codae_norm_ws_bytes(codae_handle h, const codae_norm* n) {
+    if (h == nullptr) { set_error("codae_norm_ws_bytes: null handle"); return -1; }
+    uint8_t on[64];
+    int64_t bytes = 0;
+    return norm_layout(h, n, "codae_norm_ws_bytes", on, nullptr, nullptr, &bytes) == CODAE_OK ? bytes : -1;
+}
+
+int codae_set_norm(codae_handle h, const codae_norm* n, void* ws, int64_t ws_bytes) {
+    CODAE_REQUIRE(h != nullptr, "codae_set_norm: null handle");
+    codae_engine::NormCfg c{};           // (built field by field: the graph key compares bytes)
+    std::vector<int64_t> r_off, bits_off;
+    int64_t need = 0;
+    int rc = norm_layout(h, n, "codae_set_norm", c.on, &r_off, &bits_off, &need);
+    if (rc) return rc;
+    if (need > 0) {
+        CODAE_REQUIRE(ws != nullptr && (reinterpret_cast<uintptr_t>(ws) & 15) == 0 && ws_bytes >= need,
+                      "codae_set_norm: the work space must be 16-byte aligned and hold %lld bytes (got %lld)", (long long)need, (long long)ws_bytes);
+        c.ws = ws; c.ws_bytes = ws_bytes; c.any = 1; c.kind = n->kind; c.eps = n->eps;
+    }
+    h->tc.norm = c;
+    h->norm_r_off = r_off;
+    h->norm_bits_off = bits_off;
+    h->norm_bits_live = false;
+    return CODAE_OK;
+}
+
 int codae_eval_step(codae_handle h, const codae_buffers* b, const codae_batch* batch, float* out_y, void* stream) {
     return codae_step_forward_loss(h, b, batch, nullptr, out_y, stream);
 }
@@ -1765,6 +1902,7 @@ int codae_score_outfits(codae_handle h, const codae_buffers* b, const float* dat
     const int rows = h->rows_for(B);
     h->drop_live = false;     // (an evaluation forward never drops)
     h->res_bits_live = false;
+    h->norm_bits_live = false;
     const codae_engine::ImageCfg& im = h->tc.img;
     const bool from_image = bf && !h->cfg.no_dataset_image && im.image != nullptr && data == im.data && io == im.io && n_rows == im.n_rows;
     {
@@ -1782,6 +1920,10 @@ int codae_score_outfits(codae_handle h, const codae_buffers* b, const float* dat
         if (rc) return rc;
         if (skips_layer(h, l)) {
             rc = run_residual_fwd(h, b, l, B, false, s);
+            if (rc) return rc;
+        }
+        if (norms_layer(h, l)) {
+            rc = run_norm_fwd(h, b, l, B, false, s);
             if (rc) return rc;
         }
     }

@@ -1,0 +1,234 @@
+// Normalisation (codae_norm, include/codae_hip.h): two streaming kernels around the GEMMs of a normalised layer l; a wave owns a row.
+//   forward   behind the forward GEMM of layer l (and its dropout and skip kernels): the row statistics in fp32 from the stored
+//             values, act[l + 1] <- rne(xhat) in place, r[b]; a training forward of a ReLU / LeakyReLU layer without a skip first
+//             leaves the 1-bit mask "value > 0" of what it read - afterwards act[l + 1] holds xhat, whose sign says nothing
+//   backward  behind the UNMASKED data-gradient GEMM of layer l + 1, which left U in dA_l: Gh = U + G (iff layer l + 1 is skipped),
+//             the row reductions c1, c2 against xhat = act[l + 1] and r, Gs = r (Gh - c1 - xhat c2), G <- Gs (iff layer l is
+//             skipped), dA_l <- D_l = Gs * act'_l, + the column sums of the stored D: the residual backward kernel's whole job
+// The row is RE-READ, not kept in registers: one code path for every width (the fp32 engine runs 21 and 11, the headline 1536, and
+// nothing bounds it), no register-count cliff and no scratch; a wave re-reads only what it read itself a pass earlier, 3 KB per bf16
+// row at the headline width, which the passes after the first find in the caches - HBM sees every matrix once.
+// Templates on <BF16, VEC, KIND>: 16 B per access where every row is 16-B aligned and the width is whole chunks, element accesses
+// otherwise; pad columns and pad rows are never written (xhat of a zero pad column would be -mu r, and the next GEMM's k runs over it).
+#include "codae_common.h"
+#include "row_access.h"
+
+namespace codae {
+namespace {
+
+// A lane owns 8 columns per chunk whatever the type - one 16-B access of bf16, two of fp32: exactly one mask byte.
+constexpr int NC = 8;
+
+// The sum of the wave's 64 values: a butterfly.  a + b and b + a have the same bits, so after every stage the two partners hold
+// the same value and the result does not depend on the lane; lane 0's copy is broadcast to say so.
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = opaque(v + __shfl_xor(v, m, 64));
+    return __shfl(v, 0, 64);
+}
+
+// ---- forward ----------------------------------------------------------------------------------------------------------------
+constexpr int FWD_WAVES = 4, FWD_NT = 64 * FWD_WAVES;
+
+template <bool BF16, bool VEC, int KIND>
+__global__ __launch_bounds__(FWD_NT) void norm_fwd_kernel(void* __restrict__ y, int64_t ld, int B, int width, float eps,
+                                                          float* __restrict__ rstd, uint8_t* __restrict__ bits, int64_t ld_bits) {
+    constexpr int ES = BF16 ? 2 : 4;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const float w = (float)width;
+    for (int b = blockIdx.x * FWD_WAVES + wave; b < B; b += gridDim.x * FWD_WAVES) {
+        char* row = reinterpret_cast<char*>(y) + (int64_t)b * ld * ES;
+        // pass 1: sum x (layer) or sum x^2 (rms), a lane's columns in ascending order; the mask of what was read
+        float s = 0.f;
+        for (int c = lane * NC; c < width; c += 64 * NC) {
+            float x[NC];
+            load_work<BF16, VEC, NC>(row, c, width, x);
+            uint32_t m = 0;
+#pragma unroll
+            for (int k = 0; k < NC; ++k) {
+                m |= positive_bit(x[k]) << k;                  // (a column past the width was loaded as +0: bit clear)
+                s = (KIND == CODAE_NORM_LAYER) ? opaque(s + x[k]) : opaque(s + opaque(x[k] * x[k]));
+            }
+            if (bits != nullptr) bits[(int64_t)b * ld_bits + (c >> 3)] = (uint8_t)m;
+        }
+        s = wave_sum(s);
+        float mu = 0.f;
+        if constexpr (KIND == CODAE_NORM_LAYER) {
+            // pass 2: the centred squares (a column past the width would add mu^2: left out)
+            mu = s / w;
+            s = 0.f;
+            for (int c = lane * NC; c < width; c += 64 * NC) {
+                float x[NC];
+                load_work<BF16, VEC, NC>(row, c, width, x);
+#pragma unroll
+                for (int k = 0; k < NC; ++k) {
+                    const float dlt = opaque(x[k] - mu);
+                    if (c + k < width) s = opaque(s + opaque(dlt * dlt));
+                }
+            }
+            s = wave_sum(s);
+        }
+        const float r = 1.f / sqrtf(opaque(s / w) + eps);
+        // pass 3: xhat in place
+        for (int c = lane * NC; c < width; c += 64 * NC) {
+            float x[NC], out[NC];
+            load_work<BF16, VEC, NC>(row, c, width, x);
+#pragma unroll
+            for (int k = 0; k < NC; ++k) x[k] = (KIND == CODAE_NORM_LAYER) ? opaque(x[k] - mu) * r : x[k] * r;
+            store_work<BF16, VEC, NC>(row, c, width, x, out);
+        }
+        if (lane == 0) rstd[b] = r;
+    }
+}
+
+// ---- backward ---------------------------------------------------------------------------------------------------------------
+// The row blocking, block shape and column reduction of residual_bwd_kernel: one block per 64 batch rows and all columns, 1024
+// threads, wave w owns rows 4 w .. 4 w + 3.  First the row reductions of its four rows, then tile by tile (64 chunks of 8 columns)
+// the write-out: a thread adds its four rows' STORED values in row order, the 16 waves' sums meet in LDS and are added in wave
+// order by one thread per column: a fixed order, no atomics.
+constexpr int BWD_ROWS = 64, BWD_WAVES = 16, BWD_NT = 64 * BWD_WAVES, BWD_RPW = BWD_ROWS / BWD_WAVES, BWD_TILE = 64 * NC;
+
+// Gh columns [c, c + NC) of row b: U from d, + G when the layer behind is skipped (one fp32 add)
+template <bool BF16, bool VEC>
+__device__ __forceinline__ void load_gh(const char* drow, const float* grow, int c, int width, float* g) {
+    load_work<BF16, VEC, NC>(drow, c, width, g);
+    if (grow != nullptr) {
+        float gi[NC];
+        load_work<false, VEC, NC>(grow, c, width, gi);
+#pragma unroll
+        for (int k = 0; k < NC; ++k) g[k] = opaque(g[k] + gi[k]);
+    }
+}
+
+template <bool BF16, bool VEC, int KIND>
+__global__ __launch_bounds__(BWD_NT) void norm_bwd_kernel(void* d, int64_t ld, int B, int width, NormBwd n, float* __restrict__ colsum_part) {
+    constexpr int ES = BF16 ? 2 : 4;
+    __shared__ float red[BWD_WAVES][BWD_TILE];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int row0 = blockIdx.x * BWD_ROWS + wave * BWD_RPW;
+    const float w = (float)width;
+    const bool selects = n.act_kind == CODAE_ACT_RELU;         // (ReLU selects 0 under a dead unit, LeakyReLU multiplies)
+    float c1[BWD_RPW], c2[BWD_RPW], r[BWD_RPW];
+#pragma unroll
+    for (int i = 0; i < BWD_RPW; ++i) {
+        const int b = row0 + i;
+        c1[i] = 0.f; c2[i] = 0.f; r[i] = 0.f;
+        if (b < B) {                                           // (wave-uniform)
+            const char* drow = reinterpret_cast<const char*>(d) + (int64_t)b * ld * ES;
+            const char* xrow = reinterpret_cast<const char*>(n.xhat) + (int64_t)b * n.ld_x * ES;
+            const float* grow = n.g_in != nullptr ? n.g_in + (int64_t)b * n.ld_g : nullptr;
+            float s1 = 0.f, s2 = 0.f;
+            for (int c = lane * NC; c < width; c += 64 * NC) {
+                float g[NC], xh[NC];
+                load_gh<BF16, VEC>(drow, grow, c, width, g);
+                load_work<BF16, VEC, NC>(xrow, c, width, xh);
+#pragma unroll
+                for (int k = 0; k < NC; ++k) {                 // (a column past the width was loaded as 0 in both)
+                    if constexpr (KIND == CODAE_NORM_LAYER) s1 = opaque(s1 + g[k]);
+                    s2 = opaque(s2 + opaque(g[k] * xh[k]));
+                }
+            }
+            if constexpr (KIND == CODAE_NORM_LAYER) c1[i] = wave_sum(s1) / w;
+            c2[i] = wave_sum(s2) / w;
+            r[i] = n.rstd[b];
+        }
+    }
+    for (int t0 = 0; t0 < width; t0 += BWD_TILE) {
+        const int c = t0 + lane * NC;
+        float sum[NC];
+#pragma unroll
+        for (int k = 0; k < NC; ++k) sum[k] = 0.f;
+        if (c < width) {
+#pragma unroll
+            for (int i = 0; i < BWD_RPW; ++i) {
+                const int b = row0 + i;
+                if (b < B) {
+                    char* drow = reinterpret_cast<char*>(d) + (int64_t)b * ld * ES;
+                    const char* xrow = reinterpret_cast<const char*>(n.xhat) + (int64_t)b * n.ld_x * ES;
+                    const float* grow = n.g_in != nullptr ? n.g_in + (int64_t)b * n.ld_g : nullptr;
+                    float g[NC], xh[NC], out[NC];
+                    load_gh<BF16, VEC>(drow, grow, c, width, g);                      // Gh, the bits the reductions saw
+                    load_work<BF16, VEC, NC>(xrow, c, width, xh);
+#pragma unroll
+                    for (int k = 0; k < NC; ++k) {
+                        float t = opaque(g[k] - opaque(xh[k] * c2[i]));
+                        if constexpr (KIND == CODAE_NORM_LAYER) t = opaque(t - c1[i]);
+                        g[k] = opaque(t * r[i]);                                      // Gs
+                    }
+                    if (n.g_out != nullptr) {
+                        float unused[NC];
+                        store_work<false, VEC, NC>(n.g_out + (int64_t)b * n.ld_g, c, width, g, unused);
+                    }
+                    if (n.bits != nullptr) {
+                        const uint32_t m = (uint32_t)n.bits[(int64_t)b * n.ld_bits + (c >> 3)];
+#pragma unroll
+                        for (int k = 0; k < NC; ++k) g[k] = ((m >> k) & 1u) ? g[k] : (selects ? 0.f : opaque(g[k] * n.slope));
+                    }
+                    store_work<BF16, VEC, NC>(drow, c, width, g, out);                // D
+#pragma unroll
+                    for (int k = 0; k < NC; ++k) sum[k] = opaque(sum[k] + out[k]);
+                }
+            }
+        }
+        if (colsum_part != nullptr) {                          // (block-uniform)
+#pragma unroll
+            for (int k = 0; k < NC; ++k) red[wave][lane * NC + k] = sum[k];
+            __syncthreads();
+            if (threadIdx.x < BWD_TILE && t0 + (int)threadIdx.x < width) {
+                float s = red[0][threadIdx.x];
+#pragma unroll
+                for (int wv = 1; wv < BWD_WAVES; ++wv) s = opaque(s + red[wv][threadIdx.x]);
+                colsum_part[(int64_t)blockIdx.x * width + t0 + threadIdx.x] = s;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+}  // namespace
+
+int launch_norm_fwd(void* y, int bf16, int64_t ld, int B, int width, int kind, float eps, float* rstd, uint8_t* bits, int64_t ld_bits,
+                    hipStream_t s) {
+    CODAE_REQUIRE(y != nullptr && rstd != nullptr, "codae_norm_fwd: null matrix or rstd");
+    CODAE_REQUIRE(B > 0 && width > 0 && ld >= width, "codae_norm_fwd: B %d, width %d, ld %lld", B, width, (long long)ld);
+    CODAE_REQUIRE(kind == CODAE_NORM_LAYER || kind == CODAE_NORM_RMS, "codae_norm_fwd: kind %d is neither CODAE_NORM_LAYER nor CODAE_NORM_RMS", kind);
+    CODAE_REQUIRE(eps > 0.f && eps <= 3.402823466e38f, "codae_norm_fwd: eps %g must be finite and > 0", (double)eps);
+    CODAE_REQUIRE(bits == nullptr || ld_bits >= (width + 7) / 8, "codae_norm_fwd: ld_bits %lld for %d columns", (long long)ld_bits, width);
+    const int per = bf16 ? 8 : 4;
+    const bool vec = aligned16(y) && ld % per == 0 && width % per == 0;
+    int blocks = (B + FWD_WAVES - 1) / FWD_WAVES;
+    if (blocks > 4096) blocks = 4096;
+#define NF(BF, V, K) hipLaunchKernelGGL((norm_fwd_kernel<BF, V, K>), dim3(blocks), dim3(FWD_NT), 0, s, y, ld, B, width, eps, rstd, bits, ld_bits)
+#define NFK(BF, V) do { if (kind == CODAE_NORM_LAYER) NF(BF, V, CODAE_NORM_LAYER); else NF(BF, V, CODAE_NORM_RMS); } while (0)
+    if (bf16) { if (vec) NFK(true, true); else NFK(true, false); }
+    else { if (vec) NFK(false, true); else NFK(false, false); }
+#undef NFK
+#undef NF
+    CODAE_LAUNCH_CHECK();
+    return CODAE_OK;
+}
+
+int launch_norm_bwd(void* d, int bf16, int64_t ld, int B, int width, int kind, const NormBwd& n, float* colsum_part, hipStream_t s) {
+    CODAE_REQUIRE(d != nullptr && n.xhat != nullptr && n.rstd != nullptr && d != n.xhat, "codae_norm_bwd: null or aliased matrix, xhat or rstd");
+    CODAE_REQUIRE(B > 0 && width > 0 && ld >= width && n.ld_x >= width, "codae_norm_bwd: B %d, width %d, ld %lld, ld_x %lld", B, width,
+                  (long long)ld, (long long)n.ld_x);
+    CODAE_REQUIRE(kind == CODAE_NORM_LAYER || kind == CODAE_NORM_RMS, "codae_norm_bwd: kind %d is neither CODAE_NORM_LAYER nor CODAE_NORM_RMS", kind);
+    CODAE_REQUIRE((n.g_in == nullptr && n.g_out == nullptr) || n.ld_g >= width, "codae_norm_bwd: ld_g %lld for %d columns", (long long)n.ld_g, width);
+    CODAE_REQUIRE(n.bits == nullptr || n.ld_bits >= (width + 7) / 8, "codae_norm_bwd: ld_bits %lld for %d columns", (long long)n.ld_bits, width);
+    CODAE_REQUIRE(n.bits == nullptr || n.act_kind == CODAE_ACT_RELU || n.act_kind == CODAE_ACT_LEAKY,
+                  "codae_norm_bwd: 1-bit masks carry the derivative of ReLU and LeakyReLU only (kind %d)", n.act_kind);
+    const int per = bf16 ? 8 : 4;
+    bool vec = aligned16(d) && aligned16(n.xhat) && ld % per == 0 && n.ld_x % per == 0 && width % per == 0;
+    if (n.g_in != nullptr || n.g_out != nullptr) vec = vec && aligned16(n.g_in) && aligned16(n.g_out) && n.ld_g % 4 == 0;
+    const int blocks = norm_blocks(B);
+#define NB(BF, V, K) hipLaunchKernelGGL((norm_bwd_kernel<BF, V, K>), dim3(blocks), dim3(BWD_NT), 0, s, d, ld, B, width, n, colsum_part)
+#define NBK(BF, V) do { if (kind == CODAE_NORM_LAYER) NB(BF, V, CODAE_NORM_LAYER); else NB(BF, V, CODAE_NORM_RMS); } while (0)
+    if (bf16) { if (vec) NBK(true, true); else NBK(true, false); }
+    else { if (vec) NBK(false, true); else NBK(false, false); }
+#undef NBK
+#undef NB
+    CODAE_LAUNCH_CHECK();
+    return CODAE_OK;
+}
+
+}  // namespace codae

@@ -197,6 +197,20 @@ int codae_residual_bwd(void* d, int32_t bf16, int64_t ld, int32_t B, int32_t wid
 
 int codae_residual_blocks(int32_t B) { return B > 0 ? residual_blocks(B) : 0; }
 
+int codae_norm_fwd(void* y, int32_t bf16, int64_t ld, int32_t B, int32_t width, int32_t kind, float eps, float* rstd, uint8_t* bits,
+                   int64_t ld_bits, void* stream) {
+    return launch_norm_fwd(y, bf16, ld, B, width, kind, eps, rstd, bits, ld_bits, (hipStream_t)stream);
+}
+
+int codae_norm_bwd(void* d, int32_t bf16, int64_t ld, int32_t B, int32_t width, int32_t kind, const void* xhat, int64_t ld_x,
+                   const float* rstd, const float* g_in, float* g_out, int64_t ld_g, const uint8_t* bits, int64_t ld_bits,
+                   int32_t act_kind, const float* act_param, float* colsum_part, void* stream) {
+    NormBwd n{xhat, ld_x, rstd, g_in, g_out, ld_g, bits, ld_bits, act_kind, act_param != nullptr ? act_param[0] : 0.f};
+    return launch_norm_bwd(d, bf16, ld, B, width, kind, n, colsum_part, (hipStream_t)stream);
+}
+
+int codae_norm_blocks(int32_t B) { return B > 0 ? norm_blocks(B) : 0; }
+
 int codae_noise_box_muller(const uint32_t* ra, const uint32_t* rb, float* rho, float* c, float* s, int64_t n, void* stream) {
     return launch_noise_box_muller(ra, rb, rho, c, s, n, (hipStream_t)stream);
 }

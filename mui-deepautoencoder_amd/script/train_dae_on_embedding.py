@@ -163,6 +163,10 @@ def main():
     # in training and in validation alike (it is part of the model)
     from codae.tool.residual import residual_from_config
     residual = residual_from_config(config.get("HIP", {}).get("RESIDUAL"))
+    # HIP: NORM: {KIND: layer | rms, LAYERS: hidden | [0, 1, ..], EPS: 1e-5} (build-only key): parameter-free normalisation of the chosen
+    # layers' outputs per batch row, in training and in validation alike (it is part of the model)
+    from codae.tool.norm import norm_from_config
+    norm = norm_from_config(config.get("HIP", {}).get("NORM"))
     # HIP: CRITERION: {KIND: mse | l1 | smooth_l1 | huber | slot_cosine, BETA: .., DELTA: .., MSE_WEIGHT: ..} (build-only key): the
     # training loss instead of the mean squared error (the monitors stay squared-error sums; validation never sees it)
     from codae.tool.recon_loss import recon_loss_from_config
@@ -196,7 +200,7 @@ def main():
                                    max_batch=mc["BATCH_SIZE"], precision=prec, device=device, distributed=world > 1,
                                    activation=activation, input_noise=input_noise, loss_emphasis=loss_emphasis,
                                    hidden_dropout=hidden_dropout, criterion=criterion, contrast=contrast, optimizer=optimizer,
-                                   presence=presence, tied_weights=tied_weights, weight_average=weight_average, residual=residual)
+                                   presence=presence, tied_weights=tied_weights, weight_average=weight_average, residual=residual, norm=norm)
     try:
         trainer = build(precision)
     except HipError as e:
@@ -214,6 +218,8 @@ def main():
                                                             sum(k * n + n for k, n, _ in enc + dec)))
     if trainer.engine.residual_layers:
         log.info("RESIDUAL: %r - identity skips around layers %s" % (residual, trainer.engine.residual_layers))
+    if trainer.engine.norm_layers:
+        log.info("NORM: %r - %s normalisation of the outputs of layers %s" % (norm, norm.kind, trainer.engine.norm_layers))
     if eval_weights == "average":
         log.info("WEIGHT AVERAGE: %r - the validation errors and the ranking error are those of the averaged weights" % (weight_average,))
     book = {k: [] for k in ("ftl", "ptl", "fvl", "pvl", "rl")}
