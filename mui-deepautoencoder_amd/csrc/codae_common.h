@@ -557,47 +557,23 @@ int launch_slot_contrast_prepare(const float* data, int io, const codae_slot_con
                                  hipStream_t s, const uint8_t* present = nullptr, int n_slots = 0);
 int launch_slot_contrast(const LossLaunch& ll, const codae_slot_contrast* c, hipStream_t s);
 int launch_slot_contrast_finish(double* scalars, double scale, const double* parts, int n_parts, hipStream_t s);
+// The streaming kernels between a step's GEMMs (dropout.hip, residual.hip, norm.hip).  Their backward forms share one sweep
+// (row_sweep.h): row_sweep_blocks(B) blocks of 64 batch rows, each leaving one row of colsum_part [blocks][width] (column sums of
+// the STORED values; may be null).
+inline int row_sweep_blocks(int B) { return (B + 63) / 64; }
 // Hidden dropout (codae_dropout, include/codae_hip.h; dropout.hip): a <- a * f in place on rows < B, columns < width of a [B][ld]
 // matrix (fp32 or bf16), f from the Philox words of counter (column / 4, dataset row, step, 1 + layer); step_dev as
-// launch_gather_noise.  The backward form takes dropout_blocks(B) blocks, each leaving one row of colsum_part [blocks][width]
-// (column sums of the stored values; may be null).  check_dropout_p: CODAE_E_INVALID for p outside [0, 1) or not finite.
+// launch_gather_noise.  check_dropout_p: CODAE_E_INVALID for p outside [0, 1) or not finite.
 int check_dropout_p(float p, const char* who);
-inline int dropout_blocks(int B) { return (B + 63) / 64; }
 int launch_dropout_fwd(void* a, int bf16, int64_t ld, int B, int width, const int32_t* row_idx, int layer, int32_t step,
                        const double* step_dev, float p, uint64_t seed, hipStream_t s);
 int launch_dropout_bwd(void* d, int bf16, int64_t ld, int B, int width, const int32_t* row_idx, int layer, int32_t step,
                        const double* step_dev, float p, uint64_t seed, float* colsum_part, hipStream_t s);
-// Residual connections (codae_residual, include/codae_hip.h; residual.hip): the two streaming kernels of a skipped layer.
-// forward: y <- rne(y + x) in place on rows < B, columns < width (fp32 or bf16); bits != null: first the 1-bit mask "stored y > 0" of
-// the value BEFORE the add, 8 columns per byte, column 8 j + k in bit k of byte j (the layout of the forward GEMM's masks).
-// backward: U = d (working precision), G = U + g_in (one fp32 add; g_in may be null), g_out <- G (may be null, may be g_in),
-// d <- D = G * act' rounded to the working type, act' from `bits` (act_kind RELU selects, LEAKY multiplies by act_p[0]), from the
-// saved activation `src` (any CODAE_ACT_* kind) or 1 (both null); residual_blocks(B) blocks, each leaving one row of colsum_part
-// [blocks][width] (column sums of the stored D; may be null).
-struct ResidualBwd {
-    const float* g_in;
-    float* g_out;
-    int64_t ld_g;
-    const uint8_t* bits;
-    int64_t ld_bits;
-    const void* src;
-    int64_t ld_src;
-    int act_kind;
-    float act_p[3];
-};
-inline int residual_blocks(int B) { return (B + 63) / 64; }
-int launch_residual_fwd(void* y, const void* x, int bf16, int64_t ldy, int64_t ldx, int B, int width, uint8_t* bits, int64_t ld_bits,
-                        hipStream_t s);
-int launch_residual_bwd(void* d, int bf16, int64_t ld, int B, int width, const ResidualBwd& r, float* colsum_part, hipStream_t s);
-// Normalisation (codae_norm, include/codae_hip.h; norm.hip): the two streaming kernels of a normalised layer, a wave per row.
-// forward: bits != null: first the 1-bit mask "stored y > 0" (layout of the residual masks); then y <- xhat in place on rows < B,
-// columns < width, rstd[b] <- r.  backward: Gh = d + g_in (g_in may be null), Gs = r (Gh - c1 - xhat c2) (LAYER) / r (Gh - xhat c2)
-// (RMS), g_out <- Gs (may be null, may be g_in), d <- D = Gs * act' rounded to the working type, act' from `bits` (act_kind RELU
-// selects, LEAKY multiplies by slope) or 1 (null); norm_blocks(B) blocks, each leaving one row of colsum_part [blocks][width].
-struct NormBwd {
-    const void* xhat;
-    int64_t ld_x;
-    const float* rstd;
+// What the residual and the norm backward kernels share, behind the UNMASKED data-gradient GEMM that left U in d: the gradient
+// carried past skips - Gh = U + g_in (one fp32 add; g_in may be null), g_out <- the kernel's G (may be null, may be g_in), rows ld_g
+// apart - and the derivative from a 1-bit mask: d <- D = G * act' rounded to the working type, act_kind RELU selects, LEAKY
+// multiplies by slope; bits null = the kernel's other source of act', or 1.
+struct StreamBwd {
     const float* g_in;
     float* g_out;
     int64_t ld_g;
@@ -606,7 +582,26 @@ struct NormBwd {
     int act_kind;
     float slope;
 };
-inline int norm_blocks(int B) { return (B + 63) / 64; }
+// Residual connections (codae_residual, include/codae_hip.h; residual.hip): the two streaming kernels of a skipped layer.
+// forward: y <- rne(y + x) in place on rows < B, columns < width (fp32 or bf16); bits != null: first the 1-bit mask "stored y > 0" of
+// the value BEFORE the add, 8 columns per byte, column 8 j + k in bit k of byte j (the layout of the forward GEMM's masks).
+// backward: G = Gh; act' from `bits`, from the saved activation `src` (any CODAE_ACT_* kind, parameters act_p) or 1 (both null).
+struct ResidualBwd : StreamBwd {
+    const void* src;
+    int64_t ld_src;
+    float act_p[3];
+};
+int launch_residual_fwd(void* y, const void* x, int bf16, int64_t ldy, int64_t ldx, int B, int width, uint8_t* bits, int64_t ld_bits,
+                        hipStream_t s);
+int launch_residual_bwd(void* d, int bf16, int64_t ld, int B, int width, const ResidualBwd& r, float* colsum_part, hipStream_t s);
+// Normalisation (codae_norm, include/codae_hip.h; norm.hip): the two streaming kernels of a normalised layer, a wave per row.
+// forward: bits != null: first the 1-bit mask "stored y > 0" (layout of the residual masks); then y <- xhat in place on rows < B,
+// columns < width, rstd[b] <- r.  backward: G = Gs = r (Gh - c1 - xhat c2) (LAYER) / r (Gh - xhat c2) (RMS); act' from `bits` or 1.
+struct NormBwd : StreamBwd {
+    const void* xhat;
+    int64_t ld_x;
+    const float* rstd;
+};
 int launch_norm_fwd(void* y, int bf16, int64_t ld, int B, int width, int kind, float eps, float* rstd, uint8_t* bits, int64_t ld_bits,
                     hipStream_t s);
 int launch_norm_bwd(void* d, int bf16, int64_t ld, int B, int width, int kind, const NormBwd& n, float* colsum_part, hipStream_t s);

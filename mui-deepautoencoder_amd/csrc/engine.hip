@@ -790,7 +790,7 @@ int run_dropout_fwd(codae_engine* e, const codae_buffers* b, int l, hipStream_t 
 inline bool skips_layer(const codae_engine* e, int l) { return e->tc.res.any && l >= 0 && l + 1 < e->L && e->tc.res.on[l] != 0; }
 
 // act[l + 1] <- act[l + 1] + act[l] behind the forward GEMM of a skipped layer l (and behind its dropout kernel); training: the
-// 1-bit mask of the value before the add goes to the setting's work space first.  Part of the MODEL: every forward loop calls it.
+// 1-bit mask of the value before the add goes to the setting's work space first.
 int run_residual_fwd(codae_engine* e, const codae_buffers* b, int l, int B, bool training, hipStream_t s) {
     uint8_t* bits = training && e->res_bits_off[l] >= 0 ? reinterpret_cast<uint8_t*>(e->tc.res.ws) + e->res_bits_off[l] : nullptr;
     ProfScope prof(e, CODAE_K_DROPOUT, s);
@@ -802,13 +802,53 @@ inline bool norms_layer(const codae_engine* e, int l) { return e->tc.norm.any &&
 
 // act[l + 1] <- N(act[l + 1]) in place behind the forward GEMM of a normalised layer l, behind its dropout and skip kernels; r goes
 // to the setting's work space; training, ReLU / LeakyReLU and no skip: the 1-bit mask of the value before the norm goes there first
-// (a skipped layer's residual kernel has written that mask already).  Part of the MODEL: every forward loop calls it.
+// (a skipped layer's residual kernel has written that mask already).
 int run_norm_fwd(codae_engine* e, const codae_buffers* b, int l, int B, bool training, hipStream_t s) {
     char* ws = reinterpret_cast<char*>(e->tc.norm.ws);
     uint8_t* bits = training && !skips_layer(e, l) && e->norm_bits_off[l] >= 0 ? reinterpret_cast<uint8_t*>(ws + e->norm_bits_off[l]) : nullptr;
     ProfScope prof(e, CODAE_K_DROPOUT, s);
     return launch_norm_fwd(act_ptr(e, b, l + 1), e->prec == CODAE_PREC_BF16, e->in_ld[l + 1], B, e->out[l], e->tc.norm.kind, e->tc.norm.eps,
                            reinterpret_cast<float*>(ws + e->norm_r_off[l]), bits, (e->out[l] + 7) / 8, s);
+}
+
+// What a forward leaves for the backward entry points, which take no batch: a training forward (hyper not null) of a stack with
+// dropout, skips or a norm says that the activations were dropped - with the batch rows, row indices and step of that forward - and
+// that the skips' and the norm's 1-bit masks were written; every other forward (evaluation, drop-in, scoring: batch and hyper null)
+// clears the three flags.
+void forward_leaves(codae_engine* e, const codae_batch* batch, const codae_hyper* hyper) {
+    e->drop_live = hyper != nullptr && e->tc.drop.on;
+    if (e->drop_live) { e->drop_B = batch->B; e->drop_rows = batch->row_idx; e->drop_step = hyper->step; }
+    e->res_bits_live = hyper != nullptr && e->tc.res.any;
+    e->norm_bits_live = hyper != nullptr && e->tc.norm.any;
+}
+
+// The drop-in entry points' refusal of what skips or a norm do not allow them: "<who>: residual connections are on: <what>", or
+// "<who>: a norm is on: <what>"
+int refuse_skips_or_norm(const codae_engine* e, const char* who, const char* what) {
+    if (!e->tc.res.any && !e->tc.norm.any) return CODAE_OK;
+    set_error("%s: %s on: %s", who, e->tc.res.any ? "residual connections are" : "a norm is", what);
+    return CODAE_E_UNSUPPORTED;
+}
+
+// Layer l of a forward - the MODEL, in the one place every forward loop calls: the linear layer into act[l + 1] (`rows` rows) or,
+// y_f32 not null, into that fp32 tensor (B rows); then dropout, the skip and the norm, in that order, where the settings put one.
+// Dropout is inert unless forward_leaves recorded a dropped forward; `training`: the skip and the norm leave their 1-bit masks.
+// group: the caller's run of plain forward launches, told of the GEMM.
+int run_forward_layer(codae_engine* e, const codae_buffers* b, int l, float* y_f32, int B, int rows, bool training, hipStream_t s,
+                      GroupScope* group = nullptr) {
+    int rc = y_f32 != nullptr ? run_linear(e, b, l, act_ptr(e, b, l), y_f32, true, B, s)
+                              : run_linear(e, b, l, act_ptr(e, b, l), act_ptr(e, b, l + 1), false, rows, s);
+    if (rc) return rc;
+    if (group != nullptr) group->launched();
+    if (drops_layer(e, l)) {
+        rc = run_dropout_fwd(e, b, l, s);
+        if (rc) return rc;
+    }
+    if (skips_layer(e, l)) {
+        rc = run_residual_fwd(e, b, l, B, training, s);
+        if (rc) return rc;
+    }
+    return norms_layer(e, l) ? run_norm_fwd(e, b, l, B, training, s) : CODAE_OK;
 }
 
 // the data gradient of layer l and, when layer l - 1 was dropped in the forward, dA_{l-1} <- dA_{l-1} * f right behind it on the same
@@ -826,60 +866,45 @@ int run_dgrad(codae_engine* e, const codae_buffers* b, int l, int rows, bool cos
     const bool res = dx_f32 == nullptr && l >= 1 && (nrm || skips_layer(e, l) || skips_layer(e, l - 1));
     int rc = run_dgrad_gemm(e, b, l, rows, coscheduled, dx_f32, s, res);
     if (rc || dx_f32 != nullptr) return rc;
-    if (nrm) {
-        const bool bf = e->prec == CODAE_PREC_BF16;
-        const int m = l - 1;                                     // the normalised layer, whose derivative is applied
-        const int kind = e->relu[m] ? CODAE_ACT_RELU : (int)e->act[m];
-        float* G = reinterpret_cast<float*>(e->tc.res.ws);
-        const char* ws = reinterpret_cast<const char*>(e->tc.norm.ws);
-        NormBwd n{};
-        n.xhat = act_ptr(e, b, l); n.ld_x = e->in_ld[l];
-        n.rstd = reinterpret_cast<const float*>(ws + e->norm_r_off[m]);
-        n.g_in = skips_layer(e, l) ? G : nullptr;
-        n.g_out = skips_layer(e, m) && m >= 1 ? G : nullptr;     // (layer 0's input gradient is never formed)
-        n.ld_g = e->in[l];
-        n.act_kind = kind;
-        n.slope = e->act_p[3 * m];
-        if (kind != CODAE_ACT_NONE) {
-            const bool from_skip = skips_layer(e, m);
-            CODAE_REQUIRE(from_skip ? e->res_bits_live : e->norm_bits_live, "backward through the norm of layer %d without a training forward before it", m);
-            const int64_t off = from_skip ? e->res_bits_off[m] : e->norm_bits_off[m];
-            CODAE_REQUIRE(off >= 0, "backward through the norm of layer %d: no 1-bit mask for activation kind %d", m, kind);
-            n.bits = reinterpret_cast<const uint8_t*>(from_skip ? reinterpret_cast<const char*>(e->tc.res.ws) : ws) + off;
-            n.ld_bits = (e->out[m] + 7) / 8;
-        }
-        {
-            ProfScope prof(e, CODAE_K_DROPOUT, s);
-            rc = launch_norm_bwd(dact_ptr(e, b, m), bf, bf ? e->out_ld[m] : e->out[m], e->res_B, e->out[m], e->tc.norm.kind, n, part_ptr(e, b, m), s);
-        }
-        if (rc) return rc;
-        e->parts_pending[m] = norm_blocks(e->res_B);
-    } else if (res) {
+    if (res) {
+        // a streaming kernel takes over the derivative at this site: the norm's when layer m is normalised, else the residual's
         const bool bf = e->prec == CODAE_PREC_BF16;
         const int m = l - 1;                                     // the layer whose derivative is applied
         const int kind = e->relu[m] ? CODAE_ACT_RELU : (int)e->act[m];
+        const bool from_skip = skips_layer(e, m);
         float* G = reinterpret_cast<float*>(e->tc.res.ws);
-        ResidualBwd r{};
-        r.g_in = skips_layer(e, l) ? G : nullptr;
-        r.g_out = skips_layer(e, m) && m >= 1 ? G : nullptr;     // (layer 0's input gradient is never formed)
-        r.ld_g = e->in[l];
-        r.act_kind = kind;
-        for (int k = 0; k < 3; ++k) r.act_p[k] = e->act_p[3 * m + k];
-        if (skips_layer(e, m)) {
-            if (e->res_bits_off[m] >= 0) {
-                CODAE_REQUIRE(e->res_bits_live, "backward through the skip of layer %d without a training forward before it", m);
-                r.bits = reinterpret_cast<const uint8_t*>(e->tc.res.ws) + e->res_bits_off[m];
-                r.ld_bits = (e->out[m] + 7) / 8;
-            }
-        } else if (kind != CODAE_ACT_NONE) {
-            r.src = act_ptr(e, b, l); r.ld_src = e->in_ld[l];
+        StreamBwd c{};
+        c.g_in = skips_layer(e, l) ? G : nullptr;
+        c.g_out = from_skip && m >= 1 ? G : nullptr;             // (layer 0's input gradient is never formed)
+        c.ld_g = e->in[l];
+        c.act_kind = kind;
+        c.slope = e->act_p[3 * m];
+        // act' from the 1-bit mask a training forward left: the skip kernel's when layer m is skipped (act[l] then holds a_m + h_m),
+        // else the norm kernel's (act[l] holds xhat); a layer with neither takes it from the saved activation act[l], as the GEMM
+        // epilogue does
+        if ((nrm || from_skip) && kind != CODAE_ACT_NONE) {
+            CODAE_REQUIRE(from_skip ? e->res_bits_live : e->norm_bits_live, "backward through the %s of layer %d without a training forward before it",
+                          nrm ? "norm" : "skip", m);
+            const int64_t off = from_skip ? e->res_bits_off[m] : e->norm_bits_off[m];
+            CODAE_REQUIRE(off >= 0, "backward through the %s of layer %d: no 1-bit mask for activation kind %d", nrm ? "norm" : "skip", m, kind);
+            c.bits = reinterpret_cast<const uint8_t*>(from_skip ? e->tc.res.ws : e->tc.norm.ws) + off;
+            c.ld_bits = (e->out[m] + 7) / 8;
         }
+        const int64_t ld = bf ? e->out_ld[m] : e->out[m];
         {
             ProfScope prof(e, CODAE_K_DROPOUT, s);
-            rc = launch_residual_bwd(dact_ptr(e, b, m), bf, bf ? e->out_ld[m] : e->out[m], e->res_B, e->out[m], r, part_ptr(e, b, m), s);
+            if (nrm) {
+                const NormBwd n{c, act_ptr(e, b, l), e->in_ld[l], reinterpret_cast<const float*>(reinterpret_cast<const char*>(e->tc.norm.ws) + e->norm_r_off[m])};
+                rc = launch_norm_bwd(dact_ptr(e, b, m), bf, ld, e->res_B, e->out[m], e->tc.norm.kind, n, part_ptr(e, b, m), s);
+            } else {
+                const bool from_act = !from_skip && kind != CODAE_ACT_NONE;
+                const ResidualBwd r{c, from_act ? act_ptr(e, b, l) : nullptr, from_act ? e->in_ld[l] : 0,
+                                    {e->act_p[3 * m], e->act_p[3 * m + 1], e->act_p[3 * m + 2]}};
+                rc = launch_residual_bwd(dact_ptr(e, b, m), bf, ld, e->res_B, e->out[m], r, part_ptr(e, b, m), s);
+            }
         }
         if (rc) return rc;
-        e->parts_pending[m] = residual_blocks(e->res_B);
+        e->parts_pending[m] = row_sweep_blocks(e->res_B);
     }
     if (!drops_layer(e, l - 1)) return CODAE_OK;
     {
@@ -889,7 +914,7 @@ int run_dgrad(codae_engine* e, const codae_buffers* b, int l, int rows, bool cos
                                 part_ptr(e, b, l - 1), s);
     }
     if (rc) return rc;
-    e->parts_pending[l - 1] = dropout_blocks(e->drop_B);
+    e->parts_pending[l - 1] = row_sweep_blocks(e->drop_B);
     return CODAE_OK;
 }
 
@@ -1023,6 +1048,49 @@ int backward_range(codae_handle h, const codae_buffers* b, const StepCall& c, co
         h->side_dirty = true;
         if (join) return join_side(h, s);
     }
+    return CODAE_OK;
+}
+
+// What the layouts of codae_residual and codae_norm share: the canonical flags of `flags` on this stack (all zero = off), the refusal
+// of a layer that cannot take the setting - "a <adjective> layer", which "takes no <noun>" -, and the work space: `lead(on)` bytes
+// of the setting's own first, then the 1-bit mask of every flagged layer with a ReLU or a LeakyReLU.
+template <class Lead>
+int stream_layout(codae_handle h, const char* who, int n, const uint8_t* flags, const char* noun, const char* adjective, bool equal_widths,
+                  uint8_t* on, std::vector<int64_t>* bits_off, int64_t* bytes, Lead lead) {
+    CODAE_REQUIRE(n == h->L, "%s: %d flags for %d layers", who, n, h->L);
+    CODAE_REQUIRE(flags != nullptr, "%s: null on", who);
+    bool any = false;
+    for (int l = 0; l < h->L; ++l) {
+        if (!flags[l]) continue;
+        // (codae_create keeps a ReLU layer as relu[l] = 1 with act[l] = NONE: act[l] names the generic activations only, so NONE
+        //  below is "no activation or ReLU" and kind 1 never appears)
+        char why[96] = "";
+        if (l == h->L - 1) snprintf(why, sizeof(why), "the last layer's output is the reconstruction and takes no %s", noun);
+        else if (equal_widths && h->in[l] != h->out[l]) snprintf(why, sizeof(why), "an identity skip needs equal widths");
+        else if (h->act[l] != CODAE_ACT_NONE && h->act[l] != CODAE_ACT_LEAKY)
+            snprintf(why, sizeof(why), "a %s layer's activation must be none, ReLU or LeakyReLU", adjective);
+        if (why[0] != 0) {
+            set_error("%s: layer %d (%d -> %d, activation kind %d): %s", who, l, h->in[l], h->out[l], h->relu[l] ? CODAE_ACT_RELU : (int)h->act[l], why);
+            return CODAE_E_UNSUPPORTED;
+        }
+        on[l] = 1;
+        any = true;
+    }
+    if (!any) return CODAE_OK;
+    int64_t off = lead(on);
+    for (int l = 0; l < h->L; ++l) {
+        if (!on[l] || !(h->relu[l] || h->act[l] == CODAE_ACT_LEAKY)) continue;
+        if (bits_off) (*bits_off)[l] = off;
+        off += round_up((int64_t)h->max_batch * ((h->out[l] + 7) / 8), 256);
+    }
+    *bytes = off;
+    return CODAE_OK;
+}
+
+// both setters' check of the work space the caller brought
+int check_stream_ws(const char* who, const void* ws, int64_t ws_bytes, int64_t need) {
+    CODAE_REQUIRE(ws != nullptr && (reinterpret_cast<uintptr_t>(ws) & 15) == 0 && ws_bytes >= need,
+                  "%s: the work space must be 16-byte aligned and hold %lld bytes (got %lld)", who, (long long)need, (long long)ws_bytes);
     return CODAE_OK;
 }
 
@@ -1298,18 +1366,13 @@ int codae_forward(codae_handle h, const codae_buffers* b, const float* x, float*
     CODAE_REQUIRE(x && y, "codae_forward: null x or y");
     CODAE_REQUIRE(layer_lo >= 0 && layer_lo < layer_hi && layer_hi <= h->L, "codae_forward: layer range [%d, %d)", layer_lo, layer_hi);
     (void)save_for_backward;  // activations always live in the workspace; a later forward overwrites them
-    if (h->tc.res.any && !(layer_lo == 0 && layer_hi == h->L)) {
-        set_error("codae_forward: residual connections are on: a forward over the layer range [%d, %d) of %d layers is not supported", layer_lo,
-                  layer_hi, h->L);
-        return CODAE_E_UNSUPPORTED;
+    if (!(layer_lo == 0 && layer_hi == h->L)) {
+        char what[96];
+        snprintf(what, sizeof(what), "a forward over the layer range [%d, %d) of %d layers is not supported", layer_lo, layer_hi, h->L);
+        rc = refuse_skips_or_norm(h, "codae_forward", what);
+        if (rc) return rc;
     }
-    if (h->tc.norm.any && !(layer_lo == 0 && layer_hi == h->L)) {
-        set_error("codae_forward: a norm is on: a forward over the layer range [%d, %d) of %d layers is not supported", layer_lo, layer_hi, h->L);
-        return CODAE_E_UNSUPPORTED;
-    }
-    h->drop_live = false;     // (a drop-in forward never drops)
-    h->res_bits_live = false; // (nor writes the skips' masks)
-    h->norm_bits_live = false;
+    forward_leaves(h, nullptr, nullptr);      // (a drop-in forward never drops, nor writes the skips' and the norm's masks)
     hipStream_t s = (hipStream_t)stream;
     const int rows = h->rows_for(B);
     // ingest x into act[layer_lo] in working precision (no gather, no mask)
@@ -1320,22 +1383,9 @@ int codae_forward(codae_handle h, const codae_buffers* b, const float* x, float*
     rc = zero_pad_rows(h, act_ptr(h, b, layer_lo), B, rows, h->in_ld[layer_lo], s);
     if (rc) return rc;
     for (int l = layer_lo; l < layer_hi; ++l) {
-        const bool last = (l == layer_hi - 1);
-        if (last) {
-            // the chain's result goes straight to the caller's fp32 tensor (B rows only)
-            rc = run_linear(h, b, l, act_ptr(h, b, l), y, true, B, s);
-        } else {
-            rc = run_linear(h, b, l, act_ptr(h, b, l), act_ptr(h, b, l + 1), false, rows, s);
-        }
+        // (the chain's result goes straight to the caller's fp32 tensor, B rows only)
+        rc = run_forward_layer(h, b, l, l == layer_hi - 1 ? y : nullptr, B, rows, false, s);
         if (rc) return rc;
-        if (skips_layer(h, l)) {
-            rc = run_residual_fwd(h, b, l, B, false, s);
-            if (rc) return rc;
-        }
-        if (norms_layer(h, l)) {
-            rc = run_norm_fwd(h, b, l, B, false, s);
-            if (rc) return rc;
-        }
     }
     return CODAE_OK;
 }
@@ -1346,16 +1396,9 @@ int codae_backward(codae_handle h, const codae_buffers* b, const float* dy, floa
     if (rc) return rc;
     CODAE_REQUIRE(dy && b->grads && b->dacts, "codae_backward: null dy / grads / dacts");
     CODAE_REQUIRE(layer_lo >= 0 && layer_lo < layer_hi && layer_hi <= h->L, "codae_backward: layer range [%d, %d)", layer_lo, layer_hi);
-    if (h->tc.res.any) {
-        // (the drop-in forward writes no masks, and its sub-chains cut the sum G across the cut)
-        set_error("codae_backward: residual connections are on: the drop-in backward is not supported (use the step entry points)");
-        return CODAE_E_UNSUPPORTED;
-    }
-    if (h->tc.norm.any) {
-        // (the drop-in forward writes no masks, and a sub-chain's forward does not normalise)
-        set_error("codae_backward: a norm is on: the drop-in backward is not supported (use the step entry points)");
-        return CODAE_E_UNSUPPORTED;
-    }
+    // (the drop-in forward writes no masks; its sub-chains cut the sum G across the cut, and a sub-chain's forward does not normalise)
+    rc = refuse_skips_or_norm(h, "codae_backward", "the drop-in backward is not supported (use the step entry points)");
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int rows = h->rows_for(B);
     const int top = layer_hi - 1;
@@ -1462,12 +1505,7 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
     const int B = batch->B, L = h->L;
     const int rows = plan.rows;
     const bool bf = h->prec == CODAE_PREC_BF16;
-    // hidden dropout: training forwards only; the backward entry points find the rows and the step in the handle
-    h->drop_live = hyper != nullptr && h->tc.drop.on;
-    if (h->drop_live) { h->drop_B = B; h->drop_rows = batch->row_idx; h->drop_step = hyper->step; }
-    // residual connections: every forward adds the skips; a training forward also leaves their 1-bit masks for the backward
-    h->res_bits_live = hyper != nullptr && h->tc.res.any;
-    h->norm_bits_live = hyper != nullptr && h->tc.norm.any;
+    forward_leaves(h, batch, hyper);
     const uint8_t* const pres = h->tc.pres.table;
     const int pres_slots = h->tc.pres.n_slots;
     const bool fuse_loss = plan.loss == LOSS_FUSED, fold_finish = plan.loss_finish == LOSS_FINISH_CARRIED;
@@ -1520,22 +1558,8 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
             }
             return finish_loss(h, b, batch, n_loss_parts, s);
         }
-        rc = last ? run_linear(h, b, l, act_ptr(h, b, l), y, true, B, s)
-                  : run_linear(h, b, l, act_ptr(h, b, l), act_ptr(h, b, l + 1), false, rows, s);
+        rc = run_forward_layer(h, b, l, last ? y : nullptr, B, rows, hyper != nullptr, s, &fwd_group);
         if (rc) return rc;
-        fwd_group.launched();
-        if (drops_layer(h, l)) {
-            rc = run_dropout_fwd(h, b, l, s);
-            if (rc) return rc;
-        }
-        if (skips_layer(h, l)) {
-            rc = run_residual_fwd(h, b, l, B, hyper != nullptr, s);
-            if (rc) return rc;
-        }
-        if (norms_layer(h, l)) {
-            rc = run_norm_fwd(h, b, l, B, hyper != nullptr, s);
-            if (rc) return rc;
-        }
     }
     fwd_group.close();
     if (hyper != nullptr) {
@@ -1746,40 +1770,19 @@ int codae_set_hidden_dropout(codae_handle h, const codae_dropout* d) {
     return CODAE_OK;
 }
 
-// The canonical flags of a codae_residual on this stack (all zero = off) and the layout of its work space: G first, then the 1-bit
-// mask of every skipped layer with a ReLU or a LeakyReLU.  CODAE_E_INVALID / CODAE_E_UNSUPPORTED as codae_set_residual documents.
+// The canonical flags of a codae_residual on this stack (all zero = off) and the layout of its work space: G of the widest skipped
+// layer first, then the masks.  CODAE_E_INVALID / CODAE_E_UNSUPPORTED as codae_set_residual documents.
 static int residual_layout(codae_handle h, const codae_residual* r, const char* who, uint8_t* on, std::vector<int64_t>* bits_off, int64_t* bytes) {
     memset(on, 0, 64);
     if (bits_off) bits_off->assign(h->L, -1);
     *bytes = 0;
     if (r == nullptr) return CODAE_OK;
-    CODAE_REQUIRE(r->n == h->L, "%s: %d flags for %d layers", who, r->n, h->L);
-    CODAE_REQUIRE(r->on != nullptr, "%s: null on", who);
-    int maxw = 0;
-    for (int l = 0; l < h->L; ++l) {
-        if (!r->on[l]) continue;
-        // (codae_create keeps a ReLU layer as relu[l] = 1 with act[l] = NONE: act[l] names the generic activations only, so NONE
-        //  below is "no activation or ReLU" and kind 1 never appears)
-        const char* why = nullptr;
-        if (l == h->L - 1) why = "the last layer's output is the reconstruction and takes no skip";
-        else if (h->in[l] != h->out[l]) why = "an identity skip needs equal widths";
-        else if (h->act[l] != CODAE_ACT_NONE && h->act[l] != CODAE_ACT_LEAKY) why = "a skipped layer's activation must be none, ReLU or LeakyReLU";
-        if (why != nullptr) {
-            set_error("%s: layer %d (%d -> %d, activation kind %d): %s", who, l, h->in[l], h->out[l], h->relu[l] ? CODAE_ACT_RELU : (int)h->act[l], why);
-            return CODAE_E_UNSUPPORTED;
-        }
-        on[l] = 1;
-        if (h->out[l] > maxw) maxw = h->out[l];
-    }
-    if (maxw == 0) return CODAE_OK;
-    int64_t off = round_up((int64_t)h->max_batch * maxw * 4, 256);
-    for (int l = 0; l < h->L; ++l) {
-        if (!on[l] || !(h->relu[l] || h->act[l] == CODAE_ACT_LEAKY)) continue;
-        if (bits_off) (*bits_off)[l] = off;
-        off += round_up((int64_t)h->max_batch * ((h->out[l] + 7) / 8), 256);
-    }
-    *bytes = off;
-    return CODAE_OK;
+    return stream_layout(h, who, r->n, r->on, "skip", "skipped", true, on, bits_off, bytes, [&](const uint8_t* flagged) {
+        int maxw = 0;
+        for (int l = 0; l < h->L; ++l)
+            if (flagged[l] && h->out[l] > maxw) maxw = h->out[l];
+        return round_up((int64_t)h->max_batch * maxw * 4, 256);
+    });
 }
 
 int64_t codae_residual_ws_bytes(codae_handle h, const codae_residual* r) {
@@ -1797,8 +1800,8 @@ int codae_set_residual(codae_handle h, const codae_residual* r, void* ws, int64_
     int rc = residual_layout(h, r, "codae_set_residual", c.on, &bits_off, &need);
     if (rc) return rc;
     if (need > 0) {
-        CODAE_REQUIRE(ws != nullptr && (reinterpret_cast<uintptr_t>(ws) & 15) == 0 && ws_bytes >= need,
-                      "codae_set_residual: the work space must be 16-byte aligned and hold %lld bytes (got %lld)", (long long)need, (long long)ws_bytes);
+        rc = check_stream_ws("codae_set_residual", ws, ws_bytes, need);
+        if (rc) return rc;
         c.ws = ws; c.ws_bytes = ws_bytes; c.any = 1;
     }
     h->tc.res = c;
@@ -1808,8 +1811,7 @@ int codae_set_residual(codae_handle h, const codae_residual* r, void* ws, int64_
 }
 
 // The canonical flags of a codae_norm on this stack (all zero = off) and the layout of its work space: r of every normalised layer
-// first, then the 1-bit mask of every normalised layer with a ReLU or a LeakyReLU.  CODAE_E_INVALID / CODAE_E_UNSUPPORTED as
-// codae_set_norm documents.
+// first, then the masks.  CODAE_E_INVALID / CODAE_E_UNSUPPORTED as codae_set_norm documents.
 static int norm_layout(codae_handle h, const codae_norm* n, const char* who, uint8_t* on, std::vector<int64_t>* r_off, std::vector<int64_t>* bits_off,
                        int64_t* bytes) {
     memset(on, 0, 64);
@@ -1817,32 +1819,17 @@ static int norm_layout(codae_handle h, const codae_norm* n, const char* who, uin
     if (bits_off) bits_off->assign(h->L, -1);
     *bytes = 0;
     if (n == nullptr) return CODAE_OK;
-    CODAE_REQUIRE(n->n == h->L, "%s: %d flags for %d layers", who, n->n, h->L);
-    CODAE_REQUIRE(n->on != nullptr, "%s: null on", who);
     CODAE_REQUIRE(n->kind == CODAE_NORM_LAYER || n->kind == CODAE_NORM_RMS, "%s: kind %d is neither CODAE_NORM_LAYER nor CODAE_NORM_RMS", who, n->kind);
     CODAE_REQUIRE(n->eps > 0.f && n->eps <= 3.402823466e38f, "%s: eps %g must be finite and > 0", who, (double)n->eps);
-    int64_t off = 0;
-    for (int l = 0; l < h->L; ++l) {
-        if (!n->on[l]) continue;
-        // (act[l] names the generic activations only: NONE below is "no activation or ReLU", see residual_layout)
-        const char* why = nullptr;
-        if (l == h->L - 1) why = "the last layer's output is the reconstruction and takes no norm";
-        else if (h->act[l] != CODAE_ACT_NONE && h->act[l] != CODAE_ACT_LEAKY) why = "a normalised layer's activation must be none, ReLU or LeakyReLU";
-        if (why != nullptr) {
-            set_error("%s: layer %d (%d -> %d, activation kind %d): %s", who, l, h->in[l], h->out[l], h->relu[l] ? CODAE_ACT_RELU : (int)h->act[l], why);
-            return CODAE_E_UNSUPPORTED;
+    return stream_layout(h, who, n->n, n->on, "norm", "normalised", false, on, bits_off, bytes, [&](const uint8_t* flagged) {
+        int64_t off = 0;
+        for (int l = 0; l < h->L; ++l) {
+            if (!flagged[l]) continue;
+            if (r_off) (*r_off)[l] = off;
+            off += round_up((int64_t)h->max_batch * 4, 256);
         }
-        on[l] = 1;
-        if (r_off) (*r_off)[l] = off;
-        off += round_up((int64_t)h->max_batch * 4, 256);
-    }
-    for (int l = 0; l < h->L; ++l) {
-        if (!on[l] || !(h->relu[l] || h->act[l] == CODAE_ACT_LEAKY)) continue;
-        if (bits_off) (*bits_off)[l] = off;
-        off += round_up((int64_t)h->max_batch * ((h->out[l] + 7) / 8), 256);
-    }
-    *bytes = off;
-    return CODAE_OK;
+        return off;
+    });
 }
 
 int64_t codae_norm_ws_bytes(codae_handle h, const codae_norm* n) {
@@ -1860,8 +1847,8 @@ int codae_set_norm(codae_handle h, const codae_norm* n, void* ws, int64_t ws_byt
     int rc = norm_layout(h, n, "codae_set_norm", c.on, &r_off, &bits_off, &need);
     if (rc) return rc;
     if (need > 0) {
-        CODAE_REQUIRE(ws != nullptr && (reinterpret_cast<uintptr_t>(ws) & 15) == 0 && ws_bytes >= need,
-                      "codae_set_norm: the work space must be 16-byte aligned and hold %lld bytes (got %lld)", (long long)need, (long long)ws_bytes);
+        rc = check_stream_ws("codae_set_norm", ws, ws_bytes, need);
+        if (rc) return rc;
         c.ws = ws; c.ws_bytes = ws_bytes; c.any = 1; c.kind = n->kind; c.eps = n->eps;
     }
     h->tc.norm = c;
@@ -1900,9 +1887,7 @@ int codae_score_outfits(codae_handle h, const codae_buffers* b, const float* dat
     hipStream_t s = (hipStream_t)stream;
     const bool bf = h->prec == CODAE_PREC_BF16;
     const int rows = h->rows_for(B);
-    h->drop_live = false;     // (an evaluation forward never drops)
-    h->res_bits_live = false;
-    h->norm_bits_live = false;
+    forward_leaves(h, nullptr, nullptr);      // (an evaluation forward)
     const codae_engine::ImageCfg& im = h->tc.img;
     const bool from_image = bf && !h->cfg.no_dataset_image && im.image != nullptr && data == im.data && io == im.io && n_rows == im.n_rows;
     {
@@ -1915,17 +1900,8 @@ int codae_score_outfits(codae_handle h, const codae_buffers* b, const float* dat
     if (rc) return rc;
     float* y = reinterpret_cast<float*>(act_ptr(h, b, L));
     for (int l = 0; l < L; ++l) {
-        rc = (l == L - 1) ? run_linear(h, b, l, act_ptr(h, b, l), y, true, B, s)
-                          : run_linear(h, b, l, act_ptr(h, b, l), act_ptr(h, b, l + 1), false, rows, s);
+        rc = run_forward_layer(h, b, l, l == L - 1 ? y : nullptr, B, rows, false, s);
         if (rc) return rc;
-        if (skips_layer(h, l)) {
-            rc = run_residual_fwd(h, b, l, B, false, s);
-            if (rc) return rc;
-        }
-        if (norms_layer(h, l)) {
-            rc = run_norm_fwd(h, b, l, B, false, s);
-            if (rc) return rc;
-        }
     }
     return launch_outfit_scores(data, n_rows, io, n_slots, items, Q, pres, y, io, cos, sq, score, n_present, s);
 }
@@ -2097,7 +2073,7 @@ int codae_train_step(codae_handle h, const codae_buffers* b, const codae_batch* 
         if (h->prof_on) ++h->prof_step;
         rc = join_side(h, s);
         if (rc) return rc;
-        h->drop_live = false;
+        forward_leaves(h, batch, hyper);                           // (the chain runs without dropout, skips or a norm: all clear)
         rc = run_chain(h, b, batch, hyper, s, &lf);                // (forward, loss and every data gradient)
         if (rc) return rc;
         rc = run_grouped_tail(h, b, plan, s, &lf);

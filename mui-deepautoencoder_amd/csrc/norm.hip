@@ -4,14 +4,15 @@
 //             leaves the 1-bit mask "value > 0" of what it read - afterwards act[l + 1] holds xhat, whose sign says nothing
 //   backward  behind the UNMASKED data-gradient GEMM of layer l + 1, which left U in dA_l: Gh = U + G (iff layer l + 1 is skipped),
 //             the row reductions c1, c2 against xhat = act[l + 1] and r, Gs = r (Gh - c1 - xhat c2), G <- Gs (iff layer l is
-//             skipped), dA_l <- D_l = Gs * act'_l, + the column sums of the stored D: the residual backward kernel's whole job
+//             skipped), dA_l <- D_l = Gs * act'_l, + the column sums of the stored D: the residual backward kernel's whole job,
+//             in the same sweep (row_sweep.h)
 // The row is RE-READ, not kept in registers: one code path for every width (the fp32 engine runs 21 and 11, the headline 1536, and
 // nothing bounds it), no register-count cliff and no scratch; a wave re-reads only what it read itself a pass earlier, 3 KB per bf16
 // row at the headline width, which the passes after the first find in the caches - HBM sees every matrix once.
 // Templates on <BF16, VEC, KIND>: 16 B per access where every row is 16-B aligned and the width is whole chunks, element accesses
 // otherwise; pad columns and pad rows are never written (xhat of a zero pad column would be -mu r, and the next GEMM's k runs over it).
 #include "codae_common.h"
-#include "row_access.h"
+#include "row_sweep.h"
 
 namespace codae {
 namespace {
@@ -82,45 +83,26 @@ __global__ __launch_bounds__(FWD_NT) void norm_fwd_kernel(void* __restrict__ y, 
 }
 
 // ---- backward ---------------------------------------------------------------------------------------------------------------
-// The row blocking, block shape and column reduction of residual_bwd_kernel: one block per 64 batch rows and all columns, 1024
-// threads, wave w owns rows 4 w .. 4 w + 3.  First the row reductions of its four rows, then tile by tile (64 chunks of 8 columns)
-// the write-out: a thread adds its four rows' STORED values in row order, the 16 waves' sums meet in LDS and are added in wave
-// order by one thread per column: a fixed order, no atomics.
-constexpr int BWD_ROWS = 64, BWD_WAVES = 16, BWD_NT = 64 * BWD_WAVES, BWD_RPW = BWD_ROWS / BWD_WAVES, BWD_TILE = 64 * NC;
-
-// Gh columns [c, c + NC) of row b: U from d, + G when the layer behind is skipped (one fp32 add)
-template <bool BF16, bool VEC>
-__device__ __forceinline__ void load_gh(const char* drow, const float* grow, int c, int width, float* g) {
-    load_work<BF16, VEC, NC>(drow, c, width, g);
-    if (grow != nullptr) {
-        float gi[NC];
-        load_work<false, VEC, NC>(grow, c, width, gi);
-#pragma unroll
-        for (int k = 0; k < NC; ++k) g[k] = opaque(g[k] + gi[k]);
-    }
-}
-
+// The shared sweep (row_sweep.h) behind a prologue: the row reductions c1, c2 of the wave's four rows, a wave per row as in the
+// forward.  The sweep's chunk then re-reads Gh - the bits the reductions saw - and writes Gs and D, 8 columns whatever the type.
 template <bool BF16, bool VEC, int KIND>
-__global__ __launch_bounds__(BWD_NT) void norm_bwd_kernel(void* d, int64_t ld, int B, int width, NormBwd n, float* __restrict__ colsum_part) {
+__global__ __launch_bounds__(SWEEP_NT) void norm_bwd_kernel(void* d, int64_t ld, int B, int width, NormBwd n, float* __restrict__ colsum_part) {
     constexpr int ES = BF16 ? 2 : 4;
-    __shared__ float red[BWD_WAVES][BWD_TILE];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int row0 = blockIdx.x * BWD_ROWS + wave * BWD_RPW;
+    const int lane = threadIdx.x & 63;
+    const int row0 = sweep_row0();
     const float w = (float)width;
-    const bool selects = n.act_kind == CODAE_ACT_RELU;         // (ReLU selects 0 under a dead unit, LeakyReLU multiplies)
-    float c1[BWD_RPW], c2[BWD_RPW], r[BWD_RPW];
+    float c1[SWEEP_RPW], c2[SWEEP_RPW], r[SWEEP_RPW];
 #pragma unroll
-    for (int i = 0; i < BWD_RPW; ++i) {
+    for (int i = 0; i < SWEEP_RPW; ++i) {
         const int b = row0 + i;
         c1[i] = 0.f; c2[i] = 0.f; r[i] = 0.f;
         if (b < B) {                                           // (wave-uniform)
             const char* drow = reinterpret_cast<const char*>(d) + (int64_t)b * ld * ES;
             const char* xrow = reinterpret_cast<const char*>(n.xhat) + (int64_t)b * n.ld_x * ES;
-            const float* grow = n.g_in != nullptr ? n.g_in + (int64_t)b * n.ld_g : nullptr;
             float s1 = 0.f, s2 = 0.f;
             for (int c = lane * NC; c < width; c += 64 * NC) {
                 float g[NC], xh[NC];
-                load_gh<BF16, VEC>(drow, grow, c, width, g);
+                load_gh<BF16, VEC, NC>(drow, n, b, c, width, g);
                 load_work<BF16, VEC, NC>(xrow, c, width, xh);
 #pragma unroll
                 for (int k = 0; k < NC; ++k) {                 // (a column past the width was loaded as 0 in both)
@@ -133,56 +115,30 @@ __global__ __launch_bounds__(BWD_NT) void norm_bwd_kernel(void* d, int64_t ld, i
             r[i] = n.rstd[b];
         }
     }
-    for (int t0 = 0; t0 < width; t0 += BWD_TILE) {
-        const int c = t0 + lane * NC;
-        float sum[NC];
+    row_sweep<NC>(B, width, colsum_part, [=](int b, int i, int c, float* out) {
+        char* drow = reinterpret_cast<char*>(d) + (int64_t)b * ld * ES;
+        float g[NC], xh[NC];
+        load_gh<BF16, VEC, NC>(drow, n, b, c, width, g);
+        load_work<BF16, VEC, NC>(reinterpret_cast<const char*>(n.xhat) + (int64_t)b * n.ld_x * ES, c, width, xh);
 #pragma unroll
-        for (int k = 0; k < NC; ++k) sum[k] = 0.f;
-        if (c < width) {
-#pragma unroll
-            for (int i = 0; i < BWD_RPW; ++i) {
-                const int b = row0 + i;
-                if (b < B) {
-                    char* drow = reinterpret_cast<char*>(d) + (int64_t)b * ld * ES;
-                    const char* xrow = reinterpret_cast<const char*>(n.xhat) + (int64_t)b * n.ld_x * ES;
-                    const float* grow = n.g_in != nullptr ? n.g_in + (int64_t)b * n.ld_g : nullptr;
-                    float g[NC], xh[NC], out[NC];
-                    load_gh<BF16, VEC>(drow, grow, c, width, g);                      // Gh, the bits the reductions saw
-                    load_work<BF16, VEC, NC>(xrow, c, width, xh);
-#pragma unroll
-                    for (int k = 0; k < NC; ++k) {
-                        float t = opaque(g[k] - opaque(xh[k] * c2[i]));
-                        if constexpr (KIND == CODAE_NORM_LAYER) t = opaque(t - c1[i]);
-                        g[k] = opaque(t * r[i]);                                      // Gs
-                    }
-                    if (n.g_out != nullptr) {
-                        float unused[NC];
-                        store_work<false, VEC, NC>(n.g_out + (int64_t)b * n.ld_g, c, width, g, unused);
-                    }
-                    if (n.bits != nullptr) {
-                        const uint32_t m = (uint32_t)n.bits[(int64_t)b * n.ld_bits + (c >> 3)];
-#pragma unroll
-                        for (int k = 0; k < NC; ++k) g[k] = ((m >> k) & 1u) ? g[k] : (selects ? 0.f : opaque(g[k] * n.slope));
-                    }
-                    store_work<BF16, VEC, NC>(drow, c, width, g, out);                // D
-#pragma unroll
-                    for (int k = 0; k < NC; ++k) sum[k] = opaque(sum[k] + out[k]);
-                }
-            }
+        for (int k = 0; k < NC; ++k) {
+            float t = opaque(g[k] - opaque(xh[k] * c2[i]));
+            if constexpr (KIND == CODAE_NORM_LAYER) t = opaque(t - c1[i]);
+            g[k] = opaque(t * r[i]);                                      // Gs
         }
-        if (colsum_part != nullptr) {                          // (block-uniform)
-#pragma unroll
-            for (int k = 0; k < NC; ++k) red[wave][lane * NC + k] = sum[k];
-            __syncthreads();
-            if (threadIdx.x < BWD_TILE && t0 + (int)threadIdx.x < width) {
-                float s = red[0][threadIdx.x];
-#pragma unroll
-                for (int wv = 1; wv < BWD_WAVES; ++wv) s = opaque(s + red[wv][threadIdx.x]);
-                colsum_part[(int64_t)blockIdx.x * width + t0 + threadIdx.x] = s;
-            }
-            __syncthreads();
-        }
-    }
+        store_g<VEC, NC>(n, b, c, width, g);
+        if (n.bits != nullptr) mask_deriv<NC>(n, b, c, g);
+        store_work<BF16, VEC, NC>(drow, c, width, g, out);                // D
+    });
+}
+
+// launch(BF16, VEC, KIND) as integral constants: dispatch_bf16_vec and the norm's kind
+template <class Launch>
+void dispatch_norm(int bf16, bool vec, int kind, Launch launch) {
+    dispatch_bf16_vec(bf16, vec, [&](auto BF, auto V) {
+        if (kind == CODAE_NORM_LAYER) launch(BF, V, std::integral_constant<int, CODAE_NORM_LAYER>{});
+        else launch(BF, V, std::integral_constant<int, CODAE_NORM_RMS>{});
+    });
 }
 
 }  // namespace
@@ -194,16 +150,12 @@ int launch_norm_fwd(void* y, int bf16, int64_t ld, int B, int width, int kind, f
     CODAE_REQUIRE(kind == CODAE_NORM_LAYER || kind == CODAE_NORM_RMS, "codae_norm_fwd: kind %d is neither CODAE_NORM_LAYER nor CODAE_NORM_RMS", kind);
     CODAE_REQUIRE(eps > 0.f && eps <= 3.402823466e38f, "codae_norm_fwd: eps %g must be finite and > 0", (double)eps);
     CODAE_REQUIRE(bits == nullptr || ld_bits >= (width + 7) / 8, "codae_norm_fwd: ld_bits %lld for %d columns", (long long)ld_bits, width);
-    const int per = bf16 ? 8 : 4;
-    const bool vec = aligned16(y) && ld % per == 0 && width % per == 0;
     int blocks = (B + FWD_WAVES - 1) / FWD_WAVES;
     if (blocks > 4096) blocks = 4096;
-#define NF(BF, V, K) hipLaunchKernelGGL((norm_fwd_kernel<BF, V, K>), dim3(blocks), dim3(FWD_NT), 0, s, y, ld, B, width, eps, rstd, bits, ld_bits)
-#define NFK(BF, V) do { if (kind == CODAE_NORM_LAYER) NF(BF, V, CODAE_NORM_LAYER); else NF(BF, V, CODAE_NORM_RMS); } while (0)
-    if (bf16) { if (vec) NFK(true, true); else NFK(true, false); }
-    else { if (vec) NFK(false, true); else NFK(false, false); }
-#undef NFK
-#undef NF
+    dispatch_norm(bf16, rows_vec16(bf16, width, {{y, ld}}), kind, [&](auto BF, auto V, auto K) {
+        hipLaunchKernelGGL((norm_fwd_kernel<decltype(BF)::value, decltype(V)::value, decltype(K)::value>), dim3(blocks), dim3(FWD_NT), 0, s, y, ld,
+                           B, width, eps, rstd, bits, ld_bits);
+    });
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;
 }
@@ -213,20 +165,12 @@ int launch_norm_bwd(void* d, int bf16, int64_t ld, int B, int width, int kind, c
     CODAE_REQUIRE(B > 0 && width > 0 && ld >= width && n.ld_x >= width, "codae_norm_bwd: B %d, width %d, ld %lld, ld_x %lld", B, width,
                   (long long)ld, (long long)n.ld_x);
     CODAE_REQUIRE(kind == CODAE_NORM_LAYER || kind == CODAE_NORM_RMS, "codae_norm_bwd: kind %d is neither CODAE_NORM_LAYER nor CODAE_NORM_RMS", kind);
-    CODAE_REQUIRE((n.g_in == nullptr && n.g_out == nullptr) || n.ld_g >= width, "codae_norm_bwd: ld_g %lld for %d columns", (long long)n.ld_g, width);
-    CODAE_REQUIRE(n.bits == nullptr || n.ld_bits >= (width + 7) / 8, "codae_norm_bwd: ld_bits %lld for %d columns", (long long)n.ld_bits, width);
-    CODAE_REQUIRE(n.bits == nullptr || n.act_kind == CODAE_ACT_RELU || n.act_kind == CODAE_ACT_LEAKY,
-                  "codae_norm_bwd: 1-bit masks carry the derivative of ReLU and LeakyReLU only (kind %d)", n.act_kind);
-    const int per = bf16 ? 8 : 4;
-    bool vec = aligned16(d) && aligned16(n.xhat) && ld % per == 0 && n.ld_x % per == 0 && width % per == 0;
-    if (n.g_in != nullptr || n.g_out != nullptr) vec = vec && aligned16(n.g_in) && aligned16(n.g_out) && n.ld_g % 4 == 0;
-    const int blocks = norm_blocks(B);
-#define NB(BF, V, K) hipLaunchKernelGGL((norm_bwd_kernel<BF, V, K>), dim3(blocks), dim3(BWD_NT), 0, s, d, ld, B, width, n, colsum_part)
-#define NBK(BF, V) do { if (kind == CODAE_NORM_LAYER) NB(BF, V, CODAE_NORM_LAYER); else NB(BF, V, CODAE_NORM_RMS); } while (0)
-    if (bf16) { if (vec) NBK(true, true); else NBK(true, false); }
-    else { if (vec) NBK(false, true); else NBK(false, false); }
-#undef NBK
-#undef NB
+    int rc = check_stream_bwd("codae_norm_bwd", n, width);
+    if (rc) return rc;
+    dispatch_norm(bf16, rows_vec16(bf16, width, {{d, ld}, {n.xhat, n.ld_x}}, &n), kind, [&](auto BF, auto V, auto K) {
+        hipLaunchKernelGGL((norm_bwd_kernel<decltype(BF)::value, decltype(V)::value, decltype(K)::value>), dim3(row_sweep_blocks(B)),
+                           dim3(SWEEP_NT), 0, s, d, ld, B, width, n, colsum_part);
+    });
     CODAE_LAUNCH_CHECK();
     return CODAE_OK;
 }

@@ -180,7 +180,7 @@ int codae_dropout_bwd(void* d, int32_t bf16, int64_t ld, int32_t B, int32_t widt
     return launch_dropout_bwd(d, bf16, ld, B, width, row_idx, layer, step, nullptr, p, seed, colsum_part, (hipStream_t)stream);
 }
 
-int codae_dropout_blocks(int32_t B) { return B > 0 ? dropout_blocks(B) : 0; }
+int codae_dropout_blocks(int32_t B) { return B > 0 ? row_sweep_blocks(B) : 0; }
 
 int codae_residual_fwd(void* y, const void* x, int32_t bf16, int64_t ldy, int64_t ldx, int32_t B, int32_t width, uint8_t* bits,
                        int64_t ld_bits, void* stream) {
@@ -190,12 +190,13 @@ int codae_residual_fwd(void* y, const void* x, int32_t bf16, int64_t ldy, int64_
 int codae_residual_bwd(void* d, int32_t bf16, int64_t ld, int32_t B, int32_t width, const float* g_in, float* g_out, int64_t ld_g,
                        const uint8_t* bits, int64_t ld_bits, const void* src, int64_t ld_src, int32_t act_kind, const float* act_param,
                        float* colsum_part, void* stream) {
-    ResidualBwd r{g_in, g_out, ld_g, bits, ld_bits, src, ld_src, act_kind, {0.f, 0.f, 0.f}};
+    ResidualBwd r{{g_in, g_out, ld_g, bits, ld_bits, act_kind, 0.f}, src, ld_src, {0.f, 0.f, 0.f}};
     for (int k = 0; k < 3 && act_param != nullptr; ++k) r.act_p[k] = act_param[k];
+    r.slope = r.act_p[0];
     return launch_residual_bwd(d, bf16, ld, B, width, r, colsum_part, (hipStream_t)stream);
 }
 
-int codae_residual_blocks(int32_t B) { return B > 0 ? residual_blocks(B) : 0; }
+int codae_residual_blocks(int32_t B) { return B > 0 ? row_sweep_blocks(B) : 0; }
 
 int codae_norm_fwd(void* y, int32_t bf16, int64_t ld, int32_t B, int32_t width, int32_t kind, float eps, float* rstd, uint8_t* bits,
                    int64_t ld_bits, void* stream) {
@@ -205,11 +206,11 @@ int codae_norm_fwd(void* y, int32_t bf16, int64_t ld, int32_t B, int32_t width, 
 int codae_norm_bwd(void* d, int32_t bf16, int64_t ld, int32_t B, int32_t width, int32_t kind, const void* xhat, int64_t ld_x,
                    const float* rstd, const float* g_in, float* g_out, int64_t ld_g, const uint8_t* bits, int64_t ld_bits,
                    int32_t act_kind, const float* act_param, float* colsum_part, void* stream) {
-    NormBwd n{xhat, ld_x, rstd, g_in, g_out, ld_g, bits, ld_bits, act_kind, act_param != nullptr ? act_param[0] : 0.f};
+    NormBwd n{{g_in, g_out, ld_g, bits, ld_bits, act_kind, act_param != nullptr ? act_param[0] : 0.f}, xhat, ld_x, rstd};
     return launch_norm_bwd(d, bf16, ld, B, width, kind, n, colsum_part, (hipStream_t)stream);
 }
 
-int codae_norm_blocks(int32_t B) { return B > 0 ? norm_blocks(B) : 0; }
+int codae_norm_blocks(int32_t B) { return B > 0 ? row_sweep_blocks(B) : 0; }
 
 int codae_noise_box_muller(const uint32_t* ra, const uint32_t* rb, float* rho, float* c, float* s, int64_t n, void* stream) {
     return launch_noise_box_muller(ra, rb, rho, c, s, n, (hipStream_t)stream);

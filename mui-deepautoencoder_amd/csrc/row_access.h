@@ -1,4 +1,4 @@
-// Row accessors shared by the streaming kernels that sit between a step's GEMMs (residual.hip, norm.hip): C columns of a
+// Row accessors shared by the streaming kernels that sit between a step's GEMMs (dropout.hip, residual.hip, norm.hip): C columns of a
 // working-precision row widened to fp32 and back, templated on <BF16, VEC> - 16 B per access where every row is 16-B aligned and the
 // width is whole chunks, element accesses otherwise; a column past the width is neither read nor written.
 #pragma once

@@ -39,6 +39,25 @@ def packed_mask(a, bf16=False):
     return np.packbits(positive(a), axis=1, bitorder="little")
 
 
+def colsum_parts_fixed_order(stored_f32, B):
+    """The partial column sums a backward streaming kernel (dropout, residual, norm) leaves, from the values it STORED, in the
+    order its sweep adds them: per block of 64 batch rows, wave w of 16 adds its rows 4 w .. 4 w + 3 that are < B in row order
+    to a zero, (((0 + r0) + r1) + r2) + r3, then wave 0's sum takes the sums of waves 1 .. 15 in order.  Every step is one IEEE
+    fp32 addition, so float32 numpy gives the kernel's bits.  -> float32 [ceil(B / 64), width]"""
+    d = np.ascontiguousarray(stored_f32, dtype=np.float32)[:B]
+    blocks = (B + 63) // 64
+    out = np.zeros((blocks, d.shape[1]), dtype=np.float32)
+    for k in range(blocks):
+        total = None
+        for w in range(16):
+            s = np.zeros(d.shape[1], dtype=np.float32)
+            for b in range(64 * k + 4 * w, min(64 * k + 4 * w + 4, B)):
+                s = s + d[b]
+            total = s if total is None else total + s
+        out[k] = total
+    return out
+
+
 def _act(kind, z):
     if kind is None:
         return z

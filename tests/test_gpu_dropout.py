@@ -16,6 +16,7 @@ import pytest
 
 import dropout_ref as DR
 from golden_util import close, max_err
+from residual_ref import colsum_parts_fixed_order
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -97,12 +98,11 @@ def test_forward_kernel_bits_equal_the_definition_b33(bf16, width, ld, permuted)
         assert not _same_bits(t3, want), kw
 
 
-@pytest.mark.parametrize("bf16,width,ld", SHAPES, ids=SHAPE_IDS)
-def test_backward_kernel_bits_and_column_sums_b70(bf16, width, ld):
-    """Two part rows, the second with six live rows."""
-    B, layer, step, p = 70, 0, 3, 0.5
+def _check_backward_kernel(bf16, width, ld, B):
+    """Values, pad columns and pad rows, the column sums (bound and bits), run-to-run bits, the call without column sums."""
+    layer, step, p = 0, 3, 0.5
     rng = np.random.default_rng(200 + width)
-    rows = rng.permutation(120)[:B].astype(np.int32)
+    rows = rng.permutation(max(120, B + 50))[:B].astype(np.int32)
     rows_t = torch.tensor(rows, device=DEV)
     t, a = _matrix(rng, bf16, B + 2, width, ld, B)
     f = DR.factor(rows, layer, width, step, SEED, p)
@@ -114,13 +114,17 @@ def test_backward_kernel_bits_and_column_sums_b70(bf16, width, ld):
     assert (t[:, width:].float() == FILL).all() and (t[B:].float() == FILL).all()
     d64 = want[:B, :width].astype(np.float64)
     cs = colsum.cpu().numpy().astype(np.float64)
-    assert (cs[2] == FILL).all()                                # two part rows, no third
+    blocks = (B + 63) // 64
+    assert (cs[blocks] == FILL).all()                           # one part row per 64 batch rows, none after them
     bound = 1e-5 * np.abs(d64).sum(axis=0)
-    for part, (lo, hi) in enumerate(((0, 64), (64, 70))):
-        err = np.abs(cs[part] - d64[lo:hi].sum(axis=0))
+    for part in range(blocks):
+        err = np.abs(cs[part] - d64[64 * part:64 * part + 64].sum(axis=0))
         print("part", part, "max err / bound", float((err / np.maximum(bound, 1e-300)).max()))
         assert (err <= bound).all(), part
-    assert (np.abs(cs[:2].sum(axis=0) - d64.sum(axis=0)) <= bound).all()
+    assert (np.abs(cs[:blocks].sum(axis=0) - d64.sum(axis=0)) <= bound).all()
+    # the sweep's fixed order of fp32 additions, restated: the same bits
+    got_cs = np.ascontiguousarray(colsum.cpu().numpy()[:blocks]).view(np.uint32)
+    assert np.array_equal(got_cs, colsum_parts_fixed_order(want[:B, :width], B).view(np.uint32))
     # the same call on the same input: the same bits (no atomics)
     t2 = torch.tensor(a, device=DEV).to(torch.bfloat16) if bf16 else torch.tensor(a, device=DEV)
     rc2, colsum2 = drop_bwd(t2, bf16, ld, B, width, rows_t, layer, step, p)
@@ -131,6 +135,20 @@ def test_backward_kernel_bits_and_column_sums_b70(bf16, width, ld):
     assert hip.lib().codae_dropout_bwd(hip.ptr(t3), int(bf16), ld, B, width, hip.ptr(rows_t), layer, step, p, SEED, None, hip.current_stream()) == 0
     torch.cuda.synchronize()
     assert torch.equal(_bits(t), _bits(t3))
+
+
+@pytest.mark.parametrize("bf16,width,ld", SHAPES, ids=SHAPE_IDS)
+def test_backward_kernel_bits_and_column_sums_b70(bf16, width, ld):
+    """Two part rows, the second with six live rows."""
+    _check_backward_kernel(bf16, width, ld, 70)
+
+
+# the backward sweep is the residual and norm kernels' too: their widths past one column tile (512 bf16 / 256 fp32 columns, the
+# bf16 one with a partial second tile), a bf16 element path with an odd ld, and their row counts around the 64-row block
+@pytest.mark.parametrize("bf16,width,ld", [(True, 520, 528), (False, 264, 268), (True, 24, 27)], ids=["bf16-w520", "f32-w264", "bf16-w24-elem"])
+def test_backward_kernel_past_one_column_tile_and_around_one_row_block(bf16, width, ld):
+    for B in (1, 63, 64, 65, 130):
+        _check_backward_kernel(bf16, width, ld, B)
 
 
 @pytest.mark.parametrize("bf16,width,ld", [(False, 24, 24), (True, 72, 128)], ids=["f32-w24", "bf16-w72-ld128"])

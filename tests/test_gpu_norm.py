@@ -18,6 +18,7 @@ import pytest
 
 import norm_ref as NR
 from golden_util import close, max_err
+from residual_ref import colsum_parts_fixed_order
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -189,6 +190,7 @@ def test_backward_kernel_values_and_column_sums(bf16, width, ld, kind, source, w
             err = np.abs(csn[k] - blk.sum(axis=0))
             bound = 64 * 2.0 ** -24 * np.abs(blk).sum(axis=0)
             assert (err <= bound).all(), (B, k, float((err / np.maximum(bound, 1e-300)).max()))
+        assert np.array_equal(_bits32(cs.cpu().numpy()[:blocks]), _bits32(colsum_parts_fixed_order(got[:B, :width], B))), (B, "column-sum bits")
         # G updated in place, no column sums: the same D; the same call again: the same bits (no atomics)
         d2, _ = _work(u, bf16)
         kw2 = dict(kw)

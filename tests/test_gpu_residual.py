@@ -156,6 +156,7 @@ def test_backward_kernel_bits_and_column_sums(bf16, width, ld, source):
             err = np.abs(csn[k] - blk.sum(axis=0))
             bound = 64 * 2.0 ** -24 * np.abs(blk).sum(axis=0)
             assert (err <= bound).all(), (B, k, float((err / np.maximum(bound, 1e-300)).max()))
+        assert np.array_equal(_bits32(cs.cpu().numpy()[:blocks]), _bits32(RR.colsum_parts_fixed_order(D, B))), (B, "column-sum bits")
         # G updated in place, no G at all, no column sums: the same D; the same call again: the same bits (no atomics)
         d2, _ = _work(u, bf16)
         g2 = torch.tensor(gi, device=DEV)
