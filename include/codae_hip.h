@@ -81,6 +81,8 @@ extern "C" {
  *      class of the streaming kernels between a step's GEMMs
  *      (still 11) + codae_norm, CODAE_NORM_*, codae_norm_ws_bytes, codae_set_norm, codae_norm_fwd, codae_norm_bwd, codae_norm_blocks:
  *      new entries only, no layout or existing enum change; the two kernels are booked under CODAE_K_DROPOUT as well
+ *      (still 11) + codae_export_rows, codae_encode, codae_decode: new entries with plain arguments only, no struct, no layout or enum
+ *      change; the export kernel is booked under CODAE_K_DROPOUT as well
  * The binding must refuse a library whose codae_abi_version() differs and must check its own struct sizes against
  * codae_struct_sizes() at load (mui-deepautoencoder_amd/codae/hip/__init__.py does both). */
 #define CODAE_ABI_VERSION 11
@@ -1269,6 +1271,37 @@ int codae_auc_counts(const float* pos, const uint8_t* pos_on, int32_t P, const f
                      const int32_t* neg_parent, int32_t M, int32_t n_slots, void* parts_ws, int64_t* counts, void* stream);
 int codae_score_outfits(codae_handle h, const codae_buffers* b, const float* data, int64_t n_rows, const int32_t* items, int32_t Q,
                         int32_t n_slots, float* cos, float* sq, float* score, int32_t* n_present, void* stream);
+
+/* ---- Outfit codes -----------------------------------------------------------------------------------------------------------
+ * The latent vector of an outfit, and the way back from it.  L Linears, h_0 the input, h_{l+1} as "Normalisation" defines it.
+ * Layer count.  A forward over the first k Linears, 1 <= k <= L - 1, yields h_k: the tensor the engine keeps in act[k] - the output
+ * of Linear k - 1 after its activation, its skip and its norm, where the settings put one - and exactly what Linear k reads.  It is
+ * an evaluation forward: no noise, no dropout, no criterion, no loss kernel, the metric sums are not touched.
+ * Values.  bf16 engine: bf16 numbers widened to fp32 (the low 16 bits of every word are zero), the bits the decoder consumes; fp32
+ * engine: the fp32 activations.
+ * codae_export_rows: dst[b][c] <- the stored src[b][c] widened to fp32, exactly (-0 and NaN payloads included), for b < B, c < width;
+ * src [B][ld_src] fp32 or (bf16 != 0) bf16, dst [B][ld_dst] fp32.  norm (or NULL) [B]: norm[b] = sqrt(sum_c v^2) in fp32 - the
+ * cand_norm of codae_complete_topk for a bank of codes, without a second pass (codae_row_norms) over it.  Columns of dst at or past
+ * width and rows at or past B are never written; src is never written.  A wave owns a row; 16-byte accesses where src and dst are
+ * 16-byte aligned, ld_src and width whole chunks (bf16 x 8, fp32 x 4) and ld_dst a multiple of 4, element accesses otherwise.  A
+ * lane adds its columns in ascending order and the 64 lanes are combined in one fixed tree: the bits of norm[b] depend on the row's
+ * values and width alone - not on B, the row's position, the leading dimensions or the access path.  No atomics: a NaN or Inf
+ * element gives its own row a NaN or Inf norm and touches no other.  CODAE_E_INVALID before any launch: a NULL or aliased src / dst,
+ * bf16 outside {0, 1}, B or width < 1, a leading dimension below width.
+ * codae_encode: x [B][io] dense fp32 -> act[0] as codae_forward ingests it, Linears 0 .. layers - 1 each into act[l + 1] - so every
+ * skip and norm of those layers runs, which a partial codae_forward cannot offer and refuses -, then code [B][out[layers - 1]]
+ * contiguous <- act[layers] through codae_export_rows, with norm [B] (or NULL).
+ * codae_decode: code [B][in[layer_lo]] dense fp32 -> act[layer_lo] the same way, Linears layer_lo .. L - 1 with their skips and
+ * norms (a skip around Linear layer_lo reads the code itself), the last one into y [B][io] fp32.  decode(encode(x)) has the bits of
+ * an evaluation forward of x at the same B.
+ * Both take b = the live buffers or those of the weight average; neither touches scalars, the parameters, the optimizer state, the
+ * step count or any random stream.  BOTH OVERWRITE THE ACTIVATIONS OF THE LAST FORWARD, as an evaluation does: a
+ * codae_step_backward must not follow one of them.  CODAE_E_INVALID, with the engine's state unchanged: layers / layer_lo outside
+ * [1, L - 1], B outside [1, max_batch], a NULL argument. */
+int codae_export_rows(const void* src, int32_t bf16, int64_t ld_src, int32_t B, int32_t width, float* dst, int64_t ld_dst, float* norm,
+                      void* stream);
+int codae_encode(codae_handle h, const codae_buffers* b, const float* x, int32_t B, int32_t layers, float* code, float* norm, void* stream);
+int codae_decode(codae_handle h, const codae_buffers* b, const float* code, int32_t B, int32_t layer_lo, float* y, void* stream);
 
 /* ---- State digest -------------------------------------------------------------------------------------------------------
  * A 128-bit fingerprint of a device buffer, computed on the device in one pass, and - with dst - a copy of the buffer made in that

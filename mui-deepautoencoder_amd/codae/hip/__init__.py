@@ -247,6 +247,9 @@ PROTOTYPES = {
     "codae_auc_blocks": (C.c_int, [_I32]),
     "codae_auc_counts": (C.c_int, [_P, _P, _I32, _P, _P, _P, _I32, _I32, _P, _P, _P]),
     "codae_score_outfits": (C.c_int, [_P, C.POINTER(Buffers), _P, _I64, _P, _I32, _I32, _P, _P, _P, _P, _P]),
+    "codae_export_rows": (C.c_int, [_P, _I32, _I64, _I32, _I32, _P, _I64, _P, _P]),
+    "codae_encode": (C.c_int, [_P, C.POINTER(Buffers), _P, _I32, _I32, _P, _P, _P]),
+    "codae_decode": (C.c_int, [_P, C.POINTER(Buffers), _P, _I32, _I32, _P, _P]),
     "codae_state_digest": (C.c_int, [_P, _P, _I64, _P, _P]),
     "codae_step_path": (C.c_int, [_P, _P, _I32]),
     "codae_debug_step_plan": (C.c_int, [_P, C.POINTER(Buffers), _P, _P, _I32]),

@@ -733,6 +733,58 @@ class DaeEngine:
         self._keep_outfits = (data, items)        # (raw pointers: alive until the next call's kernels are queued behind these)
         return out
 
+    def _dense_rows(self, who, t, width):
+        """t -> the contiguous fp32 [B, width] device tensor codae_encode / codae_decode read, 1 <= B <= max_batch"""
+        if not torch.is_tensor(t) or t.dim() != 2 or t.shape[1] != width or t.device != self.device:
+            raise HipError("%s: input must be a [B, %d] tensor on %s, got %s" % (
+                who, width, self.device, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+        if not 1 <= t.shape[0] <= self.max_batch:
+            raise HipError("%s: batch %d outside [1, %d]" % (who, t.shape[0], self.max_batch))
+        return t.detach().to(dtype=torch.float32).contiguous()
+
+    def _code_layer(self, who, k):
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= self.L - 1:
+            raise HipError("%s: layer must be an int in [1, %d], got %r" % (who, self.L - 1, k))
+        return k
+
+    def encode(self, x, layers, want_norm=False, weights="live", out=None, norm_out=None):
+        """codae_encode (include/codae_hip.h, "Outfit codes"): h_layers of an evaluation forward of x [B, io] -> [B, out[layers - 1]]
+        fp32, through every skip and norm of those layers (weights: "live" or "average"); want_norm: -> (code, norm [B]), the fp32
+        row norms the export kernel leaves in the same pass.  out / norm_out: contiguous fp32 [B, width] / [B] device tensors to
+        write to (a chunk of a preallocated bank and of its norms).  The metric sums, the parameters and the optimizer state are
+        not touched; the activations of the last forward are overwritten: no step_backward may follow.  No host synchronisation."""
+        k = self._code_layer("encode", layers)
+        x = self._dense_rows("encode", x, self.schedule[0][0])
+        B, Z = int(x.shape[0]), int(self.schedule[k - 1][1])
+        bufs = self._eval_bufs(weights)
+        if out is None:
+            out = torch.empty((B, Z), dtype=torch.float32, device=self.device)
+        elif not torch.is_tensor(out) or out.dtype != torch.float32 or out.device != self.device or tuple(out.shape) != (B, Z) or not out.is_contiguous():
+            raise HipError("encode: out must be a contiguous fp32 [%d, %d] tensor on %s" % (B, Z, self.device))
+        norm = None
+        if want_norm:
+            norm = torch.empty(B, dtype=torch.float32, device=self.device) if norm_out is None else norm_out
+            if norm.dtype != torch.float32 or norm.device != self.device or tuple(norm.shape) != (B,) or not norm.is_contiguous():
+                raise HipError("encode: norm_out must be a contiguous fp32 [%d] tensor on %s" % (B, self.device))
+        with torch.cuda.device(self.device):
+            check(self._lib.codae_encode(self._h, C.byref(bufs), ptr(x), B, k, ptr(out), ptr(norm), current_stream()))
+        self.generation += 1
+        self._keep_codes = x                      # (a raw pointer: alive until the next call's kernels are queued behind these)
+        return (out, norm) if want_norm else out
+
+    def decode(self, z, layer_lo, weights="live"):
+        """codae_decode: Linears layer_lo .. L - 1 on the code z [B, in[layer_lo]] - with their skips and norms; a skip around Linear
+        layer_lo reads z itself - -> the fp32 reconstruction [B, io].  Leaves what encode leaves."""
+        k = self._code_layer("decode", layer_lo)
+        z = self._dense_rows("decode", z, self.schedule[k][0])
+        bufs = self._eval_bufs(weights)
+        y = torch.empty((z.shape[0], self.schedule[self.L - 1][1]), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self._lib.codae_decode(self._h, C.byref(bufs), ptr(z), int(z.shape[0]), k, ptr(y), current_stream()))
+        self.generation += 1
+        self._keep_codes = z
+        return y
+
     def profile_begin(self, classes=("gemm_fwd", "gemm_dgrad", "gemm_wgrad"), max_records=4096, every=1):
         from . import KERNEL_CLASSES
         check(self._lib.codae_profile_stride(self._h, int(every)))

@@ -173,10 +173,13 @@ class ComplementRetriever:
     lowest dataset row.  Device tensors run codae_complete_topk (fp32 GEMM per candidate chunk + the HIP top-k selection
     kernel, no host synchronisation); host tensors a whole-tensor torch form of the same contract."""
 
-    def __init__(self, dataset, device, candidates=None, distinct=True):
+    def __init__(self, dataset, device, candidates=None, distinct=True, row_norms=None):
+        """row_norms: one-slot inventories only - an fp32 [n_obs] device tensor of the rows' norms that is already at hand (the
+        export kernel's, for a bank of codes): the device tables take the candidates' norms from it instead of sweeping them."""
         self.dataset = dataset
         self.device = device
         self.distinct = bool(distinct)
+        self.row_norms = row_norms
         self.S, self.E = int(dataset.nb_used_category), int(dataset.embedding_size)
         self.n_obs = int(dataset.data_per_category[0].shape[0])
         if candidates is None:
@@ -231,10 +234,14 @@ class ComplementRetriever:
             cand, count, row_id, pos = self._host_tables()
             S, n_cand = cand.shape[0], cand.shape[1]
             cand_d = cand.to(dev).contiguous()
-            norm = torch.empty((S, n_cand), dtype=torch.float32, device=dev)
-            with torch.cuda.device(dev):
-                _check(_hip_lib().codae_row_norms(_ptr(cand_d), S * n_cand, self.E, _ptr(norm), _stream()))
-            t = (cand_d, norm, (C.c_int32 * S)(*count), row_id.to(dev).contiguous(), pos.to(dev).contiguous())
+            row_id = row_id.to(dev).contiguous()
+            if self.row_norms is not None and S == 1:
+                norm = self.row_norms.to(dev)[row_id.clamp_min(0).long()].contiguous()      # candidate j is dataset row row_id[j]
+            else:
+                norm = torch.empty((S, n_cand), dtype=torch.float32, device=dev)
+                with torch.cuda.device(dev):
+                    _check(_hip_lib().codae_row_norms(_ptr(cand_d), S * n_cand, self.E, _ptr(norm), _stream()))
+            t = (cand_d, norm, (C.c_int32 * S)(*count), row_id, pos.to(dev).contiguous())
             self._tables[dev] = t
         return t
 

@@ -879,6 +879,104 @@ class HipEmbeddingTrainer:
         cm.trainer = self
         return cm
 
+    # ---- outfit codes (include/codae_hip.h, "Outfit codes"; codae/tool/codes.py) ------------------------------------------------
+    @property
+    def code_layers(self):
+        """k of the code h_k: the index, plus one, of the lowest hidden Linear without an activation - the z layer of every stack
+        linear_stack builds.  HipError when the stack has no such layer (encode(..., layer=k) then names it)."""
+        from .tool.codes import code_layers
+        return code_layers([(s[0], s[1], a) for s, a in zip(self.engine.schedule, self.engine.layer_activations())])
+
+    def _code_layer(self, who, layer):
+        from .tool.codes import check_layer
+        return self.code_layers if layer is None else check_layer(who, layer, self.engine.L)
+
+    def code_width(self, layer=None):
+        """Z: the width of h_k, k = layer or code_layers."""
+        return int(self.engine.schedule[self._code_layer("code_width()", layer) - 1][1])
+
+    def _blank_vector(self, who, blank, Q):
+        """blank -> None or an int32 [Q] device tensor (negative: none); a device tensor is not read back"""
+        if blank is None:
+            return None
+        S, _ = self._slots()
+        if torch.is_tensor(blank):
+            if blank.dim() != 1 or blank.shape[0] != Q or blank.dtype.is_floating_point or blank.dtype == torch.bool:
+                raise HipError("%s: blank must be None, an int slot or an integer [%d] tensor" % (who, Q))
+            return blank.to(device=self.device, dtype=torch.int32).contiguous()
+        if isinstance(blank, bool) or not isinstance(blank, int) or not -1 <= blank < S:
+            raise HipError("%s: blank must be None, an int slot in [0, %d) or an integer [Q] tensor, got %r" % (who, S, blank))
+        return torch.full((Q,), blank, dtype=torch.int32, device=self.device)
+
+    def _encode_into(self, it, bl, k, weights, code, norm):
+        """codes of the assembled outfits it [Q, S] (slot bl[q] blanked) into code [Q, Z] and norm [Q] (or None), in chunks of
+        max_batch, every chunk written at its offset; no host synchronisation"""
+        from .tool.compat import Compatibility
+        per = self.engine.max_batch
+        for o in range(0, int(it.shape[0]), per):
+            x = Compatibility.assemble(self.data, it[o:o + per], blank=None if bl is None else bl[o:o + per], presence=self.presence)
+            self.engine.encode(x, k, want_norm=norm is not None, weights=weights, out=code[o:o + per],
+                               norm_out=None if norm is None else norm[o:o + per])
+
+    def encode_items(self, items, blank=None, layer=None, weights="live", want_norm=False):
+        """The codes of assembled outfits: items integer [Q, S] in score_outfits' convention (negative = no item; with a presence
+        table a slot the row lacks is absent), assembled as complete_items assembles them - absent and blanked slots are zeros -
+        and run through the first k Linears of the evaluation forward with their skips and norms (k = layer, default
+        code_layers; weights: "live" or "average") -> [Q, Z] fp32 on the device, (codes, norms [Q]) with want_norm.  bf16 engine:
+        bf16 values widened to fp32.  blank: None (the whole outfit), an int slot, or an integer [Q] tensor with -1 for none - a
+        partial outfit ("this top and these shoes, any bottom").  Chunks of max_batch, no host synchronisation; epoch_sums(), the
+        parameters and the optimizer state stay exactly as they were."""
+        k = self._code_layer("encode()", layer)
+        it = self._outfit_items(items, "encode()")
+        Q = int(it.shape[0])
+        bl = self._blank_vector("encode()", blank, Q)
+        code = torch.empty((Q, self.code_width(k)), dtype=torch.float32, device=self.device)
+        norm = torch.empty(Q, dtype=torch.float32, device=self.device) if want_norm else None
+        self._encode_into(it, bl, k, weights, code, norm)
+        return (code, norm) if want_norm else code
+
+    def encode(self, row_idx, blank=None, layer=None, weights="live", want_norm=False):
+        """encode_items for resident rows: row r is the outfit [r, r, .., r]."""
+        S, _ = self._slots()
+        idx = torch.as_tensor(row_idx).reshape(-1)
+        if idx.dtype.is_floating_point or idx.dtype == torch.bool:
+            raise HipError("encode(): row_idx must be integer dataset rows, got %s" % idx.dtype)
+        return self.encode_items(idx[:, None].expand(-1, S), blank=blank, layer=layer, weights=weights, want_norm=want_norm)
+
+    def decode(self, z, layer=None, weights="live"):
+        """The reconstruction of codes: Linears k .. L - 1 on z [Q, Z] (k = layer, default code_layers) with their skips and norms
+        -> [Q, io] fp32 on the device.  decode(encode(rows, blank=c)) has the bits of eval_batch(rows, want_y=True) under the
+        one-slot mask {c} at the same batch size.  Chunked as encode."""
+        k = self._code_layer("decode()", layer)
+        Z = int(self.engine.schedule[k][0])
+        if not torch.is_tensor(z) or z.dim() != 2 or z.shape[1] != Z or z.shape[0] < 1:
+            raise HipError("decode(): codes must be a [Q, %d] tensor with Q >= 1, got %s" % (Z, tuple(z.shape) if torch.is_tensor(z) else type(z).__name__))
+        z = z.to(self.device)
+        per = self.engine.max_batch
+        parts = [self.engine.decode(z[o:o + per], k, weights=weights) for o in range(0, int(z.shape[0]), per)]
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+    def code_index(self, rows=None, blank=None, layer=None, weights="live", distinct=True):
+        """A tool.OutfitCodes over the codes of dataset rows `rows` (None = every resident row): the bank [M, Z], encoded chunk by
+        chunk into one preallocated tensor, its norms from the export kernel's same pass, and the rows the entries stand for.
+        similar(query, k, exclude) then ranks it against query codes from encode / encode_items."""
+        from .tool.codes import OutfitCodes
+        k = self._code_layer("code_index()", layer)
+        S, _ = self._slots()
+        if rows is None:
+            idx = torch.arange(int(self.data.shape[0]), dtype=torch.int32, device=self.device)
+        else:
+            idx = torch.as_tensor(rows).reshape(-1)
+            if idx.dtype.is_floating_point or idx.dtype == torch.bool:
+                raise HipError("code_index(): rows must be integer dataset rows, got %s" % idx.dtype)
+        it = self._outfit_items(idx[:, None].expand(-1, S), "code_index()")
+        M = int(it.shape[0])
+        bl = self._blank_vector("code_index()", blank, M)
+        bank = torch.empty((M, self.code_width(k)), dtype=torch.float32, device=self.device)
+        norm = torch.empty(M, dtype=torch.float32, device=self.device)
+        self._encode_into(it, bl, k, weights, bank, norm)
+        return OutfitCodes(bank, rows=None if rows is None else idx, norm=norm, layer=k, distinct=distinct)
+
     def epoch_sums(self, reset=True, reduce=True):
         """(sum (x-y)^2, sum (1-fmask)(x-y)^2) accumulated since the last reset (summed over the
         ranks when `reduce`)."""

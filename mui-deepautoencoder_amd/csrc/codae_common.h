@@ -605,6 +605,9 @@ struct NormBwd : StreamBwd {
 int launch_norm_fwd(void* y, int bf16, int64_t ld, int B, int width, int kind, float eps, float* rstd, uint8_t* bits, int64_t ld_bits,
                     hipStream_t s);
 int launch_norm_bwd(void* d, int bf16, int64_t ld, int B, int width, int kind, const NormBwd& n, float* colsum_part, hipStream_t s);
+// Outfit codes (codae_export_rows, include/codae_hip.h; codes.hip): dst [B][ld_dst] fp32 <- the stored rows of src (fp32 or bf16)
+// widened exactly, columns < width; norm [B] (may be null) <- the fp32 row norms, a wave per row, no atomics.
+int launch_export_rows(const void* src, int bf16, int64_t ld_src, int B, int width, float* dst, int64_t ld_dst, float* norm, hipStream_t s);
 int launch_mse_dense(const float* x, const float* y, const float* fmask, float* dy, int64_t n, float inv_n,
                      double* scalars, hipStream_t s);
 // optimizer.hip: the gradient norm, the clip coefficient, the update

@@ -1906,6 +1906,54 @@ int codae_score_outfits(codae_handle h, const codae_buffers* b, const float* dat
     return launch_outfit_scores(data, n_rows, io, n_slots, items, Q, pres, y, io, cos, sq, score, n_present, s);
 }
 
+// Outfit codes.  The dense fp32 rows of `x` into act[l] in working precision, as codae_forward ingests its input; the pad rows cleared.
+static int ingest_dense(codae_handle h, const codae_buffers* b, const float* x, int B, int rows, int l, hipStream_t s) {
+    codae_batch in{};
+    in.data = x; in.B = B; in.io = h->in[l];
+    int rc = launch_gather_noise(&in, nullptr, 0, nullptr, act_ptr(h, b, l), h->prec == CODAE_PREC_BF16, s, h->in_ld[l]);
+    if (rc) return rc;
+    return zero_pad_rows(h, act_ptr(h, b, l), B, rows, h->in_ld[l], s);
+}
+
+// h_layers of an evaluation forward: every layer lands in act[l + 1], so its skip and its norm run (codae_forward's partial range
+// writes the last Linear straight into the caller's tensor and would lose them); then the stored rows leave through the export kernel.
+int codae_encode(codae_handle h, const codae_buffers* b, const float* x, int32_t B, int32_t layers, float* code, float* norm, void* stream) {
+    int rc = check_common(h, b, B);
+    if (rc) return rc;
+    CODAE_REQUIRE(x && code, "codae_encode: null x or code");
+    CODAE_REQUIRE(layers >= 1 && layers <= h->L - 1, "codae_encode: %d layers outside [1, %d]", layers, h->L - 1);
+    hipStream_t s = (hipStream_t)stream;
+    const int rows = h->rows_for(B);
+    forward_leaves(h, nullptr, nullptr);      // (an evaluation forward)
+    rc = ingest_dense(h, b, x, B, rows, 0, s);
+    if (rc) return rc;
+    for (int l = 0; l < layers; ++l) {
+        rc = run_forward_layer(h, b, l, nullptr, B, rows, false, s);
+        if (rc) return rc;
+    }
+    ProfScope prof(h, CODAE_K_DROPOUT, s);     // the class of the streaming kernels between the GEMMs
+    return launch_export_rows(act_ptr(h, b, layers), h->prec == CODAE_PREC_BF16, h->in_ld[layers], B, h->in[layers], code, h->in[layers], norm, s);
+}
+
+// Linears layer_lo .. L - 1 on a code: it becomes act[layer_lo] (a skip around Linear layer_lo reads it there), the last Linear
+// writes the caller's fp32 tensor as every evaluation's does.
+int codae_decode(codae_handle h, const codae_buffers* b, const float* code, int32_t B, int32_t layer_lo, float* y, void* stream) {
+    int rc = check_common(h, b, B);
+    if (rc) return rc;
+    CODAE_REQUIRE(code && y, "codae_decode: null code or y");
+    CODAE_REQUIRE(layer_lo >= 1 && layer_lo <= h->L - 1, "codae_decode: layer %d outside [1, %d]", layer_lo, h->L - 1);
+    hipStream_t s = (hipStream_t)stream;
+    const int rows = h->rows_for(B), L = h->L;
+    forward_leaves(h, nullptr, nullptr);
+    rc = ingest_dense(h, b, code, B, rows, layer_lo, s);
+    if (rc) return rc;
+    for (int l = layer_lo; l < L; ++l) {
+        rc = run_forward_layer(h, b, l, l == L - 1 ? y : nullptr, B, rows, false, s);
+        if (rc) return rc;
+    }
+    return CODAE_OK;
+}
+
 // a layer range of the step's backward; join: the call returns with `stream` waiting for the side stream
 static int step_backward(const char* who, codae_handle h, const codae_buffers* b, int B, int layer_lo, int layer_hi, bool join, void* stream) {
     int rc = check_common(h, b, B);

@@ -20,14 +20,6 @@ namespace {
 // A lane owns 8 columns per chunk whatever the type - one 16-B access of bf16, two of fp32: exactly one mask byte.
 constexpr int NC = 8;
 
-// The sum of the wave's 64 values: a butterfly.  a + b and b + a have the same bits, so after every stage the two partners hold
-// the same value and the result does not depend on the lane; lane 0's copy is broadcast to say so.
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = opaque(v + __shfl_xor(v, m, 64));
-    return __shfl(v, 0, 64);
-}
-
 // ---- forward ----------------------------------------------------------------------------------------------------------------
 constexpr int FWD_WAVES = 4, FWD_NT = 64 * FWD_WAVES;
 

@@ -212,6 +212,11 @@ int codae_norm_bwd(void* d, int32_t bf16, int64_t ld, int32_t B, int32_t width, 
 
 int codae_norm_blocks(int32_t B) { return B > 0 ? row_sweep_blocks(B) : 0; }
 
+int codae_export_rows(const void* src, int32_t bf16, int64_t ld_src, int32_t B, int32_t width, float* dst, int64_t ld_dst, float* norm,
+                      void* stream) {
+    return launch_export_rows(src, bf16, ld_src, B, width, dst, ld_dst, norm, (hipStream_t)stream);
+}
+
 int codae_noise_box_muller(const uint32_t* ra, const uint32_t* rb, float* rho, float* c, float* s, int64_t n, void* stream) {
     return launch_noise_box_muller(ra, rb, rho, c, s, n, (hipStream_t)stream);
 }

@@ -1,4 +1,4 @@
-// Row accessors shared by the streaming kernels that sit between a step's GEMMs (dropout.hip, residual.hip, norm.hip): C columns of a
+// Row accessors shared by the streaming kernels that sit between a step's GEMMs (dropout.hip, residual.hip, norm.hip, codes.hip): C columns of a
 // working-precision row widened to fp32 and back, templated on <BF16, VEC> - 16 B per access where every row is 16-B aligned and the
 // width is whole chunks, element accesses otherwise; a column past the width is neither read nor written.
 #pragma once
@@ -83,6 +83,14 @@ __device__ __forceinline__ void store_work(void* row, int c, int width, const fl
             }
         }
     }
+}
+
+// The sum of the wave's 64 values: a butterfly.  a + b and b + a have the same bits, so after every stage the two partners hold
+// the same value and the result does not depend on the lane; lane 0's copy is broadcast to say so.  (norm.hip, codes.hip)
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = opaque(v + __shfl_xor(v, m, 64));
+    return __shfl(v, 0, 64);
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }

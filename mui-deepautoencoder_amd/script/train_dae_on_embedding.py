@@ -11,6 +11,10 @@ Checkpoints: `HIP: CHECKPOINT: {EVERY: 1, KEEP: 2, DIR: <the run's output direct
 EVERY-th epoch's validation sweep and keeps the newest KEEP; --resume PATH continues such a file's run at its next epoch, bit for bit
 the run that was never interrupted (codae.train.HipEmbeddingTrainer.save / load).
 
+Outfit codes: `HIP: CODES: {SAVE: true, LAYER: null, NEIGHBOURS: 0, DISTINCT: true}` writes codes.npz - every dataset row's latent
+vector and, with NEIGHBOURS k > 0, its k nearest other rows in code space - into the run's output directory after the last epoch
+(codae.train.HipEmbeddingTrainer.code_index, codae.tool.OutfitCodes).
+
 Extra flags: --precision {bf16,f32} (default: HIP.PRECISION of the config, else bf16; widths the
 bf16 tiles cannot take fall back to the exact-fp32 kernels), --epochs N (override MODEL.EPOCH).
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N`; each rank takes
@@ -275,6 +279,12 @@ def main():
         ck_every, ck_keep = int(ck.get("EVERY", 1)), int(ck.get("KEEP", 2))
         if ck_every < 1 or ck_keep < 1:
             raise HipError("HIP: CHECKPOINT: EVERY and KEEP must be at least 1, got %d and %d" % (ck_every, ck_keep))
+    # HIP: CODES: {SAVE: true, LAYER: null, NEIGHBOURS: 0, DISTINCT: true} (build-only key): after the last epoch every dataset row is
+    # encoded - on the averaged weights when WEIGHT_AVERAGE is set, as the validation sweep - and codes.npz goes to the run directory:
+    # codes [N, Z], rows, layer and, with NEIGHBOURS k > 0, each row's k nearest other rows in code space; absent = nothing is encoded,
+    # logged or written
+    from codae.tool import codes_from_config
+    codes_cfg = codes_from_config(config.get("HIP", {}).get("CODES"))
     run_dir = []
 
     def out_dir():
@@ -388,6 +398,21 @@ def main():
             pending.append((trainer.snapshot(), os.path.join(ck_dir, "checkpoint_epoch%d.npz" % (epoch + 1)), extra))
     write_pending()
     log.info("TRAINING HAS ENDED.")
+
+    if codes_cfg is not None and rank == 0:
+        index = trainer.code_index(layer=codes_cfg["layer"], weights=eval_weights, distinct=codes_cfg["distinct"])
+        n_rows = len(index)
+        out = {"codes": index.bank.cpu().numpy(), "rows": np.arange(n_rows, dtype=np.int64), "layer": np.int64(index.layer)}
+        if codes_cfg["neighbours"] > 0:
+            nb_idx, nb_score = [], []
+            for o in range(0, n_rows, trainer.engine.max_batch):          # self excluded: neighbours other than the outfit itself
+                rows = torch.arange(o, min(o + trainer.engine.max_batch, n_rows), device=device)
+                i, s = index.similar(index.bank[rows], codes_cfg["neighbours"], exclude=rows)
+                nb_idx.append(i.cpu().numpy()); nb_score.append(s.cpu().numpy())
+            out["neighbour_idx"], out["neighbour_score"] = np.concatenate(nb_idx), np.concatenate(nb_score)
+        codes_path = os.path.join(out_dir(), "codes.npz")
+        np.savez(codes_path, **out)
+        log.info("OUTFIT CODES: [%d, %d] layer %d -> %s" % (n_rows, index.width, index.layer, codes_path))
 
     if rank == 0:
         import matplotlib
