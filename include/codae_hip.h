@@ -83,6 +83,8 @@ extern "C" {
  *      new entries only, no layout or existing enum change; the two kernels are booked under CODAE_K_DROPOUT as well
  *      (still 11) + codae_export_rows, codae_encode, codae_decode: new entries with plain arguments only, no struct, no layout or enum
  *      change; the export kernel is booked under CODAE_K_DROPOUT as well
+ *      (still 11) + codae_nearest_centroid, codae_nearest_centroid_ws_bytes, codae_centroid_update, codae_centroid_update_ws_bytes: new
+ *      entries with plain arguments only, no struct, no layout or enum change, no profiling kind
  * The binding must refuse a library whose codae_abi_version() differs and must check its own struct sizes against
  * codae_struct_sizes() at load (mui-deepautoencoder_amd/codae/hip/__init__.py does both). */
 #define CODAE_ABI_VERSION 11
@@ -1302,6 +1304,46 @@ int codae_export_rows(const void* src, int32_t bf16, int64_t ld_src, int32_t B, 
                       void* stream);
 int codae_encode(codae_handle h, const codae_buffers* b, const float* x, int32_t B, int32_t layers, float* code, float* norm, void* stream);
 int codae_decode(codae_handle h, const codae_buffers* b, const float* code, int32_t B, int32_t layer_lo, float* y, void* stream);
+
+/* ---- Code clusters ----------------------------------------------------------------------------------------------------------
+ * Spherical k-means over a bank of codes: "which kinds of outfit are there, and to which does this one belong?".  The metric is the
+ * cosine, as in codae_complete_topk and the per-slot cosine loss.  codae.tool.CodeClusters is the Python side and states the same
+ * definitions in whole-tensor torch ops for host tensors.
+ * Notation.  x [M][Z] the bank (fp32), n_r its fp32 row norms as codae_export_rows leaves them, c [K][Z] fp32 centroids,
+ * eps = CODAE_COS_EPS.  op(v) is v as the product sees it: v itself in the f32 form (op_bf16 = 0), v rounded to bf16, nearest even, in
+ * the bf16 form (op_bf16 = 1).  A bank exported by the bf16 engine is bf16-valued already: only the centroids are rounded there.
+ * Nearest centroid (codae_nearest_centroid).
+ *   d[r][j] = sum_z op(x[r][z]) op(c[j][z]), accumulated in fp32 on the matrix cores.  The order of accumulation depends on Z alone: a
+ *   row's result does not depend on M, on the row's position, on its neighbours in a tile, on K's padding or on how the caller chunks
+ *   the rows; nor on the leading dimensions or the access path.
+ *   assign[r] = the lowest j whose d[r][j] equals the maximum over the non-NaN d[r][.]: -0 == +0, a tie goes to the lower index, a NaN
+ *   never wins.  assign[r] = -1 when every d[r][.] is NaN.
+ *   best[r] = d[r][assign[r]] / max(n_r, eps); the raw dot product when norm is NULL; NaN when assign[r] = -1.
+ *   Pad centroids and pad columns never take part: a pad's zero score does not beat a row whose real scores are all negative.
+ *   The [M][K] scores are never written: a wave keeps a running (max, index) pair per row across groups of 128 centroids.
+ *   ws: codae_nearest_centroid_ws_bytes(Z, K, op_bf16) bytes, 16-byte aligned: the centroids in the operand type, padded with zeros, staged
+ *   once per call.  x is read 16 bytes at a time where x is 16-byte aligned and ld_x and Z are multiples of 4, element by element
+ *   otherwise; padding is the library's business: caller memory past Z or K is never read and may hold NaN.  assign is int64 [M].
+ * Centroid update (codae_centroid_update).
+ *   sum_j = sum_{r : assign[r] = j} x[r] / max(n_r, eps): one fp32 division per element, fp32 adds; count_j = the number of members.
+ *   count_j > 0: c'[j] = sum_j / max(|sum_j|, eps), |sum_j| in fp32 in a fixed order.  count_j == 0: c'[j] = c[j] bit for bit - an empty
+ *   cluster keeps its centroid.  Rows with assign = -1 (or outside [0, K)) belong to nobody.
+ *   No float atomics: the rows are ordered by (cluster, row) with a counting sort (integer atomics count), every cluster's members are
+ *   added in ascending row order in a fixed tree.  The bits of c' are the same on every run and depend on no chunk or work space size.
+ *   counts int64 [K] <- count_j.  c_out may alias c_in.  ws: codae_centroid_update_ws_bytes(M, Z, K) bytes, 16-byte aligned.
+ * Fit (codae.tool.CodeClusters.fit).  Given c_0 and iters >= 0, for i = 0 .. iters - 1: a_i = nearest(c_i); changed[i] =
+ * #{r : a_i[r] != a_{i-1}[r]}, changed[0] = M; objective[i] = the float64 mean of best over the assigned rows (NaN without any);
+ * c_{i+1} = update(a_i, c_i).  Then assign = nearest(c_iters), score its best, objective[iters] its mean, counts its member counts: the
+ * returned assign always belongs to the returned centroids.  Everything is enqueued without a host synchronisation.
+ * Limits: 1 <= K <= 4096, M >= 1, Z >= 1, ld_x >= Z, ld_c >= Z.  Anything else, a NULL argument or op_bf16 outside {0, 1} is
+ * CODAE_E_INVALID with the offending value in codae_last_error(), before any launch; the _ws_bytes queries return -1.
+ * Neither entry is booked under a profiling kind: CODAE_K_COUNT stays as it is. */
+int64_t codae_nearest_centroid_ws_bytes(int32_t Z, int32_t K, int32_t op_bf16);
+int codae_nearest_centroid(const float* x, int64_t ld_x, int32_t M, int32_t Z, const float* c, int64_t ld_c, int32_t K, int32_t op_bf16,
+                           const float* norm, int64_t* assign, float* best, void* ws, void* stream);
+int64_t codae_centroid_update_ws_bytes(int32_t M, int32_t Z, int32_t K);
+int codae_centroid_update(const float* x, int64_t ld_x, int32_t M, int32_t Z, const float* norm, const int64_t* assign, const float* c_in,
+                          float* c_out, int64_t ld_c, int32_t K, int64_t* counts, void* ws, void* stream);
 
 /* ---- State digest -------------------------------------------------------------------------------------------------------
  * A 128-bit fingerprint of a device buffer, computed on the device in one pass, and - with dst - a copy of the buffer made in that

@@ -250,6 +250,10 @@ PROTOTYPES = {
     "codae_export_rows": (C.c_int, [_P, _I32, _I64, _I32, _I32, _P, _I64, _P, _P]),
     "codae_encode": (C.c_int, [_P, C.POINTER(Buffers), _P, _I32, _I32, _P, _P, _P]),
     "codae_decode": (C.c_int, [_P, C.POINTER(Buffers), _P, _I32, _I32, _P, _P]),
+    "codae_nearest_centroid_ws_bytes": (_I64, [_I32, _I32, _I32]),
+    "codae_nearest_centroid": (C.c_int, [_P, _I64, _I32, _I32, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
+    "codae_centroid_update_ws_bytes": (_I64, [_I32, _I32, _I32]),
+    "codae_centroid_update": (C.c_int, [_P, _I64, _I32, _I32, _P, _P, _P, _P, _I64, _I32, _P, _P, _P]),
     "codae_state_digest": (C.c_int, [_P, _P, _I64, _P, _P]),
     "codae_step_path": (C.c_int, [_P, _P, _I32]),
     "codae_debug_step_plan": (C.c_int, [_P, C.POINTER(Buffers), _P, _P, _I32]),

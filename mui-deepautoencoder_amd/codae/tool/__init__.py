@@ -2,7 +2,7 @@
 `from codae.tool import Corrupter, CombinedCriterion, ...` resolves here), gathered from this build's modules.
 The reference's legacy argparse table (codae/tool/parser.py) and attr-dict (dictionnary.py) are out of scope
 (SURVEY.md section 2): nothing on the path uses them, so they have no counterpart here."""
-from . import average, batching, codes, compat, contrast, corruption, criteria, dropout, emphasis, noise, norm, optimizer, presence, recon_loss, residual, runlog, tied
+from . import average, batching, clusters, codes, compat, contrast, corruption, criteria, dropout, emphasis, noise, norm, optimizer, presence, recon_loss, residual, runlog, tied
 
 _PUBLIC = {
     runlog: ("set_logging", "display_info", "get_date", "PlotDrawer", "export_parameters_to_json"),
@@ -26,6 +26,8 @@ _PUBLIC = {
     compat: ("Compatibility", "CompatibilityMetrics", "compatibility_from_config"),
     # the latent vector of an outfit and nearest neighbours in code space: "which outfits look like this one?"
     codes: ("OutfitCodes", "codes_from_config"),
+    # spherical k-means over a bank of codes: "which kinds of outfit are there, and to which does this one belong?"
+    clusters: ("CodeClusters", "clusters_from_config"),
 }
 __all__ = []
 for _module, _names in _PUBLIC.items():

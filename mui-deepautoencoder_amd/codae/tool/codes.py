@@ -69,6 +69,18 @@ class OutfitCodes:
             self.rows = r
         self._ret = None
         self._dev = {}
+        # the precision of the engine that wrote the bank ("bf16": every value is a bf16 number), as code_index records it; None = unknown
+        self.precision = None
+
+    def cluster(self, k, iters=25, seed=0, init="rows", precision=None):
+        """Spherical k-means over the bank: a tool.CodeClusters fitted on self.bank with self.norm and self.rows.  precision: the
+        operand type of the scores, "f32" or "bf16"; None = "bf16" for a bank the bf16 engine wrote (its values are bf16 numbers
+        already: only the centroids are rounded), "f32" otherwise - decided from the record code_index left, the bank is not
+        scanned.  Every entry counts once: `distinct` plays no part."""
+        from .clusters import CodeClusters
+        if precision is None:
+            precision = "bf16" if self.precision == "bf16" else "f32"
+        return CodeClusters.fit(self.bank, k, norm=self.norm, rows=self.rows, iters=iters, seed=seed, init=init, precision=precision)
 
     @property
     def width(self):

@@ -960,6 +960,7 @@ class HipEmbeddingTrainer:
         """A tool.OutfitCodes over the codes of dataset rows `rows` (None = every resident row): the bank [M, Z], encoded chunk by
         chunk into one preallocated tensor, its norms from the export kernel's same pass, and the rows the entries stand for.
         similar(query, k, exclude) then ranks it against query codes from encode / encode_items."""
+        from .hip import PREC_BF16
         from .tool.codes import OutfitCodes
         k = self._code_layer("code_index()", layer)
         S, _ = self._slots()
@@ -975,7 +976,9 @@ class HipEmbeddingTrainer:
         bank = torch.empty((M, self.code_width(k)), dtype=torch.float32, device=self.device)
         norm = torch.empty(M, dtype=torch.float32, device=self.device)
         self._encode_into(it, bl, k, weights, bank, norm)
-        return OutfitCodes(bank, rows=None if rows is None else idx, norm=norm, layer=k, distinct=distinct)
+        index = OutfitCodes(bank, rows=None if rows is None else idx, norm=norm, layer=k, distinct=distinct)
+        index.precision = "bf16" if self.engine.precision == PREC_BF16 else "f32"      # (cluster()'s default operand type)
+        return index
 
     def epoch_sums(self, reset=True, reduce=True):
         """(sum (x-y)^2, sum (1-fmask)(x-y)^2) accumulated since the last reset (summed over the

@@ -15,6 +15,9 @@ Outfit codes: `HIP: CODES: {SAVE: true, LAYER: null, NEIGHBOURS: 0, DISTINCT: tr
 vector and, with NEIGHBOURS k > 0, its k nearest other rows in code space - into the run's output directory after the last epoch
 (codae.train.HipEmbeddingTrainer.code_index, codae.tool.OutfitCodes).
 
+Code clusters: `HIP: CODE_CLUSTERS: {K: 64, ITERS: 25, SEED: 0, LAYER: null}` clusters those codes by spherical k-means on the device
+and writes clusters.npz - centroids, every row's cluster and score, counts, objective, changed - beside it (codae.tool.CodeClusters).
+
 Extra flags: --precision {bf16,f32} (default: HIP.PRECISION of the config, else bf16; widths the
 bf16 tiles cannot take fall back to the exact-fp32 kernels), --epochs N (override MODEL.EPOCH).
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N`; each rank takes
@@ -285,6 +288,11 @@ def main():
     # logged or written
     from codae.tool import codes_from_config
     codes_cfg = codes_from_config(config.get("HIP", {}).get("CODES"))
+    # HIP: CODE_CLUSTERS: {K: 64, ITERS: 25, SEED: 0, LAYER: null} (build-only key): after the last epoch the codes of every dataset row
+    # - those CODES encoded when both keys name the same layer - are clustered by spherical k-means and clusters.npz goes to the run
+    # directory: centroids, cluster [N], score [N], counts, objective, changed, rows, layer; absent = nothing is encoded, logged or written
+    from codae.tool import clusters_from_config
+    clusters_cfg = clusters_from_config(config.get("HIP", {}).get("CODE_CLUSTERS"))
     run_dir = []
 
     def out_dir():
@@ -399,6 +407,7 @@ def main():
     write_pending()
     log.info("TRAINING HAS ENDED.")
 
+    index = None
     if codes_cfg is not None and rank == 0:
         index = trainer.code_index(layer=codes_cfg["layer"], weights=eval_weights, distinct=codes_cfg["distinct"])
         n_rows = len(index)
@@ -413,6 +422,22 @@ def main():
         codes_path = os.path.join(out_dir(), "codes.npz")
         np.savez(codes_path, **out)
         log.info("OUTFIT CODES: [%d, %d] layer %d -> %s" % (n_rows, index.width, index.layer, codes_path))
+
+    if clusters_cfg is not None and rank == 0:
+        want = trainer.code_layers if clusters_cfg["layer"] is None else clusters_cfg["layer"]
+        reused = index is not None and index.layer == want                    # CODES encoded this layer already: one bank for both files
+        if not reused:
+            index = trainer.code_index(layer=clusters_cfg["layer"], weights=eval_weights)
+        fit = index.cluster(clusters_cfg["k"], iters=clusters_cfg["iters"], seed=clusters_cfg["seed"])
+        counts = fit.counts.cpu().numpy()
+        objective = fit.objective.cpu().numpy()
+        clusters_path = os.path.join(out_dir(), "clusters.npz")
+        np.savez(clusters_path, centroids=fit.centroids.cpu().numpy(), cluster=fit.assign.cpu().numpy(), score=fit.score.cpu().numpy(),
+                 counts=counts, objective=objective, changed=fit.changed.cpu().numpy(), rows=np.arange(len(index), dtype=np.int64),
+                 layer=np.int64(index.layer))
+        log.info("OUTFIT CLUSTERS: K %d, %d iterations, converged_at %s, objective %.6f, %d empty, bank %s -> %s" % (
+            fit.k, clusters_cfg["iters"], fit.converged_at, float(objective[-1]), int((counts == 0).sum()),
+            "reused" if reused else "encoded", clusters_path))
 
     if rank == 0:
         import matplotlib
