@@ -85,6 +85,8 @@ extern "C" {
  *      change; the export kernel is booked under CODAE_K_DROPOUT as well
  *      (still 11) + codae_nearest_centroid, codae_nearest_centroid_ws_bytes, codae_centroid_update, codae_centroid_update_ws_bytes: new
  *      entries with plain arguments only, no struct, no layout or enum change, no profiling kind
+ *      (still 11) + codae_sparse_code, codae_sparse_code_ws_bytes, codae_set_sparse_code, codae_sparse_code_fwd, codae_sparse_code_bwd,
+ *      codae_sparse_code_blocks: new entries only, no layout or enum change; the two kernels are booked under CODAE_K_DROPOUT as well
  * The binding must refuse a library whose codae_abi_version() differs and must check its own struct sizes against
  * codae_struct_sizes() at load (mui-deepautoencoder_amd/codae/hip/__init__.py does both). */
 #define CODAE_ABI_VERSION 11
@@ -422,6 +424,34 @@ typedef struct {
     int32_t kind;         /* CODAE_NORM_LAYER or CODAE_NORM_RMS, one kind for the stack */
     float eps;
 } codae_norm;
+
+/* Sparse code: the k-sparse autoencoder's hard top-k code layer (Makhzani & Frey 2013; the "TopK" form of sparse-autoencoder work).
+ * `layer` follows codae_encode's convention: it is the index of the Linear that READS the code, 1 <= layer <= L - 1; the Linear
+ * that produces it is m = layer - 1, and Z = out[m].  Sparsifying is the last thing layer m does, after the activation and the
+ * dropout factor.  For each batch row:
+ *   key(v) = the bit pattern of the STORED value v with the sign bit cleared, read as an unsigned integer (the stored value is a
+ *            bf16 number in the bf16 engine and fp32 in the fp32 engine; widening bf16 to fp32 keeps the order).  -0 and +0 have
+ *            the same key, Inf sorts above every finite value, and every NaN sorts above Inf, ordered by payload.
+ *   Columns are ranked by (key descending, column ascending).  The first `keep` columns are KEPT and their bits stay as stored;
+ *   every other column is stored as +0.  Because NaN ranks first, a NaN is always kept, so a NaN row still makes its outputs and
+ *   the loss NaN.
+ * Backward is selection, not multiplication: dA_m[b][j] is unchanged where column j was kept and exactly +0 elsewhere, even under
+ * a NaN gradient; the bias-gradient partial column sums of layer m are rewritten from those final values.
+ * keep == Z is accepted and is OFF; keep < 1 and keep > Z are refused.
+ * It is part of the MODEL, like the skips and the norm: every forward sparsifies - the training steps in every step form,
+ * codae_eval_step, codae_forward over the whole stack, codae_score_outfits, codae_encode (whose codes then have at most `keep`
+ * non-zeros per row) -, with whatever buffer set the call is given; codae_decode starts at Linear `layer` and takes the code as
+ * given.  The selection is per row: a shard of a batch gives the bits of the same rows of the whole batch, and nothing is kept
+ * between steps.
+ * Limits: no skip and no norm on layer m itself (a skip would add the dense h_m back; a norm's backward needs the full xhat, which
+ * the in-place store has overwritten) - skips and norms on every other layer are allowed, a skip around Linear `layer` included;
+ * the activation of layer m is CODAE_ACT_NONE, RELU or LEAKY (the derivative the GEMM epilogue takes from the saved output is then
+ * right wherever the value was kept, and what it takes under a dropped element is selected away); never the last layer.
+ * Pad columns (ld > width) and pad rows are never written. */
+typedef struct {
+    int32_t layer;        /* the Linear that reads the code: 1 .. n_layers - 1 */
+    int32_t keep;         /* units kept per row: 1 .. Z; Z = off */
+} codae_sparse_code;
 
 /* Optimizer and schedule: what the update at the end of every training step does with the clipped gradient; the default is the line
  * the reference script hard-wires, clip_grad_norm_ + torch.optim.Adam with L2 decay, AMSGrad off and a constant lr.
@@ -838,6 +868,24 @@ int codae_set_residual(codae_handle h, const codae_residual* r, void* ws, int64_
  * layer range, return CODAE_E_UNSUPPORTED.  A step backward needs a training forward before it: only that writes the masks. */
 int64_t codae_norm_ws_bytes(codae_handle h, const codae_norm* n);
 int codae_set_norm(codae_handle h, const codae_norm* n, void* ws, int64_t ws_bytes);
+/* Sparse code ("Sparse code" above) of every call that follows - training steps in every step form AND every evaluation forward; a
+ * change re-captures the graph.  NULL, or keep == Z, switches it off: the engine then runs exactly the launches it ran before, bit
+ * for bit, codae_step_path included, and ws may be NULL.  CODAE_E_INVALID for a layer outside [1, n_layers], a keep outside [1, Z],
+ * a ws that is NULL, not 16-byte aligned or smaller than codae_sparse_code_ws_bytes says; CODAE_E_UNSUPPORTED for layer == n_layers
+ * (the last layer's output is the reconstruction), for a layer m behind RELU6, ELU, SOFTPLUS or HARDSIGMOID, and for a layer m that
+ * the residual or the norm setting in force covers - and codae_set_residual / codae_set_norm refuse a setting that covers layer m
+ * while a sparse code is on; the message names the layer and the reason ("name the layers and leave out layer m").  On any error
+ * nothing is launched and the previous setting stays.  ws is borrowed until the setting is replaced; it holds the 1-bit keep mask
+ * of the last training forward ([max_batch] rows, ceil(Z / 8) bytes apart; column 8 j + i in bit i of byte j, pad bits 0), its
+ * contents need not be zero, and codae_sizes / codae_buffers do not change.  codae_sparse_code_ws_bytes: the bytes needed (0 when
+ * off), or -1 with the same errors.
+ * While it is on: one stand-alone kernel behind the forward GEMM of layer m (behind its dropout kernel), and one behind the
+ * data-gradient GEMM that produces dA_m (behind the residual kernel of a skip around Linear `layer`, in front of dropout's), both
+ * class CODAE_K_DROPOUT; the stack stays off the persistent chain kernel (codae_step_path reports 0), and nothing else of the step
+ * plan changes.  codae_backward, and codae_forward over a partial layer range, return CODAE_E_UNSUPPORTED.  A step backward needs a
+ * training forward before it: only that writes the mask. */
+int64_t codae_sparse_code_ws_bytes(codae_handle h, const codae_sparse_code* c);
+int codae_set_sparse_code(codae_handle h, const codae_sparse_code* c, void* ws, int64_t ws_bytes);
 /* Slot contrast of every training step that follows (the step forms codae_set_input_noise lists; a change re-captures the graph;
  * under replay the step index is read from scalars[CODAE_S_ADAM_STEP]).  NULL or weight == 0 switches it off: the engine then runs
  * exactly what it ran before, bit for bit, codae_step_path included.  CODAE_E_INVALID for n_neg outside [1, 4096], a tau that is
@@ -1056,6 +1104,22 @@ int codae_norm_bwd(void* d, int32_t bf16, int64_t ld, int32_t B, int32_t width, 
                    const float* rstd, const float* g_in, float* g_out, int64_t ld_g, const uint8_t* bits, int64_t ld_bits,
                    int32_t act_kind, const float* act_param, float* colsum_part, void* stream);
 int codae_norm_blocks(int32_t B);        /* part rows codae_norm_bwd writes: one per 64 batch rows */
+/* The two sparse-code kernels on their own (the launchers the engine uses; "Sparse code" above has the definition), on rows < B and
+ * columns < width of a [B][ld] matrix, fp32 or (bf16 != 0) bf16; pad columns and pad rows are never touched.  Both move bits, not
+ * floats; 16-byte accesses where the base address, ld and the width allow (bf16 x 8, fp32 x 4), element accesses otherwise.
+ * forward: a wave owns a row and finds its keep-th key by a radix select over the 15 / 31 magnitude bits (8-bit digits, a histogram
+ * of integer counts per wave; the row is re-read per pass, so any width >= 1 works), resolves ties at that key by ascending column
+ * and rewrites the row in place; 1 <= keep <= width (keep == width keeps every bit).  bits != NULL: bits[b][j] <- the keep mask of
+ * columns 8 j .. 8 j + 7 (bits past the width clear), rows ld_bits >= ceil(width / 8) bytes apart; bits == NULL (an evaluation
+ * forward) gives the same values.
+ * backward: d <- kept ? d : +0 in place from `bits`.  One block per 64 batch rows - codae_sparse_code_blocks(B) of them - and each
+ * leaves one row of colsum_part [blocks][width] (column sums of the STORED d widened to fp32; may be NULL) with plain stores added
+ * in a fixed order.  The same inputs give the same bits, and a row's results do not depend on the other rows of the call. */
+int codae_sparse_code_fwd(void* y, int32_t bf16, int64_t ld, int32_t B, int32_t width, int32_t keep, uint8_t* bits, int64_t ld_bits,
+                          void* stream);
+int codae_sparse_code_bwd(void* d, int32_t bf16, int64_t ld, int32_t B, int32_t width, const uint8_t* bits, int64_t ld_bits,
+                          float* colsum_part, void* stream);
+int codae_sparse_code_blocks(int32_t B); /* part rows codae_sparse_code_bwd writes: one per 64 batch rows */
 /* The Gaussian kind's device arithmetic on given words (tools/noise_accuracy.py sweeps all 2^24 values of u1 and of u2 through
  * it): rho[i] = sqrt(-2 ln u1(ra[i])), c[i] = cos(2 pi u2(rb[i])), s[i] = sin(2 pi u2(rb[i])); the unit normals of a pair are
  * rho c and rho s. */

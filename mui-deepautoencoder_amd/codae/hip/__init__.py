@@ -134,6 +134,11 @@ class NormFlags(C.Structure):
     _fields_ = [("n", C.c_int32), ("on", C.POINTER(C.c_uint8)), ("kind", C.c_int32), ("eps", C.c_float)]
 
 
+class SparseCodeCfg(C.Structure):
+    """codae_sparse_code: layer = the Linear that reads the code (1 .. n_layers - 1), keep = the units kept per row (Z = off)"""
+    _fields_ = [("layer", C.c_int32), ("keep", C.c_int32)]
+
+
 _P, _I32, _I64, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
 # name -> (restype, argtypes); mirrors include/codae_hip.h one to one
@@ -209,6 +214,11 @@ PROTOTYPES = {
     "codae_norm_fwd": (C.c_int, [_P, _I32, _I64, _I32, _I32, _I32, _F, _P, _P, _I64, _P]),
     "codae_norm_bwd": (C.c_int, [_P, _I32, _I64, _I32, _I32, _I32, _P, _I64, _P, _P, _P, _I64, _P, _I64, _I32, _P, _P, _P]),
     "codae_norm_blocks": (C.c_int, [_I32]),
+    "codae_sparse_code_ws_bytes": (_I64, [_P, C.POINTER(SparseCodeCfg)]),
+    "codae_set_sparse_code": (C.c_int, [_P, C.POINTER(SparseCodeCfg), _P, _I64]),
+    "codae_sparse_code_fwd": (C.c_int, [_P, _I32, _I64, _I32, _I32, _I32, _P, _I64, _P]),
+    "codae_sparse_code_bwd": (C.c_int, [_P, _I32, _I64, _I32, _I32, _P, _I64, _P, _P]),
+    "codae_sparse_code_blocks": (C.c_int, [_I32]),
     "codae_emph_loss": (C.c_int, [C.POINTER(Batch), C.POINTER(Noise), _I32, C.POINTER(Emphasis), _P, _P, _I32, _I64, _F, _P, _P, _P]),
     "codae_emph_loss_blocks": (C.c_int, [_I32]),
     "codae_recon_loss_fwd_bwd": (C.c_int, [C.POINTER(Batch), C.POINTER(Noise), _I32, C.POINTER(Emphasis), C.POINTER(ReconLoss), _P, _P, _I32, _I64,

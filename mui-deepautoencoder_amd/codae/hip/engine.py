@@ -124,6 +124,9 @@ class DaeEngine:
         self.norm = None              # the codae.tool.Norm in force (None = off)
         self.norm_layers = []         # the normalised layers it resolved to on this stack
         self._norm_ws = None          # the device tensor codae_set_norm borrows (r per row and the 1-bit masks)
+        self.sparse_code = None       # the codae.tool.SparseCode in force (None = off)
+        self.sparse_resolved = None   # (m, Z) it resolved to on this stack: the producing layer and the width of the code
+        self._sparse_ws = None        # the device tensor codae_set_sparse_code borrows (the 1-bit keep mask)
         self.recon_loss = None
         self.slot_contrast = None
         self._contrast_pins = None    # the device tensors codae_slot_contrast borrows (pool, item ids, work space)
@@ -612,6 +615,42 @@ class DaeEngine:
             ws = torch.empty(need, dtype=torch.uint8, device=self.device) if need else None
             check(self._lib.codae_set_norm(self._h, C.byref(st), ptr(ws), need))
         self.norm, self.norm_layers, self._norm_ws = norm, [l for l, f in enumerate(flags) if f], ws
+
+    def set_sparse_code(self, sparse):
+        """sparse: a codae.tool.SparseCode, or None to switch it off.  Every call that follows - training steps in every step form,
+        eval steps, forward, score_outfits, encode, with the engine's own or the averaged weights - keeps the `keep` first-ranked
+        units of the code layer's output per batch row and stores +0 elsewhere (include/codae_hip.h, "Sparse code"); with
+        graph=True the next step re-captures.  While it is on, step_path() is 'layers'; backward() and a forward over a partial
+        layer range raise.  The producing layer m takes neither skip nor norm, has no activation, ReLU or LeakyReLU and is never
+        the last (HipError naming the layer otherwise; the previous setting stays).  None, or keep == Z = off: the engine runs
+        exactly what it ran before.  The work space (the 1-bit keep mask of the last training forward, sparse_bits) is allocated
+        here and borrowed by the library until the setting is replaced."""
+        if sparse is not None and not (hasattr(sparse, "resolve") and hasattr(sparse, "keep")):
+            raise HipError("set_sparse_code: expected a codae.tool.SparseCode or None, got %r" % (sparse,))
+        if sparse is None:
+            check(self._lib.codae_set_sparse_code(self._h, None, None, 0))
+            self.sparse_code, self.sparse_resolved, self._sparse_ws = None, None, None
+            return
+        m, Z = sparse.resolve([s[0] for s in self.schedule], [s[1] for s in self.schedule], self.layer_activations(), self.residual, self.norm)
+        from . import SparseCodeCfg
+        st = SparseCodeCfg(m + 1, int(sparse.keep))
+        # (a setting the library refuses gives -1 here: no work space then, and the setter itself reports the error with its own code)
+        need = max(int(self._lib.codae_sparse_code_ws_bytes(self._h, C.byref(st))), 0)
+        with torch.cuda.device(self.device):
+            ws = torch.empty(need, dtype=torch.uint8, device=self.device) if need else None
+            check(self._lib.codae_set_sparse_code(self._h, C.byref(st), ptr(ws), need))
+        # (keep == Z is accepted and is off: nothing resolved, no work space)
+        self.sparse_code, self.sparse_resolved, self._sparse_ws = sparse, (m, Z) if sparse.keep < Z else None, ws
+
+    def sparse_bits(self, B):
+        """The 1-bit keep mask the last training forward left: uint8 [B, ceil(Z / 8)] (a view of the work space; column 8 j + i in
+        bit i of byte j, pad bits 0).  For tests and diagnostics."""
+        if self._sparse_ws is None:
+            raise HipError("sparse_bits: no sparse code is on")
+        if not 1 <= int(B) <= self.max_batch:
+            raise HipError("sparse_bits: batch %d outside [1, %d]" % (B, self.max_batch))
+        ldb = (self.sparse_resolved[1] + 7) // 8
+        return self._sparse_ws[:int(B) * ldb].view(int(B), ldb)
 
     def train_step(self, batch, hyper, graph=False):
         """graph=True: replay the step from a hipGraph (captured on first use; batch.row_idx / mask_id must be

@@ -2,7 +2,7 @@
 `from codae.tool import Corrupter, CombinedCriterion, ...` resolves here), gathered from this build's modules.
 The reference's legacy argparse table (codae/tool/parser.py) and attr-dict (dictionnary.py) are out of scope
 (SURVEY.md section 2): nothing on the path uses them, so they have no counterpart here."""
-from . import average, batching, clusters, codes, compat, contrast, corruption, criteria, dropout, emphasis, noise, norm, optimizer, presence, recon_loss, residual, runlog, tied
+from . import average, batching, clusters, codes, compat, contrast, corruption, criteria, dropout, emphasis, noise, norm, optimizer, presence, recon_loss, residual, runlog, sparse, tied
 
 _PUBLIC = {
     runlog: ("set_logging", "display_info", "get_date", "PlotDrawer", "export_parameters_to_json"),
@@ -16,6 +16,8 @@ _PUBLIC = {
     presence: ("SlotPresence",),   # rows that lack an item in some slots: absent slots stay out of input, loss and inventory
     dropout: ("HiddenDropout",),   # torch users expect Dropout between the Linears: the fused step's form of it
     norm: ("Norm", "norm_from_config"),   # parameter-free layer / RMS normalisation of hidden outputs, per batch row, in every forward
+    # the k-sparse autoencoder's hard top-k code layer: the `keep` largest-magnitude units of the code per row, in every forward
+    sparse: ("SparseCode", "sparse_from_config"),
     residual: ("Residual", "residual_from_config"),   # identity skips around equal-width hidden layers, in every forward
     optimizer: ("Optimizer", "LRSchedule", "optimizer_from_config"),   # what the update does: AdamW / SGD / AMSGrad, lr schedule
     average: ("WeightAverage", "weight_average_from_config"),   # an EMA / SWA of the iterates kept by the update, for evaluation

@@ -140,12 +140,14 @@ class OutfitCodes:
         return idx, score
 
     @staticmethod
-    def forward_to(x, weights, biases, activation, layers, residual=None, norm=None):
+    def forward_to(x, weights, biases, activation, layers, residual=None, norm=None, sparse=None):
         """h_layers of the definition in whole-tensor torch ops (autograd works through it): weights[l] [out, in], biases[l]
-        [out]; activation per layer as Norm.resolve takes it; residual / norm: None or the codae.tool.Residual / Norm of the
-        stack.  The counterpart of Norm.forward and Residual.forward, stopped behind Linear layers - 1."""
+        [out]; activation per layer as Norm.resolve takes it; residual / norm / sparse: None or the codae.tool.Residual / Norm /
+        SparseCode of the stack.  The counterpart of Norm.forward and Residual.forward, stopped behind Linear layers - 1."""
         L = len(weights)
         k = check_layer("forward_to", layers, L)
+        if sparse is not None:
+            return sparse.forward(x, weights, biases, activation, residual=residual, norm=norm, layers=k)
         acts = [_act_tuple(a) for a in activation]
         ins, outs = [int(w.shape[1]) for w in weights], [int(w.shape[0]) for w in weights]
         skips = residual.resolve(ins, outs, acts) if residual is not None else [0] * L

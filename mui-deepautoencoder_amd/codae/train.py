@@ -436,7 +436,7 @@ class HipEmbeddingTrainer:
                  max_batch=8192, precision="bf16", device="cuda:0", distributed=False, n_buckets=None, use_graph=False,
                  sharded_update=False, native_dp=False, activation=None, n_slots=None, input_noise=None,
                  loss_emphasis=None, hidden_dropout=None, criterion=None, contrast=None, optimizer=None, presence=None,
-                 tied_weights=None, dataset_image=True, weight_average=None, residual=None, norm=None):
+                 tied_weights=None, dataset_image=True, weight_average=None, residual=None, norm=None, sparse_code=None):
         """use_graph: replay the fused step from a hipGraph (codae_train_step_graph): for launch-bound shapes
         (small batches); single process only - the bucketed data-parallel step is not captured.
         activation: what follows every hidden Linear, as the model classes take it (a factory called as activation(True),
@@ -492,7 +492,13 @@ class HipEmbeddingTrainer:
         activation, dropout and the skip (never the last layer; after no activation, ReLU or LeakyReLU; any widths).  It is part
         of the model like the skips: every step form, eval_batch, complete, score_outfits and weights="average" run through it,
         and checkpoints record it.  A layer that cannot take it is refused (HipError naming the layer and the reason).  None (or
-        no layer) = off, exactly as before."""
+        no layer) = off, exactly as before.
+        sparse_code: a codae.tool.SparseCode(keep, layer=None): the hard top-k code layer of a k-sparse autoencoder - per batch row
+        the `keep` units of h_layer (default: code_layers) that rank first by magnitude keep their bits, every other unit is +0,
+        and the backward selects the same units.  It is part of the model like the skips and the norm: every step form,
+        eval_batch, complete, score_outfits, encode, code_index and weights="average" run through it, and checkpoints record it.
+        The producing layer takes neither skip nor norm (name the other layers), has no activation, ReLU or LeakyReLU and is
+        never the last (HipError naming the layer and the reason).  None, or keep == Z = off, exactly as before."""
         from .hip.engine import DaeEngine
         fit_host_threads()      # the loop that feeds this trainer must not get its container CPU-throttled (codae/hostcpu.py)
         self.device = torch.device(device)
@@ -516,6 +522,8 @@ class HipEmbeddingTrainer:
             self.set_residual(residual)
         if norm is not None:
             self.set_norm(norm)
+        if sparse_code is not None:
+            self.set_sparse_code(sparse_code)
         if criterion is not None:
             self.set_criterion(criterion)
         if contrast is not None:
@@ -637,6 +645,10 @@ class HipEmbeddingTrainer:
     def set_norm(self, norm):
         """DaeEngine.set_norm: a codae.tool.Norm, or None to switch the normalisation off."""
         self.engine.set_norm(norm)
+
+    def set_sparse_code(self, sparse_code):
+        """DaeEngine.set_sparse_code: a codae.tool.SparseCode, or None to switch the sparse code off."""
+        self.engine.set_sparse_code(sparse_code)
 
     # ---- parameters ---------------------------------------------------------------------
     def load_params(self, params):
@@ -1027,6 +1039,10 @@ class HipEmbeddingTrainer:
         }
         if norm is not None:          # (written only when a norm is on: the files of runs without one keep their bytes)
             meta["norm"] = norm       # {kind, eps, layers}: part of the model, load() checks it
+        from .tool.sparse import meta_record as sparse_record
+        sparse = sparse_record(getattr(eng, "sparse_code", None), getattr(eng, "sparse_resolved", None))
+        if sparse is not None:        # (written only when it is on, as the norm's)
+            meta["sparse_code"] = sparse      # {keep, layer}: part of the model, load() checks it
         return meta
 
     def snapshot(self):
@@ -1105,6 +1121,10 @@ class HipEmbeddingTrainer:
         why = norm_mismatch(meta, getattr(eng, "norm", None), getattr(eng, "norm_layers", None))
         if why is not None:
             refuse("norm", why)
+        from .tool.sparse import meta_mismatch as sparse_mismatch
+        why = sparse_mismatch(meta, getattr(eng, "sparse_code", None), getattr(eng, "sparse_resolved", None))
+        if why is not None:
+            refuse("sparse_code", why)
         live = eng.state_tensors()
         for n in need:
             if n not in tensors:
@@ -1147,7 +1167,7 @@ class HipEmbeddingTrainer:
     def load(self, path, strict=True):
         """Restore the state save() wrote, so that the next step is bit for bit the step the writing run took next.  Structure first
         (HipError naming the piece; the trainer stays as it was): the schedule and parameter count, tied weights on in one and off in
-        the other, residual connections around other layers or another norm (a file without the record has none), adam_vmax missing while AMSGrad is on; under `strict` also an average missing while averaging is on, another
+        the other, residual connections around other layers, another norm or another sparse code (a file without the record has none), adam_vmax missing while AMSGrad is on; under `strict` also an average missing while averaging is on, another
         precision or activation, and optional tensors this trainer does not keep.  Then every tensor is uploaded into a temporary,
         digested on the device and compared with the file's record (HipError naming the tensor; nothing is kept), and only then
         copied over the live state.  On success: step_count is set, the scalars are the file's, the bf16 shadows are rebuilt
@@ -1184,7 +1204,7 @@ class HipEmbeddingTrainer:
     @classmethod
     def load_for_inference(cls, path, data, mask_table_u8=None, mask_to_use_i32=None, n_slots=None, max_batch=8192, device="cuda:0",
                            presence=None):
-        """A trainer built from the file's own record (schedule, precision, activation, tied weights, skips, norm, the kind of average) over
+        """A trainer built from the file's own record (schedule, precision, activation, tied weights, skips, norm, sparse code, the kind of average) over
         `data`, holding the file's parameters and - when it has one - weight average, each verified on the device as load() does:
         eval_batch, complete*, score_outfits and the metrics give what the writing process gave.  The moments are neither read nor
         required (a file stripped of them loads)."""
@@ -1192,6 +1212,7 @@ class HipEmbeddingTrainer:
         from .tool.checkpoint import CheckpointError, read_checkpoint
         from .tool.residual import Residual
         from .tool.norm import norm_from_meta
+        from .tool.sparse import sparse_from_meta
         try:
             tensors, meta = read_checkpoint(path, verify=False)
         except CheckpointError as e:
@@ -1201,7 +1222,7 @@ class HipEmbeddingTrainer:
                  clip=meta.get("clip", 0.0), max_batch=max_batch, precision=meta.get("precision", "bf16"), device=device,
                  activation=None if act is None else [tuple(a) for a in act], n_slots=n_slots, presence=presence,
                  tied_weights=bool(meta.get("tied_weights")), residual=Residual(meta["residual"]) if meta.get("residual") else None,
-                 norm=norm_from_meta(meta))
+                 norm=norm_from_meta(meta), sparse_code=sparse_from_meta(meta))
         eng = tr.engine
         names = ["params"]
         wa = meta.get("weight_average")

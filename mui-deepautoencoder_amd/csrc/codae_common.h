@@ -605,6 +605,13 @@ struct NormBwd : StreamBwd {
 int launch_norm_fwd(void* y, int bf16, int64_t ld, int B, int width, int kind, float eps, float* rstd, uint8_t* bits, int64_t ld_bits,
                     hipStream_t s);
 int launch_norm_bwd(void* d, int bf16, int64_t ld, int B, int width, int kind, const NormBwd& n, float* colsum_part, hipStream_t s);
+// Sparse code (codae_sparse_code, include/codae_hip.h; sparse_code.hip): the two streaming kernels of the layer that produces the
+// code.  forward: per row < B the `keep` columns < width that rank first by (key descending, column ascending) keep their bits, the
+// others are stored as +0; bits != null: the 1-bit keep mask (layout of the residual masks).  backward: d <- kept ? d : +0 and the
+// column sums of the stored values, the sweep of row_sweep.h.
+int launch_sparse_code_fwd(void* y, int bf16, int64_t ld, int B, int width, int keep, uint8_t* bits, int64_t ld_bits, hipStream_t s);
+int launch_sparse_code_bwd(void* d, int bf16, int64_t ld, int B, int width, const uint8_t* bits, int64_t ld_bits, float* colsum_part,
+                           hipStream_t s);
 // Outfit codes (codae_export_rows, include/codae_hip.h; codes.hip): dst [B][ld_dst] fp32 <- the stored rows of src (fp32 or bf16)
 // widened exactly, columns < width; norm [B] (may be null) <- the fp32 row norms, a wave per row, no atomics.
 int launch_export_rows(const void* src, int bf16, int64_t ld_src, int B, int width, float* dst, int64_t ld_dst, float* norm, hipStream_t s);

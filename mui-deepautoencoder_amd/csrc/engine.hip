@@ -104,6 +104,7 @@ struct codae_engine {
     struct ImageCfg { const float* data; const void* image; int64_t n_rows; int32_t io; int32_t reserved; };
     struct ResCfg { uint8_t on[64]; void* ws; int64_t ws_bytes; int32_t any; int32_t reserved; };
     struct NormCfg { uint8_t on[64]; void* ws; int64_t ws_bytes; int32_t any; int32_t kind; float eps; int32_t reserved; };
+    struct SparseCfg { void* ws; int64_t ws_bytes; int32_t on; int32_t m; int32_t keep; int32_t reserved; };
     struct TrainCfg {
         codae_noise noise;               // input noise (codae_set_input_noise); kind NONE = off
         codae_swap swap;                 // slots and pool of CODAE_NOISE_SWAP (codae_set_swap_pool); n_slots 0 = not set
@@ -119,6 +120,7 @@ struct codae_engine {
         codae_weight_average avg;        // average of the iterates kept by the update (codae_set_weight_average); all zero = off
         ResCfg res;                      // residual connections (codae_set_residual): on[l] = a skip around layer l, all zero = off
         NormCfg norm;                    // normalisation (codae_set_norm): on[l] = layer l's output is normalised, all zero = off
+        SparseCfg sparse;                // sparse code (codae_set_sparse_code): the `keep` first-ranked units of layer m's output, all zero = off
     } tc;
     bool recon_on() const { return tc.recon.kind != CODAE_LOSS_MSE; }
     bool contrast_on() const { return tc.contrast.weight != 0.f; }
@@ -146,6 +148,9 @@ struct codae_engine {
     // layer's mask is the residual kernel's); norm_bits_live = the last forward was a training forward and wrote them
     std::vector<int64_t> norm_r_off, norm_bits_off;
     bool norm_bits_live = false;
+    // sparse code: the setting's work space is the 1-bit keep mask of layer m ([max_batch] rows, ceil(out[m] / 8) bytes apart);
+    // sparse_bits_live = the last forward was a training forward and wrote it
+    bool sparse_bits_live = false;
     std::vector<int> parts_pending;
     // backward on two streams: the weight-gradient GEMMs (+ slab reduce) run on `side`, concurrently with
     // the data-gradient chain on the caller's stream (they only share the read-only dA_l)
@@ -494,9 +499,10 @@ StepPlan step_plan(const codae_engine* e, const codae_buffers* b, const StepCall
     const bool backward = c.kind == STEP_TRAIN || c.kind == STEP_BACKWARD || c.kind == STEP_DROPIN_BACKWARD;
     const bool training = c.kind == STEP_TRAIN || c.kind == STEP_FORWARD_LOSS;       // (the forward has a hyper)
     // (the chain kernel fuses the plain gather and the unweighted loss and keeps the activations to itself: a noised input, an
-    //  emphasised loss, another criterion, hidden dropout, a skip, a norm or a slot-presence table takes the per-layer launches)
+    //  emphasised loss, another criterion, hidden dropout, a skip, a norm, a sparse code or a slot-presence table takes the per-layer
+    //  launches)
     if (c.kind == STEP_TRAIN && e->chain_ok && e->plain_mse() && e->tc.noise.kind == CODAE_NOISE_NONE && !e->tc.drop.on &&
-        !e->tc.res.any && !e->tc.norm.any && b->shadow_wt != nullptr && p.rows <= CHAIN_MAX_ROWS) {
+        !e->tc.res.any && !e->tc.norm.any && !e->tc.sparse.on && b->shadow_wt != nullptr && p.rows <= CHAIN_MAX_ROWS) {
         // narrow stack: persistent fused chain + grouped weight gradients (4 launches for the whole step)
         p.path = PATH_CHAIN;
         p.loss = LOSS_IN_CHAIN; p.loss_finish = LOSS_FINISH_CARRIED;
@@ -811,22 +817,33 @@ int run_norm_fwd(codae_engine* e, const codae_buffers* b, int l, int B, bool tra
                            reinterpret_cast<float*>(ws + e->norm_r_off[l]), bits, (e->out[l] + 7) / 8, s);
 }
 
+inline bool sparse_layer(const codae_engine* e, int l) { return e->tc.sparse.on && l >= 0 && l + 1 < e->L && l == e->tc.sparse.m; }
+
+// act[m + 1] <- its `keep` first-ranked units per row, +0 elsewhere, in place behind the forward GEMM of the layer m that produces
+// the code (behind its dropout kernel; layer m has neither skip nor norm); training: the 1-bit keep mask goes to the setting's work space
+int run_sparse_fwd(codae_engine* e, const codae_buffers* b, int l, int B, bool training, hipStream_t s) {
+    ProfScope prof(e, CODAE_K_DROPOUT, s);
+    return launch_sparse_code_fwd(act_ptr(e, b, l + 1), e->prec == CODAE_PREC_BF16, e->in_ld[l + 1], B, e->out[l], e->tc.sparse.keep,
+                                  training ? reinterpret_cast<uint8_t*>(e->tc.sparse.ws) : nullptr, (e->out[l] + 7) / 8, s);
+}
+
 // What a forward leaves for the backward entry points, which take no batch: a training forward (hyper not null) of a stack with
-// dropout, skips or a norm says that the activations were dropped - with the batch rows, row indices and step of that forward - and
-// that the skips' and the norm's 1-bit masks were written; every other forward (evaluation, drop-in, scoring: batch and hyper null)
-// clears the three flags.
+// dropout, skips, a norm or a sparse code says that the activations were dropped - with the batch rows, row indices and step of that
+// forward - and that the skips', the norm's and the sparse code's 1-bit masks were written; every other forward (evaluation, drop-in,
+// scoring: batch and hyper null) clears the four flags.
 void forward_leaves(codae_engine* e, const codae_batch* batch, const codae_hyper* hyper) {
     e->drop_live = hyper != nullptr && e->tc.drop.on;
     if (e->drop_live) { e->drop_B = batch->B; e->drop_rows = batch->row_idx; e->drop_step = hyper->step; }
     e->res_bits_live = hyper != nullptr && e->tc.res.any;
     e->norm_bits_live = hyper != nullptr && e->tc.norm.any;
+    e->sparse_bits_live = hyper != nullptr && e->tc.sparse.on;
 }
 
-// The drop-in entry points' refusal of what skips or a norm do not allow them: "<who>: residual connections are on: <what>", or
-// "<who>: a norm is on: <what>"
+// The drop-in entry points' refusal of what skips, a norm or a sparse code do not allow them: "<who>: residual connections are on:
+// <what>", "<who>: a norm is on: <what>", or "<who>: a sparse code is on: <what>"
 int refuse_skips_or_norm(const codae_engine* e, const char* who, const char* what) {
-    if (!e->tc.res.any && !e->tc.norm.any) return CODAE_OK;
-    set_error("%s: %s on: %s", who, e->tc.res.any ? "residual connections are" : "a norm is", what);
+    if (!e->tc.res.any && !e->tc.norm.any && !e->tc.sparse.on) return CODAE_OK;
+    set_error("%s: %s on: %s", who, e->tc.res.any ? "residual connections are" : (e->tc.norm.any ? "a norm is" : "a sparse code is"), what);
     return CODAE_E_UNSUPPORTED;
 }
 
@@ -848,7 +865,11 @@ int run_forward_layer(codae_engine* e, const codae_buffers* b, int l, float* y_f
         rc = run_residual_fwd(e, b, l, B, training, s);
         if (rc) return rc;
     }
-    return norms_layer(e, l) ? run_norm_fwd(e, b, l, B, training, s) : CODAE_OK;
+    if (norms_layer(e, l)) {
+        rc = run_norm_fwd(e, b, l, B, training, s);
+        if (rc) return rc;
+    }
+    return sparse_layer(e, l) ? run_sparse_fwd(e, b, l, B, training, s) : CODAE_OK;
 }
 
 // the data gradient of layer l and, when layer l - 1 was dropped in the forward, dA_{l-1} <- dA_{l-1} * f right behind it on the same
@@ -905,6 +926,20 @@ int run_dgrad(codae_engine* e, const codae_buffers* b, int l, int rows, bool cos
         }
         if (rc) return rc;
         e->parts_pending[m] = row_sweep_blocks(e->res_B);
+    }
+    if (sparse_layer(e, l - 1)) {
+        // dA_m <- kept ? dA_m : +0 behind the GEMM (and behind the residual kernel of a skip around layer l: layer m itself has
+        // neither skip nor norm, so that kernel's only outputs here are dA_m and its column sums, and the selection commutes with
+        // the element-wise derivative), in front of dropout's kernel; the partial column sums are rewritten from the final values
+        CODAE_REQUIRE(e->sparse_bits_live, "backward through the sparse code of layer %d without a training forward before it", l - 1);
+        {
+            ProfScope prof(e, CODAE_K_DROPOUT, s);
+            rc = launch_sparse_code_bwd(dact_ptr(e, b, l - 1), e->prec == CODAE_PREC_BF16, e->prec == CODAE_PREC_BF16 ? e->out_ld[l - 1] : e->out[l - 1],
+                                        e->res_B, e->out[l - 1], reinterpret_cast<const uint8_t*>(e->tc.sparse.ws), (e->out[l - 1] + 7) / 8,
+                                        part_ptr(e, b, l - 1), s);
+        }
+        if (rc) return rc;
+        e->parts_pending[l - 1] = row_sweep_blocks(e->res_B);
     }
     if (!drops_layer(e, l - 1)) return CODAE_OK;
     {
@@ -1087,7 +1122,16 @@ int stream_layout(codae_handle h, const char* who, int n, const uint8_t* flags, 
     return CODAE_OK;
 }
 
-// both setters' check of the work space the caller brought
+// codae_set_residual's and codae_set_norm's refusal of the layer a sparse code is on (codae_set_sparse_code refuses the other order)
+int refuse_on_sparse_layer(codae_handle h, const char* who, const uint8_t* on, const char* noun) {
+    if (!h->tc.sparse.on || !on[h->tc.sparse.m]) return CODAE_OK;
+    const int m = h->tc.sparse.m;
+    set_error("%s: layer %d (%d -> %d): a sparse code is on this layer and it takes no %s: name the layers and leave out layer %d", who, m, h->in[m],
+              h->out[m], noun, m);
+    return CODAE_E_UNSUPPORTED;
+}
+
+// the setters' check of the work space the caller brought
 int check_stream_ws(const char* who, const void* ws, int64_t ws_bytes, int64_t need) {
     CODAE_REQUIRE(ws != nullptr && (reinterpret_cast<uintptr_t>(ws) & 15) == 0 && ws_bytes >= need,
                   "%s: the work space must be 16-byte aligned and hold %lld bytes (got %lld)", who, (long long)need, (long long)ws_bytes);
@@ -1527,7 +1571,7 @@ static int forward_loss_impl(codae_handle h, const codae_buffers* b, const codae
     if (rc) return rc;
     float* y = out_y ? out_y : reinterpret_cast<float*>(act_ptr(h, b, L));
     GroupScope fwd_group(h, CODAE_K_GEMM_FWD, s);       // the plain forward launches of this step, back to back
-    if (h->drop_live || h->tc.res.any || h->tc.norm.any) fwd_group.close();   // (streaming kernels sit between them: every launch gets its own event pair)
+    if (h->drop_live || h->tc.res.any || h->tc.norm.any || h->tc.sparse.on) fwd_group.close();   // (streaming kernels sit between them: every launch gets its own event pair)
     for (int l = 0; l < L; ++l) {
         const bool last = (l == L - 1);
         if (last && fuse_loss) {
@@ -1804,6 +1848,8 @@ int codae_set_residual(codae_handle h, const codae_residual* r, void* ws, int64_
         if (rc) return rc;
         c.ws = ws; c.ws_bytes = ws_bytes; c.any = 1;
     }
+    rc = refuse_on_sparse_layer(h, "codae_set_residual", c.on, "skip");
+    if (rc) return rc;
     h->tc.res = c;
     h->res_bits_off = bits_off;
     h->res_bits_live = false;
@@ -1851,10 +1897,62 @@ int codae_set_norm(codae_handle h, const codae_norm* n, void* ws, int64_t ws_byt
         if (rc) return rc;
         c.ws = ws; c.ws_bytes = ws_bytes; c.any = 1; c.kind = n->kind; c.eps = n->eps;
     }
+    rc = refuse_on_sparse_layer(h, "codae_set_norm", c.on, "norm");
+    if (rc) return rc;
     h->tc.norm = c;
     h->norm_r_off = r_off;
     h->norm_bits_off = bits_off;
     h->norm_bits_live = false;
+    return CODAE_OK;
+}
+
+// The canonical form of a codae_sparse_code on this stack (all zero = off: NULL, or keep == the width of the code) and the bytes of
+// its work space, the 1-bit keep mask.  CODAE_E_INVALID / CODAE_E_UNSUPPORTED as codae_set_sparse_code documents.
+static int sparse_layout(codae_handle h, const codae_sparse_code* c, const char* who, codae_engine::SparseCfg* out, int64_t* bytes) {
+    *out = codae_engine::SparseCfg{};
+    *bytes = 0;
+    if (c == nullptr) return CODAE_OK;
+    CODAE_REQUIRE(c->layer >= 1 && c->layer <= h->L, "%s: layer %d outside [1, %d]", who, c->layer, h->L - 1);
+    const int m = c->layer - 1;
+    char why[160] = "";
+    if (m == h->L - 1) snprintf(why, sizeof(why), "the last layer's output is the reconstruction and takes no sparse code");
+    else if (h->act[m] != CODAE_ACT_NONE && h->act[m] != CODAE_ACT_LEAKY)
+        snprintf(why, sizeof(why), "the sparse layer's activation must be none, ReLU or LeakyReLU");
+    else if (h->tc.res.any && h->tc.res.on[m])
+        snprintf(why, sizeof(why), "the sparse layer takes no skip (it would add the dense h_%d back): name the layers and leave out layer %d", m, m);
+    else if (h->tc.norm.any && h->tc.norm.on[m])
+        snprintf(why, sizeof(why), "the sparse layer takes no norm (its backward needs the full xhat): name the layers and leave out layer %d", m);
+    if (why[0] != 0) {
+        set_error("%s: layer %d (%d -> %d, activation kind %d): %s", who, m, h->in[m], h->out[m], h->relu[m] ? CODAE_ACT_RELU : (int)h->act[m], why);
+        return CODAE_E_UNSUPPORTED;
+    }
+    CODAE_REQUIRE(c->keep >= 1 && c->keep <= h->out[m], "%s: keep %d outside [1, %d], the width of layer %d's output", who, c->keep, h->out[m], m);
+    if (c->keep == h->out[m]) return CODAE_OK;                 // every unit kept: off
+    out->on = 1; out->m = m; out->keep = c->keep;
+    *bytes = round_up((int64_t)h->max_batch * ((h->out[m] + 7) / 8), 256);
+    return CODAE_OK;
+}
+
+int64_t codae_sparse_code_ws_bytes(codae_handle h, const codae_sparse_code* c) {
+    if (h == nullptr) { set_error("codae_sparse_code_ws_bytes: null handle"); return -1; }
+    codae_engine::SparseCfg cfg;
+    int64_t bytes = 0;
+    return sparse_layout(h, c, "codae_sparse_code_ws_bytes", &cfg, &bytes) == CODAE_OK ? bytes : -1;
+}
+
+int codae_set_sparse_code(codae_handle h, const codae_sparse_code* c, void* ws, int64_t ws_bytes) {
+    CODAE_REQUIRE(h != nullptr, "codae_set_sparse_code: null handle");
+    codae_engine::SparseCfg cfg;         // (built field by field from zero: the graph key compares bytes)
+    int64_t need = 0;
+    int rc = sparse_layout(h, c, "codae_set_sparse_code", &cfg, &need);
+    if (rc) return rc;
+    if (need > 0) {
+        rc = check_stream_ws("codae_set_sparse_code", ws, ws_bytes, need);
+        if (rc) return rc;
+        cfg.ws = ws; cfg.ws_bytes = ws_bytes;
+    }
+    h->tc.sparse = cfg;
+    h->sparse_bits_live = false;
     return CODAE_OK;
 }
 

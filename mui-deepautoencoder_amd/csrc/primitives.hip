@@ -212,6 +212,18 @@ int codae_norm_bwd(void* d, int32_t bf16, int64_t ld, int32_t B, int32_t width, 
 
 int codae_norm_blocks(int32_t B) { return B > 0 ? row_sweep_blocks(B) : 0; }
 
+int codae_sparse_code_fwd(void* y, int32_t bf16, int64_t ld, int32_t B, int32_t width, int32_t keep, uint8_t* bits, int64_t ld_bits,
+                          void* stream) {
+    return launch_sparse_code_fwd(y, bf16, ld, B, width, keep, bits, ld_bits, (hipStream_t)stream);
+}
+
+int codae_sparse_code_bwd(void* d, int32_t bf16, int64_t ld, int32_t B, int32_t width, const uint8_t* bits, int64_t ld_bits,
+                          float* colsum_part, void* stream) {
+    return launch_sparse_code_bwd(d, bf16, ld, B, width, bits, ld_bits, colsum_part, (hipStream_t)stream);
+}
+
+int codae_sparse_code_blocks(int32_t B) { return B > 0 ? row_sweep_blocks(B) : 0; }
+
 int codae_export_rows(const void* src, int32_t bf16, int64_t ld_src, int32_t B, int32_t width, float* dst, int64_t ld_dst, float* norm,
                       void* stream) {
     return launch_export_rows(src, bf16, ld_src, B, width, dst, ld_dst, norm, (hipStream_t)stream);

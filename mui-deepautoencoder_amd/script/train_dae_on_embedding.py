@@ -174,6 +174,10 @@ def main():
     # layers' outputs per batch row, in training and in validation alike (it is part of the model)
     from codae.tool.norm import norm_from_config
     norm = norm_from_config(config.get("HIP", {}).get("NORM"))
+    # HIP: SPARSE_CODE: {KEEP: 32, LAYER: null} (build-only key): the hard top-k code layer - the KEEP largest-magnitude units of the
+    # code per row, in training and in validation alike (it is part of the model); LAYER null = the stack's code layer
+    from codae.tool.sparse import sparse_from_config
+    sparse_code = sparse_from_config(config.get("HIP", {}).get("SPARSE_CODE"))
     # HIP: CRITERION: {KIND: mse | l1 | smooth_l1 | huber | slot_cosine, BETA: .., DELTA: .., MSE_WEIGHT: ..} (build-only key): the
     # training loss instead of the mean squared error (the monitors stay squared-error sums; validation never sees it)
     from codae.tool.recon_loss import recon_loss_from_config
@@ -207,7 +211,8 @@ def main():
                                    max_batch=mc["BATCH_SIZE"], precision=prec, device=device, distributed=world > 1,
                                    activation=activation, input_noise=input_noise, loss_emphasis=loss_emphasis,
                                    hidden_dropout=hidden_dropout, criterion=criterion, contrast=contrast, optimizer=optimizer,
-                                   presence=presence, tied_weights=tied_weights, weight_average=weight_average, residual=residual, norm=norm)
+                                   presence=presence, tied_weights=tied_weights, weight_average=weight_average, residual=residual, norm=norm,
+                                   sparse_code=sparse_code)
     try:
         trainer = build(precision)
     except HipError as e:
@@ -227,6 +232,8 @@ def main():
         log.info("RESIDUAL: %r - identity skips around layers %s" % (residual, trainer.engine.residual_layers))
     if trainer.engine.norm_layers:
         log.info("NORM: %r - %s normalisation of the outputs of layers %s" % (norm, norm.kind, trainer.engine.norm_layers))
+    if trainer.engine.sparse_resolved is not None:
+        log.info("SPARSE CODE: keep %d of %d at layer %d" % (sparse_code.keep, trainer.engine.sparse_resolved[1], trainer.engine.sparse_resolved[0] + 1))
     if eval_weights == "average":
         log.info("WEIGHT AVERAGE: %r - the validation errors and the ranking error are those of the averaged weights" % (weight_average,))
     book = {k: [] for k in ("ftl", "ptl", "fvl", "pvl", "rl")}
