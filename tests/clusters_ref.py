@@ -100,3 +100,77 @@ def planted(Z, K, M, seed=0, bf16=False):
     x = op(x.astype(np.float32), bf16)
     norm = np.sqrt((x.astype(np.float64) ** 2).sum(axis=1)).astype(np.float32)
     return x, norm, c_true.astype(np.float32), labels
+
+
+# ---- the update across sort chunks: assignment patterns and an exact design -----------------------------------------------------------
+
+PATTERNS = ("round_robin", "blocked", "one", "singles", "nobody")
+
+
+def nobody_values(K):
+    """assign values that mean "nobody": -1 and everything else outside [0, K), 64-bit ones included"""
+    return np.array([-1, -2, K, K + 5, 2 ** 40, -2 ** 40], dtype=np.int64)
+
+
+def assign_pattern(kind, M, K, chunk, seed=0):
+    """an int64 assign [M] laid out against sort chunks of `chunk` rows:
+    round_robin  r % K: every cluster in every chunk (as far as K <= chunk allows)
+    blocked      cluster j lives only in chunk j % n_chunks: some clusters are absent from chunk 0, others from the last
+    one          cluster 1 % K holds every row
+    singles      three single-member clusters at rows chunk - 1, chunk and M - 1 (M > chunk), everybody else nobody
+    nobody       round_robin with 10 % of the rows, rows chunk - 1 and chunk among them, drawn from nobody_values(K)"""
+    r = np.arange(M, dtype=np.int64)
+    n_chunks = (M + chunk - 1) // chunk
+    if kind == "round_robin":
+        return r % K
+    if kind == "blocked":
+        c = r // chunk
+        per = np.maximum((K - c + n_chunks - 1) // n_chunks, 1)              # clusters congruent to c that exist
+        a = c + n_chunks * ((r % chunk) % per)
+        return np.where(a < K, a, -1)                                         # (K < n_chunks: a chunk without a cluster)
+    if kind == "one":
+        return np.full(M, 1 % K, dtype=np.int64)
+    if kind == "singles":
+        a = np.full(M, -1, dtype=np.int64)
+        a[chunk - 1], a[chunk], a[M - 1] = 0, K - 1, K // 2
+        return a
+    if kind == "nobody":
+        rng = np.random.default_rng(seed)
+        a = r % K
+        out = rng.random(M) < 0.1
+        out[[chunk - 1, chunk]] = True
+        a[out] = rng.choice(nobody_values(K), size=int(out.sum()))
+        return a
+    raise ValueError(kind)
+
+
+def exact_design(Z, M, seed=0):
+    """x [M][Z] of small integers with norm 1 everywhere: column 0 is 1 (a member count), column 1 is r % 97 + 1 (which members), the
+    rest are integers in [-2, 2].  Every member sum is an integer below 2^24: exact in fp32 in any order."""
+    assert Z >= 2 and M * 97 < 2 ** 24
+    x = np.random.default_rng(seed).integers(-2, 3, size=(M, Z)).astype(np.float32)
+    x[:, 0] = 1.0
+    x[:, 1] = np.arange(M) % 97 + 1
+    return x, np.ones(M, dtype=np.float32)
+
+
+def exact_update(x, assign, K):
+    """(sums float64 [K][Z] - exact integers -, counts int64 [K]) of exact_design rows under assign"""
+    live = (assign >= 0) & (assign < K)
+    sums = np.zeros((K, x.shape[1]))
+    np.add.at(sums, assign[live], x[live].astype(np.float64))
+    return sums, np.bincount(assign[live], minlength=K).astype(np.int64)
+
+
+def unit(sums):
+    """sums / |sums| per row in float64 (rows of zeros stay zero)"""
+    n = np.sqrt((sums * sums).sum(axis=1, keepdims=True))
+    return sums / np.where(n > 0, n, 1.0)
+
+
+def finish_bound(Z):
+    """first-order relative error per element of c = s / sqrt(sum s_z^2) formed in fp32 from exact s, in the finish kernel's order: a
+    lane's fma chain over ceil(Z / 64) columns (one rounding each), 6 butterfly additions, one square root, one division.  The sum of
+    squares is a sum of non-negative terms, so its relative error is at most (ceil(Z/64) + 6) u; the root halves that and adds u, the
+    division adds u: (ceil(Z/64) + 6) / 2 + 2 <= ceil(Z/64) + 8 roundings of u = 2^-24."""
+    return ((Z + 63) // 64 + 8) * 2.0 ** -24

@@ -43,6 +43,23 @@ def words(rows, layer, width, step, seed):
     return out
 
 
+def words_vec(rows, layer, width, step, seed):
+    """words() in whole-array uint64 arithmetic, for matrices of millions of elements (the tests compare the two on a few rows)"""
+    m = np.uint64(MASK32)
+    rows = np.asarray(rows).reshape(-1).astype(np.int64).astype(np.uint64) & m
+    B, G = rows.size, (width + 3) // 4
+    c0 = np.repeat(np.arange(G, dtype=np.uint64)[None, :], B, axis=0)
+    c1 = np.repeat(rows[:, None], G, axis=1)
+    c2 = np.full((B, G), int(step) & MASK32, dtype=np.uint64)
+    c3 = np.full((B, G), (1 + int(layer)) & MASK32, dtype=np.uint64)
+    k0, k1 = int(seed) & MASK32, (int(seed) >> 32) & MASK32
+    for _ in range(10):
+        pa, pb = np.uint64(MUL_A) * c0, np.uint64(MUL_B) * c2
+        c0, c1, c2, c3 = (pb >> np.uint64(32)) ^ c1 ^ np.uint64(k0), pb & m, (pa >> np.uint64(32)) ^ c3 ^ np.uint64(k1), pa & m
+        k0, k1 = (k0 + WEYL_A) & MASK32, (k1 + WEYL_B) & MASK32
+    return np.stack([c0, c1, c2, c3], axis=2).reshape(B, 4 * G)[:, :width].astype(np.uint32)
+
+
 def threshold(p):
     return int(math.floor(float(np.float32(p)) * 2.0 ** 32))
 

@@ -169,3 +169,42 @@ def test_the_header_has_the_section_and_keeps_its_abi_and_the_binding_declares_t
     for name in ENTRIES:
         assert name in hip.PROTOTYPES
     assert len(hip.PROTOTYPES["codae_nearest_centroid"][1]) == 13 and len(hip.PROTOTYPES["codae_centroid_update"][1]) == 13
+
+
+def test_the_exact_design_notices_any_one_lost_member_of_any_cluster():
+    """the reference alone, for every case of the chunked-update test on the GPU (tests/test_gpu_clusters.py): take any one member out
+    of any cluster and either its count changes with the cluster gone, or float64 sums / |sums| moves some element by more than the
+    test's bound (twice clusters_ref.finish_bound) - so a sort that loses one row, and with it one that duplicates a row or files it
+    under another cluster, cannot pass.  The patterns are also what they claim to be."""
+    from test_gpu_clusters import CHUNK_CASES, SORT_CHUNK
+    for K, Z, M, kind in CHUNK_CASES:
+        x, _ = CR.exact_design(Z, M, seed=K + Z)
+        assert np.abs(x).max() * M < 2 ** 24                                  # every partial sum is an exact fp32 integer
+        assign = CR.assign_pattern(kind, M, K, SORT_CHUNK, seed=K)
+        sums, counts = CR.exact_update(x, assign, K)
+        want = CR.unit(sums)
+        tol = 2 * CR.finish_bound(Z)
+        worst = np.inf
+        for j in np.flatnonzero(counts > 1):
+            mem = np.flatnonzero(assign == j)
+            less = CR.unit(sums[j][None] - x[mem].astype(np.float64))
+            moved = (np.abs(less - want[j][None]) / (tol * np.abs(want[j][None]) + 1e-300)).max(axis=1)
+            worst = min(worst, moved.min())
+        assert worst > 100, (K, Z, M, kind, worst)                            # far outside the bound, not just outside
+        chunk_of = np.arange(M) // SORT_CHUNK
+        n_chunks = chunk_of[-1] + 1
+        valid = (assign >= 0) & (assign < K)
+        if kind == "round_robin" and K <= SORT_CHUNK and M % SORT_CHUNK == 0:
+            assert all(np.unique(assign[chunk_of == c]).size == K for c in range(n_chunks))
+        if kind == "blocked":
+            assert (assign[valid] % n_chunks == chunk_of[valid]).all() and n_chunks == 3
+            if K >= n_chunks:
+                assert valid.all() and (counts > 0).all()
+        if kind == "one":
+            assert counts.max() == M and (counts > 0).sum() == 1
+        if kind == "singles":
+            assert counts.sum() == 3 and counts.max() == 1 and (assign[[SORT_CHUNK - 1, SORT_CHUNK, M - 1]] >= 0).all()
+        if kind == "nobody":
+            out = assign[~valid]
+            assert not valid[SORT_CHUNK - 1] and not valid[SORT_CHUNK] and 0.05 * M < out.size < 0.15 * M
+            assert set(out.tolist()) == set(CR.nobody_values(K).tolist())

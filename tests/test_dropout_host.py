@@ -124,3 +124,9 @@ def test_header_constants_agree_with_the_binding():
     lib = hip.lib()
     assert lib.codae_abi_version() == 11
     assert [lib.codae_dropout_blocks(b) for b in (0, 1, 64, 65, 70, 8192)] == [0, 1, 1, 2, 2, 128]
+
+
+def test_the_whole_array_philox_of_the_reference_is_its_plain_one():
+    rows = np.array([0, 1, 5, 299, 2999, 2 ** 31 - 1], dtype=np.int32)
+    for layer, width, step, seed in ((0, 1, 0, 0), (1, 21, 5, 0x0123456789ABCDEF), (254, 40, 2 ** 31 - 1, 2 ** 64 - 1)):
+        assert np.array_equal(DR.words_vec(rows, layer, width, step, seed), DR.words(rows, layer, width, step, seed))

@@ -4,13 +4,15 @@ the float64 restatement (tests/clusters_ref.py), CodeClusters.fit on the device,
 Shapes.  Z in {8, 40, 72, 100, 264}: whole and partial MFMA k-chunks (bf16: 32 columns, f32: 16); K in {1, 5, 16, 19, 300}: one
 centroid, partial tiles, an exact tile, three groups of the kernel's 128 centroids; M in {1, 37, 70, 700}: a partial row tile, more
 than one wave, more than one block (128 rows).  Dense operands take the 16-byte path, ld_x = Z + 3 / ld_c = Z + 1 the element path;
-pad columns, two pad rows and the centroid rows past K hold NaN.
+pad columns, two pad rows and the centroid rows past K hold NaN.  At the group edges: K 128 (the last centroid of a whole group), 129 (a
+group of one tile) and 4096 (the most the entries take; Z 8 and 40 only).  The update also runs across its 1024-row sort chunks: M in
+{1024, 1025, 2500} and K up to 4096 under five assignment patterns (clusters_ref.assign_pattern), see CHUNK_CASES.
 
 Tolerances.  Exact tests: integers in [-2, 2] are exact in bf16 and in every fp32 partial sum (|d| <= 4 * 264), so assign and best
 equal the integer reference.  Planted clusters: delta = 2 Z 2^-24, the fp32 accumulation bound for unit vectors (sum |a_z b_z| <= 1);
 the reference alone first shows that no row's top-two gap is within delta, then assign must be equal for every row and best within
 delta plus the project's rtol 1e-3 / atol 1e-5.  Update: per element count_j 2^-24 sum|terms| / |sum_j| (clusters_ref.update) plus
-atol 1e-6."""
+atol 1e-6.  Update of the exact integer design: twice clusters_ref.finish_bound, derived at the test."""
 import numpy as np
 import pytest
 
@@ -20,10 +22,22 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 DEV = "cuda:0"
 ZS = (8, 40, 72, 100, 264)
-KM = ((1, 1), (5, 37), (16, 70), (19, 700), (300, 70), (300, 700))
+KM = ((1, 1), (5, 37), (16, 70), (19, 700), (300, 70), (300, 700), (128, 70), (129, 70), (4096, 37))
+MAX_K = 4096                        # the most centroids the entries take: checked at Z 8 and 40 only (the reference is [M][K])
+ZKM = tuple((Z, K, M) for Z in ZS for K, M in KM if K < MAX_K or Z in (8, 40))
 FORMS = (False, True)
 FORM_IDS = ("f32", "bf16")
 GROUP = 128                         # centroids per accumulator group of the kernel
+SORT_CHUNK = 1024                   # rows per chunk of the update's counting sort
+SCAN_CLUSTERS = 4                   # clusters per thread of its scan over the chunks
+# the update across sort chunks: a whole chunk, one row more, two chunks and a ragged third; Z 72 is two column blocks of the member
+# sum; K 1100 and MAX_K put clusters on the scan's threads 75 .. 1023
+CHUNK_MS = (1024, 1025, 2500)
+CHUNK_KZ = ((5, 8), (19, 40), (19, 72), (1100, 8))
+CHUNK_CASES = tuple([(K, Z, M, "round_robin") for M in CHUNK_MS for K, Z in CHUNK_KZ] +
+                    [(K, Z, CHUNK_MS[-1], kind) for kind in CR.PATTERNS[1:] for K, Z in CHUNK_KZ] + [(MAX_K, 8, 5000, "round_robin")])
+CHUNK_IDS = ["k%d-z%d-m%d-%s" % c for c in CHUNK_CASES]
+FIT_CHUNKED = (40, 19, 2500)
 
 
 def _padded(a, ld, pad_rows=2):
@@ -60,9 +74,10 @@ def _bits(a):
 # ---- exact: small integers ------------------------------------------------------------------------------------------------------------
 
 def _integers(Z, K, M, seed):
-    """integer operands with planted exact ties: a duplicate of centroid 0 at K - 1, a +0 / -0 pair at 2 / 3, and (K > 256) copies of
-    centroid 127 at 128 and 256, across the group boundaries; centroids 0 and 127 have no zero entry, so a row equal to one of them has
-    its maximum exactly there and at the copies"""
+    """integer operands with planted exact ties: a duplicate of centroid 0 at K - 1 (K 128: the last centroid of a whole group, K 129:
+    alone in a group of one tile), a +0 / -0 pair at 2 / 3, (K > 256) copies of centroid 127 at 128 and 256, across the group
+    boundaries, and (K = MAX_K) one more at the first index of the last group; centroids 0 and 127 have no zero entry, so a row equal
+    to one of them has its maximum exactly there and at the copies"""
     rng = np.random.default_rng(seed)
     x = rng.integers(-2, 3, size=(M, Z)).astype(np.float32)
     c = rng.integers(-2, 3, size=(K, Z)).astype(np.float32)
@@ -79,14 +94,15 @@ def _integers(Z, K, M, seed):
         c[GROUP - 1] = rng.choice([-2.0, 2.0], size=Z)
         c[GROUP - 1, 0] = -c[0, 0]                                            # (not centroid 0 again)
         c[GROUP], c[2 * GROUP] = c[GROUP - 1], c[GROUP - 1]
+        if K == MAX_K:
+            c[K - GROUP] = c[GROUP - 1]
         x[M // 3] = c[GROUP - 1]
         planted.append((M // 3, GROUP - 1))
     return x, c, planted
 
 
 @pytest.mark.parametrize("bf16", FORMS, ids=FORM_IDS)
-@pytest.mark.parametrize("K,M", KM, ids=["k%d-m%d" % km for km in KM])
-@pytest.mark.parametrize("Z", ZS)
+@pytest.mark.parametrize("Z,K,M", ZKM, ids=["%d-k%d-m%d" % s for s in ZKM])
 def test_integer_operands_give_the_exact_assignment_and_score(Z, K, M, bf16):
     x, c, planted = _integers(Z, K, M, seed=Z * 1000 + K + M)
     ra, rb, d = CR.nearest(x, c, None, bf16)
@@ -276,6 +292,85 @@ def test_update_of_one_member_and_of_one_cluster_that_holds_every_row():
     assert np.array_equal(_bits(g2), _bits(got))
 
 
+# ---- the update across sort chunks ------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("K,Z,M,kind", CHUNK_CASES, ids=CHUNK_IDS)
+def test_chunked_update_of_an_exact_design_counts_exactly_and_normalises_within_the_finish_bound(K, Z, M, kind):
+    """x is clusters_ref.exact_design: integers with norm 1, so every member sum is exact in fp32 whatever the order, and what is left
+    between c_out and float64 sums / |sums| is the finish kernel alone: per lane an fma chain over ceil(Z / 64) squares, 6 butterfly
+    additions (all terms non-negative: relative error <= (ceil(Z/64) + 6) u, u = 2^-24), a square root (halves it, adds u) and one
+    division (adds u): to first order (ceil(Z/64) + 6) / 2 + 2 <= ceil(Z/64) + 8 roundings per element (clusters_ref.finish_bound).
+    Asserted at twice that.  Column 0 counts the members and column 1 tells them apart, so a lost, duplicated or foreign member
+    moves an element by >= 1 / (2 count) relative: tests/test_clusters_host.py shows it for every member of every design."""
+    x, norm = CR.exact_design(Z, M, seed=K + Z)
+    assign = CR.assign_pattern(kind, M, K, SORT_CHUNK, seed=K)
+    sums, counts = CR.exact_update(x, assign, K)
+    want = CR.unit(sums)
+    c_in = np.random.default_rng(1).standard_normal((K, Z)).astype(np.float32)
+    got, gc = _update(x, norm, assign, c_in)
+    assert np.array_equal(gc, counts)
+    live = counts > 0
+    assert np.array_equal(_bits(got[~live]), _bits(c_in[~live]))
+    bound = CR.finish_bound(Z)
+    ratio = np.abs(got[live] - want[live]) / (bound * np.abs(want[live]) + 1e-300)
+    ratio[(want[live] == 0) & (got[live] == 0)] = 0.0
+    print("MEASURE chunked update exact k%d z%d m%d %s: worst error / bound %.3f" % (K, Z, M, kind, ratio.max() if live.any() else 0.0))
+    assert (ratio <= 2.0).all()
+
+
+def _member_list_bits(x, norm, assign, c_in, clusters):
+    """row j of c_out from a call that holds only the members of j, in their order: a single-chunk call, for each j in clusters"""
+    from codae import hip
+    lib = hip.lib()
+    M, Z = x.shape
+    K = c_in.shape[0]
+    xd, nd, cb = torch.tensor(x, device=DEV), torch.tensor(norm, device=DEV), torch.tensor(c_in, device=DEV)
+    out = torch.full((K + 1, Z), 7.0, device=DEV)
+    counts = torch.full((K + 1,), -7, dtype=torch.long, device=DEV)
+    res = torch.zeros((len(clusters), Z), device=DEV)
+    ws = torch.empty(int(lib.codae_centroid_update_ws_bytes(SORT_CHUNK, Z, K)), dtype=torch.uint8, device=DEV)
+    for i, j in enumerate(clusters):
+        mem = torch.tensor(np.flatnonzero(assign == j), device=DEV)
+        n = int(mem.numel())
+        assert 1 <= n <= SORT_CHUNK
+        xs, ns = xd[mem].contiguous(), nd[mem].contiguous()
+        ab = torch.full((n,), int(j), dtype=torch.long, device=DEV)
+        hip.check(lib.codae_centroid_update(hip.ptr(xs), Z, n, Z, hip.ptr(ns), hip.ptr(ab), hip.ptr(cb), hip.ptr(out), Z, K, hip.ptr(counts),
+                                            hip.ptr(ws), hip.current_stream()))
+        res[i] = out[j]
+    torch.cuda.synchronize()
+    assert counts[K] == -7 and (out[K] == 7.0).all()
+    return res.cpu().numpy()
+
+
+@pytest.mark.parametrize("K,Z,M,kind", CHUNK_CASES, ids=CHUNK_IDS)
+def test_chunked_update_of_planted_rows_has_the_bits_of_each_member_list_alone(K, Z, M, kind):
+    """non-integer rows with their own norms.  "Every fp32 sum runs in an order fixed by the member list alone": a live cluster of at
+    most SORT_CHUNK members has the bits of a call that holds only its members (one chunk: the path the small tests cover); a larger
+    one is held to clusters_ref.update's float64 bound.  Cluster 3 is emptied and keeps c_in's bits, a NaN payload included; the
+    padded (ld_x = Z + 3, ld_c = Z + 1) and the in-place forms give the bits of the dense out-of-place one."""
+    x, norm, c_true, _ = CR.planted(Z, K, M, seed=Z + K + M)
+    assign = CR.assign_pattern(kind, M, K, SORT_CHUNK, seed=K)
+    assign[assign == 3] = -1
+    c_in = c_true.copy()
+    c_in[3, 1] = np.array([0x7FC12345], dtype=np.uint32).view(np.float32)[0]
+    want, counts, bound = CR.update(x, norm, assign, c_in)
+    assert counts[3] == 0
+    got, gc = _update(x, norm, assign, c_in)
+    assert np.array_equal(gc, counts)
+    live = np.flatnonzero(counts > 0)
+    assert np.array_equal(_bits(got[counts == 0]), _bits(c_in[counts == 0]))
+    small = [j for j in live if counts[j] <= SORT_CHUNK]
+    alone = _member_list_bits(x, norm, assign, c_in, small)
+    differ = [j for i, j in enumerate(small) if not np.array_equal(_bits(alone[i]), _bits(got[j]))]
+    assert not differ, (len(differ), differ[:8])
+    err = np.abs(got[live] - want[live])
+    assert (err <= bound[live] + 1e-6).all()
+    for kw in (dict(padded=True), dict(alias=True), dict(padded=True, alias=True)):
+        g2, c2 = _update(x, norm, assign, c_in, **kw)
+        assert np.array_equal(_bits(g2), _bits(got)) and np.array_equal(c2, counts), kw
+
+
 def test_the_entries_refuse_bad_arguments_before_any_launch():
     from codae import hip
     lib = hip.lib()
@@ -318,7 +413,7 @@ def _perturbed(c_true, seed):
 
 
 @pytest.mark.parametrize("bf16", FORMS, ids=FORM_IDS)
-@pytest.mark.parametrize("Z,K,M", ((40, 5, 70), (100, 300, 700)), ids=("z40-k5-m70", "z100-k300-m700"))
+@pytest.mark.parametrize("Z,K,M", ((40, 5, 70), (100, 300, 700), FIT_CHUNKED), ids=("z40-k5-m70", "z100-k300-m700", "z40-k19-m2500"))
 def test_fit_recovers_the_planted_labels_and_stays_at_its_fixed_point(Z, K, M, bf16):
     from codae.tool import CodeClusters
     p = _planted(Z, K, M, bf16)

@@ -10,7 +10,9 @@ B in {1, 5, 257} (one thread group, a ragged one, more than one block's worth of
 4-, 6- and 12-column slots: an 8-wide group spans two slots at io 8, 4- and 8-wide groups straddle slot borders at io 24 and 72.
 
 Everything is torch.equal on the raw bits, Gaussian included: run against the library of the commit before the kernels were
-unified, this file passed as it stands - noise_apply1 and noise_apply4 round alike there too, so no kind needs a tolerance."""
+unified, this file passed as it stands - noise_apply1 and noise_apply4 round alike there too, so no kind needs a tolerance.
+
+The last test runs one batch past the first trip of the capped grid (B 2800, io 1536) against tests/noise_ref.py."""
 import ctypes as C
 
 import numpy as np
@@ -118,3 +120,53 @@ def test_every_width_gives_the_same_bits(kind, kw, pres):
             if pres:
                 pm = d["present"][d["rows"][:B].long()].repeat_interleave(io // SLOTS[io], dim=1) != 0
                 assert (_bits(x8[:, :io])[~pm] == 0).all() and (_bits(x4[:, :io])[~pm] == 0).all(), where
+
+
+# ---- past the first trip of the capped grid ---------------------------------------------------------------------------------------------
+BIG_B, BIG_IO, BIG_SLOTS = 2800, 1536, 6      # 2800 x 192 8-wide groups (bf16 out) and 2800 x 384 4-wide ones (fp32) against 2048 x 256 a trip
+_BIG = {}
+
+
+def big_groups(bf16):
+    """work items of the aligned launch: 8-column groups for a bf16 output, 4-column groups for an fp32 one"""
+    return BIG_B * (BIG_IO // (8 if bf16 else 4))
+
+
+def _big_problem():
+    """the file's N dataset rows at io 1536 in 6 slots; 2800 batch rows drawn from them (every row about nine times), one mask each"""
+    if not _BIG:
+        E = BIG_IO // BIG_SLOTS
+        rng = np.random.default_rng(4000 + BIG_IO)
+        data = rng.standard_normal((N, BIG_IO)).astype(np.float32)
+        data[rng.random((N, BIG_IO)) < 0.05] = 0.0
+        table = np.ones((BIG_SLOTS, BIG_IO), dtype=np.uint8)
+        for m in range(BIG_SLOTS):
+            table[m, m * E:(m + 1) * E] = 0
+        rows = rng.integers(0, N, BIG_B).astype(np.int32)
+        mask_id = rng.integers(0, BIG_SLOTS, BIG_B).astype(np.int32)
+        _BIG.update(np=dict(data=data, table=table, rows=rows, mask_id=mask_id), data=torch.tensor(data, device=DEV),
+                    table=torch.tensor(table, device=DEV), rows=torch.tensor(rows, device=DEV), mask_id=torch.tensor(mask_id, device=DEV))
+    return _BIG
+
+
+@pytest.mark.parametrize("bf16", [True, False], ids=["bf16", "f32"])
+@pytest.mark.parametrize("kind,kw", KINDS, ids=[k for k, _ in KINDS])
+def test_a_batch_past_the_first_grid_trip_matches_the_definition(kind, kw, bf16):
+    """B 2800 x io 1536: the 8-wide launch makes one trip and 2.5 % of a second, the 4-wide one two trips and 5 % of a third.
+    Every kind is checked over the WHOLE matrix against tests/noise_ref.py (its Philox is whole-array numpy: under half a second
+    a kind at this size, so no kind runs on a row subset) at the tolerances of tests/test_gpu_noise.py - bit for bit, Gaussian
+    within its derived bound; `none` is the plain masked gather, bit for bit.  The pad columns keep their poison."""
+    from codae.tool import InputNoise
+    from test_gpu_noise import _check_against_reference
+    d = _big_problem()
+    h = d["np"]
+    noise = None if kw is None else InputNoise(kind, seed=SEED, **kw).as_struct()
+    got = _gather(d, BIG_IO, BIG_B, noise, False, bf16)
+    torch.cuda.synchronize()
+    assert (got[:, BIG_IO:].float() == POISON).all()
+    x, keep = h["data"][h["rows"]], h["table"][h["mask_id"]]
+    if kw is None:
+        want = torch.tensor(np.where(keep != 0, x, np.float32(0))).to(got.dtype)                 # (a blanked element is +0, not x * 0)
+        assert torch.equal(_bits(got[:, :BIG_IO]).cpu(), _bits(want))
+    else:
+        _check_against_reference(got[:, :BIG_IO], x, h["rows"], keep, STEP, kind, kw, bf16, seed=SEED)

@@ -28,10 +28,12 @@ EPS = 1e-5
 ROWS = (1, 63, 64, 65, 130)
 KINDS = {"layer": 1, "rms": 2}
 # the residual tests' grid: (bf16, width, ld) - 16-byte paths of both types, the fp32 element path, a bf16 element path, and one width
-# per type past one backward column tile (512 columns)
+# per type past one backward column tile (512 columns); fp32 widths = 4 (mod 8) on the 16-byte path, whose last lane holds half a
+# chunk (one quad, four live mask bits): in the first tile, with a wider ld, and in the first lane of the second 512-column tile
 SHAPES = [(True, 8, 16), (True, 24, 32), (True, 24, 27), (True, 520, 528), (False, 8, 12), (False, 24, 28), (False, 21, 23), (False, 11, 13),
-          (False, 264, 268)]
-SHAPE_IDS = ["bf16-w8", "bf16-w24", "bf16-w24-elem", "bf16-w520", "f32-w8", "f32-w24", "f32-w21-elem", "f32-w11-elem", "f32-w264"]
+          (False, 264, 268), (False, 12, 12), (False, 20, 24), (False, 516, 516)]
+SHAPE_IDS = ["bf16-w8", "bf16-w24", "bf16-w24-elem", "bf16-w520", "f32-w8", "f32-w24", "f32-w21-elem", "f32-w11-elem", "f32-w264", "f32-w12",
+             "f32-w20", "f32-w516"]
 
 
 def _work(a, bf16):

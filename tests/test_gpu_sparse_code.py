@@ -26,13 +26,18 @@ DEV = "cuda:0"
 POISON = 7.0
 EPS = 1e-5
 ROWS = (1, 5, 70)
+# the last three: fp32 widths = 4 (mod 8) on the 16-byte path, whose last lane holds half a chunk (one quad, four live mask bits)
 SHAPES = [(True, 8, 8), (True, 24, 32), (True, 520, 528), (True, 1536, 1536), (False, 1, 1), (False, 21, 23), (False, 264, 268),
-          (False, 1537, 1540)]
-SHAPE_IDS = ["bf16-w8", "bf16-w24", "bf16-w520", "bf16-w1536", "f32-w1", "f32-w21-elem", "f32-w264", "f32-w1537-elem"]
+          (False, 1537, 1540), (False, 12, 12), (False, 20, 24), (False, 516, 516)]
+SHAPE_IDS = ["bf16-w8", "bf16-w24", "bf16-w520", "bf16-w1536", "f32-w1", "f32-w21-elem", "f32-w264", "f32-w1537-elem", "f32-w12", "f32-w20",
+             "f32-w516"]
+TIES = (6, 7, 8, 9, 510, 511, 512, 513, 514, 515)
+HALF_TIES = (10, 11, 12, 13, 514, 515, 516, 517)
 
 
 def _keeps(width):
-    return sorted({1, min(2, width), max(1, width // 8), max(1, width - 1), width})
+    half = {4} if width % 8 == 4 and width > 4 else set()       # keep 4 with _last_quad_row: exactly the half chunk is kept
+    return sorted({1, min(2, width), max(1, width // 8), max(1, width - 1), width} | half)
 
 
 def _bf16_valued(a):
@@ -55,10 +60,18 @@ def _host_bits(t):
     return t.view(torch.int32).cpu().numpy().view(np.uint32)
 
 
-def _tie_row(width, keep, rng):
-    """ties of magnitude 2 that straddle a lane's 8-column chunk (columns 6 .. 9) and a 64-lane tile (510 .. 515), with so many
-    larger values - in the HIGHEST other columns - that the threshold falls among the ties"""
-    ties = [c for c in (6, 7, 8, 9, 510, 511, 512, 513, 514, 515) if c < width]
+def _last_quad_row(width, rng):
+    """the four largest magnitudes in the last four columns: with keep 4 and a width = 4 (mod 8), the kept set is the half chunk"""
+    r = (rng.random(width).astype(np.float32) * 0.9 + 0.05) * rng.choice([-1.0, 1.0], width).astype(np.float32)
+    r[width - 4:] = np.array([3.0, -2.5, 2.0, -3.5], dtype=np.float32)
+    return r
+
+
+def _tie_row(width, keep, rng, ties=TIES):
+    """ties of magnitude 2 that straddle a lane's 8-column chunk (columns 6 .. 9) and a 64-lane tile (510 .. 515) - HALF_TIES: the
+    two quads of a chunk (10 .. 13) and, at widths 12 and 516, the half chunk a width = 4 (mod 8) ends in (10, 11; 514, 515) -
+    with so many larger values - in the HIGHEST other columns - that the threshold falls among the ties"""
+    ties = [c for c in ties if c < width]
     r = (rng.random(width).astype(np.float32) * 0.9 + 0.05) * rng.choice([-1.0, 1.0], width).astype(np.float32)
     n_big = keep - len(ties) // 2
     others = [c for c in range(width) if c not in ties]
@@ -78,9 +91,12 @@ def _rows(rng, B, width, keep, bf16):
     planted = []
     if width >= 8:
         planted = list(SR.planted_rows(width, keep, rng))
-        t = _tie_row(width, keep, rng)
-        if t is not None:
-            planted.insert(0, t)
+        first = [_tie_row(width, keep, rng), _tie_row(width, keep, rng, HALF_TIES)]
+        if width % 8 == 4:
+            first.reverse()
+            if keep == 4:
+                first.insert(0, _last_quad_row(width, rng))
+        planted = [t for t in first if t is not None] + planted
     for i, r in enumerate(planted[:B]):
         a[i] = r
     return _bf16_valued(a) if bf16 else a
@@ -346,6 +362,20 @@ def test_norms_elsewhere_dropout_on_the_sparse_layer_tied_weights_and_emphasis_f
         factors = [None, None, drop.factor(idx, 2, 24, s + 1, n_layers=5), None]
         w = ER.weights(ER.corrupted(fm, idx, s + 1, None), 3.0, 1.0)
         _check_f32_step(t, ref, p, s, 24, dy_of=SR.mse(p["data"][idx], w), factors=factors)
+
+
+def test_skips_norms_and_dropout_around_a_half_chunk_wide_code_f32_w20_b70():
+    """width 20 = 4 (mod 8): every row-wise kernel of the step - residual, norm, dropout, sparse - ends its rows in half a chunk"""
+    from codae.tool import HiddenDropout
+    p = _square(5, 20, 70, "leaky", S=4, seed=63)
+    drop = HiddenDropout([0.0, 0.0, 0.5, 0.0], seed=77)
+    t = _trainer(p, "f32", residual=_res([1, 3]), norm=_norm("layer", layers=[0, 3]), hidden_dropout=drop, sparse_code=_sparse(5, layer=3))
+    assert t.engine.sparse_resolved == (2, 20) and t.engine.residual_layers == [1, 3] and t.engine.norm_layers == [0, 3]
+    ref = SR.StepRef(p["params"], p["names"], [0, 1, 0, 1, 0], [1, 0, 0, 1, 0], "layer", EPS, 1e-3, 1e-4, 2, 5)
+    for s in range(2):
+        idx = p["order"][s]
+        factors = [None, None, drop.factor(idx, 2, 20, s + 1, n_layers=5), None]
+        _check_f32_step(t, ref, p, s, 20, factors=factors)
 
 
 def test_swap_noise_and_slot_cosine_f32_w24_b70():
