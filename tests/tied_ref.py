@@ -5,7 +5,10 @@ for the tests: it shares no code with the library or with codae.tool.tied.
   One nn.Parameter per free tensor, so autograd adds the two uses of W_l, clip_grad_norm_ counts it once and a torch optimizer
   decays and updates it once.
 
-TiedModel(tied=False) is the same stack with one parameter per layer (what the engine computes before its fold).  bf16=True
+TiedModel(tied=False) is the same stack with one parameter per layer (what the engine computes before its fold).  It keeps each
+decoder matrix in the encoder's layout, V_l' = W_l'^T, and multiplies by V_l'.t() - the transposed view the tied model multiplies by -
+so the two models issue the same matrix products on the same strides and float64 sums run in the same order whichever BLAS path a
+host takes for a transposed operand; flat_grads transposes that gradient back into the decoder's own layout.  bf16=True
 rounds where the bf16 engine rounds (oracle/dae_oracle.py's `quant`, DESIGN.md section 3, layer 2): the corrupted input, the weight
 operands, every hidden activation and every activation gradient to bf16; accumulation, biases, the last layer's output, the
 last bias gradient (sums of the unrounded dL/dy) and the weight gradients stay wide.
@@ -92,11 +95,17 @@ class TiedModel(torch.nn.Module):
         self.L = len(schedule)
         self.tied, self.bf16 = tied, bf16
         n_own = n_free(self.L) if tied else self.L
-        self.w = torch.nn.ParameterList([torch.nn.Parameter(torch.as_tensor(params[l][0]).to(dtype).clone()) for l in range(n_own)])
+        self.w = torch.nn.ParameterList([torch.nn.Parameter(self._held(l, torch.as_tensor(params[l][0]).to(dtype))) for l in range(n_own)])
         self.b = torch.nn.ParameterList([torch.nn.Parameter(torch.as_tensor(params[l][1]).to(dtype).clone()) for l in range(self.L)])
 
+    def _held(self, l, w):
+        """a decoder matrix of the untied model is held transposed (the encoder's layout), every other matrix as it is"""
+        return w.t().contiguous() if l >= n_free(self.L) else w.clone()
+
     def weight(self, l):
-        return self.w[l] if l < len(self.w) else self.w[self.L - 1 - l].t()
+        if l < n_free(self.L):
+            return self.w[l]
+        return self.w[self.L - 1 - l].t() if self.tied else self.w[l].t()
 
     def forward(self, x):
         h = _Round.apply(x, True, False) if self.bf16 else x
@@ -126,5 +135,5 @@ class TiedModel(torch.nn.Module):
 
     def flat_grads(self):
         """Gradients in the flat layout; a tied model leaves the decoder ranges zero (the folded form)."""
-        ws = [self.w[l].grad if l < len(self.w) else None for l in range(self.L)]
+        ws = [None if l >= len(self.w) else self.w[l].grad if l < n_free(self.L) else self.w[l].grad.t() for l in range(self.L)]
         return flatten(self.schedule, ws, [b.grad for b in self.b])
