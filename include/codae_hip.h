@@ -87,6 +87,10 @@ extern "C" {
  *      entries with plain arguments only, no struct, no layout or enum change, no profiling kind
  *      (still 11) + codae_sparse_code, codae_sparse_code_ws_bytes, codae_set_sparse_code, codae_sparse_code_fwd, codae_sparse_code_bwd,
  *      codae_sparse_code_blocks: new entries only, no layout or enum change; the two kernels are booked under CODAE_K_DROPOUT as well
+ *      (still 11) + CODAE_OPT_LAMB, CODAE_OPT_LARS, codae_trust_ws_bytes, codae_trust_ws_bytes_flat, codae_trust_update; codae_optimizer grows at its END by
+ *      trust_clip, trust_coef, decay_bias, trust_ws (48 -> 72 bytes; the struct is not in codae_struct_sizes, a caller that fills the
+ *      old fields and zeroes the rest gets what it got): no existing enum value or field moves; the norms pass and the finish are
+ *      booked under CODAE_K_ADAM
  * The binding must refuse a library whose codae_abi_version() differs and must check its own struct sizes against
  * codae_struct_sizes() at load (mui-deepautoencoder_amd/codae/hip/__init__.py does both). */
 #define CODAE_ABI_VERSION 11
@@ -476,8 +480,35 @@ typedef struct {
  *   SGD    g' = g coef + wd p;  m' = mu m + g';  u = nesterov ? g' + mu m' : m';  p' = p - lr_t u;  v is neither read nor written
  *          (torch.optim.SGD with dampening 0; with a zero-initialised m its first step is torch's)
  * A NaN clip coefficient makes every parameter and every state tensor that is written NaN, as under the default.
- * Every kind writes p, the moments it keeps, the bf16 shadow and the transposed shadow in the one pass the default makes. */
-enum { CODAE_OPT_ADAM = 0, CODAE_OPT_ADAMW = 1, CODAE_OPT_SGD = 2 };
+ * Every kind writes p, the moments it keeps, the bf16 shadow and the transposed shadow in the one pass the default makes.
+ *
+ * Layer-wise trust ratios (LAMB: You et al. 2020; LARS: You et al. 2017).  A MATRIX is one weight matrix W_l of the flat parameter
+ * vector (its offset, out[l] x in[l]; with tied weights the free ones); the BIAS BLOCK is [bias_begin, n_param).  Norms are per
+ * matrix: P = sqrt(sum p^2), U = sqrt(sum u^2), G = sqrt(sum g'^2) over the matrix's elements; each square is formed in fp32 from
+ * the fp32 value, widened, and added in double, in an order the matrix shape alone fixes (per 64 x 128 tile of the tiled update, per
+ * 4096 consecutive elements of the flat one: 256 lanes in element order, an xor-butterfly per wave, the four waves in order; then the
+ * partial pairs in index order) - not the grid, not the run, not plain versus replayed.  wd' = wd in a matrix, decay_bias ? wd : 0 in
+ * the bias block; inv_bc1 = (float)(1 / bc1), inv_sqrt_bc2 = (float)(1 / sqrt(bc2)); every fp32 operation below is rounded on its
+ * own (no fused multiply-add), in the order written:
+ *   LAMB   g' = g coef;  m' = b1 m + (1-b1) g';  v' = b2 v + ((1-b2) g') g'
+ *          u  = (m' / (sqrt(v') inv_sqrt_bc2 + eps)) inv_bc1 + wd' p
+ *          matrix: phi = (P > 0 && U > 0) ? P / U : 1 in double;  if (trust_clip > 0) phi = min(phi, trust_clip);  phi32 = (float)phi
+ *          bias block: phi32 = 1 (no adaptation)
+ *          p' = p - (lr_t phi32) u
+ *   LARS   g' = g coef
+ *          matrix: lambda = (P > 0 && G > 0) ? trust_coef P / (G + wd P + eps) : 1 in double;  trust_clip as above;  lambda32 = (float)
+ *          bias block: lambda32 = 1
+ *          d = lambda32 (g' + wd' p);  m' = mu m + d;  u = nesterov ? d + mu m' : m';  p' = p - lr_t u;  v is neither read nor written
+ * A comparison with a NaN norm is false: the ratio is 1 and the NaN elements of u decide.  The norms pass reads p, g, m, v and writes
+ * no state; it forms u with the update's own prologue and per-element function.  The finish writes the fp32 ratio of matrix l to
+ * ((float*)trust_ws)[l]: the ratios of the last update can be read there.  Both run in front of the update on its stream, inside a
+ * captured graph too.  Tied weights: one ratio per free matrix, from the folded gradient.  Refused: amsgrad with either kind,
+ * trust_clip < 0 or non-finite, trust_coef <= 0 or non-finite (LARS), a missing, misaligned or short trust_ws, more than 64
+ * matrices: CODAE_E_INVALID; codae_step_update_span while either kind is set: CODAE_E_UNSUPPORTED (a matrix's norm spans shards).
+ * Not covered: decay_bias for the other kinds, per-tensor adaptation of single bias vectors, the mixed-variable path. */
+enum { CODAE_OPT_ADAM = 0, CODAE_OPT_ADAMW = 1, CODAE_OPT_SGD = 2, CODAE_OPT_LAMB = 3, CODAE_OPT_LARS = 4 };
+#define CODAE_TRUST_MAX_MATRICES 64      /* the ratios at the head of trust_ws */
+#define CODAE_TRUST_CHUNK 4096           /* elements per partial pair of the flat norms pass */
 enum { CODAE_SCHED_CONSTANT = 0, CODAE_SCHED_COSINE = 1, CODAE_SCHED_LINEAR = 2, CODAE_SCHED_STEP = 3 };
 typedef struct {
     int32_t kind;          /* CODAE_OPT_* */
@@ -491,6 +522,11 @@ typedef struct {
     float   min_factor;    /* COSINE / LINEAR: in [0, 1] */
     float   gamma;         /* STEP: in (0, 1] */
     float*  vmax;          /* device [n_param] fp32, zero before first use (padding too); required iff amsgrad; borrowed */
+    float   trust_clip;    /* LAMB / LARS: upper bound of the ratio, 0 = none */
+    float   trust_coef;    /* LARS: > 0 */
+    int32_t decay_bias;    /* LAMB / LARS: 0 or 1: weight decay in the bias block too */
+    void*   trust_ws;      /* LAMB / LARS: device work space of codae_trust_ws_bytes(h) bytes, 16-byte aligned, zero before first use;
+                            * 64 fp32 ratios, then the (sum p^2, sum u^2) double pairs of the norms pass; borrowed */
 } codae_optimizer;
 
 /* Tied weights (Vincent et al. 2010): the decoder's Linear l' = L-1-l uses the transpose of the encoder's Linear l.  With tying on
@@ -903,6 +939,8 @@ int codae_set_slot_contrast(codae_handle h, const codae_slot_contrast* contrast)
  * setting is part of the graph key (a change re-captures; a schedule alone never does) and never changes which forward or backward
  * path a stack takes: codae_step_path is unaffected.  vmax is borrowed until the setting is replaced; SGD leaves adam_v alone. */
 int codae_set_optimizer(codae_handle h, const codae_optimizer* opt);
+/* bytes of codae_optimizer.trust_ws for this handle (every update path, tied or not); 0 for a null handle */
+int64_t codae_trust_ws_bytes(codae_handle h);
 /* Slot presence of every step that follows - training (every step form codae_set_input_noise lists; the pointer is part of the
  * graph key) AND codae_eval_step.  present [n_rows][n_slots] uint8 on the device, borrowed until replaced; NULL switches it off: the
  * engine then runs exactly what it ran before, bit for bit, codae_step_path included.  CODAE_E_INVALID for n_slots outside [1, 128]
@@ -1140,6 +1178,13 @@ int codae_clip_adam(float* params, float* grads, float* adam_m, float* adam_v, i
  * read and written under amsgrad only (opt->vmax is not used here).  t = hyper->step. */
 int codae_optimizer_update(float* p, float* g, float* m, float* v, float* vmax, int64_t n, const codae_hyper* hyper,
                            const codae_optimizer* opt, double* scalars, void* stream);
+
+/* LAMB / LARS on one tensor: [0, n) is ONE matrix (opt->kind one of the two; opt->trust_ws is not used here).  trust_ws: 16-byte
+ * aligned, ws_bytes >= codae_trust_ws_bytes_flat(n) = 256 + 16 ceil(n / CODAE_TRUST_CHUNK); the ratio is left in ((float*)trust_ws)[0].
+ * v may be NULL under LARS.  For loops that keep their own backward, and for tests that plant state at odd sizes. */
+int64_t codae_trust_ws_bytes_flat(int64_t n);
+int codae_trust_update(float* p, float* g, float* m, float* v, int64_t n, const codae_hyper* hyper, const codae_optimizer* opt,
+                       double* scalars, void* trust_ws, int64_t ws_bytes, void* stream);
 
 /* The weight average on its own, for loops that keep another optimizer: avg[i] <- the definition of "Weight average" with p' = p[i],
  * i in [0, n), t = step; wa->avg is not used here.  A step that does not sample launches nothing.  float4 accesses for the body,

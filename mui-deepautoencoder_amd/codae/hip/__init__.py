@@ -25,7 +25,9 @@ NOISE_NONE, NOISE_GAUSSIAN, NOISE_MASKING, NOISE_SALT_PEPPER, NOISE_SWAP = 0, 1,
 # CODAE_LOSS_* of include/codae_hip.h: the training criterion (codae.tool.ReconstructionLoss builds the struct)
 LOSS_MSE, LOSS_L1, LOSS_SMOOTH_L1, LOSS_HUBER, LOSS_SLOT_COSINE = 0, 1, 2, 3, 4
 # CODAE_OPT_* / CODAE_SCHED_* of include/codae_hip.h: the update's optimizer and schedule (codae.tool.Optimizer builds the struct)
-OPT_ADAM, OPT_ADAMW, OPT_SGD = 0, 1, 2
+OPT_ADAM, OPT_ADAMW, OPT_SGD, OPT_LAMB, OPT_LARS = 0, 1, 2, 3, 4
+# the work space of the trust kinds: CODAE_TRUST_MAX_MATRICES fp32 ratios at its head, a partial pair per CODAE_TRUST_CHUNK elements
+TRUST_MAX_MATRICES, TRUST_CHUNK = 64, 4096
 SCHED_CONSTANT, SCHED_COSINE, SCHED_LINEAR, SCHED_STEP = 0, 1, 2, 3
 # CODAE_AVG_* of include/codae_hip.h: the average of the iterates the update keeps (codae.tool.WeightAverage builds the struct)
 AVG_OFF, AVG_EMA, AVG_SWA = 0, 1, 2
@@ -103,7 +105,10 @@ class SlotContrast(C.Structure):
 class Optimizer(C.Structure):
     _fields_ = [("kind", C.c_int32), ("amsgrad", C.c_int32), ("momentum", C.c_float), ("nesterov", C.c_int32), ("sched", C.c_int32),
                 ("warmup", C.c_int32), ("total", C.c_int32), ("period", C.c_int32), ("min_factor", C.c_float), ("gamma", C.c_float),
-                ("vmax", C.c_void_p)]
+                ("vmax", C.c_void_p),
+                # LAMB / LARS, appended: 48 -> 72 bytes (four bytes of padding in front of trust_ws); a struct built from the first
+                # eleven values alone has them zero
+                ("trust_clip", C.c_float), ("trust_coef", C.c_float), ("decay_bias", C.c_int32), ("trust_ws", C.c_void_p)]
 
 
 # codae_weight_average: five 4-byte fields, four bytes of padding, the pointer: 32 bytes (tests/test_weight_average_host.py)
@@ -179,6 +184,9 @@ PROTOTYPES = {
     "codae_set_slot_contrast": (C.c_int, [_P, C.POINTER(SlotContrast)]),
     "codae_set_optimizer": (C.c_int, [_P, C.POINTER(Optimizer)]),
     "codae_optimizer_update": (C.c_int, [_P, _P, _P, _P, _P, _I64, C.POINTER(Hyper), C.POINTER(Optimizer), _P, _P]),
+    "codae_trust_ws_bytes": (_I64, [_P]),
+    "codae_trust_ws_bytes_flat": (_I64, [_I64]),
+    "codae_trust_update": (C.c_int, [_P, _P, _P, _P, _I64, C.POINTER(Hyper), C.POINTER(Optimizer), _P, _P, _I64, _P]),
     "codae_graph_captures": (C.c_int, [_P]),
     "codae_set_weight_average": (C.c_int, [_P, C.POINTER(WeightAverage)]),
     "codae_weight_average_update": (C.c_int, [_P, _P, _I64, C.POINTER(WeightAverage), _I32, _P]),

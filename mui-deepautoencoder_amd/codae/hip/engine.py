@@ -135,6 +135,7 @@ class DaeEngine:
         self.tied_weights = False
         self._dataset_image = None    # (data, image): the device tensors codae_set_dataset_image borrows
         self.optimizer = None
+        self.trust_ws = None          # lamb / lars: ratios and partial norms (codae_optimizer.trust_ws borrows it), allocated on first use
         self.adam_vmax = None         # AMSGrad's running maximum (codae_optimizer.vmax borrows it), allocated on first use
         self.weight_average = None    # the codae.tool.WeightAverage in force (None = off)
         self.weight_avg = None        # the average itself: n_param floats in the layout of params, allocated on first use and kept
@@ -416,19 +417,37 @@ class DaeEngine:
         update kernel evaluates from the device's own step count - the lr handed to hyper() stays the base rate, and a schedule
         never re-captures a graph (a change of the setting does).  step_path() is unaffected.  AMSGrad's running maximum
         (adam_vmax, n_param floats, zero) is allocated on first use and kept.  The default (Optimizer()) = off: the engine runs
-        exactly what it ran before.  On a refusal (HipError) the previous setting stays."""
+        exactly what it ran before.  "lamb" / "lars" scale every weight matrix's step by its layer-wise trust ratio ("Layer-wise
+        trust ratios"): their work space (trust_ws: 64 ratios and the norms pass's partial sums, zero) is allocated on first use and
+        kept, trust_ratios() reads the ratios of the last update, and step_update_span is refused while either is set.  On a
+        refusal (HipError) the previous setting stays."""
         if optimizer is not None and not hasattr(optimizer, "lr_at"):
             raise HipError("set_optimizer: expected a codae.tool.Optimizer or None, got %r" % (optimizer,))
         if optimizer is None or optimizer.is_default:
             self._set_optimizer_struct(None)
             self.optimizer = optimizer
             return
-        vmax = self.adam_vmax
+        vmax, ws = self.adam_vmax, self.trust_ws
         if optimizer.amsgrad and vmax is None:
             with torch.cuda.device(self.device):
                 vmax = torch.zeros(self.n_param, dtype=torch.float32, device=self.device)
-        self._set_optimizer_struct(optimizer.as_struct(ptr(vmax)))
-        self.optimizer, self.adam_vmax = optimizer, vmax
+        if getattr(optimizer, "is_trust", False):
+            if ws is None:
+                # the trust kinds' work space: 64 fp32 ratios, then the norms pass's partial pairs (codae_trust_ws_bytes), zero
+                with torch.cuda.device(self.device):
+                    ws = torch.zeros(int(self._lib.codae_trust_ws_bytes(self._h)) // 4, dtype=torch.float32, device=self.device)
+            self._set_optimizer_struct(optimizer.as_struct(ptr(vmax), ptr(ws)))
+        else:
+            self._set_optimizer_struct(optimizer.as_struct(ptr(vmax)))
+        self.optimizer, self.adam_vmax, self.trust_ws = optimizer, vmax, ws
+
+    def trust_ratios(self):
+        """The layer-wise trust ratios of the last update under lamb / lars: an fp32 device tensor, one value per weight matrix
+        (with tied weights per free matrix), a view of the work space's head - zeros before the first update.  Nothing
+        synchronises unless the caller reads it.  HipError under another kind."""
+        if self.optimizer is None or not getattr(self.optimizer, "is_trust", False):
+            raise HipError("trust_ratios: the optimizer is neither lamb nor lars")
+        return self.trust_ws[:(self.L + 1) // 2 if self.tied_weights else self.L]
 
     def _set_optimizer_struct(self, st):
         check(self._lib.codae_set_optimizer(self._h, None if st is None else C.byref(st)))

@@ -186,6 +186,7 @@ class DataParallel:
         # bucketed, native); a shard of the sharded update would hold one half of a tied pair
         self._refuse_sharded_tie()
         self._refuse_sharded_average()
+        self._refuse_sharded_trust()
         if self.native:
             if self.sharded:
                 raise ValueError("native RCCL data parallel: the sharded update goes through torch.distributed only")
@@ -218,6 +219,12 @@ class DataParallel:
         if self.sharded and getattr(eng, "averaging", None) is not None and eng.averaging():
             raise HipError("weight average: the sharded update is not supported: the average of a shard would have to be "
                            "all-gathered too")
+
+    def _refuse_sharded_trust(self, optimizer=None):
+        """lamb / lars (the engine's setting, or the one about to be set): a matrix's norm spans shards."""
+        opt = optimizer if optimizer is not None else getattr(self.engine, "optimizer", None)
+        if self.sharded and opt is not None and getattr(opt, "is_trust", False):
+            raise HipError("%s: the sharded update is not supported: a matrix's norm spans shards" % opt.kind)
 
     # ---- exposed-wait timing (bench.py --gpus N) ------------------------------------------
     def time_waits(self, every=4):
@@ -307,6 +314,7 @@ class DataParallel:
             return
         self._refuse_sharded_tie()             # (tying switched on after this object was built)
         self._refuse_sharded_average()
+        self._refuse_sharded_trust()
         self.engine.step_forward_loss(batch, hyper)
         if self.sharded and (self.world > 1 or self.always_reduce):
             self._backward_reduce_scatter(B)
@@ -528,6 +536,7 @@ class HipEmbeddingTrainer:
             self.set_criterion(criterion)
         if contrast is not None:
             self.set_contrast(contrast)
+        self.dp = None                  # (built below, once the engine holds its settings: DataParallel refuses what a shard cannot do)
         if optimizer is not None:
             self.set_optimizer(optimizer)
         self.presence = None
@@ -623,7 +632,14 @@ class HipEmbeddingTrainer:
 
     def set_optimizer(self, optimizer):
         """DaeEngine.set_optimizer: a codae.tool.Optimizer, or None for Adam at a constant rate."""
+        if self.dp is not None:
+            self.dp._refuse_sharded_trust(optimizer)         # (before anything changes: the previous setting stays)
         self.engine.set_optimizer(optimizer)
+
+    def trust_ratios(self):
+        """DaeEngine.trust_ratios: the fp32 [n_matrices] layer-wise ratios of the last update under lamb / lars (a device tensor;
+        nothing synchronises unless the caller reads it)."""
+        return self.engine.trust_ratios()
 
     def current_lr(self):
         """The learning rate of the NEXT step as the update kernel forms it: the fp32 lr_t at step_count + 1 (the fp32 base lr
@@ -1137,6 +1153,11 @@ class HipEmbeddingTrainer:
         if "adam_vmax" in need or (eng.optimizer is not None and eng.optimizer.amsgrad and "adam_m" in need):
             if "adam_vmax" not in tensors:
                 refuse("adam_vmax", "AMSGrad is on and the file does not hold its running maximum")
+        # lamb / lars keep other moments than the kinds before them (lars: a momentum buffer of ratio-scaled steps, no v): a file and
+        # a trainer that differ in kind are refused wherever one of the two is a trust kind; the other kinds keep loading each other
+        mine, theirs = "adam" if eng.optimizer is None else eng.optimizer.kind, meta.get("optimizer", "adam")
+        if "adam_m" in need and mine != theirs and ({mine, theirs} & {"lamb", "lars"}):
+            refuse("optimizer", "the file was written under %r, this trainer runs %r" % (theirs, mine))
         if strict and eng.averaging() and "adam_m" in need and "weight_avg" not in tensors:
             refuse("weight_avg", "weight averaging is on and the file holds no average (strict=False starts it from the parameters)")
         if strict and "adam_m" in need:

@@ -643,6 +643,7 @@ struct UpdateLaunch {
     ParamVectors x; int64_t n;
     const codae_hyper* hp; const double* grad_sq; const double* coef_in; const double* step_dev;
     const codae_optimizer* opt; const codae_weight_average* wa;
+    int trust_mat;           // LAMB / LARS, the flat kernel: the matrix x[0, n) is (its ratio), -1 = the bias block (ratio 1)
 };
 // the argument checks both update launchers make, the error texts prefixed with `who`
 int check_update_launch(const char* who, const UpdateLaunch& u);
@@ -658,6 +659,13 @@ int launch_weight_average(float* avg, const float* p, int64_t n, const codae_wei
 int check_optimizer(const codae_optimizer* o);
 bool optimizer_is_default(const codae_optimizer* o);
 codae_optimizer optimizer_canonical(const codae_optimizer* o);
+inline bool is_trust_kind(const codae_optimizer* o) { return o != nullptr && (o->kind == CODAE_OPT_LAMB || o->kind == CODAE_OPT_LARS); }
+// LAMB / LARS ("Layer-wise trust ratios"): the norms pass over n_mats matrices x[off[l], off[l] + len[l]) and the finish, which leaves
+// the fp32 ratios at the head of u.opt->trust_ws - in front of the update launches, on their stream.  The partial pairs a matrix
+// leaves behind the ratios: trust_parts_flat(len) from the flat pass, trust_parts_tiled(rows, cols) from the tiled one.
+int64_t trust_parts_flat(int64_t n);
+int64_t trust_parts_tiled(int rows, int cols);
+int launch_trust_norms(const UpdateLaunch& u, int n_mats, const int64_t* off, const int64_t* len, hipStream_t s);
 int launch_set_scalar(double* dst, double value, hipStream_t s);
 // bf16 engine: Adam over the weight matrices in tiles, writing the bf16 shadow AND (layers >= transposed_from) the
 // transposed shadow in the same pass; the flat bias block [bias_off, bias_off + bias_n) rides along (u.n: the whole vector's length; u.coef_in stays null: the kernel takes none)
@@ -668,6 +676,7 @@ struct UpdateTiles {
     int64_t bias_off, bias_n;
 };
 int launch_update_tiled(const UpdateLaunch& u, const UpdateTiles& t, hipStream_t s);
+int launch_trust_norms_tiled(const UpdateLaunch& u, const UpdateTiles& t, hipStream_t s);      // the same over the update's tile table
 // dst[c][r] = src[r][c] for n bf16 matrices (element offsets off[i], shapes rows[i] x cols[i]) in one launch
 // tied weights (tied.hip; include/codae_hip.h, "Tied weights"): the fold of the decoder gradients into the encoder's, and the mirror of
 // the encoder matrices into the decoder's fp32 image and (when given) its two bf16 shadows

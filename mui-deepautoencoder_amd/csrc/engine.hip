@@ -1745,8 +1745,26 @@ int codae_set_optimizer(codae_handle h, const codae_optimizer* opt) {
     CODAE_REQUIRE(h != nullptr, "codae_set_optimizer: null handle");
     int rc = check_optimizer(opt);
     if (rc) return rc;
-    h->tc.opt = optimizer_canonical(opt);   // (built field by field from zero: the graph key compares bytes, padding included)
+    CODAE_REQUIRE(!is_trust_kind(opt) || h->L <= CODAE_TRUST_MAX_MATRICES, "optimizer: lamb / lars take at most %d matrices, the stack has %d",
+                  CODAE_TRUST_MAX_MATRICES, h->L);
+    // (the graph key compares bytes and the struct has padding in front of its second pointer: zeroed here, then field by field)
+    const codae_optimizer c = optimizer_canonical(opt);
+    codae_optimizer& d = h->tc.opt;
+    memset(&d, 0, sizeof(d));
+    d.kind = c.kind; d.amsgrad = c.amsgrad; d.momentum = c.momentum; d.nesterov = c.nesterov; d.sched = c.sched; d.warmup = c.warmup;
+    d.total = c.total; d.period = c.period; d.min_factor = c.min_factor; d.gamma = c.gamma; d.vmax = c.vmax;
+    d.trust_clip = c.trust_clip; d.trust_coef = c.trust_coef; d.decay_bias = c.decay_bias; d.trust_ws = c.trust_ws;
     return CODAE_OK;
+}
+
+int64_t codae_trust_ws_bytes(codae_handle h) {
+    if (h == nullptr) return 0;
+    int64_t flat = 0, tiled = 0;
+    for (int l = 0; l < h->L; ++l) {
+        flat += trust_parts_flat((int64_t)h->out[l] * h->in[l]);
+        tiled += trust_parts_tiled(h->out[l], h->in[l]);
+    }
+    return CODAE_TRUST_MAX_MATRICES * (int64_t)sizeof(float) + 2 * (int64_t)sizeof(double) * (flat > tiled ? flat : tiled);
 }
 
 int codae_set_weight_average(codae_handle h, const codae_weight_average* wa) {
@@ -2121,10 +2139,32 @@ static int update_impl(codae_handle h, const codae_buffers* b, const codae_hyper
     // tied: the free parameters only - the encoder matrices (and the middle one of an odd stack) and every bias; the moments of the
     // decoder matrices are neither read nor written - then the decoder's three images from the updated encoder
     const int n_mats = tied ? h->n_free() : h->L;
+    // LAMB / LARS: the norms of every free matrix and their ratios first (two launches on the tiled path, whatever the depth), then
+    // the update, which reads its matrix's ratio in its prologue
+    const bool trust = is_trust_kind(&h->tc.opt);
     if (plan.update == UPDATE_TILED) {
         // one tiled pass: p, m, v, the bf16 shadow and the transposed shadow of every layer that has a data gradient
         const UpdateTiles tiles{shadow_t, n_mats, h->w_off.data(), h->out.data(), h->in.data(), 1, h->bias_begin, h->n_param - h->bias_begin};
+        if (trust) {
+            rc = launch_trust_norms_tiled(u, tiles, s);
+            if (rc) return rc;
+        }
         rc = launch_update_tiled(u, tiles, s);
+        if (rc) return rc;
+    } else if (trust) {
+        // the flat kernel once per matrix (its own ratio; the padding behind a matrix stays as it is: zero) and once for the bias block
+        std::vector<int64_t> len(n_mats);
+        for (int l = 0; l < n_mats; ++l) len[l] = (int64_t)h->out[l] * h->in[l];
+        rc = launch_trust_norms(u, n_mats, h->w_off.data(), len.data(), s);
+        if (rc) return rc;
+        for (int l = 0; l <= n_mats; ++l) {
+            UpdateLaunch span = u;
+            const int64_t lo = l < n_mats ? h->w_off[l] : h->bias_begin;
+            span.x = u.x.at(lo); span.n = l < n_mats ? len[l] : h->n_param - h->bias_begin; span.trust_mat = l < n_mats ? l : -1;
+            rc = launch_update(span, s);
+            if (rc) return rc;
+        }
+        rc = refresh_transposed(h, b, s, 1, n_mats);
         if (rc) return rc;
     } else {
         const int64_t mats_end = tied ? h->w_off[n_mats] : h->n_param;         // (untied: one span, matrices and biases)
@@ -2163,6 +2203,10 @@ int codae_step_update_span(codae_handle h, const codae_buffers* b, const codae_h
     }
     if (h->tc.avg.kind != CODAE_AVG_OFF) {
         set_error("weight average: the sharded update is not supported: the average of a shard would have to be all-gathered too");
+        return CODAE_E_UNSUPPORTED;
+    }
+    if (is_trust_kind(&h->tc.opt)) {
+        set_error("%s: the sharded update is not supported: a matrix's norm spans shards", h->tc.opt.kind == CODAE_OPT_LAMB ? "lamb" : "lars");
         return CODAE_E_UNSUPPORTED;
     }
     hipStream_t s = (hipStream_t)stream;

@@ -255,6 +255,7 @@ int codae_clip_adam(float* params, float* grads, float* adam_m, float* adam_v, i
 int codae_optimizer_update(float* p, float* g, float* m, float* v, float* vmax, int64_t n, const codae_hyper* hyper,
                            const codae_optimizer* opt, double* scalars, void* stream) {
     CODAE_REQUIRE(hyper && scalars, "codae_optimizer_update: null argument");
+    CODAE_REQUIRE(!is_trust_kind(opt), "codae_optimizer_update: lamb / lars need a work space: codae_trust_update");
     codae_optimizer o{};
     if (opt != nullptr) { o = *opt; o.vmax = vmax; }       // (the range checks are the setter's; the maximum is this call's own)
     int rc = check_optimizer(opt != nullptr ? &o : nullptr);
@@ -267,6 +268,34 @@ int codae_optimizer_update(float* p, float* g, float* m, float* v, float* vmax, 
     }
     UpdateLaunch u{};
     u.x.p = p; u.x.g = g; u.x.m = m; u.x.v = v; u.x.vmax = o.vmax; u.n = n; u.hp = hyper; u.grad_sq = scalars + CODAE_S_GRAD_SQ; u.opt = &o;
+    return launch_update(u, s);
+}
+
+int64_t codae_trust_ws_bytes_flat(int64_t n) {
+    return n > 0 ? CODAE_TRUST_MAX_MATRICES * (int64_t)sizeof(float) + 2 * (int64_t)sizeof(double) * trust_parts_flat(n) : 0;
+}
+
+int codae_trust_update(float* p, float* g, float* m, float* v, int64_t n, const codae_hyper* hyper, const codae_optimizer* opt,
+                       double* scalars, void* trust_ws, int64_t ws_bytes, void* stream) {
+    CODAE_REQUIRE(hyper && scalars && opt, "codae_trust_update: null argument");
+    CODAE_REQUIRE(is_trust_kind(opt), "codae_trust_update: kind %d is neither lamb nor lars", opt->kind);
+    CODAE_REQUIRE(n > 0 && trust_ws != nullptr && ws_bytes >= codae_trust_ws_bytes_flat(n), "codae_trust_update: trust_ws of %lld bytes, %lld needed",
+                  (long long)ws_bytes, (long long)codae_trust_ws_bytes_flat(n));
+    codae_optimizer o = *opt;
+    o.vmax = nullptr; o.trust_ws = trust_ws;               // (the range checks are the setter's; the work space is this call's own)
+    int rc = check_optimizer(&o);
+    if (rc) return rc;
+    o = optimizer_canonical(&o);
+    hipStream_t s = (hipStream_t)stream;
+    if (hyper->max_grad_norm > 0.f) {
+        rc = launch_grad_sumsq(g, n, scalars, true, s);
+        if (rc) return rc;
+    }
+    UpdateLaunch u{};
+    u.x.p = p; u.x.g = g; u.x.m = m; u.x.v = v; u.n = n; u.hp = hyper; u.grad_sq = scalars + CODAE_S_GRAD_SQ; u.opt = &o;
+    const int64_t off = 0;
+    rc = launch_trust_norms(u, 1, &off, &n, s);
+    if (rc) return rc;
     return launch_update(u, s);
 }
 

@@ -186,7 +186,8 @@ def main():
     # over the true item of each slot and NEGATIVES rows drawn per step from the dataset, added to the criterion's loss
     from codae.tool.contrast import contrast_from_config
     contrast = contrast_from_config(config.get("HIP", {}).get("CONTRAST"))
-    # HIP: OPTIMIZER: {KIND: adam | adamw | sgd, AMSGRAD: false, MOMENTUM: 0.9, NESTEROV: true, SCHEDULE: {KIND: cosine, WARMUP: 100,
+    # HIP: OPTIMIZER: {KIND: adam | adamw | sgd | lamb | lars, AMSGRAD: false, MOMENTUM: 0.9, NESTEROV: true, TRUST_CLIP: 0,
+    # TRUST_COEF: 0.001, DECAY_BIAS: false, SCHEDULE: {KIND: cosine, WARMUP: 100,
     # TOTAL: 10000, MIN_FACTOR: 0.01}} (build-only key): the update instead of Adam with L2 decay at a constant rate; a SCHEDULE
     # without TOTAL runs over this script's own loop: epochs x runs (one mask run) x batches per epoch
     from codae.tool.optimizer import optimizer_from_config
@@ -343,6 +344,10 @@ def main():
         log.info("===================================================== EPOCH = %d" % epoch)
         if optimizer is not None:
             log.info("LEARNING RATE            = %.6g" % trainer.current_lr())
+            if getattr(optimizer, "is_trust", False) and trainer.engine.step_count > 0:
+                # lamb / lars: the layer-wise ratios of the last update (one read of a few floats per epoch)
+                lo, hi = (float(x) for x in torch.aminmax(trainer.trust_ratios()))
+                log.info("TRUST RATIO min / max    = %.6g / %.6g" % (lo, hi))
         for batch_indices in train_sampler.device_batches(device):      # one index copy per epoch, int32, on the device
             shard = shard_batch(batch_indices, rank, world)
             if shard is None:                   # fewer rows than ranks (ragged last batch): skipped by every rank
