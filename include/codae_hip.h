@@ -91,6 +91,9 @@ extern "C" {
  *      trust_clip, trust_coef, decay_bias, trust_ws (48 -> 72 bytes; the struct is not in codae_struct_sizes, a caller that fills the
  *      old fields and zeroes the rest gets what it got): no existing enum value or field moves; the norms pass and the finish are
  *      booked under CODAE_K_ADAM
+ *      (still 11) + CODAE_VAR_*, codae_variable_loss, codae_set_variable_loss, codae_variable_loss_ws_bytes, codae_variable_loss_blocks,
+ *      codae_variable_loss_fwd_bwd, codae_step_stores_output: new entries only, no layout or enum change; the three kernels are
+ *      booked under CODAE_K_LOSS
  * The binding must refuse a library whose codae_abi_version() differs and must check its own struct sizes against
  * codae_struct_sizes() at load (mui-deepautoencoder_amd/codae/hip/__init__.py does both). */
 #define CODAE_ABI_VERSION 11
@@ -290,6 +293,41 @@ typedef struct {
     float mse_weight;   /* SLOT_COSINE only: finite, >= 0; must be 0 for every other kind */
     int32_t n_slots;    /* SLOT_COSINE only: 1 <= n_slots <= 128, dividing io */
 } codae_recon_loss;
+
+/* Mixed-variable criterion: the TRAINING loss of a row made of variables (tabular data: one-hot and numeric columns), the
+ * reference's CombinedCriterion(reduction="mean").  The row is described by n_var entries (position, size, type, weight): disjoint,
+ * in ascending position, covering [0, io).  x = the clean row, y = the output, B = batch->B:
+ *   L = (1 / n_var) sum_v w_v L_v
+ *   REGRESSION      L_v = sqrt(sum_{b,k} (x - y)^2 / (B s_v)),          dL/dy = (w_v / n_var) (y - x) / (B s_v L_v)
+ *   CLASSIFICATION  L_v = -(1 / B) sum_b log_softmax(y_slice)[t_b],     dL/dy = (w_v / n_var) (softmax(y_slice) - onehot(t_b)) / B
+ *                   t_b = the FIRST maximum of the clean x slice
+ * A regression variable reconstructed exactly (L_v = 0) gets 0 * inf = NaN in every one of its columns, as torch's autograd of
+ * sqrt(mse_loss) gives; NaN and Inf in y propagate as in torch (a NaN in a one-hot slice makes the slice's dy and L NaN).
+ * CODAE_S_LAST_LOSS is L; CODAE_S_SQ_FULL / CODAE_S_SQ_PARTIAL stay the unweighted sums of (x - y)^2 over ALL columns, one-hot
+ * columns included, so they compare with those of a mean-squared-error run; evaluation never sees the criterion.
+ * Three launches behind the last forward GEMM - per-(32-row block, variable) partial sums in double, one workgroup that adds every
+ * variable's blocks in index order and forms L_v and the coefficient of its dy, then dy and the last bias gradient's partial rows -
+ * with no float or double atomics: the same inputs give the same bits.  Every coefficient is formed on the device.
+ * Limits: 1 <= n_var <= CODAE_VAR_MAX; 1 <= size (a thread walks a variable's columns of one row: any size runs, wide one-hots run
+ * slowly); weights finite and >= 0.  position / size / type / weight are HOST arrays the setter reads; ws is DEVICE memory of at
+ * least codae_variable_loss_ws_bytes(n_var, max batch) bytes, 16-byte aligned, borrowed until the setting is replaced: the table's
+ * device image, the coefficients and the partial sums. */
+enum {
+    CODAE_VAR_REGRESSION = 0,
+    CODAE_VAR_CLASSIFICATION = 1
+};
+#define CODAE_VAR_MAX 65536
+
+typedef struct {
+    int32_t n_var;
+    int32_t reserved;          /* 0 */
+    const int32_t* position;   /* [n_var] host: first column of the variable */
+    const int32_t* size;       /* [n_var] host: its columns, >= 1 */
+    const int32_t* type;       /* [n_var] host: CODAE_VAR_* */
+    const float* weight;       /* [n_var] host: w_v, finite, >= 0 */
+    void* ws;                  /* device work space */
+    int64_t ws_bytes;
+} codae_variable_loss;
 
 /* Slot contrast: a sampled softmax (InfoNCE) over the true item of a slot and K negatives sampled from the same inventory, an
  * ADDITIONAL term of the TRAINING loss on top of whichever criterion is set (MSE included).  The stack is judged on a ranking by
@@ -807,6 +845,10 @@ int codae_train_step_dp(codae_handle h, const codae_buffers* bufs, const codae_b
  * (tests and bench lines name the path they measured).  Only the fused training step takes the chain: codae_eval_step, the
  * step-by-step entries and codae_train_step_dp always run the per-layer launches.  It is field `path` of codae_debug_step_plan. */
 int codae_step_path(codae_handle h, const codae_buffers* bufs, int32_t B);
+/* 1 if codae_train_step with B rows leaves its fp32 output y [B][io] in the work space (the per-layer launches with a stand-alone
+ * loss: the fp32 engine, and the bf16 engine under any setting that takes the loss out of the last GEMM's epilogue), 0 if y is
+ * never stored (the fused-loss epilogue, the persistent chain).  Read off the same step plan the step itself follows. */
+int codae_step_stores_output(codae_handle h, const codae_buffers* bufs, int32_t B);
 /* Host-only query (no HIP call is made, no device needed; the members of bufs are only tested for null, never read through):
  * which launches a call makes on this engine with its settings as they stand and the CODAE_* variables as codae_create read them.
  * Every entry point that issues a step, or a part of one, asks the same function once and hands the answer down; this entry pins
@@ -864,6 +906,19 @@ int codae_set_loss_emphasis(codae_handle h, const codae_emphasis* emphasis);
  * While it is on, the loss runs as a stand-alone kernel behind the last forward GEMM, with or without emphasis, and the stack
  * stays off the persistent chain kernel (codae_step_path reports 0), exactly as with emphasis. */
 int codae_set_recon_loss(codae_handle h, const codae_recon_loss* loss);
+/* The mixed-variable criterion ("Mixed-variable criterion" above) as the training criterion of every step of a single process that
+ * follows: codae_train_step, codae_train_step_graph (a change re-captures), codae_step_forward_loss + _backward + _update.  NULL
+ * switches it off: the engine then runs exactly what it ran before.  The setter copies the table into ws (a blocking copy).  While
+ * it is on, the loss runs as three stand-alone launches behind the last forward GEMM and the stack stays off the persistent chain
+ * kernel (codae_step_path reports 0).  On plain steps it composes with the element noises, hidden dropout, skips, norms, the sparse
+ * code, every optimizer, tied weights and the weight average; codae_train_step_graph replays the criterion on its own only (the
+ * default Adam, none of those options) and returns CODAE_E_UNSUPPORTED, naming the option, otherwise.  CODAE_E_INVALID for n_var outside [1, CODAE_VAR_MAX], a null array, a size < 1,
+ * an unknown type, a negative or non-finite weight, variables that overlap or leave a column of [0, io) uncovered, a ws that is
+ * NULL, misaligned or smaller than codae_variable_loss_ws_bytes(n_var, max_batch).  CODAE_E_UNSUPPORTED, the message naming the
+ * option, together with what assumes equal-width slots - loss emphasis, a criterion of codae_set_recon_loss, the slot contrast, a
+ * slot-presence table, swap noise (their setters refuse likewise while this criterion is on) - and in codae_train_step_dp: a
+ * global-batch RMSE is not a sum over shards.  On any error the previous setting stays. */
+int codae_set_variable_loss(codae_handle h, const codae_variable_loss* loss);
 /* Hidden dropout of every training step that follows (the step forms codae_set_input_noise lists; a change re-captures the
  * graph; under replay the step index is read from scalars[CODAE_S_ADAM_STEP]).  NULL, or every p_l == 0, switches it off: the
  * engine then runs exactly the launches it ran before.  CODAE_E_INVALID for a p_l outside [0, 1), a non-finite p_l or
@@ -1041,6 +1096,16 @@ int codae_recon_loss_fwd_bwd(const codae_batch* batch, const codae_noise* noise,
                              const codae_recon_loss* loss, const float* y, void* dy, int32_t dy_bf16, int64_t dy_ld, float inv_n,
                              float* colsum_part, double* parts, void* stream);
 int codae_recon_loss_blocks(int32_t B);
+/* The mixed-variable criterion on its own (the launchers the engine uses; "Mixed-variable criterion" above has the definition): y
+ * [B][io] fp32 against the clean rows of `batch`; dy fp32 or (dy_bf16 != 0) bf16 - the fp32 value rounded to nearest even -, rows
+ * dy_ld elements apart (<= 0: io); one row of colsum_part [codae_variable_loss_blocks(B)][io] per 32 batch rows (partial column sums
+ * of the fp32 dy; may be NULL); scalars [CODAE_S_COUNT] doubles: LAST_LOSS = L, SQ_FULL / SQ_PARTIAL += the unweighted sums, the
+ * per-step norm accumulators zeroed.  `loss` is validated as by the setter (against batch->io and batch->B) and its table copied to
+ * ws first.  No atomics: the same inputs give the same bits.  On an error nothing is launched and nothing is written. */
+int64_t codae_variable_loss_ws_bytes(int32_t n_var, int32_t max_batch);     /* -1 out of range */
+int codae_variable_loss_blocks(int32_t B);
+int codae_variable_loss_fwd_bwd(const codae_batch* batch, const codae_variable_loss* loss, const float* y, void* dy, int32_t dy_bf16,
+                                int64_t dy_ld, float* colsum_part, double* scalars, void* stream);
 /* Slot contrast on its own (the launchers the engine uses; "Slot contrast" above has the definition).
  * codae_slot_contrast_ws_bytes: bytes of codae_slot_contrast.ws for S slots, K negatives, E columns per slot, bf16 != 0 for the bf16
  * engine (-1 out of range): the normalised candidates in the operand type, once [K][E] and once [E][K], K and E padded to

@@ -24,6 +24,8 @@ ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_RELU6, ACT_ELU, ACT_SOFTPLUS, ACT_HARDSIGMOID
 NOISE_NONE, NOISE_GAUSSIAN, NOISE_MASKING, NOISE_SALT_PEPPER, NOISE_SWAP = 0, 1, 2, 3, 4
 # CODAE_LOSS_* of include/codae_hip.h: the training criterion (codae.tool.ReconstructionLoss builds the struct)
 LOSS_MSE, LOSS_L1, LOSS_SMOOTH_L1, LOSS_HUBER, LOSS_SLOT_COSINE = 0, 1, 2, 3, 4
+# CODAE_VAR_* of include/codae_hip.h: the type of a variable of the mixed-variable criterion (codae.tool.VariableLoss builds the struct)
+VAR_REGRESSION, VAR_CLASSIFICATION, VAR_MAX = 0, 1, 65536
 # CODAE_OPT_* / CODAE_SCHED_* of include/codae_hip.h: the update's optimizer and schedule (codae.tool.Optimizer builds the struct)
 OPT_ADAM, OPT_ADAMW, OPT_SGD, OPT_LAMB, OPT_LARS = 0, 1, 2, 3, 4
 # the work space of the trust kinds: CODAE_TRUST_MAX_MATRICES fp32 ratios at its head, a partial pair per CODAE_TRUST_CHUNK elements
@@ -94,6 +96,12 @@ class Emphasis(C.Structure):
 
 class ReconLoss(C.Structure):
     _fields_ = [("kind", C.c_int32), ("param", C.c_float), ("mse_weight", C.c_float), ("n_slots", C.c_int32)]
+
+
+# codae_variable_loss: two 4-byte fields, four host arrays, the device work space and its size: 56 bytes
+class VariableLossStruct(C.Structure):
+    _fields_ = [("n_var", C.c_int32), ("reserved", C.c_int32), ("position", C.POINTER(C.c_int32)), ("size", C.POINTER(C.c_int32)),
+                ("type", C.POINTER(C.c_int32)), ("weight", C.POINTER(C.c_float)), ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
 
 
 class SlotContrast(C.Structure):
@@ -180,6 +188,10 @@ PROTOTYPES = {
                                                 _I32, _I64, _F, _P, _P, C.POINTER(Swap), _P, _I32, _P]),
     "codae_set_loss_emphasis": (C.c_int, [_P, C.POINTER(Emphasis)]),
     "codae_set_recon_loss": (C.c_int, [_P, C.POINTER(ReconLoss)]),
+    "codae_set_variable_loss": (C.c_int, [_P, C.POINTER(VariableLossStruct)]),
+    "codae_variable_loss_ws_bytes": (_I64, [_I32, _I32]),
+    "codae_variable_loss_blocks": (C.c_int, [_I32]),
+    "codae_variable_loss_fwd_bwd": (C.c_int, [C.POINTER(Batch), C.POINTER(VariableLossStruct), _P, _P, _I32, _I64, _P, _P, _P]),
     "codae_set_hidden_dropout": (C.c_int, [_P, C.POINTER(Dropout)]),
     "codae_set_slot_contrast": (C.c_int, [_P, C.POINTER(SlotContrast)]),
     "codae_set_optimizer": (C.c_int, [_P, C.POINTER(Optimizer)]),
@@ -274,6 +286,7 @@ PROTOTYPES = {
     "codae_centroid_update": (C.c_int, [_P, _I64, _I32, _I32, _P, _P, _P, _P, _I64, _I32, _P, _P, _P]),
     "codae_state_digest": (C.c_int, [_P, _P, _I64, _P, _P]),
     "codae_step_path": (C.c_int, [_P, _P, _I32]),
+    "codae_step_stores_output": (C.c_int, [_P, _P, _I32]),
     "codae_debug_step_plan": (C.c_int, [_P, C.POINTER(Buffers), _P, _P, _I32]),
     "codae_linear_f32": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _P]),
     "codae_dgrad_f32": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P]),

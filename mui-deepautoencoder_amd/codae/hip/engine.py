@@ -128,6 +128,8 @@ class DaeEngine:
         self.sparse_resolved = None   # (m, Z) it resolved to on this stack: the producing layer and the width of the code
         self._sparse_ws = None        # the device tensor codae_set_sparse_code borrows (the 1-bit keep mask)
         self.recon_loss = None
+        self.variable_loss = None     # the codae.tool.VariableLoss in force (None = off)
+        self._variable_ws = None      # the device tensor codae_set_variable_loss borrows (table, coefficients, partial sums)
         self.slot_contrast = None
         self._contrast_pins = None    # the device tensors codae_slot_contrast borrows (pool, item ids, work space)
         self.slot_presence = None
@@ -327,6 +329,36 @@ class DaeEngine:
 
     def _set_recon_struct(self, st):
         check(self._lib.codae_set_recon_loss(self._h, None if st is None else C.byref(st)))
+
+    def set_variable_loss(self, criterion):
+        """criterion: a codae.tool.VariableLoss, or None to switch it off.  Every training step form of a single process that
+        follows minimises the mixed-variable criterion (include/codae_hip.h, "Mixed-variable criterion"): RMSE per regression
+        variable, NLL per classification variable, weighted and averaged over the variables; epoch_sums() stays the unweighted
+        squared-error sums over all columns and eval steps never see it; with graph=True the next step re-captures.  While it is
+        on, step_path() is 'layers' and every step stores its reconstruction (output_view).  graph=True replays the criterion on
+        its own only: together with input noise, hidden dropout, an optimizer setting, skips, a norm, the sparse code, tied weights
+        or the weight average train_step(graph=True) is refused (HipError naming the option).  Refused (HipError naming the
+        option) together with loss emphasis, a ReconstructionLoss kind, the slot contrast, a presence table, swap noise and
+        data parallel; on a refusal the previous setting stays."""
+        if criterion is None:
+            check(self._lib.codae_set_variable_loss(self._h, None))
+            self.variable_loss, self._variable_ws = None, None
+            return
+        if not hasattr(criterion, "predict") or not hasattr(criterion, "as_struct"):
+            raise HipError("set_variable_loss: expected a codae.tool.VariableLoss or None, got %r" % (criterion,))
+        io = self.schedule[-1][1]
+        if criterion.io != io:
+            raise HipError("variable loss: the variables cover %d columns, the model has %d" % (criterion.io, io))
+        need = int(self._lib.codae_variable_loss_ws_bytes(criterion.n_var, self.max_batch))
+        if need < 0:
+            raise HipError("set_variable_loss: no work space for %d variables" % criterion.n_var)
+        with torch.cuda.device(self.device):
+            # (not zero-filled: the setter's blocking copy of the table must not be overtaken by a fill still queued on torch's current
+            #  stream, and the kernels write every coefficient and partial sum before they read it)
+            ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            st = criterion.as_struct(ws)
+            check(self._lib.codae_set_variable_loss(self._h, C.byref(st)))
+        self.variable_loss, self._variable_ws = criterion, ws
 
     def set_slot_contrast(self, contrast, data=None, n_slots=None):
         """contrast: a codae.tool.SlotContrast, or None to switch it off.  Every training step form that follows adds
@@ -756,6 +788,11 @@ class DaeEngine:
     def new_accumulator(self):
         return torch.zeros(1, dtype=torch.float64, device=self.device)
 
+    def step_stores_output(self, B):
+        """True if a fused training step of B rows leaves its fp32 output in the work space (output_view): the engine's own step
+        plan, not a guess from the settings."""
+        return self._lib.codae_step_stores_output(self._h, C.byref(self.bufs), int(B)) == 1
+
     def step_path(self, B):
         """'chain' if a fused step of B rows runs the persistent chain kernel, 'layers' for per-layer launches."""
         return "chain" if self._lib.codae_step_path(self._h, C.byref(self.bufs), int(B)) == 1 else "layers"
@@ -872,7 +909,8 @@ class DaeEngine:
         es = 2 if self.precision == PREC_BF16 else 4
         off = 0
         for (k, _, _) in self.schedule:
-            off += (rows * k * es + 255) // 256 * 256
+            ld = (k + 63) // 64 * 64 if self.precision == PREC_BF16 else k      # (bf16 rows are padded to whole 64-deep K tiles)
+            off += (rows * ld * es + 255) // 256 * 256
         return self.acts[off:off + B * n * 4].view(torch.float32).view(B, n)
 
     def read_scalars(self):

@@ -2,7 +2,7 @@
 `from codae.tool import Corrupter, CombinedCriterion, ...` resolves here), gathered from this build's modules.
 The reference's legacy argparse table (codae/tool/parser.py) and attr-dict (dictionnary.py) are out of scope
 (SURVEY.md section 2): nothing on the path uses them, so they have no counterpart here."""
-from . import average, batching, clusters, codes, compat, contrast, corruption, criteria, dropout, emphasis, noise, norm, optimizer, presence, recon_loss, residual, runlog, sparse, tied
+from . import average, batching, clusters, codes, compat, contrast, corruption, criteria, dropout, emphasis, noise, norm, optimizer, presence, recon_loss, residual, runlog, sparse, tied, variable_loss
 
 _PUBLIC = {
     runlog: ("set_logging", "display_info", "get_date", "PlotDrawer", "export_parameters_to_json"),
@@ -12,6 +12,8 @@ _PUBLIC = {
     noise: ("InputNoise",),        # not in the reference: the DAE noise models its whole-slot blank leaves out
     emphasis: ("LossEmphasis",),   # not in the reference either: the loss half of the same paper (its section 4.3)
     recon_loss: ("ReconstructionLoss",),   # the training criterion of the fused step: MSE, L1, SmoothL1, Huber, per-slot cosine
+    # the mixed-variable (tabular) criterion of the fused step: RMSE per numeric variable, NLL per one-hot variable
+    variable_loss: ("VariableLoss",),
     contrast: ("SlotContrast",),   # a sampled softmax against the slot's other items, on top of the criterion: trains the ranking
     presence: ("SlotPresence",),   # rows that lack an item in some slots: absent slots stay out of input, loss and inventory
     dropout: ("HiddenDropout",),   # torch users expect Dropout between the Linears: the fused step's form of it

@@ -437,6 +437,11 @@ class _ResidentInventory:
         self.data_per_category = {c: data[:, c * E:(c + 1) * E] for c in range(S)}
 
 
+def _is_variable_loss(criterion):
+    from .tool.variable_loss import VariableLoss
+    return isinstance(criterion, VariableLoss)
+
+
 class HipEmbeddingTrainer:
     """Owns a DaeEngine, the resident dataset and the mask tables; runs train / eval steps."""
 
@@ -464,7 +469,13 @@ class HipEmbeddingTrainer:
         criterion: a codae.tool.ReconstructionLoss: the training loss is L1, SmoothL1, Huber or the per-slot cosine (optionally
         with an MSE anchor) instead of the mean squared error, in every step form, weighted by loss_emphasis when that is on;
         epoch_sums() stays the unweighted squared-error sums, eval_batch and complete never see it.  None (or the default
-        ReconstructionLoss()) = the mean squared error, exactly as before.
+        ReconstructionLoss()) = the mean squared error, exactly as before.  Or a codae.tool.VariableLoss: the mixed-variable
+        criterion for rows made of variables (RMSE per numeric variable, NLL per one-hot variable; any io in fp32), in every
+        step form of a single process - it composes with the element noises, dropout, skips, norms, the sparse code, every
+        optimizer, tied weights, the weight average and checkpoints on plain steps (use_graph=True replays the criterion on its own
+        only: with any of those options train_batch raises a HipError naming the option), and is refused (HipError naming the option) with loss
+        emphasis, the slot contrast, a presence table, swap noise and distributed=True; last_output() then gives the step's
+        reconstruction, and the embedding-slot features (complete*, score_outfits, the metrics, encode_items, code_index) raise.
         contrast: a codae.tool.SlotContrast: a sampled softmax over the true item of each slot and negatives drawn per step from
         the resident dataset, added to the criterion's loss in every step form (candidates keyed by the optimizer step and the
         slot, shared by all ranks); epoch_sums(), eval_batch and complete never see it.  None (or weight 0) = off, exactly as
@@ -533,6 +544,8 @@ class HipEmbeddingTrainer:
         if sparse_code is not None:
             self.set_sparse_code(sparse_code)
         if criterion is not None:
+            if distributed and _is_variable_loss(criterion):
+                raise HipError("variable loss: data parallel (distributed=True) is not supported: a global-batch RMSE is not a sum over shards")
             self.set_criterion(criterion)
         if contrast is not None:
             self.set_contrast(contrast)
@@ -583,7 +596,17 @@ class HipEmbeddingTrainer:
         self.engine.set_loss_emphasis(emphasis, n_slots=S)
 
     def set_criterion(self, criterion):
-        """DaeEngine.set_recon_loss with the trainer's number of slots (n_slots, else read off the mask table) for slot_cosine."""
+        """DaeEngine.set_recon_loss with the trainer's number of slots (n_slots, else read off the mask table) for slot_cosine; a
+        codae.tool.VariableLoss goes to DaeEngine.set_variable_loss (and replaces a ReconstructionLoss kind only when that is the
+        default: both at once are refused).  None switches both off."""
+        if _is_variable_loss(criterion):
+            if self.__dict__.get("dp") is not None:
+                raise HipError("variable loss: data parallel is not supported: a global-batch RMSE is not a sum over shards")
+            self.engine.set_variable_loss(criterion)
+            self.__dict__.pop("_retrievers", None)
+            return
+        if getattr(self.engine, "variable_loss", None) is not None and (criterion is None or getattr(criterion, "is_default", False)):
+            self.engine.set_variable_loss(None)
         S = None
         if criterion is not None and getattr(criterion, "kind", None) == "slot_cosine":
             if not self.n_slots and self.mask_table is None:
@@ -731,6 +754,7 @@ class HipEmbeddingTrainer:
                 eng.train_step(batch, hyper, graph=True)
             caller.wait_stream(self._graph_stream)
             self._keep = batch
+            self._note_train_step(B)
             return B
         if mask_id is None:
             batch = self._batch(row_idx, run)
@@ -744,7 +768,33 @@ class HipEmbeddingTrainer:
         else:
             self.dp.train_step(batch, hyper, B)
         self._keep = batch  # keep the ctypes struct (and its tensors) alive until the next call
+        self._note_train_step(B)
         return B
+
+    def last_output(self):
+        """The [B, io] fp32 reconstruction of the last train_batch, a view of the engine's work space: valid until the next call
+        that runs a forward.  HipError when that step did not store y (a bf16 step whose loss rode in the last GEMM's epilogue
+        or in the chain kernel), or before the first step."""
+        B = self.__dict__.get("_last_train_B")
+        if not B:
+            raise HipError("last_output(): no train_batch has run")
+        if not self._last_train_stored_y:
+            raise HipError("last_output(): the last training step did not store its reconstruction (the bf16 step with the plain "
+                           "mean squared error folds the loss into the last GEMM); set a criterion, or use eval_batch(want_y=True)")
+        return self.engine.output_view(B)
+
+    def _note_train_step(self, B):
+        """What last_output() needs of the step just issued: its rows, and whether it stored y - the engine's answer, read off the
+        step plan the step followed (the data-parallel forms never take the fused-loss epilogue's carried finish, but store y
+        under the same rule)."""
+        self._last_train_B = int(B)
+        ask = getattr(self.engine, "step_stores_output", None)         # (an engine stand-in without the query: nothing to read back)
+        self._last_train_stored_y = bool(ask(B)) if ask is not None else False
+
+    def _refuse_slot_feature(self, who):
+        if getattr(self.engine, "variable_loss", None) is not None:
+            raise HipError("%s is an embedding-slot feature: it is not supported while a VariableLoss is set (rows made of "
+                           "variables have no equal-width slots)" % who)
 
     def eval_batch(self, row_idx, run=0, want_y=False, weights="live"):
         """weights: "live" = the parameters the last step left, "average" = the weight average (HipError when none is kept)."""
@@ -777,6 +827,7 @@ class HipEmbeddingTrainer:
         With a presence table only rows that HAVE the slot are candidates (intersected with `candidates`); a query row that
         lacks the slot is the normal case; a slot no candidate row has gives (-1, -inf) everywhere.
         weights: "live", or "average" to reconstruct with the weight average."""
+        self._refuse_slot_feature("complete()")
         from .tool.criteria import ComplementRetriever
         S, E = self._slots()
         if isinstance(slot, bool) or not isinstance(slot, int) or not 0 <= slot < S:
@@ -822,6 +873,7 @@ class HipEmbeddingTrainer:
         """A tool.RetrievalMetrics over the resident data, bound to this trainer's presence table, mask table and mask_to_use:
         its add(y, row_idx, run=0) takes the output of eval_batch(row_idx, run, want_y=True) and needs nothing else.  hit@k, MRR
         and the position histogram of every blanked slot a validation row has, incomplete rows included."""
+        self._refuse_slot_feature("retrieval_metrics()")
         from .tool.criteria import RetrievalMetrics
         if self.mask_table is None or self.mask_to_use is None:
             raise HipError("retrieval_metrics(): the trainer has no mask tables")
@@ -850,6 +902,7 @@ class HipEmbeddingTrainer:
         cosine (NaN with fewer than two items), "cos": [Q, S], "sq": [Q, S] the squared error, "n_present": [Q] int32}, device
         tensors.  Runs in chunks of max_batch // S outfits without a host synchronisation; epoch_sums(), the parameters and the
         optimizer state stay exactly as they were."""
+        self._refuse_slot_feature("score_outfits()")
         S, _ = self._slots()
         it = self._outfit_items(items, "score_outfits()")
         per = self.engine.max_batch // S
@@ -866,6 +919,7 @@ class HipEmbeddingTrainer:
         complete()'s contract: (idx LongTensor [Q, k], score FloatTensor [Q, k]), ordering, (-1, -inf) padding, presence-restricted
         candidates.  exclude_items: never return the item the query itself names in items[:, slot] (with `distinct`, the item that
         row belongs to)."""
+        self._refuse_slot_feature("complete_items()")
         from .tool.compat import Compatibility
         from .tool.criteria import ComplementRetriever
         S, E = self._slots()
@@ -900,6 +954,7 @@ class HipEmbeddingTrainer:
         """A tool.CompatibilityMetrics over the resident data, bound to this trainer and its presence table: add_batch(row_idx,
         weights=...) scores the outfits of those validation rows and their swapped negatives; total() gives the AUC and the paired
         accuracy."""
+        self._refuse_slot_feature("compatibility_metrics()")
         from .tool.compat import CompatibilityMetrics
         S, E = self._slots()
         cm = CompatibilityMetrics(_ResidentInventory(self.data, S, E), validation_indices, self.device, negatives=negatives, seed=seed,
@@ -954,6 +1009,7 @@ class HipEmbeddingTrainer:
         bf16 values widened to fp32.  blank: None (the whole outfit), an int slot, or an integer [Q] tensor with -1 for none - a
         partial outfit ("this top and these shoes, any bottom").  Chunks of max_batch, no host synchronisation; epoch_sums(), the
         parameters and the optimizer state stay exactly as they were."""
+        self._refuse_slot_feature("encode_items()")
         k = self._code_layer("encode()", layer)
         it = self._outfit_items(items, "encode()")
         Q = int(it.shape[0])
@@ -988,6 +1044,7 @@ class HipEmbeddingTrainer:
         """A tool.OutfitCodes over the codes of dataset rows `rows` (None = every resident row): the bank [M, Z], encoded chunk by
         chunk into one preallocated tensor, its norms from the export kernel's same pass, and the rows the entries stand for.
         similar(query, k, exclude) then ranks it against query codes from encode / encode_items."""
+        self._refuse_slot_feature("code_index()")
         from .hip import PREC_BF16
         from .tool.codes import OutfitCodes
         k = self._code_layer("code_index()", layer)
@@ -1053,6 +1110,9 @@ class HipEmbeddingTrainer:
                         for n in ("input_noise", "loss_emphasis", "hidden_dropout", "recon_loss", "slot_contrast", "optimizer",
                                   "slot_presence")},
         }
+        variable_loss = getattr(eng, "variable_loss", None)
+        if variable_loss is not None:          # (informational, and only when it is on: the files of other runs keep their bytes)
+            meta["options"]["variable_loss"] = variable_loss.describe()
         if norm is not None:          # (written only when a norm is on: the files of runs without one keep their bytes)
             meta["norm"] = norm       # {kind, eps, layers}: part of the model, load() checks it
         from .tool.sparse import meta_record as sparse_record

@@ -544,6 +544,17 @@ int launch_finish_emph_loss(double* scalars, double inv_n, hipStream_t s, const 
 // against n_slots).
 int check_recon_loss(const codae_recon_loss* loss, int io);
 int launch_recon_loss(const LossLaunch& ll, const codae_recon_loss* loss, hipStream_t s);
+// The mixed-variable criterion (codae_variable_loss, include/codae_hip.h; variable_loss.hip): three launches on the seam of the
+// other stand-alone losses.  ws: the setting's work space (the table's device image at its head, written by variable_loss_upload);
+// partials leaves the per-block sums there, finish forms the coefficients and writes the scalars (LAST_LOSS, the epoch sums, the
+// norm accumulators zeroed), grad writes ll.dy and one ll.colsum_part row per mse_loss_colsum_rows block.  check_variable_loss:
+// CODAE_E_INVALID as codae_set_variable_loss documents (io <= 0: not checked against io; max_B < 1: ws_bytes not checked).
+int check_variable_loss(const codae_variable_loss* v, int io, int max_B);
+int64_t variable_loss_ws_bytes(int n_var, int B);
+int variable_loss_upload(const codae_variable_loss* v);
+int launch_variable_partials(const LossLaunch& ll, const void* ws, int n_var, hipStream_t s);
+int launch_variable_finish(const LossLaunch& ll, const void* ws, int n_var, double* scalars, hipStream_t s);
+int launch_variable_grad(const LossLaunch& ll, const void* ws, int n_var, hipStream_t s);
 // Sampled-softmax slot contrast (codae_slot_contrast, include/codae_hip.h; slot_contrast.hip): an additional term on top of the
 // criterion.  prepare fills the work space with the step's S x K normalised candidates; launch_slot_contrast adds the term's
 // gradient to the dy the criterion's kernel left (operand type of the products = dy's type), leaves slot_contrast_blocks(B) rows of

@@ -105,6 +105,7 @@ struct codae_engine {
     struct ResCfg { uint8_t on[64]; void* ws; int64_t ws_bytes; int32_t any; int32_t reserved; };
     struct NormCfg { uint8_t on[64]; void* ws; int64_t ws_bytes; int32_t any; int32_t kind; float eps; int32_t reserved; };
     struct SparseCfg { void* ws; int64_t ws_bytes; int32_t on; int32_t m; int32_t keep; int32_t reserved; };
+    struct VarCfg { void* ws; int64_t ws_bytes; int32_t n_var; int32_t on; };
     struct TrainCfg {
         codae_noise noise;               // input noise (codae_set_input_noise); kind NONE = off
         codae_swap swap;                 // slots and pool of CODAE_NOISE_SWAP (codae_set_swap_pool); n_slots 0 = not set
@@ -121,14 +122,16 @@ struct codae_engine {
         ResCfg res;                      // residual connections (codae_set_residual): on[l] = a skip around layer l, all zero = off
         NormCfg norm;                    // normalisation (codae_set_norm): on[l] = layer l's output is normalised, all zero = off
         SparseCfg sparse;                // sparse code (codae_set_sparse_code): the `keep` first-ranked units of layer m's output, all zero = off
+        VarCfg var;                      // mixed-variable criterion (codae_set_variable_loss): the table lives at the head of ws, all zero = off
     } tc;
     bool recon_on() const { return tc.recon.kind != CODAE_LOSS_MSE; }
     bool contrast_on() const { return tc.contrast.weight != 0.f; }
+    bool variable_on() const { return tc.var.on != 0; }
     // tied weights: the layers [0, n_free()) own their matrices, layer L-1-l mirrors layer l < L / 2 (tie_pairs: those pairs)
     int n_free() const { return (L + 1) / 2; }
     std::vector<codae_tie_pair> tie_pairs;
     // the loss is the plain MSE of every slot: what the chain kernel and the last forward GEMM's epilogue compute
-    bool plain_mse() const { return !tc.emph_on && !recon_on() && !contrast_on() && tc.pres.table == nullptr; }
+    bool plain_mse() const { return !tc.emph_on && !recon_on() && !contrast_on() && tc.pres.table == nullptr && !variable_on(); }
     int graph_captures = 0;          // captures of codae_train_step_graph since codae_create
     // hidden dropout: the backward entry points take no batch, so a training forward leaves what they need behind: drop_live = the
     // activations in the workspace were dropped (an evaluation or drop-in forward clears it), with the batch rows, row indices and
@@ -1461,6 +1464,13 @@ int codae_backward(codae_handle h, const codae_buffers* b, const float* dy, floa
     return backward_range(h, b, call, step_plan(h, b, call), dx, s);
 }
 
+// What assumes equal-width slots (E = io / S) is refused while the mixed-variable criterion is on, naming the option
+static int refuse_with_variable_loss(codae_handle h, const char* option) {
+    if (!h->variable_on()) return CODAE_OK;
+    set_error("%s is not supported with the mixed-variable criterion (codae_set_variable_loss): it assumes equal-width slots", option);
+    return CODAE_E_UNSUPPORTED;
+}
+
 // The slot contrast behind the criterion's kernel and its finish (a no-op while it is off): prepare this step's candidates, add the
 // term's gradient to the dY the criterion left - its partial column-sum rows replace the criterion kernel's -, then add the term
 // to CODAE_S_LAST_LOSS.  The per-block sums reuse the criterion's rows, which its finish has read by then (same stream).
@@ -1504,6 +1514,30 @@ static int run_standalone_loss(codae_handle h, const codae_buffers* b, const cod
                   &h->tc.swap};
     const bool weighted = h->recon_on() || h->tc.emph_on || ll.present != nullptr;      // (the kernels that leave three sums per block)
     int rc;
+    if (h->variable_on()) {
+        // the mixed-variable criterion: per-block sums, the finish that forms every variable's coefficient, then dY (its setter
+        // refuses emphasis, another criterion, the slot contrast and a presence table: nothing else rides on this step's loss)
+        const codae_engine::VarCfg& vc = h->tc.var;
+        CODAE_REQUIRE(vc.ws_bytes >= variable_loss_ws_bytes(vc.n_var, batch->B), "variable loss: the work space does not hold %d rows", batch->B);
+        {
+            ProfScope prof(h, CODAE_K_LOSS, s);
+            rc = launch_variable_partials(ll, vc.ws, vc.n_var, s);
+        }
+        if (rc) return rc;
+        {
+            ProfScope prof(h, CODAE_K_LOSS, s);
+            rc = launch_variable_finish(ll, vc.ws, vc.n_var, b->scalars, s);
+        }
+        if (rc) return rc;
+        h->norm_scalars_zero = true;
+        {
+            ProfScope prof(h, CODAE_K_LOSS, s);
+            rc = launch_variable_grad(ll, vc.ws, vc.n_var, s);
+        }
+        if (rc) return rc;
+        h->parts_pending[L - 1] = blocks;
+        return CODAE_OK;
+    }
     {
         ProfScope prof(h, CODAE_K_LOSS, s);
         if (h->recon_on()) {
@@ -1631,6 +1665,8 @@ int codae_set_input_noise(codae_handle h, const codae_noise* noise) {
     int rc = check_noise(noise);
     if (rc) return rc;
     if (noise != nullptr && noise->kind == CODAE_NOISE_SWAP) {
+        rc = refuse_with_variable_loss(h, "swap noise");
+        if (rc) return rc;
         rc = check_swap(&h->tc.swap, h->in[0], h->tc.pres.table, h->tc.pres.n_slots, "codae_set_input_noise");
         if (rc) return rc;
     }
@@ -1663,6 +1699,10 @@ int codae_set_loss_emphasis(codae_handle h, const codae_emphasis* emphasis) {
     if (rc) return rc;
     codae_emphasis e{};                  // (built field by field: the graph key compares bytes, padding included)
     const bool on = emphasis != nullptr && !(emphasis->alpha == 1.f && emphasis->beta == 1.f && emphasis->col_weight == nullptr);
+    if (on) {
+        rc = refuse_with_variable_loss(h, "loss emphasis");
+        if (rc) return rc;
+    }
     if (on) { e.alpha = emphasis->alpha; e.beta = emphasis->beta; e.col_weight = emphasis->col_weight; }
     h->tc.emph = e;
     h->tc.emph_on = on;
@@ -1678,11 +1718,38 @@ int codae_set_recon_loss(codae_handle h, const codae_recon_loss* loss) {
     codae_recon_loss r{};                // (built field by field: the graph key compares bytes)
     const bool on = loss != nullptr && loss->kind != CODAE_LOSS_MSE;
     if (on) {
+        rc = refuse_with_variable_loss(h, "a reconstruction loss (codae_set_recon_loss)");
+        if (rc) return rc;
         r.kind = loss->kind;
         if (loss->kind == CODAE_LOSS_SMOOTH_L1 || loss->kind == CODAE_LOSS_HUBER) r.param = loss->param;
         if (loss->kind == CODAE_LOSS_SLOT_COSINE) { r.mse_weight = loss->mse_weight; r.n_slots = loss->n_slots; }
     }
     h->tc.recon = r;
+    return CODAE_OK;
+}
+
+int codae_set_variable_loss(codae_handle h, const codae_variable_loss* loss) {
+    CODAE_REQUIRE(h != nullptr, "codae_set_variable_loss: null handle");
+    codae_engine::VarCfg v{};            // (built field by field: the graph key compares bytes)
+    if (loss != nullptr) {
+        int rc = check_variable_loss(loss, h->out[h->L - 1], h->max_batch);
+        if (rc) return rc;
+        const char* clash = h->tc.emph_on ? "loss emphasis" : h->recon_on() ? "a reconstruction loss (codae_set_recon_loss)" :
+                            h->contrast_on() ? "slot contrast" : h->tc.pres.table != nullptr ? "a slot-presence table" :
+                            h->tc.noise.kind == CODAE_NOISE_SWAP ? "swap noise" : nullptr;
+        if (clash != nullptr) {
+            set_error("%s is not supported with the mixed-variable criterion (codae_set_variable_loss): it assumes equal-width slots", clash);
+            return CODAE_E_UNSUPPORTED;
+        }
+        if (h->dp != nullptr) {
+            set_error("data parallel is not supported with the mixed-variable criterion: a global-batch RMSE is not a sum over shards");
+            return CODAE_E_UNSUPPORTED;
+        }
+        rc = variable_loss_upload(loss);
+        if (rc) return rc;
+        v.ws = loss->ws; v.ws_bytes = loss->ws_bytes; v.n_var = loss->n_var; v.on = 1;
+    }
+    h->tc.var = v;
     return CODAE_OK;
 }
 
@@ -1697,6 +1764,8 @@ int codae_set_slot_contrast(codae_handle h, const codae_slot_contrast* contrast)
     codae_slot_contrast c{};             // (built field by field: the graph key compares bytes)
     const bool on = contrast != nullptr && contrast->weight != 0.f;
     if (on) {
+        rc = refuse_with_variable_loss(h, "slot contrast");
+        if (rc) return rc;
         rc = slot_contrast_warm();
         if (rc) return rc;
         c.n_slots = contrast->n_slots; c.n_neg = contrast->n_neg; c.tau = contrast->tau; c.weight = contrast->weight;
@@ -1711,7 +1780,9 @@ int codae_set_slot_presence(codae_handle h, const uint8_t* present, int64_t n_ro
     CODAE_REQUIRE(h != nullptr, "codae_set_slot_presence: null handle");
     codae_engine::PresCfg p{};           // (built field by field: the graph key compares bytes, padding included)
     if (present != nullptr) {
-        int rc = check_presence(present, n_slots, h->out[h->L - 1], "codae_set_slot_presence");
+        int rc = refuse_with_variable_loss(h, "a slot-presence table");
+        if (rc) return rc;
+        rc = check_presence(present, n_slots, h->out[h->L - 1], "codae_set_slot_presence");
         if (rc) return rc;
         CODAE_REQUIRE(n_rows >= 1, "codae_set_slot_presence: n_rows %lld must be >= 1", (long long)n_rows);
         CODAE_REQUIRE(!(h->recon_on() && h->tc.recon.kind == CODAE_LOSS_SLOT_COSINE) || h->tc.recon.n_slots == n_slots,
@@ -2243,6 +2314,12 @@ int codae_step_path(codae_handle h, const codae_buffers* b, int32_t B) {
     return step_plan(h, b, StepCall{STEP_TRAIN, B, 0, h->L, true, false, false, false}).path;
 }
 
+int codae_step_stores_output(codae_handle h, const codae_buffers* b, int32_t B) {
+    if (h == nullptr || b == nullptr || B <= 0 || B > h->max_batch) return 0;
+    const StepPlan p = step_plan(h, b, StepCall{STEP_TRAIN, B, 0, h->L, true, false, false, false});
+    return p.path == PATH_LAYERS && p.loss == LOSS_STANDALONE ? 1 : 0;
+}
+
 int codae_train_step(codae_handle h, const codae_buffers* b, const codae_batch* batch, const codae_hyper* hyper, void* stream) {
     CODAE_REQUIRE(hyper != nullptr, "codae_train_step: null hyper");
     CODAE_REQUIRE(batch != nullptr, "codae_train_step: null batch");
@@ -2284,6 +2361,19 @@ int codae_train_step_graph(codae_handle h, const codae_buffers* b, const codae_b
     CODAE_REQUIRE(!h->prof_on, "codae_train_step_graph: launch profiling (codae_profile_begin) cannot run inside a graph");
     CODAE_REQUIRE(b->scalars != nullptr, "codae_train_step_graph: scalars missing");
     CODAE_REQUIRE(stream != nullptr, "codae_train_step_graph: the default (null) stream cannot be captured - pass a created stream");
+    if (h->variable_on()) {
+        // the mixed-variable criterion is replayed on its own only: with the default Adam and none of the step's options
+        const codae_optimizer none{};
+        const char* with = h->tc.noise.kind != CODAE_NOISE_NONE ? "input noise" : h->tc.drop.on ? "hidden dropout" :
+                           !same_bytes(&h->tc.opt, &none, sizeof(none)) ? "an optimizer setting (codae_set_optimizer)" :
+                           h->tc.res.any ? "residual connections" : h->tc.norm.any ? "normalisation" : h->tc.sparse.on ? "the sparse code" :
+                           h->tc.tied ? "tied weights" : h->tc.avg.kind != CODAE_AVG_OFF ? "the weight average" : nullptr;
+        if (with != nullptr) {
+            set_error("codae_train_step_graph: graph replay of the mixed-variable criterion together with %s is not supported: "
+                      "run plain steps (codae_train_step)", with);
+            return CODAE_E_UNSUPPORTED;
+        }
+    }
     hipStream_t s = (hipStream_t)stream;
     // what the captured kernel arguments depend on (the step count is the one thing that may change)
     codae_hyper hk = *hyper;
@@ -2343,6 +2433,10 @@ int codae_dp_unique_id(void* out, int32_t capacity) {
 int codae_dp_init(codae_handle h, const void* unique_id, int32_t rank, int32_t world) {
     CODAE_REQUIRE(h != nullptr && unique_id != nullptr && world >= 1 && rank >= 0 && rank < world, "codae_dp_init: bad arguments");
     CODAE_REQUIRE(h->dp == nullptr, "codae_dp_init: this engine already has a communicator");
+    if (h->variable_on()) {
+        set_error("data parallel is not supported with the mixed-variable criterion: a global-batch RMSE is not a sum over shards");
+        return CODAE_E_UNSUPPORTED;
+    }
     int rc = rccl_load();
     if (rc) return rc;
     DpState* d = new DpState();
@@ -2393,6 +2487,10 @@ int codae_train_step_dp(codae_handle h, const codae_buffers* b, const codae_batc
     for (int i = 0; i < n_buckets; ++i) {
         CODAE_REQUIRE(bucket_lo[i] >= 0 && bucket_lo[i] < bucket_hi[i] && (i == 0 || bucket_hi[i] == bucket_lo[i - 1]),
                       "codae_train_step_dp: bucket %d = [%d, %d) does not continue the one above it", i, bucket_lo[i], bucket_hi[i]);
+    }
+    if (h->variable_on()) {
+        set_error("data parallel is not supported with the mixed-variable criterion: a global-batch RMSE is not a sum over shards");
+        return CODAE_E_UNSUPPORTED;
     }
     DpState* d = h->dp;
     hipStream_t s = (hipStream_t)stream;
